@@ -450,6 +450,7 @@ def valu_issue_step(pairs_per_step, ms_per_step):
     return None
 
 
+OUTPUT_BUDGET = 64 << 20   # bytes: --dump-outputs writes at most this much
 LINE_BUDGET = 4000   # bytes: the driver keeps an 8 KB tail of stdout and parses the LAST line (20.7 KB did not parse)
 
 
@@ -568,6 +569,23 @@ def emit(out, detail_out):
     print(compose_headline(out, written), flush=True)
 
 
+def write_outputs(out_dir, arrays, budget_bytes=OUTPUT_BUDGET, seed=0):
+    """--dump-outputs: each array of `arrays` (name -> numpy) as out_dir/<name>.npy in float64 (float32 stays float32),
+    so that two builds can be compared output for output.  Over `budget_bytes` in all, every array keeps the same fixed,
+    seeded, sorted sample of its leading-axis rows.  -> {name: rows kept}"""
+    arrays = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    kept = {}
+    for name, a in arrays.items():
+        if total > budget_bytes and a.ndim and a.shape[0] > 1:
+            n = max(1, int(a.shape[0] * budget_bytes // total))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], n, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        kept[name] = int(a.shape[0]) if a.ndim else 1
+    return kept
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -625,7 +643,14 @@ def parse():
                     help="file the FULL record goes to (per-kernel tables, notes, sub-records); stdout carries the compact line")
     ap.add_argument("--dump-records", default=None,
                     help="rank 0 writes the last step's gathered [N*B,16] records (global pair order) to this .npy file")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last TIMED step computed -- the [N*B,16] f64 records the engine hands its "
+                         "caller (global pair order: 3x4 pose, inliers, correspondences, status, best RANSAC iteration) -- as "
+                         "DIR/records.npy (at most 64 MB: a fixed seeded sample of rows beyond that); same arguments, same inputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -836,6 +861,8 @@ def main():
     prof = eng.profile_read()
     eng.profile_enable(False)
     elapsed = max_over_ranks(elapsed, dev)
+    # the last timed step's records, copied before anything below runs the engine again (its buffer is reused)
+    last_out = (gathered if dist else rec).clone() if args.dump_outputs else None
 
     # The dominant kernel on its own (nothing else on the chip): in the timed region its launches share the SIMDs with the
     # other streams' kernels, at the lowest wave priority, so their durations say how the step is scheduled, not how good
@@ -894,6 +921,8 @@ def main():
 
     if rank == 0 and args.dump_records:
         np.save(args.dump_records, (gathered if dist else rec).cpu().numpy())
+    if rank == 0 and last_out is not None:
+        write_outputs(args.dump_outputs, {"records": last_out.cpu().numpy()})
     if rank == 0:
         rec = rec.cpu().numpy()
         n_kp = np.concatenate([p.fe.n.cpu().numpy().reshape(2, -1, model.nmask).sum(-1) for p in eng.parts], axis=1)  # [view, frame]

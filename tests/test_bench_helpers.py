@@ -29,3 +29,38 @@ def test_profile_summaries_feed_the_roofline_fields():
     assert "stale" in meta
     assert b.b_alg_c2(480, 640, 2000) == 1943296                                   # algorithmic bytes per pair
     assert b.host_cores() >= 1
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: float64 .npy per array, float32 kept; over the budget every array keeps the same seeded rows."""
+    import numpy as np
+    b = _bench()
+    rec = np.arange(64 * 16, dtype=np.float64).reshape(64, 16)
+    kept = b.write_outputs(str(tmp_path / "a"), {"records": rec, "counts": np.arange(64, dtype=np.int32),
+                                                  "resp": np.ones((64, 3), np.float32)})
+    assert kept == {"records": 64, "counts": 64, "resp": 64}
+    got = np.load(str(tmp_path / "a" / "records.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, rec)
+    assert np.load(str(tmp_path / "a" / "counts.npy")).dtype == np.float64
+    assert np.load(str(tmp_path / "a" / "resp.npy")).dtype == np.float32
+    budget = rec.nbytes // 4
+    for d in ("b", "c"):
+        kept = b.write_outputs(str(tmp_path / d), {"records": rec}, budget_bytes=budget)
+        assert kept == {"records": 16}
+    s1, s2 = np.load(str(tmp_path / "b" / "records.npy")), np.load(str(tmp_path / "c" / "records.npy"))
+    assert s1.nbytes <= budget and np.array_equal(s1, s2)                          # fixed sample, run to run
+    rows = s1[:, 0] / 16
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, rec[rows.astype(int)])   # whole rows, in order
+    assert b.OUTPUT_BUDGET == 64 << 20
+
+
+def test_steps_and_dump_outputs_arguments(monkeypatch):
+    import sys
+    import pytest
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    args = b.parse()
+    assert (args.steps, args.warmup, args.dump_outputs) == (7, 2, "out")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()

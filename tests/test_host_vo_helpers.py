@@ -170,36 +170,48 @@ def test_reference_side_export_of_a_calibrated_rig(tmp_path):
     assert gums_to_dict(rig2)["bottom"]["R_model_wrt_C"] == doc2["bottom"]["R_model_wrt_C"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/omnistereo"), reason="needs the reference tree (build container only)")
+def _replay(attrs):
+    """{dotted path: value} -> nested SimpleNamespace carrying exactly those attributes (0-d arrays as Python scalars)."""
+    from types import SimpleNamespace as NS
+    root = NS()
+    for path, v in attrs.items():
+        *parents, leaf = path.split(".")
+        node = root
+        for name in parents:
+            if not hasattr(node, name):
+                setattr(node, name, NS())
+            node = getattr(node, name)
+        setattr(node, leaf, v.item() if v.ndim == 0 else v)
+    return root
+
+
 def test_reference_side_export_on_a_live_reference_object(tmp_path):
-    """The same exporter on a LIVE GUMStereo of the imported reference (the object a user's pickle holds): every LUT entry of
-    the loaded rig equals the reference's own Panorama LUT.  Runs in a child interpreter (the reference needs placeholder
-    cv2 / pyopengv / vispy modules, tests/golden/make_fixtures.py) so that nothing leaks into this process."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = """
-import json, sys, os
-import numpy as np
-sys.path.insert(0, os.path.join(%r, "tests", "golden")); sys.path.insert(0, os.path.join(%r, "scripts"))
-import make_fixtures as mf
-import export_reference_gums as exp
-gum, pano, cm, ccv, pet = mf.import_reference()
-gs, top, bot = mf.build_gums_distorted(gum, pano)
-json.dump(exp.gums_to_sosvo_json(gs), open(sys.argv[1], "w"))
-np.savez(sys.argv[2], tx=top.panorama.world2cam_LUT_map_x, ty=top.panorama.world2cam_LUT_map_y,
-         bx=bot.panorama.world2cam_LUT_map_x, by=bot.panorama.world2cam_LUT_map_y)
-""" % (root, root)
-    f, z = str(tmp_path / "rig.json"), str(tmp_path / "lut.npz")
-    env = dict(os.environ, PYTHONPATH="/root/reference", PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code, f, z], capture_output=True, text=True, env=env, timeout=900,
-                       cwd=str(tmp_path))   # (not the repository root: its `omnistereo` alias package would shadow the reference's)
-    assert r.returncode == 0, r.stderr[-2000:]
+    """The same exporter on a LIVE GUMStereo of the imported reference (the object a user's pickle holds), replayed from
+    tests/golden/export_live_rig.npz (tests/golden/make_export_fixture.py): the attributes the exporter read from the live
+    object give the same JSON document as it wrote there, and every LUT entry of the rig loaded from that document equals
+    the reference's own Panorama LUT (SHA-256 over the full float64 tables, NaN positions, a few rows in the clear)."""
+    import hashlib
+    import json
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    rig, L = load_gums_json(f), np.load(z)
-    for m, kx, ky in ((rig.top_model, "tx", "ty"), (rig.bot_model, "bx", "by")):
-        assert np.array_equal(np.asarray(m.panorama.world2cam_LUT_map_x), L[kx], equal_nan=True)
-        assert np.array_equal(np.asarray(m.panorama.world2cam_LUT_map_y), L[ky], equal_nan=True)
+    Z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "export_live_rig.npz"))
+    exp = _load_exporter()
+    attrs = {k[len("attr:"):]: Z[k] for k in Z.files if k.startswith("attr:")}
+    doc = exp.gums_to_sosvo_json(_replay(attrs))
+    assert json.dumps(doc, sort_keys=True) == str(Z["doc"])
+    f = str(tmp_path / "rig.json")
+    with open(f, "w") as fh:
+        json.dump(doc, fh)
+    rig = load_gums_json(f)
+    for name, m in (("top", rig.top_model), ("bot", rig.bot_model)):
+        rows = Z[name + "_lut_rows"]
+        for ax in ("x", "y"):
+            lut = np.ascontiguousarray(getattr(m.panorama, "world2cam_LUT_map_" + ax), dtype=np.float64)
+            key = "%s_lut_%s" % (name, ax)
+            assert list(lut.shape) == list(Z[key + "_shape"]), key
+            assert np.array_equal(lut[rows], Z[key], equal_nan=True), key
+            nan = np.isnan(lut)
+            assert np.array_equal(np.packbits(nan.ravel()), Z[key + "_nan"]), key
+            assert hashlib.sha256(np.where(nan, 0.0, lut).tobytes()).hexdigest() == str(Z[key + "_sha256"]), key
 
 
 def test_precalibration_bin_layout(tmp_path):
