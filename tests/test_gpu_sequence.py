@@ -4,7 +4,9 @@ frame_window): the reference's VO loop computes every frame's front end once and
   * the store-based entry points give the records of the pair batch (sosvo_frame_pair_batch, itself bit-exact against
     the CPU oracle in test_gpu_batch_call.py / test_gpu_endtoend.py) on the same frames, bit for bit, whatever the window;
   * run_VO on a 200-frame synthetic sequence writes the byte-identical estimated_frame_poses_TUM.txt for windows of 32, 5
-    and 1 frames (1 = the per-frame use of the same entry points), and the host-array mirror path agrees to rounding."""
+    and 1 frames (1 = the per-frame use of the same entry points), and the host-array mirror path agrees to rounding;
+  * a run ended by an unreadable frame writes the lines and keyframes of the frames before it, for every window;
+  * a run on a camera model whose engine an aborted run left behind writes what it writes on a fresh model."""
 import os
 
 import numpy as np
@@ -249,3 +251,117 @@ def test_rgbd_sequence_engine_and_demo(ctx, tmp_path):
     assert texts[8] == texts[1] and "sequence_mode" in outs[8] and "sequence_mode" not in outs[0]
     for (i, Ta), (_, Tb) in zip(outs[8]["poses"], outs[0]["poses"]):
         assert np.allclose(Ta, Tb, rtol=1e-9, atol=1e-12), (i, np.abs(Ta - Tb).max())
+
+
+def _sos_run(seq, window):
+    import demo_vo_sos
+    return demo_vo_sos.main_sos_vo([seq, "--calibrated_gums_file", os.path.join(seq, "gums-calibrated.json"), "--frame_window",
+                                    str(window)])
+
+
+def _result_files(results):
+    return tuple(open(os.path.join(results, f)).read() for f in ("estimated_frame_poses_TUM.txt", "keyframe_ids.txt"))
+
+
+def _tum(text):
+    return np.array([[float(v) for v in line.split()] for line in text.splitlines()])
+
+
+@pytest.mark.parametrize("failure", ["reader_raises", "unreadable_file"])
+def test_run_vo_ended_by_an_error_writes_the_frames_before_it(ctx, tmp_path, monkeypatch, failure):
+    """Frame 37 of a 60-frame sequence cannot be read (inside the second window of 32 frames): the reader raises, or the
+    file is not an image at all (imread returns None).  Every frame window (32, 5, 1 and the per-frame path 0) raises an
+    OSError naming the file, and leaves the pose file with exactly the lines of frames 0-36 -- byte-identical for the
+    windows, to 1e-6 for the per-frame path, those of an uninterrupted run -- and the keyframe file with the keyframes
+    those frames get in the uninterrupted run."""
+    from vo_single_camera_sos_amd.omnistereo import common_cv
+    gs, _ = _rig()
+    n, bad = 60, 37
+    seq = str(tmp_path / "seq60")
+    synthetic.write_sos_sequence(seq, gs, n_frames=n, seed=77, max_t=40.0, max_deg=2.0)
+    results = os.path.join(seq, "results-omni")
+    full = _sos_run(seq, 32)
+    assert full["tracked"] == n - 1
+    full_poses, _ = _result_files(results)
+    want_kf = "".join("%d\n" % k for k in full["keyframe_ids"] if k < bad)
+    name = "image-%04d.png" % bad
+    if failure == "reader_raises":
+        imread = common_cv.imread
+
+        def failing_imread(filename):
+            if os.path.basename(filename) == name:
+                raise OSError("simulated read error: %s" % filename)
+            return imread(filename)
+        monkeypatch.setattr(common_cv, "imread", failing_imread)
+    else:
+        with open(os.path.join(seq, "omni", name), "wb") as f:
+            f.write(b"not a PNG file\n" * 64)
+    texts = {}
+    for w in (32, 5, 1, 0):
+        with pytest.raises(OSError, match=name):
+            _sos_run(seq, w)
+        texts[w], kf = _result_files(results)
+        assert [int(line.split()[0]) for line in texts[w].splitlines()] == list(range(bad)), w
+        assert kf == want_kf, (w, kf, want_kf)
+    assert texts[32] == texts[5] == texts[1] == "".join(full_poses.splitlines(True)[:bad])
+    assert np.allclose(_tum(texts[0]), _tum(texts[32]), rtol=1e-6, atol=1e-9)
+
+
+def _sos_direct(model, seq, n, results, window):
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
+    out = run_VO(None, model, gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"),
+                 img_filename_template=os.path.join(seq, "omni", "image-*.png"), img_indices=list(range(n)),
+                 results_path=results, frame_window=window)
+    return out, _result_files(results)
+
+
+def _rgbd_model():
+    from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
+    from vo_single_camera_sos_amd.omnistereo.transformations import rotation_matrix
+    cam = RGBDCamModel(fx=554.256258, fy=554.256258, center_x=319.5, center_y=239.5, scaling_factor=1. / 1000.0,
+                       do_undistortion=False, depth_is_Z=False, focal_length_m=1. / 1000.0)    # (as demo_vo_rgbd, synthetic)
+    cam.T_Cest_wrt_Rgt = rotation_matrix(-np.pi / 2.0, [1, 0, 0])
+    return cam
+
+
+def _rgbd_direct(model, seq, n, results, window):
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
+    d = os.path.join(seq, "rgbd")
+    out = run_VO(None, model, gt_poses_filename=os.path.join(d, "gt_TUM.txt"), img_filename_template=os.path.join(d, "rgb", "*.png"),
+                 depth_filename_template=os.path.join(d, "depth", "*.png"), img_indices=list(range(n)), results_path=results,
+                 frame_window=window)
+    return out, _result_files(results)
+
+
+@pytest.mark.parametrize("kind", ["sos", "rgbd"])
+def test_run_vo_after_an_aborted_run_on_the_same_camera_model(ctx, tmp_path, kind):
+    """run_VO twice on ONE camera model, so the second run gets the sequence engine the first one left: run A stops at a
+    black frame (frame 5, in its second window of 4 frames) while its staging thread has the next window; run B, another
+    sequence on the same rig, then writes the byte-identical pose and keyframe files as on a freshly made model."""
+    from vo_single_camera_sos_amd.omnistereo.common_cv import imwrite
+    seq_a, seq_b = str(tmp_path / "seq_a"), str(tmp_path / "seq_b")
+    if kind == "sos":
+        from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
+        gs, _ = _rig()
+        n_b = 40
+        synthetic.write_sos_sequence(seq_a, gs, n_frames=9, seed=5, max_t=40.0, max_deg=2.0)
+        synthetic.write_sos_sequence(seq_b, gs, n_frames=n_b, seed=77, max_t=40.0, max_deg=2.0)
+        imwrite(os.path.join(seq_a, "omni", "image-0005.png"), np.zeros((480, 640, 3), np.uint8))
+        make = lambda: load_gums_json(os.path.join(seq_b, "gums-calibrated.json"))  # noqa: E731
+        run = _sos_direct
+    else:
+        n_b = 24
+        synthetic.write_rgbd_sequence(seq_a, n_frames=9, seed=41, max_t=40.0, max_deg=2.0, depth_is_Z=False)
+        synthetic.write_rgbd_sequence(seq_b, n_frames=n_b, seed=43, max_t=40.0, max_deg=2.0, depth_is_Z=False)
+        imwrite(os.path.join(seq_a, "rgbd", "rgb", "0005.png"), np.zeros((480, 640, 3), np.uint8))
+        make, run = _rgbd_model, _rgbd_direct
+    model = make()
+    with pytest.warns(UserWarning):
+        a, _ = run(model, seq_a, 9, str(tmp_path / "res_a"), 4)
+    assert [p[0] for p in a["poses"]] == [0, 1, 2, 3, 4] and a["sequence_mode"]["frame_window"] == 4
+    engines = list(model.__dict__["_sequence_engines"].values())
+    b, files_b = run(model, seq_b, n_b, str(tmp_path / "res_b"), 4)
+    assert list(model.__dict__["_sequence_engines"].values()) == engines     # (the same engine served run B)
+    fresh, files_fresh = run(make(), seq_b, n_b, str(tmp_path / "res_fresh"), 4)
+    assert b["tracked"] == fresh["tracked"] >= 5
+    assert files_b == files_fresh

@@ -4,6 +4,7 @@ operations as the reference, so it is compared BIT-EXACT."""
 import os
 
 import numpy as np
+import pytest
 
 from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
 from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
@@ -70,6 +71,45 @@ def test_annulus_masks_and_bucket_columns():
     assert pn.get_panorama_col_from_azimuth(0.0) == 1199
     assert pn.get_panorama_col_from_azimuth(np.pi) == 599
     assert pn.get_panorama_col_from_azimuth(2 * np.pi - 1e-9) in (0, 1)
+
+
+def _unwrap_nearest(pn):
+    """The unwrap of a mask without a GPU: nearest pixel of the panorama's own look-up tables (0 outside the image)."""
+    mx, my = pn.float32_maps()
+
+    def unwrap(omni_mask):
+        ok = np.isfinite(mx) & np.isfinite(my)
+        x, y = np.rint(np.where(ok, mx, -1)).astype(np.int64), np.rint(np.where(ok, my, -1)).astype(np.int64)
+        h, w = omni_mask.shape
+        ok &= (0 <= x) & (x < w) & (0 <= y) & (y < h)
+        return np.where(ok, omni_mask[np.clip(y, 0, h - 1), np.clip(x, 0, w - 1)], 0).astype(np.uint8)
+    return unwrap
+
+
+@pytest.mark.parametrize("moved", ["center_point_outer", "center_point_inner", "both"])
+@pytest.mark.parametrize("padding", [0, 10])
+def test_azimuthal_masks_follow_an_annulus_moved_by_whole_pixels(moved, padding):
+    """generate_azimuthal_masks keeps its masks while the request and the annulus are unchanged.  An annulus whose circles
+    move by whole pixels has the same shape, pixel count and radii as before: the masks must still be rebuilt (those of a
+    fresh Panorama on the moved model), for the model's mask (padding 0) and for one made from the centres (padding > 0)."""
+    gs = _rig()
+    m, shape = gs.top_model, (480, 640)
+    pn = m.panorama
+    unwrap = _unwrap_nearest(pn)
+    kw = dict(azimuth_mask_degrees=30, overlap_degrees=0, elev_mask_padding=padding, omni_shape=shape, unwrap_fn=unwrap)
+    m.mask = m.make_mask(shape)
+    before = [a.copy() for a in pn.generate_azimuthal_masks(**kw)]
+    n_before = int(np.count_nonzero(m.mask))
+    for name in (("center_point_outer", "center_point_inner") if moved == "both" else (moved,)):
+        setattr(m, name, getattr(m, name) + np.array([3.0, -2.0]))
+    m.mask = m.make_mask(shape)
+    assert int(np.count_nonzero(m.mask)) == n_before       # (what the cache key looked at is unchanged)
+    fresh = Panorama(m, width=1200).generate_azimuthal_masks(**kw)
+    assert any(not np.array_equal(a, b) for a, b in zip(before, fresh))
+    got = pn.generate_azimuthal_masks(**kw)
+    assert len(got) == len(fresh) == 12
+    assert all(np.array_equal(a, b) for a, b in zip(got, fresh))
+    assert pn.generate_azimuthal_masks(**kw) is got        # (and an unchanged request still comes from the cache)
 
 
 # ---- the distorted rig: the branches of the forward model the synthetic rig leaves at zero (a3 pinned on them) ----------

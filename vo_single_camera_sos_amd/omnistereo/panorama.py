@@ -129,13 +129,17 @@ class Panorama(object):
         """`unwrap_fn(omni_mask) -> pano_mask` overrides the GPU unwrap of the elevation mask (tests use it to
         build the masks without a GPU); default is self.get_panoramic_image."""
         # the same request as last time (every tracker bootstrap asks again, pose_est_tools.py:870-878): the masks are a pure
-        # function of these arguments and of the model's annulus mask -- keep them (a GPU unwrap + twelve full-size images)
+        # function of these arguments and of the model's annulus -- keep them (a GPU unwrap + twelve full-size images).  The
+        # annulus is its mask's content (a checksum: moving a circle by whole pixels keeps the pixel count) and, for a mask
+        # made here (elev_mask_padding > 0), its radii and circle centres.
+        import zlib
         mm = getattr(self.model, "mask", None)
         key = (float(azimuth_mask_degrees), float(overlap_degrees), bool(mask_also_on_elev), int(elev_mask_padding),
                tuple(float(a) for a in stand_masks_azimuth_coord_in_degrees_list), float(stand_masks_width_in_degrees),
                None if omni_shape is None else tuple(omni_shape), unwrap_fn is None, self.rows, self.cols,
-               None if mm is None else (mm.shape, int(np.count_nonzero(mm))),
-               tuple(float(v) for v in (self.model.inner_img_radius, self.model.outer_img_radius)))
+               None if mm is None else (mm.shape, str(mm.dtype), zlib.crc32(np.ascontiguousarray(mm).tobytes())),
+               tuple(float(v) for v in (self.model.inner_img_radius, self.model.outer_img_radius)),
+               tuple(float(v) for c in (self.model.center_point_inner, self.model.center_point_outer) for v in c))
         if getattr(self, "_azimuthal_masks_key", None) == key and self.azimuthal_masks:
             return self.azimuthal_masks
         self._azimuthal_masks_key = None

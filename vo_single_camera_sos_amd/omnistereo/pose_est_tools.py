@@ -16,6 +16,7 @@ reference's per-frame API.
     run_VO / driver_VO (frame loop, keyframe policy, TUM pose files)    pose_est_tools.py:1264-1741
 
 Not built: visualisation (vispy / matplotlib windows), the live-camera driver (run_VO_live)."""
+import itertools
 import os
 import threading
 import time
@@ -672,6 +673,128 @@ def _is_rgbd_model(camera_model):
     return isinstance(camera_model, RGBDCamModel)
 
 
+def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=None):
+    """run_VO's sequence mode: the items (frame index, image, depth map or None) of the iterator `it`, `W` at a time through
+    the batched front end of `eng` (a pipeline.SequenceEngine / RGBDSequenceEngine), yielded one by one as
+    (frame index, image, None, record dict, position in the sequence).  images_of(list of items) -> what eng.stage_host
+    takes; engine_state: run_VO's counters ("window_s", "windows"); on_window() is called when a window's records are in,
+    before its frames are yielded (run_VO writes the previous window's lines there); stop: the event that ends the helper
+    thread (default: a new one; set when the generator ends).
+    A source that raises ends the run after the frames read before the failure, as the per-frame path does.  However the
+    generator ends (exhausted, failed, closed), no call of this run reaches the engine once it has: the engine goes to the
+    next run with the same camera model (sequence_engine_for), and a late upload would put this run's frames into its
+    buffers.  The helper thread is joined unless it is waiting for a source that blocks (a live camera); then it leaves
+    without touching the engine when the source returns."""
+    import queue
+    W = int(W)
+    stop = threading.Event() if stop is None else stop
+    failed = []      # a read that failed after some frames of a window: raised by the next read, once those are processed
+
+    def next_chunk():
+        if failed:
+            raise failed.pop()
+        chunk = []
+        try:
+            for item in it:
+                chunk.append(item)
+                if len(chunk) >= W:
+                    break
+        except Exception as e:
+            if not chunk:
+                raise
+            failed.append(e)
+        return chunk
+    chunk = next_chunk()
+    if not chunk:
+        return
+    # a helper thread pulls the NEXT window from the source and copies it into the engine's other pinned buffer while
+    # this one is processed (the copy releases the GIL); a buffer returns to the thread after its upload was synchronised
+    free, ready = queue.Queue(), queue.Queue()
+    free.put(1)
+    # the helper thread holds `lock` while it calls the engine and checks `stop` under it; `reading` says it waits in the source
+    lock, reading = threading.Lock(), [False]
+
+    def producer():
+        try:
+            while True:
+                with lock:
+                    if stop.is_set():
+                        break
+                    reading[0] = True
+                try:
+                    c = next_chunk()
+                finally:
+                    with lock:
+                        reading[0] = False
+                if not c:
+                    break
+                b = free.get()
+                if b is None:
+                    break
+                with lock:
+                    if stop.is_set():
+                        break
+                    t0 = time.perf_counter()
+                    eng.stage_host(images_of(c), b)
+                    eng.stage_s["stage_to_pinned"] += time.perf_counter() - t0
+                    if stop.is_set():
+                        break
+                    if eng.early_upload:
+                        eng.upload_staged(b, len(c))   # the copy to the device starts now, beside the current window's kernels
+                ready.put((c, b))
+            ready.put((None, None))
+        except BaseException as e:   # handed to the consumer
+            ready.put((e, None))
+    t0 = time.perf_counter()
+    eng.stage_host(images_of(chunk), 0)
+    eng.stage_s["stage_to_pinned"] += time.perf_counter() - t0
+    worker = threading.Thread(target=producer, name="sosvo-stage", daemon=True)
+    worker.start()
+    seq_index, buf = 0, 0
+    try:
+        t0 = time.perf_counter()
+        eng.enqueue_staged(buf, len(chunk))
+        engine_state["window_s"] += time.perf_counter() - t0
+        while chunk:
+            t0 = time.perf_counter()
+            infos = eng.collect()                        # (synchronises: the upload from `buf` is complete)
+            engine_state["windows"] += 1
+            free.put(buf)
+            # the next window goes onto the GPU BEFORE this one's records are worked through, when the helper thread
+            # has it staged already (an image sequence: nearly always; a live source: never -- its frames are not
+            # held back for it)
+            nxt = None
+            if eng.enqueue_ahead:
+                try:
+                    nxt = ready.get_nowait()
+                except queue.Empty:
+                    nxt = None
+                if nxt is not None and nxt[0] is not None and not isinstance(nxt[0], BaseException):
+                    eng.enqueue_staged(nxt[1], len(nxt[0]))
+            engine_state["window_s"] += time.perf_counter() - t0
+            if on_window is not None:
+                on_window()                              # (run_VO: the previous window's lines, off the per-frame path)
+            for item, info in zip(chunk, infos):
+                yield item[0], item[1], None, info, seq_index
+                seq_index += 1
+            if nxt is None:
+                nxt = ready.get()
+                if nxt[0] is not None and not isinstance(nxt[0], BaseException):
+                    t0 = time.perf_counter()
+                    eng.enqueue_staged(nxt[1], len(nxt[0]))
+                    engine_state["window_s"] += time.perf_counter() - t0
+            chunk, buf = nxt
+            if isinstance(chunk, BaseException):
+                raise chunk
+    finally:
+        stop.set()
+        free.put(None)
+        with lock:                   # (waits for an engine call in flight; after it the thread makes none)
+            in_source = reading[0]
+        if not in_source:            # (otherwise it ends when the source returns)
+            worker.join()
+
+
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None):
@@ -751,11 +874,14 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
             img_indices = list(range(len(image_names)))
 
         def load(k):
+            img = imread(image_names[k])
+            if img is None:   # (imread's None for a file it cannot decode ends the run here, for every frame window alike)
+                raise OSError("cannot read the image file %s" % image_names[k])
             if rgbd:
                 # the reference converts BGR -> RGB (:1430) and then treats the array as BGR (:531): reproduced as is
-                return img_indices[k], np.ascontiguousarray(imread(image_names[k])[..., ::-1]), \
+                return img_indices[k], np.ascontiguousarray(img[..., ::-1]), \
                     get_depthmap_float32_from_png(depth_names[k], camera_model.scaling_factor)
-            return img_indices[k], imread(image_names[k]), None
+            return img_indices[k], img, None
 
         def frames():   # (frame index, image, depth map or None) from the files of the sequence; the next frame is
             # decoded on a helper thread while the current one is tracked (the decoder releases the GIL)
@@ -777,97 +903,20 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         source = frames
 
         def frames():   # the same frames, `frame_window` at a time through the batched front end
-            import queue
             W = int(frame_window)
             it = iter(source())
-
-            def next_chunk():
-                chunk = []
-                for item in it:
-                    chunk.append(item)
-                    if len(chunk) >= W:
-                        break
-                return chunk
-            chunk = next_chunk()
-            if not chunk:
+            first = next(it, None)
+            if first is None:
                 return
             engine_state["tried"] = True
             eng = engine_state["engine"] = (rgbd_sequence_engine_for if rgbd else sequence_engine_for)(
-                tracker, camera_model, chunk[0][1], W)
+                tracker, camera_model, first[1], W)
+            it = itertools.chain([first], it)
             if eng is None:              # no batched counterpart of this configuration: the per-frame path
-                while chunk:
-                    for item in chunk:
-                        yield item
-                    chunk = next_chunk()
+                yield from it
                 return
             images_of = (lambda c: [(item[1], item[2]) for item in c]) if rgbd else (lambda c: [item[1] for item in c])
-            # a helper thread pulls the NEXT window from the source and copies it into the engine's other pinned buffer while
-            # this one is processed (the copy releases the GIL); a buffer returns to the thread after its upload was synchronised
-            free, ready = queue.Queue(), queue.Queue()
-            free.put(1)
-            stop = threading.Event()
-
-            def producer():
-                try:
-                    while not stop.is_set():
-                        c = next_chunk()
-                        if not c:
-                            break
-                        b = free.get()
-                        if b is None:
-                            return
-                        t0 = time.perf_counter()
-                        eng.stage_host(images_of(c), b)
-                        eng.stage_s["stage_to_pinned"] += time.perf_counter() - t0
-                        if eng.early_upload:
-                            eng.upload_staged(b, len(c))   # the copy to the device starts now, beside the current window's kernels
-                        ready.put((c, b))
-                    ready.put((None, None))
-                except BaseException as e:   # handed to the consumer
-                    ready.put((e, None))
-            t0 = time.perf_counter()
-            eng.stage_host(images_of(chunk), 0)
-            eng.stage_s["stage_to_pinned"] += time.perf_counter() - t0
-            worker = threading.Thread(target=producer, name="sosvo-stage", daemon=True)
-            worker.start()
-            seq_index, buf = 0, 0
-            try:
-                t0 = time.perf_counter()
-                eng.enqueue_staged(buf, len(chunk))
-                engine_state["window_s"] += time.perf_counter() - t0
-                while chunk:
-                    t0 = time.perf_counter()
-                    infos = eng.collect()                        # (synchronises: the upload from `buf` is complete)
-                    engine_state["windows"] += 1
-                    free.put(buf)
-                    # the next window goes onto the GPU BEFORE this one's records are worked through, when the helper thread
-                    # has it staged already (an image sequence: nearly always; a live source: never -- its frames are not
-                    # held back for it)
-                    nxt = None
-                    if eng.enqueue_ahead:
-                        try:
-                            nxt = ready.get_nowait()
-                        except queue.Empty:
-                            nxt = None
-                        if nxt is not None and nxt[0] is not None and not isinstance(nxt[0], BaseException):
-                            eng.enqueue_staged(nxt[1], len(nxt[0]))
-                    engine_state["window_s"] += time.perf_counter() - t0
-                    flush_output()                               # the previous window's lines, off the per-frame path
-                    for item, info in zip(chunk, infos):
-                        yield item[0], item[1], None, info, seq_index
-                        seq_index += 1
-                    if nxt is None:
-                        nxt = ready.get()
-                        if nxt[0] is not None and not isinstance(nxt[0], BaseException):
-                            t0 = time.perf_counter()
-                            eng.enqueue_staged(nxt[1], len(nxt[0]))
-                            engine_state["window_s"] += time.perf_counter() - t0
-                    chunk, buf = nxt
-                    if isinstance(chunk, BaseException):
-                        raise chunk
-            finally:
-                stop.set()
-                free.put(None)
+            yield from sequence_windows(it, eng, W, images_of, engine_state, on_window=flush_output)
     if gt_poses_filename is None or not os.path.exists(gt_poses_filename):
         n_gt = max(len(img_indices), img_indices[-1] + 1)
         gt_list = n_gt * [np.identity(4)]   # (a live run has no ground truth: identity for every frame, as :1012)
@@ -903,120 +952,124 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     img_index_number = -1
     batched_output = False       # sequence mode: lines are written once per window (flush_output in the window generator)
     kf_lines = []
-    while True:
-        t_frame = t0 = time.process_time()
-        try:
-            item = next(frame_iter)
-        except StopIteration:
-            break
-        idx, img, depth_map = item[:3]
-        dev_info = item[3] if len(item) > 3 else None
-        batched_output = dev_info is not None
-        img_index_number += 1
-        t1 = time.process_time()
-        if img_index_number > 0:
-            acc["read"] += t1 - t0
-        t0 = t1
-        if dev_info is not None:
-            current_frame = (DeviceRGBDFrame if rgbd else DeviceStereoFrame)(
-                engine_state["engine"], dev_info, camera_model, frame_id=idx, seq_index=item[4], parent_id=current_keyframe_id)
-        elif rgbd:
-            current_frame = RGBDFrame(rgbd_camera_model=camera_model, frame_id=idx, rgb_img=img, depth_map=depth_map,
-                                      parent_id=current_keyframe_id)
-        else:
-            camera_model.set_current_omni_image(img, generate_panoramas=False, view=False, apply_mask=True, mask_RGB=(0, 0, 0))
-            current_frame = StereoPanoramicFrame(stereo_camera_model=camera_model, frame_id=idx, parent_id=current_keyframe_id)
-        t1 = time.process_time()
-        if img_index_number > 0:
-            acc["setup"] += t1 - t0
-        T_gt = gt_list[idx] if idx < len(gt_list) else (np.identity(4) if _live_frames is not None else np.full((4, 4), np.nan))
-        if T_Rgt_wrt_S is not None:
-            T_gt = tr.concatenate_matrices(T_Rgt_wrt_S, T_gt, T_S_wrt_Rgt)   # :1472
-        if img_index_number > 0:
-            t0 = t1
-            ok, msg = tracker.track_frame(reference_frame=reference_frame, current_frame=current_frame)
-            if not ok:
-                log_only.append((len(out_msgs), msg))
-                warn("%sWarning failed: %s" % (prefix, msg))
+    try:
+        while True:
+            t_frame = t0 = time.process_time()
+            try:
+                item = next(frame_iter)
+            except StopIteration:
                 break
-            reference_frame.children_ids.append(current_frame.frame_id)
-            tracked_wrt_keyframe += 1
-            acc["track"] += time.process_time() - t0
-            # keyframe policy (:1516-1550)
-            dist = tr.rpe_translation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
-            ang = tr.rpe_rotation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
-            n_tracked = tracker.num_tracked_correspondences / float(tracker.number_of_cams)
-            acc["corr"] += n_tracked
-            M_K, M_F = reference_frame.num_valid_keypoints, current_frame.num_valid_keypoints
-            if (pos_thr < dist < pos_max) or (ang_thr < ang < ang_max):
-                if n_tracked > thr_tracked * tracked_prev_avg and M_F > thr_keypoints * M_K:
-                    reason = ""
-                    if pos_thr < dist < pos_max:
-                        if ang < ang_max:
-                            reason += "translation %.2f < %.4f < %.2f [m]" % (pos_thr, dist, pos_max)
-                            create_keyframe = True
-                    elif ang_thr < ang:
-                        if dist < pos_max < ang_max:   # as written in the reference (:1534)
-                            reason += " rotation: %.2f > %.2f [radians]" % (ang, ang_thr)
-                            create_keyframe = True
-                    if create_keyframe:
-                        say("%sFrame [%d] as Keyframe due to %s... with %d tracked keypoint correspondences after tracking "
-                            "%d frames" % (prefix, idx, reason, n_tracked, tracked_wrt_keyframe))
-                    else:
-                        say("%sFrame [%d] as failed to create Keyframe due to some CRAZYNESS" % (prefix, idx))
-                else:
-                    say("%sFrame [%d] as Keyframe...doesn't satisfy %d > %.2f * %.2f and %d > %.2f * %.2f"
-                        % (prefix, idx, n_tracked, thr_tracked, tracked_prev_avg, M_F, thr_keypoints, M_K))
-            tracked_prev_avg = (n_tracked + (float(tracked_wrt_keyframe) - 1.) * tracked_prev_avg) / float(tracked_wrt_keyframe)
-            acc["ratio"] += tracker.inlier_tracked_correspondences_ratio
-            inlier_ratio_cma = (tracker.inlier_tracked_correspondences_ratio + float(img_index_number - 1) * inlier_ratio_cma) \
-                / float(img_index_number)
-        if create_keyframe:
-            tracked_wrt_keyframe = 0
-            tracked_prev_avg = 0.
-            reference_frame = KeyFrameClass(frame=current_frame)
+            idx, img, depth_map = item[:3]
+            dev_info = item[3] if len(item) > 3 else None
+            batched_output = dev_info is not None
+            img_index_number += 1
+            t1 = time.process_time()
+            if img_index_number > 0:
+                acc["read"] += t1 - t0
+            t0 = t1
             if dev_info is not None:
-                current_frame.promote()   # the frame's record moves to the store's keyframe slot
-            current_keyframe_id = reference_frame.frame_id
-            kf_lines.append("%d\n" % current_keyframe_id)
-            keyframe_ids.append(current_keyframe_id)
-            if len(tracker.T_Ckey_wrt_S_est_list) > 0:
-                T_key = tr.concatenate_matrices(tracker.T_Ckey_wrt_S_est_list[-1], reference_frame.T_frame_wrt_tracking_ref_frame)
+                current_frame = (DeviceRGBDFrame if rgbd else DeviceStereoFrame)(
+                    engine_state["engine"], dev_info, camera_model, frame_id=idx, seq_index=item[4], parent_id=current_keyframe_id)
+            elif rgbd:
+                current_frame = RGBDFrame(rgbd_camera_model=camera_model, frame_id=idx, rgb_img=img, depth_map=depth_map,
+                                          parent_id=current_keyframe_id)
             else:
-                T_key = tracker.T_C_curr_frame_wrt_S_est
-            tracker.T_Ckey_wrt_S_est_list.append(T_key)
-            create_keyframe = False
-            number_of_keyframes += 1
-        # TUM lines: idx tx ty tz qx qy qz qw (:1611-1621), quaternion_from_matrix(isprecise=False) of the pose -- formatted by
-        # flush_output (a window at a time in sequence mode)
-        T_now = np.array(tracker.T_C_curr_frame_wrt_S_est, copy=True)
-        pending.append((idx, T_now, T_gt))
-        poses_out.append((idx, T_now))
-        if img_index_number > 0:
-            acc["vo"] += time.process_time() - t_frame
-        n_done = img_index_number
-        say("%sDONE with F[%d] (Parent K[%d]). C.M.Avg. RANSAC inlier ratio = %.3f"
-            % (prefix, current_frame.frame_id, current_frame.parent_id, inlier_ratio_cma))
-        if not batched_output:
-            flush_output()
-    flush_output()
-    kf_file.write("".join(kf_lines))
-    d = float(max(n_done, 1))
-    summary = "\n".join([
-        "%sVO done with %d keyframes" % (prefix, number_of_keyframes),
-        "Image Read Avg Time: {time:.8f} seconds".format(time=acc["read"] / d),
-        "Frame Setup Avg Time: {time:.8f} seconds".format(time=acc["setup"] / d),
-        "Frame Tracking Avg Time: {time:.8f} seconds".format(time=acc["track"] / d),
-        "Overall Frame VO Avg Time: {time:.8f} seconds".format(time=acc["vo"] / d),
-        "Total Number of tracked correspondences: {corrs}".format(corrs=int(acc["corr"])),
-        "Average Number of tracked correspondences: {corrs}".format(corrs=int(int(acc["corr"]) / d)),
-        "Average tracked correspondences RANSAC inlier ratio: {ratio:.8f}".format(ratio=acc["ratio"] / d),
-        "Estimated poses in TUM format SAVED as " + est_path,
-        "Keyframes (indices) SAVED as " + kf_path])
-    say(summary)
-    flush_output()
-    for f in (est_file, gt_file, kf_file, log):
-        f.close()
+                camera_model.set_current_omni_image(img, generate_panoramas=False, view=False, apply_mask=True, mask_RGB=(0, 0, 0))
+                current_frame = StereoPanoramicFrame(stereo_camera_model=camera_model, frame_id=idx, parent_id=current_keyframe_id)
+            t1 = time.process_time()
+            if img_index_number > 0:
+                acc["setup"] += t1 - t0
+            T_gt = gt_list[idx] if idx < len(gt_list) else (np.identity(4) if _live_frames is not None else np.full((4, 4), np.nan))
+            if T_Rgt_wrt_S is not None:
+                T_gt = tr.concatenate_matrices(T_Rgt_wrt_S, T_gt, T_S_wrt_Rgt)   # :1472
+            if img_index_number > 0:
+                t0 = t1
+                ok, msg = tracker.track_frame(reference_frame=reference_frame, current_frame=current_frame)
+                if not ok:
+                    log_only.append((len(out_msgs), msg))
+                    warn("%sWarning failed: %s" % (prefix, msg))
+                    break
+                reference_frame.children_ids.append(current_frame.frame_id)
+                tracked_wrt_keyframe += 1
+                acc["track"] += time.process_time() - t0
+                # keyframe policy (:1516-1550)
+                dist = tr.rpe_translation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
+                ang = tr.rpe_rotation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
+                n_tracked = tracker.num_tracked_correspondences / float(tracker.number_of_cams)
+                acc["corr"] += n_tracked
+                M_K, M_F = reference_frame.num_valid_keypoints, current_frame.num_valid_keypoints
+                if (pos_thr < dist < pos_max) or (ang_thr < ang < ang_max):
+                    if n_tracked > thr_tracked * tracked_prev_avg and M_F > thr_keypoints * M_K:
+                        reason = ""
+                        if pos_thr < dist < pos_max:
+                            if ang < ang_max:
+                                reason += "translation %.2f < %.4f < %.2f [m]" % (pos_thr, dist, pos_max)
+                                create_keyframe = True
+                        elif ang_thr < ang:
+                            if dist < pos_max < ang_max:   # as written in the reference (:1534)
+                                reason += " rotation: %.2f > %.2f [radians]" % (ang, ang_thr)
+                                create_keyframe = True
+                        if create_keyframe:
+                            say("%sFrame [%d] as Keyframe due to %s... with %d tracked keypoint correspondences after tracking "
+                                "%d frames" % (prefix, idx, reason, n_tracked, tracked_wrt_keyframe))
+                        else:
+                            say("%sFrame [%d] as failed to create Keyframe due to some CRAZYNESS" % (prefix, idx))
+                    else:
+                        say("%sFrame [%d] as Keyframe...doesn't satisfy %d > %.2f * %.2f and %d > %.2f * %.2f"
+                            % (prefix, idx, n_tracked, thr_tracked, tracked_prev_avg, M_F, thr_keypoints, M_K))
+                tracked_prev_avg = (n_tracked + (float(tracked_wrt_keyframe) - 1.) * tracked_prev_avg) / float(tracked_wrt_keyframe)
+                acc["ratio"] += tracker.inlier_tracked_correspondences_ratio
+                inlier_ratio_cma = (tracker.inlier_tracked_correspondences_ratio + float(img_index_number - 1) * inlier_ratio_cma) \
+                    / float(img_index_number)
+            if create_keyframe:
+                tracked_wrt_keyframe = 0
+                tracked_prev_avg = 0.
+                reference_frame = KeyFrameClass(frame=current_frame)
+                if dev_info is not None:
+                    current_frame.promote()   # the frame's record moves to the store's keyframe slot
+                current_keyframe_id = reference_frame.frame_id
+                kf_lines.append("%d\n" % current_keyframe_id)
+                keyframe_ids.append(current_keyframe_id)
+                if len(tracker.T_Ckey_wrt_S_est_list) > 0:
+                    T_key = tr.concatenate_matrices(tracker.T_Ckey_wrt_S_est_list[-1], reference_frame.T_frame_wrt_tracking_ref_frame)
+                else:
+                    T_key = tracker.T_C_curr_frame_wrt_S_est
+                tracker.T_Ckey_wrt_S_est_list.append(T_key)
+                create_keyframe = False
+                number_of_keyframes += 1
+            # TUM lines: idx tx ty tz qx qy qz qw (:1611-1621), quaternion_from_matrix(isprecise=False) of the pose -- formatted by
+            # flush_output (a window at a time in sequence mode)
+            T_now = np.array(tracker.T_C_curr_frame_wrt_S_est, copy=True)
+            pending.append((idx, T_now, T_gt))
+            poses_out.append((idx, T_now))
+            if img_index_number > 0:
+                acc["vo"] += time.process_time() - t_frame
+            n_done = img_index_number
+            say("%sDONE with F[%d] (Parent K[%d]). C.M.Avg. RANSAC inlier ratio = %.3f"
+                % (prefix, current_frame.frame_id, current_frame.parent_id, inlier_ratio_cma))
+            if not batched_output:
+                flush_output()
+        d = float(max(n_done, 1))
+        summary = "\n".join([
+            "%sVO done with %d keyframes" % (prefix, number_of_keyframes),
+            "Image Read Avg Time: {time:.8f} seconds".format(time=acc["read"] / d),
+            "Frame Setup Avg Time: {time:.8f} seconds".format(time=acc["setup"] / d),
+            "Frame Tracking Avg Time: {time:.8f} seconds".format(time=acc["track"] / d),
+            "Overall Frame VO Avg Time: {time:.8f} seconds".format(time=acc["vo"] / d),
+            "Total Number of tracked correspondences: {corrs}".format(corrs=int(acc["corr"])),
+            "Average Number of tracked correspondences: {corrs}".format(corrs=int(int(acc["corr"]) / d)),
+            "Average tracked correspondences RANSAC inlier ratio: {ratio:.8f}".format(ratio=acc["ratio"] / d),
+            "Estimated poses in TUM format SAVED as " + est_path,
+            "Keyframes (indices) SAVED as " + kf_path])
+        say(summary)
+    finally:   # (an exception too: the lines of the frames tracked so far and the keyframe file are written)
+        close = getattr(frame_iter, "close", None)
+        if close is not None:
+            close()   # (sequence mode: its staging thread ends before the engine can go to another run)
+        flush_output()
+        kf_file.write("".join(kf_lines))
+        for f in (est_file, gt_file, kf_file, log):
+            f.close()
     out = dict(poses=poses_out, keyframe_ids=keyframe_ids, tracked=n_done, message=summary)
     if engine_state["engine"] is not None:
         eng = engine_state["engine"]
