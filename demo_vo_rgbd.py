@@ -35,6 +35,8 @@ def main_rgbd_vo(argv=None):
     parser.add_argument("--frame_window", default=-1, type=int,
                         help="sequence mode: frames per batched front-end pass on the GPU (-1 = default 32; 0 = the per-frame "
                              "mirror path).  The pose file does not depend on the window size.")
+    parser.add_argument("--detection_method", default="GFT", choices=("GFT", "ORB", "FAST", "AGAST"), type=str.upper,
+                        help="keypoint detector of the tracker and its frames (GFT: the reference's default)")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -69,7 +71,8 @@ def main_rgbd_vo(argv=None):
                     use_multithreads_for_VO=args.use_multithreads_for_VO, step_for_scene_images=args.step,
                     first_image_index=args.first_image_index, last_image_index=args.last_image_index,
                     thread_name="%s-%s" % (scene_name, "RGB-D"),
-                    frame_window=None if args.frame_window < 0 else args.frame_window)
+                    frame_window=None if args.frame_window < 0 else args.frame_window,
+                    detection_method=args.detection_method)
     print("GOODBYE!")
     return out
 

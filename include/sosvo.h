@@ -509,6 +509,15 @@ int32_t sosvo_f2f_assemble_central(sosvo_ctx* ctx, double pct_good_matches, doub
                                    const int32_t* order, int32_t npairs, int32_t corr_cap, double* f, double* p,
                                    int32_t* corr_q, int32_t* corr_t, int32_t* n);
 
+/* ---- keypoint detectors of the batch and sequence entry points ------------------------------------
+ * sosvo_batch_cfg.detector, and bits 8-9 of sosvo_rgbd_batch_cfg.flags (SOSVO_RGBD_DETECTOR(d)), select the
+ * feature_detection_method (pose_est_tools.py:684, :477-516).  The RGB-D detector bits never reach the RANSAC flags. */
+enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETECTOR_FAST = 2, SOSVO_DETECTOR_AGAST = 3 };
+#define SOSVO_RGBD_DETECTOR_SHIFT 8
+#define SOSVO_RGBD_DETECTOR_MASK (3 << SOSVO_RGBD_DETECTOR_SHIFT)
+#define SOSVO_RGBD_DETECTOR(d) ((d) << SOSVO_RGBD_DETECTOR_SHIFT)
+#define SOSVO_RGBD_DETECTOR_OF(flags) (((flags) & SOSVO_RGBD_DETECTOR_MASK) >> SOSVO_RGBD_DETECTOR_SHIFT)
+
 /* ---- the whole hot path for a batch of frame pairs (the throughput entry point) ----------------
  * One call = for B independent pairs (frames 2i = reference / keyframe, 2i+1 = current):
  *   OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__ for both frames
@@ -517,7 +526,15 @@ int32_t sosvo_f2f_assemble_central(sosvo_ctx* ctx, double pct_good_matches, doub
  *   midpoint triangulation, range filter), then TrackerStereoSE3.track_frame (pose_est_tools.py:736-847:
  *   frame-to-frame matching per view, |du| gate, stacking, non-central RANSAC, LM on the inliers).
  * It sequences the stage functions above on the context's stream; nothing is allocated and the host is never
- * synchronised.  Detector: GFT (the reference default, pose_est_tools.py:684).
+ * synchronised.  Detector: cfg->detector (enum sosvo_detector; 0 = GFT, the reference default, pose_est_tools.py:684).
+ * Each detector calls exactly the stages the Python ImageFrontEnd calls for it:
+ *   GFT:          sosvo_detect_gft + sosvo_describe_orb_rows (angle cos_a / sin_a); with median_ksize 3 / 5 / 11 the
+ *                 gray rows no consumer can reach are skipped (sosvo_gray_rows_needed)
+ *   ORB:          sosvo_orb_mask_pyramid (rebuilt into the workspace on every call) + sosvo_detect_describe_orb
+ *                 (nfeatures = max_corners, each keypoint's own angle; kp_cap <= 2048)
+ *   FAST / AGAST: sosvo_detect_fast / sosvo_detect_agast (threshold 10) + sosvo_describe_orb (angle cos_a / sin_a)
+ *   ORB, FAST and AGAST compute every gray row.  An unknown detector, or ORB with kp_cap > 2048, is SOSVO_ERR_ARG (and
+ *   a workspace size of 0).
  *   omni         [2B, H, W, 3] u8 BGR (device)
  *   unwrap_table from sosvo_unwrap_prepare (model constant), mask_bits [2, rows, cols] u32 (set 0 = top mirror,
  *                set 1 = bottom mirror), pattern [512, 2] i8 (descriptor test points)
@@ -545,7 +562,7 @@ typedef struct sosvo_batch_cfg {
   uint64_t seed;           /* pair i samples with seed + i */
   float cos_a, sin_a;      /* descriptor orientation given to the GFT keypoints */
   int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P */
-  int32_t reserved;        /* 0 */
+  int32_t detector;        /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg);
@@ -644,7 +661,10 @@ typedef struct sosvo_rgbd_batch_cfg {
   int32_t ransac_adaptive;
   int32_t lm_max_iter;
   int32_t flags;           /* SOSVO_FLAG_EPNP: "EPNP" (6-point samples); 0: "KNEIP" (P3P + 4th point); SOSVO_FLAG_GP3P: "GAO" / "GP3P";
-                              SOSVO_FLAG_TWOPT: "TWOPT" -- passed through to sosvo_ransac_abs_pose */
+                              SOSVO_FLAG_TWOPT: "TWOPT" -- passed through to sosvo_ransac_abs_pose;
+                              bits 8-9: SOSVO_RGBD_DETECTOR(enum sosvo_detector), 0 = GFT (masked off before the solver).
+                              The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
+                              for every frame) */
   double quality, min_distance;        /* 0.01, 5 */
   double ransac_threshold;             /* 1 - cos(5 deg) */
   double pct_good_matches;             /* 1.0 (pose_est_tools.py:225) */

@@ -116,6 +116,13 @@ FLAG_CAM_ROT_IDENTITY = 1
 FLAG_EPNP = 2
 FLAG_GP3P = 4
 FLAG_TWOPT = 8
+DETECTOR_GFT = 0
+DETECTOR_ORB = 1
+DETECTOR_FAST = 2
+DETECTOR_AGAST = 3
+DETECTORS = {"GFT": DETECTOR_GFT, "ORB": DETECTOR_ORB, "FAST": DETECTOR_FAST, "AGAST": DETECTOR_AGAST}
+RGBD_DETECTOR_SHIFT = 8
+RGBD_DETECTOR_MASK = 3 << RGBD_DETECTOR_SHIFT
 REL_FIVEPT = 5
 REL_SEVENPT = 7
 REL_EIGHTPT = 8
@@ -141,7 +148,7 @@ class BatchCfg(ctypes.Structure):
                 ("kp_cap", c_i32), ("frame_cap", c_i32), ("median_ksize", c_i32), ("max_corners", c_i32), ("edge", c_i32),
                 ("ransac_max_iter", c_i32), ("ransac_adaptive", c_i32), ("lm_max_iter", c_i32), ("quality", c_f64),
                 ("min_distance", c_f64), ("ransac_threshold", c_f64), ("seed", c_u64), ("cos_a", c_f32), ("sin_a", c_f32),
-                ("ransac_flags", c_i32), ("reserved", c_i32)]
+                ("ransac_flags", c_i32), ("detector", c_i32)]
 
 
 class RgbdBatchCfg(ctypes.Structure):
@@ -151,6 +158,24 @@ class RgbdBatchCfg(ctypes.Structure):
                 ("ransac_adaptive", c_i32), ("lm_max_iter", c_i32), ("flags", c_i32), ("quality", c_f64),
                 ("min_distance", c_f64), ("ransac_threshold", c_f64), ("pct_good_matches", c_f64), ("f2f_max_hdiff", c_f64),
                 ("seed", c_u64), ("cos_a", c_f32), ("sin_a", c_f32)]
+
+
+def detector_code(method):
+    """feature_detection_method ("GFT", "ORB", "FAST", "AGAST", any case) -> enum sosvo_detector; others raise."""
+    name = str(method).upper()
+    if name not in DETECTORS:
+        raise NotImplementedError("detection method %r: the batched paths run %s" % (method, ", ".join(DETECTORS)))
+    return DETECTORS[name]
+
+
+def rgbd_detector_flags(method):
+    """SOSVO_RGBD_DETECTOR(d): the detector's bits of sosvo_rgbd_batch_cfg.flags."""
+    return detector_code(method) << RGBD_DETECTOR_SHIFT
+
+
+def rgbd_flags_detector(flags):
+    """SOSVO_RGBD_DETECTOR_OF(flags)."""
+    return (int(flags) & RGBD_DETECTOR_MASK) >> RGBD_DETECTOR_SHIFT
 
 
 _lib = None

@@ -19,6 +19,28 @@ struct Carver {
   }
 };
 
+// the ORB detector's extra buffers (sosvo_detect_describe_orb): oriented keypoints, responses, the mask pyramid.  Carved
+// after everything else, and only for ORB, so that the other detectors' workspaces keep their sizes and layout.
+struct OrbBufs {
+  float *kp4 = nullptr, *resp = nullptr;
+  uint32_t* mask_pyr = nullptr;
+};
+OrbBufs carve_orb(Carver& cv, int detector, size_t P, size_t cap, size_t nsets, int rows, int cols) {
+  OrbBufs o;
+  if (detector != SOSVO_DETECTOR_ORB) return o;
+  o.kp4 = cv.take<float>(P * cap * 4);
+  o.resp = cv.take<float>(P * cap);
+  o.mask_pyr = cv.take<uint32_t>(nsets * (size_t)sosvo_orb_pyramid_pixels(rows, cols));
+  return o;
+}
+
+// a detector the batch entry points run, with a capacity its stages accept (sosvo_detect_describe_orb: cap <= 2048)
+bool detector_ok(int detector, int kp_cap) {
+  if (detector == SOSVO_DETECTOR_ORB) return kp_cap <= 2048;
+  return detector == SOSVO_DETECTOR_GFT || detector == SOSVO_DETECTOR_FAST || detector == SOSVO_DETECTOR_AGAST;
+}
+int rgbd_detector(const sosvo_rgbd_batch_cfg& c) { return SOSVO_RGBD_DETECTOR_OF(c.flags); }
+
 struct Buffers {
   uint8_t *pano, *gray, *desc, *d_top, *d_bot, *mask;
   float *kp, *m_top, *m_bot;
@@ -26,6 +48,7 @@ struct Buffers {
       *n_inl, *info, *lm_iters, *gray_rows;
   uint32_t *s_keys, *k_top, *k_bot;
   double *X, *b_top, *b_bot, *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
+  OrbBufs orb;
   size_t bytes;
 };
 
@@ -76,6 +99,7 @@ Buffers carve(const sosvo_batch_cfg& c, void* ws) {
   b.lm_cost = cv.take<double>(B);
   b.lm_iters = cv.take<int32_t>(B);
   b.gray_rows = cv.take<int32_t>(4);
+  b.orb = carve_orb(cv, c.detector, P, cap, 2, c.rows, c.cols);
   b.bytes = cv.off;
   return b;
 }
@@ -129,6 +153,7 @@ struct SeqBuffers {
   int32_t *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx, *n_inl, *info, *lm_iters;
   uint32_t *k_top, *k_bot;
   double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
+  OrbBufs orb;
   size_t bytes;
 };
 
@@ -179,6 +204,7 @@ SeqBuffers carve_seq(const sosvo_batch_cfg& c, int window, int slots, void* ws) 
   b.cam_rot = cv.take<double>(2 * 9);
   b.lm_cost = cv.take<double>(B);
   b.lm_iters = cv.take<int32_t>(B);
+  b.orb = carve_orb(cv, c.detector, P, cap, 2, c.rows, c.cols);
   b.bytes = cv.off;
   return b;
 }
@@ -232,6 +258,7 @@ struct RgbdBuffers {
   int32_t *n, *status, *M, *ref_frame, *cur_frame, *order, *cq, *ct, *cn, *idx, *n_inl, *info, *lm_iters;
   uint32_t* keys;
   double *X, *b, *f, *p, *T_ransac, *T, *lm_cost;
+  OrbBufs orb;
   size_t bytes;
 };
 
@@ -266,6 +293,7 @@ RgbdBuffers carve_rgbd(const sosvo_rgbd_batch_cfg& c, void* ws) {
   b.T = cv.take<double>(B * 12);
   b.lm_cost = cv.take<double>(B);
   b.lm_iters = cv.take<int32_t>(B);
+  b.orb = carve_orb(cv, rgbd_detector(c), F, cap, 1, c.rows, c.cols);
   b.bytes = cv.off;
   return b;
 }
@@ -283,6 +311,7 @@ struct RgbdSeqBuffers {
   int32_t *ref_frame, *cur_frame, *order, *cq, *ct, *cn, *idx, *n_inl, *info, *lm_iters;
   uint32_t* keys;
   double *f, *p, *T_ransac, *T, *lm_cost;
+  OrbBufs orb;
   size_t bytes;
 };
 
@@ -317,6 +346,7 @@ RgbdSeqBuffers carve_rgbd_seq(const sosvo_rgbd_batch_cfg& c, int window, int slo
   b.T = cv.take<double>(B * 12);
   b.lm_cost = cv.take<double>(B);
   b.lm_iters = cv.take<int32_t>(B);
+  b.orb = carve_orb(cv, rgbd_detector(c), F, cap, 1, c.rows, c.cols);
   b.bytes = cv.off;
   return b;
 }
@@ -360,7 +390,7 @@ extern "C" {
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->nmask <= 0 || cfg->kp_cap <= 0 ||
-      cfg->frame_cap <= 0)
+      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap))
     return 0;
   return carve(*cfg, nullptr).bytes;
 }
@@ -379,6 +409,7 @@ struct FrontEndTmp {
   float* kp;
   int32_t *n, *status, *s_order, *n_cand, *gray_rows;
   uint32_t* s_keys;
+  OrbBufs orb;
 };
 struct FrameStore {
   float *m_top, *m_bot;
@@ -393,7 +424,11 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const int h = F * NM;  // problems of one view: (frame, mask); the top view's come first (view-major images)
   int32_t rc;
   if (median_wait) SOSVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, median_wait, 0));
-  const bool rows_known = cfg->median_ksize == 3 || cfg->median_ksize == 5 || cfg->median_ksize == 11;
+  const int det = cfg->detector;
+  const bool fused_median = cfg->median_ksize == 3 || cfg->median_ksize == 5 || cfg->median_ksize == 11;
+  // skipping unreachable rows is exact for GFT only (the range is GFT's reach); ORB, FAST and AGAST see every row, as
+  // ImageFrontEnd computes them
+  const bool rows_known = det == SOSVO_DETECTOR_GFT && fused_median;
   if (rows_known) {
     // rows beyond the reach of GFT on the masks and of ORB.compute on its keypoints are not computed (the range is a
     // model constant; a 2-workgroup kernel per call keeps this entry point free of caller-side state)
@@ -401,7 +436,7 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
                                  t.gray_rows));
     STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cfg->cols, cfg->median_ksize,
                                         t.gray_rows, t.gray));
-  } else if (cfg->median_ksize <= 1) {  // no median: unwrap straight to gray, every row
+  } else if (cfg->median_ksize <= 1 || fused_median) {  // every row (ksize <= 1: unwrap straight to gray)
     STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cfg->cols, cfg->median_ksize,
                                         nullptr, t.gray));
   } else {
@@ -409,10 +444,24 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
     STAGE(sosvo_median_gray(ctx, t.pano, NI, cfg->rows, cfg->cols, cfg->median_ksize, t.gray));
   }
   if (median_done) SOSVO_HIP(ctx, hipEventRecord(median_done, ctx->stream));
-  STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, NI, F, cfg->rows, cfg->cols, NM, cfg->quality, cfg->min_distance,
-                         cfg->max_corners, cap, t.kp, t.n, t.status));
-  STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
-                                cfg->edge, rows_known ? t.gray_rows : nullptr, t.desc));
+  // the stages ImageFrontEnd.run_features calls for the detector (frontend.py), with the same arguments
+  if (det == SOSVO_DETECTOR_ORB) {
+    // the mask pyramid is a model constant, rebuilt here on every call (as gray_rows above) to keep the entry point free of
+    // caller-side state; kp_xy (level-0 x, y of the compacted keypoints) feeds the matching, each keypoint keeps its angle
+    STAGE(sosvo_orb_mask_pyramid(ctx, mask_bits, 2, cfg->rows, cfg->cols, NM, t.orb.mask_pyr));
+    STAGE(sosvo_detect_describe_orb(ctx, t.gray, t.orb.mask_pyr, NI, F, cfg->rows, cfg->cols, NM, cfg->max_corners, cap,
+                                    t.orb.kp4, t.orb.resp, t.n, pattern, t.desc, t.kp));
+  } else if (det == SOSVO_DETECTOR_FAST || det == SOSVO_DETECTOR_AGAST) {
+    STAGE((det == SOSVO_DETECTOR_FAST ? sosvo_detect_fast : sosvo_detect_agast)(ctx, t.gray, mask_bits, NI, F, cfg->rows,
+                                                                                cfg->cols, NM, 10, cap, t.kp, t.n, t.status));
+    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
+                                  cfg->edge, nullptr, t.desc));
+  } else {
+    STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, NI, F, cfg->rows, cfg->cols, NM, cfg->quality, cfg->min_distance,
+                           cfg->max_corners, cap, t.kp, t.n, t.status));
+    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
+                                  cfg->edge, rows_known ? t.gray_rows : nullptr, t.desc));
+  }
   // static stereo per frame: query = bottom view, train = top view, bucket by bucket
   const float *kp_top = t.kp, *kp_bot = t.kp + (size_t)h * cap * 2;
   const uint8_t *desc_top = t.desc, *desc_bot = t.desc + (size_t)h * cap * 32;
@@ -468,6 +517,7 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_REQUIRE(ctx, cfg->n_pairs > 0 && cfg->n_pairs <= 8192, "n_pairs out of range (1..8192)");
   SOSVO_REQUIRE(ctx, cfg->nmask >= 1 && cfg->nmask <= 32 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096, "nmask / kp_cap out of range");
   SOSVO_REQUIRE(ctx, cfg->frame_cap > 0 && cfg->frame_cap <= 16384, "frame_cap out of range (max 16384)");
+  SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const Buffers b = carve(*cfg, workspace);
   SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_frame_pair_batch_workspace)");
@@ -481,7 +531,7 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_LAUNCH(ctx, batch_setup_kernel, dim3(cdiv(B > 18 ? B : 18, 256)), dim3(256), 0, ctx->stream, B, foci, b.ref_frame,
                b.cur_frame, b.cam_off, b.cam_rot);
   SOSVO_LAUNCH_CHECK(ctx);
-  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys};
+  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys, b.orb};
   const FrameStore store{b.m_top, b.m_bot, b.d_top, b.d_bot, b.X, b.b_top, b.b_bot, b.M};
   STAGE(run_front_end(ctx, rig, cfg, F, omni, unwrap_table, mask_bits, pattern, fe, store, median_wait, median_done));
   const TrackTmp tt{b.ref_frame, b.cur_frame, b.o_top, b.o_bot, b.cam, b.cq, b.ct, b.cn, b.cn_top, b.idx, b.n_inl, b.info,
@@ -525,6 +575,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
                              const int8_t* pattern, void* workspace, size_t workspace_bytes, double* results, bool join) {
   SOSVO_REQUIRE(ctx, n_streams >= 1 && n_streams <= kSosvoMaxSubStreams, "n_streams out of range (1..4)");
   SOSVO_REQUIRE(ctx, cfg->n_pairs >= n_streams && cfg->n_pairs <= 8192, "n_pairs out of range (n_streams..8192)");
+  SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const size_t need = sosvo_frame_pair_batch_streams_workspace(cfg, n_streams);
   SOSVO_REQUIRE(ctx, need > 0 && workspace_bytes >= need, "workspace too small (see sosvo_frame_pair_batch_streams_workspace)");
@@ -628,7 +679,7 @@ int32_t sosvo_frame_pair_batch_streams_join(sosvo_ctx* ctx) {
 static bool seq_shape_ok(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
   return cfg && cfg->n_pairs > 0 && cfg->n_pairs <= 8192 && cfg->rows > 0 && cfg->cols > 0 && cfg->nmask >= 1 && cfg->nmask <= 32 &&
          cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384 && window >= 1 && window <= 16384 &&
-         slots >= window && slots <= 65535;
+         slots >= window && slots <= 65535 && detector_ok(cfg->detector, cfg->kp_cap);
 }
 
 size_t sosvo_sequence_workspace(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
@@ -649,7 +700,7 @@ int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sos
   SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_sequence_workspace)");
   if (n_frames == 0) return SOSVO_OK;
   const size_t Fc = cfg->frame_cap, o = (size_t)first_slot * Fc;
-  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys};
+  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys, b.orb};
   const FrameStore out{b.m_top + 2 * o, b.m_bot + 2 * o, b.d_top + 32 * o, b.d_bot + 32 * o,
                        b.X + 3 * o, b.b_top + 3 * o, b.b_bot + 3 * o, b.M + first_slot};
   return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, fe, out, nullptr, nullptr);
@@ -722,16 +773,20 @@ int32_t sosvo_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, 
 }
 
 size_t sosvo_rgbd_pair_batch_workspace(const sosvo_rgbd_batch_cfg* cfg) {
-  if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->kp_cap <= 0 || cfg->frame_cap <= 0) return 0;
+  if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->kp_cap <= 0 || cfg->frame_cap <= 0 ||
+      !detector_ok(rgbd_detector(*cfg), cfg->kp_cap))
+    return 0;
   return carve_rgbd(*cfg, nullptr).bytes;
 }
 
-// RGBDFrame.establish_keypoints for F frames (pose_est_tools.py:600-623): [median,] gray, whole-image GFT (one mask), ORB
-// descriptors, depth back-projection + range filter + bearings -> F frame records at the store pointers.
+// RGBDFrame.establish_keypoints for F frames (pose_est_tools.py:600-623): [median,] gray, whole-image detection (one mask;
+// GFT, ORB, FAST or AGAST), ORB descriptors, depth back-projection + range filter + bearings -> F frame records at the store
+// pointers.
 struct RgbdFrontTmp {
   uint8_t *gray, *desc;
   float* kp;
   int32_t *n, *status;
+  OrbBufs orb;
 };
 struct RgbdStore {
   float* m;
@@ -744,11 +799,22 @@ static int32_t run_rgbd_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, con
                                   const RgbdFrontTmp& t, const RgbdStore& o) {
   const int cap = cfg->kp_cap, Fc = cfg->frame_cap;
   int32_t rc;
+  const int det = rgbd_detector(*cfg);
   STAGE(sosvo_median_gray(ctx, bgr, F, cfg->rows, cfg->cols, cfg->median_ksize, t.gray));
-  STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, F, F, cfg->rows, cfg->cols, 1, cfg->quality, cfg->min_distance,
-                         cfg->max_corners, cap, t.kp, t.n, t.status));
-  STAGE(sosvo_describe_orb(ctx, t.gray, F, cfg->rows, cfg->cols, 1, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern, cfg->edge,
-                           t.desc));
+  if (det == SOSVO_DETECTOR_ORB) {  // (the mask pyramid: a model constant rebuilt per call, as in run_front_end)
+    STAGE(sosvo_orb_mask_pyramid(ctx, mask_bits, 1, cfg->rows, cfg->cols, 1, t.orb.mask_pyr));
+    STAGE(sosvo_detect_describe_orb(ctx, t.gray, t.orb.mask_pyr, F, F, cfg->rows, cfg->cols, 1, cfg->max_corners, cap, t.orb.kp4,
+                                    t.orb.resp, t.n, pattern, t.desc, t.kp));
+  } else {
+    if (det == SOSVO_DETECTOR_FAST || det == SOSVO_DETECTOR_AGAST)
+      STAGE((det == SOSVO_DETECTOR_FAST ? sosvo_detect_fast : sosvo_detect_agast)(ctx, t.gray, mask_bits, F, F, cfg->rows, cfg->cols,
+                                                                                  1, 10, cap, t.kp, t.n, t.status));
+    else
+      STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, F, F, cfg->rows, cfg->cols, 1, cfg->quality, cfg->min_distance,
+                             cfg->max_corners, cap, t.kp, t.n, t.status));
+    STAGE(sosvo_describe_orb(ctx, t.gray, F, cfg->rows, cfg->cols, 1, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern, cfg->edge,
+                             t.desc));
+  }
   STAGE(sosvo_rgbd_assemble(ctx, cam, t.kp, t.desc, t.n, depth, F, cfg->rows, cfg->cols, cap, Fc, o.m, o.d, o.X, o.b, o.M));
   return SOSVO_OK;
 }
@@ -790,6 +856,7 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   SOSVO_REQUIRE(ctx, cfg->n_pairs > 0 && cfg->n_pairs <= 8192, "n_pairs out of range (1..8192)");
   SOSVO_REQUIRE(ctx, cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384,
                 "kp_cap / frame_cap out of range");
+  SOSVO_REQUIRE(ctx, detector_ok(rgbd_detector(*cfg), cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const RgbdBuffers b = carve_rgbd(*cfg, workspace);
   SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_pair_batch_workspace)");
@@ -797,7 +864,7 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   int32_t rc;
   SOSVO_LAUNCH(ctx, pair_index_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, B, b.ref_frame, b.cur_frame);
   SOSVO_LAUNCH_CHECK(ctx);
-  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status};
+  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status, b.orb};
   const RgbdStore store{b.m, b.d, b.X, b.b, b.M};
   STAGE(run_rgbd_front_end(ctx, cam, cfg, F, bgr, depth, mask_bits, pattern, fe, store));
   const RgbdTrackTmp tt{b.ref_frame, b.cur_frame, b.order, b.cq, b.ct, b.cn, b.idx, b.n_inl, b.info, b.lm_iters, b.keys, b.mask,
@@ -808,7 +875,8 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
 // ---- RGB-D sequence mode -------------------------------------------------------------------------------------
 static bool rgbd_seq_shape_ok(const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots) {
   return cfg && cfg->n_pairs > 0 && cfg->n_pairs <= 8192 && cfg->rows > 0 && cfg->cols > 0 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096 &&
-         cfg->frame_cap > 0 && cfg->frame_cap <= 16384 && window >= 1 && window <= 16384 && slots >= window && slots <= 65535;
+         cfg->frame_cap > 0 && cfg->frame_cap <= 16384 && window >= 1 && window <= 16384 && slots >= window && slots <= 65535 &&
+         detector_ok(rgbd_detector(*cfg), cfg->kp_cap);
 }
 
 size_t sosvo_rgbd_sequence_workspace(const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots) {
@@ -829,7 +897,7 @@ int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam,
   SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
   if (n_frames == 0) return SOSVO_OK;
   const size_t Fc = cfg->frame_cap, o = (size_t)first_slot * Fc;
-  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status};
+  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status, b.orb};
   const RgbdStore out{b.m + 2 * o, b.d + 32 * o, b.X + 3 * o, b.b + 3 * o, b.M + first_slot};
   return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, fe, out);
 }

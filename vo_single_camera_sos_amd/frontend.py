@@ -48,6 +48,24 @@ class DeviceImageModel(object):
         self.pattern = torch.from_numpy(self.pattern_host).to(dev)
 
 
+def default_kp_cap(method, num_of_features):
+    """ImageFrontEnd's keypoint capacity per (frame, mirror, mask) when none is given (also the batched engines')."""
+    method = str(method).upper()
+    if method in ("FAST", "AGAST"):  # every corner is kept (num_of_features only names the ORB descriptor object)
+        return 2048
+    if method == "ORB":  # retainBest keeps ties beyond the quota: leave head room
+        return int(min(2048, max(64, -(-int(num_of_features * 1.25) // 64) * 64)))
+    return int(min(1024, max(64, -(-int(num_of_features) // 64) * 64)))
+
+
+def mirror_kp_cap(method, num_of_features):
+    """The per-frame mirror path's capacity (GUMStereo._front_end): what a batched engine must use to compute what
+    StereoPanoramicFrame computes (FAST / AGAST keep the first `cap` corners in raster order, and ORB's retainBest
+    head room changes the output)."""
+    scale = 1.25 if str(method).upper() == "ORB" else 1.0
+    return int(min(4096, max(64, -(-int(num_of_features * scale) // 64) * 64)))
+
+
 class ImageFrontEnd(object):
     def __init__(self, ctx, model, nframes, detection_method="GFT", num_of_features=1000, kp_cap=None,
                  median_win_size=11, quality=0.01, min_distance=5.0, edge=31, keep_panoramas=True,
@@ -63,14 +81,7 @@ class ImageFrontEnd(object):
         self.num_of_features, self.median_win_size = int(num_of_features), int(median_win_size)
         self.quality, self.min_distance, self.edge = float(quality), float(min_distance), int(edge)
         self.skip_unreachable_rows = bool(skip_unreachable_rows)
-        if kp_cap:
-            self.kp_cap = int(kp_cap)
-        elif self.method in ("FAST", "AGAST"):  # every corner is kept (num_of_features only names the ORB descriptor object)
-            self.kp_cap = 2048
-        elif self.method == "ORB":  # retainBest keeps ties beyond the quota: leave head room
-            self.kp_cap = int(min(2048, max(64, -(-int(self.num_of_features * 1.25) // 64) * 64)))
-        else:
-            self.kp_cap = int(min(1024, max(64, -(-self.num_of_features // 64) * 64)))
+        self.kp_cap = int(kp_cap) if kp_cap else default_kp_cap(self.method, self.num_of_features)
         dev, m = ctx.device, model
         NI, P = 2 * self.F, 2 * self.F * m.nmask
         self.omni = torch.zeros((self.F, m.H, m.W, 3), dtype=torch.uint8, device=dev)

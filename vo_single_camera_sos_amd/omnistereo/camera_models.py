@@ -385,15 +385,16 @@ class RGBDCamModel(object):
         from ..runtime import default_context
         return default_context()
 
-    def _front_end(self, shape, num_of_features, median_win_size, min_range, max_range, mask):
-        """One-frame RGBDFrontEnd per (image shape, detector budget, filter) -- buffers are reused across frames."""
+    def _front_end(self, shape, num_of_features, median_win_size, min_range, max_range, mask, method="GFT"):
+        """One-frame RGBDFrontEnd per (image shape, detector, detector budget, filter) -- buffers are reused across
+        frames."""
         from ..pipeline import RGBDCamConfig, RGBDFrontEnd
         key = (tuple(shape), int(num_of_features), int(median_win_size), float(min_range), float(max_range),
-               None if mask is None else id(mask))
+               None if mask is None else id(mask), str(method).upper())
         cache = self.__dict__.setdefault("_front_ends", {})
         if key not in cache:
             cfg = RGBDCamConfig(self.fx, self.fy, self.center_x, self.center_y, self.focal_length_m, self.depth_is_Z,
                                 min_range, max_range)
             cache[key] = RGBDFrontEnd(self._context(), cfg, 1, image_shape=shape, num_of_features=num_of_features,
-                                      median_win_size=median_win_size, mask=mask)
+                                      median_win_size=median_win_size, mask=mask, detection_method=method)
         return cache[key]

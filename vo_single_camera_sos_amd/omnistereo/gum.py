@@ -241,8 +241,8 @@ class GUMStereo(object):
     def _front_end(self, method, num_of_features, median_win_size):
         key = (str(method).upper(), int(num_of_features), int(median_win_size))
         if key not in self._front_ends:
-            from ..frontend import ImageFrontEnd
-            cap = int(min(4096, max(64, -(-int(num_of_features * (1.25 if key[0] == "ORB" else 1.0)) // 64) * 64)))
+            from ..frontend import ImageFrontEnd, mirror_kp_cap
+            cap = mirror_kp_cap(key[0], num_of_features)
             self._front_ends[key] = ImageFrontEnd(self._context(), self._device_model(), 1, detection_method=key[0],
                                                   num_of_features=key[1], kp_cap=cap, median_win_size=key[2])
         return self._front_ends[key]

@@ -411,14 +411,33 @@ class DeviceStereoFrame(StereoPanoramicFrame):
         self.engine.promote(self.slot)
 
 
+BATCHED_DETECTORS = ("GFT", "ORB", "FAST", "AGAST")   # the detection methods the sequence engines run
+
+
+def set_detection_method(tracker, method):
+    """tracker.detection_method = method (None: leave the tracker's own), and the feature matchers bootstrap_tracker built
+    from it follow: the frames detect with their feature_detection_method."""
+    if method is None:
+        return
+    tracker.detection_method = str(method).upper()
+    cm = tracker.camera_model
+    for fm in (getattr(cm, "feature_matcher_for_static_stereo", None), getattr(cm, "feature_matcher_for_motion", None)):
+        if fm is not None:
+            fm.feature_detection_method = tracker.detection_method
+
+
 def sequence_engine_for(tracker, camera_model, first_image, window):
     """The pipeline.SequenceEngine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
     StereoPanoramicFrame compute, or None when the configuration has no batched counterpart (then run_VO keeps the
     per-frame mirror path)."""
+    from ..frontend import mirror_kp_cap
     from ..pipeline import RigConfig, SequenceEngine
     om = camera_model
-    if (tracker.detection_method != "GFT" or tracker.matching_type != "BF" or tracker.k_best_matches != 1
-            or tracker.use_descriptor_radius_match_for_motion):
+    method = str(tracker.detection_method).upper()
+    fm = getattr(om, "feature_matcher_for_static_stereo", None)   # (what StereoPanoramicFrame detects with)
+    if (method not in BATCHED_DETECTORS or tracker.matching_type != "BF" or tracker.k_best_matches != 1
+            or tracker.use_descriptor_radius_match_for_motion
+            or (fm is not None and str(fm.feature_detection_method).upper() != method)):
         return None
     top, bot = om.top_model, om.bot_model
     if not (np.array_equal(tracker.cam_rotations[0], np.identity(3)) and np.array_equal(tracker.cam_rotations[1], np.identity(3))
@@ -433,10 +452,10 @@ def sequence_engine_for(tracker, camera_model, first_image, window):
                     max_range=7.0 * from_m, stereo_min_disp=1.0, stereo_max_hdiff=2.5,
                     f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     nfeat = tracker.num_features_detection_for_static_stereo
-    cap = int(min(4096, max(64, -(-int(nfeat) // 64) * 64)))      # as GUMStereo._front_end (the mirror path's capacity)
+    cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
     # an engine (frame store, pinned staging buffers, scratch) is kept with the rig and reused by later runs with the same
     # settings: building one costs more than tracking a hundred frames
-    key = (int(window), int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
+    key = (method, int(window), int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model))
     cache = om.__dict__.setdefault("_sequence_engines", {})
@@ -446,7 +465,7 @@ def sequence_engine_for(tracker, camera_model, first_image, window):
         eng = cache[key] = SequenceEngine(om._context(), model, rig, window=window, num_of_features=nfeat, kp_cap=cap,
                                           frame_cap=4096, median_win_size=11, thr=tracker.backprojection_score_threshold_3D_to_2D,
                                           max_iter=tracker.max_ransac_iterations_3D_to_2D, adaptive=True,
-                                          lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P")
+                                          lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method)
     else:
         eng.reset()
     return eng
@@ -493,13 +512,14 @@ class RGBDFrame(object):
         first channel as blue, like cv2.COLOR_BGR2GRAY applied to whatever the caller passes, :531)."""
         fm = self.rgbd_camera_model.feature_matcher_for_motion
         method = "GFT" if fm is None else str(fm.feature_detection_method).upper()
-        if method != "GFT":
-            raise NotImplementedError("RGB-D detection method %r: GFT (the trackers' default, pose_est_tools.py:684) is built"
-                                      % method)
+        if method not in BATCHED_DETECTORS:
+            raise NotImplementedError("RGB-D detection method %r: GFT (the trackers' default, pose_est_tools.py:684), ORB, "
+                                      "FAST and AGAST are built" % method)
         nfeat = 50 if fm is None else fm.num_of_features
         self.current_depth = depth
+        # (the depth of a keypoint is read at its truncated pixel, .astype(np.uint) at :611: sosvo_rgbd_assemble)
         fe = self.rgbd_camera_model._front_end(np.asarray(rgb).shape[:2], nfeat, self.median_win_size, self.min_range,
-                                               self.max_range, self.mask)
+                                               self.max_range, self.mask, method)
         fe.load_frames(np.ascontiguousarray(rgb)[None], np.ascontiguousarray(depth, dtype=np.float32)[None])
         fe.run()
         fe.ctx.synchronize()
@@ -552,16 +572,19 @@ def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
     """The pipeline.RGBDSequenceEngine that computes what `tracker` (a TrackerRGBDSE3) and RGBDFrame compute, or None when
     the configuration has no batched counterpart (then run_VO keeps the per-frame mirror path)."""
     from ..pipeline import RGBDCamConfig, RGBDSequenceEngine
-    if (tracker.detection_method != "GFT" or tracker.matching_type != "BF" or tracker.k_best_matches != 1
-            or tracker.use_descriptor_radius_match_for_motion):
-        return None
     cm = camera_model
+    method = str(tracker.detection_method).upper()
+    fm = getattr(cm, "feature_matcher_for_motion", None)   # (what RGBDFrame detects with)
+    if (method not in BATCHED_DETECTORS or tracker.matching_type != "BF" or tracker.k_best_matches != 1
+            or tracker.use_descriptor_radius_match_for_motion
+            or (fm is not None and str(fm.feature_detection_method).upper() != method)):
+        return None
     cam = RGBDCamConfig(cm.fx, cm.fy, cm.center_x, cm.center_y, cm.focal_length_m, cm.depth_is_Z, 0.8, 7.0,
                         f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     shape = tuple(int(v) for v in np.asarray(first_rgb).shape[:2])
     # (as sequence_engine_for: the engine -- frame store, 136 MB of pinned staging buffers, scratch -- stays with the camera
     # model and serves later runs with the same settings; building one costs 15 ms, a 128-frame run 45)
-    key = (int(window), shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
+    key = (method, int(window), shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
            float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z))
@@ -573,7 +596,8 @@ def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
                                               num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                                               thr=tracker.backprojection_score_threshold_3D_to_2D,
                                               max_iter=tracker.max_ransac_iterations_3D_to_2D, adaptive=True,
-                                              lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm)
+                                              lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
+                                              detection_method=method)
     else:
         eng.reset()
     return eng
@@ -797,7 +821,7 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
 
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
-           _live_frames=None, _keyframe_thresholds=None, frame_window=None):
+           _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -810,7 +834,9 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     their predecessors, serially against the keyframe where that guess fails).  None = 32 for an image sequence, 1 for a
     live source; 0 = the per-frame mirror path (StereoPanoramicFrame on host arrays, one set of C-ABI calls per stage).
     The pose file does not depend on the window size (byte-identical for 1, 2, 32, ...); the mirror path agrees with
-    it to rounding (its bearings go through numpy's trigonometry, the store's through the library's)."""
+    it to rounding (its bearings go through numpy's trigonometry, the store's through the library's).
+
+    detection_method: "GFT", "ORB", "FAST" or "AGAST" for the tracker and its frames; None = the tracker's own (GFT)."""
     from .common_cv import get_depthmap_float32_from_png, get_images, imread
     from .common_tools import get_poses_from_file
     if visualizer_3D_VO is not None:
@@ -896,6 +922,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         img_indices = [0]
         frames = _live_frames
     tracker = trackerClass(camera_model=camera_model, show_3D_points=False, results_path=results_path)
+    set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1079,7 +1106,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
-                results_path="~/temp", thread_name="", frame_window=None):
+                results_path="~/temp", thread_name="", frame_window=None, detection_method=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1099,11 +1126,12 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
             idx += 1
     return run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename=est_poses_filename,
                   results_path=results_path, thread_name=thread_name, _live_frames=frames,
-                  _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window)
+                  _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
+                  detection_method=detection_method)
 
 
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
-                   thread_name="LIVE", frame_window=None):
+                   thread_name="LIVE", frame_window=None, detection_method=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1121,7 +1149,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
             time.sleep(0.001)   # (the reference starts tracking at once and stops if no frame has arrived yet)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, cam_working_thread=cam_working_thread,
                   est_poses_filename=est_poses_filename, results_path=scene_path_vo_results, thread_name=thread_name,
-                  frame_window=frame_window)
+                  frame_window=frame_window, detection_method=detection_method)
     result, failure = {}, []
     try:
         if use_multithreads_for_VO:
@@ -1146,7 +1174,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
 
 def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filename_template, depth_filename_template,
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
-              last_image_index=-1, thread_name="", frame_window=None):
+              last_image_index=-1, thread_name="", frame_window=None, detection_method=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1169,7 +1197,8 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
                   est_poses_filename=est_poses_filename, img_filename_template=scene_img_filename_template,
                   depth_filename_template=depth_filename_template, img_indices=vo_frame_indices,
-                  results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window)
+                  results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window,
+                  detection_method=detection_method)
     result = {}
     if use_multithreads_for_VO:
         # one libsosvo context per host thread: the worker creates its own

@@ -319,13 +319,18 @@ class FramePairBatch(object):
 
     def __init__(self, ctx, model, rig, n_pairs, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
-                 n_streams=1, ransac_solver="P3P"):
-        """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library)."""
+                 n_streams=1, ransac_solver="P3P", detection_method="GFT"):
+        """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
+        detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
+        default capacity (frontend.default_kp_cap)."""
         from . import _lib, orb_pattern
+        from .frontend import default_kp_cap
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
+        detector = _lib.detector_code(detection_method)
+        self.method = str(detection_method).upper()
         if kp_cap is None:
-            kp_cap = int(min(1024, max(64, -(-int(num_of_features) // 64) * 64)))
+            kp_cap = default_kp_cap(self.method, num_of_features)
         cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         c = _lib.BatchCfg()
         c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = self.B, model.H, model.W, model.rows, model.cols, model.nmask
@@ -335,7 +340,7 @@ class FramePairBatch(object):
         c.quality, c.min_distance = float(quality), float(min_distance)
         c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
         c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
-        c.ransac_flags, c.reserved = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), 0
+        c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
         self.cfg = c
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -586,15 +591,19 @@ class SequenceEngine(_SequenceBase):
 
     def __init__(self, ctx, model, rig, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 ransac_solver="GP3P"):
+                 ransac_solver="GP3P", detection_method="GFT"):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
-        compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations)."""
+        compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
+        detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch."""
         from . import _lib, orb_pattern
+        from .frontend import default_kp_cap
         assert isinstance(ctx, Context)
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
+        detector = _lib.detector_code(detection_method)
+        self.method = str(detection_method).upper()
         self._init_windows(window)
         if kp_cap is None:
-            kp_cap = int(min(1024, max(64, -(-int(num_of_features) // 64) * 64)))
+            kp_cap = default_kp_cap(self.method, num_of_features)
         cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         c = _lib.BatchCfg()
         c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = self.W, model.H, model.W, model.rows, model.cols, model.nmask
@@ -606,7 +615,7 @@ class SequenceEngine(_SequenceBase):
         c.seed, c.cos_a, c.sin_a = 0, float(cos_a), float(sin_a)
         if str(ransac_solver).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
-        c.ransac_flags, c.reserved = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), 0
+        c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
         self.cfg = c
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -676,22 +685,37 @@ class RGBDCamConfig(object):
         return c
 
 
+def rgbd_kp_cap(method, num_of_features):
+    """The RGB-D front ends' keypoint capacity per frame (RGBDFrontEnd, the engines, RGBDFrame): GFT > 1024 selects the
+    detector's whole-image variant; ORB leaves retainBest head room (<= 2048, sosvo_detect_describe_orb); FAST / AGAST keep
+    every corner up to the batch entry points' limit, 4096 (the first in raster order beyond it)."""
+    method = str(method).upper()
+    if method in ("FAST", "AGAST"):
+        return 4096
+    if method == "ORB":
+        return int(min(2048, max(64, -(-int(num_of_features * 1.25) // 64) * 64)))
+    return int(min(4096, max(1088, -(-int(num_of_features) // 64) * 64)))
+
+
 class RGBDFrontEnd(object):
     """RGBDFrame.establish_keypoints (pose_est_tools.py:600-623) for F frames at once: [median,] gray,
-    goodFeaturesToTrack on the whole image (or RGBDFrame.mask), ORB descriptors, depth back-projection, NaN / range
-    filter, bearings.  All buffers in HBM; four asynchronous C-ABI calls."""
+    detection on the whole image (or RGBDFrame.mask) -- goodFeaturesToTrack, ORB, FAST or AGAST (:477-516) --, ORB
+    descriptors, depth back-projection, NaN / range filter, bearings.  All buffers in HBM; four asynchronous C-ABI
+    calls (three for ORB)."""
 
     def __init__(self, ctx, cam, nframes, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
-                 median_win_size=0, quality=0.01, min_distance=5.0, edge=31, mask=None):
-        from . import orb_pattern
+                 median_win_size=0, quality=0.01, min_distance=5.0, edge=31, mask=None, detection_method="GFT"):
+        from . import _lib, orb_pattern
         assert isinstance(ctx, Context)
+        _lib.detector_code(detection_method)   # (raises for the detectors that are not built)
+        self.method = str(detection_method).upper()
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.F = int(nframes)
         self.rows, self.cols = int(image_shape[0]), int(image_shape[1])
         self.num_of_features, self.median_win_size = int(num_of_features), int(median_win_size)
         self.quality, self.min_distance, self.edge = float(quality), float(min_distance), int(edge)
-        # > 1024 selects the detector's large-mask variant (whole-image masks), see sosvo_detect_gft
-        self.kp_cap = int(kp_cap) if kp_cap else int(min(4096, max(1088, -(-self.num_of_features // 64) * 64)))
+        # GFT: > 1024 selects the detector's large-mask variant (whole-image masks), see sosvo_detect_gft
+        self.kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(self.method, self.num_of_features)
         self.frame_cap = int(frame_cap) if frame_cap else self.kp_cap
         dev, F = ctx.device, self.F
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
@@ -705,6 +729,9 @@ class RGBDFrontEnd(object):
         self.cos_a, self.sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         self.kp, self.n = z((F, self.kp_cap, 2), torch.float32), z((F,), torch.int32)
         self.status, self.desc = z((F,), torch.int32), z((F, self.kp_cap, 32), torch.uint8)
+        if self.method == "ORB":
+            self.kp4, self.resp = z((F, self.kp_cap, 4), torch.float32), z((F, self.kp_cap), torch.float32)
+            self.mask_pyr = ctx.orb_mask_pyramid(self.mask_bits, 1)   # once per mask
         Fc = self.frame_cap
         self.frames = dict(m=z((F, Fc, 2), torch.float32), d=z((F, Fc, 32), torch.uint8), X=z((F, Fc, 3), torch.float64),
                            b=z((F, Fc, 3), torch.float64), M=z((F,), torch.int32))
@@ -719,11 +746,20 @@ class RGBDFrontEnd(object):
     def run(self):
         c = self.ctx
         c.median_gray(self.bgr, self.median_win_size, gray=self.gray)                              # :528, :531
-        c.detect_gft(self.gray, self.mask_bits, self.F, 1, self.kp_cap, quality=self.quality,
-                     min_distance=self.min_distance, max_corners=self.num_of_features, kp=self.kp, n=self.n,
-                     status=self.status)                                                            # :544
-        c.describe_orb(self.gray, self.kp, self.n, 1, self.pattern, self.cos_a, self.sin_a, edge=self.edge,
-                       desc=self.desc)                                                              # :553
+        if self.method == "ORB":                                                                   # :478, :547, :553
+            c.detect_describe_orb(self.gray, self.mask_pyr, self.F, 1, self.num_of_features, self.pattern, self.kp4,
+                                  self.resp, self.n, self.desc, kp_xy=self.kp)
+        else:
+            if self.method in ("FAST", "AGAST"):                                                  # :506-509, :547
+                (c.detect_fast if self.method == "FAST" else c.detect_agast)(
+                    self.gray, self.mask_bits, self.F, 1, self.kp_cap, threshold=10, kp=self.kp, n=self.n,
+                    status=self.status)
+            else:
+                c.detect_gft(self.gray, self.mask_bits, self.F, 1, self.kp_cap, quality=self.quality,
+                             min_distance=self.min_distance, max_corners=self.num_of_features, kp=self.kp, n=self.n,
+                             status=self.status)                                                    # :544
+            c.describe_orb(self.gray, self.kp, self.n, 1, self.pattern, self.cos_a, self.sin_a, edge=self.edge,
+                           desc=self.desc)                                                          # :553
         c.rgbd_assemble(self.cam, self.kp, self.desc, self.n, self.depth, self.frame_cap, out=self.frames)  # :609-623
 
 
@@ -735,8 +771,9 @@ class RGBDPairPipeline(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP"):
-        """pose_est_algorithm: TrackerSE3.pose_est_algorithm (pose_est_tools.py:697): "EPNP" = 6-point samples solved by
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+        """detection_method: "GFT", "ORB", "FAST" or "AGAST" (RGBDFrontEnd).
+        pose_est_algorithm: TrackerSE3.pose_est_algorithm (pose_est_tools.py:697): "EPNP" = 6-point samples solved by
         EPnP; "KNEIP" = P3P on 3 points + a 4th for disambiguation; "GAO" / "GP3P" = the depth formulation through the
         generalised solver; "TWOPT" = translation from 2 points.  Anything else raises ValueError."""
         from . import _lib
@@ -745,7 +782,7 @@ class RGBDPairPipeline(object):
         self.epnp = bool(self.solver_flags & _lib.FLAG_EPNP)
         self.B, self.F = int(n_pairs), 2 * int(n_pairs)
         fe = RGBDFrontEnd(ctx, cam, self.F, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                          min_distance, edge, mask)
+                          min_distance, edge, mask, detection_method=detection_method)
         self.front_end, self.frames, self.kp_cap, self.frame_cap = fe, fe.frames, fe.kp_cap, fe.frame_cap
         self.n, self.status, self.kp, self.desc, self.gray = fe.n, fe.status, fe.kp, fe.desc, fe.gray
         self.thr = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
@@ -806,18 +843,20 @@ class RGBDPairBatch(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP"):
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
         from . import _lib, orb_pattern
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         rows, cols = int(image_shape[0]), int(image_shape[1])
-        kp_cap = int(kp_cap) if kp_cap else int(min(4096, max(1088, -(-int(num_of_features) // 64) * 64)))
+        detector_flags = _lib.rgbd_detector_flags(detection_method)
+        self.method = str(detection_method).upper()
+        kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(self.method, num_of_features)
         cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         c = _lib.RgbdBatchCfg()
         c.n_pairs, c.rows, c.cols, c.kp_cap, c.frame_cap = self.B, rows, cols, kp_cap, int(frame_cap) if frame_cap else kp_cap
         c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
         c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.flags = rgbd_solver_flags(pose_est_algorithm)
+        c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
         c.quality, c.min_distance = float(quality), float(min_distance)
         c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
         c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
@@ -857,19 +896,21 @@ class RGBDSequenceEngine(_SequenceBase):
 
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 mask=None, pose_est_algorithm="EPNP"):
+                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
         from . import _lib, orb_pattern
         assert isinstance(ctx, Context)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
+        detector_flags = _lib.rgbd_detector_flags(detection_method)
+        self.method = str(detection_method).upper()
         self._init_windows(window)
         rows, cols = int(image_shape[0]), int(image_shape[1])
-        kp_cap = int(kp_cap) if kp_cap else int(min(4096, max(1088, -(-int(num_of_features) // 64) * 64)))
+        kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(self.method, num_of_features)
         cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         c = _lib.RgbdBatchCfg()
         c.n_pairs, c.rows, c.cols, c.kp_cap, c.frame_cap = self.W, rows, cols, kp_cap, int(frame_cap) if frame_cap else kp_cap
         c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
         c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.flags = rgbd_solver_flags(pose_est_algorithm)
+        c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
         c.quality, c.min_distance = float(quality), float(min_distance)
         c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
         c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
