@@ -595,8 +595,11 @@ int32_t sosvo_frame_pair_batch_streams(sosvo_ctx* ctx, const sosvo_rig* rig_host
  *     (and the model tables) of an un-joined call must not be overwritten on the context's stream -- double-buffer the
  *     frames or join first.
  * The workspace may be the same for every call: part s of every call uses the same slice on the same internal stream.
- * That holds only for the same split, so a call whose (n_pairs, n_streams) differ from the un-joined previous call's joins
- * internally first (correct, but without the overlap).  A call made while the context's stream is being captured into a
+ * That holds only for the same slice layout: part s's slice starts at workspace + the sizes of parts 0 .. s - 1, and a
+ * part's size depends on the whole cfg (detector, kp_cap, nmask, frame_cap, rows / cols, H / W, median_ksize, its pairs).
+ * So a call whose workspace pointer, n_streams or any part's size differ from the un-joined previous call's joins
+ * internally first (correct, but without the overlap): changing the detector or a capacity between calls on one context
+ * is safe, it only costs the overlap of that one call.  A call made while the context's stream is being captured into a
  * HIP graph fails with SOSVO_ERR_ARG while un-joined work is pending (join before capturing); after a join -- or after the
  * joined form sosvo_frame_pair_batch_streams -- every call is self-contained and capturable. */
 int32_t sosvo_frame_pair_batch_streams_enqueue(sosvo_ctx* ctx, const sosvo_rig* rig_host, const sosvo_batch_cfg* cfg_host,

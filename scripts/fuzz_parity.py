@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Differential fuzzing of the stage entry points against the CPU oracle (test infrastructure: the oracle is the checker).
 
-    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd]
+    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch]
 
 Every case draws its own sizes and parameters (image sizes around the strip / chunk / tile borders of the kernels, ragged
 problem counts, empty masks, fractional minimum distances, budgets that end a selection inside a round, duplicate
 descriptors, ...) from a generator seeded by (--seed, case number), runs the HIP stage through the C ABI and compares the
 result with the oracle's bit for bit.  The first mismatch stops the run and prints the stage, the case number and the drawn
 parameters: `--stages <stage> --first-case <n> --cases 1` with the same seed replays it.  Prints a progress line every ~20 s.
-A case that only trips a documented capacity (status flags) counts as `flagged`, not as a mismatch.
+A case that only trips a documented capacity (status flags, a frame_cap cut) counts as `flagged`, not as a mismatch.  A
+draw the entry point refuses, or a stage that ends short of --cases (or with no case at all) when time runs out, makes the
+run end INCOMPLETE with exit status 2: only a run in which every stage completed its cases ends "all identical".
 """
 import argparse
 import os
@@ -23,6 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle  # noqa: E402
+from oracle import flow  # noqa: E402
 from vo_single_camera_sos_amd import orb_pattern  # noqa: E402
 from vo_single_camera_sos_amd.device import Context, SosvoError  # noqa: E402
 
@@ -512,65 +515,309 @@ def fuzz_pipeline(ctx, rng):
     return params, ("flagged" if flagged else None)
 
 
-def fuzz_rgbd(ctx, rng):
-    """The RGB-D (perspective) path behind ONE C-ABI call (sosvo_rgbd_pair_batch) on small random frames -- textures shifted
-    between the frames of a pair, depth maps with holes / NaN / out-of-range values, both depth conventions, all solvers,
-    an optional median window -- against the reference's control flow on the oracle (tests/refflow.py)."""
+def _carved(ws, takes):
+    """Host views of buffers a batch entry point leaves in its workspace: `takes` lists (name, count, dtype) in the order
+    carve() / carve_rgbd() of pipeline.hip take them, each slice rounded up to 256 bytes, up to the last one wanted.  (A
+    layout that drifted from the library's reads the random bytes the workspace was filled with: a mismatch, not a pass.)"""
+    off, spans = 0, []
+    for name, count, dt in takes:
+        nb = int(count) * np.dtype(dt).itemsize
+        spans.append((name, off, nb, dt))
+        off += (nb + 255) & ~255
+    host = ws[:off].cpu().numpy()
+    return {name: host[o:o + nb].view(dt) for name, o, nb, dt in spans}
+
+
+DETECTORS = ("GFT", "ORB", "FAST", "AGAST")
+MEDIANS = (0, 1, 3, 5, 11)
+BATCH_WIDTHS = (360, 480, 600, 720, 960, 1200)
+BATCH_AZIMUTHS = (120.0, 45.0, 30.0, 15.0, 11.25)     # 3, 8, 12, 24, 32 azimuthal masks per mirror (32: the most a model holds)
+
+
+def draw_batch(rng):
+    """The parameters of one `batch` case (no GPU): a legal sosvo_batch_cfg for every detector.  GFT keeps at most 1024
+    corners wanted (max_corners <= 1000) and minimum distances below the ~30 px at which the third-of-a-cell overflow list
+    can fill, so its only documented overflow is the candidate budget (status bit 0)."""
+    det = str(rng.choice(DETECTORS))
+    d = dict(detector=det, median=int(rng.choice(MEDIANS)), width=int(rng.choice(BATCH_WIDTHS)),
+             azimuth=float(rng.choice(BATCH_AZIMUTHS)), n_pairs=int(rng.integers(1, 6)),
+             frame_cap=int(rng.choice([48, 256, 2048])), quality=0.01, min_distance=5.0,
+             solver=str(rng.choice(["P3P", "GP3P"])), max_iter=int(rng.choice([10, 100, 400])), adaptive=bool(rng.integers(0, 2)),
+             pattern=str(rng.choice(["opencv", "seeded"])), seed=int(rng.integers(0, 2 ** 31)))
+    if det == "GFT":
+        d["kp_cap"] = int(rng.choice([16, 64, 256, 1024, 1088, 2048]))
+        d["max_corners"] = int(rng.choice([7, 50, 300, 1000]))
+        d["quality"] = float(10 ** rng.uniform(-3, -0.5))
+        d["min_distance"] = float(rng.choice([0.7, 1.0, 2.5, 5.0, 7.5, 12.0]))
+    elif det == "ORB":
+        d["kp_cap"] = int(rng.choice([16, 64, 256, 1024, 2048]))
+        d["max_corners"] = int(rng.choice([10, 60, 250, 1000, 2500]))
+    else:
+        d["kp_cap"] = int(rng.choice([16, 64, 512, 2048, 4096]))
+        d["max_corners"] = int(rng.choice([50, 1000]))
+    d["n_streams"] = int(rng.integers(1, min(4, d["n_pairs"]) + 1))
+    d["frames"] = [(int(rng.integers(0, _POOL_PAIRS)), int(rng.integers(0, 5)), int(rng.integers(0, 2 ** 31)))
+                   for _ in range(d["n_pairs"])]
+    return d
+
+
+_POOL_PAIRS = 4
+_BATCH_CACHE = {}
+
+
+def _batch_model(ctx, width, azimuth):
+    """(DeviceImageModel, rig kwargs, host tables) of the synthetic rig at one panorama width and mask count, built once per
+    process; the omni frames (rendered once) do not depend on either."""
+    from vo_single_camera_sos_amd import synthetic
+    from vo_single_camera_sos_amd.frontend import DeviceImageModel
+    from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
+    from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
+    key = (width, azimuth)
+    if key not in _BATCH_CACHE:
+        gs = synthetic_gums()
+        for m in (gs.top_model, gs.bot_model):
+            m.panorama = Panorama(m, width=width)
+        gs.make_annulus_masks((480, 640))
+        if "omni" not in _BATCH_CACHE:
+            _BATCH_CACHE["omni"] = synthetic.make_frame_pairs(gs, _POOL_PAIRS, seed=5150)[0]
+        model = DeviceImageModel(ctx, gs, (480, 640), azimuth_mask_degrees=azimuth)
+        model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        pano = gs.top_model.panorama
+        geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
+        rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
+                      max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
+                      pct_good_matches=1.0)
+        host = (model.map_x.cpu().numpy(), model.map_y.cpu().numpy(), model.omni_masks.cpu().numpy())
+        _BATCH_CACHE[key] = (model, rig_kw, host)
+    return _BATCH_CACHE[key]
+
+
+def _perturb(omni_pair, kind, seed):
+    """a pooled frame pair, perturbed: 0 as rendered, 1 noise, 2 the current frame shifted, 3 a black frame, 4 a saturated one"""
+    r = np.random.default_rng(seed)
+    pair = omni_pair.copy()
+    if kind == 1:
+        pair = np.clip(pair.astype(np.int16) + r.normal(0, r.uniform(1, 8), pair.shape).round().astype(np.int16), 0, 255).astype(np.uint8)
+    elif kind == 2:
+        pair[1] = np.roll(pair[1], (int(r.integers(-6, 7)), int(r.integers(-6, 7))), axis=(0, 1))
+    elif kind == 3:
+        pair[int(r.integers(0, 2))] = 0
+    elif kind == 4:
+        pair[int(r.integers(0, 2))] = 255
+    return pair
+
+
+def fuzz_batch(ctx, rng):
+    """The omni one-call batch (sosvo_frame_pair_batch: unwrap, median, detection with any of the four detectors,
+    descriptors, static stereo, frame-to-frame matching, RANSAC, LM) driven from rendered frames, on a dirty workspace,
+    against the reference's control flow on the oracle (oracle/flow.py, tests/refflow.py): every pair's record, inlier mask and stereo point
+    counts bit for bit; the same batch through sosvo_frame_pair_batch_streams gives the same records."""
+    import ctypes
     import refflow
-    from vo_single_camera_sos_amd.pipeline import RGBDCamConfig, RGBDPairBatch
-    B = int(rng.integers(1, 4))
-    rows, cols = int(rng.integers(80, 200)), int(rng.integers(100, 320))
-    nfeat = int(rng.choice([50, 400, 2000]))
-    algo = str(rng.choice(["EPNP", "KNEIP", "GP3P", "TWOPT"]))
-    depth_is_Z = bool(rng.integers(0, 2))
-    ksize = int(rng.choice([0, 0, 3, 5]))
-    max_iter, adaptive, seed = int(rng.choice([20, 200])), bool(rng.integers(0, 2)), int(rng.integers(0, 2 ** 31))
-    thr = float(rng.choice([1.0 - np.cos(np.deg2rad(5.0)), 1.0 - np.cos(np.deg2rad(0.5))]))
-    fx, fy, cx, cy = 0.8 * cols, 0.8 * cols, 0.5 * cols - 0.5, 0.5 * rows - 0.5
-    params = dict(B=B, rows=rows, cols=cols, nfeat=nfeat, algo=algo, depth_is_Z=depth_is_Z, ksize=ksize, max_iter=max_iter,
-                  adaptive=adaptive, seed=seed, thr=thr)
+    from vo_single_camera_sos_amd import _lib
+    from vo_single_camera_sos_amd.pipeline import RigConfig
+    d = draw_batch(rng)
+    params = {k: v for k, v in d.items() if k != "frames"}
+    model, rig_kw, (mx, my, om) = _batch_model(ctx, d["width"], d["azimuth"])
+    B, NM = d["n_pairs"], model.nmask
+    params["nmask"], params["rows"], params["cols"] = NM, model.rows, model.cols
+    pool = _BATCH_CACHE["omni"]
+    omni = np.concatenate([_perturb(pool[2 * i:2 * i + 2], k, sd) for i, k, sd in d["frames"]])
+    pat_host = orb_pattern.orb_pattern(d["pattern"])
+    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    c = _lib.BatchCfg()
+    c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = B, model.H, model.W, model.rows, model.cols, NM
+    c.kp_cap, c.frame_cap, c.median_ksize, c.max_corners, c.edge = d["kp_cap"], d["frame_cap"], d["median"], d["max_corners"], 31
+    c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = d["max_iter"], int(d["adaptive"]), 30
+    c.quality, c.min_distance = d["quality"], d["min_distance"]
+    thr = float(1.0 - np.cos(np.deg2rad(5.0)))
+    c.ransac_threshold, c.seed, c.cos_a, c.sin_a = thr, d["seed"], float(ca), float(sa)
+    c.ransac_flags, c.detector = (_lib.FLAG_GP3P if d["solver"] == "GP3P" else 0), _lib.DETECTORS[d["detector"]]
+    rig = RigConfig(**rig_kw).as_struct()
+    t_omni, t_pat = _dev(ctx, omni, pat_host)
+    ws = torch.empty((ctx.frame_pair_batch_workspace(c),), dtype=torch.uint8, device=ctx.device)
+    ws.fill_(int(rng.integers(0, 256)))
+    ctx.debug_fill_scratch(int(rng.integers(0, 256)))
+    rec = ctx.frame_pair_batch(rig, c, t_omni, model.unwrap_table, model.mask_bits, t_pat, ws)
+    ctx.synchronize()
+    rec = rec.cpu().numpy()
+    # the same batch split over internal streams (n_streams = 1 included), on its own dirty workspace
+    ns = d["n_streams"]
+    ws2 = torch.empty((ctx.frame_pair_batch_streams_workspace(c, ns),), dtype=torch.uint8, device=ctx.device)
+    ws2.fill_(int(rng.integers(0, 256)))
+    rec2 = torch.full((B, 16), float("nan"), dtype=torch.float64, device=ctx.device)
+    cp = lambda x: ctypes.cast(ctypes.pointer(x), ctypes.c_void_p)  # noqa: E731
+    ctx._call(ctx._lib.sosvo_frame_pair_batch_streams, cp(rig), cp(c), ns, t_omni.data_ptr(), model.unwrap_table.data_ptr(),
+              model.mask_bits.data_ptr(), t_pat.data_ptr(), ws2.data_ptr(), ws2.numel(), rec2.data_ptr())
+    ctx.synchronize()
+    if not np.array_equal(rec2.cpu().numpy().view(np.uint64), rec.view(np.uint64)):
+        return params, "n_streams %d: records differ from the single call's" % ns
+    F, Fc = 2 * B, d["frame_cap"]
+    NI, P, cap, Cc = 2 * F, 2 * F * NM, d["kp_cap"], 2 * Fc
+    w = _carved(ws, [("gray", NI * model.rows * model.cols, np.uint8), ("kp", P * cap * 2, np.float32), ("n", P, np.int32),
+                     ("status", P, np.int32), ("desc", P * cap * 32, np.uint8), ("s_keys", P // 2 * cap, np.uint32),
+                     ("s_order", P // 2 * cap, np.int32), ("m_top", F * Fc * 2, np.float32), ("m_bot", F * Fc * 2, np.float32),
+                     ("d_top", F * Fc * 32, np.uint8), ("d_bot", F * Fc * 32, np.uint8), ("X", F * Fc * 3, np.float64),
+                     ("b_top", F * Fc * 3, np.float64), ("b_bot", F * Fc * 3, np.float64), ("M", F, np.int32),
+                     ("n_cand", F, np.int32), ("ref_frame", B, np.int32), ("cur_frame", B, np.int32),
+                     ("k_top", B * Fc, np.uint32), ("k_bot", B * Fc, np.uint32), ("o_top", B * Fc, np.int32),
+                     ("o_bot", B * Fc, np.int32), ("f", B * Cc * 3, np.float64), ("p", B * Cc * 3, np.float64),
+                     ("cam", B * Cc, np.int32), ("cq", B * Cc, np.int32), ("ct", B * Cc, np.int32), ("cn", B, np.int32),
+                     ("cn_top", B, np.int32), ("T_ransac", B * 12, np.float64), ("mask", B * Cc, np.uint8)])
+    status = w["status"].reshape(NI, NM)
+    M, mask = w["M"], w["mask"].reshape(B, Cc)
+    im = refflow.ImageModel(mx, my, om, model.mask_bits_host, NM, d["max_corners"], pat_host, ca, sa, median_ksize=d["median"],
+                            quality=d["quality"], min_distance=d["min_distance"], method=d["detector"], kp_cap=cap)
+    rp = refflow.RigParams(**rig_kw)
+    flagged = False
+    for i in range(B):
+        skip = False
+        frames = []
+        for f in (2 * i, 2 * i + 1):
+            imgs = (f, F + f)     # view-major images: top mirror of frame f, bottom mirror of frame f
+            if d["detector"] == "GFT" and status[list(imgs)].any():
+                skip = True       # the candidate budget overflowed (status bit 0): which candidates were kept is not defined
+            if d["detector"] == "AGAST":
+                for v, img in enumerate(imgs):
+                    pano = oracle.unwrap(omni[f], om[v], mx[v], my[v])
+                    over = int((oracle.fast_score_map(oracle.median_gray(pano, d["median"]), 10) > 0).sum()) > 16384
+                    if bool((status[img] & 2).any()) != over or (over and not (status[img] & 2).all()):
+                        return params, "pair %d frame %d view %d: AGAST overflow flag (%s, oracle %s)" % (i, f, v, status[img].tolist(), over)
+                    skip |= over  # more than 16384 FAST corners before AGAST's suppression: the rest is dropped (sosvo.h)
+            if not skip:     # refflow.frame_from_image on the detection flow of oracle/flow.py
+                (kt, dt, _, _), (kb, db, _, _) = flow.detect_view(im, omni[f], 0), flow.detect_view(im, omni[f], 1)
+                frames.append(refflow.stereo_frame(rp, kt, kb, dt, db))
+        if skip:
+            flagged = True
+            continue
+        for k, fr in enumerate(frames):
+            if len(fr["X"]) > Fc:
+                flagged = True     # more stereo points than the frame store holds: the first frame_cap in order are kept (sosvo.h)
+                frames[k] = {key: (v[:Fc] if key not in ("n_cand", "n_kp_top", "n_kp_bot") else v) for key, v in fr.items()}
+        ref, cur = frames
+        if M[2 * i] != len(ref["X"]) or M[2 * i + 1] != len(cur["X"]):
+            return params, "pair %d: stereo points (%d %d, oracle %d %d)" % (i, M[2 * i], M[2 * i + 1], len(ref["X"]), len(cur["X"]))
+        wt = refflow.track_pair(rp, ref, cur, thr, d["max_iter"], seed=d["seed"] + i, adaptive=d["adaptive"], gp3p=d["solver"] == "GP3P")
+        n = len(wt["corr"]["cam"])
+        want = np.concatenate([np.asarray(wt["T"], np.float64).reshape(12), [wt["ransac"]["n_inliers"], n, wt["ransac"]["status"],
+                                                                             wt["ransac"]["best_iter"]]])
+        if not np.array_equal(rec[i].view(np.uint64), want.view(np.uint64)):
+            return params, "pair %d: record %s, oracle %s" % (i, rec[i, 12:].tolist(), want[12:].tolist())
+        if not np.array_equal(mask[i, :n].astype(bool), wt["ransac"]["mask"]):
+            return params, "pair %d: inlier mask" % i
+    return params, ("flagged" if flagged else None)
+
+
+RGBD_KP_CAPS = {"GFT": (64, 512, 1024, 1088, 2048), "ORB": (64, 512, 1024, 1536, 2048), "FAST": (64, 1024, 1088, 4096),
+                "AGAST": (64, 1024, 1088, 4096)}
+
+
+def draw_rgbd(rng):
+    """The parameters of one `rgbd` case (no GPU): a legal sosvo_rgbd_batch_cfg, the detector in flags bits 8-9, kp_cap on
+    both sides of 1024 (GFT's whole-image variant starts above it; ORB up to 2048).  GFT wants at most 1000 corners."""
+    det = str(rng.choice(DETECTORS))
+    d = dict(detector=det, B=int(rng.integers(1, 4)), rows=int(rng.integers(80, 200)), cols=int(rng.integers(100, 320)),
+             kp_cap=int(rng.choice(RGBD_KP_CAPS[det])), nfeat=int(rng.choice([50, 400, 1000] if det == "GFT" else [50, 400, 2000])),
+             algo=str(rng.choice(["EPNP", "KNEIP", "GP3P", "TWOPT"])), depth_is_Z=bool(rng.integers(0, 2)),
+             ksize=int(rng.choice([0, 0, 1, 3, 5, 11])), max_iter=int(rng.choice([20, 200])), adaptive=bool(rng.integers(0, 2)),
+             seed=int(rng.integers(0, 2 ** 31)), thr=float(rng.choice([1.0 - np.cos(np.deg2rad(5.0)), 1.0 - np.cos(np.deg2rad(0.5))])))
+    d["frame_cap"] = int(rng.choice([d["kp_cap"], d["kp_cap"], 32, 200]))
+    return d
+
+
+def rgbd_frames(rng, B, rows, cols):
+    """B random RGB-D pairs (no GPU): a texture shifted between the two frames of a pair; depth in metres (the units of the
+    0.8 .. 7 m range gates) on 8x8 blocks, some beyond the gates, with holes of 0 or NaN -> bgr [2B,rows,cols,3] u8,
+    depth [2B,rows,cols] f32"""
     bgr, depth = [], []
     for i in range(B):
         base = np.stack([_image(rng, rows + 8, cols + 8, int(rng.integers(0, 2))) for _ in range(3)], axis=-1)
-        dz = rng.uniform(0.5, 9.0, (rows + 8, cols + 8)).astype(np.float32)     # metres * 1000 below; some beyond the range gates
+        dz = rng.uniform(0.5, 9.0, (rows + 8, cols + 8)).astype(np.float32)
         dz = np.kron(dz[::8, ::8], np.ones((8, 8), np.float32))[:rows + 8, :cols + 8]
         sx, sy = int(rng.integers(0, 8)), int(rng.integers(0, 8))
         for (ox, oy) in ((0, 0), (sx, sy)):
             im = np.ascontiguousarray(base[oy:oy + rows, ox:ox + cols])
-            d = (1000.0 * dz[oy:oy + rows, ox:ox + cols]).astype(np.float32)
+            d = np.array(dz[oy:oy + rows, ox:ox + cols], np.float32)
             hole = rng.random((rows, cols)) < float(rng.choice([0.0, 0.1, 0.9]))
             d[hole] = float(rng.choice([0.0, np.nan]))
             bgr.append(im)
             depth.append(d)
-    bgr, depth = np.stack(bgr), np.stack(depth)
+    return np.stack(bgr), np.stack(depth)
+
+
+def fuzz_rgbd(ctx, rng):
+    """The RGB-D (perspective) path behind ONE C-ABI call (sosvo_rgbd_pair_batch) on small random frames with any of the four
+    detectors -- textures shifted between the frames of a pair, depth maps with holes / NaN / out-of-range values, both
+    depth conventions, all solvers, an optional median window, capacities on both sides of 1024 and frame caps that cut --
+    on a dirty workspace, against the reference's control flow on the oracle (oracle/flow.py, tests/refflow.py)."""
+    import refflow
+    from vo_single_camera_sos_amd import _lib
+    from vo_single_camera_sos_amd.pipeline import RGBDCamConfig, RGBDPairBatch
+    d = draw_rgbd(rng)
+    params = dict(d)
+    B, rows, cols, nfeat, algo, ksize = d["B"], d["rows"], d["cols"], d["nfeat"], d["algo"], d["ksize"]
+    depth_is_Z, max_iter, adaptive, seed, thr, det = d["depth_is_Z"], d["max_iter"], d["adaptive"], d["seed"], d["thr"], d["detector"]
+    cap, Fc = d["kp_cap"], d["frame_cap"]
+    fx, fy, cx, cy = 0.8 * cols, 0.8 * cols, 0.5 * cols - 0.5, 0.5 * rows - 0.5
+    bgr, depth = rgbd_frames(rng, B, rows, cols)
     cam = RGBDCamConfig(fx=fx, fy=fy, center_x=cx, center_y=cy, depth_is_Z=depth_is_Z, min_range=0.8, max_range=7.0)
-    one = RGBDPairBatch(ctx, cam, B, image_shape=(rows, cols), num_of_features=nfeat, max_iter=max_iter, adaptive=adaptive, seed=seed,
-                        thr=thr, pose_est_algorithm=algo, median_win_size=ksize)
+    one = RGBDPairBatch(ctx, cam, B, image_shape=(rows, cols), num_of_features=nfeat, kp_cap=cap, frame_cap=Fc, max_iter=max_iter,
+                        adaptive=adaptive, seed=seed, thr=thr, pose_est_algorithm=algo, median_win_size=ksize, detection_method=det)
+    assert one.cfg.flags >> 8 == _lib.DETECTORS[det] and one.cfg.kp_cap == cap and one.cfg.frame_cap == Fc
+    one.workspace.fill_(int(rng.integers(0, 256)))
+    ctx.debug_fill_scratch(int(rng.integers(0, 256)))
     one.load_frames(bgr, depth)
     rec = one.step()
     ctx.synchronize()
     rec = rec.cpu().numpy()
+    F = 2 * B
+    w = _carved(one.workspace, [("gray", F * rows * cols, np.uint8), ("kp", F * cap * 2, np.float32), ("n", F, np.int32),
+                                ("status", F, np.int32), ("desc", F * cap * 32, np.uint8), ("m", F * Fc * 2, np.float32),
+                                ("d", F * Fc * 32, np.uint8), ("X", F * Fc * 3, np.float64), ("b", F * Fc * 3, np.float64),
+                                ("M", F, np.int32)])
     ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
     rc = refflow.RGBDParams(fx, fy, cx, cy, cam.focal_length_m, depth_is_Z, 0.8, 7.0, cam.f2f_max_hdiff, 1.0)
-    frames = [refflow.rgbd_frame(rc, bgr[f], depth[f], nfeat, orb_pattern.orb_pattern(), ca, sa, median_ksize=ksize) for f in range(2 * B)]
+    pat = orb_pattern.orb_pattern()
+    flagged = False
     for i in range(B):
-        w = refflow.track_pair_rgbd(rc, frames[2 * i], frames[2 * i + 1], thr, max_iter, seed=seed + i, adaptive=adaptive,
-                                    epnp=(algo == "EPNP"), gp3p=(algo == "GP3P"), twopt=(algo == "TWOPT"))
-        n = len(w["corr"]["q"])
+        skip = False
+        for f in (2 * i, 2 * i + 1):
+            if det == "GFT" and w["status"][f]:
+                skip = True       # the candidate budget overflowed (status bit 0): which candidates were kept is not defined
+            if det == "AGAST":
+                over = int((oracle.fast_score_map(oracle.median_gray(bgr[f], ksize), 10) > 0).sum()) > 16384
+                if bool(w["status"][f] & 2) != over:
+                    return params, "frame %d: AGAST overflow flag (%d, oracle %s)" % (f, w["status"][f], over)
+                skip |= over
+        if skip:
+            flagged = True
+            continue
+        frames = []
+        for f in (2 * i, 2 * i + 1):
+            fr = flow.rgbd_frame(rc, bgr[f], depth[f], nfeat, pat, ca, sa, median_ksize=ksize, method=det, kp_cap=cap)
+            if len(fr["X"]) > Fc:
+                flagged = True     # more keypoints with valid depth than the frame store holds: the first frame_cap are kept
+                fr = {k: (v[:Fc] if k != "n_kp" else v) for k, v in fr.items()}
+            if w["M"][f] != len(fr["X"]):
+                return params, "frame %d: keypoints with depth (%d, oracle %d)" % (f, w["M"][f], len(fr["X"]))
+            frames.append(fr)
+        wt = refflow.track_pair_rgbd(rc, frames[0], frames[1], thr, max_iter, seed=seed + i, adaptive=adaptive,
+                                     epnp=(algo == "EPNP"), gp3p=(algo == "GP3P"), twopt=(algo == "TWOPT"))
+        n = len(wt["corr"]["q"])
         if rec[i, 13] != n:
             return params, "pair %d: correspondences (%d, oracle %d)" % (i, rec[i, 13], n)
-        if rec[i, 14] != w["ransac"]["status"] or rec[i, 15] != w["ransac"]["best_iter"] or rec[i, 12] != w["ransac"]["n_inliers"]:
+        if rec[i, 14] != wt["ransac"]["status"] or rec[i, 15] != wt["ransac"]["best_iter"] or rec[i, 12] != wt["ransac"]["n_inliers"]:
             return params, "pair %d: RANSAC status / winner / inliers (%s, oracle %d %d %d)" % (
-                i, rec[i, 12:16].tolist(), w["ransac"]["n_inliers"], w["ransac"]["status"], w["ransac"]["best_iter"])
-        if not np.array_equal(rec[i, :12].reshape(3, 4), w["T"]):
+                i, rec[i, 12:16].tolist(), wt["ransac"]["n_inliers"], wt["ransac"]["status"], wt["ransac"]["best_iter"])
+        if not np.array_equal(rec[i, :12].reshape(3, 4), wt["T"]):
             return params, "pair %d: pose bits" % i
-    return params, None
+    return params, ("flagged" if flagged else None)
 
 
 STAGES = {"median": fuzz_median, "gft": fuzz_gft, "fast": fuzz_fast, "agast": fuzz_agast, "match": fuzz_match,
           "radius": fuzz_radius, "orb": fuzz_orb, "unwrap": fuzz_unwrap, "ransac": fuzz_ransac,
           "describe": fuzz_describe, "relpose": fuzz_relpose, "l2sort": fuzz_l2sort,
-          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd}
+          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd, "batch": fuzz_batch}
 
 
 def main():
@@ -587,7 +834,8 @@ def main():
     t_end = time.time() + 60 * args.minutes
     done = {s: 0 for s in stages}
     flagged = {s: 0 for s in stages}
-    refused = {}
+    refused = {s: 0 for s in stages}
+    messages = set()
     case = args.first_case
     t_print = time.time()
     while time.time() < t_end and (args.cases == 0 or case < args.first_case + args.cases):
@@ -595,10 +843,11 @@ def main():
             rng = np.random.default_rng([args.seed, list(STAGES).index(s), case])
             try:
                 params, err = STAGES[s](ctx, rng)
-            except SosvoError as e:     # an argument the entry point refuses (documented ranges): shown once per message
+            except SosvoError as e:     # an argument the entry point refuses: not a case (the run cannot end "all identical")
+                refused[s] += 1
                 msg = str(e).split(":")[-1].strip()
-                if msg not in refused:
-                    refused[msg] = (s, case)
+                if msg not in messages:
+                    messages.add(msg)
                     print("refused (stage %s case %d): %s" % (s, case, e), flush=True)
                 continue
             if err == "flagged":
@@ -611,6 +860,12 @@ def main():
         if time.time() - t_print > 20:
             t_print = time.time()
             print("cases %s flagged %s" % (done, flagged), flush=True)
+    # a draw the ABI refused, or --minutes ending the run before --cases, leaves stages short: say so and fail
+    short = {s: n for s, n in done.items() if (args.cases and n < args.cases) or n == 0}
+    if short or any(refused.values()):
+        print("fuzz_parity: INCOMPLETE (short %s, refused %s).  cases %s flagged %s seed %d first-case %d" % (
+            short, {s: n for s, n in refused.items() if n}, done, flagged, args.seed, args.first_case), flush=True)
+        return 2
     print("fuzz_parity: all identical.  cases %s flagged %s seed %d first-case %d" % (done, flagged, args.seed, args.first_case), flush=True)
     return 0
 

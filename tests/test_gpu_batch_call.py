@@ -215,3 +215,64 @@ def test_overlapped_streams_equal_single_pipeline(ctx, n_streams):
     assert np.array_equal(recs[0].cpu().numpy().view(np.uint64), want.view(np.uint64))
     assert torch.equal(recs[2], recs[0]) and torch.equal(recs[3], recs[1]) and not torch.equal(recs[1], recs[0])
     eng.close()
+
+
+def test_enqueue_with_changing_configs_on_one_workspace(ctx):
+    """sosvo_frame_pair_batch_streams_enqueue through plain ctypes, back to back on ONE workspace with the same (n_pairs,
+    n_streams = 3) but a different configuration each call -- ORB with kp_cap 2048, GFT with kp_cap 64, FAST, AGAST --, then
+    one call on a shifted workspace pointer, and a single join at the end.  A part's slice starts after the earlier parts'
+    bytes, which depend on the whole configuration, so every such change must join the previous call internally: every
+    record equals the joined sosvo_frame_pair_batch's with the same configuration, bit for bit."""
+    c_p = _lib.c_p
+    B, NS = 4, 3
+    model, rig, omni = _setup(ctx, B)
+    kinds = [dict(detection_method="ORB", kp_cap=2048, num_of_features=250), dict(detection_method="GFT", kp_cap=64, num_of_features=300),
+             dict(detection_method="FAST", kp_cap=2048, num_of_features=300), dict(detection_method="AGAST", kp_cap=512, num_of_features=300)]
+    want, cfgs = [], []
+    for kw in kinds:
+        one = FramePairBatch(ctx, model, rig, B, frame_cap=1024, max_iter=300, seed=11, **kw)
+        one.workspace.fill_(0x3C)
+        one.load_frames(omni)
+        want.append(one.step().clone())
+        cfgs.append(one.cfg)
+        del one
+    ctx.synchronize()
+    lib = _lib.load()
+    cp = lambda c: ctypes.cast(ctypes.pointer(c), c_p)  # noqa: E731
+
+    def part_bytes(c):
+        sizes = []
+        for lo, hi in ((0, 2), (2, 3), (3, 4)):   # the split of 4 pairs over 3 streams (sizes differ by at most one)
+            p = _lib.BatchCfg()
+            ctypes.memmove(ctypes.addressof(p), ctypes.addressof(c), ctypes.sizeof(p))
+            p.n_pairs = hi - lo
+            sizes.append(lib.sosvo_frame_pair_batch_workspace(cp(p)))
+        return sizes
+
+    # the configurations differ in their slice layout (what the join used to ignore) while (n_pairs, n_streams) stay put
+    layouts = [tuple(part_bytes(c)) for c in cfgs]
+    assert len(set(layouts)) == len(kinds) and all(min(l) > 0 for l in layouts), layouts
+    need = [lib.sosvo_frame_pair_batch_streams_workspace(cp(c), NS) for c in cfgs]
+    shift = 256
+    nbytes = max(need) + shift
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=ctx.device)
+    ws.fill_(0xC3)
+    dev_omni = torch.from_numpy(omni).to(ctx.device)
+    rig_s = rig.as_struct()
+    outs = [torch.full((B, 16), float("nan"), dtype=torch.float64, device=ctx.device) for _ in range(len(kinds) + 1)]
+    ctx.synchronize()
+    calls = [(k % len(kinds), 0) for k in range(2 * len(kinds))] + [(0, shift), (1, 0)]
+    for k, off in calls:
+        out = outs[len(kinds)] if off else outs[k]
+        rc = lib.sosvo_frame_pair_batch_streams_enqueue(ctx._h, cp(rig_s), cp(cfgs[k]), NS, dev_omni.data_ptr(),
+                                                        model.unwrap_table.data_ptr(), model.mask_bits.data_ptr(),
+                                                        model.pattern.data_ptr(), ws.data_ptr() + off, nbytes - off,
+                                                        out.data_ptr())
+        assert rc == 0, (k, off)
+    assert lib.sosvo_frame_pair_batch_streams_join(ctx._h) == 0
+    ctx.synchronize()
+    for k, kw in enumerate(kinds):
+        assert np.array_equal(outs[k].cpu().numpy().view(np.uint64), want[k].cpu().numpy().view(np.uint64)), kw
+    assert np.array_equal(outs[-1].cpu().numpy().view(np.uint64), want[0].cpu().numpy().view(np.uint64))
+    # (the four configurations give four different records: a call that ran another call's configuration would show)
+    assert len({w.cpu().numpy().tobytes() for w in want}) == len(kinds)

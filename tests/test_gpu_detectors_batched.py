@@ -16,7 +16,6 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
 import refflow
 import synth
 from vo_single_camera_sos_amd import _lib, orb_pattern, synthetic
@@ -206,28 +205,6 @@ def _rgbd_pairs(B, seed0=900):
     return np.stack(bgr), np.stack(depth), poses
 
 
-def _oracle_rgbd_frame(method, cam, bgr, depth, nfeat, cap, median=0, mask=None):
-    """RGBDFrame.establish_keypoints with ORB / FAST / AGAST (pose_est_tools.py:477-516, :547, :553, :611) on the oracle."""
-    gray = oracle.median_gray(bgr, median)
-    mb = np.ones(gray.shape, np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32)
-    if method == "ORB":
-        kp4, _ = oracle.orb_detect(gray, mb, 1, nfeat, cap)[0]
-        d, kept = oracle.orb_describe_levels(gray, kp4)
-        kp = np.ascontiguousarray(kp4[kept, :2])
-    else:
-        kp = (refflow.fast_keypoints if method == "FAST" else refflow.agast_keypoints)(gray, mb, 0)[:cap]
-        ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        d, kept = oracle.orb_describe(oracle.gauss7(gray), kp, ca, sa, orb_pattern.orb_pattern(), 31)
-        kp = kp[kept]
-    u, v = kp[:, 0].astype(np.uint64).astype(np.int32), kp[:, 1].astype(np.uint64).astype(np.int32)   # :611 (truncation)
-    xyz, b = oracle.rgbd_backproject(depth, u, v, np.array([FX, FY, CX, CY, cam.focal_length_m]), True)
-    Z = xyz[:, 2]
-    valid = ~np.isnan(Z)
-    az = np.abs(np.nan_to_num(Z))
-    valid &= (az >= cam.min_range) & (az <= cam.max_range)
-    return dict(m=kp[valid].astype(np.float32), d=d[valid], X=xyz[valid], b=b[valid], n_kp=len(kp))
-
-
 @pytest.mark.parametrize("method", METHODS)
 def test_rgbd_front_end_equals_the_oracle_and_the_batched_paths(ctx, method):
     B, nfeat = 2, 1000
@@ -250,8 +227,11 @@ def test_rgbd_front_end_equals_the_oracle_and_the_batched_paths(ctx, method):
     assert not (pipe.status.cpu().numpy() & 2).any(), (method, pipe.status.cpu().numpy())
     if method == "ORB":
         assert not np.isnan(fe.kp4.cpu().numpy()).any()
+    rc = refflow.RGBDParams(FX, FY, CX, CY, cam.focal_length_m, True, cam.min_range, cam.max_range)
+    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    pat = orb_pattern.orb_pattern()
     for f in range(2 * B):
-        w = _oracle_rgbd_frame(method, cam, bgr[f], depth[f], nfeat, fe.kp_cap, median=med)
+        w = refflow.rgbd_frame(rc, bgr[f], depth[f], nfeat, pat, ca, sa, median_ksize=med, method=method, kp_cap=fe.kp_cap)
         M = int(g["M"][f])
         assert n_kp[f] == w["n_kp"] and M == len(w["X"]), (method, f, n_kp[f], w["n_kp"], M, len(w["X"]))
         assert np.array_equal(g["m"][f, :M], w["m"]) and np.array_equal(g["d"][f, :M], w["d"]), (method, f)

@@ -37,8 +37,11 @@ struct sosvo_ctx {
   int32_t hint_shared_device;  // sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other streams' kernels share the chip
   int32_t sub_last;  // parts of the most recent sosvo_frame_pair_batch_streams[_enqueue] call
   // un-joined work of an ..._enqueue call is pending on the part streams: only then does the next call chain its first
-  // median behind the previous call's last one, and only then must its split (n_pairs, n_streams) equal the previous one
-  int32_t sub_pending, sub_last_pairs;
+  // median behind the previous call's last one, and only then must its slice layout (workspace pointer, part count, each
+  // part's bytes) equal the previous one
+  int32_t sub_pending;
+  const void* sub_last_ws;
+  size_t sub_last_bytes[kSosvoMaxSubStreams];
 };
 
 // Brackets the kernel launches of the enclosing scope with a HIP event pair when profiling is on.

@@ -596,15 +596,27 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     SOSVO_HIP(ctx, hipEventCreateWithFlags(&ctx->sub_median[i], hipEventDisableTiming));
     ctx->n_sub = i + 1;
   }
+  // the slice layout of this call: part s uses bytes[s] from workspace + bytes[0] + ... + bytes[s - 1].  A part's size
+  // depends on the whole configuration (detector, kp_cap, nmask, frame_cap, rows / cols, H / W, ...), not only on its pairs
+  size_t bytes[kSosvoMaxSubStreams];
+  for (int s = 0; s < n_streams; ++s) {
+    int lo, hi;
+    part_range(cfg->n_pairs, s, n_streams, &lo, &hi);
+    sosvo_batch_cfg c = *cfg;
+    c.n_pairs = hi - lo;
+    bytes[s] = (sosvo_frame_pair_batch_workspace(&c) + 255) & ~(size_t)255;
+  }
   if (ctx->sub_pending) {
     // un-joined parts of an earlier ..._enqueue call may still run.  A stream capture cannot depend on them (their events
-    // were recorded outside it), and a different split would lay this call's workspace slices over slices an earlier
-    // part still uses on ANOTHER stream (a slice is ordered by its own part stream only): join first in both cases.
+    // were recorded outside it), and a different slice layout would lay this call's slices over slices an earlier part
+    // still uses on ANOTHER stream (a slice is ordered by its own part stream only): join first in both cases.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     SOSVO_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cap));
     SOSVO_REQUIRE(ctx, cap == hipStreamCaptureStatusNone,
                   "un-joined sosvo_frame_pair_batch_streams_enqueue work is pending: call ..._join before capturing");
-    if (ctx->sub_last != n_streams || ctx->sub_last_pairs != cfg->n_pairs) {
+    bool same = ctx->sub_last == n_streams && ctx->sub_last_ws == workspace;
+    for (int s = 0; same && s < n_streams; ++s) same = ctx->sub_last_bytes[s] == bytes[s];
+    if (!same) {
       for (int s = 0; s < ctx->sub_last; ++s) SOSVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->sub_done[s], 0));
       ctx->sub_pending = 0;
     }
@@ -623,11 +635,10 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     sosvo_batch_cfg c = *cfg;
     c.n_pairs = hi - lo;
     c.seed = cfg->seed + (uint64_t)lo;  // pair i samples with seed + i, whatever the split
-    const size_t bytes = (sosvo_frame_pair_batch_workspace(&c) + 255) & ~(size_t)255;
     sosvo_ctx* sc = ctx->sub[s];
     SOSVO_HIP(ctx, hipStreamWaitEvent(sc->stream, ctx->sub_begin, 0));
     const int32_t rc = run_frame_pairs(sc, rig, &c, omni + (size_t)2 * lo * cfg->H * cfg->W * 3, unwrap_table, mask_bits, pattern,
-                                       ws, bytes, results + (size_t)16 * lo, token, ctx->sub_median[s]);
+                                       ws, bytes[s], results + (size_t)16 * lo, token, ctx->sub_median[s]);
     if (rc != SOSVO_OK) {
       // the parts launched so far (and whatever this one enqueued before failing) still run: the caller's stream must
       // not overtake them
@@ -640,10 +651,11 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     }
     token = ctx->sub_median[s];
     SOSVO_HIP(ctx, hipEventRecord(ctx->sub_done[s], sc->stream));
-    ws += bytes;
+    ws += bytes[s];
   }
   ctx->sub_last = n_streams;
-  ctx->sub_last_pairs = cfg->n_pairs;
+  ctx->sub_last_ws = workspace;
+  for (int s = 0; s < n_streams; ++s) ctx->sub_last_bytes[s] = bytes[s];
   ctx->sub_pending = join ? 0 : 1;
   // ... and the caller's stream continues after all of them
   if (join)
