@@ -11,6 +11,11 @@ on its own -- this program starts them itself as child processes before it touch
 pairs (rank r owns the global pairs [r*B, (r+1)*B); no data-path collective) and all-gather the per-pair
 pose records (16 doubles each) over RCCL at the end of every step.  Rank 0 prints ONE JSON line.
 BASELINE config 4 (512 pairs over 8 GPUs) is `python bench.py --gpus 8 --pairs-per-gpu 64`.
+
+A plain run does only what that line's headline needs: it renders the frames, sets up, warms up, times the K steps,
+writes --dump-outputs and prints the line.  `--full` adds everything else: isolated launches of the dominant kernel, the
+PCIe-inclusive rate, the CPU baselines, the 0.5-degree accuracy run and the sub-records (other detectors, solvers and
+panorama width, the C ABI, sequence mode, BASELINE configs 3 and 5).
 """
 import argparse
 import json
@@ -21,6 +26,13 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+if __name__ == "__main__":
+    # The frames are rendered by forked worker processes, one pair at a time each (synthetic.make_frame_pairs).  numpy's
+    # OpenBLAS gives every worker a thread pool of OPENBLAS_NUM_THREADS, else OMP_NUM_THREADS, else the host's core count
+    # threads, which oversubscribes the host many times over and makes rendering several times slower.  The rendered
+    # bytes do not depend on the count.  (Only as a program: importing this module leaves the caller's environment alone.)
+    os.environ["OPENBLAS_NUM_THREADS"] = "1"
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -616,10 +628,14 @@ def parse():
                     help="host processes rendering the synthetic frames (0 = auto; use 1 under rocprofv3, whose preloaded "
                          "tool initialises the GPU before this program forks)")
     ap.add_argument("--cpu-cores", type=int, default=0, help="processes of the all-cores CPU baseline (0 = os.cpu_count())")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the extra PCIe-inclusive measurement (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: isolated launches of the dominant kernel, the "
+                         "PCIe-inclusive rate, the CPU baselines and reference-library probe, the 0.5-degree accuracy run and "
+                         "the sub-records.  --no-cpu, --no-h2d, --no-isolated and --no-sub leave parts of it out")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines and the reference-library probe")
+    ap.add_argument("--no-h2d", action="store_true", help="with --full: skip the extra PCIe-inclusive measurement (N = 1 only)")
     ap.add_argument("--no-isolated", action="store_true",
-                    help="skip the isolated launches of the dominant kernel after the timed region (profile passes: the "
+                    help="with --full: skip the isolated launches of the dominant kernel after the timed region (the "
                          "per-kernel averages then cover the timed region only)")
     ap.add_argument("--pmc-csv", default=None, help="per-kernel PMC summary for roofline.traffic (default: newest in profiles/)")
     ap.add_argument("--seed", type=int, default=1234)
@@ -630,7 +646,7 @@ def parse():
                     help="P3P: the three solve points of a sample from one mirror (BASELINE config 2's \"P3P RANSAC\"); GP3P: "
                          "generalised P3P on samples across both mirrors (what the reference's non-central RANSAC uses)")
     ap.add_argument("--no-sub", action="store_true",
-                    help="skip the sub-records (ORB-detector path, GP3P hypotheses, BASELINE configs 3 and 5)")
+                    help="with --full: skip the sub-records (ORB-detector path, GP3P hypotheses, BASELINE configs 3 and 5)")
     ap.add_argument("--sub-steps", type=int, default=12, help="timed steps of each in-process sub-record")
     ap.add_argument("--orb-features-per-mask", type=int, default=230,
                     help="ORB_create(nfeatures) per azimuthal mask of the orb_detector sub-record (12 masks x 230: ~2000 per view)")
@@ -638,7 +654,7 @@ def parse():
                     help="frames of the synthetic sequence of the `sequence` sub-record (run_VO in sequence mode); 0 = skip")
     ap.add_argument("--sequence-child", action="store_true",
                     help="(internal) render the sequences, run the two sequence sub-records in THIS fresh process and print them "
-                         "as one JSON line: a process that has created the batch engines loses ~15 % on the host-bound VO loop")
+                         "as one JSON line: a process that has created the batch engines loses ~15 %% on the host-bound VO loop")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"),
                     help="file the FULL record goes to (per-kernel tables, notes, sub-records); stdout carries the compact line")
     ap.add_argument("--dump-records", default=None,
@@ -650,6 +666,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu = args.no_h2d = args.no_isolated = args.no_sub = True
     return args
 
 

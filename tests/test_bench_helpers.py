@@ -64,3 +64,18 @@ def test_steps_and_dump_outputs_arguments(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
     with pytest.raises(SystemExit):
         b.parse()
+
+
+def test_plain_run_leaves_everything_beyond_the_headline_to_full(monkeypatch):
+    """Without --full a run skips the CPU baselines, the PCIe leg, the isolated launches and the sub-records; with --full
+    it runs them, and the --no-* options still leave single parts out."""
+    import sys
+    b = _bench()
+    gated = ("no_cpu", "no_h2d", "no_isolated", "no_sub")
+    for argv, expect in ((["--gpus", "1", "--steps", "7", "--warmup", "2"], (True, True, True, True)),
+                         (["--full"], (False, False, False, False)),
+                         (["--full", "--no-sub", "--no-h2d"], (False, True, False, True))):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        args = b.parse()
+        assert tuple(getattr(args, k) for k in gated) == expect, argv
+        assert args.full == ("--full" in argv)
