@@ -118,16 +118,18 @@ typedef unsigned long long __attribute__((aligned(1))) u64_unaligned;
 
 // Tap loads of one table entry, unconditional and branch-free so that they can be issued a whole row ahead of
 // their use: a fast entry loads at off0 and off0 + 3 W; an edge entry loads at the clamped offsets (the blend
-// shifts the bytes back).  `row_bytes` = 3 W.
+// shifts the bytes back).  Returns whether any lane of the wave has an edge entry (wave-uniform): the blend of the
+// same entry takes it instead of testing the entries again.
 __device__ __forceinline__ int edge_tap_offset(uint2 e, int r, int W) {
   const int ix = (int)(int16_t)(e.x & 0xFFFFu), iy = (int)(int16_t)(e.x >> 16);
   return 3 * ((iy + r) * W + ix);  // byte offset of tap (ix, iy + r) inside the frame; H * W * 3 < 2^31
 }
-__device__ __forceinline__ void unwrap_gather(const uint8_t* __restrict__ src, int frame_bytes, int W, uint2 e,
+__device__ __forceinline__ bool unwrap_gather(const uint8_t* __restrict__ src, int frame_bytes, int W, uint2 e,
                                               unsigned long long v[2]) {
   uint32_t o0 = e.x & kTabOffMask, o1 = o0 + 3u * (uint32_t)W;
   const bool edge = (e.y & kTabEdge) != 0u;
-  if (__ballot(edge) != 0ULL) {  // wave-uniform branch, rarely taken: some lane has frame-edge taps
+  const bool any_edge = __ballot(edge) != 0ULL;
+  if (any_edge) {  // wave-uniform branch, rarely taken: some lane has frame-edge taps
     if (edge) {
       o0 = (uint32_t)min(max(edge_tap_offset(e, 0, W), 0), frame_bytes - 8);
       o1 = (uint32_t)min(max(edge_tap_offset(e, 1, W), 0), frame_bytes - 8);
@@ -135,14 +137,16 @@ __device__ __forceinline__ void unwrap_gather(const uint8_t* __restrict__ src, i
   }
   v[0] = *reinterpret_cast<const u64_unaligned*>(src + o0);
   v[1] = *reinterpret_cast<const u64_unaligned*>(src + o1);
+  return any_edge;
 }
 
-// 1/32-px fixed-point blend of the gathered taps -> B | G << 8 | R << 16
-__device__ __forceinline__ uint32_t unwrap_blend(int frame_bytes, int W, uint2 e, const unsigned long long vin[2]) {
+// 1/32-px fixed-point blend of the gathered taps -> B | G << 8 | R << 16; any_edge = what unwrap_gather returned for e
+__device__ __forceinline__ uint32_t unwrap_blend(int frame_bytes, int W, uint2 e, const unsigned long long vin[2],
+                                                 bool any_edge) {
   unsigned long long v0 = vin[0], v1 = vin[1];
   uint32_t w00 = e.y & 0x7FFu, w01 = (e.y >> 11) & 0x3FFu, w10 = (e.y >> 21) & 0x3FFu, w11 = e.x >> 22;
   const bool edge = (e.y & kTabEdge) != 0u;
-  if (__ballot(edge) != 0ULL && edge) {  // wave-uniform skip; rare: undo the clamp of the loads, weights from (fx, fy, valid)
+  if (any_edge && edge) {  // wave-uniform skip; rare: undo the clamp of the loads, weights from (fx, fy, valid)
     const uint32_t valid = (e.y >> 10) & 15u;
     const uint32_t fx = e.y & 31u, fy = (e.y >> 5) & 31u;
     w00 = (valid & 1u) ? (32u - fx) * (32u - fy) : 0u;
@@ -189,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void unwrap_lut_kernel(const uint8_t* __r
   if (pix < npix) {
     const uint2 e = table[(size_t)view * npix + pix];
     unsigned long long v[2];
-    unwrap_gather(src, H * W * 3, W, e, v);
-    bgr = unwrap_blend(H * W * 3, W, e, v);
+    const bool any_edge = unwrap_gather(src, H * W * 3, W, e, v);
+    bgr = unwrap_blend(H * W * 3, W, e, v, any_edge);
   }
   const size_t out0 = ((size_t)img * npix + (size_t)blk * kThreads) * 3;  // first output byte of this workgroup
   const int nvalid = min(kThreads, npix - blk * kThreads);
@@ -211,6 +215,17 @@ __global__ __launch_bounds__(kThreads) void unwrap_lut_kernel(const uint8_t* __r
 
 __device__ __forceinline__ uint8_t bgr2gray(int b, int g, int r) {
   return (uint8_t)((1868 * b + 9617 * g + 4899 * r + 8192) >> 14);
+}
+// x * k + acc as ONE v_mad_u32_u24 (x < 2^24; k wave-uniform)
+__device__ __forceinline__ uint32_t mad24(uint32_t x, uint32_t k, uint32_t acc) {
+  uint32_t r;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(k), "v"(acc));
+  return r;
+}
+// bgr2gray of three bytes the compiler cannot bound (the median's results): three 24-bit multiply-adds instead of two
+// v_mul_lo_u32 + v_mad_u64_u32 + v_add3
+__device__ __forceinline__ uint8_t bgr2gray_mad24(uint32_t b, uint32_t g, uint32_t r) {
+  return (uint8_t)(mad24(r, 4899u, mad24(g, 9617u, mad24(b, 1868u, 8192u))) >> 14);
 }
 
 __global__ __launch_bounds__(kThreads) void gray_kernel(const uint8_t* __restrict__ img, size_t npix_total,
@@ -255,14 +270,15 @@ __global__ __launch_bounds__(kThreads) void unwrap_gray_kernel(const uint8_t* __
   const int col = min(bx * TW + lx, cols - 1), row0 = by * TH + ly;
   uint2 e[NK];
   unsigned long long v[NK][2];
+  bool any_edge[NK];
 #pragma unroll
   for (int k = 0; k < NK; ++k) e[k] = table[(size_t)view * npix + (size_t)min(row0 + 4 * k, rows - 1) * cols + col];
 #pragma unroll
-  for (int k = 0; k < NK; ++k) unwrap_gather(src, H * W * 3, W, e[k], v[k]);
+  for (int k = 0; k < NK; ++k) any_edge[k] = unwrap_gather(src, H * W * 3, W, e[k], v[k]);
   uint8_t* tile8 = reinterpret_cast<uint8_t*>(&tile[0][0]);
 #pragma unroll
   for (int k = 0; k < NK; ++k) {
-    const uint32_t bgr = unwrap_blend(H * W * 3, W, e[k], v[k]);
+    const uint32_t bgr = unwrap_blend(H * W * 3, W, e[k], v[k], any_edge[k]);
     tile8[(ly + 4 * k) * TW + lx] = bgr2gray((int)(bgr & 255u), (int)((bgr >> 8) & 255u), (int)((bgr >> 16) & 255u));
   }
   __syncthreads();
@@ -296,10 +312,29 @@ __device__ __forceinline__ uint32_t popc_add(uint32_t x, uint32_t acc) {
   asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
   return r;
 }
-// c & ~(w ^ m): the candidates whose window bit equals the chosen bit (m = all-ones / zero), one v_bitop3
-__device__ __forceinline__ uint32_t keep_equal(uint32_t c, uint32_t m, uint32_t w) {
+// c & (w ^ n): the candidates whose window bit equals the chosen bit (n = all-ones when the chosen bit is 0, zero
+// when it is 1), one v_bitop3
+__device__ __forceinline__ uint32_t keep_equal(uint32_t c, uint32_t n, uint32_t w) {
   uint32_t r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x90" : "=v"(r) : "v"(c), "v"(m), "v"(w));
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x60" : "=v"(r) : "v"(c), "v"(n), "v"(w));
+  return r;
+}
+// n ? e : a with a per-lane mask n (all-ones / zero), one v_bitop3 (table 0xD8)
+__device__ __forceinline__ uint32_t select_mask(uint32_t a, uint32_t e, uint32_t n) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xd8" : "=v"(r) : "v"(a), "v"(e), "v"(n));
+  return r;
+}
+// the same with a wave-uniform a (an SGPR: the rank counter's start value on the first plane)
+__device__ __forceinline__ uint32_t select_mask_s(uint32_t a, uint32_t e, uint32_t n) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xd8" : "=v"(r) : "s"(a), "v"(e), "v"(n));
+  return r;
+}
+// a | (~n & k): one fast v_bitop3 (table 0xF2); k is a wave-uniform literal (an SGPR)
+__device__ __forceinline__ uint32_t or_andn(uint32_t a, uint32_t n, uint32_t k) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xf2" : "=v"(r) : "v"(a), "v"(n), "s"(k));
   return r;
 }
 
@@ -310,38 +345,37 @@ __device__ __forceinline__ uint32_t merge_field(uint32_t a, uint32_t x, uint32_t
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xd8" : "=v"(r) : "v"(a), "v"(x), "s"(m));
   return r;
 }
-// a | (b & k): one fast v_bitop3 (table 0xF8) instead of v_and_or_b32
-__device__ __forceinline__ uint32_t or_and(uint32_t a, uint32_t b, uint32_t k) {
-  uint32_t r;
-  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xf8" : "=v"(r) : "v"(a), "v"(b), "s"(k));
-  return r;
-}
-// ~(a ^ b): v_xnor_b32 issues at the slow rate, v_bitop3 (table 0xC3) at the fast one
-__device__ __forceinline__ uint32_t xnor_fast(uint32_t a, uint32_t b) {
-  uint32_t r;
-  asm("v_bitop3_b32 %0, %1, %2, %2 bitop3:0xc3" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 // Writes lane l's K-bit slice of a row ballot -- bits [l, l + K) of `bal` -- into ring slot `slot` of one bit-plane's
-// window: slot s occupies bits [K * s, K * s + K) of the NW-word register.  `slot` is a compile-time constant after
-// unrolling: masks and shifts are literals.
-//   slot inside one word: the ballot is shifted LEFT by sh_up = 64 - K - l, which puts the slice into the top K bits of
-//     the high word, and a 32-bit RIGHT shift (fast VALU rate; v_lshlrev_b32 issues at the slow one) drops it onto the
-//     slot; whatever lands below the slot is cut by the merge mask;
-//   slot straddling two words: slice = bal >> l, then a shift + merge per word.
+// window of NW words.  `slot` is a compile-time constant after unrolling: masks and shifts are literals.  The select does
+// not care where a window element sits, only that every plane of a channel uses the same map, so the slots are laid out
+// where a slice lands with the fewest shifts:
+//   bottom slot, bits [0, K) of word slot / 2 (even slot < 2 NW): bal >> l, one 64-bit shift, valid for every lane;
+//   top slot, bits [32 - K, 32) of word slot / 2 (odd slot < 2 NW): the high word of bal << sh_up (sh_up = 64 - K - l),
+//     one 64-bit shift, valid for the output lanes (the halo lanes' windows are never used);
+//   NW = 1 (K = 3, 5): the other slots between them, bits [K (slot - 1), K slot): the top-slot value shifted down by a
+//     32-bit RIGHT shift (fast VALU rate; v_lshlrev_b32 issues at the slow one);
+//   NW = 4 (K = 11: 8 clean slots fill bits 0-10 and 21-31 of every word): slot 8 + i (i < 3) keeps slice bits 0-9 in
+//     bits 11-20 of word i and its bit 10 in bit 11 + i of word 3 (whose bits 14-20 stay zero).
+// Per plane and 11 rows that is 8 x 2 + 3 x 5 = 31 VALU instructions, 11 of them slow-rate 64-bit shifts (the layout of
+// K consecutive bits with three word-straddling slots took 8 x 3 + 3 x 5 = 39, 14 slow).  Every merge writes only bits its
+// slot owns; the bits no slot owns are never written and stay zero, so the popcounts need no mask.
 template <int K, int NW>
 __device__ __forceinline__ void ring_insert(uint32_t (&Wp)[NW], unsigned long long bal, int lane, int sh_up, int slot) {
-  const int bit = K * slot, w = bit >> 5, pos = bit & 31;
+  static_assert((NW == 1 && K * K <= 32) || (NW == 4 && K == 11), "ring layout covers K = 3, 5 and 11");
   const uint32_t field = (1u << K) - 1u;
-  if (pos + K <= 32) {
-    const uint32_t hi = (uint32_t)((bal << sh_up) >> 32);
-    const uint32_t t = (32 - K - pos) ? hi >> (32 - K - pos) : hi;
-    Wp[w] = merge_field(Wp[w], t, field << pos);
+  if (slot < 2 * NW) {
+    const int w = slot >> 1;
+    if ((slot & 1) == 0) Wp[w] = merge_field(Wp[w], (uint32_t)(bal >> lane), field);
+    else Wp[w] = merge_field(Wp[w], (uint32_t)((bal << sh_up) >> 32), field << (32 - K));
+  } else if (NW == 1) {
+    const int pos = K * (slot - 1);
+    const uint32_t hi = (uint32_t)((bal << sh_up) >> 32);  // slice in bits [32 - K, 32)
+    Wp[0] = merge_field(Wp[0], hi >> (32 - K - pos), field << pos);
   } else {
-    const uint32_t x = (uint32_t)(bal >> lane);
-    Wp[w] = merge_field(Wp[w], x << pos, field << pos);
-    Wp[w + 1] = merge_field(Wp[w + 1], x >> (32 - pos), field >> (32 - pos));
+    const int i = slot - 2 * NW;
+    const uint32_t hi = (uint32_t)((bal << sh_up) >> 32);  // slice in bits 21-31
+    Wp[i] = merge_field(Wp[i], hi >> 10, 0x3FFu << 11);
+    Wp[NW - 1] = merge_field(Wp[NW - 1], hi >> (20 - i), 1u << (11 + i));
   }
 }
 
@@ -351,7 +385,7 @@ __device__ __forceinline__ void for_each_slot(F& f, int r_base, std::integer_seq
 }
 
 // ---- K2 + K3 (optionally with K1 in front) --------------------------------------------------------------
-// K x K median per channel (replicated border) followed by BGR->gray.  K odd, 3 <= K <= 11.
+// K x K median per channel (replicated border) followed by BGR->gray.  K = 3, 5 or 11 (the ring layouts of ring_insert).
 // FUSED = false: img is the BGR panorama batch [nimg, rows, cols, 3].
 // FUSED = true : img is the omni batch [nframes, H, W, 3] and every lane unwraps its source pixel from the table
 //                on the fly (same integer arithmetic as unwrap_lut_kernel), so the colour panoramas never touch
@@ -397,13 +431,21 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
     out_hi = max(out_lo, min(rows, row_range[2 * view + 1]));
   }
   if (out_hi <= out_lo) return;  // wave-uniform
-  const uint2* tab = FUSED ? table + (size_t)view * rows * cols + x_src : nullptr;
+  // Table entries and gray bytes are addressed as a wave-uniform base (SGPRs) + a 32-bit lane offset: row * cols is
+  // wave-uniform (SALU) and the lane adds its column with one fast v_add (a 64-bit per-lane pointer costs slow-rate
+  // v_mad_u64_u32 / v_lshl_add_u64 per row).  An image's table half and gray panorama are far below 4 GB.
+  const uint8_t* tab = FUSED ? reinterpret_cast<const uint8_t*>(table + (size_t)view * rows * cols) : nullptr;
+  const uint32_t tab_lane = (uint32_t)x_src * (uint32_t)sizeof(uint2);
   const int frame_bytes = H * W * 3;
   const bool last_image = im == nimg - 1;
   uint2 e_cur = make_uint2(0u, 0u), e_nxt = make_uint2(0u, 0u);
   unsigned long long taps[2] = {0ULL, 0ULL};
+  bool any_edge = false;
   uint32_t raw = 0u;
   auto row_of = [&](int r) { return clampi(r, 0, rows - 1); };
+  auto tab_entry = [&](int r) -> uint2 {
+    return *reinterpret_cast<const uint2*>(tab + ((uint32_t)(row_of(r) * cols) * (uint32_t)sizeof(uint2) + tab_lane));
+  };
   auto load_raw = [&](int r) -> uint32_t {
     const int rr = row_of(r);
     const uint8_t* px = src + ((size_t)rr * cols + x_src) * 3;
@@ -411,9 +453,9 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
     return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);  // the buffer's last 3 bytes
   };
   if (FUSED) {
-    e_cur = tab[(size_t)row_of(out_lo - R) * cols];
-    e_nxt = tab[(size_t)row_of(out_lo - R + 1) * cols];
-    unwrap_gather(src, frame_bytes, W, e_cur, taps);
+    e_cur = tab_entry(out_lo - R);
+    e_nxt = tab_entry(out_lo - R + 1);
+    any_edge = unwrap_gather(src, frame_bytes, W, e_cur, taps);
   } else {
     raw = load_raw(-R);
   }
@@ -435,10 +477,10 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
     if (r_src >= out_hi + R) return;  // uniform (the tail of the last group)
     uint32_t pix;
     if (FUSED) {
-      pix = unwrap_blend(frame_bytes, W, e_cur, taps);
+      pix = unwrap_blend(frame_bytes, W, e_cur, taps, any_edge);
       e_cur = e_nxt;
-      unwrap_gather(src, frame_bytes, W, e_cur, taps);   // row r_src + 1
-      e_nxt = tab[(size_t)row_of(r_src + 2) * cols];  // row r_src + 2
+      any_edge = unwrap_gather(src, frame_bytes, W, e_cur, taps);   // row r_src + 1
+      e_nxt = tab_entry(r_src + 2);                                  // row r_src + 2
     } else {
       pix = raw;
       raw = load_raw(r_src + 1);
@@ -455,33 +497,32 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
     }
     const int r_out = r_src - R;
     if (r_out < out_lo) return;  // window not complete yet (uniform)
-    int med[3];
+    uint32_t med[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      // radix select from the MSB down.  `above` = candidates ranked above the wanted element; the candidates
-      // whose current bit is 1 rank above those whose bit is 0.
+      // radix select from the MSB down.  The rank counter is kept complemented, a = ~above (above = candidates
+      // ranked above the wanted element; those whose current bit is 1 rank above those whose bit is 0), and starts the
+      // plane's popcount chain, which then ends at e = n1 - above - 1: negative (neg = all-ones) iff n1 <= above, i.e.
+      // the wanted element has the bit clear, the ones drop out of the candidates and above becomes above - n1, whose
+      // complement is e.  So the bookkeeping is a sign mask, a select and a bit set: no subtraction, no minimum.
       uint32_t C[NW];
-#pragma unroll
-      for (int j = 0; j < NW; ++j) C[j] = 0xFFFFFFFFu;
-      // (the unused top bits of the last word are never set in a window register, so no mask is needed)
-      uint32_t above = ABOVE, res = 0u;
+      uint32_t a = ~ABOVE, res = 0u;
 #pragma unroll
       for (int b = 7; b >= 0; --b) {
-        uint32_t n1 = 0;
+        uint32_t e = a;
 #pragma unroll
-        for (int j = 0; j < NW; ++j) n1 = popc_add(C[j] & Wp[c][b][j], n1);
-        const uint32_t d = above - n1;
-        const uint32_t ones = (uint32_t)((int32_t)d >> 31);  // all-ones: the wanted element has bit b set
-        // above = min(above, d) as a 16-bit minimum (v_min_u16 issues at the fast rate, v_min_u32 at the slow one):
-        // above <= NB, and a negative d has its low half >= 0x10000 - NB > above
-        above = (uint32_t)min((uint16_t)above, (uint16_t)d);
-        res = or_and(res, ones, 1u << b);
+        for (int j = 0; j < NW; ++j) e = popc_add(b == 7 ? Wp[c][b][j] : (C[j] & Wp[c][b][j]), e);
+        const uint32_t neg = (uint32_t)((int32_t)e >> 31);
+        res = b == 7 ? or_andn(vzero, neg, 1u << b) : or_andn(res, neg, 1u << b);
+        if (b > 0) {
+          a = b == 7 ? select_mask_s(~ABOVE, e, neg) : select_mask(a, e, neg);
 #pragma unroll
-        for (int j = 0; j < NW; ++j) C[j] = b == 7 ? xnor_fast(Wp[c][b][j], ones) : keep_equal(C[j], ones, Wp[c][b][j]);
+          for (int j = 0; j < NW; ++j) C[j] = b == 7 ? (Wp[c][b][j] ^ neg) : keep_equal(C[j], neg, Wp[c][b][j]);
+        }
       }
-      med[c] = (int)res;
+      med[c] = res;
     }
-    if (out_ok) dst[(size_t)r_out * cols + x_out] = bgr2gray(med[0], med[1], med[2]);
+    if (out_ok) dst[(uint32_t)(r_out * cols + x_out)] = bgr2gray_mad24(med[0], med[1], med[2]);
   };
   for (int r_base = out_lo - R; r_base < out_hi + R; r_base += K)
     for_each_slot(row_step, r_base, std::make_integer_sequence<int, K>{});
