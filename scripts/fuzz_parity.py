@@ -656,10 +656,11 @@ def fuzz_batch(ctx, rng):
     NI, P, cap, Cc = 2 * F, 2 * F * NM, d["kp_cap"], 2 * Fc
     w = _carved(ws, [("gray", NI * model.rows * model.cols, np.uint8), ("kp", P * cap * 2, np.float32), ("n", P, np.int32),
                      ("status", P, np.int32), ("desc", P * cap * 32, np.uint8), ("s_keys", P // 2 * cap, np.uint32),
-                     ("s_order", P // 2 * cap, np.int32), ("m_top", F * Fc * 2, np.float32), ("m_bot", F * Fc * 2, np.float32),
+                     ("s_order", P // 2 * cap, np.int32), ("n_cand", F, np.int32), ("gray_rows", 4, np.int32),
+                     ("m_top", F * Fc * 2, np.float32), ("m_bot", F * Fc * 2, np.float32),
                      ("d_top", F * Fc * 32, np.uint8), ("d_bot", F * Fc * 32, np.uint8), ("X", F * Fc * 3, np.float64),
                      ("b_top", F * Fc * 3, np.float64), ("b_bot", F * Fc * 3, np.float64), ("M", F, np.int32),
-                     ("n_cand", F, np.int32), ("ref_frame", B, np.int32), ("cur_frame", B, np.int32),
+                     ("ref_frame", B, np.int32), ("cur_frame", B, np.int32),
                      ("k_top", B * Fc, np.uint32), ("k_bot", B * Fc, np.uint32), ("o_top", B * Fc, np.int32),
                      ("o_bot", B * Fc, np.int32), ("f", B * Cc * 3, np.float64), ("p", B * Cc * 3, np.float64),
                      ("cam", B * Cc, np.int32), ("cq", B * Cc, np.int32), ("ct", B * Cc, np.int32), ("cn", B, np.int32),

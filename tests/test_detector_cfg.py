@@ -3,6 +3,7 @@ field) and bits 8-9 of sosvo_rgbd_batch_cfg.flags -- keeps both structs' layout,
 workspace only for ORB, and sequence_engine_for / rgbd_sequence_engine_for build an engine per method (device calls
 replaced by a recorder)."""
 import ctypes
+import itertools
 
 import numpy as np
 import pytest
@@ -99,6 +100,137 @@ def test_workspace_sizes():
     c = _rgbd_cfg("GFT")
     c.flags = _lib.FLAG_GP3P
     assert rws(c) == rws(rg)
+
+
+# workspace sizes of the build before the carve functions of pipeline.hip were merged (one per engine family): the layout
+# inside a workspace is private, its size is what a host allocates
+# (detector, median_ksize, n_pairs): (pair batch, 2 streams, 3 streams, sequence 8 / 17, sequence 32 / 65); _cfg otherwise
+_OMNI_SIZES = {
+    (0, 7, 4): (35383040, 35386880, 35390720, 38184704, 148204032),
+    (0, 7, 64): (566076160, 566078464, 566083072, 56137472, 166156800),
+    (0, 11, 4): (18103040, 18106880, 18110720, 20904704, 79084032),
+    (0, 11, 64): (289596160, 289598464, 289603072, 38857472, 97036800),
+    (1, 7, 4): (48232448, 57153536, 66074624, 51034112, 172849920),
+    (1, 7, 64): (637907968, 646827520, 655749376, 68986880, 190802688),
+    (1, 11, 4): (30952448, 39873536, 48794624, 33754112, 103729920),
+    (1, 11, 64): (361427968, 370347520, 379269376, 51706880, 121682688),
+    (2, 7, 4): (35383040, 35386880, 35390720, 38184704, 148204032),
+    (2, 7, 64): (566076160, 566078464, 566083072, 56137472, 166156800),
+    (2, 11, 4): (18103040, 18106880, 18110720, 20904704, 79084032),
+    (2, 11, 64): (289596160, 289598464, 289603072, 38857472, 97036800),
+    (3, 7, 4): (35383040, 35386880, 35390720, 38184704, 148204032),
+    (3, 7, 64): (566076160, 566078464, 566083072, 56137472, 166156800),
+    (3, 11, 4): (18103040, 18106880, 18110720, 20904704, 79084032),
+    (3, 11, 64): (289596160, 289598464, 289603072, 38857472, 97036800),
+}
+# (method, n_pairs): (pair batch, sequence 8 / 17, sequence 32 / 65); _rgbd_cfg otherwise
+_RGBD_SIZES = {
+    ("GFT", 4): (3875584, 4737280, 17750528),
+    ("GFT", 64): (61968640, 9253888, 22267136),
+    ("ORB", 4): (7852032, 8713728, 22249216),
+    ("ORB", 64): (68556288, 13230336, 26765824),
+    ("FAST", 4): (3875584, 4737280, 17750528),
+    ("FAST", 64): (61968640, 9253888, 22267136),
+    ("AGAST", 4): (3875584, 4737280, 17750528),
+    ("AGAST", 64): (61968640, 9253888, 22267136),
+}
+
+
+def test_workspace_sizes_are_those_of_the_four_layout_build():
+    lib = _lib_or_skip()
+    for (det, median, n_pairs), want in _OMNI_SIZES.items():
+        c = _cfg(det)
+        c.median_ksize, c.n_pairs = median, n_pairs
+        r = ctypes.byref(c)
+        got = (lib.sosvo_frame_pair_batch_workspace(r), lib.sosvo_frame_pair_batch_streams_workspace(r, 2),
+               lib.sosvo_frame_pair_batch_streams_workspace(r, 3), lib.sosvo_sequence_workspace(r, 8, 17),
+               lib.sosvo_sequence_workspace(r, 32, 65))
+        assert got == want, (det, median, n_pairs)
+    for (method, n_pairs), want in _RGBD_SIZES.items():
+        c = _rgbd_cfg(method)
+        c.n_pairs = n_pairs
+        r = ctypes.byref(c)
+        got = (lib.sosvo_rgbd_pair_batch_workspace(r), lib.sosvo_rgbd_sequence_workspace(r, 8, 17),
+               lib.sosvo_rgbd_sequence_workspace(r, 32, 65))
+        assert got == want, (method, n_pairs)
+
+
+def test_a_pair_batch_is_the_sequence_layout_with_two_frames_per_pair():
+    """window = slots = 2 * n_pairs: the same set of buffers, so the same size (every slice is rounded on its own, so the
+    order of the slices does not enter)."""
+    lib = _lib_or_skip()
+    n = 0
+    for B, det, cap, nmask, median, (rows, cols) in itertools.product(
+            (1, 3, 64, 256), range(4), (512, 1024, 2048), (1, 12, 32), (0, 3, 7, 11), ((146, 1440), (300, 1200))):
+        c = _cfg(det, kp_cap=cap)
+        c.n_pairs, c.nmask, c.median_ksize, c.rows, c.cols = B, nmask, median, rows, cols
+        r = ctypes.byref(c)
+        assert lib.sosvo_frame_pair_batch_workspace(r) == lib.sosvo_sequence_workspace(r, 2 * B, 2 * B) > 0, \
+            (B, det, cap, nmask, median, rows, cols)
+        n += 1
+    for B, method, cap in itertools.product((1, 3, 64, 256), METHODS, (512, 1088, 2048)):
+        c = _rgbd_cfg(method, kp_cap=cap)
+        c.n_pairs = B
+        r = ctypes.byref(c)
+        assert lib.sosvo_rgbd_pair_batch_workspace(r) == lib.sosvo_rgbd_sequence_workspace(r, 2 * B, 2 * B) > 0, (B, method, cap)
+        n += 1
+    assert n == 1152 + 48
+
+
+def _fields(c):
+    return {name: getattr(c, name) for name, _ in c._fields_}
+
+
+def test_batch_cfg_builder_fills_every_field():
+    from types import SimpleNamespace
+    from vo_single_camera_sos_amd.pipeline import batch_cfg
+    model = SimpleNamespace(H=480, W=640, rows=146, cols=1440, nmask=24)
+    kw = dict(num_of_features=700, kp_cap=None, frame_cap=1536, median_win_size=5, quality=0.02, min_distance=7.5, edge=29,
+              thr=None, max_iter=333, adaptive=True, lm_iter=17, ransac_solver="gp3p", detection_method="orb")
+    c = batch_cfg(model, 6, seed=12345678901, **kw)
+    assert _fields(c) == dict(
+        n_pairs=6, H=480, W=640, rows=146, cols=1440, nmask=24, kp_cap=896, frame_cap=1536, median_ksize=5, max_corners=700,
+        edge=29, ransac_max_iter=333, ransac_adaptive=1, lm_max_iter=17, quality=0.02, min_distance=7.5,
+        ransac_threshold=0.003805301908254455, seed=12345678901, cos_a=0.9998477101325989, sin_a=-0.017452405765652657,
+        ransac_flags=4, detector=1)
+    assert set(_fields(c)) == {name for name, _ in _lib.BatchCfg._fields_} and len(_fields(c)) == 22
+    # an explicit capacity and threshold, any solver but GP3P is P3P, adaptive off
+    d = batch_cfg(model, 6, seed=0, **dict(kw, kp_cap=640, thr=0.25, adaptive=False, ransac_solver="P3P", detection_method="GFT"))
+    assert (d.kp_cap, d.ransac_threshold, d.ransac_adaptive, d.ransac_flags, d.detector) == (640, 0.25, 0, 0, _lib.DETECTOR_GFT)
+    # the pair batch and the sequence engine hand the library the same bytes once n_pairs and seed agree
+    a, b = batch_cfg(model, 5, seed=9, **kw), batch_cfg(model, 32, seed=0, **kw)
+    assert bytes(a) != bytes(b)
+    a.n_pairs, a.seed = 32, 0
+    assert bytes(a) == bytes(b)
+    with pytest.raises(NotImplementedError):
+        batch_cfg(model, 6, seed=0, **dict(kw, detection_method="SIFT"))
+
+
+def test_rgbd_batch_cfg_builder_fills_every_field():
+    from types import SimpleNamespace
+    from vo_single_camera_sos_amd.pipeline import rgbd_batch_cfg
+    cam = SimpleNamespace(pct_good_matches=0.75, f2f_max_hdiff=37.5)
+    kw = dict(image_shape=(240, 320), num_of_features=900, kp_cap=None, frame_cap=None, median_win_size=3, quality=0.02,
+              min_distance=7.5, edge=29, thr=0.125, max_iter=333, adaptive=False, lm_iter=17, pose_est_algorithm="TWOPT",
+              detection_method="AGAST")
+    c = rgbd_batch_cfg(cam, 6, seed=12345678901, **kw)
+    assert _fields(c) == dict(
+        n_pairs=6, rows=240, cols=320, kp_cap=4096, frame_cap=4096, median_ksize=3, max_corners=900, edge=29,
+        ransac_max_iter=333, ransac_adaptive=0, lm_max_iter=17, flags=8 | 768,
+        quality=0.02, min_distance=7.5, ransac_threshold=0.125, pct_good_matches=0.75, f2f_max_hdiff=37.5, seed=12345678901,
+        cos_a=0.9998477101325989, sin_a=-0.017452405765652657)
+    assert len(_fields(c)) == len(_lib.RgbdBatchCfg._fields_) == 20
+    d = rgbd_batch_cfg(cam, 6, seed=0, **dict(kw, kp_cap=512, frame_cap=300, thr=None, adaptive=True, pose_est_algorithm="EPNP",
+                                              detection_method="ORB"))
+    assert (d.kp_cap, d.frame_cap, d.ransac_threshold, d.ransac_adaptive) == (512, 300, 0.003805301908254455, 1)
+    assert d.flags == _lib.FLAG_EPNP | _lib.rgbd_detector_flags("ORB")
+    assert rgbd_batch_cfg(cam, 6, seed=0, **dict(kw, detection_method="ORB")).kp_cap == 1152
+    a, b = rgbd_batch_cfg(cam, 5, seed=9, **kw), rgbd_batch_cfg(cam, 32, seed=0, **kw)
+    assert bytes(a) != bytes(b)
+    a.n_pairs, a.seed = 32, 0
+    assert bytes(a) == bytes(b)
+    with pytest.raises(ValueError):
+        rgbd_batch_cfg(cam, 6, seed=0, **dict(kw, pose_est_algorithm="DLS"))
 
 
 # ---- engine choice (device calls replaced by a recorder) ---------------------------------------------------------------

@@ -41,72 +41,130 @@ bool detector_ok(int detector, int kp_cap) {
 }
 int rgbd_detector(const sosvo_rgbd_batch_cfg& c) { return SOSVO_RGBD_DETECTOR_OF(c.flags); }
 
-struct Buffers {
-  uint8_t *pano, *gray, *desc, *d_top, *d_bot, *mask;
-  float *kp, *m_top, *m_bot;
-  int32_t *n, *status, *s_order, *M, *n_cand, *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx,
-      *n_inl, *info, *lm_iters, *gray_rows;
-  uint32_t *s_keys, *k_top, *k_bot;
-  double *X, *b_top, *b_bot, *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
+// ---- the workspace of the omni family: front-end temporaries of one WINDOW of frames, a frame STORE of `slots` frame
+// records, tracking of up to cfg.n_pairs slot pairs per call.  The structs below are what the runners take; each is carved
+// member by member, so a buffer has one name from the carve to its use.
+struct FrontEndTmp {
+  uint8_t *pano, *gray, *desc;
+  float* kp;
+  int32_t *n, *status, *s_order, *n_cand, *gray_rows;
+  uint32_t* s_keys;
   OrbBufs orb;
+};
+FrontEndTmp carve_front_end(Carver& cv, const sosvo_batch_cfg& c, size_t F) {
+  FrontEndTmp t{};
+  const size_t NI = 2 * F, P = NI * c.nmask, cap = c.kp_cap, npx = (size_t)c.rows * c.cols;
+  const bool fused = c.median_ksize <= 1 || c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11;  // K1 inside the median / gray kernel
+  t.pano = fused ? nullptr : cv.take<uint8_t>(NI * npx * 3);
+  t.gray = cv.take<uint8_t>(NI * npx);
+  t.kp = cv.take<float>(P * cap * 2);
+  t.n = cv.take<int32_t>(P);
+  t.status = cv.take<int32_t>(P);
+  t.desc = cv.take<uint8_t>(P * cap * 32);
+  t.s_keys = cv.take<uint32_t>(P / 2 * cap);
+  t.s_order = cv.take<int32_t>(P / 2 * cap);
+  t.n_cand = cv.take<int32_t>(F);
+  t.gray_rows = cv.take<int32_t>(4);
+  return t;
+}
+
+// PanoramicCorrespondences as SoA, slot-major
+struct FrameStore {
+  float *m_top, *m_bot;
+  uint8_t *d_top, *d_bot;
+  double *X, *b_top, *b_bot;
+  int32_t* M;
+  FrameStore at(size_t slot, size_t Fc) const {  // the records from `slot` on
+    const size_t o = slot * Fc;
+    FrameStore v = *this;
+    v.m_top += 2 * o;
+    v.m_bot += 2 * o;
+    v.d_top += 32 * o;
+    v.d_bot += 32 * o;
+    v.X += 3 * o;
+    v.b_top += 3 * o;
+    v.b_bot += 3 * o;
+    v.M += slot;
+    return v;
+  }
+};
+FrameStore carve_store(Carver& cv, size_t S, size_t Fc) {
+  FrameStore s{};
+  s.m_top = cv.take<float>(S * Fc * 2);
+  s.m_bot = cv.take<float>(S * Fc * 2);
+  s.d_top = cv.take<uint8_t>(S * Fc * 32);
+  s.d_bot = cv.take<uint8_t>(S * Fc * 32);
+  s.X = cv.take<double>(S * Fc * 3);
+  s.b_top = cv.take<double>(S * Fc * 3);
+  s.b_bot = cv.take<double>(S * Fc * 3);
+  s.M = cv.take<int32_t>(S);
+  return s;
+}
+
+struct TrackTmp {
+  int32_t *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx, *n_inl, *info, *lm_iters;
+  uint32_t *k_top, *k_bot;
+  uint8_t* mask;
+  double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
+};
+TrackTmp carve_track(Carver& cv, size_t B, size_t Fc) {
+  TrackTmp t{};
+  const size_t Cc = 2 * Fc;
+  t.ref_frame = cv.take<int32_t>(B);
+  t.cur_frame = cv.take<int32_t>(B);
+  t.k_top = cv.take<uint32_t>(B * Fc);
+  t.k_bot = cv.take<uint32_t>(B * Fc);
+  t.o_top = cv.take<int32_t>(B * Fc);
+  t.o_bot = cv.take<int32_t>(B * Fc);
+  t.f = cv.take<double>(B * Cc * 3);
+  t.p = cv.take<double>(B * Cc * 3);
+  t.cam = cv.take<int32_t>(B * Cc);
+  t.cq = cv.take<int32_t>(B * Cc);
+  t.ct = cv.take<int32_t>(B * Cc);
+  t.cn = cv.take<int32_t>(B);
+  t.cn_top = cv.take<int32_t>(B);
+  t.T_ransac = cv.take<double>(B * 12);
+  t.mask = cv.take<uint8_t>(B * Cc);
+  t.idx = cv.take<int32_t>(B * Cc);
+  t.n_inl = cv.take<int32_t>(B);
+  t.info = cv.take<int32_t>(B * 4);
+  t.T = cv.take<double>(B * 12);
+  t.cam_off = cv.take<double>(2 * 3);
+  t.cam_rot = cv.take<double>(2 * 9);
+  t.lm_cost = cv.take<double>(B);
+  t.lm_iters = cv.take<int32_t>(B);
+  return t;
+}
+
+struct Workspace {
+  FrontEndTmp fe;
+  FrameStore store;
+  TrackTmp tt;
   size_t bytes;
 };
-
-Buffers carve(const sosvo_batch_cfg& c, void* ws) {
-  Carver cv{reinterpret_cast<char*>(ws)};
-  Buffers b;
-  const size_t B = c.n_pairs, F = 2 * B, NI = 2 * F, P = NI * c.nmask, cap = c.kp_cap, Fc = c.frame_cap, Cc = 2 * Fc;
-  const size_t npx = (size_t)c.rows * c.cols;
-  const bool fused = c.median_ksize <= 1 || c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11;  // K1 inside the median / gray kernel
-  b.pano = fused ? nullptr : cv.take<uint8_t>(NI * npx * 3);
-  b.gray = cv.take<uint8_t>(NI * npx);
-  b.kp = cv.take<float>(P * cap * 2);
-  b.n = cv.take<int32_t>(P);
-  b.status = cv.take<int32_t>(P);
-  b.desc = cv.take<uint8_t>(P * cap * 32);
-  b.s_keys = cv.take<uint32_t>(P / 2 * cap);
-  b.s_order = cv.take<int32_t>(P / 2 * cap);
-  b.m_top = cv.take<float>(F * Fc * 2);
-  b.m_bot = cv.take<float>(F * Fc * 2);
-  b.d_top = cv.take<uint8_t>(F * Fc * 32);
-  b.d_bot = cv.take<uint8_t>(F * Fc * 32);
-  b.X = cv.take<double>(F * Fc * 3);
-  b.b_top = cv.take<double>(F * Fc * 3);
-  b.b_bot = cv.take<double>(F * Fc * 3);
-  b.M = cv.take<int32_t>(F);
-  b.n_cand = cv.take<int32_t>(F);
-  b.ref_frame = cv.take<int32_t>(B);
-  b.cur_frame = cv.take<int32_t>(B);
-  b.k_top = cv.take<uint32_t>(B * Fc);
-  b.k_bot = cv.take<uint32_t>(B * Fc);
-  b.o_top = cv.take<int32_t>(B * Fc);
-  b.o_bot = cv.take<int32_t>(B * Fc);
-  b.f = cv.take<double>(B * Cc * 3);
-  b.p = cv.take<double>(B * Cc * 3);
-  b.cam = cv.take<int32_t>(B * Cc);
-  b.cq = cv.take<int32_t>(B * Cc);
-  b.ct = cv.take<int32_t>(B * Cc);
-  b.cn = cv.take<int32_t>(B);
-  b.cn_top = cv.take<int32_t>(B);
-  b.T_ransac = cv.take<double>(B * 12);
-  b.mask = cv.take<uint8_t>(B * Cc);
-  b.idx = cv.take<int32_t>(B * Cc);
-  b.n_inl = cv.take<int32_t>(B);
-  b.info = cv.take<int32_t>(B * 4);
-  b.T = cv.take<double>(B * 12);
-  b.cam_off = cv.take<double>(2 * 3);
-  b.cam_rot = cv.take<double>(2 * 9);
-  b.lm_cost = cv.take<double>(B);
-  b.lm_iters = cv.take<int32_t>(B);
-  b.gray_rows = cv.take<int32_t>(4);
-  b.orb = carve_orb(cv, c.detector, P, cap, 2, c.rows, c.cols);
-  b.bytes = cv.off;
-  return b;
+// (a pair batch is the sequence layout with window = slots = 2 * n_pairs; base == nullptr: sizes only)
+Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* base) {
+  Carver cv{reinterpret_cast<char*>(base)};
+  Workspace ws;
+  ws.fe = carve_front_end(cv, c, window);
+  ws.store = carve_store(cv, slots, c.frame_cap);
+  ws.tt = carve_track(cv, c.n_pairs, c.frame_cap);
+  ws.fe.orb = carve_orb(cv, c.detector, 2 * window * c.nmask, c.kp_cap, 2, c.rows, c.cols);
+  ws.bytes = cv.off;
+  return ws;
 }
 
 struct Foci {
   double top[3], bot[3];
 };
+Foci foci_of(const sosvo_rig* rig) {
+  Foci foci;
+  for (int k = 0; k < 3; ++k) {
+    foci.top[k] = rig->F_top[k];
+    foci.bot[k] = rig->F_bot[k];
+  }
+  return foci;
+}
 
 // pair i tracks frame 2i + 1 against frame 2i; the two mirrors' foci are the non-central rig (identity rotations)
 __global__ void batch_setup_kernel(int npairs, Foci foci, int32_t* __restrict__ ref_frame, int32_t* __restrict__ cur_frame,
@@ -136,79 +194,8 @@ __global__ void batch_results_kernel(int npairs, const double* __restrict__ T, c
   out[16 * i + 15] = (double)info[4 * i + 0];
 }
 
-// ---- sequence mode: a frame STORE of `slots` frame records, a front end over a WINDOW of frames, tracking of slot pairs ----
-struct SeqBuffers {
-  // front-end temporaries of one window
-  uint8_t *pano, *gray, *desc;
-  float* kp;
-  int32_t *n, *status, *s_order, *n_cand, *gray_rows;
-  uint32_t* s_keys;
-  // the frame store (PanoramicCorrespondences as SoA, slot-major)
-  uint8_t *d_top, *d_bot;
-  float *m_top, *m_bot;
-  double *X, *b_top, *b_bot;
-  int32_t* M;
-  // tracking of up to cfg.n_pairs slot pairs per call
-  uint8_t* mask;
-  int32_t *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx, *n_inl, *info, *lm_iters;
-  uint32_t *k_top, *k_bot;
-  double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
-  OrbBufs orb;
-  size_t bytes;
-};
 
-SeqBuffers carve_seq(const sosvo_batch_cfg& c, int window, int slots, void* ws) {
-  Carver cv{reinterpret_cast<char*>(ws)};
-  SeqBuffers b;
-  const size_t B = c.n_pairs, F = window, NI = 2 * F, P = NI * c.nmask, cap = c.kp_cap, Fc = c.frame_cap, Cc = 2 * Fc, S = slots;
-  const size_t npx = (size_t)c.rows * c.cols;
-  const bool fused = c.median_ksize <= 1 || c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11;
-  b.pano = fused ? nullptr : cv.take<uint8_t>(NI * npx * 3);
-  b.gray = cv.take<uint8_t>(NI * npx);
-  b.kp = cv.take<float>(P * cap * 2);
-  b.n = cv.take<int32_t>(P);
-  b.status = cv.take<int32_t>(P);
-  b.desc = cv.take<uint8_t>(P * cap * 32);
-  b.s_keys = cv.take<uint32_t>(P / 2 * cap);
-  b.s_order = cv.take<int32_t>(P / 2 * cap);
-  b.n_cand = cv.take<int32_t>(F);
-  b.gray_rows = cv.take<int32_t>(4);
-  b.m_top = cv.take<float>(S * Fc * 2);
-  b.m_bot = cv.take<float>(S * Fc * 2);
-  b.d_top = cv.take<uint8_t>(S * Fc * 32);
-  b.d_bot = cv.take<uint8_t>(S * Fc * 32);
-  b.X = cv.take<double>(S * Fc * 3);
-  b.b_top = cv.take<double>(S * Fc * 3);
-  b.b_bot = cv.take<double>(S * Fc * 3);
-  b.M = cv.take<int32_t>(S);
-  b.ref_frame = cv.take<int32_t>(B);
-  b.cur_frame = cv.take<int32_t>(B);
-  b.k_top = cv.take<uint32_t>(B * Fc);
-  b.k_bot = cv.take<uint32_t>(B * Fc);
-  b.o_top = cv.take<int32_t>(B * Fc);
-  b.o_bot = cv.take<int32_t>(B * Fc);
-  b.f = cv.take<double>(B * Cc * 3);
-  b.p = cv.take<double>(B * Cc * 3);
-  b.cam = cv.take<int32_t>(B * Cc);
-  b.cq = cv.take<int32_t>(B * Cc);
-  b.ct = cv.take<int32_t>(B * Cc);
-  b.cn = cv.take<int32_t>(B);
-  b.cn_top = cv.take<int32_t>(B);
-  b.T_ransac = cv.take<double>(B * 12);
-  b.mask = cv.take<uint8_t>(B * Cc);
-  b.idx = cv.take<int32_t>(B * Cc);
-  b.n_inl = cv.take<int32_t>(B);
-  b.info = cv.take<int32_t>(B * 4);
-  b.T = cv.take<double>(B * 12);
-  b.cam_off = cv.take<double>(2 * 3);
-  b.cam_rot = cv.take<double>(2 * 9);
-  b.lm_cost = cv.take<double>(B);
-  b.lm_iters = cv.take<int32_t>(B);
-  b.orb = carve_orb(cv, c.detector, P, cap, 2, c.rows, c.cols);
-  b.bytes = cv.off;
-  return b;
-}
-
+// ---- sequence mode: the front end over a WINDOW of frames writes into the store, slot pairs of the store are tracked ----
 constexpr int kSeqArgPairs = 16;  // slot pairs that travel as kernel arguments (no host-to-device copy per call)
 struct SlotPairs {
   int32_t ref[kSeqArgPairs], cur[kSeqArgPairs];
@@ -251,104 +238,94 @@ __global__ void seq_copy_slot_kernel(int src, int dst, int Fc, float* m_top, flo
   if (blockIdx.x == 0 && threadIdx.x == 0) M[dst] = n;
 }
 
-// ---- RGB-D variant (BASELINE config 5) ------------------------------------------------------------------
-struct RgbdBuffers {
-  uint8_t *gray, *desc, *d, *mask;
-  float *kp, *m;
-  int32_t *n, *status, *M, *ref_frame, *cur_frame, *order, *cq, *ct, *cn, *idx, *n_inl, *info, *lm_iters;
-  uint32_t* keys;
-  double *X, *b, *f, *p, *T_ransac, *T, *lm_cost;
-  OrbBufs orb;
-  size_t bytes;
-};
-
-RgbdBuffers carve_rgbd(const sosvo_rgbd_batch_cfg& c, void* ws) {
-  Carver cv{reinterpret_cast<char*>(ws)};
-  RgbdBuffers b;
-  const size_t B = c.n_pairs, F = 2 * B, cap = c.kp_cap, Fc = c.frame_cap, npx = (size_t)c.rows * c.cols;
-  b.gray = cv.take<uint8_t>(F * npx);
-  b.kp = cv.take<float>(F * cap * 2);
-  b.n = cv.take<int32_t>(F);
-  b.status = cv.take<int32_t>(F);
-  b.desc = cv.take<uint8_t>(F * cap * 32);
-  b.m = cv.take<float>(F * Fc * 2);
-  b.d = cv.take<uint8_t>(F * Fc * 32);
-  b.X = cv.take<double>(F * Fc * 3);
-  b.b = cv.take<double>(F * Fc * 3);
-  b.M = cv.take<int32_t>(F);
-  b.ref_frame = cv.take<int32_t>(B);
-  b.cur_frame = cv.take<int32_t>(B);
-  b.keys = cv.take<uint32_t>(B * Fc);
-  b.order = cv.take<int32_t>(B * Fc);
-  b.f = cv.take<double>(B * Fc * 3);
-  b.p = cv.take<double>(B * Fc * 3);
-  b.cq = cv.take<int32_t>(B * Fc);
-  b.ct = cv.take<int32_t>(B * Fc);
-  b.cn = cv.take<int32_t>(B);
-  b.T_ransac = cv.take<double>(B * 12);
-  b.mask = cv.take<uint8_t>(B * Fc);
-  b.idx = cv.take<int32_t>(B * Fc);
-  b.n_inl = cv.take<int32_t>(B);
-  b.info = cv.take<int32_t>(B * 4);
-  b.T = cv.take<double>(B * 12);
-  b.lm_cost = cv.take<double>(B);
-  b.lm_iters = cv.take<int32_t>(B);
-  b.orb = carve_orb(cv, rgbd_detector(c), F, cap, 1, c.rows, c.cols);
-  b.bytes = cv.off;
-  return b;
-}
-
-// RGB-D sequence mode: a store of `slots` RGBDFrame records (keypoints with valid depth, descriptors, points, bearings)
-struct RgbdSeqBuffers {
-  uint8_t *gray, *desc;                        // front-end temporaries of one window
+// ---- RGB-D variant (BASELINE config 5): the same three parts; a store of `slots` RGBDFrame records (keypoints with valid
+// depth, descriptors, points, bearings)
+struct RgbdFrontTmp {
+  uint8_t *gray, *desc;
   float* kp;
   int32_t *n, *status;
-  uint8_t* d;                                  // the frame store (slot-major)
+  OrbBufs orb;
+};
+RgbdFrontTmp carve_rgbd_front_end(Carver& cv, const sosvo_rgbd_batch_cfg& c, size_t F) {
+  RgbdFrontTmp t{};
+  const size_t cap = c.kp_cap;
+  t.gray = cv.take<uint8_t>(F * ((size_t)c.rows * c.cols));
+  t.kp = cv.take<float>(F * cap * 2);
+  t.n = cv.take<int32_t>(F);
+  t.status = cv.take<int32_t>(F);
+  t.desc = cv.take<uint8_t>(F * cap * 32);
+  return t;
+}
+
+struct RgbdStore {
   float* m;
+  uint8_t* d;
   double *X, *b;
   int32_t* M;
-  uint8_t* mask;                               // tracking of up to cfg.n_pairs slot pairs per call
+  RgbdStore at(size_t slot, size_t Fc) const {  // the records from `slot` on
+    const size_t o = slot * Fc;
+    RgbdStore v = *this;
+    v.m += 2 * o;
+    v.d += 32 * o;
+    v.X += 3 * o;
+    v.b += 3 * o;
+    v.M += slot;
+    return v;
+  }
+};
+RgbdStore carve_rgbd_store(Carver& cv, size_t S, size_t Fc) {
+  RgbdStore s{};
+  s.m = cv.take<float>(S * Fc * 2);
+  s.d = cv.take<uint8_t>(S * Fc * 32);
+  s.X = cv.take<double>(S * Fc * 3);
+  s.b = cv.take<double>(S * Fc * 3);
+  s.M = cv.take<int32_t>(S);
+  return s;
+}
+
+struct RgbdTrackTmp {
   int32_t *ref_frame, *cur_frame, *order, *cq, *ct, *cn, *idx, *n_inl, *info, *lm_iters;
   uint32_t* keys;
+  uint8_t* mask;
   double *f, *p, *T_ransac, *T, *lm_cost;
-  OrbBufs orb;
+};
+RgbdTrackTmp carve_rgbd_track(Carver& cv, size_t B, size_t Fc) {
+  RgbdTrackTmp t{};
+  t.ref_frame = cv.take<int32_t>(B);
+  t.cur_frame = cv.take<int32_t>(B);
+  t.keys = cv.take<uint32_t>(B * Fc);
+  t.order = cv.take<int32_t>(B * Fc);
+  t.f = cv.take<double>(B * Fc * 3);
+  t.p = cv.take<double>(B * Fc * 3);
+  t.cq = cv.take<int32_t>(B * Fc);
+  t.ct = cv.take<int32_t>(B * Fc);
+  t.cn = cv.take<int32_t>(B);
+  t.T_ransac = cv.take<double>(B * 12);
+  t.mask = cv.take<uint8_t>(B * Fc);
+  t.idx = cv.take<int32_t>(B * Fc);
+  t.n_inl = cv.take<int32_t>(B);
+  t.info = cv.take<int32_t>(B * 4);
+  t.T = cv.take<double>(B * 12);
+  t.lm_cost = cv.take<double>(B);
+  t.lm_iters = cv.take<int32_t>(B);
+  return t;
+}
+
+struct RgbdWorkspace {
+  RgbdFrontTmp fe;
+  RgbdStore store;
+  RgbdTrackTmp tt;
   size_t bytes;
 };
-
-RgbdSeqBuffers carve_rgbd_seq(const sosvo_rgbd_batch_cfg& c, int window, int slots, void* ws) {
-  Carver cv{reinterpret_cast<char*>(ws)};
-  RgbdSeqBuffers b;
-  const size_t B = c.n_pairs, F = window, S = slots, cap = c.kp_cap, Fc = c.frame_cap, npx = (size_t)c.rows * c.cols;
-  b.gray = cv.take<uint8_t>(F * npx);
-  b.kp = cv.take<float>(F * cap * 2);
-  b.n = cv.take<int32_t>(F);
-  b.status = cv.take<int32_t>(F);
-  b.desc = cv.take<uint8_t>(F * cap * 32);
-  b.m = cv.take<float>(S * Fc * 2);
-  b.d = cv.take<uint8_t>(S * Fc * 32);
-  b.X = cv.take<double>(S * Fc * 3);
-  b.b = cv.take<double>(S * Fc * 3);
-  b.M = cv.take<int32_t>(S);
-  b.ref_frame = cv.take<int32_t>(B);
-  b.cur_frame = cv.take<int32_t>(B);
-  b.keys = cv.take<uint32_t>(B * Fc);
-  b.order = cv.take<int32_t>(B * Fc);
-  b.f = cv.take<double>(B * Fc * 3);
-  b.p = cv.take<double>(B * Fc * 3);
-  b.cq = cv.take<int32_t>(B * Fc);
-  b.ct = cv.take<int32_t>(B * Fc);
-  b.cn = cv.take<int32_t>(B);
-  b.T_ransac = cv.take<double>(B * 12);
-  b.mask = cv.take<uint8_t>(B * Fc);
-  b.idx = cv.take<int32_t>(B * Fc);
-  b.n_inl = cv.take<int32_t>(B);
-  b.info = cv.take<int32_t>(B * 4);
-  b.T = cv.take<double>(B * 12);
-  b.lm_cost = cv.take<double>(B);
-  b.lm_iters = cv.take<int32_t>(B);
-  b.orb = carve_orb(cv, rgbd_detector(c), F, cap, 1, c.rows, c.cols);
-  b.bytes = cv.off;
-  return b;
+RgbdWorkspace carve_rgbd(const sosvo_rgbd_batch_cfg& c, size_t window, size_t slots, void* base) {
+  Carver cv{reinterpret_cast<char*>(base)};
+  RgbdWorkspace ws;
+  ws.fe = carve_rgbd_front_end(cv, c, window);
+  ws.store = carve_rgbd_store(cv, slots, c.frame_cap);
+  ws.tt = carve_rgbd_track(cv, c.n_pairs, c.frame_cap);
+  ws.fe.orb = carve_orb(cv, rgbd_detector(c), window, c.kp_cap, 1, c.rows, c.cols);
+  ws.bytes = cv.off;
+  return ws;
 }
 
 __global__ void rgbd_seq_setup_kernel(int npairs, SlotPairs sp, int32_t* __restrict__ ref_frame, int32_t* __restrict__ cur_frame) {
@@ -384,6 +361,31 @@ __global__ void pair_index_kernel(int npairs, int32_t* __restrict__ ref_frame, i
   }
 }
 
+// SOSVO_REQUIRE for a helper of the entry points: the error names the entry point `fn`, not the helper
+#define REQUIRE_FOR(ctx, fn, cond, msg)                                \
+  do {                                                                 \
+    if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, (fn), msg);   \
+  } while (0)
+
+// The slot pairs of a sequence tracking call (entry point `fn`), checked against the store (host arrays: a bad slot would
+// index outside the store on the device).  Up to kSeqArgPairs come back in `sp` for the family's setup kernel; larger
+// batches are copied to b.ref_frame / b.cur_frame (pageable host memory: the copy returns when staged).
+template <typename Track>
+int32_t upload_slot_pairs(sosvo_ctx* ctx, const char* fn, const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs,
+                          int32_t slots, const Track& b, SlotPairs& sp) {
+  for (int i = 0; i < n_pairs; ++i)
+    REQUIRE_FOR(ctx, fn, ref_slot[i] >= 0 && ref_slot[i] < slots && cur_slot[i] >= 0 && cur_slot[i] < slots, "slot out of range");
+  for (int i = 0; i < kSeqArgPairs; ++i) {
+    sp.ref[i] = i < n_pairs ? ref_slot[i] : 0;
+    sp.cur[i] = i < n_pairs ? cur_slot[i] : 0;
+  }
+  if (n_pairs > kSeqArgPairs) {
+    SOSVO_HIP(ctx, hipMemcpyAsync(b.ref_frame, ref_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+    SOSVO_HIP(ctx, hipMemcpyAsync(b.cur_frame, cur_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return SOSVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,7 +394,10 @@ size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->nmask <= 0 || cfg->kp_cap <= 0 ||
       cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap))
     return 0;
-  return carve(*cfg, nullptr).bytes;
+  // (laxer than the call itself, which refuses nmask > 32, kp_cap > 4096 and frame_cap > 16384: such a shape gets a size
+  // here and "out of range" there)
+  const size_t F = 2 * (size_t)cfg->n_pairs;
+  return carve(*cfg, F, F, nullptr).bytes;
 }
 
 #define STAGE(call)              \
@@ -404,19 +409,6 @@ size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
 // The image front end + static stereo of F frames (OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__,
 // camera_models.py:3107-3120, pose_est_tools.py:271-402): K1, K2 + K3, K4, K6 over all 2 F panoramas, per-bucket top/bottom
 // matching, gates, bearings, midpoint triangulation, range filter -> F frame records written at out_* (frame-major).
-struct FrontEndTmp {
-  uint8_t *pano, *gray, *desc;
-  float* kp;
-  int32_t *n, *status, *s_order, *n_cand, *gray_rows;
-  uint32_t* s_keys;
-  OrbBufs orb;
-};
-struct FrameStore {
-  float *m_top, *m_bot;
-  uint8_t *d_top, *d_bot;
-  double *X, *b_top, *b_bot;
-  int32_t* M;
-};
 static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int F, const uint8_t* omni,
                              const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
                              const FrontEndTmp& t, const FrameStore& o, hipEvent_t median_wait, hipEvent_t median_done) {
@@ -476,12 +468,6 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
 // TrackerStereoSE3.track_frame (pose_est_tools.py:736-847) for B (reference slot, current slot) pairs of a frame store:
 // frame-to-frame matching per view (query = current frame, train = reference frame), |du| gate, stacking, non-central
 // RANSAC (problem i samples with seed + i), LM on the inliers, [B,16] records.
-struct TrackTmp {
-  int32_t *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx, *n_inl, *info, *lm_iters;
-  uint32_t *k_top, *k_bot;
-  uint8_t* mask;
-  double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
-};
 static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, uint64_t seed,
                             const FrameStore& s, const TrackTmp& b, double* results) {
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
@@ -519,24 +505,15 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_REQUIRE(ctx, cfg->frame_cap > 0 && cfg->frame_cap <= 16384, "frame_cap out of range (max 16384)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const Buffers b = carve(*cfg, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_frame_pair_batch_workspace)");
   const int B = cfg->n_pairs, F = 2 * B;
+  const Workspace ws = carve(*cfg, F, F, workspace);
+  SOSVO_REQUIRE(ctx, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_frame_pair_batch_workspace)");
   int32_t rc;
-  Foci foci;
-  for (int k = 0; k < 3; ++k) {
-    foci.top[k] = rig->F_top[k];
-    foci.bot[k] = rig->F_bot[k];
-  }
-  SOSVO_LAUNCH(ctx, batch_setup_kernel, dim3(cdiv(B > 18 ? B : 18, 256)), dim3(256), 0, ctx->stream, B, foci, b.ref_frame,
-               b.cur_frame, b.cam_off, b.cam_rot);
+  SOSVO_LAUNCH(ctx, batch_setup_kernel, dim3(cdiv(B > 18 ? B : 18, 256)), dim3(256), 0, ctx->stream, B, foci_of(rig),
+               ws.tt.ref_frame, ws.tt.cur_frame, ws.tt.cam_off, ws.tt.cam_rot);
   SOSVO_LAUNCH_CHECK(ctx);
-  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys, b.orb};
-  const FrameStore store{b.m_top, b.m_bot, b.d_top, b.d_bot, b.X, b.b_top, b.b_bot, b.M};
-  STAGE(run_front_end(ctx, rig, cfg, F, omni, unwrap_table, mask_bits, pattern, fe, store, median_wait, median_done));
-  const TrackTmp tt{b.ref_frame, b.cur_frame, b.o_top, b.o_bot, b.cam, b.cq, b.ct, b.cn, b.cn_top, b.idx, b.n_inl, b.info,
-                    b.lm_iters, b.k_top, b.k_bot, b.mask, b.f, b.p, b.T_ransac, b.T, b.cam_off, b.cam_rot, b.lm_cost};
-  return run_tracking(ctx, rig, cfg, B, cfg->seed, store, tt, results);
+  STAGE(run_front_end(ctx, rig, cfg, F, omni, unwrap_table, mask_bits, pattern, ws.fe, ws.store, median_wait, median_done));
+  return run_tracking(ctx, rig, cfg, B, cfg->seed, ws.store, ws.tt, results);
 }
 
 int32_t sosvo_frame_pair_batch(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, const uint8_t* omni,
@@ -696,7 +673,20 @@ static bool seq_shape_ok(const sosvo_batch_cfg* cfg, int32_t window, int32_t slo
 
 size_t sosvo_sequence_workspace(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
   if (!seq_shape_ok(cfg, window, slots)) return 0;
-  return carve_seq(*cfg, window, slots, nullptr).bytes;
+  return carve(*cfg, window, slots, nullptr).bytes;
+}
+
+// What every sosvo_sequence_* call checks after its own null check, in this order: the shape, the call's own range
+// (range_ok, range_msg), the alignment (aligned == false: sosvo_sequence_frame_counts, which only reads and never asked
+// for it), the size.  Errors carry the entry point's name `fn`; on SOSVO_OK `ws` is the carved workspace.
+static int32_t seq_open(sosvo_ctx* ctx, const char* fn, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, bool range_ok,
+                        const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes, Workspace& ws) {
+  REQUIRE_FOR(ctx, fn, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
+  REQUIRE_FOR(ctx, fn, range_ok, range_msg);
+  if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  ws = carve(*cfg, window, slots, workspace);
+  REQUIRE_FOR(ctx, fn, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_sequence_workspace)");
+  return SOSVO_OK;
 }
 
 int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -704,18 +694,14 @@ int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sos
                                  const uint32_t* mask_bits, const int8_t* pattern, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace, "null pointer");
-  SOSVO_REQUIRE(ctx, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
-                "frames do not fit the window / the store");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const SeqBuffers b = carve_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_sequence_workspace)");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots,
+                 n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
+                 "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
   if (n_frames == 0) return SOSVO_OK;
-  const size_t Fc = cfg->frame_cap, o = (size_t)first_slot * Fc;
-  const FrontEndTmp fe{b.pano, b.gray, b.desc, b.kp, b.n, b.status, b.s_order, b.n_cand, b.gray_rows, b.s_keys, b.orb};
-  const FrameStore out{b.m_top + 2 * o, b.m_bot + 2 * o, b.d_top + 32 * o, b.d_bot + 32 * o,
-                       b.X + 3 * o, b.b_top + 3 * o, b.b_bot + 3 * o, b.M + first_slot};
-  return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, fe, out, nullptr, nullptr);
+  return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, ws.fe,
+                       ws.store.at(first_slot, cfg->frame_cap), nullptr, nullptr);
 }
 
 int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -723,49 +709,32 @@ int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
                              size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && workspace && results, "null pointer");
-  SOSVO_REQUIRE(ctx, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const SeqBuffers b = carve_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_sequence_workspace)");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs",
+                 true, workspace, workspace_bytes, ws));
   if (n_pairs == 0) return SOSVO_OK;
-  for (int i = 0; i < n_pairs; ++i)   // host arrays: a bad slot would index outside the store on the device
-    SOSVO_REQUIRE(ctx, ref_slot[i] >= 0 && ref_slot[i] < slots && cur_slot[i] >= 0 && cur_slot[i] < slots, "slot out of range");
-  Foci foci;
-  for (int k = 0; k < 3; ++k) {
-    foci.top[k] = rig->F_top[k];
-    foci.bot[k] = rig->F_bot[k];
-  }
   SlotPairs sp;
-  for (int i = 0; i < kSeqArgPairs; ++i) {
-    sp.ref[i] = i < n_pairs ? ref_slot[i] : 0;
-    sp.cur[i] = i < n_pairs ? cur_slot[i] : 0;
-  }
-  if (n_pairs > kSeqArgPairs) {  // larger batches: the slot lists are copied (pageable host memory: the copy returns when staged)
-    SOSVO_HIP(ctx, hipMemcpyAsync(b.ref_frame, ref_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    SOSVO_HIP(ctx, hipMemcpyAsync(b.cur_frame, cur_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-  }
-  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, foci, b.ref_frame,
-               b.cur_frame, b.cam_off, b.cam_rot);
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, n_pairs, slots, ws.tt, sp));
+  // (always launched, copied slot lists or not: it also writes cam_off / cam_rot)
+  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, foci_of(rig),
+               ws.tt.ref_frame, ws.tt.cur_frame, ws.tt.cam_off, ws.tt.cam_rot);
   SOSVO_LAUNCH_CHECK(ctx);
-  const FrameStore store{b.m_top, b.m_bot, b.d_top, b.d_bot, b.X, b.b_top, b.b_bot, b.M};
-  const TrackTmp tt{b.ref_frame, b.cur_frame, b.o_top, b.o_bot, b.cam, b.cq, b.ct, b.cn, b.cn_top, b.idx, b.n_inl, b.info,
-                    b.lm_iters, b.k_top, b.k_bot, b.mask, b.f, b.p, b.T_ransac, b.T, b.cam_off, b.cam_rot, b.lm_cost};
-  return run_tracking(ctx, rig, cfg, n_pairs, seed, store, tt, results);
+  return run_tracking(ctx, rig, cfg, n_pairs, seed, ws.store, ws.tt, results);
 }
 
 int32_t sosvo_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t src_slot,
                                  int32_t dst_slot, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace, "null pointer");
-  SOSVO_REQUIRE(ctx, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots, "slot out of range");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const SeqBuffers b = carve_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_sequence_workspace)");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots,
+                 "slot out of range", true, workspace, workspace_bytes, ws));
   if (src_slot == dst_slot) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx, seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, b.m_top,
-               b.m_bot, reinterpret_cast<uint4*>(b.d_top), reinterpret_cast<uint4*>(b.d_bot), b.X, b.b_top, b.b_bot, b.M);
+  const FrameStore& s = ws.store;
+  SOSVO_LAUNCH(ctx, seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m_top,
+               s.m_bot, reinterpret_cast<uint4*>(s.d_top), reinterpret_cast<uint4*>(s.d_bot), s.X, s.b_top, s.b_bot, s.M);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }
@@ -774,12 +743,12 @@ int32_t sosvo_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, 
                                     int32_t n, void* workspace, size_t workspace_bytes, int32_t* counts_host) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace && counts_host, "null pointer");
-  SOSVO_REQUIRE(ctx, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, first_slot >= 0 && n >= 0 && first_slot + n <= slots, "slots out of range");
-  const SeqBuffers b = carve_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_sequence_workspace)");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, first_slot >= 0 && n >= 0 && first_slot + n <= slots, "slots out of range",
+                 false, workspace, workspace_bytes, ws));
   if (n == 0) return SOSVO_OK;
-  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, b.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, ws.store.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
   SOSVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SOSVO_OK;
 }
@@ -788,24 +757,13 @@ size_t sosvo_rgbd_pair_batch_workspace(const sosvo_rgbd_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->kp_cap <= 0 || cfg->frame_cap <= 0 ||
       !detector_ok(rgbd_detector(*cfg), cfg->kp_cap))
     return 0;
-  return carve_rgbd(*cfg, nullptr).bytes;
+  const size_t F = 2 * (size_t)cfg->n_pairs;
+  return carve_rgbd(*cfg, F, F, nullptr).bytes;
 }
 
 // RGBDFrame.establish_keypoints for F frames (pose_est_tools.py:600-623): [median,] gray, whole-image detection (one mask;
 // GFT, ORB, FAST or AGAST), ORB descriptors, depth back-projection + range filter + bearings -> F frame records at the store
 // pointers.
-struct RgbdFrontTmp {
-  uint8_t *gray, *desc;
-  float* kp;
-  int32_t *n, *status;
-  OrbBufs orb;
-};
-struct RgbdStore {
-  float* m;
-  uint8_t* d;
-  double *X, *b;
-  int32_t* M;
-};
 static int32_t run_rgbd_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg, int F,
                                   const uint8_t* bgr, const float* depth, const uint32_t* mask_bits, const int8_t* pattern,
                                   const RgbdFrontTmp& t, const RgbdStore& o) {
@@ -833,12 +791,6 @@ static int32_t run_rgbd_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, con
 
 // TrackerRGBDSE3.track_frame (pose_est_tools.py:896-954) for B (reference slot, current slot) pairs of a frame store:
 // query = current frame, train = reference frame; central RANSAC (problem i samples with seed + i) + LM.
-struct RgbdTrackTmp {
-  int32_t *ref_frame, *cur_frame, *order, *cq, *ct, *cn, *idx, *n_inl, *info, *lm_iters;
-  uint32_t* keys;
-  uint8_t* mask;
-  double *f, *p, *T_ransac, *T, *lm_cost;
-};
 static int32_t run_rgbd_tracking(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int B, uint64_t seed, const RgbdStore& s,
                                  const RgbdTrackTmp& b, double* results) {
   const int Fc = cfg->frame_cap;
@@ -870,18 +822,14 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
                 "kp_cap / frame_cap out of range");
   SOSVO_REQUIRE(ctx, detector_ok(rgbd_detector(*cfg), cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const RgbdBuffers b = carve_rgbd(*cfg, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_pair_batch_workspace)");
   const int B = cfg->n_pairs, F = 2 * B;
+  const RgbdWorkspace ws = carve_rgbd(*cfg, F, F, workspace);
+  SOSVO_REQUIRE(ctx, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_rgbd_pair_batch_workspace)");
   int32_t rc;
-  SOSVO_LAUNCH(ctx, pair_index_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, B, b.ref_frame, b.cur_frame);
+  SOSVO_LAUNCH(ctx, pair_index_kernel, dim3(cdiv(B, 256)), dim3(256), 0, ctx->stream, B, ws.tt.ref_frame, ws.tt.cur_frame);
   SOSVO_LAUNCH_CHECK(ctx);
-  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status, b.orb};
-  const RgbdStore store{b.m, b.d, b.X, b.b, b.M};
-  STAGE(run_rgbd_front_end(ctx, cam, cfg, F, bgr, depth, mask_bits, pattern, fe, store));
-  const RgbdTrackTmp tt{b.ref_frame, b.cur_frame, b.order, b.cq, b.ct, b.cn, b.idx, b.n_inl, b.info, b.lm_iters, b.keys, b.mask,
-                        b.f, b.p, b.T_ransac, b.T, b.lm_cost};
-  return run_rgbd_tracking(ctx, cfg, B, cfg->seed, store, tt, results);
+  STAGE(run_rgbd_front_end(ctx, cam, cfg, F, bgr, depth, mask_bits, pattern, ws.fe, ws.store));
+  return run_rgbd_tracking(ctx, cfg, B, cfg->seed, ws.store, ws.tt, results);
 }
 
 // ---- RGB-D sequence mode -------------------------------------------------------------------------------------
@@ -893,7 +841,19 @@ static bool rgbd_seq_shape_ok(const sosvo_rgbd_batch_cfg* cfg, int32_t window, i
 
 size_t sosvo_rgbd_sequence_workspace(const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots) {
   if (!rgbd_seq_shape_ok(cfg, window, slots)) return 0;
-  return carve_rgbd_seq(*cfg, window, slots, nullptr).bytes;
+  return carve_rgbd(*cfg, window, slots, nullptr).bytes;
+}
+
+// seq_open for the sosvo_rgbd_sequence_* calls (aligned == false: sosvo_rgbd_sequence_frame_counts)
+static int32_t rgbd_seq_open(sosvo_ctx* ctx, const char* fn, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
+                             bool range_ok, const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes,
+                             RgbdWorkspace& ws) {
+  REQUIRE_FOR(ctx, fn, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
+  REQUIRE_FOR(ctx, fn, range_ok, range_msg);
+  if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  ws = carve_rgbd(*cfg, window, slots, workspace);
+  REQUIRE_FOR(ctx, fn, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
+  return SOSVO_OK;
 }
 
 int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg, int32_t window,
@@ -901,17 +861,14 @@ int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam,
                                       const uint32_t* mask_bits, const int8_t* pattern, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cam && cfg && bgr && depth && mask_bits && pattern && workspace, "null pointer");
-  SOSVO_REQUIRE(ctx, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
-                "frames do not fit the window / the store");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const RgbdSeqBuffers b = carve_rgbd_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots,
+                      n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
+                      "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
   if (n_frames == 0) return SOSVO_OK;
-  const size_t Fc = cfg->frame_cap, o = (size_t)first_slot * Fc;
-  const RgbdFrontTmp fe{b.gray, b.desc, b.kp, b.n, b.status, b.orb};
-  const RgbdStore out{b.m + 2 * o, b.d + 32 * o, b.X + 3 * o, b.b + 3 * o, b.M + first_slot};
-  return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, fe, out);
+  return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, ws.fe,
+                            ws.store.at(first_slot, cfg->frame_cap));
 }
 
 int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -919,44 +876,32 @@ int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cf
                                   size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && ref_slot && cur_slot && workspace && results, "null pointer");
-  SOSVO_REQUIRE(ctx, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const RgbdSeqBuffers b = carve_rgbd_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs,
+                      "more slot pairs than cfg->n_pairs", true, workspace, workspace_bytes, ws));
   if (n_pairs == 0) return SOSVO_OK;
-  for (int i = 0; i < n_pairs; ++i)
-    SOSVO_REQUIRE(ctx, ref_slot[i] >= 0 && ref_slot[i] < slots && cur_slot[i] >= 0 && cur_slot[i] < slots, "slot out of range");
   SlotPairs sp;
-  for (int i = 0; i < kSeqArgPairs; ++i) {
-    sp.ref[i] = i < n_pairs ? ref_slot[i] : 0;
-    sp.cur[i] = i < n_pairs ? cur_slot[i] : 0;
-  }
-  if (n_pairs > kSeqArgPairs) {
-    SOSVO_HIP(ctx, hipMemcpyAsync(b.ref_frame, ref_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-    SOSVO_HIP(ctx, hipMemcpyAsync(b.cur_frame, cur_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
-  } else {
-    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, b.ref_frame, b.cur_frame);
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, n_pairs, slots, ws.tt, sp));
+  if (n_pairs <= kSeqArgPairs) {  // (copied slot lists need no kernel: nothing else to set up)
+    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ws.tt.ref_frame, ws.tt.cur_frame);
     SOSVO_LAUNCH_CHECK(ctx);
   }
-  const RgbdStore store{b.m, b.d, b.X, b.b, b.M};
-  const RgbdTrackTmp tt{b.ref_frame, b.cur_frame, b.order, b.cq, b.ct, b.cn, b.idx, b.n_inl, b.info, b.lm_iters, b.keys, b.mask,
-                        b.f, b.p, b.T_ransac, b.T, b.lm_cost};
-  return run_rgbd_tracking(ctx, cfg, n_pairs, seed, store, tt, results);
+  return run_rgbd_tracking(ctx, cfg, n_pairs, seed, ws.store, ws.tt, results);
 }
 
 int32_t sosvo_rgbd_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
                                       int32_t src_slot, int32_t dst_slot, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace, "null pointer");
-  SOSVO_REQUIRE(ctx, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots, "slot out of range");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  const RgbdSeqBuffers b = carve_rgbd_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots,
+                      "slot out of range", true, workspace, workspace_bytes, ws));
   if (src_slot == dst_slot) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx, rgbd_seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, b.m,
-               reinterpret_cast<uint4*>(b.d), b.X, b.b, b.M);
+  const RgbdStore& s = ws.store;
+  SOSVO_LAUNCH(ctx, rgbd_seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m,
+               reinterpret_cast<uint4*>(s.d), s.X, s.b, s.M);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }
@@ -966,12 +911,12 @@ int32_t sosvo_rgbd_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_rgbd_batch_
                                          int32_t* counts_host) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace && counts_host, "null pointer");
-  SOSVO_REQUIRE(ctx, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  SOSVO_REQUIRE(ctx, first_slot >= 0 && n >= 0 && first_slot + n <= slots, "slots out of range");
-  const RgbdSeqBuffers b = carve_rgbd_seq(*cfg, window, slots, workspace);
-  SOSVO_REQUIRE(ctx, workspace_bytes >= b.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, first_slot >= 0 && n >= 0 && first_slot + n <= slots,
+                      "slots out of range", false, workspace, workspace_bytes, ws));
   if (n == 0) return SOSVO_OK;
-  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, b.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, ws.store.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
   SOSVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SOSVO_OK;
 }

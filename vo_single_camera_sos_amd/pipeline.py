@@ -313,6 +313,29 @@ class OverlappedFramePairs(object):
         self.main.close()
 
 
+def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
+              adaptive, seed, lm_iter, ransac_solver, detection_method):
+    """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
+    kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
+    any ransac_solver but "GP3P" is P3P."""
+    from . import _lib, orb_pattern
+    from .frontend import default_kp_cap
+    detector = _lib.detector_code(detection_method)
+    if kp_cap is None:
+        kp_cap = default_kp_cap(str(detection_method).upper(), num_of_features)
+    cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    c = _lib.BatchCfg()
+    c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = int(n_pairs), model.H, model.W, model.rows, model.cols, model.nmask
+    c.kp_cap, c.frame_cap, c.median_ksize, c.max_corners, c.edge = int(kp_cap), int(frame_cap), int(median_win_size), \
+        int(num_of_features), int(edge)
+    c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
+    c.quality, c.min_distance = float(quality), float(min_distance)
+    c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
+    c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
+    c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
+    return c
+
+
 class FramePairBatch(object):
     """The same hot path behind ONE C-ABI call per step (sosvo_frame_pair_batch): what a non-Python host would
     bind.  `model` is a DeviceImageModel (model constants in HBM); the workspace is allocated once."""
@@ -323,25 +346,11 @@ class FramePairBatch(object):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap)."""
-        from . import _lib, orb_pattern
-        from .frontend import default_kp_cap
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
-        detector = _lib.detector_code(detection_method)
+        self.cfg = c = batch_cfg(model, self.B, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                                 thr, max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method)
         self.method = str(detection_method).upper()
-        if kp_cap is None:
-            kp_cap = default_kp_cap(self.method, num_of_features)
-        cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        c = _lib.BatchCfg()
-        c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = self.B, model.H, model.W, model.rows, model.cols, model.nmask
-        c.kp_cap, c.frame_cap, c.median_ksize, c.max_corners, c.edge = int(kp_cap), int(frame_cap), int(median_win_size), \
-            int(num_of_features), int(edge)
-        c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.quality, c.min_distance = float(quality), float(min_distance)
-        c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
-        c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
-        c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
-        self.cfg = c
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
         nbytes = ctx.frame_pair_batch_workspace(c) if self.n_streams == 1 else ctx.frame_pair_batch_streams_workspace(c, self.n_streams)
@@ -595,28 +604,14 @@ class SequenceEngine(_SequenceBase):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch."""
-        from . import _lib, orb_pattern
-        from .frontend import default_kp_cap
         assert isinstance(ctx, Context)
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
-        detector = _lib.detector_code(detection_method)
-        self.method = str(detection_method).upper()
         self._init_windows(window)
-        if kp_cap is None:
-            kp_cap = default_kp_cap(self.method, num_of_features)
-        cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        c = _lib.BatchCfg()
-        c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = self.W, model.H, model.W, model.rows, model.cols, model.nmask
-        c.kp_cap, c.frame_cap, c.median_ksize, c.max_corners, c.edge = int(kp_cap), int(frame_cap), int(median_win_size), \
-            int(num_of_features), int(edge)
-        c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.quality, c.min_distance = float(quality), float(min_distance)
-        c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
-        c.seed, c.cos_a, c.sin_a = 0, float(cos_a), float(sin_a)
+        self.cfg = c = batch_cfg(model, self.W, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                                 thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
+        self.method = str(detection_method).upper()
         if str(ransac_solver).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
-        c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
-        self.cfg = c
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
         nbytes = ctx.sequence_workspace(c, self.W, self.slots)
@@ -837,6 +832,28 @@ class RGBDPairPipeline(object):
         return out
 
 
+def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                   thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method):
+    """The `sosvo_rgbd_batch_cfg` of RGBDPairBatch and RGBDSequenceEngine (n_pairs: pairs per call / slot pairs per tracking
+    call; cam: an RGBDCamConfig).  kp_cap None or 0 = rgbd_kp_cap; frame_cap None or 0 = kp_cap; thr None = the trackers'
+    5-degree threshold."""
+    from . import _lib, orb_pattern
+    detector_flags = _lib.rgbd_detector_flags(detection_method)
+    kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(str(detection_method).upper(), num_of_features)
+    cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    c = _lib.RgbdBatchCfg()
+    c.n_pairs, c.rows, c.cols = int(n_pairs), int(image_shape[0]), int(image_shape[1])
+    c.kp_cap, c.frame_cap = kp_cap, int(frame_cap) if frame_cap else kp_cap
+    c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
+    c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
+    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
+    c.quality, c.min_distance = float(quality), float(min_distance)
+    c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
+    c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
+    c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
+    return c
+
+
 class RGBDPairBatch(object):
     """RGBDPairPipeline behind ONE C-ABI call per step (sosvo_rgbd_pair_batch): what a non-Python host would bind for
     BASELINE config 5.  Same arguments and results as RGBDPairPipeline; the workspace is allocated once."""
@@ -844,23 +861,13 @@ class RGBDPairBatch(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
-        from . import _lib, orb_pattern
+        from . import orb_pattern
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
-        rows, cols = int(image_shape[0]), int(image_shape[1])
-        detector_flags = _lib.rgbd_detector_flags(detection_method)
+        c = rgbd_batch_cfg(cam, self.B, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
+                           edge, thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method)
         self.method = str(detection_method).upper()
-        kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(self.method, num_of_features)
-        cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        c = _lib.RgbdBatchCfg()
-        c.n_pairs, c.rows, c.cols, c.kp_cap, c.frame_cap = self.B, rows, cols, kp_cap, int(frame_cap) if frame_cap else kp_cap
-        c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
-        c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
-        c.quality, c.min_distance = float(quality), float(min_distance)
-        c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
-        c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
-        c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
+        rows, cols = c.rows, c.cols
         self.cfg, self.thr = c, c.ransac_threshold
         dev = ctx.device
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
@@ -897,25 +904,14 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
-        from . import _lib, orb_pattern
+        from . import orb_pattern
         assert isinstance(ctx, Context)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
-        detector_flags = _lib.rgbd_detector_flags(detection_method)
-        self.method = str(detection_method).upper()
         self._init_windows(window)
-        rows, cols = int(image_shape[0]), int(image_shape[1])
-        kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(self.method, num_of_features)
-        cos_a, sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        c = _lib.RgbdBatchCfg()
-        c.n_pairs, c.rows, c.cols, c.kp_cap, c.frame_cap = self.W, rows, cols, kp_cap, int(frame_cap) if frame_cap else kp_cap
-        c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
-        c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-        c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
-        c.quality, c.min_distance = float(quality), float(min_distance)
-        c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
-        c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
-        c.seed, c.cos_a, c.sin_a = 0, float(cos_a), float(sin_a)
-        self.cfg = c
+        self.cfg = c = rgbd_batch_cfg(cam, self.W, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
+                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
+        self.method = str(detection_method).upper()
+        rows, cols = c.rows, c.cols
         dev = ctx.device
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
         self.mask_bits = torch.from_numpy(mb).to(dev)
