@@ -2,12 +2,14 @@
 """Frame-to-frame visual odometry on a single-camera omnistereo (SOS) sequence -- same entry point and arguments
 as the reference's demo_vo_sos.py, running the hot path on the MI355X through libsosvo.
 
-    python demo_vo_sos.py <sequence_path> --calibrated_gums_file gums-calibrated.json [--visualize_VO false]
+    python demo_vo_sos.py <sequence_path> [<sequence_path> ...] --calibrated_gums_file gums-calibrated.json [--visualize_VO false]
 
 <sequence_path>/omni/image-*.png are the omni frames; results go to <sequence_path>/results-omni/
 (estimated_frame_poses_TUM.txt, gt_associated_frame_poses_TUM.txt, keyframe_ids.txt, printed_messages.log);
 <sequence_path>/omni/gt_TUM.txt is used as ground truth when present.  The calibrated rig is a JSON document
-(vo_single_camera_sos_amd.omnistereo.gum.save_gums_json) instead of the reference's pickle of live objects."""
+(vo_single_camera_sos_amd.omnistereo.gum.save_gums_json) instead of the reference's pickle of live objects.
+Several sequence paths (recorded with the same rig) are tracked together as the lanes of one engine (run_VO_many); each
+gets the result files it would get on its own."""
 import fnmatch
 import os.path as osp
 import sys
@@ -23,7 +25,10 @@ def main_sos_vo(argv=None):
     from vo_single_camera_sos_amd.omnistereo.common_tools import make_sure_path_exists, str2bool
     parser = ArgumentParser(description="Demo of frame-to-frame visual odometry for the Single-camera SOS images.")
     parser.register("type", "bool", str2bool)
-    parser.add_argument("sequence_path", nargs=1, help="The path to the sequence where the omni folder is located.")
+    parser.add_argument("sequence_path", nargs="+", help="The path to the sequence where the omni folder is located (several "
+                        "paths: sequences of the same rig, tracked together).")
+    parser.add_argument("--lanes", default=-1, type=int,
+                        help="several sequence paths: how many are tracked concurrently (-1 = all)")
     parser.add_argument("--calibrated_gums_file", default="gums-calibrated.json", type=str,
                         help="Complete path and name of the calibrated GUMS file (JSON)")
     parser.add_argument("--visualize_VO", default=False, type="bool",
@@ -40,17 +45,29 @@ def main_sos_vo(argv=None):
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import driver_VO
-    scene_path = osp.realpath(osp.expanduser(args.sequence_path[0]))
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import driver_VO, driver_VO_many
     gums_file = osp.realpath(osp.expanduser(args.calibrated_gums_file))
     scene_prefix_filename = "image-*.png"
-    scene_path_omni = osp.join(scene_path, "omni")
-    template = osp.join(scene_path_omni, scene_prefix_filename)
-    num_scene_images = len(fnmatch.filter(listdir(scene_path_omni), scene_prefix_filename))
-    results = osp.join(scene_path, "results-omni")
-    make_sure_path_exists(results)
-    _, scene_name = osp.split(scene_path)
+    scenes = []
+    for path in args.sequence_path:
+        scene_path = osp.realpath(osp.expanduser(path))
+        scene_path_omni = osp.join(scene_path, "omni")
+        template = osp.join(scene_path_omni, scene_prefix_filename)
+        num_scene_images = len(fnmatch.filter(listdir(scene_path_omni), scene_prefix_filename))
+        results = osp.join(scene_path, "results-omni")
+        make_sure_path_exists(results)
+        _, scene_name = osp.split(scene_path)
+        scenes.append(dict(scene_path=scene_path_omni, scene_path_vo_results=results, scene_img_filename_template=template,
+                           depth_filename_template=None, num_scene_images=num_scene_images,
+                           thread_name="%s-%s" % (scene_name, "SOS")))
     gums_calibrated = load_gums_json(gums_file)
+    if len(scenes) > 1:
+        out = driver_VO_many(camera_model=gums_calibrated, scenes=scenes, visualize_VO=args.visualize_VO,
+                             step_for_scene_images=args.step, first_image_index=args.first_image_index,
+                             last_image_index=args.last_image_index, frame_window=None if args.frame_window < 0 else args.frame_window,
+                             detection_method=args.detection_method, lanes=None if args.lanes < 0 else args.lanes)
+        print("GOODBYE!")
+        return out
     out = driver_VO(camera_model=gums_calibrated, scene_path=scene_path_omni, scene_path_vo_results=results,
                     scene_img_filename_template=template, depth_filename_template=None, num_scene_images=num_scene_images,
                     visualize_VO=args.visualize_VO, use_multithreads_for_VO=args.use_multithreads_for_VO,

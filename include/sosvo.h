@@ -352,6 +352,16 @@ int32_t sosvo_ransac_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, 
                               int32_t max_iter, int32_t adaptive, uint64_t seed, double* T_out,
                               uint8_t* inlier_mask, int32_t* inlier_idx, int32_t* n_inliers,
                               int32_t* info, int32_t* hyp_counts);
+/* As sosvo_ransac_abs_pose with ONE SEED PER PROBLEM: problem b samples from (seeds[b], iteration), seeds [nprob] u64
+ * (device).  The problems of a call then need not be consecutive frames of one sequence (the multi-sequence entry points
+ * below: lane s is at frame t_s and tracks with seed t_s - 1).  seeds[b] = seed + b gives sosvo_ransac_abs_pose(seed)
+ * exactly; everything but the sampler's seed (solvers, scoring, adaptive stop, outputs) is shared.                 */
+int32_t sosvo_ransac_abs_pose_seeds(sosvo_ctx* ctx, const double* f, const double* p, const int32_t* cam,
+                                    const double* cam_off, const double* cam_rot, int32_t ncam, int32_t flags,
+                                    const int32_t* n, int32_t nprob, int32_t stride, double thr,
+                                    int32_t max_iter, int32_t adaptive, const uint64_t* seeds, double* T_out,
+                                    uint8_t* inlier_mask, int32_t* inlier_idx, int32_t* n_inliers,
+                                    int32_t* info, int32_t* hyp_counts);
 
 /* ---- K9: non-linear refinement --------------------------------------------------------------
  * Replaces pyopengv.absolute_pose_noncentral_optimize_nonlinear (pose_est_tools.py:830) and
@@ -642,6 +652,36 @@ int32_t sosvo_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg_h
                                     int32_t first_slot, int32_t n, void* workspace, size_t workspace_bytes,
                                     int32_t* counts_host);
 
+/* ---- Several sequences through one frame store ("lanes") ---------------------------------------------------------
+ * A frame record is a function of its image only and a tracking record of (reference record, current record, seed)
+ * only, so S sequences that share ONE rig may share one store, one stream and one launch per stage: which call computes
+ * a record never changes its bits.  A host that tracks S lanes with windows of W frames sizes the SAME workspace as
+ * sosvo_sequence_workspace(cfg, S * W, S * (2 W + 1)) with cfg->n_pairs = S * W, gives lane s the slots
+ * s (2 W + 1) .. s (2 W + 1) + 2 W (two window halves and its keyframe slot), and reads all lanes' counts with ONE
+ * sosvo_sequence_frame_counts over the store.  The limits of the shape (window <= 16384, slots <= 65535,
+ * n_pairs <= 8192) bound S * W.  What the single-sequence calls above cannot express:
+ * sosvo_sequence_front_end_slots: sosvo_sequence_front_end with frame i's record written to slot slot_of_frame[i] (HOST
+ *   array [n_frames]; every entry a slot of the store, none twice: SOSVO_ERR_ARG otherwise, nothing launched).  The
+ *   frames of one call belong to different lanes, whose windows end at different times.  Asynchronous (the table
+ *   travels as kernel arguments).
+ * sosvo_sequence_track_seeds: sosvo_sequence_track with pair i sampling with seed_host[i] (HOST array [n_pairs]) instead
+ *   of seed + i.  Asynchronous; up to 16 pairs travel with their seeds as kernel arguments, larger batches are copied.
+ * sosvo_sequence_copy_slots: n_copies (source, destination) pairs (HOST arrays) in ONE launch; n_copies <=
+ *   cfg->n_pairs.  A slot that is a destination twice, or both a source and a destination (src == dst included), is
+ *   refused with SOSVO_ERR_ARG: the pairs are copied concurrently.  Asynchronous.                                    */
+int32_t sosvo_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, const sosvo_batch_cfg* cfg_host,
+                                       int32_t window, int32_t slots, const uint8_t* omni, int32_t n_frames,
+                                       const int32_t* slot_of_frame_host, const uint32_t* unwrap_table,
+                                       const uint32_t* mask_bits, const int8_t* pattern, void* workspace,
+                                       size_t workspace_bytes);
+int32_t sosvo_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rig* rig_host, const sosvo_batch_cfg* cfg_host, int32_t window,
+                                   int32_t slots, const int32_t* ref_slot_host, const int32_t* cur_slot_host,
+                                   const uint64_t* seed_host, int32_t n_pairs, void* workspace, size_t workspace_bytes,
+                                   double* results);
+int32_t sosvo_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg_host, int32_t window, int32_t slots,
+                                  const int32_t* src_slot_host, const int32_t* dst_slot_host, int32_t n_copies,
+                                  void* workspace, size_t workspace_bytes);
+
 /* ---- The RGB-D path for B independent frame pairs behind ONE call (BASELINE config 5) ------------------
  * RGBDFrame.establish_keypoints (omnistereo/pose_est_tools.py:600-623: [median,] gray, goodFeaturesToTrack on the
  * whole image or on RGBDFrame.mask, ORB descriptors, depth back-projection, NaN / range filter, bearings) for the
@@ -700,6 +740,20 @@ int32_t sosvo_rgbd_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg
 int32_t sosvo_rgbd_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg_host, int32_t window, int32_t slots,
                                          int32_t first_slot, int32_t n, void* workspace, size_t workspace_bytes,
                                          int32_t* counts_host);
+/* Several RGB-D sequences of one camera through one store: as "Several sequences through one frame store" above, on
+ * sosvo_rgbd_sequence_workspace(cfg, S * W, S * (2 W + 1)) with cfg->n_pairs = S * W.                              */
+int32_t sosvo_rgbd_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam_host,
+                                            const sosvo_rgbd_batch_cfg* cfg_host, int32_t window, int32_t slots,
+                                            const uint8_t* bgr, const float* depth, int32_t n_frames,
+                                            const int32_t* slot_of_frame_host, const uint32_t* mask_bits,
+                                            const int8_t* pattern, void* workspace, size_t workspace_bytes);
+int32_t sosvo_rgbd_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg_host, int32_t window, int32_t slots,
+                                        const int32_t* ref_slot_host, const int32_t* cur_slot_host,
+                                        const uint64_t* seed_host, int32_t n_pairs, void* workspace,
+                                        size_t workspace_bytes, double* results);
+int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg_host, int32_t window, int32_t slots,
+                                       const int32_t* src_slot_host, const int32_t* dst_slot_host, int32_t n_copies,
+                                       void* workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

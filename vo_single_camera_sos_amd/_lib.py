@@ -82,6 +82,8 @@ SIGNATURES = {
     "sosvo_f2f_assemble": (c_i32, [c_p] + [c_p] * 7 + [c_i32] + [c_p] * 6 + [c_i32, c_i32] + [c_p] * 7),
     "sosvo_ransac_abs_pose": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
                                       c_i32, c_i32, c_u64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "sosvo_ransac_abs_pose_seeds": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
+                                            c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sosvo_match_l2": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_ransac_rel_pose": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_f64, c_i32, c_i32, c_u64, c_p, c_p, c_p, c_p,
                                       c_p, c_p]),
@@ -101,11 +103,18 @@ SIGNATURES = {
     "sosvo_sequence_track": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_u64, c_p, ctypes.c_size_t, c_p]),
     "sosvo_sequence_copy_slot": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, ctypes.c_size_t]),
     "sosvo_sequence_frame_counts": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, ctypes.c_size_t, c_p]),
+    "sosvo_sequence_front_end_slots": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t]),
+    "sosvo_sequence_track_seeds": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_p, ctypes.c_size_t, c_p]),
+    "sosvo_sequence_copy_slots": (c_i32, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, ctypes.c_size_t]),
     "sosvo_rgbd_sequence_workspace": (ctypes.c_size_t, [c_p, c_i32, c_i32]),
     "sosvo_rgbd_sequence_front_end": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p, ctypes.c_size_t]),
     "sosvo_rgbd_sequence_track": (c_i32, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_u64, c_p, ctypes.c_size_t, c_p]),
     "sosvo_rgbd_sequence_copy_slot": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, ctypes.c_size_t]),
     "sosvo_rgbd_sequence_frame_counts": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, ctypes.c_size_t, c_p]),
+    "sosvo_rgbd_sequence_front_end_slots": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p,
+                                                    ctypes.c_size_t]),
+    "sosvo_rgbd_sequence_track_seeds": (c_i32, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_p, ctypes.c_size_t, c_p]),
+    "sosvo_rgbd_sequence_copy_slots": (c_i32, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, ctypes.c_size_t]),
     "sosvo_rgbd_pair_batch_workspace": (ctypes.c_size_t, [c_p]),
     "sosvo_rgbd_pair_batch": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
 }

@@ -165,3 +165,22 @@ int32_t sosvo_launch_gauss7_to(sosvo_ctx* ctx, const uint8_t* in, long long in_s
 // ... restricted to the output rows [row_range[2 v], row_range[2 v + 1]) (device array; v = image / imgs_per_range)
 int32_t sosvo_launch_gauss7_rows(sosvo_ctx* ctx, const uint8_t* in, long long in_stride, int nimg, int rows, int cols,
                                  uint8_t* out, long long out_stride, const int32_t* row_range, int imgs_per_range);
+
+// geometry.hip / rgbd.hip: the assemble stages with frame i's record written at record slot_of_frame[i] of the outputs (the
+// ..._front_end_slots entry points).  The HOST table travels in kernel arguments, kSosvoSlotArgFrames frames per launch.
+constexpr int kSosvoSlotArgFrames = 256;
+struct sosvo_slot_table {
+  int32_t slot[kSosvoSlotArgFrames];
+};
+extern "C" {
+int32_t sosvo_stereo_assemble_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* kp_top, const float* kp_bot,
+                                    const uint8_t* desc_top, const uint8_t* desc_bot, const int32_t* n_top,
+                                    const int32_t* n_bot, const uint32_t* keys, const int32_t* order, int32_t nframes,
+                                    const int32_t* slot_of_frame, int32_t nmask, int32_t cap, int32_t out_cap, float* m_top,
+                                    float* m_bot, uint8_t* d_top, uint8_t* d_bot, double* X, double* b_top, double* b_bot,
+                                    int32_t* M, int32_t* n_cand);
+int32_t sosvo_rgbd_assemble_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam_host, const float* kp, const uint8_t* desc,
+                                  const int32_t* n, const float* depth, int32_t nframes, const int32_t* slot_of_frame,
+                                  int32_t rows, int32_t cols, int32_t cap, int32_t out_cap, float* m, uint8_t* d, double* X,
+                                  double* b, int32_t* M);
+}

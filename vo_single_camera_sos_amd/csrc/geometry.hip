@@ -119,8 +119,9 @@ __device__ __forceinline__ int block_compact_pos(bool valid, int* wave_off /*[5]
   return wave_off[wid] + __popcll(bal & ((1ULL << lane) - 1ULL));
 }
 
-__global__ __launch_bounds__(kThreads) void stereo_assemble_kernel(
-    sosvo_rig rig, const float* __restrict__ kp_top, const float* __restrict__ kp_bot,
+// The record of input frame `fr` (one workgroup) written at record `slot` of the outputs.
+__device__ __forceinline__ void stereo_assemble_frame(
+    const int fr, const int slot, const sosvo_rig& rig, const float* __restrict__ kp_top, const float* __restrict__ kp_bot,
     const uint4* __restrict__ desc_top, const uint4* __restrict__ desc_bot, const int32_t* __restrict__ n_top,
     const int32_t* __restrict__ n_bot, const uint32_t* __restrict__ keys, const int32_t* __restrict__ order, int nmask,
     int cap, int out_cap, float* __restrict__ m_top, float* __restrict__ m_bot, uint4* __restrict__ d_top,
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void stereo_assemble_kernel(
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ int wave_off[kThreads / 64 + 1];
   __shared__ int s_running;
-  const int tid = threadIdx.x, fr = blockIdx.x;
+  const int tid = threadIdx.x;
   if (tid == 0) s_running = 0;
   __syncthreads();
   int cand_total = 0;
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void stereo_assemble_kernel(
       }
       const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
       if (valid && pos < out_cap) {
-        const size_t o = (size_t)fr * out_cap + pos;
+        const size_t o = (size_t)slot * out_cap + pos;
         m_top[2 * o] = ut;
         m_top[2 * o + 1] = vt;
         m_bot[2 * o] = ub;
@@ -184,9 +185,34 @@ __global__ __launch_bounds__(kThreads) void stereo_assemble_kernel(
   }
   __syncthreads();
   if (tid == 0) {
-    M[fr] = min(s_running, out_cap);
+    M[slot] = min(s_running, out_cap);
     if (n_cand) n_cand[fr] = cand_total;
   }
+}
+
+// frame blockIdx.x -> record blockIdx.x
+__global__ __launch_bounds__(kThreads) void stereo_assemble_kernel(
+    sosvo_rig rig, const float* __restrict__ kp_top, const float* __restrict__ kp_bot,
+    const uint4* __restrict__ desc_top, const uint4* __restrict__ desc_bot, const int32_t* __restrict__ n_top,
+    const int32_t* __restrict__ n_bot, const uint32_t* __restrict__ keys, const int32_t* __restrict__ order, int nmask,
+    int cap, int out_cap, float* __restrict__ m_top, float* __restrict__ m_bot, uint4* __restrict__ d_top,
+    uint4* __restrict__ d_bot, double* __restrict__ X, double* __restrict__ b_top, double* __restrict__ b_bot,
+    int32_t* __restrict__ M, int32_t* __restrict__ n_cand) {
+  stereo_assemble_frame(blockIdx.x, blockIdx.x, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, keys, order, nmask, cap,
+                        out_cap, m_top, m_bot, d_top, d_bot, X, b_top, b_bot, M, n_cand);
+}
+
+// frame frame0 + blockIdx.x -> record tab.slot[blockIdx.x] (sosvo_sequence_front_end_slots: the frames of one call belong
+// to several sequences whose store slots are not one range).  The table travels as a kernel argument: no copy per call.
+__global__ __launch_bounds__(kThreads) void stereo_assemble_slots_kernel(
+    sosvo_rig rig, sosvo_slot_table tab, int frame0, const float* __restrict__ kp_top, const float* __restrict__ kp_bot,
+    const uint4* __restrict__ desc_top, const uint4* __restrict__ desc_bot, const int32_t* __restrict__ n_top,
+    const int32_t* __restrict__ n_bot, const uint32_t* __restrict__ keys, const int32_t* __restrict__ order, int nmask,
+    int cap, int out_cap, float* __restrict__ m_top, float* __restrict__ m_bot, uint4* __restrict__ d_top,
+    uint4* __restrict__ d_bot, double* __restrict__ X, double* __restrict__ b_top, double* __restrict__ b_bot,
+    int32_t* __restrict__ M, int32_t* __restrict__ n_cand) {
+  stereo_assemble_frame(frame0 + (int)blockIdx.x, tab.slot[blockIdx.x], rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot,
+                        keys, order, nmask, cap, out_cap, m_top, m_bot, d_top, d_bot, X, b_top, b_bot, M, n_cand);
 }
 
 __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
@@ -333,6 +359,32 @@ int32_t sosvo_stereo_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const f
                      keys, order, nmask, cap, out_cap, m_top, m_bot, reinterpret_cast<uint4*>(d_top),
                      reinterpret_cast<uint4*>(d_bot), X, b_top, b_bot, M, n_cand);
   SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+// (internal, common.h) sosvo_stereo_assemble with the record of frame i written at record slot_of_frame[i] of the outputs
+// (HOST table, checked by the caller: distinct records inside the outputs)
+int32_t sosvo_stereo_assemble_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* kp_top, const float* kp_bot,
+                                    const uint8_t* desc_top, const uint8_t* desc_bot, const int32_t* n_top,
+                                    const int32_t* n_bot, const uint32_t* keys, const int32_t* order, int32_t nframes,
+                                    const int32_t* slot_of_frame, int32_t nmask, int32_t cap, int32_t out_cap, float* m_top,
+                                    float* m_bot, uint8_t* d_top, uint8_t* d_bot, double* X, double* b_top, double* b_bot,
+                                    int32_t* M, int32_t* n_cand) {
+  SOSVO_REQUIRE(ctx, rig_host && kp_top && kp_bot && desc_top && desc_bot && n_top && n_bot && keys && order && slot_of_frame,
+                "null input pointer");
+  SOSVO_REQUIRE(ctx, m_top && m_bot && d_top && d_bot && X && b_top && b_bot && M, "null output pointer");
+  SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= (1 << 20) && nmask > 0 && cap > 0 && out_cap > 0, "sizes out of range");
+  SOSVO_REQUIRE(ctx, cap <= (1 << SOSVO_KEY_SHIFT), "cap out of range");
+  for (int f0 = 0; f0 < nframes; f0 += kSosvoSlotArgFrames) {
+    const int nf = nframes - f0 < kSosvoSlotArgFrames ? nframes - f0 : kSosvoSlotArgFrames;
+    sosvo_slot_table tab;
+    for (int i = 0; i < kSosvoSlotArgFrames; ++i) tab.slot[i] = i < nf ? slot_of_frame[f0 + i] : 0;
+    SOSVO_LAUNCH(ctx, stereo_assemble_slots_kernel, dim3(nf), dim3(kThreads), 0, ctx->stream, *rig_host, tab, f0, kp_top, kp_bot,
+                 reinterpret_cast<const uint4*>(desc_top), reinterpret_cast<const uint4*>(desc_bot), n_top, n_bot, keys, order,
+                 nmask, cap, out_cap, m_top, m_bot, reinterpret_cast<uint4*>(d_top), reinterpret_cast<uint4*>(d_bot), X, b_top,
+                 b_bot, M, n_cand);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
   return SOSVO_OK;
 }
 

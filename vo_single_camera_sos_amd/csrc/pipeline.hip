@@ -4,6 +4,8 @@
 // TrackerStereoSE3.track_frame (pose_est_tools.py:736-847) per pair.  It only sequences the stage entry points
 // of this library on the context's stream (no host synchronisation, no allocation: every intermediate lives in
 // the caller's workspace), so its results are those of calling the stages one by one.
+#include <vector>
+
 #include "common.h"
 
 namespace {
@@ -200,12 +202,18 @@ constexpr int kSeqArgPairs = 16;  // slot pairs that travel as kernel arguments 
 struct SlotPairs {
   int32_t ref[kSeqArgPairs], cur[kSeqArgPairs];
 };
-__global__ void seq_setup_kernel(int npairs, SlotPairs sp, Foci foci, int32_t* __restrict__ ref_frame,
-                                 int32_t* __restrict__ cur_frame, double* __restrict__ cam_off, double* __restrict__ cam_rot) {
+// ... and their seeds (the ..._track_seeds entry points; seeds_out == nullptr: the call has one scalar seed)
+struct PairSeeds {
+  uint64_t seed[kSeqArgPairs];
+};
+__global__ void seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, Foci foci, int32_t* __restrict__ ref_frame,
+                                 int32_t* __restrict__ cur_frame, uint64_t* __restrict__ seeds_out, double* __restrict__ cam_off,
+                                 double* __restrict__ cam_rot) {
   const int i = threadIdx.x;
   if (i < npairs && i < kSeqArgPairs) {
     ref_frame[i] = sp.ref[i];
     cur_frame[i] = sp.cur[i];
+    if (seeds_out) seeds_out[i] = ps.seed[i];
   }
   if (i < 3) {
     cam_off[i] = foci.top[i];
@@ -236,6 +244,38 @@ __global__ void seq_copy_slot_kernel(int src, int dst, int Fc, float* m_top, flo
   }
   __syncthreads();  // (every thread has read M[src] before it may be overwritten when src == dst is excluded by the caller)
   if (blockIdx.x == 0 && threadIdx.x == 0) M[dst] = n;
+}
+
+// k (source, destination) pairs in one launch (sosvo_sequence_copy_slots): workgroup (j, c) copies every gridDim.y-th
+// block of 256 entries of pair j.  The host has checked that no slot is written twice or read and written.
+struct CopyPairs {
+  int32_t src[kSeqArgPairs], dst[kSeqArgPairs];
+};
+constexpr int kCopyChunks = 4;
+__global__ __launch_bounds__(256) void seq_copy_slots_kernel(CopyPairs cp, const int32_t* __restrict__ src_list,
+                                                             const int32_t* __restrict__ dst_list, int Fc, float* m_top,
+                                                             float* m_bot, uint4* d_top, uint4* d_bot, double* X, double* b_top,
+                                                             double* b_bot, int32_t* M) {
+  const int j = blockIdx.x;
+  const int src = src_list ? src_list[j] : cp.src[j], dst = src_list ? dst_list[j] : cp.dst[j];
+  const int n = min(M[src], Fc);
+  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
+    const size_t s = (size_t)src * Fc + i, d = (size_t)dst * Fc + i;
+    m_top[2 * d] = m_top[2 * s];
+    m_top[2 * d + 1] = m_top[2 * s + 1];
+    m_bot[2 * d] = m_bot[2 * s];
+    m_bot[2 * d + 1] = m_bot[2 * s + 1];
+    d_top[2 * d] = d_top[2 * s];
+    d_top[2 * d + 1] = d_top[2 * s + 1];
+    d_bot[2 * d] = d_bot[2 * s];
+    d_bot[2 * d + 1] = d_bot[2 * s + 1];
+    for (int k = 0; k < 3; ++k) {
+      X[3 * d + k] = X[3 * s + k];
+      b_top[3 * d + k] = b_top[3 * s + k];
+      b_bot[3 * d + k] = b_bot[3 * s + k];
+    }
+  }
+  if (blockIdx.y == 0 && threadIdx.x == 0) M[dst] = M[src];  // (no slot of the list is both read and written)
 }
 
 // ---- RGB-D variant (BASELINE config 5): the same three parts; a store of `slots` RGBDFrame records (keypoints with valid
@@ -328,12 +368,34 @@ RgbdWorkspace carve_rgbd(const sosvo_rgbd_batch_cfg& c, size_t window, size_t sl
   return ws;
 }
 
-__global__ void rgbd_seq_setup_kernel(int npairs, SlotPairs sp, int32_t* __restrict__ ref_frame, int32_t* __restrict__ cur_frame) {
+__global__ void rgbd_seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, int32_t* __restrict__ ref_frame,
+                                      int32_t* __restrict__ cur_frame, uint64_t* __restrict__ seeds_out) {
   const int i = threadIdx.x;
   if (i < npairs && i < kSeqArgPairs) {
     ref_frame[i] = sp.ref[i];
     cur_frame[i] = sp.cur[i];
+    if (seeds_out) seeds_out[i] = ps.seed[i];
   }
+}
+
+__global__ __launch_bounds__(256) void rgbd_seq_copy_slots_kernel(CopyPairs cp, const int32_t* __restrict__ src_list,
+                                                                  const int32_t* __restrict__ dst_list, int Fc, float* m, uint4* d,
+                                                                  double* X, double* b, int32_t* M) {
+  const int j = blockIdx.x;
+  const int src = src_list ? src_list[j] : cp.src[j], dst = src_list ? dst_list[j] : cp.dst[j];
+  const int n = min(M[src], Fc);
+  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
+    const size_t s = (size_t)src * Fc + i, t = (size_t)dst * Fc + i;
+    m[2 * t] = m[2 * s];
+    m[2 * t + 1] = m[2 * s + 1];
+    d[2 * t] = d[2 * s];
+    d[2 * t + 1] = d[2 * s + 1];
+    for (int k = 0; k < 3; ++k) {
+      X[3 * t + k] = X[3 * s + k];
+      b[3 * t + k] = b[3 * s + k];
+    }
+  }
+  if (blockIdx.y == 0 && threadIdx.x == 0) M[dst] = M[src];
 }
 
 __global__ void rgbd_seq_copy_slot_kernel(int src, int dst, int Fc, float* m, uint4* d, double* X, double* b, int32_t* M) {
@@ -367,21 +429,81 @@ __global__ void pair_index_kernel(int npairs, int32_t* __restrict__ ref_frame, i
     if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, (fn), msg);   \
   } while (0)
 
+// Where the device keeps the seeds of a ..._track_seeds call: the slice of the LM costs.  8 bytes per pair both, and the
+// costs are not written before the refinement, which runs after the last reader of the seeds (the hypothesis kernels) on
+// the stream -- so the workspace keeps the size sosvo_[rgbd_]sequence_workspace has always answered.
+template <typename Track>
+uint64_t* pair_seeds(const Track& b) {
+  return reinterpret_cast<uint64_t*>(b.lm_cost);
+}
+
 // The slot pairs of a sequence tracking call (entry point `fn`), checked against the store (host arrays: a bad slot would
 // index outside the store on the device).  Up to kSeqArgPairs come back in `sp` for the family's setup kernel; larger
 // batches are copied to b.ref_frame / b.cur_frame (pageable host memory: the copy returns when staged).
+// seed_host (the ..._track_seeds entry points; nullptr otherwise): the pairs' seeds travel the same way, in `ps` or, copied,
+// to pair_seeds(b).
 template <typename Track>
-int32_t upload_slot_pairs(sosvo_ctx* ctx, const char* fn, const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs,
-                          int32_t slots, const Track& b, SlotPairs& sp) {
+int32_t upload_slot_pairs(sosvo_ctx* ctx, const char* fn, const int32_t* ref_slot, const int32_t* cur_slot,
+                          const uint64_t* seed_host, int32_t n_pairs, int32_t slots, const Track& b, SlotPairs& sp,
+                          PairSeeds& ps) {
   for (int i = 0; i < n_pairs; ++i)
     REQUIRE_FOR(ctx, fn, ref_slot[i] >= 0 && ref_slot[i] < slots && cur_slot[i] >= 0 && cur_slot[i] < slots, "slot out of range");
   for (int i = 0; i < kSeqArgPairs; ++i) {
     sp.ref[i] = i < n_pairs ? ref_slot[i] : 0;
     sp.cur[i] = i < n_pairs ? cur_slot[i] : 0;
+    ps.seed[i] = seed_host && i < n_pairs ? seed_host[i] : 0;
   }
   if (n_pairs > kSeqArgPairs) {
+    if (seed_host)
+      SOSVO_HIP(ctx, hipMemcpyAsync(pair_seeds(b), seed_host, sizeof(uint64_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     SOSVO_HIP(ctx, hipMemcpyAsync(b.ref_frame, ref_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
     SOSVO_HIP(ctx, hipMemcpyAsync(b.cur_frame, cur_slot, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return SOSVO_OK;
+}
+
+// The (source, destination) lists of a ..._copy_slots call (entry point `fn`), checked on the host: slots of the store, no
+// slot written twice, none both read and written (a launch copies all pairs at once).
+int32_t check_copy_lists(sosvo_ctx* ctx, const char* fn, const int32_t* src, const int32_t* dst, int32_t n, int32_t slots,
+                         CopyPairs& cp) {
+  for (int i = 0; i < n; ++i)
+    REQUIRE_FOR(ctx, fn, src[i] >= 0 && src[i] < slots && dst[i] >= 0 && dst[i] < slots, "slot out of range");
+  const char* msg = "a slot is a destination twice, or both a source and a destination";
+  if (n <= kSeqArgPairs) {  // (the serial round of up to 16 lanes: pairwise, nothing allocated)
+    for (int i = 0; i < n; ++i) {
+      for (int j = 0; j < n; ++j) REQUIRE_FOR(ctx, fn, dst[i] != src[j], msg);
+      for (int j = 0; j < i; ++j) REQUIRE_FOR(ctx, fn, dst[i] != dst[j], msg);
+    }
+  } else {
+    std::vector<uint8_t> use((size_t)slots, 0);  // 1: read, 2: written
+    for (int i = 0; i < n; ++i) use[src[i]] = 1;
+    for (int i = 0; i < n; ++i) {
+      REQUIRE_FOR(ctx, fn, use[dst[i]] == 0, msg);
+      use[dst[i]] = 2;
+    }
+  }
+  for (int i = 0; i < kSeqArgPairs; ++i) {
+    cp.src[i] = i < n ? src[i] : 0;
+    cp.dst[i] = i < n ? dst[i] : 0;
+  }
+  return SOSVO_OK;
+}
+
+// The slot table of a ..._front_end_slots call (entry point `fn`): slots of the store, none twice (a bad table would write
+// outside the store, or two frames' records over each other).  Once per window of frames, not per serial call; small
+// tables are compared pairwise, larger ones marked in a host array.
+int32_t check_slot_table(sosvo_ctx* ctx, const char* fn, const int32_t* slot_of_frame, int32_t n, int32_t slots) {
+  for (int i = 0; i < n; ++i) REQUIRE_FOR(ctx, fn, slot_of_frame[i] >= 0 && slot_of_frame[i] < slots, "slot out of range");
+  const char* msg = "a slot appears twice in slot_of_frame";
+  if (n <= 64) {
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j < i; ++j) REQUIRE_FOR(ctx, fn, slot_of_frame[i] != slot_of_frame[j], msg);
+    return SOSVO_OK;
+  }
+  std::vector<uint8_t> used((size_t)slots, 0);
+  for (int i = 0; i < n; ++i) {
+    REQUIRE_FOR(ctx, fn, !used[slot_of_frame[i]], msg);
+    used[slot_of_frame[i]] = 1;
   }
   return SOSVO_OK;
 }
@@ -411,7 +533,8 @@ size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
 // matching, gates, bearings, midpoint triangulation, range filter -> F frame records written at out_* (frame-major).
 static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int F, const uint8_t* omni,
                              const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
-                             const FrontEndTmp& t, const FrameStore& o, hipEvent_t median_wait, hipEvent_t median_done) {
+                             const FrontEndTmp& t, const FrameStore& o, hipEvent_t median_wait, hipEvent_t median_done,
+                             const int32_t* slot_of_frame = nullptr) {
   const int NI = 2 * F, NM = cfg->nmask, cap = cfg->kp_cap, Fc = cfg->frame_cap;
   const int h = F * NM;  // problems of one view: (frame, mask); the top view's come first (view-major images)
   int32_t rc;
@@ -460,16 +583,22 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const int32_t *n_top = t.n, *n_bot = t.n + h;
   STAGE(sosvo_match_hamming(ctx, desc_bot, desc_top, n_bot, n_top, nullptr, nullptr, h, cap, cap, 1, t.s_keys));
   STAGE(sosvo_sort_matches(ctx, t.s_keys, n_bot, nullptr, h, cap, t.s_order));
-  STAGE(sosvo_stereo_assemble(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F, NM, cap,
-                              Fc, o.m_top, o.m_bot, o.d_top, o.d_bot, o.X, o.b_top, o.b_bot, o.M, t.n_cand));
+  if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
+    STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
+                                      slot_of_frame, NM, cap, Fc, o.m_top, o.m_bot, o.d_top, o.d_bot, o.X, o.b_top, o.b_bot, o.M,
+                                      t.n_cand));
+  else
+    STAGE(sosvo_stereo_assemble(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F, NM, cap,
+                                Fc, o.m_top, o.m_bot, o.d_top, o.d_bot, o.X, o.b_top, o.b_bot, o.M, t.n_cand));
   return SOSVO_OK;
 }
 
 // TrackerStereoSE3.track_frame (pose_est_tools.py:736-847) for B (reference slot, current slot) pairs of a frame store:
 // frame-to-frame matching per view (query = current frame, train = reference frame), |du| gate, stacking, non-central
 // RANSAC (problem i samples with seed + i), LM on the inliers, [B,16] records.
+// (seeds: device array of per-pair seeds, pair i samples with seeds[i]; nullptr: with seed + i)
 static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, uint64_t seed,
-                            const FrameStore& s, const TrackTmp& b, double* results) {
+                            const FrameStore& s, const TrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
   int32_t rc;
   STAGE(sosvo_match_hamming(ctx, s.d_top, s.d_top, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_top));
@@ -479,10 +608,15 @@ static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_ba
   STAGE(sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top,
                            b.o_top, b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top));
   // 3D-2D absolute pose: RANSAC, then LM on the inliers
-  STAGE(sosvo_ransac_abs_pose(ctx, b.f, b.p, b.cam, b.cam_off, b.cam_rot, 2,
-                              SOSVO_FLAG_CAM_ROT_IDENTITY | (cfg->ransac_flags & SOSVO_FLAG_GP3P), b.cn, B, Cc,
-                              cfg->ransac_threshold, cfg->ransac_max_iter, cfg->ransac_adaptive, seed, b.T_ransac,
-                              b.mask, b.idx, b.n_inl, b.info, nullptr));
+  const int32_t rflags = SOSVO_FLAG_CAM_ROT_IDENTITY | (cfg->ransac_flags & SOSVO_FLAG_GP3P);
+  if (seeds)
+    STAGE(sosvo_ransac_abs_pose_seeds(ctx, b.f, b.p, b.cam, b.cam_off, b.cam_rot, 2, rflags, b.cn, B, Cc, cfg->ransac_threshold,
+                                      cfg->ransac_max_iter, cfg->ransac_adaptive, seeds, b.T_ransac, b.mask, b.idx, b.n_inl,
+                                      b.info, nullptr));
+  else
+    STAGE(sosvo_ransac_abs_pose(ctx, b.f, b.p, b.cam, b.cam_off, b.cam_rot, 2, rflags, b.cn, B, Cc, cfg->ransac_threshold,
+                                cfg->ransac_max_iter, cfg->ransac_adaptive, seed, b.T_ransac, b.mask, b.idx, b.n_inl, b.info,
+                                nullptr));
   SOSVO_HIP(ctx, hipMemcpyAsync(b.T, b.T_ransac, sizeof(double) * 12 * B, hipMemcpyDeviceToDevice, ctx->stream));
   STAGE(sosvo_refine_abs_pose(ctx, b.f, b.p, b.cam, b.cam_off, b.cam_rot, 2, b.cn, B, Cc, b.idx, b.n_inl, cfg->lm_max_iter,
                               b.T, b.lm_cost, b.lm_iters));
@@ -704,6 +838,22 @@ int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sos
                        ws.store.at(first_slot, cfg->frame_cap), nullptr, nullptr);
 }
 
+int32_t sosvo_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
+                                       int32_t slots, const uint8_t* omni, int32_t n_frames, const int32_t* slot_of_frame,
+                                       const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
+                                       void* workspace, size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && omni && slot_of_frame && unwrap_table && mask_bits && pattern && workspace, "null pointer");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_frames >= 0 && n_frames <= window && n_frames <= slots,
+                 "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
+  STAGE(check_slot_table(ctx, __func__, slot_of_frame, n_frames, slots));
+  if (n_frames == 0) return SOSVO_OK;
+  return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, ws.fe, ws.store, nullptr, nullptr,
+                       slot_of_frame);
+}
+
 int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
                              const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs, uint64_t seed, void* workspace,
                              size_t workspace_bytes, double* results) {
@@ -715,12 +865,32 @@ int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
                  true, workspace, workspace_bytes, ws));
   if (n_pairs == 0) return SOSVO_OK;
   SlotPairs sp;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, n_pairs, slots, ws.tt, sp));
+  PairSeeds ps;
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, nullptr, n_pairs, slots, ws.tt, sp, ps));
   // (always launched, copied slot lists or not: it also writes cam_off / cam_rot)
-  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, foci_of(rig),
-               ws.tt.ref_frame, ws.tt.cur_frame, ws.tt.cam_off, ws.tt.cam_rot);
+  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, ps,
+               foci_of(rig), ws.tt.ref_frame, ws.tt.cur_frame, (uint64_t*)nullptr, ws.tt.cam_off, ws.tt.cam_rot);
   SOSVO_LAUNCH_CHECK(ctx);
   return run_tracking(ctx, rig, cfg, n_pairs, seed, ws.store, ws.tt, results);
+}
+
+int32_t sosvo_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
+                                   int32_t slots, const int32_t* ref_slot, const int32_t* cur_slot, const uint64_t* seed,
+                                   int32_t n_pairs, void* workspace, size_t workspace_bytes, double* results) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && seed && workspace && results, "null pointer");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs",
+                 true, workspace, workspace_bytes, ws));
+  if (n_pairs == 0) return SOSVO_OK;
+  SlotPairs sp;
+  PairSeeds ps;
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, seed, n_pairs, slots, ws.tt, sp, ps));
+  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, ps,
+               foci_of(rig), ws.tt.ref_frame, ws.tt.cur_frame, pair_seeds(ws.tt), ws.tt.cam_off, ws.tt.cam_rot);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return run_tracking(ctx, rig, cfg, n_pairs, 0, ws.store, ws.tt, results, pair_seeds(ws.tt));
 }
 
 int32_t sosvo_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t src_slot,
@@ -735,6 +905,31 @@ int32_t sosvo_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int
   const FrameStore& s = ws.store;
   SOSVO_LAUNCH(ctx, seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m_top,
                s.m_bot, reinterpret_cast<uint4*>(s.d_top), reinterpret_cast<uint4*>(s.d_bot), s.X, s.b_top, s.b_bot, s.M);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
+                                  const int32_t* src_slot, const int32_t* dst_slot, int32_t n_copies, void* workspace,
+                                  size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && src_slot && dst_slot && workspace, "null pointer");
+  Workspace ws;
+  int32_t rc;
+  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_copies >= 0 && n_copies <= cfg->n_pairs, "more copies than cfg->n_pairs",
+                 true, workspace, workspace_bytes, ws));
+  CopyPairs cp;
+  STAGE(check_copy_lists(ctx, __func__, src_slot, dst_slot, n_copies, slots, cp));
+  if (n_copies == 0) return SOSVO_OK;
+  const bool copied = n_copies > kSeqArgPairs;  // (the lists go where a tracking call keeps its slot pairs)
+  if (copied) {
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const FrameStore& s = ws.store;
+  SOSVO_LAUNCH(ctx, seq_copy_slots_kernel, dim3(n_copies, kCopyChunks), dim3(256), 0, ctx->stream, cp,
+               copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, cfg->frame_cap, s.m_top, s.m_bot,
+               reinterpret_cast<uint4*>(s.d_top), reinterpret_cast<uint4*>(s.d_bot), s.X, s.b_top, s.b_bot, s.M);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }
@@ -766,7 +961,7 @@ size_t sosvo_rgbd_pair_batch_workspace(const sosvo_rgbd_batch_cfg* cfg) {
 // pointers.
 static int32_t run_rgbd_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg, int F,
                                   const uint8_t* bgr, const float* depth, const uint32_t* mask_bits, const int8_t* pattern,
-                                  const RgbdFrontTmp& t, const RgbdStore& o) {
+                                  const RgbdFrontTmp& t, const RgbdStore& o, const int32_t* slot_of_frame = nullptr) {
   const int cap = cfg->kp_cap, Fc = cfg->frame_cap;
   int32_t rc;
   const int det = rgbd_detector(*cfg);
@@ -785,24 +980,33 @@ static int32_t run_rgbd_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, con
     STAGE(sosvo_describe_orb(ctx, t.gray, F, cfg->rows, cfg->cols, 1, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern, cfg->edge,
                              t.desc));
   }
-  STAGE(sosvo_rgbd_assemble(ctx, cam, t.kp, t.desc, t.n, depth, F, cfg->rows, cfg->cols, cap, Fc, o.m, o.d, o.X, o.b, o.M));
+  if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
+    STAGE(sosvo_rgbd_assemble_slots(ctx, cam, t.kp, t.desc, t.n, depth, F, slot_of_frame, cfg->rows, cfg->cols, cap, Fc, o.m, o.d,
+                                    o.X, o.b, o.M));
+  else
+    STAGE(sosvo_rgbd_assemble(ctx, cam, t.kp, t.desc, t.n, depth, F, cfg->rows, cfg->cols, cap, Fc, o.m, o.d, o.X, o.b, o.M));
   return SOSVO_OK;
 }
 
 // TrackerRGBDSE3.track_frame (pose_est_tools.py:896-954) for B (reference slot, current slot) pairs of a frame store:
 // query = current frame, train = reference frame; central RANSAC (problem i samples with seed + i) + LM.
 static int32_t run_rgbd_tracking(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int B, uint64_t seed, const RgbdStore& s,
-                                 const RgbdTrackTmp& b, double* results) {
+                                 const RgbdTrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
   const int Fc = cfg->frame_cap;
   int32_t rc;
   STAGE(sosvo_match_hamming(ctx, s.d, s.d, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.keys));
   STAGE(sosvo_sort_matches(ctx, b.keys, s.M, b.cur_frame, B, Fc, b.order));
   STAGE(sosvo_f2f_assemble_central(ctx, cfg->pct_good_matches, cfg->f2f_max_hdiff, s.m, s.X, s.b, s.M, Fc, b.ref_frame,
                                    b.cur_frame, b.keys, b.order, B, Fc, b.f, b.p, b.cq, b.ct, b.cn));
-  STAGE(sosvo_ransac_abs_pose(ctx, b.f, b.p, nullptr, nullptr, nullptr, 1,
-                              cfg->flags & (SOSVO_FLAG_EPNP | SOSVO_FLAG_GP3P | SOSVO_FLAG_TWOPT), b.cn, B, Fc,
-                              cfg->ransac_threshold, cfg->ransac_max_iter, cfg->ransac_adaptive, seed, b.T_ransac, b.mask, b.idx,
-                              b.n_inl, b.info, nullptr));
+  const int32_t rflags = cfg->flags & (SOSVO_FLAG_EPNP | SOSVO_FLAG_GP3P | SOSVO_FLAG_TWOPT);
+  if (seeds)
+    STAGE(sosvo_ransac_abs_pose_seeds(ctx, b.f, b.p, nullptr, nullptr, nullptr, 1, rflags, b.cn, B, Fc, cfg->ransac_threshold,
+                                      cfg->ransac_max_iter, cfg->ransac_adaptive, seeds, b.T_ransac, b.mask, b.idx, b.n_inl,
+                                      b.info, nullptr));
+  else
+    STAGE(sosvo_ransac_abs_pose(ctx, b.f, b.p, nullptr, nullptr, nullptr, 1, rflags, b.cn, B, Fc, cfg->ransac_threshold,
+                                cfg->ransac_max_iter, cfg->ransac_adaptive, seed, b.T_ransac, b.mask, b.idx, b.n_inl, b.info,
+                                nullptr));
   SOSVO_HIP(ctx, hipMemcpyAsync(b.T, b.T_ransac, sizeof(double) * 12 * B, hipMemcpyDeviceToDevice, ctx->stream));
   STAGE(sosvo_refine_abs_pose(ctx, b.f, b.p, nullptr, nullptr, nullptr, 1, b.cn, B, Fc, b.idx, b.n_inl, cfg->lm_max_iter, b.T,
                               b.lm_cost, b.lm_iters));
@@ -871,6 +1075,21 @@ int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam,
                             ws.store.at(first_slot, cfg->frame_cap));
 }
 
+int32_t sosvo_rgbd_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg,
+                                            int32_t window, int32_t slots, const uint8_t* bgr, const float* depth,
+                                            int32_t n_frames, const int32_t* slot_of_frame, const uint32_t* mask_bits,
+                                            const int8_t* pattern, void* workspace, size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cam && cfg && bgr && depth && slot_of_frame && mask_bits && pattern && workspace, "null pointer");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_frames >= 0 && n_frames <= window && n_frames <= slots,
+                      "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
+  STAGE(check_slot_table(ctx, __func__, slot_of_frame, n_frames, slots));
+  if (n_frames == 0) return SOSVO_OK;
+  return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, ws.fe, ws.store, slot_of_frame);
+}
+
 int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
                                   const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs, uint64_t seed, void* workspace,
                                   size_t workspace_bytes, double* results) {
@@ -882,12 +1101,35 @@ int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cf
                       "more slot pairs than cfg->n_pairs", true, workspace, workspace_bytes, ws));
   if (n_pairs == 0) return SOSVO_OK;
   SlotPairs sp;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, n_pairs, slots, ws.tt, sp));
+  PairSeeds ps;
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, nullptr, n_pairs, slots, ws.tt, sp, ps));
   if (n_pairs <= kSeqArgPairs) {  // (copied slot lists need no kernel: nothing else to set up)
-    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ws.tt.ref_frame, ws.tt.cur_frame);
+    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ps, ws.tt.ref_frame, ws.tt.cur_frame,
+                 (uint64_t*)nullptr);
     SOSVO_LAUNCH_CHECK(ctx);
   }
   return run_rgbd_tracking(ctx, cfg, n_pairs, seed, ws.store, ws.tt, results);
+}
+
+int32_t sosvo_rgbd_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
+                                        const int32_t* ref_slot, const int32_t* cur_slot, const uint64_t* seed, int32_t n_pairs,
+                                        void* workspace, size_t workspace_bytes, double* results) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && ref_slot && cur_slot && seed && workspace && results, "null pointer");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs,
+                      "more slot pairs than cfg->n_pairs", true, workspace, workspace_bytes, ws));
+  if (n_pairs == 0) return SOSVO_OK;
+  SlotPairs sp;
+  PairSeeds ps;
+  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, seed, n_pairs, slots, ws.tt, sp, ps));
+  if (n_pairs <= kSeqArgPairs) {
+    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ps, ws.tt.ref_frame, ws.tt.cur_frame,
+                 pair_seeds(ws.tt));
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return run_rgbd_tracking(ctx, cfg, n_pairs, 0, ws.store, ws.tt, results, pair_seeds(ws.tt));
 }
 
 int32_t sosvo_rgbd_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -901,6 +1143,31 @@ int32_t sosvo_rgbd_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg
   if (src_slot == dst_slot) return SOSVO_OK;
   const RgbdStore& s = ws.store;
   SOSVO_LAUNCH(ctx, rgbd_seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m,
+               reinterpret_cast<uint4*>(s.d), s.X, s.b, s.M);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
+                                       const int32_t* src_slot, const int32_t* dst_slot, int32_t n_copies, void* workspace,
+                                       size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && src_slot && dst_slot && workspace, "null pointer");
+  RgbdWorkspace ws;
+  int32_t rc;
+  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_copies >= 0 && n_copies <= cfg->n_pairs,
+                      "more copies than cfg->n_pairs", true, workspace, workspace_bytes, ws));
+  CopyPairs cp;
+  STAGE(check_copy_lists(ctx, __func__, src_slot, dst_slot, n_copies, slots, cp));
+  if (n_copies == 0) return SOSVO_OK;
+  const bool copied = n_copies > kSeqArgPairs;
+  if (copied) {
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const RgbdStore& s = ws.store;
+  SOSVO_LAUNCH(ctx, rgbd_seq_copy_slots_kernel, dim3(n_copies, kCopyChunks), dim3(256), 0, ctx->stream, cp,
+               copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, cfg->frame_cap, s.m,
                reinterpret_cast<uint4*>(s.d), s.X, s.b, s.M);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;

@@ -35,7 +35,11 @@ constexpr int kScoreHypChunkMax = 128;
 __device__ const double kEye9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
 __device__ const double kZero3[3] = {0, 0, 0};
 
+// Problem b samples with seed + b (sosvo_ransac_abs_pose: SeedT = uint64_t) or with its own seeds[b]
+// (sosvo_ransac_abs_pose_seeds: SeedT = const uint64_t*; the problems of one call need not be consecutive frames of one
+// sequence).  The hypothesis kernels are templates on SeedT, so the scalar instantiation is the code it always was.
 __device__ __forceinline__ uint64_t problem_seed(uint64_t seed, int b) { return seed + (uint64_t)b; }
+__device__ __forceinline__ uint64_t problem_seed(const uint64_t* seeds, int b) { return seeds[b]; }
 
 // ---- 1. prepare -----------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void ransac_prepare_kernel(const int32_t* __restrict__ cam,
@@ -136,12 +140,13 @@ __device__ __forceinline__ void hyp_store_wave(double* __restrict__ hyp_b, int i
   }
 }
 
+template <class SeedT>
 __global__ __launch_bounds__(64) void ransac_hyp_kernel(const double* __restrict__ f, const double* __restrict__ p,
                                                         const int32_t* __restrict__ cam,
                                                         const double* __restrict__ cam_off,
                                                         const double* __restrict__ cam_rot,
                                                         const int32_t* __restrict__ n_arr, int nprob, int stride, int H,
-                                                        uint64_t seed, const int32_t* __restrict__ perm,
+                                                        SeedT seed, const int32_t* __restrict__ perm,
                                                         const int32_t* __restrict__ cinfo, double* __restrict__ hyp,
                                                         int32_t* __restrict__ counts) {
   SOSVO_LATENCY_BOUND_PRIO();
@@ -163,9 +168,10 @@ __global__ __launch_bounds__(64) void ransac_hyp_kernel(const double* __restrict
 }
 
 // TWOPT (SOSVO_FLAG_TWOPT, central problems): two distinct correspondences, translation only (sv_hypothesis_twopt).
+template <class SeedT>
 __global__ __launch_bounds__(64) void ransac_hyp_twopt_kernel(const double* __restrict__ f, const double* __restrict__ p,
                                                               const int32_t* __restrict__ n_arr, int nprob, int stride,
-                                                              int H, uint64_t seed, double* __restrict__ hyp,
+                                                              int H, SeedT seed, double* __restrict__ hyp,
                                                               int32_t* __restrict__ counts) {
   int b, chunk;
   if (!hyp_block(nprob, (H + 63) >> 6, &b, &chunk)) return;  // uniform
@@ -183,12 +189,13 @@ __global__ __launch_bounds__(64) void ransac_hyp_twopt_kernel(const double* __re
 // correspondences out of all cameras, sv_hypothesis_gp3p (gp3p_core.h, the oracle's text).  Latency-bound (SQ counters:
 // 32.5 k VALU instructions per wave at 7.2 SIMD-cycles each: chains of FP64 divisions and square roots), so the register
 // budget is capped for three waves per SIMD (measured 2 / 3 / 4 / 5 / 6 waves: 0.785 / 0.700 / 0.715 / 0.806 / 0.781 ms).
+template <class SeedT>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void ransac_hyp_gp3p_kernel(const double* __restrict__ f, const double* __restrict__ p,
                                                              const int32_t* __restrict__ cam,
                                                              const double* __restrict__ cam_off,
                                                              const double* __restrict__ cam_rot,
                                                              const int32_t* __restrict__ n_arr, int nprob, int stride,
-                                                             int H, uint64_t seed, double* __restrict__ hyp,
+                                                             int H, SeedT seed, double* __restrict__ hyp,
                                                              int32_t* __restrict__ counts) {
   SOSVO_LATENCY_BOUND_PRIO();
   int b, chunk;
@@ -233,9 +240,10 @@ __device__ __forceinline__ int epnp_sample_front(const double* __restrict__ f, c
 }
 
 constexpr int kEpnpVecDoubles = 48;
+template <class SeedT>
 __global__ __launch_bounds__(64) void ransac_epnp_eigen_kernel(const double* __restrict__ f, const double* __restrict__ p,
                                                                const int32_t* __restrict__ n_arr, int nprob, int stride,
-                                                               int H, uint64_t seed, double* __restrict__ vvbuf,
+                                                               int H, SeedT seed, double* __restrict__ vvbuf,
                                                                int32_t* __restrict__ counts) {
   int b, chunk;
   if (!hyp_block(nprob, (H + 63) >> 6, &b, &chunk)) return;  // uniform
@@ -256,9 +264,10 @@ __global__ __launch_bounds__(64) void ransac_epnp_eigen_kernel(const double* __r
   counts[(size_t)b * H + it] = ok ? 0 : -1;
 }
 
+template <class SeedT>
 __global__ __launch_bounds__(64) void ransac_epnp_pose_kernel(const double* __restrict__ f, const double* __restrict__ p,
                                                               const int32_t* __restrict__ n_arr, int nprob, int stride,
-                                                              int H, uint64_t seed, const double* __restrict__ vvbuf,
+                                                              int H, SeedT seed, const double* __restrict__ vvbuf,
                                                               double* __restrict__ hyp, int32_t* __restrict__ counts) {
   SOSVO_LATENCY_BOUND_PRIO();
   int b, chunk;
@@ -916,21 +925,32 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(
 
 }  // namespace
 
-extern "C" {
-
-int32_t sosvo_ransac_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, const int32_t* cam,
-                              const double* cam_off, const double* cam_rot, int32_t ncam, int32_t flags,
-                              const int32_t* n, int32_t nprob, int32_t stride, double thr, int32_t max_iter,
-                              int32_t adaptive, uint64_t seed, double* T_out, uint8_t* inlier_mask,
-                              int32_t* inlier_idx, int32_t* n_inliers, int32_t* info, int32_t* hyp_counts) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, f && p && n && T_out && inlier_mask && inlier_idx && n_inliers && info, "null pointer");
-  SOSVO_REQUIRE(ctx, cam == nullptr || (cam_off && cam_rot), "cam given without cam_off / cam_rot");
-  SOSVO_REQUIRE(ctx, ncam >= 1 && ncam <= kMaxCam, "ncam out of range (1..8)");
-  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
-  SOSVO_REQUIRE(ctx, stride > 0 && stride <= (1 << 20), "stride out of range");
-  SOSVO_REQUIRE(ctx, max_iter > 0 && max_iter <= (1 << 20), "max_iter out of range");
-  SOSVO_REQUIRE(ctx, thr > 0.0, "threshold must be positive");
+// sosvo_ransac_abs_pose (SeedT = uint64_t: problem b samples with seed + b) and sosvo_ransac_abs_pose_seeds (SeedT = const
+// uint64_t*: with seed[b]); errors carry the entry point's name `fn`.
+template <class SeedT>
+static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double* f, const double* p, const int32_t* cam,
+                                    const double* cam_off, const double* cam_rot, int32_t ncam, int32_t flags,
+                                    const int32_t* n, int32_t nprob, int32_t stride, double thr, int32_t max_iter,
+                                    int32_t adaptive, SeedT seed, double* T_out,
+                                    uint8_t* inlier_mask, int32_t* inlier_idx, int32_t* n_inliers, int32_t* info,
+                                    int32_t* hyp_counts) {
+// (a hypothesis kernel's SeedT instantiation, labelled with the kernel's plain name for the profile)
+#define SOSVO_LAUNCH_HYP(ctx, kernel, ...)              \
+  do {                                                  \
+    SOSVO_PROFILE(ctx, #kernel);                        \
+    hipLaunchKernelGGL((kernel<SeedT>), __VA_ARGS__);   \
+  } while (0)
+#define SOSVO_REQUIRE_FN(ctx, cond, msg)                               \
+  do {                                                                 \
+    if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, fn, msg);     \
+  } while (0)
+  SOSVO_REQUIRE_FN(ctx, f && p && n && T_out && inlier_mask && inlier_idx && n_inliers && info, "null pointer");
+  SOSVO_REQUIRE_FN(ctx, cam == nullptr || (cam_off && cam_rot), "cam given without cam_off / cam_rot");
+  SOSVO_REQUIRE_FN(ctx, ncam >= 1 && ncam <= kMaxCam, "ncam out of range (1..8)");
+  SOSVO_REQUIRE_FN(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
+  SOSVO_REQUIRE_FN(ctx, stride > 0 && stride <= (1 << 20), "stride out of range");
+  SOSVO_REQUIRE_FN(ctx, max_iter > 0 && max_iter <= (1 << 20), "max_iter out of range");
+  SOSVO_REQUIRE_FN(ctx, thr > 0.0, "threshold must be positive");
   if (nprob == 0) return SOSVO_OK;
   const int H = max_iter;
   // workspace carve-up
@@ -958,25 +978,25 @@ int32_t sosvo_ransac_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, 
                      cam ? ncam : 1, perm, cinfo);
   SOSVO_LAUNCH_CHECK(ctx);
   const int epnp = (flags & SOSVO_FLAG_EPNP) != 0;
-  SOSVO_REQUIRE(ctx, !epnp || cam == nullptr, "SOSVO_FLAG_EPNP is for central problems (cam == NULL)");
+  SOSVO_REQUIRE_FN(ctx, !epnp || cam == nullptr, "SOSVO_FLAG_EPNP is for central problems (cam == NULL)");
   const int twopt = (flags & SOSVO_FLAG_TWOPT) != 0 && !epnp && !(flags & SOSVO_FLAG_GP3P);
-  SOSVO_REQUIRE(ctx, !twopt || cam == nullptr, "SOSVO_FLAG_TWOPT is for central problems (cam == NULL)");
+  SOSVO_REQUIRE_FN(ctx, !twopt || cam == nullptr, "SOSVO_FLAG_TWOPT is for central problems (cam == NULL)");
   if (epnp) adaptive = (adaptive ? 1 : 0) | 2;  // bit 1: the adaptive stop uses 6-point samples
   if (twopt) adaptive = (adaptive ? 1 : 0) | 4;  // bit 2: ... 2-point samples
   if (epnp) {
     double* vvbuf = (double*)(ws + o_vv);
-    SOSVO_LAUNCH(ctx, ransac_epnp_eigen_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
+    SOSVO_LAUNCH_HYP(ctx, ransac_epnp_eigen_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
                  seed, vvbuf, counts);
-    SOSVO_LAUNCH(ctx, ransac_epnp_pose_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
+    SOSVO_LAUNCH_HYP(ctx, ransac_epnp_pose_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
                  seed, vvbuf, hyp, counts);
   } else if (twopt) {
-    SOSVO_LAUNCH(ctx, ransac_hyp_twopt_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H, seed,
+    SOSVO_LAUNCH_HYP(ctx, ransac_hyp_twopt_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H, seed,
                  hyp, counts);
   } else if (flags & SOSVO_FLAG_GP3P) {
-    SOSVO_LAUNCH(ctx, ransac_hyp_gp3p_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, cam, cam_off, cam_rot,
+    SOSVO_LAUNCH_HYP(ctx, ransac_hyp_gp3p_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, cam, cam_off, cam_rot,
                  n, nprob, stride, H, seed, hyp, counts);
   } else
-    SOSVO_LAUNCH(ctx, ransac_hyp_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n,
+    SOSVO_LAUNCH_HYP(ctx, ransac_hyp_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n,
                  nprob, stride, H, seed, perm, cinfo, hyp, counts);
   SOSVO_LAUNCH_CHECK(ctx);
 
@@ -1017,6 +1037,31 @@ int32_t sosvo_ransac_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, 
                        n_inliers, info);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
+}
+#undef SOSVO_REQUIRE_FN
+#undef SOSVO_LAUNCH_HYP
+
+extern "C" {
+
+int32_t sosvo_ransac_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, const int32_t* cam,
+                              const double* cam_off, const double* cam_rot, int32_t ncam, int32_t flags,
+                              const int32_t* n, int32_t nprob, int32_t stride, double thr, int32_t max_iter,
+                              int32_t adaptive, uint64_t seed, double* T_out, uint8_t* inlier_mask,
+                              int32_t* inlier_idx, int32_t* n_inliers, int32_t* info, int32_t* hyp_counts) {
+  SOSVO_ENTER(ctx);
+  return ransac_abs_pose_impl(ctx, __func__, f, p, cam, cam_off, cam_rot, ncam, flags, n, nprob, stride, thr, max_iter, adaptive,
+                              seed, T_out, inlier_mask, inlier_idx, n_inliers, info, hyp_counts);
+}
+
+int32_t sosvo_ransac_abs_pose_seeds(sosvo_ctx* ctx, const double* f, const double* p, const int32_t* cam,
+                                    const double* cam_off, const double* cam_rot, int32_t ncam, int32_t flags,
+                                    const int32_t* n, int32_t nprob, int32_t stride, double thr, int32_t max_iter,
+                                    int32_t adaptive, const uint64_t* seeds, double* T_out, uint8_t* inlier_mask,
+                                    int32_t* inlier_idx, int32_t* n_inliers, int32_t* info, int32_t* hyp_counts) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, seeds, "null seed array");
+  return ransac_abs_pose_impl(ctx, __func__, f, p, cam, cam_off, cam_rot, ncam, flags, n, nprob, stride, thr, max_iter, adaptive,
+                              seeds, T_out, inlier_mask, inlier_idx, n_inliers, info, hyp_counts);
 }
 
 int32_t sosvo_refine_abs_pose(sosvo_ctx* ctx, const double* f, const double* p, const int32_t* cam,

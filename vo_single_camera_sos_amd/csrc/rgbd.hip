@@ -17,16 +17,16 @@ namespace {
 
 constexpr int kThreads = 256;
 
-__global__ __launch_bounds__(kThreads) void rgbd_assemble_kernel(sosvo_rgbd_cam cam, const float* __restrict__ kp,
-                                                                 const uint4* __restrict__ desc,
-                                                                 const int32_t* __restrict__ n_kp,
-                                                                 const float* __restrict__ depth, int rows, int cols,
-                                                                 int cap, int out_cap, float* __restrict__ m,
-                                                                 uint4* __restrict__ d, double* __restrict__ X,
-                                                                 double* __restrict__ b, int32_t* __restrict__ M) {
+// The record of input frame `fr` (one workgroup) written at record `slot` of the outputs.
+__device__ __forceinline__ void rgbd_assemble_frame(const int fr, const int slot, const sosvo_rgbd_cam& cam,
+                                                    const float* __restrict__ kp, const uint4* __restrict__ desc,
+                                                    const int32_t* __restrict__ n_kp, const float* __restrict__ depth,
+                                                    int rows, int cols, int cap, int out_cap, float* __restrict__ m,
+                                                    uint4* __restrict__ d, double* __restrict__ X, double* __restrict__ b,
+                                                    int32_t* __restrict__ M) {
   __shared__ int wave_off[kThreads / 64 + 1];
   __shared__ int s_running;
-  const int tid = threadIdx.x, fr = blockIdx.x;
+  const int tid = threadIdx.x;
   if (tid == 0) s_running = 0;
   __syncthreads();
   const int n = min(n_kp[fr], cap);
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kThreads) void rgbd_assemble_kernel(sosvo_rgbd_cam 
     }
     const int pos = sosvo_block_compact_pos(valid, wave_off, &s_running, tid);
     if (valid && pos < out_cap) {
-      const size_t o = (size_t)fr * out_cap + pos;
+      const size_t o = (size_t)slot * out_cap + pos;
       m[2 * o] = x;
       m[2 * o + 1] = y;
       d[2 * o] = desc[2 * ((size_t)fr * cap + i)];
@@ -74,7 +74,31 @@ __global__ __launch_bounds__(kThreads) void rgbd_assemble_kernel(sosvo_rgbd_cam 
     }
   }
   __syncthreads();
-  if (tid == 0) M[fr] = min(s_running, out_cap);
+  if (tid == 0) M[slot] = min(s_running, out_cap);
+}
+
+// frame blockIdx.x -> record blockIdx.x
+__global__ __launch_bounds__(kThreads) void rgbd_assemble_kernel(sosvo_rgbd_cam cam, const float* __restrict__ kp,
+                                                                 const uint4* __restrict__ desc,
+                                                                 const int32_t* __restrict__ n_kp,
+                                                                 const float* __restrict__ depth, int rows, int cols,
+                                                                 int cap, int out_cap, float* __restrict__ m,
+                                                                 uint4* __restrict__ d, double* __restrict__ X,
+                                                                 double* __restrict__ b, int32_t* __restrict__ M) {
+  rgbd_assemble_frame(blockIdx.x, blockIdx.x, cam, kp, desc, n_kp, depth, rows, cols, cap, out_cap, m, d, X, b, M);
+}
+
+// frame frame0 + blockIdx.x -> record tab.slot[blockIdx.x] (sosvo_rgbd_sequence_front_end_slots; the table is a kernel argument)
+__global__ __launch_bounds__(kThreads) void rgbd_assemble_slots_kernel(sosvo_rgbd_cam cam, sosvo_slot_table tab, int frame0,
+                                                                       const float* __restrict__ kp,
+                                                                       const uint4* __restrict__ desc,
+                                                                       const int32_t* __restrict__ n_kp,
+                                                                       const float* __restrict__ depth, int rows, int cols,
+                                                                       int cap, int out_cap, float* __restrict__ m,
+                                                                       uint4* __restrict__ d, double* __restrict__ X,
+                                                                       double* __restrict__ b, int32_t* __restrict__ M) {
+  rgbd_assemble_frame(frame0 + (int)blockIdx.x, tab.slot[blockIdx.x], cam, kp, desc, n_kp, depth, rows, cols, cap, out_cap, m, d,
+                      X, b, M);
 }
 
 __global__ __launch_bounds__(kThreads) void f2f_assemble_central_kernel(
@@ -141,6 +165,28 @@ int32_t sosvo_rgbd_assemble(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam_host, cons
                reinterpret_cast<const uint4*>(desc), n, depth, rows, cols, cap, out_cap, m, reinterpret_cast<uint4*>(d), X, b,
                M);
   SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+// (internal, common.h) sosvo_rgbd_assemble with the record of frame i written at record slot_of_frame[i] of the outputs
+// (HOST table, checked by the caller: distinct records inside the outputs)
+int32_t sosvo_rgbd_assemble_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam_host, const float* kp, const uint8_t* desc,
+                                  const int32_t* n, const float* depth, int32_t nframes, const int32_t* slot_of_frame,
+                                  int32_t rows, int32_t cols, int32_t cap, int32_t out_cap, float* m, uint8_t* d, double* X,
+                                  double* b, int32_t* M) {
+  SOSVO_REQUIRE(ctx, cam_host && kp && desc && n && depth && slot_of_frame && m && d && X && b && M, "null pointer");
+  SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= (1 << 20) && rows > 0 && cols > 0 && cap > 0 && out_cap > 0,
+                "sizes out of range");
+  SOSVO_REQUIRE(ctx, cam_host->fx != 0 && cam_host->fy != 0, "focal lengths must be non-zero");
+  SOSVO_REQUIRE(ctx, (((uintptr_t)desc | (uintptr_t)d) & 15) == 0, "descriptor buffers must be 16-byte aligned");
+  for (int f0 = 0; f0 < nframes; f0 += kSosvoSlotArgFrames) {
+    const int nf = nframes - f0 < kSosvoSlotArgFrames ? nframes - f0 : kSosvoSlotArgFrames;
+    sosvo_slot_table tab;
+    for (int i = 0; i < kSosvoSlotArgFrames; ++i) tab.slot[i] = i < nf ? slot_of_frame[f0 + i] : 0;
+    SOSVO_LAUNCH(ctx, rgbd_assemble_slots_kernel, dim3(nf), dim3(kThreads), 0, ctx->stream, *cam_host, tab, f0, kp,
+                 reinterpret_cast<const uint4*>(desc), n, depth, rows, cols, cap, out_cap, m, reinterpret_cast<uint4*>(d), X, b, M);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
   return SOSVO_OK;
 }
 

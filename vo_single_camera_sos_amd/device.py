@@ -459,10 +459,12 @@ class Context(object):
         return _ptr(cam), _ptr(cam_off), _ptr(cam_rot), ncam
 
     def ransac_abs_pose(self, f, p, n, thr, max_iter, seed=0, adaptive=False, cam=None, cam_off=None,
-                        cam_rot=None, cam_rot_identity=False, want_counts=False, out=None, epnp=False, gp3p=False, twopt=False):
+                        cam_rot=None, cam_rot_identity=False, want_counts=False, out=None, epnp=False, gp3p=False, twopt=False,
+                        seeds=None):
         """f, p [P, S, 3] f64, n [P] i32 (+ cam [P, S] i32, cam_off [C,3], cam_rot [C,3,3]) ->
         dict(T [P,3,4], mask [P,S] u8, idx [P,S] i32, n_inliers [P] i32, info [P,4] i32[, counts [P,max_iter]]).
-        `out` may carry preallocated result tensors (same keys) to avoid allocations in a hot loop."""
+        `out` may carry preallocated result tensors (same keys) to avoid allocations in a hot loop.
+        seeds: one seed per problem (sosvo_ransac_abs_pose_seeds; see ransac_abs_pose_seeds) instead of seed + b."""
         _check(f, torch.float64, "f", (None, None, 3))
         P, S = f.shape[0], f.shape[1]
         _check(p, torch.float64, "p", (P, S, 3))
@@ -487,11 +489,30 @@ class Context(object):
             _check(counts, torch.int32, "counts", (P, int(max_iter)))
         flags = (_lib.FLAG_CAM_ROT_IDENTITY if cam_rot_identity else 0) | (_lib.FLAG_EPNP if epnp else 0) | \
             (_lib.FLAG_GP3P if gp3p else 0) | (_lib.FLAG_TWOPT if twopt else 0)
+        if seeds is not None:
+            if not isinstance(seeds, torch.Tensor):   # host integers (any 64-bit pattern) -> device, as int64 bits
+                import numpy as np
+                seeds = torch.from_numpy(np.array([int(v) & (2 ** 64 - 1) for v in seeds], dtype=np.uint64).view(np.int64)).to(dev)
+            if seeds.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or tuple(seeds.shape) != (P,) \
+                    or not seeds.is_contiguous() or seeds.device != dev:
+                raise SosvoError("seeds: [P] 64-bit integers, contiguous, on the problems' device")
+            self._call(self._lib.sosvo_ransac_abs_pose_seeds, _ptr(f), _ptr(p), cam_p, off_p, rot_p, ncam, flags,
+                       _ptr(n), P, S, float(thr), int(max_iter), 1 if adaptive else 0, _ptr(seeds),
+                       _ptr(out["T"]), _ptr(out["mask"]), _ptr(out["idx"]), _ptr(out["n_inliers"]), _ptr(out["info"]),
+                       _ptr(counts))
+            return out
         self._call(self._lib.sosvo_ransac_abs_pose, _ptr(f), _ptr(p), cam_p, off_p, rot_p, ncam, flags,
                    _ptr(n), P, S, float(thr), int(max_iter), 1 if adaptive else 0, int(seed) & (2 ** 64 - 1),
                    _ptr(out["T"]), _ptr(out["mask"]), _ptr(out["idx"]), _ptr(out["n_inliers"]), _ptr(out["info"]),
                    _ptr(counts))
         return out
+
+    def ransac_abs_pose_seeds(self, f, p, n, thr, max_iter, seeds, **kwargs):
+        """ransac_abs_pose with problem b sampling with seeds[b] ([P] device tensor of 64-bit integers, or host integers)
+        instead of seed + b: the problems of one call may belong to different sequences."""
+        if seeds is None:
+            raise SosvoError("seeds: one per problem")
+        return self.ransac_abs_pose(f, p, n, thr, max_iter, seeds=seeds, **kwargs)
 
     def ransac_rel_pose(self, f1, f2, n, thr, max_iter, algorithm=_lib.REL_EIGHTPT, seed=0, adaptive=False, want_counts=False):
         """f1, f2 [P, S, 3] f64 (bearings of the same features from viewpoints 1 and 2), n [P] i32 ->
@@ -767,6 +788,82 @@ class Context(object):
         self._call(self._lib.sosvo_sequence_frame_counts, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
                    int(first_slot), int(n), _ptr(workspace), int(workspace.numel()), ctypes.cast(out, c_p))
         return [int(out[i]) for i in range(int(n))]
+
+    # ---- several sequences through one store (include/sosvo.h "Several sequences through one frame store")
+    @staticmethod
+    def _host_i32(values):
+        n = len(values)
+        return (ctypes.c_int32 * max(n, 1))(*[int(x) for x in values]), n
+
+    def _track_seeds_args(self, ref_slots, cur_slots, seeds, workspace, results):
+        n = len(ref_slots)
+        if len(cur_slots) != n or len(seeds) != n:
+            raise SosvoError("ref_slots, cur_slots and seeds must have the same length")
+        _check(workspace, torch.uint8, "workspace", ndim=1)
+        _check(results, torch.float64, "results", (None, 16))
+        if results.shape[0] < n:
+            raise SosvoError("results holds fewer rows than slot pairs")
+        ref, cur = self._host_i32(ref_slots)[0], self._host_i32(cur_slots)[0]
+        sd = (ctypes.c_uint64 * max(n, 1))(*[int(x) & (2 ** 64 - 1) for x in seeds])
+        return ref, cur, sd, n
+
+    def sequence_front_end_slots(self, rig, cfg, window, slots, omni, slot_of_frame, unwrap_table, mask_bits, pattern, workspace):
+        """sequence_front_end with frame i's record written to store slot slot_of_frame[i] (host ints, one per frame of
+        omni, no slot twice); asynchronous."""
+        _check(omni, torch.uint8, "omni", (None, cfg.H, cfg.W, 3))
+        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cfg.cols, 2))
+        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cfg.cols))
+        _check(pattern, torch.int8, "pattern", (512, 2))
+        _check(workspace, torch.uint8, "workspace", ndim=1)
+        tab, n = self._host_i32(slot_of_frame)
+        if n != int(omni.shape[0]):
+            raise SosvoError("slot_of_frame: one slot per frame")
+        self._call(self._lib.sosvo_sequence_front_end_slots, ctypes.cast(ctypes.pointer(rig), c_p),
+                   ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), _ptr(omni), n, ctypes.cast(tab, c_p),
+                   _ptr(unwrap_table), _ptr(mask_bits), _ptr(pattern), _ptr(workspace), int(workspace.numel()))
+
+    def sequence_track_seeds(self, rig, cfg, window, slots, ref_slots, cur_slots, seeds, workspace, results):
+        """sequence_track with pair i sampling with seeds[i] (host ints) -> results[:n] (device, asynchronous)."""
+        ref, cur, sd, n = self._track_seeds_args(ref_slots, cur_slots, seeds, workspace, results)
+        self._call(self._lib.sosvo_sequence_track_seeds, ctypes.cast(ctypes.pointer(rig), c_p), ctypes.cast(ctypes.pointer(cfg), c_p),
+                   int(window), int(slots), ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), ctypes.cast(sd, c_p), n, _ptr(workspace),
+                   int(workspace.numel()), _ptr(results))
+        return results
+
+    def sequence_copy_slots(self, cfg, window, slots, src_slots, dst_slots, workspace):
+        """Store slots src_slots[i] -> dst_slots[i], all pairs in one launch (no slot written twice or read and written)."""
+        (src, n), (dst, nd) = self._host_i32(src_slots), self._host_i32(dst_slots)
+        if n != nd:
+            raise SosvoError("src_slots and dst_slots must have the same length")
+        self._call(self._lib.sosvo_sequence_copy_slots, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
+                   ctypes.cast(src, c_p), ctypes.cast(dst, c_p), n, _ptr(workspace), int(workspace.numel()))
+
+    def rgbd_sequence_front_end_slots(self, cam, cfg, window, slots, bgr, depth, slot_of_frame, mask_bits, pattern, workspace):
+        _check(bgr, torch.uint8, "bgr", (None, cfg.rows, cfg.cols, 3))
+        _check(depth, torch.float32, "depth", (bgr.shape[0], cfg.rows, cfg.cols))
+        _check(mask_bits, torch.uint32, "mask_bits", (1, cfg.rows, cfg.cols))
+        _check(pattern, torch.int8, "pattern", (512, 2))
+        _check(workspace, torch.uint8, "workspace", ndim=1)
+        tab, n = self._host_i32(slot_of_frame)
+        if n != int(bgr.shape[0]):
+            raise SosvoError("slot_of_frame: one slot per frame")
+        self._call(self._lib.sosvo_rgbd_sequence_front_end_slots, ctypes.cast(ctypes.pointer(cam), c_p),
+                   ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), _ptr(bgr), _ptr(depth), n, ctypes.cast(tab, c_p),
+                   _ptr(mask_bits), _ptr(pattern), _ptr(workspace), int(workspace.numel()))
+
+    def rgbd_sequence_track_seeds(self, cfg, window, slots, ref_slots, cur_slots, seeds, workspace, results):
+        ref, cur, sd, n = self._track_seeds_args(ref_slots, cur_slots, seeds, workspace, results)
+        self._call(self._lib.sosvo_rgbd_sequence_track_seeds, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
+                   ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), ctypes.cast(sd, c_p), n, _ptr(workspace), int(workspace.numel()),
+                   _ptr(results))
+        return results
+
+    def rgbd_sequence_copy_slots(self, cfg, window, slots, src_slots, dst_slots, workspace):
+        (src, n), (dst, nd) = self._host_i32(src_slots), self._host_i32(dst_slots)
+        if n != nd:
+            raise SosvoError("src_slots and dst_slots must have the same length")
+        self._call(self._lib.sosvo_rgbd_sequence_copy_slots, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
+                   ctypes.cast(src, c_p), ctypes.cast(dst, c_p), n, _ptr(workspace), int(workspace.numel()))
 
     # ---- RGB-D sequence mode ------------------------------------------------------------------------
     def rgbd_sequence_workspace(self, cfg, window, slots):

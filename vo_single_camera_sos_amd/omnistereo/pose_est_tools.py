@@ -426,12 +426,12 @@ def set_detection_method(tracker, method):
             fm.feature_detection_method = tracker.detection_method
 
 
-def sequence_engine_for(tracker, camera_model, first_image, window):
-    """The pipeline.SequenceEngine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
-    StereoPanoramicFrame compute, or None when the configuration has no batched counterpart (then run_VO keeps the
-    per-frame mirror path)."""
+def _sos_engine_settings(tracker, camera_model, first_image):
+    """What a sequence engine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
+    StereoPanoramicFrame compute is built from -> (positional arguments after ctx, keyword arguments, cache key), or None
+    when the configuration has no batched counterpart."""
     from ..frontend import mirror_kp_cap
-    from ..pipeline import RigConfig, SequenceEngine
+    from ..pipeline import RigConfig
     om = camera_model
     method = str(tracker.detection_method).upper()
     fm = getattr(om, "feature_matcher_for_static_stereo", None)   # (what StereoPanoramicFrame detects with)
@@ -453,19 +453,33 @@ def sequence_engine_for(tracker, camera_model, first_image, window):
                     f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     nfeat = tracker.num_features_detection_for_static_stereo
     cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
-    # an engine (frame store, pinned staging buffers, scratch) is kept with the rig and reused by later runs with the same
-    # settings: building one costs more than tracking a hundred frames
-    key = (method, int(window), int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
+    key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model))
+    kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
+                  thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
+                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method)
+    return (model, rig), kwargs, key
+
+
+def sequence_engine_for(tracker, camera_model, first_image, window):
+    """The pipeline.SequenceEngine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
+    StereoPanoramicFrame compute, or None when the configuration has no batched counterpart (then run_VO keeps the
+    per-frame mirror path)."""
+    from ..pipeline import SequenceEngine
+    om = camera_model
+    settings = _sos_engine_settings(tracker, om, first_image)
+    if settings is None:
+        return None
+    args, kwargs, key = settings
+    # an engine (frame store, pinned staging buffers, scratch) is kept with the rig and reused by later runs with the same
+    # settings: building one costs more than tracking a hundred frames
+    key = key[:1] + (int(window),) + key[1:]
     cache = om.__dict__.setdefault("_sequence_engines", {})
     eng = cache.get(key)
     if eng is None:
         cache.clear()   # (one engine per rig: a new configuration replaces the old one's buffers)
-        eng = cache[key] = SequenceEngine(om._context(), model, rig, window=window, num_of_features=nfeat, kp_cap=cap,
-                                          frame_cap=4096, median_win_size=11, thr=tracker.backprojection_score_threshold_3D_to_2D,
-                                          max_iter=tracker.max_ransac_iterations_3D_to_2D, adaptive=True,
-                                          lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method)
+        eng = cache[key] = SequenceEngine(om._context(), *args, window=window, **kwargs)
     else:
         eng.reset()
     return eng
@@ -568,10 +582,9 @@ class DeviceRGBDFrame(RGBDFrame):
         self.engine.promote(self.slot)
 
 
-def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
-    """The pipeline.RGBDSequenceEngine that computes what `tracker` (a TrackerRGBDSE3) and RGBDFrame compute, or None when
-    the configuration has no batched counterpart (then run_VO keeps the per-frame mirror path)."""
-    from ..pipeline import RGBDCamConfig, RGBDSequenceEngine
+def _rgbd_engine_settings(tracker, camera_model, first_rgb):
+    """As _sos_engine_settings for a TrackerRGBDSE3 and RGBDFrame."""
+    from ..pipeline import RGBDCamConfig
     cm = camera_model
     method = str(tracker.detection_method).upper()
     fm = getattr(cm, "feature_matcher_for_motion", None)   # (what RGBDFrame detects with)
@@ -582,25 +595,62 @@ def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
     cam = RGBDCamConfig(cm.fx, cm.fy, cm.center_x, cm.center_y, cm.focal_length_m, cm.depth_is_Z, 0.8, 7.0,
                         f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     shape = tuple(int(v) for v in np.asarray(first_rgb).shape[:2])
-    # (as sequence_engine_for: the engine -- frame store, 136 MB of pinned staging buffers, scratch -- stays with the camera
-    # model and serves later runs with the same settings; building one costs 15 ms, a 128-frame run 45)
-    key = (method, int(window), shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
+    key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
            float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z))
+    kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
+                  thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
+                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
+                  detection_method=method)
+    return (cam,), kwargs, key
+
+
+def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
+    """The pipeline.RGBDSequenceEngine that computes what `tracker` (a TrackerRGBDSE3) and RGBDFrame compute, or None when
+    the configuration has no batched counterpart (then run_VO keeps the per-frame mirror path)."""
+    from ..pipeline import RGBDSequenceEngine
+    cm = camera_model
+    settings = _rgbd_engine_settings(tracker, cm, first_rgb)
+    if settings is None:
+        return None
+    args, kwargs, key = settings
+    # (as sequence_engine_for: the engine -- frame store, 136 MB of pinned staging buffers, scratch -- stays with the camera
+    # model and serves later runs with the same settings; building one costs 15 ms, a 128-frame run 45)
+    key = key[:1] + (int(window),) + key[1:]
     cache = cm.__dict__.setdefault("_sequence_engines", {})
     eng = cache.get(key)
     if eng is None:
         cache.clear()
-        eng = cache[key] = RGBDSequenceEngine(cm._context(), cam, window=window, image_shape=shape,
-                                              num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
-                                              thr=tracker.backprojection_score_threshold_3D_to_2D,
-                                              max_iter=tracker.max_ransac_iterations_3D_to_2D, adaptive=True,
-                                              lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
-                                              detection_method=method)
+        eng = cache[key] = RGBDSequenceEngine(cm._context(), *args, window=window, **kwargs)
     else:
         eng.reset()
     return eng
+
+
+def multi_sequence_engine_for(tracker, camera_model, first_image, window, lanes):
+    """The pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine of `lanes` lanes with the settings sequence_engine_for /
+    rgbd_sequence_engine_for would give a single-sequence engine -> (engine, settings key), or (None, None) when the
+    configuration has no batched counterpart.  Kept with the camera model beside the single-sequence engine (its own
+    cache: a solo run between two multi-sequence runs does not evict it) and reused while nothing of it failed."""
+    from ..pipeline import MultiSequenceEngine, RGBDMultiSequenceEngine
+    rgbd = _is_rgbd_model(camera_model)
+    settings = (_rgbd_engine_settings if rgbd else _sos_engine_settings)(tracker, camera_model, first_image)
+    if settings is None:
+        return None, None
+    args, kwargs, key = settings
+    full = key + (int(window), int(lanes))
+    cache = camera_model.__dict__.setdefault("_multi_sequence_engines", {})
+    eng = cache.get(full)
+    if eng is not None and (eng._error is not None or eng._live):
+        eng = None          # (a device call failed, or a run is still on it: not reused)
+    if eng is None:
+        cache.clear()
+        eng = cache[full] = (RGBDMultiSequenceEngine if rgbd else MultiSequenceEngine)(
+            camera_model._context(), *args, lanes=lanes, window=window, **kwargs)
+    else:
+        eng.reset_counters()
+    return eng, key
 
 
 class TrackerRGBDSE3(TrackerSE3):
@@ -690,6 +740,12 @@ def _rgbd_track_device_frame(self, reference_frame, current_frame):
 
 
 TrackerRGBDSE3._track_device_frame = _rgbd_track_device_frame
+
+
+# A tracker's construction writes to its camera model (the feature matchers; bootstrap_tracker regenerates the azimuthal masks
+# of the panoramas in place), and an engine is built from the model's masks: the lanes of run_VO_many share one camera model,
+# so both happen under this lock (a solo run_VO finds it free).
+_CAMERA_MODEL_LOCK = threading.RLock()
 
 
 def _is_rgbd_model(camera_model):
@@ -821,7 +877,7 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
 
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
-           _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None):
+           _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -921,8 +977,9 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     else:
         img_indices = [0]
         frames = _live_frames
-    tracker = trackerClass(camera_model=camera_model, show_3D_points=False, results_path=results_path)
-    set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
+    with _CAMERA_MODEL_LOCK:
+        tracker = trackerClass(camera_model=camera_model, show_3D_points=False, results_path=results_path)
+        set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -936,7 +993,8 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
             if first is None:
                 return
             engine_state["tried"] = True
-            eng = engine_state["engine"] = (rgbd_sequence_engine_for if rgbd else sequence_engine_for)(
+            # (_engine_for: run_VO_many hands a lane of its multi-sequence engine to each of its runs)
+            eng = engine_state["engine"] = (_engine_for or (rgbd_sequence_engine_for if rgbd else sequence_engine_for))(
                 tracker, camera_model, first[1], W)
             it = itertools.chain([first], it)
             if eng is None:              # no batched counterpart of this configuration: the per-frame path
@@ -1218,3 +1276,163 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
         result.update(run_VO(**kwargs))
     print("%s Done with VO for %s!" % (thread_name, scene_path))
     return result
+
+
+def _lane_limit(n_sequences, lanes, window):
+    """Lanes that run concurrently: `lanes` (None: one per sequence), at most one per sequence, and few enough for the
+    shape limits of the sequence entry points (include/sosvo.h: lanes * window <= 8192 slot pairs per tracking call,
+    lanes * (2 window + 1) <= 65535 slots)."""
+    S = int(n_sequences) if lanes is None else int(lanes)
+    if S < 1:
+        raise ValueError("lanes: at least one")
+    return max(1, min(S, int(n_sequences), 8192 // int(window), 65535 // (2 * int(window) + 1)))
+
+
+def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
+                _keyframe_thresholds=None):
+    """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
+    pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
+    over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
+    need at that moment as ONE batched call).  Tracking one sequence is a serial chain that cannot fill the GPU; several
+    sequences are where the parallelism of real VO comes from.
+
+    sequences: a list of dicts of run_VO's per-sequence arguments (img_filename_template, depth_filename_template,
+    gt_poses_filename, img_indices, results_path, thread_name, est_poses_filename; or _live_frames, run_VO's in-memory
+    source, as scripts/bench_sequences.py uses it); every sequence gets the four result files run_VO writes, in its own
+    results_path.  estimated_frame_poses_TUM.txt, gt_associated_frame_poses_TUM.txt and
+    keyframe_ids.txt are those of run_VO(frame_window=...) on that sequence alone, byte for byte: a frame record is a
+    function of its image and a tracking record of (reference record, current record, seed), so the launch that computes a
+    record does not change it.  The "Avg Time" lines of printed_messages.log are NOT comparable between a lane and a solo
+    run: they come from process_time(), which counts the CPU time of every lane's thread.
+    frame_window: as run_VO's, at least 1 (the per-frame mirror path and live sources have no lanes).
+    lanes: how many sequences run concurrently (None: all, capped by the shape limits of the entry points); further
+    sequences take a lane as one frees up.
+    shard=(rank, world_size): this call processes parallel.shard_range(len(sequences), rank, world_size) only -- sequences
+    are independent, so ranks need no collective; a rank with an empty share returns [].
+    All sequences share the camera model: one rig, one frame size, one detector, one set of tracker settings; a sequence
+    whose tracker or frames do not fit the engine is refused (ValueError from its lane).  Each lane runs run_VO on its own
+    host thread; what the lanes would share they do not use or do not share: the sampler seed of pyopengv.set_seed is only
+    read by the mirror path, the lanes' engine has a cache of its own beside the single-sequence engine's, current_omni_img
+    and the device model of the camera model are only touched under the lock (_CAMERA_MODEL_LOCK) that also covers every
+    lane's tracker construction -- which regenerates the panoramas' azimuthal masks in place --, the staging pool of
+    pipeline.py is created under a lock.
+    -> the list of run_VO's dicts in input order (of this rank's share), each "sequence_mode" entry extended by lane,
+    lanes and the engine's launch counters (pipeline._MultiSequenceBase.reset_counters).  An exception of a lane (a reader
+    that fails, a sequence that does not fit) is raised after every other lane has finished and written its files."""
+    from ..parallel import shard_range
+    sequences = list(sequences)
+    if shard is not None:
+        lo, hi = shard_range(len(sequences), int(shard[0]), int(shard[1]))
+        sequences = sequences[lo:hi]
+    if not sequences:
+        return []
+    W = int(frame_window)
+    if W < 1:
+        raise ValueError("run_VO_many: frame_window >= 1 (the per-frame mirror path has no lanes)")
+    allowed = {"img_filename_template", "depth_filename_template", "gt_poses_filename", "img_indices", "results_path",
+               "thread_name", "est_poses_filename", "_live_frames"}
+    for q in sequences:
+        if not isinstance(q, dict) or not set(q) <= allowed or ("img_filename_template" not in q and "_live_frames" not in q):
+            raise ValueError("run_VO_many: a sequence is a dict of %s" % ", ".join(sorted(allowed)))
+    rgbd = _is_rgbd_model(camera_model)
+    if any((q.get("depth_filename_template") is not None) != rgbd for q in sequences if "_live_frames" not in q):
+        raise ValueError("run_VO_many: %s" % ("an RGB-D camera model needs a depth_filename_template for every sequence" if rgbd
+                                              else "an omnistereo camera model takes no depth maps: SOS and RGB-D "
+                                                   "sequences do not mix"))
+    S = _lane_limit(len(sequences), lanes, W)
+    shared = dict(engine=None, key=None)
+    guard, exited = threading.Lock(), set()
+
+    def engine_for_lane(s):
+        def engine_for(tracker, cm, first_image, window):
+            # (the first lane to arrive builds the engine, current_omni_img and the device model with it, from masks no
+            # other lane's tracker is regenerating at that moment)
+            with _CAMERA_MODEL_LOCK, guard:
+                shape = tuple(np.asarray(first_image).shape[:2])
+                if shared["engine"] is None:
+                    shared["engine"], shared["key"] = multi_sequence_engine_for(tracker, cm, first_image, window, S)
+                    shared["shape"] = shape
+                    if shared["engine"] is None:
+                        shared["engine"] = False
+                    else:   # every lane that still has work counts as live from the first round on: the rounds wait for
+                        for other in range(S):          # the lanes that are still reading their first frame
+                            if other not in exited:
+                                shared["engine"].begin(other)
+                if shared["engine"] is False:
+                    raise ValueError("run_VO_many: this tracker configuration has no batched engine")
+                settings = (_rgbd_engine_settings if rgbd else _sos_engine_settings)(tracker, cm, first_image)
+                if settings is None or settings[2] != shared["key"] or shape != shared["shape"]:
+                    raise ValueError("run_VO_many: the sequence does not fit the lanes' engine (another frame size, rig or "
+                                     "tracker configuration)")
+            return shared["engine"].begin(s)
+        return engine_for
+    todo = list(enumerate(sequences))[::-1]
+    results, failures = [None] * len(sequences), [None] * len(sequences)
+
+    def work(s):
+        while True:
+            with guard:
+                job = todo.pop() if todo else None
+                if job is None:
+                    exited.add(s)
+            if job is None:
+                if shared["engine"]:
+                    shared["engine"].end(s)     # (a lane counted as live before it had anything to run)
+                return
+            i, q = job
+            try:
+                out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method,
+                             _keyframe_thresholds=_keyframe_thresholds, _engine_for=engine_for_lane(s), **q)
+                if "sequence_mode" in out:
+                    out["sequence_mode"].update(lane=s, lanes=S)
+                results[i] = out
+            except BaseException as e:  # noqa: B902 -- raised by the calling thread, after the other lanes
+                failures[i] = e
+            finally:
+                eng = shared["engine"]
+                if eng:
+                    try:
+                        eng.end(s)
+                    except BaseException as e:  # noqa: B902 -- (a device call of the round this lane's end set off)
+                        if failures[i] is None:
+                            failures[i] = e
+    threads = [threading.Thread(target=work, args=(s,), name="sosvo-lane-%d" % s) for s in range(S)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    if shared["engine"]:
+        counters = dict(shared["engine"].counters)
+        for out in results:
+            if out is not None and "sequence_mode" in out:
+                out["sequence_mode"].update(counters)
+    for e in failures:
+        if e is not None:
+            raise e
+    return results
+
+
+def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
+                   frame_window=None, detection_method=None, lanes=None, shard=None):
+    """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
+    scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
+    index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
+    if visualize_VO:
+        raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
+    sequences = []
+    for sc in scenes:
+        scene_path, n_img = sc["scene_path"], int(sc["num_scene_images"])
+        low = scene_path.lower()
+        rig_is_static = "static" in low or "GCT" in scene_path.upper() or "CCNY" in scene_path.upper() or "park" in low \
+            or "grand" in low
+        last = min(last_image_index, n_img) if last_image_index > 0 else n_img
+        sequences.append(dict(gt_poses_filename=None if rig_is_static else os.path.join(scene_path, "gt_TUM.txt"),
+                              est_poses_filename="estimated_frame_poses_TUM.txt",
+                              img_filename_template=sc["scene_img_filename_template"],
+                              depth_filename_template=sc.get("depth_filename_template"),
+                              img_indices=list(range(first_image_index, last, step_for_scene_images)),
+                              results_path=sc["scene_path_vo_results"], thread_name=sc.get("thread_name", "")))
+    results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window,
+                          detection_method=detection_method, lanes=lanes, shard=shard)
+    print("Done with VO for %d sequences!" % len(results))
+    return results

@@ -4,6 +4,8 @@
 asynchronous C-ABI calls on one stream, no host synchronisation inside a step.
 
 Pair i tracks frame 2i+1 (current) against frame 2i (reference / keyframe)."""
+import threading
+
 import numpy as np
 import torch
 
@@ -388,6 +390,7 @@ class FramePairBatch(object):
 
 
 _STAGE_POOL = None
+_STAGE_POOL_LOCK = threading.Lock()   # (the lanes of a MultiSequenceEngine stage from several threads at once)
 _STAGE_THREADS = 4
 
 
@@ -400,9 +403,10 @@ def _stage_rows(dst_np, images):
         for i, im in enumerate(images):
             np.copyto(dst_np[i], im)
         return
-    if _STAGE_POOL is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _STAGE_POOL = ThreadPoolExecutor(_STAGE_THREADS, thread_name_prefix="sosvo-stage")
+    with _STAGE_POOL_LOCK:
+        if _STAGE_POOL is None:
+            from concurrent.futures import ThreadPoolExecutor
+            _STAGE_POOL = ThreadPoolExecutor(_STAGE_THREADS, thread_name_prefix="sosvo-stage")
     list(_STAGE_POOL.map(lambda i: np.copyto(dst_np[i], images[i]), range(len(images))))
 
 
@@ -416,10 +420,11 @@ class _SequenceBase(object):
 
     early_upload = True   # run_VO's staging thread starts a window's host-to-device copy itself (upload_staged); False: A/B
     enqueue_ahead = True  # run_VO enqueues window k + 1 before it works through window k's records (enqueue_staged); False: A/B
+    _slot0 = 0            # first slot of this sequence's 2 W + 1 slots in the store (a lane of a MultiSequenceEngine: s (2 W + 1))
 
     def _init_windows(self, window):
         self.W = max(1, int(window))
-        self.slots, self.key_slot = 2 * self.W + 1, 2 * self.W
+        self.slots, self.key_slot = 2 * self.W + 1, self._slot0 + 2 * self.W
         self.reset()
 
     def reset(self):
@@ -506,9 +511,9 @@ class _SequenceBase(object):
         if self._win_events is None:
             import torch
             self._win_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        self.half = 1 - self.half
-        first = self.half * self.W
-        if self._key_src is not None and first <= self._key_src < first + self.W:
+        w = self._plan_window(n)
+        first = w["first"]
+        if w["refills_promoted"]:
             self._flush_promotion()   # the promoted frame's record is about to be overwritten
         self._win_events[0].record(self.ctx.stream)
         if self._up_pending[buf] == n:            # copied ahead by upload_staged: order the compute stream behind it
@@ -517,14 +522,26 @@ class _SequenceBase(object):
             self._upload(buf, n)
         self._up_pending[buf] = 0
         self._front_end(n, first, buf)
+        if w["cur"]:
+            self._track(w["prev"], w["cur"], w["seed0"], self.spec)
+        if w["cur2"]:
+            self._track(w["prev2"], w["cur2"], w["seed2"], self.spec2)
+        self._win_events[1].record(self.ctx.stream)
+        self._commit_window(w)
+        self.stage_s["enqueue"] += time.perf_counter() - t1
+
+    def _plan_window(self, n):
+        """The bookkeeping of the next window of n frames, nothing on the device: the half it goes to, its slots, the slot
+        pairs and seeds of the two speculative tracking batches.  (Flips self.half; _commit_window() does the rest.)"""
+        self.half = 1 - self.half
+        first = self._slot0 + self.half * self.W
+        refills_promoted = self._key_src is not None and first <= self._key_src < first + self.W
         # speculative tracking: frame i of the window against its predecessor (the first one against the previous
         # window's last frame; the very first frame of the sequence has nothing to track against)
         slots = [first + i for i in range(n)]
         prev = ([self.last_slot] if self.last_slot is not None else []) + slots[:-1]
         cur = slots if self.last_slot is not None else slots[1:]
         seed0 = self.frames_seen - 1 if self.last_slot is not None else 0   # frame t tracks with seed t - 1
-        if cur:
-            self._track(prev, cur, seed0, self.spec)
         # second guess: frame t against frame t - 2 -- the reference whenever frame t - 1 was NOT promoted to keyframe (then
         # the keyframe usually is t - 2: a frame is passed over when it has moved too little, rarely twice in a row).  Same
         # seeds (t - 1), so these are the records the serial call would return; what neither guess covers stays serial.
@@ -535,15 +552,17 @@ class _SequenceBase(object):
         k0 = len(older) - n                                     # position of the window's first frame in `older`
         cur2 = [slots[i] for i in range(n) if k0 + i - 2 >= 0]
         prev2 = [older[k0 + i - 2] for i in range(n) if k0 + i - 2 >= 0]
-        if cur2:
-            self._track(prev2, cur2, self.frames_seen + (n - len(cur2)) - 1, self.spec2)
-        self._win_events[1].record(self.ctx.stream)
-        self._pending = dict(first=first, n=n, slots=slots, prev=prev, n_cur=len(cur), n_cur2=len(cur2),
+        return dict(first=first, n=n, slots=slots, prev=prev, cur=cur, seed0=seed0, prev2=prev2, cur2=cur2,
+                    seed2=self.frames_seen + (n - len(cur2)) - 1, refills_promoted=refills_promoted)
+
+    def _commit_window(self, w):
+        """The window planned by _plan_window() is on its way: it is the pending one, its frames are part of the sequence."""
+        n, slots = w["n"], w["slots"]
+        self._pending = dict(first=w["first"], n=n, slots=slots, prev=w["prev"], n_cur=len(w["cur"]), n_cur2=len(w["cur2"]),
                              frames_seen=self.frames_seen, had_last=self.last_slot is not None)
         self.frames_seen += n
         self.last2_slot = slots[-2] if n >= 2 else self.last_slot
         self.last_slot = slots[-1]
-        self.stage_s["enqueue"] += time.perf_counter() - t1
 
     def collect(self):
         """Waits for the window enqueue_staged() put on the stream and returns its n dicts (see push_window)."""
@@ -552,13 +571,18 @@ class _SequenceBase(object):
         if p is None:
             raise RuntimeError("no window pending")
         t2 = time.perf_counter()
-        n, slots, prev = p["n"], p["slots"], p["prev"]
-        counts = self._counts(p["first"], n)   # synchronises
+        counts = self._counts(p["first"], p["n"])   # synchronises
         spec = self.spec[:p["n_cur"]].cpu().numpy() if p["n_cur"] else np.zeros((0, 16))
         spec2 = self.spec2[:p["n_cur2"]].cpu().numpy() if p["n_cur2"] else np.zeros((0, 16))
         self._pending = None
         self.stage_s["wait_and_readback"] += time.perf_counter() - t2
         self.stage_s["gpu_windows"] += 1e-3 * self._win_events[0].elapsed_time(self._win_events[1])
+        return self._window_records(p, counts, spec, spec2)
+
+    @staticmethod
+    def _window_records(p, counts, spec, spec2):
+        """The n dicts of a window (see push_window) from its plan, its slots' counts and its two speculative batches."""
+        n, slots, prev = p["n"], p["slots"], p["prev"]
         out = []
         for i in range(n):
             t = p["frames_seen"] + i            # index of the frame in the sequence
@@ -949,3 +973,423 @@ class RGBDSequenceEngine(_SequenceBase):
 
     def _copy(self, src, dst):
         self.ctx.rgbd_sequence_copy_slot(self.cfg, self.W, self.slots, src, dst, self.workspace)
+
+
+# ---- several sequences ("lanes") through one engine ----------------------------------------------------------------------
+class _Lane(_SequenceBase):
+    """One sequence of a multi-sequence engine: the bookkeeping of _SequenceBase over its own 2 W + 1 slots of the shared
+    store, with the interface run_VO, sequence_windows, the device frames and the trackers use.  It makes no device call
+    of its own: enqueue_staged(), track() and a promotion that has to be flushed file REQUESTS with the engine, collect()
+    and track() park the calling thread until the engine has served them (see _MultiSequenceBase)."""
+
+    def __init__(self, engine, index):
+        self.engine, self.index, self.ctx = engine, int(index), engine.ctx
+        self.cfg = engine.cfg
+        for name in ("rig_cfg", "cam_cfg", "method", "model"):
+            if hasattr(engine, name):
+                setattr(self, name, getattr(engine, name))
+        self._slot0 = self.index * (2 * engine.W + 1)
+        self._win_req = self._win_res = self._track_req = self._track_res = self._copy_req = None
+        self._init_windows(engine.W)
+
+    def reset(self):
+        eng = self.engine
+        with eng._cv:
+            # (a window that was served has been read back, one that was not never reached the stream: nothing of an aborted
+            # run is left on the compute stream; an upload it started ahead may still read the lane's pinned rows)
+            self._pending = None
+            self._win_req = self._win_res = self._track_req = self._track_res = self._copy_req = None
+            if eng._copy_stream is not None:
+                eng._copy_stream.synchronize()
+            self._up_ahead = [0, 0]      # frames of pinned buffer b already on their way to this lane's device rows b
+            _SequenceBase.reset(self)
+
+    def stage_host(self, images, buf):
+        self.engine._stage_lane(self.index, images, int(buf))
+
+    def upload_staged(self, buf, n):
+        buf, n = int(buf), int(n)
+        if n > 0:
+            self.engine._upload_ahead(self, buf, n)
+
+    def enqueue_staged(self, buf, n):
+        """Files the window (n frames staged in pinned buffer `buf`) with the engine; nothing reaches the device before every
+        live lane waits for the engine."""
+        import time
+        if n <= 0 or n > self.W:
+            raise ValueError("1 .. window frames per push")
+        if self._pending is not None:
+            raise RuntimeError("collect() the pending window first")
+        t1 = time.perf_counter()
+        with self.engine._cv:
+            w = self._plan_window(n)
+            if w["refills_promoted"]:
+                self._flush_promotion()
+            w["buf"] = int(buf)
+            self._win_req, self._win_res = w, None
+            self._commit_window(w)
+        self.stage_s["enqueue"] += time.perf_counter() - t1
+
+    def collect(self):
+        import time
+        p = self._pending
+        if p is None:
+            raise RuntimeError("no window pending")
+        t2 = time.perf_counter()
+        self.engine._park(self, lambda: self._win_res is not None)
+        res, self._win_res, self._pending = self._win_res, None, None
+        self.stage_s["wait_and_readback"] += time.perf_counter() - t2
+        self.stage_s["gpu_windows"] += res["gpu_s"]
+        return self._window_records(p, res["counts"], res["spec"], res["spec2"])
+
+    def track(self, ref_slot, cur_slot, seed):
+        import time
+        t0 = time.perf_counter()
+        self.serial_calls += 1
+        with self.engine._cv:
+            if int(ref_slot) == self.key_slot:
+                self._flush_promotion()
+            self._track_req, self._track_res = (int(ref_slot), int(cur_slot), int(seed)), None
+        self.engine._park(self, lambda: self._track_res is not None)
+        rec, self._track_res = self._track_res, None
+        self.stage_s["serial_track"] += time.perf_counter() - t0
+        return rec
+
+    def _flush_promotion(self):
+        # (a later promotion of this lane replaces one that has not been served: both go to the lane's keyframe slot, and
+        # nothing reads that slot in between -- a reader parks the lane, which gets the request served)
+        if self._key_src is not None:
+            self._copy_req = (self._key_src, self.key_slot)
+            self._key_src = None
+
+
+class _MultiSequenceBase(object):
+    """S sequences ("lanes") that share one camera model through ONE frame store, one stream and one launch per stage and
+    round (include/sosvo.h "Several sequences through one frame store").  lane(s) is an object with the interface of a
+    single-sequence engine; each lane is driven by its own host thread (run_VO_many: one run_VO per lane).  The lanes'
+    requests -- windows, serial tracking calls, promotions to flush -- are only FILED; when every live lane waits for the
+    engine (collect() or track()), the thread that parked last serves everything pending, grouped by kind:
+        promotions  -> one ..._copy_slots call
+        windows     -> one ..._front_end_slots call over all their frames, one ..._track_seeds call for the first guesses
+                       (t against t - 1), one for the second (t against t - 2)
+        track()     -> one ..._track_seeds call
+    and ONE read-back, then wakes the lanes.  A frame record is a function of its image, a tracking record of (reference
+    record, current record, seed): which call computes a record never changes it, so the lanes' results are those of S
+    single-sequence engines whatever the grouping.  begin(s) / end(s) bracket a lane's run (a lane that is not live is not
+    waited for).  Subclasses provide the buffers and the five device calls."""
+
+    def _init_lanes(self, lanes, window):
+        self.S, self.W = max(1, int(lanes)), max(1, int(window))
+        self.window, self.slots = self.S * self.W, self.S * (2 * self.W + 1)
+        self._cv = threading.Condition(threading.RLock())
+        self._live, self._parked, self._error = set(), set(), None
+        self._copy_stream = self._up_events = self._round_events = None
+        self._up_lock = threading.Lock()
+        self.reset_counters()
+
+    def _make_lanes(self):
+        self.lanes = [_Lane(self, s) for s in range(self.S)]
+
+    def reset_counters(self):
+        """front_end_launches / speculative_track_launches / serial_track_launches / copy_launches: device calls made;
+        max_serial_pairs: the largest number of pairs in one serial launch; rounds: serves that held a window;
+        gpu_windows: the rounds' own time on the stream (events around the front end and the speculative batches), seconds."""
+        self.counters = dict(front_end_launches=0, speculative_track_launches=0, serial_track_launches=0, max_serial_pairs=0,
+                             copy_launches=0, rounds=0, host_syncs=0, gpu_windows=0.0)
+
+    def lane(self, s):
+        return self.lanes[int(s)]
+
+    def begin(self, s):
+        """Lane s starts a sequence: it is reset and the engine waits for it from now on."""
+        lane = self.lanes[int(s)]
+        lane.reset()
+        with self._cv:
+            self._live.add(lane.index)
+        return lane
+
+    def end(self, s):
+        """Lane s has finished (sequence exhausted, failed, aborted): its unserved requests are dropped and the others no
+        longer wait for it."""
+        lane = self.lanes[int(s)]
+        with self._cv:
+            self._live.discard(lane.index)
+            self._parked.discard(lane.index)
+            lane._win_req = lane._track_req = lane._copy_req = None
+            self._serve_if_due()
+            self._cv.notify_all()
+
+    def _park(self, lane, ready):
+        with self._cv:
+            if lane.index not in self._live:     # (a lane used on its own, without begin(): served at once)
+                if not ready():
+                    self._serve()
+                return
+            try:
+                while not ready():
+                    self._parked.add(lane.index)
+                    if self._error is not None:
+                        raise RuntimeError("a device call of the multi-sequence engine failed") from self._error
+                    if self._live <= self._parked:
+                        self._serve()
+                        self._cv.notify_all()
+                    else:
+                        self._cv.wait()
+            finally:
+                self._parked.discard(lane.index)
+
+    def _serve_if_due(self):
+        if self._live and self._live <= self._parked and self._error is None:
+            self._serve()
+
+    def _serve(self):
+        try:
+            self._serve_requests()
+            # every parked lane had a request, and it has been served: none of them waits any more, whenever its thread gets
+            # to notice (a lane that files its next request before the others have woken up must not take them for parked)
+            self._parked.clear()
+        except BaseException as e:
+            self._error = e
+            self._cv.notify_all()
+            raise
+
+    def _serve_requests(self):
+        """Everything filed, grouped by kind, on the stream; one read-back.  (Called with the lock held.)"""
+        c = self.counters
+        copies = [l for l in self.lanes if l._copy_req is not None]
+        wins = [l for l in self.lanes if l._win_req is not None]
+        tracks = [l for l in self.lanes if l._track_req is not None]
+        if not (copies or wins or tracks):
+            return
+        with self._stream_scope():
+            if copies:      # before anything refills a promoted frame's half or reads a keyframe slot
+                self._copy_slots([l._copy_req[0] for l in copies], [l._copy_req[1] for l in copies])
+                c["copy_launches"] += 1
+                for l in copies:
+                    l._copy_req = None
+            n_spec = n_spec2 = 0
+            if wins:
+                if self._round_events is None:
+                    self._round_events = self._timing_events()
+                self._round_events[0].record(self.ctx.stream)
+                self._front_end_round([(l.index, l._win_req["buf"], l._win_req["n"]) for l in wins],
+                                      [s_ for l in wins for s_ in l._win_req["slots"]])
+                c["front_end_launches"] += 1
+                ref = [s_ for l in wins for s_ in l._win_req["prev"]]
+                cur = [s_ for l in wins for s_ in l._win_req["cur"]]
+                seeds = [l._win_req["seed0"] + i for l in wins for i in range(len(l._win_req["cur"]))]
+                n_spec = len(cur)
+                if n_spec:
+                    self._track_seeds(ref, cur, seeds, self.spec)
+                    c["speculative_track_launches"] += 1
+                ref2 = [s_ for l in wins for s_ in l._win_req["prev2"]]
+                cur2 = [s_ for l in wins for s_ in l._win_req["cur2"]]
+                seeds2 = [l._win_req["seed2"] + i for l in wins for i in range(len(l._win_req["cur2"]))]
+                n_spec2 = len(cur2)
+                if n_spec2:
+                    self._track_seeds(ref2, cur2, seeds2, self.spec2)
+                    c["speculative_track_launches"] += 1
+                self._round_events[1].record(self.ctx.stream)
+            if tracks:
+                self._track_seeds([l._track_req[0] for l in tracks], [l._track_req[1] for l in tracks],
+                                  [l._track_req[2] for l in tracks], self.serial)
+                c["serial_track_launches"] += 1
+                c["max_serial_pairs"] = max(c["max_serial_pairs"], len(tracks))
+            # ---- one read-back for the round
+            c["host_syncs"] += 1
+            if wins:
+                counts = self._counts_all()      # synchronises
+                spec = self.spec[:n_spec].cpu().numpy() if n_spec else np.zeros((0, 16))
+                spec2 = self.spec2[:n_spec2].cpu().numpy() if n_spec2 else np.zeros((0, 16))
+                gpu_s = 1e-3 * self._round_events[0].elapsed_time(self._round_events[1])
+                c["rounds"] += 1
+                c["gpu_windows"] += gpu_s
+                frames = sum(l._win_req["n"] for l in wins)
+                o1 = o2 = 0
+                for l in wins:
+                    w = l._win_req
+                    n1, n2 = len(w["cur"]), len(w["cur2"])
+                    l._win_res = dict(counts=[counts[s_] for s_ in w["slots"]], spec=spec[o1:o1 + n1], spec2=spec2[o2:o2 + n2],
+                                      gpu_s=gpu_s * w["n"] / frames)     # (the round's time, shared out by frames)
+                    l._win_req = None
+                    o1, o2 = o1 + n1, o2 + n2
+            if tracks:
+                recs = self.serial[:len(tracks)].cpu().numpy()   # synchronises
+                for i, l in enumerate(tracks):
+                    l._track_res, l._track_req = recs[i].copy(), None
+
+    def _stream_scope(self):
+        """(the serving thread is any lane's: its torch work goes to the context's stream, whatever that thread's current one)"""
+        return torch.cuda.stream(self.ctx.stream)
+
+    @staticmethod
+    def _timing_events():
+        return torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    # (the lanes' early uploads: one copy stream, one event per (lane, buffer))
+    def _upload_ahead(self, lane, buf, n):
+        # Not under the engine's lock: a serve holds that across its read-back, and the copy of window k + 1 is meant to run
+        # beside round k.  What it touches is the lane's own: rows (lane, buf) of the input buffers and their event are free
+        # from the collect() of the window that used them until the enqueue_staged() of this one, which the staging thread
+        # orders after this call (sequence_windows' ready queue).
+        with self._up_lock:
+            if self._copy_stream is None:
+                self._up_events = [[torch.cuda.Event(), torch.cuda.Event()] for _ in range(self.S)]
+                self._copy_stream = torch.cuda.Stream(device=self.ctx.device)
+            stream = self._copy_stream
+        with torch.cuda.stream(stream):
+            self._upload_lane(lane.index, buf, n)
+            self._up_events[lane.index][buf].record(stream)
+        lane._up_ahead[buf] = n
+
+    def _input_rows(self, requests):
+        """requests: [(lane, buf, n)] of a round.  Every lane's frames are brought to its own rows of device input buffer
+        `buf` (uploaded ahead on the copy stream, or copied now), then the round's frames are made ONE contiguous range:
+        the rows themselves where they already are one (every lane but the last with a full window, neighbours, one
+        buffer), else gathered into the round buffer by device-to-device copies.  -> (buffer index or None = gathered,
+        first row, frames)."""
+        for s, buf, n in requests:
+            lane = self.lanes[s]
+            if lane._up_ahead[buf] == n:
+                self.ctx.stream.wait_event(self._up_events[s][buf])
+            else:
+                self._upload_lane(s, buf, n)
+            lane._up_ahead[buf] = 0
+        total = sum(n for _, _, n in requests)
+        contiguous = len({buf for _, buf, _ in requests}) == 1 and all(
+            requests[i + 1][0] == requests[i][0] + 1 and requests[i][2] == self.W for i in range(len(requests) - 1))
+        if contiguous:
+            return requests[0][1], requests[0][0] * self.W, total
+        pos = 0
+        for s, buf, n in requests:
+            self._gather_lane(s, buf, n, pos)
+            pos += n
+        return None, 0, total
+
+
+class MultiSequenceEngine(_MultiSequenceBase):
+    """`lanes` SOS sequences of one rig through one SequenceEngine-like store: same keyword arguments as SequenceEngine.
+    The store is sosvo_sequence_workspace(cfg, S W, S (2 W + 1)) with cfg.n_pairs = S W; lane s owns the slots
+    s (2 W + 1) .. s (2 W + 1) + 2 W."""
+
+    def __init__(self, ctx, model, rig, lanes=2, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
+                 quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
+                 ransac_solver="GP3P", detection_method="GFT"):
+        assert isinstance(ctx, Context)
+        self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
+        self._init_lanes(lanes, window)
+        self.cfg = c = batch_cfg(model, self.window, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
+                                 edge, thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
+        self.method = str(detection_method).upper()
+        if str(ransac_solver).upper() not in ("P3P", "GP3P"):
+            raise ValueError("ransac_solver: P3P or GP3P")
+        if getattr(model, "unwrap_table", None) is None:  # once per model
+            model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        nbytes = ctx.sequence_workspace(c, self.window, self.slots)
+        if nbytes <= 0:
+            raise ValueError("bad sequence configuration (lanes * window: at most 8192 frames, lanes * (2 window + 1) <= 65535)")
+        dev, F = ctx.device, self.window
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        shape = (F, model.H, model.W, 3)
+        self._omni = [torch.zeros(shape, dtype=torch.uint8, device=dev) for _ in range(2)]    # lane s: rows s W ..
+        self._round = torch.zeros(shape, dtype=torch.uint8, device=dev)                       # a ragged round, gathered
+        self._host = [torch.zeros(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._host_np = [h.numpy() for h in self._host]
+        self.spec = torch.zeros((F, 16), dtype=torch.float64, device=dev)
+        self.spec2 = torch.zeros((F, 16), dtype=torch.float64, device=dev)
+        self.serial = torch.zeros((self.S, 16), dtype=torch.float64, device=dev)
+        self._make_lanes()
+
+    def _stage_lane(self, s, images, buf):
+        _stage_rows(self._host_np[buf][s * self.W:(s + 1) * self.W], images)
+
+    def _upload_lane(self, s, buf, n):
+        r = s * self.W
+        self._omni[buf][r:r + n].copy_(self._host[buf][r:r + n], non_blocking=True)
+
+    def _gather_lane(self, s, buf, n, pos):
+        r = s * self.W
+        self._round[pos:pos + n].copy_(self._omni[buf][r:r + n], non_blocking=True)
+
+    def _front_end_round(self, requests, slot_of_frame):
+        buf, r, n = self._input_rows(requests)
+        omni = self._round[:n] if buf is None else self._omni[buf][r:r + n]
+        m = self.model
+        self.ctx.sequence_front_end_slots(self.rig, self.cfg, self.window, self.slots, omni, slot_of_frame, m.unwrap_table,
+                                          m.mask_bits, m.pattern, self.workspace)
+
+    def _track_seeds(self, ref_slots, cur_slots, seeds, out):
+        self.ctx.sequence_track_seeds(self.rig, self.cfg, self.window, self.slots, ref_slots, cur_slots, seeds, self.workspace, out)
+
+    def _counts_all(self):
+        return self.ctx.sequence_frame_counts(self.cfg, self.window, self.slots, 0, self.slots, self.workspace)
+
+    def _copy_slots(self, src, dst):
+        self.ctx.sequence_copy_slots(self.cfg, self.window, self.slots, src, dst, self.workspace)
+
+
+class RGBDMultiSequenceEngine(_MultiSequenceBase):
+    """`lanes` RGB-D sequences of one camera through one store: same keyword arguments as RGBDSequenceEngine; the lanes'
+    push_window() takes (bgr, depth) tuples."""
+
+    def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
+                 median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
+                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+        from . import orb_pattern
+        assert isinstance(ctx, Context)
+        self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
+        self._init_lanes(lanes, window)
+        self.cfg = c = rgbd_batch_cfg(cam, self.window, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
+                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
+        self.method = str(detection_method).upper()
+        rows, cols = c.rows, c.cols
+        dev, F = ctx.device, self.window
+        mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
+        self.mask_bits = torch.from_numpy(mb).to(dev)
+        self.pattern = torch.from_numpy(orb_pattern.orb_pattern()).to(dev)
+        nbytes = ctx.rgbd_sequence_workspace(c, self.window, self.slots)
+        if nbytes <= 0:
+            raise ValueError("bad sequence configuration (lanes * window: at most 8192 frames, lanes * (2 window + 1) <= 65535)")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        self._bgr = [torch.zeros((F, rows, cols, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
+        self._depth = [torch.zeros((F, rows, cols), dtype=torch.float32, device=dev) for _ in range(2)]
+        self._round_bgr = torch.zeros((F, rows, cols, 3), dtype=torch.uint8, device=dev)
+        self._round_depth = torch.zeros((F, rows, cols), dtype=torch.float32, device=dev)
+        self._host_bgr = [torch.zeros((F, rows, cols, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._host_depth = [torch.zeros((F, rows, cols), dtype=torch.float32).pin_memory() for _ in range(2)]
+        self._np_bgr, self._np_depth = [h.numpy() for h in self._host_bgr], [h.numpy() for h in self._host_depth]
+        self.spec = torch.zeros((F, 16), dtype=torch.float64, device=dev)
+        self.spec2 = torch.zeros((F, 16), dtype=torch.float64, device=dev)
+        self.serial = torch.zeros((self.S, 16), dtype=torch.float64, device=dev)
+        self._make_lanes()
+
+    def _stage_lane(self, s, images, buf):
+        r = slice(s * self.W, (s + 1) * self.W)
+        _stage_rows(self._np_bgr[buf][r], [im[0] for im in images])
+        _stage_rows(self._np_depth[buf][r], [np.asarray(im[1], dtype=np.float32) for im in images])
+
+    def _upload_lane(self, s, buf, n):
+        r = s * self.W
+        self._bgr[buf][r:r + n].copy_(self._host_bgr[buf][r:r + n], non_blocking=True)
+        self._depth[buf][r:r + n].copy_(self._host_depth[buf][r:r + n], non_blocking=True)
+
+    def _gather_lane(self, s, buf, n, pos):
+        r = s * self.W
+        self._round_bgr[pos:pos + n].copy_(self._bgr[buf][r:r + n], non_blocking=True)
+        self._round_depth[pos:pos + n].copy_(self._depth[buf][r:r + n], non_blocking=True)
+
+    def _front_end_round(self, requests, slot_of_frame):
+        buf, r, n = self._input_rows(requests)
+        bgr, depth = (self._round_bgr[:n], self._round_depth[:n]) if buf is None else \
+            (self._bgr[buf][r:r + n], self._depth[buf][r:r + n])
+        self.ctx.rgbd_sequence_front_end_slots(self.cam, self.cfg, self.window, self.slots, bgr, depth, slot_of_frame,
+                                               self.mask_bits, self.pattern, self.workspace)
+
+    def _track_seeds(self, ref_slots, cur_slots, seeds, out):
+        self.ctx.rgbd_sequence_track_seeds(self.cfg, self.window, self.slots, ref_slots, cur_slots, seeds, self.workspace, out)
+
+    def _counts_all(self):
+        return self.ctx.rgbd_sequence_frame_counts(self.cfg, self.window, self.slots, 0, self.slots, self.workspace)
+
+    def _copy_slots(self, src, dst):
+        self.ctx.rgbd_sequence_copy_slots(self.cfg, self.window, self.slots, src, dst, self.workspace)
