@@ -14,7 +14,9 @@
 //                  a 64-bit __ballot + popcount per wave, summed in LDS, one integer atomic per
 //                  (workgroup, hypothesis).  A squared-cosine test with a 1e-9 guard band decides
 //                  all but near-threshold points without FP64 sqrt/div; the guard band falls back
-//                  to the exact reference formula, so counts are bit-identical to it.
+//                  to the exact reference formula, so counts are bit-identical to it.  With a fixed iteration count and no
+//                  counts asked for: a probe pass over the first 256 points, ransac_prune_kernel (drops every hypothesis
+//                  that provably cannot reach the best count), then the rest of the points for the survivors only.
 //   4. select      sequential semantics of sac::Ransac (strictly-better update, adaptive stop)
 //                  replayed over the counts; exact inlier mask + ascending index list of the winner.
 //   5. refine      one workgroup per problem, Levenberg-Marquardt on (t, Cayley) with fixed-order
@@ -376,29 +378,43 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
     const double* __restrict__ f, const double* __restrict__ p, const int32_t* __restrict__ cam,
     const double* __restrict__ cam_off, const double* __restrict__ cam_rot, const int32_t* __restrict__ n_arr,
     int stride, int H, int hchunk, int hspan, double thr, int fast_ok, const double* __restrict__ hyp,
-    int32_t* __restrict__ counts) {
+    int32_t* __restrict__ counts, int set_lo, int set_hi, int hsplit, const int32_t* __restrict__ alive_idx,
+    const int32_t* __restrict__ n_alive) {
   static_assert(!T1 || (IDENT && PPT <= 4), "tier 1 is written for the identity-rotation form");
   SOSVO_LATENCY_BOUND_PRIO();
   constexpr bool KEEP = !T1;
   __shared__ int lcnt[kScoreHypChunkMax];  // by position in the compacted list
   __shared__ double shyp[kScoreHypChunkMax][12];
   __shared__ unsigned long long sok[(kScoreHypChunkMax + 63) / 64];  // bit = hypothesis of the chunk is a solved one
-  __shared__ int sidx[kScoreHypChunkMax];   // compacted list of the solved hypotheses of the chunk
+  __shared__ int sidx[kScoreHypChunkMax];   // compacted list of the solved hypotheses of the chunk (index in the problem)
+  __shared__ int srec[kScoreHypChunkMax];   // hypothesis (index in the problem) behind entry hh of the chunk
   // tier 1: the solved hypotheses once more in single precision, R, -R^T t and the two coefficients of the error term
   // (see score_tier1_hyp), in list order
   __shared__ float shyp32[T1 ? kScoreHypChunkMax : 1][16];
   const int tid = threadIdx.x, b = blockIdx.z;
   const int n = min(n_arr[b], stride);
+  // The launch's hypotheses: all H of the problem, or (rest pass of the pruned flow) the n_alive[b] that
+  // ransac_prune_kernel listed in alive_idx.  The listed ones fill the first few hypothesis spans only: which workgroup
+  // takes which span rotates with the problem, so that the live workgroups land on all eight XCDs (see below).
+  const int Hb = alive_idx ? n_alive[b] : H;
+  const int xspan = alive_idx ? (int)((blockIdx.x + blockIdx.z) % gridDim.x) : (int)blockIdx.x;
+  if (xspan * hspan >= Hb) return;
   // XCD-aware grid: workgroups are dealt round-robin over the 8 XCDs by linear id, so the dimension with
   // early-exiting workgroups (point blocks beyond n) must NOT be the fastest one: x = hypothesis chunk.
   // Point sets of 64 are split EVENLY over the point blocks this problem needs (nb = sets / 16 rounded up, each block
   // takes ceil(sets / nb) consecutive sets): a ragged problem (say 22 sets) runs as 11 + 11 instead of 16 + 6, so
   // every block amortises its per-hypothesis work (LDS reads, the count atomic) over about the same number of sets.
-  const int nsets = (n + 63) >> 6;
-  const int nb = (nsets + (kThreads / 64) * PPT - 1) / ((kThreads / 64) * PPT);
-  if ((int)blockIdx.y >= nb) return;
+  // The launch covers the point sets [set_lo, set_hi) of every problem (all of them: 0, INT_MAX).  The pruned flow
+  // (ransac_abs_pose_impl) scores a probe range first and the rest for the hypotheses that ransac_prune_kernel left alive.
+  const int sbeg = set_lo, send = min((n + 63) >> 6, set_hi);
+  const int nsets = send - sbeg;
+  const int bcap = hsplit ? PPT : (kThreads / 64) * PPT;  // sets a point block can take
+  const int nb = (nsets + bcap - 1) / bcap;
+  if ((int)blockIdx.y >= nb) return;  // (also nsets <= 0)
   const int spb = (nsets + nb - 1) / nb;
-  const int set0 = blockIdx.y * spb, set1 = min(set0 + spb, nsets);
+  // (hsplit: blocks of floor or ceil(nsets / nb) sets -- 17 sets run as 4 + 3 + 3 + 4 + 3, not 4 + 4 + 4 + 4 + 1)
+  const int set0 = hsplit ? sbeg + ((int)blockIdx.y * nsets) / nb : sbeg + (int)blockIdx.y * spb;
+  const int set1 = hsplit ? sbeg + (((int)blockIdx.y + 1) * nsets) / nb : min(set0 + spb, send);
   const int p0 = set0 * 64;
 
   double fx[KEEP ? PPT : 1], fy[KEEP ? PPT : 1], fz[KEEP ? PPT : 1];
@@ -416,12 +432,16 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   // wave w of a workgroup sits on SIMD w: which wave takes the short column of a ragged block rotates with the
   // workgroup, or SIMD 0 would always carry the most sets and SIMD 3 the fewest
   const int wslot = (wave + blockIdx.x + blockIdx.y + blockIdx.z) & (kThreads / 64 - 1);
+  // hsplit (point blocks of at most PPT sets): every wave takes ALL the sets of the block and every fourth entry of the
+  // hypothesis list instead of every entry on a fourth of the sets -- the four waves carry the same load whatever the
+  // number of sets, and the per-entry work of a wave (LDS broadcasts, the count) is spread over up to PPT sets
+  const int jstep = hsplit ? kThreads / 64 : 1, jbeg = hsplit ? wslot : 0;
   const size_t base = (size_t)b * stride;
   unsigned long long vmask[PPT];
   int nlive_v = 0;
 #pragma unroll
   for (int r = 0; r < PPT; ++r) {
-    const int set = set0 + r * (kThreads / 64) + wslot;
+    const int set = set0 + (hsplit ? r : r * (kThreads / 64) + wslot);
     const int i0 = set * 64;
     const int i = i0 + lane;
     nlive_v += set < set1 ? 1 : 0;
@@ -459,18 +479,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   const float c2hs = (float)((c2 + kTier1QBand) * (1.0 + 1e-6)), c2ls = (float)((c2 - kTier1QBand) * (1.0 - 1e-6));
   // the workgroup's hypotheses [blockIdx.x * hspan, + hspan) go through LDS in chunks of hchunk: the lanes' points are
   // loaded and converted once for all of them
-  const int hend = min(H, ((int)blockIdx.x + 1) * hspan);
-  for (int h0 = blockIdx.x * hspan; h0 < hend; h0 += hchunk) {
+  const int hend = min(Hb, (xspan + 1) * hspan);
+  for (int h0 = xspan * hspan; h0 < hend; h0 += hchunk) {
   const int h1 = min(hend, h0 + hchunk);
   for (int k = tid; k < kScoreHypChunkMax; k += kThreads) lcnt[k] = 0;
   const int nh = h1 - h0;
-  const double* hb = hyp + ((size_t)b * H + h0) * kHypDoubles;
+  const double* hb = hyp + (size_t)b * H * kHypDoubles;
   static_assert(kScoreHypChunkMax == 128, "two words of solved-hypothesis flags");
   if (wave < 2) {  // wave w flags hypotheses [64 w, 64 w + 64): a failed minimal solve left a NaN in R[0]
     const int hh = wave * 64 + lane;
-    const double r00 = hh < nh ? hb[(size_t)hh * kHypDoubles] : 0.0;
+    const int rec = hh < nh ? (alive_idx ? alive_idx[(size_t)b * H + h0 + hh] : h0 + hh) : 0;
+    const double r00 = hh < nh ? hb[(size_t)rec * kHypDoubles] : 0.0;
     const unsigned long long okb = __ballot(hh < nh && r00 == r00);
     if (lane == 0) sok[wave] = okb;
+    srec[hh] = rec;
   }
   __syncthreads();
   // the solved hypotheses go to LDS as a compact list (position = rank among the solved ones, coalesced loads): the
@@ -482,8 +504,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
     const unsigned long long w = hh < 64 ? ok0 : ok1;
     if ((w >> (hh & 63)) & 1ULL) {
       const int pos = __popcll(w & ((1ULL << (hh & 63)) - 1ULL)) + (hh < 64 ? 0 : __popcll(ok0));
-      shyp[pos][e] = hb[(size_t)hh * kHypDoubles + (e < 9 ? e : e + 3)];
-      if (e == 0) sidx[pos] = hh;
+      const int rec = srec[hh];
+      shyp[pos][e] = hb[(size_t)rec * kHypDoubles + (e < 9 ? e : e + 3)];
+      if (e == 0) sidx[pos] = rec;
     }
   }
   __syncthreads();
@@ -589,11 +612,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   };
 
   // the wave's count of live sets is fixed: the hypothesis loop exists once per count (no switch inside it).  The
-  // count of list entry j stays in lane j & 63 of the wave until 64 entries are through.
+  // count of the wave's k-th list entry j = jbeg + k jstep stays in lane k & 63 of the wave until 64 entries are through.
   auto hyp_loop = [&](auto nl) {
     constexpr int NL = decltype(nl)::value;
-    int cntv = 0;
-    for (int j = 0; j < nok; ++j) {
+    int cntv = 0, k = 0;
+    for (int j = jbeg; j < nok; j += jstep, ++k) {
       unsigned long long und[PPT], any = 0ULL;
       int tot = 0;
       if (T1) {
@@ -606,13 +629,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
         }
       }
       if (any) tot += tier2(nl, j, und);  // scalar; with tier 1 in front: rare
-      if (lane == (j & 63)) cntv += tot;
-      if ((j & 63) == 63) {
-        if (cntv) atomicAdd(&lcnt[(j & ~63) + lane], cntv);
+      if (lane == (k & 63)) cntv += tot;
+      if ((k & 63) == 63) {
+        if (cntv) atomicAdd(&lcnt[jbeg + ((k & ~63) + lane) * jstep], cntv);
         cntv = 0;
       }
     }
-    if (cntv) atomicAdd(&lcnt[((nok - 1) & ~63) + lane], cntv);
+    if (cntv) atomicAdd(&lcnt[jbeg + (((k - 1) & ~63) + lane) * jstep], cntv);
   };
   if (nlive >= 4) hyp_loop(std::integral_constant<int, 4>{});
   else if (nlive == 3) hyp_loop(std::integral_constant<int, 3>{});
@@ -621,9 +644,81 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   __syncthreads();
   for (int k = tid; k < nok; k += kThreads) {
     const int v = lcnt[k];
-    if (v) atomicAdd(&counts[(size_t)b * H + h0 + sidx[k]], v);
+    if (v) atomicAdd(&counts[(size_t)b * H + sidx[k]], v);
   }
   }  // chunks of the workgroup
+}
+
+// ---- 3b. prune ---------------------------------------------------------
+// Between the probe pass (counts over the first pn = min(n, 64 probe_sets) points) and the rest pass; one workgroup per
+// problem.  h* = the first solved hypothesis with the largest probe count; L = its count over all n points by the
+// reference's formula (what the score kernel's tiers add up to).  The best full count is >= L, and the full count of
+// hypothesis h is <= probe[h] + (n - pn): h is left alive iff that bound reaches L (a tie may be the first maximum), and
+// only those are scored on the remaining points.  A pruned hypothesis keeps its probe count, which is below L: the
+// select kernel sees the same first maximum as with every count complete.  The hypothesis records are not touched: the
+// survivors leave as an ascending index list (alive_idx[b * H + 0 .. n_alive[b])), which the rest pass walks in spans
+// as full as those of a launch over all hypotheses, whatever fraction survived; workgroups beyond the list exit at once.
+__global__ __launch_bounds__(kThreads) void ransac_prune_kernel(
+    const double* __restrict__ f, const double* __restrict__ p, const int32_t* __restrict__ cam,
+    const double* __restrict__ cam_off, const int32_t* __restrict__ n_arr, int stride, int H, int probe_sets, double thr,
+    const double* __restrict__ hyp, const int32_t* __restrict__ counts, int32_t* __restrict__ alive_idx,
+    int32_t* __restrict__ n_alive) {
+  SOSVO_LATENCY_BOUND_PRIO();
+  __shared__ long long red[kThreads / 64];
+  __shared__ int redc[kThreads / 64];
+  __shared__ int wave_off[kThreads / 64 + 1];
+  const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int n = min(n_arr[b], stride);
+  const int32_t* cb = counts + (size_t)b * H;
+  int32_t* ab = alive_idx + (size_t)b * H;
+  long long best_key = -1;
+  for (int it = tid; it < H; it += kThreads) {
+    const int c = cb[it];
+    const long long key = ((long long)c << 32) | (long long)(0x7FFFFFFF - it);  // max count, then min it
+    if (c >= 0 && key > best_key) best_key = key;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long other = __shfl_down(best_key, o);
+    best_key = other > best_key ? other : best_key;
+  }
+  if (lane == 0) red[wid] = best_key;
+  __syncthreads();
+  best_key = red[0];
+  for (int w = 1; w < kThreads / 64; ++w) best_key = red[w] > best_key ? red[w] : best_key;
+  if (best_key < 0) {  // no solved hypothesis: nothing to score
+    if (tid == 0) n_alive[b] = 0;
+    return;
+  }
+  const int hstar = 0x7FFFFFFF - (int)(best_key & 0xFFFFFFFFLL);
+  const double* hp = hyp + ((size_t)b * H + hstar) * kHypDoubles;
+  const size_t base = (size_t)b * stride;
+  int cnt = 0;
+  for (int i = tid; i < n; i += kThreads) {
+    const size_t row = base + i;
+    const double* o = cam ? cam_off + 3 * cam[row] : kZero3;
+    cnt += inlier_exact<true>(hp, f[3 * row], f[3 * row + 1], f[3 * row + 2], p[3 * row], p[3 * row + 1], p[3 * row + 2], o[0],
+                              o[1], o[2], kEye9, thr) ? 1 : 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+  if (lane == 0) redc[wid] = cnt;
+  __syncthreads();
+  const int L = ((redc[0] + redc[1]) + redc[2]) + redc[3];
+  const int rest = n - min(n, probe_sets * 64);
+  int running = 0;  // stable compaction, 256 hypotheses a round
+  for (int it0 = 0; it0 < H; it0 += kThreads) {
+    const int it = it0 + tid;
+    const int c = it < H ? cb[it] : -1;
+    const bool keep = c >= 0 && c + rest >= L;
+    const unsigned long long bal = __ballot(keep);
+    __syncthreads();
+    if (lane == 0) wave_off[wid + 1] = __popcll(bal);
+    __syncthreads();
+    int off = running;
+    for (int w = 0; w < wid; ++w) off += wave_off[w + 1];
+    if (keep) ab[off + __popcll(bal & ((1ULL << lane) - 1ULL))] = it;
+    running += ((wave_off[1] + wave_off[2]) + wave_off[3]) + wave_off[4];
+  }
+  if (tid == 0) n_alive[b] = running;
 }
 
 // ---- 4. select ------------------------------------------------------------------------------
@@ -966,6 +1061,7 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   const size_t o_counts = carve(sizeof(int32_t) * (size_t)nprob * H);
   const bool epnp_vec = (flags & SOSVO_FLAG_EPNP) != 0;
   const size_t o_vv = carve(epnp_vec ? sizeof(double) * (size_t)nprob * H * kEpnpVecDoubles : 0);
+  const size_t o_alive = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));  // ransac_prune_kernel's survivor lists and their lengths
   int32_t rc = sosvo_ws_reserve(ctx, off);
   if (rc != SOSVO_OK) return rc;
   char* ws = (char*)ctx->ws;
@@ -1018,8 +1114,35 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   hchunks = cdiv(H, hspan);
   const int hchunk = cdiv(hspan, cdiv(hspan, kScoreHypChunkMax));
   dim3 grid(hchunks, gx, nprob);
-#define SOSVO_SCORE_ARGS grid, dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hchunk, hspan, thr, fast_ok, hyp, counts
-  if (t1)
+  // Pruned flow: only where nothing the caller receives depends on the count of a losing
+  // hypothesis -- fixed iteration count, no counts asked for -- and only in the tier-1 form with Kneip P3P hypotheses
+  // (or GP3P: the records and the scoring are the same); a capacity of at least kPruneMinSets sets of 64, or the probe
+  // leaves too little to skip; and at least kPruneMinProblems problems, or the two extra launches cost more than the
+  // skipped work saves (measured at 2000 hypotheses x ~1285 points: 16 problems 42 -> 63 us, 64: 142 -> 136 us, 128: 233 ->
+  // 228 us, 256: 425 -> 377 us).  Everything else scores every hypothesis on every point in one launch, as before.
+  constexpr int kProbeSets = 4, kPruneMinSets = 8, kPruneMinProblems = 64;
+  const bool prune = t1 && adaptive == 0 && hyp_counts == nullptr && !epnp && !twopt && stride >= 64 * kPruneMinSets &&
+                     nprob >= kPruneMinProblems;
+#define SOSVO_SCORE_ARGS grid, dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hchunk, hspan, thr, fast_ok, hyp, counts, 0, INT_MAX, 0, (const int32_t*)nullptr, (const int32_t*)nullptr
+  if (prune) {
+    int32_t* alive_idx = (int32_t*)(ws + o_alive);
+    int32_t* n_alive = alive_idx + (size_t)nprob * H;
+    // Both passes in the hypothesis-split form (point blocks of at most 4 sets, see the kernel): a workgroup sets up a
+    // quarter of the points of a full block, so it takes more hypotheses -- 4 spans in the probe (one block per problem),
+    // 2 in the rest pass and never less than one full LDS chunk there (measured at 256 x 1285 x 2000: probe 97 -> 92 us,
+    // rest 292 -> 272 us against 1 span each; at 64 problems, rest pass with 64 / 125 hypotheses a workgroup: 133 / 91 us)
+    auto pass = [&](int set_lo, int set_hi, int hs, const int32_t* list, const int32_t* nlist) {
+      const int hck = cdiv(hs, cdiv(hs, kScoreHypChunkMax));
+      const int sets = min(set_hi, cdiv(stride, 64)) - set_lo;
+      SOSVO_LAUNCH(ctx,(ransac_score_kernel<true, 4, true>), dim3(cdiv(H, hs), cdiv(sets, 4), nprob), dim3(kThreads), 0,
+                   ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hck, hs, thr, fast_ok, hyp, counts, set_lo, set_hi, 1,
+                   list, nlist);
+    };
+    pass(0, kProbeSets, min(H, 4 * hspan), nullptr, nullptr);
+    SOSVO_LAUNCH(ctx,ransac_prune_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, n, stride, H,
+                 kProbeSets, thr, hyp, counts, alive_idx, n_alive);
+    pass(kProbeSets, INT_MAX, min(H, max(kScoreHypChunkMax, 2 * hspan)), alive_idx, n_alive);
+  } else if (t1)
     SOSVO_LAUNCH(ctx,(ransac_score_kernel<true, 4, true>), SOSVO_SCORE_ARGS);
   else if (ident)
     SOSVO_LAUNCH(ctx,(ransac_score_kernel<true, 4, false>), SOSVO_SCORE_ARGS);
