@@ -206,6 +206,7 @@ struct SlotPairs {
 struct PairSeeds {
   uint64_t seed[kSeqArgPairs];
 };
+// (cam_off == nullptr: the RGB-D family, a central camera with nothing but the slot pairs and seeds to set up)
 __global__ void seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, Foci foci, int32_t* __restrict__ ref_frame,
                                  int32_t* __restrict__ cur_frame, uint64_t* __restrict__ seeds_out, double* __restrict__ cam_off,
                                  double* __restrict__ cam_rot) {
@@ -215,6 +216,7 @@ __global__ void seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, Foci fo
     cur_frame[i] = sp.cur[i];
     if (seeds_out) seeds_out[i] = ps.seed[i];
   }
+  if (!cam_off) return;
   if (i < 3) {
     cam_off[i] = foci.top[i];
     cam_off[3 + i] = foci.bot[i];
@@ -222,60 +224,37 @@ __global__ void seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, Foci fo
   if (i < 18) cam_rot[i] = (i % 9) % 4 == 0 ? 1.0 : 0.0;
 }
 
-// one frame record of the store -> another slot (a frame promoted to keyframe outlives its window)
-__global__ void seq_copy_slot_kernel(int src, int dst, int Fc, float* m_top, float* m_bot, uint4* d_top, uint4* d_bot,
-                                     double* X, double* b_top, double* b_bot, int32_t* M) {
-  const int n = M[src];
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const size_t s = (size_t)src * Fc + i, d = (size_t)dst * Fc + i;
-    m_top[2 * d] = m_top[2 * s];
-    m_top[2 * d + 1] = m_top[2 * s + 1];
-    m_bot[2 * d] = m_bot[2 * s];
-    m_bot[2 * d + 1] = m_bot[2 * s + 1];
-    d_top[2 * d] = d_top[2 * s];
-    d_top[2 * d + 1] = d_top[2 * s + 1];
-    d_bot[2 * d] = d_bot[2 * s];
-    d_bot[2 * d + 1] = d_bot[2 * s + 1];
-    for (int k = 0; k < 3; ++k) {
-      X[3 * d + k] = X[3 * s + k];
-      b_top[3 * d + k] = b_top[3 * s + k];
-      b_bot[3 * d + k] = b_bot[3 * s + k];
-    }
-  }
-  __syncthreads();  // (every thread has read M[src] before it may be overwritten when src == dst is excluded by the caller)
-  if (blockIdx.x == 0 && threadIdx.x == 0) M[dst] = n;
-}
+// A frame store of either family as the copy kernel sees it: per field of a record the base pointer and the bytes of one
+// entry (8 for m*, 32 for d*, 24 for X and b*: all multiples of 8, and every base is 256-byte aligned), then the counts.
+// Unused fields have 0 bytes.
+constexpr int kStoreFields = 7;
+struct StoreFields {
+  char* base[kStoreFields];
+  int32_t bytes[kStoreFields];
+  int32_t* M;
+};
 
-// k (source, destination) pairs in one launch (sosvo_sequence_copy_slots): workgroup (j, c) copies every gridDim.y-th
-// block of 256 entries of pair j.  The host has checked that no slot is written twice or read and written.
+// Frame records of the store -> other slots (a frame promoted to keyframe outlives its window), k (source, destination)
+// pairs in one launch: workgroup (j, c) copies every gridDim.y-th block of 256 8-byte words of each field of pair j (the
+// entries of a slot are contiguous within a field).  The host has checked that no slot is written twice or read and written.
 struct CopyPairs {
   int32_t src[kSeqArgPairs], dst[kSeqArgPairs];
 };
 constexpr int kCopyChunks = 4;
 __global__ __launch_bounds__(256) void seq_copy_slots_kernel(CopyPairs cp, const int32_t* __restrict__ src_list,
-                                                             const int32_t* __restrict__ dst_list, int Fc, float* m_top,
-                                                             float* m_bot, uint4* d_top, uint4* d_bot, double* X, double* b_top,
-                                                             double* b_bot, int32_t* M) {
+                                                             const int32_t* __restrict__ dst_list, int Fc, StoreFields st) {
   const int j = blockIdx.x;
   const int src = src_list ? src_list[j] : cp.src[j], dst = src_list ? dst_list[j] : cp.dst[j];
-  const int n = min(M[src], Fc);
-  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
-    const size_t s = (size_t)src * Fc + i, d = (size_t)dst * Fc + i;
-    m_top[2 * d] = m_top[2 * s];
-    m_top[2 * d + 1] = m_top[2 * s + 1];
-    m_bot[2 * d] = m_bot[2 * s];
-    m_bot[2 * d + 1] = m_bot[2 * s + 1];
-    d_top[2 * d] = d_top[2 * s];
-    d_top[2 * d + 1] = d_top[2 * s + 1];
-    d_bot[2 * d] = d_bot[2 * s];
-    d_bot[2 * d + 1] = d_bot[2 * s + 1];
-    for (int k = 0; k < 3; ++k) {
-      X[3 * d + k] = X[3 * s + k];
-      b_top[3 * d + k] = b_top[3 * s + k];
-      b_bot[3 * d + k] = b_bot[3 * s + k];
-    }
+  const int n = min(st.M[src], Fc);
+#pragma unroll
+  for (int f = 0; f < kStoreFields; ++f) {
+    const size_t slot_bytes = (size_t)Fc * st.bytes[f];
+    const uint2* s = reinterpret_cast<const uint2*>(st.base[f] + src * slot_bytes);
+    uint2* d = reinterpret_cast<uint2*>(st.base[f] + dst * slot_bytes);
+    const int words = n * (st.bytes[f] / 8);
+    for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < words; i += gridDim.y * blockDim.x) d[i] = s[i];
   }
-  if (blockIdx.y == 0 && threadIdx.x == 0) M[dst] = M[src];  // (no slot of the list is both read and written)
+  if (blockIdx.y == 0 && threadIdx.x == 0) st.M[dst] = st.M[src];  // (no slot of the list is both read and written)
 }
 
 // ---- RGB-D variant (BASELINE config 5): the same three parts; a store of `slots` RGBDFrame records (keypoints with valid
@@ -328,6 +307,7 @@ struct RgbdTrackTmp {
   uint32_t* keys;
   uint8_t* mask;
   double *f, *p, *T_ransac, *T, *lm_cost;
+  double *cam_off, *cam_rot;  // (never carved: a central camera has none, they stay null for the setup kernel)
 };
 RgbdTrackTmp carve_rgbd_track(Carver& cv, size_t B, size_t Fc) {
   RgbdTrackTmp t{};
@@ -368,53 +348,6 @@ RgbdWorkspace carve_rgbd(const sosvo_rgbd_batch_cfg& c, size_t window, size_t sl
   return ws;
 }
 
-__global__ void rgbd_seq_setup_kernel(int npairs, SlotPairs sp, PairSeeds ps, int32_t* __restrict__ ref_frame,
-                                      int32_t* __restrict__ cur_frame, uint64_t* __restrict__ seeds_out) {
-  const int i = threadIdx.x;
-  if (i < npairs && i < kSeqArgPairs) {
-    ref_frame[i] = sp.ref[i];
-    cur_frame[i] = sp.cur[i];
-    if (seeds_out) seeds_out[i] = ps.seed[i];
-  }
-}
-
-__global__ __launch_bounds__(256) void rgbd_seq_copy_slots_kernel(CopyPairs cp, const int32_t* __restrict__ src_list,
-                                                                  const int32_t* __restrict__ dst_list, int Fc, float* m, uint4* d,
-                                                                  double* X, double* b, int32_t* M) {
-  const int j = blockIdx.x;
-  const int src = src_list ? src_list[j] : cp.src[j], dst = src_list ? dst_list[j] : cp.dst[j];
-  const int n = min(M[src], Fc);
-  for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n; i += gridDim.y * blockDim.x) {
-    const size_t s = (size_t)src * Fc + i, t = (size_t)dst * Fc + i;
-    m[2 * t] = m[2 * s];
-    m[2 * t + 1] = m[2 * s + 1];
-    d[2 * t] = d[2 * s];
-    d[2 * t + 1] = d[2 * s + 1];
-    for (int k = 0; k < 3; ++k) {
-      X[3 * t + k] = X[3 * s + k];
-      b[3 * t + k] = b[3 * s + k];
-    }
-  }
-  if (blockIdx.y == 0 && threadIdx.x == 0) M[dst] = M[src];
-}
-
-__global__ void rgbd_seq_copy_slot_kernel(int src, int dst, int Fc, float* m, uint4* d, double* X, double* b, int32_t* M) {
-  const int n = M[src];
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const size_t s = (size_t)src * Fc + i, t = (size_t)dst * Fc + i;
-    m[2 * t] = m[2 * s];
-    m[2 * t + 1] = m[2 * s + 1];
-    d[2 * t] = d[2 * s];
-    d[2 * t + 1] = d[2 * s + 1];
-    for (int k = 0; k < 3; ++k) {
-      X[3 * t + k] = X[3 * s + k];
-      b[3 * t + k] = b[3 * s + k];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) M[dst] = n;
-}
-
 __global__ void pair_index_kernel(int npairs, int32_t* __restrict__ ref_frame, int32_t* __restrict__ cur_frame) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < npairs) {
@@ -438,7 +371,7 @@ uint64_t* pair_seeds(const Track& b) {
 }
 
 // The slot pairs of a sequence tracking call (entry point `fn`), checked against the store (host arrays: a bad slot would
-// index outside the store on the device).  Up to kSeqArgPairs come back in `sp` for the family's setup kernel; larger
+// index outside the store on the device).  Up to kSeqArgPairs come back in `sp` for the setup kernel; larger
 // batches are copied to b.ref_frame / b.cur_frame (pageable host memory: the copy returns when staged).
 // seed_host (the ..._track_seeds entry points; nullptr otherwise): the pairs' seeds travel the same way, in `ps` or, copied,
 // to pair_seeds(b).
@@ -798,156 +731,6 @@ int32_t sosvo_frame_pair_batch_streams_join(sosvo_ctx* ctx) {
   return SOSVO_OK;
 }
 
-// ---- sequence mode ---------------------------------------------------------------------------------------
-static bool seq_shape_ok(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
-  return cfg && cfg->n_pairs > 0 && cfg->n_pairs <= 8192 && cfg->rows > 0 && cfg->cols > 0 && cfg->nmask >= 1 && cfg->nmask <= 32 &&
-         cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384 && window >= 1 && window <= 16384 &&
-         slots >= window && slots <= 65535 && detector_ok(cfg->detector, cfg->kp_cap);
-}
-
-size_t sosvo_sequence_workspace(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
-  if (!seq_shape_ok(cfg, window, slots)) return 0;
-  return carve(*cfg, window, slots, nullptr).bytes;
-}
-
-// What every sosvo_sequence_* call checks after its own null check, in this order: the shape, the call's own range
-// (range_ok, range_msg), the alignment (aligned == false: sosvo_sequence_frame_counts, which only reads and never asked
-// for it), the size.  Errors carry the entry point's name `fn`; on SOSVO_OK `ws` is the carved workspace.
-static int32_t seq_open(sosvo_ctx* ctx, const char* fn, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, bool range_ok,
-                        const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes, Workspace& ws) {
-  REQUIRE_FOR(ctx, fn, seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  REQUIRE_FOR(ctx, fn, range_ok, range_msg);
-  if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  ws = carve(*cfg, window, slots, workspace);
-  REQUIRE_FOR(ctx, fn, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_sequence_workspace)");
-  return SOSVO_OK;
-}
-
-int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
-                                 const uint8_t* omni, int32_t n_frames, int32_t first_slot, const uint32_t* unwrap_table,
-                                 const uint32_t* mask_bits, const int8_t* pattern, void* workspace, size_t workspace_bytes) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots,
-                 n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
-                 "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
-  if (n_frames == 0) return SOSVO_OK;
-  return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, ws.fe,
-                       ws.store.at(first_slot, cfg->frame_cap), nullptr, nullptr);
-}
-
-int32_t sosvo_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
-                                       int32_t slots, const uint8_t* omni, int32_t n_frames, const int32_t* slot_of_frame,
-                                       const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
-                                       void* workspace, size_t workspace_bytes) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig && cfg && omni && slot_of_frame && unwrap_table && mask_bits && pattern && workspace, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_frames >= 0 && n_frames <= window && n_frames <= slots,
-                 "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
-  STAGE(check_slot_table(ctx, __func__, slot_of_frame, n_frames, slots));
-  if (n_frames == 0) return SOSVO_OK;
-  return run_front_end(ctx, rig, cfg, n_frames, omni, unwrap_table, mask_bits, pattern, ws.fe, ws.store, nullptr, nullptr,
-                       slot_of_frame);
-}
-
-int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
-                             const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs, uint64_t seed, void* workspace,
-                             size_t workspace_bytes, double* results) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && workspace && results, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs",
-                 true, workspace, workspace_bytes, ws));
-  if (n_pairs == 0) return SOSVO_OK;
-  SlotPairs sp;
-  PairSeeds ps;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, nullptr, n_pairs, slots, ws.tt, sp, ps));
-  // (always launched, copied slot lists or not: it also writes cam_off / cam_rot)
-  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, ps,
-               foci_of(rig), ws.tt.ref_frame, ws.tt.cur_frame, (uint64_t*)nullptr, ws.tt.cam_off, ws.tt.cam_rot);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return run_tracking(ctx, rig, cfg, n_pairs, seed, ws.store, ws.tt, results);
-}
-
-int32_t sosvo_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
-                                   int32_t slots, const int32_t* ref_slot, const int32_t* cur_slot, const uint64_t* seed,
-                                   int32_t n_pairs, void* workspace, size_t workspace_bytes, double* results) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && seed && workspace && results, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs",
-                 true, workspace, workspace_bytes, ws));
-  if (n_pairs == 0) return SOSVO_OK;
-  SlotPairs sp;
-  PairSeeds ps;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, seed, n_pairs, slots, ws.tt, sp, ps));
-  SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, ps,
-               foci_of(rig), ws.tt.ref_frame, ws.tt.cur_frame, pair_seeds(ws.tt), ws.tt.cam_off, ws.tt.cam_rot);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return run_tracking(ctx, rig, cfg, n_pairs, 0, ws.store, ws.tt, results, pair_seeds(ws.tt));
-}
-
-int32_t sosvo_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t src_slot,
-                                 int32_t dst_slot, void* workspace, size_t workspace_bytes) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, cfg && workspace, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots,
-                 "slot out of range", true, workspace, workspace_bytes, ws));
-  if (src_slot == dst_slot) return SOSVO_OK;
-  const FrameStore& s = ws.store;
-  SOSVO_LAUNCH(ctx, seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m_top,
-               s.m_bot, reinterpret_cast<uint4*>(s.d_top), reinterpret_cast<uint4*>(s.d_bot), s.X, s.b_top, s.b_bot, s.M);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
-}
-
-int32_t sosvo_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
-                                  const int32_t* src_slot, const int32_t* dst_slot, int32_t n_copies, void* workspace,
-                                  size_t workspace_bytes) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, cfg && src_slot && dst_slot && workspace, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, n_copies >= 0 && n_copies <= cfg->n_pairs, "more copies than cfg->n_pairs",
-                 true, workspace, workspace_bytes, ws));
-  CopyPairs cp;
-  STAGE(check_copy_lists(ctx, __func__, src_slot, dst_slot, n_copies, slots, cp));
-  if (n_copies == 0) return SOSVO_OK;
-  const bool copied = n_copies > kSeqArgPairs;  // (the lists go where a tracking call keeps its slot pairs)
-  if (copied) {
-    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
-    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
-  }
-  const FrameStore& s = ws.store;
-  SOSVO_LAUNCH(ctx, seq_copy_slots_kernel, dim3(n_copies, kCopyChunks), dim3(256), 0, ctx->stream, cp,
-               copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, cfg->frame_cap, s.m_top, s.m_bot,
-               reinterpret_cast<uint4*>(s.d_top), reinterpret_cast<uint4*>(s.d_bot), s.X, s.b_top, s.b_bot, s.M);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
-}
-
-int32_t sosvo_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t first_slot,
-                                    int32_t n, void* workspace, size_t workspace_bytes, int32_t* counts_host) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, cfg && workspace && counts_host, "null pointer");
-  Workspace ws;
-  int32_t rc;
-  STAGE(seq_open(ctx, __func__, cfg, window, slots, first_slot >= 0 && n >= 0 && first_slot + n <= slots, "slots out of range",
-                 false, workspace, workspace_bytes, ws));
-  if (n == 0) return SOSVO_OK;
-  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, ws.store.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-  SOSVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SOSVO_OK;
-}
-
 size_t sosvo_rgbd_pair_batch_workspace(const sosvo_rgbd_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->kp_cap <= 0 || cfg->frame_cap <= 0 ||
       !detector_ok(rgbd_detector(*cfg), cfg->kp_cap))
@@ -1036,28 +819,264 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   return run_rgbd_tracking(ctx, cfg, B, cfg->seed, ws.store, ws.tt, results);
 }
 
-// ---- RGB-D sequence mode -------------------------------------------------------------------------------------
-static bool rgbd_seq_shape_ok(const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots) {
-  return cfg && cfg->n_pairs > 0 && cfg->n_pairs <= 8192 && cfg->rows > 0 && cfg->cols > 0 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096 &&
+}  // extern "C"
+
+// ---- sequence mode: one body per operation, over a description of the family -------------------------------------
+namespace {
+
+template <typename Cfg>
+bool seq_shape_ok(const Cfg* cfg, int detector, int32_t window, int32_t slots) {
+  return cfg->n_pairs > 0 && cfg->n_pairs <= 8192 && cfg->rows > 0 && cfg->cols > 0 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096 &&
          cfg->frame_cap > 0 && cfg->frame_cap <= 16384 && window >= 1 && window <= 16384 && slots >= window && slots <= 65535 &&
-         detector_ok(rgbd_detector(*cfg), cfg->kp_cap);
+         detector_ok(detector, cfg->kp_cap);
+}
+
+// What the input of a front end consists of, besides the configuration and the frame count
+struct OmniFrames {
+  const sosvo_rig* rig;
+  const uint8_t* omni;
+  const uint32_t *unwrap_table, *mask_bits;
+  const int8_t* pattern;
+};
+struct RgbdFrames {
+  const sosvo_rgbd_cam* cam;
+  const uint8_t* bgr;
+  const float* depth;
+  const uint32_t* mask_bits;
+  const int8_t* pattern;
+};
+
+// A family of sequence entry points: its configuration, workspace and input types, and its runners.  (`rig` of track():
+// the omni rig; the RGB-D tracking calls have none and pass nullptr.)
+struct OmniSeq {
+  using Cfg = sosvo_batch_cfg;
+  using Ws = Workspace;
+  using Frames = OmniFrames;
+  static constexpr const char* kTooSmall = "workspace too small (see sosvo_sequence_workspace)";
+  static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
+    return c && c->nmask >= 1 && c->nmask <= 32 && seq_shape_ok(c, c->detector, window, slots);
+  }
+  static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return ::carve(c, window, slots, base); }
+  static StoreFields fields(const FrameStore& s) {
+    return {{(char*)s.m_top, (char*)s.m_bot, (char*)s.d_top, (char*)s.d_bot, (char*)s.X, (char*)s.b_top, (char*)s.b_bot},
+            {8, 8, 32, 32, 24, 24, 24},
+            s.M};
+  }
+  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const FrontEndTmp& t, const FrameStore& o,
+                           const int32_t* slot_of_frame) {
+    return run_front_end(ctx, in.rig, cfg, F, in.omni, in.unwrap_table, in.mask_bits, in.pattern, t, o, nullptr, nullptr,
+                         slot_of_frame);
+  }
+  static int32_t track(sosvo_ctx* ctx, const sosvo_rig* rig, const Cfg* cfg, int B, uint64_t seed, const Ws& ws, double* results,
+                       const uint64_t* seeds) {
+    return run_tracking(ctx, rig, cfg, B, seed, ws.store, ws.tt, results, seeds);
+  }
+};
+struct RgbdSeq {
+  using Cfg = sosvo_rgbd_batch_cfg;
+  using Ws = RgbdWorkspace;
+  using Frames = RgbdFrames;
+  static constexpr const char* kTooSmall = "workspace too small (see sosvo_rgbd_sequence_workspace)";
+  static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
+    return c && seq_shape_ok(c, rgbd_detector(*c), window, slots);
+  }
+  static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return carve_rgbd(c, window, slots, base); }
+  static StoreFields fields(const RgbdStore& s) {
+    return {{(char*)s.m, (char*)s.d, (char*)s.X, (char*)s.b}, {8, 32, 24, 24}, s.M};
+  }
+  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const RgbdFrontTmp& t, const RgbdStore& o,
+                           const int32_t* slot_of_frame) {
+    return run_rgbd_front_end(ctx, in.cam, cfg, F, in.bgr, in.depth, in.mask_bits, in.pattern, t, o, slot_of_frame);
+  }
+  static int32_t track(sosvo_ctx* ctx, const sosvo_rig*, const Cfg* cfg, int B, uint64_t seed, const Ws& ws, double* results,
+                       const uint64_t* seeds) {
+    return run_rgbd_tracking(ctx, cfg, B, seed, ws.store, ws.tt, results, seeds);
+  }
+};
+
+template <typename Fam>
+size_t seq_workspace(const typename Fam::Cfg* cfg, int32_t window, int32_t slots) {
+  if (!Fam::shape_ok(cfg, window, slots)) return 0;
+  return Fam::carve(*cfg, window, slots, nullptr).bytes;
+}
+
+// What every sosvo_[rgbd_]sequence_* call checks after its own null check, in this order: the shape, the call's own range
+// (range_ok, range_msg), the alignment (aligned == false: ..._frame_counts, which only reads and never asked for it), the
+// size.  Errors carry the entry point's name `fn`; on SOSVO_OK `ws` is the carved workspace.
+template <typename Fam>
+int32_t seq_open(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots, bool range_ok,
+                 const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes, typename Fam::Ws& ws) {
+  REQUIRE_FOR(ctx, fn, Fam::shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
+  REQUIRE_FOR(ctx, fn, range_ok, range_msg);
+  if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+  ws = Fam::carve(*cfg, window, slots, workspace);
+  REQUIRE_FOR(ctx, fn, workspace_bytes >= ws.bytes, Fam::kTooSmall);
+  return SOSVO_OK;
+}
+
+// ..._front_end (slot_of_frame == nullptr: frame i's record goes to slot first_slot + i) and ..._front_end_slots (HOST table)
+template <typename Fam>
+int32_t seq_front_end(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots,
+                      const typename Fam::Frames& in, int32_t n_frames, int32_t first_slot, const int32_t* slot_of_frame,
+                      void* workspace, size_t workspace_bytes) {
+  typename Fam::Ws ws;
+  int32_t rc;
+  const bool fits = slot_of_frame ? n_frames <= slots : first_slot >= 0 && first_slot + n_frames <= slots;
+  STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, n_frames >= 0 && n_frames <= window && fits,
+                      "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
+  if (slot_of_frame) STAGE(check_slot_table(ctx, fn, slot_of_frame, n_frames, slots));
+  if (n_frames == 0) return SOSVO_OK;
+  if (slot_of_frame) return Fam::front_end(ctx, cfg, n_frames, in, ws.fe, ws.store, slot_of_frame);
+  return Fam::front_end(ctx, cfg, n_frames, in, ws.fe, ws.store.at(first_slot, cfg->frame_cap), nullptr);
+}
+
+// ..._track (seed_host == nullptr: pair i samples with seed + i) and ..._track_seeds (HOST list, `seed` unused): the slot
+// pairs reach the device, then the family's tracking.  The setup kernel is launched whenever it has something to write:
+// slot pairs that travel as its arguments, or the rig's cam_off / cam_rot (every omni call).
+template <typename Fam>
+int32_t seq_track(sosvo_ctx* ctx, const char* fn, const sosvo_rig* rig, const typename Fam::Cfg* cfg, int32_t window,
+                  int32_t slots, const int32_t* ref_slot, const int32_t* cur_slot, uint64_t seed, const uint64_t* seed_host,
+                  int32_t n_pairs, void* workspace, size_t workspace_bytes, double* results) {
+  typename Fam::Ws ws;
+  int32_t rc;
+  STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs, "more slot pairs than cfg->n_pairs",
+                      true, workspace, workspace_bytes, ws));
+  if (n_pairs == 0) return SOSVO_OK;
+  SlotPairs sp;
+  PairSeeds ps;
+  STAGE(upload_slot_pairs(ctx, fn, ref_slot, cur_slot, seed_host, n_pairs, slots, ws.tt, sp, ps));
+  uint64_t* seeds = seed_host ? pair_seeds(ws.tt) : nullptr;
+  if (rig || n_pairs <= kSeqArgPairs) {
+    SOSVO_LAUNCH(ctx, seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs > kSeqArgPairs ? 0 : n_pairs, sp, ps,
+                 rig ? foci_of(rig) : Foci{}, ws.tt.ref_frame, ws.tt.cur_frame, seeds, ws.tt.cam_off, ws.tt.cam_rot);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return Fam::track(ctx, rig, cfg, n_pairs, seed_host ? 0 : seed, ws, results, seeds);
+}
+
+// n (source, destination) pairs of the store `st` in one launch: in `cp` up to kSeqArgPairs, in the device lists beyond
+int32_t launch_copy(sosvo_ctx* ctx, const CopyPairs& cp, const int32_t* src_list, const int32_t* dst_list, int32_t n, int Fc,
+                    const StoreFields& st) {
+  SOSVO_LAUNCH(ctx, seq_copy_slots_kernel, dim3(n, kCopyChunks), dim3(256), 0, ctx->stream, cp, src_list, dst_list, Fc, st);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+template <typename Fam>
+int32_t seq_copy_slot(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots, int32_t src,
+                      int32_t dst, void* workspace, size_t workspace_bytes) {
+  typename Fam::Ws ws;
+  int32_t rc;
+  STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, src >= 0 && src < slots && dst >= 0 && dst < slots, "slot out of range", true,
+                      workspace, workspace_bytes, ws));
+  if (src == dst) return SOSVO_OK;
+  CopyPairs cp{};
+  cp.src[0] = src;
+  cp.dst[0] = dst;
+  return launch_copy(ctx, cp, nullptr, nullptr, 1, cfg->frame_cap, Fam::fields(ws.store));
+}
+
+template <typename Fam>
+int32_t seq_copy_slots(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots,
+                       const int32_t* src, const int32_t* dst, int32_t n, void* workspace, size_t workspace_bytes) {
+  typename Fam::Ws ws;
+  int32_t rc;
+  STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, n >= 0 && n <= cfg->n_pairs, "more copies than cfg->n_pairs", true, workspace,
+                      workspace_bytes, ws));
+  CopyPairs cp;
+  STAGE(check_copy_lists(ctx, fn, src, dst, n, slots, cp));
+  if (n == 0) return SOSVO_OK;
+  const bool copied = n > kSeqArgPairs;  // (the lists go where a tracking call keeps its slot pairs)
+  if (copied) {
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+  }
+  return launch_copy(ctx, cp, copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, n, cfg->frame_cap,
+                     Fam::fields(ws.store));
+}
+
+template <typename Fam>
+int32_t seq_frame_counts(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots,
+                         int32_t first_slot, int32_t n, void* workspace, size_t workspace_bytes, int32_t* counts_host) {
+  typename Fam::Ws ws;
+  int32_t rc;
+  STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, first_slot >= 0 && n >= 0 && first_slot + n <= slots, "slots out of range",
+                      false, workspace, workspace_bytes, ws));
+  if (n == 0) return SOSVO_OK;
+  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, ws.store.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+  SOSVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SOSVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sosvo_sequence_workspace(const sosvo_batch_cfg* cfg, int32_t window, int32_t slots) {
+  return seq_workspace<OmniSeq>(cfg, window, slots);
+}
+
+int32_t sosvo_sequence_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
+                                 const uint8_t* omni, int32_t n_frames, int32_t first_slot, const uint32_t* unwrap_table,
+                                 const uint32_t* mask_bits, const int8_t* pattern, void* workspace, size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace, "null pointer");
+  return seq_front_end<OmniSeq>(ctx, __func__, cfg, window, slots, {rig, omni, unwrap_table, mask_bits, pattern}, n_frames,
+                                first_slot, nullptr, workspace, workspace_bytes);
+}
+
+int32_t sosvo_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
+                                       int32_t slots, const uint8_t* omni, int32_t n_frames, const int32_t* slot_of_frame,
+                                       const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
+                                       void* workspace, size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && omni && slot_of_frame && unwrap_table && mask_bits && pattern && workspace, "null pointer");
+  return seq_front_end<OmniSeq>(ctx, __func__, cfg, window, slots, {rig, omni, unwrap_table, mask_bits, pattern}, n_frames, 0,
+                                slot_of_frame, workspace, workspace_bytes);
+}
+
+int32_t sosvo_sequence_track(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
+                             const int32_t* ref_slot, const int32_t* cur_slot, int32_t n_pairs, uint64_t seed, void* workspace,
+                             size_t workspace_bytes, double* results) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && workspace && results, "null pointer");
+  return seq_track<OmniSeq>(ctx, __func__, rig, cfg, window, slots, ref_slot, cur_slot, seed, nullptr, n_pairs, workspace,
+                            workspace_bytes, results);
+}
+
+int32_t sosvo_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int32_t window,
+                                   int32_t slots, const int32_t* ref_slot, const int32_t* cur_slot, const uint64_t* seed,
+                                   int32_t n_pairs, void* workspace, size_t workspace_bytes, double* results) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig && cfg && ref_slot && cur_slot && seed && workspace && results, "null pointer");
+  return seq_track<OmniSeq>(ctx, __func__, rig, cfg, window, slots, ref_slot, cur_slot, 0, seed, n_pairs, workspace,
+                            workspace_bytes, results);
+}
+
+int32_t sosvo_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t src_slot,
+                                 int32_t dst_slot, void* workspace, size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && workspace, "null pointer");
+  return seq_copy_slot<OmniSeq>(ctx, __func__, cfg, window, slots, src_slot, dst_slot, workspace, workspace_bytes);
+}
+
+int32_t sosvo_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots,
+                                  const int32_t* src_slot, const int32_t* dst_slot, int32_t n_copies, void* workspace,
+                                  size_t workspace_bytes) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && src_slot && dst_slot && workspace, "null pointer");
+  return seq_copy_slots<OmniSeq>(ctx, __func__, cfg, window, slots, src_slot, dst_slot, n_copies, workspace, workspace_bytes);
+}
+
+int32_t sosvo_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_batch_cfg* cfg, int32_t window, int32_t slots, int32_t first_slot,
+                                    int32_t n, void* workspace, size_t workspace_bytes, int32_t* counts_host) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, cfg && workspace && counts_host, "null pointer");
+  return seq_frame_counts<OmniSeq>(ctx, __func__, cfg, window, slots, first_slot, n, workspace, workspace_bytes, counts_host);
 }
 
 size_t sosvo_rgbd_sequence_workspace(const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots) {
-  if (!rgbd_seq_shape_ok(cfg, window, slots)) return 0;
-  return carve_rgbd(*cfg, window, slots, nullptr).bytes;
-}
-
-// seq_open for the sosvo_rgbd_sequence_* calls (aligned == false: sosvo_rgbd_sequence_frame_counts)
-static int32_t rgbd_seq_open(sosvo_ctx* ctx, const char* fn, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
-                             bool range_ok, const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes,
-                             RgbdWorkspace& ws) {
-  REQUIRE_FOR(ctx, fn, rgbd_seq_shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
-  REQUIRE_FOR(ctx, fn, range_ok, range_msg);
-  if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  ws = carve_rgbd(*cfg, window, slots, workspace);
-  REQUIRE_FOR(ctx, fn, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_rgbd_sequence_workspace)");
-  return SOSVO_OK;
+  return seq_workspace<RgbdSeq>(cfg, window, slots);
 }
 
 int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg, int32_t window,
@@ -1065,14 +1084,8 @@ int32_t sosvo_rgbd_sequence_front_end(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam,
                                       const uint32_t* mask_bits, const int8_t* pattern, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cam && cfg && bgr && depth && mask_bits && pattern && workspace, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots,
-                      n_frames >= 0 && n_frames <= window && first_slot >= 0 && first_slot + n_frames <= slots,
-                      "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
-  if (n_frames == 0) return SOSVO_OK;
-  return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, ws.fe,
-                            ws.store.at(first_slot, cfg->frame_cap));
+  return seq_front_end<RgbdSeq>(ctx, __func__, cfg, window, slots, {cam, bgr, depth, mask_bits, pattern}, n_frames, first_slot,
+                                nullptr, workspace, workspace_bytes);
 }
 
 int32_t sosvo_rgbd_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const sosvo_rgbd_batch_cfg* cfg,
@@ -1081,13 +1094,8 @@ int32_t sosvo_rgbd_sequence_front_end_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam
                                             const int8_t* pattern, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cam && cfg && bgr && depth && slot_of_frame && mask_bits && pattern && workspace, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_frames >= 0 && n_frames <= window && n_frames <= slots,
-                      "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
-  STAGE(check_slot_table(ctx, __func__, slot_of_frame, n_frames, slots));
-  if (n_frames == 0) return SOSVO_OK;
-  return run_rgbd_front_end(ctx, cam, cfg, n_frames, bgr, depth, mask_bits, pattern, ws.fe, ws.store, slot_of_frame);
+  return seq_front_end<RgbdSeq>(ctx, __func__, cfg, window, slots, {cam, bgr, depth, mask_bits, pattern}, n_frames, 0,
+                                slot_of_frame, workspace, workspace_bytes);
 }
 
 int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -1095,20 +1103,8 @@ int32_t sosvo_rgbd_sequence_track(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cf
                                   size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && ref_slot && cur_slot && workspace && results, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs,
-                      "more slot pairs than cfg->n_pairs", true, workspace, workspace_bytes, ws));
-  if (n_pairs == 0) return SOSVO_OK;
-  SlotPairs sp;
-  PairSeeds ps;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, nullptr, n_pairs, slots, ws.tt, sp, ps));
-  if (n_pairs <= kSeqArgPairs) {  // (copied slot lists need no kernel: nothing else to set up)
-    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ps, ws.tt.ref_frame, ws.tt.cur_frame,
-                 (uint64_t*)nullptr);
-    SOSVO_LAUNCH_CHECK(ctx);
-  }
-  return run_rgbd_tracking(ctx, cfg, n_pairs, seed, ws.store, ws.tt, results);
+  return seq_track<RgbdSeq>(ctx, __func__, nullptr, cfg, window, slots, ref_slot, cur_slot, seed, nullptr, n_pairs, workspace,
+                            workspace_bytes, results);
 }
 
 int32_t sosvo_rgbd_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -1116,36 +1112,15 @@ int32_t sosvo_rgbd_sequence_track_seeds(sosvo_ctx* ctx, const sosvo_rgbd_batch_c
                                         void* workspace, size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && ref_slot && cur_slot && seed && workspace && results, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_pairs >= 0 && n_pairs <= cfg->n_pairs,
-                      "more slot pairs than cfg->n_pairs", true, workspace, workspace_bytes, ws));
-  if (n_pairs == 0) return SOSVO_OK;
-  SlotPairs sp;
-  PairSeeds ps;
-  STAGE(upload_slot_pairs(ctx, __func__, ref_slot, cur_slot, seed, n_pairs, slots, ws.tt, sp, ps));
-  if (n_pairs <= kSeqArgPairs) {
-    SOSVO_LAUNCH(ctx, rgbd_seq_setup_kernel, dim3(1), dim3(64), 0, ctx->stream, n_pairs, sp, ps, ws.tt.ref_frame, ws.tt.cur_frame,
-                 pair_seeds(ws.tt));
-    SOSVO_LAUNCH_CHECK(ctx);
-  }
-  return run_rgbd_tracking(ctx, cfg, n_pairs, 0, ws.store, ws.tt, results, pair_seeds(ws.tt));
+  return seq_track<RgbdSeq>(ctx, __func__, nullptr, cfg, window, slots, ref_slot, cur_slot, 0, seed, n_pairs, workspace,
+                            workspace_bytes, results);
 }
 
 int32_t sosvo_rgbd_sequence_copy_slot(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
                                       int32_t src_slot, int32_t dst_slot, void* workspace, size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, src_slot >= 0 && src_slot < slots && dst_slot >= 0 && dst_slot < slots,
-                      "slot out of range", true, workspace, workspace_bytes, ws));
-  if (src_slot == dst_slot) return SOSVO_OK;
-  const RgbdStore& s = ws.store;
-  SOSVO_LAUNCH(ctx, rgbd_seq_copy_slot_kernel, dim3(1), dim3(1024), 0, ctx->stream, src_slot, dst_slot, cfg->frame_cap, s.m,
-               reinterpret_cast<uint4*>(s.d), s.X, s.b, s.M);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return seq_copy_slot<RgbdSeq>(ctx, __func__, cfg, window, slots, src_slot, dst_slot, workspace, workspace_bytes);
 }
 
 int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -1153,24 +1128,7 @@ int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cf
                                        size_t workspace_bytes) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && src_slot && dst_slot && workspace, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, n_copies >= 0 && n_copies <= cfg->n_pairs,
-                      "more copies than cfg->n_pairs", true, workspace, workspace_bytes, ws));
-  CopyPairs cp;
-  STAGE(check_copy_lists(ctx, __func__, src_slot, dst_slot, n_copies, slots, cp));
-  if (n_copies == 0) return SOSVO_OK;
-  const bool copied = n_copies > kSeqArgPairs;
-  if (copied) {
-    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
-    SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst_slot, sizeof(int32_t) * n_copies, hipMemcpyHostToDevice, ctx->stream));
-  }
-  const RgbdStore& s = ws.store;
-  SOSVO_LAUNCH(ctx, rgbd_seq_copy_slots_kernel, dim3(n_copies, kCopyChunks), dim3(256), 0, ctx->stream, cp,
-               copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, cfg->frame_cap, s.m,
-               reinterpret_cast<uint4*>(s.d), s.X, s.b, s.M);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return seq_copy_slots<RgbdSeq>(ctx, __func__, cfg, window, slots, src_slot, dst_slot, n_copies, workspace, workspace_bytes);
 }
 
 int32_t sosvo_rgbd_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg, int32_t window, int32_t slots,
@@ -1178,14 +1136,7 @@ int32_t sosvo_rgbd_sequence_frame_counts(sosvo_ctx* ctx, const sosvo_rgbd_batch_
                                          int32_t* counts_host) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, cfg && workspace && counts_host, "null pointer");
-  RgbdWorkspace ws;
-  int32_t rc;
-  STAGE(rgbd_seq_open(ctx, __func__, cfg, window, slots, first_slot >= 0 && n >= 0 && first_slot + n <= slots,
-                      "slots out of range", false, workspace, workspace_bytes, ws));
-  if (n == 0) return SOSVO_OK;
-  SOSVO_HIP(ctx, hipMemcpyAsync(counts_host, ws.store.M + first_slot, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-  SOSVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SOSVO_OK;
+  return seq_frame_counts<RgbdSeq>(ctx, __func__, cfg, window, slots, first_slot, n, workspace, workspace_bytes, counts_host);
 }
 
 }  // extern "C"

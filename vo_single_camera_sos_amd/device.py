@@ -746,162 +746,144 @@ class Context(object):
                    _ptr(workspace), int(workspace.numel()), _ptr(results))
         return results
 
-    # ---- sequence mode (include/sosvo.h "Sequence mode") -----------------------------------------
-    def sequence_workspace(self, cfg, window, slots):
-        return int(self._lib.sosvo_sequence_workspace(ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots)))
-
-    def sequence_front_end(self, rig, cfg, window, slots, omni, first_slot, unwrap_table, mask_bits, pattern, workspace):
-        """omni [n,H,W,3] u8 (n <= window) -> store slots first_slot .. first_slot + n - 1 (asynchronous)."""
-        _check(omni, torch.uint8, "omni", (None, cfg.H, cfg.W, 3))
-        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cfg.cols, 2))
-        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cfg.cols))
-        _check(pattern, torch.int8, "pattern", (512, 2))
-        _check(workspace, torch.uint8, "workspace", ndim=1)
-        self._call(self._lib.sosvo_sequence_front_end, ctypes.cast(ctypes.pointer(rig), c_p), ctypes.cast(ctypes.pointer(cfg), c_p),
-                   int(window), int(slots), _ptr(omni), int(omni.shape[0]), int(first_slot), _ptr(unwrap_table), _ptr(mask_bits),
-                   _ptr(pattern), _ptr(workspace), int(workspace.numel()))
-
-    def sequence_track(self, rig, cfg, window, slots, ref_slots, cur_slots, seed, workspace, results):
-        """ref_slots / cur_slots: host int sequences of equal length n <= cfg.n_pairs -> results[:n] [n,16] f64 (device,
-        asynchronous); pair i samples with seed + i."""
-        n = len(ref_slots)
-        if len(cur_slots) != n:
-            raise SosvoError("ref_slots and cur_slots must have the same length")
-        _check(workspace, torch.uint8, "workspace", ndim=1)
-        _check(results, torch.float64, "results", (None, 16))
-        if results.shape[0] < n:
-            raise SosvoError("results holds fewer rows than slot pairs")
-        ref = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in ref_slots])
-        cur = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in cur_slots])
-        self._call(self._lib.sosvo_sequence_track, ctypes.cast(ctypes.pointer(rig), c_p), ctypes.cast(ctypes.pointer(cfg), c_p),
-                   int(window), int(slots), ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), n, int(seed), _ptr(workspace),
-                   int(workspace.numel()), _ptr(results))
-        return results
-
-    def sequence_copy_slot(self, cfg, window, slots, src, dst, workspace):
-        self._call(self._lib.sosvo_sequence_copy_slot, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), int(src),
-                   int(dst), _ptr(workspace), int(workspace.numel()))
-
-    def sequence_frame_counts(self, cfg, window, slots, first_slot, n, workspace):
-        """-> list of n ints (StereoPanoramicFrame.num_valid_keypoints of the slots); synchronises the stream."""
-        out = (ctypes.c_int32 * max(int(n), 1))()
-        self._call(self._lib.sosvo_sequence_frame_counts, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   int(first_slot), int(n), _ptr(workspace), int(workspace.numel()), ctypes.cast(out, c_p))
-        return [int(out[i]) for i in range(int(n))]
-
-    # ---- several sequences through one store (include/sosvo.h "Several sequences through one frame store")
+    # ---- sequence mode, one or several sequences through one store (include/sosvo.h "Sequence mode", "Several sequences
+    # through one frame store").  One helper per operation serves both families: `prefix` is "sosvo_sequence_" or
+    # "sosvo_rgbd_sequence_", `heads` the structs the entry point takes first (rig or cam, cfg).
     @staticmethod
-    def _host_i32(values):
-        n = len(values)
-        return (ctypes.c_int32 * max(n, 1))(*[int(x) for x in values]), n
+    def _host_ints(values, ctype=ctypes.c_int32):
+        """Host ints as a C array behind a void* (never empty: an empty list is no null pointer); seeds wrap to 64 bits."""
+        wrap = 2 ** 64 - 1 if ctype is ctypes.c_uint64 else -1   # (x & -1 == x)
+        return ctypes.cast((ctype * max(len(values), 1))(*[int(x) & wrap for x in values]), c_p)
 
-    def _track_seeds_args(self, ref_slots, cur_slots, seeds, workspace, results):
+    def _seq_call(self, name, heads, window, slots, *args):
+        self._call(getattr(self._lib, name), *[ctypes.cast(ctypes.pointer(h), c_p) for h in heads], int(window), int(slots), *args)
+
+    def _seq_workspace(self, prefix, cfg, window, slots):
+        return int(getattr(self._lib, prefix + "workspace")(ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots)))
+
+    def _seq_front_end(self, prefix, heads, window, slots, images, first_slot, slot_of_frame, consts, workspace):
+        """images: the tensors with one row per frame, consts: the model's; slot_of_frame None: ..._front_end at first_slot."""
+        n = int(images[0].shape[0])
+        if slot_of_frame is None:
+            name, where = "front_end", int(first_slot)
+        else:
+            if len(slot_of_frame) != n:
+                raise SosvoError("slot_of_frame: one slot per frame")
+            name, where = "front_end_slots", self._host_ints(slot_of_frame)
+        self._seq_call(prefix + name, heads, window, slots, *[_ptr(t) for t in images], n, where, *[_ptr(t) for t in consts],
+                       _ptr(workspace), int(workspace.numel()))
+
+    def _seq_track(self, prefix, heads, window, slots, ref_slots, cur_slots, seed, seeds, workspace, results):
+        """seeds None: ..._track with the scalar seed; else ..._track_seeds."""
         n = len(ref_slots)
-        if len(cur_slots) != n or len(seeds) != n:
+        if seeds is None and len(cur_slots) != n:
+            raise SosvoError("ref_slots and cur_slots must have the same length")
+        if seeds is not None and (len(cur_slots) != n or len(seeds) != n):
             raise SosvoError("ref_slots, cur_slots and seeds must have the same length")
         _check(workspace, torch.uint8, "workspace", ndim=1)
         _check(results, torch.float64, "results", (None, 16))
         if results.shape[0] < n:
             raise SosvoError("results holds fewer rows than slot pairs")
-        ref, cur = self._host_i32(ref_slots)[0], self._host_i32(cur_slots)[0]
-        sd = (ctypes.c_uint64 * max(n, 1))(*[int(x) & (2 ** 64 - 1) for x in seeds])
-        return ref, cur, sd, n
+        name, tail = ("track", (n, int(seed))) if seeds is None else ("track_seeds", (self._host_ints(seeds, ctypes.c_uint64), n))
+        self._seq_call(prefix + name, heads, window, slots, self._host_ints(ref_slots), self._host_ints(cur_slots), *tail,
+                       _ptr(workspace), int(workspace.numel()), _ptr(results))
+        return results
 
-    def sequence_front_end_slots(self, rig, cfg, window, slots, omni, slot_of_frame, unwrap_table, mask_bits, pattern, workspace):
-        """sequence_front_end with frame i's record written to store slot slot_of_frame[i] (host ints, one per frame of
-        omni, no slot twice); asynchronous."""
+    def _seq_copy(self, prefix, cfg, window, slots, src, dst, workspace, lists):
+        """lists False: ..._copy_slot of two ints; True: ..._copy_slots of two host sequences."""
+        if not lists:
+            args = ("copy_slot", int(src), int(dst))
+        elif len(src) != len(dst):
+            raise SosvoError("src_slots and dst_slots must have the same length")
+        else:
+            args = ("copy_slots", self._host_ints(src), self._host_ints(dst), len(src))
+        self._seq_call(prefix + args[0], (cfg,), window, slots, *args[1:], _ptr(workspace), int(workspace.numel()))
+
+    def _seq_counts(self, prefix, cfg, window, slots, first_slot, n, workspace):
+        out = (ctypes.c_int32 * max(int(n), 1))()
+        self._seq_call(prefix + "frame_counts", (cfg,), window, slots, int(first_slot), int(n), _ptr(workspace),
+                       int(workspace.numel()), ctypes.cast(out, c_p))
+        return [int(out[i]) for i in range(int(n))]
+
+    @staticmethod
+    def _check_omni_inputs(cfg, omni, unwrap_table, mask_bits, pattern, workspace):
         _check(omni, torch.uint8, "omni", (None, cfg.H, cfg.W, 3))
         _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cfg.cols, 2))
         _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cfg.cols))
         _check(pattern, torch.int8, "pattern", (512, 2))
         _check(workspace, torch.uint8, "workspace", ndim=1)
-        tab, n = self._host_i32(slot_of_frame)
-        if n != int(omni.shape[0]):
-            raise SosvoError("slot_of_frame: one slot per frame")
-        self._call(self._lib.sosvo_sequence_front_end_slots, ctypes.cast(ctypes.pointer(rig), c_p),
-                   ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), _ptr(omni), n, ctypes.cast(tab, c_p),
-                   _ptr(unwrap_table), _ptr(mask_bits), _ptr(pattern), _ptr(workspace), int(workspace.numel()))
+
+    @staticmethod
+    def _check_rgbd_inputs(cfg, bgr, depth, mask_bits, pattern, workspace):
+        _check(bgr, torch.uint8, "bgr", (None, cfg.rows, cfg.cols, 3))
+        _check(depth, torch.float32, "depth", (bgr.shape[0], cfg.rows, cfg.cols))
+        _check(mask_bits, torch.uint32, "mask_bits", (1, cfg.rows, cfg.cols))
+        _check(pattern, torch.int8, "pattern", (512, 2))
+        _check(workspace, torch.uint8, "workspace", ndim=1)
+
+    def sequence_workspace(self, cfg, window, slots):
+        return self._seq_workspace("sosvo_sequence_", cfg, window, slots)
+
+    def sequence_front_end(self, rig, cfg, window, slots, omni, first_slot, unwrap_table, mask_bits, pattern, workspace):
+        """omni [n,H,W,3] u8 (n <= window) -> store slots first_slot .. first_slot + n - 1 (asynchronous)."""
+        self._check_omni_inputs(cfg, omni, unwrap_table, mask_bits, pattern, workspace)
+        self._seq_front_end("sosvo_sequence_", (rig, cfg), window, slots, (omni,), first_slot, None,
+                            (unwrap_table, mask_bits, pattern), workspace)
+
+    def sequence_track(self, rig, cfg, window, slots, ref_slots, cur_slots, seed, workspace, results):
+        """ref_slots / cur_slots: host int sequences of equal length n <= cfg.n_pairs -> results[:n] [n,16] f64 (device,
+        asynchronous); pair i samples with seed + i."""
+        return self._seq_track("sosvo_sequence_", (rig, cfg), window, slots, ref_slots, cur_slots, seed, None, workspace, results)
+
+    def sequence_copy_slot(self, cfg, window, slots, src, dst, workspace):
+        self._seq_copy("sosvo_sequence_", cfg, window, slots, src, dst, workspace, False)
+
+    def sequence_frame_counts(self, cfg, window, slots, first_slot, n, workspace):
+        """-> list of n ints (StereoPanoramicFrame.num_valid_keypoints of the slots); synchronises the stream."""
+        return self._seq_counts("sosvo_sequence_", cfg, window, slots, first_slot, n, workspace)
+
+    def sequence_front_end_slots(self, rig, cfg, window, slots, omni, slot_of_frame, unwrap_table, mask_bits, pattern, workspace):
+        """sequence_front_end with frame i's record written to store slot slot_of_frame[i] (host ints, one per frame of
+        omni, no slot twice); asynchronous."""
+        self._check_omni_inputs(cfg, omni, unwrap_table, mask_bits, pattern, workspace)
+        self._seq_front_end("sosvo_sequence_", (rig, cfg), window, slots, (omni,), None, slot_of_frame,
+                            (unwrap_table, mask_bits, pattern), workspace)
 
     def sequence_track_seeds(self, rig, cfg, window, slots, ref_slots, cur_slots, seeds, workspace, results):
         """sequence_track with pair i sampling with seeds[i] (host ints) -> results[:n] (device, asynchronous)."""
-        ref, cur, sd, n = self._track_seeds_args(ref_slots, cur_slots, seeds, workspace, results)
-        self._call(self._lib.sosvo_sequence_track_seeds, ctypes.cast(ctypes.pointer(rig), c_p), ctypes.cast(ctypes.pointer(cfg), c_p),
-                   int(window), int(slots), ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), ctypes.cast(sd, c_p), n, _ptr(workspace),
-                   int(workspace.numel()), _ptr(results))
-        return results
+        return self._seq_track("sosvo_sequence_", (rig, cfg), window, slots, ref_slots, cur_slots, None, seeds, workspace, results)
 
     def sequence_copy_slots(self, cfg, window, slots, src_slots, dst_slots, workspace):
         """Store slots src_slots[i] -> dst_slots[i], all pairs in one launch (no slot written twice or read and written)."""
-        (src, n), (dst, nd) = self._host_i32(src_slots), self._host_i32(dst_slots)
-        if n != nd:
-            raise SosvoError("src_slots and dst_slots must have the same length")
-        self._call(self._lib.sosvo_sequence_copy_slots, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   ctypes.cast(src, c_p), ctypes.cast(dst, c_p), n, _ptr(workspace), int(workspace.numel()))
+        self._seq_copy("sosvo_sequence_", cfg, window, slots, src_slots, dst_slots, workspace, True)
 
-    def rgbd_sequence_front_end_slots(self, cam, cfg, window, slots, bgr, depth, slot_of_frame, mask_bits, pattern, workspace):
-        _check(bgr, torch.uint8, "bgr", (None, cfg.rows, cfg.cols, 3))
-        _check(depth, torch.float32, "depth", (bgr.shape[0], cfg.rows, cfg.cols))
-        _check(mask_bits, torch.uint32, "mask_bits", (1, cfg.rows, cfg.cols))
-        _check(pattern, torch.int8, "pattern", (512, 2))
-        _check(workspace, torch.uint8, "workspace", ndim=1)
-        tab, n = self._host_i32(slot_of_frame)
-        if n != int(bgr.shape[0]):
-            raise SosvoError("slot_of_frame: one slot per frame")
-        self._call(self._lib.sosvo_rgbd_sequence_front_end_slots, ctypes.cast(ctypes.pointer(cam), c_p),
-                   ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), _ptr(bgr), _ptr(depth), n, ctypes.cast(tab, c_p),
-                   _ptr(mask_bits), _ptr(pattern), _ptr(workspace), int(workspace.numel()))
-
-    def rgbd_sequence_track_seeds(self, cfg, window, slots, ref_slots, cur_slots, seeds, workspace, results):
-        ref, cur, sd, n = self._track_seeds_args(ref_slots, cur_slots, seeds, workspace, results)
-        self._call(self._lib.sosvo_rgbd_sequence_track_seeds, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), ctypes.cast(sd, c_p), n, _ptr(workspace), int(workspace.numel()),
-                   _ptr(results))
-        return results
-
-    def rgbd_sequence_copy_slots(self, cfg, window, slots, src_slots, dst_slots, workspace):
-        (src, n), (dst, nd) = self._host_i32(src_slots), self._host_i32(dst_slots)
-        if n != nd:
-            raise SosvoError("src_slots and dst_slots must have the same length")
-        self._call(self._lib.sosvo_rgbd_sequence_copy_slots, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   ctypes.cast(src, c_p), ctypes.cast(dst, c_p), n, _ptr(workspace), int(workspace.numel()))
-
-    # ---- RGB-D sequence mode ------------------------------------------------------------------------
     def rgbd_sequence_workspace(self, cfg, window, slots):
-        return int(self._lib.sosvo_rgbd_sequence_workspace(ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots)))
+        return self._seq_workspace("sosvo_rgbd_sequence_", cfg, window, slots)
 
     def rgbd_sequence_front_end(self, cam, cfg, window, slots, bgr, depth, first_slot, mask_bits, pattern, workspace):
-        _check(bgr, torch.uint8, "bgr", (None, cfg.rows, cfg.cols, 3))
-        _check(depth, torch.float32, "depth", (bgr.shape[0], cfg.rows, cfg.cols))
-        _check(mask_bits, torch.uint32, "mask_bits", (1, cfg.rows, cfg.cols))
-        _check(pattern, torch.int8, "pattern", (512, 2))
-        _check(workspace, torch.uint8, "workspace", ndim=1)
-        self._call(self._lib.sosvo_rgbd_sequence_front_end, ctypes.cast(ctypes.pointer(cam), c_p), ctypes.cast(ctypes.pointer(cfg), c_p),
-                   int(window), int(slots), _ptr(bgr), _ptr(depth), int(bgr.shape[0]), int(first_slot), _ptr(mask_bits),
-                   _ptr(pattern), _ptr(workspace), int(workspace.numel()))
+        self._check_rgbd_inputs(cfg, bgr, depth, mask_bits, pattern, workspace)
+        self._seq_front_end("sosvo_rgbd_sequence_", (cam, cfg), window, slots, (bgr, depth), first_slot, None,
+                            (mask_bits, pattern), workspace)
 
     def rgbd_sequence_track(self, cfg, window, slots, ref_slots, cur_slots, seed, workspace, results):
-        n = len(ref_slots)
-        if len(cur_slots) != n:
-            raise SosvoError("ref_slots and cur_slots must have the same length")
-        _check(workspace, torch.uint8, "workspace", ndim=1)
-        _check(results, torch.float64, "results", (None, 16))
-        if results.shape[0] < n:
-            raise SosvoError("results holds fewer rows than slot pairs")
-        ref = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in ref_slots])
-        cur = (ctypes.c_int32 * max(n, 1))(*[int(x) for x in cur_slots])
-        self._call(self._lib.sosvo_rgbd_sequence_track, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   ctypes.cast(ref, c_p), ctypes.cast(cur, c_p), n, int(seed), _ptr(workspace), int(workspace.numel()), _ptr(results))
-        return results
+        return self._seq_track("sosvo_rgbd_sequence_", (cfg,), window, slots, ref_slots, cur_slots, seed, None, workspace, results)
 
     def rgbd_sequence_copy_slot(self, cfg, window, slots, src, dst, workspace):
-        self._call(self._lib.sosvo_rgbd_sequence_copy_slot, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots), int(src),
-                   int(dst), _ptr(workspace), int(workspace.numel()))
+        self._seq_copy("sosvo_rgbd_sequence_", cfg, window, slots, src, dst, workspace, False)
 
     def rgbd_sequence_frame_counts(self, cfg, window, slots, first_slot, n, workspace):
-        out = (ctypes.c_int32 * max(int(n), 1))()
-        self._call(self._lib.sosvo_rgbd_sequence_frame_counts, ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots),
-                   int(first_slot), int(n), _ptr(workspace), int(workspace.numel()), ctypes.cast(out, c_p))
-        return [int(out[i]) for i in range(int(n))]
+        return self._seq_counts("sosvo_rgbd_sequence_", cfg, window, slots, first_slot, n, workspace)
+
+    def rgbd_sequence_front_end_slots(self, cam, cfg, window, slots, bgr, depth, slot_of_frame, mask_bits, pattern, workspace):
+        self._check_rgbd_inputs(cfg, bgr, depth, mask_bits, pattern, workspace)
+        self._seq_front_end("sosvo_rgbd_sequence_", (cam, cfg), window, slots, (bgr, depth), None, slot_of_frame,
+                            (mask_bits, pattern), workspace)
+
+    def rgbd_sequence_track_seeds(self, cfg, window, slots, ref_slots, cur_slots, seeds, workspace, results):
+        return self._seq_track("sosvo_rgbd_sequence_", (cfg,), window, slots, ref_slots, cur_slots, None, seeds, workspace, results)
+
+    def rgbd_sequence_copy_slots(self, cfg, window, slots, src_slots, dst_slots, workspace):
+        self._seq_copy("sosvo_rgbd_sequence_", cfg, window, slots, src_slots, dst_slots, workspace, True)
 
     def rgbd_pair_batch_workspace(self, cfg):
         return int(self._lib.sosvo_rgbd_pair_batch_workspace(ctypes.cast(ctypes.pointer(cfg), c_p)))

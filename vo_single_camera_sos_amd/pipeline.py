@@ -410,13 +410,142 @@ def _stage_rows(dst_np, images):
     list(_STAGE_POOL.map(lambda i: np.copyto(dst_np[i], images[i]), range(len(images))))
 
 
+class _SequenceFamily(object):
+    """What the sequence engines of one family (omnistereo / RGB-D) keep for one frame store, and their device calls: `cfg`,
+    the model constants, the workspace of `slots` slots, two pinned and two device input buffers of `frames` frames (a frame
+    is a row of every tensor of a buffer: one tensor for omni images, two for (bgr, depth)) and, on request, the buffer a
+    ragged round of a multi-sequence engine is gathered into.  `window` of the calls is `frames`.  A subclass sets up cfg
+    and the constants and names its calls: `prefix` of the Context methods, `heads` (what the front-end calls take before
+    cfg) and `track_heads` (the tracking calls), `consts()` (the model tensors of a front-end call), `shared` (the
+    attributes an engine shows as its own)."""
+
+    def _allocate(self, ctx, frames, slots, gather, frame_shapes):
+        self.ctx, self.frames, self.slots = ctx, int(frames), int(slots)
+        nbytes = self._call("workspace", ())
+        if nbytes <= 0:   # (gather: the store of a multi-sequence engine)
+            raise ValueError("bad sequence configuration" + (
+                " (lanes * window: at most 8192 frames, lanes * (2 window + 1) <= 65535)" if gather else ""))
+        dev = ctx.device
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        new = lambda **kw: tuple(torch.zeros((self.frames,) + shape, dtype=dt, **kw) for shape, dt in frame_shapes)  # noqa: E731
+        self._dev = [new(device=dev) for _ in range(2)]
+        self._round = new(device=dev) if gather else None
+        self._host = [tuple(t.pin_memory() for t in new()) for _ in range(2)]
+        self._host_np = [tuple(t.numpy() for t in h) for h in self._host]
+
+    def stage(self, buf, row, images):
+        """images -> rows row .. of pinned buffer `buf`."""
+        for dst, plane in zip(self._host_np[buf], self._planes(images)):
+            _stage_rows(dst[row:row + len(plane)], plane)
+
+    def upload(self, buf, row, n):
+        for d, h in zip(self._dev[buf], self._host[buf]):
+            d[row:row + n].copy_(h[row:row + n], non_blocking=True)
+
+    def gather(self, buf, row, n, pos):
+        for g, d in zip(self._round, self._dev[buf]):
+            g[pos:pos + n].copy_(d[row:row + n], non_blocking=True)
+
+    def rows(self, buf, row, n):
+        """n frames of device buffer `buf` from `row` on (buf None: of the gathered round), as the front-end calls take them."""
+        return tuple(t[row:row + n] for t in (self._round if buf is None else self._dev[buf]))
+
+    def _call(self, name, heads, *args):
+        return getattr(self.ctx, self.prefix + name)(*heads, self.cfg, self.frames, self.slots, *args)
+
+    def front_end(self, rows, first_slot):
+        self._call("front_end", self.heads, *rows, first_slot, *self.consts(), self.workspace)
+
+    def front_end_slots(self, rows, table):
+        self._call("front_end_slots", self.heads, *rows, table, *self.consts(), self.workspace)
+
+    def track(self, ref_slots, cur_slots, seed, out):
+        self._call("track", self.track_heads, ref_slots, cur_slots, seed, self.workspace, out)
+
+    def track_seeds(self, ref_slots, cur_slots, seeds, out):
+        self._call("track_seeds", self.track_heads, ref_slots, cur_slots, seeds, self.workspace, out)
+
+    def counts(self, first, n):
+        return self._call("frame_counts", (), first, n, self.workspace)
+
+    def copy(self, src, dst):
+        self._call("copy_slot", (), src, dst, self.workspace)
+
+    def copy_slots(self, src, dst):
+        self._call("copy_slots", (), src, dst, self.workspace)
+
+
+class _OmniFamily(_SequenceFamily):
+    prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
+
+    def __init__(self, ctx, model, rig, frames, slots, gather, num_of_features, kp_cap, frame_cap, median_win_size, quality,
+                 min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method):
+        assert isinstance(ctx, Context)
+        self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
+        self.heads = self.track_heads = (self.rig,)
+        self.cfg = batch_cfg(model, frames, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                             thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
+        self.method = str(detection_method).upper()
+        if str(ransac_solver).upper() not in ("P3P", "GP3P"):
+            raise ValueError("ransac_solver: P3P or GP3P")
+        if getattr(model, "unwrap_table", None) is None:  # once per model
+            model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        self._allocate(ctx, frames, slots, gather, [((model.H, model.W, 3), torch.uint8)])
+
+    def consts(self):
+        m = self.model
+        return m.unwrap_table, m.mask_bits, m.pattern
+
+    @staticmethod
+    def _planes(images):
+        return (images,)
+
+
+class _RGBDFamily(_SequenceFamily):
+    prefix, track_heads = "rgbd_sequence_", ()
+    shared = ("ctx", "cfg", "method", "workspace", "cam_cfg", "cam", "mask_bits", "pattern")
+
+    def __init__(self, ctx, cam, _rig, frames, slots, gather, image_shape, num_of_features, kp_cap, frame_cap, median_win_size,
+                 quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask, pose_est_algorithm, detection_method):
+        from . import orb_pattern
+        assert isinstance(ctx, Context)
+        self.cam_cfg, self.cam = cam, cam.as_struct()
+        self.heads = (self.cam,)
+        self.cfg = c = rgbd_batch_cfg(cam, frames, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
+                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
+        self.method = str(detection_method).upper()
+        rows, cols = c.rows, c.cols
+        mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
+        self.mask_bits = torch.from_numpy(mb).to(ctx.device)
+        self.pattern = torch.from_numpy(orb_pattern.orb_pattern()).to(ctx.device)
+        self._allocate(ctx, frames, slots, gather, [((rows, cols, 3), torch.uint8), ((rows, cols), torch.float32)])
+
+    def consts(self):
+        return self.mask_bits, self.pattern
+
+    @staticmethod
+    def _planes(images):   # (bgr, depth) tuples
+        return [im[0] for im in images], [np.asarray(im[1], dtype=np.float32) for im in images]
+
+
+def _adopt_family(engine, fam, **records):
+    """The family's store is the engine's: what callers read on an engine (cfg, workspace, model constants, ...), and the
+    engine's buffers of tracking records (name = rows)."""
+    engine.fam = fam
+    for name in fam.shared:
+        setattr(engine, name, getattr(fam, name))
+    for name, rows in records.items():
+        setattr(engine, name, torch.zeros((rows, 16), dtype=torch.float64, device=fam.ctx.device))
+
+
 class _SequenceBase(object):
     """Window / slot bookkeeping shared by the sequence engines (include/sosvo.h "Sequence mode"): two window halves
     [0, W) and [W, 2W) used alternately (the last frame of the previous window stays readable) and slot 2W for the current
     keyframe.  A tracking record is a pure function of (reference frame, current frame, seed): push_window() tracks every
     frame of the window against its PREDECESSOR in one batched call; the VO loop takes that record where the predecessor
     was the reference and asks for one serial track() call where it was not.  Either way the records are those of the
-    serial loop, whatever the window size.  Subclasses provide _stage / _front_end / _track / _counts / _copy."""
+    serial loop, whatever the window size.  The hooks _stage_host / _upload / _front_end / _track / _counts / _copy go to the
+    engine's family (self.fam, see _adopt).  The frames of a sequence are rows 0 .. of the family's buffers."""
 
     early_upload = True   # run_VO's staging thread starts a window's host-to-device copy itself (upload_staged); False: A/B
     enqueue_ahead = True  # run_VO enqueues window k + 1 before it works through window k's records (enqueue_staged); False: A/B
@@ -426,6 +555,27 @@ class _SequenceBase(object):
         self.W = max(1, int(window))
         self.slots, self.key_slot = 2 * self.W + 1, self._slot0 + 2 * self.W
         self.reset()
+
+    def _adopt(self, fam):
+        _adopt_family(self, fam, spec=self.W, spec2=self.W, one=1)
+
+    def _stage_host(self, images, buf):
+        self.fam.stage(buf, 0, images)
+
+    def _upload(self, buf, n):
+        self.fam.upload(buf, 0, n)
+
+    def _front_end(self, n, first, buf):
+        self.fam.front_end(self.fam.rows(buf, 0, n), first)
+
+    def _track(self, ref_slots, cur_slots, seed, out):
+        self.fam.track(ref_slots, cur_slots, seed, out)
+
+    def _counts(self, first, n):
+        return self.fam.counts(first, n)
+
+    def _copy(self, src, dst):
+        self.fam.copy(src, dst)
 
     def reset(self):
         """Forget the sequence (an engine is reused from run to run: its buffers -- pinned host memory among them -- are the
@@ -502,10 +652,7 @@ class _SequenceBase(object):
         before its half is refilled (here, as ever), serial track() calls read the keyframe slot and a slot of window k
         only, and everything is ordered on one stream.  One window may be pending."""
         import time
-        if n <= 0 or n > self.W:
-            raise ValueError("1 .. window frames per push")
-        if self._pending is not None:
-            raise RuntimeError("collect() the pending window first")
+        self._check_push(n)
         t1 = time.perf_counter()
         buf = int(buf)
         if self._win_events is None:
@@ -529,6 +676,12 @@ class _SequenceBase(object):
         self._win_events[1].record(self.ctx.stream)
         self._commit_window(w)
         self.stage_s["enqueue"] += time.perf_counter() - t1
+
+    def _check_push(self, n):
+        if n <= 0 or n > self.W:
+            raise ValueError("1 .. window frames per push")
+        if self._pending is not None:
+            raise RuntimeError("collect() the pending window first")
 
     def _plan_window(self, n):
         """The bookkeeping of the next window of n frames, nothing on the device: the half it goes to, its slots, the slot
@@ -628,47 +781,9 @@ class SequenceEngine(_SequenceBase):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch."""
-        assert isinstance(ctx, Context)
-        self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self._init_windows(window)
-        self.cfg = c = batch_cfg(model, self.W, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                                 thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
-        self.method = str(detection_method).upper()
-        if str(ransac_solver).upper() not in ("P3P", "GP3P"):
-            raise ValueError("ransac_solver: P3P or GP3P")
-        if getattr(model, "unwrap_table", None) is None:  # once per model
-            model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
-        nbytes = ctx.sequence_workspace(c, self.W, self.slots)
-        if nbytes <= 0:
-            raise ValueError("bad sequence configuration")
-        dev = ctx.device
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self._omni = [torch.zeros((self.W, model.H, model.W, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self._host = [torch.zeros((self.W, model.H, model.W, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._host_np = [h.numpy() for h in self._host]
-        self.spec = torch.zeros((self.W, 16), dtype=torch.float64, device=dev)
-        self.spec2 = torch.zeros((self.W, 16), dtype=torch.float64, device=dev)
-        self.one = torch.zeros((1, 16), dtype=torch.float64, device=dev)
-
-    def _stage_host(self, images, buf):
-        _stage_rows(self._host_np[buf], images)
-
-    def _upload(self, buf, n):
-        self._omni[buf][:n].copy_(self._host[buf][:n], non_blocking=True)
-
-    def _front_end(self, n, first, buf):
-        m = self.model
-        self.ctx.sequence_front_end(self.rig, self.cfg, self.W, self.slots, self._omni[buf][:n], first, m.unwrap_table,
-                                    m.mask_bits, m.pattern, self.workspace)
-
-    def _track(self, ref_slots, cur_slots, seed, out):
-        self.ctx.sequence_track(self.rig, self.cfg, self.W, self.slots, ref_slots, cur_slots, seed, self.workspace, out)
-
-    def _counts(self, first, n):
-        return self.ctx.sequence_frame_counts(self.cfg, self.W, self.slots, first, n, self.workspace)
-
-    def _copy(self, src, dst):
-        self.ctx.sequence_copy_slot(self.cfg, self.W, self.slots, src, dst, self.workspace)
+        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, num_of_features, kp_cap, frame_cap, median_win_size,
+                                quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -928,51 +1043,10 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
-        from . import orb_pattern
-        assert isinstance(ctx, Context)
-        self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self._init_windows(window)
-        self.cfg = c = rgbd_batch_cfg(cam, self.W, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
-        self.method = str(detection_method).upper()
-        rows, cols = c.rows, c.cols
-        dev = ctx.device
-        mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
-        self.mask_bits = torch.from_numpy(mb).to(dev)
-        self.pattern = torch.from_numpy(orb_pattern.orb_pattern()).to(dev)
-        nbytes = ctx.rgbd_sequence_workspace(c, self.W, self.slots)
-        if nbytes <= 0:
-            raise ValueError("bad sequence configuration")
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self._bgr = [torch.zeros((self.W, rows, cols, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self._depth = [torch.zeros((self.W, rows, cols), dtype=torch.float32, device=dev) for _ in range(2)]
-        self._host_bgr = [torch.zeros((self.W, rows, cols, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._host_depth = [torch.zeros((self.W, rows, cols), dtype=torch.float32).pin_memory() for _ in range(2)]
-        self._np_bgr, self._np_depth = [h.numpy() for h in self._host_bgr], [h.numpy() for h in self._host_depth]
-        self.spec = torch.zeros((self.W, 16), dtype=torch.float64, device=dev)
-        self.spec2 = torch.zeros((self.W, 16), dtype=torch.float64, device=dev)
-        self.one = torch.zeros((1, 16), dtype=torch.float64, device=dev)
-
-    def _stage_host(self, images, buf):
-        _stage_rows(self._np_bgr[buf], [im[0] for im in images])
-        _stage_rows(self._np_depth[buf], [np.asarray(im[1], dtype=np.float32) for im in images])
-
-    def _upload(self, buf, n):
-        self._bgr[buf][:n].copy_(self._host_bgr[buf][:n], non_blocking=True)
-        self._depth[buf][:n].copy_(self._host_depth[buf][:n], non_blocking=True)
-
-    def _front_end(self, n, first, buf):
-        self.ctx.rgbd_sequence_front_end(self.cam, self.cfg, self.W, self.slots, self._bgr[buf][:n], self._depth[buf][:n], first,
-                                         self.mask_bits, self.pattern, self.workspace)
-
-    def _track(self, ref_slots, cur_slots, seed, out):
-        self.ctx.rgbd_sequence_track(self.cfg, self.W, self.slots, ref_slots, cur_slots, seed, self.workspace, out)
-
-    def _counts(self, first, n):
-        return self.ctx.rgbd_sequence_frame_counts(self.cfg, self.W, self.slots, first, n, self.workspace)
-
-    def _copy(self, src, dst):
-        self.ctx.rgbd_sequence_copy_slot(self.cfg, self.W, self.slots, src, dst, self.workspace)
+        self._adopt(_RGBDFamily(ctx, cam, None, self.W, self.slots, False, image_shape, num_of_features, kp_cap, frame_cap,
+                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
+                                pose_est_algorithm, detection_method))
 
 
 # ---- several sequences ("lanes") through one engine ----------------------------------------------------------------------
@@ -1016,10 +1090,7 @@ class _Lane(_SequenceBase):
         """Files the window (n frames staged in pinned buffer `buf`) with the engine; nothing reaches the device before every
         live lane waits for the engine."""
         import time
-        if n <= 0 or n > self.W:
-            raise ValueError("1 .. window frames per push")
-        if self._pending is not None:
-            raise RuntimeError("collect() the pending window first")
+        self._check_push(n)
         t1 = time.perf_counter()
         with self.engine._cv:
             w = self._plan_window(n)
@@ -1076,7 +1147,8 @@ class _MultiSequenceBase(object):
     and ONE read-back, then wakes the lanes.  A frame record is a function of its image, a tracking record of (reference
     record, current record, seed): which call computes a record never changes it, so the lanes' results are those of S
     single-sequence engines whatever the grouping.  begin(s) / end(s) bracket a lane's run (a lane that is not live is not
-    waited for).  Subclasses provide the buffers and the five device calls."""
+    waited for).  The hooks _stage_lane / _upload_lane / _gather_lane / _front_end_round / _track_seeds / _counts_all /
+    _copy_slots go to the engine's family (self.fam, see _adopt); lane s owns rows s W .. of the family's buffers."""
 
     def _init_lanes(self, lanes, window):
         self.S, self.W = max(1, int(lanes)), max(1, int(window))
@@ -1089,6 +1161,32 @@ class _MultiSequenceBase(object):
 
     def _make_lanes(self):
         self.lanes = [_Lane(self, s) for s in range(self.S)]
+
+    def _adopt(self, fam):
+        _adopt_family(self, fam, spec=self.window, spec2=self.window, serial=self.S)
+        self._make_lanes()
+
+    def _stage_lane(self, s, images, buf):
+        self.fam.stage(buf, s * self.W, images)
+
+    def _upload_lane(self, s, buf, n):
+        self.fam.upload(buf, s * self.W, n)
+
+    def _gather_lane(self, s, buf, n, pos):
+        self.fam.gather(buf, s * self.W, n, pos)
+
+    def _front_end_round(self, requests, slot_of_frame):
+        buf, row, n = self._input_rows(requests)
+        self.fam.front_end_slots(self.fam.rows(buf, row, n), slot_of_frame)
+
+    def _track_seeds(self, ref_slots, cur_slots, seeds, out):
+        self.fam.track_seeds(ref_slots, cur_slots, seeds, out)
+
+    def _counts_all(self):
+        return self.fam.counts(0, self.slots)
+
+    def _copy_slots(self, src, dst):
+        self.fam.copy_slots(src, dst)
 
     def reset_counters(self):
         """front_end_launches / speculative_track_launches / serial_track_launches / copy_launches: device calls made;
@@ -1275,57 +1373,10 @@ class MultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, model, rig, lanes=2, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT"):
-        assert isinstance(ctx, Context)
-        self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self._init_lanes(lanes, window)
-        self.cfg = c = batch_cfg(model, self.window, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
-                                 edge, thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
-        self.method = str(detection_method).upper()
-        if str(ransac_solver).upper() not in ("P3P", "GP3P"):
-            raise ValueError("ransac_solver: P3P or GP3P")
-        if getattr(model, "unwrap_table", None) is None:  # once per model
-            model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
-        nbytes = ctx.sequence_workspace(c, self.window, self.slots)
-        if nbytes <= 0:
-            raise ValueError("bad sequence configuration (lanes * window: at most 8192 frames, lanes * (2 window + 1) <= 65535)")
-        dev, F = ctx.device, self.window
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        shape = (F, model.H, model.W, 3)
-        self._omni = [torch.zeros(shape, dtype=torch.uint8, device=dev) for _ in range(2)]    # lane s: rows s W ..
-        self._round = torch.zeros(shape, dtype=torch.uint8, device=dev)                       # a ragged round, gathered
-        self._host = [torch.zeros(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._host_np = [h.numpy() for h in self._host]
-        self.spec = torch.zeros((F, 16), dtype=torch.float64, device=dev)
-        self.spec2 = torch.zeros((F, 16), dtype=torch.float64, device=dev)
-        self.serial = torch.zeros((self.S, 16), dtype=torch.float64, device=dev)
-        self._make_lanes()
-
-    def _stage_lane(self, s, images, buf):
-        _stage_rows(self._host_np[buf][s * self.W:(s + 1) * self.W], images)
-
-    def _upload_lane(self, s, buf, n):
-        r = s * self.W
-        self._omni[buf][r:r + n].copy_(self._host[buf][r:r + n], non_blocking=True)
-
-    def _gather_lane(self, s, buf, n, pos):
-        r = s * self.W
-        self._round[pos:pos + n].copy_(self._omni[buf][r:r + n], non_blocking=True)
-
-    def _front_end_round(self, requests, slot_of_frame):
-        buf, r, n = self._input_rows(requests)
-        omni = self._round[:n] if buf is None else self._omni[buf][r:r + n]
-        m = self.model
-        self.ctx.sequence_front_end_slots(self.rig, self.cfg, self.window, self.slots, omni, slot_of_frame, m.unwrap_table,
-                                          m.mask_bits, m.pattern, self.workspace)
-
-    def _track_seeds(self, ref_slots, cur_slots, seeds, out):
-        self.ctx.sequence_track_seeds(self.rig, self.cfg, self.window, self.slots, ref_slots, cur_slots, seeds, self.workspace, out)
-
-    def _counts_all(self):
-        return self.ctx.sequence_frame_counts(self.cfg, self.window, self.slots, 0, self.slots, self.workspace)
-
-    def _copy_slots(self, src, dst):
-        self.ctx.sequence_copy_slots(self.cfg, self.window, self.slots, src, dst, self.workspace)
+        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, num_of_features, kp_cap, frame_cap,
+                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver,
+                                detection_method))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
@@ -1335,61 +1386,7 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
-        from . import orb_pattern
-        assert isinstance(ctx, Context)
-        self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self._init_lanes(lanes, window)
-        self.cfg = c = rgbd_batch_cfg(cam, self.window, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
-        self.method = str(detection_method).upper()
-        rows, cols = c.rows, c.cols
-        dev, F = ctx.device, self.window
-        mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
-        self.mask_bits = torch.from_numpy(mb).to(dev)
-        self.pattern = torch.from_numpy(orb_pattern.orb_pattern()).to(dev)
-        nbytes = ctx.rgbd_sequence_workspace(c, self.window, self.slots)
-        if nbytes <= 0:
-            raise ValueError("bad sequence configuration (lanes * window: at most 8192 frames, lanes * (2 window + 1) <= 65535)")
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        self._bgr = [torch.zeros((F, rows, cols, 3), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self._depth = [torch.zeros((F, rows, cols), dtype=torch.float32, device=dev) for _ in range(2)]
-        self._round_bgr = torch.zeros((F, rows, cols, 3), dtype=torch.uint8, device=dev)
-        self._round_depth = torch.zeros((F, rows, cols), dtype=torch.float32, device=dev)
-        self._host_bgr = [torch.zeros((F, rows, cols, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._host_depth = [torch.zeros((F, rows, cols), dtype=torch.float32).pin_memory() for _ in range(2)]
-        self._np_bgr, self._np_depth = [h.numpy() for h in self._host_bgr], [h.numpy() for h in self._host_depth]
-        self.spec = torch.zeros((F, 16), dtype=torch.float64, device=dev)
-        self.spec2 = torch.zeros((F, 16), dtype=torch.float64, device=dev)
-        self.serial = torch.zeros((self.S, 16), dtype=torch.float64, device=dev)
-        self._make_lanes()
-
-    def _stage_lane(self, s, images, buf):
-        r = slice(s * self.W, (s + 1) * self.W)
-        _stage_rows(self._np_bgr[buf][r], [im[0] for im in images])
-        _stage_rows(self._np_depth[buf][r], [np.asarray(im[1], dtype=np.float32) for im in images])
-
-    def _upload_lane(self, s, buf, n):
-        r = s * self.W
-        self._bgr[buf][r:r + n].copy_(self._host_bgr[buf][r:r + n], non_blocking=True)
-        self._depth[buf][r:r + n].copy_(self._host_depth[buf][r:r + n], non_blocking=True)
-
-    def _gather_lane(self, s, buf, n, pos):
-        r = s * self.W
-        self._round_bgr[pos:pos + n].copy_(self._bgr[buf][r:r + n], non_blocking=True)
-        self._round_depth[pos:pos + n].copy_(self._depth[buf][r:r + n], non_blocking=True)
-
-    def _front_end_round(self, requests, slot_of_frame):
-        buf, r, n = self._input_rows(requests)
-        bgr, depth = (self._round_bgr[:n], self._round_depth[:n]) if buf is None else \
-            (self._bgr[buf][r:r + n], self._depth[buf][r:r + n])
-        self.ctx.rgbd_sequence_front_end_slots(self.cam, self.cfg, self.window, self.slots, bgr, depth, slot_of_frame,
-                                               self.mask_bits, self.pattern, self.workspace)
-
-    def _track_seeds(self, ref_slots, cur_slots, seeds, out):
-        self.ctx.rgbd_sequence_track_seeds(self.cfg, self.window, self.slots, ref_slots, cur_slots, seeds, self.workspace, out)
-
-    def _counts_all(self):
-        return self.ctx.rgbd_sequence_frame_counts(self.cfg, self.window, self.slots, 0, self.slots, self.workspace)
-
-    def _copy_slots(self, src, dst):
-        self.ctx.rgbd_sequence_copy_slots(self.cfg, self.window, self.slots, src, dst, self.workspace)
+        self._adopt(_RGBDFamily(ctx, cam, None, self.window, self.slots, True, image_shape, num_of_features, kp_cap, frame_cap,
+                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
+                                pose_est_algorithm, detection_method))
