@@ -41,6 +41,8 @@ def main_rgbd_vo(argv=None):
                              "mirror path).  The pose file does not depend on the window size.")
     parser.add_argument("--detection_method", default="GFT", choices=("GFT", "ORB", "FAST", "AGAST"), type=str.upper,
                         help="keypoint detector of the tracker and its frames (GFT: the reference's default)")
+    parser.add_argument("--cross_check", action="store_true",
+                        help="mutual matches only (cv2.BFMatcher's crossCheck) in the frame-to-frame matcher; default: off")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -78,7 +80,8 @@ def main_rgbd_vo(argv=None):
         out = driver_VO_many(camera_model=cam, scenes=scenes, visualize_VO=args.visualize_VO, step_for_scene_images=args.step,
                              first_image_index=args.first_image_index, last_image_index=args.last_image_index,
                              frame_window=None if args.frame_window < 0 else args.frame_window,
-                             detection_method=args.detection_method, lanes=None if args.lanes < 0 else args.lanes)
+                             detection_method=args.detection_method, cross_check=True if args.cross_check else None,
+                             lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
     out = driver_VO(camera_model=cam, scene_path=scene_path_rgbd, scene_path_vo_results=results,
@@ -88,7 +91,7 @@ def main_rgbd_vo(argv=None):
                     first_image_index=args.first_image_index, last_image_index=args.last_image_index,
                     thread_name="%s-%s" % (scene_name, "RGB-D"),
                     frame_window=None if args.frame_window < 0 else args.frame_window,
-                    detection_method=args.detection_method)
+                    detection_method=args.detection_method, cross_check=True if args.cross_check else None)
     print("GOODBYE!")
     return out
 

@@ -42,6 +42,9 @@ def main_sos_vo(argv=None):
                              "mirror path).  The pose file does not depend on the window size.")
     parser.add_argument("--detection_method", default="GFT", choices=("GFT", "ORB", "FAST", "AGAST"), type=str.upper,
                         help="keypoint detector of the tracker and its frames (GFT: the reference's default)")
+    parser.add_argument("--cross_check", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
+                        help="mutual matches only (cv2.BFMatcher's crossCheck): in both matchers when given without a value, "
+                             "or in the static-stereo / the frame-to-frame matcher alone; default: off")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -61,11 +64,12 @@ def main_sos_vo(argv=None):
                            depth_filename_template=None, num_scene_images=num_scene_images,
                            thread_name="%s-%s" % (scene_name, "SOS")))
     gums_calibrated = load_gums_json(gums_file)
+    cross_check = None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check)
     if len(scenes) > 1:
         out = driver_VO_many(camera_model=gums_calibrated, scenes=scenes, visualize_VO=args.visualize_VO,
                              step_for_scene_images=args.step, first_image_index=args.first_image_index,
                              last_image_index=args.last_image_index, frame_window=None if args.frame_window < 0 else args.frame_window,
-                             detection_method=args.detection_method, lanes=None if args.lanes < 0 else args.lanes)
+                             detection_method=args.detection_method, cross_check=cross_check, lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
     out = driver_VO(camera_model=gums_calibrated, scene_path=scene_path_omni, scene_path_vo_results=results,
@@ -74,7 +78,7 @@ def main_sos_vo(argv=None):
                     step_for_scene_images=args.step, first_image_index=args.first_image_index,
                     last_image_index=args.last_image_index, thread_name="%s-%s" % (scene_name, "SOS"),
                     frame_window=None if args.frame_window < 0 else args.frame_window,
-                    detection_method=args.detection_method)
+                    detection_method=args.detection_method, cross_check=cross_check)
     print("GOODBYE!")
     return out
 

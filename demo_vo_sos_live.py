@@ -34,6 +34,9 @@ def main_sos_vo_live(argv=None, frame_source=None):
     parser.add_argument("--use_multithreads_for_VO", default=True, type="bool")
     parser.add_argument("--frame_window", default=-1, type=int,
                         help="frames per batched front-end pass (-1 = 1 for a live source; 0 = the per-frame mirror path)")
+    parser.add_argument("--cross_check", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
+                        help="mutual matches only (cv2.BFMatcher's crossCheck): in both matchers when given without a value, "
+                             "or in the static-stereo / the frame-to-frame matcher alone; default: off")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -50,7 +53,8 @@ def main_sos_vo_live(argv=None, frame_source=None):
     gums_calibrated = load_gums_json(osp.realpath(osp.expanduser(args.calibrated_gums_file)))
     out = driver_VO_live(gums_calibrated, results, cam_working_thread, visualize_VO=args.visualize_VO,
                          use_multithreads_for_VO=args.use_multithreads_for_VO, thread_name="LIVE-SOS",
-                         frame_window=None if args.frame_window < 0 else args.frame_window)
+                         frame_window=None if args.frame_window < 0 else args.frame_window,
+                         cross_check=None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check))
     print("GOODBYE!")
     return out
 

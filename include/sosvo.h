@@ -304,6 +304,21 @@ int32_t sosvo_match_radius(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t*
                            int32_t q_stride, int32_t t_stride, int32_t max_distance, int32_t cap,
                            uint32_t* keys, int32_t* counts);
 
+/* Mutual-consistency filter: cv2.BFMatcher(normType=cv2.NORM_HAMMING, crossCheck=True), the matcher the reference
+ * carries commented out at omnistereo/camera_models.py:401.  keys_fwd [nprob, q_stride] are the keys of
+ * sosvo_match_hamming(k = 1) for the problems (nq, nt, q_slot, t_slot); keys_rev [nprob, t_stride] those of the same call
+ * with query and train (descriptors, counts, slots and strides) swapped, so keys_rev[p*t_stride + j] names the query
+ * closest to train j, lowest query index on ties.  For each query row i < nq[qs]:
+ *   keys_out[p*q_stride + i] = keys_fwd[p*q_stride + i]  if its train j chose i back: (keys_rev[p*t_stride + j] & IDX_MASK) == i
+ *                            = SOSVO_KEY_NONE            otherwise (and where keys_fwd is SOSVO_KEY_NONE)
+ *   n_kept[p] = number of kept matches (n_kept may be NULL).
+ * Rows i >= nq[qs] are not written.  keys_out may be keys_fwd.  sosvo_sort_matches puts the kept matches first, in the
+ * order sorted() gives them; the assemble stages take len(matches) as the number of keys that are not SOSVO_KEY_NONE.
+ * Defined for 1-NN Hamming keys only (OpenCV refuses crossCheck with k > 1).  Counts / slots as in sosvo_match_hamming. */
+int32_t sosvo_cross_check_matches(sosvo_ctx* ctx, const uint32_t* keys_fwd, const uint32_t* keys_rev, const int32_t* nq,
+                                  const int32_t* nt, const int32_t* q_slot, const int32_t* t_slot, int32_t nprob,
+                                  int32_t q_stride, int32_t t_stride, uint32_t* keys_out, int32_t* n_kept);
+
 /* Stable sort of each problem's 1-NN matches by distance, the `sorted(matches,
  * key=distance)` of omnistereo/camera_models.py:444.  Input keys as written by
  * sosvo_match_hamming with k = 1.  Output, for rank r < nq[qs]:
@@ -528,6 +543,21 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
 #define SOSVO_RGBD_DETECTOR(d) ((d) << SOSVO_RGBD_DETECTOR_SHIFT)
 #define SOSVO_RGBD_DETECTOR_OF(flags) (((flags) & SOSVO_RGBD_DETECTOR_MASK) >> SOSVO_RGBD_DETECTOR_SHIFT)
 
+/* ---- mutual-consistency (cross-check) matching in the batch and sequence entry points --------------------
+ * The reference has two matcher objects, and each may be built with crossCheck=True (camera_models.py:401):
+ *   SOSVO_FLAG_CROSS_CHECK_STEREO  feature_matcher_for_static_stereo: top / bottom matching per azimuthal bucket
+ *   SOSVO_FLAG_CROSS_CHECK_F2F     feature_matcher_for_motion: frame-to-frame matching per view (RGB-D: the one matcher)
+ * Both are honoured in sosvo_batch_cfg.ransac_flags, ..._F2F in sosvo_rgbd_batch_cfg.flags; ..._STEREO in an RGB-D
+ * configuration is SOSVO_ERR_ARG (and a workspace size of 0).  With a bit set, the forward and the role-swapped problems
+ * of a matching step run as ONE sosvo_match_hamming launch over a slot table, sosvo_cross_check_matches filters the
+ * forward keys, and the sort / assemble stages follow as always: int(pct_good_matches * len(matches)) then counts the
+ * kept matches.  The workspaces grow by the reverse keys and the slot tables only when a bit is set; with both clear
+ * sizes, launches and results are unchanged.  The bits never reach the RANSAC flags.  A matching launch holds at most 65535
+ * problems (sosvo_match_hamming), forward and reverse together: frames x nmask <= 32767 per front-end call with ..._STEREO,
+ * pairs <= 32767 per tracking call with ..._F2F (n_pairs <= 8192 anyway). */
+#define SOSVO_FLAG_CROSS_CHECK_STEREO 0x1000
+#define SOSVO_FLAG_CROSS_CHECK_F2F 0x2000
+
 /* ---- the whole hot path for a batch of frame pairs (the throughput entry point) ----------------
  * One call = for B independent pairs (frames 2i = reference / keyframe, 2i+1 = current):
  *   OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__ for both frames
@@ -571,7 +601,8 @@ typedef struct sosvo_batch_cfg {
   double ransac_threshold; /* 1 - cos(5 deg) (pose_est_tools.py:675-676) */
   uint64_t seed;           /* pair i samples with seed + i */
   float cos_a, sin_a;      /* descriptor orientation given to the GFT keypoints */
-  int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P */
+  int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P;
+                              SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above) */
   int32_t detector;        /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
@@ -706,6 +737,7 @@ typedef struct sosvo_rgbd_batch_cfg {
   int32_t flags;           /* SOSVO_FLAG_EPNP: "EPNP" (6-point samples); 0: "KNEIP" (P3P + 4th point); SOSVO_FLAG_GP3P: "GAO" / "GP3P";
                               SOSVO_FLAG_TWOPT: "TWOPT" -- passed through to sosvo_ransac_abs_pose;
                               bits 8-9: SOSVO_RGBD_DETECTOR(enum sosvo_detector), 0 = GFT (masked off before the solver).
+                              SOSVO_FLAG_CROSS_CHECK_F2F: mutual matches only (masked off as well; ..._STEREO: SOSVO_ERR_ARG).
                               The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
                               for every frame) */
   double quality, min_distance;        /* 0.01, 5 */

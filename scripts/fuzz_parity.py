@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzzing of the stage entry points against the CPU oracle (test infrastructure: the oracle is the checker).
 
-    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch]
+    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch,cross_check]
 
 Every case draws its own sizes and parameters (image sizes around the strip / chunk / tile borders of the kernels, ragged
 problem counts, empty masks, fractional minimum distances, budgets that end a selection inside a round, duplicate
@@ -200,6 +200,61 @@ def fuzz_match(ctx, rng):
         want = oracle.match_hamming(q[p, :nq[p]], t[p, :nt[p]], k=k)
         if not np.array_equal(keys[p, :nq[p]], want):
             return params, "problem %d" % p
+    return params, None
+
+
+def fuzz_cross_check(ctx, rng):
+    """The mutual-consistency filter (sosvo_cross_check_matches on the keys of two sosvo_match_hamming calls, then the sort)
+    against the composition of oracle calls: query i keeps its best train j iff the best query of j is i.  Sizes 0 and 1, the
+    32-query / 128-train tile edges of the matcher, and half of the cases through slot tables over one descriptor store."""
+    NONE, IDX = 0xFFFFFFFF, 0xFFFFF
+    sizes = [0, 1, 2, 31, 32, 33, 127, 128, 129, 255, 257, 300]
+    slots = rng.random() < 0.5
+    if slots:            # a store of blocks, problems = (query block, train block) pairs, a block may meet itself
+        nb, S = int(rng.integers(1, 6)), int(rng.choice([1, 33, 130, 320]))
+        cnt = np.minimum(rng.choice(sizes, nb), S).astype(np.int32)
+        store, _ = _descriptors(rng, nb, S, S, cnt, cnt)
+        for b in range(1, nb):   # later blocks re-observe earlier ones: several queries per train
+            m = min(cnt[b], cnt[b - 1])
+            if m:
+                store[b, :m:2] = store[b - 1, rng.integers(0, max(1, m // 2), len(range(0, m, 2)))]
+        P = int(rng.integers(1, 9))
+        qs, ts = rng.integers(0, nb, P).astype(np.int32), rng.integers(0, nb, P).astype(np.int32)
+        q = t = store
+        nq = nt = cnt
+        Sq = St = S
+    else:
+        P = int(rng.integers(1, 9))
+        Sq, St = int(rng.choice([1, 33, 130, 320])), int(rng.choice([1, 33, 129, 320]))
+        nq = np.minimum(rng.choice(sizes, P), Sq).astype(np.int32)
+        nt = np.minimum(rng.choice(sizes, P), St).astype(np.int32)
+        q, t = _descriptors(rng, P, Sq, St, nq, nt)
+        qs = ts = np.arange(P, dtype=np.int32)
+    alias = bool(rng.integers(0, 2))
+    params = dict(P=P, slots=slots, q_stride=Sq, t_stride=St, nq=nq.tolist(), nt=nt.tolist(), q_slot=qs.tolist(), t_slot=ts.tolist(),
+                  alias=alias)
+    tq, tt, tnq, tnt, tqs, tts = _dev(ctx, q, t, nq, nt, qs, ts)
+    fwd_slots = dict(q_slot=tqs, t_slot=tts) if slots else {}
+    rev_slots = dict(q_slot=tts, t_slot=tqs) if slots else {}
+    fwd = ctx.match_hamming(tq, tt, tnq, tnt, k=1, **fwd_slots)
+    rev = ctx.match_hamming(tt, tq, tnt, tnq, k=1, **rev_slots)
+    out, n_kept = ctx.cross_check_matches(fwd, rev, tnq, tnt, keys_out=fwd if alias else None, **fwd_slots)
+    order = ctx.sort_matches(out, tnq, q_slot=tqs if slots else None)
+    ctx.synchronize()
+    out, n_kept, order = out.cpu().numpy()[:, :, 0], n_kept.cpu().numpy(), order.cpu().numpy()
+    for p in range(P):
+        n, m = int(nq[qs[p]]), int(nt[ts[p]])
+        want = np.full(n, NONE, np.uint32)
+        if n and m:
+            f = oracle.match_hamming(q[qs[p], :n], t[ts[p], :m], k=1)[:, 0]
+            r = oracle.match_hamming(t[ts[p], :m], q[qs[p], :n], k=1)[:, 0]
+            want = np.where((r[f & IDX] & IDX) == np.arange(n), f, np.uint32(NONE)).astype(np.uint32)
+        if not np.array_equal(out[p, :n], want):
+            return params, "problem %d: keys" % p
+        if n_kept[p] != int((want != NONE).sum()):
+            return params, "problem %d: n_kept" % p
+        if not np.array_equal(order[p, :n], oracle.sort_matches(want)):
+            return params, "problem %d: order" % p
     return params, None
 
 
@@ -818,7 +873,7 @@ def fuzz_rgbd(ctx, rng):
 STAGES = {"median": fuzz_median, "gft": fuzz_gft, "fast": fuzz_fast, "agast": fuzz_agast, "match": fuzz_match,
           "radius": fuzz_radius, "orb": fuzz_orb, "unwrap": fuzz_unwrap, "ransac": fuzz_ransac,
           "describe": fuzz_describe, "relpose": fuzz_relpose, "l2sort": fuzz_l2sort,
-          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd, "batch": fuzz_batch}
+          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd, "batch": fuzz_batch, "cross_check": fuzz_cross_check}
 
 
 def main():

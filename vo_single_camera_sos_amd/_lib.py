@@ -71,6 +71,7 @@ SIGNATURES = {
     "sosvo_detect_agast": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     "sosvo_match_hamming": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_match_radius": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sosvo_cross_check_matches": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_sort_matches": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p]),
     "sosvo_pano_to_bearing": (c_i32, [c_p, c_p, c_i32, c_f64, c_f64, c_f64, c_f64, c_p, c_p, c_p]),
     "sosvo_triangulate_midpoint": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p]),
@@ -125,6 +126,8 @@ FLAG_CAM_ROT_IDENTITY = 1
 FLAG_EPNP = 2
 FLAG_GP3P = 4
 FLAG_TWOPT = 8
+FLAG_CROSS_CHECK_STEREO = 0x1000   # mutual matches only: static stereo (sosvo_batch_cfg.ransac_flags)
+FLAG_CROSS_CHECK_F2F = 0x2000      # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1
 DETECTOR_FAST = 2
@@ -180,6 +183,11 @@ def detector_code(method):
 def rgbd_detector_flags(method):
     """SOSVO_RGBD_DETECTOR(d): the detector's bits of sosvo_rgbd_batch_cfg.flags."""
     return detector_code(method) << RGBD_DETECTOR_SHIFT
+
+
+def cross_check_flags(stereo=False, f2f=False):
+    """The SOSVO_FLAG_CROSS_CHECK_* bits of a batch configuration for the two matchers' switches."""
+    return (FLAG_CROSS_CHECK_STEREO if stereo else 0) | (FLAG_CROSS_CHECK_F2F if f2f else 0)
 
 
 def rgbd_flags_detector(flags):

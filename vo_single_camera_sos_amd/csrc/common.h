@@ -154,6 +154,15 @@ __device__ __forceinline__ int sosvo_block_compact_pos(bool valid, int* wave_off
   __syncthreads();
   return wave_off[wid] + __popcll(bal & ((1ULL << lane) - 1ULL));
 }
+
+// len(matches) of one matching problem, for the assemble kernels: how many of its nq 1-NN keys are not SOSVO_KEY_NONE
+// (every query's when the train set is not empty; fewer after sosvo_cross_check_matches).  Called by all `threads` threads of
+// the workgroup with the same arguments; the result is uniform.
+__device__ __forceinline__ int sosvo_block_count_matches(const uint32_t* __restrict__ keys, int nq, int tid, int threads) {
+  int kept = 0;
+  for (int i0 = 0; i0 < nq; i0 += threads) kept += __syncthreads_count(i0 + tid < nq && keys[i0 + tid] != SOSVO_KEY_NONE);
+  return kept;
+}
 #endif
 
 // detect.hip: the rolling 7x7 blur on images that lie img_stride bytes apart (also used by orb.hip for the pyramid levels)

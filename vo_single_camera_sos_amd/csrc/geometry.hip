@@ -129,27 +129,39 @@ __device__ __forceinline__ void stereo_assemble_frame(
     int32_t* __restrict__ M, int32_t* __restrict__ n_cand) {
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ int wave_off[kThreads / 64 + 1];
-  __shared__ int s_running;
+  __shared__ int s_running, s_cand;
   const int tid = threadIdx.x;
-  if (tid == 0) s_running = 0;
+  if (tid == 0) s_running = s_cand = 0;
   __syncthreads();
-  int cand_total = 0;
+  // len(matches) is the number of keys that are not SOSVO_KEY_NONE: every query's when the train set is not empty, the
+  // mutual matches alone after sosvo_cross_check_matches (the sort put them first).  With pct_good_matches == 1 (the
+  // trackers' setting) every one of them is a candidate, so the ranks are walked to nq and a NONE key is no match; any
+  // other fraction needs the count before the walk.
+  const bool take_all = rig.pct_good_matches == 1.0;
   for (int m = 0; m < nmask; ++m) {
     const int p = fr * nmask + m;
     const int nq = min(n_bot[p], cap), nt = min(n_top[p], cap);
     if (nq == 0 || nt == 0) continue;                                 // camera_models.py:3039
-    const int good = (int)(rig.pct_good_matches * (double)nq);        // camera_models.py:3045
-    cand_total += good;
     const size_t pb = (size_t)p * cap;
+    const int kept = take_all ? nq : sosvo_block_count_matches(keys + pb, nq, tid, kThreads);
+    const int good = (int)(rig.pct_good_matches * (double)kept);      // camera_models.py:3045
     for (int r0 = 0; r0 < good; r0 += kThreads) {
       const int r = r0 + tid;
-      bool valid = false;
+      bool valid = false, matched = false;
       int q = 0, t = 0;
       double xyz[3], bt[3], bb[3];
       float ut = 0, vt = 0, ub = 0, vb = 0;
       if (r < good) {
         q = order[pb + r];                                            // query = bottom (:3042)
-        t = (int)(keys[pb + q] & SOSVO_KEY_IDX_MASK);                 // train = top
+        const uint32_t key = keys[pb + q];
+        matched = key != SOSVO_KEY_NONE;
+        t = matched ? (int)(key & SOSVO_KEY_IDX_MASK) : 0;            // train = top
+      }
+      if (n_cand) {                                                   // candidates = matches among the first `good` ranks
+        const unsigned long long bal = __ballot(matched);
+        if ((tid & 63) == 0 && bal) atomicAdd(&s_cand, __popcll(bal));
+      }
+      if (matched) {
         ut = kp_top[2 * (pb + t)];
         vt = kp_top[2 * (pb + t) + 1];
         ub = kp_bot[2 * (pb + q)];
@@ -186,7 +198,7 @@ __device__ __forceinline__ void stereo_assemble_frame(
   __syncthreads();
   if (tid == 0) {
     M[slot] = min(s_running, out_cap);
-    if (n_cand) n_cand[fr] = cand_total;
+    if (n_cand) n_cand[fr] = s_cand;
   }
 }
 
@@ -231,10 +243,14 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
   __syncthreads();
   const int fr_ref = ref_frame[pr], fr_cur = cur_frame[pr];
   const int nq = min(M[fr_cur], frame_cap), nt = min(M[fr_ref], frame_cap);
-  const int good = (nt > 0) ? (int)(rig.pct_good_matches * (double)nq) : 0;  // pose_est_tools.py:225
+  const bool take_all = rig.pct_good_matches == 1.0;
   const size_t kb = (size_t)pr * frame_cap;
   for (int view = 0; view < 2; ++view) {
     const uint32_t* keys = view == 0 ? keys_top : keys_bot;
+    // len(matches) = the keys that are not SOSVO_KEY_NONE, as in stereo_assemble_frame: walked to nq when every match is
+    // taken, counted first otherwise
+    const int kept = nt == 0 ? 0 : take_all ? nq : sosvo_block_count_matches(keys + kb, nq, tid, kThreads);
+    const int good = (int)(rig.pct_good_matches * (double)kept);  // pose_est_tools.py:225
     const int32_t* order = view == 0 ? order_top : order_bot;
     const float* mm = view == 0 ? m_top : m_bot;
     const double* bb = view == 0 ? b_top : b_bot;
@@ -244,9 +260,10 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
       int q = 0, t = 0;
       if (r < good) {
         q = order[kb + r];                                  // query = current frame (:215)
-        t = (int)(keys[kb + q] & SOSVO_KEY_IDX_MASK);       // train = reference (key)frame
-        valid = true;
-        if (rig.f2f_max_hdiff >= 0) {                       // :245-247, gate inside common_cv.py:177
+        const uint32_t key = keys[kb + q];
+        valid = key != SOSVO_KEY_NONE;
+        t = valid ? (int)(key & SOSVO_KEY_IDX_MASK) : 0;    // train = reference (key)frame
+        if (valid && rig.f2f_max_hdiff >= 0) {              // :245-247, gate inside common_cv.py:177
           const double u_train = (double)mm[2 * ((size_t)fr_ref * frame_cap + t)];
           const double u_query = (double)mm[2 * ((size_t)fr_cur * frame_cap + q)];
           valid = sv_pixel_gate(u_train, 0.0, u_query, 0.0, -1.0, rig.f2f_max_hdiff);

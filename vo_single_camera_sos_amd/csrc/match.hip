@@ -322,6 +322,45 @@ __global__ __launch_bounds__(kThreads) void sort_matches_kernel(const uint32_t* 
   if (i < n) order[(size_t)p * q_stride + rank] = i;
 }
 
+// ---- mutual-consistency filter (cv2.BFMatcher(NORM_HAMMING, crossCheck=True), the commented-out matcher of
+// omnistereo/camera_models.py:401).  keys_fwd are the 1-NN keys of the queries, keys_rev those of the same search with the
+// roles swapped (both "smallest distance, first index"): query i keeps its key iff the train it chose chose it back.  One
+// workgroup per problem, so the count of kept matches needs neither atomics nor a cleared output.  keys_out may be
+// keys_fwd: a lane reads the entry it writes, and nothing else of that array.
+__global__ __launch_bounds__(kThreads) void cross_check_kernel(const uint32_t* keys_fwd, const uint32_t* __restrict__ keys_rev,
+                                                               const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
+                                                               const int32_t* __restrict__ q_slot,
+                                                               const int32_t* __restrict__ t_slot, int q_stride, int t_stride,
+                                                               uint32_t* keys_out, int32_t* __restrict__ n_kept) {
+  __shared__ int wave_kept[kThreads / 64];
+  const int tid = threadIdx.x, p = blockIdx.x;
+  const int n = min(nq[q_slot ? q_slot[p] : p], q_stride), m = min(nt[t_slot ? t_slot[p] : p], t_stride);
+  const uint32_t* fwd = keys_fwd + (size_t)p * q_stride;
+  const uint32_t* rev = keys_rev + (size_t)p * t_stride;
+  uint32_t* out = keys_out + (size_t)p * q_stride;
+  int kept = 0;
+  for (int i = tid; i < n; i += kThreads) {
+    uint32_t k = fwd[i];
+    const uint32_t j = k & SOSVO_KEY_IDX_MASK;
+    bool keep = false;
+    if (k != SOSVO_KEY_NONE && j < (uint32_t)m) {  // (j < m always holds for keys of sosvo_match_hamming: a bounds guard)
+      const uint32_t r = rev[j];
+      keep = r != SOSVO_KEY_NONE && (r & SOSVO_KEY_IDX_MASK) == (uint32_t)i;
+    }
+    out[i] = keep ? k : SOSVO_KEY_NONE;
+    kept += keep ? 1 : 0;
+  }
+  if (!n_kept) return;
+  for (int s = 32; s > 0; s >>= 1) kept += __shfl_down(kept, s);
+  if ((tid & 63) == 0) wave_kept[tid >> 6] = kept;
+  __syncthreads();
+  if (tid == 0) {
+    int total = 0;
+    for (int w = 0; w < kThreads / 64; ++w) total += wave_kept[w];
+    n_kept[p] = total;
+  }
+}
+
 // ---- radius match ------------------------------------------------------------------------------------------
 // cv2.BFMatcher.radiusMatch (omnistereo/camera_models.py:413, FeatureMatcher.use_radius_match): for every query
 // ALL train descriptors within max_distance.  One wave per query: the query sits in 8 VGPRs of every lane, lane l
@@ -461,6 +500,21 @@ int32_t sosvo_match_hamming(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t
       SOSVO_LAUNCH(ctx, (match_hamming_mfma_kernel<1, 2>), grid, block, 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride,
                    t_stride, nsplit, keys);
   }
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_cross_check_matches(sosvo_ctx* ctx, const uint32_t* keys_fwd, const uint32_t* keys_rev, const int32_t* nq,
+                                  const int32_t* nt, const int32_t* q_slot, const int32_t* t_slot, int32_t nprob,
+                                  int32_t q_stride, int32_t t_stride, uint32_t* keys_out, int32_t* n_kept) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, keys_fwd && keys_rev && nq && nt && keys_out, "null pointer");
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
+  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT) && t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT),
+                "strides out of range");
+  if (nprob == 0) return SOSVO_OK;
+  SOSVO_LAUNCH(ctx, cross_check_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, keys_fwd, keys_rev, nq, nt, q_slot, t_slot,
+               q_stride, t_stride, keys_out, n_kept);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }

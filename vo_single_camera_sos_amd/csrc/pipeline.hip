@@ -43,6 +43,41 @@ bool detector_ok(int detector, int kp_cap) {
 }
 int rgbd_detector(const sosvo_rgbd_batch_cfg& c) { return SOSVO_RGBD_DETECTOR_OF(c.flags); }
 
+// ---- mutual-consistency matching (SOSVO_FLAG_CROSS_CHECK_*, camera_models.py:401) -------------------------------------
+// A matching step of n problems over ONE descriptor store runs as 2 n problems of one sosvo_match_hamming launch: problem
+// p < n is the forward search (query block q[p], train block t[p]), problem n + p the same search with the roles swapped.
+// The slot tables hold both halves: q_slot = [q | t], t_slot = [t | q], 2 n entries each, and the keys [2 n, stride] are
+// forward rows first.  Carved only when the switch is set, after everything else, so that the other members keep their
+// offsets and the workspace its size.
+struct MutualTabs {
+  int32_t *q_slot = nullptr, *t_slot = nullptr;
+};
+MutualTabs carve_mutual(Carver& cv, bool on, size_t n) {
+  MutualTabs m;
+  if (!on) return m;
+  m.q_slot = cv.take<int32_t>(2 * n);
+  m.t_slot = cv.take<int32_t>(2 * n);
+  return m;
+}
+bool cross_stereo(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_CROSS_CHECK_STEREO) != 0; }
+bool cross_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
+bool cross_f2f(const sosvo_rgbd_batch_cfg& c) { return (c.flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
+// (an RGB-D camera has no static stereo to cross-check)
+bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) { return (c.flags & SOSVO_FLAG_CROSS_CHECK_STEREO) == 0; }
+
+// q == nullptr: static stereo, bucket p's query block is n + p (bottom view), its train block p (top view);
+// otherwise the slot pairs of a tracking call: query = current frame, train = reference frame
+__global__ void mutual_tabs_kernel(int n, const int32_t* __restrict__ q, const int32_t* __restrict__ t,
+                                   int32_t* __restrict__ q_slot, int32_t* __restrict__ t_slot) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const int qs = q ? q[p] : n + p, ts = q ? t[p] : p;
+  q_slot[p] = qs;
+  t_slot[p] = ts;
+  q_slot[n + p] = ts;
+  t_slot[n + p] = qs;
+}
+
 // ---- the workspace of the omni family: front-end temporaries of one WINDOW of frames, a frame STORE of `slots` frame
 // records, tracking of up to cfg.n_pairs slot pairs per call.  The structs below are what the runners take; each is carved
 // member by member, so a buffer has one name from the carve to its use.
@@ -52,6 +87,7 @@ struct FrontEndTmp {
   int32_t *n, *status, *s_order, *n_cand, *gray_rows;
   uint32_t* s_keys;
   OrbBufs orb;
+  MutualTabs mutual;
 };
 FrontEndTmp carve_front_end(Carver& cv, const sosvo_batch_cfg& c, size_t F) {
   FrontEndTmp t{};
@@ -63,7 +99,7 @@ FrontEndTmp carve_front_end(Carver& cv, const sosvo_batch_cfg& c, size_t F) {
   t.n = cv.take<int32_t>(P);
   t.status = cv.take<int32_t>(P);
   t.desc = cv.take<uint8_t>(P * cap * 32);
-  t.s_keys = cv.take<uint32_t>(P / 2 * cap);
+  t.s_keys = cv.take<uint32_t>((cross_stereo(c) ? P : P / 2) * cap);  // (cross-check: the reverse keys follow the forward ones)
   t.s_order = cv.take<int32_t>(P / 2 * cap);
   t.n_cand = cv.take<int32_t>(F);
   t.gray_rows = cv.take<int32_t>(4);
@@ -108,14 +144,15 @@ struct TrackTmp {
   uint32_t *k_top, *k_bot;
   uint8_t* mask;
   double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
+  MutualTabs mutual;
 };
-TrackTmp carve_track(Carver& cv, size_t B, size_t Fc) {
+TrackTmp carve_track(Carver& cv, size_t B, size_t Fc, bool mutual) {
   TrackTmp t{};
-  const size_t Cc = 2 * Fc;
+  const size_t Cc = 2 * Fc, Kr = mutual ? 2 : 1;  // (cross-check: the reverse keys follow the forward ones)
   t.ref_frame = cv.take<int32_t>(B);
   t.cur_frame = cv.take<int32_t>(B);
-  t.k_top = cv.take<uint32_t>(B * Fc);
-  t.k_bot = cv.take<uint32_t>(B * Fc);
+  t.k_top = cv.take<uint32_t>(Kr * B * Fc);
+  t.k_bot = cv.take<uint32_t>(Kr * B * Fc);
   t.o_top = cv.take<int32_t>(B * Fc);
   t.o_bot = cv.take<int32_t>(B * Fc);
   t.f = cv.take<double>(B * Cc * 3);
@@ -150,8 +187,10 @@ Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* bas
   Workspace ws;
   ws.fe = carve_front_end(cv, c, window);
   ws.store = carve_store(cv, slots, c.frame_cap);
-  ws.tt = carve_track(cv, c.n_pairs, c.frame_cap);
+  ws.tt = carve_track(cv, c.n_pairs, c.frame_cap, cross_f2f(c));
   ws.fe.orb = carve_orb(cv, c.detector, 2 * window * c.nmask, c.kp_cap, 2, c.rows, c.cols);
+  ws.fe.mutual = carve_mutual(cv, cross_stereo(c), window * c.nmask);
+  ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
   ws.bytes = cv.off;
   return ws;
 }
@@ -308,12 +347,13 @@ struct RgbdTrackTmp {
   uint8_t* mask;
   double *f, *p, *T_ransac, *T, *lm_cost;
   double *cam_off, *cam_rot;  // (never carved: a central camera has none, they stay null for the setup kernel)
+  MutualTabs mutual;
 };
-RgbdTrackTmp carve_rgbd_track(Carver& cv, size_t B, size_t Fc) {
+RgbdTrackTmp carve_rgbd_track(Carver& cv, size_t B, size_t Fc, bool mutual) {
   RgbdTrackTmp t{};
   t.ref_frame = cv.take<int32_t>(B);
   t.cur_frame = cv.take<int32_t>(B);
-  t.keys = cv.take<uint32_t>(B * Fc);
+  t.keys = cv.take<uint32_t>((mutual ? 2 : 1) * B * Fc);  // (cross-check: the reverse keys follow the forward ones)
   t.order = cv.take<int32_t>(B * Fc);
   t.f = cv.take<double>(B * Fc * 3);
   t.p = cv.take<double>(B * Fc * 3);
@@ -342,8 +382,9 @@ RgbdWorkspace carve_rgbd(const sosvo_rgbd_batch_cfg& c, size_t window, size_t sl
   RgbdWorkspace ws;
   ws.fe = carve_rgbd_front_end(cv, c, window);
   ws.store = carve_rgbd_store(cv, slots, c.frame_cap);
-  ws.tt = carve_rgbd_track(cv, c.n_pairs, c.frame_cap);
+  ws.tt = carve_rgbd_track(cv, c.n_pairs, c.frame_cap, cross_f2f(c));
   ws.fe.orb = carve_orb(cv, rgbd_detector(c), window, c.kp_cap, 1, c.rows, c.cols);
+  ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
   ws.bytes = cv.off;
   return ws;
 }
@@ -461,6 +502,25 @@ size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
     if (rc != SOSVO_OK) return rc; \
   } while (0)
 
+// The slot tables of a matching step of n problems with the mutual-consistency filter.  q / t: the tracking call's device
+// slot pairs (nullptr: static stereo, see mutual_tabs_kernel).
+static int32_t mutual_tabs(sosvo_ctx* ctx, const int32_t* q, const int32_t* t, int n, const MutualTabs& m) {
+  SOSVO_LAUNCH(ctx, mutual_tabs_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ctx->stream, n, q, t, m.q_slot, m.t_slot);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+// One such step over the descriptor store `desc` (blocks of `stride` rows, counts `cnt`): ONE launch of n forward + n
+// role-swapped problems through the tables, then the filter on the forward keys.  The forward keys of `keys` [2 n, stride]
+// are sorted and assembled like those of a plain sosvo_match_hamming call.
+static int32_t match_mutual(sosvo_ctx* ctx, const uint8_t* desc, const int32_t* cnt, int n, int stride, const MutualTabs& m,
+                            uint32_t* keys) {
+  int32_t rc;
+  STAGE(sosvo_match_hamming(ctx, desc, desc, cnt, cnt, m.q_slot, m.t_slot, 2 * n, stride, stride, 1, keys));
+  return sosvo_cross_check_matches(ctx, keys, keys + (size_t)n * stride, cnt, cnt, m.q_slot, m.t_slot, n, stride, stride, keys,
+                                   nullptr);
+}
+
 // The image front end + static stereo of F frames (OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__,
 // camera_models.py:3107-3120, pose_est_tools.py:271-402): K1, K2 + K3, K4, K6 over all 2 F panoramas, per-bucket top/bottom
 // matching, gates, bearings, midpoint triangulation, range filter -> F frame records written at out_* (frame-major).
@@ -514,7 +574,11 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const float *kp_top = t.kp, *kp_bot = t.kp + (size_t)h * cap * 2;
   const uint8_t *desc_top = t.desc, *desc_bot = t.desc + (size_t)h * cap * 32;
   const int32_t *n_top = t.n, *n_bot = t.n + h;
-  STAGE(sosvo_match_hamming(ctx, desc_bot, desc_top, n_bot, n_top, nullptr, nullptr, h, cap, cap, 1, t.s_keys));
+  if (cross_stereo(*cfg)) {  // (top and bottom are the two halves of t.desc / t.n: blocks p and h + p)
+    STAGE(mutual_tabs(ctx, nullptr, nullptr, h, t.mutual));
+    STAGE(match_mutual(ctx, t.desc, t.n, h, cap, t.mutual, t.s_keys));
+  } else
+    STAGE(sosvo_match_hamming(ctx, desc_bot, desc_top, n_bot, n_top, nullptr, nullptr, h, cap, cap, 1, t.s_keys));
   STAGE(sosvo_sort_matches(ctx, t.s_keys, n_bot, nullptr, h, cap, t.s_order));
   if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
     STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
@@ -534,9 +598,17 @@ static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_ba
                             const FrameStore& s, const TrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
   int32_t rc;
-  STAGE(sosvo_match_hamming(ctx, s.d_top, s.d_top, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_top));
+  const bool mutual = cross_f2f(*cfg);
+  if (mutual) {  // (one pair of tables serves both views)
+    STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
+    STAGE(match_mutual(ctx, s.d_top, s.M, B, Fc, b.mutual, b.k_top));
+  } else
+    STAGE(sosvo_match_hamming(ctx, s.d_top, s.d_top, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_top));
   STAGE(sosvo_sort_matches(ctx, b.k_top, s.M, b.cur_frame, B, Fc, b.o_top));
-  STAGE(sosvo_match_hamming(ctx, s.d_bot, s.d_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_bot));
+  if (mutual)
+    STAGE(match_mutual(ctx, s.d_bot, s.M, B, Fc, b.mutual, b.k_bot));
+  else
+    STAGE(sosvo_match_hamming(ctx, s.d_bot, s.d_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_bot));
   STAGE(sosvo_sort_matches(ctx, b.k_bot, s.M, b.cur_frame, B, Fc, b.o_bot));
   STAGE(sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top,
                            b.o_top, b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top));
@@ -733,7 +805,7 @@ int32_t sosvo_frame_pair_batch_streams_join(sosvo_ctx* ctx) {
 
 size_t sosvo_rgbd_pair_batch_workspace(const sosvo_rgbd_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->kp_cap <= 0 || cfg->frame_cap <= 0 ||
-      !detector_ok(rgbd_detector(*cfg), cfg->kp_cap))
+      !detector_ok(rgbd_detector(*cfg), cfg->kp_cap) || !rgbd_flags_ok(*cfg))
     return 0;
   const size_t F = 2 * (size_t)cfg->n_pairs;
   return carve_rgbd(*cfg, F, F, nullptr).bytes;
@@ -777,7 +849,11 @@ static int32_t run_rgbd_tracking(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg
                                  const RgbdTrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
   const int Fc = cfg->frame_cap;
   int32_t rc;
-  STAGE(sosvo_match_hamming(ctx, s.d, s.d, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.keys));
+  if (cross_f2f(*cfg)) {
+    STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
+    STAGE(match_mutual(ctx, s.d, s.M, B, Fc, b.mutual, b.keys));
+  } else
+    STAGE(sosvo_match_hamming(ctx, s.d, s.d, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.keys));
   STAGE(sosvo_sort_matches(ctx, b.keys, s.M, b.cur_frame, B, Fc, b.order));
   STAGE(sosvo_f2f_assemble_central(ctx, cfg->pct_good_matches, cfg->f2f_max_hdiff, s.m, s.X, s.b, s.M, Fc, b.ref_frame,
                                    b.cur_frame, b.keys, b.order, B, Fc, b.f, b.p, b.cq, b.ct, b.cn));
@@ -808,6 +884,7 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   SOSVO_REQUIRE(ctx, cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384,
                 "kp_cap / frame_cap out of range");
   SOSVO_REQUIRE(ctx, detector_ok(rgbd_detector(*cfg), cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
+  SOSVO_REQUIRE(ctx, rgbd_flags_ok(*cfg), "SOSVO_FLAG_CROSS_CHECK_STEREO: an RGB-D camera has no static stereo");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
   const RgbdWorkspace ws = carve_rgbd(*cfg, F, F, workspace);
@@ -878,7 +955,7 @@ struct RgbdSeq {
   using Frames = RgbdFrames;
   static constexpr const char* kTooSmall = "workspace too small (see sosvo_rgbd_sequence_workspace)";
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
-    return c && seq_shape_ok(c, rgbd_detector(*c), window, slots);
+    return c && rgbd_flags_ok(*c) && seq_shape_ok(c, rgbd_detector(*c), window, slots);
   }
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return carve_rgbd(c, window, slots, base); }
   static StoreFields fields(const RgbdStore& s) {

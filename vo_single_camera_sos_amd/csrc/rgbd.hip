@@ -114,17 +114,22 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_central_kernel(
   __syncthreads();
   const int fr_ref = ref_frame[pr], fr_cur = cur_frame[pr];
   const int nq = min(M[fr_cur], frame_cap), nt = min(M[fr_ref], frame_cap);
-  const int good = (nt > 0) ? (int)(pct_good_matches * (double)nq) : 0;  // pose_est_tools.py:225
   const size_t kb = (size_t)pr * frame_cap;
+  // len(matches) = the keys that are not SOSVO_KEY_NONE (the mutual matches alone after sosvo_cross_check_matches; the sort
+  // put them first): walked to nq when every match is taken (pct_good_matches == 1, the trackers' setting), counted first
+  // otherwise
+  const int kept = nt == 0 ? 0 : pct_good_matches == 1.0 ? nq : sosvo_block_count_matches(keys + kb, nq, tid, kThreads);
+  const int good = (int)(pct_good_matches * (double)kept);  // pose_est_tools.py:225
   for (int r0 = 0; r0 < good; r0 += kThreads) {
     const int r = r0 + tid;
     bool valid = false;
     int q = 0, t = 0;
     if (r < good) {
       q = order[kb + r];                              // query = current frame (:215)
-      t = (int)(keys[kb + q] & SOSVO_KEY_IDX_MASK);   // train = reference (key)frame
-      valid = true;
-      if (max_hdiff > 0) {                            // :245-247 -> common_cv.py:177 (only |du| is tested)
+      const uint32_t key = keys[kb + q];
+      valid = key != SOSVO_KEY_NONE;
+      t = valid ? (int)(key & SOSVO_KEY_IDX_MASK) : 0;  // train = reference (key)frame
+      if (valid && max_hdiff > 0) {                   // :245-247 -> common_cv.py:177 (only |du| is tested)
         const double u_train = (double)m[2 * ((size_t)fr_ref * frame_cap + t)];
         const double u_query = (double)m[2 * ((size_t)fr_cur * frame_cap + q)];
         valid = fabs(u_train - u_query) <= max_hdiff;

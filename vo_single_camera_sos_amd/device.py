@@ -430,6 +430,33 @@ class Context(object):
                    P, Sq, St, int(max_distance), int(cap), _ptr(keys), _ptr(counts))
         return keys, counts
 
+    def cross_check_matches(self, keys_fwd, keys_rev, nq, nt, q_slot=None, t_slot=None, keys_out=None, n_kept=None):
+        """cv2.BFMatcher(NORM_HAMMING, crossCheck=True) on 1-NN keys: keys_fwd [P, Sq, 1] u32 from match_hamming(k=1),
+        keys_rev [P, St, 1] u32 from the same call with query and train (and the slots) swapped -> (keys_out [P, Sq, 1]
+        with the keys of non-mutual matches replaced by KEY_NONE, n_kept [P] i32).  keys_out may be keys_fwd."""
+        _check(keys_fwd, torch.uint32, "keys_fwd", (None, None, 1))
+        P, Sq = keys_fwd.shape[0], keys_fwd.shape[1]
+        _check(keys_rev, torch.uint32, "keys_rev", (P, None, 1))
+        St = keys_rev.shape[1]
+        _check(nq, torch.int32, "nq", ndim=1)
+        _check(nt, torch.int32, "nt", ndim=1)
+        if (q_slot is None) != (t_slot is None):
+            raise SosvoError("q_slot and t_slot go together")
+        if q_slot is not None:
+            _check(q_slot, torch.int32, "q_slot", (P,))
+            _check(t_slot, torch.int32, "t_slot", (P,))
+        elif nq.shape[0] != P or nt.shape[0] != P:
+            raise SosvoError("nq and nt must have one entry per problem without slots")
+        if keys_out is None:
+            keys_out = torch.full((P, Sq, 1), _lib.KEY_NONE, dtype=torch.uint32, device=keys_fwd.device)
+        _check(keys_out, torch.uint32, "keys_out", (P, Sq, 1))
+        if n_kept is None:
+            n_kept = torch.empty((P,), dtype=torch.int32, device=keys_fwd.device)
+        _check(n_kept, torch.int32, "n_kept", (P,))
+        self._call(self._lib.sosvo_cross_check_matches, _ptr(keys_fwd), _ptr(keys_rev), _ptr(nq), _ptr(nt), _ptr(q_slot),
+                   _ptr(t_slot), P, Sq, St, _ptr(keys_out), _ptr(n_kept))
+        return keys_out, n_kept
+
     def sort_matches(self, keys, nq, order=None, q_slot=None):
         """keys [P, Sq, 1] u32 (1-NN), nq i32 (per block) -> order [P, Sq] i32 (query index by rank)."""
         _check(keys, torch.uint32, "keys", (None, None, 1))

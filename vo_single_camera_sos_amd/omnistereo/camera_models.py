@@ -133,7 +133,11 @@ class FeatureMatcher(object):
     "SURF", :394-396).  k_best 1 (the trackers' setting, pose_est_tools.py:686) and 2, the "SIFT" k_best == 2 ratio
     rule, radius match for binary descriptors (use_radius_match, at most 512 matches per query).
     matcher_type "FLANN" (:384-393: randomised KD-trees / LSH tables, approximate) is served by the same EXACT searches:
-    the neighbours FLANN approximates.  Not built (raises): k_best > 2, radius match on float descriptors."""
+    the neighbours FLANN approximates.  Not built (raises): k_best > 2, radius match on float descriptors.
+    cross_check=True is the matcher the reference carries commented out at :401, cv2.BFMatcher(NORM_HAMMING,
+    crossCheck=True): a query keeps its best match only if that train descriptor's best query is the query itself (first
+    index on ties, both ways).  As in OpenCV it goes with one match per query only: k_best 1, no radius match; and here with
+    binary descriptors only (ValueError otherwise)."""
 
     def __init__(self, method, matcher_type, k_best, *args, **kwargs):
         self.feature_detection_method = method
@@ -148,6 +152,19 @@ class FeatureMatcher(object):
         if str(matcher_type).upper() not in ("BF", "FLANN"):
             raise ValueError("matcher_type %r: \"BF\" or \"FLANN\"" % matcher_type)
         self._ctx = kwargs.get("context", None)
+        self.cross_check = bool(kwargs.get("cross_check", False))
+        self._check_cross_check()
+
+    def _check_cross_check(self):
+        if not self.cross_check:
+            return
+        if self.k_best != 1:
+            raise ValueError("cross_check goes with k_best == 1 only (as cv2.BFMatcher refuses knnMatch with k > 1 under crossCheck)")
+        if self.use_radius_match:
+            raise ValueError("cross_check is defined for best-match search, not for radius match")
+        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
+            raise ValueError("cross_check is built for binary (Hamming) descriptors only; %r makes float descriptors"
+                             % self.feature_detection_method)
 
     def _context(self):
         if self._ctx is None:
@@ -178,7 +195,7 @@ class FeatureMatcher(object):
         every pair, but as ONE batched launch + one copy back when the matcher is in its best-match mode (the per-bucket
         loop of match_features_panoramic_top_bottom costs a dozen launch / synchronise round trips per frame otherwise)."""
         import torch
-        if self.use_radius_match or self.k_best != 1 or len(pairs) == 0 or any(self._is_float(q) for q, _ in pairs):
+        if self.use_radius_match or self.k_best != 1 or len(pairs) == 0 or any(self._is_float(q) or self._is_float(t) for q, t in pairs):
             return [self.match_arrays(q, t) for q, t in pairs]
         ctx = self._context()
         qs = [np.ascontiguousarray(np.asarray(q)) for q, _ in pairs]
@@ -198,9 +215,12 @@ class FeatureMatcher(object):
             ht[i, :nt[i]] = ts[i]
         dev = ctx.device
         nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
-        keys = ctx.match_hamming(torch.from_numpy(hq).to(dev), torch.from_numpy(ht).to(dev), nq_d, nt_d, k=1)
+        dq, dt = torch.from_numpy(hq).to(dev), torch.from_numpy(ht).to(dev)
+        keys = ctx.match_hamming(dq, dt, nq_d, nt_d, k=1)
+        if self.cross_check:
+            ctx.cross_check_matches(keys, ctx.match_hamming(dt, dq, nt_d, nq_d, k=1), nq_d, nt_d, keys_out=keys)
         order = ctx.sort_matches(keys, nq_d)
-        from .._lib import KEY_SHIFT, KEY_IDX_MASK
+        from .._lib import KEY_SHIFT, KEY_IDX_MASK, KEY_NONE
         kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
         out = []
         for i in range(P):
@@ -209,6 +229,8 @@ class FeatureMatcher(object):
                 continue
             o = oh[i, :nq[i]]
             k = kh[i][o]
+            if self.cross_check:  # (the rejected queries sorted last)
+                o, k = o[k != KEY_NONE], k[k != KEY_NONE]
             out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
         return out
 
@@ -259,7 +281,10 @@ class FeatureMatcher(object):
     def match_arrays(self, query_descriptors, train_descriptors, max_descriptor_distance_radius=-1):
         """-> (query_idx, train_idx, distance) numpy arrays in the order of match()."""
         import torch
+        self._check_cross_check()
         if self._is_float(query_descriptors) or self._is_float(train_descriptors):
+            if self.cross_check:
+                raise ValueError("cross_check is built for binary (Hamming) descriptors only, not float descriptors")
             return self._l2_arrays(query_descriptors, train_descriptors)
         if self.use_radius_match:
             return self._radius_arrays(query_descriptors, train_descriptors, max_descriptor_distance_radius)
@@ -281,9 +306,14 @@ class FeatureMatcher(object):
             # sorted(matches, key=distance) of one match per query (:442-444); for the ratio rule the filter
             # below keeps the sorted order of the survivors, which is the sorted order of the filtered list
             best = keys[:, :, :1].contiguous()
+            if self.cross_check:  # (k == 1) the role-swapped search, then the mutual filter in place
+                ctx.cross_check_matches(best, ctx.match_hamming(dt, dq, nt_t, nq_t, k=1), nq_t, nt_t, keys_out=best)
+                keys = best
             order = ctx.sort_matches(best, nq_t)
             kh = keys[0, :nq].cpu().numpy().astype(np.int64)
             oh = order[0, :nq].cpu().numpy().astype(np.int64)
+            if self.cross_check:  # (the rejected queries sorted last)
+                oh = oh[kh[oh, 0] != KEY_NONE]
             q = oh
             t = kh[oh, 0] & KEY_IDX_MASK
             d = (kh[oh, 0] >> KEY_SHIFT).astype(np.float32)

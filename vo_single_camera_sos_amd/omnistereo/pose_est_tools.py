@@ -241,6 +241,9 @@ class TrackerSE3(object):
         self.k_best_matches = 1
         self.percentage_good_matches = 1.0
         self.use_descriptor_radius_match_for_motion = False
+        # the matchers' crossCheck: off, as the reference builds them (camera_models.py:401-402); see set_cross_check
+        self.cross_check_static_stereo = False
+        self.cross_check_for_motion = False
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -279,12 +282,12 @@ class TrackerStereoSE3(TrackerSE3):
         om.feature_matcher_for_static_stereo = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_static_stereo,
-            use_radius_match=False)
+            use_radius_match=False, cross_check=self.cross_check_static_stereo)
         self.max_horizontal_diff_f2f_matches = 0.125 * self.max_horizontal_search_ratio * om.top_model.panorama.cols
         om.feature_matcher_for_motion = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
-            use_radius_match=self.use_descriptor_radius_match_for_motion)
+            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion)
         self.omni_mask_extra_padding = 10
         shape = None if om.current_omni_img is None else om.current_omni_img.shape[:2]
         if shape is None:
@@ -426,6 +429,47 @@ def set_detection_method(tracker, method):
             fm.feature_detection_method = tracker.detection_method
 
 
+def parse_cross_check(cross_check):
+    """run_VO's cross_check argument -> (static stereo, frame to frame) switches, or None for "the tracker's own setting":
+    None -> None; True / False -> both matchers; "stereo" / "f2f" -> that matcher alone ("both", "none" are accepted too)."""
+    if cross_check is None:
+        return None
+    if isinstance(cross_check, (bool, np.bool_)):
+        return bool(cross_check), bool(cross_check)
+    table = {"stereo": (True, False), "f2f": (False, True), "both": (True, True), "none": (False, False)}
+    name = str(cross_check).lower()
+    if not isinstance(cross_check, str) or name not in table:
+        raise ValueError("cross_check: None, True, False, \"stereo\" or \"f2f\"; got %r" % (cross_check,))
+    return table[name]
+
+
+def set_cross_check(tracker, cross_check):
+    """Switch the mutual-consistency filter (cv2.BFMatcher's crossCheck, camera_models.py:401) of the tracker's matchers:
+    cross_check as parse_cross_check takes it (None: leave the tracker's own setting).  The matchers bootstrap_tracker
+    built carry the switch, so the per-frame mirror path and the engine chosen from the tracker's settings both follow.
+    An RGB-D tracker has the frame-to-frame matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
+    switches = parse_cross_check(cross_check)
+    if switches is None:
+        return
+    stereo, f2f = switches
+    cm = tracker.camera_model
+    fm_stereo = getattr(cm, "feature_matcher_for_static_stereo", None)
+    fm_motion = getattr(cm, "feature_matcher_for_motion", None)
+    if _is_rgbd_model(cm):
+        if isinstance(cross_check, str) and stereo:
+            raise ValueError("cross_check=%r: an RGB-D tracker has no static-stereo matcher" % (cross_check,))
+        stereo = False
+    tracker.cross_check_static_stereo, tracker.cross_check_for_motion = stereo, f2f
+    for fm, on in ((fm_stereo, stereo), (fm_motion, f2f)):
+        if fm is not None:
+            fm.cross_check = on
+            fm._check_cross_check()   # (k_best > 1, radius match, float descriptors: ValueError)
+
+
+def _cross_check_of(fm):
+    return bool(getattr(fm, "cross_check", False)) if fm is not None else False
+
+
 def _sos_engine_settings(tracker, camera_model, first_image):
     """What a sequence engine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
     StereoPanoramicFrame compute is built from -> (positional arguments after ctx, keyword arguments, cache key), or None
@@ -453,12 +497,16 @@ def _sos_engine_settings(tracker, camera_model, first_image):
                     f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     nfeat = tracker.num_features_detection_for_static_stereo
     cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
+    # the two matchers' crossCheck (what the mirror path matches with): part of the engine's configuration and of its key
+    cc_stereo, cc_f2f = _cross_check_of(fm), _cross_check_of(getattr(om, "feature_matcher_for_motion", None))
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
-           float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model))
+           float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
+           cc_stereo, cc_f2f)
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
-                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method)
+                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
+                  cross_check_stereo=cc_stereo, cross_check_f2f=cc_f2f)
     return (model, rig), kwargs, key
 
 
@@ -598,11 +646,11 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
-           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z))
+           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm))
     kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
-                  detection_method=method)
+                  detection_method=method, cross_check=_cross_check_of(fm))
     return (cam,), kwargs, key
 
 
@@ -668,7 +716,7 @@ class TrackerRGBDSE3(TrackerSE3):
         self.camera_model.feature_matcher_for_motion = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
-            use_radius_match=self.use_descriptor_radius_match_for_motion)
+            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion)
         self.max_horizontal_diff_f2f_matches = self.max_horizontal_search_ratio * (self.camera_model.center_x * 2.)
 
     def track_frame(self, reference_frame, current_frame):
@@ -877,7 +925,8 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
 
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
-           _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None):
+           _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
+           cross_check=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -892,7 +941,11 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     The pose file does not depend on the window size (byte-identical for 1, 2, 32, ...); the mirror path agrees with
     it to rounding (its bearings go through numpy's trigonometry, the store's through the library's).
 
-    detection_method: "GFT", "ORB", "FAST" or "AGAST" for the tracker and its frames; None = the tracker's own (GFT)."""
+    detection_method: "GFT", "ORB", "FAST" or "AGAST" for the tracker and its frames; None = the tracker's own (GFT).
+
+    cross_check: mutual matches only, cv2.BFMatcher's crossCheck (camera_models.py:401).  None = the tracker's own setting
+    (off); True / False = both matchers; "stereo" / "f2f" = the static-stereo / the frame-to-frame matcher alone (see
+    set_cross_check).  Sequence mode and the mirror path follow alike."""
     from .common_cv import get_depthmap_float32_from_png, get_images, imread
     from .common_tools import get_poses_from_file
     if visualizer_3D_VO is not None:
@@ -980,6 +1033,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     with _CAMERA_MODEL_LOCK:
         tracker = trackerClass(camera_model=camera_model, show_3D_points=False, results_path=results_path)
         set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
+        set_cross_check(tracker, cross_check)             # (likewise: it runs the matchers' crossCheck)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1164,7 +1218,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
-                results_path="~/temp", thread_name="", frame_window=None, detection_method=None):
+                results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1185,11 +1239,11 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
     return run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename=est_poses_filename,
                   results_path=results_path, thread_name=thread_name, _live_frames=frames,
                   _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
-                  detection_method=detection_method)
+                  detection_method=detection_method, cross_check=cross_check)
 
 
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
-                   thread_name="LIVE", frame_window=None, detection_method=None):
+                   thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1207,7 +1261,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
             time.sleep(0.001)   # (the reference starts tracking at once and stops if no frame has arrived yet)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, cam_working_thread=cam_working_thread,
                   est_poses_filename=est_poses_filename, results_path=scene_path_vo_results, thread_name=thread_name,
-                  frame_window=frame_window, detection_method=detection_method)
+                  frame_window=frame_window, detection_method=detection_method, cross_check=cross_check)
     result, failure = {}, []
     try:
         if use_multithreads_for_VO:
@@ -1232,7 +1286,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
 
 def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filename_template, depth_filename_template,
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
-              last_image_index=-1, thread_name="", frame_window=None, detection_method=None):
+              last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1256,7 +1310,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
                   est_poses_filename=est_poses_filename, img_filename_template=scene_img_filename_template,
                   depth_filename_template=depth_filename_template, img_indices=vo_frame_indices,
                   results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window,
-                  detection_method=detection_method)
+                  detection_method=detection_method, cross_check=cross_check)
     result = {}
     if use_multithreads_for_VO:
         # one libsosvo context per host thread: the worker creates its own
@@ -1289,7 +1343,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
-                _keyframe_thresholds=None):
+                _keyframe_thresholds=None, cross_check=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1381,7 +1435,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
                 return
             i, q = job
             try:
-                out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method,
+                out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method, cross_check=cross_check,
                              _keyframe_thresholds=_keyframe_thresholds, _engine_for=engine_for_lane(s), **q)
                 if "sequence_mode" in out:
                     out["sequence_mode"].update(lane=s, lanes=S)
@@ -1413,7 +1467,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 
 
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
-                   frame_window=None, detection_method=None, lanes=None, shard=None):
+                   frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1433,6 +1487,6 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
                               img_indices=list(range(first_image_index, last, step_for_scene_images)),
                               results_path=sc["scene_path_vo_results"], thread_name=sc.get("thread_name", "")))
     results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window,
-                          detection_method=detection_method, lanes=lanes, shard=shard)
+                          detection_method=detection_method, lanes=lanes, shard=shard, cross_check=cross_check)
     print("Done with VO for %d sequences!" % len(results))
     return results

@@ -32,12 +32,16 @@ class RigConfig(object):
 
 class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
-                 adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P"):
+                 adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
+                 cross_check_f2f=False):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
-        uses, pose_est_tools.py:696); "P3P" = the three solve points of a sample from one mirror (BASELINE config 2)."""
+        uses, pose_est_tools.py:696); "P3P" = the three solve points of a sample from one mirror (BASELINE config 2).
+        cross_check_stereo / cross_check_f2f: mutual matches only (cv2.BFMatcher's crossCheck, camera_models.py:401) in
+        the static-stereo matcher / the frame-to-frame matcher."""
         assert isinstance(ctx, Context)
+        self.cross_check_stereo, self.cross_check_f2f = bool(cross_check_stereo), bool(cross_check_f2f)
         self.ctx, self.rig_cfg, self.rig = ctx, rig, rig.as_struct()
         self.front_end = front_end
         if front_end is not None:
@@ -63,6 +67,7 @@ class FramePairPipeline(object):
             self.desc_top, self.desc_bot = z((P, bucket_cap, 32), torch.uint8), z((P, bucket_cap, 32), torch.uint8)
             self.n_top, self.n_bot = z((P,), torch.int32), z((P,), torch.int32)
         self.s_keys, self.s_order = z((P, bucket_cap, 1), torch.uint32), z((P, bucket_cap), torch.int32)
+        self.s_keys_rev = z((P, bucket_cap, 1), torch.uint32) if self.cross_check_stereo else None
         Fc, Cc = self.frame_cap, self.corr_cap
         # descriptors and counts of both views back to back (view-major): the two frame-to-frame matchings of a step
         # (top with top, bottom with bottom) are ONE launch of 2B problems, and so are the two sorts
@@ -77,7 +82,13 @@ class FramePairPipeline(object):
         self.cur_frame = torch.arange(1, self.F, 2, dtype=torch.int32, device=dev)
         self._q2 = torch.cat([self.cur_frame, self.cur_frame + self.F])   # problem i: top view, B + i: bottom view
         self._t2 = torch.cat([self.ref_frame, self.ref_frame + self.F])
-        self._k2, self._o2 = z((2 * self.B, Fc, 1), torch.uint32), z((2 * self.B, Fc), torch.int32)
+        self._o2 = z((2 * self.B, Fc), torch.int32)
+        if self.cross_check_f2f:   # the 2B role-swapped problems ride in the same launch, after the 2B forward ones
+            self._q4, self._t4 = torch.cat([self._q2, self._t2]), torch.cat([self._t2, self._q2])
+            self._k4 = z((4 * self.B, Fc, 1), torch.uint32)
+            self._k2 = self._k4[: 2 * self.B]
+        else:
+            self._k2 = z((2 * self.B, Fc, 1), torch.uint32)
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
         self.o_top, self.o_bot = self._o2[: self.B], self._o2[self.B:]
         self.corr = dict(f=z((self.B, Cc, 3), torch.float64), p=z((self.B, Cc, 3), torch.float64),
@@ -102,6 +113,9 @@ class FramePairPipeline(object):
     def stereo(self):
         c = self.ctx
         c.match_hamming(self.desc_bot, self.desc_top, self.n_bot, self.n_top, k=1, keys=self.s_keys)
+        if self.cross_check_stereo:
+            c.match_hamming(self.desc_top, self.desc_bot, self.n_top, self.n_bot, k=1, keys=self.s_keys_rev)
+            c.cross_check_matches(self.s_keys, self.s_keys_rev, self.n_bot, self.n_top, keys_out=self.s_keys)
         c.sort_matches(self.s_keys, self.n_bot, order=self.s_order)
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
                           self.s_keys, self.s_order, self.F, self.NM, self.frame_cap, out=self.frames)
@@ -110,7 +124,11 @@ class FramePairPipeline(object):
         c, fr = self.ctx, self.frames
         self._M2[1].copy_(self._M2[0])                      # the bottom view's blocks have the same counts
         d2, M2 = self._d2.view(2 * self.F, self.frame_cap, 32), self._M2.view(2 * self.F)
-        c.match_hamming(d2, d2, M2, M2, k=1, keys=self._k2, q_slot=self._q2, t_slot=self._t2)   # both views, 2B problems
+        if self.cross_check_f2f:
+            c.match_hamming(d2, d2, M2, M2, k=1, keys=self._k4, q_slot=self._q4, t_slot=self._t4)
+            c.cross_check_matches(self._k2, self._k4[2 * self.B:], M2, M2, q_slot=self._q2, t_slot=self._t2, keys_out=self._k2)
+        else:
+            c.match_hamming(d2, d2, M2, M2, k=1, keys=self._k2, q_slot=self._q2, t_slot=self._t2)   # both views, 2B problems
         c.sort_matches(self._k2, M2, order=self._o2, q_slot=self._q2)
         c.f2f_assemble(self.rig, fr, self.ref_frame, self.cur_frame, self.k_top, self.o_top, self.k_bot, self.o_bot,
                        self.corr_cap, out=self.corr)
@@ -159,7 +177,8 @@ class OverlappedFramePairs(object):
 
     def __init__(self, device, gums, omni_shape, rig, n_pairs, n_streams=2, num_of_features=1000, kp_cap=512,
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
-                 serialize_medians=True, ransac_solver="P3P", median_win_size=11):
+                 serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
+                 cross_check_f2f=False):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray."""
         from .frontend import DeviceImageModel, ImageFrontEnd
@@ -187,7 +206,8 @@ class OverlappedFramePairs(object):
                                      median_win_size=median_win_size)
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
-                                           ransac_solver=ransac_solver)
+                                           ransac_solver=ransac_solver, cross_check_stereo=cross_check_stereo,
+                                           cross_check_f2f=cross_check_f2f)
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -316,7 +336,7 @@ class OverlappedFramePairs(object):
 
 
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
-              adaptive, seed, lm_iter, ransac_solver, detection_method):
+              adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
     any ransac_solver but "GP3P" is P3P."""
@@ -335,6 +355,7 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
     c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
+    c.ransac_flags |= _lib.cross_check_flags(cross_check_stereo, cross_check_f2f)
     return c
 
 
@@ -344,14 +365,15 @@ class FramePairBatch(object):
 
     def __init__(self, ctx, model, rig, n_pairs, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
-                 n_streams=1, ransac_solver="P3P", detection_method="GFT"):
+                 n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap)."""
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         self.cfg = c = batch_cfg(model, self.B, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                                 thr, max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method)
+                                 thr, max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo,
+                                 cross_check_f2f)
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -479,12 +501,14 @@ class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
     def __init__(self, ctx, model, rig, frames, slots, gather, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                 min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method):
+                 min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method, cross_check_stereo=False,
+                 cross_check_f2f=False):
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
         self.cfg = batch_cfg(model, frames, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                             thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method)
+                             thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method, cross_check_stereo,
+                             cross_check_f2f)
         self.method = str(detection_method).upper()
         if str(ransac_solver).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -506,13 +530,15 @@ class _RGBDFamily(_SequenceFamily):
     shared = ("ctx", "cfg", "method", "workspace", "cam_cfg", "cam", "mask_bits", "pattern")
 
     def __init__(self, ctx, cam, _rig, frames, slots, gather, image_shape, num_of_features, kp_cap, frame_cap, median_win_size,
-                 quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask, pose_est_algorithm, detection_method):
+                 quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask, pose_est_algorithm, detection_method,
+                 cross_check=False):
         from . import orb_pattern
         assert isinstance(ctx, Context)
         self.cam_cfg, self.cam = cam, cam.as_struct()
         self.heads = (self.cam,)
         self.cfg = c = rgbd_batch_cfg(cam, frames, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method)
+                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method,
+                                      cross_check)
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
@@ -777,13 +803,15 @@ class SequenceEngine(_SequenceBase):
 
     def __init__(self, ctx, model, rig, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 ransac_solver="GP3P", detection_method="GFT"):
+                 ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
-        detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch."""
+        detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
+        cross_check_stereo / cross_check_f2f: mutual matches only in the static-stereo / the frame-to-frame matcher."""
         self._init_windows(window)
         self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, num_of_features, kp_cap, frame_cap, median_win_size,
-                                quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method))
+                                quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method,
+                                cross_check_stereo, cross_check_f2f))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -905,8 +933,9 @@ class RGBDPairPipeline(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False):
         """detection_method: "GFT", "ORB", "FAST" or "AGAST" (RGBDFrontEnd).
+        cross_check: mutual matches only (cv2.BFMatcher's crossCheck, camera_models.py:401) in feature_matcher_for_motion.
         pose_est_algorithm: TrackerSE3.pose_est_algorithm (pose_est_tools.py:697): "EPNP" = 6-point samples solved by
         EPnP; "KNEIP" = P3P on 3 points + a 4th for disambiguation; "GAO" / "GP3P" = the depth formulation through the
         generalised solver; "TWOPT" = translation from 2 points.  Anything else raises ValueError."""
@@ -926,6 +955,11 @@ class RGBDPairPipeline(object):
         self.ref_frame = torch.arange(0, F, 2, dtype=torch.int32, device=dev)
         self.cur_frame = torch.arange(1, F, 2, dtype=torch.int32, device=dev)
         self.keys, self.order = z((B, Fc, 1), torch.uint32), z((B, Fc), torch.int32)
+        self.cross_check = bool(cross_check)
+        if self.cross_check:   # the B role-swapped problems ride in the same launch, after the forward ones
+            self._q2, self._t2 = torch.cat([self.cur_frame, self.ref_frame]), torch.cat([self.ref_frame, self.cur_frame])
+            self._k2 = z((2 * B, Fc, 1), torch.uint32)
+            self.keys = self._k2[:B]
         self.corr = dict(f=z((B, Fc, 3), torch.float64), p=z((B, Fc, 3), torch.float64), q=z((B, Fc), torch.int32),
                          t=z((B, Fc), torch.int32), n=z((B,), torch.int32))
         self.ransac = dict(T=z((B, 3, 4), torch.float64), mask=z((B, Fc), torch.uint8), idx=z((B, Fc), torch.int32),
@@ -941,8 +975,13 @@ class RGBDPairPipeline(object):
 
     def track(self):
         c, fr, cfg = self.ctx, self.frames, self.cam_cfg
-        c.match_hamming(fr["d"], fr["d"], fr["M"], fr["M"], k=1, keys=self.keys, q_slot=self.cur_frame,
-                        t_slot=self.ref_frame)
+        if self.cross_check:
+            c.match_hamming(fr["d"], fr["d"], fr["M"], fr["M"], k=1, keys=self._k2, q_slot=self._q2, t_slot=self._t2)
+            c.cross_check_matches(self.keys, self._k2[self.B:], fr["M"], fr["M"], q_slot=self.cur_frame, t_slot=self.ref_frame,
+                                  keys_out=self.keys)
+        else:
+            c.match_hamming(fr["d"], fr["d"], fr["M"], fr["M"], k=1, keys=self.keys, q_slot=self.cur_frame,
+                            t_slot=self.ref_frame)
         c.sort_matches(self.keys, fr["M"], order=self.order, q_slot=self.cur_frame)
         c.f2f_assemble_central(fr, self.ref_frame, self.cur_frame, self.keys, self.order, self.frame_cap,
                                pct_good_matches=cfg.pct_good_matches, max_hdiff=cfg.f2f_max_hdiff, out=self.corr)
@@ -972,7 +1011,7 @@ class RGBDPairPipeline(object):
 
 
 def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                   thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method):
+                   thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check=False):
     """The `sosvo_rgbd_batch_cfg` of RGBDPairBatch and RGBDSequenceEngine (n_pairs: pairs per call / slot pairs per tracking
     call; cam: an RGBDCamConfig).  kp_cap None or 0 = rgbd_kp_cap; frame_cap None or 0 = kp_cap; thr None = the trackers'
     5-degree threshold."""
@@ -985,7 +1024,7 @@ def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap
     c.kp_cap, c.frame_cap = kp_cap, int(frame_cap) if frame_cap else kp_cap
     c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
     c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
+    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags | _lib.cross_check_flags(f2f=cross_check)
     c.quality, c.min_distance = float(quality), float(min_distance)
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
@@ -999,12 +1038,12 @@ class RGBDPairBatch(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False):
         from . import orb_pattern
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         c = rgbd_batch_cfg(cam, self.B, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
-                           edge, thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method)
+                           edge, thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check)
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         self.cfg, self.thr = c, c.ransac_threshold
@@ -1042,11 +1081,11 @@ class RGBDSequenceEngine(_SequenceBase):
 
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False):
         self._init_windows(window)
         self._adopt(_RGBDFamily(ctx, cam, None, self.W, self.slots, False, image_shape, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method))
+                                pose_est_algorithm, detection_method, cross_check))
 
 
 # ---- several sequences ("lanes") through one engine ----------------------------------------------------------------------
@@ -1372,11 +1411,11 @@ class MultiSequenceEngine(_MultiSequenceBase):
 
     def __init__(self, ctx, model, rig, lanes=2, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 ransac_solver="GP3P", detection_method="GFT"):
+                 ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False):
         self._init_lanes(lanes, window)
         self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver,
-                                detection_method))
+                                detection_method, cross_check_stereo, cross_check_f2f))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
@@ -1385,8 +1424,8 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
 
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
-                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT"):
+                 mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False):
         self._init_lanes(lanes, window)
         self._adopt(_RGBDFamily(ctx, cam, None, self.window, self.slots, True, image_shape, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method))
+                                pose_est_algorithm, detection_method, cross_check))
