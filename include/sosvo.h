@@ -175,8 +175,10 @@ int32_t sosvo_gray_rows_needed(sosvo_ctx* ctx, const uint32_t* mask_bits, int32_
  * the threshold is positive wherever the mask's maximum is; a mask whose maximum is <= 0 has no corners).
  *   kp [nimg*nmask, cap, 2] f32 (x, y) in acceptance order, n [nimg*nmask] i32,
  *   status [nimg*nmask] i32 (optional): bit 0 = more candidates than the selection keeps (4096; 16384 when
- *   cap > 1024: the large-mask variant for whole-image detection, e.g. the RGB-D frames) -- the result then
- *   depends on which were kept; bit 1 = mask too large for the on-chip grid (3584 / 15872 cells of
+ *   cap > 1024: the large-mask variant for whole-image detection, e.g. the RGB-D frames) -- the result is then
+ *   goodFeaturesToTrack on the CAND strongest candidates, a prefix of the full result (CAND = 4096 or 16384, a function
+ *   of cap alone; the strongest in the order of the sort: descending response, higher address first among equal
+ *   responses; when max_corners or cap is reached inside them the result is the full one); bit 1 = mask too large for the on-chip grid (3584 / 15872 cells of
  *   minDistance^2 pixels) and more than 1024 corners wanted, or more than 1024 corners were the THIRD of their grid
  *   cell (possible from minDistance ~30 px on; up to 1024 of them are kept exactly in an overflow list). */
 int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask_bits, int32_t nimg,

@@ -406,17 +406,29 @@ def min_eigen(gray):
     return eig
 
 
-def gft_select(eig, mask_bits, which, quality=0.01, min_distance=5.0, max_corners=1000):
+def gft_cand_cap(kp_cap):
+    """The number of candidates the GPU selection sorts for a keypoint capacity: the cand_cap of gft_select that a
+    detect_gft call (or an engine) with that capacity implies."""
+    return 4096 if kp_cap <= 1024 else 16384
+
+
+def gft_select(eig, mask_bits, which, quality=0.01, min_distance=5.0, max_corners=1000, cand_cap=0, with_count=False):
+    """goodFeaturesToTrack's selection for mask `which` -> (kp [n,2] float32, maximum response).  cand_cap > 0: only the
+    cand_cap strongest candidates (descending response, higher address first) enter the greedy pass; <= 0: all of them.
+    with_count: a third value, the number of candidates before that cut."""
     eig = _c(eig, np.float32)
     mask_bits = _c(mask_bits, np.uint32)
     rows, cols = eig.shape
     kp = np.zeros((rows * cols, 2), dtype=np.float32)
     maxv = ctypes.c_float(0)
+    ncand = ctypes.c_int32(0)
     L = lib()
     L.orc_gft_select.restype = ctypes.c_int32
     n = L.orc_gft_select(_p(eig), _p(mask_bits), ctypes.c_int32(which), ctypes.c_int32(rows), ctypes.c_int32(cols),
                          ctypes.c_double(quality), ctypes.c_double(min_distance), ctypes.c_int32(max_corners), _p(kp),
-                         ctypes.byref(maxv))
+                         ctypes.byref(maxv), ctypes.c_int32(int(cand_cap)), ctypes.byref(ncand))
+    if with_count:
+        return kp[:n].copy(), maxv.value, ncand.value
     return kp[:n].copy(), maxv.value
 
 

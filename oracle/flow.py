@@ -59,7 +59,8 @@ def detect_view(im, omni, view):
         return kps, descs, pano, gray
     eig = oracle.min_eigen(gray)
     for m in range(im.nmask):                                                         # :1730
-        kp, _ = oracle.gft_select(eig, im.mask_bits[view], m, im.quality, im.min_distance, im.max_corners)  # :1739
+        kp, _ = oracle.gft_select(eig, im.mask_bits[view], m, im.quality, im.min_distance, im.max_corners,
+                                  cand_cap=oracle.gft_cand_cap(im.kp_cap))  # :1739 (the GPU selection's candidate limit)
         kp = kp[: im.kp_cap]                     # the selection stops at the capacity: its first kp_cap acceptances
         d, kept = oracle.orb_describe(blurred, kp, im.cos_a, im.sin_a, im.pattern, im.edge)                 # :1765
         kps.append(kp[kept])
@@ -72,7 +73,7 @@ def rgbd_frame(cam, bgr, depth, max_corners, pattern, cos_a, sin_a, median_ksize
     """RGBDFrame.establish_keypoints (pose_est_tools.py:600-623) with the GFT, ORB, FAST or AGAST detector (:477-516, :544,
     :547) and ORB descriptors (:553) on the oracle -> dict(m [M,2] f32, d [M,32] u8, X [M,3], b [M,3], n_kp).  kp_cap: the
     keypoint capacity per frame of the GPU front end (None: no cut for GFT / FAST / AGAST; ORB needs it, as its retainBest
-    is cut inside the detector)."""
+    is cut inside the detector).  With GFT it also implies the candidate limit of the GPU selection (oracle.gft_cand_cap)."""
     method = method.upper()
     gray = oracle.median_gray(bgr, median_ksize)                                     # :528, :531
     mb = np.ones(gray.shape, np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32)
@@ -84,7 +85,8 @@ def rgbd_frame(cam, bgr, depth, max_corners, pattern, cos_a, sin_a, median_ksize
         if method in ("FAST", "AGAST"):                                              # :506-509
             kp = (fast_keypoints if method == "FAST" else agast_keypoints)(gray, mb, 0)
         else:
-            kp, _ = oracle.gft_select(oracle.min_eigen(gray), mb, 0, quality, min_distance, max_corners)   # :544
+            kp, _ = oracle.gft_select(oracle.min_eigen(gray), mb, 0, quality, min_distance, max_corners,   # :544
+                                      cand_cap=oracle.gft_cand_cap(kp_cap) if kp_cap else 0)
         kp = kp[:kp_cap]
         d, kept = oracle.orb_describe(oracle.gauss7(gray), kp, cos_a, sin_a, pattern, edge)            # :553
         kp = kp[kept]

@@ -174,7 +174,11 @@ void orc_min_eigen(const uint8_t* gray, int32_t rows, int32_t cols, float* eig) 
 
 /* ---- K4b: goodFeaturesToTrack selection for one mask ---------------------------------------------
  * Bit `which` of mask_bits[y*cols+x] set = the pixel belongs to this mask (masks may overlap).  Returns the number of
- * corners written to kp_xy (x, y as float, in acceptance order = descending quality). */
+ * corners written to kp_xy (x, y as float, in acceptance order = descending quality).
+ * cand_cap > 0: only the cand_cap strongest candidates (the head of the sorted list: descending response, higher address
+ * first among equal ones) enter the greedy pass -- the rule of the GPU selection, which sorts 4096 or 16384 candidates;
+ * the result is then a prefix of the unlimited one.  cand_cap <= 0: no limit.  n_cand_out (may be NULL): the number of
+ * candidates before that cut. */
 typedef struct {
   float v;
   int32_t idx;
@@ -190,7 +194,7 @@ static int cand_cmp(const void* pa, const void* pb) {
 
 int32_t orc_gft_select(const float* eig, const uint32_t* mask_bits, int32_t which, int32_t rows, int32_t cols,
                        double quality, double min_distance, int32_t max_corners, float* kp_xy,
-                       float* max_val_out) {
+                       float* max_val_out, int32_t cand_cap, int32_t* n_cand_out) {
   float maxv = -INFINITY;
   int any = 0;
   for (int64_t i = 0; i < (int64_t)rows * cols; ++i)
@@ -199,6 +203,7 @@ int32_t orc_gft_select(const float* eig, const uint32_t* mask_bits, int32_t whic
       any = 1;
     }
   if (max_val_out) *max_val_out = any ? maxv : 0.0f;
+  if (n_cand_out) *n_cand_out = 0;
   if (!any) return 0;
   const float thr = (float)((double)maxv * quality); /* threshold(eig, maxVal * qualityLevel, THRESH_TOZERO) */
   cand_t* cand = (cand_t*)malloc(sizeof(cand_t) * (size_t)rows * cols);
@@ -223,6 +228,8 @@ int32_t orc_gft_select(const float* eig, const uint32_t* mask_bits, int32_t whic
       }
     }
   qsort(cand, (size_t)nc, sizeof(cand_t), cand_cmp);
+  if (n_cand_out) *n_cand_out = nc;
+  if (cand_cap > 0 && nc > cand_cap) nc = cand_cap;
   int ncorners = 0;
   if (min_distance >= 1) {
     const int cell = (int)lrint(min_distance);

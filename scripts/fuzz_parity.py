@@ -8,7 +8,8 @@ problem counts, empty masks, fractional minimum distances, budgets that end a se
 descriptors, ...) from a generator seeded by (--seed, case number), runs the HIP stage through the C ABI and compares the
 result with the oracle's bit for bit.  The first mismatch stops the run and prints the stage, the case number and the drawn
 parameters: `--stages <stage> --first-case <n> --cases 1` with the same seed replays it.  Prints a progress line every ~20 s.
-A case that only trips a documented capacity (status flags, a frame_cap cut) counts as `flagged`, not as a mismatch.  A
+A case that only trips a documented capacity (status flags, a frame_cap cut) counts as `flagged`, not as a mismatch -- except
+GFT's candidate limit (status bit 0 of sosvo_detect_gft), whose result is defined: such a case is compared like any other.  A
 draw the entry point refuses, or a stage that ends short of --cases (or with no case at all) when time runs out, makes the
 run end INCOMPLETE with exit status 2: only a run in which every stage completed its cases ends "all identical".
 """
@@ -115,11 +116,15 @@ def fuzz_gft(ctx, rng):
     for i in range(ni):
         eig = oracle.min_eigen(imgs[i])
         for m in range(nmask):
-            want, _ = oracle.gft_select(eig, bits[0], m, q, md, mc)
+            # (more candidates than the selection sorts -- status bit 0 -- is a defined result: the CAND strongest are kept)
+            cand_cap = oracle.gft_cand_cap(cap)
+            want, _, count = oracle.gft_select(eig, bits[0], m, q, md, mc, cand_cap=cand_cap, with_count=True)
             p = i * nmask + m
-            if status[p]:
+            if status[p] & 2:     # the mask's cell grid does not fit on chip: at most 1024 corners (sosvo.h)
                 flagged = True
                 continue
+            if status[p] != (1 if count > cand_cap else 0):
+                return params, "image %d mask %d: status %d with %d candidates" % (i, m, status[p], count)
             want = want[:cap]
             if n[p] != len(want) or not np.array_equal(kp[p, :n[p]], want):
                 return params, "image %d mask %d: %d corners, oracle %d" % (i, m, n[p], len(want))
@@ -592,7 +597,8 @@ BATCH_AZIMUTHS = (120.0, 45.0, 30.0, 15.0, 11.25)     # 3, 8, 12, 24, 32 azimuth
 def draw_batch(rng):
     """The parameters of one `batch` case (no GPU): a legal sosvo_batch_cfg for every detector.  GFT keeps at most 1024
     corners wanted (max_corners <= 1000) and minimum distances below the ~30 px at which the third-of-a-cell overflow list
-    can fill, so its only documented overflow is the candidate budget (status bit 0)."""
+    can fill, so its only documented overflow is the candidate limit (status bit 0: the strongest candidates are kept, which
+    the oracle's flow restates)."""
     det = str(rng.choice(DETECTORS))
     d = dict(detector=det, median=int(rng.choice(MEDIANS)), width=int(rng.choice(BATCH_WIDTHS)),
              azimuth=float(rng.choice(BATCH_AZIMUTHS)), n_pairs=int(rng.integers(1, 6)),
@@ -731,8 +737,9 @@ def fuzz_batch(ctx, rng):
         frames = []
         for f in (2 * i, 2 * i + 1):
             imgs = (f, F + f)     # view-major images: top mirror of frame f, bottom mirror of frame f
-            if d["detector"] == "GFT" and status[list(imgs)].any():
-                skip = True       # the candidate budget overflowed (status bit 0): which candidates were kept is not defined
+            if d["detector"] == "GFT" and (status[list(imgs)] & 2).any():
+                skip = True       # a mask's cell grid does not fit on chip (status bit 1); bit 0 alone is a defined result:
+                                  # the strongest candidates are kept, and flow.detect_view cuts its list the same way
             if d["detector"] == "AGAST":
                 for v, img in enumerate(imgs):
                     pano = oracle.unwrap(omni[f], om[v], mx[v], my[v])
@@ -838,8 +845,9 @@ def fuzz_rgbd(ctx, rng):
     for i in range(B):
         skip = False
         for f in (2 * i, 2 * i + 1):
-            if det == "GFT" and w["status"][f]:
-                skip = True       # the candidate budget overflowed (status bit 0): which candidates were kept is not defined
+            if det == "GFT" and w["status"][f] & 2:
+                skip = True       # the cell grid does not fit on chip (status bit 1); bit 0 alone is a defined result: the
+                                  # strongest candidates are kept, and flow.rgbd_frame cuts its list the same way
             if det == "AGAST":
                 over = int((oracle.fast_score_map(oracle.median_gray(bgr[f], ksize), 10) > 0).sum()) > 16384
                 if bool(w["status"][f] & 2) != over:

@@ -365,3 +365,47 @@ def test_run_vo_after_an_aborted_run_on_the_same_camera_model(ctx, tmp_path, kin
     fresh, files_fresh = run(make(), seq_b, n_b, str(tmp_path / "res_fresh"), 4)
     assert b["tracked"] == fresh["tracked"] >= 5
     assert files_b == files_fresh
+
+
+def test_rgbd_front_end_at_a_small_keypoint_capacity_depends_on_the_frames_only(ctx):
+    """The RGB-D sequence front end on three rendered 480 x 640 frames, 300 features, kp_cap 320: up to 1024 the whole-image
+    GFT selection keeps 4096 candidates and these frames have more, so the records used to depend on which waves claimed
+    the slots first (the same call twice differed in 7 to 48 KB of its workspace).  With the rule "the 4096 strongest" the
+    call run twice on zero-filled workspaces leaves the SAME workspace, byte for byte -- counts, keypoints, descriptors,
+    points, bearings -- and counts and tracking records equal the oracle's flow with the candidate limit that kp_cap implies."""
+    import refflow
+    import torch
+    import oracle
+    from test_gpu_sequence_forms import _RGBD, SHAPE
+    from vo_single_camera_sos_amd import orb_pattern
+    f = _RGBD(ctx, **SHAPE)
+    cfg, cam = f.eng.cfg, f.eng.cam_cfg
+    assert cfg.kp_cap == 320 and cfg.max_corners == 300 and cfg.median_ksize == 0
+    bgr, depth = (x[:3].cpu().numpy() for x in f.images)
+    counts_cand = [oracle.gft_select(oracle.min_eigen(oracle.median_gray(im, 0)), np.ones(im.shape[:2], np.uint32), 0, cfg.quality,
+                                     cfg.min_distance, 300, with_count=True)[2] for im in bgr]
+    assert max(counts_cand) > 4096, counts_cand                                   # the regime this test is about
+    A, B = torch.zeros_like(f.eng.workspace), torch.zeros_like(f.eng.workspace)
+    f.front_end(A, 5)
+    ctx.synchronize()
+    ctx.debug_fill_scratch(0xFF)
+    f.front_end(B, 5)
+    ctx.synchronize()
+    counts = f.counts(A)
+    assert counts == f.counts(B) and min(counts[5:8]) > 100
+    assert torch.equal(A, B)
+    # once against the oracle: valid-depth counts per frame, tracking records of (5, 6), (6, 7), (5, 7)
+    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    rc = refflow.RGBDParams(cam.fx, cam.fy, cam.center_x, cam.center_y, cam.focal_length_m, cam.depth_is_Z, cam.min_range,
+                            cam.max_range, cam.f2f_max_hdiff, cam.pct_good_matches)
+    frames = [refflow.rgbd_frame(rc, bgr[k], depth[k], 300, orb_pattern.orb_pattern(), ca, sa, kp_cap=320) for k in range(3)]
+    assert counts[5:8] == [len(fr["X"]) for fr in frames]
+    out = torch.zeros((18, 16), dtype=torch.float64, device=ctx.device)
+    f.track(A, [5, 6, 5], [6, 7, 7], 11, out)
+    rec = out[:3].cpu().numpy()
+    for i, (r, c) in enumerate(((0, 1), (1, 2), (0, 2))):
+        w = refflow.track_pair_rgbd(rc, frames[r], frames[c], cfg.ransac_threshold, cfg.ransac_max_iter, seed=11 + i,
+                                    adaptive=bool(cfg.ransac_adaptive), epnp=True)
+        assert rec[i, 13] == len(w["corr"]["q"]) and rec[i, 12] == w["ransac"]["n_inliers"] > 30, (i, rec[i, 12:])
+        assert rec[i, 14] == w["ransac"]["status"] == 0 and rec[i, 15] == w["ransac"]["best_iter"]
+        assert np.array_equal(rec[i, :12].reshape(3, 4), w["T"]), i

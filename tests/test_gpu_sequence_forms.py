@@ -10,11 +10,12 @@ cfg.n_pairs = 18 and the store has 39 slots; omnistereo: 300 features, kp_cap 32
 the black one), copies to slots 20 and 21.  17 pairs is beyond the 16 that travel as kernel arguments: the lists are copied
 to the device.
 
-The RGB-D family cannot be compared at kp_cap = 320: up to 1024 the GFT detector keeps 4096 candidates, a whole image has
-more, and "the result then depends on which were kept" (include/sosvo.h, sosvo_detect_gft, status bit 0) -- measured: the
-same front-end call twice on zero-filled workspaces differs in 7 to 48 KB of its keypoints and records, on the commit
-before this test as on the one that adds it.  Its cases use the family's default keypoint capacity (1088: the whole-image variant, deterministic),
-once with the 300 features and frame_cap = 1024 of the omni case and once with 1000 features.
+The RGB-D family runs at kp_cap = 320 too: up to 1024 the GFT detector keeps 4096 candidates and a whole image has more,
+but the kept ones are the 4096 strongest (include/sosvo.h, sosvo_detect_gft, status bit 0), so the records are a function
+of the image there as well.  (Before that rule the slots went to whichever waves came first, and the same front-end call
+twice on zero-filled workspaces differed in 7 to 48 KB of its keypoints and records.)  Its other cases use the family's
+default keypoint capacity (1088: the whole-image variant), once with the 300 features and frame_cap = 1024 of the omni
+case and once with 1000 features.
 
 Sizes of the records.  The copy kernel's grid takes 4 x 256 eight-byte words of a field in one pass.  The omni records
 here hold 767, 733 and 733 entries: more than one chunk of 256 in every field, and three passes of the stride loop in the
@@ -128,7 +129,7 @@ class _RGBD(object):
 
 
 @pytest.mark.parametrize("family,shape,beyond_a_chunk", [(_Omni, SHAPE, True), (_RGBD, dict(SHAPE, kp_cap=None), False),
-                                                         (_RGBD, dict(num_of_features=1000), True)])
+                                                         (_RGBD, dict(num_of_features=1000), True), (_RGBD, SHAPE, False)])
 def test_single_and_list_forms_are_one_operation(ctx, family, shape, beyond_a_chunk):
     f = family(ctx, **shape)
     assert f.eng.cfg.n_pairs == 18 and f.eng.slots == 39

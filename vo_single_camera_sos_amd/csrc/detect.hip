@@ -341,6 +341,107 @@ __device__ __forceinline__ uint32_t dist2_packed(uint32_t a, uint32_t b) {
   return (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);
 }
 
+// The candidate regions of one problem (what phase 1 of gft_select_kernel walks), for the overflow path below.
+struct gft_regions {
+  const uint2* cand;
+  const uint32_t* wcnt;
+  const uint32_t* mb;
+  int img, m, strips, nchunks, wcap, s0, c0, ns, R;
+  float thr;
+};
+
+// Every sort key of the problem (the records of this mask above the threshold), one call of f per key and lane, the
+// regions NT at a time as in phase 1.  Ends with a barrier.
+template <int NT, class F>
+__device__ __forceinline__ void gft_walk_keys(const gft_regions& g, int* s_region, int tid, F&& f) {
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  for (int rb = 0; rb < g.R; rb += NT) {
+    if (rb + tid < g.R) {
+      const int rg = rb + tid, c = g.c0 + rg / g.ns, sidx = g.s0 + rg % g.ns;
+      s_region[tid] = min((int)g.wcnt[(g.img * g.nchunks + c) * g.strips + sidx], g.wcap);
+    }
+    __syncthreads();
+    const int rend = min(NT, g.R - rb);
+    for (int rr = wave; rr < rend; rr += NT / 64) {
+      const int have = s_region[rr];
+      const int rg = rb + rr, c = g.c0 + rg / g.ns, sidx = g.s0 + rg % g.ns;
+      const uint2* region = g.cand + (size_t)((g.img * g.nchunks + c) * g.strips + sidx) * g.wcap;
+      for (int i = lane; i < have; i += 64) {
+        const uint2 r = region[i];
+        if (__uint_as_float(r.x) > g.thr && ((g.mb[r.y] >> g.m) & 1u))
+          f(((unsigned long long)sosvo_float_ordered(__uint_as_float(r.x)) << 32) | r.y);
+      }
+    }
+    __syncthreads();  // s_region is rewritten by the next tile
+  }
+}
+
+// More candidates than the selection sorts (total > CAND, uniform): the kept set is the CAND LARGEST keys.  The keys
+// (ordered response << 32 | pixel) are unique, so that set -- and with it kp, n and their order -- depends on the image, the
+// mask and the parameters only, and the greedy pass on it gives a prefix of the unlimited result.  A radix select finds the
+// CAND-th largest key: one more walk over the regions per 11-bit digit with a histogram in the key LDS (which holds
+// nothing worth keeping at this point), from the top digit down, until every key left under the digits found so far is
+// kept -- three walks when the responses around the cut differ, up to six when the cut lies inside a run of equal responses
+// and the address decides.  A last walk gathers the keys >= that cutoff (in any order: the sort follows).  Inlined
+// into the one uniform branch that calls it (as a call it raised the kernel's register count from 34 to 72-84 and cost the
+// 256-thread variant three of its eight waves per SIMD; inlined the count is 42 and the occupancy unchanged), and that
+// branch is marked unlikely so that its code lies behind the usual path, not in the middle of it.
+template <int CAND, int NT>
+__device__ __forceinline__ void gft_keep_largest(const gft_regions g, unsigned long long* keys, int* s_region, int* s_count,
+                                              int* s_sel, int tid) {
+  constexpr int kBits = 11, kBins = 1 << kBits, kPer = kBins / 64;
+  static_assert(kBins * sizeof(uint32_t) <= CAND * sizeof(unsigned long long), "the histogram lives in the key LDS");
+  uint32_t* hist = reinterpret_cast<uint32_t*>(keys);
+  unsigned long long prefix = 0ULL;  // the digits of the cutoff found so far, in place
+  int want = CAND;                   // rank of the cutoff among the keys that share those digits
+  for (int shift = 64; shift > 0;) {
+    const int width = min(kBits, shift);
+    const unsigned long long high = shift < 64 ? ~0ULL << shift : 0ULL;
+    shift -= width;
+    for (int i = tid; i < kBins; i += NT) hist[i] = 0u;
+    __syncthreads();
+    gft_walk_keys<NT>(g, s_region, tid, [&](unsigned long long key) {
+      if ((key & high) == prefix) atomicAdd(&hist[(uint32_t)(key >> shift) & ((1u << width) - 1u)], 1u);
+    });
+    if (tid < 64) {  // the digit whose bin holds the rank: lane l sums bins l * kPer .., a suffix sum over the lanes
+      uint32_t sum = 0u;
+      for (int b = 0; b < kPer; ++b) sum += hist[tid * kPer + b];
+      uint32_t incl = sum;  // keys in the bins of this lane and of the higher ones
+      for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_down((int)incl, s);
+        if (tid + s < 64) incl += o;
+      }
+      uint32_t above = incl - sum;
+      if (above < (uint32_t)want && (uint32_t)want <= incl) {  // exactly one lane (want <= the keys under the prefix)
+        for (int b = kPer - 1; b >= 0; --b) {
+          const uint32_t c = hist[tid * kPer + b];
+          if (above + c >= (uint32_t)want) {
+            s_sel[0] = tid * kPer + b;
+            s_sel[1] = want - (int)above;
+            s_sel[2] = (int)c;
+            break;
+          }
+          above += c;
+        }
+      }
+    }
+    __syncthreads();
+    prefix |= (unsigned long long)(uint32_t)s_sel[0] << shift;
+    want = s_sel[1];
+    const bool whole_bin = want == s_sel[2];  // uniform: every key under the prefix is kept -- the cutoff is the prefix
+    __syncthreads();                          // (s_sel and the histogram are rewritten by the next digit)
+    if (whole_bin) break;
+  }
+  if (tid == 0) *s_count = 0;
+  __syncthreads();
+  gft_walk_keys<NT>(g, s_region, tid, [&](unsigned long long key) {
+    if (key >= prefix) {
+      const int slot = atomicAdd(s_count, 1);
+      if (slot < CAND) keys[slot] = key;  // (exactly CAND keys pass)
+    }
+  });
+}
+
 template <int CAND, int NT>
 __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict__ cand,
                                                               const uint32_t* __restrict__ wcnt, int strips, int nchunks,
@@ -363,6 +464,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   __shared__ unsigned long long lds_u64[CAND];
   __shared__ int s_count, s_accepted, s_overflow;
   __shared__ int s_region[NT];  // phase 1: record counts of the regions in flight
+  __shared__ int s_sel[3];      // overflow path: digit, rank inside its bin, size of the bin (gft_keep_largest)
   __shared__ unsigned long long s_conf[64];  // phase 3: conflict rows of the round
   __shared__ unsigned long long s_prior;     // phase 3: candidates of the round that conflict with an earlier round's points
   __shared__ int s_ovf;                      // phase 3: accepted points that found both slots of their grid cell taken
@@ -440,6 +542,14 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
     const bool fits = total <= CAND && (gw_ + 2) * (gh_ + 2) <= kSelGridCells;  // (the bordered grid of phase 3)
     if (tid == 0) redo[p] = fits ? 0 : 1;
     if (!fits) return;
+  }
+  if (__builtin_expect(total > CAND, 0)) {  // uniform, and rare: the slots above went to whichever waves came first -- gather the CAND largest keys
+    const gft_regions g = {cand, wcnt, mask_bits + (size_t)(img / images_per_maskset) * rows * cols, img, m, strips, nchunks, wcap,
+                           bx0 / kEigStripW, by0 / chunk_rows, bx1 / kEigStripW - bx0 / kEigStripW + 1,
+                           (by1 / chunk_rows - by0 / chunk_rows + 1) * (bx1 / kEigStripW - bx0 / kEigStripW + 1),
+                           (float)((double)sosvo_ordered_float(st[0]) * quality)};
+    gft_keep_largest<CAND, NT>(g, keys, s_region, &s_count, s_sel, tid);
+    __syncthreads();
   }
   const int n = min(total, CAND);
   // ---- phase 2: bitonic sort, descending (keys are unique: value, then higher address first) ---------------
