@@ -43,6 +43,10 @@ def main_rgbd_vo(argv=None):
                         help="keypoint detector of the tracker and its frames (GFT: the reference's default)")
     parser.add_argument("--cross_check", action="store_true",
                         help="mutual matches only (cv2.BFMatcher's crossCheck) in the frame-to-frame matcher; default: off")
+    parser.add_argument("--gated_matching", action="store_true",
+                        help="the frame-to-frame matcher searches among the keypoints within the tracker's |du| gate; default: off")
+    parser.add_argument("--gated_max_distance", default=None, type=int,
+                        help="with --gated_matching: a match whose Hamming distance exceeds this (1 .. 256) is no match; default: no cap")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -81,6 +85,7 @@ def main_rgbd_vo(argv=None):
                              first_image_index=args.first_image_index, last_image_index=args.last_image_index,
                              frame_window=None if args.frame_window < 0 else args.frame_window,
                              detection_method=args.detection_method, cross_check=True if args.cross_check else None,
+                             gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
                              lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
@@ -91,7 +96,8 @@ def main_rgbd_vo(argv=None):
                     first_image_index=args.first_image_index, last_image_index=args.last_image_index,
                     thread_name="%s-%s" % (scene_name, "RGB-D"),
                     frame_window=None if args.frame_window < 0 else args.frame_window,
-                    detection_method=args.detection_method, cross_check=True if args.cross_check else None)
+                    detection_method=args.detection_method, cross_check=True if args.cross_check else None,
+                    gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance)
     print("GOODBYE!")
     return out
 

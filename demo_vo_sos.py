@@ -45,6 +45,11 @@ def main_sos_vo(argv=None):
     parser.add_argument("--cross_check", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
                         help="mutual matches only (cv2.BFMatcher's crossCheck): in both matchers when given without a value, "
                              "or in the static-stereo / the frame-to-frame matcher alone; default: off")
+    parser.add_argument("--gated_matching", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
+                        help="the matchers search among the candidates that pass their pixel gates: both matchers when given "
+                             "without a value, or the static-stereo / the frame-to-frame matcher alone; default: off")
+    parser.add_argument("--gated_max_distance", default=None, type=int,
+                        help="with --gated_matching: a match whose Hamming distance exceeds this (1 .. 256) is no match; default: no cap")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -65,11 +70,14 @@ def main_sos_vo(argv=None):
                            thread_name="%s-%s" % (scene_name, "SOS")))
     gums_calibrated = load_gums_json(gums_file)
     cross_check = None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check)
+    gated = dict(gated_matching=None if args.gated_matching is None else (True if args.gated_matching == "both" else args.gated_matching),
+                 gated_max_distance=args.gated_max_distance)
     if len(scenes) > 1:
         out = driver_VO_many(camera_model=gums_calibrated, scenes=scenes, visualize_VO=args.visualize_VO,
                              step_for_scene_images=args.step, first_image_index=args.first_image_index,
                              last_image_index=args.last_image_index, frame_window=None if args.frame_window < 0 else args.frame_window,
-                             detection_method=args.detection_method, cross_check=cross_check, lanes=None if args.lanes < 0 else args.lanes)
+                             detection_method=args.detection_method, cross_check=cross_check,
+                             lanes=None if args.lanes < 0 else args.lanes, **gated)
         print("GOODBYE!")
         return out
     out = driver_VO(camera_model=gums_calibrated, scene_path=scene_path_omni, scene_path_vo_results=results,
@@ -78,7 +86,7 @@ def main_sos_vo(argv=None):
                     step_for_scene_images=args.step, first_image_index=args.first_image_index,
                     last_image_index=args.last_image_index, thread_name="%s-%s" % (scene_name, "SOS"),
                     frame_window=None if args.frame_window < 0 else args.frame_window,
-                    detection_method=args.detection_method, cross_check=cross_check)
+                    detection_method=args.detection_method, cross_check=cross_check, **gated)
     print("GOODBYE!")
     return out
 

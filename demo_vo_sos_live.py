@@ -37,6 +37,11 @@ def main_sos_vo_live(argv=None, frame_source=None):
     parser.add_argument("--cross_check", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
                         help="mutual matches only (cv2.BFMatcher's crossCheck): in both matchers when given without a value, "
                              "or in the static-stereo / the frame-to-frame matcher alone; default: off")
+    parser.add_argument("--gated_matching", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
+                        help="the matchers search among the candidates that pass their pixel gates: both matchers when given "
+                             "without a value, or the static-stereo / the frame-to-frame matcher alone; default: off")
+    parser.add_argument("--gated_max_distance", default=None, type=int,
+                        help="with --gated_matching: a match whose Hamming distance exceeds this (1 .. 256) is no match; default: no cap")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -54,7 +59,9 @@ def main_sos_vo_live(argv=None, frame_source=None):
     out = driver_VO_live(gums_calibrated, results, cam_working_thread, visualize_VO=args.visualize_VO,
                          use_multithreads_for_VO=args.use_multithreads_for_VO, thread_name="LIVE-SOS",
                          frame_window=None if args.frame_window < 0 else args.frame_window,
-                         cross_check=None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check))
+                         cross_check=None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check),
+                         gated_matching=None if args.gated_matching is None else (True if args.gated_matching == "both" else args.gated_matching),
+                         gated_max_distance=args.gated_max_distance)
     print("GOODBYE!")
     return out
 

@@ -284,6 +284,28 @@ int32_t sosvo_match_hamming(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t
                             const int32_t* t_slot, int32_t nprob, int32_t q_stride,
                             int32_t t_stride, int32_t k, uint32_t* keys);
 
+/* The 1-NN search under the pixel gates (guided matching: the search along the epipolar band, where sosvo_match_hamming
+ * searches everywhere and leaves the geometry to the assemble stages).  Blocks, slots, strides and counts as in
+ * sosvo_match_hamming; q_pos [*, q_stride, 2] f32 and t_pos [*, t_stride, 2] f32 (8-byte aligned) hold the pixel (u, v)
+ * of every descriptor row, indexed like the descriptors, finite values.  With the float32 positions converted to double,
+ *   gate(i, j) = (max_du > 0 ? fabs(u_t - u_q) <= max_du : true) && (min_dv >= 0 ? v_t - v_q >= min_dv : true)
+ * which is the gate of the assemble stages (sosvo_stereo_assemble with the train the top and the query the bottom view:
+ * min_dv = stereo_min_disp, max_du = stereo_max_hdiff; sosvo_f2f_assemble: min_dv < 0, max_du = f2f_max_hdiff), evaluated in
+ * double exactly as they do; the azimuth gets no wrap-around, as there.  Problems p >= n_forward are REVERSED: their v side
+ * reads v_q - v_t >= min_dv (the same gate seen from the swapped roles; the u side is symmetric), so a step's forward
+ * problems and their role-swapped twins for sosvo_cross_check_matches run as one launch; n_forward = nprob: none is.
+ * For each query row i < nq[qs]:
+ *   keys[p*q_stride + i] = min over j < nt[ts] with gate(i, j) of (hamming(q_i, t_j) << 20 | j)
+ *                        = SOSVO_KEY_NONE if no j passes, or if the winner's distance exceeds max_distance
+ * max_distance: 0 .. 256 (256: no cap; the winner has the smallest admissible distance, so the cap acts on it alone).
+ * Rows i >= nq[qs] are unspecified.  1-NN only.  With both gate sides disabled and max_distance = 256 the keys are those
+ * of sosvo_match_hamming(k = 1), bit for bit.  sosvo_sort_matches puts SOSVO_KEY_NONE last and the assemble stages count
+ * the keys that are not SOSVO_KEY_NONE, as after sosvo_cross_check_matches. */
+int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                                  const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
+                                  const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
+                                  double min_dv, double max_du, int32_t max_distance, uint32_t* keys);
+
 /* Float descriptors (SIFT / SURF / KAZE ...; feature_detection_method "SIFT" / "SURF" makes FeatureMatcher build
  * cv2.BFMatcher() with its default NORM_L2, omnistereo/camera_models.py:394-396): brute-force L2 matching.
  * q_desc [nprob, q_stride, dim] f32, t_desc [nprob, t_stride, dim] f32, dim <= 128, finite values.  distance = sqrt of the
@@ -461,7 +483,7 @@ typedef struct sosvo_rig {
   double max_range;        /* <= 0 disables */
   double stereo_min_disp;  /* v_top - v_bot >= this, < 0 disables (common_cv.py:182) */
   double stereo_max_hdiff; /* |u_top - u_bot| <= this, <= 0 disables (common_cv.py:177) */
-  double f2f_max_hdiff;    /* frame-to-frame |du| gate, < 0 disables (pose_est_tools.py:245) */
+  double f2f_max_hdiff;    /* frame-to-frame |du| gate, <= 0 disables (< 0 skips it, pose_est_tools.py:245; 0 passes all) */
   double pct_good_matches; /* 1.0 */
 } sosvo_rig;
 
@@ -560,6 +582,28 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
 #define SOSVO_FLAG_CROSS_CHECK_STEREO 0x1000
 #define SOSVO_FLAG_CROSS_CHECK_F2F 0x2000
 
+/* ---- gated matching in the batch and sequence entry points (sosvo_match_hamming_gated) ----------------------
+ *   SOSVO_FLAG_GATED_STEREO  static stereo: each bottom keypoint takes its nearest top keypoint of the bucket among those
+ *                            that pass the rig's stereo_min_disp / stereo_max_hdiff gate
+ *   SOSVO_FLAG_GATED_F2F     frame to frame, per view: the nearest keypoint of the reference frame within f2f_max_hdiff
+ *                            columns; the gate is disabled exactly when the assemble stage's is (f2f_max_hdiff <= 0 in
+ *                            sosvo_rig and in sosvo_rgbd_batch_cfg: below 0 the stage skips its gate, at 0 the gate
+ *                            passes every pair)
+ *   SOSVO_GATED_MAX_DIST(d)  bits 16-24: 0 = no cap; 1 .. 256: a match whose distance exceeds d is no match (a larger
+ *                            field value is SOSVO_ERR_ARG, from sosvo_match_hamming_gated); ignored without a GATED bit
+ * Honoured in sosvo_batch_cfg.ransac_flags; ..._F2F and the distance field in sosvo_rgbd_batch_cfg.flags, ..._STEREO there
+ * is SOSVO_ERR_ARG (and a workspace size of 0).  A query without an admissible partner has the key SOSVO_KEY_NONE; sort
+ * and assemble treat it as after the cross-check filter, and the assemble gates stay (they now pass every match they see).
+ * Together with SOSVO_FLAG_CROSS_CHECK_*: the role-swapped problems run under the same gate in the same launch ("mutual
+ * under the gate"; the gate is symmetric in the pair).  The bits never reach the RANSAC flags; the struct layouts and,
+ * with the bits clear, workspace sizes, launches and results are unchanged -- the gated search needs no workspace. */
+#define SOSVO_FLAG_GATED_STEREO 0x4000
+#define SOSVO_FLAG_GATED_F2F 0x8000
+#define SOSVO_GATED_MAX_DIST_SHIFT 16
+#define SOSVO_GATED_MAX_DIST_MASK (0x1FF << SOSVO_GATED_MAX_DIST_SHIFT)
+#define SOSVO_GATED_MAX_DIST(d) ((d) << SOSVO_GATED_MAX_DIST_SHIFT)
+#define SOSVO_GATED_MAX_DIST_OF(flags) (((flags) & SOSVO_GATED_MAX_DIST_MASK) >> SOSVO_GATED_MAX_DIST_SHIFT)
+
 /* ---- the whole hot path for a batch of frame pairs (the throughput entry point) ----------------
  * One call = for B independent pairs (frames 2i = reference / keyframe, 2i+1 = current):
  *   OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__ for both frames
@@ -604,7 +648,8 @@ typedef struct sosvo_batch_cfg {
   uint64_t seed;           /* pair i samples with seed + i */
   float cos_a, sin_a;      /* descriptor orientation given to the GFT keypoints */
   int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P;
-                              SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above) */
+                              SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above);
+                              SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above) */
   int32_t detector;        /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
@@ -740,6 +785,7 @@ typedef struct sosvo_rgbd_batch_cfg {
                               SOSVO_FLAG_TWOPT: "TWOPT" -- passed through to sosvo_ransac_abs_pose;
                               bits 8-9: SOSVO_RGBD_DETECTOR(enum sosvo_detector), 0 = GFT (masked off before the solver).
                               SOSVO_FLAG_CROSS_CHECK_F2F: mutual matches only (masked off as well; ..._STEREO: SOSVO_ERR_ARG).
+                              SOSVO_FLAG_GATED_F2F, SOSVO_GATED_MAX_DIST(d): search under the gate (likewise; ..._STEREO: SOSVO_ERR_ARG).
                               The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
                               for every frame) */
   double quality, min_distance;        /* 0.01, 5 */

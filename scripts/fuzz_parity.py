@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential fuzzing of the stage entry points against the CPU oracle (test infrastructure: the oracle is the checker).
 
-    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch,cross_check]
+    python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch,cross_check,gated_match]
 
 Every case draws its own sizes and parameters (image sizes around the strip / chunk / tile borders of the kernels, ragged
 problem counts, empty masks, fractional minimum distances, budgets that end a selection inside a round, duplicate
@@ -260,6 +260,78 @@ def fuzz_cross_check(ctx, rng):
             return params, "problem %d: n_kept" % p
         if not np.array_equal(order[p, :n], oracle.sort_matches(want)):
             return params, "problem %d: order" % p
+    return params, None
+
+
+def fuzz_gated_match(ctx, rng):
+    """sosvo_match_hamming_gated against its definition in numpy: key(i) = min over the trains j that pass
+    oracle.pixel_gates (on the float32 positions converted to double) of (hamming << 20 | j), SOSVO_KEY_NONE without one or
+    when the winner's distance exceeds the cap; then the sort.  Random sizes around the 32-query / 128-train tile edges, gates
+    with either side disabled, limits that sit exactly on a position difference, caps 0 .. 256, half of the cases through
+    slot tables over one store, a random share of the problems reversed (the role-swapped problems of a cross-checked
+    step).  With both sides disabled and no cap the keys must also be those of sosvo_match_hamming."""
+    NONE = 0xFFFFFFFF
+    popcount = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
+    sizes = [0, 1, 2, 31, 32, 33, 127, 128, 129, 255, 257, 300]
+    slots = rng.random() < 0.5
+    if slots:
+        nb, S = int(rng.integers(1, 6)), int(rng.choice([1, 33, 130, 320]))
+        cnt = np.minimum(rng.choice(sizes, nb), S).astype(np.int32)
+        store, _ = _descriptors(rng, nb, S, S, cnt, cnt)
+        for b in range(1, nb):
+            m = min(cnt[b], cnt[b - 1])
+            if m:
+                store[b, :m:2] = store[b - 1, rng.integers(0, max(1, m // 2), len(range(0, m, 2)))]
+        P = int(rng.integers(1, 9))
+        qs, ts = rng.integers(0, nb, P).astype(np.int32), rng.integers(0, nb, P).astype(np.int32)
+        q = t = store
+        nq = nt = cnt
+        Sq = St = S
+    else:
+        P = int(rng.integers(1, 9))
+        Sq, St = int(rng.choice([1, 33, 130, 320, 1024])), int(rng.choice([1, 33, 129, 320]))
+        nq = np.minimum(rng.choice(sizes, P), Sq).astype(np.int32)
+        nt = np.minimum(rng.choice(sizes, P), St).astype(np.int32)
+        q, t = _descriptors(rng, P, Sq, St, nq, nt)
+        qs = ts = np.arange(P, dtype=np.int32)
+    # positions on a quarter-pixel grid inside a small window: many pairs sit exactly on a limit drawn from the same grid
+    span = float(rng.choice([4.0, 16.0, 64.0]))
+    grid = lambda shape: (np.round(rng.uniform(0.0, span, shape) * 4.0) / 4.0).astype(np.float32)  # noqa: E731
+    qp = grid(q.shape[:2] + (2,))
+    tp = qp if slots else grid(t.shape[:2] + (2,))
+    if rng.random() < 0.3:                   # off-grid positions: differences that are not representable in float32
+        qp = (qp + rng.uniform(0.0, 1e-3, qp.shape)).astype(np.float32)
+        tp = qp if slots else (tp + rng.uniform(0.0, 1e-3, tp.shape)).astype(np.float32)
+    min_dv = float(rng.choice([-1.0, 0.0, 0.25, 1.0, 3.5]))
+    max_du = float(rng.choice([-1.0, 0.0, 0.25, 2.5, 7.75, 1e9]))
+    cap = [None, 0, 1, 40, 64, 100, 128, 256][int(rng.integers(0, 8))]
+    n_forward = int(rng.integers(0, P + 1))
+    params = dict(P=P, slots=slots, q_stride=Sq, t_stride=St, nq=nq.tolist(), nt=nt.tolist(), q_slot=qs.tolist(), t_slot=ts.tolist(),
+                  span=span, min_dv=min_dv, max_du=max_du, cap=cap, n_forward=n_forward)
+    tq, tt, tqp, ttp, tnq, tnt, tqs, tts = _dev(ctx, q, t, qp, tp, nq, nt, qs, ts)
+    sl = dict(q_slot=tqs, t_slot=tts) if slots else {}
+    keys = ctx.match_hamming_gated(tq, tt, tqp, ttp, tnq, tnt, min_dv, max_du, cap, n_forward=n_forward, **sl)
+    order = ctx.sort_matches(keys, tnq, q_slot=tqs if slots else None)
+    plain = ctx.match_hamming(tq, tt, tnq, tnt, k=1, **sl) if (min_dv < 0 and max_du <= 0 and cap in (None, 256)) else None
+    ctx.synchronize()
+    keys, order = keys.cpu().numpy()[:, :, 0], order.cpu().numpy()
+    for p in range(P):
+        n, m = int(nq[qs[p]]), int(nt[ts[p]])
+        want = np.full(n, NONE, np.uint32)
+        if n and m:
+            qd, td = q[qs[p], :n], t[ts[p], :m]
+            a = np.repeat(qp[qs[p], :n].astype(np.float64)[:, None], m, 1).reshape(-1, 2)
+            b = np.repeat(tp[ts[p], :m].astype(np.float64)[None], n, 0).reshape(-1, 2)
+            ok = (oracle.pixel_gates(a, b, min_dv, max_du) if p >= n_forward else oracle.pixel_gates(b, a, min_dv, max_du)).reshape(n, m)
+            k = (popcount[qd[:, None, :] ^ td[None, :, :]].sum(-1, dtype=np.uint32) << 20) | np.arange(m, dtype=np.uint32)[None]
+            want = np.where(ok, k, np.uint32(NONE)).min(1).astype(np.uint32)
+            want[(want >> 20) > (256 if cap is None else cap)] = NONE
+        if not np.array_equal(keys[p, :n], want):
+            return params, "problem %d: keys" % p
+        if not np.array_equal(order[p, :n], oracle.sort_matches(want)):
+            return params, "problem %d: order" % p
+        if plain is not None and not np.array_equal(plain.cpu().numpy()[p, :n, 0], want):
+            return params, "problem %d: differs from sosvo_match_hamming" % p
     return params, None
 
 
@@ -881,7 +953,8 @@ def fuzz_rgbd(ctx, rng):
 STAGES = {"median": fuzz_median, "gft": fuzz_gft, "fast": fuzz_fast, "agast": fuzz_agast, "match": fuzz_match,
           "radius": fuzz_radius, "orb": fuzz_orb, "unwrap": fuzz_unwrap, "ransac": fuzz_ransac,
           "describe": fuzz_describe, "relpose": fuzz_relpose, "l2sort": fuzz_l2sort,
-          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd, "batch": fuzz_batch, "cross_check": fuzz_cross_check}
+          "pipeline": fuzz_pipeline, "rgbd": fuzz_rgbd, "batch": fuzz_batch, "cross_check": fuzz_cross_check,
+          "gated_match": fuzz_gated_match}
 
 
 def main():

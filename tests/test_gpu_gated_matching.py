@@ -1,0 +1,855 @@
+"""GPU: gated matching -- the 1-NN search among the trains that pass the pixel gates (sosvo_match_hamming_gated) -- through
+every layer: the stage entry, FeatureMatcher.match_gated, the pair pipelines and one-call batches, the sequence engines
+behind run_VO / run_VO_many, RGB-D, and the subset relations the definition implies.
+
+The CPU checker is the definition itself, composed of oracle calls (gated_keys below): oracle.pixel_gates on the float32
+positions converted to double, a numpy min over popcounts, oracle.sort_matches.  refflow.stereo_frame / f2f_view are swapped
+for gated versions defined here (gated_matching below) and restored afterwards.  Everything is compared bit for bit or byte
+for byte; the mirror path (frame_window 0) to 1e-6, as the existing sequence tests compare it."""
+import contextlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+import refflow
+from vo_single_camera_sos_amd import orb_pattern, synthetic
+from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
+from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
+from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
+from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
+from vo_single_camera_sos_amd.pipeline import (FramePairBatch, FramePairPipeline, RGBDCamConfig, RGBDPairBatch, RGBDPairPipeline,
+                                               RigConfig)
+
+pytestmark = pytest.mark.gpu
+
+IDX, NONE = 0xFFFFF, 0xFFFFFFFF
+FILES = ("estimated_frame_poses_TUM.txt", "keyframe_ids.txt")
+POPCOUNT = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
+
+
+# ---- the definition ------------------------------------------------------------------------------------------------------
+def distances(q, t):
+    """[nq, nt] Hamming distances."""
+    return POPCOUNT[q[:, None, :] ^ t[None, :, :]].sum(-1, dtype=np.uint32)
+
+
+def gate_matrix(q_pos, t_pos, min_dv, max_du, reverse=False):
+    """gate(i, j) [nq, nt]: oracle.pixel_gates(train, query) on doubles converted from the float32 positions; a reversed
+    problem evaluates the same gate with the roles swapped (v_q - v_t >= min_dv)."""
+    nq, nt = len(q_pos), len(t_pos)
+    qp = np.repeat(q_pos.astype(np.float64)[:, None, :], nt, 1).reshape(-1, 2)
+    tp = np.repeat(t_pos.astype(np.float64)[None, :, :], nq, 0).reshape(-1, 2)
+    ok = oracle.pixel_gates(qp, tp, min_dv, max_du) if reverse else oracle.pixel_gates(tp, qp, min_dv, max_du)
+    return ok.reshape(nq, nt)
+
+
+def gated_keys(q, t, q_pos, t_pos, min_dv, max_du, cap=None, reverse=False, dist=None):
+    """key(i) = min over admissible j of (hamming << 20 | j); NONE without an admissible train or beyond the cap."""
+    nq, nt = len(q), len(t)
+    if nq == 0 or nt == 0:
+        return np.full(nq, NONE, np.uint32)
+    d = distances(q, t) if dist is None else dist
+    keys = (d << 20) | np.arange(nt, dtype=np.uint32)[None, :]
+    keys = np.where(gate_matrix(q_pos, t_pos, min_dv, max_du, reverse), keys, np.uint32(NONE)).min(1).astype(np.uint32)
+    keys[(keys >> 20) > (256 if cap is None else cap)] = NONE      # (NONE >> 20 is 4095)
+    return keys
+
+
+def gated_match_sorted(query_desc, train_desc, query_pos, train_pos, min_dv, max_du, cap=None):
+    """refflow.match_sorted on the gated keys: the matches that exist, stably sorted by distance."""
+    keys = gated_keys(query_desc, train_desc, query_pos, train_pos, min_dv, max_du, cap)
+    kept = np.nonzero(keys != NONE)[0]
+    if len(kept) == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z, z
+    k = keys[kept]
+    order = oracle.sort_matches(k)
+    return kept[order].astype(np.int64), (k[order] & IDX).astype(np.int64), (k[order] >> 20).astype(np.int64)
+
+
+def _dev(ctx, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
+
+
+def _scene(rng, blocks, stride, counts, u_span=40.0, v_span=12.0):
+    """A descriptor / position store: every block re-observes block 0's first rows with 0-6 flipped bits at a position
+    jittered by a few pixels, some rows are copies of each other (ties), the rest is random."""
+    desc = rng.integers(0, 256, (blocks, stride, 32), dtype=np.uint8)
+    pos = np.stack([rng.uniform(0, u_span, (blocks, stride)), rng.uniform(0, v_span, (blocks, stride))], -1).astype(np.float32)
+    n0 = max(1, int(counts[0]))
+    for b in range(blocks):
+        n = int(counts[b])
+        for i in range(0, n, 2):
+            src = int(rng.integers(0, n0))
+            d = desc[0, src].copy()
+            for bit in rng.integers(0, 256, rng.integers(0, 7)):
+                d[bit >> 3] ^= np.uint8(1 << (bit & 7))
+            desc[b, i] = d
+            pos[b, i] = pos[0, src] + rng.uniform(-3.0, 3.0, 2).astype(np.float32)
+        for i in range(5, n, 11):
+            desc[b, i] = desc[b, i - 3]
+    return desc, pos
+
+
+class _Stage(object):
+    """One set of problems on the device, the distance matrices cached per (query block, train block)."""
+
+    def __init__(self, ctx, qd, td, qp, tp, nq, nt, q_slot=None, t_slot=None, n_forward=None):
+        self.ctx, self.qd, self.td, self.qp, self.tp, self.nq, self.nt = ctx, qd, td, qp, tp, nq, nt
+        self.P = len(nq) if q_slot is None else len(q_slot)
+        self.qs = np.arange(self.P) if q_slot is None else q_slot
+        self.ts = np.arange(self.P) if t_slot is None else t_slot
+        self.n_forward = self.P if n_forward is None else n_forward
+        self.dev = [_dev(ctx, a) for a in (qd, td, qp, tp, nq.astype(np.int32), nt.astype(np.int32))]
+        self.sl = {} if q_slot is None else dict(q_slot=_dev(ctx, q_slot.astype(np.int32)), t_slot=_dev(ctx, t_slot.astype(np.int32)))
+        self.dist, self.want = {}, {}
+
+    def run(self, min_dv, max_du, cap):
+        keys = self.ctx.match_hamming_gated(*self.dev, min_dv=min_dv, max_du=max_du, max_distance=cap, n_forward=self.n_forward,
+                                            **self.sl)
+        self.ctx.synchronize()
+        return keys.cpu().numpy()[:, :, 0]
+
+    def expect(self, p, min_dv, max_du, cap):
+        qs, ts, rev = int(self.qs[p]), int(self.ts[p]), p >= self.n_forward
+        n, m = int(self.nq[qs]), int(self.nt[ts])
+        if (qs, ts) not in self.dist:
+            self.dist[qs, ts] = distances(self.qd[qs, :n], self.td[ts, :m])
+        sig = (qs, ts, rev, min_dv, max_du, cap)
+        if sig not in self.want:
+            self.want[sig] = gated_keys(self.qd[qs, :n], self.td[ts, :m], self.qp[qs, :n], self.tp[ts, :m], min_dv, max_du, cap,
+                                        reverse=rev, dist=self.dist[qs, ts])
+        return self.want[sig]
+
+    def check(self, min_dv, max_du, cap):
+        got = self.run(min_dv, max_du, cap)
+        for p in range(self.P):
+            want = self.expect(p, min_dv, max_du, cap)
+            assert np.array_equal(got[p, : len(want)], want), (p, min_dv, max_du, cap)     # (padding rows are unspecified)
+        return got
+
+
+GATES = [(1.0, 2.5), (-1.0, 2.5), (1.0, 0.0), (-1.0, -1.0)]      # both sides, du alone, dv alone, neither
+TRAINS = (1, 31, 32, 33, 127, 128, 129, 257)                     # 32-row blocks, 128-train tiles, a range split over tiles
+QUERIES = (1, 32, 33, 128, 129)
+
+
+# ---- 1. the stage -------------------------------------------------------------------------------------------------------
+def test_stage_equals_the_definition_at_the_tile_edges(ctx):
+    """Every (query count, train count) pair as one problem of one launch (stride 320: the train range is split over three
+    workgroups), all four gate forms, caps none / 256 / 64 / 0."""
+    rng = np.random.default_rng(2025)
+    shapes = [(a, b) for a in QUERIES for b in TRAINS]
+    S = 320
+    nq, nt = np.array([s[0] for s in shapes]), np.array([s[1] for s in shapes])
+    qd, qp = _scene(rng, len(shapes), S, nq)
+    td, tp = _scene(rng, len(shapes), S, nt)
+    td[:, ::2] = qd[:, ::2]                                       # (true partners exist: same descriptor, nearby position)
+    tp[:, ::2] = qp[:, ::2] + rng.uniform(-2.0, 4.0, qp[:, ::2].shape).astype(np.float32)
+    st = _Stage(ctx, qd, td, qp, tp, nq, nt)
+    for (min_dv, max_du) in GATES:
+        for cap in (None, 256, 64, 0):
+            got = st.check(min_dv, max_du, cap)
+            real = np.concatenate([got[p, : nq[p]] for p in range(st.P)])
+            if cap == 0:
+                assert ((real == NONE) | ((real >> 20) == 0)).all()
+            elif cap == 64:
+                assert (real != NONE).any() and (real == NONE).any()
+    # the gate decided something: with both sides on some queries have no admissible train, with none every query has one
+    both = np.concatenate([st.expect(p, 1.0, 2.5, None) for p in range(st.P)])
+    none = np.concatenate([st.expect(p, -1.0, -1.0, None) for p in range(st.P)])
+    assert (both == NONE).any() and (both != NONE).any() and (none != NONE).all() and (both != none).sum() > 100
+
+
+def test_stage_without_gate_and_cap_equals_the_plain_matcher(ctx):
+    rng = np.random.default_rng(3)
+    nq, nt = np.array([129, 33, 300]), np.array([257, 128, 300])
+    qd, qp = _scene(rng, 3, 320, nq)
+    td, tp = _scene(rng, 3, 320, nt)
+    st = _Stage(ctx, qd, td, qp, tp, nq, nt)
+    plain = ctx.match_hamming(st.dev[0], st.dev[1], st.dev[4], st.dev[5], k=1)
+    ctx.synchronize()
+    plain = plain.cpu().numpy()[:, :, 0]
+    for cap in (None, 256):
+        got = st.check(-1.0, 0.0, cap)
+        for p in range(3):
+            assert np.array_equal(got[p, : nq[p]], plain[p, : nq[p]])
+
+
+def test_stage_constructed_cases(ctx):
+    """One problem, 8 queries against 140 trains (two tiles), gate du <= 2.5 and dv >= 1:
+    query 0: no admissible train -> NONE;  query 1: its copies are trains 5 and 130, train 5 gated out -> 130 wins;
+    query 2: copies at trains 7, 40 and 131, all admissible -> 7 (lowest index);  query 3: the whole first tile is gated
+    out -> the winner lies in the second;  query 4: |du| == max_du and dv == min_dv exactly -> passes;  query 5: du passes,
+    dv fails by one ulp -> its copy is rejected;  queries 6, 7: each side disabled on its own lets the other's failure pass."""
+    rng = np.random.default_rng(17)
+    S, nq, nt = 160, 8, 140
+    qd = rng.integers(0, 256, (1, S, 32), dtype=np.uint8)
+    td = rng.integers(0, 256, (1, S, 32), dtype=np.uint8)
+    qp = np.zeros((1, S, 2), np.float32)
+    tp = np.zeros((1, S, 2), np.float32)
+    tp[0, :, 0] = 1000.0 + 10.0 * np.arange(S)                    # by default no train is near any query
+    tp[0, :, 1] = 50.0
+    qp[0, :nq, 0] = 100.0 * np.arange(nq)
+    qp[0, :nq, 1] = 10.0
+    # query 1
+    td[0, 5] = td[0, 130] = qd[0, 1]
+    tp[0, 5] = (100.0 + 2.75, 12.0)
+    tp[0, 130] = (100.0 - 2.0, 12.0)
+    # query 2
+    td[0, 7] = td[0, 40] = td[0, 131] = qd[0, 2]
+    tp[0, 7] = tp[0, 40] = tp[0, 131] = (200.0, 11.5)
+    # query 3: admissible trains only at 128 .. 139, one of them at distance 3
+    td[0, 135] = qd[0, 3]
+    td[0, 135, 0] ^= 0x07
+    tp[0, 132:140, 0] = 300.0 + np.linspace(-2.0, 2.0, 8)
+    tp[0, 132:140, 1] = 20.0
+    td[0, 20] = qd[0, 3]                                          # (the exact copy sits in the first tile, out of the band)
+    tp[0, 20] = (303.0, 20.0)
+    # query 4: the bounds themselves
+    td[0, 60] = qd[0, 4]
+    tp[0, 60] = (400.0 + 2.5, 11.0)
+    # query 5: dv one float32 step below 1
+    td[0, 61] = qd[0, 5]
+    tp[0, 61] = (500.0, np.nextafter(np.float32(11.0), np.float32(0.0)))
+    # queries 6 / 7
+    td[0, 62] = qd[0, 6]
+    tp[0, 62] = (600.0 + 30.0, 12.0)                              # du fails, dv passes
+    td[0, 63] = qd[0, 7]
+    tp[0, 63] = (700.0, 5.0)                                      # du passes, dv fails
+    st = _Stage(ctx, qd, td, qp, tp, np.array([nq]), np.array([nt]))
+    k = st.check(1.0, 2.5, None)[0, :nq]
+    assert k[0] == NONE
+    assert k[1] == 130 and k[2] == 7
+    assert k[3] == ((3 << 20) | 135)
+    assert k[4] == 60
+    assert k[5] == NONE and k[6] == NONE and k[7] == NONE
+    k = st.check(1.0, 0.0, None)[0, :nq]                          # du side off
+    assert k[6] == 62 and k[1] == 5 and (k[7] >> 20) > 0
+    k = st.check(-1.0, 2.5, None)[0, :nq]                         # dv side off
+    assert k[7] == 63 and k[5] == 61 and k[6] == NONE
+    k = st.check(1.0, 2.5, 2)[0, :nq]                             # the cap acts on the winner: query 3's distance is 3
+    assert k[3] == NONE and k[1] == 130
+
+
+def test_stage_slots_reversed_problems_and_the_unsplit_train_loop(ctx):
+    """2100 problems over a store of 6 blocks (so many that the train range is not split: one workgroup walks all tiles),
+    the second half reversed, as the role-swapped problems of a cross-checked step are."""
+    rng = np.random.default_rng(23)
+    S, counts = 320, np.array([257, 129, 128, 33, 300, 0])
+    desc, pos = _scene(rng, 6, S, counts)
+    P = 2100
+    q_slot, t_slot = rng.integers(0, 6, P), rng.integers(0, 6, P)
+    st = _Stage(ctx, desc, desc, pos, pos, counts, counts, q_slot, t_slot, n_forward=P // 2)
+    st.check(1.0, 2.5, None)
+    st.check(1.0, 2.5, 80)
+    st.check(-1.0, 2.5, None)
+    fwd = gated_keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], 1.0, 2.5)
+    rev = gated_keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], 1.0, 2.5, reverse=True)
+    assert not np.array_equal(fwd, rev)                           # (the reversed gate is another gate)
+
+
+def test_stage_two_tiles_per_wave(ctx):
+    """q_stride 1024: the kernel form with two query tiles per wave, a dead second tile included (nq = 1000 - 40)."""
+    rng = np.random.default_rng(29)
+    nq, nt = np.array([960]), np.array([300])
+    qd, qp = _scene(rng, 1, 1024, nq)
+    td, tp = _scene(rng, 1, 320, nt)
+    td[0, :300:3] = qd[0, :300:3]
+    tp[0, :300:3] = qp[0, :300:3] + np.float32(1.25)
+    st = _Stage(ctx, qd, td, qp, tp, nq, nt)
+    for (min_dv, max_du) in GATES:
+        st.check(min_dv, max_du, None)
+    st.check(1.0, 2.5, 64)
+    assert (st.expect(0, 1.0, 2.5, None) != NONE).sum() > 100
+
+
+def test_gate_is_evaluated_in_double(ctx):
+    """u_t is the smallest float32 above u_q + 2.5: the exact difference exceeds max_du = 2.5, and for about half the draws
+    its float32 rounding IS 2.5 -- a gate that subtracted in float32 would accept those.  Query i's only zero-distance train
+    is train i, so accepting it shows in the key."""
+    rng = np.random.default_rng(31)
+    n = 256
+    uq = rng.uniform(0.0, 1.0, n).astype(np.float32)
+    uq = np.maximum(uq, np.float32(1e-3))
+    s = uq.astype(np.float64) + 2.5                               # exact in double
+    ut = s.astype(np.float32)
+    ut = np.where(ut.astype(np.float64) <= s, np.nextafter(ut, np.float32(np.inf)), ut).astype(np.float32)
+    exact = ut.astype(np.float64) - uq.astype(np.float64)
+    assert (exact > 2.5).all() and (np.nextafter(ut, np.float32(0.0)).astype(np.float64) <= s).all()
+    rounds_onto = (ut - uq) == np.float32(2.5)                    # float32 subtraction
+    print("float32 difference rounds onto 2.5 in %d of %d draws" % (rounds_onto.sum(), n))
+    assert rounds_onto.sum() >= 64                                # about half by construction (measured: see the print)
+    qd = rng.integers(0, 256, (1, n, 32), dtype=np.uint8)
+    td = qd.copy()
+    qp = np.zeros((1, n, 2), np.float32)
+    tp = np.zeros((1, n, 2), np.float32)
+    qp[0, :, 0], tp[0, :, 0] = uq, ut
+    tp[0, :, 1] = 1.0
+    st = _Stage(ctx, qd, td, qp, tp, np.array([n]), np.array([n]))
+    for min_dv in (1.0, -1.0):
+        k = st.check(min_dv, 2.5, None)[0]
+        assert ((k == NONE) | ((k & IDX) != np.arange(n))).all()  # nobody got its own train
+        assert ((k[rounds_onto] == NONE) | ((k[rounds_onto] >> 20) > 0)).all()
+    k = st.check(1.0, 2.5000005, None)[0]                         # (a hair wider and every query has it)
+    assert np.array_equal(k, np.arange(n, dtype=np.uint32))
+
+
+# ---- 2. FeatureMatcher.match_gated ----------------------------------------------------------------------------------------
+def test_feature_matcher_match_gated(ctx):
+    rng = np.random.default_rng(5)
+    desc, pos = _scene(rng, 2, 320, np.array([257, 300]))
+    q, t, qp, tp = desc[1, :300], desc[0, :257], pos[1, :300], pos[0, :257]
+    fm = FeatureMatcher("ORB", "BF", 1, context=ctx)
+    plain = fm.match(q, t)
+    for cap in (None, 80, 0):
+        got = fm.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=cap)
+        wq, wt, wd = gated_match_sorted(q, t, qp, tp, 1.0, 2.5, cap)
+        assert np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
+        assert [m.queryIdx for m in got] == list(wq) and [m.trainIdx for m in got] == list(wt)
+    wq, wt, wd = gated_match_sorted(q, t, qp, tp, 1.0, 2.5)
+    assert 20 < len(wq) < 300
+    # the plain matches that pass the gate are gated matches (the search under the gate can only add)
+    ok = oracle.pixel_gates(tp[plain.train_idx].astype(np.float64), qp[plain.query_idx].astype(np.float64), 1.0, 2.5)
+    kept = {(a, b) for a, b, o in zip(plain.query_idx, plain.train_idx, ok) if o}
+    assert kept < set(zip(wq, wt))
+    # without a gate and a cap it is match()
+    got = fm.match_gated(q, t, qp, tp, -1.0, 0.0)
+    assert np.array_equal(got.query_idx, plain.query_idx) and np.array_equal(got.train_idx, plain.train_idx)
+    # [n, 3] homogeneous pixel rows are taken as they come from the frames; empty sides give no match
+    got3 = fm.match_gated(q, t, np.hstack([qp, np.ones((300, 1), np.float32)]), np.hstack([tp, np.ones((257, 1), np.float32)]), 1.0, 2.5)
+    assert np.array_equal(got3.query_idx, wq) and np.array_equal(got3.train_idx, wt)
+    assert len(fm.match_gated(q, t[:0], qp, tp[:0], 1.0, 2.5)) == 0 and len(fm.match_gated(q[:0], t, qp[:0], tp, 1.0, 2.5)) == 0
+    # mutual under the gate
+    fmc = FeatureMatcher("ORB", "BF", 1, context=ctx, cross_check=True)
+    got = fmc.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=80)
+    wq, wt, wd = matches_under(q, t, qp, tp, (1.0, 2.5), 80, True)
+    assert 0 < len(wq) and np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
+    assert len(set(got.train_idx)) == len(got)
+
+
+# ---- the gated reference flow ---------------------------------------------------------------------------------------------
+def matches_under(qd, td, qp, tp, gate, cap, mutual):
+    """refflow.match_sorted of one problem: gate = (min_dv, max_du) or None for the plain search; mutual: keep query i only
+    if the role-swapped search (under the reversed gate) of its train returns i."""
+    if len(qd) == 0 or len(td) == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, z, z
+    if gate is None:
+        fwd = oracle.match_hamming(qd, td, k=1)[:, 0]
+        rev = oracle.match_hamming(td, qd, k=1)[:, 0] if mutual else None
+    else:
+        fwd = gated_keys(qd, td, qp, tp, gate[0], gate[1], cap)
+        rev = gated_keys(td, qd, tp, qp, gate[0], gate[1], cap, reverse=True) if mutual else None
+    keep = fwd != NONE
+    if mutual:
+        r = rev[np.where(keep, fwd & IDX, 0)]
+        keep &= (r != NONE) & ((r & IDX) == np.arange(len(qd)))
+    kept = np.nonzero(keep)[0]
+    k = fwd[kept]
+    order = oracle.sort_matches(k) if len(k) else np.zeros(0, np.int64)
+    return kept[order].astype(np.int64), (k[order] & IDX).astype(np.int64), (k[order] >> 20).astype(np.int64)
+
+
+def stereo_frame_under(gated, cap, mutual):
+    """refflow.stereo_frame with the bucket matcher replaced (the lines around it are refflow's)."""
+    def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot):
+        mt, mb, dt, db = [], [], [], []
+        n_cand = 0
+        gate = (rig.stereo_min_disp, rig.stereo_max_hdiff) if gated else None
+        for kt, kb, et, eb in zip(kp_top, kp_bot, desc_top, desc_bot):
+            if len(kt) == 0 or len(kb) == 0:
+                continue
+            q, t, _ = matches_under(eb, et, kb, kt, gate, cap, mutual)    # query = bottom, train = top
+            good = int(rig.pct_good_matches * len(q))
+            q, t = q[:good], t[:good]
+            n_cand += good
+            mt.append(kt[t])
+            mb.append(kb[q])
+            dt.append(et[t])
+            db.append(eb[q])
+        if not mt:
+            e2, e3, e32 = np.zeros((0, 2), np.float32), np.zeros((0, 3)), np.zeros((0, 32), np.uint8)
+            return dict(m_top=e2, m_bot=e2, d_top=e32, d_bot=e32, X=e3, b_top=e3, b_bot=e3, n_cand=0)
+        mt, mb = np.concatenate(mt).astype(np.float32), np.concatenate(mb).astype(np.float32)
+        dt, db = np.concatenate(dt), np.concatenate(db)
+        ok = oracle.pixel_gates(mt.astype(np.float64), mb.astype(np.float64), rig.stereo_min_disp, rig.stereo_max_hdiff)
+        if gated:
+            assert ok.all()                                  # the assemble gate now passes every match it sees
+        mt, mb, dt, db = mt[ok], mb[ok], dt[ok], db[ok]
+        az1, el1 = oracle.pano_to_angles(mt[:, 0], mt[:, 1], *rig.pano_top)
+        az2, el2 = oracle.pano_to_angles(mb[:, 0], mb[:, 1], *rig.pano_bot)
+        bt, bb = oracle.angles_to_bearing(az1, el1), oracle.angles_to_bearing(az2, el2)
+        X = oracle.triangulate_midpoint(az1, el1, az2, el2, rig.F_top, rig.F_bot)
+        good = oracle.range_filter_homo(X, rig.min_range, rig.max_range)
+        return dict(m_top=mt[good], m_bot=mb[good], d_top=dt[good], d_bot=db[good], X=X[good], b_top=bt[good], b_bot=bb[good],
+                    n_cand=n_cand)
+    return stereo_frame
+
+
+def f2f_view_under(gated, cap, mutual):
+    """refflow.f2f_view with the matcher replaced; the gate is off exactly when the view's own |du| gate is."""
+    def f2f_view(rig, m_train, d_train, m_query, d_query):
+        gate = (-1.0, rig.f2f_max_hdiff if rig.f2f_max_hdiff >= 0 else -1.0) if gated else None
+        q, t, _ = matches_under(d_query, d_train, np.asarray(m_query, np.float32)[:, :2], np.asarray(m_train, np.float32)[:, :2],
+                                gate, cap, mutual)
+        good = int(rig.pct_good_matches * len(q))
+        q, t = q[:good], t[:good]
+        if good > 0 and rig.f2f_max_hdiff >= 0:
+            pt, pq = np.zeros((good, 2)), np.zeros((good, 2))
+            pt[:, 0], pq[:, 0] = m_train[t, 0], m_query[q, 0]
+            ok = oracle.pixel_gates(pt, pq, -1, rig.f2f_max_hdiff)
+            if gated:
+                assert ok.all()
+            q, t = q[ok], t[ok]
+        return t, q
+    return f2f_view
+
+
+class Setting(object):
+    def __init__(self, name, stereo, f2f, cap=None, cc=False):
+        self.name, self.stereo, self.f2f, self.cap, self.cc = name, stereo, f2f, cap, cc
+
+    def omni_kw(self):
+        return dict(gated_stereo=self.stereo, gated_f2f=self.f2f, gated_max_distance=self.cap, cross_check_stereo=self.cc,
+                    cross_check_f2f=self.cc)
+
+    def rgbd_kw(self):
+        return dict(gated_f2f=self.f2f, gated_max_distance=self.cap, cross_check=self.cc)
+
+    def run_vo_kw(self):
+        value = "both" if self.stereo and self.f2f else "stereo" if self.stereo else "f2f" if self.f2f else None
+        return dict(gated_matching=value, gated_max_distance=self.cap, cross_check=True if self.cc else None)
+
+
+@contextlib.contextmanager
+def gated_matching(s):
+    """refflow with the setting's matchers in static stereo (stereo_frame) and frame to frame (f2f_view)."""
+    stereo_frame, f2f_view = refflow.stereo_frame, refflow.f2f_view
+    if s.stereo or s.cc:
+        refflow.stereo_frame = stereo_frame_under(s.stereo, s.cap, s.cc)
+    if s.f2f or s.cc:
+        refflow.f2f_view = f2f_view_under(s.f2f, s.cap, s.cc)
+    try:
+        yield
+    finally:
+        refflow.stereo_frame, refflow.f2f_view = stereo_frame, f2f_view
+
+
+SETTINGS = [Setting("stereo", True, False), Setting("f2f", False, True), Setting("both", True, True),
+            Setting("stereo_cap80", True, False, 80), Setting("f2f_cap80", False, True, 80), Setting("both_cap80", True, True, 80),
+            Setting("both_with_cross_check", True, True, None, True)]
+OFF = Setting("off", False, False)
+BY_NAME = {s.name: s for s in SETTINGS}
+NAMES = [s.name for s in SETTINGS]
+
+
+def _rig():
+    gs = synthetic_gums()
+    for m in (gs.top_model, gs.bot_model):
+        m.panorama = Panorama(m, width=1200)
+    gs.make_annulus_masks((480, 640))
+    pano = gs.top_model.panorama
+    geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
+    rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
+                  max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
+                  pct_good_matches=1.0)
+    return gs, rig_kw
+
+
+class _Pairs(object):
+    pass
+
+
+@pytest.fixture(scope="module")
+def pairs(ctx):
+    """2 rendered pairs (GFT 330 features): the front end on the GPU, the detection on the oracle (once, shared).  The
+    trackers' solver settings (generalised P3P, 210 iterations with the adaptive stop) so that one reference serves the pair
+    paths (pair i samples with seed + i) and the sequence engine (frame t with seed t - 1)."""
+    s = _Pairs()
+    s.B, s.nfeat, s.seed = 2, 330, 5
+    s.solver = dict(max_iter=210, adaptive=True, ransac_solver="GP3P")
+    gs, s.rig_kw = _rig()
+    s.omni, _ = synthetic.make_frame_pairs(gs, s.B, seed=99)
+    s.model = DeviceImageModel(ctx, gs, (480, 640))
+    s.fe = ImageFrontEnd(ctx, s.model, 2 * s.B, detection_method="GFT", num_of_features=s.nfeat)
+    s.fe.load_frames(s.omni)
+    s.fe.run()
+    ctx.synchronize()
+    ca, sa = orb_pattern.angle_cos_sin(-1.0)
+    im = refflow.ImageModel(s.model.map_x.cpu().numpy(), s.model.map_y.cpu().numpy(), s.model.omni_masks.cpu().numpy(),
+                            s.model.mask_bits_host, 12, s.nfeat, orb_pattern.orb_pattern(), ca, sa, method="GFT", kp_cap=s.fe.kp_cap)
+    s.views = [[refflow.detect_view(im, s.omni[f], v)[:2] for v in range(2)] for f in range(2 * s.B)]
+    s.rp = refflow.RigParams(**s.rig_kw)
+    s.thr = float(1.0 - np.cos(np.deg2rad(5.0)))
+    s.cache = {}
+
+    def reference(setting):
+        """-> (frames, pair tracks with seed + i, sequence tracks of (t - 1, t) with seed t - 1) under the setting."""
+        if setting.name not in s.cache:
+            with gated_matching(setting):
+                frames = [refflow.stereo_frame(s.rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
+                track = lambda a, b, seed: refflow.track_pair(s.rp, frames[a], frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
+                                                              gp3p=True)
+                s.cache[setting.name] = (frames, [track(2 * i, 2 * i + 1, s.seed + i) for i in range(s.B)],
+                                         [track(t - 1, t, t - 1) for t in range(1, 2 * s.B)])
+            assert refflow.stereo_frame.__name__ == "stereo_frame" and refflow.f2f_view.__module__ == "refflow"
+        return s.cache[setting.name]
+    s.reference = reference
+    return s
+
+
+def _record(w):
+    """The [16] record of a refflow track."""
+    out = np.zeros(16)
+    out[:12] = np.asarray(w["T"]).reshape(12)
+    out[12], out[13] = w["ransac"]["n_inliers"], len(w["corr"]["cam"] if "cam" in w["corr"] else w["corr"]["q"])
+    out[14], out[15] = w["ransac"]["status"], w["ransac"]["best_iter"]
+    return out
+
+
+# ---- 3. the omni paths against the gated refflow ------------------------------------------------------------------------
+@pytest.mark.parametrize("name", NAMES)
+def test_pair_pipeline_stage_by_stage_equals_the_gated_refflow(ctx, pairs, name):
+    s, setting = pairs, BY_NAME[name]
+    frames, want, _ = s.reference(setting)
+    pipe = FramePairPipeline(ctx, RigConfig(**s.rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
+                             **setting.omni_kw())
+    pipe.stereo()
+    pipe.track()
+    rec = pipe.results().cpu().numpy()
+    M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
+    assert [int(x) for x in M] == [len(fr["X"]) for fr in frames] and M.min() > 100
+    assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
+    for f, fr in enumerate(frames):
+        for key in ("m_top", "m_bot", "d_top", "d_bot", "X"):
+            assert np.array_equal(pipe.frames[key][f, : M[f]].cpu().numpy(), fr[key]), (f, key)
+    mask = pipe.ransac["mask"].cpu().numpy()
+    cq, ct = pipe.corr["q"].cpu().numpy(), pipe.corr["t"].cpu().numpy()
+    for i, w in enumerate(want):
+        n = len(w["corr"]["cam"])
+        assert n > 100 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
+        assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
+        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64)) and rec[i, 14] == 0
+    off = s.reference(OFF)
+    if setting.stereo and not setting.cc and setting.cap is None:   # the search under the gate can only add stereo points
+        assert all(len(a["X"]) >= len(b["X"]) for a, b in zip(frames, off[0]))
+        assert sum(len(a["X"]) for a in frames) > sum(len(b["X"]) for b in off[0])
+    if not setting.stereo and not setting.cc:                 # the stereo stage is untouched by the f2f switch
+        assert all(np.array_equal(a["X"], b["X"]) for a, b in zip(frames, off[0]))
+
+
+def test_pair_path_with_a_fraction_of_the_gated_matches(ctx, pairs):
+    """pct_good_matches = 0.75 with both switches and cap 80: the gate and the cap leave many SOSVO_KEY_NONE keys, and
+    int(0.75 * len(matches)) counts the REAL matches per bucket and per view, in the stage path and behind the one C call."""
+    s, setting = pairs, BY_NAME["both_cap80"]
+    rig_kw = dict(s.rig_kw, pct_good_matches=0.75)
+    pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
+                             **setting.omni_kw())
+    pipe.stereo()
+    pipe.track()
+    rec = pipe.results().cpu().numpy()
+    rp = refflow.RigParams(**rig_kw)
+    with gated_matching(setting):
+        frames = [refflow.stereo_frame(rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
+        want = [refflow.track_pair(rp, frames[2 * i], frames[2 * i + 1], s.thr, 210, seed=s.seed + i, adaptive=True, gp3p=True)
+                for i in range(s.B)]
+    full = s.reference(setting)[0]
+    M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
+    assert [int(x) for x in M] == [len(fr["X"]) for fr in frames]
+    assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
+    assert all(0 < a["n_cand"] < b["n_cand"] for a, b in zip(frames, full))      # the fraction bites in every frame
+    mask = pipe.ransac["mask"].cpu().numpy()
+    cq, ct = pipe.corr["q"].cpu().numpy(), pipe.corr["t"].cpu().numpy()
+    for i, w in enumerate(want):
+        n = len(w["corr"]["cam"])
+        assert n > 0 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
+        assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
+        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64))
+    batch = FramePairBatch(ctx, s.model, RigConfig(**rig_kw), s.B, num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048,
+                           seed=s.seed, **s.solver, **setting.omni_kw())
+    batch.load_frames(s.omni)
+    got = batch.step()
+    ctx.synchronize()
+    assert np.array_equal(got.cpu().numpy().view(np.uint64), rec.view(np.uint64))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_one_call_batches_equal_the_gated_refflow(ctx, pairs, name):
+    s, setting = pairs, BY_NAME[name]
+    want = np.stack([_record(w) for w in s.reference(setting)[1]])
+    kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, seed=s.seed, **s.solver, **setting.omni_kw())
+    for ns in (1, 2):
+        batch = FramePairBatch(ctx, s.model, RigConfig(**s.rig_kw), s.B, n_streams=ns, **kw)
+        batch.workspace.fill_(0xA5)
+        batch.load_frames(s.omni)
+        for _ in range(2):
+            got = batch.step().clone()
+            ctx.synchronize()
+            assert np.array_equal(got.cpu().numpy().view(np.uint64), want.view(np.uint64)), ns
+        if ns == 2:                                          # the enqueue / join form
+            bufs = [torch.zeros_like(batch.out), torch.zeros_like(batch.out)]
+            for k in range(4):
+                batch.enqueue(bufs[k & 1])
+            batch.join()
+            ctx.synchronize()
+            for b in bufs:
+                assert np.array_equal(b.cpu().numpy().view(np.uint64), want.view(np.uint64))
+    assert not np.array_equal(want[:, :12], np.stack([_record(w) for w in s.reference(OFF)[1]])[:, :12])
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_sequence_engine_equals_the_gated_refflow_for_windows_1_and_5(ctx, pairs, name):
+    from vo_single_camera_sos_amd.pipeline import MultiSequenceEngine, SequenceEngine
+    s, setting = pairs, BY_NAME[name]
+    want = np.stack([_record(w) for w in s.reference(setting)[2]])
+    kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, **s.solver, **setting.omni_kw())
+    n = 2 * s.B
+    for window in (1, 5):
+        eng = SequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), window=window, **kw)
+        got = []
+        for w0 in range(0, n, window):
+            got += [info["spec"] for info in eng.push_window(list(s.omni[w0:w0 + window])) if info["spec"] is not None]
+        assert np.array_equal(np.stack(got).view(np.uint64), want.view(np.uint64)), window
+    assert MultiSequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), lanes=2, window=2, **kw).cfg.ransac_flags == eng.cfg.ransac_flags
+
+
+# ---- 4. RGB-D --------------------------------------------------------------------------------------------------------------
+FX = FY = 554.256258
+CX, CY = 319.5, 239.5
+RGBD_SETTINGS = [Setting("f2f", False, True), Setting("f2f_cap80", False, True, 80), Setting("f2f_with_cross_check", False, True, None, True)]
+
+
+@pytest.fixture(scope="module")
+def rgbd(ctx):
+    s = _Pairs()
+    s.B, s.nfeat = 2, 1000
+    yaw = np.deg2rad(40.0)
+    R_yaw = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
+    bgr, depth = [], []
+    for i in range(s.B):
+        rng = np.random.default_rng(900 + i)
+        room = synthetic.Room(seed=900 + i, half_x=(1800.0, 2600.0), half_y=(2500.0, 3500.0), cells=(150.0, 40.0))
+        R, t = synthetic.random_step(rng, max_t=80.0, max_deg=8.0)
+        for (Rw, tw) in ((R_yaw, np.zeros(3)), (R_yaw @ R, R_yaw @ t)):
+            im, dp = synthetic.render_rgbd(room, Rw, tw, rng, FX, FY, CX, CY, depth_is_Z=True)
+            bgr.append(im)
+            depth.append(dp)
+    s.bgr, s.depth = np.stack(bgr), np.stack(depth)
+    s.cam = RGBDCamConfig(fx=FX, fy=FY, center_x=CX, center_y=CY, depth_is_Z=True, min_range=0.8, max_range=7.0)
+    s.kw = dict(num_of_features=s.nfeat, max_iter=210, adaptive=True, pose_est_algorithm="EPNP")
+    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
+    s.rc = refflow.RGBDParams(FX, FY, CX, CY, s.cam.focal_length_m, True, 0.8, 7.0, s.cam.f2f_max_hdiff, 1.0)
+    s.frames = [refflow.rgbd_frame(s.rc, s.bgr[f], s.depth[f], s.nfeat, orb_pattern.orb_pattern(), ca, sa) for f in range(2 * s.B)]
+    s.thr = float(1.0 - np.cos(np.deg2rad(5.0)))
+    return s
+
+
+@pytest.mark.parametrize("setting", RGBD_SETTINGS, ids=[x.name for x in RGBD_SETTINGS])
+def test_rgbd_pair_paths_and_sequence_equal_the_gated_refflow(ctx, rgbd, setting):
+    from vo_single_camera_sos_amd.pipeline import RGBDSequenceEngine
+    s = rgbd
+    track = lambda a, b, seed: refflow.track_pair_rgbd(s.rc, s.frames[a], s.frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
+                                                       epnp=True)
+    with gated_matching(setting):
+        want = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+        want_seq = np.stack([_record(track(t - 1, t, t - 1)) for t in range(1, 2 * s.B)])
+    plain = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+    pipe = RGBDPairPipeline(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
+    pipe.load_frames(s.bgr, s.depth)
+    pipe.step()
+    rec, mask = pipe.results().cpu().numpy(), pipe.ransac["mask"].cpu().numpy()
+    cq, ct = pipe.corr["q"].cpu().numpy(), pipe.corr["t"].cpu().numpy()
+    for i, w in enumerate(want):
+        n = len(w["corr"]["q"])
+        assert n > 100 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
+        assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
+        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64)) and rec[i, 14] == 0
+        if not setting.cc and setting.cap is None:           # the plain correspondences are a subset of the gated ones
+            assert set(zip(plain[i]["corr"]["q"], plain[i]["corr"]["t"])) < set(zip(w["corr"]["q"], w["corr"]["t"]))
+    one = RGBDPairBatch(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
+    one.load_frames(s.bgr, s.depth)
+    got = one.step()
+    ctx.synchronize()
+    assert np.array_equal(got.cpu().numpy().view(np.uint64), rec.view(np.uint64))
+    for window in (1, 5):
+        eng = RGBDSequenceEngine(ctx, s.cam, window=window, **s.kw, **setting.rgbd_kw())
+        got = []
+        for w0 in range(0, 2 * s.B, window):
+            infos = eng.push_window([(s.bgr[i], s.depth[i]) for i in range(w0, min(2 * s.B, w0 + window))])
+            got += [info["spec"] for info in infos if info["spec"] is not None]
+        assert np.array_equal(np.stack(got).view(np.uint64), want_seq.view(np.uint64)), window
+
+
+def test_rgbd_refuses_gated_stereo(ctx):
+    from vo_single_camera_sos_amd import _lib
+    from vo_single_camera_sos_amd.device import SosvoError
+    cam = RGBDCamConfig(fx=FX, fy=FY, center_x=CX, center_y=CY, depth_is_Z=True, min_range=0.8, max_range=7.0)
+    one = RGBDPairBatch(ctx, cam, 1, num_of_features=100)
+    one.cfg.flags |= _lib.FLAG_GATED_STEREO
+    with pytest.raises(SosvoError, match="SOSVO_FLAG_GATED_STEREO"):
+        one.step()
+
+
+# ---- 5. run_VO: the sequence engines, the mirror path, run_VO_many -------------------------------------------------------
+def _read(results):
+    return tuple(open(os.path.join(results, f)).read() for f in FILES)
+
+
+def _sos_kwargs(seq, n, results):
+    return dict(gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"), img_filename_template=os.path.join(seq, "omni", "image-*.png"),
+                img_indices=list(range(n)), results_path=results)
+
+
+def _rgbd_kwargs(seq, n, results):
+    d = os.path.join(seq, "rgbd")
+    return dict(gt_poses_filename=os.path.join(d, "gt_TUM.txt"), img_filename_template=os.path.join(d, "rgb", "*.png"),
+                depth_filename_template=os.path.join(d, "depth", "*.png"), img_indices=list(range(n)), results_path=results)
+
+
+N_SEQ = 6
+
+
+@pytest.fixture(scope="module")
+def sos_sequences(tmp_path_factory):
+    gs, _ = _rig()
+    root = tmp_path_factory.mktemp("gated_sos")
+    seqs = []
+    for seed in (77, 61):
+        seq = str(root / ("seq_%d" % seed))
+        synthetic.write_sos_sequence(seq, gs, n_frames=N_SEQ, seed=seed, max_t=40.0, max_deg=2.0)
+        seqs.append(seq)
+    return seqs
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
+    """The pose file is byte-identical for frame windows 5 and 1, and the per-frame mirror path (frame_window 0: the
+    FeatureMatcher objects of the camera model, match_features_panoramic_top_bottom / match_features_frame_to_frame) gives
+    the same poses to rounding and the same keyframes."""
+    from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
+    seq, kw = sos_sequences[0], BY_NAME[name].run_vo_kw()
+    model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
+    outs, files = {}, {}
+    for w in (5, 1, 0):
+        res = str(tmp_path / ("w%d" % w))
+        outs[w] = run_VO(None, model, frame_window=w, **kw, **_sos_kwargs(seq, N_SEQ, res))
+        files[w] = _read(res)
+        assert outs[w]["tracked"] == N_SEQ - 1
+    assert files[5] == files[1] and "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
+    for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[5]["poses"]):
+        assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())
+    assert outs[0]["keyframe_ids"] == outs[5]["keyframe_ids"]
+    res = str(tmp_path / "off")
+    off = run_VO(None, model, frame_window=5, gated_matching=False, **_sos_kwargs(seq, N_SEQ, res))
+    assert off["tracked"] == N_SEQ - 1 and _read(res)[0] != files[5][0]
+    res = str(tmp_path / "none")                             # None is the tracker's own setting: off
+    run_VO(None, model, frame_window=5, gated_max_distance=80, **_sos_kwargs(seq, N_SEQ, res))
+    assert _read(res) == _read(str(tmp_path / "off"))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):
+    from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO, run_VO_many
+    gums = os.path.join(sos_sequences[0], "gums-calibrated.json")
+    kw = BY_NAME[name].run_vo_kw()
+    want = []
+    for k, seq in enumerate(sos_sequences):
+        res = str(tmp_path / ("solo_%d" % k))
+        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **_sos_kwargs(seq, N_SEQ, res))
+        assert out["tracked"] == N_SEQ - 1
+        want.append(_read(res))
+    many = [_sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
+    outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, **kw)
+    for q, files, o in zip(many, want, outs):
+        assert _read(q["results_path"]) == files
+        assert o["sequence_mode"]["lanes"] == 2
+    assert want[0] != want[1]
+
+
+def test_rgbd_run_vo(ctx, tmp_path):
+    from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
+    from vo_single_camera_sos_amd.omnistereo.transformations import rotation_matrix
+    seq = str(tmp_path / "seq_rgbd")
+    synthetic.write_rgbd_sequence(seq, n_frames=N_SEQ, seed=41, max_t=40.0, max_deg=2.0, depth_is_Z=False)
+    model = RGBDCamModel(fx=FX, fy=FY, center_x=CX, center_y=CY, scaling_factor=1. / 1000.0, do_undistortion=False,
+                         depth_is_Z=False, focal_length_m=1. / 1000.0)
+    model.T_Cest_wrt_Rgt = rotation_matrix(-np.pi / 2.0, [1, 0, 0])
+    files, outs = {}, {}
+    for w in (5, 1, 0):
+        res = str(tmp_path / ("w%d" % w))
+        outs[w] = run_VO(None, model, frame_window=w, gated_matching=True, gated_max_distance=80, **_rgbd_kwargs(seq, N_SEQ, res))
+        files[w] = _read(res)
+        assert outs[w]["tracked"] == N_SEQ - 1
+    assert files[5] == files[1]
+    for (i, Ta), (_, Tb) in zip(outs[5]["poses"], outs[0]["poses"]):
+        assert np.allclose(Ta, Tb, rtol=1e-9, atol=1e-12), (i, np.abs(Ta - Tb).max())
+    res = str(tmp_path / "off")
+    run_VO(None, model, frame_window=5, **_rgbd_kwargs(seq, N_SEQ, res))
+    assert _read(res)[0] != files[5][0]
+    with pytest.raises(ValueError, match="no static-stereo matcher"):
+        run_VO(None, model, frame_window=5, gated_matching="stereo", **_rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
+
+
+# ---- 6. the relations of the definition ---------------------------------------------------------------------------------------
+def _hamming_rows(a, b):
+    return POPCOUNT[a ^ b].sum(-1)
+
+
+def test_plain_matches_are_a_subset_of_the_gated_ones_on_the_six_rendered_pairs(ctx):
+    """The six rendered pairs of test_gpu_cross_check.py (seed 4100, GFT 1000 features, kp_cap 512, frame_cap 2048: no
+    capacity is reached).  Without a cap the plain stereo survivors of every frame are among the gated ones, and the plain
+    frame-to-frame (query, train) pairs of every pair and view among the gated ones; with cap 80 the same holds for the plain
+    matches whose distance is within the cap."""
+    B = 6
+    gs, rig_kw = _rig()
+    omni, _ = synthetic.make_frame_pairs(gs, B, seed=4100)
+    model = DeviceImageModel(ctx, gs, (480, 640))
+    fe = ImageFrontEnd(ctx, model, 2 * B, detection_method="GFT", num_of_features=1000, kp_cap=512)
+    fe.load_frames(omni)
+    fe.run()
+
+    def run(**kw):
+        pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), B, frame_cap=2048, max_iter=200, seed=11, front_end=fe, **kw)
+        pipe.stereo()
+        pipe.track()
+        ctx.synchronize()
+        fr = {k: v.cpu().numpy() for k, v in pipe.frames.items()}
+        co = {k: v.cpu().numpy() for k, v in pipe.corr.items()}
+        assert fr["M"].max() < 2048 and co["n"].max() < 4096    # neither frame_cap nor the correspondence capacity is reached
+        stereo = []
+        for f in range(2 * B):
+            m = int(fr["M"][f])
+            rows = np.hstack([fr["m_top"][f, :m], fr["m_bot"][f, :m]])
+            stereo.append(dict(zip(map(bytes, rows), _hamming_rows(fr["d_top"][f, :m], fr["d_bot"][f, :m]))))
+        f2f = []
+        for i in range(B):
+            n, nt = int(co["n"][i]), int(co["n_top"][i])
+            views = []
+            for view, (lo, hi) in enumerate(((0, nt), (nt, n))):
+                d = fr["d_top" if view == 0 else "d_bot"]
+                q, t = co["q"][i, lo:hi], co["t"][i, lo:hi]
+                views.append(dict(zip(zip(q.tolist(), t.tolist()), _hamming_rows(d[2 * i + 1][q], d[2 * i][t]))))
+            f2f.append(views)
+        return stereo, f2f
+    plain_s, plain_f = run()
+    for cap in (None, 80):
+        gated_s, _ = run(gated_stereo=True, gated_max_distance=cap)
+        _, gated_f = run(gated_f2f=True, gated_max_distance=cap)      # (on the plain frames: the same train and query sets)
+        within = (lambda d: True) if cap is None else (lambda d: d <= cap)
+        for f in range(2 * B):
+            assert {k for k, d in plain_s[f].items() if within(d)} <= set(gated_s[f]), (cap, f)
+            assert cap is None or max(gated_s[f].values()) <= cap
+        for i in range(B):
+            for view in range(2):
+                assert {k for k, d in plain_f[i][view].items() if within(d)} <= set(gated_f[i][view]), (cap, i, view)
+        print("cap %s: stereo points per frame plain %s gated %s; correspondences per pair plain %s gated %s" % (
+            cap, [len(x) for x in plain_s], [len(x) for x in gated_s], [len(a) + len(b) for a, b in plain_f],
+            [len(a) + len(b) for a, b in gated_f]))
+    assert min(len(x) for x in plain_s) > 300

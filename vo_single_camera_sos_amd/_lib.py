@@ -70,6 +70,8 @@ SIGNATURES = {
     "sosvo_detect_fast": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     "sosvo_detect_agast": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     "sosvo_match_hamming": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_match_hamming_gated": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64,
+                                          c_i32, c_p]),
     "sosvo_match_radius": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_cross_check_matches": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_sort_matches": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p]),
@@ -128,6 +130,10 @@ FLAG_GP3P = 4
 FLAG_TWOPT = 8
 FLAG_CROSS_CHECK_STEREO = 0x1000   # mutual matches only: static stereo (sosvo_batch_cfg.ransac_flags)
 FLAG_CROSS_CHECK_F2F = 0x2000      # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
+FLAG_GATED_STEREO = 0x4000         # search under the pixel gates: static stereo (sosvo_batch_cfg.ransac_flags)
+FLAG_GATED_F2F = 0x8000            # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
+GATED_MAX_DIST_SHIFT = 16          # SOSVO_GATED_MAX_DIST(d): bits 16-24, 0 = no cap
+GATED_MAX_DIST_MASK = 0x1FF << GATED_MAX_DIST_SHIFT
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1
 DETECTOR_FAST = 2
@@ -188,6 +194,17 @@ def rgbd_detector_flags(method):
 def cross_check_flags(stereo=False, f2f=False):
     """The SOSVO_FLAG_CROSS_CHECK_* bits of a batch configuration for the two matchers' switches."""
     return (FLAG_CROSS_CHECK_STEREO if stereo else 0) | (FLAG_CROSS_CHECK_F2F if f2f else 0)
+
+
+def gated_flags(stereo=False, f2f=False, max_distance=None):
+    """The SOSVO_FLAG_GATED_* bits and the SOSVO_GATED_MAX_DIST field of a batch configuration.  max_distance: None = no
+    cap (the field's 0), or 1 .. 256.  The cap belongs to the gated search: without a switch it is not encoded."""
+    if max_distance is not None and (int(max_distance) != max_distance or not 1 <= max_distance <= 256):
+        raise ValueError("gated_max_distance must be None or an integer in 1 .. 256, got %r" % (max_distance,))
+    flags = (FLAG_GATED_STEREO if stereo else 0) | (FLAG_GATED_F2F if f2f else 0)
+    if flags and max_distance is not None:
+        flags |= int(max_distance) << GATED_MAX_DIST_SHIFT
+    return flags
 
 
 def rgbd_flags_detector(flags):

@@ -63,7 +63,27 @@ bool cross_stereo(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLA
 bool cross_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
 bool cross_f2f(const sosvo_rgbd_batch_cfg& c) { return (c.flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
 // (an RGB-D camera has no static stereo to cross-check)
-bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) { return (c.flags & SOSVO_FLAG_CROSS_CHECK_STEREO) == 0; }
+bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) {
+  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO)) == 0;
+}
+
+// ---- gated matching (SOSVO_FLAG_GATED_*): the 1-NN search among the trains that pass the assemble stage's own pixel gate.
+// A Gate holds that stage's arguments; with `on` clear a matching step is the plain sosvo_match_hamming call it always was.
+struct Gate {
+  bool on;
+  double min_dv, max_du;
+  int32_t max_distance;
+};
+int32_t gate_cap(int32_t flags) { return SOSVO_GATED_MAX_DIST_OF(flags) ? SOSVO_GATED_MAX_DIST_OF(flags) : 256; }
+Gate gate_stereo(const sosvo_batch_cfg& c, const sosvo_rig& rig) {  // stereo_assemble_frame's sv_pixel_gate
+  return Gate{(c.ransac_flags & SOSVO_FLAG_GATED_STEREO) != 0, rig.stereo_min_disp, rig.stereo_max_hdiff, gate_cap(c.ransac_flags)};
+}
+Gate gate_f2f(const sosvo_batch_cfg& c, const sosvo_rig& rig) {  // f2f_assemble_kernel's: |du| only; off for f2f_max_hdiff <= 0 (< 0: gate skipped, 0: sv_pixel_gate passes all)
+  return Gate{(c.ransac_flags & SOSVO_FLAG_GATED_F2F) != 0, -1.0, rig.f2f_max_hdiff, gate_cap(c.ransac_flags)};
+}
+Gate gate_f2f(const sosvo_rgbd_batch_cfg& c) {  // f2f_assemble_central_kernel's
+  return Gate{(c.flags & SOSVO_FLAG_GATED_F2F) != 0, -1.0, c.f2f_max_hdiff, gate_cap(c.flags)};
+}
 
 // q == nullptr: static stereo, bucket p's query block is n + p (bottom view), its train block p (top view);
 // otherwise the slot pairs of a tracking call: query = current frame, train = reference frame
@@ -510,13 +530,23 @@ static int32_t mutual_tabs(sosvo_ctx* ctx, const int32_t* q, const int32_t* t, i
   return SOSVO_OK;
 }
 
-// One such step over the descriptor store `desc` (blocks of `stride` rows, counts `cnt`): ONE launch of n forward + n
-// role-swapped problems through the tables, then the filter on the forward keys.  The forward keys of `keys` [2 n, stride]
-// are sorted and assembled like those of a plain sosvo_match_hamming call.
-static int32_t match_mutual(sosvo_ctx* ctx, const uint8_t* desc, const int32_t* cnt, int n, int stride, const MutualTabs& m,
-                            uint32_t* keys) {
+// The 1-NN search of a matching step: under the gate g when it is on (positions q_pos / t_pos, indexed like the descriptors;
+// problems at and beyond n_forward have the roles swapped), plain otherwise.
+static int32_t match_1nn(sosvo_ctx* ctx, const Gate& g, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                         const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot, const int32_t* t_slot,
+                         int nprob, int n_forward, int stride, uint32_t* keys) {
+  if (!g.on) return sosvo_match_hamming(ctx, q_desc, t_desc, nq, nt, q_slot, t_slot, nprob, stride, stride, 1, keys);
+  return sosvo_match_hamming_gated(ctx, q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, nprob, n_forward, stride, stride,
+                                   g.min_dv, g.max_du, g.max_distance, keys);
+}
+
+// One such step over the descriptor store `desc` (blocks of `stride` rows, counts `cnt`, positions `pos`): ONE launch of n
+// forward + n role-swapped problems through the tables, then the filter on the forward keys.  The forward keys of `keys`
+// [2 n, stride] are sorted and assembled like those of a plain sosvo_match_hamming call.
+static int32_t match_mutual(sosvo_ctx* ctx, const Gate& g, const uint8_t* desc, const float* pos, const int32_t* cnt, int n,
+                            int stride, const MutualTabs& m, uint32_t* keys) {
   int32_t rc;
-  STAGE(sosvo_match_hamming(ctx, desc, desc, cnt, cnt, m.q_slot, m.t_slot, 2 * n, stride, stride, 1, keys));
+  STAGE(match_1nn(ctx, g, desc, desc, pos, pos, cnt, cnt, m.q_slot, m.t_slot, 2 * n, n, stride, keys));
   return sosvo_cross_check_matches(ctx, keys, keys + (size_t)n * stride, cnt, cnt, m.q_slot, m.t_slot, n, stride, stride, keys,
                                    nullptr);
 }
@@ -574,11 +604,12 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const float *kp_top = t.kp, *kp_bot = t.kp + (size_t)h * cap * 2;
   const uint8_t *desc_top = t.desc, *desc_bot = t.desc + (size_t)h * cap * 32;
   const int32_t *n_top = t.n, *n_bot = t.n + h;
-  if (cross_stereo(*cfg)) {  // (top and bottom are the two halves of t.desc / t.n: blocks p and h + p)
+  const Gate gate = gate_stereo(*cfg, *rig);
+  if (cross_stereo(*cfg)) {  // (top and bottom are the two halves of t.desc / t.kp / t.n: blocks p and h + p)
     STAGE(mutual_tabs(ctx, nullptr, nullptr, h, t.mutual));
-    STAGE(match_mutual(ctx, t.desc, t.n, h, cap, t.mutual, t.s_keys));
+    STAGE(match_mutual(ctx, gate, t.desc, t.kp, t.n, h, cap, t.mutual, t.s_keys));
   } else
-    STAGE(sosvo_match_hamming(ctx, desc_bot, desc_top, n_bot, n_top, nullptr, nullptr, h, cap, cap, 1, t.s_keys));
+    STAGE(match_1nn(ctx, gate, desc_bot, desc_top, kp_bot, kp_top, n_bot, n_top, nullptr, nullptr, h, h, cap, t.s_keys));
   STAGE(sosvo_sort_matches(ctx, t.s_keys, n_bot, nullptr, h, cap, t.s_order));
   if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
     STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
@@ -599,16 +630,17 @@ static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_ba
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
   int32_t rc;
   const bool mutual = cross_f2f(*cfg);
+  const Gate gate = gate_f2f(*cfg, *rig);
   if (mutual) {  // (one pair of tables serves both views)
     STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
-    STAGE(match_mutual(ctx, s.d_top, s.M, B, Fc, b.mutual, b.k_top));
+    STAGE(match_mutual(ctx, gate, s.d_top, s.m_top, s.M, B, Fc, b.mutual, b.k_top));
   } else
-    STAGE(sosvo_match_hamming(ctx, s.d_top, s.d_top, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_top));
+    STAGE(match_1nn(ctx, gate, s.d_top, s.d_top, s.m_top, s.m_top, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_top));
   STAGE(sosvo_sort_matches(ctx, b.k_top, s.M, b.cur_frame, B, Fc, b.o_top));
   if (mutual)
-    STAGE(match_mutual(ctx, s.d_bot, s.M, B, Fc, b.mutual, b.k_bot));
+    STAGE(match_mutual(ctx, gate, s.d_bot, s.m_bot, s.M, B, Fc, b.mutual, b.k_bot));
   else
-    STAGE(sosvo_match_hamming(ctx, s.d_bot, s.d_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.k_bot));
+    STAGE(match_1nn(ctx, gate, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
   STAGE(sosvo_sort_matches(ctx, b.k_bot, s.M, b.cur_frame, B, Fc, b.o_bot));
   STAGE(sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top,
                            b.o_top, b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top));
@@ -849,11 +881,12 @@ static int32_t run_rgbd_tracking(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg
                                  const RgbdTrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
   const int Fc = cfg->frame_cap;
   int32_t rc;
+  const Gate gate = gate_f2f(*cfg);
   if (cross_f2f(*cfg)) {
     STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
-    STAGE(match_mutual(ctx, s.d, s.M, B, Fc, b.mutual, b.keys));
+    STAGE(match_mutual(ctx, gate, s.d, s.m, s.M, B, Fc, b.mutual, b.keys));
   } else
-    STAGE(sosvo_match_hamming(ctx, s.d, s.d, s.M, s.M, b.cur_frame, b.ref_frame, B, Fc, Fc, 1, b.keys));
+    STAGE(match_1nn(ctx, gate, s.d, s.d, s.m, s.m, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.keys));
   STAGE(sosvo_sort_matches(ctx, b.keys, s.M, b.cur_frame, B, Fc, b.order));
   STAGE(sosvo_f2f_assemble_central(ctx, cfg->pct_good_matches, cfg->f2f_max_hdiff, s.m, s.X, s.b, s.M, Fc, b.ref_frame,
                                    b.cur_frame, b.keys, b.order, B, Fc, b.f, b.p, b.cq, b.ct, b.cn));
@@ -884,7 +917,7 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   SOSVO_REQUIRE(ctx, cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384,
                 "kp_cap / frame_cap out of range");
   SOSVO_REQUIRE(ctx, detector_ok(rgbd_detector(*cfg), cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
-  SOSVO_REQUIRE(ctx, rgbd_flags_ok(*cfg), "SOSVO_FLAG_CROSS_CHECK_STEREO: an RGB-D camera has no static stereo");
+  SOSVO_REQUIRE(ctx, rgbd_flags_ok(*cfg), "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO: an RGB-D camera has no static stereo");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
   const RgbdWorkspace ws = carve_rgbd(*cfg, F, F, workspace);

@@ -391,6 +391,38 @@ class Context(object):
                    _ptr(t_slot), P, Sq, St, int(k), _ptr(keys))
         return keys
 
+    def match_hamming_gated(self, q_desc, t_desc, q_pos, t_pos, nq, nt, min_dv, max_du, max_distance=None, keys=None,
+                            q_slot=None, t_slot=None, n_forward=None):
+        """The 1-NN search of match_hamming among the trains that pass the pixel gate: q_pos [Bq, Sq, 2] / t_pos [Bt, St, 2]
+        f32 are the (u, v) of the descriptor rows; gate = |u_t - u_q| <= max_du (if max_du > 0) and v_t - v_q >= min_dv (if
+        min_dv >= 0), in double.  max_distance: None = no cap, else 0 .. 256.  Problems p >= n_forward (default: none) are
+        reversed (v_q - v_t >= min_dv).  -> keys [P, Sq, 1] u32, KEY_NONE where no admissible train is within the cap."""
+        _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
+        _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
+        Bq, Sq = q_desc.shape[0], q_desc.shape[1]
+        Bt, St = t_desc.shape[0], t_desc.shape[1]
+        _check(q_pos, torch.float32, "q_pos", (Bq, Sq, 2))
+        _check(t_pos, torch.float32, "t_pos", (Bt, St, 2))
+        _check(nq, torch.int32, "nq", (Bq,))
+        _check(nt, torch.int32, "nt", (Bt,))
+        if (q_slot is None) != (t_slot is None):
+            raise SosvoError("q_slot and t_slot go together")
+        if q_slot is not None:
+            P = q_slot.shape[0]
+            _check(q_slot, torch.int32, "q_slot", (P,))
+            _check(t_slot, torch.int32, "t_slot", (P,))
+        else:
+            if Bq != Bt:
+                raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
+            P = Bq
+        if keys is None:
+            keys = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
+        _check(keys, torch.uint32, "keys", (P, Sq, 1))
+        self._call(self._lib.sosvo_match_hamming_gated, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq), _ptr(nt),
+                   _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
+                   float(max_du), 256 if max_distance is None else int(max_distance), _ptr(keys))
+        return keys
+
     def match_l2(self, q_desc, t_desc, nq, nt, k=1):
         """Float descriptors: q_desc [P, Sq, dim] f32, t_desc [P, St, dim] f32 -> keys [P, Sq, k] int64 holding the u64
         (float32 distance bits << 32 | train index); all ones (-1) if absent."""

@@ -137,7 +137,11 @@ class FeatureMatcher(object):
     cross_check=True is the matcher the reference carries commented out at :401, cv2.BFMatcher(NORM_HAMMING,
     crossCheck=True): a query keeps its best match only if that train descriptor's best query is the query itself (first
     index on ties, both ways).  As in OpenCV it goes with one match per query only: k_best 1, no radius match; and here with
-    binary descriptors only (ValueError otherwise)."""
+    binary descriptors only (ValueError otherwise).
+    gated=True (with gated_max_distance=None or 1 .. 256) marks the matcher for the search under the pixel gates: the
+    callers that know the keypoint positions and the gate (match_features_panoramic_top_bottom,
+    match_features_frame_to_frame) then call match_gated / match_gated_many in place of match; match itself has no
+    positions and stays the plain search.  Same restrictions as cross_check, and both may be set: mutual under the gate."""
 
     def __init__(self, method, matcher_type, k_best, *args, **kwargs):
         self.feature_detection_method = method
@@ -154,6 +158,21 @@ class FeatureMatcher(object):
         self._ctx = kwargs.get("context", None)
         self.cross_check = bool(kwargs.get("cross_check", False))
         self._check_cross_check()
+        self.gated = bool(kwargs.get("gated", False))
+        self.gated_max_distance = kwargs.get("gated_max_distance", None)
+        if self.gated:
+            self._check_gated(self.gated_max_distance)
+
+    def _check_gated(self, max_distance=None):
+        if self.k_best != 1:
+            raise ValueError("gated matching goes with k_best == 1 only")
+        if self.use_radius_match:
+            raise ValueError("gated matching is defined for best-match search, not for radius match")
+        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
+            raise ValueError("gated matching is built for binary (Hamming) descriptors only; %r makes float descriptors"
+                             % self.feature_detection_method)
+        if max_distance is not None and (int(max_distance) != max_distance or not 0 <= max_distance <= 256):
+            raise ValueError("gated matching: max_distance must be None or an integer in 0 .. 256, got %r" % (max_distance,))
 
     def _check_cross_check(self):
         if not self.cross_check:
@@ -233,6 +252,61 @@ class FeatureMatcher(object):
                 o, k = o[k != KEY_NONE], k[k != KEY_NONE]
             out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
         return out
+
+    def match_gated_many(self, items, min_dv, max_du, max_distance=None):
+        """[(query_descriptors, train_descriptors, query_pts, train_pts), ...] -> [(query_idx, train_idx, distance), ...] as
+        match_arrays_many, each query searching among the trains that pass the pixel gate (Context.match_hamming_gated):
+        |u_train - u_query| <= max_du (if max_du > 0) and v_train - v_query >= min_dv (if min_dv >= 0) on the float32
+        positions *_pts [n, >= 2] (u, v), in double.  max_distance: None = no cap, else 0 .. 256.  A query without an
+        admissible train within the cap has no match.  With cross_check the role-swapped search runs under the same gate.
+        One launch (two with cross_check) and one copy back for all items."""
+        import torch
+        self._check_cross_check()
+        self._check_gated(max_distance)
+        if any(self._is_float(q) or self._is_float(t) for q, t, _, _ in items):
+            raise ValueError("gated matching is built for binary (Hamming) descriptors only, not float descriptors")
+        P = len(items)
+        if P == 0:
+            return []
+        ctx = self._context()
+        qs = [np.ascontiguousarray(np.asarray(q)).reshape(-1, 32) for q, _, _, _ in items]
+        ts = [np.ascontiguousarray(np.asarray(t)).reshape(-1, 32) for _, t, _, _ in items]
+        for name, arrs in (("query_descriptors", qs), ("train_descriptors", ts)):
+            for a in arrs:
+                if a.dtype != np.uint8:
+                    raise NotImplementedError("%s: dtype %s -- only uint8 (binary, Hamming) descriptors are built" % (name, a.dtype))
+        nq, nt = np.array([a.shape[0] for a in qs], np.int32), np.array([a.shape[0] for a in ts], np.int32)
+        cq, ct = max(1, int(nq.max())), max(1, int(nt.max()))
+        hq, ht = np.zeros((P, cq, 32), np.uint8), np.zeros((P, ct, 32), np.uint8)
+        pq, pt = np.zeros((P, cq, 2), np.float32), np.zeros((P, ct, 2), np.float32)
+        for i, (_, _, q_pts, t_pts) in enumerate(items):
+            hq[i, :nq[i]], ht[i, :nt[i]] = qs[i], ts[i]
+            for dst, pts, n, name in ((pq, q_pts, nq[i], "query_pts"), (pt, t_pts, nt[i], "train_pts")):
+                a = np.asarray(pts, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 2))
+                if a.shape[1] < 2:
+                    raise ValueError("%s: expected [n, 2] pixel positions" % name)
+                dst[i, :n] = a[:, :2]
+        dev = ctx.device
+        nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
+        dq, dt, dpq, dpt = (torch.from_numpy(a).to(dev) for a in (hq, ht, pq, pt))
+        keys = ctx.match_hamming_gated(dq, dt, dpq, dpt, nq_d, nt_d, min_dv, max_du, max_distance)
+        if self.cross_check:    # the role-swapped search under the same gate (all its problems reversed), then the filter
+            rev = ctx.match_hamming_gated(dt, dq, dpt, dpq, nt_d, nq_d, min_dv, max_du, max_distance, n_forward=0)
+            ctx.cross_check_matches(keys, rev, nq_d, nt_d, keys_out=keys)
+        order = ctx.sort_matches(keys, nq_d)
+        from .._lib import KEY_SHIFT, KEY_IDX_MASK, KEY_NONE
+        kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
+        out = []
+        for i in range(P):
+            o = oh[i, :nq[i]]
+            k = kh[i][o]
+            o, k = o[k != KEY_NONE], k[k != KEY_NONE]      # (the queries without a match sorted last)
+            out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
+        return out
+
+    def match_gated(self, query_desc, train_desc, query_pts, train_pts, min_dv, max_du, max_distance=None):
+        """match() under the pixel gates -> MatchList, ascending by distance, ties in query order (see match_gated_many)."""
+        return MatchList(*self.match_gated_many([(query_desc, train_desc, query_pts, train_pts)], min_dv, max_du, max_distance)[0])
 
     @staticmethod
     def _is_float(d):

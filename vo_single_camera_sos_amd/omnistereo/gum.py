@@ -299,7 +299,12 @@ class GUMStereo(object):
         fm = self.feature_matcher_for_static_stereo
         sel_top, sel_bot, dsel_top, dsel_bot = [], [], [], []
         buckets = [b for b in zip(keypts_list_top, desc_list_top, keypts_list_bot, desc_list_bot) if len(b[0]) and len(b[2])]
-        matched = fm.match_arrays_many([(bot_d, top_d) for _, top_d, _, bot_d in buckets])   # all buckets in one launch
+        if getattr(fm, "gated", False):   # the search under the gate that filter_pixel_correspondences applies below
+            matched = fm.match_gated_many([(bot_d, top_d, keypoints_to_array(bot_k), keypoints_to_array(top_k))
+                                           for top_k, top_d, bot_k, bot_d in buckets], min_rectified_disparity,
+                                          max_horizontal_diff, fm.gated_max_distance)
+        else:
+            matched = fm.match_arrays_many([(bot_d, top_d) for _, top_d, _, bot_d in buckets])   # all buckets in one launch
         for (top_k, top_d, bot_k, bot_d), (q, t, _) in zip(buckets, matched):
             good = int(fm.percentage_good_matches * len(q))
             if good > 0:

@@ -120,7 +120,13 @@ def match_features_frame_to_frame(cam_model, train_kpts, train_desc, query_kpts,
     sorted matches; gate |du| <= max_horizontal_diff (no wrap-around, as the reference).
     -> (train idx, train kpts, train desc), (query idx, query kpts, query desc), colours"""
     fm = cam_model.feature_matcher_for_motion
-    q, t, _ = fm.match_arrays(query_desc, train_desc)
+    if getattr(fm, "gated", False):   # the search under the |du| gate applied below (off when that gate is off)
+        pts = [keypoints_to_array(k) if p is None else np.asarray(p)
+               for k, p in ((query_kpts, keypts_as_points_query), (train_kpts, keypts_as_points_train))]
+        q, t, _ = fm.match_gated_many([(query_desc, train_desc, pts[0], pts[1])], -1.0, max_horizontal_diff,
+                                      fm.gated_max_distance)[0]
+    else:
+        q, t, _ = fm.match_arrays(query_desc, train_desc)
     matched_train_indices, matched_query_indices = [], []
     matched_kpts_train, matched_kpts_query, matched_desc_train, matched_desc_query, random_colors = [], [], [], [], []
     good = int(fm.percentage_good_matches * len(q))
@@ -244,6 +250,10 @@ class TrackerSE3(object):
         # the matchers' crossCheck: off, as the reference builds them (camera_models.py:401-402); see set_cross_check
         self.cross_check_static_stereo = False
         self.cross_check_for_motion = False
+        # the search under the pixel gates (FeatureMatcher.match_gated): off; see set_gated_matching
+        self.gated_static_stereo = False
+        self.gated_for_motion = False
+        self.gated_max_distance = None
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -282,12 +292,14 @@ class TrackerStereoSE3(TrackerSE3):
         om.feature_matcher_for_static_stereo = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_static_stereo,
-            use_radius_match=False, cross_check=self.cross_check_static_stereo)
+            use_radius_match=False, cross_check=self.cross_check_static_stereo, gated=self.gated_static_stereo,
+            gated_max_distance=self.gated_max_distance)
         self.max_horizontal_diff_f2f_matches = 0.125 * self.max_horizontal_search_ratio * om.top_model.panorama.cols
         om.feature_matcher_for_motion = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
-            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion)
+            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion,
+            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance)
         self.omni_mask_extra_padding = 10
         shape = None if om.current_omni_img is None else om.current_omni_img.shape[:2]
         if shape is None:
@@ -470,6 +482,41 @@ def _cross_check_of(fm):
     return bool(getattr(fm, "cross_check", False)) if fm is not None else False
 
 
+def set_gated_matching(tracker, gated_matching, gated_max_distance=None):
+    """Switch the search under the pixel gates (FeatureMatcher.match_gated) of the tracker's matchers: gated_matching as
+    parse_cross_check takes its argument (None: leave the tracker's own setting, and gated_max_distance is ignored);
+    gated_max_distance: None = no cap, or 1 .. 256.  The matchers bootstrap_tracker built carry the switch, so the per-frame
+    mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame
+    matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
+    from .._lib import gated_flags
+    if gated_matching is None:
+        return
+    try:
+        stereo, f2f = parse_cross_check(gated_matching)
+    except ValueError:
+        raise ValueError("gated_matching: None, True, False, \"stereo\", \"f2f\" or \"both\"; got %r" % (gated_matching,))
+    gated_flags(stereo, f2f, gated_max_distance)      # (ValueError for a cap outside 1 .. 256)
+    cm = tracker.camera_model
+    if _is_rgbd_model(cm):
+        if isinstance(gated_matching, str) and stereo:
+            raise ValueError("gated_matching=%r: an RGB-D tracker has no static-stereo matcher" % (gated_matching,))
+        stereo = False
+    cap = None if gated_max_distance is None else int(gated_max_distance)
+    tracker.gated_static_stereo, tracker.gated_for_motion, tracker.gated_max_distance = stereo, f2f, cap
+    for fm, on in ((getattr(cm, "feature_matcher_for_static_stereo", None), stereo),
+                   (getattr(cm, "feature_matcher_for_motion", None), f2f)):
+        if fm is not None:
+            fm.gated, fm.gated_max_distance = on, cap
+            if on:
+                fm._check_gated(cap)              # (k_best > 1, radius match, float descriptors: ValueError)
+
+
+def _gated_of(fm):
+    """(switch, cap) of a matcher, as the engine-cache keys carry them."""
+    on = bool(getattr(fm, "gated", False)) if fm is not None else False
+    return on, (getattr(fm, "gated_max_distance", None) if on else None)
+
+
 def _sos_engine_settings(tracker, camera_model, first_image):
     """What a sequence engine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
     StereoPanoramicFrame compute is built from -> (positional arguments after ctx, keyword arguments, cache key), or None
@@ -499,14 +546,20 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
     # the two matchers' crossCheck (what the mirror path matches with): part of the engine's configuration and of its key
     cc_stereo, cc_f2f = _cross_check_of(fm), _cross_check_of(getattr(om, "feature_matcher_for_motion", None))
+    # ... and their search under the gates.  The engine has one cap for both matchers (as set_gated_matching sets them)
+    (g_stereo, cap_stereo), (g_f2f, cap_f2f) = _gated_of(fm), _gated_of(getattr(om, "feature_matcher_for_motion", None))
+    if g_stereo and g_f2f and cap_stereo != cap_f2f:
+        return None
+    g_cap = cap_stereo if g_stereo else cap_f2f
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           cc_stereo, cc_f2f)
+           cc_stereo, cc_f2f, g_stereo, g_f2f, g_cap)
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
-                  cross_check_stereo=cc_stereo, cross_check_f2f=cc_f2f)
+                  cross_check_stereo=cc_stereo, cross_check_f2f=cc_f2f, gated_stereo=g_stereo, gated_f2f=g_f2f,
+                  gated_max_distance=g_cap)
     return (model, rig), kwargs, key
 
 
@@ -646,11 +699,12 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
-           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm))
+           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm)) + _gated_of(fm)
     kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
-                  detection_method=method, cross_check=_cross_check_of(fm))
+                  detection_method=method, cross_check=_cross_check_of(fm), gated_f2f=_gated_of(fm)[0],
+                  gated_max_distance=_gated_of(fm)[1])
     return (cam,), kwargs, key
 
 
@@ -716,7 +770,8 @@ class TrackerRGBDSE3(TrackerSE3):
         self.camera_model.feature_matcher_for_motion = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
-            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion)
+            use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion,
+            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance)
         self.max_horizontal_diff_f2f_matches = self.max_horizontal_search_ratio * (self.camera_model.center_x * 2.)
 
     def track_frame(self, reference_frame, current_frame):
@@ -926,7 +981,7 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
-           cross_check=None):
+           cross_check=None, gated_matching=None, gated_max_distance=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -945,7 +1000,11 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
     cross_check: mutual matches only, cv2.BFMatcher's crossCheck (camera_models.py:401).  None = the tracker's own setting
     (off); True / False = both matchers; "stereo" / "f2f" = the static-stereo / the frame-to-frame matcher alone (see
-    set_cross_check).  Sequence mode and the mirror path follow alike."""
+    set_cross_check).  Sequence mode and the mirror path follow alike.
+
+    gated_matching: the matchers search among the candidates that pass their pixel gates (the static-stereo gates / the
+    frame-to-frame |du| gate) instead of everywhere; same values as cross_check.  gated_max_distance: None = no cap, or
+    1 .. 256: a match whose Hamming distance exceeds it is no match (see set_gated_matching).  Off by default."""
     from .common_cv import get_depthmap_float32_from_png, get_images, imread
     from .common_tools import get_poses_from_file
     if visualizer_3D_VO is not None:
@@ -1034,6 +1093,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         tracker = trackerClass(camera_model=camera_model, show_3D_points=False, results_path=results_path)
         set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
         set_cross_check(tracker, cross_check)             # (likewise: it runs the matchers' crossCheck)
+        set_gated_matching(tracker, gated_matching, gated_max_distance)   # (... and their search under the gates)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1218,7 +1278,8 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
-                results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None):
+                results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
+                gated_matching=None, gated_max_distance=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1239,11 +1300,13 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
     return run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename=est_poses_filename,
                   results_path=results_path, thread_name=thread_name, _live_frames=frames,
                   _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
-                  detection_method=detection_method, cross_check=cross_check)
+                  detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                  gated_max_distance=gated_max_distance)
 
 
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
-                   thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None):
+                   thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
+                   gated_matching=None, gated_max_distance=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1261,7 +1324,8 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
             time.sleep(0.001)   # (the reference starts tracking at once and stops if no frame has arrived yet)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, cam_working_thread=cam_working_thread,
                   est_poses_filename=est_poses_filename, results_path=scene_path_vo_results, thread_name=thread_name,
-                  frame_window=frame_window, detection_method=detection_method, cross_check=cross_check)
+                  frame_window=frame_window, detection_method=detection_method, cross_check=cross_check,
+                  gated_matching=gated_matching, gated_max_distance=gated_max_distance)
     result, failure = {}, []
     try:
         if use_multithreads_for_VO:
@@ -1286,7 +1350,8 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
 
 def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filename_template, depth_filename_template,
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
-              last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None):
+              last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
+              gated_matching=None, gated_max_distance=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1310,7 +1375,8 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
                   est_poses_filename=est_poses_filename, img_filename_template=scene_img_filename_template,
                   depth_filename_template=depth_filename_template, img_indices=vo_frame_indices,
                   results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window,
-                  detection_method=detection_method, cross_check=cross_check)
+                  detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                  gated_max_distance=gated_max_distance)
     result = {}
     if use_multithreads_for_VO:
         # one libsosvo context per host thread: the worker creates its own
@@ -1343,7 +1409,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
-                _keyframe_thresholds=None, cross_check=None):
+                _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1436,6 +1502,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
             i, q = job
             try:
                 out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method, cross_check=cross_check,
+                             gated_matching=gated_matching, gated_max_distance=gated_max_distance,
                              _keyframe_thresholds=_keyframe_thresholds, _engine_for=engine_for_lane(s), **q)
                 if "sequence_mode" in out:
                     out["sequence_mode"].update(lane=s, lanes=S)
@@ -1467,7 +1534,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 
 
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
-                   frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None):
+                   frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
+                   gated_max_distance=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1487,6 +1555,7 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
                               img_indices=list(range(first_image_index, last, step_for_scene_images)),
                               results_path=sc["scene_path_vo_results"], thread_name=sc.get("thread_name", "")))
     results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window,
-                          detection_method=detection_method, lanes=lanes, shard=shard, cross_check=cross_check)
+                          detection_method=detection_method, lanes=lanes, shard=shard, cross_check=cross_check,
+                          gated_matching=gated_matching, gated_max_distance=gated_max_distance)
     print("Done with VO for %d sequences!" % len(results))
     return results
