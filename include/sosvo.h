@@ -110,7 +110,7 @@ int32_t sosvo_debug_fill_scratch(sosvo_ctx* ctx, int32_t byte);
  *       NaN entries give the border colour 0
  *   pano  [2, nframes, rows, cols, 3] u8 -- VIEW-MAJOR: image i = view * nframes + frame
  * Arithmetic: coordinates rounded to 1/32 px (ties to even), weights (32-fx)(32-fy),
- * (sum + 512) >> 10; taps outside the image read 0.                                            */
+ * (sum + 512) >> 10; taps outside the image read 0.  1 <= H, W <= 16384, every such frame size.  */
 int32_t sosvo_unwrap(sosvo_ctx* ctx, const uint8_t* omni, const uint8_t* masks, const float* map_x,
                      const float* map_y, int32_t nframes, int32_t H, int32_t W, int32_t rows,
                      int32_t cols, uint8_t* pano);
@@ -120,7 +120,13 @@ int32_t sosvo_unwrap(sosvo_ctx* ctx, const uint8_t* omni, const uint8_t* masks, 
  * [2, rows, cols, 2] u32 once per model (an opaque 8-byte entry per panorama pixel: the byte offset of the first
  * tap and the four blend weights; the table is specific to (H, W), and frames larger than 4 MB take a slower,
  * still exact entry format); sosvo_unwrap_table then unwraps nframes frames with one 8-byte table load and two
- * unaligned 8-byte tap loads per panorama pixel.  H * W * 3 >= 2 * 3 * W + 8.                              */
+ * unaligned 8-byte tap loads per panorama pixel.
+ * FRAME SIZE of the table form: 1 <= H, W <= 16384 and 3 * W * (H - 1) >= 8, i.e. 8 bytes must follow the start of the
+ * frame's second row (the kernels load 8 bytes there for a panorama pixel without a valid tap).  That excludes one-row
+ * frames and 2 x 2; (2, 3), (3, 2) and (4, 1) are the smallest accepted.  sosvo_unwrap_prepare and every entry point that
+ * reads frames through the table refuse other sizes with SOSVO_ERR_ARG: sosvo_unwrap_table,
+ * sosvo_unwrap_median_gray[_rows], sosvo_frame_pair_batch[_streams[_enqueue]] and sosvo_sequence_front_end[_slots].  The
+ * map form sosvo_unwrap above has no such loads.                                                                  */
 int32_t sosvo_unwrap_prepare(sosvo_ctx* ctx, const uint8_t* masks, const float* map_x, const float* map_y,
                              int32_t H, int32_t W, int32_t rows, int32_t cols, uint32_t* table);
 int32_t sosvo_unwrap_table(sosvo_ctx* ctx, const uint8_t* omni, const uint32_t* table, int32_t nframes,
@@ -138,7 +144,8 @@ int32_t sosvo_median_gray(sosvo_ctx* ctx, const uint8_t* img, int32_t nimg, int3
  * sosvo_median_gray on its output): every lane unwraps its source pixel from the table on the fly, so the
  * colour panoramas (camera_models.py:2991-2996 -> :1711 -> :1714) are never written to HBM.
  *   omni [nframes, H, W, 3] u8, table from sosvo_unwrap_prepare -> gray [2 * nframes, rows, cols] u8
- *   (view-major).  ksize in {3, 5, 11}; 0 / 1 = no median: the pixel is unwrapped and converted to gray at once.   */
+ *   (view-major).  ksize in {3, 5, 11}; 0 / 1 = no median: the pixel is unwrapped and converted to gray at once.
+ *   H, W: the frame size of the table form (see sosvo_unwrap_prepare), for this call and the _rows form below.     */
 int32_t sosvo_unwrap_median_gray(sosvo_ctx* ctx, const uint8_t* omni, const uint32_t* table, int32_t nframes,
                                  int32_t H, int32_t W, int32_t rows, int32_t cols, int32_t ksize, uint8_t* gray);
 
@@ -631,7 +638,7 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
  *                n_correspondences, status (0 ok, 1 too few correspondences), best RANSAC iteration        */
 typedef struct sosvo_batch_cfg {
   int32_t n_pairs;
-  int32_t H, W;            /* omni frame */
+  int32_t H, W;            /* omni frame: 1 <= H, W <= 16384, 3 * W * (H - 1) >= 8 (see sosvo_unwrap_prepare) */
   int32_t rows, cols;      /* panorama (both mirrors) */
   int32_t nmask;           /* azimuthal masks per mirror */
   int32_t kp_cap;          /* keypoint capacity per (frame, mirror, mask) */
@@ -664,7 +671,8 @@ int32_t sosvo_frame_pair_batch(sosvo_ctx* ctx, const sosvo_rig* rig_host, const 
  * results are those of sosvo_frame_pair_batch, bit for bit.  The parts start after the work already queued on the context's
  * stream and the context's stream continues after all of them (events; no host synchronisation); the internal streams
  * and their scratch memory are created on first use and live as long as the context.
- * workspace: sosvo_frame_pair_batch_streams_workspace(cfg, n_streams) bytes, 256-aligned; n_pairs >= n_streams. */
+ * workspace: sosvo_frame_pair_batch_streams_workspace(cfg, n_streams) bytes, 256-aligned; n_pairs >= n_streams.  (H, W)
+ * as for sosvo_frame_pair_batch: a frame size the table form refuses is refused before any part starts. */
 size_t sosvo_frame_pair_batch_streams_workspace(const sosvo_batch_cfg* cfg, int32_t n_streams);
 int32_t sosvo_frame_pair_batch_streams(sosvo_ctx* ctx, const sosvo_rig* rig_host, const sosvo_batch_cfg* cfg_host,
                                        int32_t n_streams, const uint8_t* omni, const uint32_t* unwrap_table,
@@ -707,7 +715,8 @@ int32_t sosvo_frame_pair_batch_streams_join(sosvo_ctx* ctx);
  *   workspace: sosvo_sequence_workspace(cfg, window, slots) bytes, 256-aligned, caller-owned; the SAME (cfg, window,
  *   slots) on every call.
  * sosvo_sequence_front_end: the front end of n_frames <= window omni frames [n_frames, H, W, 3] u8 (device) -> store
- *   slots first_slot .. first_slot + n_frames - 1.  Asynchronous.
+ *   slots first_slot .. first_slot + n_frames - 1.  Asynchronous.  (H, W): the frame size of the table form (see
+ *   sosvo_unwrap_prepare); another is SOSVO_ERR_ARG, in the _slots form too.
  * sosvo_sequence_track: TrackerStereoSE3.track_frame for n_pairs (reference slot, current slot) pairs given as HOST
  *   arrays; pair i samples with seed + i -> results [n_pairs, 16] f64 (device) as sosvo_frame_pair_batch.  A pair's
  *   record depends only on its two slots' frames and its seed, so speculative tracking (every frame against its

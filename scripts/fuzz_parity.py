@@ -3,7 +3,8 @@
 
     python scripts/fuzz_parity.py --minutes 10 --seed 1 [--stages median,gft,fast,agast,match,radius,orb,unwrap,ransac,describe,relpose,l2sort,pipeline,rgbd,batch,cross_check,gated_match]
 
-Every case draws its own sizes and parameters (image sizes around the strip / chunk / tile borders of the kernels, ragged
+Every case draws its own sizes and parameters (image sizes around the strip / chunk / tile borders of the kernels, omni
+frames larger than 4 MB and at the 16384 limits for the unwrap table in about one `unwrap` case of eight, ragged
 problem counts, empty masks, fractional minimum distances, budgets that end a selection inside a round, duplicate
 descriptors, ...) from a generator seeded by (--seed, case number), runs the HIP stage through the C ABI and compares the
 result with the oracle's bit for bit.  The first mismatch stops the run and prints the stage, the case number and the drawn
@@ -27,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle  # noqa: E402
 from oracle import flow  # noqa: E402
+import unwrap_cases  # noqa: E402  (tests/)
 from vo_single_camera_sos_amd import orb_pattern  # noqa: E402
 from vo_single_camera_sos_amd.device import Context, SosvoError  # noqa: E402
 
@@ -429,12 +431,25 @@ def fuzz_describe(ctx, rng):
     return params, None
 
 
-def fuzz_unwrap(ctx, rng):
-    H, W = int(rng.integers(2, 80)), int(rng.integers(2, 120))
-    rows, cols, nf = int(rng.integers(1, 50)), int(rng.integers(1, 150)), int(rng.integers(1, 4))
-    ksize = int(rng.choice([0, 3, 5, 11]))
-    params = dict(H=H, W=W, rows=rows, cols=cols, nframes=nf, ksize=ksize)
-    omni = rng.integers(0, 256, (nf, H, W, 3), dtype=np.uint8)
+def draw_unwrap(rng):
+    """The frame, panorama and maps of an `unwrap` case (no GPU).  About one case in eight takes one of the frames larger
+    than 4 MB of tests/unwrap_cases.py with its maps (a) - (d): taps beyond byte 2^22 of a frame, which the table stores in
+    its edge format, W / H at the 16384 limit.  The others are small frames, never one the table form refuses (a frame
+    holds 8 bytes after the start of its second row, 3 W (H - 1) >= 8: include/sosvo.h)."""
+    large = rng.random() < 0.125
+    if large:
+        H, W = list(unwrap_cases.LARGE_FRAMES)[int(rng.integers(0, len(unwrap_cases.LARGE_FRAMES)))]
+        rows, cols = int(rng.integers(5, 50)), int(rng.integers(16, 150))
+    else:
+        H, W = int(rng.integers(2, 80)), int(rng.integers(2, 120))
+        if 3 * W * (H - 1) < 8:      # (2, 2), the one refused size of this range
+            H += 1
+        rows, cols = int(rng.integers(1, 50)), int(rng.integers(1, 150))
+    nf, ksize = int(rng.integers(1, 4)), int(rng.choice([0, 3, 5, 11]))
+    params = dict(H=H, W=W, rows=rows, cols=cols, nframes=nf, ksize=ksize, large=large)
+    if large:
+        mx, my = unwrap_cases.large_frame_maps(rng, H, W, (rows, cols))
+        return params, mx, my
     span = float(rng.choice([1.0, 1.3, 4.0]))   # maps that stay inside / leave the frame
     mx = (rng.uniform(-0.5 * (span - 1) * W - 5, W * (1 + 0.5 * (span - 1)) + 5, (2, rows, cols))).astype(np.float32)
     my = (rng.uniform(-0.5 * (span - 1) * H - 5, H * (1 + 0.5 * (span - 1)) + 5, (2, rows, cols))).astype(np.float32)
@@ -443,6 +458,13 @@ def fuzz_unwrap(ctx, rng):
         my = np.round(my * 64) / 64
     mx[rng.random(mx.shape) < 0.02] = np.nan
     my[rng.random(my.shape) < 0.02] = np.inf
+    return params, mx, my
+
+
+def fuzz_unwrap(ctx, rng):
+    params, mx, my = draw_unwrap(rng)
+    H, W, nf, ksize = params["H"], params["W"], params["nframes"], params["ksize"]
+    omni = rng.integers(0, 256, (nf, H, W, 3), dtype=np.uint8)
     masks = ((rng.random((2, H, W)) < rng.uniform(0.3, 1.0)).astype(np.uint8)) * 255
     use_mask = rng.random() < 0.7
     t_omni, t_masks, t_mx, t_my = _dev(ctx, omni, masks, mx.astype(np.float32), my.astype(np.float32))

@@ -86,6 +86,15 @@ static inline int32_t sosvo_fail(sosvo_ctx* ctx, int32_t code, const char* what,
     if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, __func__, msg); \
   } while (0)
 
+// Frames that are read through the unwrap table (sosvo_unwrap_prepare and every consumer of its table): the per-frame
+// kernels load 8 bytes at a tap's offset and at that offset + 3 W without a test, and the all-zero entry of a pixel without
+// valid taps stands for offset 0, so the 8 bytes from the start of the second row must lie inside the frame.
+static inline bool sosvo_table_frame_ok(int64_t H, int64_t W) {
+  return H > 0 && W > 0 && H <= 16384 && W <= 16384 && 3 * W * (H - 1) >= 8;
+}
+#define SOSVO_TABLE_FRAME_MSG \
+  "frame size out of range for the unwrap table: 1 <= H, W <= 16384 and 3 * W * (H - 1) >= 8 (8 bytes must follow the start of the second row)"
+
 #define SOSVO_HIP(ctx, call)                                                          \
   do {                                                                                \
     hipError_t e_ = (call);                                                           \

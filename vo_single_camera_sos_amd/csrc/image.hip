@@ -70,9 +70,13 @@ __global__ __launch_bounds__(kThreads) void unwrap_kernel(const uint8_t* __restr
 //                                    (0 for a tap outside the image or masked out: w00 <= 1024, the others <= 992)
 //         Both 8-byte row loads at off0 and off0 + 3 W lie inside the frame.  A pixel without valid taps is the
 //         all-zero entry.
-//   edge  (.y bit 31 = 1): a tap row starts before the frame or ends within its last 8 bytes (or the frame is
-//         larger than 4 MB): .x = (iy << 16) | (ix & 0xFFFF) (int16 each), .y = fx | fy << 5 | valid << 10 | 1 << 31
-//         (valid: 4 bits, tap t in-bounds and unmasked); the kernels clamp the loads and shift the bytes back.
+//   edge  (.y bit 31 = 1): a tap row starts before the frame or ends within its last 8 bytes (a frame-border pixel),
+//         or off0 >= 2^22 (per pixel, not per frame: of a frame larger than 4 MB the pixels whose first tap lies beyond
+//         byte 4 194 303 -- pixel index 1 398 102 onwards -- are edge entries, interior ones included, and the pixels
+//         before stay fast): .x = (iy << 16) | (ix & 0xFFFF) (int16 each; -4 <= ix <= W + 3 <= 16387, iy likewise),
+//         .y = fx | fy << 5 | valid << 10 | 1 << 31 (valid: 4 bits, tap t in-bounds and unmasked); the kernels rebuild
+//         the offset 3 ((iy + r) W + ix), clamp the loads to [0, frame_bytes - 8] and shift the bytes back (no shift
+//         for an interior pixel).  frame_bytes >= 8 follows from the frame-size rule of sosvo_table_frame_ok.
 // The per-frame kernels then do no float work, no mask loads, no bounds tests: one 8-byte table load, two
 // unaligned 8-byte tap loads (the two taps of a source row are adjacent pixels = 6 consecutive bytes) and 12
 // multiply-adds per pixel.
@@ -627,8 +631,8 @@ int32_t sosvo_unwrap_prepare(sosvo_ctx* ctx, const uint8_t* masks, const float* 
                              int32_t W, int32_t rows, int32_t cols, uint32_t* table) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, map_x && map_y && table, "null pointer");
-  SOSVO_REQUIRE(ctx, H > 0 && W > 0 && H <= 16384 && W <= 16384 && rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28),
-                "image sizes out of range");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(H, W), SOSVO_TABLE_FRAME_MSG);
+  SOSVO_REQUIRE(ctx, rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
   SOSVO_REQUIRE(ctx, ((uintptr_t)table & 7) == 0, "table must be 8-byte aligned");
   SOSVO_LAUNCH(ctx, unwrap_table_kernel, dim3(cdiv(rows * cols, kThreads), 2), dim3(kThreads), 0, ctx->stream, masks, map_x,
                map_y, H, W, rows * cols, reinterpret_cast<uint2*>(table));
@@ -641,8 +645,8 @@ int32_t sosvo_unwrap_table(sosvo_ctx* ctx, const uint8_t* omni, const uint32_t* 
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, omni && table && pano, "null pointer");
   SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= 32767, "nframes out of range");
-  SOSVO_REQUIRE(ctx, H > 0 && W > 0 && H <= 16384 && W <= 16384 && rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28),
-                "image sizes out of range");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(H, W), SOSVO_TABLE_FRAME_MSG);
+  SOSVO_REQUIRE(ctx, rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
   SOSVO_REQUIRE(ctx, ((uintptr_t)table & 7) == 0 && ((uintptr_t)pano & 3) == 0, "table / pano alignment");
   if (nframes == 0) return SOSVO_OK;
   SOSVO_LAUNCH(ctx, unwrap_lut_kernel, dim3((unsigned)(cdiv(rows * cols, kThreads) * 8 * cdiv(2 * nframes, 8))), dim3(kThreads), 0,
@@ -693,8 +697,8 @@ int32_t sosvo_unwrap_median_gray_rows(sosvo_ctx* ctx, const uint8_t* omni, const
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, omni && table && gray, "null pointer");
   SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= 32767, "nframes out of range");
-  SOSVO_REQUIRE(ctx, H > 0 && W > 0 && H <= 16384 && W <= 16384 && rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28),
-                "image sizes out of range");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(H, W), SOSVO_TABLE_FRAME_MSG);
+  SOSVO_REQUIRE(ctx, rows > 0 && cols > 0 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
   SOSVO_REQUIRE(ctx, ((uintptr_t)table & 7) == 0, "table must be 8-byte aligned");
   SOSVO_REQUIRE(ctx, ksize == 0 || ksize == 1 || ksize == 3 || ksize == 5 || ksize == 11, "ksize must be 0/1 (no median), 3, 5 or 11");
   if (nframes == 0) return SOSVO_OK;

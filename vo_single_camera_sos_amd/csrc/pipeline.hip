@@ -692,6 +692,7 @@ int32_t sosvo_frame_pair_batch(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
                                void* workspace, size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace && results, "null pointer");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(cfg->H, cfg->W), SOSVO_TABLE_FRAME_MSG);
   return run_frame_pairs(ctx, rig, cfg, omni, unwrap_table, mask_bits, pattern, workspace, workspace_bytes, results, nullptr,
                          nullptr);
 }
@@ -816,6 +817,7 @@ int32_t sosvo_frame_pair_batch_streams(sosvo_ctx* ctx, const sosvo_rig* rig, con
                                        const int8_t* pattern, void* workspace, size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace && results, "null pointer");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(cfg->H, cfg->W), SOSVO_TABLE_FRAME_MSG);
   return sosvo_frame_pair_batch_streams_impl(ctx, rig, cfg, n_streams, omni, unwrap_table, mask_bits, pattern, workspace, workspace_bytes, results, true);
 }
 
@@ -825,6 +827,7 @@ int32_t sosvo_frame_pair_batch_streams_enqueue(sosvo_ctx* ctx, const sosvo_rig* 
                                                size_t workspace_bytes, double* results) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig && cfg && omni && unwrap_table && mask_bits && pattern && workspace && results, "null pointer");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(cfg->H, cfg->W), SOSVO_TABLE_FRAME_MSG);
   return sosvo_frame_pair_batch_streams_impl(ctx, rig, cfg, n_streams, omni, unwrap_table, mask_bits, pattern, workspace, workspace_bytes, results, false);
 }
 
@@ -966,6 +969,8 @@ struct OmniSeq {
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
     return c && c->nmask >= 1 && c->nmask <= 32 && seq_shape_ok(c, c->detector, window, slots);
   }
+  static constexpr const char* kBadFrames = SOSVO_TABLE_FRAME_MSG;
+  static bool frames_ok(const Cfg* c) { return sosvo_table_frame_ok(c->H, c->W); }  // the front end reads them through the table
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return ::carve(c, window, slots, base); }
   static StoreFields fields(const FrameStore& s) {
     return {{(char*)s.m_top, (char*)s.m_bot, (char*)s.d_top, (char*)s.d_bot, (char*)s.X, (char*)s.b_top, (char*)s.b_bot},
@@ -990,6 +995,8 @@ struct RgbdSeq {
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
     return c && rgbd_flags_ok(*c) && seq_shape_ok(c, rgbd_detector(*c), window, slots);
   }
+  static constexpr const char* kBadFrames = "";
+  static bool frames_ok(const Cfg*) { return true; }  // no table: the RGB-D frames are the images
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return carve_rgbd(c, window, slots, base); }
   static StoreFields fields(const RgbdStore& s) {
     return {{(char*)s.m, (char*)s.d, (char*)s.X, (char*)s.b}, {8, 32, 24, 24}, s.M};
@@ -1032,6 +1039,7 @@ int32_t seq_front_end(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* c
   typename Fam::Ws ws;
   int32_t rc;
   const bool fits = slot_of_frame ? n_frames <= slots : first_slot >= 0 && first_slot + n_frames <= slots;
+  REQUIRE_FOR(ctx, fn, Fam::frames_ok(cfg), Fam::kBadFrames);  // (first: a frame size, not a matter of the workspace)
   STAGE(seq_open<Fam>(ctx, fn, cfg, window, slots, n_frames >= 0 && n_frames <= window && fits,
                       "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
   if (slot_of_frame) STAGE(check_slot_table(ctx, fn, slot_of_frame, n_frames, slots));

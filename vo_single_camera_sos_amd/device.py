@@ -151,7 +151,8 @@ class Context(object):
         return pano
 
     def unwrap_prepare(self, masks, map_x, map_y, omni_shape):
-        """Model constants -> packed unwrap table [2, rows, cols, 2] u32 (once per model)."""
+        """Model constants -> packed unwrap table [2, rows, cols, 2] u32 (once per model).  omni_shape (H, W): at most
+        16384 each and 3 * W * (H - 1) >= 8, the frame-size rule of the table form (include/sosvo.h)."""
         H, W = omni_shape
         if masks is not None:
             _check(masks, torch.uint8, "masks", (2, H, W))
