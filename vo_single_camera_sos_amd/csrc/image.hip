@@ -118,6 +118,7 @@ __global__ __launch_bounds__(kThreads) void unwrap_table_kernel(const uint8_t* _
 }
 
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+typedef uint16_t __attribute__((aligned(1))) u16_unaligned;
 typedef unsigned long long __attribute__((aligned(1))) u64_unaligned;
 
 // Tap loads of one table entry, unconditional and branch-free so that they can be issued a whole row ahead of
@@ -445,23 +446,29 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
   uint2 e_cur = make_uint2(0u, 0u), e_nxt = make_uint2(0u, 0u);
   unsigned long long taps[2] = {0ULL, 0ULL};
   bool any_edge = false;
-  uint32_t raw = 0u;
+  uint32_t raw = 0u, raw_hi = 0u;
   auto row_of = [&](int r) { return clampi(r, 0, rows - 1); };
   auto tab_entry = [&](int r) -> uint2 {
     return *reinterpret_cast<const uint2*>(tab + ((uint32_t)(row_of(r) * cols) * (uint32_t)sizeof(uint2) + tab_lane));
   };
-  auto load_raw = [&](int r) -> uint32_t {
+  // The buffer's last 3 bytes are loaded as 2 + 1 and joined where the row is used (pix = raw | raw_hi << 16), so that
+  // the load itself never waits (a wait here would sit right behind the deferred gray store of row_step).  raw_hi is
+  // written by these lanes alone; they sit on the last row and column and, rows being clamped, stay there: it is zero
+  // for every other lane and for these until then.
+  auto load_raw = [&](int r, uint32_t hi) -> uint2 {
     const int rr = row_of(r);
     const uint8_t* px = src + ((size_t)rr * cols + x_src) * 3;
-    if (!(last_image && rr == rows - 1 && x_src == cols - 1)) return *reinterpret_cast<const u32_unaligned*>(px);
-    return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16);  // the buffer's last 3 bytes
+    if (!(last_image && rr == rows - 1 && x_src == cols - 1)) return make_uint2(*reinterpret_cast<const u32_unaligned*>(px), hi);
+    return make_uint2((uint32_t)*reinterpret_cast<const u16_unaligned*>(px), (uint32_t)px[2]);
   };
   if (FUSED) {
     e_cur = tab_entry(out_lo - R);
     e_nxt = tab_entry(out_lo - R + 1);
     any_edge = unwrap_gather(src, frame_bytes, W, e_cur, taps);
   } else {
-    raw = load_raw(-R);
+    const uint2 px = load_raw(-R, 0u);
+    raw = px.x;
+    raw_hi = px.y;
   }
 
   uint32_t vzero;
@@ -475,19 +482,37 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
 #pragma unroll
       for (int j = 0; j < NW; ++j) Wp[c][b][j] = 0u;
 
+  // The gray byte of an output row is stored one row step LATE: it waits in `pend` and leaves at the top of the next
+  // step, after that step's wait for its source pixel and before its new loads are issued.  The store is then older
+  // than every load the following wait is for and has had a whole row of the wave's work to complete; stored at the
+  // end of its own row it was the youngest memory operation when the next row waited (a conditional store the
+  // compiler cannot count, hence s_waitcnt vmcnt(0)) and every wave stalled once per row for its acknowledgement.
+  // Output row r_src - R - 1 is pending at the top of source row r_src iff it is >= out_lo (uniform); the last
+  // output row, out_hi - 1, is flushed after the loop.
+  uint8_t pend = 0;
+  auto store_pending = [&](const int r_out) __attribute__((always_inline)) {
+    if (out_ok) dst[(uint32_t)(r_out * cols + x_out)] = pend;
+  };
   // one source row: ring slot = compile-time constant (the row loop below is unrolled K times by a fold)
   auto row_step = [&](auto slot_tag, const int r_src) __attribute__((always_inline)) {
     constexpr int slot = decltype(slot_tag)::value;
-    if (r_src >= out_hi + R) return;  // uniform (the tail of the last group)
+    if (r_src >= out_hi + R) return;  // uniform (the tail of the last group; the flush below stores its pending row)
     uint32_t pix;
     if (FUSED) {
       pix = unwrap_blend(frame_bytes, W, e_cur, taps, any_edge);
+      // the waits for this row's taps and for the next row's table entry stay above the store
+      asm volatile("" : "+v"(pix), "+v"(e_nxt.x), "+v"(e_nxt.y));
+      if (r_src - R - 1 >= out_lo) store_pending(r_src - R - 1);
       e_cur = e_nxt;
       any_edge = unwrap_gather(src, frame_bytes, W, e_cur, taps);   // row r_src + 1
       e_nxt = tab_entry(r_src + 2);                                  // row r_src + 2
     } else {
-      pix = raw;
-      raw = load_raw(r_src + 1);
+      pix = raw | (raw_hi << 16);
+      asm volatile("" : "+v"(pix));
+      if (r_src - R - 1 >= out_lo) store_pending(r_src - R - 1);
+      const uint2 nxt = load_raw(r_src + 1, raw_hi);
+      raw = nxt.x;
+      raw_hi = nxt.y;
     }
     // overwrite the oldest row slot with the new row's 24 bit-plane slices
     uint32_t sh = pix;  // bit b of every channel sits in the sign position of its byte
@@ -526,10 +551,11 @@ __global__ __launch_bounds__(kThreads) void median_gray_kernel(const uint8_t* __
       }
       med[c] = res;
     }
-    if (out_ok) dst[(uint32_t)(r_out * cols + x_out)] = bgr2gray_mad24(med[0], med[1], med[2]);
+    pend = bgr2gray_mad24(med[0], med[1], med[2]);
   };
   for (int r_base = out_lo - R; r_base < out_hi + R; r_base += K)
     for_each_slot(row_step, r_base, std::make_integer_sequence<int, K>{});
+  store_pending(out_hi - 1);  // the last source row, out_hi + R - 1, completed output row out_hi - 1 (out_hi > out_lo)
 }
 
 // launches the K-templated strip kernel; FUSED takes the omni batch + unwrap table instead of panoramas
