@@ -23,11 +23,9 @@ KEY_NONE = 0xFFFFFFFF
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, f) for f in os.listdir(_HERE) if f.endswith((".c", ".h"))]
-    stale = (not os.path.exists(LIB_PATH)) or any(
-        os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
-    if force or stale:
-        subprocess.check_call(["make", "-s", "-C", _HERE])
+    # make decides what is stale, every time: its prerequisites include the solver headers that the oracle shares with
+    # the product (vo_single_camera_sos_amd/csrc/, see the Makefile), which a list of this directory's files would miss
+    subprocess.check_call(["make", "-s", "-C", _HERE] + (["-B"] if force else []))
     return LIB_PATH
 
 

@@ -308,9 +308,9 @@ void orc_gauss7(const uint8_t* gray, int32_t rows, int32_t cols, uint8_t* out) {
 }
 
 /* ---- K6b: the 256 test pairs ----------------------------------------------------------------------
- * default: OpenCV's bit_pattern_31_ */
+ * default: OpenCV's bit_pattern_31_, the product's own table (csrc/orb_bit_pattern_31.h: one copy for both sides) */
 #include "orb_bit_pattern_31.h"
-void orc_orb_pattern_opencv(int8_t* pts /* [512][2] */) { memcpy(pts, orc_orb_bit_pattern_31, 1024); }
+void orc_orb_pattern_opencv(int8_t* pts /* [512][2] */) { memcpy(pts, sosvo_orb_bit_pattern_31_table, 1024); }
 
 /* the seeded pattern of rounds 1-3 (kept as an option) ------------------------------------------------
  * 512 points (x, y) as int8, |x|, |y| <= 12: sum of three uniform draws in [-4, 4] (bell-shaped, as the

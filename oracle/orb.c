@@ -395,7 +395,7 @@ int32_t orc_orb_describe_levels(const uint8_t* gray, int32_t rows, int32_t cols,
     float angle = kp[4 * i + 2];
     angle *= (float)(3.14159265358979323846 / 180.0);
     double sd, cd; /* trig_core.h: the same arithmetic as on the device */
-    orc_sincos((double)angle, &sd, &cd);
+    sv_sincos((double)angle, &sd, &cd);
     const float ca = (float)cd, sa = (float)sd;
     const int cx = (int)lrintf(x * scale), cy = (int)lrintf(y * scale);
     const int hh = hs[l], ww = ws[l];

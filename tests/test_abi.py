@@ -31,20 +31,39 @@ def test_abi_version_and_loud_failure_without_gpu():
             Context(0)
 
 
-def test_generated_device_headers_are_current():
-    """csrc/trig_core.h is the text of oracle/trig_core.h (tests/gen_device_headers.py): same arithmetic on both sides."""
-    import importlib.util
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("gen_device_headers", os.path.join(root, "tests", "gen_device_headers.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    assert mod.main(check=True), "run python tests/gen_device_headers.py"
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_CSRC = os.path.join(_ROOT, "vo_single_camera_sos_amd", "csrc")
+# the solver, trig and BRIEF-table headers that exist ONCE, under csrc/, and that the oracle's build reads from there
+_SHARED_HEADERS = ("trig_core.h", "ransac_core.h", "epnp_core.h", "gp3p_core.h", "relpose_core.h", "orb_bit_pattern_31.h")
+
+
+def test_no_header_name_exists_in_both_oracle_and_csrc():
+    """A quoted #include resolves next to the including file first: a header in oracle/ with the name of one in csrc/
+    would shadow the shared text in the oracle's build without any error."""
+    def headers(d):
+        return {f for f in os.listdir(d) if f.endswith(".h")}
+    assert set(_SHARED_HEADERS) <= headers(_CSRC)
+    both = headers(os.path.join(_ROOT, "oracle")) & headers(_CSRC)
+    assert not both, "in oracle/ and in csrc/: %s" % sorted(both)
+
+
+def test_oracle_build_reads_the_shared_headers_from_csrc():
+    """One text, and both builds read it: the preprocessor's dependency list of the oracle's sources, taken with the
+    oracle Makefile's own flags (`make deps` = $(CC) $(CFLAGS) -MM), names csrc/'s copy of every shared header and no
+    other file called *_core.h.  (The device build includes them by quoted name from csrc/ itself.)"""
+    import subprocess
+    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", os.path.join(_ROOT, "oracle"), "deps"], text=True)
+    deps = {os.path.realpath(w) for w in out.split() if w.endswith(".h")}
+    shared = {os.path.realpath(os.path.join(_CSRC, h)) for h in _SHARED_HEADERS}
+    assert shared <= deps, "not read by the oracle's build: %s" % sorted(shared - deps)
+    cores = {d for d in deps if d.endswith("_core.h")}
+    assert cores <= shared, "other *_core.h files in the oracle's build: %s" % sorted(cores - shared)
 
 
 def test_opencv_pattern_headers_and_c_entry_carry_the_data_file():
-    """data/orb_bit_pattern_31.txt (OpenCV's bit_pattern_31_) == the generated oracle / device headers == what the C ABI
-    hands out (sosvo_orb_bit_pattern_31: host memory, no context, no GPU)."""
+    """data/orb_bit_pattern_31.txt (OpenCV's bit_pattern_31_) == the generated header (one, under csrc/) == what the C ABI
+    hands out (sosvo_orb_bit_pattern_31: host memory, no context, no GPU) == what the oracle hands out
+    (orc_orb_pattern_opencv, compiled from the same header)."""
     import ctypes
     import importlib.util
     import os
@@ -59,3 +78,5 @@ def test_opencv_pattern_headers_and_c_entry_carry_the_data_file():
     assert _lib.load().sosvo_orb_bit_pattern_31(ctypes.c_void_p(buf.ctypes.data)) == 0
     assert np.array_equal(buf, orb_pattern.opencv_pattern())
     assert _lib.load().sosvo_orb_bit_pattern_31(None) != 0
+    import oracle
+    assert np.array_equal(oracle.orb_pattern(), orb_pattern.opencv_pattern())

@@ -100,8 +100,8 @@ def test_score_matches_reference_restatement():
 
 
 def test_trig_core_against_the_host_math_library():
-    """oracle/trig_core.h (sin / cos / atan from + - * / only, shared with the device): within one ulp of numpy over the
-    arguments of the path (azimuth in [0, 2 pi], elevation within +-pi/2, tan(elevation) a few units), exact at the
+    """csrc/trig_core.h (sin / cos / atan from + - * / only, one text for the oracle and the device): within one ulp of numpy
+    over the arguments of the path (azimuth in [0, 2 pi], elevation within +-pi/2, tan(elevation) a few units), exact at the
     awkward points."""
     import ctypes
     L = oracle.lib()

@@ -1,5 +1,5 @@
-"""The generalised P3P restatement (oracle/gp3p_core.h) checked by means that do not share its code:
-planted poses must be among the solutions; every returned pose must satisfy the three ray constraints (numpy
+"""The generalised P3P restatement (csrc/gp3p_core.h, the text shared with the device) checked by means that do not
+share its code: planted poses must be among the solutions; every returned pose must satisfy the three ray constraints (numpy
 evaluation); the real positive roots of the octic found by numpy.roots (companion-matrix eigenvalues) must be the
 depths of the returned solutions; the one-camera case must agree with Kneip's central P3P of the oracle; RANSAC with
 GP3P hypotheses must find the planted inliers of a contaminated two-mirror problem."""

@@ -107,8 +107,8 @@ def test_refine_converges_to_known_pose():
 
 
 def test_epnp_recovers_known_poses_and_sampler_is_distinct():
-    """EPnP restatement (oracle/epnp_core.h): noise-free 5..8-point problems give the planted pose to 1e-9; the
-    6-index sampler returns distinct in-range indices, deterministic in (seed, iteration); RANSAC with EPnP
+    """EPnP restatement (csrc/epnp_core.h, the text shared with the device, + oracle/epnp_eig12_plain.h): noise-free
+    5..8-point problems give the planted pose to 1e-9; the 6-index sampler returns distinct in-range indices, deterministic in (seed, iteration); RANSAC with EPnP
     hypotheses finds the planted inliers of a contaminated central problem."""
     rng = np.random.default_rng(3)
     worst = 0.0
@@ -123,7 +123,7 @@ def test_epnp_recovers_known_poses_and_sampler_is_distinct():
         T = oracle.epnp(f, P)
         assert T is not None
         worst = max(worst, np.abs(T[:, :3] - R).max(), np.abs(T[:, 3] - t).max())
-    assert worst < 2e-7, worst   # (Jacobi sweeps stop at off / diag < 1e-13, ORC_JACOBI12_TOL: 6e-8 here; 1e-9 with 1e-20)
+    assert worst < 2e-7, worst   # (Jacobi sweeps stop at off / diag < 1e-13, SV_JACOBI12_TOL: 6e-8 here; 1e-9 with 1e-20)
     assert oracle.epnp(np.ones((4, 3)), np.ones((4, 3))) is None and oracle.sample_distinct(5, 6, 1, 0) is None
     for it in range(50):
         s = oracle.sample_distinct(9, 6, 123, it)

@@ -1,5 +1,5 @@
-"""2D-2D relative-pose RANSAC restatement (oracle/relpose_core.h): the SCORE is pinned by the reference's own code
-(tests/golden/geometry_c2.npz does not hold it, so it is re-derived here in numpy from pose_est_tools.py:150-203); the
+"""2D-2D relative-pose RANSAC restatement (csrc/relpose_core.h, the text shared with the device): the SCORE is pinned
+by the reference's own code (tests/golden/geometry_c2.npz does not hold it, so it is re-derived here in numpy from pose_est_tools.py:150-203); the
 eight-, seven- and five-point solvers are checked against planted motions and independent numpy evaluations (SVD null
 space, epipolar residuals, the essential-matrix constraints); RANSAC finds the planted inliers with each of them."""
 import numpy as np

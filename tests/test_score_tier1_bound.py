@@ -70,7 +70,7 @@ def tier1(f, p, o, h, thr):
 
 
 def exact(f, p, o, h, thr):
-    """The reference's decision (oracle/ransac_core.h sv_score: no contraction) -> [m,n] bool."""
+    """The reference's decision (csrc/ransac_core.h sv_score as the oracle compiles it: no contraction) -> [m,n] bool."""
     with np.errstate(all="ignore"):
         w = []
         for k in range(3):

@@ -145,6 +145,34 @@ __host__ __device__ static inline float sosvo_ordered_float(uint32_t u) {
 }
 
 #ifdef __HIPCC__
+// Index i of a row / column of n mirrored into [0, n) without repeating the border element (OpenCV's BORDER_REFLECT_101).
+__device__ __forceinline__ int refl101(int i, int n) {
+  if (n == 1) return 0;
+  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
+  return i;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Value of the neighbouring lane through the DPP operand path (wave_shr:1 / wave_shl:1): a VALU move the compiler
+// folds into the consuming add/max where it can, instead of a ds_bpermute through the LDS crossbar -- the rolling
+// kernels issue 6-10 lane exchanges per row and the LDS pipe, shared by the four SIMDs of a CU, was their limit.
+// Lane 0 / 63 receive 0 (they are halo lanes).  Only valid where "neighbouring lane" = "neighbouring column",
+// i.e. not in the strips that touch the image border (mirrored columns): those keep the bpermute form.
+__device__ __forceinline__ int lane_from_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
+__device__ __forceinline__ int lane_from_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
+__device__ __forceinline__ float lane_from_left(float v) { return __int_as_float(lane_from_left(__float_as_int(v))); }
+__device__ __forceinline__ float lane_from_right(float v) { return __int_as_float(lane_from_right(__float_as_int(v))); }
+
+// k * x + acc with 24-bit k, x as ONE v_mad_u32_u24, every operand in a VGPR (the compiler multiplies 32-bit values with
+// v_mul_lo_u32 and adds separately; __umul24 does not survive its constant folding either).  Integer arithmetic: the
+// order of the additions does not matter.
+__device__ __forceinline__ uint32_t vmad24(uint32_t k, uint32_t x, uint32_t acc) {
+  uint32_t r;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(k), "v"(acc));
+  return r;
+}
+
 // Stable position of a lane's element among the valid elements of a workgroup round of NW waves (256 threads unless
 // said otherwise): wave ballot prefix + running base (*s_running is advanced by the round's total).  wave_off: NW + 1
 // ints of LDS.

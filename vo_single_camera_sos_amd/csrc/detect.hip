@@ -29,24 +29,6 @@ constexpr int kCandCapSmall = 2048;   // first pass of the two-pass selection: 1
 constexpr int kCandCapLarge = 16384; // large-mask variant (whole-image detection, cap > 1024): 128 KB of the 160 KB LDS
 constexpr int kMaxMasks = 32;
 
-__device__ __forceinline__ int refl101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-  return i;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// Value of the neighbouring lane through the DPP operand path (wave_shr:1 / wave_shl:1): a VALU move the compiler
-// folds into the consuming add/max where it can, instead of a ds_bpermute through the LDS crossbar -- the rolling
-// kernels issue 6-10 lane exchanges per row and the LDS pipe, shared by the four SIMDs of a CU, was their limit.
-// Lane 0 / 63 receive 0 (they are halo lanes).  Only valid where "neighbouring lane" = "neighbouring column",
-// i.e. not in the strips that touch the image border (mirrored columns): those keep the bpermute form.
-__device__ __forceinline__ int lane_from_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
-__device__ __forceinline__ int lane_from_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
-__device__ __forceinline__ float lane_from_left(float v) { return __int_as_float(lane_from_left(__float_as_int(v))); }
-__device__ __forceinline__ float lane_from_right(float v) { return __int_as_float(lane_from_right(__float_as_int(v))); }
-
 // Workgroup -> problem (image, mask) for the kernels that run one workgroup per problem and read that image's data (the
 // response map around the candidates, the blurred image under the descriptor patches): workgroups are dealt round-robin
 // over the 8 XCDs by linear id, so a plain p = blockIdx.x spreads the 12 masks of one image over all eight L2s and
@@ -786,15 +768,6 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   }
 }
 
-// a * b + c with 24-bit operands as ONE v_mad_u32_u24 (the compiler multiplies 32-bit values with v_mul_lo_u32 and adds
-// separately; __umul24 does not survive its constant folding either).  Integer arithmetic: the order of the additions
-// does not matter.
-__device__ __forceinline__ uint32_t mad24(uint32_t k, uint32_t x, uint32_t acc) {
-  uint32_t r;
-  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(k), "v"(acc));
-  return r;
-}
-
 // ---- K6a: 7x7 Gaussian, 8.8 fixed point ------------------------------------------------------------------
 // Same rolling layout as min_eigen_kernel: a wave owns a 64-column strip (58 output columns) and walks down a
 // chunk of rows; the six horizontal neighbours come from neighbouring lanes (mirrored lanes at the image
@@ -854,12 +827,12 @@ __global__ __launch_bounds__(kThreads) void gauss7_kernel(const uint8_t* __restr
     }
     // (24-bit multiplies -- every operand is below 2^18, every sum below 2^24 -- so that each tap is ONE v_mad_u32_u24
     // instead of a 32-bit multiply plus an add)
-    h[P] = mad24(18u, (uint32_t)(l3 + r3), mad24(34u, (uint32_t)(l2 + r2), mad24(49u, (uint32_t)(l1 + r1), 54u * (uint32_t)c)));
+    h[P] = vmad24(18u, (uint32_t)(l3 + r3), vmad24(34u, (uint32_t)(l2 + r2), vmad24(49u, (uint32_t)(l1 + r1), 54u * (uint32_t)c)));
     const int y = t - 3;
     if (y < ys) return;  // uniform
     // rows y-3 .. y+3 = t-6 .. t live in slots P+1 .. P+7 (mod 7)
-    const uint32_t vsum = mad24(18u, h[(P + 1) % 7] + h[P], mad24(34u, h[(P + 2) % 7] + h[(P + 6) % 7],
-                                mad24(49u, h[(P + 3) % 7] + h[(P + 5) % 7], 54u * h[(P + 4) % 7])));
+    const uint32_t vsum = vmad24(18u, h[(P + 1) % 7] + h[P], vmad24(34u, h[(P + 2) % 7] + h[(P + 6) % 7],
+                                vmad24(49u, h[(P + 3) % 7] + h[(P + 5) % 7], 54u * h[(P + 4) % 7])));
     if (out_lane) o[(uint32_t)(y * cols) + (uint32_t)xc] = (uint8_t)((vsum + 32768u) >> 16);
   };
   auto run = [&](auto edge_tag) __attribute__((always_inline)) {

@@ -1,12 +1,25 @@
-// Device-side EPnP (Lepetit, Moreno-Noguer, Fua, IJCV 2009) for the central absolute-pose RANSAC with algorithm
-// "EPNP" (omnistereo/pose_est_tools.py:697, :915: OpenGV solves 6-point samples with EPnP): control points,
-// barycentric coordinates, [the null space of M^T M: epnp_eig12_reg.h], the three beta initialisations with five
-// Gauss-Newton steps each, absolute orientation, the candidate with the smallest reprojection error; plus the sampler
-// of k distinct indices.  One lane per hypothesis, every array index a compile-time constant after unrolling.
-// GENERATED from oracle/epnp_core.h by tests/gen_device_headers.py (the oracle's text minus its "oracle only" section, device
-// prefixes): both sides evaluate the same operations in the same order; tests/test_abi.py checks the two files.
+/* ONE TEXT FOR BOTH SIDES: the device code (hipcc) and the CPU oracle (gcc, oracle/Makefile reads this directory)
+ * compile this very file, so both evaluate the same operations in the same order; there is no second copy.
+ * sv_core_decl.h spells the function qualifiers for each side.  (Provenance: header of oracle/ransac.c.)
+ *
+ * EPnP (Lepetit, Moreno-Noguer, Fua, IJCV 2009) on n >= 5 bearing / point pairs, the central absolute-pose solver
+ * OpenGV runs inside absolute_pose_ransac(..., "EPNP", ...) on 6-point samples (omnistereo/pose_est_tools.py:697,
+ * :915).  OpenGV is not in the reference tree: this is a restatement of the published algorithm (four control points
+ * from the principal axes of the world points, barycentric coordinates, the null space of M^T M by a symmetric
+ * eigen-decomposition, the three beta initialisations with five Gauss-Newton steps each, absolute orientation, the
+ * candidate with the smallest reprojection error), with own numerics: Jacobi rotations for the symmetric
+ * eigen-problems of the 3 x 3 matrices (row-cyclic order), normal equations for the small least-squares fits, and the
+ * rotation from the Jacobi SVD of the 3x3 correlation matrix completed to a proper rotation by cross products; plus the
+ * sampler of k distinct indices.  On the device: one lane per hypothesis, every array index a compile-time constant
+ * after unrolling.  Only + - * / sqrt and comparisons, fully parenthesised, no FMA contraction.
+ * The one piece the two sides word differently is the 12 x 12 eigen-solver behind the null space of M^T M, with the
+ * driver sv_epnp on top of it (see the end of this file): registers and unrolled rounds on the device
+ * (epnp_eig12_reg.h, hand-written), plain loops in the oracle (oracle/epnp_eig12_plain.h).  The bit-exact GPU parity
+ * tests compare the two; the oracle's sv_symeig12 and sv_jacobi12_rr are checked against numpy.linalg.eigh and against
+ * each other (tests/test_oracle_ransac.py, which shares none of this text).
+ */
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sv_core_decl.h"
 #include "ransac_core.h"
 
 #define SV_EPNP_MAXN 8
@@ -17,7 +30,7 @@
  * (p, q) plane changes rows / columns p and q only -- a'kp = c akp - s akq, a'kq = s akp + c akq for k != p, q
  * (mirrored), a'pp = app - t apq, a'qq = aqq + t apq, a'pq = 0 exactly.  The iterations of each inner loop touch
  * disjoint elements: all their loads come before the stores. */
-__device__ static void sv_jacobi_sym(double* A, int n, double* V) {
+SV_FN void sv_jacobi_sym(double* A, int n, double* V) {
   #pragma unroll
   for (int i = 0; i < n; ++i)
     #pragma unroll
@@ -74,7 +87,7 @@ __device__ static void sv_jacobi_sym(double* A, int n, double* V) {
 
 /* Least squares min |A x - b| for an m x k system (k <= 5) through the normal equations, Gaussian elimination
  * with partial pivoting.  A row-major with row stride lda.  Returns 0 on a vanishing pivot. */
-__device__ static int sv_lsq_small(const double* A, int lda, const double* b, int m, int k, double* x) {
+SV_FN int sv_lsq_small(const double* A, int lda, const double* b, int m, int k, double* x) {
   double N[5 * 6];
   #pragma unroll
   for (int i = 0; i < k; ++i) {
@@ -133,7 +146,7 @@ __device__ static int sv_lsq_small(const double* A, int lda, const double* b, in
 
 /* world -> camera (Rcw, tcw) from the control-point coordinates in the camera frame; returns the mean
  * reprojection error (normalised image plane) or a negative number on failure. */
-__device__ static double sv_epnp_pose_from_betas(const double* betas, const double* vv /*[4][12]*/, const double* alphas,
+SV_FN double sv_epnp_pose_from_betas(const double* betas, const double* vv /*[4][12]*/, const double* alphas,
                                               const double* pw, const double* uv, int n, double* Rcw, double* tcw) {
   double ccs[12], pcs[3 * SV_EPNP_MAXN];
   #pragma unroll
@@ -238,7 +251,7 @@ __device__ static double sv_epnp_pose_from_betas(const double* betas, const doub
 
 /* EPnP, first half: f, p: n rows of 3 (bearings in the camera, points in the world), 5 <= n <= SV_EPNP_MAXN ->
  * normalised image coordinates uv, control points cw, barycentric coordinates alphas.  0 on failure. */
-__device__ static int sv_epnp_front(const double* f, const double* p, int n, double* uv, double* cw, double* alphas) {
+SV_FN int sv_epnp_front(const double* f, const double* p, int n, double* uv, double* cw, double* alphas) {
   if (n < 5 || n > SV_EPNP_MAXN) return 0; /* 4 points leave a 4-dimensional null space: not handled */
   #pragma unroll
   for (int i = 0; i < n; ++i) {
@@ -301,7 +314,7 @@ __device__ static int sv_epnp_front(const double* f, const double* p, int n, dou
 
 /* EPnP, second half: the four null-space vectors vv (vv[0] of the smallest eigenvalue) -> R, t: pose of the camera in
  * the world (points map by R^T (p - t)), as pyopengv returns it.  0 on failure. */
-__device__ static int sv_epnp_back(const double* p, int n, const double* uv, const double* cw, const double* alphas,
+SV_FN int sv_epnp_back(const double* p, int n, const double* uv, const double* cw, const double* alphas,
                                    const double* vv, double* R, double* t) {
   /* L (6 x 10) and rho (6) over the control-point pairs */
   const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
@@ -431,7 +444,7 @@ __device__ static int sv_epnp_back(const double* p, int n, const double* uv, con
 
 /* k distinct indices below n from the counter-based generator (draw numbers d0, d0 + 1, ...): the j-th draw picks
  * among the n - j values not taken yet (kept sorted).  Returns 0 if n < k. */
-__device__ static int sv_sample_distinct(int32_t n, int k, uint64_t seed, uint64_t it, int32_t* s) {
+SV_FN int sv_sample_distinct(int32_t n, int k, uint64_t seed, uint64_t it, int32_t* s) {
   if (n < k || k > 9) return 0;
   int32_t taken[9]; /* ascending */
 #pragma unroll
@@ -458,4 +471,9 @@ __device__ static int sv_sample_distinct(int32_t n, int k, uint64_t seed, uint64
 }
 
 
+/* The null space of M^T M and the driver sv_epnp: the device keeps the 12 x 12 eigen-solver in registers
+ * (epnp_eig12_reg.h, hand-written), the oracle as plain loops (oracle/epnp_eig12_plain.h, included by its sources
+ * after this file).  Same operations in the same order; the bit-exact GPU parity tests compare the two. */
+#ifdef __HIPCC__
 #include "epnp_eig12_reg.h"
+#endif

@@ -1,10 +1,11 @@
 // The 12 x 12 eigen-solver of EPnP on the device and the solver's driver: the ONE part of the EPnP restatement that is
-// not the oracle's text (csrc/epnp_core.h is generated from oracle/epnp_core.h; this file is hand-written and included at its
-// end).  Same operations in the same order as orc_symeig12 / orc_epnp_null4 -- the GPU parity tests compare every
+// not text shared with the CPU oracle (epnp_core.h is the one text both sides compile; this file is hand-written, device
+// only, and included at its end under __HIPCC__; the oracle's counterpart is oracle/epnp_eig12_plain.h).  Same
+// operations in the same order as that file's sv_symeig12 / sv_epnp_null4 -- the GPU parity tests compare every
 // hypothesis bit for bit -- but worded for registers: the 12 x 12 matrix (which becomes the eigenvector matrix), the
 // diagonal and the sub-diagonal in 144 + 24 doubles, every loop unrolled so that every index is a compile-time constant.
 // (Until round 2 this was a round-robin Jacobi solver, ~7 x the arithmetic: 1.52 ms per 128 pairs x 2000 hypotheses
-// against the figure in DESIGN.md section 10 now; the oracle keeps its loop form, orc_jacobi12_rr, as a cross-check.)
+// against the figure in DESIGN.md section 10 now; the oracle keeps its loop form, sv_jacobi12_rr, as a cross-check.)
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -14,7 +15,7 @@ __device__ __forceinline__ void sv_for_each_const(F& f, std::integer_sequence<in
 }
 
 /* ---- Householder tridiagonalisation + QL with implicit shifts, register-resident --------------------------------------
- * The same operations in the same order as orc_symeig12 (oracle/epnp_core.h: the EISPACK tred2 / tql2 pair restated;
+ * The same operations in the same order as sv_symeig12 (oracle/epnp_eig12_plain.h: the EISPACK tred2 / tql2 pair restated;
  * explicit fused multiply-adds where the oracle writes fma()), worded so that every array index is a compile-time
  * constant after unrolling: the loops of the reduction have static bounds; in the QL part the two data-dependent indices
  * -- m, where the matrix splits, and the start of the rotation chain -- become per-lane predicates over static ranges
@@ -193,7 +194,7 @@ __device__ __forceinline__ static int sv_symeig12_reg(double (&A)[144], double (
 
 /* M^T M of the sample (two rows of M per point, [a_j, 0, -a_j u] and [0, a_j, -a_j v]) -> the four eigenvectors of the
  * smallest eigenvalues, vv[0] the smallest (eigenvalue k has rank = the number of eigenvalues below it; equal ones:
- * those with a lower index); orc_epnp_null4's operations.  Returns 0 if the eigen-solver gives up. */
+ * those with a lower index); the operations of the oracle's sv_epnp_null4.  Returns 0 if the eigen-solver gives up. */
 __device__ static int sv_epnp_null4_ql(const double* alphas, const double* uv, int n, double* vv) {
   double A[144], d[12], e[12];
 #pragma unroll

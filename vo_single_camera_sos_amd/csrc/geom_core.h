@@ -4,7 +4,7 @@
 //   omnistereo/camera_models.py:3333-3340, :2437-2490  rays on the unit cylinder, midpoint triangulation
 //   omnistereo/camera_models.py:3309-3319      range filter on the homogeneous row (norm includes the 1)
 //   omnistereo/common_cv.py:177-186            pixel gates
-// FP64 throughout; sin / cos / atan are trig_core.h's (the text of oracle/trig_core.h: + - * / only), not the device math
+// FP64 throughout; sin / cos / atan are trig_core.h's (the very file the CPU oracle compiles: + - * / only), not the device math
 // library's, so that the angles, bearings and triangulated points equal the CPU oracle's bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,11 +1,29 @@
-// Generalised P3P, the minimal solver of the non-central absolute-pose RANSAC (the reference's
-// absolute_pose_noncentral_ransac "will ALWAYS use GP3P", omnistereo/pose_est_tools.py:696, :785): three quadrics in
-// the three depths -> an octic in the first one (resultants) -> Laguerre roots -> Newton polish -> triangle alignment;
-// up to 8 poses, the fourth correspondence picks one.  GENERATED from oracle/gp3p_core.h by tests/gen_device_headers.py (same text,
-// device prefixes): the CPU oracle evaluates the same operations in the same order, tests/test_abi.py checks that the
-// two files stay identical.  The derivation and the independent checks are documented in the oracle header.
+/* ONE TEXT FOR BOTH SIDES: the device code (hipcc) and the CPU oracle (gcc, oracle/Makefile reads this directory)
+ * compile this very file, so both produce the same bits; there is no second copy.  sv_core_decl.h spells the function
+ * qualifiers for each side.  (Provenance of the restatement: header of oracle/ransac.c.)
+ *
+ * Generalised P3P: the minimal solver of the NON-CENTRAL absolute-pose RANSAC.  The reference calls
+ * pyopengv.absolute_pose_noncentral_ransac, which "will ALWAYS use GP3P" (omnistereo/pose_est_tools.py:696, :785):
+ * OpenGV's AbsolutePoseSacProblem draws 4 correspondences from ALL cameras of the rig, solves the generalised
+ * three-point problem on the first three (up to 8 poses) and keeps the pose that reprojects the fourth one best.
+ * OpenGV's gp3p is machine-generated Groebner-basis code (Kneip, Furgale, Siegwart, ICRA 2013) that is not in the
+ * reference tree; this is a restatement of the PROBLEM it solves, with an own elimination:
+ *   rays x_i = o_i + l_i f_i in the body frame (o_i camera offset, f_i unit bearing rotated into the body frame), world
+ *   points P_i, i = 1..3.  Rigid motion keeps distances: |x_i - x_j|^2 = |P_i - P_j|^2 gives three quadrics
+ *     E_ij: l_i^2 + l_j^2 - 2 c_ij l_i l_j + 2 a_ij l_i - 2 b_ij l_j + k_ij = 0,
+ *     c_ij = f_i.f_j, a_ij = f_i.(o_i - o_j), b_ij = f_j.(o_i - o_j), k_ij = |o_i - o_j|^2 - |P_i - P_j|^2,
+ *   each in two unknowns only.  E_12 and E_23 are monic quadratics in l_2: their resultant R(l_1, l_3) is quartic in
+ *   l_3; modulo E_13 (monic quadratic in l_3) it becomes A(l_1) l_3 + B(l_1), and substituting l_3 = -B / A into E_13
+ *   leaves the OCTIC B^2 - A B u + A^2 v in l_1 (Nister & Stewenius 2007 reach an octic for the same problem): up to 8
+ *   solutions, as Bezout's bound for three quadrics says.  Roots by Laguerre's method with deflation (all eight,
+ *   complex arithmetic), real ones kept; l_3 = -B / A, l_2 from the common root of E_12 and E_23; three Newton steps
+ *   on (E_12, E_13, E_23) remove what the elimination lost in accuracy; solutions with a non-positive depth or a
+ *   residual are dropped; the pose follows from aligning the two triangles.
+ * Only + - * / sqrt, fabs and comparisons, fully parenthesised, no FMA contraction.  Checks that do not share this
+ * text: tests/test_oracle_gp3p.py (numpy.roots on the octic, residuals, planted poses).
+ */
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sv_core_decl.h"
 #include "epnp_core.h"
 
 #define SV_GP3P_MAXSOL 8
@@ -14,20 +32,20 @@ typedef struct {
   double re, im;
 } sv_cplx;
 
-__device__ static sv_cplx sv_c(double re, double im) {
+SV_FN sv_cplx sv_c(double re, double im) {
   sv_cplx z;
   z.re = re;
   z.im = im;
   return z;
 }
-__device__ static sv_cplx sv_cadd(sv_cplx a, sv_cplx b) { return sv_c(a.re + b.re, a.im + b.im); }
-__device__ static sv_cplx sv_csub(sv_cplx a, sv_cplx b) { return sv_c(a.re - b.re, a.im - b.im); }
-__device__ static sv_cplx sv_cmul(sv_cplx a, sv_cplx b) {
+SV_FN sv_cplx sv_cadd(sv_cplx a, sv_cplx b) { return sv_c(a.re + b.re, a.im + b.im); }
+SV_FN sv_cplx sv_csub(sv_cplx a, sv_cplx b) { return sv_c(a.re - b.re, a.im - b.im); }
+SV_FN sv_cplx sv_cmul(sv_cplx a, sv_cplx b) {
   return sv_c((a.re * b.re) - (a.im * b.im), (a.re * b.im) + (a.im * b.re));
 }
-__device__ static sv_cplx sv_cscale(sv_cplx a, double s) { return sv_c(a.re * s, a.im * s); }
-__device__ static double sv_cabs(sv_cplx a) { return sqrt((a.re * a.re) + (a.im * a.im)); }
-__device__ static sv_cplx sv_cdiv(sv_cplx a, sv_cplx b) { /* Smith's formula */
+SV_FN sv_cplx sv_cscale(sv_cplx a, double s) { return sv_c(a.re * s, a.im * s); }
+SV_FN double sv_cabs(sv_cplx a) { return sqrt((a.re * a.re) + (a.im * a.im)); }
+SV_FN sv_cplx sv_cdiv(sv_cplx a, sv_cplx b) { /* Smith's formula */
   if (fabs(b.re) >= fabs(b.im)) {
     const double r = b.im / b.re, den = b.re + (r * b.im);
     return sv_c((a.re + (r * a.im)) / den, (a.im - (r * a.re)) / den);
@@ -35,7 +53,7 @@ __device__ static sv_cplx sv_cdiv(sv_cplx a, sv_cplx b) { /* Smith's formula */
   const double r = b.re / b.im, den = b.im + (r * b.re);
   return sv_c(((a.re * r) + a.im) / den, ((a.im * r) - a.re) / den);
 }
-__device__ static sv_cplx sv_csqrt(sv_cplx z) { /* principal square root from real square roots */
+SV_FN sv_cplx sv_csqrt(sv_cplx z) { /* principal square root from real square roots */
   if (z.re == 0.0 && z.im == 0.0) return sv_c(0.0, 0.0);
   const double x = fabs(z.re), y = fabs(z.im);
   double w;
@@ -55,8 +73,8 @@ __device__ static sv_cplx sv_csqrt(sv_cplx z) { /* principal square root from re
  * formulation with a fractional step every tenth iteration to break limit cycles.  Magnitudes that only feed the
  * rounding-error bound of the evaluation (Adams' running bound) or a comparison are taken in the 1-norm / squared:
  * a square root per coefficient and three per iteration were more than half of the instructions of an iteration. */
-__device__ static double sv_cabs1(sv_cplx a) { return fabs(a.re) + fabs(a.im); }
-__device__ static void sv_laguerre(const double* a, int m, sv_cplx* x) {
+SV_FN double sv_cabs1(sv_cplx a) { return fabs(a.re) + fabs(a.im); }
+SV_FN void sv_laguerre(const double* a, int m, sv_cplx* x) {
   const double frac[9] = {0.0, 0.5, 0.25, 0.75, 0.13, 0.38, 0.62, 0.88, 1.0};
   for (int iter = 1; iter <= 80; ++iter) {
     sv_cplx b = sv_c(a[m], 0.0), d = sv_c(0.0, 0.0), f = sv_c(0.0, 0.0);
@@ -96,7 +114,7 @@ __device__ static void sv_laguerre(const double* a, int m, sv_cplx* x) {
  * polynomial need not be searched twice); once four roots are left, the real ones among them come from the closed-form
  * quartic solver.  Then the roots that can still turn out real (|Im| <= 1e-3 (1 + |Re|): every
  * caller discards the others) are polished on the undeflated polynomial. */
-__device__ static void sv_poly_roots(const double* c, int m, sv_cplx* roots) {
+SV_FN void sv_poly_roots(const double* c, int m, sv_cplx* roots) {
   double ad[11];
   for (int j = 0; j <= m; ++j) ad[j] = c[j];
   int deg = m, nr = 0;
@@ -142,13 +160,13 @@ __device__ static void sv_poly_roots(const double* c, int m, sv_cplx* roots) {
 }
 
 /* small real-polynomial helpers: p (degree dp) times q (degree dq) accumulated into out with weight w */
-__device__ static void sv_pmul_acc(const double* p, int dp, const double* q, int dq, double w, double* out) {
+SV_FN void sv_pmul_acc(const double* p, int dp, const double* q, int dq, double w, double* out) {
   for (int i = 0; i <= dp; ++i)
     for (int j = 0; j <= dq; ++j) out[i + j] = out[i + j] + (w * (p[i] * q[j]));
 }
 
 /* The coefficients of one quadric E_ij (see the header): {c, a, b, k}. */
-__device__ static void sv_gp3p_pair(const double* fi, const double* fj, const double* oi, const double* oj, const double* Pi,
+SV_FN void sv_gp3p_pair(const double* fi, const double* fj, const double* oi, const double* oj, const double* Pi,
                                  const double* Pj, double* e) {
   const double d0 = oi[0] - oj[0], d1 = oi[1] - oj[1], d2 = oi[2] - oj[2];
   const double q0 = Pi[0] - Pj[0], q1 = Pi[1] - Pj[1], q2 = Pi[2] - Pj[2];
@@ -157,13 +175,13 @@ __device__ static void sv_gp3p_pair(const double* fi, const double* fj, const do
   e[2] = ((fj[0] * d0) + (fj[1] * d1)) + (fj[2] * d2);
   e[3] = (((d0 * d0) + (d1 * d1)) + (d2 * d2)) - (((q0 * q0) + (q1 * q1)) + (q2 * q2));
 }
-__device__ static double sv_gp3p_eval(const double* e, double li, double lj) {
+SV_FN double sv_gp3p_eval(const double* e, double li, double lj) {
   return (((((li * li) + (lj * lj)) - (((2.0 * e[0]) * li) * lj)) + ((2.0 * e[1]) * li)) - ((2.0 * e[2]) * lj)) + e[3];
 }
 
 /* The octic in l_1 (oct[0..8], oct[8] leading) and the polynomials A (degree <= 3), B (degree <= 4) of the linear
  * relation A l_3 + B = 0.  e12, e13, e23: quadric coefficients {c, a, b, k}. */
-__device__ static void sv_gp3p_octic(const double* e12, const double* e13, const double* e23, double* oct, double* Apoly,
+SV_FN void sv_gp3p_octic(const double* e12, const double* e13, const double* e23, double* oct, double* Apoly,
                                   double* Bpoly) {
   /* E_12 as a quadratic in l_2: l_2^2 + p l_2 + q,  p = -2 c12 l_1 - 2 b12,  q = l_1^2 + 2 a12 l_1 + k12 */
   const double p[2] = {-(2.0 * e12[2]), -(2.0 * e12[0])};
@@ -243,7 +261,7 @@ __device__ static void sv_gp3p_octic(const double* e12, const double* e13, const
   sv_pmul_acc(AA, 6, v, 2, 1.0, oct);
 }
 
-__device__ static double sv_peval(const double* c, int deg, double x) {
+SV_FN double sv_peval(const double* c, int deg, double x) {
   double y = c[deg];
   for (int j = deg - 1; j >= 0; --j) y = (y * x) + c[j];
   return y;
@@ -252,7 +270,7 @@ __device__ static double sv_peval(const double* c, int deg, double x) {
 /* Generalised P3P.  fb[9]: three unit bearings in the BODY frame, o[9]: their camera offsets (body frame), P[9]: the
  * three world points.  -> up to 8 body poses (R [9] row-major, t [3]) with x_body = R^T (P - t), i.e. P = R x + t.
  * Returns the number of solutions. */
-__device__ static int sv_gp3p(const double* fb, const double* o, const double* P, double* R_out, double* t_out) {
+SV_FN int sv_gp3p(const double* fb, const double* o, const double* P, double* R_out, double* t_out) {
   /* lengths in units of the largest side of the world triangle: depths and coefficients of order one */
   double L = 0.0;
   for (int i = 0; i < 3; ++i) {
@@ -363,7 +381,7 @@ __device__ static int sv_gp3p(const double* fb, const double* o, const double* P
 
 /* One RANSAC hypothesis of the non-central problem with GP3P: four distinct correspondences out of all n (any camera),
  * GP3P on the first three, the pose with the smallest score on the fourth (first wins ties). */
-__device__ static int sv_hypothesis_gp3p(const double* f, const double* p, const int32_t* cam, const double* cam_off,
+SV_FN int sv_hypothesis_gp3p(const double* f, const double* p, const int32_t* cam, const double* cam_off,
                                       const double* cam_rot, int32_t n, uint64_t seed, uint64_t it, double* R_best,
                                       double* t_best) {
   int32_t s[4];
@@ -399,7 +417,7 @@ __device__ static int sv_hypothesis_gp3p(const double* f, const double* p, const
 
 /* One RANSAC hypothesis of the central problem with TWOPT (known rotation = identity, the binding's prior): two distinct
  * correspondences, the translation from sv_twopt. */
-__device__ static int sv_hypothesis_twopt(const double* f, const double* p, int32_t n, uint64_t seed, uint64_t it, double* R_out,
+SV_FN int sv_hypothesis_twopt(const double* f, const double* p, int32_t n, uint64_t seed, uint64_t it, double* R_out,
                                        double* t_out) {
   int32_t s[2];
   if (!sv_sample_distinct(n, 2, seed, it, s)) return 0;

@@ -23,8 +23,6 @@ namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // ---- K1 ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void unwrap_kernel(const uint8_t* __restrict__ omni,
                                                           const uint8_t* __restrict__ masks,
@@ -221,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void unwrap_lut_kernel(const uint8_t* __r
 __device__ __forceinline__ uint8_t bgr2gray(int b, int g, int r) {
   return (uint8_t)((1868 * b + 9617 * g + 4899 * r + 8192) >> 14);
 }
-// x * k + acc as ONE v_mad_u32_u24 (x < 2^24; k wave-uniform)
+// x * k + acc as ONE v_mad_u32_u24 (x < 2^24; k wave-uniform, in an SGPR: not common.h's all-VGPR vmad24)
 __device__ __forceinline__ uint32_t mad24(uint32_t x, uint32_t k, uint32_t acc) {
   uint32_t r;
   asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(k), "v"(acc));

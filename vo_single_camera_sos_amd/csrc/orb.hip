@@ -72,12 +72,6 @@ __device__ __forceinline__ int orb_xcd_problem(int nimg, int nmask) {
 }
 inline unsigned orb_xcd_grid(int nimg, int nmask) { return (unsigned)(8 * ((nimg + 7) / 8) * nmask); }
 
-__device__ __forceinline__ int refl101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-  return i;
-}
-
 // ---- pyramid -------------------------------------------------------------------------------------------
 struct ResizeTap {
   int i0, i1, w0, w1;
@@ -212,9 +206,7 @@ __global__ __launch_bounds__(kThreads) void mask_level_kernel(uint32_t* __restri
 }
 
 // ---- FAST-9/16 score map (+ local-maximum flags) ----------------------------------------------------------------
-// Neighbouring lane's value through the DPP operand path (a VALU move; 0 beyond the wave's ends: halo lanes only).
-__device__ __forceinline__ int fs_from_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, true); }
-__device__ __forceinline__ int fs_from_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xF, 0xF, true); }
+// (the neighbouring lane's value: lane_from_left / lane_from_right of common.h, 0 beyond the wave's ends: halo lanes only)
 __device__ __forceinline__ uint32_t min16(uint32_t a, uint32_t b) { return (uint32_t)min((uint16_t)a, (uint16_t)b); }
 __device__ __forceinline__ uint32_t max16(uint32_t a, uint32_t b) { return (uint32_t)max((uint16_t)a, (uint16_t)b); }
 
@@ -331,12 +323,12 @@ __global__ __launch_bounds__(kThreads) void fast_score_rolling_kernel(const uint
     {
       const int c = c_pre[P];  // row t
       vc[P] = c;
-      vr1[P] = fs_from_right(c);
-      vr2[P] = fs_from_right(vr1[P]);
-      vr3[P] = fs_from_right(vr2[P]);
-      vl1[P] = fs_from_left(c);
-      vl2[P] = fs_from_left(vl1[P]);
-      vl3[P] = fs_from_left(vl2[P]);
+      vr1[P] = lane_from_right(c);
+      vr2[P] = lane_from_right(vr1[P]);
+      vr3[P] = lane_from_right(vr2[P]);
+      vl1[P] = lane_from_left(c);
+      vl2[P] = lane_from_left(vl1[P]);
+      vl3[P] = lane_from_left(vl2[P]);
     }
     const int y = t - 3;
     if (y < r0) return;  // uniform
@@ -367,7 +359,7 @@ __global__ __launch_bounds__(kThreads) void fast_score_rolling_kernel(const uint
     }
     if (out_lane) o[(uint32_t)(y * cols) + (uint32_t)xc] = (uint8_t)s;
     if (fo) {  // uniform
-      const int lr = max(fs_from_left(s), fs_from_right(s)), hm = max(lr, s);
+      const int lr = max(lane_from_left(s), lane_from_right(s)), hm = max(lr, s);
       if (y - 1 > r0 && y - 1 < r1 - 1) {  // flag row y - 1 (uniform)
         const bool is_max = out_lane && s_b > 0 && s_b > lr_b && s_b > hm_a && s_b > hm;
         const unsigned long long bal = __ballot(is_max);
@@ -440,11 +432,6 @@ struct LevelPass {
   const uint32_t* xtaps;
 };
 
-__device__ __forceinline__ uint32_t orb_mad24(uint32_t k, uint32_t x, uint32_t acc) {  // (detect.hip's mad24)
-  uint32_t r;
-  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(k), "v"(acc));
-  return r;
-}
 __device__ __forceinline__ uint32_t orb_mul24(uint32_t a, uint32_t b) {  // a, b < 2^24, product < 2^32: full-rate multiply
   uint32_t r;
   asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -664,8 +651,8 @@ __global__ __launch_bounds__(kThreads) void orb_level_pass_kernel(const LevelPas
     {
       const uint32_t c = __builtin_amdgcn_perm(0u, c_pre[P], unpack_sel);  // row t: (x, x + 1) as 16-bit halves
       e_next = s_tab[min(t + 1, t_last) + 3];
-      const uint32_t nx = (uint32_t)fs_from_right((int)c), nx2 = (uint32_t)fs_from_right((int)nx);   // (x+2, x+3), (x+4, x+5)
-      const uint32_t pv = (uint32_t)fs_from_left((int)c), pv2 = (uint32_t)fs_from_left((int)pv);     // (x-2, x-1), (x-4, x-3)
+      const uint32_t nx = (uint32_t)lane_from_right((int)c), nx2 = (uint32_t)lane_from_right((int)nx);   // (x+2, x+3), (x+4, x+5)
+      const uint32_t pv = (uint32_t)lane_from_left((int)c), pv2 = (uint32_t)lane_from_left((int)pv);     // (x-2, x-1), (x-4, x-3)
       vc[P] = c;
       vr1[P] = __builtin_amdgcn_alignbit(nx, c, 16);    // (x+1, x+2)
       vr3[P] = __builtin_amdgcn_alignbit(nx2, nx, 16);  // (x+3, x+4)
@@ -682,7 +669,7 @@ __global__ __launch_bounds__(kThreads) void orb_level_pass_kernel(const LevelPas
         const uint32_t q0 = (uint32_t)__builtin_amdgcn_ds_bpermute(la[q], (int)vc[P]);
         const uint32_t q1 = (uint32_t)__builtin_amdgcn_ds_bpermute(la[q], (int)row_nx);
         const uint32_t win = __builtin_amdgcn_alignbit(q1, q0, (uint32_t)sh[q]);  // (pixel x0, pixel x0 + 1)
-        hx[q] = orb_mad24(wx1[q], win >> 16, orb_mul24(2048u - wx1[q], win & 0xFFFFu));
+        hx[q] = vmad24(wx1[q], win >> 16, orb_mul24(2048u - wx1[q], win & 0xFFFFu));
       }
       if (e0 & kRtEmit) {  // uniform
         const uint32_t wy1 = (e0 >> 16) & 0xFFFu, wy0 = 2048u - wy1, dy = e0 & 0xFFFFu;
@@ -708,8 +695,8 @@ __global__ __launch_bounds__(kThreads) void orb_level_pass_kernel(const LevelPas
         auto hi = [](uint32_t x) { return x >> 16; };
         const uint32_t h1 = hsp[(P + 1) % 7], h2 = hsp[(P + 2) % 7], h3 = hsp[(P + 3) % 7], h4 = hsp[(P + 4) % 7], h5 = hsp[(P + 5) % 7],
                        h6 = hsp[(P + 6) % 7], h7 = hsp[P];
-        const uint32_t vl = orb_mad24(18u, lo(h1) + lo(h7), orb_mad24(34u, lo(h2) + lo(h6), orb_mad24(49u, lo(h3) + lo(h5), orb_mul24(54u, lo(h4)))));
-        const uint32_t vh = orb_mad24(18u, hi(h1) + hi(h7), orb_mad24(34u, hi(h2) + hi(h6), orb_mad24(49u, hi(h3) + hi(h5), orb_mul24(54u, hi(h4)))));
+        const uint32_t vl = vmad24(18u, lo(h1) + lo(h7), vmad24(34u, lo(h2) + lo(h6), vmad24(49u, lo(h3) + lo(h5), orb_mul24(54u, lo(h4)))));
+        const uint32_t vh = vmad24(18u, hi(h1) + hi(h7), vmad24(34u, hi(h2) + hi(h6), vmad24(49u, hi(h3) + hi(h5), orb_mul24(54u, hi(h4)))));
         const uint32_t bl = (vl + 32768u) >> 16, bh = (vh + 32768u) >> 16;
         uint8_t* o = bo + (uint32_t)((t - 3) * cols) + (uint32_t)x_lo;
         if (out_hi) {
@@ -726,14 +713,14 @@ __global__ __launch_bounds__(kThreads) void orb_level_pass_kernel(const LevelPas
     if (e1 & kRtScore) {  // uniform
       constexpr int s3 = (P + 7) % 7, s2 = (P + 6) % 7, s1 = (P + 5) % 7, s0 = (P + 4) % 7, m1 = (P + 3) % 7, m2 = (P + 2) % 7,
                     m3 = (P + 1) % 7;
-      const uint32_t r2s = (uint32_t)fs_from_right((int)vc[s2]), r2m = (uint32_t)fs_from_right((int)vc[m2]);  // (x+2, x+3) of rows y+2, y-2
-      const uint32_t l2s = (uint32_t)fs_from_left((int)vc[s2]), l2m = (uint32_t)fs_from_left((int)vc[m2]);    // (x-2, x-1)
+      const uint32_t r2s = (uint32_t)lane_from_right((int)vc[s2]), r2m = (uint32_t)lane_from_right((int)vc[m2]);  // (x+2, x+3) of rows y+2, y-2
+      const uint32_t l2s = (uint32_t)lane_from_left((int)vc[s2]), l2m = (uint32_t)lane_from_left((int)vc[m2]);    // (x-2, x-1)
       const uint32_t v[16] = {vc[s3],  vr1[s3], r2s, vr3[s1], vr3[s0], vr3[m1], r2m, vr1[m3],
                               vc[m3],  vl1[m3], l2m, vl3[m1], vl3[s0], vl3[s1], l2s, vl1[s3]};
       s = fast_score_pk(v, vc[s0], thr_pk, thrm1_pk, valid_pk);
     }
     // packed scores of the left / right neighbours: (x-1, x) and (x+1, x+2)
-    const uint32_t sn = (uint32_t)fs_from_right((int)s), sp = (uint32_t)fs_from_left((int)s);
+    const uint32_t sn = (uint32_t)lane_from_right((int)s), sp = (uint32_t)lane_from_left((int)s);
     const uint32_t lr = pk_max(__builtin_amdgcn_alignbit(s, sp, 16), __builtin_amdgcn_alignbit(sn, s, 16)), hm = pk_max(lr, s);
     if (e1 & kRtFlagRow) {  // flag row y - 1 (uniform)
       // strictly greater than the eight neighbours (and hence > 0): saturating difference to their maximum, nonzero = flagged
@@ -848,7 +835,7 @@ __global__ __launch_bounds__(64) void fast_collect_kernel(const unsigned long lo
 // 1670-1671, :1755; pose_est_tools.py:508-509): the 9-of-16 segment test by an optimal decision tree -- the corner set and
 // the response of FAST-9/16 (the score map above, threshold 10) -- followed by AGAST's own suppression: corners that touch
 // vertically or horizontally form blocks, a raster scan with a link table keeps one maximum per block (oracle/orb.c,
-// orc_agast_nms, for the exact rule).  That scan is sequential by nature: one workgroup per image builds the corner list
+// its agast_nms, for the exact rule).  That scan is sequential by nature: one workgroup per image builds the corner list
 // in raster order (all lanes), lane 0 walks it with everything in LDS (entry = pixel index | response << 24, link table,
 // row starts: 132 KB), then all lanes compact the survivors per mask.
 constexpr int kAgastCap = 16384, kAgastMaxRows = 1024;
@@ -1711,7 +1698,7 @@ __global__ __launch_bounds__(kThreads) void orb_describe_levels_kernel(const uin
       const uint8_t* c = (k.staged ? ctr : safe) - (size_t)(R * pitch + R);  // the patch's first byte (scalar)
 #pragma unroll
       for (int it = 0; it < NIT; ++it)
-        reg[it] = *reinterpret_cast<const u32_unaligned*>(c + orb_mad24((uint32_t)prow[it], (uint32_t)pitch, (uint32_t)(4 * pk[it])));
+        reg[it] = *reinterpret_cast<const u32_unaligned*>(c + vmad24((uint32_t)prow[it], (uint32_t)pitch, (uint32_t)(4 * pk[it])));
       return k;
     };
     uint32_t reg_n[NIT];
@@ -1737,7 +1724,7 @@ __global__ __launch_bounds__(kThreads) void orb_describe_levels_kernel(const uin
           const float px = ppx[r][e], py = ppy[r][e];
           const float xr = (px * k.ca) - (py * k.sa), yr = (px * k.sa) + (py * k.ca);
           const int dx = __float2int_rn(xr), dy = __float2int_rn(yr);
-          val[e] = patch8[orb_mad24((uint32_t)(dy + R), (uint32_t)(4 * pstride), (uint32_t)(dx + R))];
+          val[e] = patch8[vmad24((uint32_t)(dy + R), (uint32_t)(4 * pstride), (uint32_t)(dx + R))];
         }
         const unsigned long long bal = __ballot(val[0] < val[1]);
         if (lane == 0) d[r] = bal;

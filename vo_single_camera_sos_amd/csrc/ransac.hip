@@ -188,7 +188,7 @@ __global__ __launch_bounds__(64) void ransac_hyp_twopt_kernel(const double* __re
 }
 
 // The generalised-P3P hypothesis generator (SOSVO_FLAG_GP3P): one lane per (problem, iteration): four distinct
-// correspondences out of all cameras, sv_hypothesis_gp3p (gp3p_core.h, the oracle's text).  Latency-bound (SQ counters:
+// correspondences out of all cameras, sv_hypothesis_gp3p (gp3p_core.h, the text the CPU oracle compiles too).  Latency-bound (SQ counters:
 // 32.5 k VALU instructions per wave at 7.2 SIMD-cycles each: chains of FP64 divisions and square roots), so the register
 // budget is capped for three waves per SIMD (measured 2 / 3 / 4 / 5 / 6 waves: 0.785 / 0.700 / 0.715 / 0.806 / 0.781 ms).
 template <class SeedT>

@@ -1,12 +1,20 @@
-// Device-side numeric core of the absolute-pose RANSAC (K8/K10) and LM refinement (K9): counter-based sampler, Kneip
-// P3P, real quartic roots, score, Cayley parametrisation, LM pieces.  Reference call sites replaced:
-// pyopengv.absolute_pose_noncentral_ransac (omnistereo/pose_est_tools.py:785), absolute_pose_ransac (:915),
-// *_optimize_nonlinear (:830, :937); score definition from pose_est_tools.py:150-203 (+ :181-185 non-central).
-// Only + - * / sqrt and comparisons, fully parenthesised, built with -ffp-contract=off.  GENERATED from oracle/ransac_core.h by
-// tests/gen_device_headers.py (same text, device prefixes): the CPU oracle evaluates the same operations in the same
-// order, tests/test_abi.py checks that the two files stay identical.
+/* ONE TEXT FOR BOTH SIDES: the device code (hipcc) and the CPU oracle (gcc, oracle/Makefile reads this directory)
+ * compile this very file, so both evaluate the same operations in the same order; there is no second copy.
+ * sv_core_decl.h spells the function qualifiers for each side -- SV_FN_INLINE throughout THIS file (forced inlining
+ * on the device; the other solver headers use SV_FN, and the difference decides the generated code).  `#pragma unroll`
+ * lines are for the device compiler; gcc ignores them.  (Provenance of the restatement: header of oracle/ransac.c.)
+ *
+ * Numeric core of the absolute-pose RANSAC (K8/K10) and of the LM refinement (K9): counter-based sampler, Kneip P3P,
+ * real quartic roots, score, Cayley parametrisation, LM pieces.  Reference call sites replaced:
+ * pyopengv.absolute_pose_noncentral_ransac (omnistereo/pose_est_tools.py:785), absolute_pose_ransac (:915),
+ * *_optimize_nonlinear (:830, :937); score definition from pose_est_tools.py:150-203 (+ :181-185 non-central).
+ * Only + - * / sqrt and comparisons are used (no libm transcendental), every expression is fully parenthesised and
+ * both builds disable FMA contraction (-ffp-contract=off).  What a shared text cannot catch -- an error in the formulas
+ * themselves -- is covered by checks that do not share this code: tests/test_oracle_ransac.py (numpy / scipy
+ * evaluations, planted poses, exhaustive small problems).
+ */
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sv_core_decl.h"
 #include <math.h>
 #include <stdbool.h>
 #include <stdint.h>
@@ -19,7 +27,7 @@
 #define SV_SQRT_EPS 1.4901161193847656e-08
 #define SV_RANSAC_PROB_FAIL 0.01 /* 1 - 0.99, OpenGV sac::Ransac default probability */
 
-__device__ __forceinline__ static void sv_T_to_Rt(const double* T, double* R, double* t) {
+SV_FN_INLINE void sv_T_to_Rt(const double* T, double* R, double* t) {
   for (int i = 0; i < 3; ++i) {
     R[3 * i + 0] = T[4 * i + 0];
     R[3 * i + 1] = T[4 * i + 1];
@@ -28,7 +36,7 @@ __device__ __forceinline__ static void sv_T_to_Rt(const double* T, double* R, do
   }
 }
 
-__device__ __forceinline__ static void sv_Rt_to_T(const double* R, const double* t, double* T) {
+SV_FN_INLINE void sv_Rt_to_T(const double* R, const double* t, double* T) {
   for (int i = 0; i < 3; ++i) {
     T[4 * i + 0] = R[3 * i + 0];
     T[4 * i + 1] = R[3 * i + 1];
@@ -38,7 +46,7 @@ __device__ __forceinline__ static void sv_Rt_to_T(const double* R, const double*
 }
 
 /* ---- counter-based sampler ------------------------------------------------------------------ */
-__device__ __forceinline__ static uint64_t sv_mix64(uint64_t seed, uint64_t iter, uint64_t draw) {
+SV_FN_INLINE uint64_t sv_mix64(uint64_t seed, uint64_t iter, uint64_t draw) {
   uint64_t z = seed + 0x9E3779B97F4A7C15ULL * (iter * 8ULL + draw + 1ULL);
   z ^= z >> 30;
   z *= 0xBF58476D1CE4E5B9ULL;
@@ -48,14 +56,14 @@ __device__ __forceinline__ static uint64_t sv_mix64(uint64_t seed, uint64_t iter
   return z;
 }
 
-__device__ __forceinline__ static uint32_t sv_below(uint64_t z, uint32_t range) {
+SV_FN_INLINE uint32_t sv_below(uint64_t z, uint32_t range) {
   return (uint32_t)(((z >> 32) * (uint64_t)range) >> 32);
 }
 
 /* Four distinct point indices: three solve points from ONE camera (the camera of the first
  * draw), the fourth (disambiguation) from all points.  Works in "perm position" space, perm
  * being the stable partition of the point indices by camera.  Returns 0 if impossible. */
-__device__ __forceinline__ static int sv_sample4(const int32_t* cam, int32_t n, const int32_t* perm, const int32_t* cstart,
+SV_FN_INLINE int sv_sample4(const int32_t* cam, int32_t n, const int32_t* perm, const int32_t* cstart,
                               const int32_t* ccount, uint64_t seed, uint64_t it, int32_t* s) {
   if (n < 4) return 0;
   int32_t j0 = (int32_t)sv_below(sv_mix64(seed, it, 0), (uint32_t)n);
@@ -90,7 +98,7 @@ __device__ __forceinline__ static int sv_sample4(const int32_t* cam, int32_t n, 
 /* ---- score: 1 - f . normalize(R_c^T (R^T p - R^T t - o_c)) ----------------------------------
  * pose_est_tools.py:158-160,:177 build inverse = [R^T | -R^T t] and apply it to the homogeneous
  * point; :181-185 give the non-central extension; :199 the score. */
-__device__ __forceinline__ static double sv_score(const double* R, const double* t, const double* f, const double* p,
+SV_FN_INLINE double sv_score(const double* R, const double* t, const double* f, const double* p,
                                const double* o, const double* Rc) {
   const double itx = -(((R[0] * t[0]) + (R[3] * t[1])) + (R[6] * t[2]));
   const double ity = -(((R[1] * t[0]) + (R[4] * t[1])) + (R[7] * t[2]));
@@ -111,7 +119,7 @@ __device__ __forceinline__ static double sv_score(const double* R, const double*
  * k = log(1 - 0.99) / log(1 - w^4), w = best/N clamped to [eps, 1 - eps].  Evaluated without
  * log: iterations < k  <=>  (1 - w^4)^iterations > 0.01.  sv_adaptive_k returns the base
  * (1 - w^4); sv_ransac_continue evaluates the power by repeated squaring. */
-__device__ __forceinline__ static double sv_adaptive_base(int32_t best, int32_t n) {
+SV_FN_INLINE double sv_adaptive_base(int32_t best, int32_t n) {
   const double w = (double)best / (double)n;
   double pno = 1.0 - (((w * w) * w) * w);
   const double eps = 2.220446049250313e-16;
@@ -121,7 +129,7 @@ __device__ __forceinline__ static double sv_adaptive_base(int32_t best, int32_t 
 }
 
 // the same for 6-point samples (EPnP): 1 - w^6
-__device__ __forceinline__ static double sv_adaptive_base6(int32_t best, int32_t n) {
+SV_FN_INLINE double sv_adaptive_base6(int32_t best, int32_t n) {
   const double w = (double)best / (double)n;
   const double w2 = w * w;
   double pno = 1.0 - ((w2 * w2) * w2);
@@ -132,7 +140,7 @@ __device__ __forceinline__ static double sv_adaptive_base6(int32_t best, int32_t
 }
 
 // ... and for 2-point samples (TWOPT): 1 - w^2
-__device__ __forceinline__ static double sv_adaptive_base2(int32_t best, int32_t n) {
+SV_FN_INLINE double sv_adaptive_base2(int32_t best, int32_t n) {
   const double w = (double)best / (double)n;
   double pno = 1.0 - (w * w);
   const double eps = 2.220446049250313e-16;
@@ -141,7 +149,7 @@ __device__ __forceinline__ static double sv_adaptive_base2(int32_t best, int32_t
   return pno;
 }
 
-__device__ __forceinline__ static int sv_ransac_continue(double base, int32_t iterations) {
+SV_FN_INLINE int sv_ransac_continue(double base, int32_t iterations) {
   double result = 1.0, b = base;
   int32_t m = iterations;
   while (m > 0) {
@@ -153,13 +161,13 @@ __device__ __forceinline__ static int sv_ransac_continue(double base, int32_t it
 }
 
 /* ---- real roots of a quartic a[0] x^4 + a[1] x^3 + a[2] x^2 + a[3] x + a[4] ------------------ */
-__device__ __forceinline__ static double sv_cubic_eval(double c2, double c1, double c0, double z) {
+SV_FN_INLINE double sv_cubic_eval(double c2, double c1, double c0, double z) {
   return (((((z + c2) * z) + c1) * z) + c0);
 }
 
 /* One real root of z^3 + c2 z^2 + c1 z + c0 inside [lo, hi] with g(lo) <= 0 < g(hi):
  * Newton safeguarded by bisection, fixed iteration budget. */
-__device__ __forceinline__ static double sv_cubic_root_bracketed(double c2, double c1, double c0, double lo, double hi) {
+SV_FN_INLINE double sv_cubic_root_bracketed(double c2, double c1, double c0, double lo, double hi) {
   double z = 0.5 * (lo + hi);
   for (int it = 0; it < 200; ++it) {
     const double g = sv_cubic_eval(c2, c1, c0, z);
@@ -175,7 +183,7 @@ __device__ __forceinline__ static double sv_cubic_root_bracketed(double c2, doub
   return z;
 }
 
-__device__ __forceinline__ static int sv_quartic(const double* a, double* roots) {
+SV_FN_INLINE int sv_quartic(const double* a, double* roots) {
   const double a0 = a[0];
   if (!(a0 != 0.0) || !isfinite(a0)) return 0;
   const double b = a[1] / a0, c = a[2] / a0, d = a[3] / a0, e = a[4] / a0;
@@ -265,17 +273,17 @@ __device__ __forceinline__ static int sv_quartic(const double* a, double* roots)
 /* ---- Kneip P3P (CVPR 2011).  f1..f3 unit bearings in the camera frame, P1..P3 world points.
  * Returns up to 4 solutions: R_out[k] (row-major, camera->world) and C_out[k] (camera centre),
  * i.e. P = R x_cam + C.  -------------------------------------------------------------------- */
-__device__ __forceinline__ static void sv_cross(const double* a, const double* b, double* o) {
+SV_FN_INLINE void sv_cross(const double* a, const double* b, double* o) {
   o[0] = (a[1] * b[2]) - (a[2] * b[1]);
   o[1] = (a[2] * b[0]) - (a[0] * b[2]);
   o[2] = (a[0] * b[1]) - (a[1] * b[0]);
 }
 
-__device__ __forceinline__ static double sv_dot(const double* a, const double* b) {
+SV_FN_INLINE double sv_dot(const double* a, const double* b) {
   return ((a[0] * b[0]) + (a[1] * b[1])) + (a[2] * b[2]);
 }
 
-__device__ __forceinline__ static int sv_p3p(const double* f1_in, const double* f2_in, const double* f3_in, const double* P1_in,
+SV_FN_INLINE int sv_p3p(const double* f1_in, const double* f2_in, const double* f3_in, const double* P1_in,
                           const double* P2_in, const double* P3_in, double* R_out, double* C_out) {
   double f1[3], f2[3], f3[3], P1[3], P2[3], P3[3];
   for (int i = 0; i < 3; ++i) {
@@ -437,7 +445,7 @@ __device__ __forceinline__ static int sv_p3p(const double* f1_in, const double* 
 
 /* One RANSAC hypothesis: sample, solve in the sampled camera, move to the body frame, pick the
  * solution with the smallest score on the 4th point (first wins ties). */
-__device__ __forceinline__ static int sv_hypothesis(const double* f, const double* p, const int32_t* cam, const double* cam_off,
+SV_FN_INLINE int sv_hypothesis(const double* f, const double* p, const int32_t* cam, const double* cam_off,
                                  const double* cam_rot, int32_t n, const int32_t* perm, const int32_t* cstart,
                                  const int32_t* ccount, uint64_t seed, uint64_t it, double* R_best, double* t_best) {
   int32_t s[4];
@@ -472,14 +480,14 @@ __device__ __forceinline__ static int sv_hypothesis(const double* f, const doubl
 }
 
 /* ---- Cayley parametrisation -------------------------------------------------------------- */
-__device__ __forceinline__ static void sv_rot2cayley(const double* R, double* c) {
+SV_FN_INLINE void sv_rot2cayley(const double* R, double* c) {
   const double s = 1.0 + ((R[0] + R[4]) + R[8]);
   c[0] = (R[7] - R[5]) / s;
   c[1] = (R[2] - R[6]) / s;
   c[2] = (R[3] - R[1]) / s;
 }
 
-__device__ __forceinline__ static void sv_cayley2rot(const double* c, double* R) {
+SV_FN_INLINE void sv_cayley2rot(const double* c, double* R) {
   const double x = c[0], y = c[1], z = c[2];
   const double xx = x * x, yy = y * y, zz = z * z;
   const double s = 1.0 + ((xx + yy) + zz);
@@ -494,14 +502,14 @@ __device__ __forceinline__ static void sv_cayley2rot(const double* c, double* R)
   R[8] = (((1.0 - xx) - yy) + zz) / s;
 }
 
-__device__ __forceinline__ static double sv_residual(const double* x, const double* f, const double* p, const double* o,
+SV_FN_INLINE double sv_residual(const double* x, const double* f, const double* p, const double* o,
                                   const double* Rc) {
   double R[9];
   sv_cayley2rot(x + 3, R);
   return sv_score(R, x, f, p, o, Rc);
 }
 
-__device__ __forceinline__ static void sv_residual_jac(const double* x, const double* f, const double* p, const double* o,
+SV_FN_INLINE void sv_residual_jac(const double* x, const double* f, const double* p, const double* o,
                                     const double* Rc, double* r, double* J, double* Hq) {
   /* Analytic Jacobian of r = 1 - f . u/|u|, u = Rc^T (R(c)^T (p - t) - o), wrt (t, Cayley c).
    * (OpenGV differentiates numerically; the forward-difference noise stalls LM ~1e-5 short of the
@@ -593,7 +601,7 @@ __device__ __forceinline__ static void sv_residual_jac(const double* x, const do
 
 /* Solve (A + lambda diag(A)) dx = -g for the packed upper triangle A (21) by LDL^T without
  * pivoting.  Returns 0 if a pivot is not positive. */
-__device__ __forceinline__ static int sv_solve_damped(const double* Apacked, const double* g, double lambda, double* dx) {
+SV_FN_INLINE int sv_solve_damped(const double* Apacked, const double* g, double lambda, double* dx) {
   // Every loop is fully unrolled so that M, L, yv live in registers (runtime-indexed local arrays would go to
   // scratch memory); a failed pivot only clears `ok`, the arithmetic of the successful case is unchanged.
   double M[36];
@@ -660,7 +668,7 @@ __device__ __forceinline__ static int sv_solve_damped(const double* Apacked, con
  * rotation prior of its adapter, which the binding leaves at the identity.)  Restated as the least-squares meeting
  * point of the two rays through the world points: minimise sum |(I - f_i f_i^T)(p_i - t)|^2, f_i the bearings rotated
  * into the world frame -- a 3 x 3 linear system, solved by Cramer's rule.  Returns 0 for (nearly) parallel rays. */
-__device__ __forceinline__ static int sv_twopt(const double* f1, const double* f2, const double* p1, const double* p2, const double* R,
+SV_FN_INLINE int sv_twopt(const double* f1, const double* f2, const double* p1, const double* p2, const double* R,
                             double* t) {
   double A[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
   for (int k = 0; k < 2; ++k) {
@@ -687,7 +695,7 @@ __device__ __forceinline__ static int sv_twopt(const double* f1, const double* f
 
 /* Sum of 256 partials: four groups of 64, each by the binary tree v[l] += v[l + o], o = 32..1,
  * then ((w0 + w1) + w2) + w3. */
-__device__ __forceinline__ static double sv_tree_sum256(const double* part) {
+SV_FN_INLINE double sv_tree_sum256(const double* part) {
   double w[4];
   for (int k = 0; k < 4; ++k) {
     double v[64];

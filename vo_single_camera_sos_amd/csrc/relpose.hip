@@ -5,7 +5,7 @@
 //            omnistereo/pose_est_tools.py:150-203  score of a correspondence under a relative pose
 //
 // Same decomposition as the absolute-pose RANSAC (ransac.hip): hypotheses for every (problem, iteration) in parallel, one
-// lane each (relpose_core.h: the oracle's text) -> the iters x N scoring loop, a lane keeps its correspondence in VGPRs and
+// lane each (relpose_core.h: the text the CPU oracle compiles too) -> the iters x N scoring loop, a lane keeps its correspondence in VGPRs and
 // reads the chunk's hypotheses as LDS broadcasts, the inlier decision is a wave ballot + scalar popcount -> the sequential
 // semantics of sac::Ransac replayed over the counts, exact mask + ascending index list of the winner.  The score needs a
 // triangulation, two square roots and three divisions per (correspondence, hypothesis); it is evaluated with the oracle's

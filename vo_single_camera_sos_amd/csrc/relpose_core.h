@@ -1,16 +1,30 @@
-// Device-side numeric core of the 2D-2D relative-pose RANSAC (pyopengv.relative_pose_ransac, reference call site
-// omnistereo/pose_est_tools.py:78): the reference's own score of a correspondence under a relative pose
-// (pose_est_tools.py:150-203), the decomposition of an essential matrix, the minimal solvers, one hypothesis per lane.
-// GENERATED from oracle/relpose_core.h by tests/gen_device_headers.py (same text, device prefixes): the CPU oracle evaluates the same
-// operations in the same order, tests/test_abi.py checks that the two files stay identical.
+/* ONE TEXT FOR BOTH SIDES: the device code (hipcc, one hypothesis per lane) and the CPU oracle (gcc, oracle/Makefile
+ * reads this directory) compile this very file, so both evaluate the same operations in the same order; there is no
+ * second copy.  sv_core_decl.h spells the function qualifiers for each side.  (Provenance: header of oracle/ransac.c.)
+ *
+ * 2D-2D relative-pose RANSAC: pyopengv.relative_pose_ransac(b1, b2, algorithm, threshold, max_iterations) as called by
+ * pose_relative_ransac_2D_to_2D (omnistereo/pose_est_tools.py:54-90, call at :78; not reached by the VO drivers).
+ *   SCORE -- the reference restates OpenGV's CentralRelativePoseSacProblem in its own code (pose_est_tools.py:150-203,
+ *   is_relative_2D_to_2D_case): X = triangulate2(f1, f2, t, R) in frame 1, e1 = 1 - f1 . X/|X|,
+ *   e2 = 1 - f2 . x2/|x2| with x2 = R^T (X - t); score = e1 + e2, inlier iff score < threshold.  PINNED by that text.
+ *   MINIMAL SOLVERS -- OpenGV (not in the reference tree) offers STEWENIUS / NISTER (5 points), SEVENPT, EIGHTPT; all
+ *   built here from the published algorithms (five-point: Nister 2004, serving both five-point names; seven-point: the
+ *   cubic of the two-dimensional null space).  EIGHTPT, the linear eight-point algorithm (Longuet-Higgins 1981; Hartley 1997), restated: the 8 x 9 system
+ *   f1^T E f2 = 0 -> E = the eigenvector of A^T A with the smallest eigenvalue (cyclic Jacobi) -> SVD of E through the
+ *   Jacobi eigen-decomposition of E^T E -> the four (R, t) of E = [t]x R, |t| = 1 -> the one with the smallest summed
+ *   score over the sample points (first wins ties), as OpenGV's problem class chooses among decompositions.
+ * T = [R | t]: pose of viewpoint 2 in frame 1 (X1 = R X2 + t), as pyopengv returns it.
+ * Only + - * / sqrt and comparisons, fully parenthesised, no FMA contraction.  Checks that do not share this text:
+ * tests/test_oracle_relpose.py.
+ */
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sv_core_decl.h"
 #include "epnp_core.h"
 #include "gp3p_core.h"
 
 /* OpenGV's closed-form midpoint of the two rays (triangulation::triangulate2): the point in frame 1 and the two ray
  * parameters (depth along f1, depth along R f2). */
-__device__ static void sv_rel_triangulate(const double* R, const double* t, const double* f1, const double* f2, double* X,
+SV_FN void sv_rel_triangulate(const double* R, const double* t, const double* f1, const double* f2, double* X,
                                        double* l0_out, double* l1_out) {
   double g[3];
   for (int i = 0; i < 3; ++i) g[i] = ((R[3 * i] * f2[0]) + (R[3 * i + 1] * f2[1])) + (R[3 * i + 2] * f2[2]);
@@ -26,7 +40,7 @@ __device__ static void sv_rel_triangulate(const double* R, const double* t, cons
 }
 
 /* pose_est_tools.py:150-203 (relative case): sum of the two reprojection errors 1 - cos(angle). */
-__device__ static double sv_rel_score(const double* R, const double* t, const double* f1, const double* f2) {
+SV_FN double sv_rel_score(const double* R, const double* t, const double* f1, const double* f2) {
   double X[3], l0, l1;
   sv_rel_triangulate(R, t, f1, f2, X, &l0, &l1);
   const double n1 = sqrt(((X[0] * X[0]) + (X[1] * X[1])) + (X[2] * X[2]));
@@ -42,7 +56,7 @@ __device__ static double sv_rel_score(const double* R, const double* t, const do
 
 /* the adaptive stop of sac::Ransac for k-point samples: 1 - w^k (k = the problem's sample size INCLUDING the points it
  * draws for disambiguation: 8 for the eight-point and the five-point solvers (5 + 3), 9 for the seven-point one (7 + 2)) */
-__device__ static double sv_adaptive_base_k(int32_t best, int32_t n, int k) {
+SV_FN double sv_adaptive_base_k(int32_t best, int32_t n, int k) {
   const double w = (double)best / (double)n;
   double wk = 1.0;
   for (int j = 0; j < k; ++j) wk = wk * w;
@@ -64,7 +78,7 @@ __device__ static double sv_adaptive_base_k(int32_t best, int32_t n, int k) {
  * behind a view costs ~2) -- the candidate with the smallest sum wins, as OpenGV's CentralRelativePoseSacProblem picks
  * among the decompositions of its essential matrices.  *best_q carries the smallest sum so far across calls (several
  * essential matrices of one sample); R_out / t_out are overwritten only by a strictly better candidate. */
-__device__ static void sv_rel_decompose_pick(const double* E, const double* f1, const double* f2, int m, double* best_q,
+SV_FN void sv_rel_decompose_pick(const double* E, const double* f1, const double* f2, int m, double* best_q,
                                           double* R_out, double* t_out) {
   double S[9], Vs[9];
   for (int r = 0; r < 3; ++r)
@@ -131,7 +145,7 @@ __device__ static void sv_rel_decompose_pick(const double* E, const double* f1, 
 /* A^T A of the epipolar constraints f1^T E f2 = 0 of m correspondences (rows of A: f1_r f2_c at 3 r + c), its Jacobi
  * eigen-decomposition, and the k eigenvectors of the SMALLEST eigenvalues (ascending) as 3 x 3 matrices Eb[k][9]: an
  * orthonormal basis of the null space of A for m = 9 - k generic correspondences. */
-__device__ static void sv_rel_null_basis(const double* f1, const double* f2, int m, int k, double* Eb) {
+SV_FN void sv_rel_null_basis(const double* f1, const double* f2, int m, int k, double* Eb) {
   double M[81], V[81];
   for (int q = 0; q < 81; ++q) M[q] = 0.0;
   for (int i = 0; i < m; ++i) {
@@ -154,7 +168,7 @@ __device__ static void sv_rel_null_basis(const double* f1, const double* f2, int
 }
 
 /* Eight-point algorithm on 8 correspondences (f1[24], f2[24]) -> R, t (|t| = 1).  Returns 0 on a degenerate sample. */
-__device__ static int sv_eightpt(const double* f1, const double* f2, double* R_out, double* t_out) {
+SV_FN int sv_eightpt(const double* f1, const double* f2, double* R_out, double* t_out) {
   double E[9];
   sv_rel_null_basis(f1, f2, 8, 1, E);
   double best_q = 1e300;
@@ -165,7 +179,7 @@ __device__ static int sv_eightpt(const double* f1, const double* f2, double* R_o
 /* ---- seven-point algorithm (Hartley & Zisserman, alg. 11.1, on bearing vectors) -------------------------------------
  * The two-dimensional null space E2 + a (E1 - E2) of seven epipolar constraints; det = 0 is a cubic in a with one or
  * three real roots.  E_out[3][9]; returns the number of matrices. */
-__device__ static int sv_sevenpt(const double* f1, const double* f2, double* E_out) {
+SV_FN int sv_sevenpt(const double* f1, const double* f2, double* E_out) {
   double Eb[18];
   sv_rel_null_basis(f1, f2, 7, 2, Eb);
   /* entries as polynomials of degree 1 in a: e[k] = {E2_k, E1_k - E2_k} */
@@ -211,13 +225,13 @@ __device__ static int sv_sevenpt(const double* f1, const double* f2, double* E_o
  * Polynomials in (x, y, z) of total degree <= 3 are arrays over the 20 monomials in the paper's elimination order:
  *   0 x^3  1 y^3  2 x^2y  3 xy^2  4 x^2z  5 x^2  6 y^2z  7 y^2  8 xyz  9 xy | 10 xz^2  11 xz  12 x  13 yz^2  14 yz  15 y
  *   16 z^3  17 z^2  18 z  19 1.   A linear form is {x, y, z, 1}. */
-__device__ static void sv_fp_lin_lin_acc(const double* p, const double* q, double w, double* out) {
+SV_FN void sv_fp_lin_lin_acc(const double* p, const double* q, double w, double* out) {
   const int pr[16] = {5, 9, 11, 12, 9, 7, 14, 15, 11, 14, 17, 18, 12, 15, 18, 19};
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) out[pr[(4 * i) + j]] = out[pr[(4 * i) + j]] + (w * (p[i] * q[j]));
 }
 
-__device__ static void sv_fp_quad_lin_acc(const double* p, const double* q, double w, double* out) {
+SV_FN void sv_fp_quad_lin_acc(const double* p, const double* q, double w, double* out) {
   const int qi[10] = {5, 7, 17, 9, 11, 14, 12, 15, 18, 19}; /* x^2 y^2 z^2 xy xz yz x y z 1 */
   const int pr[40] = {0, 2, 4, 5,    3, 1, 6, 7,     10, 13, 16, 17, 2, 3, 8, 9,     4, 8, 10, 11,
                       8, 6, 13, 14,  5, 9, 11, 12,   9, 7, 14, 15,   11, 14, 17, 18, 12, 15, 18, 19};
@@ -226,7 +240,7 @@ __device__ static void sv_fp_quad_lin_acc(const double* p, const double* q, doub
 }
 
 /* f1, f2: five correspondences.  E_out[10][9]; returns the number of real solutions. */
-__device__ static int sv_fivept(const double* f1, const double* f2, double* E_out) {
+SV_FN int sv_fivept(const double* f1, const double* f2, double* E_out) {
   double Eb[36];
   sv_rel_null_basis(f1, f2, 5, 4, Eb);
   double L[9][4]; /* entry k of E as a linear form {x, y, z, 1} */
@@ -425,7 +439,7 @@ __device__ static int sv_fivept(const double* f1, const double* f2, double* E_ou
 /* One RANSAC hypothesis: distinct correspondences from the counter-based sampler (the solver's points first, then the
  * ones OpenGV's problem class draws for disambiguation: 5 + 3, 7 + 2, 8), the minimal solver, and among all the
  * decompositions of all its essential matrices the (R, t) with the smallest summed score over the whole sample. */
-__device__ static int sv_rel_hypothesis(const double* f1, const double* f2, int32_t n, int algorithm, uint64_t seed, uint64_t it,
+SV_FN int sv_rel_hypothesis(const double* f1, const double* f2, int32_t n, int algorithm, uint64_t seed, uint64_t it,
                                      double* R, double* t) {
   int32_t s[9];
   const int k = (algorithm == SV_REL_SEVENPT) ? 9 : 8;

@@ -1,12 +1,19 @@
-// sin / cos / atan in double precision from + - * / and comparisons only (Cody-Waite reduction, minimax
-// polynomials): the panorama geometry of the device code.  The CPU oracle evaluates the SAME text (oracle/trig_core.h, with
-// its own prefix) so that both sides agree to the bit; tests/gen_device_headers.py keeps the two files identical
-// and tests/test_abi.py checks it.  Edit both through that script.
+/* ONE TEXT FOR BOTH SIDES: the device code (hipcc) and the CPU oracle (gcc, oracle/Makefile reads this directory)
+ * compile this very file; sv_core_decl.h spells the function qualifiers for each.  There is no second copy.
+ *
+ * sin / cos / atan in double precision from + - * / and comparisons only, every expression fully parenthesised and built
+ * without contraction, so that the CPU oracle and the GPU evaluate the panorama geometry (pixel -> angles -> bearing,
+ * ray directions of the triangulation) to the SAME BITS: the host's and the device's math libraries differ in the last
+ * bit now and then, which was enough to break a tie between two RANSAC hypotheses in one of ~1600 soak pairs.
+ * The algorithms are the classic ones (Cody-Waite reduction by pi/2 in three pieces, minimax polynomials on
+ * [-pi/4, pi/4]; atan by argument reduction to five intervals and an odd polynomial), error below one ulp for the
+ * arguments of this path (|x| <= 2 pi); tests/test_oracle_geometry.py checks them against the host library
+ * (a check that does not share this text). */
 #pragma once
-#include <hip/hip_runtime.h>
+#include "sv_core_decl.h"
 
 /* x -> (*s, *c) = (sin x, cos x), |x| < ~1e5 */
-__device__ static void sv_sincos(double x, double* s, double* c) {
+SV_FN void sv_sincos(double x, double* s, double* c) {
   const double invpio2 = 6.36619772367581382433e-01;
   const double pio2_1 = 1.57079632673412561417e+00;  /* first 33 bits of pi/2 */
   const double pio2_2 = 6.07710050630396597660e-11;  /* second 33 bits */
@@ -62,7 +69,7 @@ __device__ static void sv_sincos(double x, double* s, double* c) {
 }
 
 /* atan x for finite x (atan2(x, 1) of the panorama's elevation) */
-__device__ static double sv_atan(double x) {
+SV_FN double sv_atan(double x) {
   if (!(x == x)) return x;
   const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01,
                aT3 = -1.11111104054623557880e-01, aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
