@@ -165,18 +165,21 @@ def test_stage_equals_the_definition_at_the_tile_edges(ctx):
 
 
 def test_stage_without_gate_and_cap_equals_the_plain_matcher(ctx):
-    rng = np.random.default_rng(3)
-    nq, nt = np.array([129, 33, 300]), np.array([257, 128, 300])
-    qd, qp = _scene(rng, 3, 320, nq)
-    td, tp = _scene(rng, 3, 320, nt)
-    st = _Stage(ctx, qd, td, qp, tp, nq, nt)
-    plain = ctx.match_hamming(st.dev[0], st.dev[1], st.dev[4], st.dev[5], k=1)
-    ctx.synchronize()
-    plain = plain.cpu().numpy()[:, :, 0]
-    for cap in (None, 256):
-        got = st.check(-1.0, 0.0, cap)
-        for p in range(3):
-            assert np.array_equal(got[p, : nq[p]], plain[p, : nq[p]])
+    """The two entry kernels are one search.  Second case: q_stride 1024 (two query tiles per wave, nq = 960: a dead second
+    tile) against t_stride 320 as ONE problem (the train range is split over three workgroups)."""
+    for seed, q_stride, nq, nt in ((3, 320, [129, 33, 300], [257, 128, 300]), (37, 1024, [960], [300])):
+        rng = np.random.default_rng(seed)
+        nq, nt = np.array(nq), np.array(nt)
+        qd, qp = _scene(rng, len(nq), q_stride, nq)
+        td, tp = _scene(rng, len(nt), 320, nt)
+        st = _Stage(ctx, qd, td, qp, tp, nq, nt)
+        plain = ctx.match_hamming(st.dev[0], st.dev[1], st.dev[4], st.dev[5], k=1)
+        ctx.synchronize()
+        plain = plain.cpu().numpy()[:, :, 0]
+        for cap in (None, 256):
+            got = st.check(-1.0, 0.0, cap)                        # (against the oracle's keys)
+            for p in range(len(nq)):
+                assert np.array_equal(got[p, : nq[p]], plain[p, : nq[p]])
 
 
 def test_stage_constructed_cases(ctx):

@@ -48,4 +48,4 @@ def test_library_mfma_kernels_keep_their_wait_states():
             assert r["branches_inside_chains"] == 0, sym
             assert not r["violations"], (sym, r["violations"][:3])
         assert not bad
-    assert seen >= 4   # match_hamming_mfma_kernel<1|2, 1|2>
+    assert seen >= 8   # match_hamming_mfma_kernel<1|2, 1|2>, match_hamming_gated_mfma_kernel<1|2, true|false>

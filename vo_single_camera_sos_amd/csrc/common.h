@@ -192,6 +192,19 @@ __device__ __forceinline__ int sosvo_block_compact_pos(bool valid, int* wave_off
   return wave_off[wid] + __popcll(bal & ((1ULL << lane) - 1ULL));
 }
 
+// Workgroup -> problem (image, mask) for the kernels that run one workgroup per problem and read that image's data (the
+// response map around the candidates, the blurred image under the descriptor patches): workgroups are dealt round-robin
+// over the 8 XCDs by linear id, so a plain p = blockIdx.x spreads the 12 masks of one image over all eight L2s and
+// every L2 fetches the image (measured: 4.1 MB of HBM fetches per pair for 0.84 MB of blurred images; 6.8 MB of pyramid
+// fetches per pair in the ORB selection alone).  Here XCD x takes
+// the images x, x + 8, x + 16, ... with all their masks: grid = 8 * ceil(nimg / 8) * nmask, -1 for the padding ids.
+__device__ __forceinline__ int xcd_problem(int nimg, int nmask) {
+  const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
+  const int img = (slot / nmask) * 8 + xcd, m = slot - (slot / nmask) * nmask;
+  return img < nimg ? img * nmask + m : -1;
+}
+static inline unsigned xcd_grid(int nimg, int nmask) { return (unsigned)(8 * cdiv(nimg, 8) * nmask); }
+
 // len(matches) of one matching problem, for the assemble kernels: how many of its nq 1-NN keys are not SOSVO_KEY_NONE
 // (every query's when the train set is not empty; fewer after sosvo_cross_check_matches).  Called by all `threads` threads of
 // the workgroup with the same arguments; the result is uniform.

@@ -29,18 +29,6 @@ constexpr int kCandCapSmall = 2048;   // first pass of the two-pass selection: 1
 constexpr int kCandCapLarge = 16384; // large-mask variant (whole-image detection, cap > 1024): 128 KB of the 160 KB LDS
 constexpr int kMaxMasks = 32;
 
-// Workgroup -> problem (image, mask) for the kernels that run one workgroup per problem and read that image's data (the
-// response map around the candidates, the blurred image under the descriptor patches): workgroups are dealt round-robin
-// over the 8 XCDs by linear id, so a plain p = blockIdx.x spreads the 12 masks of one image over all eight L2s and
-// every L2 fetches the image (measured: 4.1 MB of HBM fetches per pair for 0.84 MB of blurred images).  Here XCD x takes
-// the images x, x + 8, x + 16, ... with all their masks: grid = 8 * ceil(nimg / 8) * nmask, -1 for the padding ids.
-__device__ __forceinline__ int xcd_problem(int nimg, int nmask) {
-  const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
-  const int img = (slot / nmask) * 8 + xcd, m = slot - (slot / nmask) * nmask;
-  return img < nimg ? img * nmask + m : -1;
-}
-static inline unsigned xcd_grid(int nimg, int nmask) { return (unsigned)(8 * cdiv(nimg, 8) * nmask); }
-
 // ---- K4a: min-eigenvalue map, rolling over rows ---------------------------------------------------------
 // One wave owns a 64-column strip (3 halo columns each side, 58 output columns) of one image and walks down a
 // chunk of rows; everything a 3x3 Sobel + 3x3 box sum + 3x3 local-maximum test needs from neighbouring columns

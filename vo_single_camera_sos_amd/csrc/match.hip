@@ -51,6 +51,25 @@ __device__ __forceinline__ uint32_t hamming256(const uint4& a0, const uint4& a1,
 //     ((h ? x : x << 4) >> s) & 0x10101010, byte b.  A operands (trains): unpacked once per workgroup into an LDS tile (row
 //     pitch 272 B: conflict-free ds_read_b128 across the 16-lane groups); B operands (queries): 32 VGPRs per 32-query tile.
 //   accumulator r of lane l is (train row 8 (r / 4) + 4 (l / 32) + r % 4, query column l % 32).
+// Two entry kernels, one body: match_hamming_mfma_kernel<QT, K> (the 1-NN / 2-NN search over every train) and
+// match_hamming_gated_mfma_kernel<QT, DV> (guided matching: the 1-NN search over the trains that pass sv_pixel_gate,
+// geom_core.h, against the query: key(i) = min over admissible j of (hamming << 20 | j)) are match_hamming_mfma_body with
+// GATED off and on.  The contraction, the operand layout and the base7 preload exist once; the gated form adds:
+//   the train tile also stages the positions, as DOUBLES in structure-of-arrays order (tu[128], tv[128]): the four rows of
+//     an accumulator group are 32 consecutive bytes per coordinate, two ds_read_b128; the conversion float -> double is
+//     paid once per train and tile, not per pair;
+//   a lane keeps its query's position resident as doubles;
+//   the epilogue evaluates the gate on doubles -- fabs(u_t - u_q) <= max_du and v_t - v_q >= min_dv, literally
+//     sv_pixel_gate's expressions, so equal to the assemble kernels' for every finite float32 input (a float32 subtraction
+//     would round a difference just above max_du onto it) -- and replaces a failing element by kMmaInvalid with one select
+//     before the min chain.  None of this depends on the accumulators, so it is scheduled beside the MFMAs.
+//   DV = false drops the v side (the frame-to-frame form pays for du only).  A disabled du side is max_du = +inf (the
+//     difference of two finite float32 is finite in double), decided by the host.
+//   reversed problems (p >= n_forward) negate both v coordinates while staging: (-v_t) - (-v_q) is v_q - v_t exactly, and
+//     fabs(u_t - u_q) is symmetric, so the gate of the swapped roles costs nothing per pair.
+//   the cap: a winner whose distance exceeds max_distance is stored as SOSVO_KEY_NONE.  With a train-range split each
+//     partial winner is capped before its atomicMin: the overall winner has the smallest admissible distance, so it is
+//     stored iff it is within the cap, and no partial that loses to it matters.
 // Built with -mllvm -amdgpu-mfma-vgpr-form (csrc/Makefile): the accumulators live in VGPRs, no v_accvgpr_read per element.
 // KEEP THE MFMA SEQUENCE BRANCH-FREE.  A first version with a wave-uniform `if` around every MFMA returned a wrong key in
 // ~8 % of launches under load.  Cause (found from the ISA in round 4): a result of the 8-pass
@@ -74,19 +93,25 @@ __device__ __forceinline__ void two_smallest(int32_t& b, int32_t& s, int32_t k) 
   b = min(b, k);
 }
 
-template <int QT, int K>
-__global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
-    const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const int32_t* __restrict__ nq,
-    const int32_t* __restrict__ nt, const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot,
-    int q_stride, int t_stride, int nsplit, uint32_t* __restrict__ keys) {
+// (q_pos ... max_distance are read by the GATED form only)
+template <int QT, int K, bool GATED, bool DV>
+__device__ __forceinline__ void match_hamming_mfma_body(
+    const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
+    const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
+    const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
+    double min_dv, double max_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
+  static_assert(!GATED || K == 1, "the gated search is 1-NN");
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ __attribute__((aligned(16))) uint8_t tile[kMmaTrainTile * kMmaRowPitch];
   __shared__ __attribute__((aligned(16))) int32_t base7[kMmaTrainTile];
+  __shared__ __attribute__((aligned(16))) double tu[GATED ? kMmaTrainTile : 2];
+  __shared__ __attribute__((aligned(16))) double tv[GATED && DV ? kMmaTrainTile : 2];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
   const int p = blockIdx.x;
   const int qs = q_slot ? q_slot[p] : p, ts = t_slot ? t_slot[p] : p;
   const int nqp = min(nq[qs], q_stride), ntp = min(nt[ts], t_stride);
+  const double vsign = GATED && p >= n_forward ? -1.0 : 1.0;  // uniform over the workgroup
   constexpr int kQPerWg = (kThreads / 64) * 32 * QT;
   const int q0 = blockIdx.y * kQPerWg;
   if (q0 >= nqp) return;  // uniform over the workgroup
@@ -96,10 +121,11 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
   const int te = min(ntp, tb + tiles_per * kMmaTrainTile);
   if (nsplit > 1 && tb >= te) return;  // keys were pre-set to NONE
 
-  // ---- this wave's queries: unpacked B operands (-16 per set bit), resident
+  // ---- this wave's queries: unpacked B operands (-16 per set bit) and, when gated, positions, resident
   v4i32 bq[QT][8];
   int32_t pq[QT];
   int32_t best[QT], second[QT];
+  double qu[QT], qv[QT];
   // (a wave whose first tile lies beyond the query count sits out the contraction; a dead SECOND tile is computed on a
   // repeated row and never stored: no branch inside the MFMA sequence)
   const bool wave_live = q0 + wave * QT * 32 < nqp;  // wave-uniform
@@ -108,6 +134,11 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
     const int qi = q0 + (wave * QT + t) * 32 + col;
     const size_t row = (size_t)qs * q_stride + (qi < nqp ? qi : q0);
     const uint4 a = q_desc[row * 2 + 0], b = q_desc[row * 2 + 1];
+    if constexpr (GATED) {
+      const float2 pos = q_pos[row];
+      qu[t] = (double)pos.x;
+      qv[t] = vsign * (double)pos.y;
+    }
     const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     int32_t pc = 0;
 #pragma unroll
@@ -128,6 +159,7 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
   }
 
   const uint4* tsrc = t_desc + (size_t)ts * t_stride * 2;
+  const float2* tpsrc = GATED ? t_pos + (size_t)ts * t_stride : nullptr;
   for (int t0 = tb; t0 < te; t0 += kMmaTrainTile) {
     const int lim = min(kMmaTrainTile, te - t0);
     const int nrb = (lim + 31) >> 5;  // 32-row blocks that hold a train
@@ -151,13 +183,17 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
     }
     for (int j = tid; j < nrb * 32; j += kThreads) {
       int32_t v = kMmaInvalid7;
+      float2 pos = make_float2(0.0f, 0.0f);  // (a row without a train: its base7 loses whatever the gate says)
       if (j < lim) {
         const uint4 a = tsrc[(size_t)(t0 + j) * 2 + 0], b = tsrc[(size_t)(t0 + j) * 2 + 1];
         const int32_t pc = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) +
                            __popc(b.w);
         v = (pc << 7) + j;
+        if constexpr (GATED) pos = tpsrc[t0 + j];
       }
       base7[j] = v;
+      if constexpr (GATED) tu[j] = (double)pos.x;
+      if constexpr (GATED && DV) tv[j] = vsign * (double)pos.y;
     }
     __syncthreads();
     if (!wave_live) continue;  // (uniform per wave; the barriers above are reached by every wave)
@@ -184,16 +220,41 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
 #pragma unroll
         for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[t][kb], acc[t], 0, 0, 0);
       }
+      // the min chain over this lane's 16 (train row, query) elements per query tile, a group of four rows at a time; when
+      // gated, an element that fails the gate is replaced by kMmaInvalid first.  A CHAIN min(min(best, a), b) per pair of
+      // elements: one v_min3_i32 each (no inline asm here: the compiler's hazard recogniser has to see the reads of the MFMA
+      // results to place the wait states)
 #pragma unroll
-      for (int t = 0; t < QT; ++t) {
-        if (K == 1) {
+      for (int g = 0; g < 4; ++g) {
+        double ur[4], vr[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (GATED) {
+          const int r0 = rb * 32 + 8 * g + 4 * half;
+          const double2 u01 = *reinterpret_cast<const double2*>(tu + r0), u23 = *reinterpret_cast<const double2*>(tu + r0 + 2);
+          ur[0] = u01.x, ur[1] = u01.y, ur[2] = u23.x, ur[3] = u23.y;
+          if (DV) {
+            const double2 v01 = *reinterpret_cast<const double2*>(tv + r0), v23 = *reinterpret_cast<const double2*>(tv + r0 + 2);
+            vr[0] = v01.x, vr[1] = v01.y, vr[2] = v23.x, vr[3] = v23.y;
+          }
+        }
 #pragma unroll
-          // a CHAIN min(min(best, a), b) per pair of elements: one v_min3_i32 each (no inline asm here: the compiler's
-          // hazard recogniser has to see the reads of the MFMA results to place the wait states)
-          for (int r = 0; r < 16; r += 2) b7[t] = min(min(b7[t], acc[t][r]), acc[t][r + 1]);
-        } else {
+        for (int t = 0; t < QT; ++t) {
+          int32_t e[4];
 #pragma unroll
-          for (int r = 0; r < 16; ++r) two_smallest(b7[t], s7[t], acc[t][r]);
+          for (int r = 0; r < 4; ++r) {
+            e[r] = acc[t][4 * g + r];
+            if constexpr (GATED) {
+              bool pass = fabs(ur[r] - qu[t]) <= max_du;
+              if (DV) pass = pass && (vr[r] - qv[t] >= min_dv);
+              e[r] = pass ? e[r] : kMmaInvalid;
+            }
+          }
+          if (K == 1) {
+            b7[t] = min(min(b7[t], e[0]), e[1]);
+            b7[t] = min(min(b7[t], e[2]), e[3]);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) two_smallest(b7[t], s7[t], e[r]);
+          }
         }
       }
     }
@@ -209,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
     }
   }
 
-  // ---- the two lane halves of a column hold the same query: merge, add |q|, store
+  // ---- the two lane halves of a column hold the same query: merge, add |q|, apply the cap (gated), store
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
     const int32_t ob = __shfl_xor(best[t], 32), os = __shfl_xor(second[t], 32);
@@ -219,7 +280,8 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
     if (half == 0 && qi < nqp) {
       uint32_t* out = keys + ((size_t)p * q_stride + qi) * K;
       const uint32_t add = (uint32_t)pq[t] << SOSVO_KEY_SHIFT;
-      const uint32_t kb1 = mb >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)mb + add;
+      uint32_t kb1 = mb >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)mb + add;
+      if (GATED && kb1 != SOSVO_KEY_NONE && (kb1 >> SOSVO_KEY_SHIFT) > max_distance) kb1 = SOSVO_KEY_NONE;
       if (K == 1 && nsplit > 1) {
         atomicMin(out, kb1);
       } else {
@@ -230,197 +292,23 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
   }
 }
 
-// ---- K7 under the pixel gates (guided matching: the search along the epipolar band) ----------------------------------
-// The 1-NN search of match_hamming_mfma_kernel<QT, 1> over the trains that pass sv_pixel_gate (geom_core.h) against the
-// query: key(i) = min over admissible j of (hamming << 20 | j).  A sibling of that kernel and not a mode of it, so that its
-// four instantiations keep their machine code: the contraction, the operand layout and the base7 preload are the same, and
-// the MFMA sequence is as branch-free.  What is added:
-//   the train tile also stages the positions, as DOUBLES in structure-of-arrays order (tu[128], tv[128]): the four rows of
-//     an accumulator group are 32 consecutive bytes per coordinate, two ds_read_b128; the conversion float -> double is
-//     paid once per train and tile, not per pair;
-//   a lane keeps its query's position resident as doubles;
-//   the epilogue evaluates the gate on doubles -- fabs(u_t - u_q) <= max_du and v_t - v_q >= min_dv, literally
-//     sv_pixel_gate's expressions, so equal to the assemble kernels' for every finite float32 input (a float32 subtraction
-//     would round a difference just above max_du onto it) -- and replaces a failing element by kMmaInvalid with one select
-//     before the min chain.  None of this depends on the accumulators, so it is scheduled beside the MFMAs.
-//   DV = false drops the v side (the frame-to-frame form pays for du only).  A disabled du side is max_du = +inf (the
-//     difference of two finite float32 is finite in double), decided by the host.
-//   reversed problems (p >= n_forward) negate both v coordinates while staging: (-v_t) - (-v_q) is v_q - v_t exactly, and
-//     fabs(u_t - u_q) is symmetric, so the gate of the swapped roles costs nothing per pair.
-//   the cap: a winner whose distance exceeds max_distance is stored as SOSVO_KEY_NONE.  With a train-range split each
-//     partial winner is capped before its atomicMin: the overall winner has the smallest admissible distance, so it is
-//     stored iff it is within the cap, and no partial that loses to it matters.
+template <int QT, int K>
+__global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
+    const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const int32_t* __restrict__ nq,
+    const int32_t* __restrict__ nt, const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot,
+    int q_stride, int t_stride, int nsplit, uint32_t* __restrict__ keys) {
+  match_hamming_mfma_body<QT, K, false, false>(q_desc, t_desc, nullptr, nullptr, nq, nt, q_slot, t_slot, 0, q_stride, t_stride,
+                                               nsplit, 0.0, 0.0, 0u, keys);
+}
+
 template <int QT, bool DV>
 __global__ __launch_bounds__(kThreads) void match_hamming_gated_mfma_kernel(
     const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
     const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
     const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
     double min_dv, double max_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
-  SOSVO_LATENCY_BOUND_PRIO();
-  __shared__ __attribute__((aligned(16))) uint8_t tile[kMmaTrainTile * kMmaRowPitch];
-  __shared__ __attribute__((aligned(16))) int32_t base7[kMmaTrainTile];
-  __shared__ __attribute__((aligned(16))) double tu[kMmaTrainTile];
-  __shared__ __attribute__((aligned(16))) double tv[DV ? kMmaTrainTile : 2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 31, half = lane >> 5;
-  const int p = blockIdx.x;
-  const int qs = q_slot ? q_slot[p] : p, ts = t_slot ? t_slot[p] : p;
-  const int nqp = min(nq[qs], q_stride), ntp = min(nt[ts], t_stride);
-  const double vsign = p >= n_forward ? -1.0 : 1.0;  // uniform over the workgroup
-  constexpr int kQPerWg = (kThreads / 64) * 32 * QT;
-  const int q0 = blockIdx.y * kQPerWg;
-  if (q0 >= nqp) return;  // uniform over the workgroup
-  const int tiles = (ntp + kMmaTrainTile - 1) / kMmaTrainTile;
-  const int tiles_per = (tiles + nsplit - 1) / nsplit;
-  const int tb = blockIdx.z * tiles_per * kMmaTrainTile;
-  const int te = min(ntp, tb + tiles_per * kMmaTrainTile);
-  if (nsplit > 1 && tb >= te) return;  // keys were pre-set to NONE
-
-  // ---- this wave's queries: unpacked B operands and positions, resident (as in match_hamming_mfma_kernel)
-  v4i32 bq[QT][8];
-  int32_t pq[QT];
-  int32_t best[QT];
-  double qu[QT], qv[QT];
-  const bool wave_live = q0 + wave * QT * 32 < nqp;  // wave-uniform
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    const int qi = q0 + (wave * QT + t) * 32 + col;
-    const size_t row = (size_t)qs * q_stride + (qi < nqp ? qi : q0);
-    const uint4 a = q_desc[row * 2 + 0], b = q_desc[row * 2 + 1];
-    const float2 pos = q_pos[row];
-    qu[t] = (double)pos.x;
-    qv[t] = vsign * (double)pos.y;
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    int32_t pc = 0;
-#pragma unroll
-    for (int kb = 0; kb < 8; ++kb) {
-      pc += __popc(w[kb]);
-      const uint32_t y = half ? w[kb] : w[kb] << 4;
-      uint32_t n[4];
-#pragma unroll
-      for (int sft = 0; sft < 4; ++sft) {
-        const uint32_t m = (y >> sft) & 0x10101010u;
-        n[sft] = (m << 4) - m;  // 0x10 -> 0xF0 = -16 per byte (no carry between bytes)
-      }
-      bq[t][kb] = v4i32{(int)n[0], (int)n[1], (int)n[2], (int)n[3]};
-    }
-    pq[t] = pc;
-    best[t] = kMmaInvalid;
-  }
-
-  const uint4* tsrc = t_desc + (size_t)ts * t_stride * 2;
-  const float2* tpsrc = t_pos + (size_t)ts * t_stride;
-  for (int t0 = tb; t0 < te; t0 += kMmaTrainTile) {
-    const int lim = min(kMmaTrainTile, te - t0);
-    const int nrb = (lim + 31) >> 5;  // 32-row blocks that hold a train
-    __syncthreads();
-    for (int it = tid; it < nrb * 32 * 8; it += kThreads) {
-      const int j = it >> 3, kb = it & 7;
-      const uint32_t x = j < lim ? reinterpret_cast<const uint32_t*>(tsrc + (size_t)(t0 + j) * 2)[kb] : 0u;
-      uint4 lo, hi;
-      lo.x = (x << 4) & 0x10101010u;
-      lo.y = (x << 3) & 0x10101010u;
-      lo.z = (x << 2) & 0x10101010u;
-      lo.w = (x << 1) & 0x10101010u;
-      hi.x = x & 0x10101010u;
-      hi.y = (x >> 1) & 0x10101010u;
-      hi.z = (x >> 2) & 0x10101010u;
-      hi.w = (x >> 3) & 0x10101010u;
-      uint4* dst = reinterpret_cast<uint4*>(tile + j * kMmaRowPitch + kb * 32);
-      dst[0] = lo;
-      dst[1] = hi;
-    }
-    for (int j = tid; j < nrb * 32; j += kThreads) {
-      int32_t v = kMmaInvalid7;
-      float2 pos = make_float2(0.0f, 0.0f);  // (a row without a train: its base7 loses whatever the gate says)
-      if (j < lim) {
-        const uint4 a = tsrc[(size_t)(t0 + j) * 2 + 0], b = tsrc[(size_t)(t0 + j) * 2 + 1];
-        const int32_t pc = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) +
-                           __popc(b.w);
-        v = (pc << 7) + j;
-        pos = tpsrc[t0 + j];
-      }
-      base7[j] = v;
-      tu[j] = (double)pos.x;
-      if (DV) tv[j] = vsign * (double)pos.y;
-    }
-    __syncthreads();
-    if (!wave_live) continue;  // (uniform per wave; the barriers above are reached by every wave)
-    int32_t b7[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) b7[t] = kMmaInvalid;
-    for (int rb = 0; rb < nrb; ++rb) {
-      v16i32 acc[QT];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const v4i32 b4 = *reinterpret_cast<const v4i32*>(base7 + rb * 32 + 8 * g + 4 * half);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          acc[t][4 * g + 0] = b4.x;
-          acc[t][4 * g + 1] = b4.y;
-          acc[t][4 * g + 2] = b4.z;
-          acc[t][4 * g + 3] = b4.w;
-        }
-      }
-      const uint8_t* arow = tile + (rb * 32 + col) * kMmaRowPitch + half * 16;
-#pragma unroll
-      for (int kb = 0; kb < 8; ++kb) {
-        const v4i32 a = *reinterpret_cast<const v4i32*>(arow + kb * 32);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[t][kb], acc[t], 0, 0, 0);
-      }
-      // the gate of this lane's 16 (train row, query) elements per query tile, then the min chain over the admissible ones
-      // (plain C++ as in the ungated kernel: the compiler's hazard recogniser has to see the reads of the MFMA results)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int r0 = rb * 32 + 8 * g + 4 * half;
-        const double2 u01 = *reinterpret_cast<const double2*>(tu + r0), u23 = *reinterpret_cast<const double2*>(tu + r0 + 2);
-        const double ur[4] = {u01.x, u01.y, u23.x, u23.y};
-        double vr[4] = {0.0, 0.0, 0.0, 0.0};
-        if (DV) {
-          const double2 v01 = *reinterpret_cast<const double2*>(tv + r0), v23 = *reinterpret_cast<const double2*>(tv + r0 + 2);
-          vr[0] = v01.x;
-          vr[1] = v01.y;
-          vr[2] = v23.x;
-          vr[3] = v23.y;
-        }
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          int32_t e[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            bool pass = fabs(ur[r] - qu[t]) <= max_du;
-            if (DV) pass = pass && (vr[r] - qv[t] >= min_dv);
-            e[r] = pass ? acc[t][4 * g + r] : kMmaInvalid;
-          }
-          b7[t] = min(min(b7[t], e[0]), e[1]);
-          b7[t] = min(min(b7[t], e[2]), e[3]);
-        }
-      }
-    }
-    // widen the tile's winner: ((|t| - 2 q.t) << 7) + row  ->  ((|t| - 2 q.t) << 20) + train index
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int32_t kb1 = b7[t] < (1 << 23) ? ((b7[t] >> 7) << SOSVO_KEY_SHIFT) + (t0 + (b7[t] & 127)) : kMmaInvalid;
-      best[t] = min(best[t], kb1);
-    }
-  }
-
-  // ---- the two lane halves of a column hold the same query: merge, add |q|, apply the cap, store
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    const int32_t mb = min(best[t], __shfl_xor(best[t], 32));
-    const int qi = q0 + (wave * QT + t) * 32 + col;
-    if (half == 0 && qi < nqp) {
-      uint32_t* out = keys + (size_t)p * q_stride + qi;
-      uint32_t k1 = mb >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)mb + ((uint32_t)pq[t] << SOSVO_KEY_SHIFT);
-      if (k1 != SOSVO_KEY_NONE && (k1 >> SOSVO_KEY_SHIFT) > max_distance) k1 = SOSVO_KEY_NONE;
-      if (nsplit > 1)
-        atomicMin(out, k1);
-      else
-        out[0] = k1;
-    }
-  }
+  match_hamming_mfma_body<QT, 1, true, DV>(q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, n_forward, q_stride, t_stride,
+                                           nsplit, min_dv, max_du, max_distance, keys);
 }
 
 // ---- float descriptors (SIFT / SURF / KAZE ...): brute-force L2, cv2.BFMatcher() with its default norm
@@ -645,6 +533,23 @@ __global__ __launch_bounds__(kThreads) void match_radius_kernel(
   if (lane == 0) counts[(size_t)p * q_stride + i] = total;
 }
 
+// The launch plan of the matrix-core kernels: 4 waves x qt tiles of 32 queries per workgroup, and for the 1-NN search the
+// train range split over grid.z until ~2k workgroups exist (the split results merge with atomicMin on the packed key, so
+// the keys are pre-set to NONE here).
+struct MmaPlan {
+  int qt, nsplit;
+  dim3 grid;
+};
+int32_t mma_plan(sosvo_ctx* ctx, int nprob, int q_stride, int t_stride, int k, uint32_t* keys, MmaPlan* plan) {
+  plan->qt = (q_stride >= 1024) ? 2 : 1;
+  const int gx = cdiv(q_stride, (kThreads / 64) * 32 * plan->qt);
+  plan->nsplit = k == 1 ? std::max(1, std::min(cdiv(2048, gx * nprob), std::min(cdiv(t_stride, kMmaTrainTile), 64))) : 1;
+  if (plan->nsplit > 1)
+    SOSVO_HIP(ctx, hipMemsetAsync(keys, 0xFF, (size_t)nprob * q_stride * sizeof(uint32_t), ctx->stream));
+  plan->grid = dim3(nprob, gx, plan->nsplit);
+  return SOSVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -664,38 +569,20 @@ int32_t sosvo_match_hamming(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t
   if (nprob == 0) return SOSVO_OK;
   const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
   const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
-
-  // Matrix-pipe kernel (see match_hamming_mfma_kernel): 4 waves x QT tiles of 32 queries per workgroup.
-  const int qt = (q_stride >= 1024) ? 2 : 1;
-  const int q_per_wg = (kThreads / 64) * 32 * qt;
-  const int gx = cdiv(q_stride, q_per_wg);
-  // Split the train range over grid.z until ~2k workgroups exist (1-NN only: the split
-  // results merge with atomicMin on the packed key).
-  int nsplit = 1;
+  MmaPlan plan;
+  if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, k, keys, &plan)) return rc;
+  // (the profile labels a launch with its instantiation, as SOSVO_LAUNCH does)
+  auto launch = [&](auto kernel, const char* name) {
+    SOSVO_PROFILE(ctx, name);
+    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride, t_stride,
+                       plan.nsplit, keys);
+  };
   if (k == 1) {
-    const int tiles = cdiv(t_stride, kMmaTrainTile);
-    nsplit = cdiv(2048, gx * nprob);
-    if (nsplit > tiles) nsplit = tiles;
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > 64) nsplit = 64;
-  }
-  if (nsplit > 1)
-    SOSVO_HIP(ctx, hipMemsetAsync(keys, 0xFF, (size_t)nprob * q_stride * sizeof(uint32_t), ctx->stream));
-  dim3 grid(nprob, gx, nsplit), block(kThreads);
-  if (k == 1) {
-    if (qt == 2)
-      SOSVO_LAUNCH(ctx, (match_hamming_mfma_kernel<2, 1>), grid, block, 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride,
-                   t_stride, nsplit, keys);
-    else
-      SOSVO_LAUNCH(ctx, (match_hamming_mfma_kernel<1, 1>), grid, block, 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride,
-                   t_stride, nsplit, keys);
+    if (plan.qt == 2) launch(match_hamming_mfma_kernel<2, 1>, "(match_hamming_mfma_kernel<2, 1>)");
+    else launch(match_hamming_mfma_kernel<1, 1>, "(match_hamming_mfma_kernel<1, 1>)");
   } else {
-    if (qt == 2)
-      SOSVO_LAUNCH(ctx, (match_hamming_mfma_kernel<2, 2>), grid, block, 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride,
-                   t_stride, nsplit, keys);
-    else
-      SOSVO_LAUNCH(ctx, (match_hamming_mfma_kernel<1, 2>), grid, block, 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride,
-                   t_stride, nsplit, keys);
+    if (plan.qt == 2) launch(match_hamming_mfma_kernel<2, 2>, "(match_hamming_mfma_kernel<2, 2>)");
+    else launch(match_hamming_mfma_kernel<1, 2>, "(match_hamming_mfma_kernel<1, 2>)");
   }
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
@@ -721,32 +608,23 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
   const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
   const float2* qp = reinterpret_cast<const float2*>(q_pos);
   const float2* tp = reinterpret_cast<const float2*>(t_pos);
-  // the grid of sosvo_match_hamming(k = 1)
-  const int qt = (q_stride >= 1024) ? 2 : 1;
-  const int gx = cdiv(q_stride, (kThreads / 64) * 32 * qt);
-  int nsplit = cdiv(2048, gx * nprob);
-  nsplit = std::max(1, std::min(nsplit, std::min(cdiv(t_stride, kMmaTrainTile), 64)));
-  if (nsplit > 1)
-    SOSVO_HIP(ctx, hipMemsetAsync(keys, 0xFF, (size_t)nprob * q_stride * sizeof(uint32_t), ctx->stream));
+  MmaPlan plan;
+  if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan)) return rc;
   // sv_pixel_gate's switches: the du side is on for max_du > 0, the dv side for min_dv >= 0
   const double du = max_du > 0 ? max_du : HUGE_VAL;
   const bool dv = min_dv >= 0;
   const uint32_t cap = (uint32_t)max_distance;
-  dim3 grid(nprob, gx, nsplit), block(kThreads);
-  if (qt == 2) {
-    if (dv)
-      SOSVO_LAUNCH(ctx, (match_hamming_gated_mfma_kernel<2, true>), grid, block, 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot,
-                   t_slot, n_forward, q_stride, t_stride, nsplit, min_dv, du, cap, keys);
-    else
-      SOSVO_LAUNCH(ctx, (match_hamming_gated_mfma_kernel<2, false>), grid, block, 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot,
-                   t_slot, n_forward, q_stride, t_stride, nsplit, min_dv, du, cap, keys);
+  auto launch = [&](auto kernel, const char* name) {
+    SOSVO_PROFILE(ctx, name);
+    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                       q_stride, t_stride, plan.nsplit, min_dv, du, cap, keys);
+  };
+  if (plan.qt == 2) {
+    if (dv) launch(match_hamming_gated_mfma_kernel<2, true>, "(match_hamming_gated_mfma_kernel<2, true>)");
+    else launch(match_hamming_gated_mfma_kernel<2, false>, "(match_hamming_gated_mfma_kernel<2, false>)");
   } else {
-    if (dv)
-      SOSVO_LAUNCH(ctx, (match_hamming_gated_mfma_kernel<1, true>), grid, block, 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot,
-                   t_slot, n_forward, q_stride, t_stride, nsplit, min_dv, du, cap, keys);
-    else
-      SOSVO_LAUNCH(ctx, (match_hamming_gated_mfma_kernel<1, false>), grid, block, 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot,
-                   t_slot, n_forward, q_stride, t_stride, nsplit, min_dv, du, cap, keys);
+    if (dv) launch(match_hamming_gated_mfma_kernel<1, true>, "(match_hamming_gated_mfma_kernel<1, true>)");
+    else launch(match_hamming_gated_mfma_kernel<1, false>, "(match_hamming_gated_mfma_kernel<1, false>)");
   }
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;

@@ -61,17 +61,6 @@ __device__ __forceinline__ const uint8_t* level_image(const LevelSrc& S, const P
   return l == 0 ? S.gray + (size_t)img * S.npix0 : S.pyr + (size_t)img * S.total + P.off[l];
 }
 
-// Workgroup -> problem (image, mask), XCD-aware (as detect.hip's xcd_problem): workgroups are dealt round-robin over the 8
-// XCDs by linear id, so p = blockIdx.x spreads the 12 masks of one image over all eight L2s and every L2 fetches that
-// image's pyramid (round 3's PMC pass: 6.8 MB of fetches per frame pair in the selection alone).  Here XCD x takes the images
-// x, x + 8, ... with all their masks: grid = 8 * ceil(nimg / 8) * nmask, -1 for the padding ids.
-__device__ __forceinline__ int orb_xcd_problem(int nimg, int nmask) {
-  const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
-  const int img = (slot / nmask) * 8 + xcd, m = slot - (slot / nmask) * nmask;
-  return img < nimg ? img * nmask + m : -1;
-}
-inline unsigned orb_xcd_grid(int nimg, int nmask) { return (unsigned)(8 * ((nimg + 7) / 8) * nmask); }
-
 // ---- pyramid -------------------------------------------------------------------------------------------
 struct ResizeTap {
   int i0, i1, w0, w1;
@@ -1155,7 +1144,7 @@ __global__ __launch_bounds__(kThreads, 4) void orb_select_kernel(LevelSrc S, con
   __shared__ uint32_t region32[kSelRegionBytes / 4];  // the level's pixels under the mask's candidates (steps 3 and 6)
   __shared__ int s_nc, s_thr, s_keep, s_nout, s_nk;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int p = orb_xcd_problem(nimg_total, nmask);
+  const int p = xcd_problem(nimg_total, nmask);
   if (p < 0) return;  // uniform (padding workgroup)
   const int img = p / nmask, m = p - img * nmask;
   if (tid == 0) s_nout = 0;
@@ -1468,7 +1457,7 @@ __global__ __launch_bounds__(kThreads) void orb_describe_levels_kernel(const uin
   __shared__ int wave_off[5];
   __shared__ int s_running;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int p = orb_xcd_problem(nimg_total, nmask);
+  const int p = xcd_problem(nimg_total, nmask);
   if (p < 0) return;  // uniform (padding workgroup)
   const int img = p / nmask;
   const int n = min(n_io[p], cap);
@@ -1882,7 +1871,7 @@ int32_t run_orb_detect(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask
     if (rc != SOSVO_OK) return rc;
   }
   LevelSrc S{gray, W.pyr, (long long)rows * cols, P.total};
-  SOSVO_LAUNCH(ctx, orb_select_kernel, dim3(orb_xcd_grid(nimg, nmask)), dim3(kThreads), 0, ctx->stream, S, W.score,
+  SOSVO_LAUNCH(ctx, orb_select_kernel, dim3(xcd_grid(nimg, nmask)), dim3(kThreads), 0, ctx->stream, S, W.score,
                W.flags, mask_pyr, W.bbox, P, images_per_maskset, nmask, cap, kp4, resp, n, nimg,
                have_flags ? 1 : 0);
   SOSVO_LAUNCH_CHECK(ctx);
@@ -1954,7 +1943,7 @@ int32_t run_orb_describe(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows
                                                          P.total, rr, nimg);
     if (rc != SOSVO_OK) return rc;
   }
-  SOSVO_LAUNCH(ctx, orb_describe_levels_kernel, dim3(orb_xcd_grid(nimg, nmask)), dim3(kThreads),
+  SOSVO_LAUNCH(ctx, orb_describe_levels_kernel, dim3(xcd_grid(nimg, nmask)), dim3(kThreads),
                (size_t)cap * 6 * sizeof(float), ctx->stream, W.blur, P, nlev_have, rows, cols, nmask, cap, kp4, n, pattern, desc,
                kp_xy, nimg);
   SOSVO_LAUNCH_CHECK(ctx);
