@@ -47,6 +47,11 @@ def main_rgbd_vo(argv=None):
                         help="the frame-to-frame matcher searches among the keypoints within the tracker's |du| gate; default: off")
     parser.add_argument("--gated_max_distance", default=None, type=int,
                         help="with --gated_matching: a match whose Hamming distance exceeds this (1 .. 256) is no match; default: no cap")
+    parser.add_argument("--ratio_test", action="store_true",
+                        help="Lowe's ratio rule in the frame-to-frame matcher, on the GPU; needs --ratio; default: off")
+    parser.add_argument("--ratio", default=None, type=float,
+                        help="with --ratio_test: keep a match iff its distance is below this times the runner-up's; a multiple "
+                             "of 1/64 in (0, 1), e.g. 0.75")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -86,6 +91,7 @@ def main_rgbd_vo(argv=None):
                              frame_window=None if args.frame_window < 0 else args.frame_window,
                              detection_method=args.detection_method, cross_check=True if args.cross_check else None,
                              gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
+                             ratio_test=True if args.ratio_test else None, ratio=args.ratio,
                              lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
@@ -97,7 +103,8 @@ def main_rgbd_vo(argv=None):
                     thread_name="%s-%s" % (scene_name, "RGB-D"),
                     frame_window=None if args.frame_window < 0 else args.frame_window,
                     detection_method=args.detection_method, cross_check=True if args.cross_check else None,
-                    gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance)
+                    gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
+                    ratio_test=True if args.ratio_test else None, ratio=args.ratio)
     print("GOODBYE!")
     return out
 

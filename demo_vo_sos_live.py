@@ -42,6 +42,12 @@ def main_sos_vo_live(argv=None, frame_source=None):
                              "without a value, or the static-stereo / the frame-to-frame matcher alone; default: off")
     parser.add_argument("--gated_max_distance", default=None, type=int,
                         help="with --gated_matching: a match whose Hamming distance exceeds this (1 .. 256) is no match; default: no cap")
+    parser.add_argument("--ratio_test", nargs="?", const="both", default=None, choices=("both", "stereo", "f2f"),
+                        help="Lowe's ratio rule in the matchers, on the GPU: both matchers when given without a value, or the "
+                             "static-stereo / the frame-to-frame matcher alone; needs --ratio; default: off")
+    parser.add_argument("--ratio", default=None, type=float,
+                        help="with --ratio_test: keep a match iff its distance is below this times the runner-up's; a multiple "
+                             "of 1/64 in (0, 1), e.g. 0.75")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -61,7 +67,9 @@ def main_sos_vo_live(argv=None, frame_source=None):
                          frame_window=None if args.frame_window < 0 else args.frame_window,
                          cross_check=None if args.cross_check is None else (True if args.cross_check == "both" else args.cross_check),
                          gated_matching=None if args.gated_matching is None else (True if args.gated_matching == "both" else args.gated_matching),
-                         gated_max_distance=args.gated_max_distance)
+                         gated_max_distance=args.gated_max_distance,
+                         ratio_test=None if args.ratio_test is None else (True if args.ratio_test == "both" else args.ratio_test),
+                         ratio=args.ratio)
     print("GOODBYE!")
     return out
 

@@ -76,6 +76,12 @@ int32_t sosvo_set_stream(sosvo_ctx* ctx, void* stream);
  * test in double precision, as rounds 1 - 3 did.  Same counts, bit for bit (tests/test_gpu_ransac.py compares the two
  * forms); ~1.6 x the kernel's time.  For A/B measurements (scripts/score_tiers.py). */
 #define SOSVO_HINT_SCORE_FP64_ONLY 2
+/* SOSVO_HINT_MATCH_UNSPLIT (value != 0): sosvo_match_hamming(k = 1), sosvo_match_hamming_gated and sosvo_match_hamming_ratio
+ * walk the whole train range in one workgroup per query tile instead of splitting it over workgroups that merge with atomics
+ * (small problem counts: the live driver, sequence mode at window 1).  Same keys and rivals, bit for bit
+ * (tests/test_gpu_ratio_test.py compares the two forms).  For A/B measurements (scripts/bench_ratio_test.py); not passed on
+ * to the internal contexts of sosvo_frame_pair_batch_streams. */
+#define SOSVO_HINT_MATCH_UNSPLIT 3
 int32_t sosvo_set_hint(sosvo_ctx* ctx, int32_t hint, int32_t value);
 int32_t sosvo_synchronize(sosvo_ctx* ctx);
 const char* sosvo_last_error(const sosvo_ctx* ctx);
@@ -312,6 +318,35 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
                                   const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
                                   const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
                                   double min_dv, double max_du, int32_t max_distance, uint32_t* keys);
+
+/* Lowe's distinctiveness ("ratio") rule fused into the 1-NN search (omnistereo/camera_models.py:421-423: knnMatch(k = 2) and
+ * m[0].distance < m[1].distance * 0.75).  Arguments as in sosvo_match_hamming_gated, and two forms:
+ *   q_pos == t_pos == NULL  the PLAIN form: every train j < nt[ts] is admissible; min_dv / max_du are ignored and
+ *                           max_distance must be 256
+ *   both given              the GATED form: the admissible trains are those that pass gate(i, j) of
+ *                           sosvo_match_hamming_gated, reversed problems included
+ *   exactly one given       SOSVO_ERR_ARG
+ * For query i of a FORWARD problem (p < n_forward) let k1 < k2 be the two smallest keys (hamming << 20 | j) over the
+ * admissible trains, d1 = k1 >> 20, d2 = k2 >> 20.  All distances are integers, and so is the rule:
+ *   keep(i)  <=>  64 * d1 < ratio_64ths * d2                 (ratio_64ths 1 .. 63; 48 is d1 < d2 * 0.75 for all integers)
+ *   keys[p*q_stride + i]   = k1 if keep(i) and d1 <= max_distance, else SOSVO_KEY_NONE   (the cap acts after the rule)
+ *   rivals[p*q_stride + i] = k2, or SOSVO_KEY_NONE if fewer than two trains are admissible
+ * Two trains at the same distance never pass (not even at distance 0); ties between trains are resolved by the key order
+ * (lowest train index first).  NO RUNNER-UP (fewer than two admissible trains): the plain form drops the match, as the
+ * reference's len(m) == 2 does; the gated form KEEPS it -- a partner that is alone inside the geometric gate is unique by
+ * construction.  The form decides, not the gate values: the gated form with both gate sides disabled still keeps a lone
+ * train, and that is the one place where it differs from the plain form.
+ * REVERSED problems (p >= n_forward) only answer "did train j choose i back" for sosvo_cross_check_matches and get no
+ * rule: their keys are those of sosvo_match_hamming(k = 1) (plain) or sosvo_match_hamming_gated (gated), bit for bit, and
+ * their rows of rivals are unspecified.  After the cross-check a match thus survives iff it passes the rule AND is mutual.
+ * keys and rivals are [nprob, q_stride] u32 and BOTH required: rivals is the second merge word of the train-range split.
+ * Rows i >= nq[qs] are unspecified.  The results do not depend on how the train range is split.  Wherever a key is not
+ * SOSVO_KEY_NONE it is the key of the search of the same form without the rule. */
+int32_t sosvo_match_hamming_ratio(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                                  const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
+                                  const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
+                                  double min_dv, double max_du, int32_t max_distance, int32_t ratio_64ths,
+                                  uint32_t* keys, uint32_t* rivals);
 
 /* Float descriptors (SIFT / SURF / KAZE ...; feature_detection_method "SIFT" / "SURF" makes FeatureMatcher build
  * cv2.BFMatcher() with its default NORM_L2, omnistereo/camera_models.py:394-396): brute-force L2 matching.
@@ -611,6 +646,26 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
 #define SOSVO_GATED_MAX_DIST(d) ((d) << SOSVO_GATED_MAX_DIST_SHIFT)
 #define SOSVO_GATED_MAX_DIST_OF(flags) (((flags) & SOSVO_GATED_MAX_DIST_MASK) >> SOSVO_GATED_MAX_DIST_SHIFT)
 
+/* ---- the ratio rule in the batch and sequence entry points (sosvo_match_hamming_ratio) -----------------------
+ *   SOSVO_FLAG_RATIO_STEREO  static stereo: a bottom keypoint's match is kept only if 64 * d1 < r * d2 against the runner-up
+ *   SOSVO_FLAG_RATIO_F2F     frame to frame, per view: likewise
+ *   SOSVO_RATIO_64THS(r)     bits 25-30: the ratio r in 64ths, 1 .. 63 (48 = the reference's 0.75); a switch bit with the
+ *                            field 0 is SOSVO_ERR_ARG (and a workspace size of 0); ignored without a RATIO bit
+ * Honoured in sosvo_batch_cfg.ransac_flags; ..._F2F and the field in sosvo_rgbd_batch_cfg.flags, ..._STEREO there is
+ * SOSVO_ERR_ARG (and a workspace size of 0).  Without SOSVO_FLAG_GATED_* of the same step the plain form runs (a query with
+ * a single train has no match); with it the gated form: the runner-up is sought among the admissible trains, a partner
+ * alone inside the gate is kept, and the cap acts after the rule.  Together with SOSVO_FLAG_CROSS_CHECK_*: the
+ * role-swapped problems get no rule, so a match survives iff it passes the rule AND is mutual; one launch as before.
+ * A dropped match has the key SOSVO_KEY_NONE; sort and assemble treat it as after the cross-check filter.  The bits never
+ * reach the RANSAC flags; the struct layouts and, with the switch bits clear, workspace sizes, launches and results are
+ * unchanged.  With a switch set the workspace grows by that step's rivals (one u32 per key of the step). */
+#define SOSVO_FLAG_RATIO_STEREO 0x10
+#define SOSVO_FLAG_RATIO_F2F 0x20
+#define SOSVO_RATIO_64THS_SHIFT 25
+#define SOSVO_RATIO_64THS_MASK (0x3F << SOSVO_RATIO_64THS_SHIFT)
+#define SOSVO_RATIO_64THS(r) ((r) << SOSVO_RATIO_64THS_SHIFT)
+#define SOSVO_RATIO_64THS_OF(flags) (((flags) & SOSVO_RATIO_64THS_MASK) >> SOSVO_RATIO_64THS_SHIFT)
+
 /* ---- the whole hot path for a batch of frame pairs (the throughput entry point) ----------------
  * One call = for B independent pairs (frames 2i = reference / keyframe, 2i+1 = current):
  *   OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__ for both frames
@@ -656,7 +711,8 @@ typedef struct sosvo_batch_cfg {
   float cos_a, sin_a;      /* descriptor orientation given to the GFT keypoints */
   int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P;
                               SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above);
-                              SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above) */
+                              SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above);
+                              SOSVO_FLAG_RATIO_STEREO / _F2F, SOSVO_RATIO_64THS(r): the ratio rule (see above) */
   int32_t detector;        /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
@@ -795,6 +851,7 @@ typedef struct sosvo_rgbd_batch_cfg {
                               bits 8-9: SOSVO_RGBD_DETECTOR(enum sosvo_detector), 0 = GFT (masked off before the solver).
                               SOSVO_FLAG_CROSS_CHECK_F2F: mutual matches only (masked off as well; ..._STEREO: SOSVO_ERR_ARG).
                               SOSVO_FLAG_GATED_F2F, SOSVO_GATED_MAX_DIST(d): search under the gate (likewise; ..._STEREO: SOSVO_ERR_ARG).
+                              SOSVO_FLAG_RATIO_F2F, SOSVO_RATIO_64THS(r): the ratio rule (likewise; ..._STEREO: SOSVO_ERR_ARG).
                               The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
                               for every frame) */
   double quality, min_distance;        /* 0.01, 5 */

@@ -62,13 +62,15 @@ def _accuracy(rec, poses, stereo_points):
             "median_translation_error_mm": round(float(np.median(tra)), 3)}
 
 
-def bench_pairs(args, emit, names, gs, rig_kw, omni, poses):
+# (kw / run_vo_kw: setting name -> the engines' / run_VO's keyword arguments; other benchmarks reuse these three functions with
+# settings of their own)
+def bench_pairs(args, emit, names, gs, rig_kw, omni, poses, kw=_kw):
     import torch
     from vo_single_camera_sos_amd.pipeline import OverlappedFramePairs, RigConfig
     engines = {}
     for name in names:
         eng = OverlappedFramePairs(0, gs, (480, 640), RigConfig(**rig_kw), args.pairs, n_streams=args.streams, num_of_features=1000,
-                                   kp_cap=512, frame_cap=2048, max_iter=args.iters, adaptive=False, seed=args.seed, **_kw(name))
+                                   kp_cap=512, frame_cap=2048, max_iter=args.iters, adaptive=False, seed=args.seed, **kw(name))
         eng.load_frames(omni)
         engines[name] = eng
 
@@ -105,7 +107,7 @@ def bench_pairs(args, emit, names, gs, rig_kw, omni, poses):
         eng.close()
 
 
-def bench_six(args, emit, names):
+def bench_six(args, emit, names, kw=_kw):
     from vo_single_camera_sos_amd import synthetic
     from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
     from vo_single_camera_sos_amd.pipeline import FramePairPipeline, RigConfig
@@ -118,7 +120,7 @@ def bench_six(args, emit, names):
     fe.load_frames(omni)
     fe.run()
     for name in names:
-        pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), B, frame_cap=2048, max_iter=2000, seed=11, front_end=fe, **_kw(name))
+        pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), B, frame_cap=2048, max_iter=2000, seed=11, front_end=fe, **kw(name))
         pipe.stereo()
         pipe.track()
         out = {"record": "six_pairs", "setting": name}
@@ -126,7 +128,7 @@ def bench_six(args, emit, names):
         emit(out)
 
 
-def bench_sequence(args, emit, names, seq, seq_poses):
+def bench_sequence(args, emit, names, seq, seq_poses, run_vo_kw=_run_vo_kw):
     import torch
     from vo_single_camera_sos_amd.omnistereo import transformations as tr
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
@@ -140,12 +142,12 @@ def bench_sequence(args, emit, names, seq, seq_poses):
     times, last = {name: [] for name in names}, {}
     with tempfile.TemporaryDirectory() as d, contextlib.redirect_stdout(io.StringIO()):
         for name in names:                           # engine, scratch, first-use costs: outside the clock
-            run_VO(None, models[name], results_path=d, _live_frames=lambda: frames(min(N, 34)), frame_window=32, **_run_vo_kw(name))
+            run_VO(None, models[name], results_path=d, _live_frames=lambda: frames(min(N, 34)), frame_window=32, **run_vo_kw(name))
         torch.cuda.synchronize()
         for _ in range(args.reps):
             for name in names:
                 t0 = time.perf_counter()
-                last[name] = run_VO(None, models[name], results_path=d, _live_frames=frames, frame_window=32, **_run_vo_kw(name))
+                last[name] = run_VO(None, models[name], results_path=d, _live_frames=frames, frame_window=32, **run_vo_kw(name))
                 torch.cuda.synchronize()
                 times[name].append(time.perf_counter() - t0)
     base = statistics.median(times["off"]) if "off" in times else None

@@ -72,6 +72,8 @@ SIGNATURES = {
     "sosvo_match_hamming": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_match_hamming_gated": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64,
                                           c_i32, c_p]),
+    "sosvo_match_hamming_ratio": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64,
+                                          c_i32, c_i32, c_p, c_p]),
     "sosvo_match_radius": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_cross_check_matches": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_sort_matches": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p]),
@@ -124,6 +126,7 @@ SIGNATURES = {
 
 HINT_SHARED_DEVICE = 1
 HINT_SCORE_FP64_ONLY = 2
+HINT_MATCH_UNSPLIT = 3
 FLAG_CAM_ROT_IDENTITY = 1
 FLAG_EPNP = 2
 FLAG_GP3P = 4
@@ -134,6 +137,10 @@ FLAG_GATED_STEREO = 0x4000         # search under the pixel gates: static stereo
 FLAG_GATED_F2F = 0x8000            # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
 GATED_MAX_DIST_SHIFT = 16          # SOSVO_GATED_MAX_DIST(d): bits 16-24, 0 = no cap
 GATED_MAX_DIST_MASK = 0x1FF << GATED_MAX_DIST_SHIFT
+FLAG_RATIO_STEREO = 0x10           # the ratio rule: static stereo (sosvo_batch_cfg.ransac_flags)
+FLAG_RATIO_F2F = 0x20              # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
+RATIO_64THS_SHIFT = 25             # SOSVO_RATIO_64THS(r): bits 25-30, the ratio in 64ths, 1 .. 63
+RATIO_64THS_MASK = 0x3F << RATIO_64THS_SHIFT
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1
 DETECTOR_FAST = 2
@@ -204,6 +211,34 @@ def gated_flags(stereo=False, f2f=False, max_distance=None):
     flags = (FLAG_GATED_STEREO if stereo else 0) | (FLAG_GATED_F2F if f2f else 0)
     if flags and max_distance is not None:
         flags |= int(max_distance) << GATED_MAX_DIST_SHIFT
+    return flags
+
+
+def ratio_64ths(ratio):
+    """A Python ratio -> SOSVO_RATIO_64THS's r: a float in (0, 1) with ratio * 64 an integer (0.75 -> 48).  Nothing is
+    rounded: the device rule is the integer rule 64 * d1 < r * d2, and a ratio it cannot represent is refused."""
+    try:
+        x = float(ratio) * 64.0
+    except (TypeError, ValueError):
+        raise ValueError("ratio must be a float in (0, 1) with ratio * 64 an integer, got %r" % (ratio,))
+    if not (x == x and 1.0 <= x <= 63.0 and x == int(x)):
+        if x != x:
+            raise ValueError("ratio must be a float in (0, 1) with ratio * 64 an integer, got %r" % (ratio,))
+        lo, hi = sorted(sorted(range(1, 64), key=lambda c: abs(c - x))[:2])
+        raise ValueError("ratio must be a float in (0, 1) with ratio * 64 an integer, got %r; the nearest admissible values "
+                         "are %r (%d/64) and %r (%d/64)" % (ratio, lo / 64.0, lo, hi / 64.0, hi))
+    return int(x)
+
+
+def ratio_flags(stereo=False, f2f=False, ratio=None):
+    """The SOSVO_FLAG_RATIO_* bits and the SOSVO_RATIO_64THS field of a batch configuration.  ratio: see ratio_64ths; a
+    switch needs one.  The ratio belongs to the rule: without a switch it is checked but not encoded."""
+    r = None if ratio is None else ratio_64ths(ratio)
+    flags = (FLAG_RATIO_STEREO if stereo else 0) | (FLAG_RATIO_F2F if f2f else 0)
+    if flags and r is None:
+        raise ValueError("the ratio test needs a ratio (a float in (0, 1) with ratio * 64 an integer, e.g. 0.75)")
+    if flags:
+        flags |= r << RATIO_64THS_SHIFT
     return flags
 
 

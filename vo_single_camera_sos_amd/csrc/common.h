@@ -35,6 +35,7 @@ struct sosvo_ctx {
   int32_t n_sub;
   int32_t hint_score_fp64_only;  // sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): no single-precision tier in ransac_score_kernel
   int32_t hint_shared_device;  // sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other streams' kernels share the chip
+  int32_t hint_match_unsplit;  // sosvo_set_hint(SOSVO_HINT_MATCH_UNSPLIT): the matrix-core matchers do not split the train range
   int32_t sub_last;  // parts of the most recent sosvo_frame_pair_batch_streams[_enqueue] call
   // un-joined work of an ..._enqueue call is pending on the part streams: only then does the next call chain its first
   // median behind the previous call's last one, and only then must its slice layout (workspace pointer, part count, each

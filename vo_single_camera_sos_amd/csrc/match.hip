@@ -70,6 +70,21 @@ __device__ __forceinline__ uint32_t hamming256(const uint4& a0, const uint4& a1,
 //   the cap: a winner whose distance exceeds max_distance is stored as SOSVO_KEY_NONE.  With a train-range split each
 //     partial winner is capped before its atomicMin: the overall winner has the smallest admissible distance, so it is
 //     stored iff it is within the cap, and no partial that loses to it matters.
+// RATIO (match_hamming_ratio_mfma_kernel<QT, GATED, DV>, sosvo_match_hamming_ratio): Lowe's distinctiveness rule on the
+// device.  The body tracks the runner-up among the admissible keys beside the MFMAs as K == 2 does (two_smallest on the
+// elements AFTER the gate's select, so an inadmissible train is neither winner nor runner-up) and forms, per query of a
+// forward problem (p < n_forward, uniform over the workgroup and read in the epilogue only),
+//   keep = runner-up present ? 64 * d1 < ratio * d2 : GATED        (integers; a lone train inside a gate is unique)
+// then the cap on the winner.  Reversed problems keep their unfiltered 1-NN keys.  keys and rivals are [nprob, q_stride].
+//   the train-range split stays: the two smallest merge across splits with vector atomics on the two words of a query,
+//     old = atomicMin(&best, b); atomicMin(&rival, max(old, b)); atomicMin(&rival, s);
+//     with (b, s) a split's two smallest.  Keys are unique per train, so the minima do not depend on the order of arrival.
+//     `best` ends as the smallest b.  Every b that is not that one reaches `rival`: by its own split when it arrives above
+//     the current best (max(old, b) = b; best only falls, so it never wins later), or by the split that displaces it
+//     (max(old, b) = old).  The overall winner arrives below everything and is never displaced, so it is never pushed.
+//     The overall runner-up is either another split's b or the winning split's s, and both kinds are pushed: the end state
+//     is the exact two smallest, the bits of the unsplit loop.  The rule and the cap are then one elementwise pass over
+//     (best, rival) (ratio_finish_kernel); with nsplit == 1 they are fused into the epilogue here and the pass is skipped.
 // Built with -mllvm -amdgpu-mfma-vgpr-form (csrc/Makefile): the accumulators live in VGPRs, no v_accvgpr_read per element.
 // KEEP THE MFMA SEQUENCE BRANCH-FREE.  A first version with a wave-uniform `if` around every MFMA returned a wrong key in
 // ~8 % of launches under load.  Cause (found from the ISA in round 4): a result of the 8-pass
@@ -93,14 +108,27 @@ __device__ __forceinline__ void two_smallest(int32_t& b, int32_t& s, int32_t k) 
   b = min(b, k);
 }
 
-// (q_pos ... max_distance are read by the GATED form only)
-template <int QT, int K, bool GATED, bool DV>
+// keep(i) of the ratio rule and the cap, on final keys: the one text of the fused epilogue and of ratio_finish_kernel
+template <bool GATED>
+__device__ __forceinline__ uint32_t ratio_filter(uint32_t k1, uint32_t k2, uint32_t ratio, uint32_t max_distance) {
+  if (k1 == SOSVO_KEY_NONE) return k1;
+  const uint32_t d1 = k1 >> SOSVO_KEY_SHIFT, d2 = k2 >> SOSVO_KEY_SHIFT;
+  const bool keep = k2 == SOSVO_KEY_NONE ? GATED : 64u * d1 < ratio * d2;
+  return keep && d1 <= max_distance ? k1 : SOSVO_KEY_NONE;
+}
+
+// (q_pos ... max_distance are read by the GATED form only; n_forward by the GATED and the RATIO forms; ratio and rivals by
+// the RATIO form, whose K is 1: one key per query in each of keys and rivals)
+template <int QT, int K, bool GATED, bool DV, bool RATIO = false>
 __device__ __forceinline__ void match_hamming_mfma_body(
     const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
     const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
     const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
-    double min_dv, double max_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
-  static_assert(!GATED || K == 1, "the gated search is 1-NN");
+    double min_dv, double max_du, uint32_t max_distance, uint32_t ratio, uint32_t* __restrict__ keys,
+    uint32_t* __restrict__ rivals) {
+  static_assert(!GATED || K == 1, "the gated search stores one key per query");
+  static_assert(!RATIO || K == 1, "the ratio form stores one key per query in keys and one in rivals");
+  constexpr bool TWO = K == 2 || RATIO;  // track the runner-up
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ __attribute__((aligned(16))) uint8_t tile[kMmaTrainTile * kMmaRowPitch];
   __shared__ __attribute__((aligned(16))) int32_t base7[kMmaTrainTile];
@@ -248,7 +276,7 @@ __device__ __forceinline__ void match_hamming_mfma_body(
               e[r] = pass ? e[r] : kMmaInvalid;
             }
           }
-          if (K == 1) {
+          if (!TWO) {
             b7[t] = min(min(b7[t], e[0]), e[1]);
             b7[t] = min(min(b7[t], e[2]), e[3]);
           } else {
@@ -262,7 +290,7 @@ __device__ __forceinline__ void match_hamming_mfma_body(
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
       const int32_t kb1 = b7[t] < (1 << 23) ? ((b7[t] >> 7) << SOSVO_KEY_SHIFT) + (t0 + (b7[t] & 127)) : kMmaInvalid;
-      if (K == 2) {
+      if (TWO) {
         const int32_t ks1 = s7[t] < (1 << 23) ? ((s7[t] >> 7) << SOSVO_KEY_SHIFT) + (t0 + (s7[t] & 127)) : kMmaInvalid;
         second[t] = min(max(best[t], kb1), min(second[t], ks1));
       }
@@ -282,7 +310,23 @@ __device__ __forceinline__ void match_hamming_mfma_body(
       const uint32_t add = (uint32_t)pq[t] << SOSVO_KEY_SHIFT;
       uint32_t kb1 = mb >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)mb + add;
       if (GATED && kb1 != SOSVO_KEY_NONE && (kb1 >> SOSVO_KEY_SHIFT) > max_distance) kb1 = SOSVO_KEY_NONE;
-      if (K == 1 && nsplit > 1) {
+      if constexpr (RATIO) {
+        // (the cap above is the reversed rows' and a no-op at 256; a forward row is capped after the rule)
+        const uint32_t raw = mb >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)mb + add;
+        const uint32_t ks1 = ms >= kMmaInvalid ? SOSVO_KEY_NONE : (uint32_t)ms + add;
+        uint32_t* riv = rivals + (size_t)p * q_stride + qi;
+        if (p >= n_forward) {  // uniform over the workgroup: the unfiltered 1-NN key of today
+          if (nsplit > 1) atomicMin(out, kb1);
+          else out[0] = kb1, riv[0] = ks1;
+        } else if (nsplit > 1) {
+          const uint32_t old = atomicMin(out, raw);
+          atomicMin(riv, max(old, raw));
+          atomicMin(riv, ks1);
+        } else {
+          out[0] = ratio_filter<GATED>(raw, ks1, ratio, max_distance);
+          riv[0] = ks1;
+        }
+      } else if (K == 1 && nsplit > 1) {
         atomicMin(out, kb1);
       } else {
         out[0] = kb1;
@@ -298,7 +342,7 @@ __global__ __launch_bounds__(kThreads) void match_hamming_mfma_kernel(
     const int32_t* __restrict__ nt, const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot,
     int q_stride, int t_stride, int nsplit, uint32_t* __restrict__ keys) {
   match_hamming_mfma_body<QT, K, false, false>(q_desc, t_desc, nullptr, nullptr, nq, nt, q_slot, t_slot, 0, q_stride, t_stride,
-                                               nsplit, 0.0, 0.0, 0u, keys);
+                                               nsplit, 0.0, 0.0, 0u, 0u, keys, nullptr);
 }
 
 template <int QT, bool DV>
@@ -308,7 +352,27 @@ __global__ __launch_bounds__(kThreads) void match_hamming_gated_mfma_kernel(
     const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
     double min_dv, double max_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
   match_hamming_mfma_body<QT, 1, true, DV>(q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, n_forward, q_stride, t_stride,
-                                           nsplit, min_dv, max_du, max_distance, keys);
+                                           nsplit, min_dv, max_du, max_distance, 0u, keys, nullptr);
+}
+
+template <int QT, bool GATED, bool DV>
+__global__ __launch_bounds__(kThreads) void match_hamming_ratio_mfma_kernel(
+    const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
+    const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
+    const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
+    double min_dv, double max_du, uint32_t max_distance, uint32_t ratio, uint32_t* __restrict__ keys,
+    uint32_t* __restrict__ rivals) {
+  match_hamming_mfma_body<QT, 1, GATED, DV, true>(q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, n_forward, q_stride,
+                                                  t_stride, nsplit, min_dv, max_du, max_distance, ratio, keys, rivals);
+}
+
+// The rule and the cap over the merged (best, rival) of a split ratio launch: forward rows only (n rows of q_stride keys).
+// A row past its problem's query count still holds the NONE it was pre-set to and stays NONE.
+template <bool GATED>
+__global__ __launch_bounds__(kThreads) void ratio_finish_kernel(uint32_t* __restrict__ keys, const uint32_t* __restrict__ rivals,
+                                                                size_t n, uint32_t ratio, uint32_t max_distance) {
+  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < n) keys[i] = ratio_filter<GATED>(keys[i], rivals[i], ratio, max_distance);
 }
 
 // ---- float descriptors (SIFT / SURF / KAZE ...): brute-force L2, cv2.BFMatcher() with its default norm
@@ -540,12 +604,15 @@ struct MmaPlan {
   int qt, nsplit;
   dim3 grid;
 };
-int32_t mma_plan(sosvo_ctx* ctx, int nprob, int q_stride, int t_stride, int k, uint32_t* keys, MmaPlan* plan) {
+int32_t mma_plan(sosvo_ctx* ctx, int nprob, int q_stride, int t_stride, int k, uint32_t* keys, MmaPlan* plan,
+                 uint32_t* rivals = nullptr) {  // (rivals: the ratio form's second merge word, k = 1)
   plan->qt = (q_stride >= 1024) ? 2 : 1;
   const int gx = cdiv(q_stride, (kThreads / 64) * 32 * plan->qt);
-  plan->nsplit = k == 1 ? std::max(1, std::min(cdiv(2048, gx * nprob), std::min(cdiv(t_stride, kMmaTrainTile), 64))) : 1;
+  plan->nsplit = k == 1 && !ctx->hint_match_unsplit ? std::max(1, std::min(cdiv(2048, gx * nprob), std::min(cdiv(t_stride, kMmaTrainTile), 64))) : 1;
   if (plan->nsplit > 1)
     SOSVO_HIP(ctx, hipMemsetAsync(keys, 0xFF, (size_t)nprob * q_stride * sizeof(uint32_t), ctx->stream));
+  if (plan->nsplit > 1 && rivals)
+    SOSVO_HIP(ctx, hipMemsetAsync(rivals, 0xFF, (size_t)nprob * q_stride * sizeof(uint32_t), ctx->stream));
   plan->grid = dim3(nprob, gx, plan->nsplit);
   return SOSVO_OK;
 }
@@ -627,6 +694,68 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
     else launch(match_hamming_gated_mfma_kernel<1, false>, "(match_hamming_gated_mfma_kernel<1, false>)");
   }
   SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_match_hamming_ratio(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                                  const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
+                                  const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
+                                  double min_dv, double max_du, int32_t max_distance, int32_t ratio_64ths, uint32_t* keys,
+                                  uint32_t* rivals) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, q_desc && t_desc && nq && nt, "null pointer");
+  SOSVO_REQUIRE(ctx, keys && rivals, "keys and rivals are both required");
+  SOSVO_REQUIRE(ctx, (q_pos != nullptr) == (t_pos != nullptr), "q_pos and t_pos go together (both NULL: the plain form)");
+  const bool gated = q_pos != nullptr;
+  SOSVO_REQUIRE(ctx, ratio_64ths >= 1 && ratio_64ths <= 63, "ratio_64ths out of range (1..63)");
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
+  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");
+  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");
+  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range");
+  if (gated) {
+    SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)");
+    SOSVO_REQUIRE(ctx, min_dv == min_dv && max_du == max_du, "min_dv / max_du must not be NaN");
+    SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned");
+  } else {
+    SOSVO_REQUIRE(ctx, max_distance == 256, "max_distance must be 256 in the plain form (no positions)");
+  }
+  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0,
+                "descriptor arrays must be 16-byte aligned");
+  SOSVO_REQUIRE(ctx, ((uintptr_t)keys & 3) == 0 && ((uintptr_t)rivals & 3) == 0, "keys and rivals must be 4-byte aligned");
+  if (nprob == 0) return SOSVO_OK;
+  const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
+  const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
+  const float2* qp = reinterpret_cast<const float2*>(q_pos);
+  const float2* tp = reinterpret_cast<const float2*>(t_pos);
+  MmaPlan plan;
+  if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan, rivals)) return rc;
+  const double du = max_du > 0 ? max_du : HUGE_VAL;  // (sv_pixel_gate's switches, as in sosvo_match_hamming_gated)
+  const bool dv = gated && min_dv >= 0;
+  const uint32_t cap = (uint32_t)max_distance, ratio = (uint32_t)ratio_64ths;
+  auto launch = [&](auto kernel, const char* name) {
+    SOSVO_PROFILE(ctx, name);
+    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                       q_stride, t_stride, plan.nsplit, min_dv, du, cap, ratio, keys, rivals);
+  };
+  if (plan.qt == 2) {
+    if (!gated) launch(match_hamming_ratio_mfma_kernel<2, false, false>, "(match_hamming_ratio_mfma_kernel<2, false, false>)");
+    else if (dv) launch(match_hamming_ratio_mfma_kernel<2, true, true>, "(match_hamming_ratio_mfma_kernel<2, true, true>)");
+    else launch(match_hamming_ratio_mfma_kernel<2, true, false>, "(match_hamming_ratio_mfma_kernel<2, true, false>)");
+  } else {
+    if (!gated) launch(match_hamming_ratio_mfma_kernel<1, false, false>, "(match_hamming_ratio_mfma_kernel<1, false, false>)");
+    else if (dv) launch(match_hamming_ratio_mfma_kernel<1, true, true>, "(match_hamming_ratio_mfma_kernel<1, true, true>)");
+    else launch(match_hamming_ratio_mfma_kernel<1, true, false>, "(match_hamming_ratio_mfma_kernel<1, true, false>)");
+  }
+  SOSVO_LAUNCH_CHECK(ctx);
+  if (plan.nsplit > 1 && n_forward > 0) {
+    const size_t n = (size_t)n_forward * q_stride;
+    const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
+    if (gated)
+      SOSVO_LAUNCH(ctx, ratio_finish_kernel<true>, grid, dim3(kThreads), 0, ctx->stream, keys, rivals, n, ratio, cap);
+    else
+      SOSVO_LAUNCH(ctx, ratio_finish_kernel<false>, grid, dim3(kThreads), 0, ctx->stream, keys, rivals, n, ratio, cap);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
   return SOSVO_OK;
 }
 

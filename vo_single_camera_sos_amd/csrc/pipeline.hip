@@ -63,9 +63,37 @@ bool cross_stereo(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLA
 bool cross_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
 bool cross_f2f(const sosvo_rgbd_batch_cfg& c) { return (c.flags & SOSVO_FLAG_CROSS_CHECK_F2F) != 0; }
 // (an RGB-D camera has no static stereo to cross-check)
-bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) {
-  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO)) == 0;
+// ---- the ratio rule (SOSVO_FLAG_RATIO_*, sosvo_match_hamming_ratio): a matching step with its switch set runs the fused
+// ratio form of its search, plain or under the step's Gate.  r64 = 0: off, the step is the call it always was.  `rivals` is
+// the step's runner-up / split-merge buffer, as large as the step's keys; carved only when a switch is set, after everything
+// else, so that the other members keep their offsets and the workspace its size.
+struct Ratio {
+  int32_t r64 = 0;
+  uint32_t* rivals = nullptr;
+};
+// a switch bit needs a ratio; the field alone is ignored
+bool ratio_flags_ok(int32_t flags) {
+  return (flags & (SOSVO_FLAG_RATIO_STEREO | SOSVO_FLAG_RATIO_F2F)) == 0 || SOSVO_RATIO_64THS_OF(flags) != 0;
 }
+int32_t ratio_of(int32_t flags, int32_t bit) { return (flags & bit) ? SOSVO_RATIO_64THS_OF(flags) : 0; }
+int32_t ratio_stereo(const sosvo_batch_cfg& c) { return ratio_of(c.ransac_flags, SOSVO_FLAG_RATIO_STEREO); }
+int32_t ratio_f2f(const sosvo_batch_cfg& c) { return ratio_of(c.ransac_flags, SOSVO_FLAG_RATIO_F2F); }
+int32_t ratio_f2f(const sosvo_rgbd_batch_cfg& c) { return ratio_of(c.flags, SOSVO_FLAG_RATIO_F2F); }
+Ratio carve_ratio(Carver& cv, int32_t r64, size_t n_keys) {
+  Ratio r;
+  if (!r64) return r;
+  r.r64 = r64;
+  r.rivals = cv.take<uint32_t>(n_keys);
+  return r;
+}
+constexpr const char* kBadRatioFlags = "SOSVO_FLAG_RATIO_STEREO / _F2F need SOSVO_RATIO_64THS(r), r in 1..63";
+
+bool rgbd_stereo_flags_ok(const sosvo_rgbd_batch_cfg& c) {
+  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO | SOSVO_FLAG_RATIO_STEREO)) == 0;
+}
+constexpr const char* kRgbdStereoFlags =
+    "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO / SOSVO_FLAG_RATIO_STEREO: an RGB-D camera has no static stereo";
+bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) { return rgbd_stereo_flags_ok(c) && ratio_flags_ok(c.flags); }
 
 // ---- gated matching (SOSVO_FLAG_GATED_*): the 1-NN search among the trains that pass the assemble stage's own pixel gate.
 // A Gate holds that stage's arguments; with `on` clear a matching step is the plain sosvo_match_hamming call it always was.
@@ -108,6 +136,7 @@ struct FrontEndTmp {
   uint32_t* s_keys;
   OrbBufs orb;
   MutualTabs mutual;
+  Ratio ratio;
 };
 FrontEndTmp carve_front_end(Carver& cv, const sosvo_batch_cfg& c, size_t F) {
   FrontEndTmp t{};
@@ -165,6 +194,7 @@ struct TrackTmp {
   uint8_t* mask;
   double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
   MutualTabs mutual;
+  Ratio ratio;  // (one buffer serves both views: their matching steps follow each other on the stream)
 };
 TrackTmp carve_track(Carver& cv, size_t B, size_t Fc, bool mutual) {
   TrackTmp t{};
@@ -211,6 +241,8 @@ Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* bas
   ws.fe.orb = carve_orb(cv, c.detector, 2 * window * c.nmask, c.kp_cap, 2, c.rows, c.cols);
   ws.fe.mutual = carve_mutual(cv, cross_stereo(c), window * c.nmask);
   ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
+  ws.fe.ratio = carve_ratio(cv, ratio_stereo(c), (cross_stereo(c) ? 2 : 1) * window * c.nmask * c.kp_cap);
+  ws.tt.ratio = carve_ratio(cv, ratio_f2f(c), (cross_f2f(c) ? 2 : 1) * (size_t)c.n_pairs * c.frame_cap);
   ws.bytes = cv.off;
   return ws;
 }
@@ -368,6 +400,7 @@ struct RgbdTrackTmp {
   double *f, *p, *T_ransac, *T, *lm_cost;
   double *cam_off, *cam_rot;  // (never carved: a central camera has none, they stay null for the setup kernel)
   MutualTabs mutual;
+  Ratio ratio;
 };
 RgbdTrackTmp carve_rgbd_track(Carver& cv, size_t B, size_t Fc, bool mutual) {
   RgbdTrackTmp t{};
@@ -405,6 +438,7 @@ RgbdWorkspace carve_rgbd(const sosvo_rgbd_batch_cfg& c, size_t window, size_t sl
   ws.tt = carve_rgbd_track(cv, c.n_pairs, c.frame_cap, cross_f2f(c));
   ws.fe.orb = carve_orb(cv, rgbd_detector(c), window, c.kp_cap, 1, c.rows, c.cols);
   ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
+  ws.tt.ratio = carve_ratio(cv, ratio_f2f(c), (cross_f2f(c) ? 2 : 1) * (size_t)c.n_pairs * c.frame_cap);
   ws.bytes = cv.off;
   return ws;
 }
@@ -508,7 +542,7 @@ extern "C" {
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->nmask <= 0 || cfg->kp_cap <= 0 ||
-      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap))
+      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap) || !ratio_flags_ok(cfg->ransac_flags))
     return 0;
   // (laxer than the call itself, which refuses nmask > 32, kp_cap > 4096 and frame_cap > 16384: such a shape gets a size
   // here and "out of range" there)
@@ -531,10 +565,15 @@ static int32_t mutual_tabs(sosvo_ctx* ctx, const int32_t* q, const int32_t* t, i
 }
 
 // The 1-NN search of a matching step: under the gate g when it is on (positions q_pos / t_pos, indexed like the descriptors;
-// problems at and beyond n_forward have the roles swapped), plain otherwise.
-static int32_t match_1nn(sosvo_ctx* ctx, const Gate& g, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+// problems at and beyond n_forward have the roles swapped), plain otherwise; with the ratio rule r on the forward problems
+// when it is on.
+static int32_t match_1nn(sosvo_ctx* ctx, const Gate& g, const Ratio& r, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
                          const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot, const int32_t* t_slot,
                          int nprob, int n_forward, int stride, uint32_t* keys) {
+  if (r.r64)
+    return sosvo_match_hamming_ratio(ctx, q_desc, t_desc, g.on ? q_pos : nullptr, g.on ? t_pos : nullptr, nq, nt, q_slot, t_slot,
+                                     nprob, n_forward, stride, stride, g.min_dv, g.max_du, g.on ? g.max_distance : 256, r.r64,
+                                     keys, r.rivals);
   if (!g.on) return sosvo_match_hamming(ctx, q_desc, t_desc, nq, nt, q_slot, t_slot, nprob, stride, stride, 1, keys);
   return sosvo_match_hamming_gated(ctx, q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, nprob, n_forward, stride, stride,
                                    g.min_dv, g.max_du, g.max_distance, keys);
@@ -543,10 +582,10 @@ static int32_t match_1nn(sosvo_ctx* ctx, const Gate& g, const uint8_t* q_desc, c
 // One such step over the descriptor store `desc` (blocks of `stride` rows, counts `cnt`, positions `pos`): ONE launch of n
 // forward + n role-swapped problems through the tables, then the filter on the forward keys.  The forward keys of `keys`
 // [2 n, stride] are sorted and assembled like those of a plain sosvo_match_hamming call.
-static int32_t match_mutual(sosvo_ctx* ctx, const Gate& g, const uint8_t* desc, const float* pos, const int32_t* cnt, int n,
+static int32_t match_mutual(sosvo_ctx* ctx, const Gate& g, const Ratio& r, const uint8_t* desc, const float* pos, const int32_t* cnt, int n,
                             int stride, const MutualTabs& m, uint32_t* keys) {
   int32_t rc;
-  STAGE(match_1nn(ctx, g, desc, desc, pos, pos, cnt, cnt, m.q_slot, m.t_slot, 2 * n, n, stride, keys));
+  STAGE(match_1nn(ctx, g, r, desc, desc, pos, pos, cnt, cnt, m.q_slot, m.t_slot, 2 * n, n, stride, keys));
   return sosvo_cross_check_matches(ctx, keys, keys + (size_t)n * stride, cnt, cnt, m.q_slot, m.t_slot, n, stride, stride, keys,
                                    nullptr);
 }
@@ -607,9 +646,9 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const Gate gate = gate_stereo(*cfg, *rig);
   if (cross_stereo(*cfg)) {  // (top and bottom are the two halves of t.desc / t.kp / t.n: blocks p and h + p)
     STAGE(mutual_tabs(ctx, nullptr, nullptr, h, t.mutual));
-    STAGE(match_mutual(ctx, gate, t.desc, t.kp, t.n, h, cap, t.mutual, t.s_keys));
+    STAGE(match_mutual(ctx, gate, t.ratio, t.desc, t.kp, t.n, h, cap, t.mutual, t.s_keys));
   } else
-    STAGE(match_1nn(ctx, gate, desc_bot, desc_top, kp_bot, kp_top, n_bot, n_top, nullptr, nullptr, h, h, cap, t.s_keys));
+    STAGE(match_1nn(ctx, gate, t.ratio, desc_bot, desc_top, kp_bot, kp_top, n_bot, n_top, nullptr, nullptr, h, h, cap, t.s_keys));
   STAGE(sosvo_sort_matches(ctx, t.s_keys, n_bot, nullptr, h, cap, t.s_order));
   if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
     STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
@@ -633,14 +672,14 @@ static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_ba
   const Gate gate = gate_f2f(*cfg, *rig);
   if (mutual) {  // (one pair of tables serves both views)
     STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
-    STAGE(match_mutual(ctx, gate, s.d_top, s.m_top, s.M, B, Fc, b.mutual, b.k_top));
+    STAGE(match_mutual(ctx, gate, b.ratio, s.d_top, s.m_top, s.M, B, Fc, b.mutual, b.k_top));
   } else
-    STAGE(match_1nn(ctx, gate, s.d_top, s.d_top, s.m_top, s.m_top, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_top));
+    STAGE(match_1nn(ctx, gate, b.ratio, s.d_top, s.d_top, s.m_top, s.m_top, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_top));
   STAGE(sosvo_sort_matches(ctx, b.k_top, s.M, b.cur_frame, B, Fc, b.o_top));
   if (mutual)
-    STAGE(match_mutual(ctx, gate, s.d_bot, s.m_bot, s.M, B, Fc, b.mutual, b.k_bot));
+    STAGE(match_mutual(ctx, gate, b.ratio, s.d_bot, s.m_bot, s.M, B, Fc, b.mutual, b.k_bot));
   else
-    STAGE(match_1nn(ctx, gate, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
+    STAGE(match_1nn(ctx, gate, b.ratio, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
   STAGE(sosvo_sort_matches(ctx, b.k_bot, s.M, b.cur_frame, B, Fc, b.o_bot));
   STAGE(sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top,
                            b.o_top, b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top));
@@ -675,6 +714,7 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_REQUIRE(ctx, cfg->nmask >= 1 && cfg->nmask <= 32 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096, "nmask / kp_cap out of range");
   SOSVO_REQUIRE(ctx, cfg->frame_cap > 0 && cfg->frame_cap <= 16384, "frame_cap out of range (max 16384)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
+  SOSVO_REQUIRE(ctx, ratio_flags_ok(cfg->ransac_flags), kBadRatioFlags);
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
   const Workspace ws = carve(*cfg, F, F, workspace);
@@ -887,9 +927,9 @@ static int32_t run_rgbd_tracking(sosvo_ctx* ctx, const sosvo_rgbd_batch_cfg* cfg
   const Gate gate = gate_f2f(*cfg);
   if (cross_f2f(*cfg)) {
     STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
-    STAGE(match_mutual(ctx, gate, s.d, s.m, s.M, B, Fc, b.mutual, b.keys));
+    STAGE(match_mutual(ctx, gate, b.ratio, s.d, s.m, s.M, B, Fc, b.mutual, b.keys));
   } else
-    STAGE(match_1nn(ctx, gate, s.d, s.d, s.m, s.m, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.keys));
+    STAGE(match_1nn(ctx, gate, b.ratio, s.d, s.d, s.m, s.m, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.keys));
   STAGE(sosvo_sort_matches(ctx, b.keys, s.M, b.cur_frame, B, Fc, b.order));
   STAGE(sosvo_f2f_assemble_central(ctx, cfg->pct_good_matches, cfg->f2f_max_hdiff, s.m, s.X, s.b, s.M, Fc, b.ref_frame,
                                    b.cur_frame, b.keys, b.order, B, Fc, b.f, b.p, b.cq, b.ct, b.cn));
@@ -920,7 +960,8 @@ int32_t sosvo_rgbd_pair_batch(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam, const s
   SOSVO_REQUIRE(ctx, cfg->kp_cap > 0 && cfg->kp_cap <= 4096 && cfg->frame_cap > 0 && cfg->frame_cap <= 16384,
                 "kp_cap / frame_cap out of range");
   SOSVO_REQUIRE(ctx, detector_ok(rgbd_detector(*cfg), cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
-  SOSVO_REQUIRE(ctx, rgbd_flags_ok(*cfg), "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO: an RGB-D camera has no static stereo");
+  SOSVO_REQUIRE(ctx, rgbd_stereo_flags_ok(*cfg), kRgbdStereoFlags);
+  SOSVO_REQUIRE(ctx, ratio_flags_ok(cfg->flags), kBadRatioFlags);
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
   const RgbdWorkspace ws = carve_rgbd(*cfg, F, F, workspace);
@@ -967,8 +1008,9 @@ struct OmniSeq {
   using Frames = OmniFrames;
   static constexpr const char* kTooSmall = "workspace too small (see sosvo_sequence_workspace)";
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
-    return c && c->nmask >= 1 && c->nmask <= 32 && seq_shape_ok(c, c->detector, window, slots);
+    return c && c->nmask >= 1 && c->nmask <= 32 && ratio_flags_ok(c->ransac_flags) && seq_shape_ok(c, c->detector, window, slots);
   }
+  static const char* flags_msg(const Cfg* c) { return ratio_flags_ok(c->ransac_flags) ? nullptr : kBadRatioFlags; }
   static constexpr const char* kBadFrames = SOSVO_TABLE_FRAME_MSG;
   static bool frames_ok(const Cfg* c) { return sosvo_table_frame_ok(c->H, c->W); }  // the front end reads them through the table
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return ::carve(c, window, slots, base); }
@@ -994,6 +1036,9 @@ struct RgbdSeq {
   static constexpr const char* kTooSmall = "workspace too small (see sosvo_rgbd_sequence_workspace)";
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
     return c && rgbd_flags_ok(*c) && seq_shape_ok(c, rgbd_detector(*c), window, slots);
+  }
+  static const char* flags_msg(const Cfg* c) {
+    return !rgbd_stereo_flags_ok(*c) ? kRgbdStereoFlags : ratio_flags_ok(c->flags) ? nullptr : kBadRatioFlags;
   }
   static constexpr const char* kBadFrames = "";
   static bool frames_ok(const Cfg*) { return true; }  // no table: the RGB-D frames are the images
@@ -1023,6 +1068,7 @@ size_t seq_workspace(const typename Fam::Cfg* cfg, int32_t window, int32_t slots
 template <typename Fam>
 int32_t seq_open(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* cfg, int32_t window, int32_t slots, bool range_ok,
                  const char* range_msg, bool aligned, void* workspace, size_t workspace_bytes, typename Fam::Ws& ws) {
+  if (cfg && Fam::flags_msg(cfg)) return sosvo_fail(ctx, SOSVO_ERR_ARG, fn, Fam::flags_msg(cfg));  // (a message that says what to fix)
   REQUIRE_FOR(ctx, fn, Fam::shape_ok(cfg, window, slots), "bad sequence configuration (window, slots, capacities)");
   REQUIRE_FOR(ctx, fn, range_ok, range_msg);
   if (aligned) REQUIRE_FOR(ctx, fn, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");

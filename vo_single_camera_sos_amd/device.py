@@ -89,6 +89,11 @@ class Context(object):
         """sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other contexts' kernels run beside this one's (scheduling only)."""
         self._call(self._lib.sosvo_set_hint, _lib.HINT_SHARED_DEVICE, 1 if on else 0)
 
+    def set_hint_match_unsplit(self, on=True):
+        """sosvo_set_hint(SOSVO_HINT_MATCH_UNSPLIT): the matrix-core matchers walk the train range in one workgroup per query tile
+        instead of splitting it (same keys, bit for bit; for A/B measurements)."""
+        self._call(self._lib.sosvo_set_hint, _lib.HINT_MATCH_UNSPLIT, 1 if on else 0)
+
     def set_hint_score_fp64_only(self, on=True):
         """sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): RANSAC scoring without its single-precision first tier (same counts;
         for A/B measurements and the cross-check of the two forms)."""
@@ -423,6 +428,49 @@ class Context(object):
                    _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
                    float(max_du), 256 if max_distance is None else int(max_distance), _ptr(keys))
         return keys
+
+    def match_hamming_ratio(self, q_desc, t_desc, nq, nt, ratio_64ths, q_pos=None, t_pos=None, min_dv=-1.0, max_du=0.0,
+                            max_distance=None, keys=None, rivals=None, q_slot=None, t_slot=None, n_forward=None):
+        """The 1-NN search with Lowe's ratio rule fused in (sosvo_match_hamming_ratio): a forward problem's query keeps its
+        key iff 64 * d1 < ratio_64ths * d2 against the runner-up (ratio_64ths 1 .. 63, 48 = 0.75).  q_pos / t_pos both None:
+        the plain form (no runner-up: dropped); both given: the gated form of match_hamming_gated with min_dv / max_du /
+        max_distance (no runner-up inside the gate: kept; the cap acts after the rule).  Problems p >= n_forward (default:
+        none) are reversed and get no rule.  -> (keys [P, Sq, 1] u32, rivals [P, Sq, 1] u32): the filtered keys, KEY_NONE
+        where dropped, and each query's runner-up key (unspecified in reversed rows)."""
+        _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
+        _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
+        Bq, Sq = q_desc.shape[0], q_desc.shape[1]
+        Bt, St = t_desc.shape[0], t_desc.shape[1]
+        if (q_pos is None) != (t_pos is None):
+            raise SosvoError("q_pos and t_pos go together")
+        if q_pos is not None:
+            _check(q_pos, torch.float32, "q_pos", (Bq, Sq, 2))
+            _check(t_pos, torch.float32, "t_pos", (Bt, St, 2))
+        elif max_distance is not None:
+            raise SosvoError("max_distance belongs to the gated form (q_pos / t_pos)")
+        _check(nq, torch.int32, "nq", (Bq,))
+        _check(nt, torch.int32, "nt", (Bt,))
+        if (q_slot is None) != (t_slot is None):
+            raise SosvoError("q_slot and t_slot go together")
+        if q_slot is not None:
+            P = q_slot.shape[0]
+            _check(q_slot, torch.int32, "q_slot", (P,))
+            _check(t_slot, torch.int32, "t_slot", (P,))
+        else:
+            if Bq != Bt:
+                raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
+            P = Bq
+        if keys is None:
+            keys = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
+        if rivals is None:
+            rivals = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
+        _check(keys, torch.uint32, "keys", (P, Sq, 1))
+        _check(rivals, torch.uint32, "rivals", (P, Sq, 1))
+        self._call(self._lib.sosvo_match_hamming_ratio, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq), _ptr(nt),
+                   _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
+                   float(max_du), 256 if max_distance is None else int(max_distance), int(ratio_64ths), _ptr(keys),
+                   _ptr(rivals))
+        return keys, rivals
 
     def match_l2(self, q_desc, t_desc, nq, nt, k=1):
         """Float descriptors: q_desc [P, Sq, dim] f32, t_desc [P, St, dim] f32 -> keys [P, Sq, k] int64 holding the u64

@@ -141,7 +141,14 @@ class FeatureMatcher(object):
     gated=True (with gated_max_distance=None or 1 .. 256) marks the matcher for the search under the pixel gates: the
     callers that know the keypoint positions and the gate (match_features_panoramic_top_bottom,
     match_features_frame_to_frame) then call match_gated / match_gated_many in place of match; match itself has no
-    positions and stays the plain search.  Same restrictions as cross_check, and both may be set: mutual under the gate."""
+    positions and stays the plain search.  Same restrictions as cross_check, and both may be set: mutual under the gate.
+    ratio=r (a float in (0, 1) with r * 64 an integer, e.g. the reference's 0.75 of :423) applies Lowe's ratio rule ON THE
+    DEVICE, fused into the search (Context.match_hamming_ratio): a match is kept iff distance < r * the runner-up's, in
+    integers.  match / match_arrays run the plain form (a query with a single train descriptor has no match, as the
+    reference's len(m) == 2), match_gated / match_gated_many the gated form (the runner-up is sought among the admissible
+    trains; a partner alone inside the gate is kept; the cap acts after the rule).  With cross_check the role-swapped search
+    gets no rule: a match survives iff it passes the rule and is mutual.  Same restrictions as cross_check (k_best == 1, no
+    radius match, binary descriptors; ValueError otherwise).  The "SIFT" k_best == 2 host rule is separate and unchanged."""
 
     def __init__(self, method, matcher_type, k_best, *args, **kwargs):
         self.feature_detection_method = method
@@ -162,6 +169,22 @@ class FeatureMatcher(object):
         self.gated_max_distance = kwargs.get("gated_max_distance", None)
         if self.gated:
             self._check_gated(self.gated_max_distance)
+        self.ratio = kwargs.get("ratio", None)
+        self._check_ratio()
+
+    def _check_ratio(self):
+        """-> the ratio in 64ths, 0 without one."""
+        if self.ratio is None:
+            return 0
+        from .._lib import ratio_64ths
+        if self.k_best != 1:
+            raise ValueError("ratio goes with k_best == 1 only (the rule returns one match per query; k_best == 2 returns both neighbours)")
+        if self.use_radius_match:
+            raise ValueError("ratio is defined for best-match search, not for radius match")
+        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
+            raise ValueError("ratio is built for binary (Hamming) descriptors only; %r makes float descriptors"
+                             % self.feature_detection_method)
+        return ratio_64ths(self.ratio)
 
     def _check_gated(self, max_distance=None):
         if self.k_best != 1:
@@ -214,6 +237,9 @@ class FeatureMatcher(object):
         every pair, but as ONE batched launch + one copy back when the matcher is in its best-match mode (the per-bucket
         loop of match_features_panoramic_top_bottom costs a dozen launch / synchronise round trips per frame otherwise)."""
         import torch
+        r64 = self._check_ratio()
+        if r64 and any(self._is_float(q) or self._is_float(t) for q, t in pairs):
+            raise ValueError("ratio is built for binary (Hamming) descriptors only, not float descriptors")
         if self.use_radius_match or self.k_best != 1 or len(pairs) == 0 or any(self._is_float(q) or self._is_float(t) for q, t in pairs):
             return [self.match_arrays(q, t) for q, t in pairs]
         ctx = self._context()
@@ -235,7 +261,7 @@ class FeatureMatcher(object):
         dev = ctx.device
         nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
         dq, dt = torch.from_numpy(hq).to(dev), torch.from_numpy(ht).to(dev)
-        keys = ctx.match_hamming(dq, dt, nq_d, nt_d, k=1)
+        keys = ctx.match_hamming_ratio(dq, dt, nq_d, nt_d, r64)[0] if r64 else ctx.match_hamming(dq, dt, nq_d, nt_d, k=1)
         if self.cross_check:
             ctx.cross_check_matches(keys, ctx.match_hamming(dt, dq, nt_d, nq_d, k=1), nq_d, nt_d, keys_out=keys)
         order = ctx.sort_matches(keys, nq_d)
@@ -248,7 +274,7 @@ class FeatureMatcher(object):
                 continue
             o = oh[i, :nq[i]]
             k = kh[i][o]
-            if self.cross_check:  # (the rejected queries sorted last)
+            if self.cross_check or r64:  # (the rejected queries sorted last)
                 o, k = o[k != KEY_NONE], k[k != KEY_NONE]
             out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
         return out
@@ -263,6 +289,7 @@ class FeatureMatcher(object):
         import torch
         self._check_cross_check()
         self._check_gated(max_distance)
+        r64 = self._check_ratio()
         if any(self._is_float(q) or self._is_float(t) for q, t, _, _ in items):
             raise ValueError("gated matching is built for binary (Hamming) descriptors only, not float descriptors")
         P = len(items)
@@ -289,7 +316,11 @@ class FeatureMatcher(object):
         dev = ctx.device
         nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
         dq, dt, dpq, dpt = (torch.from_numpy(a).to(dev) for a in (hq, ht, pq, pt))
-        keys = ctx.match_hamming_gated(dq, dt, dpq, dpt, nq_d, nt_d, min_dv, max_du, max_distance)
+        if r64:
+            keys = ctx.match_hamming_ratio(dq, dt, nq_d, nt_d, r64, q_pos=dpq, t_pos=dpt, min_dv=min_dv, max_du=max_du,
+                                           max_distance=max_distance)[0]
+        else:
+            keys = ctx.match_hamming_gated(dq, dt, dpq, dpt, nq_d, nt_d, min_dv, max_du, max_distance)
         if self.cross_check:    # the role-swapped search under the same gate (all its problems reversed), then the filter
             rev = ctx.match_hamming_gated(dt, dq, dpt, dpq, nt_d, nq_d, min_dv, max_du, max_distance, n_forward=0)
             ctx.cross_check_matches(keys, rev, nq_d, nt_d, keys_out=keys)
@@ -356,7 +387,10 @@ class FeatureMatcher(object):
         """-> (query_idx, train_idx, distance) numpy arrays in the order of match()."""
         import torch
         self._check_cross_check()
+        r64 = self._check_ratio()
         if self._is_float(query_descriptors) or self._is_float(train_descriptors):
+            if r64:
+                raise ValueError("ratio is built for binary (Hamming) descriptors only, not float descriptors")
             if self.cross_check:
                 raise ValueError("cross_check is built for binary (Hamming) descriptors only, not float descriptors")
             return self._l2_arrays(query_descriptors, train_descriptors)
@@ -374,7 +408,8 @@ class FeatureMatcher(object):
         nq_t = torch.tensor([nq], dtype=torch.int32, device=dev)
         nt_t = torch.tensor([nt], dtype=torch.int32, device=dev)
         k = 2 if self.k_best == 2 else 1
-        keys = ctx.match_hamming(dq, dt, nq_t, nt_t, k=k)  # [1, nq, k]
+        # [1, nq, k]; with a ratio (k == 1) the rule is applied by the search itself
+        keys = ctx.match_hamming_ratio(dq, dt, nq_t, nt_t, r64)[0] if r64 else ctx.match_hamming(dq, dt, nq_t, nt_t, k=k)
         ratio_rule = k == 2 and str(self.feature_detection_method).upper() == "SIFT"
         if k == 1 or ratio_rule:
             # sorted(matches, key=distance) of one match per query (:442-444); for the ratio rule the filter
@@ -386,7 +421,7 @@ class FeatureMatcher(object):
             order = ctx.sort_matches(best, nq_t)
             kh = keys[0, :nq].cpu().numpy().astype(np.int64)
             oh = order[0, :nq].cpu().numpy().astype(np.int64)
-            if self.cross_check:  # (the rejected queries sorted last)
+            if self.cross_check or r64:  # (the rejected queries sorted last)
                 oh = oh[kh[oh, 0] != KEY_NONE]
             q = oh
             t = kh[oh, 0] & KEY_IDX_MASK

@@ -161,6 +161,17 @@ def match_features_frame_to_frame(cam_model, train_kpts, train_desc, query_kpts,
         (matched_query_indices, matched_kpts_query, matched_desc_query), random_colors
 
 
+def _device_angles_and_bearings(ctx, pano, m_pano):
+    """Pixels [n, >= 2] of a panorama -> (azimuth [n], elevation [n], unit bearing [n, 3]) as Context.pano_to_bearing gives them."""
+    import torch
+    if len(m_pano) == 0:   # (a frame without stereo matches)
+        return np.zeros(0), np.zeros(0), np.zeros((0, 3))
+    uv = np.ascontiguousarray(np.asarray(m_pano, dtype=np.float64).reshape(len(m_pano), -1)[:, :2])
+    az, el, b = ctx.pano_to_bearing(torch.from_numpy(uv).to(ctx.device), pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
+    ctx.synchronize()
+    return az.cpu().numpy(), el.cpu().numpy(), b.cpu().numpy()
+
+
 class StereoPanoramicFrame(object):
     """pose_est_tools.py:271-402: one omnistereo frame = detected + stereo-matched + triangulated + range-filtered
     correspondences of the rig's current omni image."""
@@ -199,10 +210,13 @@ class StereoPanoramicFrame(object):
         (m_top0, k_top0, d_top0), (m_bot0, k_bot0, d_bot0), colors0 = omnistereo_model.match_features_panoramic_top_bottom(
             keypts_list_top=kl_top, desc_list_top=dl_top, keypts_list_bot=kl_bot, desc_list_bot=dl_bot,
             min_rectified_disparity=self.min_disp, max_horizontal_diff=self.max_u_dist, show_matches=False)
-        az1, el1 = top.panorama.get_direction_angles_from_pixel_pano(m_top0, use_LUTs=False)
-        az2, el2 = bot.panorama.get_direction_angles_from_pixel_pano(m_bot0, use_LUTs=False)
-        b1 = top.get_3D_point_from_angles_wrt_focus(azimuth=az1, elevation=el1)[0, ..., :3]
-        b2 = bot.get_3D_point_from_angles_wrt_focus(azimuth=az2, elevation=el2)[0, ..., :3]
+        # direction angles and bearings (pose_est_tools.py:344-352) from the stage the engines' stereo assembly computes them
+        # with, sosvo_pano_to_bearing: panorama.get_direction_angles_from_pixel_pano / get_3D_point_from_angles_wrt_focus give
+        # the same values in numpy's arithmetic, which differs from the device's in the last bit of about 1 elevation in 70 and
+        # 1 bearing entry in 24 -- enough to move the refined pose in its 15th digit, so that this per-frame path and the
+        # sequence engines wrote pose files that differed in their last digits
+        az1, el1, b1 = _device_angles_and_bearings(omnistereo_model._context(), top.panorama, m_top0)
+        az2, el2, b2 = _device_angles_and_bearings(omnistereo_model._context(), bot.panorama, m_bot0)
         if self.use_opengv_triangulation:
             T = omnistereo_model.T_bot_wrt_top
             xyz_top = pyopengv.triangulation_triangulate2(b1, b2, T[:3, 3], T[:3, :3])
@@ -254,6 +268,9 @@ class TrackerSE3(object):
         self.gated_static_stereo = False
         self.gated_for_motion = False
         self.gated_max_distance = None
+        # Lowe's ratio rule on the device (FeatureMatcher's ratio): off; see set_ratio_test
+        self.ratio_static_stereo = None
+        self.ratio_for_motion = None
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -293,13 +310,13 @@ class TrackerStereoSE3(TrackerSE3):
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_static_stereo,
             use_radius_match=False, cross_check=self.cross_check_static_stereo, gated=self.gated_static_stereo,
-            gated_max_distance=self.gated_max_distance)
+            gated_max_distance=self.gated_max_distance, ratio=self.ratio_static_stereo)
         self.max_horizontal_diff_f2f_matches = 0.125 * self.max_horizontal_search_ratio * om.top_model.panorama.cols
         om.feature_matcher_for_motion = FeatureMatcher(
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
             use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion,
-            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance)
+            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance, ratio=self.ratio_for_motion)
         self.omni_mask_extra_padding = 10
         shape = None if om.current_omni_img is None else om.current_omni_img.shape[:2]
         if shape is None:
@@ -511,6 +528,46 @@ def set_gated_matching(tracker, gated_matching, gated_max_distance=None):
                 fm._check_gated(cap)              # (k_best > 1, radius match, float descriptors: ValueError)
 
 
+def set_ratio_test(tracker, ratio_test, ratio=None):
+    """Switch Lowe's ratio rule (FeatureMatcher's ratio: evaluated on the device, fused into the search) of the tracker's
+    matchers: ratio_test as parse_cross_check takes its argument (None: leave the tracker's own setting, and ratio is
+    ignored); ratio: a float in (0, 1) with ratio * 64 an integer (0.75: the reference's, camera_models.py:423), required
+    when a matcher is switched on.  The matchers bootstrap_tracker built carry the setting, so the per-frame mirror path and
+    the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame matcher only: True /
+    False / "f2f" set it, "stereo" is a ValueError."""
+    from .._lib import ratio_flags
+    if ratio_test is None:
+        return
+    try:
+        stereo, f2f = parse_cross_check(ratio_test)
+    except ValueError:
+        raise ValueError("ratio_test: None, True, False, \"stereo\", \"f2f\" or \"both\"; got %r" % (ratio_test,))
+    ratio_flags(stereo, f2f, ratio)      # (ValueError for a ratio that is no 64th, or a switch without a ratio)
+    cm = tracker.camera_model
+    if _is_rgbd_model(cm):
+        if isinstance(ratio_test, str) and stereo:
+            raise ValueError("ratio_test=%r: an RGB-D tracker has no static-stereo matcher" % (ratio_test,))
+        stereo = False
+    value = None if ratio is None else float(ratio)
+    matchers = [(fm, on) for fm, on in ((getattr(cm, "feature_matcher_for_static_stereo", None), stereo),
+                                        (getattr(cm, "feature_matcher_for_motion", None), f2f)) if fm is not None]
+    before = [fm.ratio for fm, _ in matchers]
+    try:                                          # every matcher is checked before anything is kept: a refused setting changes nothing
+        for fm, on in matchers:
+            fm.ratio = value if on else None
+            fm._check_ratio()                     # (k_best > 1, radius match, float descriptors: ValueError)
+    except ValueError:
+        for (fm, _), old in zip(matchers, before):
+            fm.ratio = old
+        raise
+    tracker.ratio_static_stereo, tracker.ratio_for_motion = (value if stereo else None), (value if f2f else None)
+
+
+def _ratio_of(fm):
+    """The ratio of a matcher (None: off), as the engine-cache keys carry it."""
+    return getattr(fm, "ratio", None) if fm is not None else None
+
+
 def _gated_of(fm):
     """(switch, cap) of a matcher, as the engine-cache keys carry them."""
     on = bool(getattr(fm, "gated", False)) if fm is not None else False
@@ -551,15 +608,20 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     if g_stereo and g_f2f and cap_stereo != cap_f2f:
         return None
     g_cap = cap_stereo if g_stereo else cap_f2f
+    # ... and their ratio rule.  The engine has one ratio for both matchers (as set_ratio_test sets them)
+    r_stereo, r_f2f = _ratio_of(fm), _ratio_of(getattr(om, "feature_matcher_for_motion", None))
+    if r_stereo is not None and r_f2f is not None and r_stereo != r_f2f:
+        return None
+    r_value = r_stereo if r_stereo is not None else r_f2f
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           cc_stereo, cc_f2f, g_stereo, g_f2f, g_cap)
+           cc_stereo, cc_f2f, g_stereo, g_f2f, g_cap, r_stereo, r_f2f)
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
                   cross_check_stereo=cc_stereo, cross_check_f2f=cc_f2f, gated_stereo=g_stereo, gated_f2f=g_f2f,
-                  gated_max_distance=g_cap)
+                  gated_max_distance=g_cap, ratio_stereo=r_stereo is not None, ratio_f2f=r_f2f is not None, ratio=r_value)
     return (model, rig), kwargs, key
 
 
@@ -699,12 +761,12 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
-           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm)) + _gated_of(fm)
+           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm)) + _gated_of(fm) + (_ratio_of(fm),)
     kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
                   detection_method=method, cross_check=_cross_check_of(fm), gated_f2f=_gated_of(fm)[0],
-                  gated_max_distance=_gated_of(fm)[1])
+                  gated_max_distance=_gated_of(fm)[1], ratio_f2f=_ratio_of(fm) is not None, ratio=_ratio_of(fm))
     return (cam,), kwargs, key
 
 
@@ -771,7 +833,7 @@ class TrackerRGBDSE3(TrackerSE3):
             method=self.detection_method, matcher_type=self.matching_type, k_best=self.k_best_matches,
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
             use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion,
-            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance)
+            gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance, ratio=self.ratio_for_motion)
         self.max_horizontal_diff_f2f_matches = self.max_horizontal_search_ratio * (self.camera_model.center_x * 2.)
 
     def track_frame(self, reference_frame, current_frame):
@@ -981,7 +1043,7 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
-           cross_check=None, gated_matching=None, gated_max_distance=None):
+           cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -1004,7 +1066,11 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
     gated_matching: the matchers search among the candidates that pass their pixel gates (the static-stereo gates / the
     frame-to-frame |du| gate) instead of everywhere; same values as cross_check.  gated_max_distance: None = no cap, or
-    1 .. 256: a match whose Hamming distance exceeds it is no match (see set_gated_matching).  Off by default."""
+    1 .. 256: a match whose Hamming distance exceeds it is no match (see set_gated_matching).  Off by default.
+
+    ratio_test: Lowe's ratio rule in the matchers, evaluated on the device: a match is kept iff its distance is below
+    ratio times the runner-up's (under gated_matching: the runner-up among the admissible candidates); same values as
+    cross_check.  ratio: a float in (0, 1) with ratio * 64 an integer, e.g. 0.75 (see set_ratio_test).  Off by default."""
     from .common_cv import get_depthmap_float32_from_png, get_images, imread
     from .common_tools import get_poses_from_file
     if visualizer_3D_VO is not None:
@@ -1094,6 +1160,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         set_detection_method(tracker, detection_method)   # (before the engine is chosen: it runs the tracker's detector)
         set_cross_check(tracker, cross_check)             # (likewise: it runs the matchers' crossCheck)
         set_gated_matching(tracker, gated_matching, gated_max_distance)   # (... and their search under the gates)
+        set_ratio_test(tracker, ratio_test, ratio)                        # (... and their ratio rule)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1279,7 +1346,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
                 results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
-                gated_matching=None, gated_max_distance=None):
+                gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1301,12 +1368,12 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   results_path=results_path, thread_name=thread_name, _live_frames=frames,
                   _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                  gated_max_distance=gated_max_distance)
+                  gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
 
 
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
-                   gated_matching=None, gated_max_distance=None):
+                   gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1325,7 +1392,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, cam_working_thread=cam_working_thread,
                   est_poses_filename=est_poses_filename, results_path=scene_path_vo_results, thread_name=thread_name,
                   frame_window=frame_window, detection_method=detection_method, cross_check=cross_check,
-                  gated_matching=gated_matching, gated_max_distance=gated_max_distance)
+                  gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
     result, failure = {}, []
     try:
         if use_multithreads_for_VO:
@@ -1351,7 +1418,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
 def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filename_template, depth_filename_template,
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
               last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
-              gated_matching=None, gated_max_distance=None):
+              gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1376,7 +1443,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
                   depth_filename_template=depth_filename_template, img_indices=vo_frame_indices,
                   results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window,
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                  gated_max_distance=gated_max_distance)
+                  gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
     result = {}
     if use_multithreads_for_VO:
         # one libsosvo context per host thread: the worker creates its own
@@ -1409,7 +1476,8 @@ def _lane_limit(n_sequences, lanes, window):
 
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
-                _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None):
+                _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None,
+                ratio=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1502,7 +1570,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
             i, q = job
             try:
                 out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method, cross_check=cross_check,
-                             gated_matching=gated_matching, gated_max_distance=gated_max_distance,
+                             gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test,
+                             ratio=ratio,
                              _keyframe_thresholds=_keyframe_thresholds, _engine_for=engine_for_lane(s), **q)
                 if "sequence_mode" in out:
                     out["sequence_mode"].update(lane=s, lanes=S)
@@ -1535,7 +1604,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
                    frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
-                   gated_max_distance=None):
+                   gated_max_distance=None, ratio_test=None, ratio=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1556,6 +1625,6 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
                               results_path=sc["scene_path_vo_results"], thread_name=sc.get("thread_name", "")))
     results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window,
                           detection_method=detection_method, lanes=lanes, shard=shard, cross_check=cross_check,
-                          gated_matching=gated_matching, gated_max_distance=gated_max_distance)
+                          gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
     print("Done with VO for %d sequences!" % len(results))
     return results

@@ -33,7 +33,8 @@ class RigConfig(object):
 class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
                  adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
-                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
@@ -42,10 +43,15 @@ class FramePairPipeline(object):
         the static-stereo matcher / the frame-to-frame matcher.
         gated_stereo / gated_f2f: the matcher searches among the candidates that pass the stage's own pixel gate
         (Context.match_hamming_gated); gated_max_distance: None = no cap, or 1 .. 256: a match whose Hamming distance
-        exceeds it is no match."""
+        exceeds it is no match.
+        ratio_stereo / ratio_f2f: Lowe's ratio rule fused into that matcher's search (Context.match_hamming_ratio), plain or
+        under the gate; ratio: a float in (0, 1) with ratio * 64 an integer (0.75 = the reference's, camera_models.py:423)."""
         assert isinstance(ctx, Context)
         from . import _lib
         _lib.gated_flags(gated_stereo, gated_f2f, gated_max_distance)   # (ValueError for a cap out of range)
+        _lib.ratio_flags(ratio_stereo, ratio_f2f, ratio)                 # (ValueError for a ratio that is no 64th)
+        self.ratio_stereo = _lib.ratio_64ths(ratio) if ratio_stereo else 0   # (in 64ths; 0: off)
+        self.ratio_f2f = _lib.ratio_64ths(ratio) if ratio_f2f else 0
         self.gated_stereo, self.gated_f2f, self.gated_max_distance = bool(gated_stereo), bool(gated_f2f), gated_max_distance
         self.cross_check_stereo, self.cross_check_f2f = bool(cross_check_stereo), bool(cross_check_f2f)
         self.ctx, self.rig_cfg, self.rig = ctx, rig, rig.as_struct()
@@ -74,6 +80,7 @@ class FramePairPipeline(object):
             self.n_top, self.n_bot = z((P,), torch.int32), z((P,), torch.int32)
         self.s_keys, self.s_order = z((P, bucket_cap, 1), torch.uint32), z((P, bucket_cap), torch.int32)
         self.s_keys_rev = z((P, bucket_cap, 1), torch.uint32) if self.cross_check_stereo else None
+        self.s_rivals = z((P, bucket_cap, 1), torch.uint32) if self.ratio_stereo else None
         Fc, Cc = self.frame_cap, self.corr_cap
         # descriptors and counts of both views back to back (view-major): the two frame-to-frame matchings of a step
         # (top with top, bottom with bottom) are ONE launch of 2B problems, and so are the two sorts
@@ -96,6 +103,7 @@ class FramePairPipeline(object):
             self._k2 = self._k4[: 2 * self.B]
         else:
             self._k2 = z((2 * self.B, Fc, 1), torch.uint32)
+        self._rivals = torch.zeros_like(self._k4 if self.cross_check_f2f else self._k2) if self.ratio_f2f else None
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
         self.o_top, self.o_bot = self._o2[: self.B], self._o2[self.B:]
         self.corr = dict(f=z((self.B, Cc, 3), torch.float64), p=z((self.B, Cc, 3), torch.float64),
@@ -119,17 +127,23 @@ class FramePairPipeline(object):
     # ---- one step ----------------------------------------------------------------------------
     def stereo(self):
         c = self.ctx
-        if self.gated_stereo:   # query = bottom, train = top: the gate of stereo_assemble; the role-swapped search is reversed
-            g = dict(min_dv=self.rig_cfg.stereo_min_disp, max_du=self.rig_cfg.stereo_max_hdiff, max_distance=self.gated_max_distance)
+        # query = bottom, train = top: the gate of stereo_assemble
+        g = dict(min_dv=self.rig_cfg.stereo_min_disp, max_du=self.rig_cfg.stereo_max_hdiff,
+                 max_distance=self.gated_max_distance) if self.gated_stereo else None
+        if self.ratio_stereo:
+            pos = dict(q_pos=self.kp_bot, t_pos=self.kp_top, **g) if g else {}
+            c.match_hamming_ratio(self.desc_bot, self.desc_top, self.n_bot, self.n_top, self.ratio_stereo, keys=self.s_keys,
+                                  rivals=self.s_rivals, **pos)
+        elif g:
             c.match_hamming_gated(self.desc_bot, self.desc_top, self.kp_bot, self.kp_top, self.n_bot, self.n_top, keys=self.s_keys, **g)
-            if self.cross_check_stereo:
-                c.match_hamming_gated(self.desc_top, self.desc_bot, self.kp_top, self.kp_bot, self.n_top, self.n_bot,
-                                      keys=self.s_keys_rev, n_forward=0, **g)
         else:
             c.match_hamming(self.desc_bot, self.desc_top, self.n_bot, self.n_top, k=1, keys=self.s_keys)
-            if self.cross_check_stereo:
+        if self.cross_check_stereo:   # the role-swapped search: under the reversed gate, and never with the ratio rule
+            if g:
+                c.match_hamming_gated(self.desc_top, self.desc_bot, self.kp_top, self.kp_bot, self.n_top, self.n_bot,
+                                      keys=self.s_keys_rev, n_forward=0, **g)
+            else:
                 c.match_hamming(self.desc_top, self.desc_bot, self.n_top, self.n_bot, k=1, keys=self.s_keys_rev)
-        if self.cross_check_stereo:
             c.cross_check_matches(self.s_keys, self.s_keys_rev, self.n_bot, self.n_top, keys_out=self.s_keys)
         c.sort_matches(self.s_keys, self.n_bot, order=self.s_order)
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
@@ -140,7 +154,13 @@ class FramePairPipeline(object):
         self._M2[1].copy_(self._M2[0])                      # the bottom view's blocks have the same counts
         d2, M2 = self._d2.view(2 * self.F, self.frame_cap, 32), self._M2.view(2 * self.F)
         keys, q_slot, t_slot = (self._k4, self._q4, self._t4) if self.cross_check_f2f else (self._k2, self._q2, self._t2)
-        if self.gated_f2f:      # the |du| gate of f2f_assemble; the role-swapped problems are the second half
+        if self.ratio_f2f:      # plain or under the |du| gate; the role-swapped second half gets no rule
+            m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
+            g = dict(q_pos=m2, t_pos=m2, min_dv=-1.0, max_du=self.rig_cfg.f2f_max_hdiff,
+                     max_distance=self.gated_max_distance) if self.gated_f2f else {}
+            c.match_hamming_ratio(d2, d2, M2, M2, self.ratio_f2f, keys=keys, rivals=self._rivals, q_slot=q_slot, t_slot=t_slot,
+                                  n_forward=2 * self.B, **g)
+        elif self.gated_f2f:    # the |du| gate of f2f_assemble; the role-swapped problems are the second half
             m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
             c.match_hamming_gated(d2, d2, m2, m2, M2, M2, min_dv=-1.0, max_du=self.rig_cfg.f2f_max_hdiff,
                                   max_distance=self.gated_max_distance, keys=keys, q_slot=q_slot, t_slot=t_slot,
@@ -198,7 +218,8 @@ class OverlappedFramePairs(object):
     def __init__(self, device, gums, omni_shape, rig, n_pairs, n_streams=2, num_of_features=1000, kp_cap=512,
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
-                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray."""
         from .frontend import DeviceImageModel, ImageFrontEnd
@@ -228,7 +249,8 @@ class OverlappedFramePairs(object):
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
                                            ransac_solver=ransac_solver, cross_check_stereo=cross_check_stereo,
                                            cross_check_f2f=cross_check_f2f, gated_stereo=gated_stereo, gated_f2f=gated_f2f,
-                                           gated_max_distance=gated_max_distance)
+                                           gated_max_distance=gated_max_distance, ratio_stereo=ratio_stereo,
+                                           ratio_f2f=ratio_f2f, ratio=ratio)
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -358,7 +380,7 @@ class OverlappedFramePairs(object):
 
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
               adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
-              gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+              gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
     any ransac_solver but "GP3P" is P3P."""
@@ -379,6 +401,7 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
     c.ransac_flags |= _lib.cross_check_flags(cross_check_stereo, cross_check_f2f)
     c.ransac_flags |= _lib.gated_flags(gated_stereo, gated_f2f, gated_max_distance)
+    c.ransac_flags |= _lib.ratio_flags(ratio_stereo, ratio_f2f, ratio)
     return c
 
 
@@ -389,7 +412,8 @@ class FramePairBatch(object):
     def __init__(self, ctx, model, rig, n_pairs, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap)."""
@@ -397,7 +421,7 @@ class FramePairBatch(object):
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         self.cfg = c = batch_cfg(model, self.B, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
                                  thr, max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo,
-                                 cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance)
+                                 cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -526,13 +550,14 @@ class _OmniFamily(_SequenceFamily):
 
     def __init__(self, ctx, model, rig, frames, slots, gather, num_of_features, kp_cap, frame_cap, median_win_size, quality,
                  min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method, cross_check_stereo=False,
-                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
         self.cfg = batch_cfg(model, frames, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
                              thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method, cross_check_stereo,
-                             cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance)
+                             cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
         self.method = str(detection_method).upper()
         if str(ransac_solver).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -555,14 +580,14 @@ class _RGBDFamily(_SequenceFamily):
 
     def __init__(self, ctx, cam, _rig, frames, slots, gather, image_shape, num_of_features, kp_cap, frame_cap, median_win_size,
                  quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask, pose_est_algorithm, detection_method,
-                 cross_check=False, gated_f2f=False, gated_max_distance=None):
+                 cross_check=False, gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None):
         from . import orb_pattern
         assert isinstance(ctx, Context)
         self.cam_cfg, self.cam = cam, cam.as_struct()
         self.heads = (self.cam,)
         self.cfg = c = rgbd_batch_cfg(cam, frames, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
                                       min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method,
-                                      cross_check, gated_f2f, gated_max_distance)
+                                      cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
@@ -828,7 +853,8 @@ class SequenceEngine(_SequenceBase):
     def __init__(self, ctx, model, rig, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
@@ -837,7 +863,8 @@ class SequenceEngine(_SequenceBase):
         self._init_windows(window)
         self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, num_of_features, kp_cap, frame_cap, median_win_size,
                                 quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method,
-                                cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance))
+                                cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
+                                ratio_stereo, ratio_f2f, ratio))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -960,7 +987,7 @@ class RGBDPairPipeline(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None):
         """detection_method: "GFT", "ORB", "FAST" or "AGAST" (RGBDFrontEnd).
         cross_check: mutual matches only (cv2.BFMatcher's crossCheck, camera_models.py:401) in feature_matcher_for_motion.
         gated_f2f: the matcher searches among the keypoints within the tracker's |du| gate (Context.match_hamming_gated);
@@ -986,11 +1013,14 @@ class RGBDPairPipeline(object):
         self.keys, self.order = z((B, Fc, 1), torch.uint32), z((B, Fc), torch.int32)
         _lib.gated_flags(False, gated_f2f, gated_max_distance)   # (ValueError for a cap out of range)
         self.gated_f2f, self.gated_max_distance = bool(gated_f2f), gated_max_distance
+        _lib.ratio_flags(False, ratio_f2f, ratio)                 # (ValueError for a ratio that is no 64th)
+        self.ratio_f2f = _lib.ratio_64ths(ratio) if ratio_f2f else 0   # (in 64ths; 0: off)
         self.cross_check = bool(cross_check)
         if self.cross_check:   # the B role-swapped problems ride in the same launch, after the forward ones
             self._q2, self._t2 = torch.cat([self.cur_frame, self.ref_frame]), torch.cat([self.ref_frame, self.cur_frame])
             self._k2 = z((2 * B, Fc, 1), torch.uint32)
             self.keys = self._k2[:B]
+        self._rivals = z(((2 if self.cross_check else 1) * B, Fc, 1), torch.uint32) if self.ratio_f2f else None
         self.corr = dict(f=z((B, Fc, 3), torch.float64), p=z((B, Fc, 3), torch.float64), q=z((B, Fc), torch.int32),
                          t=z((B, Fc), torch.int32), n=z((B,), torch.int32))
         self.ransac = dict(T=z((B, 3, 4), torch.float64), mask=z((B, Fc), torch.uint8), idx=z((B, Fc), torch.int32),
@@ -1007,7 +1037,12 @@ class RGBDPairPipeline(object):
     def track(self):
         c, fr, cfg = self.ctx, self.frames, self.cam_cfg
         keys, q_slot, t_slot = (self._k2, self._q2, self._t2) if self.cross_check else (self.keys, self.cur_frame, self.ref_frame)
-        if self.gated_f2f:      # the |du| gate of f2f_assemble_central; the role-swapped problems are the second half
+        if self.ratio_f2f:      # plain or under the |du| gate; the role-swapped second half gets no rule
+            g = dict(q_pos=fr["m"], t_pos=fr["m"], min_dv=-1.0, max_du=cfg.f2f_max_hdiff,
+                     max_distance=self.gated_max_distance) if self.gated_f2f else {}
+            c.match_hamming_ratio(fr["d"], fr["d"], fr["M"], fr["M"], self.ratio_f2f, keys=keys, rivals=self._rivals, q_slot=q_slot,
+                                  t_slot=t_slot, n_forward=self.B, **g)
+        elif self.gated_f2f:    # the |du| gate of f2f_assemble_central; the role-swapped problems are the second half
             c.match_hamming_gated(fr["d"], fr["d"], fr["m"], fr["m"], fr["M"], fr["M"], min_dv=-1.0, max_du=cfg.f2f_max_hdiff,
                                   max_distance=self.gated_max_distance, keys=keys, q_slot=q_slot, t_slot=t_slot, n_forward=self.B)
         else:
@@ -1045,7 +1080,7 @@ class RGBDPairPipeline(object):
 
 def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
                    thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check=False, gated_f2f=False,
-                   gated_max_distance=None):
+                   gated_max_distance=None, ratio_f2f=False, ratio=None):
     """The `sosvo_rgbd_batch_cfg` of RGBDPairBatch and RGBDSequenceEngine (n_pairs: pairs per call / slot pairs per tracking
     call; cam: an RGBDCamConfig).  kp_cap None or 0 = rgbd_kp_cap; frame_cap None or 0 = kp_cap; thr None = the trackers'
     5-degree threshold."""
@@ -1060,6 +1095,7 @@ def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap
     c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
     c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags | _lib.cross_check_flags(f2f=cross_check)
     c.flags |= _lib.gated_flags(False, gated_f2f, gated_max_distance)
+    c.flags |= _lib.ratio_flags(False, ratio_f2f, ratio)
     c.quality, c.min_distance = float(quality), float(min_distance)
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
@@ -1074,13 +1110,13 @@ class RGBDPairBatch(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None):
         from . import orb_pattern
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         c = rgbd_batch_cfg(cam, self.B, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
                            edge, thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check, gated_f2f,
-                           gated_max_distance)
+                           gated_max_distance, ratio_f2f, ratio)
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         self.cfg, self.thr = c, c.ransac_threshold
@@ -1119,11 +1155,11 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None):
         self._init_windows(window)
         self._adopt(_RGBDFamily(ctx, cam, None, self.W, self.slots, False, image_shape, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance))
+                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio))
 
 
 # ---- several sequences ("lanes") through one engine ----------------------------------------------------------------------
@@ -1450,11 +1486,13 @@ class MultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, model, rig, lanes=2, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
+                 ratio_f2f=False, ratio=None):
         self._init_lanes(lanes, window)
         self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver,
-                                detection_method, cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance))
+                                detection_method, cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
+                                ratio_stereo, ratio_f2f, ratio))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
@@ -1464,8 +1502,8 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None):
         self._init_lanes(lanes, window)
         self._adopt(_RGBDFamily(ctx, cam, None, self.window, self.slots, True, image_shape, num_of_features, kp_cap, frame_cap,
                                 median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance))
+                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio))
