@@ -258,9 +258,18 @@ def test_set_cross_check_switches_the_matchers():
         pet.set_cross_check(t, value)
         assert (rig.feature_matcher_for_static_stereo.cross_check, rig.feature_matcher_for_motion.cross_check) == want, value
         assert (t.cross_check_static_stereo, t.cross_check_for_motion) == want
-    rig.feature_matcher_for_motion.use_radius_match = True
-    with pytest.raises(ValueError, match="radius"):
+    pet.set_cross_check(t, "stereo")
+    rig.feature_matcher_for_motion.use_radius_match = True   # the second matcher refuses: the first one and the tracker stay as they were
+    for value in ("f2f", True):
+        with pytest.raises(ValueError, match="radius"):
+            pet.set_cross_check(t, value)
+        assert (rig.feature_matcher_for_static_stereo.cross_check, rig.feature_matcher_for_motion.cross_check) == (True, False)
+        assert (t.cross_check_static_stereo, t.cross_check_for_motion) == (True, False)
+    rig.feature_matcher_for_motion.use_radius_match, rig.feature_matcher_for_motion.k_best = False, 2
+    with pytest.raises(ValueError, match="k_best"):
         pet.set_cross_check(t, "f2f")
+    assert (rig.feature_matcher_for_static_stereo.cross_check, rig.feature_matcher_for_motion.cross_check) == (True, False)
+    assert (t.cross_check_static_stereo, t.cross_check_for_motion) == (True, False)
     r = _tracker(rgbd=True)
     r.camera_model = cam = _rgbd_cam()
     pet.set_cross_check(r, True)                             # both matchers = the one an RGB-D tracker has

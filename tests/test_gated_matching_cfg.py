@@ -199,12 +199,22 @@ def test_set_gated_matching_switches_the_matchers():
     for bad in (0, 257, 12.5):
         with pytest.raises(ValueError, match="gated_max_distance"):
             pet.set_gated_matching(t, True, bad)
-    fmm.use_radius_match = True
-    with pytest.raises(ValueError, match="radius"):
-        pet.set_gated_matching(t, "f2f")
+    pet.set_gated_matching(t, "stereo", 64)
+
+    def state():
+        return (fms.gated, fmm.gated, fms.gated_max_distance, fmm.gated_max_distance, t.gated_static_stereo, t.gated_for_motion,
+                t.gated_max_distance)
+    before = state()
+    assert before == (True, False, 64, 64, True, False, 64)
+    fmm.use_radius_match = True                              # the second matcher refuses: the first one and the tracker stay as they were
+    for value, cap in (("f2f", None), (True, 80)):
+        with pytest.raises(ValueError, match="radius"):
+            pet.set_gated_matching(t, value, cap)
+        assert state() == before
     fmm.use_radius_match, fmm.k_best = False, 2
     with pytest.raises(ValueError, match="k_best"):
         pet.set_gated_matching(t, "f2f")
+    assert state() == before
     r = _tracker(rgbd=True)
     r.camera_model = cam = _rgbd_cam()
     pet.set_gated_matching(r, True, 100)                     # both matchers = the one an RGB-D tracker has

@@ -10,7 +10,11 @@ RATIO: the smallest of 48, 54 and 58 (in 64ths) for which, in the ratio-only set
 starved pairs shows nothing).  Chosen: 54.  Observed on one MI355X build (correspondences of the two pair tracks and the three
 sequence hops, the hop between the two unrelated pairs being the smallest): at r = 48 the minima are 145 (stereo), 7 (f2f), 5
 (both) and 16 (RGB-D f2f), so 48 starves; at r = 54 they are 156 (stereo), 37 (f2f), 28 (both) and 67 (RGB-D f2f), every status
-0; at r = 58: 174, 68, 57 and 163."""
+0; at r = 58: 174, 68, 57 and 163.
+
+The stage-by-stage pipelines also run the two combinations of {ratio, gate, cross-check} the settings above leave out, at
+r = 54 too (neither starves; observed minima, stereo points per frame / correspondences per pair): both + gated at no cap,
+no cross-check 930 / 1088; gated + cross-check without the rule 805 / 984, RGB-D 233 correspondences (its smallest hop)."""
 import contextlib
 import os
 
@@ -146,7 +150,10 @@ SETTINGS = [Setting("stereo", True, False), Setting("f2f", False, True), Setting
             Setting("both_with_cross_check", True, True, cc=True),
             Setting("both_gated_cap80_with_cross_check", True, True, gated=True, cap=80, cc=True)]
 OFF = Setting("off", False, False)
-BY_NAME = {s.name: s for s in SETTINGS}
+# the combinations of {ratio, gate, cross-check} the settings above leave out: for the stage-by-stage pipelines only
+GATED_NO_CC = Setting("both_gated", True, True, gated=True)
+GATED_CC_NO_RATIO = Setting("gated_with_cross_check", False, False, gated=True, cc=True)
+BY_NAME = {s.name: s for s in SETTINGS + [GATED_NO_CC, GATED_CC_NO_RATIO]}
 NAMES = [s.name for s in SETTINGS]
 
 
@@ -214,7 +221,7 @@ def test_the_patched_refflow_without_a_switch_is_refflow(pairs):
 
 
 # ---- the omni paths --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", NAMES + [GATED_NO_CC.name, GATED_CC_NO_RATIO.name])
 def test_pair_pipeline_stage_by_stage_equals_the_patched_refflow(ctx, pairs, name):
     s, setting = pairs, BY_NAME[name]
     frames, want, _ = s.reference(setting)
@@ -224,6 +231,8 @@ def test_pair_pipeline_stage_by_stage_equals_the_patched_refflow(ctx, pairs, nam
     pipe.track()
     rec = pipe.results().cpu().numpy()
     M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
+    print("setting %s at r = %d: stereo points of the patched refflow %s, correspondences %s"
+          % (name, setting.r, [len(fr["X"]) for fr in frames], [len(w["corr"]["cam"]) for w in want]))
     assert [int(x) for x in M] == [len(fr["X"]) for fr in frames] and M.min() >= MIN_CORR
     assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
     for f, fr in enumerate(frames):
@@ -335,7 +344,7 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
 
 # ---- RGB-D -------------------------------------------------------------------------------------------------------------------
 RGBD_SETTINGS = [Setting("f2f", False, True), Setting("f2f_with_cross_check", False, True, cc=True),
-                 Setting("f2f_gated", False, True, gated=True)]
+                 Setting("f2f_gated", False, True, gated=True), GATED_CC_NO_RATIO]
 
 
 @pytest.mark.parametrize("setting", RGBD_SETTINGS, ids=[x.name for x in RGBD_SETTINGS])
@@ -348,6 +357,8 @@ def test_rgbd_pair_paths_and_sequence_equal_the_patched_refflow(ctx, rgbd, setti
         want = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
         want_seq_tracks = [track(t - 1, t, t - 1) for t in range(1, 2 * s.B)]
     want_seq = np.stack([_record(w) for w in want_seq_tracks])
+    print("rgbd setting %s at r = %d: correspondences of the patched refflow %s"
+          % (setting.name, setting.r, [len(w["corr"]["q"]) for w in want + want_seq_tracks]))
     if setting.ratio_only:
         _starvation_check("rgbd " + setting.name, want + want_seq_tracks)
     plain = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]

@@ -6,6 +6,7 @@ absent this module raises, it never routes anywhere else.
 import ctypes
 import os
 import re
+from collections import namedtuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsosvo.so")
@@ -240,6 +241,61 @@ def ratio_flags(stereo=False, f2f=False, ratio=None):
     if flags:
         flags |= r << RATIO_64THS_SHIFT
     return flags
+
+
+class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2f gated_stereo gated_f2f gated_max_distance "
+                                              "ratio_stereo ratio_f2f ratio")):
+    """The matchers' options as ONE value: what every public constructor builds from its own arguments and passes inward,
+    down to the flags of a batch configuration (flags()) or the arguments of Context.match_1nn.  Checked on construction by
+    the three flag functions above (their ValueErrors).  Immutable and hashable: it is its own engine-cache key.  A new
+    matcher option is a field here, an argument of Context.match_1nn and of match_1nn in pipeline.hip."""
+    __slots__ = ()
+
+    def __new__(cls, cross_check_stereo=False, cross_check_f2f=False, gated_stereo=False, gated_f2f=False,
+                gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None):
+        v = super().__new__(cls, bool(cross_check_stereo), bool(cross_check_f2f), bool(gated_stereo), bool(gated_f2f),
+                            gated_max_distance, bool(ratio_stereo), bool(ratio_f2f), ratio)
+        v.flags()
+        return v
+
+    def flags(self):
+        """The options' bits of sosvo_batch_cfg.ransac_flags / sosvo_rgbd_batch_cfg.flags."""
+        return (cross_check_flags(self.cross_check_stereo, self.cross_check_f2f)
+                | gated_flags(self.gated_stereo, self.gated_f2f, self.gated_max_distance)
+                | ratio_flags(self.ratio_stereo, self.ratio_f2f, self.ratio))
+
+    @property
+    def ratio_64ths_stereo(self):
+        """The static-stereo matcher's ratio in 64ths; 0: off."""
+        return ratio_64ths(self.ratio) if self.ratio_stereo else 0
+
+    @property
+    def ratio_64ths_f2f(self):
+        return ratio_64ths(self.ratio) if self.ratio_f2f else 0
+
+    @classmethod
+    def rgbd(cls, cross_check=False, gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None):
+        """From the RGB-D classes' names: a camera without static stereo has the frame-to-frame matcher only."""
+        return cls(cross_check_f2f=cross_check, gated_f2f=gated_f2f, gated_max_distance=gated_max_distance, ratio_f2f=ratio_f2f,
+                   ratio=ratio)
+
+    def rgbd_kwargs(self):
+        """The inverse of rgbd()."""
+        return dict(cross_check=self.cross_check_f2f, gated_f2f=self.gated_f2f, gated_max_distance=self.gated_max_distance,
+                    ratio_f2f=self.ratio_f2f, ratio=self.ratio)
+
+    @classmethod
+    def from_matchers(cls, fm_stereo, fm_f2f):
+        """What a batched engine runs for a pair of FeatureMatchers (None: no such matcher), or None when they have no batched
+        counterpart: an engine has one cap and one ratio for both matchers.  Cap and ratio of a matcher that is off are dropped."""
+        fms = (fm_stereo, fm_f2f)
+        cross, gated = ([bool(getattr(fm, name, False)) for fm in fms] for name in ("cross_check", "gated"))
+        caps = {getattr(fm, "gated_max_distance", None) for fm, on in zip(fms, gated) if on}
+        ratios = [getattr(fm, "ratio", None) for fm in fms]
+        if len(caps) > 1 or len({r for r in ratios if r is not None}) > 1:
+            return None
+        return cls(cross[0], cross[1], gated[0], gated[1], caps.pop() if caps else None, ratios[0] is not None,
+                   ratios[1] is not None, ratios[0] if ratios[0] is not None else ratios[1])
 
 
 def rgbd_flags_detector(flags):

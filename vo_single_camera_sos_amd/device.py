@@ -371,13 +371,16 @@ class Context(object):
         return kp4, resp, n, desc, kp_xy
 
     # ---- K7 ----------------------------------------------------------------------------
-    def match_hamming(self, q_desc, t_desc, nq, nt, k=1, keys=None, q_slot=None, t_slot=None):
-        """q_desc [Bq, Sq, 32] u8, t_desc [Bt, St, 32] u8, nq [Bq] / nt [Bt] i32 -> keys [P, Sq, k] u32.
-        Without slots P = Bq = Bt; with q_slot / t_slot [P] i32, problem p uses blocks q_slot[p] / t_slot[p]."""
+    def _hamming_args(self, q_desc, t_desc, nq, nt, q_slot, t_slot, keys, k=1, pos=None):
+        """The checks the Hamming searches share: descriptor blocks, pos = (q_pos, t_pos) of a gated search, counts, the slot
+        pair -> (P, Sq, St, keys [P, Sq, k] u32, allocated when None)."""
         _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
         _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
         Bq, Sq = q_desc.shape[0], q_desc.shape[1]
         Bt, St = t_desc.shape[0], t_desc.shape[1]
+        if pos is not None:
+            _check(pos[0], torch.float32, "q_pos", (Bq, Sq, 2))
+            _check(pos[1], torch.float32, "t_pos", (Bt, St, 2))
         _check(nq, torch.int32, "nq", (Bq,))
         _check(nt, torch.int32, "nt", (Bt,))
         if (q_slot is None) != (t_slot is None):
@@ -393,6 +396,12 @@ class Context(object):
         if keys is None:
             keys = torch.empty((P, Sq, k), dtype=torch.uint32, device=q_desc.device)
         _check(keys, torch.uint32, "keys", (P, Sq, k))
+        return P, Sq, St, keys
+
+    def match_hamming(self, q_desc, t_desc, nq, nt, k=1, keys=None, q_slot=None, t_slot=None):
+        """q_desc [Bq, Sq, 32] u8, t_desc [Bt, St, 32] u8, nq [Bq] / nt [Bt] i32 -> keys [P, Sq, k] u32.
+        Without slots P = Bq = Bt; with q_slot / t_slot [P] i32, problem p uses blocks q_slot[p] / t_slot[p]."""
+        P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, keys, k)
         self._call(self._lib.sosvo_match_hamming, _ptr(q_desc), _ptr(t_desc), _ptr(nq), _ptr(nt), _ptr(q_slot),
                    _ptr(t_slot), P, Sq, St, int(k), _ptr(keys))
         return keys
@@ -403,27 +412,7 @@ class Context(object):
         f32 are the (u, v) of the descriptor rows; gate = |u_t - u_q| <= max_du (if max_du > 0) and v_t - v_q >= min_dv (if
         min_dv >= 0), in double.  max_distance: None = no cap, else 0 .. 256.  Problems p >= n_forward (default: none) are
         reversed (v_q - v_t >= min_dv).  -> keys [P, Sq, 1] u32, KEY_NONE where no admissible train is within the cap."""
-        _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
-        _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
-        Bq, Sq = q_desc.shape[0], q_desc.shape[1]
-        Bt, St = t_desc.shape[0], t_desc.shape[1]
-        _check(q_pos, torch.float32, "q_pos", (Bq, Sq, 2))
-        _check(t_pos, torch.float32, "t_pos", (Bt, St, 2))
-        _check(nq, torch.int32, "nq", (Bq,))
-        _check(nt, torch.int32, "nt", (Bt,))
-        if (q_slot is None) != (t_slot is None):
-            raise SosvoError("q_slot and t_slot go together")
-        if q_slot is not None:
-            P = q_slot.shape[0]
-            _check(q_slot, torch.int32, "q_slot", (P,))
-            _check(t_slot, torch.int32, "t_slot", (P,))
-        else:
-            if Bq != Bt:
-                raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
-            P = Bq
-        if keys is None:
-            keys = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
-        _check(keys, torch.uint32, "keys", (P, Sq, 1))
+        P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, keys, 1, (q_pos, t_pos))
         self._call(self._lib.sosvo_match_hamming_gated, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq), _ptr(nt),
                    _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
                    float(max_du), 256 if max_distance is None else int(max_distance), _ptr(keys))
@@ -437,40 +426,57 @@ class Context(object):
         max_distance (no runner-up inside the gate: kept; the cap acts after the rule).  Problems p >= n_forward (default:
         none) are reversed and get no rule.  -> (keys [P, Sq, 1] u32, rivals [P, Sq, 1] u32): the filtered keys, KEY_NONE
         where dropped, and each query's runner-up key (unspecified in reversed rows)."""
-        _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
-        _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
-        Bq, Sq = q_desc.shape[0], q_desc.shape[1]
-        Bt, St = t_desc.shape[0], t_desc.shape[1]
         if (q_pos is None) != (t_pos is None):
             raise SosvoError("q_pos and t_pos go together")
-        if q_pos is not None:
-            _check(q_pos, torch.float32, "q_pos", (Bq, Sq, 2))
-            _check(t_pos, torch.float32, "t_pos", (Bt, St, 2))
-        elif max_distance is not None:
+        if q_pos is None and max_distance is not None:
             raise SosvoError("max_distance belongs to the gated form (q_pos / t_pos)")
-        _check(nq, torch.int32, "nq", (Bq,))
-        _check(nt, torch.int32, "nt", (Bt,))
-        if (q_slot is None) != (t_slot is None):
-            raise SosvoError("q_slot and t_slot go together")
-        if q_slot is not None:
-            P = q_slot.shape[0]
-            _check(q_slot, torch.int32, "q_slot", (P,))
-            _check(t_slot, torch.int32, "t_slot", (P,))
-        else:
-            if Bq != Bt:
-                raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
-            P = Bq
-        if keys is None:
-            keys = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
+        P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, keys, 1,
+                                             None if q_pos is None else (q_pos, t_pos))
         if rivals is None:
             rivals = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
-        _check(keys, torch.uint32, "keys", (P, Sq, 1))
         _check(rivals, torch.uint32, "rivals", (P, Sq, 1))
         self._call(self._lib.sosvo_match_hamming_ratio, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq), _ptr(nt),
                    _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
                    float(max_du), 256 if max_distance is None else int(max_distance), int(ratio_64ths), _ptr(keys),
                    _ptr(rivals))
         return keys, rivals
+
+    def match_1nn(self, q_desc, t_desc, nq, nt, *, ratio_64ths=0, rivals=None, gate=None, q_pos=None, t_pos=None, keys=None,
+                  q_slot=None, t_slot=None, n_forward=None):
+        """The Python twin of match_1nn in pipeline.hip: one best-match search, ONE library call.  ratio_64ths > 0: the ratio
+        form (match_hamming_ratio), plain or, with a gate, gated; else with a gate: match_hamming_gated; else
+        match_hamming(k=1), which has no reversed problems and so no n_forward.  gate: None or (min_dv, max_du, max_distance)
+        on q_pos / t_pos.  -> keys [P, Sq, 1] u32."""
+        where = dict(keys=keys, q_slot=q_slot, t_slot=t_slot)
+        if ratio_64ths:
+            g = dict(q_pos=q_pos, t_pos=t_pos, min_dv=gate[0], max_du=gate[1], max_distance=gate[2]) if gate is not None else {}
+            return self.match_hamming_ratio(q_desc, t_desc, nq, nt, ratio_64ths, rivals=rivals, n_forward=n_forward, **g, **where)[0]
+        if gate is not None:
+            return self.match_hamming_gated(q_desc, t_desc, q_pos, t_pos, nq, nt, *gate, n_forward=n_forward, **where)
+        return self.match_hamming(q_desc, t_desc, nq, nt, k=1, **where)
+
+    def match_1nn_slots(self, desc, pos, n, q_slot, t_slot, keys, n_forward, *, ratio_64ths=0, rivals=None, gate=None):
+        """The matching step, slot form: ONE search over the problems (q_slot[p], t_slot[p]) of one set of blocks (desc, pos, n).
+        Problems p >= n_forward are the role-swapped twins of the forward ones (reversed gate, no ratio rule); when there are
+        any, the forward keys are filtered to the mutual matches in place.  -> the forward keys, keys[:n_forward]."""
+        self.match_1nn(desc, desc, n, n, ratio_64ths=ratio_64ths, rivals=rivals, gate=gate, q_pos=pos, t_pos=pos, keys=keys,
+                       q_slot=q_slot, t_slot=t_slot, n_forward=n_forward)
+        fwd = keys[:n_forward]
+        if keys.shape[0] > n_forward:
+            self.cross_check_matches(fwd, keys[n_forward:], n, n, q_slot=q_slot[:n_forward], t_slot=t_slot[:n_forward], keys_out=fwd)
+        return fwd
+
+    def match_1nn_two_launch(self, q_desc, t_desc, nq, nt, *, cross_check=False, keys_rev=None, ratio_64ths=0, rivals=None,
+                             gate=None, q_pos=None, t_pos=None, keys=None):
+        """The matching step, two-launch form: the forward search; with cross_check a second search with roles and positions
+        swapped (every problem reversed: n_forward=0, never the ratio rule) into keys_rev, then the mutual filter on keys in
+        place.  -> keys."""
+        keys = self.match_1nn(q_desc, t_desc, nq, nt, ratio_64ths=ratio_64ths, rivals=rivals, gate=gate, q_pos=q_pos, t_pos=t_pos,
+                              keys=keys)
+        if cross_check:
+            rev = self.match_1nn(t_desc, q_desc, nt, nq, gate=gate, q_pos=t_pos, t_pos=q_pos, keys=keys_rev, n_forward=0)
+            self.cross_check_matches(keys, rev, nq, nt, keys_out=keys)
+        return keys
 
     def match_l2(self, q_desc, t_desc, nq, nt, k=1):
         """Float descriptors: q_desc [P, Sq, dim] f32, t_desc [P, St, dim] f32 -> keys [P, Sq, k] int64 holding the u64
@@ -489,23 +495,7 @@ class Context(object):
     def match_radius(self, q_desc, t_desc, nq, nt, max_distance, cap, q_slot=None, t_slot=None):
         """radiusMatch: q_desc [Bq, Sq, 32] u8, t_desc [Bt, St, 32] u8 -> (keys [P, Sq, cap] u32 ascending,
         KEY_NONE padded; counts [P, Sq] i32 = matches within max_distance, may exceed cap)."""
-        _check(q_desc, torch.uint8, "q_desc", (None, None, _lib.DESC_BYTES))
-        _check(t_desc, torch.uint8, "t_desc", (None, None, _lib.DESC_BYTES))
-        Bq, Sq = q_desc.shape[0], q_desc.shape[1]
-        Bt, St = t_desc.shape[0], t_desc.shape[1]
-        _check(nq, torch.int32, "nq", (Bq,))
-        _check(nt, torch.int32, "nt", (Bt,))
-        if (q_slot is None) != (t_slot is None):
-            raise SosvoError("q_slot and t_slot go together")
-        if q_slot is not None:
-            P = q_slot.shape[0]
-            _check(q_slot, torch.int32, "q_slot", (P,))
-            _check(t_slot, torch.int32, "t_slot", (P,))
-        else:
-            if Bq != Bt:
-                raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
-            P = Bq
-        keys = torch.empty((P, Sq, int(cap)), dtype=torch.uint32, device=q_desc.device)
+        P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, None, int(cap))
         counts = torch.zeros((P, Sq), dtype=torch.int32, device=q_desc.device)
         self._call(self._lib.sosvo_match_radius, _ptr(q_desc), _ptr(t_desc), _ptr(nq), _ptr(nt), _ptr(q_slot), _ptr(t_slot),
                    P, Sq, St, int(max_distance), int(cap), _ptr(keys), _ptr(counts))

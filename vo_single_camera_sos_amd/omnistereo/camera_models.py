@@ -172,41 +172,32 @@ class FeatureMatcher(object):
         self.ratio = kwargs.get("ratio", None)
         self._check_ratio()
 
+    def _check_best_match_only(self, what, why=""):
+        """What cross_check, gated and ratio share: one match per query, binary descriptors."""
+        if self.k_best != 1:
+            raise ValueError("%s goes with k_best == 1 only%s" % (what, why))
+        if self.use_radius_match:
+            raise ValueError("%s is defined for best-match search, not for radius match" % what)
+        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
+            raise ValueError("%s is built for binary (Hamming) descriptors only; %r makes float descriptors"
+                             % (what, self.feature_detection_method))
+
     def _check_ratio(self):
         """-> the ratio in 64ths, 0 without one."""
         if self.ratio is None:
             return 0
         from .._lib import ratio_64ths
-        if self.k_best != 1:
-            raise ValueError("ratio goes with k_best == 1 only (the rule returns one match per query; k_best == 2 returns both neighbours)")
-        if self.use_radius_match:
-            raise ValueError("ratio is defined for best-match search, not for radius match")
-        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
-            raise ValueError("ratio is built for binary (Hamming) descriptors only; %r makes float descriptors"
-                             % self.feature_detection_method)
+        self._check_best_match_only("ratio", " (the rule returns one match per query; k_best == 2 returns both neighbours)")
         return ratio_64ths(self.ratio)
 
     def _check_gated(self, max_distance=None):
-        if self.k_best != 1:
-            raise ValueError("gated matching goes with k_best == 1 only")
-        if self.use_radius_match:
-            raise ValueError("gated matching is defined for best-match search, not for radius match")
-        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
-            raise ValueError("gated matching is built for binary (Hamming) descriptors only; %r makes float descriptors"
-                             % self.feature_detection_method)
+        self._check_best_match_only("gated matching")
         if max_distance is not None and (int(max_distance) != max_distance or not 0 <= max_distance <= 256):
             raise ValueError("gated matching: max_distance must be None or an integer in 0 .. 256, got %r" % (max_distance,))
 
     def _check_cross_check(self):
-        if not self.cross_check:
-            return
-        if self.k_best != 1:
-            raise ValueError("cross_check goes with k_best == 1 only (as cv2.BFMatcher refuses knnMatch with k > 1 under crossCheck)")
-        if self.use_radius_match:
-            raise ValueError("cross_check is defined for best-match search, not for radius match")
-        if str(self.feature_detection_method).upper() in ("SIFT", "SURF"):
-            raise ValueError("cross_check is built for binary (Hamming) descriptors only; %r makes float descriptors"
-                             % self.feature_detection_method)
+        if self.cross_check:
+            self._check_best_match_only("cross_check", " (as cv2.BFMatcher refuses knnMatch with k > 1 under crossCheck)")
 
     def _context(self):
         if self._ctx is None:
@@ -232,52 +223,61 @@ class FeatureMatcher(object):
             buf[0, :n] = t.to(ctx.device)
         return buf, n
 
+    @staticmethod
+    def _host_desc(descs, name, flat=False):
+        """-> the descriptor arrays as [n, 32] uint8 numpy arrays (flat: reshaped to rows of 32 first); others raise."""
+        out = [np.ascontiguousarray(np.asarray(d)) for d in descs]
+        if flat:
+            out = [a.reshape(-1, 32) for a in out]
+        for a in out:
+            if a.dtype != np.uint8:
+                raise NotImplementedError("%s: dtype %s -- only uint8 (binary, Hamming) descriptors are built" % (name, a.dtype))
+            if a.ndim != 2 or a.shape[1] != 32:
+                raise ValueError("%s: expected [n, 32] uint8 descriptors, got %s" % (name, a.shape))
+        return out
+
+    def _match_many(self, qs, ts, r64, q_pts=None, t_pts=None, gate=None):
+        """The batched best-match search of match_arrays_many / match_gated_many: the P problems padded to [P, cap, 32] (and
+        their positions to [P, cap, 2] under a gate), counts, upload; the matching step (Context.match_1nn_two_launch: one
+        launch, two with cross_check) and the sort; one copy back, the queries in rank order without those that have no match
+        (they sort last), the keys split into train index and distance."""
+        import torch
+        from .._lib import KEY_SHIFT, KEY_IDX_MASK, KEY_NONE
+        ctx = self._context()
+        nq, nt = np.array([len(a) for a in qs], np.int32), np.array([len(a) for a in ts], np.int32)
+
+        def upload(arrays, n, width, dtype):
+            h = np.zeros((len(arrays), max(1, int(n.max())), width), dtype)
+            for i, a in enumerate(arrays):
+                h[i, :n[i]] = a
+            return torch.from_numpy(h).to(ctx.device)
+        dq, dt = upload(qs, nq, 32, np.uint8), upload(ts, nt, 32, np.uint8)
+        nq_d, nt_d = torch.from_numpy(nq).to(ctx.device), torch.from_numpy(nt).to(ctx.device)
+        pos = dict(q_pos=upload(q_pts, nq, 2, np.float32), t_pos=upload(t_pts, nt, 2, np.float32), gate=gate) if gate else {}
+        keys = ctx.match_1nn_two_launch(dq, dt, nq_d, nt_d, cross_check=self.cross_check, ratio_64ths=r64, **pos)
+        order = ctx.sort_matches(keys, nq_d)
+        kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
+        out = []
+        for i in range(len(qs)):
+            o = oh[i, :nq[i]]
+            k = kh[i][o]
+            o, k = o[k != KEY_NONE], k[k != KEY_NONE]
+            out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
+        return out
+
     def match_arrays_many(self, pairs):
         """[(query_descriptors, train_descriptors), ...] -> [(query_idx, train_idx, distance), ...]: match_arrays for
         every pair, but as ONE batched launch + one copy back when the matcher is in its best-match mode (the per-bucket
         loop of match_features_panoramic_top_bottom costs a dozen launch / synchronise round trips per frame otherwise)."""
-        import torch
         r64 = self._check_ratio()
         if r64 and any(self._is_float(q) or self._is_float(t) for q, t in pairs):
             raise ValueError("ratio is built for binary (Hamming) descriptors only, not float descriptors")
         if self.use_radius_match or self.k_best != 1 or len(pairs) == 0 or any(self._is_float(q) or self._is_float(t) for q, t in pairs):
             return [self.match_arrays(q, t) for q, t in pairs]
-        ctx = self._context()
-        qs = [np.ascontiguousarray(np.asarray(q)) for q, _ in pairs]
-        ts = [np.ascontiguousarray(np.asarray(t)) for _, t in pairs]
-        for name, arrs in (("query_descriptors", qs), ("train_descriptors", ts)):
-            for a in arrs:
-                if a.dtype != np.uint8:
-                    raise NotImplementedError("%s: dtype %s -- only uint8 (binary, Hamming) descriptors are built" % (name, a.dtype))
-                if a.ndim != 2 or a.shape[1] != 32:
-                    raise ValueError("%s: expected [n, 32] uint8 descriptors, got %s" % (name, a.shape))
-        P = len(pairs)
-        nq, nt = np.array([a.shape[0] for a in qs], np.int32), np.array([a.shape[0] for a in ts], np.int32)
-        cq, ct = max(1, int(nq.max())), max(1, int(nt.max()))
-        hq, ht = np.zeros((P, cq, 32), np.uint8), np.zeros((P, ct, 32), np.uint8)
-        for i in range(P):
-            hq[i, :nq[i]] = qs[i]
-            ht[i, :nt[i]] = ts[i]
-        dev = ctx.device
-        nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
-        dq, dt = torch.from_numpy(hq).to(dev), torch.from_numpy(ht).to(dev)
-        keys = ctx.match_hamming_ratio(dq, dt, nq_d, nt_d, r64)[0] if r64 else ctx.match_hamming(dq, dt, nq_d, nt_d, k=1)
-        if self.cross_check:
-            ctx.cross_check_matches(keys, ctx.match_hamming(dt, dq, nt_d, nq_d, k=1), nq_d, nt_d, keys_out=keys)
-        order = ctx.sort_matches(keys, nq_d)
-        from .._lib import KEY_SHIFT, KEY_IDX_MASK, KEY_NONE
-        kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
-        out = []
-        for i in range(P):
-            if nq[i] == 0 or nt[i] == 0:
-                out.append((np.empty(0, np.int64),) * 2 + (np.empty(0, np.float32),))
-                continue
-            o = oh[i, :nq[i]]
-            k = kh[i][o]
-            if self.cross_check or r64:  # (the rejected queries sorted last)
-                o, k = o[k != KEY_NONE], k[k != KEY_NONE]
-            out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
-        return out
+        qs = self._host_desc([q for q, _ in pairs], "query_descriptors")
+        ts = self._host_desc([t for _, t in pairs], "train_descriptors")
+        empty = (np.empty(0, np.int64),) * 2 + (np.empty(0, np.float32),)
+        return [empty if len(q) == 0 or len(t) == 0 else m for q, t, m in zip(qs, ts, self._match_many(qs, ts, r64))]
 
     def match_gated_many(self, items, min_dv, max_du, max_distance=None):
         """[(query_descriptors, train_descriptors, query_pts, train_pts), ...] -> [(query_idx, train_idx, distance), ...] as
@@ -286,54 +286,22 @@ class FeatureMatcher(object):
         positions *_pts [n, >= 2] (u, v), in double.  max_distance: None = no cap, else 0 .. 256.  A query without an
         admissible train within the cap has no match.  With cross_check the role-swapped search runs under the same gate.
         One launch (two with cross_check) and one copy back for all items."""
-        import torch
         self._check_cross_check()
         self._check_gated(max_distance)
         r64 = self._check_ratio()
         if any(self._is_float(q) or self._is_float(t) for q, t, _, _ in items):
             raise ValueError("gated matching is built for binary (Hamming) descriptors only, not float descriptors")
-        P = len(items)
-        if P == 0:
+        if len(items) == 0:
             return []
-        ctx = self._context()
-        qs = [np.ascontiguousarray(np.asarray(q)).reshape(-1, 32) for q, _, _, _ in items]
-        ts = [np.ascontiguousarray(np.asarray(t)).reshape(-1, 32) for _, t, _, _ in items]
-        for name, arrs in (("query_descriptors", qs), ("train_descriptors", ts)):
-            for a in arrs:
-                if a.dtype != np.uint8:
-                    raise NotImplementedError("%s: dtype %s -- only uint8 (binary, Hamming) descriptors are built" % (name, a.dtype))
-        nq, nt = np.array([a.shape[0] for a in qs], np.int32), np.array([a.shape[0] for a in ts], np.int32)
-        cq, ct = max(1, int(nq.max())), max(1, int(nt.max()))
-        hq, ht = np.zeros((P, cq, 32), np.uint8), np.zeros((P, ct, 32), np.uint8)
-        pq, pt = np.zeros((P, cq, 2), np.float32), np.zeros((P, ct, 2), np.float32)
-        for i, (_, _, q_pts, t_pts) in enumerate(items):
-            hq[i, :nq[i]], ht[i, :nt[i]] = qs[i], ts[i]
-            for dst, pts, n, name in ((pq, q_pts, nq[i], "query_pts"), (pt, t_pts, nt[i], "train_pts")):
-                a = np.asarray(pts, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 2))
-                if a.shape[1] < 2:
-                    raise ValueError("%s: expected [n, 2] pixel positions" % name)
-                dst[i, :n] = a[:, :2]
-        dev = ctx.device
-        nq_d, nt_d = torch.from_numpy(nq).to(dev), torch.from_numpy(nt).to(dev)
-        dq, dt, dpq, dpt = (torch.from_numpy(a).to(dev) for a in (hq, ht, pq, pt))
-        if r64:
-            keys = ctx.match_hamming_ratio(dq, dt, nq_d, nt_d, r64, q_pos=dpq, t_pos=dpt, min_dv=min_dv, max_du=max_du,
-                                           max_distance=max_distance)[0]
-        else:
-            keys = ctx.match_hamming_gated(dq, dt, dpq, dpt, nq_d, nt_d, min_dv, max_du, max_distance)
-        if self.cross_check:    # the role-swapped search under the same gate (all its problems reversed), then the filter
-            rev = ctx.match_hamming_gated(dt, dq, dpt, dpq, nt_d, nq_d, min_dv, max_du, max_distance, n_forward=0)
-            ctx.cross_check_matches(keys, rev, nq_d, nt_d, keys_out=keys)
-        order = ctx.sort_matches(keys, nq_d)
-        from .._lib import KEY_SHIFT, KEY_IDX_MASK, KEY_NONE
-        kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
-        out = []
-        for i in range(P):
-            o = oh[i, :nq[i]]
-            k = kh[i][o]
-            o, k = o[k != KEY_NONE], k[k != KEY_NONE]      # (the queries without a match sorted last)
-            out.append((o, k & KEY_IDX_MASK, (k >> KEY_SHIFT).astype(np.float32)))
-        return out
+        qs = self._host_desc([q for q, _, _, _ in items], "query_descriptors", flat=True)
+        ts = self._host_desc([t for _, t, _, _ in items], "train_descriptors", flat=True)
+        pts = []
+        for name, descs, k in (("query_pts", qs, 2), ("train_pts", ts, 3)):
+            a = [np.asarray(item[k], dtype=np.float64).reshape(len(d), -1) if len(d) else np.zeros((0, 2)) for item, d in zip(items, descs)]
+            if any(x.shape[1] < 2 for x in a):
+                raise ValueError("%s: expected [n, 2] pixel positions" % name)
+            pts.append([x[:, :2] for x in a])
+        return self._match_many(qs, ts, r64, pts[0], pts[1], (min_dv, max_du, max_distance))
 
     def match_gated(self, query_desc, train_desc, query_pts, train_pts, min_dv, max_du, max_distance=None):
         """match() under the pixel gates -> MatchList, ascending by distance, ties in query order (see match_gated_many)."""
@@ -408,17 +376,14 @@ class FeatureMatcher(object):
         nq_t = torch.tensor([nq], dtype=torch.int32, device=dev)
         nt_t = torch.tensor([nt], dtype=torch.int32, device=dev)
         k = 2 if self.k_best == 2 else 1
-        # [1, nq, k]; with a ratio (k == 1) the rule is applied by the search itself
-        keys = ctx.match_hamming_ratio(dq, dt, nq_t, nt_t, r64)[0] if r64 else ctx.match_hamming(dq, dt, nq_t, nt_t, k=k)
+        # [1, nq, k]; k == 1: the matching step -- a ratio's rule applied by the search itself, the mutual filter in place
+        keys = ctx.match_1nn_two_launch(dq, dt, nq_t, nt_t, cross_check=self.cross_check, ratio_64ths=r64) if k == 1 else \
+            ctx.match_hamming(dq, dt, nq_t, nt_t, k=k)
         ratio_rule = k == 2 and str(self.feature_detection_method).upper() == "SIFT"
         if k == 1 or ratio_rule:
             # sorted(matches, key=distance) of one match per query (:442-444); for the ratio rule the filter
             # below keeps the sorted order of the survivors, which is the sorted order of the filtered list
-            best = keys[:, :, :1].contiguous()
-            if self.cross_check:  # (k == 1) the role-swapped search, then the mutual filter in place
-                ctx.cross_check_matches(best, ctx.match_hamming(dt, dq, nt_t, nq_t, k=1), nq_t, nt_t, keys_out=best)
-                keys = best
-            order = ctx.sort_matches(best, nq_t)
+            order = ctx.sort_matches(keys[:, :, :1].contiguous(), nq_t)
             kh = keys[0, :nq].cpu().numpy().astype(np.int64)
             oh = order[0, :nq].cpu().numpy().astype(np.int64)
             if self.cross_check or r64:  # (the rejected queries sorted last)

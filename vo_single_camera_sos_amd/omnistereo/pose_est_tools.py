@@ -27,6 +27,7 @@ from math import log10, sqrt
 import numpy as np
 
 from .. import pyopengv
+from .._lib import MatchOptions
 from . import transformations as tr
 from .camera_models import FeatureMatcher, KeyPoint, KeyPointAndDescriptor, PanoramicCorrespondences, keypoints_to_array
 from .common_cv import filter_pixel_correspondences
@@ -472,31 +473,48 @@ def parse_cross_check(cross_check):
     return table[name]
 
 
+def _set_matcher_option(tracker, name, value, validate, setting, check, mirror):
+    """What set_cross_check / set_gated_matching / set_ratio_test share.  value as parse_cross_check takes its argument (None:
+    nothing happens); validate(stereo, f2f) checks the option's own values; an RGB-D tracker has the frame-to-frame matcher
+    only ("stereo" is a ValueError); setting(on) -> the FeatureMatcher attributes of a matcher switched `on`, check(fm, on)
+    raises what that matcher refuses (k_best > 1, radius match, float descriptors); mirror(stereo, f2f) -> the tracker's
+    attributes.  Every matcher is checked before anything is kept: a refused setting leaves matchers and tracker as they were."""
+    if value is None:
+        return
+    try:
+        stereo, f2f = parse_cross_check(value)
+    except ValueError:
+        if name == "cross_check":
+            raise
+        raise ValueError("%s: None, True, False, \"stereo\", \"f2f\" or \"both\"; got %r" % (name, value))
+    validate(stereo, f2f)
+    cm = tracker.camera_model
+    if _is_rgbd_model(cm):
+        if isinstance(value, str) and stereo:
+            raise ValueError("%s=%r: an RGB-D tracker has no static-stereo matcher" % (name, value))
+        stereo = False
+    matchers = [(fm, on) for fm, on in ((getattr(cm, "feature_matcher_for_static_stereo", None), stereo),
+                                        (getattr(cm, "feature_matcher_for_motion", None), f2f)) if fm is not None]
+    before = [{k: getattr(fm, k) for k in setting(on)} for fm, on in matchers]
+    try:
+        for fm, on in matchers:
+            fm.__dict__.update(setting(on))
+            check(fm, on)
+    except ValueError:
+        for (fm, _), old in zip(matchers, before):
+            fm.__dict__.update(old)
+        raise
+    tracker.__dict__.update(mirror(stereo, f2f))
+
+
 def set_cross_check(tracker, cross_check):
     """Switch the mutual-consistency filter (cv2.BFMatcher's crossCheck, camera_models.py:401) of the tracker's matchers:
     cross_check as parse_cross_check takes it (None: leave the tracker's own setting).  The matchers bootstrap_tracker
     built carry the switch, so the per-frame mirror path and the engine chosen from the tracker's settings both follow.
     An RGB-D tracker has the frame-to-frame matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
-    switches = parse_cross_check(cross_check)
-    if switches is None:
-        return
-    stereo, f2f = switches
-    cm = tracker.camera_model
-    fm_stereo = getattr(cm, "feature_matcher_for_static_stereo", None)
-    fm_motion = getattr(cm, "feature_matcher_for_motion", None)
-    if _is_rgbd_model(cm):
-        if isinstance(cross_check, str) and stereo:
-            raise ValueError("cross_check=%r: an RGB-D tracker has no static-stereo matcher" % (cross_check,))
-        stereo = False
-    tracker.cross_check_static_stereo, tracker.cross_check_for_motion = stereo, f2f
-    for fm, on in ((fm_stereo, stereo), (fm_motion, f2f)):
-        if fm is not None:
-            fm.cross_check = on
-            fm._check_cross_check()   # (k_best > 1, radius match, float descriptors: ValueError)
-
-
-def _cross_check_of(fm):
-    return bool(getattr(fm, "cross_check", False)) if fm is not None else False
+    _set_matcher_option(tracker, "cross_check", cross_check, lambda stereo, f2f: None, lambda on: dict(cross_check=on),
+                        lambda fm, on: fm._check_cross_check(),
+                        lambda stereo, f2f: dict(cross_check_static_stereo=stereo, cross_check_for_motion=f2f))
 
 
 def set_gated_matching(tracker, gated_matching, gated_max_distance=None):
@@ -506,26 +524,12 @@ def set_gated_matching(tracker, gated_matching, gated_max_distance=None):
     mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame
     matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
     from .._lib import gated_flags
-    if gated_matching is None:
-        return
-    try:
-        stereo, f2f = parse_cross_check(gated_matching)
-    except ValueError:
-        raise ValueError("gated_matching: None, True, False, \"stereo\", \"f2f\" or \"both\"; got %r" % (gated_matching,))
-    gated_flags(stereo, f2f, gated_max_distance)      # (ValueError for a cap outside 1 .. 256)
-    cm = tracker.camera_model
-    if _is_rgbd_model(cm):
-        if isinstance(gated_matching, str) and stereo:
-            raise ValueError("gated_matching=%r: an RGB-D tracker has no static-stereo matcher" % (gated_matching,))
-        stereo = False
-    cap = None if gated_max_distance is None else int(gated_max_distance)
-    tracker.gated_static_stereo, tracker.gated_for_motion, tracker.gated_max_distance = stereo, f2f, cap
-    for fm, on in ((getattr(cm, "feature_matcher_for_static_stereo", None), stereo),
-                   (getattr(cm, "feature_matcher_for_motion", None), f2f)):
-        if fm is not None:
-            fm.gated, fm.gated_max_distance = on, cap
-            if on:
-                fm._check_gated(cap)              # (k_best > 1, radius match, float descriptors: ValueError)
+    cap = gated_max_distance      # (gated_flags: ValueError for a cap outside 1 .. 256; then an integer)
+    _set_matcher_option(tracker, "gated_matching", gated_matching, lambda stereo, f2f: gated_flags(stereo, f2f, cap),
+                        lambda on: dict(gated=on, gated_max_distance=None if cap is None else int(cap)),
+                        lambda fm, on: on and fm._check_gated(cap),
+                        lambda stereo, f2f: dict(gated_static_stereo=stereo, gated_for_motion=f2f,
+                                                 gated_max_distance=None if cap is None else int(cap)))
 
 
 def set_ratio_test(tracker, ratio_test, ratio=None):
@@ -536,42 +540,10 @@ def set_ratio_test(tracker, ratio_test, ratio=None):
     the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame matcher only: True /
     False / "f2f" set it, "stereo" is a ValueError."""
     from .._lib import ratio_flags
-    if ratio_test is None:
-        return
-    try:
-        stereo, f2f = parse_cross_check(ratio_test)
-    except ValueError:
-        raise ValueError("ratio_test: None, True, False, \"stereo\", \"f2f\" or \"both\"; got %r" % (ratio_test,))
-    ratio_flags(stereo, f2f, ratio)      # (ValueError for a ratio that is no 64th, or a switch without a ratio)
-    cm = tracker.camera_model
-    if _is_rgbd_model(cm):
-        if isinstance(ratio_test, str) and stereo:
-            raise ValueError("ratio_test=%r: an RGB-D tracker has no static-stereo matcher" % (ratio_test,))
-        stereo = False
-    value = None if ratio is None else float(ratio)
-    matchers = [(fm, on) for fm, on in ((getattr(cm, "feature_matcher_for_static_stereo", None), stereo),
-                                        (getattr(cm, "feature_matcher_for_motion", None), f2f)) if fm is not None]
-    before = [fm.ratio for fm, _ in matchers]
-    try:                                          # every matcher is checked before anything is kept: a refused setting changes nothing
-        for fm, on in matchers:
-            fm.ratio = value if on else None
-            fm._check_ratio()                     # (k_best > 1, radius match, float descriptors: ValueError)
-    except ValueError:
-        for (fm, _), old in zip(matchers, before):
-            fm.ratio = old
-        raise
-    tracker.ratio_static_stereo, tracker.ratio_for_motion = (value if stereo else None), (value if f2f else None)
-
-
-def _ratio_of(fm):
-    """The ratio of a matcher (None: off), as the engine-cache keys carry it."""
-    return getattr(fm, "ratio", None) if fm is not None else None
-
-
-def _gated_of(fm):
-    """(switch, cap) of a matcher, as the engine-cache keys carry them."""
-    on = bool(getattr(fm, "gated", False)) if fm is not None else False
-    return on, (getattr(fm, "gated_max_distance", None) if on else None)
+    of = lambda on: float(ratio) if on else None      # noqa: E731 (ratio_flags: ValueError for a ratio that is no 64th, or none)
+    _set_matcher_option(tracker, "ratio_test", ratio_test, lambda stereo, f2f: ratio_flags(stereo, f2f, ratio),
+                        lambda on: dict(ratio=of(on)), lambda fm, on: fm._check_ratio(),
+                        lambda stereo, f2f: dict(ratio_static_stereo=of(stereo), ratio_for_motion=of(f2f)))
 
 
 def _sos_engine_settings(tracker, camera_model, first_image):
@@ -601,27 +573,19 @@ def _sos_engine_settings(tracker, camera_model, first_image):
                     f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     nfeat = tracker.num_features_detection_for_static_stereo
     cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
-    # the two matchers' crossCheck (what the mirror path matches with): part of the engine's configuration and of its key
-    cc_stereo, cc_f2f = _cross_check_of(fm), _cross_check_of(getattr(om, "feature_matcher_for_motion", None))
-    # ... and their search under the gates.  The engine has one cap for both matchers (as set_gated_matching sets them)
-    (g_stereo, cap_stereo), (g_f2f, cap_f2f) = _gated_of(fm), _gated_of(getattr(om, "feature_matcher_for_motion", None))
-    if g_stereo and g_f2f and cap_stereo != cap_f2f:
+    # the two matchers' options (what the mirror path matches with): part of the engine's configuration and of its key.  The
+    # engine has one cap and one ratio for both matchers (as set_gated_matching / set_ratio_test set them)
+    opts = MatchOptions.from_matchers(fm, getattr(om, "feature_matcher_for_motion", None))
+    if opts is None:
         return None
-    g_cap = cap_stereo if g_stereo else cap_f2f
-    # ... and their ratio rule.  The engine has one ratio for both matchers (as set_ratio_test sets them)
-    r_stereo, r_f2f = _ratio_of(fm), _ratio_of(getattr(om, "feature_matcher_for_motion", None))
-    if r_stereo is not None and r_f2f is not None and r_stereo != r_f2f:
-        return None
-    r_value = r_stereo if r_stereo is not None else r_f2f
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           cc_stereo, cc_f2f, g_stereo, g_f2f, g_cap, r_stereo, r_f2f)
+           opts)
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
-                  cross_check_stereo=cc_stereo, cross_check_f2f=cc_f2f, gated_stereo=g_stereo, gated_f2f=g_f2f,
-                  gated_max_distance=g_cap, ratio_stereo=r_stereo is not None, ratio_f2f=r_f2f is not None, ratio=r_value)
+                  **opts._asdict())
     return (model, rig), kwargs, key
 
 
@@ -758,15 +722,15 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     cam = RGBDCamConfig(cm.fx, cm.fy, cm.center_x, cm.center_y, cm.focal_length_m, cm.depth_is_Z, 0.8, 7.0,
                         f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     shape = tuple(int(v) for v in np.asarray(first_rgb).shape[:2])
+    opts = MatchOptions.from_matchers(None, fm)
     key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
-           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), _cross_check_of(fm)) + _gated_of(fm) + (_ratio_of(fm),)
+           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), opts)
     kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
-                  detection_method=method, cross_check=_cross_check_of(fm), gated_f2f=_gated_of(fm)[0],
-                  gated_max_distance=_gated_of(fm)[1], ratio_f2f=_ratio_of(fm) is not None, ratio=_ratio_of(fm))
+                  detection_method=method, **opts.rgbd_kwargs())
     return (cam,), kwargs, key
 
 

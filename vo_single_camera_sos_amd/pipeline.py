@@ -9,6 +9,7 @@ import threading
 import numpy as np
 import torch
 
+from ._lib import MatchOptions
 from .device import Context, make_rig
 
 
@@ -47,13 +48,9 @@ class FramePairPipeline(object):
         ratio_stereo / ratio_f2f: Lowe's ratio rule fused into that matcher's search (Context.match_hamming_ratio), plain or
         under the gate; ratio: a float in (0, 1) with ratio * 64 an integer (0.75 = the reference's, camera_models.py:423)."""
         assert isinstance(ctx, Context)
-        from . import _lib
-        _lib.gated_flags(gated_stereo, gated_f2f, gated_max_distance)   # (ValueError for a cap out of range)
-        _lib.ratio_flags(ratio_stereo, ratio_f2f, ratio)                 # (ValueError for a ratio that is no 64th)
-        self.ratio_stereo = _lib.ratio_64ths(ratio) if ratio_stereo else 0   # (in 64ths; 0: off)
-        self.ratio_f2f = _lib.ratio_64ths(ratio) if ratio_f2f else 0
-        self.gated_stereo, self.gated_f2f, self.gated_max_distance = bool(gated_stereo), bool(gated_f2f), gated_max_distance
-        self.cross_check_stereo, self.cross_check_f2f = bool(cross_check_stereo), bool(cross_check_f2f)
+        # (ValueError for a cap out of range, a ratio that is no 64th)
+        self.opts = o = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
+                                     ratio_stereo, ratio_f2f, ratio)
         self.ctx, self.rig_cfg, self.rig = ctx, rig, rig.as_struct()
         self.front_end = front_end
         if front_end is not None:
@@ -79,8 +76,13 @@ class FramePairPipeline(object):
             self.desc_top, self.desc_bot = z((P, bucket_cap, 32), torch.uint8), z((P, bucket_cap, 32), torch.uint8)
             self.n_top, self.n_bot = z((P,), torch.int32), z((P,), torch.int32)
         self.s_keys, self.s_order = z((P, bucket_cap, 1), torch.uint32), z((P, bucket_cap), torch.int32)
-        self.s_keys_rev = z((P, bucket_cap, 1), torch.uint32) if self.cross_check_stereo else None
-        self.s_rivals = z((P, bucket_cap, 1), torch.uint32) if self.ratio_stereo else None
+        self.s_keys_rev = z((P, bucket_cap, 1), torch.uint32) if o.cross_check_stereo else None
+        self.s_rivals = z((P, bucket_cap, 1), torch.uint32) if o.ratio_stereo else None
+        # what stereo() / track() hand the matching step: query = bottom, train = top under the gate of stereo_assemble; the
+        # |du| gate of f2f_assemble
+        self._stereo_search = dict(cross_check=o.cross_check_stereo, keys_rev=self.s_keys_rev, ratio_64ths=o.ratio_64ths_stereo,
+                                   rivals=self.s_rivals, keys=self.s_keys,
+                                   gate=(rig.stereo_min_disp, rig.stereo_max_hdiff, gated_max_distance) if o.gated_stereo else None)
         Fc, Cc = self.frame_cap, self.corr_cap
         # descriptors and counts of both views back to back (view-major): the two frame-to-frame matchings of a step
         # (top with top, bottom with bottom) are ONE launch of 2B problems, and so are the two sorts
@@ -94,16 +96,15 @@ class FramePairPipeline(object):
                            n_cand=z((self.F,), torch.int32))
         self.ref_frame = torch.arange(0, self.F, 2, dtype=torch.int32, device=dev)
         self.cur_frame = torch.arange(1, self.F, 2, dtype=torch.int32, device=dev)
-        self._q2 = torch.cat([self.cur_frame, self.cur_frame + self.F])   # problem i: top view, B + i: bottom view
-        self._t2 = torch.cat([self.ref_frame, self.ref_frame + self.F])
+        q = torch.cat([self.cur_frame, self.cur_frame + self.F])   # problem i: top view, B + i: bottom view
+        t = torch.cat([self.ref_frame, self.ref_frame + self.F])
         self._o2 = z((2 * self.B, Fc), torch.int32)
-        if self.cross_check_f2f:   # the 2B role-swapped problems ride in the same launch, after the 2B forward ones
-            self._q4, self._t4 = torch.cat([self._q2, self._t2]), torch.cat([self._t2, self._q2])
-            self._k4 = z((4 * self.B, Fc, 1), torch.uint32)
-            self._k2 = self._k4[: 2 * self.B]
-        else:
-            self._k2 = z((2 * self.B, Fc, 1), torch.uint32)
-        self._rivals = torch.zeros_like(self._k4 if self.cross_check_f2f else self._k2) if self.ratio_f2f else None
+        if o.cross_check_f2f:   # the 2B role-swapped problems ride in the same launch, after the 2B forward ones
+            q, t = torch.cat([q, t]), torch.cat([t, q])
+        self._q, self._t, self._k = q, t, z((len(q), Fc, 1), torch.uint32)
+        self._q2, self._t2, self._k2 = q[: 2 * self.B], t[: 2 * self.B], self._k[: 2 * self.B]     # the forward problems
+        self._f2f_search = dict(ratio_64ths=o.ratio_64ths_f2f, rivals=torch.zeros_like(self._k) if o.ratio_f2f else None,
+                                gate=(-1.0, rig.f2f_max_hdiff, gated_max_distance) if o.gated_f2f else None)
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
         self.o_top, self.o_bot = self._o2[: self.B], self._o2[self.B:]
         self.corr = dict(f=z((self.B, Cc, 3), torch.float64), p=z((self.B, Cc, 3), torch.float64),
@@ -127,24 +128,8 @@ class FramePairPipeline(object):
     # ---- one step ----------------------------------------------------------------------------
     def stereo(self):
         c = self.ctx
-        # query = bottom, train = top: the gate of stereo_assemble
-        g = dict(min_dv=self.rig_cfg.stereo_min_disp, max_du=self.rig_cfg.stereo_max_hdiff,
-                 max_distance=self.gated_max_distance) if self.gated_stereo else None
-        if self.ratio_stereo:
-            pos = dict(q_pos=self.kp_bot, t_pos=self.kp_top, **g) if g else {}
-            c.match_hamming_ratio(self.desc_bot, self.desc_top, self.n_bot, self.n_top, self.ratio_stereo, keys=self.s_keys,
-                                  rivals=self.s_rivals, **pos)
-        elif g:
-            c.match_hamming_gated(self.desc_bot, self.desc_top, self.kp_bot, self.kp_top, self.n_bot, self.n_top, keys=self.s_keys, **g)
-        else:
-            c.match_hamming(self.desc_bot, self.desc_top, self.n_bot, self.n_top, k=1, keys=self.s_keys)
-        if self.cross_check_stereo:   # the role-swapped search: under the reversed gate, and never with the ratio rule
-            if g:
-                c.match_hamming_gated(self.desc_top, self.desc_bot, self.kp_top, self.kp_bot, self.n_top, self.n_bot,
-                                      keys=self.s_keys_rev, n_forward=0, **g)
-            else:
-                c.match_hamming(self.desc_top, self.desc_bot, self.n_top, self.n_bot, k=1, keys=self.s_keys_rev)
-            c.cross_check_matches(self.s_keys, self.s_keys_rev, self.n_bot, self.n_top, keys_out=self.s_keys)
+        c.match_1nn_two_launch(self.desc_bot, self.desc_top, self.n_bot, self.n_top, q_pos=self.kp_bot, t_pos=self.kp_top,
+                               **self._stereo_search)
         c.sort_matches(self.s_keys, self.n_bot, order=self.s_order)
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
                           self.s_keys, self.s_order, self.F, self.NM, self.frame_cap, out=self.frames)
@@ -153,22 +138,8 @@ class FramePairPipeline(object):
         c, fr = self.ctx, self.frames
         self._M2[1].copy_(self._M2[0])                      # the bottom view's blocks have the same counts
         d2, M2 = self._d2.view(2 * self.F, self.frame_cap, 32), self._M2.view(2 * self.F)
-        keys, q_slot, t_slot = (self._k4, self._q4, self._t4) if self.cross_check_f2f else (self._k2, self._q2, self._t2)
-        if self.ratio_f2f:      # plain or under the |du| gate; the role-swapped second half gets no rule
-            m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
-            g = dict(q_pos=m2, t_pos=m2, min_dv=-1.0, max_du=self.rig_cfg.f2f_max_hdiff,
-                     max_distance=self.gated_max_distance) if self.gated_f2f else {}
-            c.match_hamming_ratio(d2, d2, M2, M2, self.ratio_f2f, keys=keys, rivals=self._rivals, q_slot=q_slot, t_slot=t_slot,
-                                  n_forward=2 * self.B, **g)
-        elif self.gated_f2f:    # the |du| gate of f2f_assemble; the role-swapped problems are the second half
-            m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
-            c.match_hamming_gated(d2, d2, m2, m2, M2, M2, min_dv=-1.0, max_du=self.rig_cfg.f2f_max_hdiff,
-                                  max_distance=self.gated_max_distance, keys=keys, q_slot=q_slot, t_slot=t_slot,
-                                  n_forward=2 * self.B)
-        else:
-            c.match_hamming(d2, d2, M2, M2, k=1, keys=keys, q_slot=q_slot, t_slot=t_slot)   # both views, 2B problems
-        if self.cross_check_f2f:
-            c.cross_check_matches(self._k2, self._k4[2 * self.B:], M2, M2, q_slot=self._q2, t_slot=self._t2, keys_out=self._k2)
+        m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
+        c.match_1nn_slots(d2, m2, M2, self._q, self._t, self._k, 2 * self.B, **self._f2f_search)   # both views, 2B problems
         c.sort_matches(self._k2, M2, order=self._o2, q_slot=self._q2)
         c.f2f_assemble(self.rig, fr, self.ref_frame, self.cur_frame, self.k_top, self.o_top, self.k_bot, self.o_bot,
                        self.corr_cap, out=self.corr)
@@ -224,6 +195,8 @@ class OverlappedFramePairs(object):
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray."""
         from .frontend import DeviceImageModel, ImageFrontEnd
         from .parallel import shard_range
+        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
@@ -247,10 +220,7 @@ class OverlappedFramePairs(object):
                                      median_win_size=median_win_size)
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
-                                           ransac_solver=ransac_solver, cross_check_stereo=cross_check_stereo,
-                                           cross_check_f2f=cross_check_f2f, gated_stereo=gated_stereo, gated_f2f=gated_f2f,
-                                           gated_max_distance=gated_max_distance, ratio_stereo=ratio_stereo,
-                                           ratio_f2f=ratio_f2f, ratio=ratio)
+                                           ransac_solver=ransac_solver, **opts._asdict())
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -399,9 +369,8 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
     c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
-    c.ransac_flags |= _lib.cross_check_flags(cross_check_stereo, cross_check_f2f)
-    c.ransac_flags |= _lib.gated_flags(gated_stereo, gated_f2f, gated_max_distance)
-    c.ransac_flags |= _lib.ratio_flags(ratio_stereo, ratio_f2f, ratio)
+    c.ransac_flags |= MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                                   ratio_f2f, ratio).flags()
     return c
 
 
@@ -419,9 +388,12 @@ class FramePairBatch(object):
         default capacity (frontend.default_kp_cap)."""
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
-        self.cfg = c = batch_cfg(model, self.B, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                                 thr, max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo,
-                                 cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
+        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio)
+        self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
+                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
+                                 max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
+                                 detection_method=detection_method, **opts._asdict())
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -548,18 +520,14 @@ class _SequenceFamily(object):
 class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
-    def __init__(self, ctx, model, rig, frames, slots, gather, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                 min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method, cross_check_stereo=False,
-                 cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+    def __init__(self, ctx, model, rig, frames, slots, gather, opts, **settings):
+        """opts: a MatchOptions; settings: batch_cfg's tracker settings (num_of_features ... detection_method) but the seed."""
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
-        self.cfg = batch_cfg(model, frames, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                             thr, max_iter, adaptive, 0, lm_iter, ransac_solver, detection_method, cross_check_stereo,
-                             cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
-        self.method = str(detection_method).upper()
-        if str(ransac_solver).upper() not in ("P3P", "GP3P"):
+        self.cfg = batch_cfg(model, frames, seed=0, **settings, **opts._asdict())
+        self.method = str(settings["detection_method"]).upper()
+        if str(settings["ransac_solver"]).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -578,17 +546,14 @@ class _RGBDFamily(_SequenceFamily):
     prefix, track_heads = "rgbd_sequence_", ()
     shared = ("ctx", "cfg", "method", "workspace", "cam_cfg", "cam", "mask_bits", "pattern")
 
-    def __init__(self, ctx, cam, _rig, frames, slots, gather, image_shape, num_of_features, kp_cap, frame_cap, median_win_size,
-                 quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask, pose_est_algorithm, detection_method,
-                 cross_check=False, gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None):
+    def __init__(self, ctx, cam, frames, slots, gather, opts, mask, **settings):
+        """opts: a MatchOptions; settings: rgbd_batch_cfg's tracker settings (image_shape ... detection_method) but the seed."""
         from . import orb_pattern
         assert isinstance(ctx, Context)
         self.cam_cfg, self.cam = cam, cam.as_struct()
         self.heads = (self.cam,)
-        self.cfg = c = rgbd_batch_cfg(cam, frames, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality,
-                                      min_distance, edge, thr, max_iter, adaptive, 0, lm_iter, pose_est_algorithm, detection_method,
-                                      cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
-        self.method = str(detection_method).upper()
+        self.cfg = c = rgbd_batch_cfg(cam, frames, seed=0, **settings, **opts.rgbd_kwargs())
+        self.method = str(settings["detection_method"]).upper()
         rows, cols = c.rows, c.cols
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
         self.mask_bits = torch.from_numpy(mb).to(ctx.device)
@@ -861,10 +826,13 @@ class SequenceEngine(_SequenceBase):
         cross_check_stereo / cross_check_f2f: mutual matches only in the static-stereo / the frame-to-frame matcher.
         gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline."""
         self._init_windows(window)
-        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, num_of_features, kp_cap, frame_cap, median_win_size,
-                                quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver, detection_method,
-                                cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
-                                ratio_stereo, ratio_f2f, ratio))
+        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio)
+        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts,
+                                num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
+                                median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
+                                max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
+                                detection_method=detection_method))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -1010,17 +978,17 @@ class RGBDPairPipeline(object):
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
         self.ref_frame = torch.arange(0, F, 2, dtype=torch.int32, device=dev)
         self.cur_frame = torch.arange(1, F, 2, dtype=torch.int32, device=dev)
-        self.keys, self.order = z((B, Fc, 1), torch.uint32), z((B, Fc), torch.int32)
-        _lib.gated_flags(False, gated_f2f, gated_max_distance)   # (ValueError for a cap out of range)
-        self.gated_f2f, self.gated_max_distance = bool(gated_f2f), gated_max_distance
-        _lib.ratio_flags(False, ratio_f2f, ratio)                 # (ValueError for a ratio that is no 64th)
-        self.ratio_f2f = _lib.ratio_64ths(ratio) if ratio_f2f else 0   # (in 64ths; 0: off)
-        self.cross_check = bool(cross_check)
-        if self.cross_check:   # the B role-swapped problems ride in the same launch, after the forward ones
-            self._q2, self._t2 = torch.cat([self.cur_frame, self.ref_frame]), torch.cat([self.ref_frame, self.cur_frame])
-            self._k2 = z((2 * B, Fc, 1), torch.uint32)
-            self.keys = self._k2[:B]
-        self._rivals = z(((2 if self.cross_check else 1) * B, Fc, 1), torch.uint32) if self.ratio_f2f else None
+        self.order = z((B, Fc), torch.int32)
+        # (ValueError for a cap out of range, a ratio that is no 64th)
+        self.opts = o = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
+        q, t = self.cur_frame, self.ref_frame
+        if o.cross_check_f2f:   # the B role-swapped problems ride in the same launch, after the forward ones
+            q, t = torch.cat([q, t]), torch.cat([t, q])
+        self._q, self._t, self._k = q, t, z((len(q), Fc, 1), torch.uint32)
+        self.cur_frame, self.ref_frame, self.keys = q[:B], t[:B], self._k[:B]     # the forward problems
+        # what track() hands the matching step: the |du| gate of f2f_assemble_central
+        self._f2f_search = dict(ratio_64ths=o.ratio_64ths_f2f, rivals=torch.zeros_like(self._k) if o.ratio_f2f else None,
+                                gate=(-1.0, cam.f2f_max_hdiff, gated_max_distance) if o.gated_f2f else None)
         self.corr = dict(f=z((B, Fc, 3), torch.float64), p=z((B, Fc, 3), torch.float64), q=z((B, Fc), torch.int32),
                          t=z((B, Fc), torch.int32), n=z((B,), torch.int32))
         self.ransac = dict(T=z((B, 3, 4), torch.float64), mask=z((B, Fc), torch.uint8), idx=z((B, Fc), torch.int32),
@@ -1036,20 +1004,7 @@ class RGBDPairPipeline(object):
 
     def track(self):
         c, fr, cfg = self.ctx, self.frames, self.cam_cfg
-        keys, q_slot, t_slot = (self._k2, self._q2, self._t2) if self.cross_check else (self.keys, self.cur_frame, self.ref_frame)
-        if self.ratio_f2f:      # plain or under the |du| gate; the role-swapped second half gets no rule
-            g = dict(q_pos=fr["m"], t_pos=fr["m"], min_dv=-1.0, max_du=cfg.f2f_max_hdiff,
-                     max_distance=self.gated_max_distance) if self.gated_f2f else {}
-            c.match_hamming_ratio(fr["d"], fr["d"], fr["M"], fr["M"], self.ratio_f2f, keys=keys, rivals=self._rivals, q_slot=q_slot,
-                                  t_slot=t_slot, n_forward=self.B, **g)
-        elif self.gated_f2f:    # the |du| gate of f2f_assemble_central; the role-swapped problems are the second half
-            c.match_hamming_gated(fr["d"], fr["d"], fr["m"], fr["m"], fr["M"], fr["M"], min_dv=-1.0, max_du=cfg.f2f_max_hdiff,
-                                  max_distance=self.gated_max_distance, keys=keys, q_slot=q_slot, t_slot=t_slot, n_forward=self.B)
-        else:
-            c.match_hamming(fr["d"], fr["d"], fr["M"], fr["M"], k=1, keys=keys, q_slot=q_slot, t_slot=t_slot)
-        if self.cross_check:
-            c.cross_check_matches(self.keys, self._k2[self.B:], fr["M"], fr["M"], q_slot=self.cur_frame, t_slot=self.ref_frame,
-                                  keys_out=self.keys)
+        c.match_1nn_slots(fr["d"], fr["m"], fr["M"], self._q, self._t, self._k, self.B, **self._f2f_search)
         c.sort_matches(self.keys, fr["M"], order=self.order, q_slot=self.cur_frame)
         c.f2f_assemble_central(fr, self.ref_frame, self.cur_frame, self.keys, self.order, self.frame_cap,
                                pct_good_matches=cfg.pct_good_matches, max_hdiff=cfg.f2f_max_hdiff, out=self.corr)
@@ -1093,9 +1048,8 @@ def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap
     c.kp_cap, c.frame_cap = kp_cap, int(frame_cap) if frame_cap else kp_cap
     c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
     c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags | _lib.cross_check_flags(f2f=cross_check)
-    c.flags |= _lib.gated_flags(False, gated_f2f, gated_max_distance)
-    c.flags |= _lib.ratio_flags(False, ratio_f2f, ratio)
+    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
+    c.flags |= MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio).flags()
     c.quality, c.min_distance = float(quality), float(min_distance)
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
@@ -1114,9 +1068,12 @@ class RGBDPairBatch(object):
         from . import orb_pattern
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
-        c = rgbd_batch_cfg(cam, self.B, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance,
-                           edge, thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check, gated_f2f,
-                           gated_max_distance, ratio_f2f, ratio)
+        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
+        c = rgbd_batch_cfg(cam, self.B, seed=seed, image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
+                           frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                           edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                           pose_est_algorithm=pose_est_algorithm, detection_method=detection_method,
+                           **opts.rgbd_kwargs())
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         self.cfg, self.thr = c, c.ransac_threshold
@@ -1157,9 +1114,12 @@ class RGBDSequenceEngine(_SequenceBase):
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
                  gated_max_distance=None, ratio_f2f=False, ratio=None):
         self._init_windows(window)
-        self._adopt(_RGBDFamily(ctx, cam, None, self.W, self.slots, False, image_shape, num_of_features, kp_cap, frame_cap,
-                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio))
+        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
+        self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, opts, mask,
+                                image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
+                                frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                                edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                                pose_est_algorithm=pose_est_algorithm, detection_method=detection_method))
 
 
 # ---- several sequences ("lanes") through one engine ----------------------------------------------------------------------
@@ -1489,10 +1449,13 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
                  ratio_f2f=False, ratio=None):
         self._init_lanes(lanes, window)
-        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, num_of_features, kp_cap, frame_cap,
-                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, ransac_solver,
-                                detection_method, cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
-                                ratio_stereo, ratio_f2f, ratio))
+        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio)
+        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts,
+                                num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
+                                median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
+                                max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
+                                detection_method=detection_method))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
@@ -1504,6 +1467,9 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
                  gated_max_distance=None, ratio_f2f=False, ratio=None):
         self._init_lanes(lanes, window)
-        self._adopt(_RGBDFamily(ctx, cam, None, self.window, self.slots, True, image_shape, num_of_features, kp_cap, frame_cap,
-                                median_win_size, quality, min_distance, edge, thr, max_iter, adaptive, lm_iter, mask,
-                                pose_est_algorithm, detection_method, cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio))
+        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
+        self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, opts, mask,
+                                image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
+                                frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                                edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                                pose_est_algorithm=pose_est_algorithm, detection_method=detection_method))
