@@ -212,9 +212,9 @@ def fuzz_match(ctx, rng):
 
 def fuzz_cross_check(ctx, rng):
     """The mutual-consistency filter (sosvo_cross_check_matches on the keys of two sosvo_match_hamming calls, then the sort)
-    against the composition of oracle calls: query i keeps its best train j iff the best query of j is i.  Sizes 0 and 1, the
+    against the definition (tests/refmatch.py): query i keeps its best train j iff the best query of j is i.  Sizes 0 and 1, the
     32-query / 128-train tile edges of the matcher, and half of the cases through slot tables over one descriptor store."""
-    NONE, IDX = 0xFFFFFFFF, 0xFFFFF
+    from refmatch import NONE, Matching
     sizes = [0, 1, 2, 31, 32, 33, 127, 128, 129, 255, 257, 300]
     slots = rng.random() < 0.5
     if slots:            # a store of blocks, problems = (query block, train block) pairs, a block may meet itself
@@ -251,11 +251,7 @@ def fuzz_cross_check(ctx, rng):
     out, n_kept, order = out.cpu().numpy()[:, :, 0], n_kept.cpu().numpy(), order.cpu().numpy()
     for p in range(P):
         n, m = int(nq[qs[p]]), int(nt[ts[p]])
-        want = np.full(n, NONE, np.uint32)
-        if n and m:
-            f = oracle.match_hamming(q[qs[p], :n], t[ts[p], :m], k=1)[:, 0]
-            r = oracle.match_hamming(t[ts[p], :m], q[qs[p], :n], k=1)[:, 0]
-            want = np.where((r[f & IDX] & IDX) == np.arange(n), f, np.uint32(NONE)).astype(np.uint32)
+        want = Matching(mutual=True).kept(q[qs[p], :n], t[ts[p], :m], None, None, None)
         if not np.array_equal(out[p, :n], want):
             return params, "problem %d: keys" % p
         if n_kept[p] != int((want != NONE).sum()):
@@ -266,14 +262,13 @@ def fuzz_cross_check(ctx, rng):
 
 
 def fuzz_gated_match(ctx, rng):
-    """sosvo_match_hamming_gated against its definition in numpy: key(i) = min over the trains j that pass
+    """sosvo_match_hamming_gated against its definition in numpy (tests/refmatch.py): key(i) = min over the trains j that pass
     oracle.pixel_gates (on the float32 positions converted to double) of (hamming << 20 | j), SOSVO_KEY_NONE without one or
     when the winner's distance exceeds the cap; then the sort.  Random sizes around the 32-query / 128-train tile edges, gates
     with either side disabled, limits that sit exactly on a position difference, caps 0 .. 256, half of the cases through
     slot tables over one store, a random share of the problems reversed (the role-swapped problems of a cross-checked
     step).  With both sides disabled and no cap the keys must also be those of sosvo_match_hamming."""
-    NONE = 0xFFFFFFFF
-    popcount = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
+    from refmatch import Matching
     sizes = [0, 1, 2, 31, 32, 33, 127, 128, 129, 255, 257, 300]
     slots = rng.random() < 0.5
     if slots:
@@ -319,15 +314,8 @@ def fuzz_gated_match(ctx, rng):
     keys, order = keys.cpu().numpy()[:, :, 0], order.cpu().numpy()
     for p in range(P):
         n, m = int(nq[qs[p]]), int(nt[ts[p]])
-        want = np.full(n, NONE, np.uint32)
-        if n and m:
-            qd, td = q[qs[p], :n], t[ts[p], :m]
-            a = np.repeat(qp[qs[p], :n].astype(np.float64)[:, None], m, 1).reshape(-1, 2)
-            b = np.repeat(tp[ts[p], :m].astype(np.float64)[None], n, 0).reshape(-1, 2)
-            ok = (oracle.pixel_gates(a, b, min_dv, max_du) if p >= n_forward else oracle.pixel_gates(b, a, min_dv, max_du)).reshape(n, m)
-            k = (popcount[qd[:, None, :] ^ td[None, :, :]].sum(-1, dtype=np.uint32) << 20) | np.arange(m, dtype=np.uint32)[None]
-            want = np.where(ok, k, np.uint32(NONE)).min(1).astype(np.uint32)
-            want[(want >> 20) > (256 if cap is None else cap)] = NONE
+        want = Matching(gated=True, cap=cap).keys(q[qs[p], :n], t[ts[p], :m], qp[qs[p], :n], tp[ts[p], :m], (min_dv, max_du),
+                                                  reverse=p >= n_forward)
         if not np.array_equal(keys[p, :n], want):
             return params, "problem %d: keys" % p
         if not np.array_equal(order[p, :n], oracle.sort_matches(want)):

@@ -33,16 +33,22 @@ def match_sorted(query_desc, train_desc):
     return order.astype(np.int64), (keys[order] & IDX).astype(np.int64), (keys[order] >> 20).astype(np.int64)
 
 
-def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot):
+def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot, *, matching=None):
     """match_features_panoramic_top_bottom (camera_models.py:3027-3101) followed by
     establish_stereo_correspondences (pose_est_tools.py:339-397).  kp_* / desc_*: lists over buckets of
-    [n,2] float32 / [n,32] uint8.  -> dict of arrays in the reference's order."""
+    [n,2] float32 / [n,32] uint8.  -> dict of arrays in the reference's order.
+    matching: None for the reference's matcher, or the step's matcher under other options: a callable (query_desc, train_desc,
+    query_pos, train_pos, gate) -> match_sorted's triple, gate = the step's pixel gate (min_dv, max_du), with an attribute
+    `gated` (tests/refmatch.py).  A gated one has searched under the gate already, so the gate below passes all it sees."""
     mt, mb, dt, db = [], [], [], []
     n_cand = 0
     for kt, kb, et, eb in zip(kp_top, kp_bot, desc_top, desc_bot):
         if len(kt) == 0 or len(kb) == 0:  # :3039
             continue
-        q, t, _ = match_sorted(eb, et)  # query = bottom, train = top (:3042)
+        if matching is None:
+            q, t, _ = match_sorted(eb, et)  # query = bottom, train = top (:3042)
+        else:
+            q, t, _ = matching(eb, et, kb, kt, (rig.stereo_min_disp, rig.stereo_max_hdiff))
         good = int(rig.pct_good_matches * len(q))  # :3045
         q, t = q[:good], t[:good]
         n_cand += good
@@ -57,6 +63,8 @@ def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot):
     dt, db = np.concatenate(dt), np.concatenate(db)
     ok = oracle.pixel_gates(mt.astype(np.float64), mb.astype(np.float64), rig.stereo_min_disp,
                             rig.stereo_max_hdiff)  # :3086
+    if matching is not None and matching.gated:
+        assert ok.all()
     mt, mb, dt, db = mt[ok], mb[ok], dt[ok], db[ok]
     az1, el1 = oracle.pano_to_angles(mt[:, 0], mt[:, 1], *rig.pano_top)  # pose_est_tools.py:344
     az2, el2 = oracle.pano_to_angles(mb[:, 0], mb[:, 1], *rig.pano_bot)  # :345
@@ -90,9 +98,14 @@ def frame_from_image(rig, im, omni):
     return fr
 
 
-def f2f_view(rig, m_train, d_train, m_query, d_query):
-    """match_features_frame_to_frame (pose_est_tools.py:211-269) for one view -> (train_idx, query_idx)."""
-    q, t, _ = match_sorted(d_query, d_train)  # query = current, train = reference (:215)
+def f2f_view(rig, m_train, d_train, m_query, d_query, *, matching=None):
+    """match_features_frame_to_frame (pose_est_tools.py:211-269) for one view -> (train_idx, query_idx).
+    matching: as in stereo_frame; its gate is off exactly when the view's own |du| gate is."""
+    if matching is None:
+        q, t, _ = match_sorted(d_query, d_train)  # query = current, train = reference (:215)
+    else:
+        q, t, _ = matching(d_query, d_train, np.asarray(m_query, np.float32)[:, :2], np.asarray(m_train, np.float32)[:, :2],
+                           (-1.0, rig.f2f_max_hdiff if rig.f2f_max_hdiff >= 0 else -1.0))
     good = int(rig.pct_good_matches * len(q))  # :225
     q, t = q[:good], t[:good]
     if good > 0 and rig.f2f_max_hdiff >= 0:  # :245
@@ -101,15 +114,17 @@ def f2f_view(rig, m_train, d_train, m_query, d_query):
         pt[:, 0] = m_train[t, 0]
         pq[:, 0] = m_query[q, 0]
         ok = oracle.pixel_gates(pt, pq, -1, rig.f2f_max_hdiff)  # :247
+        if matching is not None and matching.gated:
+            assert ok.all()
         q, t = q[ok], t[ok]
     return t, q
 
 
-def track_inputs(rig, ref, cur):
+def track_inputs(rig, ref, cur, *, matching=None):
     """Correspondence stacking of TrackerStereoSE3.track_frame (pose_est_tools.py:741-778).
     ref / cur: dicts from stereo_frame.  -> f [n,3], p [n,3], cam [n], (q, t) index arrays, n_top."""
-    t_top, q_top = f2f_view(rig, ref["m_top"], ref["d_top"], cur["m_top"], cur["d_top"])
-    t_bot, q_bot = f2f_view(rig, ref["m_bot"], ref["d_bot"], cur["m_bot"], cur["d_bot"])
+    t_top, q_top = f2f_view(rig, ref["m_top"], ref["d_top"], cur["m_top"], cur["d_top"], matching=matching)
+    t_bot, q_bot = f2f_view(rig, ref["m_bot"], ref["d_bot"], cur["m_bot"], cur["d_bot"], matching=matching)
     f = np.vstack([cur["b_top"][q_top], cur["b_bot"][q_bot]])
     p = np.vstack([ref["X"][t_top], ref["X"][t_bot]])
     cam = np.concatenate([np.zeros(len(q_top), np.int32), np.ones(len(q_bot), np.int32)])
@@ -117,9 +132,9 @@ def track_inputs(rig, ref, cur):
                 n_top=len(q_top))
 
 
-def track_pair(rig, ref, cur, thr, max_iter, seed, adaptive=False, lm_iter=30, gp3p=False):
+def track_pair(rig, ref, cur, thr, max_iter, seed, adaptive=False, lm_iter=30, gp3p=False, *, matching=None):
     """track_frame steps 3-4 (pose_est_tools.py:785, :830) on the oracle: RANSAC + LM on the inliers."""
-    c = track_inputs(rig, ref, cur)
+    c = track_inputs(rig, ref, cur, matching=matching)
     cam_off = np.stack([rig.F_top, rig.F_bot])
     cam_rot = np.stack([np.eye(3), np.eye(3)])
     r = oracle.ransac_abs_pose(c["f"], c["p"], thr, max_iter, seed=seed, adaptive=adaptive, cam=c["cam"],
@@ -144,10 +159,11 @@ class RGBDParams(object):
         self.f2f_max_hdiff, self.pct_good_matches = f2f_max_hdiff, pct_good_matches
 
 
-def track_pair_rgbd(cam, ref, cur, thr, max_iter, seed, adaptive=False, lm_iter=30, epnp=True, gp3p=False, twopt=False):
+def track_pair_rgbd(cam, ref, cur, thr, max_iter, seed, adaptive=False, lm_iter=30, epnp=True, gp3p=False, twopt=False, *,
+                    matching=None):
     """TrackerRGBDSE3.track_frame (pose_est_tools.py:896-954) on the oracle: frame-to-frame matches, central
     RANSAC (:915), LM on the inliers (:937)."""
-    t, q = f2f_view(cam, ref["m"], ref["d"], cur["m"], cur["d"])
+    t, q = f2f_view(cam, ref["m"], ref["d"], cur["m"], cur["d"], matching=matching)
     f, p = cur["b"][q], ref["X"][t]
     r = oracle.ransac_abs_pose(f, p, thr, max_iter, seed=seed, adaptive=adaptive, epnp=epnp, gp3p=gp3p, twopt=twopt)
     idx = np.nonzero(r["mask"])[0].astype(np.int32)

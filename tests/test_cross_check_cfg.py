@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+from cfg_fakes import Engine, Rig, cfg, lib_or_skip, rgbd_cam, rgbd_cfg, tracker
 from vo_single_camera_sos_amd import _lib
 from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
 from vo_single_camera_sos_amd.pipeline import batch_cfg, rgbd_batch_cfg, rgbd_solver_flags
@@ -76,60 +77,38 @@ def test_the_cfg_builders_set_the_bits():
     assert r_off.flags == _lib.FLAG_EPNP | _lib.rgbd_detector_flags("ORB") and r_on.flags == r_off.flags | F2F
 
 
-def _lib_or_skip():
-    try:
-        return _lib.load()
-    except Exception as e:  # noqa: BLE001 -- the library is not built on this machine
-        pytest.skip("libsosvo.so does not load here: %s" % e)
-
-
-def _cfg(flags, detector=0, n_pairs=4):
-    c = _lib.BatchCfg()
-    c.n_pairs, c.H, c.W, c.rows, c.cols, c.nmask = n_pairs, 480, 640, 300, 1200, 12
-    c.kp_cap, c.frame_cap, c.median_ksize, c.max_corners, c.edge = 1024, 2048, 11, 1000, 31
-    c.detector, c.ransac_flags = detector, flags
-    return c
-
-
-def _rgbd_cfg(flags, method="GFT", n_pairs=4):
-    c = _lib.RgbdBatchCfg()
-    c.n_pairs, c.rows, c.cols, c.kp_cap, c.frame_cap, c.max_corners, c.edge = n_pairs, 480, 640, 1088, 1088, 1000, 31
-    c.flags = _lib.FLAG_EPNP | _lib.rgbd_detector_flags(method) | flags
-    return c
-
-
 def test_workspaces_grow_only_with_a_switch_set():
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     r = ctypes.byref
     queries = (lambda c: lib.sosvo_frame_pair_batch_workspace(r(c)),
                lambda c: lib.sosvo_frame_pair_batch_streams_workspace(r(c), 2),
                lambda c: lib.sosvo_sequence_workspace(r(c), 8, 17))
     for det in (0, 1):
         for q in queries:
-            base = q(_cfg(0, det))
-            assert base > 0 and q(_cfg(_lib.FLAG_GP3P, det)) == base          # the solver bit alone changes nothing
-            sizes = [q(_cfg(f, det)) for f in (STEREO, F2F, STEREO | F2F)]
+            base = q(cfg(0, det))
+            assert base > 0 and q(cfg(_lib.FLAG_GP3P, det)) == base          # the solver bit alone changes nothing
+            sizes = [q(cfg(f, det)) for f in (STEREO, F2F, STEREO | F2F)]
             assert all(s >= base for s in sizes) and sizes[0] > base and sizes[1] > base
             assert sizes[2] - base == (sizes[0] - base) + (sizes[1] - base)   # the two switches' buffers are independent
     # what a switch adds to the pair batch: the reverse keys (one u32 per forward key) and two slot tables of 2 n i32
-    c = _cfg(0)
+    c = cfg(0)
     F, B = 2 * c.n_pairs, c.n_pairs
     pad = lambda n: (n + 255) & ~255  # noqa: E731
     h = F * c.nmask
     ws = queries[0]
-    assert ws(_cfg(STEREO)) - ws(c) == pad(2 * h * c.kp_cap * 4) - pad(h * c.kp_cap * 4) + 2 * pad(2 * h * 4)
-    assert ws(_cfg(F2F)) - ws(c) == 2 * (pad(2 * B * c.frame_cap * 4) - pad(B * c.frame_cap * 4)) + 2 * pad(2 * B * 4)
+    assert ws(cfg(STEREO)) - ws(c) == pad(2 * h * c.kp_cap * 4) - pad(h * c.kp_cap * 4) + 2 * pad(2 * h * 4)
+    assert ws(cfg(F2F)) - ws(c) == 2 * (pad(2 * B * c.frame_cap * 4) - pad(B * c.frame_cap * 4)) + 2 * pad(2 * B * 4)
     rqueries = (lambda c: lib.sosvo_rgbd_pair_batch_workspace(r(c)), lambda c: lib.sosvo_rgbd_sequence_workspace(r(c), 8, 17))
     for method in ("GFT", "ORB"):
         for q in rqueries:
-            base = q(_rgbd_cfg(0, method))
-            assert q(_rgbd_cfg(F2F, method)) > base > 0
+            base = q(rgbd_cfg(0, method))
+            assert q(rgbd_cfg(F2F, method)) > base > 0
             # an RGB-D camera has no static stereo: SOSVO_ERR_ARG in the calls, 0 here
-            assert q(_rgbd_cfg(STEREO, method)) == 0 and q(_rgbd_cfg(STEREO | F2F, method)) == 0
+            assert q(rgbd_cfg(STEREO, method)) == 0 and q(rgbd_cfg(STEREO | F2F, method)) == 0
 
 
 def test_the_stage_entry_refuses_null_arguments_before_touching_the_device():
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     # (a NULL context is refused first; with a context, NULL keys are SOSVO_ERR_ARG -- tests/test_gpu_abi_errors.py walks it)
     rc = lib.sosvo_cross_check_matches(None, None, None, None, None, None, None, 1, 8, 8, None, None)
     assert rc == -1, rc
@@ -184,74 +163,15 @@ def test_every_driver_takes_cross_check():
         assert inspect.signature(cls.__init__).parameters["cross_check"].default is False, cls.__name__
 
 
-class _Engine(object):
-    def __init__(self, *args, **kwargs):
-        self.args, self.kwargs, self.resets = args, kwargs, 0
-        self._error, self._live = None, 0
-
-    def reset(self):
-        self.resets += 1
-
-    def reset_counters(self):
-        self.resets += 1
-
-
-def _tracker(rgbd):
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import TrackerSE3
-    t = TrackerSE3.__new__(TrackerSE3)
-    t.set_global_parameters_for_tracking()
-    t.num_features_detection_for_static_stereo = 1000
-    t.max_horizontal_diff_f2f_matches = 37.5
-    if not rgbd:
-        t.cam_rotations = np.array([np.identity(3), np.identity(3)])
-        t.cam_offsets = np.array([[0.0, 0.0, 10.0], [0.0, 0.0, -10.0]])
-    return t
-
-
-class _Pano(object):
-    cols, rows, pixel_size, cyl_height_max = 1200, 300, 0.01, 1.0
-
-
-class _Mirror(object):
-    def __init__(self, z):
-        self.F = np.array([[0.0], [0.0], [z], [1.0]])
-        self.panorama = _Pano()
-
-
-class _Rig(object):
-    units = "mm"
-
-    def __init__(self):
-        self.top_model, self.bot_model = _Mirror(10.0), _Mirror(-10.0)
-        self.current_omni_img = None
-        self.feature_matcher_for_static_stereo = FeatureMatcher("GFT", "BF", 1)
-        self.feature_matcher_for_motion = FeatureMatcher("GFT", "BF", 1)
-        self.model = object()
-
-    def _device_model(self):
-        return self.model
-
-    def _context(self):
-        return "ctx"
-
-
-def _rgbd_cam():
-    from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
-    cam = RGBDCamModel()
-    cam.feature_matcher_for_motion = FeatureMatcher("GFT", "BF", 1)
-    cam._context = lambda: "ctx"
-    return cam
-
-
 def test_the_trackers_start_with_the_switches_off():
-    t = _tracker(rgbd=False)
+    t = tracker(rgbd=False)
     assert t.cross_check_static_stereo is False and t.cross_check_for_motion is False
 
 
 def test_set_cross_check_switches_the_matchers():
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    t = _tracker(rgbd=False)
-    t.camera_model = rig = _Rig()
+    t = tracker(rgbd=False)
+    t.camera_model = rig = Rig()
     pet.set_cross_check(t, None)
     assert (rig.feature_matcher_for_static_stereo.cross_check, rig.feature_matcher_for_motion.cross_check) == (False, False)
     for value, want in ((True, (True, True)), ("stereo", (True, False)), ("f2f", (False, True)), (False, (False, False))):
@@ -270,8 +190,8 @@ def test_set_cross_check_switches_the_matchers():
         pet.set_cross_check(t, "f2f")
     assert (rig.feature_matcher_for_static_stereo.cross_check, rig.feature_matcher_for_motion.cross_check) == (True, False)
     assert (t.cross_check_static_stereo, t.cross_check_for_motion) == (True, False)
-    r = _tracker(rgbd=True)
-    r.camera_model = cam = _rgbd_cam()
+    r = tracker(rgbd=True)
+    r.camera_model = cam = rgbd_cam()
     pet.set_cross_check(r, True)                             # both matchers = the one an RGB-D tracker has
     assert cam.feature_matcher_for_motion.cross_check is True and r.cross_check_static_stereo is False
     with pytest.raises(ValueError, match="static-stereo"):
@@ -281,10 +201,10 @@ def test_set_cross_check_switches_the_matchers():
 def test_the_engine_cache_key_distinguishes_the_switches(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "SequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "MultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=False)
-    t.camera_model = rig = _Rig()
+    monkeypatch.setattr(pipeline, "SequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "MultiSequenceEngine", Engine)
+    t = tracker(rgbd=False)
+    t.camera_model = rig = Rig()
     img = np.zeros((4, 4, 3), np.uint8)
     seen, keys = {}, set()
     for value in (False, "stereo", "f2f", True):
@@ -305,10 +225,10 @@ def test_the_engine_cache_key_distinguishes_the_switches(monkeypatch):
 def test_the_rgbd_engine_cache_key_distinguishes_the_switch(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=True)
-    t.camera_model = cam = _rgbd_cam()
+    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", Engine)
+    t = tracker(rgbd=True)
+    t.camera_model = cam = rgbd_cam()
     img = np.zeros((480, 640, 3), np.uint8)
     off = pet.rgbd_sequence_engine_for(t, cam, img, 8)
     assert off.kwargs["cross_check"] is False

@@ -11,7 +11,7 @@ import re
 import numpy as np
 import pytest
 
-from test_cross_check_cfg import _Engine, _Rig, _cfg, _lib_or_skip, _rgbd_cam, _rgbd_cfg, _tracker
+from cfg_fakes import Engine, Rig, cfg, lib_or_skip, rgbd_cam, rgbd_cfg, tracker
 from vo_single_camera_sos_amd import _lib
 from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
 from vo_single_camera_sos_amd.pipeline import batch_cfg, rgbd_batch_cfg, rgbd_solver_flags
@@ -97,7 +97,7 @@ def test_workspaces_do_not_depend_on_the_bits():
     """The gated search reads the keypoint positions the stores hold anyway and writes the keys the plain search writes:
     with the cross-check bits clear every workspace keeps its size, and combined with them it is the size cross-check alone
     asks for (the reverse problems' keys and slot tables)."""
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     r = ctypes.byref
     queries = (lambda c: lib.sosvo_frame_pair_batch_workspace(r(c)),
                lambda c: lib.sosvo_frame_pair_batch_streams_workspace(r(c), 2),
@@ -105,24 +105,24 @@ def test_workspaces_do_not_depend_on_the_bits():
     gated = (STEREO, F2F, STEREO | F2F, STEREO | F2F | (80 << SHIFT), 256 << SHIFT)
     for det in (0, 1):
         for q in queries:
-            base = q(_cfg(0, det))
+            base = q(cfg(0, det))
             assert base > 0
             for g in gated:
-                assert q(_cfg(g, det)) == base, (det, hex(g))
+                assert q(cfg(g, det)) == base, (det, hex(g))
                 for cc in (CC_STEREO, CC_F2F, CC_STEREO | CC_F2F):
-                    assert q(_cfg(g | cc, det)) == q(_cfg(cc, det)) > base, (det, hex(g), hex(cc))
+                    assert q(cfg(g | cc, det)) == q(cfg(cc, det)) > base, (det, hex(g), hex(cc))
     rqueries = (lambda c: lib.sosvo_rgbd_pair_batch_workspace(r(c)), lambda c: lib.sosvo_rgbd_sequence_workspace(r(c), 8, 17))
     for method in ("GFT", "ORB"):
         for q in rqueries:
-            base = q(_rgbd_cfg(0, method))
-            assert base > 0 and q(_rgbd_cfg(F2F, method)) == base and q(_rgbd_cfg(F2F | (64 << SHIFT), method)) == base
-            assert q(_rgbd_cfg(F2F | CC_F2F, method)) == q(_rgbd_cfg(CC_F2F, method)) > base
+            base = q(rgbd_cfg(0, method))
+            assert base > 0 and q(rgbd_cfg(F2F, method)) == base and q(rgbd_cfg(F2F | (64 << SHIFT), method)) == base
+            assert q(rgbd_cfg(F2F | CC_F2F, method)) == q(rgbd_cfg(CC_F2F, method)) > base
             # an RGB-D camera has no static stereo: SOSVO_ERR_ARG in the calls, 0 here
-            assert q(_rgbd_cfg(STEREO, method)) == 0 and q(_rgbd_cfg(STEREO | F2F, method)) == 0
+            assert q(rgbd_cfg(STEREO, method)) == 0 and q(rgbd_cfg(STEREO | F2F, method)) == 0
 
 
 def test_the_stage_entry_refuses_a_null_context():
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     # (with a context, NULL buffers are SOSVO_ERR_ARG -- tests/test_gpu_abi_errors.py walks it)
     rc = lib.sosvo_match_hamming_gated(None, None, None, None, None, None, None, None, None, 1, 1, 8, 8, 1.0, 2.5, 256, None)
     assert rc == -1, rc
@@ -180,9 +180,9 @@ def test_every_driver_and_engine_takes_the_arguments():
 
 def test_set_gated_matching_switches_the_matchers():
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    t = _tracker(rgbd=False)
+    t = tracker(rgbd=False)
     assert (t.gated_static_stereo, t.gated_for_motion, t.gated_max_distance) == (False, False, None)
-    t.camera_model = rig = _Rig()
+    t.camera_model = rig = Rig()
     fms, fmm = rig.feature_matcher_for_static_stereo, rig.feature_matcher_for_motion
     pet.set_gated_matching(t, None, 80)                      # None: the tracker's own setting, whatever the cap says
     assert (fms.gated, fmm.gated, fms.gated_max_distance) == (False, False, None)
@@ -215,8 +215,8 @@ def test_set_gated_matching_switches_the_matchers():
     with pytest.raises(ValueError, match="k_best"):
         pet.set_gated_matching(t, "f2f")
     assert state() == before
-    r = _tracker(rgbd=True)
-    r.camera_model = cam = _rgbd_cam()
+    r = tracker(rgbd=True)
+    r.camera_model = cam = rgbd_cam()
     pet.set_gated_matching(r, True, 100)                     # both matchers = the one an RGB-D tracker has
     assert cam.feature_matcher_for_motion.gated is True and cam.feature_matcher_for_motion.gated_max_distance == 100
     assert r.gated_static_stereo is False
@@ -227,10 +227,10 @@ def test_set_gated_matching_switches_the_matchers():
 def test_the_engine_cache_key_distinguishes_the_settings(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "SequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "MultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=False)
-    t.camera_model = rig = _Rig()
+    monkeypatch.setattr(pipeline, "SequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "MultiSequenceEngine", Engine)
+    t = tracker(rgbd=False)
+    t.camera_model = rig = Rig()
     img = np.zeros((4, 4, 3), np.uint8)
     seen, keys = [], set()
     settings = [(False, None), ("stereo", None), ("f2f", None), (True, None), (True, 80), (True, 64), ("f2f", 80)]
@@ -257,10 +257,10 @@ def test_the_engine_cache_key_distinguishes_the_settings(monkeypatch):
 def test_the_rgbd_engine_cache_key_distinguishes_the_settings(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=True)
-    t.camera_model = cam = _rgbd_cam()
+    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", Engine)
+    t = tracker(rgbd=True)
+    t.camera_model = cam = rgbd_cam()
     img = np.zeros((480, 640, 3), np.uint8)
     off = pet.rgbd_sequence_engine_for(t, cam, img, 8)
     assert off.kwargs["gated_f2f"] is False and off.kwargs["gated_max_distance"] is None

@@ -3,74 +3,30 @@ reference carries commented out at omnistereo/camera_models.py:401 -- through ev
 (sosvo_cross_check_matches), FeatureMatcher, the pair pipelines and one-call batches, the sequence engines behind run_VO /
 run_VO_many, and what the filter is for.
 
-The CPU checker is a composition of existing oracle calls (mutual_keep below): query i keeps its best train j iff the best
-query of j, found by the same search with the roles swapped, is i.  refflow.stereo_frame / f2f_view look match_sorted up in
-their module, so the reference flow runs with the mutual matcher in either stage (mutual_matching below).  Everything is
-compared bit for bit or byte for byte; the mirror path (frame_window 0) to 1e-6, as the existing sequence tests compare it."""
-import contextlib
+The CPU checker is the definition (tests/refmatch.py, Matching(mutual=True)): query i keeps its best train j iff the best
+query of j, found by the same search with the roles swapped, is i.  refflow's flow functions take it as the matcher of either
+stage (matching_scenes.Setting.matchings).  Everything is compared bit for bit or byte for byte; the mirror path
+(frame_window 0) to 1e-6, as the existing sequence tests compare it."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import matching_scenes as scenes
 import oracle
 import refflow
 import synth
-from vo_single_camera_sos_amd import orb_pattern, synthetic
+from matching_scenes import CX, CY, FX, FY, N_SEQ, Setting, dev as _dev, read_results, rgbd_kwargs, sos_kwargs
+from refmatch import IDX, NONE, Matching
+from vo_single_camera_sos_amd import synthetic
 from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
 from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
-from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
-from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
-from vo_single_camera_sos_amd.pipeline import (FramePairBatch, FramePairPipeline, RGBDCamConfig, RGBDPairBatch, RGBDPairPipeline,
-                                               RigConfig)
+from vo_single_camera_sos_amd.pipeline import FramePairBatch, FramePairPipeline, RGBDPairBatch, RGBDPairPipeline, RigConfig
 
 pytestmark = pytest.mark.gpu
 
-IDX, NONE = 0xFFFFF, 0xFFFFFFFF
-FILES = ("estimated_frame_poses_TUM.txt", "keyframe_ids.txt")
-
-
-# ---- the oracle composition ----------------------------------------------------------------------------------------------
-def mutual_keep(q, t):
-    """-> (forward keys [nq] u32, keep [nq] bool) of one problem; empty sets keep nothing."""
-    if len(q) == 0 or len(t) == 0:
-        return np.full(len(q), NONE, np.uint32), np.zeros(len(q), bool)
-    fwd = oracle.match_hamming(q, t, k=1)[:, 0]
-    rev = oracle.match_hamming(t, q, k=1)[:, 0]
-    return fwd, (rev[fwd & IDX] & IDX) == np.arange(len(q))
-
-
-def mutual_match_sorted(query_desc, train_desc):
-    """refflow.match_sorted on the kept matches alone."""
-    fwd, keep = mutual_keep(query_desc, train_desc)
-    kept = np.nonzero(keep)[0]
-    if len(kept) == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return z, z, z
-    keys = fwd[kept]
-    order = oracle.sort_matches(keys)          # stable: ties keep the order of `kept`, which is query order
-    return kept[order].astype(np.int64), (keys[order] & IDX).astype(np.int64), (keys[order] >> 20).astype(np.int64)
-
-
-@contextlib.contextmanager
-def mutual_matching(stereo, f2f):
-    """refflow with the mutual matcher in static stereo (stereo_frame) and / or frame to frame (f2f_view) only."""
-    plain, stereo_frame, f2f_view = refflow.match_sorted, refflow.stereo_frame, refflow.f2f_view
-
-    def staged(fn, on):
-        def run(*args, **kwargs):
-            refflow.match_sorted = mutual_match_sorted if on else plain
-            try:
-                return fn(*args, **kwargs)
-            finally:
-                refflow.match_sorted = plain
-        return run
-    refflow.stereo_frame, refflow.f2f_view = staged(stereo_frame, stereo), staged(f2f_view, f2f)
-    try:
-        yield
-    finally:
-        refflow.match_sorted, refflow.stereo_frame, refflow.f2f_view = plain, stereo_frame, f2f_view
+MUTUAL = Matching(mutual=True)
 
 
 def _descriptors(rng, nq, nt, stride):
@@ -87,10 +43,6 @@ def _descriptors(rng, nq, nt, stride):
                 d[b >> 3] ^= np.uint8(1 << (b & 7))
             q[i] = d
     return q, t
-
-
-def _dev(ctx, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
 
 
 def _check_stage(ctx, q, t, nq, nt, q_slot=None, t_slot=None):
@@ -114,13 +66,13 @@ def _check_stage(ctx, q, t, nq, nt, q_slot=None, t_slot=None):
     for p in range(P):
         n = int(nq[qs[p]])
         qd, td = q[qs[p], :n], t[ts[p], : int(nt[ts[p]])]
-        f, keep = mutual_keep(qd, td)
-        want = np.where(keep, f, np.uint32(NONE)).astype(np.uint32)
+        want = MUTUAL.kept(qd, td, None, None, None)
+        kept = int((want != NONE).sum())
         assert np.array_equal(out_h[p, :n], want), p
         assert np.array_equal(out2_h[p, :n], want), p
-        assert int(n_kept.cpu().numpy()[p]) == int(keep.sum()), p
+        assert int(n_kept.cpu().numpy()[p]) == kept, p
         assert np.array_equal(order_h[p, :n], oracle.sort_matches(want)), p
-        assert np.array_equal(order_h[p, : int(keep.sum())], mutual_match_sorted(qd, td)[0]), p
+        assert np.array_equal(order_h[p, :kept], MUTUAL(qd, td, None, None, None)[0]), p
     return out_h
 
 
@@ -173,7 +125,7 @@ def test_feature_matcher_cross_check(ctx):
     plain = FeatureMatcher("ORB", "BF", 1, context=ctx).match(q, t)
     fm = FeatureMatcher("ORB", "BF", 1, context=ctx, cross_check=True)
     got = fm.match(q, t)
-    wq, wt, wd = mutual_match_sorted(q, t)
+    wq, wt, wd = MUTUAL(q, t, None, None, None)
     assert 0 < len(wq) < 300
     assert np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
     assert [m.queryIdx for m in got] == list(wq) and [m.trainIdx for m in got] == list(wt)
@@ -183,70 +135,46 @@ def test_feature_matcher_cross_check(ctx):
     # the batched form the mirror path's static stereo uses, with an empty bucket
     many = fm.match_arrays_many([(q, t), (q[:0], t), (q[:40], t[:1])])
     assert np.array_equal(many[0][0], wq) and np.array_equal(many[0][1], wt) and len(many[1][0]) == 0
-    assert np.array_equal(many[2][0], mutual_match_sorted(q[:40], t[:1])[0]) and len(many[2][0]) == 1
+    assert np.array_equal(many[2][0], MUTUAL(q[:40], t[:1], None, None, None)[0]) and len(many[2][0]) == 1
     assert len(fm.match(q, t[:0])) == 0
 
 
 # ---- 3 / 4. the pair path against refflow, and the one-call forms ---------------------------------------------------------
-SETTINGS = {"stereo": (True, False), "f2f": (False, True), "both": (True, True)}
-
-
-def _rig():
-    gs = synthetic_gums()
-    for m in (gs.top_model, gs.bot_model):
-        m.panorama = Panorama(m, width=1200)
-    gs.make_annulus_masks((480, 640))
-    pano = gs.top_model.panorama
-    geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
-    rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
-                  max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
-                  pct_good_matches=1.0)
-    return gs, rig_kw
-
-
-class _Pairs(object):
-    pass
+SETTINGS = {name: Setting(name, cc=name) for name in ("stereo", "f2f", "both")}
+OFF = Setting("off")
 
 
 @pytest.fixture(scope="module")
 def pairs(ctx):
     """3 rendered pairs as in test_full_hot_path_from_images (GFT 330 features, one black frame): the front end on the GPU,
-    the detection on the oracle (once, shared), and the stage-by-stage records per switch setting."""
-    s = _Pairs()
-    s.B, s.nfeat, s.iters, s.seed = 3, 330, 500, 5
-    gs, s.rig_kw = _rig()
-    s.omni, _ = synthetic.make_frame_pairs(gs, s.B, seed=99)
-    s.omni[5] = 0
-    s.model = DeviceImageModel(ctx, gs, (480, 640))
-    s.fe = ImageFrontEnd(ctx, s.model, 2 * s.B, detection_method="GFT", num_of_features=s.nfeat)
-    s.fe.load_frames(s.omni)
-    s.fe.run()
-    ctx.synchronize()
-    ca, sa = orb_pattern.angle_cos_sin(-1.0)
-    im = refflow.ImageModel(s.model.map_x.cpu().numpy(), s.model.map_y.cpu().numpy(), s.model.omni_masks.cpu().numpy(),
-                            s.model.mask_bits_host, 12, s.nfeat, orb_pattern.orb_pattern(), ca, sa, method="GFT", kp_cap=s.fe.kp_cap)
-    s.views = [[refflow.detect_view(im, s.omni[f], v)[:2] for v in range(2)] for f in range(2 * s.B)]
-    s.rp = refflow.RigParams(**s.rig_kw)
-    s.records, s.pipes = {}, {}
-    for name, (st, ff) in dict(SETTINGS, off=(False, False)).items():
-        pipe = FramePairPipeline(ctx, RigConfig(**s.rig_kw), s.B, frame_cap=2048, max_iter=s.iters, seed=s.seed, front_end=s.fe,
-                                 cross_check_stereo=st, cross_check_f2f=ff)
+    the detection on the oracle (once, shared), one-mirror P3P with 500 fixed iterations."""
+    return scenes.omni_pairs(ctx, B=3, black=(5,), solver=(("max_iter", 500),))
+
+
+@pytest.fixture(scope="module")
+def pipes(ctx, pairs):
+    """The stage-by-stage pipeline per switch setting, run."""
+    s, out = pairs, {}
+    for name, setting in dict(SETTINGS, off=OFF).items():
+        out[name] = pipe = FramePairPipeline(ctx, RigConfig(**s.rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
+                                             cross_check_stereo=setting.cc_stereo, cross_check_f2f=setting.cc_f2f)
         pipe.stereo()
         pipe.track()
-        s.records[name] = pipe.results().cpu().numpy()
-        s.pipes[name] = pipe
     ctx.synchronize()
-    return s
+    return out
+
+
+def records(pipes, name):
+    return pipes[name].results().cpu().numpy()
 
 
 @pytest.mark.parametrize("name", sorted(SETTINGS))
-def test_pair_path_equals_refflow_with_the_mutual_matcher(ctx, pairs, name):
-    s, (st, ff) = pairs, SETTINGS[name]
-    pipe, rec = s.pipes[name], s.records[name]
-    with mutual_matching(st, ff):
-        frames = [refflow.stereo_frame(s.rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
-        want = [refflow.track_pair(s.rp, frames[2 * i], frames[2 * i + 1], pipe.thr, s.iters, seed=s.seed + i) for i in range(s.B)]
-    assert refflow.match_sorted.__name__ == "match_sorted"
+def test_pair_path_equals_refflow_with_the_mutual_matcher(ctx, pairs, pipes, name):
+    s, setting = pairs, SETTINGS[name]
+    st, ff = setting.cc_stereo, setting.cc_f2f
+    pipe, rec = pipes[name], records(pipes, name)
+    assert pipe.thr == s.thr
+    frames, want = s.frames(setting), s.pair_tracks(setting)
     M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
     assert [int(x) for x in M] == [len(fr["X"]) for fr in frames]
     assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
@@ -261,35 +189,33 @@ def test_pair_path_equals_refflow_with_the_mutual_matcher(ctx, pairs, name):
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
         assert np.array_equal(rec[i, :12].reshape(3, 4), w["T"])
     assert rec[2, 14] == 1 and rec[2, 13] == 0 and (rec[:2, 14] == 0).all()
-    off = s.records["off"]
+    off = records(pipes, "off")
     if ff:
         assert (rec[:2, 13] < off[:2, 13]).all()             # fewer correspondences than the plain matcher gives
     if st:
-        assert (M[:5] < s.pipes["off"].frames["M"].cpu().numpy()[:5]).all()   # ... fewer stereo points
+        assert (M[:5] < pipes["off"].frames["M"].cpu().numpy()[:5]).all()   # ... fewer stereo points
     if name == "both":
         assert not np.array_equal(rec[:2, :12], off[:2, :12])
     if name == "f2f":                                        # the stereo stage is untouched by the f2f switch
-        assert np.array_equal(M, s.pipes["off"].frames["M"].cpu().numpy())
+        assert np.array_equal(M, pipes["off"].frames["M"].cpu().numpy())
 
 
-def test_pair_path_with_a_fraction_of_the_mutual_matches(ctx, pairs):
+def test_pair_path_with_a_fraction_of_the_mutual_matches(ctx, pairs, pipes):
     """pct_good_matches = 0.75 with both switches: int(0.75 * len(matches)) counts the KEPT matches per bucket and per view
     (camera_models.py:3045, pose_est_tools.py:225), in the stage path and behind the one C call."""
     s = pairs
     rig_kw = dict(s.rig_kw, pct_good_matches=0.75)
-    pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), s.B, frame_cap=2048, max_iter=s.iters, seed=s.seed, front_end=s.fe,
+    pipe = FramePairPipeline(ctx, RigConfig(**rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
                              cross_check_stereo=True, cross_check_f2f=True)
     pipe.stereo()
     pipe.track()
     rec = pipe.results().cpu().numpy()
-    rp = refflow.RigParams(**rig_kw)
-    with mutual_matching(True, True):
-        frames = [refflow.stereo_frame(rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
-        want = [refflow.track_pair(rp, frames[2 * i], frames[2 * i + 1], pipe.thr, s.iters, seed=s.seed + i) for i in range(s.B)]
+    assert pipe.thr == s.thr
+    frames, want = s.frames(SETTINGS["both"], pct=0.75), s.pair_tracks(SETTINGS["both"], pct=0.75)
     M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
     assert [int(x) for x in M] == [len(fr["X"]) for fr in frames]
     assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
-    assert (n_cand[:5] < s.pipes["both"].frames["n_cand"].cpu().numpy()[:5]).all()
+    assert (n_cand[:5] < pipes["both"].frames["n_cand"].cpu().numpy()[:5]).all()
     mask = pipe.ransac["mask"].cpu().numpy()
     for i, w in enumerate(want):
         n = len(w["corr"]["cam"])
@@ -297,7 +223,7 @@ def test_pair_path_with_a_fraction_of_the_mutual_matches(ctx, pairs):
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
         assert np.array_equal(rec[i, :12].reshape(3, 4), w["T"])
     batch = FramePairBatch(ctx, s.model, RigConfig(**rig_kw), s.B, num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048,
-                           max_iter=s.iters, seed=s.seed, cross_check_stereo=True, cross_check_f2f=True)
+                           seed=s.seed, **s.solver, cross_check_stereo=True, cross_check_f2f=True)
     batch.load_frames(s.omni)
     got = batch.step()
     ctx.synchronize()
@@ -305,11 +231,11 @@ def test_pair_path_with_a_fraction_of_the_mutual_matches(ctx, pairs):
 
 
 @pytest.mark.parametrize("name", sorted(SETTINGS))
-def test_one_call_batches_give_the_pair_path_records(ctx, pairs, name):
-    s, (st, ff) = pairs, SETTINGS[name]
-    want = s.records[name]
-    kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, max_iter=s.iters, seed=s.seed, cross_check_stereo=st,
-              cross_check_f2f=ff)
+def test_one_call_batches_give_the_pair_path_records(ctx, pairs, pipes, name):
+    s, setting = pairs, SETTINGS[name]
+    want = records(pipes, name)
+    kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, seed=s.seed, **s.solver,
+              cross_check_stereo=setting.cc_stereo, cross_check_f2f=setting.cc_f2f)
     sizes = {}
     for ns in (1, 2):
         batch = FramePairBatch(ctx, s.model, RigConfig(**s.rig_kw), s.B, n_streams=ns, **kw)
@@ -332,28 +258,12 @@ def test_one_call_batches_give_the_pair_path_records(ctx, pairs, name):
     assert off.workspace.numel() < sizes[1]                  # the workspace grows only with a switch set
 
 
-FX = FY = 554.256258
-CX, CY = 319.5, 239.5
-
-
 def test_rgbd_pair_path_and_batch(ctx):
     """RGBDPairPipeline and RGBDPairBatch with cross_check=True on 2 pairs against refflow.track_pair_rgbd under the mutual
     matcher."""
-    B, nfeat, iters = 2, 1000, 300
-    yaw = np.deg2rad(40.0)
-    R_yaw = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
-    bgr, depth = [], []
-    for i in range(B):
-        rng = np.random.default_rng(900 + i)
-        room = synthetic.Room(seed=900 + i, half_x=(1800.0, 2600.0), half_y=(2500.0, 3500.0), cells=(150.0, 40.0))
-        R, t = synthetic.random_step(rng, max_t=80.0, max_deg=8.0)
-        for (Rw, tw) in ((R_yaw, np.zeros(3)), (R_yaw @ R, R_yaw @ t)):
-            im, dp = synthetic.render_rgbd(room, Rw, tw, rng, FX, FY, CX, CY, depth_is_Z=True)
-            bgr.append(im)
-            depth.append(dp)
-    bgr, depth = np.stack(bgr), np.stack(depth)
-    cam = RGBDCamConfig(fx=FX, fy=FY, center_x=CX, center_y=CY, depth_is_Z=True, min_range=0.8, max_range=7.0)
-    kw = dict(num_of_features=nfeat, max_iter=iters, seed=31, pose_est_algorithm="EPNP")
+    s, iters = scenes.rgbd_pairs(ctx), 300
+    B, bgr, depth, cam, rc, frames = s.B, s.bgr, s.depth, s.cam, s.rc, s.frames
+    kw = dict(num_of_features=s.nfeat, max_iter=iters, seed=31, pose_est_algorithm="EPNP")
     recs = {}
     for on in (False, True):
         pipe = RGBDPairPipeline(ctx, cam, B, cross_check=on, **kw)
@@ -365,14 +275,10 @@ def test_rgbd_pair_path_and_batch(ctx):
         got = one.step()
         ctx.synchronize()
         assert np.array_equal(got.cpu().numpy().view(np.uint64), recs[on].view(np.uint64)), on
-    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-    rc = refflow.RGBDParams(FX, FY, CX, CY, cam.focal_length_m, True, 0.8, 7.0, cam.f2f_max_hdiff, 1.0)
-    frames = [refflow.rgbd_frame(rc, bgr[f], depth[f], nfeat, orb_pattern.orb_pattern(), ca, sa) for f in range(2 * B)]
     rec, mask = recs[True], pipe.ransac["mask"].cpu().numpy()
     cq, ct = pipe.corr["q"].cpu().numpy(), pipe.corr["t"].cpu().numpy()
-    with mutual_matching(False, True):
-        want = [refflow.track_pair_rgbd(rc, frames[2 * i], frames[2 * i + 1], pipe.thr, iters, seed=31 + i, epnp=True)
-                for i in range(B)]
+    want = [refflow.track_pair_rgbd(rc, frames[2 * i], frames[2 * i + 1], pipe.thr, iters, seed=31 + i, epnp=True, matching=MUTUAL)
+            for i in range(B)]
     for i, w in enumerate(want):
         n = len(w["corr"]["q"])
         assert rec[i, 13] == n and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
@@ -384,21 +290,6 @@ def test_rgbd_pair_path_and_batch(ctx):
 
 
 # ---- 5. sequence mode ---------------------------------------------------------------------------------------------------------
-def _read(results):
-    return tuple(open(os.path.join(results, f)).read() for f in FILES)
-
-
-def _sos_kwargs(seq, n, results):
-    return dict(gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"), img_filename_template=os.path.join(seq, "omni", "image-*.png"),
-                img_indices=list(range(n)), results_path=results)
-
-
-def _rgbd_kwargs(seq, n, results):
-    d = os.path.join(seq, "rgbd")
-    return dict(gt_poses_filename=os.path.join(d, "gt_TUM.txt"), img_filename_template=os.path.join(d, "rgb", "*.png"),
-                depth_filename_template=os.path.join(d, "depth", "*.png"), img_indices=list(range(n)), results_path=results)
-
-
 def _rgbd_model():
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
     from vo_single_camera_sos_amd.omnistereo.transformations import rotation_matrix
@@ -408,19 +299,9 @@ def _rgbd_model():
     return cam
 
 
-N_SEQ = 6
-
-
 @pytest.fixture(scope="module")
 def sos_sequences(tmp_path_factory):
-    gs, _ = _rig()
-    root = tmp_path_factory.mktemp("cross_check_sos")
-    seqs = []
-    for seed in (77, 61):
-        seq = str(root / ("seq_%d" % seed))
-        synthetic.write_sos_sequence(seq, gs, n_frames=N_SEQ, seed=seed, max_t=40.0, max_deg=2.0)
-        seqs.append(seq)
-    return seqs
+    return scenes.write_sos_sequences(tmp_path_factory.mktemp("cross_check_sos"))
 
 
 def test_run_vo_cross_check_windows_and_mirror_path(ctx, sos_sequences, tmp_path):
@@ -431,23 +312,23 @@ def test_run_vo_cross_check_windows_and_mirror_path(ctx, sos_sequences, tmp_path
     outs, files = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, cross_check=True, **_sos_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, cross_check=True, **sos_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert files[5] == files[1] and "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[5]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())
     assert outs[0]["keyframe_ids"] == outs[5]["keyframe_ids"]
     res = str(tmp_path / "off")
-    off = run_VO(None, model, frame_window=5, cross_check=False, **_sos_kwargs(seq, N_SEQ, res))
-    assert off["tracked"] == N_SEQ - 1 and _read(res)[0] != files[5][0]
+    off = run_VO(None, model, frame_window=5, cross_check=False, **sos_kwargs(seq, N_SEQ, res))
+    assert off["tracked"] == N_SEQ - 1 and read_results(res)[0] != files[5][0]
     # one matcher alone is a third result, and None is the tracker's own setting: off
     res = str(tmp_path / "f2f")
-    run_VO(None, model, frame_window=5, cross_check="f2f", **_sos_kwargs(seq, N_SEQ, res))
-    assert _read(res)[0] not in (files[5][0], _read(str(tmp_path / "off"))[0])
+    run_VO(None, model, frame_window=5, cross_check="f2f", **sos_kwargs(seq, N_SEQ, res))
+    assert read_results(res)[0] not in (files[5][0], read_results(str(tmp_path / "off"))[0])
     res = str(tmp_path / "none")
-    run_VO(None, model, frame_window=5, **_sos_kwargs(seq, N_SEQ, res))
-    assert _read(res) == _read(str(tmp_path / "off"))
+    run_VO(None, model, frame_window=5, **sos_kwargs(seq, N_SEQ, res))
+    assert read_results(res) == read_results(str(tmp_path / "off"))
 
 
 def test_run_vo_many_cross_check_equals_the_solo_runs(ctx, sos_sequences, tmp_path):
@@ -457,13 +338,13 @@ def test_run_vo_many_cross_check_equals_the_solo_runs(ctx, sos_sequences, tmp_pa
     want = []
     for k, seq in enumerate(sos_sequences):
         res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=5, cross_check=True, **_sos_kwargs(seq, N_SEQ, res))
+        out = run_VO(None, load_gums_json(gums), frame_window=5, cross_check=True, **sos_kwargs(seq, N_SEQ, res))
         assert out["tracked"] == N_SEQ - 1
-        want.append(_read(res))
-    many = [_sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
+        want.append(read_results(res))
+    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
     outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, cross_check=True)
     for q, files, o in zip(many, want, outs):
-        assert _read(q["results_path"]) == files
+        assert read_results(q["results_path"]) == files
         assert o["sequence_mode"]["lanes"] == 2
     assert want[0] != want[1]
 
@@ -476,17 +357,17 @@ def test_rgbd_run_vo_cross_check(ctx, tmp_path):
     files, outs = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, cross_check=True, **_rgbd_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, cross_check=True, **rgbd_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert files[5] == files[1]
     for (i, Ta), (_, Tb) in zip(outs[5]["poses"], outs[0]["poses"]):
         assert np.allclose(Ta, Tb, rtol=1e-9, atol=1e-12), (i, np.abs(Ta - Tb).max())
     res = str(tmp_path / "off")
-    run_VO(None, model, frame_window=5, **_rgbd_kwargs(seq, N_SEQ, res))
-    assert _read(res)[0] != files[5][0]
+    run_VO(None, model, frame_window=5, **rgbd_kwargs(seq, N_SEQ, res))
+    assert read_results(res)[0] != files[5][0]
     with pytest.raises(ValueError, match="no static-stereo matcher"):
-        run_VO(None, model, frame_window=5, cross_check="stereo", **_rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
+        run_VO(None, model, frame_window=5, cross_check="stereo", **rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
 
 
 # ---- 6. what it is for ----------------------------------------------------------------------------------------------------------
@@ -497,7 +378,7 @@ def test_cross_check_raises_the_inlier_share_and_lowers_the_pose_error(ctx):
     off.  Relations, not thresholds; the CPU oracle flow gives 0.981 vs 0.913, 0.284 vs 0.602 degrees, 18.2 vs 25.2 mm, and
     the pair path equals that flow bit for bit (test_pair_path_equals_refflow_with_the_mutual_matcher)."""
     B = 6
-    gs, rig_kw = _rig()
+    gs, rig_kw = scenes.rig()
     omni, poses = synthetic.make_frame_pairs(gs, B, seed=4100)
     model = DeviceImageModel(ctx, gs, (480, 640))
     fe = ImageFrontEnd(ctx, model, 2 * B, detection_method="GFT", num_of_features=1000, kp_cap=512)

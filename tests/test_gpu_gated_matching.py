@@ -2,127 +2,45 @@
 every layer: the stage entry, FeatureMatcher.match_gated, the pair pipelines and one-call batches, the sequence engines
 behind run_VO / run_VO_many, RGB-D, and the subset relations the definition implies.
 
-The CPU checker is the definition itself, composed of oracle calls (gated_keys below): oracle.pixel_gates on the float32
-positions converted to double, a numpy min over popcounts, oracle.sort_matches.  refflow.stereo_frame / f2f_view are swapped
-for gated versions defined here (gated_matching below) and restored afterwards.  Everything is compared bit for bit or byte
-for byte; the mirror path (frame_window 0) to 1e-6, as the existing sequence tests compare it."""
-import contextlib
+The CPU checker is the definition itself, composed of oracle calls (tests/refmatch.py): oracle.pixel_gates on the float32
+positions converted to double, a numpy min over popcounts, oracle.sort_matches.  refflow's flow functions take it as their
+matcher (matching_scenes.Setting.matchings).  Everything is compared bit for bit or byte for byte; the mirror path
+(frame_window 0) to 1e-6, as the existing sequence tests compare it."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import matching_scenes as scenes
 import oracle
-import refflow
-from vo_single_camera_sos_amd import orb_pattern, synthetic
+from matching_scenes import CX, CY, FX, FY, N_SEQ, Setting, descriptor_scene, read_results, record, rgbd_kwargs, sos_kwargs
+from refmatch import IDX, NONE, POPCOUNT, Matching, capped
+from vo_single_camera_sos_amd import synthetic
 from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
 from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
-from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
-from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
 from vo_single_camera_sos_amd.pipeline import (FramePairBatch, FramePairPipeline, RGBDCamConfig, RGBDPairBatch, RGBDPairPipeline,
                                                RigConfig)
 
 pytestmark = pytest.mark.gpu
 
-IDX, NONE = 0xFFFFF, 0xFFFFFFFF
-FILES = ("estimated_frame_poses_TUM.txt", "keyframe_ids.txt")
-POPCOUNT = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
 
+class _Stage(scenes.StageProblems):
+    """sosvo_match_hamming_gated on the problems, the last P - n_forward of them reversed, against the definition."""
 
-# ---- the definition ------------------------------------------------------------------------------------------------------
-def distances(q, t):
-    """[nq, nt] Hamming distances."""
-    return POPCOUNT[q[:, None, :] ^ t[None, :, :]].sum(-1, dtype=np.uint32)
-
-
-def gate_matrix(q_pos, t_pos, min_dv, max_du, reverse=False):
-    """gate(i, j) [nq, nt]: oracle.pixel_gates(train, query) on doubles converted from the float32 positions; a reversed
-    problem evaluates the same gate with the roles swapped (v_q - v_t >= min_dv)."""
-    nq, nt = len(q_pos), len(t_pos)
-    qp = np.repeat(q_pos.astype(np.float64)[:, None, :], nt, 1).reshape(-1, 2)
-    tp = np.repeat(t_pos.astype(np.float64)[None, :, :], nq, 0).reshape(-1, 2)
-    ok = oracle.pixel_gates(qp, tp, min_dv, max_du) if reverse else oracle.pixel_gates(tp, qp, min_dv, max_du)
-    return ok.reshape(nq, nt)
-
-
-def gated_keys(q, t, q_pos, t_pos, min_dv, max_du, cap=None, reverse=False, dist=None):
-    """key(i) = min over admissible j of (hamming << 20 | j); NONE without an admissible train or beyond the cap."""
-    nq, nt = len(q), len(t)
-    if nq == 0 or nt == 0:
-        return np.full(nq, NONE, np.uint32)
-    d = distances(q, t) if dist is None else dist
-    keys = (d << 20) | np.arange(nt, dtype=np.uint32)[None, :]
-    keys = np.where(gate_matrix(q_pos, t_pos, min_dv, max_du, reverse), keys, np.uint32(NONE)).min(1).astype(np.uint32)
-    keys[(keys >> 20) > (256 if cap is None else cap)] = NONE      # (NONE >> 20 is 4095)
-    return keys
-
-
-def gated_match_sorted(query_desc, train_desc, query_pos, train_pos, min_dv, max_du, cap=None):
-    """refflow.match_sorted on the gated keys: the matches that exist, stably sorted by distance."""
-    keys = gated_keys(query_desc, train_desc, query_pos, train_pos, min_dv, max_du, cap)
-    kept = np.nonzero(keys != NONE)[0]
-    if len(kept) == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return z, z, z
-    k = keys[kept]
-    order = oracle.sort_matches(k)
-    return kept[order].astype(np.int64), (k[order] & IDX).astype(np.int64), (k[order] >> 20).astype(np.int64)
-
-
-def _dev(ctx, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
-
-
-def _scene(rng, blocks, stride, counts, u_span=40.0, v_span=12.0):
-    """A descriptor / position store: every block re-observes block 0's first rows with 0-6 flipped bits at a position
-    jittered by a few pixels, some rows are copies of each other (ties), the rest is random."""
-    desc = rng.integers(0, 256, (blocks, stride, 32), dtype=np.uint8)
-    pos = np.stack([rng.uniform(0, u_span, (blocks, stride)), rng.uniform(0, v_span, (blocks, stride))], -1).astype(np.float32)
-    n0 = max(1, int(counts[0]))
-    for b in range(blocks):
-        n = int(counts[b])
-        for i in range(0, n, 2):
-            src = int(rng.integers(0, n0))
-            d = desc[0, src].copy()
-            for bit in rng.integers(0, 256, rng.integers(0, 7)):
-                d[bit >> 3] ^= np.uint8(1 << (bit & 7))
-            desc[b, i] = d
-            pos[b, i] = pos[0, src] + rng.uniform(-3.0, 3.0, 2).astype(np.float32)
-        for i in range(5, n, 11):
-            desc[b, i] = desc[b, i - 3]
-    return desc, pos
-
-
-class _Stage(object):
-    """One set of problems on the device, the distance matrices cached per (query block, train block)."""
-
-    def __init__(self, ctx, qd, td, qp, tp, nq, nt, q_slot=None, t_slot=None, n_forward=None):
-        self.ctx, self.qd, self.td, self.qp, self.tp, self.nq, self.nt = ctx, qd, td, qp, tp, nq, nt
-        self.P = len(nq) if q_slot is None else len(q_slot)
-        self.qs = np.arange(self.P) if q_slot is None else q_slot
-        self.ts = np.arange(self.P) if t_slot is None else t_slot
+    def __init__(self, *args, n_forward=None):
+        super().__init__(*args)
         self.n_forward = self.P if n_forward is None else n_forward
-        self.dev = [_dev(ctx, a) for a in (qd, td, qp, tp, nq.astype(np.int32), nt.astype(np.int32))]
-        self.sl = {} if q_slot is None else dict(q_slot=_dev(ctx, q_slot.astype(np.int32)), t_slot=_dev(ctx, t_slot.astype(np.int32)))
-        self.dist, self.want = {}, {}
 
     def run(self, min_dv, max_du, cap):
-        keys = self.ctx.match_hamming_gated(*self.dev, min_dv=min_dv, max_du=max_du, max_distance=cap, n_forward=self.n_forward,
-                                            **self.sl)
+        keys = self.ctx.match_hamming_gated(self.d_qd, self.d_td, self.d_qp, self.d_tp, self.d_nq, self.d_nt, min_dv=min_dv,
+                                            max_du=max_du, max_distance=cap, n_forward=self.n_forward, **self.sl)
         self.ctx.synchronize()
         return keys.cpu().numpy()[:, :, 0]
 
     def expect(self, p, min_dv, max_du, cap):
-        qs, ts, rev = int(self.qs[p]), int(self.ts[p]), p >= self.n_forward
-        n, m = int(self.nq[qs]), int(self.nt[ts])
-        if (qs, ts) not in self.dist:
-            self.dist[qs, ts] = distances(self.qd[qs, :n], self.td[ts, :m])
-        sig = (qs, ts, rev, min_dv, max_du, cap)
-        if sig not in self.want:
-            self.want[sig] = gated_keys(self.qd[qs, :n], self.td[ts, :m], self.qp[qs, :n], self.tp[ts, :m], min_dv, max_du, cap,
-                                        reverse=rev, dist=self.dist[qs, ts])
-        return self.want[sig]
+        """key(i) = min over admissible j of (hamming << 20 | j); NONE without an admissible train or beyond the cap."""
+        return capped(self.smallest(p, (min_dv, max_du), p >= self.n_forward)[0], cap)
 
     def check(self, min_dv, max_du, cap):
         got = self.run(min_dv, max_du, cap)
@@ -145,8 +63,8 @@ def test_stage_equals_the_definition_at_the_tile_edges(ctx):
     shapes = [(a, b) for a in QUERIES for b in TRAINS]
     S = 320
     nq, nt = np.array([s[0] for s in shapes]), np.array([s[1] for s in shapes])
-    qd, qp = _scene(rng, len(shapes), S, nq)
-    td, tp = _scene(rng, len(shapes), S, nt)
+    qd, qp = descriptor_scene(rng, len(shapes), S, nq)
+    td, tp = descriptor_scene(rng, len(shapes), S, nt)
     td[:, ::2] = qd[:, ::2]                                       # (true partners exist: same descriptor, nearby position)
     tp[:, ::2] = qp[:, ::2] + rng.uniform(-2.0, 4.0, qp[:, ::2].shape).astype(np.float32)
     st = _Stage(ctx, qd, td, qp, tp, nq, nt)
@@ -170,10 +88,10 @@ def test_stage_without_gate_and_cap_equals_the_plain_matcher(ctx):
     for seed, q_stride, nq, nt in ((3, 320, [129, 33, 300], [257, 128, 300]), (37, 1024, [960], [300])):
         rng = np.random.default_rng(seed)
         nq, nt = np.array(nq), np.array(nt)
-        qd, qp = _scene(rng, len(nq), q_stride, nq)
-        td, tp = _scene(rng, len(nt), 320, nt)
+        qd, qp = descriptor_scene(rng, len(nq), q_stride, nq)
+        td, tp = descriptor_scene(rng, len(nt), 320, nt)
         st = _Stage(ctx, qd, td, qp, tp, nq, nt)
-        plain = ctx.match_hamming(st.dev[0], st.dev[1], st.dev[4], st.dev[5], k=1)
+        plain = ctx.match_hamming(st.d_qd, st.d_td, st.d_nq, st.d_nt, k=1)
         ctx.synchronize()
         plain = plain.cpu().numpy()[:, :, 0]
         for cap in (None, 256):
@@ -243,15 +161,15 @@ def test_stage_slots_reversed_problems_and_the_unsplit_train_loop(ctx):
     the second half reversed, as the role-swapped problems of a cross-checked step are."""
     rng = np.random.default_rng(23)
     S, counts = 320, np.array([257, 129, 128, 33, 300, 0])
-    desc, pos = _scene(rng, 6, S, counts)
+    desc, pos = descriptor_scene(rng, 6, S, counts)
     P = 2100
     q_slot, t_slot = rng.integers(0, 6, P), rng.integers(0, 6, P)
     st = _Stage(ctx, desc, desc, pos, pos, counts, counts, q_slot, t_slot, n_forward=P // 2)
     st.check(1.0, 2.5, None)
     st.check(1.0, 2.5, 80)
     st.check(-1.0, 2.5, None)
-    fwd = gated_keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], 1.0, 2.5)
-    rev = gated_keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], 1.0, 2.5, reverse=True)
+    fwd = Matching(gated=True).keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], (1.0, 2.5))
+    rev = Matching(gated=True).keys(desc[1, :129], desc[0, :257], pos[1, :129], pos[0, :257], (1.0, 2.5), reverse=True)
     assert not np.array_equal(fwd, rev)                           # (the reversed gate is another gate)
 
 
@@ -259,8 +177,8 @@ def test_stage_two_tiles_per_wave(ctx):
     """q_stride 1024: the kernel form with two query tiles per wave, a dead second tile included (nq = 1000 - 40)."""
     rng = np.random.default_rng(29)
     nq, nt = np.array([960]), np.array([300])
-    qd, qp = _scene(rng, 1, 1024, nq)
-    td, tp = _scene(rng, 1, 320, nt)
+    qd, qp = descriptor_scene(rng, 1, 1024, nq)
+    td, tp = descriptor_scene(rng, 1, 320, nt)
     td[0, :300:3] = qd[0, :300:3]
     tp[0, :300:3] = qp[0, :300:3] + np.float32(1.25)
     st = _Stage(ctx, qd, td, qp, tp, nq, nt)
@@ -304,16 +222,16 @@ def test_gate_is_evaluated_in_double(ctx):
 # ---- 2. FeatureMatcher.match_gated ----------------------------------------------------------------------------------------
 def test_feature_matcher_match_gated(ctx):
     rng = np.random.default_rng(5)
-    desc, pos = _scene(rng, 2, 320, np.array([257, 300]))
+    desc, pos = descriptor_scene(rng, 2, 320, np.array([257, 300]))
     q, t, qp, tp = desc[1, :300], desc[0, :257], pos[1, :300], pos[0, :257]
     fm = FeatureMatcher("ORB", "BF", 1, context=ctx)
     plain = fm.match(q, t)
     for cap in (None, 80, 0):
         got = fm.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=cap)
-        wq, wt, wd = gated_match_sorted(q, t, qp, tp, 1.0, 2.5, cap)
+        wq, wt, wd = Matching(gated=True, cap=cap)(q, t, qp, tp, (1.0, 2.5))
         assert np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
         assert [m.queryIdx for m in got] == list(wq) and [m.trainIdx for m in got] == list(wt)
-    wq, wt, wd = gated_match_sorted(q, t, qp, tp, 1.0, 2.5)
+    wq, wt, wd = Matching(gated=True)(q, t, qp, tp, (1.0, 2.5))
     assert 20 < len(wq) < 300
     # the plain matches that pass the gate are gated matches (the search under the gate can only add)
     ok = oracle.pixel_gates(tp[plain.train_idx].astype(np.float64), qp[plain.query_idx].astype(np.float64), 1.0, 2.5)
@@ -329,142 +247,18 @@ def test_feature_matcher_match_gated(ctx):
     # mutual under the gate
     fmc = FeatureMatcher("ORB", "BF", 1, context=ctx, cross_check=True)
     got = fmc.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=80)
-    wq, wt, wd = matches_under(q, t, qp, tp, (1.0, 2.5), 80, True)
+    wq, wt, wd = Matching(gated=True, cap=80, mutual=True)(q, t, qp, tp, (1.0, 2.5))
     assert 0 < len(wq) and np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
     assert len(set(got.train_idx)) == len(got)
 
 
-# ---- the gated reference flow ---------------------------------------------------------------------------------------------
-def matches_under(qd, td, qp, tp, gate, cap, mutual):
-    """refflow.match_sorted of one problem: gate = (min_dv, max_du) or None for the plain search; mutual: keep query i only
-    if the role-swapped search (under the reversed gate) of its train returns i."""
-    if len(qd) == 0 or len(td) == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return z, z, z
-    if gate is None:
-        fwd = oracle.match_hamming(qd, td, k=1)[:, 0]
-        rev = oracle.match_hamming(td, qd, k=1)[:, 0] if mutual else None
-    else:
-        fwd = gated_keys(qd, td, qp, tp, gate[0], gate[1], cap)
-        rev = gated_keys(td, qd, tp, qp, gate[0], gate[1], cap, reverse=True) if mutual else None
-    keep = fwd != NONE
-    if mutual:
-        r = rev[np.where(keep, fwd & IDX, 0)]
-        keep &= (r != NONE) & ((r & IDX) == np.arange(len(qd)))
-    kept = np.nonzero(keep)[0]
-    k = fwd[kept]
-    order = oracle.sort_matches(k) if len(k) else np.zeros(0, np.int64)
-    return kept[order].astype(np.int64), (k[order] & IDX).astype(np.int64), (k[order] >> 20).astype(np.int64)
-
-
-def stereo_frame_under(gated, cap, mutual):
-    """refflow.stereo_frame with the bucket matcher replaced (the lines around it are refflow's)."""
-    def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot):
-        mt, mb, dt, db = [], [], [], []
-        n_cand = 0
-        gate = (rig.stereo_min_disp, rig.stereo_max_hdiff) if gated else None
-        for kt, kb, et, eb in zip(kp_top, kp_bot, desc_top, desc_bot):
-            if len(kt) == 0 or len(kb) == 0:
-                continue
-            q, t, _ = matches_under(eb, et, kb, kt, gate, cap, mutual)    # query = bottom, train = top
-            good = int(rig.pct_good_matches * len(q))
-            q, t = q[:good], t[:good]
-            n_cand += good
-            mt.append(kt[t])
-            mb.append(kb[q])
-            dt.append(et[t])
-            db.append(eb[q])
-        if not mt:
-            e2, e3, e32 = np.zeros((0, 2), np.float32), np.zeros((0, 3)), np.zeros((0, 32), np.uint8)
-            return dict(m_top=e2, m_bot=e2, d_top=e32, d_bot=e32, X=e3, b_top=e3, b_bot=e3, n_cand=0)
-        mt, mb = np.concatenate(mt).astype(np.float32), np.concatenate(mb).astype(np.float32)
-        dt, db = np.concatenate(dt), np.concatenate(db)
-        ok = oracle.pixel_gates(mt.astype(np.float64), mb.astype(np.float64), rig.stereo_min_disp, rig.stereo_max_hdiff)
-        if gated:
-            assert ok.all()                                  # the assemble gate now passes every match it sees
-        mt, mb, dt, db = mt[ok], mb[ok], dt[ok], db[ok]
-        az1, el1 = oracle.pano_to_angles(mt[:, 0], mt[:, 1], *rig.pano_top)
-        az2, el2 = oracle.pano_to_angles(mb[:, 0], mb[:, 1], *rig.pano_bot)
-        bt, bb = oracle.angles_to_bearing(az1, el1), oracle.angles_to_bearing(az2, el2)
-        X = oracle.triangulate_midpoint(az1, el1, az2, el2, rig.F_top, rig.F_bot)
-        good = oracle.range_filter_homo(X, rig.min_range, rig.max_range)
-        return dict(m_top=mt[good], m_bot=mb[good], d_top=dt[good], d_bot=db[good], X=X[good], b_top=bt[good], b_bot=bb[good],
-                    n_cand=n_cand)
-    return stereo_frame
-
-
-def f2f_view_under(gated, cap, mutual):
-    """refflow.f2f_view with the matcher replaced; the gate is off exactly when the view's own |du| gate is."""
-    def f2f_view(rig, m_train, d_train, m_query, d_query):
-        gate = (-1.0, rig.f2f_max_hdiff if rig.f2f_max_hdiff >= 0 else -1.0) if gated else None
-        q, t, _ = matches_under(d_query, d_train, np.asarray(m_query, np.float32)[:, :2], np.asarray(m_train, np.float32)[:, :2],
-                                gate, cap, mutual)
-        good = int(rig.pct_good_matches * len(q))
-        q, t = q[:good], t[:good]
-        if good > 0 and rig.f2f_max_hdiff >= 0:
-            pt, pq = np.zeros((good, 2)), np.zeros((good, 2))
-            pt[:, 0], pq[:, 0] = m_train[t, 0], m_query[q, 0]
-            ok = oracle.pixel_gates(pt, pq, -1, rig.f2f_max_hdiff)
-            if gated:
-                assert ok.all()
-            q, t = q[ok], t[ok]
-        return t, q
-    return f2f_view
-
-
-class Setting(object):
-    def __init__(self, name, stereo, f2f, cap=None, cc=False):
-        self.name, self.stereo, self.f2f, self.cap, self.cc = name, stereo, f2f, cap, cc
-
-    def omni_kw(self):
-        return dict(gated_stereo=self.stereo, gated_f2f=self.f2f, gated_max_distance=self.cap, cross_check_stereo=self.cc,
-                    cross_check_f2f=self.cc)
-
-    def rgbd_kw(self):
-        return dict(gated_f2f=self.f2f, gated_max_distance=self.cap, cross_check=self.cc)
-
-    def run_vo_kw(self):
-        value = "both" if self.stereo and self.f2f else "stereo" if self.stereo else "f2f" if self.f2f else None
-        return dict(gated_matching=value, gated_max_distance=self.cap, cross_check=True if self.cc else None)
-
-
-@contextlib.contextmanager
-def gated_matching(s):
-    """refflow with the setting's matchers in static stereo (stereo_frame) and frame to frame (f2f_view)."""
-    stereo_frame, f2f_view = refflow.stereo_frame, refflow.f2f_view
-    if s.stereo or s.cc:
-        refflow.stereo_frame = stereo_frame_under(s.stereo, s.cap, s.cc)
-    if s.f2f or s.cc:
-        refflow.f2f_view = f2f_view_under(s.f2f, s.cap, s.cc)
-    try:
-        yield
-    finally:
-        refflow.stereo_frame, refflow.f2f_view = stereo_frame, f2f_view
-
-
-SETTINGS = [Setting("stereo", True, False), Setting("f2f", False, True), Setting("both", True, True),
-            Setting("stereo_cap80", True, False, 80), Setting("f2f_cap80", False, True, 80), Setting("both_cap80", True, True, 80),
-            Setting("both_with_cross_check", True, True, None, True)]
-OFF = Setting("off", False, False)
+# ---- the settings --------------------------------------------------------------------------------------------------------
+SETTINGS = [Setting("stereo", gate="stereo"), Setting("f2f", gate="f2f"), Setting("both", gate="both"),
+            Setting("stereo_cap80", gate="stereo", cap=80), Setting("f2f_cap80", gate="f2f", cap=80),
+            Setting("both_cap80", gate="both", cap=80), Setting("both_with_cross_check", gate="both", cc=True)]
+OFF = Setting("off")
 BY_NAME = {s.name: s for s in SETTINGS}
 NAMES = [s.name for s in SETTINGS]
-
-
-def _rig():
-    gs = synthetic_gums()
-    for m in (gs.top_model, gs.bot_model):
-        m.panorama = Panorama(m, width=1200)
-    gs.make_annulus_masks((480, 640))
-    pano = gs.top_model.panorama
-    geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
-    rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
-                  max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
-                  pct_good_matches=1.0)
-    return gs, rig_kw
-
-
-class _Pairs(object):
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -472,53 +266,14 @@ def pairs(ctx):
     """2 rendered pairs (GFT 330 features): the front end on the GPU, the detection on the oracle (once, shared).  The
     trackers' solver settings (generalised P3P, 210 iterations with the adaptive stop) so that one reference serves the pair
     paths (pair i samples with seed + i) and the sequence engine (frame t with seed t - 1)."""
-    s = _Pairs()
-    s.B, s.nfeat, s.seed = 2, 330, 5
-    s.solver = dict(max_iter=210, adaptive=True, ransac_solver="GP3P")
-    gs, s.rig_kw = _rig()
-    s.omni, _ = synthetic.make_frame_pairs(gs, s.B, seed=99)
-    s.model = DeviceImageModel(ctx, gs, (480, 640))
-    s.fe = ImageFrontEnd(ctx, s.model, 2 * s.B, detection_method="GFT", num_of_features=s.nfeat)
-    s.fe.load_frames(s.omni)
-    s.fe.run()
-    ctx.synchronize()
-    ca, sa = orb_pattern.angle_cos_sin(-1.0)
-    im = refflow.ImageModel(s.model.map_x.cpu().numpy(), s.model.map_y.cpu().numpy(), s.model.omni_masks.cpu().numpy(),
-                            s.model.mask_bits_host, 12, s.nfeat, orb_pattern.orb_pattern(), ca, sa, method="GFT", kp_cap=s.fe.kp_cap)
-    s.views = [[refflow.detect_view(im, s.omni[f], v)[:2] for v in range(2)] for f in range(2 * s.B)]
-    s.rp = refflow.RigParams(**s.rig_kw)
-    s.thr = float(1.0 - np.cos(np.deg2rad(5.0)))
-    s.cache = {}
-
-    def reference(setting):
-        """-> (frames, pair tracks with seed + i, sequence tracks of (t - 1, t) with seed t - 1) under the setting."""
-        if setting.name not in s.cache:
-            with gated_matching(setting):
-                frames = [refflow.stereo_frame(s.rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
-                track = lambda a, b, seed: refflow.track_pair(s.rp, frames[a], frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
-                                                              gp3p=True)
-                s.cache[setting.name] = (frames, [track(2 * i, 2 * i + 1, s.seed + i) for i in range(s.B)],
-                                         [track(t - 1, t, t - 1) for t in range(1, 2 * s.B)])
-            assert refflow.stereo_frame.__name__ == "stereo_frame" and refflow.f2f_view.__module__ == "refflow"
-        return s.cache[setting.name]
-    s.reference = reference
-    return s
-
-
-def _record(w):
-    """The [16] record of a refflow track."""
-    out = np.zeros(16)
-    out[:12] = np.asarray(w["T"]).reshape(12)
-    out[12], out[13] = w["ransac"]["n_inliers"], len(w["corr"]["cam"] if "cam" in w["corr"] else w["corr"]["q"])
-    out[14], out[15] = w["ransac"]["status"], w["ransac"]["best_iter"]
-    return out
+    return scenes.omni_pairs(ctx)
 
 
 # ---- 3. the omni paths against the gated refflow ------------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES)
 def test_pair_pipeline_stage_by_stage_equals_the_gated_refflow(ctx, pairs, name):
     s, setting = pairs, BY_NAME[name]
-    frames, want, _ = s.reference(setting)
+    frames, want = s.frames(setting), s.pair_tracks(setting)
     pipe = FramePairPipeline(ctx, RigConfig(**s.rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
                              **setting.omni_kw())
     pipe.stereo()
@@ -536,13 +291,13 @@ def test_pair_pipeline_stage_by_stage_equals_the_gated_refflow(ctx, pairs, name)
         n = len(w["corr"]["cam"])
         assert n > 100 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
-        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64)) and rec[i, 14] == 0
-    off = s.reference(OFF)
-    if setting.stereo and not setting.cc and setting.cap is None:   # the search under the gate can only add stereo points
-        assert all(len(a["X"]) >= len(b["X"]) for a, b in zip(frames, off[0]))
-        assert sum(len(a["X"]) for a in frames) > sum(len(b["X"]) for b in off[0])
-    if not setting.stereo and not setting.cc:                 # the stereo stage is untouched by the f2f switch
-        assert all(np.array_equal(a["X"], b["X"]) for a, b in zip(frames, off[0]))
+        assert np.array_equal(rec[i].view(np.uint64), record(w).view(np.uint64)) and rec[i, 14] == 0
+    off = s.frames(OFF)
+    if setting.gate_stereo and not setting.cc and setting.cap is None:   # the search under the gate can only add stereo points
+        assert all(len(a["X"]) >= len(b["X"]) for a, b in zip(frames, off))
+        assert sum(len(a["X"]) for a in frames) > sum(len(b["X"]) for b in off)
+    if not setting.changes_stereo:                            # the stereo stage is untouched by the f2f switch
+        assert all(np.array_equal(a["X"], b["X"]) for a, b in zip(frames, off))
 
 
 def test_pair_path_with_a_fraction_of_the_gated_matches(ctx, pairs):
@@ -555,12 +310,8 @@ def test_pair_path_with_a_fraction_of_the_gated_matches(ctx, pairs):
     pipe.stereo()
     pipe.track()
     rec = pipe.results().cpu().numpy()
-    rp = refflow.RigParams(**rig_kw)
-    with gated_matching(setting):
-        frames = [refflow.stereo_frame(rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
-        want = [refflow.track_pair(rp, frames[2 * i], frames[2 * i + 1], s.thr, 210, seed=s.seed + i, adaptive=True, gp3p=True)
-                for i in range(s.B)]
-    full = s.reference(setting)[0]
+    frames, want = s.frames(setting, pct=0.75), s.pair_tracks(setting, pct=0.75)
+    full = s.frames(setting)
     M, n_cand = pipe.frames["M"].cpu().numpy(), pipe.frames["n_cand"].cpu().numpy()
     assert [int(x) for x in M] == [len(fr["X"]) for fr in frames]
     assert [int(x) for x in n_cand] == [fr["n_cand"] for fr in frames]
@@ -571,7 +322,7 @@ def test_pair_path_with_a_fraction_of_the_gated_matches(ctx, pairs):
         n = len(w["corr"]["cam"])
         assert n > 0 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
-        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64))
+        assert np.array_equal(rec[i].view(np.uint64), record(w).view(np.uint64))
     batch = FramePairBatch(ctx, s.model, RigConfig(**rig_kw), s.B, num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048,
                            seed=s.seed, **s.solver, **setting.omni_kw())
     batch.load_frames(s.omni)
@@ -583,7 +334,7 @@ def test_pair_path_with_a_fraction_of_the_gated_matches(ctx, pairs):
 @pytest.mark.parametrize("name", NAMES)
 def test_one_call_batches_equal_the_gated_refflow(ctx, pairs, name):
     s, setting = pairs, BY_NAME[name]
-    want = np.stack([_record(w) for w in s.reference(setting)[1]])
+    want = np.stack([record(w) for w in s.pair_tracks(setting)])
     kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, seed=s.seed, **s.solver, **setting.omni_kw())
     for ns in (1, 2):
         batch = FramePairBatch(ctx, s.model, RigConfig(**s.rig_kw), s.B, n_streams=ns, **kw)
@@ -601,14 +352,14 @@ def test_one_call_batches_equal_the_gated_refflow(ctx, pairs, name):
             ctx.synchronize()
             for b in bufs:
                 assert np.array_equal(b.cpu().numpy().view(np.uint64), want.view(np.uint64))
-    assert not np.array_equal(want[:, :12], np.stack([_record(w) for w in s.reference(OFF)[1]])[:, :12])
+    assert not np.array_equal(want[:, :12], np.stack([record(w) for w in s.pair_tracks(OFF)])[:, :12])
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_sequence_engine_equals_the_gated_refflow_for_windows_1_and_5(ctx, pairs, name):
     from vo_single_camera_sos_amd.pipeline import MultiSequenceEngine, SequenceEngine
     s, setting = pairs, BY_NAME[name]
-    want = np.stack([_record(w) for w in s.reference(setting)[2]])
+    want = np.stack([record(w) for w in s.hop_tracks(setting)])
     kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, **s.solver, **setting.omni_kw())
     n = 2 * s.B
     for window in (1, 5):
@@ -621,46 +372,22 @@ def test_sequence_engine_equals_the_gated_refflow_for_windows_1_and_5(ctx, pairs
 
 
 # ---- 4. RGB-D --------------------------------------------------------------------------------------------------------------
-FX = FY = 554.256258
-CX, CY = 319.5, 239.5
-RGBD_SETTINGS = [Setting("f2f", False, True), Setting("f2f_cap80", False, True, 80), Setting("f2f_with_cross_check", False, True, None, True)]
+RGBD_SETTINGS = [Setting("f2f", gate="f2f"), Setting("f2f_cap80", gate="f2f", cap=80),
+                 Setting("f2f_with_cross_check", gate="f2f", cc=True)]
 
 
 @pytest.fixture(scope="module")
 def rgbd(ctx):
-    s = _Pairs()
-    s.B, s.nfeat = 2, 1000
-    yaw = np.deg2rad(40.0)
-    R_yaw = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
-    bgr, depth = [], []
-    for i in range(s.B):
-        rng = np.random.default_rng(900 + i)
-        room = synthetic.Room(seed=900 + i, half_x=(1800.0, 2600.0), half_y=(2500.0, 3500.0), cells=(150.0, 40.0))
-        R, t = synthetic.random_step(rng, max_t=80.0, max_deg=8.0)
-        for (Rw, tw) in ((R_yaw, np.zeros(3)), (R_yaw @ R, R_yaw @ t)):
-            im, dp = synthetic.render_rgbd(room, Rw, tw, rng, FX, FY, CX, CY, depth_is_Z=True)
-            bgr.append(im)
-            depth.append(dp)
-    s.bgr, s.depth = np.stack(bgr), np.stack(depth)
-    s.cam = RGBDCamConfig(fx=FX, fy=FY, center_x=CX, center_y=CY, depth_is_Z=True, min_range=0.8, max_range=7.0)
-    s.kw = dict(num_of_features=s.nfeat, max_iter=210, adaptive=True, pose_est_algorithm="EPNP")
-    ca, sa = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-    s.rc = refflow.RGBDParams(FX, FY, CX, CY, s.cam.focal_length_m, True, 0.8, 7.0, s.cam.f2f_max_hdiff, 1.0)
-    s.frames = [refflow.rgbd_frame(s.rc, s.bgr[f], s.depth[f], s.nfeat, orb_pattern.orb_pattern(), ca, sa) for f in range(2 * s.B)]
-    s.thr = float(1.0 - np.cos(np.deg2rad(5.0)))
-    return s
+    return scenes.rgbd_pairs(ctx)
 
 
 @pytest.mark.parametrize("setting", RGBD_SETTINGS, ids=[x.name for x in RGBD_SETTINGS])
 def test_rgbd_pair_paths_and_sequence_equal_the_gated_refflow(ctx, rgbd, setting):
     from vo_single_camera_sos_amd.pipeline import RGBDSequenceEngine
     s = rgbd
-    track = lambda a, b, seed: refflow.track_pair_rgbd(s.rc, s.frames[a], s.frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
-                                                       epnp=True)
-    with gated_matching(setting):
-        want = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
-        want_seq = np.stack([_record(track(t - 1, t, t - 1)) for t in range(1, 2 * s.B)])
-    plain = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+    want = [s.track(setting, 2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+    want_seq = np.stack([record(s.track(setting, t - 1, t, t - 1)) for t in range(1, 2 * s.B)])
+    plain = [s.track(None, 2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
     pipe = RGBDPairPipeline(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
     pipe.load_frames(s.bgr, s.depth)
     pipe.step()
@@ -670,7 +397,7 @@ def test_rgbd_pair_paths_and_sequence_equal_the_gated_refflow(ctx, rgbd, setting
         n = len(w["corr"]["q"])
         assert n > 100 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
-        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64)) and rec[i, 14] == 0
+        assert np.array_equal(rec[i].view(np.uint64), record(w).view(np.uint64)) and rec[i, 14] == 0
         if not setting.cc and setting.cap is None:           # the plain correspondences are a subset of the gated ones
             assert set(zip(plain[i]["corr"]["q"], plain[i]["corr"]["t"])) < set(zip(w["corr"]["q"], w["corr"]["t"]))
     one = RGBDPairBatch(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
@@ -698,34 +425,9 @@ def test_rgbd_refuses_gated_stereo(ctx):
 
 
 # ---- 5. run_VO: the sequence engines, the mirror path, run_VO_many -------------------------------------------------------
-def _read(results):
-    return tuple(open(os.path.join(results, f)).read() for f in FILES)
-
-
-def _sos_kwargs(seq, n, results):
-    return dict(gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"), img_filename_template=os.path.join(seq, "omni", "image-*.png"),
-                img_indices=list(range(n)), results_path=results)
-
-
-def _rgbd_kwargs(seq, n, results):
-    d = os.path.join(seq, "rgbd")
-    return dict(gt_poses_filename=os.path.join(d, "gt_TUM.txt"), img_filename_template=os.path.join(d, "rgb", "*.png"),
-                depth_filename_template=os.path.join(d, "depth", "*.png"), img_indices=list(range(n)), results_path=results)
-
-
-N_SEQ = 6
-
-
 @pytest.fixture(scope="module")
 def sos_sequences(tmp_path_factory):
-    gs, _ = _rig()
-    root = tmp_path_factory.mktemp("gated_sos")
-    seqs = []
-    for seed in (77, 61):
-        seq = str(root / ("seq_%d" % seed))
-        synthetic.write_sos_sequence(seq, gs, n_frames=N_SEQ, seed=seed, max_t=40.0, max_deg=2.0)
-        seqs.append(seq)
-    return seqs
+    return scenes.write_sos_sequences(tmp_path_factory.mktemp("gated_sos"))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -740,19 +442,19 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
     outs, files = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **kw, **_sos_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, **kw, **sos_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert files[5] == files[1] and "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[5]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())
     assert outs[0]["keyframe_ids"] == outs[5]["keyframe_ids"]
     res = str(tmp_path / "off")
-    off = run_VO(None, model, frame_window=5, gated_matching=False, **_sos_kwargs(seq, N_SEQ, res))
-    assert off["tracked"] == N_SEQ - 1 and _read(res)[0] != files[5][0]
+    off = run_VO(None, model, frame_window=5, gated_matching=False, **sos_kwargs(seq, N_SEQ, res))
+    assert off["tracked"] == N_SEQ - 1 and read_results(res)[0] != files[5][0]
     res = str(tmp_path / "none")                             # None is the tracker's own setting: off
-    run_VO(None, model, frame_window=5, gated_max_distance=80, **_sos_kwargs(seq, N_SEQ, res))
-    assert _read(res) == _read(str(tmp_path / "off"))
+    run_VO(None, model, frame_window=5, gated_max_distance=80, **sos_kwargs(seq, N_SEQ, res))
+    assert read_results(res) == read_results(str(tmp_path / "off"))
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -764,13 +466,13 @@ def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):
     want = []
     for k, seq in enumerate(sos_sequences):
         res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **_sos_kwargs(seq, N_SEQ, res))
+        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **sos_kwargs(seq, N_SEQ, res))
         assert out["tracked"] == N_SEQ - 1
-        want.append(_read(res))
-    many = [_sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
+        want.append(read_results(res))
+    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
     outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, **kw)
     for q, files, o in zip(many, want, outs):
-        assert _read(q["results_path"]) == files
+        assert read_results(q["results_path"]) == files
         assert o["sequence_mode"]["lanes"] == 2
     assert want[0] != want[1]
 
@@ -787,17 +489,17 @@ def test_rgbd_run_vo(ctx, tmp_path):
     files, outs = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, gated_matching=True, gated_max_distance=80, **_rgbd_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, gated_matching=True, gated_max_distance=80, **rgbd_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert files[5] == files[1]
     for (i, Ta), (_, Tb) in zip(outs[5]["poses"], outs[0]["poses"]):
         assert np.allclose(Ta, Tb, rtol=1e-9, atol=1e-12), (i, np.abs(Ta - Tb).max())
     res = str(tmp_path / "off")
-    run_VO(None, model, frame_window=5, **_rgbd_kwargs(seq, N_SEQ, res))
-    assert _read(res)[0] != files[5][0]
+    run_VO(None, model, frame_window=5, **rgbd_kwargs(seq, N_SEQ, res))
+    assert read_results(res)[0] != files[5][0]
     with pytest.raises(ValueError, match="no static-stereo matcher"):
-        run_VO(None, model, frame_window=5, gated_matching="stereo", **_rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
+        run_VO(None, model, frame_window=5, gated_matching="stereo", **rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
 
 
 # ---- 6. the relations of the definition ---------------------------------------------------------------------------------------
@@ -811,7 +513,7 @@ def test_plain_matches_are_a_subset_of_the_gated_ones_on_the_six_rendered_pairs(
     frame-to-frame (query, train) pairs of every pair and view among the gated ones; with cap 80 the same holds for the plain
     matches whose distance is within the cap."""
     B = 6
-    gs, rig_kw = _rig()
+    gs, rig_kw = scenes.rig()
     omni, _ = synthetic.make_frame_pairs(gs, B, seed=4100)
     model = DeviceImageModel(ctx, gs, (480, 640))
     fe = ImageFrontEnd(ctx, model, 2 * B, detection_method="GFT", num_of_features=1000, kp_cap=512)

@@ -14,13 +14,13 @@ import numpy as np
 import pytest
 import torch
 
+import matching_scenes as scenes
 import oracle
 import synth
+from matching_scenes import drive as _drive, rig as _rig, sos_kwargs as _sos_kwargs
 from vo_single_camera_sos_amd import synthetic
 from vo_single_camera_sos_amd.device import SosvoError
 from vo_single_camera_sos_amd.frontend import DeviceImageModel
-from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
-from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
 from vo_single_camera_sos_amd.pipeline import (MultiSequenceEngine, RGBDCamConfig, RGBDMultiSequenceEngine, RGBDSequenceEngine,
                                                RigConfig, SequenceEngine)
 
@@ -30,19 +30,6 @@ FILES = ("estimated_frame_poses_TUM.txt", "gt_associated_frame_poses_TUM.txt", "
 SOS_SEEDS, SOS_FRAMES = (77, 5, 61), (26, 17, 21)
 RGBD_SEEDS, RGBD_FRAMES = (41, 43), (14, 10)
 LIVE_THRESHOLDS = (0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0))      # run_VO_live's
-
-
-def _rig():
-    gs = synthetic_gums()
-    for m in (gs.top_model, gs.bot_model):
-        m.panorama = Panorama(m, width=1200)
-    gs.make_annulus_masks((480, 640))
-    pano = gs.top_model.panorama
-    geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
-    rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
-                  max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
-                  pct_good_matches=1.0)
-    return gs, rig_kw
 
 
 def _to(dev, *arrs):
@@ -111,21 +98,6 @@ def test_per_problem_seeds_equal_the_oracle_problem_by_problem(ctx, solver, adap
 
 
 # ---- 2. the engines against the single-sequence engines ---------------------------------------------------------------
-def _drive(eng, frames, window):
-    """What a VO loop asks of an engine: windows of frames; frame 0 becomes the keyframe, every later frame is also
-    tracked serially against the keyframe slot.  -> per frame (count, seed, spec, spec2, serial record)."""
-    out = []
-    for w0 in range(0, len(frames), window):
-        for i, info in enumerate(eng.push_window(list(frames[w0:w0 + window]))):
-            rec = None
-            if w0 + i == 0:
-                eng.promote(info["slot"])
-            else:
-                rec = eng.track(eng.key_slot, info["slot"], info["seed"])
-            out.append((info["count"], info["seed"], info["spec"], info["spec2"], rec))
-    return out
-
-
 def _same(a, b):
     return (a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b))
 
@@ -406,19 +378,12 @@ def test_run_vo_many_refuses_a_sequence_of_another_frame_size(ctx, tmp_path):
 
 # ---- 4 - 6. the whole path ----------------------------------------------------------------------------------------------
 def _read(results):
-    return tuple(open(os.path.join(results, f)).read() for f in FILES)
+    return scenes.read_results(results, FILES)
 
 
 @pytest.fixture(scope="module")
 def sos_sequences(tmp_path_factory):
-    gs, _ = _rig()
-    root = tmp_path_factory.mktemp("multi_sos")
-    seqs = []
-    for k, (seed, n) in enumerate(zip(SOS_SEEDS, SOS_FRAMES)):
-        seq = str(root / ("seq_%d" % k))
-        synthetic.write_sos_sequence(seq, gs, n_frames=n, seed=seed, max_t=40.0, max_deg=2.0)
-        seqs.append(seq)
-    return seqs
+    return scenes.write_sos_sequences(tmp_path_factory.mktemp("multi_sos"), SOS_SEEDS, SOS_FRAMES)
 
 
 def _sos_main(seqs, window, *extra):
@@ -447,11 +412,6 @@ def test_demo_with_several_sequences_writes_each_sequences_solo_files(ctx, sos_s
         assert sorted(o["sequence_mode"]["lane"] for o in outs2) in ([0, 0, 1], [0, 1, 1])
         for seq, want in zip(sos_sequences, solo):
             assert _read(os.path.join(seq, "results-omni")) == want, seq
-
-
-def _sos_kwargs(seq, n, results):
-    return dict(gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"), img_filename_template=os.path.join(seq, "omni", "image-*.png"),
-                img_indices=list(range(n)), results_path=results)
 
 
 def test_the_batched_serial_call_is_taken(ctx, sos_sequences, tmp_path):

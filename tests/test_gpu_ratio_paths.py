@@ -1,9 +1,10 @@
 """GPU: the ratio rule through the whole paths -- the stage-by-stage pipelines, the one-call batches and their streams form,
 the sequence and multi-sequence engines, run_VO with its window sizes and the mirror path, RGB-D -- against tests/refflow.py
-with its two matchers replaced by the definition (test_gpu_ratio_test.two_smallest_keys / ratio_rule), bit for bit; and the
-relations the definition implies on the six rendered pairs.
+with the definition (tests/refmatch.py) as its two matchers, bit for bit; and the relations the definition implies on the
+six rendered pairs.  ("The patched refflow" below is that: refflow under a setting's matchers.)
 
-The scenes are those of tests/test_gpu_gated_matching.py (its `pairs` and `rgbd` fixtures' sizes, its sequences).
+The scenes are those of tests/test_gpu_gated_matching.py (matching_scenes.omni_pairs / rgbd_pairs, built once for both modules,
+and its sequences).
 
 RATIO: the smallest of 48, 54 and 58 (in 64ths) for which, in the ratio-only settings, the patched refflow alone gives status
 0 and at least 20 correspondences for every pair (checked again on the CPU side of the fixtures below: a parity test on
@@ -15,19 +16,17 @@ sequence hops, the hop between the two unrelated pairs being the smallest): at r
 The stage-by-stage pipelines also run the two combinations of {ratio, gate, cross-check} the settings above leave out, at
 r = 54 too (neither starves; observed minima, stereo points per frame / correspondences per pair): both + gated at no cap,
 no cross-check 930 / 1088; gated + cross-check without the rule 805 / 984, RGB-D 233 correspondences (its smallest hop)."""
-import contextlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-import oracle
+import matching_scenes as scenes
 import refflow
-from test_gpu_gated_matching import (CX, CY, FILES, FX, FY, N_SEQ, _Pairs, _read, _record, _rgbd_kwargs, _rig, _sos_kwargs, rgbd,  # noqa: F401
-                                     sos_sequences)
-from test_gpu_ratio_test import IDX, NONE, gate_matrix, ratio_rule, two_smallest_keys
-from vo_single_camera_sos_amd import orb_pattern, synthetic
+from matching_scenes import CX, CY, FX, FY, N_SEQ, Setting, read_results, record, rgbd_kwargs, sos_kwargs
+from refmatch import Matching
+from vo_single_camera_sos_amd import synthetic
 from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
 from vo_single_camera_sos_amd.pipeline import (FramePairBatch, FramePairPipeline, RGBDCamConfig, RGBDPairBatch, RGBDPairPipeline,
                                                RigConfig)
@@ -38,121 +37,14 @@ RATIO = 54            # in 64ths (0.84375); the observed minimum over the ratio-
 MIN_CORR = 20
 
 
-# ---- the reference flow under a setting -------------------------------------------------------------------------------------
-def matches_under(qd, td, qp, tp, gate, cap, mutual, r):
-    """refflow.match_sorted of one problem.  gate = (min_dv, max_du) or None for the plain search; r: the ratio in 64ths or
-    None; mutual: keep query i only if the role-swapped 1-NN search (under the reversed gate, WITHOUT the rule) of its train
-    returns i."""
-    if len(qd) == 0 or len(td) == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return z, z, z
-    cap = 256 if cap is None or gate is None else cap
-    k1, k2 = two_smallest_keys(qd, td, None if gate is None else gate_matrix(qp, tp, gate[0], gate[1]))
-    fwd = ratio_rule(k1, k2, r, gate is not None, cap) if r else np.where((k1 >> 20) > cap, np.uint32(NONE), k1)
-    keep = fwd != NONE
-    if mutual:
-        rev, _ = two_smallest_keys(td, qd, None if gate is None else gate_matrix(tp, qp, gate[0], gate[1], reverse=True))
-        rev = np.where((rev >> 20) > cap, np.uint32(NONE), rev)
-        back = rev[np.where(keep, fwd & IDX, 0)]
-        keep &= (back != NONE) & ((back & IDX) == np.arange(len(qd)))
-    kept = np.nonzero(keep)[0]
-    k = fwd[kept]
-    order = oracle.sort_matches(k) if len(k) else np.zeros(0, np.int64)
-    return kept[order].astype(np.int64), (k[order] & IDX).astype(np.int64), (k[order] >> 20).astype(np.int64)
-
-
-def stereo_frame_under(s):
-    """refflow.stereo_frame with the bucket matcher replaced (the lines around it are refflow's)."""
-    def stereo_frame(rig, kp_top, kp_bot, desc_top, desc_bot):
-        mt, mb, dt, db = [], [], [], []
-        n_cand = 0
-        gate = (rig.stereo_min_disp, rig.stereo_max_hdiff) if s.gated else None
-        for kt, kb, et, eb in zip(kp_top, kp_bot, desc_top, desc_bot):
-            if len(kt) == 0 or len(kb) == 0:
-                continue
-            q, t, _ = matches_under(eb, et, kb, kt, gate, s.cap, s.cc, s.r if s.stereo else None)   # query = bottom, train = top
-            good = int(rig.pct_good_matches * len(q))
-            q, t = q[:good], t[:good]
-            n_cand += good
-            mt.append(kt[t])
-            mb.append(kb[q])
-            dt.append(et[t])
-            db.append(eb[q])
-        if not mt:
-            e2, e3, e32 = np.zeros((0, 2), np.float32), np.zeros((0, 3)), np.zeros((0, 32), np.uint8)
-            return dict(m_top=e2, m_bot=e2, d_top=e32, d_bot=e32, X=e3, b_top=e3, b_bot=e3, n_cand=0)
-        mt, mb = np.concatenate(mt).astype(np.float32), np.concatenate(mb).astype(np.float32)
-        dt, db = np.concatenate(dt), np.concatenate(db)
-        ok = oracle.pixel_gates(mt.astype(np.float64), mb.astype(np.float64), rig.stereo_min_disp, rig.stereo_max_hdiff)
-        mt, mb, dt, db = mt[ok], mb[ok], dt[ok], db[ok]
-        az1, el1 = oracle.pano_to_angles(mt[:, 0], mt[:, 1], *rig.pano_top)
-        az2, el2 = oracle.pano_to_angles(mb[:, 0], mb[:, 1], *rig.pano_bot)
-        bt, bb = oracle.angles_to_bearing(az1, el1), oracle.angles_to_bearing(az2, el2)
-        X = oracle.triangulate_midpoint(az1, el1, az2, el2, rig.F_top, rig.F_bot)
-        good = oracle.range_filter_homo(X, rig.min_range, rig.max_range)
-        return dict(m_top=mt[good], m_bot=mb[good], d_top=dt[good], d_bot=db[good], X=X[good], b_top=bt[good], b_bot=bb[good],
-                    n_cand=n_cand)
-    return stereo_frame
-
-
-def f2f_view_under(s):
-    """refflow.f2f_view with the matcher replaced; the gate is off exactly when the view's own |du| gate is."""
-    def f2f_view(rig, m_train, d_train, m_query, d_query):
-        gate = (-1.0, rig.f2f_max_hdiff if rig.f2f_max_hdiff >= 0 else -1.0) if s.gated else None
-        q, t, _ = matches_under(d_query, d_train, np.asarray(m_query, np.float32)[:, :2], np.asarray(m_train, np.float32)[:, :2],
-                                gate, s.cap, s.cc, s.r if s.f2f else None)
-        good = int(rig.pct_good_matches * len(q))
-        q, t = q[:good], t[:good]
-        if good > 0 and rig.f2f_max_hdiff >= 0:
-            pt, pq = np.zeros((good, 2)), np.zeros((good, 2))
-            pt[:, 0], pq[:, 0] = m_train[t, 0], m_query[q, 0]
-            ok = oracle.pixel_gates(pt, pq, -1, rig.f2f_max_hdiff)
-            q, t = q[ok], t[ok]
-        return t, q
-    return f2f_view
-
-
-class Setting(object):
-    """stereo / f2f: the ratio rule in that matcher; gated (+ cap) and cc: the other two switches, in both matchers."""
-
-    def __init__(self, name, stereo, f2f, gated=False, cap=None, cc=False, r=RATIO):
-        self.name, self.stereo, self.f2f, self.gated, self.cap, self.cc, self.r = name, stereo, f2f, gated, cap, cc, r
-
-    @property
-    def ratio_only(self):
-        return not (self.gated or self.cc) and (self.stereo or self.f2f)
-
-    def omni_kw(self):
-        return dict(ratio_stereo=self.stereo, ratio_f2f=self.f2f, ratio=self.r / 64.0, gated_stereo=self.gated, gated_f2f=self.gated,
-                    gated_max_distance=self.cap, cross_check_stereo=self.cc, cross_check_f2f=self.cc)
-
-    def rgbd_kw(self):
-        return dict(ratio_f2f=self.f2f, ratio=self.r / 64.0, gated_f2f=self.gated, gated_max_distance=self.cap, cross_check=self.cc)
-
-    def run_vo_kw(self):
-        value = "both" if self.stereo and self.f2f else "stereo" if self.stereo else "f2f" if self.f2f else None
-        return dict(ratio_test=value, ratio=self.r / 64.0, gated_matching=True if self.gated else None, gated_max_distance=self.cap,
-                    cross_check=True if self.cc else None)
-
-
-@contextlib.contextmanager
-def patched_refflow(s):
-    """refflow with the setting's matchers in static stereo (stereo_frame) and frame to frame (f2f_view)."""
-    stereo_frame, f2f_view = refflow.stereo_frame, refflow.f2f_view
-    refflow.stereo_frame, refflow.f2f_view = stereo_frame_under(s), f2f_view_under(s)
-    try:
-        yield
-    finally:
-        refflow.stereo_frame, refflow.f2f_view = stereo_frame, f2f_view
-
-
-SETTINGS = [Setting("stereo", True, False), Setting("f2f", False, True), Setting("both", True, True),
-            Setting("both_with_cross_check", True, True, cc=True),
-            Setting("both_gated_cap80_with_cross_check", True, True, gated=True, cap=80, cc=True)]
-OFF = Setting("off", False, False)
+# ---- the settings ------------------------------------------------------------------------------------------------------------
+SETTINGS = [Setting("stereo", ratio="stereo", r=RATIO), Setting("f2f", ratio="f2f", r=RATIO), Setting("both", ratio="both", r=RATIO),
+            Setting("both_with_cross_check", ratio="both", cc=True, r=RATIO),
+            Setting("both_gated_cap80_with_cross_check", ratio="both", gate=True, cap=80, cc=True, r=RATIO)]
+OFF = Setting("off", r=RATIO)
 # the combinations of {ratio, gate, cross-check} the settings above leave out: for the stage-by-stage pipelines only
-GATED_NO_CC = Setting("both_gated", True, True, gated=True)
-GATED_CC_NO_RATIO = Setting("gated_with_cross_check", False, False, gated=True, cc=True)
+GATED_NO_CC = Setting("both_gated", ratio="both", gate=True, r=RATIO)
+GATED_CC_NO_RATIO = Setting("gated_with_cross_check", gate=True, cc=True, r=RATIO)
 BY_NAME = {s.name: s for s in SETTINGS + [GATED_NO_CC, GATED_CC_NO_RATIO]}
 NAMES = [s.name for s in SETTINGS]
 
@@ -166,65 +58,49 @@ def _starvation_check(name, tracks):
     assert min(n) >= MIN_CORR and not any(status), (name, n, status)
 
 
-def make_pairs(ctx):
+@pytest.fixture(scope="module")
+def pairs(ctx):
     """The scene of test_gpu_gated_matching's `pairs`: 2 rendered pairs (GFT 330 features), the front end on the GPU, the
     detection on the oracle (once, shared), the trackers' solver settings."""
-    s = _Pairs()
-    s.B, s.nfeat, s.seed = 2, 330, 5
-    s.solver = dict(max_iter=210, adaptive=True, ransac_solver="GP3P")
-    gs, s.rig_kw = _rig()
-    s.omni, _ = synthetic.make_frame_pairs(gs, s.B, seed=99)
-    s.model = DeviceImageModel(ctx, gs, (480, 640))
-    s.fe = ImageFrontEnd(ctx, s.model, 2 * s.B, detection_method="GFT", num_of_features=s.nfeat)
-    s.fe.load_frames(s.omni)
-    s.fe.run()
-    ctx.synchronize()
-    ca, sa = orb_pattern.angle_cos_sin(-1.0)
-    im = refflow.ImageModel(s.model.map_x.cpu().numpy(), s.model.map_y.cpu().numpy(), s.model.omni_masks.cpu().numpy(),
-                            s.model.mask_bits_host, 12, s.nfeat, orb_pattern.orb_pattern(), ca, sa, method="GFT", kp_cap=s.fe.kp_cap)
-    s.views = [[refflow.detect_view(im, s.omni[f], v)[:2] for v in range(2)] for f in range(2 * s.B)]
-    s.rp = refflow.RigParams(**s.rig_kw)
-    s.thr = float(1.0 - np.cos(np.deg2rad(5.0)))
-    s.cache = {}
-
-    def reference(setting):
-        """-> (frames, pair tracks with seed + i, sequence tracks of (t - 1, t) with seed t - 1) under the setting."""
-        if setting.name not in s.cache:
-            with patched_refflow(setting):
-                frames = [refflow.stereo_frame(s.rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
-                track = lambda a, b, seed: refflow.track_pair(s.rp, frames[a], frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
-                                                              gp3p=True)
-                s.cache[setting.name] = (frames, [track(2 * i, 2 * i + 1, s.seed + i) for i in range(s.B)],
-                                         [track(t - 1, t, t - 1) for t in range(1, 2 * s.B)])
-            assert refflow.stereo_frame.__name__ == "stereo_frame" and refflow.f2f_view.__module__ == "refflow"
-            if setting.ratio_only:
-                _starvation_check(setting.name, s.cache[setting.name][1] + s.cache[setting.name][2])
-        return s.cache[setting.name]
-    s.reference = reference
-    return s
+    return scenes.omni_pairs(ctx)
 
 
 @pytest.fixture(scope="module")
-def pairs(ctx):
-    return make_pairs(ctx)
+def rgbd(ctx):
+    return scenes.rgbd_pairs(ctx)
+
+
+@pytest.fixture(scope="module")
+def sos_sequences(tmp_path_factory):
+    return scenes.write_sos_sequences(tmp_path_factory.mktemp("ratio_sos"))
+
+
+def reference(s, setting):
+    """-> (frames, pair tracks with seed + i, sequence tracks of (t - 1, t) with seed t - 1) of the scene under the setting."""
+    out = s.frames(setting), s.pair_tracks(setting), s.hop_tracks(setting)
+    if setting.ratio_only:
+        _starvation_check(setting.name, out[1] + out[2])
+    return out
 
 
 def test_the_patched_refflow_without_a_switch_is_refflow(pairs):
-    """The replaced matchers with every switch off give refflow's own frames and tracks: the patch changes the matcher only."""
+    """The definition with every switch off (matching=Matching()) gives the frames and tracks of refflow's own matcher
+    (matching=None)."""
     s = pairs
-    frames, tracks, _ = s.reference(OFF)
+    assert OFF.matchings() == (Matching(), Matching())
+    frames, tracks, _ = reference(s, OFF)
     plain = [refflow.stereo_frame(s.rp, v[0][0], v[1][0], v[0][1], v[1][1]) for v in s.views]
     for a, b in zip(frames, plain):
         assert all(np.array_equal(a[k], b[k]) for k in ("m_top", "m_bot", "d_top", "d_bot", "X")) and a["n_cand"] == b["n_cand"]
     w = refflow.track_pair(s.rp, plain[0], plain[1], s.thr, 210, seed=s.seed, adaptive=True, gp3p=True)
-    assert np.array_equal(_record(w).view(np.uint64), _record(tracks[0]).view(np.uint64))
+    assert np.array_equal(record(w).view(np.uint64), record(tracks[0]).view(np.uint64))
 
 
 # ---- the omni paths --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES + [GATED_NO_CC.name, GATED_CC_NO_RATIO.name])
 def test_pair_pipeline_stage_by_stage_equals_the_patched_refflow(ctx, pairs, name):
     s, setting = pairs, BY_NAME[name]
-    frames, want, _ = s.reference(setting)
+    frames, want, _ = reference(s, setting)
     pipe = FramePairPipeline(ctx, RigConfig(**s.rig_kw), s.B, frame_cap=2048, seed=s.seed, front_end=s.fe, **s.solver,
                              **setting.omni_kw())
     pipe.stereo()
@@ -244,19 +120,19 @@ def test_pair_pipeline_stage_by_stage_equals_the_patched_refflow(ctx, pairs, nam
         n = len(w["corr"]["cam"])
         assert n > 0 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
-        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64))
-    off = s.reference(OFF)
-    if setting.stereo and not setting.gated:                  # the rule only removes stereo points, and it removes some
+        assert np.array_equal(rec[i].view(np.uint64), record(w).view(np.uint64))
+    off = reference(s, OFF)
+    if setting.ratio_stereo and not setting.gate:             # the rule only removes stereo points, and it removes some
         assert all(len(a["X"]) <= len(b["X"]) for a, b in zip(frames, off[0]))
         assert sum(len(a["X"]) for a in frames) < sum(len(b["X"]) for b in off[0])
-    if not setting.stereo and not setting.cc and not setting.gated:   # the stereo stage is untouched by the f2f switch
+    if not setting.changes_stereo:                            # the stereo stage is untouched by the f2f switch
         assert all(np.array_equal(a["X"], b["X"]) for a, b in zip(frames, off[0]))
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_one_call_batches_and_streams_equal_the_patched_refflow(ctx, pairs, name):
     s, setting = pairs, BY_NAME[name]
-    want = np.stack([_record(w) for w in s.reference(setting)[1]])
+    want = np.stack([record(w) for w in reference(s, setting)[1]])
     kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, seed=s.seed, **s.solver, **setting.omni_kw())
     for ns in (1, 2):
         batch = FramePairBatch(ctx, s.model, RigConfig(**s.rig_kw), s.B, n_streams=ns, **kw)
@@ -274,14 +150,14 @@ def test_one_call_batches_and_streams_equal_the_patched_refflow(ctx, pairs, name
             ctx.synchronize()
             for b in bufs:
                 assert np.array_equal(b.cpu().numpy().view(np.uint64), want.view(np.uint64))
-    assert not np.array_equal(want[:, :12], np.stack([_record(w) for w in s.reference(OFF)[1]])[:, :12])
+    assert not np.array_equal(want[:, :12], np.stack([record(w) for w in reference(s, OFF)[1]])[:, :12])
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_sequence_engines_equal_the_patched_refflow_for_windows_1_and_5(ctx, pairs, name):
     from vo_single_camera_sos_amd.pipeline import SequenceEngine
     s, setting = pairs, BY_NAME[name]
-    want = np.stack([_record(w) for w in s.reference(setting)[2]])
+    want = np.stack([record(w) for w in reference(s, setting)[2]])
     kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, **s.solver, **setting.omni_kw())
     n = 2 * s.B
     for window in (1, 5):
@@ -300,13 +176,11 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
     its predecessor, seed t - 1) and its serial record against the keyframe slot (the lanes' serial calls of one moment share a
     launch) equal the patched refflow bit for bit."""
     import threading
-    from test_gpu_multi_sequence import _drive
     from vo_single_camera_sos_amd.pipeline import MultiSequenceEngine
     s, setting = pairs, BY_NAME[name]
-    frames, _, hops = s.reference(setting)
-    with patched_refflow(setting):          # (0, t) with the seed of frame t: what the serial call against the keyframe computes
-        serial = [None] + [_record(refflow.track_pair(s.rp, frames[0], frames[t], s.thr, 210, seed=t - 1, adaptive=True, gp3p=True))
-                           for t in range(1, 2 * s.B)]
+    frames, _, hops = reference(s, setting)
+    # (0, t) with the seed of frame t: what the serial call against the keyframe computes
+    serial = [None] + [record(s.track(setting, 0, t, t - 1)) for t in range(1, 2 * s.B)]
     kw = dict(num_of_features=s.nfeat, kp_cap=s.fe.kp_cap, frame_cap=2048, **s.solver, **setting.omni_kw())
     multi = MultiSequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), lanes=2, window=2, **kw)
     assert multi.slots == 2 * (2 * 2 + 1) and multi.cfg.n_pairs == 2 * 2
@@ -315,7 +189,7 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
 
     def work(lane):
         try:
-            got[lane] = _drive(multi.lane(lane), sequences[lane], 2)
+            got[lane] = scenes.drive(multi.lane(lane), sequences[lane], 2)
         except BaseException as e:  # noqa: B902
             errors.append(e)
         finally:
@@ -336,32 +210,29 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
                 assert spec is None and rec is None
                 continue
             assert seed == t - 1
-            assert np.array_equal(np.asarray(spec).view(np.uint64), _record(hops[t - 1]).view(np.uint64)), (lane, t, "speculative")
+            assert np.array_equal(np.asarray(spec).view(np.uint64), record(hops[t - 1]).view(np.uint64)), (lane, t, "speculative")
             assert np.array_equal(np.asarray(rec).view(np.uint64), serial[t].view(np.uint64)), (lane, t, "serial")
     c = multi.counters
     assert c["front_end_launches"] == c["rounds"] == 2 and c["max_serial_pairs"] == 2
 
 
 # ---- RGB-D -------------------------------------------------------------------------------------------------------------------
-RGBD_SETTINGS = [Setting("f2f", False, True), Setting("f2f_with_cross_check", False, True, cc=True),
-                 Setting("f2f_gated", False, True, gated=True), GATED_CC_NO_RATIO]
+RGBD_SETTINGS = [Setting("f2f", ratio="f2f", r=RATIO), Setting("f2f_with_cross_check", ratio="f2f", cc=True, r=RATIO),
+                 Setting("f2f_gated", ratio="f2f", gate=True, r=RATIO), GATED_CC_NO_RATIO]
 
 
 @pytest.mark.parametrize("setting", RGBD_SETTINGS, ids=[x.name for x in RGBD_SETTINGS])
-def test_rgbd_pair_paths_and_sequence_equal_the_patched_refflow(ctx, rgbd, setting):  # noqa: F811
+def test_rgbd_pair_paths_and_sequence_equal_the_patched_refflow(ctx, rgbd, setting):
     from vo_single_camera_sos_amd.pipeline import RGBDSequenceEngine
     s = rgbd
-    track = lambda a, b, seed: refflow.track_pair_rgbd(s.rc, s.frames[a], s.frames[b], s.thr, 210, seed=seed, adaptive=True,  # noqa: E731
-                                                       epnp=True)
-    with patched_refflow(setting):
-        want = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
-        want_seq_tracks = [track(t - 1, t, t - 1) for t in range(1, 2 * s.B)]
-    want_seq = np.stack([_record(w) for w in want_seq_tracks])
+    want = [s.track(setting, 2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+    want_seq_tracks = [s.track(setting, t - 1, t, t - 1) for t in range(1, 2 * s.B)]
+    want_seq = np.stack([record(w) for w in want_seq_tracks])
     print("rgbd setting %s at r = %d: correspondences of the patched refflow %s"
           % (setting.name, setting.r, [len(w["corr"]["q"]) for w in want + want_seq_tracks]))
     if setting.ratio_only:
         _starvation_check("rgbd " + setting.name, want + want_seq_tracks)
-    plain = [track(2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
+    plain = [s.track(None, 2 * i, 2 * i + 1, 31 + i) for i in range(s.B)]
     pipe = RGBDPairPipeline(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
     pipe.load_frames(s.bgr, s.depth)
     pipe.step()
@@ -371,7 +242,7 @@ def test_rgbd_pair_paths_and_sequence_equal_the_patched_refflow(ctx, rgbd, setti
         n = len(w["corr"]["q"])
         assert n > 0 and np.array_equal(cq[i, :n], w["corr"]["q"]) and np.array_equal(ct[i, :n], w["corr"]["t"])
         assert np.array_equal(mask[i, :n].astype(bool), w["ransac"]["mask"])
-        assert np.array_equal(rec[i].view(np.uint64), _record(w).view(np.uint64))
+        assert np.array_equal(rec[i].view(np.uint64), record(w).view(np.uint64))
         if setting.ratio_only:                               # the kept correspondences are a proper subset of the plain ones
             assert set(zip(w["corr"]["q"], w["corr"]["t"])) < set(zip(plain[i]["corr"]["q"], plain[i]["corr"]["t"]))
     one = RGBDPairBatch(ctx, s.cam, s.B, seed=31, **s.kw, **setting.rgbd_kw())
@@ -415,7 +286,7 @@ def test_omni_batch_refuses_a_switch_without_a_ratio(ctx, pairs):
 
 # ---- run_VO: the sequence engines and the mirror path -----------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES)
-def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):  # noqa: F811
+def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
     """The pose files are byte-identical for frame windows 5 and 1 and for the per-frame mirror path (frame_window 0: the
     FeatureMatcher objects of the camera model carry the ratio and apply it on the device)."""
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -425,8 +296,8 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):  # 
     outs, files = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **kw, **_sos_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, **kw, **sos_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
     assert files[5] == files[1] and outs[0]["keyframe_ids"] == outs[5]["keyframe_ids"]
@@ -434,14 +305,14 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):  # 
         float(np.abs(Ta - Tb).max()) for (_, Ta), (_, Tb) in zip(outs[0]["poses"], outs[5]["poses"])))
     assert files[0] == files[5]
     res = str(tmp_path / "off")
-    off = run_VO(None, model, frame_window=5, ratio_test=False, **_sos_kwargs(seq, N_SEQ, res))
-    assert off["tracked"] == N_SEQ - 1 and _read(res)[0] != files[5][0]
+    off = run_VO(None, model, frame_window=5, ratio_test=False, **sos_kwargs(seq, N_SEQ, res))
+    assert off["tracked"] == N_SEQ - 1 and read_results(res)[0] != files[5][0]
     res = str(tmp_path / "none")                             # None is the tracker's own setting: off
-    run_VO(None, model, frame_window=5, ratio=0.75, **_sos_kwargs(seq, N_SEQ, res))
-    assert _read(res) == _read(str(tmp_path / "off"))
+    run_VO(None, model, frame_window=5, ratio=0.75, **sos_kwargs(seq, N_SEQ, res))
+    assert read_results(res) == read_results(str(tmp_path / "off"))
 
 
-def test_run_vo_mirror_path_pose_file_is_byte_identical_to_the_engines_without_a_switch(ctx, sos_sequences, tmp_path):  # noqa: F811
+def test_run_vo_mirror_path_pose_file_is_byte_identical_to_the_engines_without_a_switch(ctx, sos_sequences, tmp_path):
     """With every switch off too: the per-frame mirror path takes its direction angles and bearings from the stage the engines'
     stereo assembly uses (sosvo_pano_to_bearing), so its pose file is the engines' byte for byte.  (With numpy's arithmetic
     there, one elevation in 70 differed in its last bit and the poses in their 15th digit: at most 3.98e-15.)"""
@@ -452,15 +323,15 @@ def test_run_vo_mirror_path_pose_file_is_byte_identical_to_the_engines_without_a
     files, outs = {}, {}
     for w in (5, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **_sos_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, **sos_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
     print("max |pose difference| mirror path against window 5: %.3e" % max(
         float(np.abs(Ta - Tb).max()) for (_, Ta), (_, Tb) in zip(outs[0]["poses"], outs[5]["poses"])))
     assert outs[0]["tracked"] == N_SEQ - 1 and files[0] == files[5]
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):  # noqa: F811
+def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):
     """Two sequences through the two lanes of one MultiSequenceEngine (run_VO_many) write the pose and keyframe files of their
     solo run_VO runs, byte for byte."""
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -470,27 +341,27 @@ def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):  
     want = []
     for k, seq in enumerate(sos_sequences):
         res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **_sos_kwargs(seq, N_SEQ, res))
+        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **sos_kwargs(seq, N_SEQ, res))
         assert out["tracked"] == N_SEQ - 1
-        want.append(_read(res))
-    many = [_sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
+        want.append(read_results(res))
+    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
     outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, **kw)
     for q, files, o in zip(many, want, outs):
-        assert _read(q["results_path"]) == files
+        assert read_results(q["results_path"]) == files
         assert o["sequence_mode"]["lanes"] == 2
     assert want[0] != want[1]
     res = str(tmp_path / "off")                              # (the rule did something to these sequences)
-    run_VO(None, load_gums_json(gums), frame_window=5, **_sos_kwargs(sos_sequences[0], N_SEQ, res))
-    assert _read(res)[0] != want[0][0]
+    run_VO(None, load_gums_json(gums), frame_window=5, **sos_kwargs(sos_sequences[0], N_SEQ, res))
+    assert read_results(res)[0] != want[0][0]
 
 
-def test_run_vo_refuses_a_ratio_that_is_no_64th(ctx, sos_sequences, tmp_path):  # noqa: F811
+def test_run_vo_refuses_a_ratio_that_is_no_64th(ctx, sos_sequences, tmp_path):
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     seq = sos_sequences[0]
     model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
     with pytest.raises(ValueError, match="nearest admissible"):
-        run_VO(None, model, frame_window=5, ratio_test=True, ratio=0.8, **_sos_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
+        run_VO(None, model, frame_window=5, ratio_test=True, ratio=0.8, **sos_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
 
 
 def test_rgbd_run_vo(ctx, tmp_path):
@@ -505,31 +376,31 @@ def test_rgbd_run_vo(ctx, tmp_path):
     files, outs = {}, {}
     for w in (5, 1, 0):
         res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, ratio_test=True, ratio=RATIO / 64.0, **_rgbd_kwargs(seq, N_SEQ, res))
-        files[w] = _read(res)
+        outs[w] = run_VO(None, model, frame_window=w, ratio_test=True, ratio=RATIO / 64.0, **rgbd_kwargs(seq, N_SEQ, res))
+        files[w] = read_results(res)
         assert outs[w]["tracked"] == N_SEQ - 1
     assert files[5] == files[1] and files[0] == files[5]
     res = str(tmp_path / "off")
-    run_VO(None, model, frame_window=5, **_rgbd_kwargs(seq, N_SEQ, res))
-    assert _read(res)[0] != files[5][0]
+    run_VO(None, model, frame_window=5, **rgbd_kwargs(seq, N_SEQ, res))
+    assert read_results(res)[0] != files[5][0]
     with pytest.raises(ValueError, match="no static-stereo matcher"):
-        run_VO(None, model, frame_window=5, ratio_test="stereo", ratio=0.75, **_rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
+        run_VO(None, model, frame_window=5, ratio_test="stereo", ratio=0.75, **rgbd_kwargs(seq, N_SEQ, str(tmp_path / "bad")))
 
 
 # ---- the mirror matcher against the definition -------------------------------------------------------------------------------
 def test_feature_matcher_with_a_ratio_equals_the_definition(ctx):
-    from test_gpu_ratio_test import _scene
     from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
     rng = np.random.default_rng(5)
-    desc, pos = _scene(rng, 2, 320, np.array([257, 300]))
+    desc, pos = scenes.descriptor_scene(rng, 2, 320, np.array([257, 300]))
     q, t, qp, tp = desc[1, :300], desc[0, :257], pos[1, :300], pos[0, :257]
     fm = FeatureMatcher("ORB", "BF", 1, context=ctx, ratio=0.75)
     plain = FeatureMatcher("ORB", "BF", 1, context=ctx).match(q, t)
-    for got, want in ((fm.match(q, t), matches_under(q, t, qp, tp, None, None, False, 48)),
-                      (fm.match_gated(q, t, qp, tp, 1.0, 2.5), matches_under(q, t, qp, tp, (1.0, 2.5), None, False, 48)),
-                      (fm.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=4), matches_under(q, t, qp, tp, (1.0, 2.5), 4, False, 48)),
+    gate = (1.0, 2.5)
+    for got, want in ((fm.match(q, t), Matching(ratio=48)(q, t, qp, tp, None)),
+                      (fm.match_gated(q, t, qp, tp, 1.0, 2.5), Matching(gated=True, ratio=48)(q, t, qp, tp, gate)),
+                      (fm.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=4), Matching(gated=True, cap=4, ratio=48)(q, t, qp, tp, gate)),
                       (MatchListOf(fm.match_arrays_many([(q, t), (t, q), (q[:0], t), (q, t[:1])])[0]),
-                       matches_under(q, t, qp, tp, None, None, False, 48))):
+                       Matching(ratio=48)(q, t, qp, tp, None))):
         wq, wt, wd = want
         assert 0 < len(wq) < 300
         assert np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
@@ -538,8 +409,9 @@ def test_feature_matcher_with_a_ratio_equals_the_definition(ctx):
     assert len(many[2][0]) == 0 and len(many[3][0]) == 0      # no query; a single train: no runner-up, dropped in the plain form
     assert len(fm.match_gated(q[:1], t[:1], qp[:1], qp[:1] + np.float32([0.0, 2.0]), 1.0, 2.5)) == 1   # ... kept in the gated one
     fmc = FeatureMatcher("ORB", "BF", 1, context=ctx, ratio=0.75, cross_check=True)
-    for got, want in ((fmc.match(q, t), matches_under(q, t, qp, tp, None, None, True, 48)),
-                      (fmc.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=80), matches_under(q, t, qp, tp, (1.0, 2.5), 80, True, 48))):
+    for got, want in ((fmc.match(q, t), Matching(mutual=True, ratio=48)(q, t, qp, tp, None)),
+                      (fmc.match_gated(q, t, qp, tp, 1.0, 2.5, max_distance=80),
+                       Matching(gated=True, cap=80, mutual=True, ratio=48)(q, t, qp, tp, gate))):
         wq, wt, wd = want
         assert 0 < len(wq) and np.array_equal(got.query_idx, wq) and np.array_equal(got.train_idx, wt) and np.array_equal(got.distances, wd)
 
@@ -555,7 +427,7 @@ def test_kept_matches_are_matches_without_the_rule_and_grow_with_the_ratio(ctx):
     stereo point / frame-to-frame correspondence kept under a ratio setting is one of the same setting without the rule, and
     the kept counts do not fall as r grows (32, 48, 58, 63)."""
     B = 6
-    gs, rig_kw = _rig()
+    gs, rig_kw = scenes.rig()
     omni, _ = synthetic.make_frame_pairs(gs, B, seed=4100)
     model = DeviceImageModel(ctx, gs, (480, 640))
     fe = ImageFrontEnd(ctx, model, 2 * B, detection_method="GFT", num_of_features=1000, kp_cap=512)

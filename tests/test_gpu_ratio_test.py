@@ -1,94 +1,26 @@
 """GPU: Lowe's ratio rule fused into the matrix-core matcher (sosvo_match_hamming_ratio), stage level.
 
-The CPU checker is the definition of include/sosvo.h written in numpy (two_smallest_keys / ratio_rule below): the popcount
-distance matrix, oracle.pixel_gates on doubles converted from the float32 positions, the two smallest packed keys over the
-admissible trains, the integer rule 64 * d1 < r * d2, the cap.  keys and rivals are compared bit for bit."""
+The CPU checker is the definition of include/sosvo.h written in numpy (tests/refmatch.py, two_smallest_keys / ratio_rule): the
+popcount distance matrix, oracle.pixel_gates on doubles converted from the float32 positions, the two smallest packed keys over
+the admissible trains, the integer rule 64 * d1 < r * d2, the cap.  keys and rivals are compared bit for bit."""
 import numpy as np
 import pytest
 import torch
 
 import oracle
+from matching_scenes import StageProblems, descriptor_scene as _scene
+from refmatch import NONE, capped, ratio_rule
 
 pytestmark = pytest.mark.gpu
 
-IDX, NONE = 0xFFFFF, 0xFFFFFFFF
-POPCOUNT = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
 RATIOS = (1, 48, 63)
 # (query count, train count) at the edges of the 32-query tiles, the 32-row blocks and the 128-train tiles
 COUNTS = ((1, 1), (1, 2), (33, 2), (31, 127), (32, 128), (33, 129), (129, 257))
 GROUPS = ((0, 1, 2), (3, 4, 5), (6, 0, 4))                       # three problems per call
 
 
-# ---- the definition ------------------------------------------------------------------------------------------------------
-def distances(q, t):
-    """[nq, nt] Hamming distances."""
-    return POPCOUNT[q[:, None, :] ^ t[None, :, :]].sum(-1, dtype=np.uint32)
-
-
-def gate_matrix(q_pos, t_pos, min_dv, max_du, reverse=False):
-    """gate(i, j) [nq, nt]: oracle.pixel_gates(train, query) on doubles converted from the float32 positions; a reversed
-    problem evaluates the same gate with the roles swapped."""
-    nq, nt = len(q_pos), len(t_pos)
-    qp = np.repeat(q_pos.astype(np.float64)[:, None, :], nt, 1).reshape(-1, 2)
-    tp = np.repeat(t_pos.astype(np.float64)[None, :, :], nq, 0).reshape(-1, 2)
-    ok = oracle.pixel_gates(qp, tp, min_dv, max_du) if reverse else oracle.pixel_gates(tp, qp, min_dv, max_du)
-    return ok.reshape(nq, nt)
-
-
-def two_smallest_keys(q, t, admissible=None):
-    """(k1, k2): the two smallest keys (hamming << 20 | j) over the admissible trains of every query, NONE where absent."""
-    nq, nt = len(q), len(t)
-    keys = np.full((nq, nt + 2), NONE, np.uint32)
-    if nq and nt:
-        k = (distances(q, t) << 20) | np.arange(nt, dtype=np.uint32)[None, :]
-        keys[:, :nt] = k if admissible is None else np.where(admissible, k, np.uint32(NONE))
-    keys.sort(axis=1)
-    return keys[:, 0].copy(), keys[:, 1].copy()
-
-
-def ratio_rule(k1, k2, r, gated, cap=256):
-    """keep(i) <=> 64 * d1 < r * d2; no runner-up: dropped in the plain form, kept in the gated one; then the cap."""
-    d1, d2 = (k1 >> 20).astype(np.int64), (k2 >> 20).astype(np.int64)
-    keep = np.where(k2 == NONE, bool(gated), 64 * d1 < r * d2) & (k1 != NONE) & (d1 <= cap)
-    return np.where(keep, k1, np.uint32(NONE)).astype(np.uint32)
-
-
-def _dev(ctx, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
-
-
-def _scene(rng, blocks, stride, counts, u_span=40.0, v_span=12.0):
-    """A descriptor / position store: every block re-observes block 0's first rows with 0-6 flipped bits at a position
-    jittered by a few pixels (distinctive matches), some rows are copies of each other (duplicates), the rest is random."""
-    desc = rng.integers(0, 256, (blocks, stride, 32), dtype=np.uint8)
-    pos = np.stack([rng.uniform(0, u_span, (blocks, stride)), rng.uniform(0, v_span, (blocks, stride))], -1).astype(np.float32)
-    n0 = max(1, int(counts[0]))
-    for b in range(blocks):
-        n = int(counts[b])
-        for i in range(0, n, 2):
-            src = int(rng.integers(0, n0))
-            d = desc[0, src].copy()
-            for bit in rng.integers(0, 256, rng.integers(0, 7)):
-                d[bit >> 3] ^= np.uint8(1 << (bit & 7))
-            desc[b, i] = d
-            pos[b, i] = pos[0, src] + rng.uniform(-3.0, 3.0, 2).astype(np.float32)
-        for i in range(5, n, 11):
-            desc[b, i] = desc[b, i - 3]
-    return desc, pos
-
-
-class _Stage(object):
-    """One set of problems on the device; the two smallest keys are computed once per (blocks, gate, direction)."""
-
-    def __init__(self, ctx, qd, td, qp, tp, nq, nt, q_slot=None, t_slot=None):
-        self.ctx, self.qd, self.td, self.qp, self.tp, self.nq, self.nt = ctx, qd, td, qp, tp, nq, nt
-        self.P = len(nq) if q_slot is None else len(q_slot)
-        self.qs = np.arange(self.P) if q_slot is None else q_slot
-        self.ts = np.arange(self.P) if t_slot is None else t_slot
-        self.d_qd, self.d_td, self.d_qp, self.d_tp = [_dev(ctx, a) for a in (qd, td, qp, tp)]
-        self.d_nq, self.d_nt = _dev(ctx, nq.astype(np.int32)), _dev(ctx, nt.astype(np.int32))
-        self.sl = {} if q_slot is None else dict(q_slot=_dev(ctx, q_slot.astype(np.int32)), t_slot=_dev(ctx, t_slot.astype(np.int32)))
-        self.cache = {}
+class _Stage(StageProblems):
+    """sosvo_match_hamming_ratio on the problems, the last P - n_forward of them reversed, against the definition."""
 
     def run(self, r, gate=None, cap=None, n_forward=None, **kw):
         pos = {} if gate is None else dict(q_pos=self.d_qp, t_pos=self.d_tp, min_dv=gate[0], max_du=gate[1], max_distance=cap)
@@ -98,23 +30,12 @@ class _Stage(object):
         self.ctx.synchronize()
         return keys.cpu().numpy()[:, :, 0], rivals.cpu().numpy()[:, :, 0]
 
-    def smallest(self, p, gate, reverse):
-        qs, ts = int(self.qs[p]), int(self.ts[p])
-        sig = (qs, ts, gate, reverse and gate is not None)
-        if sig not in self.cache:
-            n, m = min(int(self.nq[qs]), self.qd.shape[1]), min(int(self.nt[ts]), self.td.shape[1])
-            adm = None if gate is None else gate_matrix(self.qp[qs, :n], self.tp[ts, :m], gate[0], gate[1], reverse)
-            self.cache[sig] = two_smallest_keys(self.qd[qs, :n], self.td[ts, :m], adm)
-        return self.cache[sig]
-
     def expect(self, p, r, gate, cap, n_forward):
         """(keys, rivals or None) of problem p; a reversed problem's keys are the unfiltered, capped 1-NN keys."""
-        cap = 256 if cap is None else cap
         if p < n_forward:
             k1, k2 = self.smallest(p, gate, False)
-            return ratio_rule(k1, k2, r, gate is not None, cap), k2
-        k1, _ = self.smallest(p, gate, True)
-        return np.where((k1 >> 20) > cap, np.uint32(NONE), k1).astype(np.uint32), None
+            return ratio_rule(k1, k2, r, gate is not None, 256 if cap is None else cap), k2
+        return capped(self.smallest(p, gate, True)[0], cap), None
 
     def check(self, r, gate=None, cap=None, n_forward=None):
         nf = self.P if n_forward is None else n_forward

@@ -12,26 +12,12 @@ import os
 import numpy as np
 import pytest
 
+from matching_scenes import read_results as _result_files, rgbd_kwargs, rig as _rig, sos_kwargs
 from vo_single_camera_sos_amd import synthetic
 from vo_single_camera_sos_amd.frontend import DeviceImageModel
-from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
-from vo_single_camera_sos_amd.omnistereo.panorama import Panorama
 from vo_single_camera_sos_amd.pipeline import FramePairBatch, RigConfig, SequenceEngine
 
 pytestmark = pytest.mark.gpu
-
-
-def _rig():
-    gs = synthetic_gums()
-    for m in (gs.top_model, gs.bot_model):
-        m.panorama = Panorama(m, width=1200)
-    gs.make_annulus_masks((480, 640))
-    pano = gs.top_model.panorama
-    geo = (pano.cols, pano.rows, pano.pixel_size, pano.cyl_height_max)
-    rig_kw = dict(pano_top=geo, pano_bot=geo, F_top=gs.top_model.F[:3, 0], F_bot=gs.bot_model.F[:3, 0], min_range=500.0,
-                  max_range=7000.0, stereo_min_disp=1.0, stereo_max_hdiff=2.5, f2f_max_hdiff=0.125 * 0.5 * pano.cols,
-                  pct_good_matches=1.0)
-    return gs, rig_kw
 
 
 def _sequence_frames(gs, n, seed):
@@ -259,10 +245,6 @@ def _sos_run(seq, window):
                                     str(window)])
 
 
-def _result_files(results):
-    return tuple(open(os.path.join(results, f)).read() for f in ("estimated_frame_poses_TUM.txt", "keyframe_ids.txt"))
-
-
 def _tum(text):
     return np.array([[float(v) for v in line.split()] for line in text.splitlines()])
 
@@ -309,9 +291,7 @@ def test_run_vo_ended_by_an_error_writes_the_frames_before_it(ctx, tmp_path, mon
 
 def _sos_direct(model, seq, n, results, window):
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
-    out = run_VO(None, model, gt_poses_filename=os.path.join(seq, "omni", "gt_TUM.txt"),
-                 img_filename_template=os.path.join(seq, "omni", "image-*.png"), img_indices=list(range(n)),
-                 results_path=results, frame_window=window)
+    out = run_VO(None, model, frame_window=window, **sos_kwargs(seq, n, results))
     return out, _result_files(results)
 
 
@@ -326,10 +306,7 @@ def _rgbd_model():
 
 def _rgbd_direct(model, seq, n, results, window):
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
-    d = os.path.join(seq, "rgbd")
-    out = run_VO(None, model, gt_poses_filename=os.path.join(d, "gt_TUM.txt"), img_filename_template=os.path.join(d, "rgb", "*.png"),
-                 depth_filename_template=os.path.join(d, "depth", "*.png"), img_indices=list(range(n)), results_path=results,
-                 frame_window=window)
+    out = run_VO(None, model, frame_window=window, **rgbd_kwargs(seq, n, results))
     return out, _result_files(results)
 
 

@@ -11,7 +11,7 @@ import re
 import numpy as np
 import pytest
 
-from test_cross_check_cfg import _Engine, _Rig, _cfg, _lib_or_skip, _rgbd_cam, _rgbd_cfg, _tracker
+from cfg_fakes import Engine, Rig, cfg, lib_or_skip, rgbd_cam, rgbd_cfg, tracker
 from vo_single_camera_sos_amd import _lib
 from vo_single_camera_sos_amd.omnistereo.camera_models import FeatureMatcher
 from vo_single_camera_sos_amd.pipeline import batch_cfg, rgbd_batch_cfg, rgbd_solver_flags
@@ -126,7 +126,7 @@ def test_workspaces_change_only_with_a_switch_set():
     """With the switch bits clear -- the field set or not, the other features' switches set or not -- every workspace has
     the size it had; a switch with a ratio adds that step's rivals (one u32 per key of the step: doubled with the step's
     cross-check) and nothing else; a switch without a ratio, or the stereo switch for an RGB-D camera, is 0."""
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     r = ctypes.byref
     al = lambda n: (n + 255) & ~255                            # noqa: E731 -- the carver's alignment
     queries = ((lambda c: lib.sosvo_frame_pair_batch_workspace(r(c)), 2 * 4, 4),            # (query, frames of a window, pairs)
@@ -135,35 +135,35 @@ def test_workspaces_change_only_with_a_switch_set():
     for det in (0, 1):
         for q, window, pairs in queries:
             for o in others:
-                base = q(_cfg(o, det))
+                base = q(cfg(o, det))
                 assert base > 0
-                assert q(_cfg(o | R(48), det)) == base, (det, hex(o))            # the field alone is ignored
+                assert q(cfg(o | R(48), det)) == base, (det, hex(o))            # the field alone is ignored
                 n_stereo = (2 if o & CC_STEREO else 1) * window * 12 * 1024       # frames * nmask * kp_cap keys
                 n_f2f = (2 if o & CC_F2F else 1) * pairs * 2048                   # pairs * frame_cap keys (one buffer, both views)
-                assert q(_cfg(o | STEREO | R(48), det)) == base + al(4 * n_stereo), (det, hex(o))
-                assert q(_cfg(o | F2F | R(1), det)) == base + al(4 * n_f2f), (det, hex(o))
-                assert q(_cfg(o | STEREO | F2F | R(63), det)) == base + al(4 * n_stereo) + al(4 * n_f2f), (det, hex(o))
+                assert q(cfg(o | STEREO | R(48), det)) == base + al(4 * n_stereo), (det, hex(o))
+                assert q(cfg(o | F2F | R(1), det)) == base + al(4 * n_f2f), (det, hex(o))
+                assert q(cfg(o | STEREO | F2F | R(63), det)) == base + al(4 * n_stereo) + al(4 * n_f2f), (det, hex(o))
                 for sw in (STEREO, F2F, STEREO | F2F):                              # a switch needs a ratio
-                    assert q(_cfg(o | sw, det)) == 0, (det, hex(o), hex(sw))
+                    assert q(cfg(o | sw, det)) == 0, (det, hex(o), hex(sw))
         streams = lambda c: lib.sosvo_frame_pair_batch_streams_workspace(r(c), 2)    # noqa: E731
-        base = streams(_cfg(0, det))
-        assert base > 0 and streams(_cfg(R(48), det)) == base and streams(_cfg(STEREO, det)) == 0
-        assert streams(_cfg(STEREO | F2F | R(48), det)) > base
+        base = streams(cfg(0, det))
+        assert base > 0 and streams(cfg(R(48), det)) == base and streams(cfg(STEREO, det)) == 0
+        assert streams(cfg(STEREO | F2F | R(48), det)) > base
     rqueries = (lambda c: lib.sosvo_rgbd_pair_batch_workspace(r(c)), lambda c: lib.sosvo_rgbd_sequence_workspace(r(c), 8, 17))
     for method in ("GFT", "ORB"):
         for q in rqueries:
             for o in (0, CC_F2F, G_F2F | (64 << G_SHIFT), CC_F2F | G_F2F):
-                base = q(_rgbd_cfg(o, method))
-                assert base > 0 and q(_rgbd_cfg(o | R(48), method)) == base
+                base = q(rgbd_cfg(o, method))
+                assert base > 0 and q(rgbd_cfg(o | R(48), method)) == base
                 n_f2f = (2 if o & CC_F2F else 1) * 4 * 1088
-                assert q(_rgbd_cfg(o | F2F | R(48), method)) == base + al(4 * n_f2f), (method, hex(o))
-                assert q(_rgbd_cfg(o | F2F, method)) == 0                         # a switch needs a ratio
+                assert q(rgbd_cfg(o | F2F | R(48), method)) == base + al(4 * n_f2f), (method, hex(o))
+                assert q(rgbd_cfg(o | F2F, method)) == 0                         # a switch needs a ratio
                 # an RGB-D camera has no static stereo: SOSVO_ERR_ARG in the calls, 0 here
-                assert q(_rgbd_cfg(o | STEREO | R(48), method)) == 0 and q(_rgbd_cfg(o | STEREO | F2F | R(48), method)) == 0
+                assert q(rgbd_cfg(o | STEREO | R(48), method)) == 0 and q(rgbd_cfg(o | STEREO | F2F | R(48), method)) == 0
 
 
 def test_the_stage_entry_refuses_a_null_context():
-    lib = _lib_or_skip()
+    lib = lib_or_skip()
     # (with a context, NULL buffers are SOSVO_ERR_ARG -- tests/test_gpu_abi_errors.py walks it)
     rc = lib.sosvo_match_hamming_ratio(None, None, None, None, None, None, None, None, None, 1, 1, 8, 8, 1.0, 2.5, 256, 48, None, None)
     assert rc == -1, rc
@@ -228,9 +228,9 @@ def test_every_driver_and_engine_takes_the_arguments():
 
 def test_set_ratio_test_switches_the_matchers():
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    t = _tracker(rgbd=False)
+    t = tracker(rgbd=False)
     assert (t.ratio_static_stereo, t.ratio_for_motion) == (None, None)
-    t.camera_model = rig = _Rig()
+    t.camera_model = rig = Rig()
     fms, fmm = rig.feature_matcher_for_static_stereo, rig.feature_matcher_for_motion
     pet.set_ratio_test(t, None, 0.75)                        # None: the tracker's own setting, whatever the ratio says
     assert (fms.ratio, fmm.ratio) == (None, None)
@@ -257,8 +257,8 @@ def test_set_ratio_test_switches_the_matchers():
     with pytest.raises(ValueError, match="k_best"):
         pet.set_ratio_test(t, "f2f", 0.75)
     assert (fms.ratio, fmm.ratio, t.ratio_static_stereo, t.ratio_for_motion) == (0.5, None, 0.5, None)
-    r = _tracker(rgbd=True)
-    r.camera_model = cam = _rgbd_cam()
+    r = tracker(rgbd=True)
+    r.camera_model = cam = rgbd_cam()
     pet.set_ratio_test(r, True, 0.75)                        # both matchers = the one an RGB-D tracker has
     assert cam.feature_matcher_for_motion.ratio == 0.75 and r.ratio_static_stereo is None and r.ratio_for_motion == 0.75
     with pytest.raises(ValueError, match="static-stereo"):
@@ -268,10 +268,10 @@ def test_set_ratio_test_switches_the_matchers():
 def test_the_engine_cache_key_distinguishes_the_settings(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "SequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "MultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=False)
-    t.camera_model = rig = _Rig()
+    monkeypatch.setattr(pipeline, "SequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "MultiSequenceEngine", Engine)
+    t = tracker(rgbd=False)
+    t.camera_model = rig = Rig()
     img = np.zeros((4, 4, 3), np.uint8)
     seen, keys = [], set()
     settings = [(False, 0.75), ("stereo", 0.75), ("f2f", 0.75), (True, 0.75), (True, 51 / 64.0), ("f2f", 58 / 64.0)]
@@ -301,10 +301,10 @@ def test_the_engine_cache_key_distinguishes_the_settings(monkeypatch):
 def test_the_rgbd_engine_cache_key_distinguishes_the_settings(monkeypatch):
     from vo_single_camera_sos_amd import pipeline
     from vo_single_camera_sos_amd.omnistereo import pose_est_tools as pet
-    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", _Engine)
-    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", _Engine)
-    t = _tracker(rgbd=True)
-    t.camera_model = cam = _rgbd_cam()
+    monkeypatch.setattr(pipeline, "RGBDSequenceEngine", Engine)
+    monkeypatch.setattr(pipeline, "RGBDMultiSequenceEngine", Engine)
+    t = tracker(rgbd=True)
+    t.camera_model = cam = rgbd_cam()
     img = np.zeros((480, 640, 3), np.uint8)
     off = pet.rgbd_sequence_engine_for(t, cam, img, 8)
     assert off.kwargs["ratio_f2f"] is False and off.kwargs["ratio"] is None
