@@ -100,3 +100,44 @@ def rgbd_cam(matcher=None):
     cam.feature_matcher_for_motion = matcher or FeatureMatcher("GFT", "BF", 1)
     cam._context = lambda: "ctx"
     return cam
+
+
+class ScriptedRig(object):
+    """A rig for run_VO's per-frame loop (frame_window 0) with ScriptedTracker and ScriptedFrame in place of TrackerStereoSE3
+    and StereoPanoramicFrame: it only counts the images it is handed.  script: one entry per frame of the run,
+    (T_frame_wrt_tracking_ref_frame, num_tracked_correspondences, inlier ratio, num_valid_keypoints, True or the failure
+    message); the first frame is not tracked, only its num_valid_keypoints is read."""
+    units = "mm"
+
+    def __init__(self, script, T_Cest_wrt_Rgt=None):
+        self.script, self.position, self.T_Cest_wrt_Rgt = list(script), -1, T_Cest_wrt_Rgt
+
+    def set_current_omni_image(self, img, **kwargs):
+        self.position += 1
+
+
+class ScriptedFrame(object):
+    def __init__(self, stereo_camera_model, frame_id, parent_id=-1):
+        self.frame_id, self.parent_id = frame_id, parent_id
+        self.T_frame_wrt_tracking_ref_frame = np.identity(4)
+        self.num_valid_keypoints = stereo_camera_model.script[stereo_camera_model.position][3]
+
+
+class ScriptedTracker(object):
+    """What run_VO reads of a tracker; track_frame replays the rig's script entry of the current frame and chains the pose as
+    TrackerStereoSE3 does."""
+
+    def __init__(self, camera_model, show_3D_points=False, **kwargs):
+        self.camera_model, self.number_of_cams = camera_model, 2
+        self.T_C_wrt_S_init, self.T_C_curr_frame_wrt_S_est = np.identity(4), np.identity(4)
+        self.num_tracked_correspondences, self.inlier_tracked_correspondences_ratio = 0, 0.
+        self.T_Ckey_wrt_S_est_list = []
+
+    def track_frame(self, reference_frame, current_frame):
+        T, n, ratio, _, ok = self.camera_model.script[self.camera_model.position]
+        if ok is not True:
+            return False, ok
+        self.num_tracked_correspondences, self.inlier_tracked_correspondences_ratio = n, ratio
+        current_frame.T_frame_wrt_tracking_ref_frame = T
+        self.T_C_curr_frame_wrt_S_est = self.T_Ckey_wrt_S_est_list[-1].dot(T)
+        return True, "tracking used %d inlier point correspondences" % n

@@ -16,6 +16,7 @@ reference's per-frame API.
     run_VO / driver_VO (frame loop, keyframe policy, TUM pose files)    pose_est_tools.py:1264-1741
 
 Not built: visualisation (vispy / matplotlib windows), the live-camera driver (run_VO_live)."""
+import functools
 import itertools
 import os
 import threading
@@ -291,9 +292,53 @@ class TrackerSE3(object):
         std_of_k = sqrt(1.0 - w ** n_points_for_model) / (w ** n_points_for_model)
         return int(num_of_iters + 3 * std_of_k)
 
+    # What the track_frame of the two families differ in beside their solvers, each as the reference has it
+    min_matches_per_cam = 1.0            # tracking needs 2 n (min_matches_per_cam * number_of_cams) correspondences
+    refuses_without_model = False        # fewer inliers than the model needs points: the frame is reported as not tracked
+    device_track_resets = {}             # attributes the host path fills and a device record does not
+    chain_pose = staticmethod(np.dot)    # (keyframe pose, frame wrt keyframe) -> frame pose
+
+    def min_matches_to_track(self):
+        return 2 * self.n_points_for_RANSAC_model * (self.min_matches_per_cam * self.number_of_cams)
+
+    def _keep_pose(self, current_frame, T):
+        """T [3, 4], the frame wrt its reference in the model's units -> current_frame.T_frame_wrt_tracking_ref_frame [m] and,
+        chained with the newest keyframe's pose, self.T_C_curr_frame_wrt_S_est."""
+        T_homo = np.identity(4)
+        T_homo[:3] = T
+        T_homo[:3, 3] = T[:3, 3] * current_frame.conversion_factor_length_to_m
+        current_frame.T_frame_wrt_tracking_ref_frame = T_homo
+        T_key = self.T_Ckey_wrt_S_est_list[-1] if self.T_Ckey_wrt_S_est_list else np.identity(4)
+        self.T_C_curr_frame_wrt_S_est = self.chain_pose(T_key, T_homo)
+
+    def _track_device_frame(self, reference_frame, current_frame):
+        """track_frame on frames of a sequence engine's store: the [16] record (refined pose, inliers, correspondences,
+        status) of the pair -- the speculative one when the reference is the frame's predecessor, one serial tracking
+        call against the keyframe slot otherwise -- put through the bookkeeping of the family's track_frame."""
+        eng = current_frame.engine
+        ref_seq = getattr(reference_frame, "seq_index", None)
+        if current_frame.spec_record is not None and ref_seq == current_frame.seq_index - 1:
+            rec = current_frame.spec_record
+        elif current_frame.spec2_record is not None and ref_seq == current_frame.seq_index - 2:
+            rec = current_frame.spec2_record      # the frame in between was not promoted: tracked against t - 2 in the batch
+        else:
+            rec = eng.track(eng.key_slot, current_frame.slot, current_frame.seed)
+        num_initial_matches = int(rec[13])
+        if num_initial_matches < self.min_matches_to_track():
+            return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
+        self.__dict__.update(self.device_track_resets)
+        self.num_tracked_correspondences = int(rec[12])
+        self.inlier_tracked_correspondences_ratio = float(self.num_tracked_correspondences) / float(num_initial_matches)
+        if self.refuses_without_model and self.num_tracked_correspondences < self.n_points_for_RANSAC_model:
+            return False, "RANSAC (%s) found no model among %d correspondences" % (self.pose_est_algorithm, num_initial_matches)
+        self._keep_pose(current_frame, rec[:12].reshape(3, 4))
+        return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
+
 
 class TrackerStereoSE3(TrackerSE3):
     """pose_est_tools.py:722-878"""
+    min_matches_per_cam = 0.33
+    device_track_resets = dict(indices_inliers_combined=None)    # (the inlier list stays on the device)
 
     def __init__(self, camera_model, show_3D_points=False, **kwargs):
         TrackerSE3.__init__(self, camera_model, show_3D_points, **kwargs)
@@ -335,7 +380,7 @@ class TrackerStereoSE3(TrackerSE3):
         self.T_C_curr_frame_wrt_S_est."""
         self.num_tracked_correspondences = 0
         self.inlier_tracked_correspondences_ratio = 0.
-        if isinstance(current_frame, DeviceStereoFrame):
+        if isinstance(current_frame, _DeviceFrame):
             return self._track_device_frame(reference_frame, current_frame)
         ref, cur = reference_frame.pano_correspondences, current_frame.pano_correspondences
         (t_top, _, _), (q_top, _, _), _ = match_features_frame_to_frame(
@@ -356,7 +401,7 @@ class TrackerStereoSE3(TrackerSE3):
         b_all = np.vstack(bearings).reshape(-1, 3)
         p_all = np.vstack(points).reshape(-1, 3)
         num_initial_matches = b_all.shape[0]
-        if num_initial_matches < 2 * self.n_points_for_RANSAC_model * (0.33 * self.number_of_cams):
+        if num_initial_matches < self.min_matches_to_track():
             return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
         T_ransac, inliers = pyopengv.absolute_pose_noncentral_ransac(
             b_all, cam_all, p_all, self.cam_offsets, self.cam_rotations, self.backprojection_score_threshold_3D_to_2D,
@@ -367,71 +412,24 @@ class TrackerStereoSE3(TrackerSE3):
         T_nl = pyopengv.absolute_pose_noncentral_optimize_nonlinear(
             b_all[inliers], cam_all[inliers], p_all[inliers], self.cam_offsets, self.cam_rotations, T_ransac[:3, 3],
             T_ransac[:3, :3])
-        T_homo = np.identity(4)
-        T_homo[:3] = T_nl
-        T_homo[:3, 3] = T_nl[:3, 3] * current_frame.conversion_factor_length_to_m
-        current_frame.T_frame_wrt_tracking_ref_frame = T_homo
-        T_key = self.T_Ckey_wrt_S_est_list[-1] if self.T_Ckey_wrt_S_est_list else np.identity(4)
-        self.T_C_curr_frame_wrt_S_est = T_key.dot(T_homo)
+        self._keep_pose(current_frame, T_nl)
         if self.show_3D_points:
             self.xyz_homo_points_wrt_C_inliers = np.hstack((p_all[inliers] * current_frame.conversion_factor_length_to_m,
                                                             np.ones((len(inliers), 1))))
         return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
 
 
-    def _track_device_frame(self, reference_frame, current_frame):
-        """track_frame on frames of a SequenceEngine's store: the [16] record (refined pose, inliers, correspondences,
-        status) of the pair -- the speculative one when the reference is the frame's predecessor, one serial tracking
-        call against the keyframe slot otherwise -- put through the same bookkeeping as above."""
-        eng = current_frame.engine
-        ref_seq = getattr(reference_frame, "seq_index", None)
-        if current_frame.spec_record is not None and ref_seq == current_frame.seq_index - 1:
-            rec = current_frame.spec_record
-        elif current_frame.spec2_record is not None and ref_seq == current_frame.seq_index - 2:
-            rec = current_frame.spec2_record      # the frame in between was not promoted: tracked against t - 2 in the batch
-        else:
-            rec = eng.track(eng.key_slot, current_frame.slot, current_frame.seed)
-        num_initial_matches = int(rec[13])
-        if num_initial_matches < 2 * self.n_points_for_RANSAC_model * (0.33 * self.number_of_cams):
-            return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
-        self.indices_inliers_combined = None    # (the inlier list stays on the device)
-        self.num_tracked_correspondences = int(rec[12])
-        self.inlier_tracked_correspondences_ratio = float(self.num_tracked_correspondences) / float(num_initial_matches)
-        T_homo = np.identity(4)
-        T_homo[:3] = rec[:12].reshape(3, 4)
-        T_homo[:3, 3] = T_homo[:3, 3] * current_frame.conversion_factor_length_to_m
-        current_frame.T_frame_wrt_tracking_ref_frame = T_homo
-        T_key = self.T_Ckey_wrt_S_est_list[-1] if self.T_Ckey_wrt_S_est_list else np.identity(4)
-        self.T_C_curr_frame_wrt_S_est = T_key.dot(T_homo)
-        return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
 
+class _DeviceFrame(object):
+    """What DeviceStereoFrame and DeviceRGBDFrame share: a frame whose data live in the frame store of a sequence engine
+    (HBM; slot `slot` of the store while the frame's window is current, the keyframe slot once promoted) instead of host
+    arrays.  run_VO's sequence mode builds these, `window` frames per batched front-end pass, from the engine's records
+    (`info`).  A family supplies engine_consts: the attributes that are the same for every frame of an engine."""
 
-class StereoPanoramicKeyFrame(StereoPanoramicFrame):
-    """pose_est_tools.py:625-632: a frame promoted to keyframe (a blind copy of its attributes)."""
-
-    def __init__(self, frame, **kwargs):
-        if isinstance(frame, DeviceStereoFrame):   # (plain instance attributes only: the same blind copy, without dir())
-            self.__dict__.update(frame.__dict__)
-        else:
-            copy_only_attributes(objfrom=frame, objto=self)
-        self.children_ids = []
-
-
-class DeviceStereoFrame(StereoPanoramicFrame):
-    """A StereoPanoramicFrame whose correspondences live in the frame store of a pipeline.SequenceEngine (HBM) instead
-    of host arrays: run_VO's sequence mode builds these, `window` frames per batched front-end pass.  Same attributes as
-    the host frame except pano_correspondences / the bearing arrays, which stay on the device (slot `slot` of the
-    store while the frame's window is current; the keyframe slot once promoted)."""
-
-    def __init__(self, engine, info, stereo_camera_model, frame_id, seq_index, **kwargs):
+    def __init__(self, engine, info, camera_model, frame_id, seq_index, **kwargs):
         consts = getattr(engine, "_frame_consts", None)
-        if consts is None:   # the same for every frame of the engine (ctypes field reads are slow: once)
-            consts = engine._frame_consts = dict(
-                panoramic_image_top=None, panoramic_image_bottom=None, use_midpoint_triangulation=True,
-                use_opengv_triangulation=False, first_row_to_crop_bottom=0, total_time=0., pano_correspondences=None,
-                conversion_factor_length_to_m=get_length_units_conversion_factor(stereo_camera_model.units, "m"),
-                median_win_size=int(engine.cfg.median_ksize), min_disp=engine.rig_cfg.stereo_min_disp,
-                max_u_dist=engine.rig_cfg.stereo_max_hdiff, min_range=engine.rig_cfg.min_range, max_range=engine.rig_cfg.max_range)
+        if consts is None:   # (ctypes field reads are slow: once per engine; an engine belongs to one camera model)
+            consts = engine._frame_consts = self.engine_consts(engine, camera_model)
         self.__dict__.update(consts)
         self.frame_id = frame_id
         self.parent_id = kwargs.get("parent_id", -1)
@@ -442,6 +440,20 @@ class DeviceStereoFrame(StereoPanoramicFrame):
 
     def promote(self):
         self.engine.promote(self.slot)
+
+
+class DeviceStereoFrame(_DeviceFrame, StereoPanoramicFrame):
+    """A StereoPanoramicFrame in the store of a pipeline.SequenceEngine: same attributes as the host frame except
+    pano_correspondences / the bearing arrays, which stay on the device."""
+
+    @staticmethod
+    def engine_consts(engine, stereo_camera_model):
+        return dict(
+            panoramic_image_top=None, panoramic_image_bottom=None, use_midpoint_triangulation=True,
+            use_opengv_triangulation=False, first_row_to_crop_bottom=0, total_time=0., pano_correspondences=None,
+            conversion_factor_length_to_m=get_length_units_conversion_factor(stereo_camera_model.units, "m"),
+            median_win_size=int(engine.cfg.median_ksize), min_disp=engine.rig_cfg.stereo_min_disp,
+            max_u_dist=engine.rig_cfg.stereo_max_hdiff, min_range=engine.rig_cfg.min_range, max_range=engine.rig_cfg.max_range)
 
 
 BATCHED_DETECTORS = ("GFT", "ORB", "FAST", "AGAST")   # the detection methods the sequence engines run
@@ -546,6 +558,15 @@ def set_ratio_test(tracker, ratio_test, ratio=None):
                         lambda stereo, f2f: dict(ratio_static_stereo=of(stereo), ratio_for_motion=of(f2f)))
 
 
+def _has_batched_counterpart(tracker, fm):
+    """Whether the sequence engines run what `tracker` is set to; fm: the matcher the family's frames detect with (None:
+    none yet)."""
+    method = str(tracker.detection_method).upper()
+    return (method in BATCHED_DETECTORS and tracker.matching_type == "BF" and tracker.k_best_matches == 1
+            and not tracker.use_descriptor_radius_match_for_motion
+            and (fm is None or str(fm.feature_detection_method).upper() == method))
+
+
 def _sos_engine_settings(tracker, camera_model, first_image):
     """What a sequence engine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
     StereoPanoramicFrame compute is built from -> (positional arguments after ctx, keyword arguments, cache key), or None
@@ -555,9 +576,7 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     om = camera_model
     method = str(tracker.detection_method).upper()
     fm = getattr(om, "feature_matcher_for_static_stereo", None)   # (what StereoPanoramicFrame detects with)
-    if (method not in BATCHED_DETECTORS or tracker.matching_type != "BF" or tracker.k_best_matches != 1
-            or tracker.use_descriptor_radius_match_for_motion
-            or (fm is not None and str(fm.feature_detection_method).upper() != method)):
+    if not _has_batched_counterpart(tracker, fm):
         return None
     top, bot = om.top_model, om.bot_model
     if not (np.array_equal(tracker.cam_rotations[0], np.identity(3)) and np.array_equal(tracker.cam_rotations[1], np.identity(3))
@@ -587,29 +606,6 @@ def _sos_engine_settings(tracker, camera_model, first_image):
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
                   **opts._asdict())
     return (model, rig), kwargs, key
-
-
-def sequence_engine_for(tracker, camera_model, first_image, window):
-    """The pipeline.SequenceEngine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
-    StereoPanoramicFrame compute, or None when the configuration has no batched counterpart (then run_VO keeps the
-    per-frame mirror path)."""
-    from ..pipeline import SequenceEngine
-    om = camera_model
-    settings = _sos_engine_settings(tracker, om, first_image)
-    if settings is None:
-        return None
-    args, kwargs, key = settings
-    # an engine (frame store, pinned staging buffers, scratch) is kept with the rig and reused by later runs with the same
-    # settings: building one costs more than tracking a hundred frames
-    key = key[:1] + (int(window),) + key[1:]
-    cache = om.__dict__.setdefault("_sequence_engines", {})
-    eng = cache.get(key)
-    if eng is None:
-        cache.clear()   # (one engine per rig: a new configuration replaces the old one's buffers)
-        eng = cache[key] = SequenceEngine(om._context(), *args, window=window, **kwargs)
-    else:
-        eng.reset()
-    return eng
 
 
 class RGBDFrame(object):
@@ -674,39 +670,35 @@ class RGBDFrame(object):
         self.num_valid_keypoints = M
 
 
-class RGBDKeyFrame(RGBDFrame):
-    """pose_est_tools.py:634-641"""
+class _KeyFrame(object):
+    """A frame promoted to keyframe: a blind copy of its attributes (pose_est_tools.py:625-641)."""
 
     def __init__(self, frame, **kwargs):
-        if isinstance(frame, DeviceRGBDFrame):   # (plain instance attributes only: the same blind copy, without dir())
+        if isinstance(frame, _DeviceFrame):   # (plain instance attributes only: the same blind copy, without dir())
             self.__dict__.update(frame.__dict__)
         else:
             copy_only_attributes(objfrom=frame, objto=self)
         self.children_ids = []
 
 
-class DeviceRGBDFrame(RGBDFrame):
-    """An RGBDFrame whose keypoints, descriptors, points and bearings live in the frame store of a
-    pipeline.RGBDSequenceEngine (HBM): run_VO's sequence mode builds these, `window` frames per batched front-end pass."""
+class StereoPanoramicKeyFrame(_KeyFrame, StereoPanoramicFrame):
+    """pose_est_tools.py:625-632"""
 
-    def __init__(self, engine, info, rgbd_camera_model, frame_id, seq_index, **kwargs):
-        self.rgbd_camera_model = rgbd_camera_model
-        self.frame_id = frame_id
-        self.parent_id = kwargs.get("parent_id", -1)
-        self.T_frame_wrt_tracking_ref_frame = np.identity(4)
-        self.conversion_factor_length_to_m = get_length_units_conversion_factor(rgbd_camera_model.units, "m")
-        self.total_time = 0.
-        self.median_win_size = engine.cfg.median_ksize
-        self.min_range, self.max_range = engine.cam_cfg.min_range, engine.cam_cfg.max_range
-        self.mask = None
-        self.rgb_img = self.depth_map = self.current_depth = None
-        self.keypoints_and_descriptors = self.bearing_vectors = self.keypoints_3D_points = None
-        self.engine, self.slot, self.seq_index = engine, int(info["slot"]), int(seq_index)
-        self.seed, self.spec_record, self.spec2_record = int(info["seed"]), info["spec"], info.get("spec2")
-        self.num_valid_keypoints = int(info["count"])
 
-    def promote(self):
-        self.engine.promote(self.slot)
+class RGBDKeyFrame(_KeyFrame, RGBDFrame):
+    """pose_est_tools.py:634-641"""
+
+
+class DeviceRGBDFrame(_DeviceFrame, RGBDFrame):
+    """An RGBDFrame whose keypoints, descriptors, points and bearings stay in the store of a pipeline.RGBDSequenceEngine."""
+
+    @staticmethod
+    def engine_consts(engine, rgbd_camera_model):
+        return dict(
+            rgbd_camera_model=rgbd_camera_model, total_time=0., mask=None, rgb_img=None, depth_map=None, current_depth=None,
+            keypoints_and_descriptors=None, bearing_vectors=None, keypoints_3D_points=None,
+            conversion_factor_length_to_m=get_length_units_conversion_factor(rgbd_camera_model.units, "m"),
+            median_win_size=engine.cfg.median_ksize, min_range=engine.cam_cfg.min_range, max_range=engine.cam_cfg.max_range)
 
 
 def _rgbd_engine_settings(tracker, camera_model, first_rgb):
@@ -715,9 +707,7 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     cm = camera_model
     method = str(tracker.detection_method).upper()
     fm = getattr(cm, "feature_matcher_for_motion", None)   # (what RGBDFrame detects with)
-    if (method not in BATCHED_DETECTORS or tracker.matching_type != "BF" or tracker.k_best_matches != 1
-            or tracker.use_descriptor_radius_match_for_motion
-            or (fm is not None and str(fm.feature_detection_method).upper() != method)):
+    if not _has_batched_counterpart(tracker, fm):
         return None
     cam = RGBDCamConfig(cm.fx, cm.fy, cm.center_x, cm.center_y, cm.focal_length_m, cm.depth_is_Z, 0.8, 7.0,
                         f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
@@ -734,55 +724,66 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     return (cam,), kwargs, key
 
 
+def _engine_settings(tracker, camera_model, first_image):
+    """_sos_engine_settings or _rgbd_engine_settings, by the camera model's family."""
+    return (_rgbd_engine_settings if _is_rgbd_model(camera_model) else _sos_engine_settings)(tracker, camera_model, first_image)
+
+
+def _engine_for(tracker, camera_model, first_image, window, lanes=None):
+    """The sequence engine (lanes None) or the multi-sequence engine of `lanes` lanes that computes what `tracker` and its
+    family's frames compute -> (engine, settings key), or (None, None) when the configuration has no batched counterpart.
+    An engine (frame store, pinned staging buffers, scratch) stays with the camera model and serves later runs with the same
+    settings and window: building one costs more than tracking a hundred frames.  One engine per model and kind (a new
+    configuration replaces the old one's buffers; a solo run between two multi-sequence runs does not evict their engine)."""
+    from .. import pipeline
+    settings = _engine_settings(tracker, camera_model, first_image)
+    if settings is None:
+        return None, None
+    args, kwargs, key = settings
+    multi = lanes is not None
+    name = (("SequenceEngine", "MultiSequenceEngine"), ("RGBDSequenceEngine", "RGBDMultiSequenceEngine"))[_is_rgbd_model(camera_model)][multi]
+    if multi:
+        full, kwargs = key + (int(window), int(lanes)), dict(kwargs, lanes=lanes)
+    else:
+        full = key[:1] + (int(window),) + key[1:]
+    cache = camera_model.__dict__.setdefault("_multi_sequence_engines" if multi else "_sequence_engines", {})
+    eng = cache.get(full)
+    if multi and eng is not None and (eng._error is not None or eng._live):
+        eng = None          # (a device call failed, or a run is still on it: not reused)
+    if eng is None:
+        cache.clear()
+        eng = cache[full] = getattr(pipeline, name)(camera_model._context(), *args, window=window, **kwargs)
+    elif multi:
+        eng.reset_counters()
+    else:
+        eng.reset()
+    return eng, key
+
+
+def sequence_engine_for(tracker, camera_model, first_image, window):
+    """The pipeline.SequenceEngine that computes what `tracker` (a TrackerStereoSE3 with the reference's settings) and
+    StereoPanoramicFrame compute, or None when the configuration has no batched counterpart (then run_VO keeps the
+    per-frame mirror path)."""
+    return _engine_for(tracker, camera_model, first_image, window)[0]
+
+
 def rgbd_sequence_engine_for(tracker, camera_model, first_rgb, window):
     """The pipeline.RGBDSequenceEngine that computes what `tracker` (a TrackerRGBDSE3) and RGBDFrame compute, or None when
     the configuration has no batched counterpart (then run_VO keeps the per-frame mirror path)."""
-    from ..pipeline import RGBDSequenceEngine
-    cm = camera_model
-    settings = _rgbd_engine_settings(tracker, cm, first_rgb)
-    if settings is None:
-        return None
-    args, kwargs, key = settings
-    # (as sequence_engine_for: the engine -- frame store, 136 MB of pinned staging buffers, scratch -- stays with the camera
-    # model and serves later runs with the same settings; building one costs 15 ms, a 128-frame run 45)
-    key = key[:1] + (int(window),) + key[1:]
-    cache = cm.__dict__.setdefault("_sequence_engines", {})
-    eng = cache.get(key)
-    if eng is None:
-        cache.clear()
-        eng = cache[key] = RGBDSequenceEngine(cm._context(), *args, window=window, **kwargs)
-    else:
-        eng.reset()
-    return eng
+    return _engine_for(tracker, camera_model, first_rgb, window)[0]
 
 
 def multi_sequence_engine_for(tracker, camera_model, first_image, window, lanes):
     """The pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine of `lanes` lanes with the settings sequence_engine_for /
     rgbd_sequence_engine_for would give a single-sequence engine -> (engine, settings key), or (None, None) when the
-    configuration has no batched counterpart.  Kept with the camera model beside the single-sequence engine (its own
-    cache: a solo run between two multi-sequence runs does not evict it) and reused while nothing of it failed."""
-    from ..pipeline import MultiSequenceEngine, RGBDMultiSequenceEngine
-    rgbd = _is_rgbd_model(camera_model)
-    settings = (_rgbd_engine_settings if rgbd else _sos_engine_settings)(tracker, camera_model, first_image)
-    if settings is None:
-        return None, None
-    args, kwargs, key = settings
-    full = key + (int(window), int(lanes))
-    cache = camera_model.__dict__.setdefault("_multi_sequence_engines", {})
-    eng = cache.get(full)
-    if eng is not None and (eng._error is not None or eng._live):
-        eng = None          # (a device call failed, or a run is still on it: not reused)
-    if eng is None:
-        cache.clear()
-        eng = cache[full] = (RGBDMultiSequenceEngine if rgbd else MultiSequenceEngine)(
-            camera_model._context(), *args, lanes=lanes, window=window, **kwargs)
-    else:
-        eng.reset_counters()
-    return eng, key
+    configuration has no batched counterpart."""
+    return _engine_for(tracker, camera_model, first_image, window, lanes)
 
 
 class TrackerRGBDSE3(TrackerSE3):
     """pose_est_tools.py:880-958: central 3D-2D tracking of RGB-D frames."""
+    refuses_without_model = True
+    chain_pose = staticmethod(tr.concatenate_matrices)     # (multiplies into an identity first, as the reference does here)
 
     def __init__(self, camera_model, show_3D_points=False, **kwargs):
         TrackerSE3.__init__(self, camera_model, show_3D_points, **kwargs)
@@ -804,7 +805,7 @@ class TrackerRGBDSE3(TrackerSE3):
         """pose_est_tools.py:896-954 -> (ok, message)."""
         self.num_tracked_correspondences = 0
         self.inlier_tracked_correspondences_ratio = 0.
-        if isinstance(current_frame, DeviceRGBDFrame):
+        if isinstance(current_frame, _DeviceFrame):
             return self._track_device_frame(reference_frame, current_frame)
         ref, cur = reference_frame.keypoints_and_descriptors, current_frame.keypoints_and_descriptors
         (t_idx, _, _), (q_idx, _, _), _ = match_features_frame_to_frame(
@@ -814,7 +815,7 @@ class TrackerRGBDSE3(TrackerSE3):
             max_horizontal_diff=self.max_horizontal_diff_f2f_matches, max_descriptor_distance_radius=-1)
         t_idx, q_idx = np.asarray(t_idx, dtype=np.int64), np.asarray(q_idx, dtype=np.int64)
         num_initial_matches = len(t_idx)
-        if num_initial_matches < 2 * self.n_points_for_RANSAC_model * self.number_of_cams:
+        if num_initial_matches < self.min_matches_to_track():
             return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
         b = current_frame.bearing_vectors[q_idx]
         p = reference_frame.keypoints_3D_points[t_idx]
@@ -828,47 +829,11 @@ class TrackerRGBDSE3(TrackerSE3):
             # frame as not tracked instead of refining from an empty inlier set
             return False, "RANSAC (%s) found no model among %d correspondences" % (self.pose_est_algorithm, num_initial_matches)
         T_nl = pyopengv.absolute_pose_optimize_nonlinear(b[inliers], p[inliers], T_ransac[:3, 3], T_ransac[:3, :3])
-        T_homo = np.identity(4)
-        T_homo[:3] = T_nl
-        T_homo[:3, 3] = T_nl[:3, 3] * current_frame.conversion_factor_length_to_m
-        current_frame.T_frame_wrt_tracking_ref_frame = T_homo
-        T_key = self.T_Ckey_wrt_S_est_list[-1] if self.T_Ckey_wrt_S_est_list else np.identity(4)
-        self.T_C_curr_frame_wrt_S_est = tr.concatenate_matrices(T_key, T_homo)
+        self._keep_pose(current_frame, T_nl)
         if self.show_3D_points:
             self.xyz_homo_points_wrt_C_inliers = np.hstack((p[inliers] * current_frame.conversion_factor_length_to_m,
                                                             np.ones((len(inliers), 1))))
         return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
-
-
-def _rgbd_track_device_frame(self, reference_frame, current_frame):
-    """TrackerRGBDSE3.track_frame on frames of an RGBDSequenceEngine's store: the [16] record of the pair (the speculative
-    one when the reference is the frame's predecessor, one serial call against the keyframe slot otherwise) put through the
-    bookkeeping of track_frame above."""
-    eng = current_frame.engine
-    ref_seq = getattr(reference_frame, "seq_index", None)
-    if current_frame.spec_record is not None and ref_seq == current_frame.seq_index - 1:
-        rec = current_frame.spec_record
-    elif current_frame.spec2_record is not None and ref_seq == current_frame.seq_index - 2:
-        rec = current_frame.spec2_record
-    else:
-        rec = eng.track(eng.key_slot, current_frame.slot, current_frame.seed)
-    num_initial_matches = int(rec[13])
-    if num_initial_matches < 2 * self.n_points_for_RANSAC_model * self.number_of_cams:
-        return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
-    self.num_tracked_correspondences = int(rec[12])
-    self.inlier_tracked_correspondences_ratio = float(self.num_tracked_correspondences) / float(num_initial_matches)
-    if self.num_tracked_correspondences < self.n_points_for_RANSAC_model:
-        return False, "RANSAC (%s) found no model among %d correspondences" % (self.pose_est_algorithm, num_initial_matches)
-    T_homo = np.identity(4)
-    T_homo[:3] = rec[:12].reshape(3, 4)
-    T_homo[:3, 3] = T_homo[:3, 3] * current_frame.conversion_factor_length_to_m
-    current_frame.T_frame_wrt_tracking_ref_frame = T_homo
-    T_key = self.T_Ckey_wrt_S_est_list[-1] if self.T_Ckey_wrt_S_est_list else np.identity(4)
-    self.T_C_curr_frame_wrt_S_est = tr.concatenate_matrices(T_key, T_homo)
-    return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
-
-
-TrackerRGBDSE3._track_device_frame = _rgbd_track_device_frame
 
 
 # A tracker's construction writes to its camera model (the feature matchers; bootstrap_tracker regenerates the azimuthal masks
@@ -1004,6 +969,190 @@ def sequence_windows(it, eng, W, images_of, engine_state, on_window=None, stop=N
             worker.join()
 
 
+def _tum_fields(t, q):
+    """" tx ty tz qx qy qz qw" + newline of a translation and a quaternion (w first), every number as its repr."""
+    return " %s %s %s %s %s %s %s\n" % (repr(t[0]), repr(t[1]), repr(t[2]), repr(q[1]), repr(q[2]), repr(q[3]), repr(q[0]))
+
+
+class _VOOutput(object):
+    """What run_VO says and writes: printed_messages.log and stdout, the two TUM pose files and keyframe_ids.txt.
+    Sequence mode keeps the per-frame host work small: messages and pose lines are collected and written once per window
+    (same text, same order), the quaternions of a window's poses come from ONE batched eigen-decomposition
+    (tr.quaternions_from_matrices: bit-identical rows).  The per-frame paths (frame_window 0, live sources) flush every frame."""
+
+    def __init__(self, results_path):
+        self.log = open(os.path.join(results_path, "printed_messages.log"), "w")
+        self.results_path = results_path
+        self.out_msgs, self.log_only, self.pending, self.kf_lines = [], [], [], []   # stdout + log | log only | poses | keyframes
+        self.say = self.out_msgs.append
+
+    def open_pose_files(self, est_poses_filename):
+        self.est_path = os.path.join(self.results_path, est_poses_filename)
+        self.kf_path = os.path.join(self.results_path, "keyframe_ids.txt")
+        self.est_file = open(self.est_path, "w")
+        self.gt_file = open(self.est_path.replace("estimated", "gt_associated"), "w")
+        self.kf_file = open(self.kf_path, "w")
+
+    def say_to_log_only(self, msg):
+        self.log_only.append((len(self.out_msgs), msg))     # (a failure message goes to the log only, where it was said)
+
+    def pose(self, idx, T_est, T_gt):
+        """(TUM lines idx tx ty tz qx qy qz qw, :1611-1621, with quaternion_from_matrix(isprecise=False): formatted by flush)"""
+        self.pending.append((idx, T_est, T_gt))
+
+    def keyframe(self, idx):
+        self.kf_lines.append("%d\n" % idx)
+
+    def flush(self):
+        out_msgs, log_only, pending = self.out_msgs, self.log_only, self.pending
+        if out_msgs or log_only:
+            if out_msgs:
+                print("\n".join(out_msgs))
+            lines, extra = list(out_msgs), sorted(log_only, key=lambda e: e[0], reverse=True)
+            for pos, line in extra:
+                lines.insert(pos, line)
+            self.log.write("\n".join(lines) + "\n")
+            del out_msgs[:], log_only[:]
+        if pending:
+            idxs = [p_[0] for p_ in pending]
+            Te = np.stack([p_[1] for p_ in pending])
+            qe, te = tr.quaternions_from_matrices(Te).tolist(), Te[:, :3, 3].tolist()
+            self.est_file.write("".join("%d%s" % (i, _tum_fields(t, q)) for i, t, q in zip(idxs, te, qe)))
+            gts = [p_[2] for p_ in pending]
+            uniq = {}
+            for g in gts:                        # (one shared identity for a run without ground truth: decomposed once)
+                uniq.setdefault(id(g), g)
+            keys = list(uniq)
+            Tg = np.stack([uniq[k_] for k_ in keys])
+            bad = np.isnan(Tg).any(axis=(1, 2))
+            qg = tr.quaternions_from_matrices(np.where(bad[:, None, None], np.identity(4), Tg)).tolist()
+            tg = Tg[:, :3, 3].tolist()
+            line_of = {k_: " nan nan nan nan nan nan nan\n" if b_ else _tum_fields(t, q) for k_, b_, t, q in zip(keys, bad.tolist(), tg, qg)}
+            self.gt_file.write("".join("%d%s" % (i, line_of[id(g)]) for i, g in zip(idxs, gts)))
+            del pending[:]
+
+    def close(self):
+        self.flush()
+        self.kf_file.write("".join(self.kf_lines))
+        for f in (self.est_file, self.gt_file, self.kf_file, self.log):
+            f.close()
+
+
+def _file_frames(camera_model, image_names, depth_names, indices):
+    """(frame index, image, depth map or None) from the files of a sequence (depth_names None: no depth maps); the next frame
+    is decoded on a helper thread while the current one is tracked (the decoder releases the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from .common_cv import get_depthmap_float32_from_png, imread
+
+    def load(k):
+        img = imread(image_names[k])
+        if img is None:   # (imread's None for a file it cannot decode ends the run here, for every frame window alike)
+            raise OSError("cannot read the image file %s" % image_names[k])
+        if depth_names is not None:
+            # the reference converts BGR -> RGB (:1430) and then treats the array as BGR (:531): reproduced as is
+            return indices[k], np.ascontiguousarray(img[..., ::-1]), \
+                get_depthmap_float32_from_png(depth_names[k], camera_model.scaling_factor)
+        return indices[k], img, None
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        pending = pool.submit(load, 0) if len(indices) else None
+        for k in range(len(indices)):
+            item = pending.result()
+            pending = pool.submit(load, k + 1) if k + 1 < len(indices) else None
+            yield item
+
+
+def _windowed_frames(source, frame_window, engine_for, tracker, camera_model, engine_state, on_window):
+    """The frames of source(), `frame_window` at a time through the batched front end of the engine that
+    engine_for(tracker, camera_model, first image, frame_window) gives on the first frame (kept in engine_state); no batched
+    counterpart of this configuration: the frames as they are, for the per-frame path."""
+    W = int(frame_window)
+    it = iter(source())
+    first = next(it, None)
+    if first is None:
+        return
+    engine_state["tried"] = True
+    eng = engine_state["engine"] = engine_for(tracker, camera_model, first[1], W)
+    it = itertools.chain([first], it)
+    if eng is None:
+        yield from it
+        return
+    images_of = (lambda c: [(item[1], item[2]) for item in c]) if _is_rgbd_model(camera_model) else (lambda c: [item[1] for item in c])
+    yield from sequence_windows(it, eng, W, images_of, engine_state, on_window=on_window)
+
+
+def _ground_truth_of(gt_poses_filename, camera_model, T_C_wrt_S_init, img_indices, live):
+    """-> the function frame index -> ground-truth pose T_gt in the frame the estimates are in.  No ground-truth file (a live
+    run has none, :1012): one shared identity for every frame; a frame the file has no pose for: NaN (a live run: identity)."""
+    from .common_tools import get_poses_from_file
+    pose_output_file_units = "m"
+    have_file = gt_poses_filename is not None and os.path.exists(gt_poses_filename)
+    if have_file:
+        _, gt_list = get_poses_from_file(poses_filename=gt_poses_filename, input_units="m",
+                                         output_working_units=pose_output_file_units, indices=[], pose_format="tum",
+                                         zero_up_wrt_origin=True)
+    else:
+        gt_list = max(len(img_indices), img_indices[-1] + 1) * [np.identity(4)]
+    T_Rgt_wrt_S = T_S_wrt_Rgt = None
+    if have_file and getattr(camera_model, "T_Cest_wrt_Rgt", None) is not None:
+        # fixed hand-eye transformation between the estimated camera frame and the ground-truth rig frame (:1362-1367)
+        k_units = get_length_units_conversion_factor(camera_model.units, pose_output_file_units)
+        T_Cest_wrt_Rgt = np.array(camera_model.T_Cest_wrt_Rgt, dtype=np.float64, copy=True)
+        T_Cest_wrt_Rgt[:3, 3] = k_units * T_Cest_wrt_Rgt[:3, 3]
+        T_Rgt_wrt_S = tr.concatenate_matrices(T_C_wrt_S_init, tr.inverse_matrix(T_Cest_wrt_Rgt))
+        T_S_wrt_Rgt = tr.inverse_matrix(T_Rgt_wrt_S)
+
+    def T_gt_of(idx):
+        T_gt = gt_list[idx] if idx < len(gt_list) else (np.identity(4) if live else np.full((4, 4), np.nan))
+        if T_Rgt_wrt_S is not None:
+            T_gt = tr.concatenate_matrices(T_Rgt_wrt_S, T_gt, T_S_wrt_Rgt)   # :1472
+        return T_gt
+    return T_gt_of
+
+
+# the share of the running average of tracked correspondences / of the keyframe's keypoints a new keyframe needs (:1308-1313)
+KEYFRAME_MIN_TRACKED, KEYFRAME_MIN_KEYPOINTS = 0.10, 0.10
+
+
+def keyframe_policy(dist, ang, n_tracked, tracked_prev_avg, M_F, M_K, thresholds, prefix="", idx=0, tracked_wrt_keyframe=0):
+    """The keyframe policy (:1516-1550) for a tracked frame: dist [m] and ang [radians] of its pose wrt the keyframe, n_tracked
+    correspondences per camera against the average tracked_prev_avg since the keyframe, M_F / M_K valid keypoints of the frame /
+    the keyframe, thresholds = (pos_thr, pos_max, ang_thr, ang_max); prefix, idx and tracked_wrt_keyframe go into the message
+    -> (create a keyframe, the message to say or None)."""
+    pos_thr, pos_max, ang_thr, ang_max = thresholds
+    if not ((pos_thr < dist < pos_max) or (ang_thr < ang < ang_max)):
+        return False, None
+    if not (n_tracked > KEYFRAME_MIN_TRACKED * tracked_prev_avg and M_F > KEYFRAME_MIN_KEYPOINTS * M_K):
+        return False, "%sFrame [%d] as Keyframe...doesn't satisfy %d > %.2f * %.2f and %d > %.2f * %.2f" % (
+            prefix, idx, n_tracked, KEYFRAME_MIN_TRACKED, tracked_prev_avg, M_F, KEYFRAME_MIN_KEYPOINTS, M_K)
+    reason = None
+    if pos_thr < dist < pos_max:
+        if ang < ang_max:
+            reason = "translation %.2f < %.4f < %.2f [m]" % (pos_thr, dist, pos_max)
+    elif ang_thr < ang:
+        if dist < pos_max < ang_max:   # as written in the reference (:1534)
+            reason = " rotation: %.2f > %.2f [radians]" % (ang, ang_thr)
+    if reason is None:
+        return False, "%sFrame [%d] as failed to create Keyframe due to some CRAZYNESS" % (prefix, idx)
+    return True, "%sFrame [%d] as Keyframe due to %s... with %d tracked keypoint correspondences after tracking %d frames" % (
+        prefix, idx, reason, n_tracked, tracked_wrt_keyframe)
+
+
+def _vo_summary(prefix, number_of_keyframes, acc, n_done, est_path, kf_path):
+    """The closing message of a run from its accumulators (process time per phase, tracked correspondences, inlier ratios)."""
+    d = float(max(n_done, 1))
+    return "\n".join([
+        "%sVO done with %d keyframes" % (prefix, number_of_keyframes),
+        "Image Read Avg Time: {time:.8f} seconds".format(time=acc["read"] / d),
+        "Frame Setup Avg Time: {time:.8f} seconds".format(time=acc["setup"] / d),
+        "Frame Tracking Avg Time: {time:.8f} seconds".format(time=acc["track"] / d),
+        "Overall Frame VO Avg Time: {time:.8f} seconds".format(time=acc["vo"] / d),
+        "Total Number of tracked correspondences: {corrs}".format(corrs=int(acc["corr"])),
+        "Average Number of tracked correspondences: {corrs}".format(corrs=int(int(acc["corr"]) / d)),
+        "Average tracked correspondences RANSAC inlier ratio: {ratio:.8f}".format(ratio=acc["ratio"] / d),
+        "Estimated poses in TUM format SAVED as " + est_path,
+        "Keyframes (indices) SAVED as " + kf_path])
+
+
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
@@ -1035,8 +1184,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     ratio_test: Lowe's ratio rule in the matchers, evaluated on the device: a match is kept iff its distance is below
     ratio times the runner-up's (under gated_matching: the runner-up among the admissible candidates); same values as
     cross_check.  ratio: a float in (0, 1) with ratio * 64 an integer, e.g. 0.75 (see set_ratio_test).  Off by default."""
-    from .common_cv import get_depthmap_float32_from_png, get_images, imread
-    from .common_tools import get_poses_from_file
+    from .common_cv import get_images
     if visualizer_3D_VO is not None:
         raise NotImplementedError("3-D visualisation is not built: pass visualizer_3D_VO=None")
     pyopengv.set_seed(0)  # a run is a pure function of its inputs (OpenGV seeds its sampler from the clock)
@@ -1045,77 +1193,15 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     trackerClass, KeyFrameClass = (TrackerRGBDSE3, RGBDKeyFrame) if rgbd else (TrackerStereoSE3, StereoPanoramicKeyFrame)
     results_path = os.path.realpath(os.path.expanduser(results_path))
     make_sure_path_exists(results_path)
-    log = open(os.path.join(results_path, "printed_messages.log"), "w")
-    # Sequence mode keeps the per-frame host work small: messages and pose lines are collected and written once per window
-    # (same text, same order), the quaternions of a window's poses come from ONE batched eigen-decomposition
-    # (tr.quaternions_from_matrices: bit-identical rows).  The per-frame paths (frame_window 0, live sources) flush every frame.
-    out_msgs, log_only, pending = [], [], []    # stdout + log lines | (position in out_msgs, line) for the log only | poses
-
-    def say(msg):
-        out_msgs.append(msg)
-
-    def flush_output():
-        if out_msgs or log_only:
-            if out_msgs:
-                print("\n".join(out_msgs))
-            lines, extra = list(out_msgs), sorted(log_only, key=lambda e: e[0], reverse=True)
-            for pos, line in extra:            # (a failure message goes to the log only, where it was said)
-                lines.insert(pos, line)
-            log.write("\n".join(lines) + "\n")
-            del out_msgs[:], log_only[:]
-        if pending:
-            idxs = [p_[0] for p_ in pending]
-            Te = np.stack([p_[1] for p_ in pending])
-            qe, te = tr.quaternions_from_matrices(Te).tolist(), Te[:, :3, 3].tolist()
-            est_file.write("".join("%d %s %s %s %s %s %s %s\n" % (i, repr(t[0]), repr(t[1]), repr(t[2]), repr(q[1]), repr(q[2]),
-                                                                     repr(q[3]), repr(q[0])) for i, t, q in zip(idxs, te, qe)))
-            gts = [p_[2] for p_ in pending]
-            uniq = {}
-            for g in gts:                        # (one shared identity for a run without ground truth: decomposed once)
-                uniq.setdefault(id(g), g)
-            keys = list(uniq)
-            Tg = np.stack([uniq[k_] for k_ in keys])
-            bad = np.isnan(Tg).any(axis=(1, 2))
-            qg = tr.quaternions_from_matrices(np.where(bad[:, None, None], np.identity(4), Tg)).tolist()
-            tg = Tg[:, :3, 3].tolist()
-            line_of = {}
-            for k_, b_, t, q in zip(keys, bad.tolist(), tg, qg):
-                line_of[k_] = " nan nan nan nan nan nan nan\n" if b_ else " %s %s %s %s %s %s %s\n" % (
-                    repr(t[0]), repr(t[1]), repr(t[2]), repr(q[1]), repr(q[2]), repr(q[3]), repr(q[0]))
-            gt_file.write("".join("%d%s" % (i, line_of[id(g)]) for i, g in zip(idxs, gts)))
-            del pending[:]
-
-    pose_output_file_units = "m"
-    zero_up_gt_wrt_origin = True
+    out = _VOOutput(results_path)
     # indoor thresholds (pose_est_tools.py:1308-1313); run_VO_live passes its own (:991-1003)
-    pos_thr, pos_max, ang_thr, ang_max = _keyframe_thresholds or (0.01, 0.20, np.deg2rad(1.0), np.deg2rad(10.0))
-    thr_tracked, thr_keypoints = 0.10, 0.10
-
+    thresholds = _keyframe_thresholds or (0.01, 0.20, np.deg2rad(1.0), np.deg2rad(10.0))
     if _live_frames is None:
         image_names = get_images(img_filename_template, indices_list=img_indices, return_names_only=True)
         depth_names = get_images(depth_filename_template, indices_list=img_indices, return_names_only=True) if rgbd else None
         if img_indices is None or len(img_indices) == 0:
             img_indices = list(range(len(image_names)))
-
-        def load(k):
-            img = imread(image_names[k])
-            if img is None:   # (imread's None for a file it cannot decode ends the run here, for every frame window alike)
-                raise OSError("cannot read the image file %s" % image_names[k])
-            if rgbd:
-                # the reference converts BGR -> RGB (:1430) and then treats the array as BGR (:531): reproduced as is
-                return img_indices[k], np.ascontiguousarray(img[..., ::-1]), \
-                    get_depthmap_float32_from_png(depth_names[k], camera_model.scaling_factor)
-            return img_indices[k], img, None
-
-        def frames():   # (frame index, image, depth map or None) from the files of the sequence; the next frame is
-            # decoded on a helper thread while the current one is tracked (the decoder releases the GIL)
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=1) as pool:
-                pending = pool.submit(load, 0) if len(img_indices) else None
-                for k in range(len(img_indices)):
-                    item = pending.result()
-                    pending = pool.submit(load, k + 1) if k + 1 < len(img_indices) else None
-                    yield item
+        frames = functools.partial(_file_frames, camera_model, image_names, depth_names, img_indices)
     else:
         img_indices = [0]
         frames = _live_frames
@@ -1128,50 +1214,16 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
-    if int(frame_window) > 0:
-        source = frames
-
-        def frames():   # the same frames, `frame_window` at a time through the batched front end
-            W = int(frame_window)
-            it = iter(source())
-            first = next(it, None)
-            if first is None:
-                return
-            engine_state["tried"] = True
-            # (_engine_for: run_VO_many hands a lane of its multi-sequence engine to each of its runs)
-            eng = engine_state["engine"] = (_engine_for or (rgbd_sequence_engine_for if rgbd else sequence_engine_for))(
-                tracker, camera_model, first[1], W)
-            it = itertools.chain([first], it)
-            if eng is None:              # no batched counterpart of this configuration: the per-frame path
-                yield from it
-                return
-            images_of = (lambda c: [(item[1], item[2]) for item in c]) if rgbd else (lambda c: [item[1] for item in c])
-            yield from sequence_windows(it, eng, W, images_of, engine_state, on_window=flush_output)
-    if gt_poses_filename is None or not os.path.exists(gt_poses_filename):
-        n_gt = max(len(img_indices), img_indices[-1] + 1)
-        gt_list = n_gt * [np.identity(4)]   # (a live run has no ground truth: identity for every frame, as :1012)
-    else:
-        _, gt_list = get_poses_from_file(poses_filename=gt_poses_filename, input_units="m",
-                                         output_working_units=pose_output_file_units, indices=[], pose_format="tum",
-                                         zero_up_wrt_origin=zero_up_gt_wrt_origin)
-    T_Rgt_wrt_S = None
-    if gt_poses_filename is not None and os.path.exists(gt_poses_filename) and getattr(camera_model, "T_Cest_wrt_Rgt", None) is not None:
-        # fixed hand-eye transformation between the estimated camera frame and the ground-truth rig frame (:1362-1367)
-        k_units = get_length_units_conversion_factor(camera_model.units, pose_output_file_units)
-        T_Cest_wrt_Rgt = np.array(camera_model.T_Cest_wrt_Rgt, dtype=np.float64, copy=True)
-        T_Cest_wrt_Rgt[:3, 3] = k_units * T_Cest_wrt_Rgt[:3, 3]
-        T_Rgt_wrt_S = tr.concatenate_matrices(tracker.T_C_wrt_S_init, tr.inverse_matrix(T_Cest_wrt_Rgt))
-        T_S_wrt_Rgt = tr.inverse_matrix(T_Rgt_wrt_S)
-    est_path = os.path.join(results_path, est_poses_filename)
-    est_file = open(est_path, "w")
-    gt_file = open(est_path.replace("estimated", "gt_associated"), "w")
-    kf_path = os.path.join(results_path, "keyframe_ids.txt")
-    kf_file = open(kf_path, "w")
+    if int(frame_window) > 0:   # sequence mode: the same frames, `frame_window` at a time through the batched front end
+        # (_engine_for: run_VO_many hands a lane of its multi-sequence engine to each of its runs)
+        engine_for = _engine_for or (rgbd_sequence_engine_for if rgbd else sequence_engine_for)
+        frames = functools.partial(_windowed_frames, frames, frame_window, engine_for, tracker, camera_model, engine_state, out.flush)
+    T_gt_of = _ground_truth_of(gt_poses_filename, camera_model, tracker.T_C_wrt_S_init, img_indices, live=_live_frames is not None)
+    out.open_pose_files(est_poses_filename)
 
     reference_frame, current_frame = None, None
     create_keyframe = True
     current_keyframe_id = img_indices[0]
-    number_of_keyframes = 0
     tracked_wrt_keyframe = 0
     tracked_prev_avg = 0.
     inlier_ratio_cma = tracker.inlier_tracked_correspondences_ratio
@@ -1180,8 +1232,6 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     n_done = 0
     frame_iter = iter(frames())
     img_index_number = -1
-    batched_output = False       # sequence mode: lines are written once per window (flush_output in the window generator)
-    kf_lines = []
     try:
         while True:
             t_frame = t0 = time.process_time()
@@ -1191,7 +1241,6 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
                 break
             idx, img, depth_map = item[:3]
             dev_info = item[3] if len(item) > 3 else None
-            batched_output = dev_info is not None
             img_index_number += 1
             t1 = time.process_time()
             if img_index_number > 0:
@@ -1209,44 +1258,25 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
             t1 = time.process_time()
             if img_index_number > 0:
                 acc["setup"] += t1 - t0
-            T_gt = gt_list[idx] if idx < len(gt_list) else (np.identity(4) if _live_frames is not None else np.full((4, 4), np.nan))
-            if T_Rgt_wrt_S is not None:
-                T_gt = tr.concatenate_matrices(T_Rgt_wrt_S, T_gt, T_S_wrt_Rgt)   # :1472
+            T_gt = T_gt_of(idx)
             if img_index_number > 0:
                 t0 = t1
                 ok, msg = tracker.track_frame(reference_frame=reference_frame, current_frame=current_frame)
                 if not ok:
-                    log_only.append((len(out_msgs), msg))
+                    out.say_to_log_only(msg)
                     warn("%sWarning failed: %s" % (prefix, msg))
                     break
                 reference_frame.children_ids.append(current_frame.frame_id)
                 tracked_wrt_keyframe += 1
                 acc["track"] += time.process_time() - t0
-                # keyframe policy (:1516-1550)
-                dist = tr.rpe_translation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
-                ang = tr.rpe_rotation_metric(current_frame.T_frame_wrt_tracking_ref_frame)
                 n_tracked = tracker.num_tracked_correspondences / float(tracker.number_of_cams)
                 acc["corr"] += n_tracked
-                M_K, M_F = reference_frame.num_valid_keypoints, current_frame.num_valid_keypoints
-                if (pos_thr < dist < pos_max) or (ang_thr < ang < ang_max):
-                    if n_tracked > thr_tracked * tracked_prev_avg and M_F > thr_keypoints * M_K:
-                        reason = ""
-                        if pos_thr < dist < pos_max:
-                            if ang < ang_max:
-                                reason += "translation %.2f < %.4f < %.2f [m]" % (pos_thr, dist, pos_max)
-                                create_keyframe = True
-                        elif ang_thr < ang:
-                            if dist < pos_max < ang_max:   # as written in the reference (:1534)
-                                reason += " rotation: %.2f > %.2f [radians]" % (ang, ang_thr)
-                                create_keyframe = True
-                        if create_keyframe:
-                            say("%sFrame [%d] as Keyframe due to %s... with %d tracked keypoint correspondences after tracking "
-                                "%d frames" % (prefix, idx, reason, n_tracked, tracked_wrt_keyframe))
-                        else:
-                            say("%sFrame [%d] as failed to create Keyframe due to some CRAZYNESS" % (prefix, idx))
-                    else:
-                        say("%sFrame [%d] as Keyframe...doesn't satisfy %d > %.2f * %.2f and %d > %.2f * %.2f"
-                            % (prefix, idx, n_tracked, thr_tracked, tracked_prev_avg, M_F, thr_keypoints, M_K))
+                create_keyframe, msg = keyframe_policy(
+                    tr.rpe_translation_metric(current_frame.T_frame_wrt_tracking_ref_frame),
+                    tr.rpe_rotation_metric(current_frame.T_frame_wrt_tracking_ref_frame), n_tracked, tracked_prev_avg,
+                    current_frame.num_valid_keypoints, reference_frame.num_valid_keypoints, thresholds, prefix, idx, tracked_wrt_keyframe)
+                if msg is not None:
+                    out.say(msg)
                 tracked_prev_avg = (n_tracked + (float(tracked_wrt_keyframe) - 1.) * tracked_prev_avg) / float(tracked_wrt_keyframe)
                 acc["ratio"] += tracker.inlier_tracked_correspondences_ratio
                 inlier_ratio_cma = (tracker.inlier_tracked_correspondences_ratio + float(img_index_number - 1) * inlier_ratio_cma) \
@@ -1258,7 +1288,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
                 if dev_info is not None:
                     current_frame.promote()   # the frame's record moves to the store's keyframe slot
                 current_keyframe_id = reference_frame.frame_id
-                kf_lines.append("%d\n" % current_keyframe_id)
+                out.keyframe(current_keyframe_id)
                 keyframe_ids.append(current_keyframe_id)
                 if len(tracker.T_Ckey_wrt_S_est_list) > 0:
                     T_key = tr.concatenate_matrices(tracker.T_Ckey_wrt_S_est_list[-1], reference_frame.T_frame_wrt_tracking_ref_frame)
@@ -1266,46 +1296,29 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
                     T_key = tracker.T_C_curr_frame_wrt_S_est
                 tracker.T_Ckey_wrt_S_est_list.append(T_key)
                 create_keyframe = False
-                number_of_keyframes += 1
-            # TUM lines: idx tx ty tz qx qy qz qw (:1611-1621), quaternion_from_matrix(isprecise=False) of the pose -- formatted by
-            # flush_output (a window at a time in sequence mode)
             T_now = np.array(tracker.T_C_curr_frame_wrt_S_est, copy=True)
-            pending.append((idx, T_now, T_gt))
+            out.pose(idx, T_now, T_gt)
             poses_out.append((idx, T_now))
             if img_index_number > 0:
                 acc["vo"] += time.process_time() - t_frame
             n_done = img_index_number
-            say("%sDONE with F[%d] (Parent K[%d]). C.M.Avg. RANSAC inlier ratio = %.3f"
+            out.say("%sDONE with F[%d] (Parent K[%d]). C.M.Avg. RANSAC inlier ratio = %.3f"
                 % (prefix, current_frame.frame_id, current_frame.parent_id, inlier_ratio_cma))
-            if not batched_output:
-                flush_output()
-        d = float(max(n_done, 1))
-        summary = "\n".join([
-            "%sVO done with %d keyframes" % (prefix, number_of_keyframes),
-            "Image Read Avg Time: {time:.8f} seconds".format(time=acc["read"] / d),
-            "Frame Setup Avg Time: {time:.8f} seconds".format(time=acc["setup"] / d),
-            "Frame Tracking Avg Time: {time:.8f} seconds".format(time=acc["track"] / d),
-            "Overall Frame VO Avg Time: {time:.8f} seconds".format(time=acc["vo"] / d),
-            "Total Number of tracked correspondences: {corrs}".format(corrs=int(acc["corr"])),
-            "Average Number of tracked correspondences: {corrs}".format(corrs=int(int(acc["corr"]) / d)),
-            "Average tracked correspondences RANSAC inlier ratio: {ratio:.8f}".format(ratio=acc["ratio"] / d),
-            "Estimated poses in TUM format SAVED as " + est_path,
-            "Keyframes (indices) SAVED as " + kf_path])
-        say(summary)
+            if dev_info is None:   # (sequence mode: lines are written once per window, out.flush in the window generator)
+                out.flush()
+        summary = _vo_summary(prefix, len(keyframe_ids), acc, n_done, out.est_path, out.kf_path)
+        out.say(summary)
     finally:   # (an exception too: the lines of the frames tracked so far and the keyframe file are written)
         close = getattr(frame_iter, "close", None)
         if close is not None:
             close()   # (sequence mode: its staging thread ends before the engine can go to another run)
-        flush_output()
-        kf_file.write("".join(kf_lines))
-        for f in (est_file, gt_file, kf_file, log):
-            f.close()
-    out = dict(poses=poses_out, keyframe_ids=keyframe_ids, tracked=n_done, message=summary)
+        out.close()
+    result = dict(poses=poses_out, keyframe_ids=keyframe_ids, tracked=n_done, message=summary)
     if engine_state["engine"] is not None:
         eng = engine_state["engine"]
-        out["sequence_mode"] = dict(frame_window=eng.W, windows=engine_state["windows"], serial_tracking_calls=eng.serial_calls,
-                                    front_end_and_speculation_s=engine_state["window_s"], stage_s=dict(eng.stage_s))
-    return out
+        result["sequence_mode"] = dict(frame_window=eng.W, windows=engine_state["windows"], serial_tracking_calls=eng.serial_calls,
+                                       front_end_and_speculation_s=engine_state["window_s"], stage_s=dict(eng.stage_s))
+    return result
 
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
@@ -1335,6 +1348,42 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
 
 
+def _est_poses_filename(timestamped):
+    """The pose file's name: plain next to a worker thread's run, with the time of the call otherwise (:1700-1706)."""
+    if not timestamped:
+        return "estimated_frame_poses_TUM.txt"
+    from datetime import datetime
+    now = datetime.now()
+    return "estimated_frame_poses_TUM-%d-%d-%d-%d-%d-%d.txt" % (now.year, now.month, now.day, now.hour, now.minute, now.second)
+
+
+def _on_worker_thread(fn, **kwargs):
+    """fn(**kwargs) on a thread of its own (one libsosvo context per host thread, INTEGRATION.md section 6: the worker creates
+    its own) -> its result; what it raises is raised here."""
+    result, failure = [], []
+
+    def work():
+        try:
+            result.append(fn(**kwargs))
+        except BaseException as e:  # noqa: B902 -- handed to the calling thread
+            failure.append(e)
+    th = threading.Thread(target=work)
+    th.start()
+    th.join()
+    if failure:
+        raise failure[0]
+    return result[0]
+
+
+def _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index, last_image_index, step_for_scene_images):
+    """-> (gt_TUM.txt of the scene, None for a scene taken with a static rig; the frame index list) (:1708-1722)."""
+    low = scene_path.lower()
+    rig_is_static = "static" in low or "GCT" in scene_path.upper() or "CCNY" in scene_path.upper() or "park" in low \
+        or "grand" in low
+    last = min(last_image_index, num_scene_images) if last_image_index > 0 else num_scene_images
+    return (None if rig_is_static else os.path.join(scene_path, "gt_TUM.txt")), list(range(first_image_index, last, step_for_scene_images))
+
+
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
                    gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
@@ -1342,39 +1391,21 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
     and join the camera thread."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
-    if use_multithreads_for_VO:
-        est_poses_filename = "estimated_frame_poses_TUM.txt"
-    else:
-        from datetime import datetime
-        now = datetime.now()
-        est_poses_filename = "estimated_frame_poses_TUM-%d-%d-%d-%d-%d-%d.txt" % (now.year, now.month, now.day, now.hour,
-                                                                                   now.minute, now.second)
+    options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+    est_poses_filename = _est_poses_filename(timestamped=not use_multithreads_for_VO)
     cam_working_thread.start()
     if not getattr(cam_working_thread, "lockstep", False):
         while cam_working_thread.current_frame is None and cam_working_thread.is_alive() and not cam_working_thread.quit_flag:
             time.sleep(0.001)   # (the reference starts tracking at once and stops if no frame has arrived yet)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, cam_working_thread=cam_working_thread,
                   est_poses_filename=est_poses_filename, results_path=scene_path_vo_results, thread_name=thread_name,
-                  frame_window=frame_window, detection_method=detection_method, cross_check=cross_check,
-                  gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
-    result, failure = {}, []
+                  frame_window=frame_window, **options)
     try:
-        if use_multithreads_for_VO:
-            def work():
-                try:
-                    result.update(run_VO_live(**kwargs))
-                except BaseException as e:  # noqa: B902 -- handed to the calling thread
-                    failure.append(e)
-            th = threading.Thread(target=work)
-            th.start()
-            th.join()
-        else:
-            result.update(run_VO_live(**kwargs))
+        result = _on_worker_thread(run_VO_live, **kwargs) if use_multithreads_for_VO else run_VO_live(**kwargs)
     finally:
         cam_working_thread.quit_flag = True   # :1792-1793
         cam_working_thread.join()
-    if failure:
-        raise failure[0]
     print("DONE")
     return result
 
@@ -1387,44 +1418,16 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
-    if use_multithreads_for_VO:
-        est_poses_filename = "estimated_frame_poses_TUM.txt"
-    else:
-        from datetime import datetime
-        now = datetime.now()
-        est_poses_filename = "estimated_frame_poses_TUM-%d-%d-%d-%d-%d-%d.txt" % (now.year, now.month, now.day, now.hour,
-                                                                                   now.minute, now.second)
-    gt_poses_filename = None
-    low = scene_path.lower()
-    rig_is_static = "static" in low or "GCT" in scene_path.upper() or "CCNY" in scene_path.upper() or "park" in low \
-        or "grand" in low
-    if not rig_is_static:
-        gt_poses_filename = os.path.join(scene_path, "gt_TUM.txt")
-    last_image_index = min(last_image_index, num_scene_images) if last_image_index > 0 else num_scene_images
-    vo_frame_indices = list(range(first_image_index, last_image_index, step_for_scene_images))
+    options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+    gt_poses_filename, vo_frame_indices = _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index,
+                                                                          last_image_index, step_for_scene_images)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
-                  est_poses_filename=est_poses_filename, img_filename_template=scene_img_filename_template,
-                  depth_filename_template=depth_filename_template, img_indices=vo_frame_indices,
-                  results_path=scene_path_vo_results, thread_name=thread_name, frame_window=frame_window,
-                  detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                  gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
-    result = {}
-    if use_multithreads_for_VO:
-        # one libsosvo context per host thread (INTEGRATION.md section 6): the worker creates its own
-        failure = []
-
-        def work():
-            try:
-                result.update(run_VO(**kwargs))
-            except BaseException as e:  # noqa: B902 -- handed to the calling thread
-                failure.append(e)
-        th = threading.Thread(target=work)
-        th.start()
-        th.join()
-        if failure:
-            raise failure[0]
-    else:
-        result.update(run_VO(**kwargs))
+                  est_poses_filename=_est_poses_filename(timestamped=not use_multithreads_for_VO),
+                  img_filename_template=scene_img_filename_template, depth_filename_template=depth_filename_template,
+                  img_indices=vo_frame_indices, results_path=scene_path_vo_results, thread_name=thread_name,
+                  frame_window=frame_window, **options)
+    result = _on_worker_thread(run_VO, **kwargs) if use_multithreads_for_VO else run_VO(**kwargs)
     print("%s Done with VO for %s!" % (thread_name, scene_path))
     return result
 
@@ -1492,6 +1495,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
                                               else "an omnistereo camera model takes no depth maps: SOS and RGB-D "
                                                    "sequences do not mix"))
     S = _lane_limit(len(sequences), lanes, W)
+    options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
     shared = dict(engine=None, key=None)
     guard, exited = threading.Lock(), set()
 
@@ -1512,7 +1517,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
                                 shared["engine"].begin(other)
                 if shared["engine"] is False:
                     raise ValueError("run_VO_many: this tracker configuration has no batched engine")
-                settings = (_rgbd_engine_settings if rgbd else _sos_engine_settings)(tracker, cm, first_image)
+                settings = _engine_settings(tracker, cm, first_image)
                 if settings is None or settings[2] != shared["key"] or shape != shared["shape"]:
                     raise ValueError("run_VO_many: the sequence does not fit the lanes' engine (another frame size, rig or "
                                      "tracker configuration)")
@@ -1533,10 +1538,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
                 return
             i, q = job
             try:
-                out = run_VO(None, camera_model, frame_window=W, detection_method=detection_method, cross_check=cross_check,
-                             gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test,
-                             ratio=ratio,
-                             _keyframe_thresholds=_keyframe_thresholds, _engine_for=engine_for_lane(s), **q)
+                out = run_VO(None, camera_model, frame_window=W, _keyframe_thresholds=_keyframe_thresholds,
+                             _engine_for=engine_for_lane(s), **options, **q)
                 if "sequence_mode" in out:
                     out["sequence_mode"].update(lane=s, lanes=S)
                 results[i] = out
@@ -1574,21 +1577,17 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
+    options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
     sequences = []
     for sc in scenes:
-        scene_path, n_img = sc["scene_path"], int(sc["num_scene_images"])
-        low = scene_path.lower()
-        rig_is_static = "static" in low or "GCT" in scene_path.upper() or "CCNY" in scene_path.upper() or "park" in low \
-            or "grand" in low
-        last = min(last_image_index, n_img) if last_image_index > 0 else n_img
-        sequences.append(dict(gt_poses_filename=None if rig_is_static else os.path.join(scene_path, "gt_TUM.txt"),
-                              est_poses_filename="estimated_frame_poses_TUM.txt",
+        gt_poses_filename, indices = _scene_ground_truth_and_indices(sc["scene_path"], int(sc["num_scene_images"]), first_image_index,
+                                                                     last_image_index, step_for_scene_images)
+        sequences.append(dict(gt_poses_filename=gt_poses_filename, est_poses_filename=_est_poses_filename(timestamped=False),
                               img_filename_template=sc["scene_img_filename_template"],
-                              depth_filename_template=sc.get("depth_filename_template"),
-                              img_indices=list(range(first_image_index, last, step_for_scene_images)),
+                              depth_filename_template=sc.get("depth_filename_template"), img_indices=indices,
                               results_path=sc["scene_path_vo_results"], thread_name=sc.get("thread_name", "")))
-    results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window,
-                          detection_method=detection_method, lanes=lanes, shard=shard, cross_check=cross_check,
-                          gated_matching=gated_matching, gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+    results = run_VO_many(camera_model, sequences, frame_window=32 if frame_window is None else frame_window, lanes=lanes,
+                          shard=shard, **options)
     print("Done with VO for %d sequences!" % len(results))
     return results
