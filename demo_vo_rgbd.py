@@ -52,6 +52,11 @@ def main_rgbd_vo(argv=None):
     parser.add_argument("--ratio", default=None, type=float,
                         help="with --ratio_test: keep a match iff its distance is below this times the runner-up's; a multiple "
                              "of 1/64 in (0, 1), e.g. 0.75")
+    parser.add_argument("--subpix_refine", action="store_true",
+                        help="move the detected keypoints to their sub-pixel positions (cornerSubPix, on the GPU) before the "
+                             "static-stereo matching; default: off (an RGB-D camera reads depth at integer pixels: refused)")
+    parser.add_argument("--subpix_half", default=None, type=int,
+                        help="with --subpix_refine: the window half-size 2 .. 5; default: 5")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -92,6 +97,7 @@ def main_rgbd_vo(argv=None):
                              detection_method=args.detection_method, cross_check=True if args.cross_check else None,
                              gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
                              ratio_test=True if args.ratio_test else None, ratio=args.ratio,
+                             subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half,
                              lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
@@ -104,7 +110,8 @@ def main_rgbd_vo(argv=None):
                     frame_window=None if args.frame_window < 0 else args.frame_window,
                     detection_method=args.detection_method, cross_check=True if args.cross_check else None,
                     gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
-                    ratio_test=True if args.ratio_test else None, ratio=args.ratio)
+                    ratio_test=True if args.ratio_test else None, ratio=args.ratio,
+                    subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half)
     print("GOODBYE!")
     return out
 

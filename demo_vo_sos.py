@@ -56,6 +56,11 @@ def main_sos_vo(argv=None):
     parser.add_argument("--ratio", default=None, type=float,
                         help="with --ratio_test: keep a match iff its distance is below this times the runner-up's; a multiple "
                              "of 1/64 in (0, 1), e.g. 0.75")
+    parser.add_argument("--subpix_refine", action="store_true",
+                        help="move the detected keypoints to their sub-pixel positions (cornerSubPix, on the GPU) before the "
+                             "static-stereo matching; default: off")
+    parser.add_argument("--subpix_half", default=None, type=int,
+                        help="with --subpix_refine: the window half-size 2 .. 5; default: 5")
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
@@ -79,7 +84,7 @@ def main_sos_vo(argv=None):
     gated = dict(gated_matching=None if args.gated_matching is None else (True if args.gated_matching == "both" else args.gated_matching),
                  gated_max_distance=args.gated_max_distance,
                  ratio_test=None if args.ratio_test is None else (True if args.ratio_test == "both" else args.ratio_test),
-                 ratio=args.ratio)
+                 ratio=args.ratio, subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half)
     if len(scenes) > 1:
         out = driver_VO_many(camera_model=gums_calibrated, scenes=scenes, visualize_VO=args.visualize_VO,
                              step_for_scene_images=args.step, first_image_index=args.first_image_index,

@@ -70,6 +70,7 @@ int main(int argc, char** argv) {
   if (!f) return 1;
   sosvo_batch_cfg cfg;
   sosvo_rig rig;
+  /* (cfg.ransac_flags |= SOSVO_FLAG_SUBPIX | SOSVO_SUBPIX_HALF(5) would refine the keypoints to sub-pixel positions) */
   if (fread(&cfg, sizeof(cfg), 1, f) != 1 || fread(&rig, sizeof(rig), 1, f) != 1) return 4;
   const size_t B = (size_t)cfg.n_pairs, HW = (size_t)cfg.H * cfg.W, P = (size_t)cfg.rows * cfg.cols;
   uint8_t* omni = (uint8_t*)upload(f, 2 * B * HW * 3);

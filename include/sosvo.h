@@ -221,6 +221,35 @@ int32_t sosvo_describe_orb_rows(sosvo_ctx* ctx, const uint8_t* gray, int32_t nim
                                 int32_t nmask, int32_t cap, float* kp, int32_t* n, float cos_a, float sin_a,
                                 const int8_t* pattern, int32_t edge, const int32_t* row_range, uint8_t* desc);
 
+/* ---- sub-pixel refinement of detected keypoints (cv2.cornerSubPix, the companion of goodFeaturesToTrack) ----------
+ * Refines kp [nimg*nmask, cap, 2] f32 IN PLACE on gray [nimg, rows, cols] u8, the image the detector saw; n, the order and
+ * the rows of kp at and beyond n[p] are untouched.  Problem p = image * nmask + mask as above.  The rule is cornerSubPix
+ * restated in exact integers.  Per keypoint: c0 = the position as given (f32 -> double), c = c0; each iteration
+ *   1. rounds the sampling centre to 1/32 px: xq = floor(32 c.x + 0.5), yq likewise;
+ *   2. takes the (2 half + 3)^2 bilinear samples at centre + (j - half - 1, i - half - 1) px as integers,
+ *      S = (32 - fy) ((32 - fx) p00 + fx p01) + fy ((32 - fx) p10 + fx p11) <= 255 * 1024; pixel coordinates are
+ *      clamped (replicated) to the columns [0, cols) and to the rows [first, last + 1) of the view's row_range;
+ *   3. over the (2 half + 1)^2 window, in int64: gx = S[i+1][j+2] - S[i+1][j], gy = S[i+2][j+1] - S[i][j+1],
+ *      m = (w[i] w[j]) >> 8 with the table of sosvo_subpix_weights, px = j - half, py = i - half,
+ *      a += gx gx m, b += gx gy m, c2 += gy gy m, b1 += gx gx m px + gx gy m py, b2 += gx gy m px + gy gy m py
+ *      (each sum < 2^55: exact, whatever the order of summation);
+ *   4. solves in double, every sum converted once: det = a c2 - b b; det == 0 ends the iteration and c stays; otherwise
+ *      c' = (xq / 32 + (c2 b1 - b b2) / det, yq / 32 + (a b2 - b b1) / det), err = |c' - c|^2;
+ *   5. if !(|c'.x - c0.x| <= half && |c'.y - c0.y| <= half) the result is c0 (a NaN reverts too); otherwise c = c', and the
+ *      iteration ends after max_iter iterations or when err <= eps^2.
+ * The output is (float)c.  A keypoint with a non-finite coordinate is left as it is.  Reads stay within 2 half + 2 px of c0.
+ *   half 2..5, max_iter >= 1, eps >= 0 (cv2's TermCriteria(COUNT + EPS, max_iter, eps)); otherwise SOSVO_ERR_ARG.
+ *   row_range: int32 [2][2] in DEVICE memory as for sosvo_describe_orb_rows (view-major, nimg even); NULL = all rows.  A
+ *   range is cut to the image and holds at least one row.  With the range the gray image was computed for, keypoints that
+ *   sosvo_describe_orb_rows kept never touch the clamp (pattern radius + 3 >= 2 half + 2).
+ * sosvo_subpix_weights: the table w[k] = floor(256 exp(-((k - half) / half)^2) + 0.5), k = 0 .. 2 half, written to HOST memory
+ * (2 half + 1 int32); what the kernel uses, so that a reference on another libm cannot differ in the last bit.  ctx may be
+ * NULL (it only receives the error message); no GPU needed.                                                          */
+int32_t sosvo_subpix_weights(sosvo_ctx* ctx, int32_t half, int32_t* w_host);
+int32_t sosvo_refine_subpix(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t nmask,
+                            int32_t cap, float* kp, const int32_t* n, int32_t half, int32_t max_iter, double eps,
+                            const int32_t* row_range);
+
 /* ---- K5: ORB keypoint detection per azimuthal mask (a4, feature_detection_method "ORB") ----------
  * Replaces cv2.ORB_create(nfeatures=N).detect(image, mask) (omnistereo/camera_models.py:1640, :1755;
  * pose_est_tools.py:478, :547) for all azimuthal masks of all images at once: 8 levels x 1.2, per-level
@@ -666,6 +695,21 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
 #define SOSVO_RATIO_64THS(r) ((r) << SOSVO_RATIO_64THS_SHIFT)
 #define SOSVO_RATIO_64THS_OF(flags) (((flags) & SOSVO_RATIO_64THS_MASK) >> SOSVO_RATIO_64THS_SHIFT)
 
+/* ---- sub-pixel keypoint refinement in the batch and sequence entry points (sosvo_refine_subpix) --------------
+ *   SOSVO_FLAG_SUBPIX        refine every keypoint after the descriptor stage and before the static-stereo matching
+ *   SOSVO_SUBPIX_HALF(h)     bits 10-11: the window half-size h = 2 .. 5, stored as h - 2; ignored without the switch bit
+ * max_iter is 10 and eps 0.01 here.  Honoured in sosvo_batch_cfg.ransac_flags for every detector (ORB: on kp_xy; kp4 keeps
+ * the detector's positions).  Descriptors stay those of the unrefined positions, bit for bit; the stereo gates, the gated
+ * search, bearings, triangulation, the frame records' m_top / m_bot and everything after them see the refined positions.
+ * In sosvo_rgbd_batch_cfg.flags the switch is SOSVO_ERR_ARG (and a workspace size of 0): depth is read at integer pixels.
+ * The bits never reach the RANSAC flags; the struct layouts and, with the switch clear, workspace sizes, launches and
+ * results are unchanged -- the stage needs no workspace. */
+#define SOSVO_FLAG_SUBPIX 0x40
+#define SOSVO_SUBPIX_HALF_SHIFT 10
+#define SOSVO_SUBPIX_HALF_MASK (3 << SOSVO_SUBPIX_HALF_SHIFT)
+#define SOSVO_SUBPIX_HALF(h) (((h) - 2) << SOSVO_SUBPIX_HALF_SHIFT)
+#define SOSVO_SUBPIX_HALF_OF(flags) ((((flags) & SOSVO_SUBPIX_HALF_MASK) >> SOSVO_SUBPIX_HALF_SHIFT) + 2)
+
 /* ---- the whole hot path for a batch of frame pairs (the throughput entry point) ----------------
  * One call = for B independent pairs (frames 2i = reference / keyframe, 2i+1 = current):
  *   OmniStereoModel.set_current_omni_image + StereoPanoramicFrame.__init__ for both frames
@@ -712,8 +756,9 @@ typedef struct sosvo_batch_cfg {
   int32_t ransac_flags;    /* SOSVO_FLAG_GP3P: generalised-P3P hypotheses (samples across both mirrors); 0: one-mirror P3P;
                               SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above);
                               SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above);
-                              SOSVO_FLAG_RATIO_STEREO / _F2F, SOSVO_RATIO_64THS(r): the ratio rule (see above) */
-  int32_t detector;        /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
+                              SOSVO_FLAG_RATIO_STEREO / _F2F, SOSVO_RATIO_64THS(r): the ratio rule (see above);
+                              SOSVO_FLAG_SUBPIX, SOSVO_SUBPIX_HALF(h): sub-pixel keypoint refinement (see above) */
+  int32_t detector;       /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg);
@@ -852,6 +897,7 @@ typedef struct sosvo_rgbd_batch_cfg {
                               SOSVO_FLAG_CROSS_CHECK_F2F: mutual matches only (masked off as well; ..._STEREO: SOSVO_ERR_ARG).
                               SOSVO_FLAG_GATED_F2F, SOSVO_GATED_MAX_DIST(d): search under the gate (likewise; ..._STEREO: SOSVO_ERR_ARG).
                               SOSVO_FLAG_RATIO_F2F, SOSVO_RATIO_64THS(r): the ratio rule (likewise; ..._STEREO: SOSVO_ERR_ARG).
+                              SOSVO_FLAG_SUBPIX: SOSVO_ERR_ARG (depth is read at integer pixels).
                               The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
                               for every frame) */
   double quality, min_distance;        /* 0.01, 5 */

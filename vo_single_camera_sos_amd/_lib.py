@@ -62,6 +62,8 @@ SIGNATURES = {
                                    c_p]),
     "sosvo_describe_orb_rows": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_f32, c_f32, c_p, c_i32,
                                         c_p, c_p]),
+    "sosvo_subpix_weights": (c_i32, [c_p, c_i32, c_p]),
+    "sosvo_refine_subpix": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_f64, c_p]),
     "sosvo_orb_pyramid_pixels": (ctypes.c_int64, [c_i32, c_i32]),
     "sosvo_orb_mask_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_detect_orb": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
@@ -142,6 +144,11 @@ FLAG_RATIO_STEREO = 0x10           # the ratio rule: static stereo (sosvo_batch_
 FLAG_RATIO_F2F = 0x20              # ... frame to frame (sosvo_batch_cfg.ransac_flags, sosvo_rgbd_batch_cfg.flags)
 RATIO_64THS_SHIFT = 25             # SOSVO_RATIO_64THS(r): bits 25-30, the ratio in 64ths, 1 .. 63
 RATIO_64THS_MASK = 0x3F << RATIO_64THS_SHIFT
+FLAG_SUBPIX = 0x40                 # sub-pixel keypoint refinement before the static stereo (sosvo_batch_cfg.ransac_flags)
+SUBPIX_HALF_SHIFT = 10             # SOSVO_SUBPIX_HALF(h): bits 10-11, the window half-size 2 .. 5 stored as h - 2
+SUBPIX_HALF_MASK = 3 << SUBPIX_HALF_SHIFT
+SUBPIX_MAX_ITER = 10               # what the one-call and sequence entry points run the stage with
+SUBPIX_EPS = 0.01
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1
 DETECTOR_FAST = 2
@@ -241,6 +248,39 @@ def ratio_flags(stereo=False, f2f=False, ratio=None):
     if flags:
         flags |= r << RATIO_64THS_SHIFT
     return flags
+
+
+def subpix_half(subpix):
+    """A `subpix` argument (None / False: off; True: half 5; or the window half-size 2 .. 5) -> the half-size or None."""
+    if subpix is None or subpix is False:
+        return None
+    if subpix is True:
+        return 5
+    if int(subpix) != subpix or not 2 <= subpix <= 5:
+        raise ValueError("subpix must be None or a window half-size in 2 .. 5, got %r" % (subpix,))
+    return int(subpix)
+
+
+def subpix_flags(subpix=None):
+    """The SOSVO_FLAG_SUBPIX bit and the SOSVO_SUBPIX_HALF field of a batch configuration; the field belongs to the
+    switch: without it nothing is encoded."""
+    half = subpix_half(subpix)
+    return 0 if half is None else FLAG_SUBPIX | ((half - 2) << SUBPIX_HALF_SHIFT)
+
+
+def subpix_half_of(flags):
+    """SOSVO_SUBPIX_HALF_OF(flags) with the switch set, else None."""
+    flags = int(flags)
+    return ((flags & SUBPIX_HALF_MASK) >> SUBPIX_HALF_SHIFT) + 2 if flags & FLAG_SUBPIX else None
+
+
+def subpix_weights(half):
+    """sosvo_subpix_weights: the library's weight table of a window half-size (host call, no GPU)."""
+    w = (c_i32 * 11)()      # (the largest table: half 5)
+    rc = load().sosvo_subpix_weights(None, int(half), w)
+    if rc != 0:
+        raise SosvoError("sosvo_subpix_weights(%r) -> %s" % (half, STATUS_NAMES.get(rc, rc)))
+    return list(w)[:2 * int(half) + 1]
 
 
 class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2f gated_stereo gated_f2f gated_max_distance "

@@ -88,11 +88,13 @@ Ratio carve_ratio(Carver& cv, int32_t r64, size_t n_keys) {
 }
 constexpr const char* kBadRatioFlags = "SOSVO_FLAG_RATIO_STEREO / _F2F need SOSVO_RATIO_64THS(r), r in 1..63";
 
+// (SOSVO_FLAG_SUBPIX is refused with them: the RGB-D assemble stage reads depth at the keypoints' integer pixels)
 bool rgbd_stereo_flags_ok(const sosvo_rgbd_batch_cfg& c) {
-  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO | SOSVO_FLAG_RATIO_STEREO)) == 0;
+  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO | SOSVO_FLAG_RATIO_STEREO | SOSVO_FLAG_SUBPIX)) == 0;
 }
 constexpr const char* kRgbdStereoFlags =
-    "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO / SOSVO_FLAG_RATIO_STEREO: an RGB-D camera has no static stereo";
+    "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO / SOSVO_FLAG_RATIO_STEREO: an RGB-D camera has no static stereo; "
+    "SOSVO_FLAG_SUBPIX: depth is read at integer pixels";
 bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) { return rgbd_stereo_flags_ok(c) && ratio_flags_ok(c.flags); }
 
 // ---- gated matching (SOSVO_FLAG_GATED_*): the 1-NN search among the trains that pass the assemble stage's own pixel gate.
@@ -639,6 +641,11 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
     STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
                                   cfg->edge, rows_known ? t.gray_rows : nullptr, t.desc));
   }
+  // sub-pixel refinement (SOSVO_FLAG_SUBPIX) where ImageFrontEnd.run_features has it: the descriptors above are those of the
+  // detector's positions, everything below sees the refined ones (ORB: kp_xy; kp4 keeps the detector's)
+  if (cfg->ransac_flags & SOSVO_FLAG_SUBPIX)
+    STAGE(sosvo_refine_subpix(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, SOSVO_SUBPIX_HALF_OF(cfg->ransac_flags), 10,
+                              0.01, rows_known ? t.gray_rows : nullptr));
   // static stereo per frame: query = bottom view, train = top view, bucket by bucket
   const float *kp_top = t.kp, *kp_bot = t.kp + (size_t)h * cap * 2;
   const uint8_t *desc_top = t.desc, *desc_bot = t.desc + (size_t)h * cap * 32;

@@ -295,6 +295,21 @@ class Context(object):
                    float(cos_a), float(sin_a), _ptr(pattern), int(edge), _ptr(row_range), _ptr(desc))
         return desc
 
+    def refine_subpix(self, gray, kp, n, nmask, half=5, max_iter=_lib.SUBPIX_MAX_ITER, eps=_lib.SUBPIX_EPS, row_range=None):
+        """cv2.cornerSubPix in exact integers (sosvo_refine_subpix): refines kp [NI*nmask, cap, 2] f32 in place on gray
+        [NI,rows,cols] u8, the image the detector saw; n and the rows beyond it are untouched.  half 2 .. 5; row_range
+        (int32 [2,2] on the device, from gray_rows_needed): samples are clamped to those rows of each view."""
+        _check(gray, torch.uint8, "gray", ndim=3)
+        NI, rows, cols = gray.shape
+        P = NI * nmask
+        _check(kp, torch.float32, "kp", (P, None, 2))
+        _check(n, torch.int32, "n", (P,))
+        if row_range is not None:
+            _check(row_range, torch.int32, "row_range", (2, 2))
+        self._call(self._lib.sosvo_refine_subpix, _ptr(gray), NI, rows, cols, int(nmask), kp.shape[1], _ptr(kp), _ptr(n),
+                   int(half), int(max_iter), float(eps), _ptr(row_range))
+        return kp
+
     # ---- K5 / K6' ----------------------------------------------------------------------
     def orb_pyramid_pixels(self, rows, cols):
         return int(self._lib.sosvo_orb_pyramid_pixels(int(rows), int(cols)))

@@ -5,7 +5,7 @@ at once.  All buffers live in HBM; a run is five asynchronous C-ABI calls (K1, K
 import numpy as np
 import torch
 
-from . import orb_pattern
+from . import _lib, orb_pattern
 from .device import Context
 
 
@@ -69,10 +69,12 @@ def mirror_kp_cap(method, num_of_features):
 class ImageFrontEnd(object):
     def __init__(self, ctx, model, nframes, detection_method="GFT", num_of_features=1000, kp_cap=None,
                  median_win_size=11, quality=0.01, min_distance=5.0, edge=31, keep_panoramas=True,
-                 skip_unreachable_rows=True):
+                 skip_unreachable_rows=True, subpix=None):
         """num_of_features: per azimuthal mask (FeatureMatcher.num_of_features, pose_est_tools.py:862).
         keep_panoramas=False: K1 is fused into the median kernel and the colour panoramas are not materialised
-        (nothing downstream of K3 reads them); identical gray images."""
+        (nothing downstream of K3 reads them); identical gray images.
+        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel refinement (Context.refine_subpix) that
+        run_features applies to the keypoints after their descriptors are computed."""
         if detection_method.upper() not in ("GFT", "ORB", "FAST", "AGAST"):
             raise NotImplementedError("detection method %r: GFT (the reference default, pose_est_tools.py:684), ORB, "
                                       "FAST and AGAST are built" % detection_method)
@@ -81,6 +83,7 @@ class ImageFrontEnd(object):
         self.num_of_features, self.median_win_size = int(num_of_features), int(median_win_size)
         self.quality, self.min_distance, self.edge = float(quality), float(min_distance), int(edge)
         self.skip_unreachable_rows = bool(skip_unreachable_rows)
+        self.subpix = _lib.subpix_half(subpix)
         self.kp_cap = int(kp_cap) if kp_cap else default_kp_cap(self.method, self.num_of_features)
         dev, m = ctx.device, model
         NI, P = 2 * self.F, 2 * self.F * m.nmask
@@ -132,7 +135,14 @@ class ImageFrontEnd(object):
                                  row_range=self.gray_rows)                                           # K1 + K2 + K3
 
     def run_features(self):
-        """K4 / K5 + K6: keypoints and descriptors per azimuthal mask on the gray panoramas."""
+        """K4 / K5 + K6: keypoints and descriptors per azimuthal mask on the gray panoramas; then, with `subpix`, the
+        keypoints move to their sub-pixel positions (the descriptors stay those of the detector's positions)."""
+        self._detect_describe()
+        if self.subpix is not None:
+            self.ctx.refine_subpix(self.gray, self.kp, self.n, self.model.nmask, half=self.subpix,
+                                   row_range=None if self.keep_panoramas else self.gray_rows)
+
+    def _detect_describe(self):
         c, m = self.ctx, self.model
         if self.method == "ORB":
             c.detect_describe_orb(self.gray, m.mask_pyr, self.F, m.nmask, self.num_of_features, m.pattern, self.kp4,

@@ -238,13 +238,17 @@ class GUMStereo(object):
             self._dev_model = DeviceImageModel(self._context(), self, shape, mask_bits=bits)
         return self._dev_model
 
+    def _subpix_half(self):
+        """The sub-pixel refinement the frames detect with: the static-stereo matcher carries it (set_subpixel_refinement)."""
+        return getattr(self.feature_matcher_for_static_stereo, "subpix_half", None)
+
     def _front_end(self, method, num_of_features, median_win_size):
-        key = (str(method).upper(), int(num_of_features), int(median_win_size))
+        key = (str(method).upper(), int(num_of_features), int(median_win_size), self._subpix_half())
         if key not in self._front_ends:
             from ..frontend import ImageFrontEnd, mirror_kp_cap
             cap = mirror_kp_cap(key[0], num_of_features)
             self._front_ends[key] = ImageFrontEnd(self._context(), self._device_model(), 1, detection_method=key[0],
-                                                  num_of_features=key[1], kp_cap=cap, median_win_size=key[2])
+                                                  num_of_features=key[1], kp_cap=cap, median_win_size=key[2], subpix=key[3])
         return self._front_ends[key]
 
     def set_current_omni_image(self, img, pano_width_in_pixels=1200, generate_panoramas=False, idx=-1, view=False,
@@ -269,7 +273,7 @@ class GUMStereo(object):
             self.top_model.panorama.omni_img = self.bot_model.panorama.omni_img = img
 
     def _detect_both(self, method, num_of_features, median_win_size):
-        token = (self._omni_serial, str(method).upper(), int(num_of_features), int(median_win_size))
+        token = (self._omni_serial, str(method).upper(), int(num_of_features), int(median_win_size), self._subpix_half())
         if self._detect_cache[0] == token:
             return self._detect_cache[1]
         from .camera_models import KeyPoint

@@ -273,6 +273,8 @@ class TrackerSE3(object):
         # Lowe's ratio rule on the device (FeatureMatcher's ratio): off; see set_ratio_test
         self.ratio_static_stereo = None
         self.ratio_for_motion = None
+        # sub-pixel refinement of the detected keypoints (window half-size): off; see set_subpixel_refinement
+        self.subpix_half = None
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -558,6 +560,27 @@ def set_ratio_test(tracker, ratio_test, ratio=None):
                         lambda stereo, f2f: dict(ratio_static_stereo=of(stereo), ratio_for_motion=of(f2f)))
 
 
+def set_subpixel_refinement(tracker, subpix, half=5):
+    """Switch the sub-pixel refinement of the detected keypoints (cv2.cornerSubPix restated in integers, on the device:
+    Context.refine_subpix, after the descriptors and before the static-stereo matching).  subpix: None = leave the tracker's
+    own setting (and half is ignored), True / False; half: the window half-size 2 .. 5 (None: 5).  The static-stereo matcher
+    bootstrap_tracker built carries the setting to the frames, so the per-frame mirror path and the engine chosen from the
+    tracker's settings both follow.  An RGB-D tracker reads depth at the keypoints' integer pixels: True is a ValueError."""
+    from .._lib import subpix_half
+    if subpix is None:
+        return
+    if not isinstance(subpix, (bool, np.bool_)):
+        raise ValueError("subpix_refine: None, True or False; got %r" % (subpix,))
+    value = subpix_half(5 if half is None else half) if subpix else None     # (ValueError for a half outside 2 .. 5)
+    cm = tracker.camera_model
+    if value is not None and _is_rgbd_model(cm):
+        raise ValueError("subpix_refine: an RGB-D tracker reads depth at the keypoints' integer pixels")
+    fm = getattr(cm, "feature_matcher_for_static_stereo", None)
+    if fm is not None:
+        fm.subpix_half = value
+    tracker.subpix_half = value
+
+
 def _has_batched_counterpart(tracker, fm):
     """Whether the sequence engines run what `tracker` is set to; fm: the matcher the family's frames detect with (None:
     none yet)."""
@@ -600,11 +623,11 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           opts)
+           opts, getattr(fm, "subpix_half", None))
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
-                  **opts._asdict())
+                  subpix=getattr(fm, "subpix_half", None), **opts._asdict())
     return (model, rig), kwargs, key
 
 
@@ -1156,7 +1179,8 @@ def _vo_summary(prefix, number_of_keyframes, acc, n_done, est_path, kf_path):
 def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_filename="estimated_frame_poses_TUM.txt",
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
-           cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
+           cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
+           subpix_refine=None, subpix_half=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -1183,7 +1207,12 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
     ratio_test: Lowe's ratio rule in the matchers, evaluated on the device: a match is kept iff its distance is below
     ratio times the runner-up's (under gated_matching: the runner-up among the admissible candidates); same values as
-    cross_check.  ratio: a float in (0, 1) with ratio * 64 an integer, e.g. 0.75 (see set_ratio_test).  Off by default."""
+    cross_check.  ratio: a float in (0, 1) with ratio * 64 an integer, e.g. 0.75 (see set_ratio_test).  Off by default.
+
+    subpix_refine: the detected keypoints move to their sub-pixel positions before the static-stereo matching (the
+    descriptors stay those of the detector's positions); None = the tracker's own setting (off), True / False.
+    subpix_half: the window half-size 2 .. 5, None = 5 (see set_subpixel_refinement).  Sequence mode and the mirror path
+    follow alike; an RGB-D camera model refuses True."""
     from .common_cv import get_images
     if visualizer_3D_VO is not None:
         raise NotImplementedError("3-D visualisation is not built: pass visualizer_3D_VO=None")
@@ -1211,6 +1240,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         set_cross_check(tracker, cross_check)             # (likewise: it runs the matchers' crossCheck)
         set_gated_matching(tracker, gated_matching, gated_max_distance)   # (... and their search under the gates)
         set_ratio_test(tracker, ratio_test, ratio)                        # (... and their ratio rule)
+        set_subpixel_refinement(tracker, subpix_refine, subpix_half)      # (... and the frames' sub-pixel keypoints)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1323,7 +1353,8 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
                 results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
-                gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
+                gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
+                subpix_refine=None, subpix_half=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1345,7 +1376,8 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   results_path=results_path, thread_name=thread_name, _live_frames=frames,
                   _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                  gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+                  gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
+                  subpix_refine=subpix_refine, subpix_half=subpix_half)
 
 
 def _est_poses_filename(timestamped):
@@ -1386,13 +1418,15 @@ def _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_in
 
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
-                   gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
+                   gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
+                   subpix_refine=None, subpix_half=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
+                   subpix_refine=subpix_refine, subpix_half=subpix_half)
     est_poses_filename = _est_poses_filename(timestamped=not use_multithreads_for_VO)
     cam_working_thread.start()
     if not getattr(cam_working_thread, "lockstep", False):
@@ -1413,13 +1447,15 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
 def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filename_template, depth_filename_template,
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
               last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
-              gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None):
+              gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
+              subpix_refine=None, subpix_half=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
+                   subpix_refine=subpix_refine, subpix_half=subpix_half)
     gt_poses_filename, vo_frame_indices = _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index,
                                                                           last_image_index, step_for_scene_images)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
@@ -1444,7 +1480,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
                 _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None,
-                ratio=None):
+                ratio=None, subpix_refine=None, subpix_half=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1496,7 +1532,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
                                                    "sequences do not mix"))
     S = _lane_limit(len(sequences), lanes, W)
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
+                   subpix_refine=subpix_refine, subpix_half=subpix_half)
     shared = dict(engine=None, key=None)
     guard, exited = threading.Lock(), set()
 
@@ -1571,14 +1608,16 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
                    frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
-                   gated_max_distance=None, ratio_test=None, ratio=None):
+                   gated_max_distance=None, ratio_test=None, ratio=None,
+                   subpix_refine=None, subpix_half=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
-                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio)
+                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
+                   subpix_refine=subpix_refine, subpix_half=subpix_half)
     sequences = []
     for sc in scenes:
         gt_poses_filename, indices = _scene_ground_truth_and_indices(sc["scene_path"], int(sc["num_scene_images"]), first_image_index,

@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import MatchOptions
+from ._lib import MatchOptions, subpix_flags, subpix_half
 from .device import Context, make_rig
 
 
@@ -35,7 +35,7 @@ class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
                  adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+                 ratio_f2f=False, ratio=None, subpix=None):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
@@ -46,8 +46,14 @@ class FramePairPipeline(object):
         (Context.match_hamming_gated); gated_max_distance: None = no cap, or 1 .. 256: a match whose Hamming distance
         exceeds it is no match.
         ratio_stereo / ratio_f2f: Lowe's ratio rule fused into that matcher's search (Context.match_hamming_ratio), plain or
-        under the gate; ratio: a float in (0, 1) with ratio * 64 an integer (0.75 = the reference's, camera_models.py:423)."""
+        under the gate; ratio: a float in (0, 1) with ratio * 64 an integer (0.75 = the reference's, camera_models.py:423).
+        subpix: None = the front end's own setting, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement,
+        handed on to the front end (ImageFrontEnd's subpix)."""
         assert isinstance(ctx, Context)
+        if subpix is not None:
+            if front_end is None:
+                raise ValueError("subpix needs a front end: the refinement reads the gray panoramas")
+            front_end.subpix = subpix_half(subpix)
         # (ValueError for a cap out of range, a ratio that is no 64th)
         self.opts = o = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
                                      ratio_stereo, ratio_f2f, ratio)
@@ -190,7 +196,7 @@ class OverlappedFramePairs(object):
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+                 ratio_f2f=False, ratio=None, subpix=None):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray."""
         from .frontend import DeviceImageModel, ImageFrontEnd
@@ -217,7 +223,7 @@ class OverlappedFramePairs(object):
                     p.ctx.set_hint_shared_device(True)   # the parts run side by side: leave wave slots for each other
                 p.fe = ImageFrontEnd(p.ctx, m, 2 * (hi - lo), detection_method=detection_method,
                                      num_of_features=num_of_features, kp_cap=kp_cap, keep_panoramas=False,
-                                     median_win_size=median_win_size)
+                                     median_win_size=median_win_size, subpix=subpix)
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
                                            ransac_solver=ransac_solver, **opts._asdict())
@@ -350,7 +356,8 @@ class OverlappedFramePairs(object):
 
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
               adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
-              gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None):
+              gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
+              subpix=None):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
     any ransac_solver but "GP3P" is P3P."""
@@ -371,6 +378,7 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
     c.ransac_flags |= MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                                    ratio_f2f, ratio).flags()
+    c.ransac_flags |= subpix_flags(subpix)
     return c
 
 
@@ -382,10 +390,11 @@ class FramePairBatch(object):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+                 ratio_f2f=False, ratio=None, subpix=None):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
-        default capacity (frontend.default_kp_cap)."""
+        default capacity (frontend.default_kp_cap).
+        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement (SOSVO_FLAG_SUBPIX)."""
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
@@ -393,7 +402,7 @@ class FramePairBatch(object):
         self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                  median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                  max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                 detection_method=detection_method, **opts._asdict())
+                                 detection_method=detection_method, subpix=subpix, **opts._asdict())
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -819,12 +828,13 @@ class SequenceEngine(_SequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+                 ratio_f2f=False, ratio=None, subpix=None):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
         cross_check_stereo / cross_check_f2f: mutual matches only in the static-stereo / the frame-to-frame matcher.
-        gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline."""
+        gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline.
+        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement, as FramePairBatch."""
         self._init_windows(window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
@@ -832,7 +842,7 @@ class SequenceEngine(_SequenceBase):
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                detection_method=detection_method))
+                                detection_method=detection_method, subpix=subpix))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -1447,7 +1457,7 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None):
+                 ratio_f2f=False, ratio=None, subpix=None):
         self._init_lanes(lanes, window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
@@ -1455,7 +1465,7 @@ class MultiSequenceEngine(_MultiSequenceBase):
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                detection_method=detection_method))
+                                detection_method=detection_method, subpix=subpix))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
