@@ -250,6 +250,59 @@ int32_t sosvo_refine_subpix(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, i
                             int32_t cap, float* kp, const int32_t* n, int32_t half, int32_t max_iter, double eps,
                             const int32_t* row_range);
 
+/* ---- pyramidal Lucas-Kanade tracking (cv2.calcOpticalFlowPyrLK, the call the reference carries commented out beside its
+ * matcher, omnistereo/camera_models.py:3070) restated in exact integers ---------------------------------------------------
+ * sosvo_gray_pyramid builds the levels 1 .. levels - 1 of nimg gray images [nimg, rows, cols] u8; level 0 is the caller's
+ * buffer and is not copied.  rows_{l+1} = (rows_l + 1) / 2, cols likewise; a pixel of level l + 1 is
+ *   (sum over i, j in -2 .. 2 of k_i k_j L_l[clamp(2 y + i)][clamp(2 x + j)] + 128) >> 8,  k = (1, 4, 6, 4, 1).
+ * The border is REPLICATED (clamp), not OpenCV's reflect-101: a row range can clamp the same way.
+ *   row_range: int32 [2][2] in DEVICE memory as for sosvo_refine_subpix (view-major, nimg even; image i belongs to view
+ *   i / (nimg / 2)): rows [first, last + 1) of level 0, cut to the image and to at least one row; NULL = all rows.  The range
+ *   of level l + 1 is [(r0_l + 1) / 2, max((r1_l + 1) / 2, that + 1)), cut to the level's rows as at level 0 (a range on the
+ *   last row of an even level); only those rows are computed and written, and the reads of level l clamp into ITS range.
+ *   Rows outside keep what the buffer held.
+ *   pyr: the levels back to back, level l as [nimg, rows_l, cols_l]; sosvo_gray_pyramid_bytes gives its size (HOST out
+ *   pointer; ctx may be NULL, no GPU needed).  levels 1 .. 4 (1: nothing to do, pyr may be NULL); rows, cols <= 16384.
+ *
+ * sosvo_track_lk: problem p < nprob tracks the points prev_pts[p, 0 .. n[p]) ([nprob, cap, 2] f32, level-0 pixels) from
+ * image prev_img[p] to image next_img[p] of ONE pyramid set (gray = level 0, pyr = sosvo_gray_pyramid's output for the same
+ * nimg, rows, cols, levels, row_range; prev_img, next_img: [nprob] int32 in DEVICE memory, as the matcher's slots; a problem
+ * with an index outside [0, nimg) is ignored).  Outputs next_pts [nprob, cap, 2] f32, status [nprob, cap] u8 (1 = tracked),
+ * err [nprob, cap] f32; rows at and beyond n[p] are untouched.  Per point, p = the start (f32 -> double), g = the guess:
+ *   g = p, or next_pts on entry with SOSVO_LK_INITIAL_FLOW; a non-finite p or g: status 0, next = prev, err 0.
+ *   g_L-1 = g / 2^(L-1); then for l = L-1 .. 0, on level l (cols_l columns, rows [r0_l, r1_l) of the view's range):
+ *   1. the template centre p / 2^l is rounded to 1/32 px (tq = floor(32 x + 0.5), base tq >> 5, fraction tq & 31).  A rounded
+ *      centre outside [0, cols_l - 1] x [r0_l, r1_l - 1]: the point is LOST at level 0; above it the level is skipped.
+ *   2. T = the (2 half + 3)^2 integer bilinear samples around it (weights (32 - f) and f, <= 255 * 1024; coordinates clamped
+ *      to the columns and the row range).  Scharr gradients over the (2 half + 1)^2 window:
+ *      gx = 3 (T[i-1][j+1] - T[i-1][j-1]) + 10 (T[i][j+1] - T[i][j-1]) + 3 (T[i+1][j+1] - T[i+1][j-1]), gy transposed;
+ *      A = sum gx^2, B = sum gx gy, C = sum gy^2 in int64 (each < 441 * 2^44 < 2^53).
+ *   3. in double, every sum converted once: det = A C - B B; e = (A + C - sqrt((A - C)(A - C) + 4 B B)) / (N 2^31),
+ *      N = (2 half + 1)^2, the square root correctly rounded -- OpenCV's minimum eigenvalue per pixel in gray levels squared.
+ *      det == 0 or e < min_eig: LOST at level 0, the level is skipped above it (the guess is carried down).
+ *   4. up to max_iter times: the guess is rounded to 1/32 px (gq); a rounded guess outside the level (as in 1., with the NEXT
+ *      image's row range) loses the point at level 0 and ends the level's iteration above it; J = the (2 half + 1)^2 samples
+ *      of the next image around it; d = J - T, b1 = sum d gx, b2 = sum d gy in int64 (< 2^49);
+ *      dx = -32 (C b1 - B b2) / det, dy = -32 (A b2 - B b1) / det; g = gq / 32 + (dx, dy).
+ *      Stop when dx^2 + dy^2 <= eps^2; from the second iteration on also when |dx + previous dx| < 0.01 and the same in y
+ *      (OpenCV's oscillation stop): then g -= (dx, dy) / 2.
+ *   5. l > 0: g_{l-1} = 2 g_l.  l = 0: the guess is rounded once more (outside: LOST), err = sum |J - T| / (1024 N) there,
+ *      next = (float)g, status 1.  A LOST point: status 0, err 0, next = (float) of the guess it was lost with.
+ *   half 2 .. 10, max_iter 1 .. 30, eps >= 0, min_eig >= 0 (OpenCV's default 1e-4), cap <= 4096, levels 1 .. 4; otherwise
+ *   SOSVO_ERR_ARG.  No wrap-around of the panorama's columns.
+ *   back (optional, [nprob, cap, 2] f32) with fb_max > 0: the forward-backward check.  Every point with status 1 is tracked
+ *   back from next_pts (no initial guess) in image next_img[p] to image prev_img[p]; back receives that position (next_pts for
+ *   the points whose status was 0) and the status is cleared where the way back is lost or |back - prev|^2 > fb_max^2
+ *   (differences of the float32 values in double).                                                                      */
+#define SOSVO_LK_INITIAL_FLOW 1
+int32_t sosvo_gray_pyramid_bytes(sosvo_ctx* ctx, int32_t nimg, int32_t rows, int32_t cols, int32_t levels, int64_t* bytes);
+int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
+                           const int32_t* row_range, uint8_t* pyr);
+int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
+                       int32_t levels, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int32_t nprob,
+                       int32_t cap, const float* prev_pts, const int32_t* n, int32_t half, int32_t max_iter, double eps,
+                       double min_eig, int32_t flags, float* next_pts, uint8_t* status, float* err, float* back, double fb_max);
+
 /* ---- K5: ORB keypoint detection per azimuthal mask (a4, feature_detection_method "ORB") ----------
  * Replaces cv2.ORB_create(nfeatures=N).detect(image, mask) (omnistereo/camera_models.py:1640, :1755;
  * pose_est_tools.py:478, :547) for all azimuthal masks of all images at once: 8 levels x 1.2, per-level
@@ -596,6 +649,21 @@ int32_t sosvo_f2f_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const floa
                            const int32_t* order_top, const uint32_t* keys_bot, const int32_t* order_bot,
                            int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam,
                            int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview);
+
+/* The twin of sosvo_f2f_assemble for TRACKED points (sosvo_track_lk in place of the matcher): pair pr tracked the points
+ * m_top / m_bot [.., frame_cap, 2] of (key)frame ref_frame[pr] into its current frame; trk_top, trk_bot [npairs, frame_cap, 2]
+ * f32 are the tracked pixels and st_top, st_bot [npairs, frame_cap] u8 their status, rows k < min(M[ref_frame[pr]], frame_cap).
+ * Output rows [pr*corr_cap ...) in the layout sosvo_ransac_abs_pose reads: top-view correspondences first, then bottom view,
+ * each in POINT order; a point is kept when its status is not 0 and |u_tracked - u_reference| <= f2f_max_hdiff (the gate is
+ * disabled as in sosvo_f2f_assemble).  f = the bearing of the tracked pixel through the pixel-to-bearing code of
+ * sosvo_stereo_assemble for that view (pano_top / pano_bot of the rig), p = the 3-D point X of the reference frame,
+ * cam = 0/1, corr_t = the point's index in the reference frame, corr_q = -1 (the current frame has no keypoint index),
+ * n [npairs] = count (at most corr_cap: the first corr_cap are kept), n_topview [npairs] (optional).                   */
+int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                   const double* X, const int32_t* M, int32_t frame_cap, const int32_t* ref_frame,
+                                   const float* trk_top, const float* trk_bot, const uint8_t* st_top, const uint8_t* st_bot,
+                                   int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam, int32_t* corr_q,
+                                   int32_t* corr_t, int32_t* n, int32_t* n_topview);
 
 /* ---- RGB-D (perspective camera) variant: a12 + a15 glue ----------------------------------------
  * Constants of one RGB-D camera (HOST struct): RGBDCamModel (omnistereo/camera_models.py:756-779) and the

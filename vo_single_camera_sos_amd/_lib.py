@@ -64,6 +64,10 @@ SIGNATURES = {
                                         c_p, c_p]),
     "sosvo_subpix_weights": (c_i32, [c_p, c_i32, c_p]),
     "sosvo_refine_subpix": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_f64, c_p]),
+    "sosvo_gray_pyramid_bytes": (c_i32, [c_p, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_int64)]),
+    "sosvo_gray_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sosvo_track_lk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32,
+                               c_f64, c_f64, c_i32, c_p, c_p, c_p, c_p, c_f64]),
     "sosvo_orb_pyramid_pixels": (ctypes.c_int64, [c_i32, c_i32]),
     "sosvo_orb_mask_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_detect_orb": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
@@ -88,6 +92,7 @@ SIGNATURES = {
                                        c_i32, c_p, c_p]),
     "sosvo_stereo_assemble": (c_i32, [c_p] + [c_p] * 9 + [c_i32] * 4 + [c_p] * 9),
     "sosvo_f2f_assemble": (c_i32, [c_p] + [c_p] * 7 + [c_i32] + [c_p] * 6 + [c_i32, c_i32] + [c_p] * 7),
+    "sosvo_f2f_assemble_tracked": (c_i32, [c_p] + [c_p] * 5 + [c_i32] + [c_p] * 5 + [c_i32, c_i32] + [c_p] * 7),
     "sosvo_ransac_abs_pose": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
                                       c_i32, c_i32, c_u64, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sosvo_ransac_abs_pose_seeds": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
@@ -149,6 +154,8 @@ SUBPIX_HALF_SHIFT = 10             # SOSVO_SUBPIX_HALF(h): bits 10-11, the windo
 SUBPIX_HALF_MASK = 3 << SUBPIX_HALF_SHIFT
 SUBPIX_MAX_ITER = 10               # what the one-call and sequence entry points run the stage with
 SUBPIX_EPS = 0.01
+LK_INITIAL_FLOW = 1                # SOSVO_LK_INITIAL_FLOW: next_pts holds the starting guess on entry
+LK_MAX_HALF, LK_MAX_LEVELS, LK_MAX_ITER, LK_MAX_CAP = 10, 4, 30, 4096
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1
 DETECTOR_FAST = 2
@@ -281,6 +288,51 @@ def subpix_weights(half):
     if rc != 0:
         raise SosvoError("sosvo_subpix_weights(%r) -> %s" % (half, STATUS_NAMES.get(rc, rc)))
     return list(w)[:2 * int(half) + 1]
+
+
+class LKOptions(namedtuple("LKOptions", "half levels max_iter eps min_eig fb_max")):
+    """The settings of the pyramidal Lucas-Kanade tracker (sosvo_track_lk) as one checked value: window half-size 2 .. 10,
+    pyramid levels 1 .. 4, max_iter 1 .. 30, eps >= 0, min_eig >= 0 (OpenCV's minEigThreshold), fb_max None (no
+    forward-backward check) or > 0 pixels.  Defaults: cv2.calcOpticalFlowPyrLK's (21 x 21 window, maxLevel 2 -> 3 levels,
+    TermCriteria(30, 0.01), 1e-4).  A value out of range raises ValueError; nothing is rounded."""
+    __slots__ = ()
+
+    def __new__(cls, half=10, levels=3, max_iter=30, eps=0.01, min_eig=1e-4, fb_max=None):
+        for name, v, lo, hi in (("half", half, 2, LK_MAX_HALF), ("levels", levels, 1, LK_MAX_LEVELS),
+                                ("max_iter", max_iter, 1, LK_MAX_ITER)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
+                raise ValueError("lk %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+        for name, v in (("eps", eps), ("min_eig", min_eig)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
+                raise ValueError("lk %s must be a finite number >= 0, got %r" % (name, v))
+        if fb_max is not None and (isinstance(fb_max, bool) or not isinstance(fb_max, (int, float))
+                                   or not 0.0 < fb_max < float("inf")):
+            raise ValueError("lk fb_max must be None or a finite number > 0 (pixels), got %r" % (fb_max,))
+        return super().__new__(cls, int(half), int(levels), int(max_iter), float(eps), float(min_eig),
+                               None if fb_max is None else float(fb_max))
+
+    @classmethod
+    def of(cls, lk):
+        """An `lk` argument (None: the defaults; an LKOptions; a dict of its fields) -> LKOptions."""
+        if lk is None:
+            return cls()
+        if isinstance(lk, cls):
+            return lk
+        if isinstance(lk, dict):
+            unknown = set(lk) - set(cls._fields)
+            if unknown:
+                raise ValueError("lk: unknown settings %s" % sorted(unknown))
+            return cls(**lk)
+        raise ValueError("lk must be None, an LKOptions or a dict of its fields, got %r" % (lk,))
+
+
+def gray_pyramid_bytes(nimg, rows, cols, levels):
+    """sosvo_gray_pyramid_bytes: bytes of the levels 1 .. levels - 1 of nimg images (host call, no GPU)."""
+    out = ctypes.c_int64(0)
+    rc = load().sosvo_gray_pyramid_bytes(None, int(nimg), int(rows), int(cols), int(levels), ctypes.byref(out))
+    if rc != 0:
+        raise SosvoError("sosvo_gray_pyramid_bytes(%r, %r, %r, %r) -> %s" % (nimg, rows, cols, levels, STATUS_NAMES.get(rc, rc)))
+    return int(out.value)
 
 
 class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2f gated_stereo gated_f2f gated_max_distance "

@@ -290,6 +290,60 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
   if (tid == 0) n[pr] = min(s_running, corr_cap);
 }
 
+// f2f_assemble_kernel for tracked points: the correspondences of pair pr are the reference frame's points whose track
+// succeeded, in point order; the bearing of the tracked pixel is computed here, as stereo_assemble_frame computes its own.
+__global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_kernel(
+    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+    const int32_t* __restrict__ M, int frame_cap, const int32_t* __restrict__ ref_frame, const float* __restrict__ trk_top,
+    const float* __restrict__ trk_bot, const uint8_t* __restrict__ st_top, const uint8_t* __restrict__ st_bot, int corr_cap,
+    double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
+    int32_t* __restrict__ corr_t, int32_t* __restrict__ n, int32_t* __restrict__ n_topview) {
+  SOSVO_LATENCY_BOUND_PRIO();
+  __shared__ int wave_off[kThreads / 64 + 1];
+  __shared__ int s_running;
+  const int tid = threadIdx.x, pr = blockIdx.x;
+  if (tid == 0) s_running = 0;
+  __syncthreads();
+  const int fr_ref = ref_frame[pr];
+  const int nt = min(max(M[fr_ref], 0), frame_cap);
+  const size_t kb = (size_t)pr * frame_cap, rb = (size_t)fr_ref * frame_cap;
+  for (int view = 0; view < 2; ++view) {
+    const float* mm = view == 0 ? m_top : m_bot;
+    const float* trk = view == 0 ? trk_top : trk_bot;
+    const uint8_t* st = view == 0 ? st_top : st_bot;
+    const double* pano = view == 0 ? rig.pano_top : rig.pano_bot;
+    for (int t0 = 0; t0 < nt; t0 += kThreads) {
+      const int t = t0 + tid;
+      bool valid = false;
+      double b[3] = {0.0, 0.0, 0.0};
+      if (t < nt && st[kb + t] != 0) {
+        const double u = (double)trk[2 * (kb + t)], v = (double)trk[2 * (kb + t) + 1];
+        valid = true;
+        if (rig.f2f_max_hdiff >= 0) valid = sv_pixel_gate((double)mm[2 * (rb + t)], 0.0, u, 0.0, -1.0, rig.f2f_max_hdiff);
+        double az, el;
+        sv_pano_angles(u, v, pano, &az, &el);
+        sv_bearing(az, el, b);
+      }
+      const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
+      if (valid && pos < corr_cap) {
+        const size_t o = (size_t)pr * corr_cap + pos;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          f[3 * o + k] = b[k];
+          p[3 * o + k] = X[3 * (rb + t) + k];
+        }
+        cam[o] = view;
+        corr_q[o] = -1;
+        corr_t[o] = t;
+      }
+    }
+    __syncthreads();
+    if (view == 0 && tid == 0 && n_topview) n_topview[pr] = min(s_running, corr_cap);
+  }
+  __syncthreads();
+  if (tid == 0) n[pr] = min(s_running, corr_cap);
+}
+
 }  // namespace
 
 extern "C" {
@@ -421,6 +475,23 @@ int32_t sosvo_f2f_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const floa
   SOSVO_LAUNCH(ctx,f2f_assemble_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X,
                      b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot,
                      corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                   const double* X, const int32_t* M, int32_t frame_cap, const int32_t* ref_frame,
+                                   const float* trk_top, const float* trk_bot, const uint8_t* st_top, const uint8_t* st_bot,
+                                   int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam, int32_t* corr_q,
+                                   int32_t* corr_t, int32_t* n, int32_t* n_topview) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && M && ref_frame && trk_top && trk_bot && st_top && st_bot,
+                "null input pointer");
+  SOSVO_REQUIRE(ctx, f && p && cam && corr_q && corr_t && n, "null output pointer");
+  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
+  if (npairs == 0) return SOSVO_OK;
+  SOSVO_LAUNCH(ctx, f2f_assemble_tracked_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, M,
+               frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }

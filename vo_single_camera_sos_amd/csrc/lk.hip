@@ -1,0 +1,433 @@
+// sosvo_gray_pyramid, sosvo_track_lk -- cv2.calcOpticalFlowPyrLK restated in exact integers: the points
+// of one gray image are tracked into another, coarse to fine over a pyramid of up to four levels.
+//
+// Per point and level: the template T is (2 half + 3)^2 integer bilinear samples on the 1/32-px grid (at most 255 * 1024),
+// its Scharr gradients are integers below 2^22, the normal equations A, B, C and the right-hand sides b1, b2 of every
+// iteration are int64 sums (below 2^53 / 2^49).  Exact integers: the sums do not depend on which lane adds what, and the CPU
+// reference (tests/reflk.py) gets the same bits.  Only the minimum eigenvalue, the 2 x 2 solve and the position arithmetic are
+// floating point -- FP64, every sum converted once, no contraction, a correctly rounded square root -- and every lane of a
+// keypoint's group evaluates them on the same values.
+//
+// MAPPING.  A workgroup is one wave.  A keypoint owns a GROUP of GS lanes: 16 lanes for half 2 .. 5 (25 .. 121 window elements,
+// four keypoints per wave), the whole wave for half 6 .. 10 (169 .. 441 elements).  Lane r of a group owns the window elements
+// r, r + GS, ... for all iterations.  The groups of a wave run in lockstep: loops have wave-uniform bounds and a group that is
+// done is predicated off, so the group reductions (xor shuffles below GS) always see every lane.
+//
+// LDS per group: the template with its one-pixel halo (pitch 2 half + 3, read once per level for the gradients) and three DENSE
+// planes of (2 half + 1)^2 int32 -- the template's window, gx, gy -- that every iteration reads at element index e: lane r of
+// a group reads word base + r + k GS, consecutive lanes consecutive banks.  A group's block is 16 words more than a multiple
+// of 32, so the two 16-lane groups that share a 32-lane half of a ds_read_b32 sit on opposite halves of the 32 banks.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kLkMaxHalf = 10;
+constexpr int kLkMaxLevels = 4;
+constexpr int kPyrTileX = 32, kPyrTileY = 8;  // output pixels of one pyramid workgroup
+
+// ---- the levels of a pyramid set ---------------------------------------------------------------------------------------------
+struct LkLevels {
+  const uint8_t* base[kLkMaxLevels];  // level l as [nimg, rows[l], cols[l]]
+  int32_t rows[kLkMaxLevels], cols[kLkMaxLevels];
+};
+
+// bytes of the levels 1 .. levels - 1 of nimg images (what sosvo_gray_pyramid writes), and their table
+int64_t lk_levels(const uint8_t* gray, const uint8_t* pyr, int nimg, int rows, int cols, int levels, LkLevels* t) {
+  int64_t off = 0;
+  for (int l = 0; l < kLkMaxLevels; ++l) {
+    const bool above = l >= 1 && l < levels;
+    if (t) {
+      t->base[l] = l == 0 ? gray : (above ? pyr + off : nullptr);
+      t->rows[l] = rows;
+      t->cols[l] = cols;
+    }
+    if (above) off += (int64_t)nimg * rows * cols;
+    rows = (rows + 1) / 2;
+    cols = (cols + 1) / 2;
+  }
+  return off;
+}
+
+// The rows [r0, r1) of level `level` that belong to the view's row range (row_range = nullptr: all rows).  Level 0: the range
+// cut to the image and to at least one row; level l + 1: [(r0 + 1) / 2, max((r1 + 1) / 2, that + 1)), cut to the level.
+__device__ __forceinline__ void lk_level_rows(const int32_t* __restrict__ row_range, int view, int rows0, int level, int* r0_out,
+                                              int* r1_out) {
+  int r0 = 0, r1 = rows0;
+  if (row_range) {
+    r0 = clampi(row_range[2 * view], 0, rows0 - 1);
+    r1 = clampi(row_range[2 * view + 1], r0 + 1, rows0);
+  }
+  int rows = rows0;
+  for (int l = 0; l < level; ++l) {
+    rows = (rows + 1) / 2;
+    r0 = min((r0 + 1) / 2, rows - 1);  // (a range that is the last row of an even level: cut to the level, as at level 0)
+    r1 = min(max((r1 + 1) / 2, r0 + 1), rows);
+  }
+  *r0_out = r0;
+  *r1_out = r1;
+}
+
+// ---- one pyramid level: (sum k_i k_j in[clamp(2 y + i)][clamp(2 x + j)] + 128) >> 8, k = (1, 4, 6, 4, 1) --------------------
+__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
+                                                                          uint8_t* __restrict__ out, int rows_out, int cols_out,
+                                                                          const int32_t* __restrict__ row_range, int imgs_per_range,
+                                                                          int rows0, int level_in) {
+  constexpr int TW = 2 * kPyrTileX + 3, TH = 2 * kPyrTileY + 3;
+  __shared__ uint8_t s_in[TH][TW + 1];
+  const int image = blockIdx.z;
+  int ri0, ri1, ro0, ro1;
+  lk_level_rows(row_range, image / imgs_per_range, rows0, level_in, &ri0, &ri1);
+  lk_level_rows(row_range, image / imgs_per_range, rows0, level_in + 1, &ro0, &ro1);
+  ri1 = min(ri1, rows_in);  // (the formula never exceeds the level; belt and braces for the reads)
+  ro1 = min(ro1, rows_out);
+  const int x0 = blockIdx.x * kPyrTileX, y0 = blockIdx.y * kPyrTileY;
+  if (y0 >= ro1 || y0 + kPyrTileY <= ro0) return;  // (uniform) no row of this tile is in the range
+  const uint8_t* src = in + (size_t)image * rows_in * cols_in;
+  const int tid = threadIdx.y * kPyrTileX + threadIdx.x;
+  for (int s = tid; s < TH * TW; s += kPyrTileX * kPyrTileY) {
+    const int i = s / TW, j = s - i * TW;
+    const int y = clampi(2 * y0 - 2 + i, ri0, ri1 - 1), x = clampi(2 * x0 - 2 + j, 0, cols_in - 1);
+    s_in[i][j] = src[(size_t)y * cols_in + x];
+  }
+  __syncthreads();
+  const int x = x0 + threadIdx.x, y = y0 + threadIdx.y;
+  if (x >= cols_out || y < ro0 || y >= ro1) return;
+  const int k[5] = {1, 4, 6, 4, 1};
+  int sum = 128;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    int row = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) row += k[j] * s_in[2 * threadIdx.y + i][2 * threadIdx.x + j];
+    sum += k[i] * row;
+  }
+  out[((size_t)image * rows_out + y) * cols_out + x] = (uint8_t)(sum >> 8);
+}
+
+// ---- the tracker -------------------------------------------------------------------------------------------------------------
+template <int GS>
+__device__ __forceinline__ long long group_sum(long long v) {
+#pragma unroll
+  for (int s = GS / 2; s > 0; s >>= 1) v += __shfl_xor(v, s);
+  return v;
+}
+
+// the integer bilinear sample of a level at pixel (x, y) + (fx, fy) / 32, coordinates clamped to the columns and to the rows
+// [r0, r1) of the level
+__device__ __forceinline__ int lk_sample(const uint8_t* __restrict__ img, int cols, int r0, int r1, int x, int y, int fx, int fy) {
+  const int xa = clampi(x, 0, cols - 1), xb = clampi(x + 1, 0, cols - 1);
+  const int ya = clampi(y, r0, r1 - 1), yb = clampi(y + 1, r0, r1 - 1);
+  const int p00 = img[(size_t)ya * cols + xa], p01 = img[(size_t)ya * cols + xb];
+  const int p10 = img[(size_t)yb * cols + xa], p11 = img[(size_t)yb * cols + xb];
+  return (32 - fy) * ((32 - fx) * p00 + fx * p01) + fy * ((32 - fx) * p10 + fx * p11);
+}
+
+// A position on the 1/32-px grid of a level: tq = floor(32 c + 0.5) per axis; inside = the rounded position lies in
+// [0, cols - 1] x [r0, r1 - 1] (false for NaN); then base and fraction are small integers.
+struct LkGrid {
+  double tqx, tqy;
+  int bx, by, fx, fy;
+  bool inside;
+};
+__device__ __forceinline__ LkGrid lk_grid(double cx, double cy, int cols, int r0, int r1) {
+  LkGrid g;
+  g.tqx = floor(32.0 * cx + 0.5);
+  g.tqy = floor(32.0 * cy + 0.5);
+  g.inside = g.tqx >= 0.0 && g.tqx <= 32.0 * (double)(cols - 1) && g.tqy >= 32.0 * (double)r0 && g.tqy <= 32.0 * (double)(r1 - 1);
+  const int qx = g.inside ? (int)g.tqx : 0, qy = g.inside ? (int)g.tqy : 0;
+  g.bx = qx >> 5;
+  g.fx = qx & 31;
+  g.by = qy >> 5;
+  g.fy = qy & 31;
+  return g;
+}
+
+struct LkArgs {
+  LkLevels lv;
+  int nimg, levels, cap, half, max_iter, initial_flow;
+  double eps2, min_eig, fb_max2;  // fb_max2 < 0: the forward pass
+};
+
+// Words of LDS of one group: the halo'd template, three dense planes, rounded up to 16 more than a multiple of 32.
+__host__ __device__ constexpr int lk_group_words(int half) {
+  const int side3 = 2 * half + 3, side1 = 2 * half + 1;
+  return ((side3 * side3 + 3 * side1 * side1 + 31) / 32) * 32 + 16;
+}
+constexpr int kLkLdsWords16 = 4 * lk_group_words(5), kLkLdsWords64 = lk_group_words(kLkMaxHalf);
+
+// The FORWARD pass (a.fb_max2 < 0) tracks start = prev_pts (guess: next_pts with the initial-flow flag) from image prev_img[p] to
+// image next_img[p] and writes next_pts, status, err.  The BACKWARD pass (a.fb_max2 >= 0) is launched with the images swapped
+// and start = the forward results: points whose status is 1 are tracked back, `out` = back receives the position (the start
+// for the others), and the status is cleared where the point is lost or |back - ref|^2 > fb_max^2 (ref = the forward start).
+template <int GS>
+__global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* __restrict__ row_range, const int32_t* __restrict__ from_img,
+                                                      const int32_t* __restrict__ to_img, const float* __restrict__ start,
+                                                      const int32_t* __restrict__ n, float* __restrict__ out,
+                                                      uint8_t* __restrict__ status, float* __restrict__ err,
+                                                      const float* __restrict__ ref) {
+  constexpr int KPW = 64 / GS;  // keypoints per wave
+  __shared__ int32_t s_lds[GS == 64 ? kLkLdsWords64 : kLkLdsWords16];
+  const int lane = threadIdx.x, grp = lane / GS, r = lane - grp * GS;
+  const int p = blockIdx.x;
+  const int img_a = from_img[p], img_b = to_img[p];
+  if (img_a < 0 || img_a >= a.nimg || img_b < 0 || img_b >= a.nimg) return;  // (uniform) no such image: the problem is ignored
+  const int count = min(__builtin_amdgcn_readfirstlane(n[p]), a.cap);
+  const int half = a.half, side3 = 2 * half + 3, side1 = 2 * half + 1, N = side1 * side1;
+  const bool backward = a.fb_max2 >= 0.0;
+  const int imgs_per_range = a.nimg > 1 ? a.nimg / 2 : 1;
+  const int view_a = row_range ? img_a / imgs_per_range : 0, view_b = row_range ? img_b / imgs_per_range : 0;
+  int32_t* s_T = s_lds + grp * lk_group_words(GS == 64 ? kLkMaxHalf : 5);
+  int32_t* s_Tc = s_T + side3 * side3;
+  int32_t* s_gx = s_Tc + N;
+  int32_t* s_gy = s_gx + N;
+  const double den = (double)N * 2147483648.0;  // 2 N 2^30
+
+  for (int k0 = blockIdx.y * KPW; k0 < count; k0 += gridDim.y * KPW) {  // (uniform)
+    const int k = k0 + grp;
+    const size_t row = (size_t)p * a.cap + min(k, count - 1);
+    const float sx = start[2 * row], sy = start[2 * row + 1];
+    float gx0 = sx, gy0 = sy;
+    if (a.initial_flow) {
+      gx0 = out[2 * row];
+      gy0 = out[2 * row + 1];
+    }
+    // `live`: this group tracks a point.  `lost` is final once set.
+    bool live = k < count && isfinite(sx) && isfinite(sy) && isfinite(gx0) && isfinite(gy0);
+    if (backward) live = live && status[row] != 0;
+    const bool skipped = k < count && !live;  // not tracked: the result is the start
+    bool lost = false;
+    const double px = (double)sx, py = (double)sy;
+    const double top = 1.0 / (double)(1 << (a.levels - 1));
+    double cx = (double)gx0 * top, cy = (double)gy0 * top;  // the guess at the current level
+    long long err_sum = 0;
+
+    for (int l = a.levels - 1; l >= 0; --l) {  // (uniform)
+      const int cols = a.lv.cols[l], rows = a.lv.rows[l];
+      int ra0, ra1, rb0, rb1;
+      lk_level_rows(row_range, view_a, a.lv.rows[0], l, &ra0, &ra1);
+      lk_level_rows(row_range, view_b, a.lv.rows[0], l, &rb0, &rb1);
+      ra1 = min(ra1, rows);
+      rb1 = min(rb1, rows);
+      const uint8_t* ia = a.lv.base[l] + (size_t)img_a * rows * cols;
+      const uint8_t* ib = a.lv.base[l] + (size_t)img_b * rows * cols;
+      const double scale = 1.0 / (double)(1 << l);
+      const LkGrid t = lk_grid(px * scale, py * scale, cols, ra0, ra1);
+      bool run = live && !lost && t.inside;  // this group iterates at this level
+      if (live && !lost && !t.inside && l == 0) lost = true;
+      // ---- the template and its gradients
+      if (run) {
+        for (int s = r; s < side3 * side3; s += GS) {
+          const int i = s / side3, j = s - i * side3;
+          s_T[s] = lk_sample(ia, cols, ra0, ra1, t.bx + j - half - 1, t.by + i - half - 1, t.fx, t.fy);
+        }
+      }
+      __syncthreads();
+      long long sa = 0, sb = 0, sc = 0;
+      if (run) {
+        for (int e = r; e < N; e += GS) {
+          const int i = e / side1, j = e - i * side1;
+          const int32_t* q = s_T + i * side3 + j;  // q[0] = T[i][j] of the halo'd template, the window element is q[side3 + 1]
+          const int t00 = q[0], t01 = q[1], t02 = q[2];
+          const int t10 = q[side3], t12 = q[side3 + 2];
+          const int t20 = q[2 * side3], t21 = q[2 * side3 + 1], t22 = q[2 * side3 + 2];
+          const int gx = 3 * (t02 - t00) + 10 * (t12 - t10) + 3 * (t22 - t20);
+          const int gy = 3 * (t20 - t00) + 10 * (t21 - t01) + 3 * (t22 - t02);
+          s_Tc[e] = q[side3 + 1];
+          s_gx[e] = gx;
+          s_gy[e] = gy;
+          sa += (long long)gx * gx;
+          sb += (long long)gx * gy;
+          sc += (long long)gy * gy;
+        }
+      }
+      const double A = (double)group_sum<GS>(sa), B = (double)group_sum<GS>(sb), C = (double)group_sum<GS>(sc);
+      const double det = A * C - B * B;
+      const double diff = A - C;
+      const double eig = (A + C - __dsqrt_rn(diff * diff + 4.0 * B * B)) / den;
+      if (run && (det == 0.0 || eig < a.min_eig)) {  // no texture: the point is lost at level 0, the level is skipped above it
+        run = false;
+        if (l == 0) lost = true;
+      }
+      // ---- the iteration
+      double pdx = 0.0, pdy = 0.0;
+      bool iterating = run;
+      for (int it = 0; it < a.max_iter; ++it) {  // (uniform bound; left when no group of the wave iterates)
+        if (!__any(iterating)) break;
+        const LkGrid g = lk_grid(cx, cy, cols, rb0, rb1);
+        if (iterating && !g.inside) {  // left the image: lost at level 0, the end of this level above it
+          iterating = false;
+          if (l == 0) lost = true;
+        }
+        long long s1 = 0, s2 = 0;
+        if (iterating) {
+          for (int e = r; e < N; e += GS) {
+            const int i = e / side1, j = e - i * side1;
+            const long long d = lk_sample(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
+            s1 += d * s_gx[e];
+            s2 += d * s_gy[e];
+          }
+        }
+        const double b1 = (double)group_sum<GS>(s1), b2 = (double)group_sum<GS>(s2);
+        if (iterating) {
+          const double dx = -32.0 * (C * b1 - B * b2) / det, dy = -32.0 * (A * b2 - B * b1) / det;
+          cx = g.tqx * 0.03125 + dx;
+          cy = g.tqy * 0.03125 + dy;
+          if (dx * dx + dy * dy <= a.eps2) {
+            iterating = false;
+          } else if (it > 0 && fabs(dx + pdx) < 0.01 && fabs(dy + pdy) < 0.01) {  // oscillation: half the step back
+            cx -= dx * 0.5;
+            cy -= dy * 0.5;
+            iterating = false;
+          } else if (floor(32.0 * cx + 0.5) == g.tqx && floor(32.0 * cy + 0.5) == g.tqy) {
+            // The new guess rounds to the position this step was taken from: the next iteration would sample the same J and
+            // take the same step, and so would every one after it.  (The step is measured from the ROUNDED guess, so at the
+            // fixed point it is the solution's distance to the grid, up to 1/64 px: the eps stop fires only within eps of a grid
+            // point.)  What those iterations would do is known now: the oscillation rule at the next one, if there is one,
+            // sees 2 dx and 2 dy; otherwise nothing changes up to max_iter.  Same bits, without running them.
+            if (it + 1 < a.max_iter && fabs(dx + dx) < 0.01 && fabs(dy + dy) < 0.01) {
+              cx -= dx * 0.5;
+              cy -= dy * 0.5;
+            }
+            iterating = false;
+          }
+          pdx = dx;
+          pdy = dy;
+        }
+      }
+      if (l > 0) {
+        cx *= 2.0;
+        cy *= 2.0;
+      } else {
+        // ---- the residual at the final rounded position
+        const LkGrid g = lk_grid(cx, cy, cols, rb0, rb1);
+        const bool ok = live && !lost && g.inside;
+        if (live && !lost && !g.inside) lost = true;
+        long long s = 0;
+        if (ok) {
+          for (int e = r; e < N; e += GS) {
+            const int i = e / side1, j = e - i * side1;
+            const int d = lk_sample(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
+            s += d < 0 ? -d : d;
+          }
+        }
+        err_sum = group_sum<GS>(s);
+      }
+      __syncthreads();  // (the next level / keypoint writes the template)
+    }
+
+    if (r == 0 && k < count) {
+      const size_t o = (size_t)p * a.cap + k;
+      if (skipped) {
+        out[2 * o] = sx;
+        out[2 * o + 1] = sy;
+        if (!backward) {
+          status[o] = 0;
+          err[o] = 0.0f;
+        }
+      } else {
+        const float ox = (float)cx, oy = (float)cy;
+        out[2 * o] = ox;
+        out[2 * o + 1] = oy;
+        if (!backward) {
+          status[o] = lost ? 0 : 1;
+          err[o] = lost ? 0.0f : (float)((double)err_sum / (1024.0 * (double)N));
+        } else {
+          const double ddx = (double)ox - (double)ref[2 * o], ddy = (double)oy - (double)ref[2 * o + 1];
+          if (lost || !(ddx * ddx + ddy * ddy <= a.fb_max2)) status[o] = 0;
+        }
+      }
+    }
+  }
+}
+
+bool lk_sizes_ok(int64_t nimg, int64_t rows, int64_t cols, int64_t levels) {
+  return nimg >= 0 && nimg <= 65535 && rows >= 1 && cols >= 1 && rows <= 16384 && cols <= 16384 && levels >= 1 &&
+         levels <= kLkMaxLevels && nimg * rows * cols < ((int64_t)1 << 40);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t sosvo_gray_pyramid_bytes(sosvo_ctx* ctx, int32_t nimg, int32_t rows, int32_t cols, int32_t levels, int64_t* bytes) {
+  if (!bytes) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, "null pointer");
+  if (!lk_sizes_ok(nimg, rows, cols, levels)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, "sizes out of range (levels 1..4)");
+  *bytes = lk_levels(nullptr, nullptr, nimg, rows, cols, levels, nullptr);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
+                           const int32_t* row_range, uint8_t* pyr) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray, "null pointer");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
+  SOSVO_REQUIRE(ctx, pyr || levels == 1, "null pointer");
+  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
+  if (nimg == 0) return SOSVO_OK;
+  LkLevels t;
+  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
+  for (int l = 0; l + 1 < levels; ++l) {
+    const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), nimg);
+    SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                 const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, rows, l);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return SOSVO_OK;
+}
+
+int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
+                       int32_t levels, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int32_t nprob,
+                       int32_t cap, const float* prev_pts, const int32_t* n, int32_t half, int32_t max_iter, double eps,
+                       double min_eig, int32_t flags, float* next_pts, uint8_t* status, float* err, float* back, double fb_max) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray && prev_img && next_img && prev_pts && n && next_pts && status && err, "null pointer");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
+  SOSVO_REQUIRE(ctx, pyr || levels == 1, "null pointer (the levels above 0)");
+  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
+  SOSVO_REQUIRE(ctx, cap > 0 && cap <= 4096, "cap out of range");
+  SOSVO_REQUIRE(ctx, half >= 2 && half <= kLkMaxHalf, "half out of range (2..10)");
+  SOSVO_REQUIRE(ctx, max_iter >= 1 && max_iter <= 30, "max_iter out of range (1..30)");
+  SOSVO_REQUIRE(ctx, eps >= 0.0 && min_eig >= 0.0, "eps / min_eig must not be negative or NaN");
+  SOSVO_REQUIRE(ctx, (flags & ~SOSVO_LK_INITIAL_FLOW) == 0, "unknown flag");
+  SOSVO_REQUIRE(ctx, back == nullptr || fb_max > 0.0, "fb_max must be positive with a back buffer");
+  if (nprob == 0 || nimg == 0) return SOSVO_OK;
+  LkArgs a;
+  lk_levels(gray, pyr, nimg, rows, cols, levels, &a.lv);
+  a.nimg = nimg;
+  a.levels = levels;
+  a.cap = cap;
+  a.half = half;
+  a.max_iter = max_iter;
+  a.initial_flow = (flags & SOSVO_LK_INITIAL_FLOW) ? 1 : 0;
+  a.eps2 = eps * eps;
+  a.min_eig = min_eig;
+  a.fb_max2 = -1.0;
+  const bool small = half <= 5;
+  const int kpw = small ? 4 : 1;
+  // waves per problem: enough for the chip at a few problems, several rounds per wave at thousands
+  const dim3 grid(nprob, min(cdiv(cap, kpw), nprob >= 4096 ? 16 : 64));
+  if (small)
+    SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
+                 status, err, (const float*)nullptr);
+  else
+    SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
+                 status, err, (const float*)nullptr);
+  SOSVO_LAUNCH_CHECK(ctx);
+  if (back) {  // the forward results tracked back: images swapped, no initial guess
+    a.initial_flow = 0;
+    a.fb_max2 = fb_max * fb_max;
+    if (small)
+      SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
+                   (float*)nullptr, prev_pts);
+    else
+      SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
+                   (float*)nullptr, prev_pts);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return SOSVO_OK;
+}
+
+}  // extern "C"

@@ -48,6 +48,26 @@ def make_rig(pano_top, pano_bot, F_top, F_bot, min_range, max_range, stereo_min_
     return r
 
 
+class GrayPyramid(object):
+    """What Context.gray_pyramid returns and Context.track_lk reads: `gray` [NI,rows,cols] u8 (level 0, the caller's tensor),
+    `upper` (the levels 1 .. levels - 1 back to back, flat u8), `levels`, and the `row_range` the levels were built under."""
+
+    def __init__(self, gray, upper, levels, row_range):
+        self.gray, self.upper, self.levels, self.row_range = gray, upper, levels, row_range
+
+    def level(self, l):
+        """Level l as a [NI, rows_l, cols_l] view."""
+        NI, rows, cols = self.gray.shape
+        if l == 0:
+            return self.gray
+        off = 0
+        for k in range(1, l + 1):
+            rows, cols = (rows + 1) // 2, (cols + 1) // 2
+            if k < l:
+                off += NI * rows * cols
+        return self.upper[off:off + NI * rows * cols].view(NI, rows, cols)
+
+
 class Context(object):
     """One sosvo_ctx bound to (device, stream).  Not shared between host threads."""
 
@@ -309,6 +329,94 @@ class Context(object):
         self._call(self._lib.sosvo_refine_subpix, _ptr(gray), NI, rows, cols, int(nmask), kp.shape[1], _ptr(kp), _ptr(n),
                    int(half), int(max_iter), float(eps), _ptr(row_range))
         return kp
+
+    # ---- pyramidal Lucas-Kanade tracking --------------------------------------------------
+    def gray_pyramid(self, gray, levels, row_range=None, out=None):
+        """sosvo_gray_pyramid: the levels 1 .. levels - 1 of gray [NI,rows,cols] u8 (level 0 is `gray` itself, not copied) ->
+        a GrayPyramid, what track_lk reads.  row_range (int32 [2,2] on the device, view-major) as for refine_subpix: only the
+        rows a level inherits from it are computed.  out: a GrayPyramid of the same sizes to refill (no allocation)."""
+        _check(gray, torch.uint8, "gray", ndim=3)
+        NI, rows, cols = gray.shape
+        nbytes = _lib.gray_pyramid_bytes(NI, rows, cols, levels)     # (SosvoError for sizes / levels out of range)
+        if row_range is not None:
+            _check(row_range, torch.int32, "row_range", (2, 2))
+        upper = out.upper if out is not None else torch.zeros((nbytes,), dtype=torch.uint8, device=gray.device)
+        _check(upper, torch.uint8, "out.upper", (nbytes,))
+        self._call(self._lib.sosvo_gray_pyramid, _ptr(gray), NI, rows, cols, int(levels), _ptr(row_range),
+                   _ptr(upper) if nbytes else NULL)
+        return GrayPyramid(gray, upper, int(levels), row_range)
+
+    def track_lk(self, pyr, prev_img, next_img, prev_pts, n, half=10, max_iter=30, eps=0.01, min_eig=1e-4, next_pts=None,
+                 fb_max=None, out=None):
+        """sosvo_track_lk: problem p tracks prev_pts[p, :n[p]] ([NP,cap,2] f32) from image prev_img[p] to image next_img[p]
+        ([NP] i32 on the device) of the GrayPyramid `pyr` -> (next_pts [NP,cap,2] f32, status [NP,cap] u8, err [NP,cap] f32).
+        next_pts: given = the starting guesses (SOSVO_LK_INITIAL_FLOW), overwritten with the results.  fb_max: None, or the
+        forward-backward check's bound in pixels; then the 4-tuple (next_pts, status, err, back).  out: buffers to reuse, in
+        the order of the result (out[0] is not read when next_pts is given); rows at and beyond n[p] of every output are
+        untouched."""
+        if not isinstance(pyr, GrayPyramid):
+            raise SosvoError("pyr: expected the result of gray_pyramid")
+        NI, rows, cols = pyr.gray.shape
+        _check(prev_pts, torch.float32, "prev_pts", (None, None, 2))
+        NP, cap = prev_pts.shape[:2]
+        _check(prev_img, torch.int32, "prev_img", (NP,))
+        _check(next_img, torch.int32, "next_img", (NP,))
+        _check(n, torch.int32, "n", (NP,))
+        flags = 0
+        if next_pts is not None:
+            flags = _lib.LK_INITIAL_FLOW
+        else:
+            next_pts = out[0] if out is not None else torch.zeros_like(prev_pts)
+        _check(next_pts, torch.float32, "next_pts", (NP, cap, 2))
+        dev = prev_pts.device
+        status = out[1] if out is not None else torch.zeros((NP, cap), dtype=torch.uint8, device=dev)
+        err = out[2] if out is not None else torch.zeros((NP, cap), dtype=torch.float32, device=dev)
+        _check(status, torch.uint8, "status", (NP, cap))
+        _check(err, torch.float32, "err", (NP, cap))
+        back = None
+        if fb_max is not None:
+            back = out[3] if out is not None and len(out) > 3 else torch.zeros_like(prev_pts)
+            _check(back, torch.float32, "back", (NP, cap, 2))
+        self._call(self._lib.sosvo_track_lk, _ptr(pyr.gray), _ptr(pyr.upper) if pyr.upper.numel() else NULL, NI, rows, cols,
+                   pyr.levels, _ptr(pyr.row_range), _ptr(prev_img), _ptr(next_img), NP, cap, _ptr(prev_pts), _ptr(n), int(half),
+                   int(max_iter), float(eps), float(min_eig), flags, _ptr(next_pts), _ptr(status), _ptr(err), _ptr(back),
+                   0.0 if fb_max is None else float(fb_max))
+        return (next_pts, status, err) if fb_max is None else (next_pts, status, err, back)
+
+    def f2f_assemble_tracked(self, rig, frames, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, out=None):
+        """sosvo_f2f_assemble_tracked: frames = dict from stereo_assemble (m_top, m_bot, X, M); ref_frame [NP] i32; trk_*
+        [NP, frame_cap, 2] f32 and st_* [NP, frame_cap] u8 from track_lk -> the dict of f2f_assemble (q = -1)."""
+        F, frame_cap = frames["m_top"].shape[0], frames["m_top"].shape[1]
+        NP = ref_frame.shape[0]
+        _check(ref_frame, torch.int32, "ref_frame", (NP,))
+        _check(frames["m_top"], torch.float32, "m_top", (F, frame_cap, 2))
+        _check(frames["m_bot"], torch.float32, "m_bot", (F, frame_cap, 2))
+        _check(frames["X"], torch.float64, "X", (F, frame_cap, 3))
+        _check(frames["M"], torch.int32, "M", (F,))
+        for name, t in (("trk_top", trk_top), ("trk_bot", trk_bot)):
+            _check(t, torch.float32, name, (NP, frame_cap, 2))
+        for name, t in (("st_top", st_top), ("st_bot", st_bot)):
+            _check(t, torch.uint8, name, (NP, frame_cap))
+        dev = ref_frame.device
+        if out is None:
+            out = dict(f=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
+                       p=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
+                       cam=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
+                       q=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
+                       t=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
+                       n=torch.zeros((NP,), dtype=torch.int32, device=dev),
+                       n_top=torch.zeros((NP,), dtype=torch.int32, device=dev))
+        _check(out["f"], torch.float64, "f", (NP, corr_cap, 3))
+        _check(out["p"], torch.float64, "p", (NP, corr_cap, 3))
+        for k in ("cam", "q", "t"):
+            _check(out[k], torch.int32, k, (NP, corr_cap))
+        _check(out["n"], torch.int32, "n", (NP,))
+        _check(out["n_top"], torch.int32, "n_top", (NP,))
+        self._call(self._lib.sosvo_f2f_assemble_tracked, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
+                   _ptr(frames["m_bot"]), _ptr(frames["X"]), _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(trk_top),
+                   _ptr(trk_bot), _ptr(st_top), _ptr(st_bot), NP, corr_cap, _ptr(out["f"]), _ptr(out["p"]), _ptr(out["cam"]),
+                   _ptr(out["q"]), _ptr(out["t"]), _ptr(out["n"]), _ptr(out["n_top"]))
+        return out
 
     # ---- K5 / K6' ----------------------------------------------------------------------
     def orb_pyramid_pixels(self, rows, cols):

@@ -60,3 +60,41 @@ def filter_pixel_correspondences(matched_points_top, matched_points_bot, min_rec
         validation_min_disparity = matched_points_top[..., 1] - matched_points_bot[..., 1] >= min_rectified_disparity
         return np.logical_and(validation_hor_diff, validation_min_disparity)
     return validation_hor_diff
+
+
+def calc_optical_flow_pyr_lk(prev_gray, next_gray, prev_pts, next_pts=None, win_half=10, max_level=2, max_iter=30, eps=0.01,
+                             min_eig_threshold=1e-4, ctx=None):
+    """cv2.calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(2 win_half + 1,) * 2, maxLevel=max_level,
+    criteria=(COUNT + EPS, max_iter, eps), minEigThreshold=min_eig_threshold), the call the reference carries commented out
+    at camera_models.py:3070, with cv2's shapes and the arithmetic on the GPU (Context.gray_pyramid + Context.track_lk: the
+    integer restatement of include/sosvo.h, replicated borders).  prev_gray, next_gray: [rows, cols] u8 of one size;
+    prev_pts: [N, 1, 2] or [N, 2] float32; next_pts: the starting guesses (OPTFLOW_USE_INITIAL_FLOW) or None
+    -> (next_pts [N, 1, 2] float32, status [N, 1] uint8, err [N, 1] float32).  More than 4096 points go in chunks."""
+    import torch
+    from .. import _lib
+    from ..runtime import default_context
+    c = default_context() if ctx is None else ctx
+    prev_gray, next_gray = np.ascontiguousarray(prev_gray), np.ascontiguousarray(next_gray)
+    if prev_gray.dtype != np.uint8 or prev_gray.ndim != 2 or next_gray.dtype != np.uint8 or next_gray.shape != prev_gray.shape:
+        raise ValueError("prev_gray / next_gray: two uint8 images [rows, cols] of one size")
+    pts = np.ascontiguousarray(prev_pts, dtype=np.float32).reshape(-1, 2)
+    guess = None if next_pts is None else np.ascontiguousarray(next_pts, dtype=np.float32).reshape(-1, 2)
+    if guess is not None and guess.shape != pts.shape:
+        raise ValueError("next_pts: one starting guess per point")
+    opts = _lib.LKOptions(half=win_half, levels=max_level + 1 if isinstance(max_level, int) else max_level,
+                          max_iter=max_iter, eps=eps, min_eig=min_eig_threshold)
+    N = len(pts)
+    out = (np.zeros((N, 1, 2), np.float32), np.zeros((N, 1), np.uint8), np.zeros((N, 1), np.float32))
+    if N == 0:
+        return out
+    dev = c.device
+    pyr = c.gray_pyramid(torch.from_numpy(np.stack([prev_gray, next_gray])).to(dev), opts.levels)
+    img0, img1 = torch.zeros((1,), dtype=torch.int32, device=dev), torch.ones((1,), dtype=torch.int32, device=dev)
+    for lo in range(0, N, _lib.LK_MAX_CAP):
+        hi = min(N, lo + _lib.LK_MAX_CAP)
+        n = torch.full((1,), hi - lo, dtype=torch.int32, device=dev)
+        g = None if guess is None else torch.from_numpy(guess[lo:hi]).to(dev).reshape(1, hi - lo, 2).contiguous()
+        nx, st, er = c.track_lk(pyr, img0, img1, torch.from_numpy(pts[lo:hi]).to(dev).reshape(1, hi - lo, 2).contiguous(), n,
+                                half=opts.half, max_iter=opts.max_iter, eps=opts.eps, min_eig=opts.min_eig, next_pts=g)
+        out[0][lo:hi, 0], out[1][lo:hi, 0], out[2][lo:hi, 0] = nx[0].cpu().numpy(), st[0].cpu().numpy(), er[0].cpu().numpy()
+    return out

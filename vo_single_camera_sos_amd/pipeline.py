@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import MatchOptions, subpix_flags, subpix_half
+from ._lib import LKOptions, MatchOptions, subpix_flags, subpix_half
 from .device import Context, make_rig
 
 
@@ -35,7 +35,7 @@ class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
                  adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
@@ -48,8 +48,19 @@ class FramePairPipeline(object):
         ratio_stereo / ratio_f2f: Lowe's ratio rule fused into that matcher's search (Context.match_hamming_ratio), plain or
         under the gate; ratio: a float in (0, 1) with ratio * 64 an integer (0.75 = the reference's, camera_models.py:423).
         subpix: None = the front end's own setting, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement,
-        handed on to the front end (ImageFrontEnd's subpix)."""
+        handed on to the front end (ImageFrontEnd's subpix).
+        f2f_tracker: "match" = the frame-to-frame correspondences come from the descriptor matcher (the reference's way);
+        "lk" = the reference frames' stereo points are tracked into the current frames' gray panoramas by pyramidal
+        Lucas-Kanade (Context.track_lk; cv2.calcOpticalFlowPyrLK, camera_models.py:3070) -- needs a front end.  lk: its
+        settings, None / an LKOptions / a dict of its fields (half, levels, max_iter, eps, min_eig, fb_max)."""
         assert isinstance(ctx, Context)
+        if f2f_tracker not in ("match", "lk"):
+            raise ValueError("f2f_tracker: \"match\" or \"lk\", got %r" % (f2f_tracker,))
+        if f2f_tracker == "lk" and front_end is None:
+            raise ValueError("f2f_tracker=\"lk\" needs a front end: the tracker reads the gray panoramas")
+        if f2f_tracker != "lk" and lk is not None:
+            raise ValueError("lk settings without f2f_tracker=\"lk\"")
+        self.f2f_tracker, self.lk = f2f_tracker, LKOptions.of(lk) if f2f_tracker == "lk" else None
         if subpix is not None:
             if front_end is None:
                 raise ValueError("subpix needs a front end: the refinement reads the gray panoramas")
@@ -123,6 +134,14 @@ class FramePairPipeline(object):
         self.lm_cost, self.lm_iters = z((self.B,), torch.float64), z((self.B,), torch.int32)
         self.cam_off = torch.from_numpy(np.stack([rig.F_top, rig.F_bot])).to(dev)
         self.cam_rot = torch.from_numpy(np.stack([np.eye(3), np.eye(3)])).to(dev)
+        if self.lk is not None:    # the tracker's buffers: 2B problems (top views, then bottom views), frame_cap points each
+            self._lk_pyr = None
+            self._lk_prev = z((2 * self.B, Fc, 2), torch.float32)
+            self._lk_n = z((2 * self.B,), torch.int32)
+            self._lk_out = (z((2 * self.B, Fc, 2), torch.float32), z((2 * self.B, Fc), torch.uint8),
+                            z((2 * self.B, Fc), torch.float32)) + \
+                ((z((2 * self.B, Fc, 2), torch.float32),) if self.lk.fb_max is not None else ())
+            self._lk_ref = self._t2.to(torch.int64)
 
     # ---- inputs ------------------------------------------------------------------------------
     def load_keypoints(self, packed):
@@ -140,8 +159,26 @@ class FramePairPipeline(object):
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
                           self.s_keys, self.s_order, self.F, self.NM, self.frame_cap, out=self.frames)
 
+    def _track_lk(self):
+        """The frame-to-frame correspondences by tracking: pyramids of the front end's gray panoramas, the reference frames'
+        m_top / m_bot tracked into the current frames' images as ONE launch of 2B problems, the tracked assemble."""
+        c, fe, o = self.ctx, self.front_end, self.lk
+        self._M2[1].copy_(self._M2[0])
+        rr = None if fe.keep_panoramas else fe.gray_rows
+        self._lk_pyr = c.gray_pyramid(fe.gray, o.levels, row_range=rr, out=self._lk_pyr)
+        torch.index_select(self._m2.view(2 * self.F, self.frame_cap, 2), 0, self._lk_ref, out=self._lk_prev)
+        torch.index_select(self._M2.view(2 * self.F), 0, self._lk_ref, out=self._lk_n)
+        res = c.track_lk(self._lk_pyr, self._t2, self._q2, self._lk_prev, self._lk_n, half=o.half, max_iter=o.max_iter,
+                         eps=o.eps, min_eig=o.min_eig, fb_max=o.fb_max, out=self._lk_out)
+        nxt, st = res[0], res[1]
+        c.f2f_assemble_tracked(self.rig, self.frames, self.ref_frame, nxt[: self.B], nxt[self.B:], st[: self.B], st[self.B:],
+                               self.corr_cap, out=self.corr)
+
     def track(self):
         c, fr = self.ctx, self.frames
+        if self.lk is not None:
+            self._track_lk()
+            return self._solve()
         self._M2[1].copy_(self._M2[0])                      # the bottom view's blocks have the same counts
         d2, M2 = self._d2.view(2 * self.F, self.frame_cap, 32), self._M2.view(2 * self.F)
         m2 = self._m2.view(2 * self.F, self.frame_cap, 2)
@@ -149,7 +186,10 @@ class FramePairPipeline(object):
         c.sort_matches(self._k2, M2, order=self._o2, q_slot=self._q2)
         c.f2f_assemble(self.rig, fr, self.ref_frame, self.cur_frame, self.k_top, self.o_top, self.k_bot, self.o_bot,
                        self.corr_cap, out=self.corr)
-        co = self.corr
+        self._solve()
+
+    def _solve(self):
+        c, co = self.ctx, self.corr
         c.ransac_abs_pose(co["f"], co["p"], co["n"], self.thr, self.max_iter, seed=self.seed, adaptive=self.adaptive,
                           cam=co["cam"], cam_off=self.cam_off, cam_rot=self.cam_rot, cam_rot_identity=True,
                           out=self.ransac, gp3p=self.gp3p)
