@@ -20,8 +20,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def main_rgbd_vo(argv=None):
-    from vo_single_camera_sos_amd.omnistereo.common_tools import get_poses_from_file, make_sure_path_exists, str2bool
+def build_parser():
+    from vo_single_camera_sos_amd.omnistereo.common_tools import add_f2f_tracker_arguments, str2bool
     parser = ArgumentParser(description="Demo of frame-to-frame visual odometry for RGB-D images.")
     parser.register("type", "bool", str2bool)
     parser.add_argument("sequence_path", nargs="+", help="The path to the sequence where the rgbd folder is located (several "
@@ -57,6 +57,13 @@ def main_rgbd_vo(argv=None):
                              "static-stereo matching; default: off (an RGB-D camera reads depth at integer pixels: refused)")
     parser.add_argument("--subpix_half", default=None, type=int,
                         help="with --subpix_refine: the window half-size 2 .. 5; default: 5")
+    add_f2f_tracker_arguments(parser)
+    return parser
+
+
+def main_rgbd_vo(argv=None):
+    from vo_single_camera_sos_amd.omnistereo.common_tools import f2f_tracker_arguments, get_poses_from_file, make_sure_path_exists
+    parser = build_parser()
     args = parser.parse_args(argv)
 
     from vo_single_camera_sos_amd.omnistereo.camera_models import RGBDCamModel
@@ -97,7 +104,7 @@ def main_rgbd_vo(argv=None):
                              detection_method=args.detection_method, cross_check=True if args.cross_check else None,
                              gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
                              ratio_test=True if args.ratio_test else None, ratio=args.ratio,
-                             subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half,
+                             subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half, **f2f_tracker_arguments(args),
                              lanes=None if args.lanes < 0 else args.lanes)
         print("GOODBYE!")
         return out
@@ -111,7 +118,7 @@ def main_rgbd_vo(argv=None):
                     detection_method=args.detection_method, cross_check=True if args.cross_check else None,
                     gated_matching=True if args.gated_matching else None, gated_max_distance=args.gated_max_distance,
                     ratio_test=True if args.ratio_test else None, ratio=args.ratio,
-                    subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half)
+                    subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half, **f2f_tracker_arguments(args))
     print("GOODBYE!")
     return out
 

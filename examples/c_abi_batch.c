@@ -88,6 +88,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "sosvo_create failed\n");
     return 3;
   }
+  if (cfg.ransac_flags & SOSVO_FLAG_LK_F2F) { /* Lucas-Kanade tracking in place of the frame-to-frame matcher: the flag is in the
+                                                 configuration, the tracker's settings belong to the context */
+    const sosvo_lk_options lk = {4, 3, 30, 0, 0.01, 1e-4, 0.5}; /* 9 x 9 window, 3 levels, forward-backward check at 0.5 px */
+    CHECK_SOSVO(sosvo_set_lk_options(ctx, &lk));
+  }
   uint32_t* table = NULL;
   void* workspace = NULL;
   double* results = NULL;

@@ -773,6 +773,38 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
  * The bits never reach the RANSAC flags; the struct layouts and, with the switch clear, workspace sizes, launches and
  * results are unchanged -- the stage needs no workspace. */
 #define SOSVO_FLAG_SUBPIX 0x40
+/* ---- Lucas-Kanade tracking in the batch and sequence entry points (sosvo_track_lk in place of the frame-to-frame matcher) ----
+ *   SOSVO_FLAG_LK_F2F        the tracking step follows the reference frame's stereo points m_top / m_bot into the current
+ *                            frame's gray panoramas (one sosvo_track_lk launch of 2 B problems, top views first) and stacks
+ *                            them with sosvo_f2f_assemble_tracked; the two match / sort pairs and sosvo_f2f_assemble do not
+ *                            run.  RANSAC, the refinement and the [B, 16] records follow as always.
+ * Honoured in sosvo_batch_cfg.ransac_flags; in sosvo_rgbd_batch_cfg.flags it is SOSVO_ERR_ARG (and a workspace size of 0).
+ * Together with SOSVO_FLAG_CROSS_CHECK_F2F, SOSVO_FLAG_GATED_F2F or SOSVO_FLAG_RATIO_F2F it is SOSVO_ERR_ARG (size 0) as well:
+ * they act on a matcher that no longer runs.  The ..._STEREO bits and SOSVO_FLAG_SUBPIX combine freely with it.  The bit never
+ * reaches the RANSAC flags; the struct layouts and, with the bit clear, workspace sizes, launches and results are unchanged.
+ *
+ * The tracker's six settings do not fit the flags: they belong to the CONTEXT (sosvo_set_lk_options).  A new context has the
+ * defaults SOSVO_LK_OPTIONS_DEFAULT: half 10, levels 3, max_iter 30, eps 0.01, min_eig 1e-4, no check.  fb_max <= 0: no
+ * forward-backward check.  The ranges are sosvo_track_lk's (and finite values); a refused call -- a value out of range, or a
+ * NULL pointer, as everywhere in this ABI -- is SOSVO_ERR_ARG and leaves the previous settings.
+ * Unlike the hints they change results: sosvo_frame_pair_batch_streams* hands them to its internal contexts at every call.
+ *
+ * With the bit set the frame store also keeps every frame's gray panoramas and their pyramid: level l as
+ * [2 * slots, rows_l, cols_l] u8, view-major (image v * slots + s is view v of slot s), for l = 0 .. SOSVO_LK_MAX_LEVELS - 1
+ * whatever the settings (the workspace functions take no context); slots <= 32767 then.  The front end fills the levels the
+ * context's settings use, in the rows of the range it computed (all rows unless GFT runs with the fused median); each level
+ * equals sosvo_gray_pyramid of that frame's gray under the same range.  In a pair batch level 0 IS the front end's gray buffer.
+ * sosvo_sequence_copy_slot[s] moves a slot's images with its record.  Raise `levels` only between sequences: a tracking call
+ * reads the levels the settings name, a front end or copy has written those its settings named.
+ * A pair's record depends only on its two slots' frames, its seed and the context's settings. */
+#define SOSVO_FLAG_LK_F2F 0x80
+#define SOSVO_LK_MAX_LEVELS 4
+typedef struct sosvo_lk_options {
+  int32_t half, levels, max_iter, reserved;
+  double eps, min_eig, fb_max;
+} sosvo_lk_options;
+#define SOSVO_LK_OPTIONS_DEFAULT {10, 3, 30, 0, 0.01, 1e-4, 0.0}
+int32_t sosvo_set_lk_options(sosvo_ctx* ctx, const sosvo_lk_options* options);
 #define SOSVO_SUBPIX_HALF_SHIFT 10
 #define SOSVO_SUBPIX_HALF_MASK (3 << SOSVO_SUBPIX_HALF_SHIFT)
 #define SOSVO_SUBPIX_HALF(h) (((h) - 2) << SOSVO_SUBPIX_HALF_SHIFT)
@@ -825,7 +857,8 @@ typedef struct sosvo_batch_cfg {
                               SOSVO_FLAG_CROSS_CHECK_STEREO / _F2F: mutual matches only (see above);
                               SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above);
                               SOSVO_FLAG_RATIO_STEREO / _F2F, SOSVO_RATIO_64THS(r): the ratio rule (see above);
-                              SOSVO_FLAG_SUBPIX, SOSVO_SUBPIX_HALF(h): sub-pixel keypoint refinement (see above) */
+                              SOSVO_FLAG_SUBPIX, SOSVO_SUBPIX_HALF(h): sub-pixel keypoint refinement (see above);
+                              SOSVO_FLAG_LK_F2F: Lucas-Kanade tracking in place of the frame-to-frame matcher (see above) */
   int32_t detector;       /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 
@@ -966,6 +999,7 @@ typedef struct sosvo_rgbd_batch_cfg {
                               SOSVO_FLAG_GATED_F2F, SOSVO_GATED_MAX_DIST(d): search under the gate (likewise; ..._STEREO: SOSVO_ERR_ARG).
                               SOSVO_FLAG_RATIO_F2F, SOSVO_RATIO_64THS(r): the ratio rule (likewise; ..._STEREO: SOSVO_ERR_ARG).
                               SOSVO_FLAG_SUBPIX: SOSVO_ERR_ARG (depth is read at integer pixels).
+                              SOSVO_FLAG_LK_F2F: SOSVO_ERR_ARG (the omni family's).
                               The detectors' stages are those of sosvo_frame_pair_batch on one whole-image mask (set 0
                               for every frame) */
   double quality, min_distance;        /* 0.01, 5 */

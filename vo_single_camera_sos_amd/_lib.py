@@ -40,6 +40,7 @@ SIGNATURES = {
     "sosvo_destroy": (c_i32, [c_p]),
     "sosvo_set_stream": (c_i32, [c_p, c_p]),
     "sosvo_set_hint": (c_i32, [c_p, c_i32, c_i32]),
+    "sosvo_set_lk_options": (c_i32, [c_p, c_p]),
     "sosvo_synchronize": (c_i32, [c_p]),
     "sosvo_last_error": (ctypes.c_char_p, [c_p]),
     "sosvo_timer_start": (c_i32, [c_p]),
@@ -154,6 +155,7 @@ SUBPIX_HALF_SHIFT = 10             # SOSVO_SUBPIX_HALF(h): bits 10-11, the windo
 SUBPIX_HALF_MASK = 3 << SUBPIX_HALF_SHIFT
 SUBPIX_MAX_ITER = 10               # what the one-call and sequence entry points run the stage with
 SUBPIX_EPS = 0.01
+FLAG_LK_F2F = 0x80                 # Lucas-Kanade tracking in place of the frame-to-frame matcher (sosvo_batch_cfg.ransac_flags)
 LK_INITIAL_FLOW = 1                # SOSVO_LK_INITIAL_FLOW: next_pts holds the starting guess on entry
 LK_MAX_HALF, LK_MAX_LEVELS, LK_MAX_ITER, LK_MAX_CAP = 10, 4, 30, 4096
 DETECTOR_GFT = 0
@@ -324,6 +326,35 @@ class LKOptions(namedtuple("LKOptions", "half levels max_iter eps min_eig fb_max
                 raise ValueError("lk: unknown settings %s" % sorted(unknown))
             return cls(**lk)
         raise ValueError("lk must be None, an LKOptions or a dict of its fields, got %r" % (lk,))
+
+
+class LkOptionsStruct(ctypes.Structure):
+    """Mirror of `struct sosvo_lk_options` (include/sosvo.h)."""
+    _fields_ = [("half", c_i32), ("levels", c_i32), ("max_iter", c_i32), ("reserved", c_i32), ("eps", c_f64), ("min_eig", c_f64),
+                ("fb_max", c_f64)]
+
+    @classmethod
+    def of(cls, lk):
+        """An LKOptions -> the struct of sosvo_set_lk_options (fb_max None -> 0: no forward-backward check)."""
+        return cls(lk.half, lk.levels, lk.max_iter, 0, lk.eps, lk.min_eig, 0.0 if lk.fb_max is None else lk.fb_max)
+
+
+def f2f_tracker_options(f2f_tracker, lk, opts=None, rgbd=False):
+    """The `f2f_tracker` / `lk` arguments of the engines' constructors -> the LKOptions of an engine that tracks ("lk"), None
+    for one that matches ("match").  As FramePairPipeline: settings without the tracker are refused; so are the options
+    (`opts`, a MatchOptions) of the frame-to-frame matcher the tracker replaces, and the tracker on an RGB-D engine."""
+    if f2f_tracker not in ("match", "lk"):
+        raise ValueError("f2f_tracker: \"match\" or \"lk\", got %r" % (f2f_tracker,))
+    if f2f_tracker != "lk":
+        if lk is not None:
+            raise ValueError("lk settings without f2f_tracker=\"lk\"")
+        return None
+    if rgbd:
+        raise ValueError("f2f_tracker=\"lk\": the RGB-D engines have no Lucas-Kanade tracking")
+    if opts is not None and (opts.cross_check_f2f or opts.gated_f2f or opts.ratio_f2f):
+        raise ValueError("f2f_tracker=\"lk\" replaces the frame-to-frame matcher: cross_check_f2f / gated_f2f / ratio_f2f "
+                         "cannot be set with it")
+    return LKOptions.of(lk)
 
 
 def gray_pyramid_bytes(nimg, rows, cols, levels):

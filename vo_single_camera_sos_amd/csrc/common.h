@@ -36,6 +36,7 @@ struct sosvo_ctx {
   int32_t hint_score_fp64_only;  // sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): no single-precision tier in ransac_score_kernel
   int32_t hint_shared_device;  // sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other streams' kernels share the chip
   int32_t hint_match_unsplit;  // sosvo_set_hint(SOSVO_HINT_MATCH_UNSPLIT): the matrix-core matchers do not split the train range
+  sosvo_lk_options lk;  // sosvo_set_lk_options: the tracker's settings under SOSVO_FLAG_LK_F2F (cv2's defaults at creation)
   int32_t sub_last;  // parts of the most recent sosvo_frame_pair_batch_streams[_enqueue] call
   // un-joined work of an ..._enqueue call is pending on the part streams: only then does the next call chain its first
   // median behind the previous call's last one, and only then must its slice layout (workspace pointer, part count, each
@@ -155,6 +156,18 @@ __device__ __forceinline__ int refl101(int i, int n) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// nbytes from s to d by the threads i0, i0 + stride, ... of a launch: 16 bytes per lane where both pointers allow it, the
+// rest (and everything between unaligned pointers) byte by byte.
+__device__ __forceinline__ void sosvo_copy_bytes(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, size_t nbytes, int i0, int stride) {
+  size_t done = 0;
+  if ((((uintptr_t)d | (uintptr_t)s) & 15) == 0) {
+    const size_t nv = nbytes / 16;
+    for (size_t i = i0; i < nv; i += stride) reinterpret_cast<uint4*>(d)[i] = reinterpret_cast<const uint4*>(s)[i];
+    done = nv * 16;
+  }
+  for (size_t i = done + i0; i < nbytes; i += stride) d[i] = s[i];
+}
+
 // Value of the neighbouring lane through the DPP operand path (wave_shr:1 / wave_shl:1): a VALU move the compiler
 // folds into the consuming add/max where it can, instead of a ds_bpermute through the LDS crossbar -- the rolling
 // kernels issue 6-10 lane exchanges per row and the LDS pipe, shared by the four SIMDs of a CU, was their limit.
@@ -244,3 +257,16 @@ int32_t sosvo_rgbd_assemble_slots(sosvo_ctx* ctx, const sosvo_rgbd_cam* cam_host
                                   int32_t rows, int32_t cols, int32_t cap, int32_t out_cap, float* m, uint8_t* d, double* X,
                                   double* b, int32_t* M);
 }
+
+// lk.hip: the gray images of a frame store under SOSVO_FLAG_LK_F2F (pipeline.hip carves them).  Level l is
+// [2 * slots, rows_l, cols_l] u8, view-major: image v * slots + s is view v of slot s; rows_{l+1} = (rows_l + 1) / 2.
+struct sosvo_lk_images {
+  uint8_t* level[SOSVO_LK_MAX_LEVELS];
+  int32_t slots, rows, cols;
+};
+bool sosvo_lk_options_ok(const sosvo_lk_options& o);
+int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame);
+int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,
+                              const int32_t* from_img, const int32_t* to_img, int32_t nprob, int32_t cap, const float* pts,
+                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back);

@@ -4,6 +4,10 @@
 
 #include <stdlib.h>
 
+// the defaults of LKOptions (_lib.py): a 21 x 21 window, three levels, TermCriteria(COUNT + EPS, 30, 0.01), minEigThreshold
+// 1e-4, no forward-backward check
+static const sosvo_lk_options kLkDefaults = SOSVO_LK_OPTIONS_DEFAULT;
+
 extern "C" {
 
 int32_t sosvo_abi_version(void) { return 1; }
@@ -34,7 +38,21 @@ int32_t sosvo_create(sosvo_ctx** out, int32_t device, void* stream) {
     free(ctx);
     return SOSVO_ERR_HIP;
   }
+  ctx->lk = kLkDefaults;
   *out = ctx;
+  return SOSVO_OK;
+}
+
+int32_t sosvo_set_lk_options(sosvo_ctx* ctx, const sosvo_lk_options* options) {
+  if (!ctx) return SOSVO_ERR_ARG;
+  // (NULL is refused like every null pointer of this ABI; SOSVO_LK_OPTIONS_DEFAULT is the initialiser of the defaults)
+  if (!options) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, "null pointer (SOSVO_LK_OPTIONS_DEFAULT gives the defaults)");
+  const sosvo_lk_options o = *options;
+  if (!sosvo_lk_options_ok(o))  // (the previous settings stay)
+    return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__,
+                      "out of range: half 2..10, levels 1..4, max_iter 1..30, eps and min_eig finite and >= 0, fb_max finite");
+  ctx->lk = o;
+  ctx->lk.reserved = 0;
   return SOSVO_OK;
 }
 

@@ -70,16 +70,15 @@ __device__ __forceinline__ void lk_level_rows(const int32_t* __restrict__ row_ra
 }
 
 // ---- one pyramid level: (sum k_i k_j in[clamp(2 y + i)][clamp(2 x + j)] + 128) >> 8, k = (1, 4, 6, 4, 1) --------------------
-__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
-                                                                          uint8_t* __restrict__ out, int rows_out, int cols_out,
-                                                                          const int32_t* __restrict__ row_range, int imgs_per_range,
-                                                                          int rows0, int level_in) {
+// (the tile blockIdx.x, blockIdx.y of image `image`, which belongs to view `view` of the row range)
+__device__ __forceinline__ void lk_pyr_down_tile(const uint8_t* __restrict__ in, int rows_in, int cols_in, uint8_t* __restrict__ out,
+                                                 int rows_out, int cols_out, const int32_t* __restrict__ row_range, int image, int view,
+                                                 int rows0, int level_in) {
   constexpr int TW = 2 * kPyrTileX + 3, TH = 2 * kPyrTileY + 3;
   __shared__ uint8_t s_in[TH][TW + 1];
-  const int image = blockIdx.z;
   int ri0, ri1, ro0, ro1;
-  lk_level_rows(row_range, image / imgs_per_range, rows0, level_in, &ri0, &ri1);
-  lk_level_rows(row_range, image / imgs_per_range, rows0, level_in + 1, &ro0, &ro1);
+  lk_level_rows(row_range, view, rows0, level_in, &ri0, &ri1);
+  lk_level_rows(row_range, view, rows0, level_in + 1, &ro0, &ro1);
   ri1 = min(ri1, rows_in);  // (the formula never exceeds the level; belt and braces for the reads)
   ro1 = min(ro1, rows_out);
   const int x0 = blockIdx.x * kPyrTileX, y0 = blockIdx.y * kPyrTileY;
@@ -104,6 +103,39 @@ __global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_kernel(const
     sum += k[i] * row;
   }
   out[((size_t)image * rows_out + y) * cols_out + x] = (uint8_t)(sum >> 8);
+}
+
+__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
+                                                                          uint8_t* __restrict__ out, int rows_out, int cols_out,
+                                                                          const int32_t* __restrict__ row_range, int imgs_per_range,
+                                                                          int rows0, int level_in) {
+  const int image = blockIdx.z;
+  lk_pyr_down_tile(in, rows_in, cols_in, out, rows_out, cols_out, row_range, image, image / imgs_per_range, rows0, level_in);
+}
+
+// ---- the images of a frame store (SOSVO_FLAG_LK_F2F) ----------------------------------------------------
+// A store of `slots` frames keeps level l as [2 * slots, rows_l, cols_l], view-major: image v * slots + s is view v of slot s,
+// so the kernels above and the tracker see one pyramid set of nimg = 2 * slots images under the views' row range.  A front
+// end over nf frames has its gray rows as [2, nf_all, rows, cols]; frame f0 + i of it goes to slot tab.slot[i].
+//
+// Level 0: the rows of the view's range, copied (workgroup (c, i, v) takes every gridDim.x-th 4 KB block of the span).
+__global__ __launch_bounds__(256) void lk_store_level0_kernel(const uint8_t* __restrict__ gray, int nf_all, int f0, sosvo_slot_table tab,
+                                                              int slots, int rows, int cols, const int32_t* __restrict__ row_range,
+                                                              uint8_t* __restrict__ level0) {
+  const int i = blockIdx.y, v = blockIdx.z;
+  int r0, r1;
+  lk_level_rows(row_range, v, rows, 0, &r0, &r1);
+  const size_t npx = (size_t)rows * cols, first = (size_t)r0 * cols, bytes = (size_t)(r1 - r0) * cols;
+  sosvo_copy_bytes(level0 + ((size_t)v * slots + tab.slot[i]) * npx + first, gray + ((size_t)v * nf_all + f0 + i) * npx + first, bytes,
+                   blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+// Level l + 1 from level l, both in the store: blockIdx.z = v * nf + i is view v of slot tab.slot[i].
+__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_slots_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
+                                                                                uint8_t* __restrict__ out, int rows_out, int cols_out,
+                                                                                const int32_t* __restrict__ row_range, int nf,
+                                                                                sosvo_slot_table tab, int slots, int rows0, int level_in) {
+  const int v = blockIdx.z / nf, i = blockIdx.z - v * nf;
+  lk_pyr_down_tile(in, rows_in, cols_in, out, rows_out, cols_out, row_range, v * slots + tab.slot[i], v, rows0, level_in);
 }
 
 // ---- the tracker -------------------------------------------------------------------------------------------------------------
@@ -161,12 +193,14 @@ constexpr int kLkLdsWords16 = 4 * lk_group_words(5), kLkLdsWords64 = lk_group_wo
 // image next_img[p] and writes next_pts, status, err.  The BACKWARD pass (a.fb_max2 >= 0) is launched with the images swapped
 // and start = the forward results: points whose status is 1 are tracked back, `out` = back receives the position (the start
 // for the others), and the status is cleared where the point is lost or |back - ref|^2 > fb_max^2 (ref = the forward start).
+// store_pt (nullptr: the points of problem p are the rows p * cap ...): the forward start points -- `start` of the forward pass,
+// `ref` of the backward pass -- are read where they lie, problem p's from point store_pt[p] on (a frame store's m_top / m_bot).
 template <int GS>
 __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* __restrict__ row_range, const int32_t* __restrict__ from_img,
                                                       const int32_t* __restrict__ to_img, const float* __restrict__ start,
                                                       const int32_t* __restrict__ n, float* __restrict__ out,
                                                       uint8_t* __restrict__ status, float* __restrict__ err,
-                                                      const float* __restrict__ ref) {
+                                                      const float* __restrict__ ref, const int64_t* __restrict__ store_pt) {
   constexpr int KPW = 64 / GS;  // keypoints per wave
   __shared__ int32_t s_lds[GS == 64 ? kLkLdsWords64 : kLkLdsWords16];
   const int lane = threadIdx.x, grp = lane / GS, r = lane - grp * GS;
@@ -187,7 +221,8 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
   for (int k0 = blockIdx.y * KPW; k0 < count; k0 += gridDim.y * KPW) {  // (uniform)
     const int k = k0 + grp;
     const size_t row = (size_t)p * a.cap + min(k, count - 1);
-    const float sx = start[2 * row], sy = start[2 * row + 1];
+    const size_t srow = store_pt && !backward ? (size_t)store_pt[p] + min(k, count - 1) : row;
+    const float sx = start[2 * srow], sy = start[2 * srow + 1];
     float gx0 = sx, gy0 = sy;
     if (a.initial_flow) {
       gx0 = out[2 * row];
@@ -334,7 +369,8 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
           status[o] = lost ? 0 : 1;
           err[o] = lost ? 0.0f : (float)((double)err_sum / (1024.0 * (double)N));
         } else {
-          const double ddx = (double)ox - (double)ref[2 * o], ddy = (double)oy - (double)ref[2 * o + 1];
+          const size_t ro = store_pt ? (size_t)store_pt[p] + k : o;
+          const double ddx = (double)ox - (double)ref[2 * ro], ddy = (double)oy - (double)ref[2 * ro + 1];
           if (lost || !(ddx * ddx + ddy * ddy <= a.fb_max2)) status[o] = 0;
         }
       }
@@ -347,7 +383,124 @@ bool lk_sizes_ok(int64_t nimg, int64_t rows, int64_t cols, int64_t levels) {
          levels <= kLkMaxLevels && nimg * rows * cols < ((int64_t)1 << 40);
 }
 
+// the levels of a frame store's images as the kernels' table
+LkLevels lk_store_levels(const sosvo_lk_images& im) {
+  LkLevels t;
+  int rows = im.rows, cols = im.cols;
+  for (int l = 0; l < kLkMaxLevels; ++l) {
+    t.base[l] = im.level[l];
+    t.rows[l] = rows;
+    t.cols[l] = cols;
+    rows = (rows + 1) / 2;
+    cols = (cols + 1) / 2;
+  }
+  return t;
+}
+
+// the levels 1 .. levels - 1 of all nimg images of the table, each from the one below
+int32_t lk_build_levels(sosvo_ctx* ctx, const LkLevels& t, int nimg, int levels, const int32_t* row_range) {
+  for (int l = 0; l + 1 < levels; ++l) {
+    const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), nimg);
+    SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                 const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return SOSVO_OK;
+}
+
+// the forward launch and, with `back`, the backward one (a: everything but initial_flow's reset and fb_max2, set here)
+int32_t lk_launch(sosvo_ctx* ctx, LkArgs a, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int nprob,
+                  const float* prev_pts, const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err,
+                  float* back, double fb_max) {
+  a.fb_max2 = -1.0;
+  const bool small = a.half <= 5;
+  const int kpw = small ? 4 : 1;
+  // waves per problem: enough for the chip at a few problems, several rounds per wave at thousands
+  const dim3 grid(nprob, min(cdiv(a.cap, kpw), nprob >= 4096 ? 16 : 64));
+  if (small)
+    SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
+                 status, err, (const float*)nullptr, store_pt);
+  else
+    SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
+                 status, err, (const float*)nullptr, store_pt);
+  SOSVO_LAUNCH_CHECK(ctx);
+  if (back) {  // the forward results tracked back: images swapped, no initial guess
+    a.initial_flow = 0;
+    a.fb_max2 = fb_max * fb_max;
+    if (small)
+      SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
+                   (float*)nullptr, prev_pts, store_pt);
+    else
+      SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
+                   (float*)nullptr, prev_pts, store_pt);
+    SOSVO_LAUNCH_CHECK(ctx);
+  }
+  return SOSVO_OK;
+}
+
 }  // namespace
+
+bool sosvo_lk_options_ok(const sosvo_lk_options& o) {
+  return o.half >= 2 && o.half <= kLkMaxHalf && o.levels >= 1 && o.levels <= kLkMaxLevels && o.max_iter >= 1 && o.max_iter <= 30 &&
+         o.eps >= 0.0 && isfinite(o.eps) && o.min_eig >= 0.0 && isfinite(o.min_eig) && isfinite(o.fb_max);
+}
+
+// (internal, common.h) The images of nframes frames into a frame store.  gray [2, nframes, rows, cols]: the front end's gray
+// rows, frame i goes to slot slot_of_frame[i] (HOST table, checked by the caller) or first_slot + i; gray == nullptr: level 0 of
+// the store IS the front end's buffer (a pair batch, frame i in slot i) and nothing is copied.  Then the levels in use, each
+// from the one below inside the store.  The table travels in kernel arguments, kSosvoSlotArgFrames frames per launch.
+int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame) {
+  SOSVO_REQUIRE(ctx, im.level[0] && im.level[1] && im.level[2] && im.level[3], "null pointer");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(2 * (int64_t)im.slots, im.rows, im.cols, levels), "sizes out of range (2 * slots <= 65535, levels 1..4)");
+  const LkLevels t = lk_store_levels(im);
+  if (!gray) return lk_build_levels(ctx, t, 2 * im.slots, levels, row_range);
+  for (int f0 = 0; f0 < nframes; f0 += kSosvoSlotArgFrames) {
+    const int nf = nframes - f0 < kSosvoSlotArgFrames ? nframes - f0 : kSosvoSlotArgFrames;
+    sosvo_slot_table tab;
+    for (int i = 0; i < kSosvoSlotArgFrames; ++i) tab.slot[i] = i >= nf ? 0 : slot_of_frame ? slot_of_frame[f0 + i] : first_slot + f0 + i;
+    for (int i = 0; i < nf; ++i) SOSVO_REQUIRE(ctx, tab.slot[i] >= 0 && tab.slot[i] < im.slots, "slot out of range");
+    const int blocks = min(cdiv(im.rows * im.cols, 4096), 64);
+    SOSVO_LAUNCH(ctx, lk_store_level0_kernel, dim3(blocks, nf, 2), dim3(256), 0, ctx->stream, gray, nframes, f0, tab, im.slots, im.rows,
+                 im.cols, row_range, im.level[0]);
+    SOSVO_LAUNCH_CHECK(ctx);
+    for (int l = 0; l + 1 < levels; ++l) {
+      const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), 2 * nf);
+      SOSVO_LAUNCH(ctx, lk_pyr_down_slots_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                   im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
+      SOSVO_LAUNCH_CHECK(ctx);
+    }
+  }
+  return SOSVO_OK;
+}
+
+// (internal, common.h) sosvo_track_lk on a frame store's images with the settings o: problem p tracks the n[p] points that lie
+// from point store_pt[p] of `pts` on (DEVICE table; points, not floats) from image from_img[p] to image to_img[p]; outputs as
+// sosvo_track_lk's, [nprob, cap, ...]; back: its buffer, used when o.fb_max > 0.
+int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,
+                              const int32_t* from_img, const int32_t* to_img, int32_t nprob, int32_t cap, const float* pts,
+                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back) {
+  SOSVO_REQUIRE(ctx, im.level[0] && im.level[1] && im.level[2] && im.level[3] && from_img && to_img && pts && store_pt && n &&
+                         next_pts && status && err && back,
+                "null pointer");
+  SOSVO_REQUIRE(ctx, sosvo_lk_options_ok(o), "LK settings out of range (sosvo_set_lk_options)");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(2 * (int64_t)im.slots, im.rows, im.cols, o.levels), "sizes out of range (2 * slots <= 65535)");
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535 && cap > 0, "nprob / cap out of range");
+  if (nprob == 0) return SOSVO_OK;
+  LkArgs a;
+  a.lv = lk_store_levels(im);
+  for (int l = o.levels; l < kLkMaxLevels; ++l) a.lv.base[l] = nullptr;  // (not built, never read)
+  a.nimg = 2 * im.slots;
+  a.levels = o.levels;
+  a.cap = cap;
+  a.half = o.half;
+  a.max_iter = o.max_iter;
+  a.initial_flow = 0;
+  a.eps2 = o.eps * o.eps;
+  a.min_eig = o.min_eig;
+  return lk_launch(ctx, a, row_range, from_img, to_img, nprob, pts, store_pt, n, next_pts, status, err, o.fb_max > 0.0 ? back : nullptr,
+                   o.fb_max);
+}
 
 extern "C" {
 
@@ -368,13 +521,7 @@ int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, in
   if (nimg == 0) return SOSVO_OK;
   LkLevels t;
   lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
-  for (int l = 0; l + 1 < levels; ++l) {
-    const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), nimg);
-    SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                 const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, rows, l);
-    SOSVO_LAUNCH_CHECK(ctx);
-  }
-  return SOSVO_OK;
+  return lk_build_levels(ctx, t, nimg, levels, row_range);
 }
 
 int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
@@ -404,30 +551,7 @@ int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, 
   a.initial_flow = (flags & SOSVO_LK_INITIAL_FLOW) ? 1 : 0;
   a.eps2 = eps * eps;
   a.min_eig = min_eig;
-  a.fb_max2 = -1.0;
-  const bool small = half <= 5;
-  const int kpw = small ? 4 : 1;
-  // waves per problem: enough for the chip at a few problems, several rounds per wave at thousands
-  const dim3 grid(nprob, min(cdiv(cap, kpw), nprob >= 4096 ? 16 : 64));
-  if (small)
-    SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
-                 status, err, (const float*)nullptr);
-  else
-    SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
-                 status, err, (const float*)nullptr);
-  SOSVO_LAUNCH_CHECK(ctx);
-  if (back) {  // the forward results tracked back: images swapped, no initial guess
-    a.initial_flow = 0;
-    a.fb_max2 = fb_max * fb_max;
-    if (small)
-      SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
-                   (float*)nullptr, prev_pts);
-    else
-      SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
-                   (float*)nullptr, prev_pts);
-    SOSVO_LAUNCH_CHECK(ctx);
-  }
-  return SOSVO_OK;
+  return lk_launch(ctx, a, row_range, prev_img, next_img, nprob, prev_pts, nullptr, n, next_pts, status, err, back, fb_max);
 }
 
 }  // extern "C"

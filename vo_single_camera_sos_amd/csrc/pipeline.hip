@@ -88,13 +88,30 @@ Ratio carve_ratio(Carver& cv, int32_t r64, size_t n_keys) {
 }
 constexpr const char* kBadRatioFlags = "SOSVO_FLAG_RATIO_STEREO / _F2F need SOSVO_RATIO_64THS(r), r in 1..63";
 
+// ---- Lucas-Kanade tracking (SOSVO_FLAG_LK_F2F): the tracking step follows the reference frame's points into the current
+// frame's images instead of matching descriptors.  The options of the matcher it replaces are refused with it.
+bool lk_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_LK_F2F) != 0; }
+bool lk_flags_ok(int32_t flags) {
+  return (flags & SOSVO_FLAG_LK_F2F) == 0 ||
+         (flags & (SOSVO_FLAG_CROSS_CHECK_F2F | SOSVO_FLAG_GATED_F2F | SOSVO_FLAG_RATIO_F2F)) == 0;
+}
+constexpr const char* kBadLkFlags =
+    "SOSVO_FLAG_LK_F2F replaces the frame-to-frame matcher: SOSVO_FLAG_CROSS_CHECK_F2F / _GATED_F2F / _RATIO_F2F cannot be set with it";
+// what every omni entry point asks of cfg->ransac_flags (nullptr: fine)
+const char* omni_flags_msg(int32_t flags) { return !ratio_flags_ok(flags) ? kBadRatioFlags : lk_flags_ok(flags) ? nullptr : kBadLkFlags; }
+// the gray rows the front end computes are those of sosvo_gray_rows_needed (GFT with the fused median), else all rows
+bool gray_rows_known(const sosvo_batch_cfg& c) {
+  return c.detector == SOSVO_DETECTOR_GFT && (c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11);
+}
+
 // (SOSVO_FLAG_SUBPIX is refused with them: the RGB-D assemble stage reads depth at the keypoints' integer pixels)
 bool rgbd_stereo_flags_ok(const sosvo_rgbd_batch_cfg& c) {
-  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO | SOSVO_FLAG_RATIO_STEREO | SOSVO_FLAG_SUBPIX)) == 0;
+  return (c.flags & (SOSVO_FLAG_CROSS_CHECK_STEREO | SOSVO_FLAG_GATED_STEREO | SOSVO_FLAG_RATIO_STEREO | SOSVO_FLAG_SUBPIX |
+                     SOSVO_FLAG_LK_F2F)) == 0;
 }
 constexpr const char* kRgbdStereoFlags =
     "SOSVO_FLAG_CROSS_CHECK_STEREO / SOSVO_FLAG_GATED_STEREO / SOSVO_FLAG_RATIO_STEREO: an RGB-D camera has no static stereo; "
-    "SOSVO_FLAG_SUBPIX: depth is read at integer pixels";
+    "SOSVO_FLAG_SUBPIX: depth is read at integer pixels; SOSVO_FLAG_LK_F2F: the omni family's";
 bool rgbd_flags_ok(const sosvo_rgbd_batch_cfg& c) { return rgbd_stereo_flags_ok(c) && ratio_flags_ok(c.flags); }
 
 // ---- gated matching (SOSVO_FLAG_GATED_*): the 1-NN search among the trains that pass the assemble stage's own pixel gate.
@@ -190,6 +207,45 @@ FrameStore carve_store(Carver& cv, size_t S, size_t Fc) {
   return s;
 }
 
+// The tracker's temporaries (SOSVO_FLAG_LK_F2F), [2 B, ...]: problem v * B + i is view v of pair i.  from / to: its images in
+// the store, n: its point count M[ref[i]], pt: where its points begin in m_top (in points; the bottom view's lie in m_bot).
+// Carved only when the switch is set, after everything else.
+struct LkTmp {
+  float *next = nullptr, *err = nullptr, *back = nullptr;
+  uint8_t* status = nullptr;
+  int32_t *from = nullptr, *to = nullptr, *n = nullptr;
+  int64_t* pt = nullptr;
+};
+LkTmp carve_lk_tmp(Carver& cv, bool on, size_t B, size_t Fc) {
+  LkTmp t;
+  if (!on) return t;
+  t.next = cv.take<float>(2 * B * Fc * 2);
+  t.status = cv.take<uint8_t>(2 * B * Fc);
+  t.err = cv.take<float>(2 * B * Fc);
+  t.back = cv.take<float>(2 * B * Fc * 2);
+  t.from = cv.take<int32_t>(2 * B);
+  t.to = cv.take<int32_t>(2 * B);
+  t.n = cv.take<int32_t>(2 * B);
+  t.pt = cv.take<int64_t>(2 * B);
+  return t;
+}
+// The store's images (SOSVO_FLAG_LK_F2F; sosvo_lk_images, common.h): every level [2 * slots, rows_l, cols_l], each 256-byte
+// aligned.  level0 != nullptr (a pair batch: frame i in slot i of 2 * n_pairs): the front end's gray buffer is level 0.
+// `on` clear: level[0] stays null, which is how the runners see the switch.
+sosvo_lk_images carve_lk_images(Carver& cv, bool on, size_t S, int rows, int cols, uint8_t* level0, bool in_place) {
+  sosvo_lk_images im{};
+  if (!on) return im;
+  im.slots = (int32_t)S;
+  im.rows = rows;
+  im.cols = cols;
+  for (int l = 0; l < SOSVO_LK_MAX_LEVELS; ++l) {
+    im.level[l] = l == 0 && in_place ? level0 : cv.take<uint8_t>(2 * S * (size_t)rows * cols);
+    rows = (rows + 1) / 2;
+    cols = (cols + 1) / 2;
+  }
+  return im;
+}
+
 struct TrackTmp {
   int32_t *ref_frame, *cur_frame, *o_top, *o_bot, *cam, *cq, *ct, *cn, *cn_top, *idx, *n_inl, *info, *lm_iters;
   uint32_t *k_top, *k_bot;
@@ -197,6 +253,7 @@ struct TrackTmp {
   double *f, *p, *T_ransac, *T, *cam_off, *cam_rot, *lm_cost;
   MutualTabs mutual;
   Ratio ratio;  // (one buffer serves both views: their matching steps follow each other on the stream)
+  LkTmp lk;
 };
 TrackTmp carve_track(Carver& cv, size_t B, size_t Fc, bool mutual) {
   TrackTmp t{};
@@ -231,10 +288,13 @@ struct Workspace {
   FrontEndTmp fe;
   FrameStore store;
   TrackTmp tt;
+  sosvo_lk_images img;      // (level[0] == nullptr without SOSVO_FLAG_LK_F2F)
+  bool img_in_place;        // level 0 is fe.gray: nothing to copy
+  const int32_t* img_rows;  // the row range of the images: fe.gray_rows where the front end computes only those, else nullptr
   size_t bytes;
 };
 // (a pair batch is the sequence layout with window = slots = 2 * n_pairs; base == nullptr: sizes only)
-Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* base) {
+Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* base, bool pair_batch = false) {
   Carver cv{reinterpret_cast<char*>(base)};
   Workspace ws;
   ws.fe = carve_front_end(cv, c, window);
@@ -245,6 +305,10 @@ Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* bas
   ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
   ws.fe.ratio = carve_ratio(cv, ratio_stereo(c), (cross_stereo(c) ? 2 : 1) * window * c.nmask * c.kp_cap);
   ws.tt.ratio = carve_ratio(cv, ratio_f2f(c), (cross_f2f(c) ? 2 : 1) * (size_t)c.n_pairs * c.frame_cap);
+  ws.img = carve_lk_images(cv, lk_f2f(c), slots, c.rows, c.cols, ws.fe.gray, pair_batch);
+  ws.img_in_place = pair_batch;
+  ws.img_rows = gray_rows_known(c) ? ws.fe.gray_rows : nullptr;
+  ws.tt.lk = carve_lk_tmp(cv, lk_f2f(c), c.n_pairs, c.frame_cap);
   ws.bytes = cv.off;
   return ws;
 }
@@ -348,6 +412,38 @@ __global__ __launch_bounds__(256) void seq_copy_slots_kernel(CopyPairs cp, const
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < words; i += gridDim.y * blockDim.x) d[i] = s[i];
   }
   if (blockIdx.y == 0 && threadIdx.x == 0) st.M[dst] = st.M[src];  // (no slot of the list is both read and written)
+}
+
+// ... and the images of those slots (SOSVO_FLAG_LK_F2F), in a launch of their own: workgroup (j, c, 2 l + v) copies every
+// gridDim.y-th block of view v, level l of pair j -- whole images, also the rows outside the range, which nobody reads.
+constexpr int kCopyImageChunks = 16;
+__global__ __launch_bounds__(256) void seq_copy_images_kernel(CopyPairs cp, const int32_t* __restrict__ src_list,
+                                                              const int32_t* __restrict__ dst_list, sosvo_lk_images im) {
+  const int j = blockIdx.x, v = blockIdx.z & 1, l = blockIdx.z >> 1;
+  const int src = src_list ? src_list[j] : cp.src[j], dst = src_list ? dst_list[j] : cp.dst[j];
+  int rows = im.rows, cols = im.cols;
+  for (int k = 0; k < l; ++k) {
+    rows = (rows + 1) / 2;
+    cols = (cols + 1) / 2;
+  }
+  const size_t npx = (size_t)rows * cols;
+  sosvo_copy_bytes(im.level[l] + ((size_t)v * im.slots + dst) * npx, im.level[l] + ((size_t)v * im.slots + src) * npx, npx,
+                   blockIdx.y * blockDim.x + threadIdx.x, gridDim.y * blockDim.x);
+}
+
+// The tracker's problems of B slot pairs (LkTmp): view v of pair i tracks the points of slot ref[i] from image
+// v * slots + ref[i] to image v * slots + cur[i].  bot_pt: where m_bot begins, in points from m_top.
+__global__ void lk_setup_kernel(int B, int slots, int Fc, const int32_t* __restrict__ ref, const int32_t* __restrict__ cur,
+                                const int32_t* __restrict__ M, int64_t bot_pt, int32_t* __restrict__ from, int32_t* __restrict__ to,
+                                int32_t* __restrict__ n, int64_t* __restrict__ pt) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= 2 * B) return;
+  const int v = p / B, i = p - v * B;
+  const int r = clampi(ref[i], 0, slots - 1), c = clampi(cur[i], 0, slots - 1);  // (the host has checked them)
+  from[p] = v * slots + r;
+  to[p] = v * slots + c;
+  n[p] = M[r];
+  pt[p] = v * bot_pt + (int64_t)r * Fc;
 }
 
 // ---- RGB-D variant (BASELINE config 5): the same three parts; a store of `slots` RGBDFrame records (keypoints with valid
@@ -544,12 +640,13 @@ extern "C" {
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->nmask <= 0 || cfg->kp_cap <= 0 ||
-      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap) || !ratio_flags_ok(cfg->ransac_flags))
+      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap) || omni_flags_msg(cfg->ransac_flags) ||
+      (lk_f2f(*cfg) && cfg->n_pairs > 8192))  // (the store's images: 2 * slots <= 65535)
     return 0;
   // (laxer than the call itself, which refuses nmask > 32, kp_cap > 4096 and frame_cap > 16384: such a shape gets a size
   // here and "out of range" there)
   const size_t F = 2 * (size_t)cfg->n_pairs;
-  return carve(*cfg, F, F, nullptr).bytes;
+  return carve(*cfg, F, F, nullptr, true).bytes;
 }
 
 #define STAGE(call)              \
@@ -598,7 +695,7 @@ static int32_t match_mutual(sosvo_ctx* ctx, const Gate& g, const Ratio& r, const
 static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int F, const uint8_t* omni,
                              const uint32_t* unwrap_table, const uint32_t* mask_bits, const int8_t* pattern,
                              const FrontEndTmp& t, const FrameStore& o, hipEvent_t median_wait, hipEvent_t median_done,
-                             const int32_t* slot_of_frame = nullptr) {
+                             const int32_t* slot_of_frame = nullptr, const Workspace* images = nullptr, int first_slot = 0) {
   const int NI = 2 * F, NM = cfg->nmask, cap = cfg->kp_cap, Fc = cfg->frame_cap;
   const int h = F * NM;  // problems of one view: (frame, mask); the top view's come first (view-major images)
   int32_t rc;
@@ -607,7 +704,7 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   const bool fused_median = cfg->median_ksize == 3 || cfg->median_ksize == 5 || cfg->median_ksize == 11;
   // skipping unreachable rows is exact for GFT only (the range is GFT's reach); ORB, FAST and AGAST see every row, as
   // ImageFrontEnd computes them
-  const bool rows_known = det == SOSVO_DETECTOR_GFT && fused_median;
+  const bool rows_known = gray_rows_known(*cfg);
   if (rows_known) {
     // rows beyond the reach of GFT on the masks and of ORB.compute on its keypoints are not computed (the range is a
     // model constant; a 2-workgroup kernel per call keeps this entry point free of caller-side state)
@@ -623,6 +720,11 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
     STAGE(sosvo_median_gray(ctx, t.pano, NI, cfg->rows, cfg->cols, cfg->median_ksize, t.gray));
   }
   if (median_done) SOSVO_HIP(ctx, hipEventRecord(median_done, ctx->stream));
+  // SOSVO_FLAG_LK_F2F: the frames' gray rows and the pyramid levels in use go where their records go (`images`: the workspace
+  // whose store `o` belongs to, o shifted by first_slot)
+  if (images && images->img.level[0])
+    STAGE(sosvo_lk_images_fill(ctx, images->img, ctx->lk.levels, images->img_rows, images->img_in_place ? nullptr : t.gray, F,
+                               first_slot, slot_of_frame));
   // the stages ImageFrontEnd.run_features calls for the detector (frontend.py), with the same arguments
   if (det == SOSVO_DETECTOR_ORB) {
     // the mask pyramid is a model constant, rebuilt here on every call (as gray_rows above) to keep the entry point free of
@@ -667,12 +769,10 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   return SOSVO_OK;
 }
 
-// TrackerStereoSE3.track_frame (pose_est_tools.py:736-847) for B (reference slot, current slot) pairs of a frame store:
-// frame-to-frame matching per view (query = current frame, train = reference frame), |du| gate, stacking, non-central
-// RANSAC (problem i samples with seed + i), LM on the inliers, [B,16] records.
-// (seeds: device array of per-pair seeds, pair i samples with seeds[i]; nullptr: with seed + i)
-static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, uint64_t seed,
-                            const FrameStore& s, const TrackTmp& b, double* results, const uint64_t* seeds = nullptr) {
+// The frame-to-frame correspondences of B slot pairs by MATCHING: per view query = current frame, train = reference frame, sort,
+// |du| gate, stacking (b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top).
+static int32_t correspondences_matched(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, const FrameStore& s,
+                                       const TrackTmp& b) {
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
   int32_t rc;
   const bool mutual = cross_f2f(*cfg);
@@ -688,8 +788,42 @@ static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_ba
   else
     STAGE(match_1nn(ctx, gate, b.ratio, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
   STAGE(sosvo_sort_matches(ctx, b.k_bot, s.M, b.cur_frame, B, Fc, b.o_bot));
-  STAGE(sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top,
-                           b.o_top, b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top));
+  return sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top, b.o_top,
+                            b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top);
+}
+
+// ... by TRACKING (SOSVO_FLAG_LK_F2F): the reference frames' points, read where the store keeps them, followed into the current
+// frames' images with the context's settings -- ONE tracker launch of 2 B problems, top views first -- then the tracked
+// assemble into the same outputs.
+static int32_t correspondences_tracked(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, const FrameStore& s,
+                                       const TrackTmp& b, const sosvo_lk_images& im, const int32_t* img_rows) {
+  const int Fc = cfg->frame_cap, Cc = 2 * Fc;
+  int32_t rc;
+  const LkTmp& k = b.lk;
+  SOSVO_REQUIRE(ctx, im.level[0] && k.next, "SOSVO_FLAG_LK_F2F without the store's images");
+  SOSVO_LAUNCH(ctx, lk_setup_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, ctx->stream, B, im.slots, Fc, b.ref_frame, b.cur_frame, s.M,
+               (int64_t)((s.m_bot - s.m_top) / 2), k.from, k.to, k.n, k.pt);
+  SOSVO_LAUNCH_CHECK(ctx);
+  STAGE(sosvo_lk_images_track(ctx, im, ctx->lk, img_rows, k.from, k.to, 2 * B, Fc, s.m_top, k.pt, k.n, k.next, k.status, k.err, k.back));
+  return sosvo_f2f_assemble_tracked(ctx, rig, s.m_top, s.m_bot, s.X, s.M, Fc, b.ref_frame, k.next, k.next + (size_t)B * Fc * 2, k.status,
+                                    k.status + (size_t)B * Fc, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top);
+}
+
+// TrackerStereoSE3.track_frame (pose_est_tools.py:736-847) for B (reference slot, current slot) pairs of a frame store:
+// frame-to-frame matching per view (query = current frame, train = reference frame), |du| gate, stacking -- or the tracker in
+// the matcher's place (`images`: the workspace the store belongs to, for its images) --, non-central
+// RANSAC (problem i samples with seed + i), LM on the inliers, [B,16] records.
+// (seeds: device array of per-pair seeds, pair i samples with seeds[i]; nullptr: with seed + i)
+static int32_t run_tracking(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, int B, uint64_t seed,
+                            const FrameStore& s, const TrackTmp& b, double* results, const uint64_t* seeds = nullptr,
+                            const Workspace* images = nullptr) {
+  const int Fc = cfg->frame_cap, Cc = 2 * Fc;
+  int32_t rc;
+  SOSVO_REQUIRE(ctx, !lk_f2f(*cfg) || images, "SOSVO_FLAG_LK_F2F without the store's images");
+  if (lk_f2f(*cfg))
+    STAGE(correspondences_tracked(ctx, rig, cfg, B, s, b, images->img, images->img_rows));
+  else
+    STAGE(correspondences_matched(ctx, rig, cfg, B, s, b));
   // 3D-2D absolute pose: RANSAC, then LM on the inliers
   const int32_t rflags = SOSVO_FLAG_CAM_ROT_IDENTITY | (cfg->ransac_flags & SOSVO_FLAG_GP3P);
   if (seeds)
@@ -721,17 +855,19 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_REQUIRE(ctx, cfg->nmask >= 1 && cfg->nmask <= 32 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096, "nmask / kp_cap out of range");
   SOSVO_REQUIRE(ctx, cfg->frame_cap > 0 && cfg->frame_cap <= 16384, "frame_cap out of range (max 16384)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
-  SOSVO_REQUIRE(ctx, ratio_flags_ok(cfg->ransac_flags), kBadRatioFlags);
+  if (omni_flags_msg(cfg->ransac_flags)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(cfg->ransac_flags));
+  SOSVO_REQUIRE(ctx, !lk_f2f(*cfg) || sosvo_lk_options_ok(ctx->lk), "LK settings out of range (sosvo_set_lk_options)");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
-  const Workspace ws = carve(*cfg, F, F, workspace);
+  const Workspace ws = carve(*cfg, F, F, workspace, true);
   SOSVO_REQUIRE(ctx, workspace_bytes >= ws.bytes, "workspace too small (see sosvo_frame_pair_batch_workspace)");
   int32_t rc;
   SOSVO_LAUNCH(ctx, batch_setup_kernel, dim3(cdiv(B > 18 ? B : 18, 256)), dim3(256), 0, ctx->stream, B, foci_of(rig),
                ws.tt.ref_frame, ws.tt.cur_frame, ws.tt.cam_off, ws.tt.cam_rot);
   SOSVO_LAUNCH_CHECK(ctx);
-  STAGE(run_front_end(ctx, rig, cfg, F, omni, unwrap_table, mask_bits, pattern, ws.fe, ws.store, median_wait, median_done));
-  return run_tracking(ctx, rig, cfg, B, cfg->seed, ws.store, ws.tt, results);
+  STAGE(run_front_end(ctx, rig, cfg, F, omni, unwrap_table, mask_bits, pattern, ws.fe, ws.store, median_wait, median_done, nullptr,
+                      &ws));
+  return run_tracking(ctx, rig, cfg, B, cfg->seed, ws.store, ws.tt, results, nullptr, &ws);
 }
 
 int32_t sosvo_frame_pair_batch(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_batch_cfg* cfg, const uint8_t* omni,
@@ -772,6 +908,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
   SOSVO_REQUIRE(ctx, n_streams >= 1 && n_streams <= kSosvoMaxSubStreams, "n_streams out of range (1..4)");
   SOSVO_REQUIRE(ctx, cfg->n_pairs >= n_streams && cfg->n_pairs <= 8192, "n_pairs out of range (n_streams..8192)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
+  if (omni_flags_msg(cfg->ransac_flags)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(cfg->ransac_flags));
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const size_t need = sosvo_frame_pair_batch_streams_workspace(cfg, n_streams);
   SOSVO_REQUIRE(ctx, need > 0 && workspace_bytes >= need, "workspace too small (see sosvo_frame_pair_batch_streams_workspace)");
@@ -832,6 +969,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     c.n_pairs = hi - lo;
     c.seed = cfg->seed + (uint64_t)lo;  // pair i samples with seed + i, whatever the split
     sosvo_ctx* sc = ctx->sub[s];
+    sc->lk = ctx->lk;  // (settings, not hints: they change results, so every part tracks with the caller's)
     SOSVO_HIP(ctx, hipStreamWaitEvent(sc->stream, ctx->sub_begin, 0));
     const int32_t rc = run_frame_pairs(sc, rig, &c, omni + (size_t)2 * lo * cfg->H * cfg->W * 3, unwrap_table, mask_bits, pattern,
                                        ws, bytes[s], results + (size_t)16 * lo, token, ctx->sub_median[s]);
@@ -1015,9 +1153,10 @@ struct OmniSeq {
   using Frames = OmniFrames;
   static constexpr const char* kTooSmall = "workspace too small (see sosvo_sequence_workspace)";
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
-    return c && c->nmask >= 1 && c->nmask <= 32 && ratio_flags_ok(c->ransac_flags) && seq_shape_ok(c, c->detector, window, slots);
+    return c && c->nmask >= 1 && c->nmask <= 32 && !omni_flags_msg(c->ransac_flags) && seq_shape_ok(c, c->detector, window, slots) &&
+           (!lk_f2f(*c) || slots <= 32767);  // (the store's images: 2 * slots <= 65535)
   }
-  static const char* flags_msg(const Cfg* c) { return ratio_flags_ok(c->ransac_flags) ? nullptr : kBadRatioFlags; }
+  static const char* flags_msg(const Cfg* c) { return omni_flags_msg(c->ransac_flags); }
   static constexpr const char* kBadFrames = SOSVO_TABLE_FRAME_MSG;
   static bool frames_ok(const Cfg* c) { return sosvo_table_frame_ok(c->H, c->W); }  // the front end reads them through the table
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return ::carve(c, window, slots, base); }
@@ -1026,14 +1165,24 @@ struct OmniSeq {
             {8, 8, 32, 32, 24, 24, 24},
             s.M};
   }
-  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const FrontEndTmp& t, const FrameStore& o,
+  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const Ws& ws, int first_slot,
                            const int32_t* slot_of_frame) {
-    return run_front_end(ctx, in.rig, cfg, F, in.omni, in.unwrap_table, in.mask_bits, in.pattern, t, o, nullptr, nullptr,
-                         slot_of_frame);
+    return run_front_end(ctx, in.rig, cfg, F, in.omni, in.unwrap_table, in.mask_bits, in.pattern, ws.fe,
+                         ws.store.at(first_slot, cfg->frame_cap), nullptr, nullptr, slot_of_frame, &ws, first_slot);
   }
   static int32_t track(sosvo_ctx* ctx, const sosvo_rig* rig, const Cfg* cfg, int B, uint64_t seed, const Ws& ws, double* results,
                        const uint64_t* seeds) {
-    return run_tracking(ctx, rig, cfg, B, seed, ws.store, ws.tt, results, seeds);
+    return run_tracking(ctx, rig, cfg, B, seed, ws.store, ws.tt, results, seeds, &ws);
+  }
+  // the images of the copied slots follow their records (SOSVO_FLAG_LK_F2F: the levels the context's settings use)
+  static int32_t copy_images(sosvo_ctx* ctx, const CopyPairs& cp, const int32_t* src_list, const int32_t* dst_list, int32_t n,
+                             const Ws& ws) {
+    if (!ws.img.level[0]) return SOSVO_OK;
+    SOSVO_REQUIRE(ctx, sosvo_lk_options_ok(ctx->lk), "LK settings out of range (sosvo_set_lk_options)");
+    SOSVO_LAUNCH(ctx, seq_copy_images_kernel, dim3(n, kCopyImageChunks, 2 * ctx->lk.levels), dim3(256), 0, ctx->stream, cp, src_list,
+                 dst_list, ws.img);
+    SOSVO_LAUNCH_CHECK(ctx);
+    return SOSVO_OK;
   }
 };
 struct RgbdSeq {
@@ -1053,10 +1202,12 @@ struct RgbdSeq {
   static StoreFields fields(const RgbdStore& s) {
     return {{(char*)s.m, (char*)s.d, (char*)s.X, (char*)s.b}, {8, 32, 24, 24}, s.M};
   }
-  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const RgbdFrontTmp& t, const RgbdStore& o,
+  static int32_t front_end(sosvo_ctx* ctx, const Cfg* cfg, int F, const Frames& in, const Ws& ws, int first_slot,
                            const int32_t* slot_of_frame) {
-    return run_rgbd_front_end(ctx, in.cam, cfg, F, in.bgr, in.depth, in.mask_bits, in.pattern, t, o, slot_of_frame);
+    return run_rgbd_front_end(ctx, in.cam, cfg, F, in.bgr, in.depth, in.mask_bits, in.pattern, ws.fe,
+                              ws.store.at(first_slot, cfg->frame_cap), slot_of_frame);
   }
+  static int32_t copy_images(sosvo_ctx*, const CopyPairs&, const int32_t*, const int32_t*, int32_t, const Ws&) { return SOSVO_OK; }
   static int32_t track(sosvo_ctx* ctx, const sosvo_rig*, const Cfg* cfg, int B, uint64_t seed, const Ws& ws, double* results,
                        const uint64_t* seeds) {
     return run_rgbd_tracking(ctx, cfg, B, seed, ws.store, ws.tt, results, seeds);
@@ -1097,8 +1248,7 @@ int32_t seq_front_end(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* c
                       "frames do not fit the window / the store", true, workspace, workspace_bytes, ws));
   if (slot_of_frame) STAGE(check_slot_table(ctx, fn, slot_of_frame, n_frames, slots));
   if (n_frames == 0) return SOSVO_OK;
-  if (slot_of_frame) return Fam::front_end(ctx, cfg, n_frames, in, ws.fe, ws.store, slot_of_frame);
-  return Fam::front_end(ctx, cfg, n_frames, in, ws.fe, ws.store.at(first_slot, cfg->frame_cap), nullptr);
+  return Fam::front_end(ctx, cfg, n_frames, in, ws, slot_of_frame ? 0 : first_slot, slot_of_frame);
 }
 
 // ..._track (seed_host == nullptr: pair i samples with seed + i) and ..._track_seeds (HOST list, `seed` unused): the slot
@@ -1144,7 +1294,8 @@ int32_t seq_copy_slot(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* c
   CopyPairs cp{};
   cp.src[0] = src;
   cp.dst[0] = dst;
-  return launch_copy(ctx, cp, nullptr, nullptr, 1, cfg->frame_cap, Fam::fields(ws.store));
+  STAGE(launch_copy(ctx, cp, nullptr, nullptr, 1, cfg->frame_cap, Fam::fields(ws.store)));
+  return Fam::copy_images(ctx, cp, nullptr, nullptr, 1, ws);
 }
 
 template <typename Fam>
@@ -1162,8 +1313,9 @@ int32_t seq_copy_slots(sosvo_ctx* ctx, const char* fn, const typename Fam::Cfg* 
     SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.ref_frame, src, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
     SOSVO_HIP(ctx, hipMemcpyAsync(ws.tt.cur_frame, dst, sizeof(int32_t) * n, hipMemcpyHostToDevice, ctx->stream));
   }
-  return launch_copy(ctx, cp, copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, n, cfg->frame_cap,
-                     Fam::fields(ws.store));
+  STAGE(launch_copy(ctx, cp, copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, n, cfg->frame_cap,
+                    Fam::fields(ws.store)));
+  return Fam::copy_images(ctx, cp, copied ? ws.tt.ref_frame : nullptr, copied ? ws.tt.cur_frame : nullptr, n, ws);
 }
 
 template <typename Fam>

@@ -85,6 +85,7 @@ class Context(object):
         if rc != 0:
             raise SosvoError("sosvo_create failed: %s" % _lib.STATUS_NAMES.get(rc, rc))
         self._h = h
+        self.lk_options = _lib.LKOptions()   # what the context tracks with under SOSVO_FLAG_LK_F2F (set_lk_options)
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -118,6 +119,14 @@ class Context(object):
         """sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): RANSAC scoring without its single-precision first tier (same counts;
         for A/B measurements and the cross-check of the two forms)."""
         self._call(self._lib.sosvo_set_hint, _lib.HINT_SCORE_FP64_ONLY, 1 if on else 0)
+
+    def set_lk_options(self, lk=None):
+        """sosvo_set_lk_options: the tracker's settings of the batch and sequence entry points under SOSVO_FLAG_LK_F2F (an
+        LKOptions, a dict of its fields, or None = the defaults).  They change results; a refused value leaves the previous
+        settings.  self.lk_options is what the context holds."""
+        lk = _lib.LKOptions.of(lk)
+        self._call(self._lib.sosvo_set_lk_options, ctypes.byref(_lib.LkOptionsStruct.of(lk)))
+        self.lk_options = lk
 
     def set_stream(self, stream):
         """Enqueue on `stream` (a torch.cuda.Stream) from now on, e.g. the capture stream of a HIP graph."""

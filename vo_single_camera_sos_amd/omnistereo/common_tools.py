@@ -30,6 +30,24 @@ def str2bool(v):
     return str(v).lower() in ("yes", "true", "t", "1")
 
 
+def add_f2f_tracker_arguments(parser):
+    """The demos' flags for where the frame-to-frame correspondences come from (run_VO's f2f_tracker / lk)."""
+    parser.add_argument("--f2f_tracker", default=None, choices=("match", "lk"),
+                        help="frame-to-frame correspondences from the descriptor matcher (match, the default) or by pyramidal "
+                             "Lucas-Kanade tracking of the reference frame's stereo points (lk), on the GPU")
+    parser.add_argument("--lk_half", default=None, type=int, help="with --f2f_tracker lk: the window half-size 2 .. 10; default: 10")
+    parser.add_argument("--lk_levels", default=None, type=int, help="with --f2f_tracker lk: pyramid levels 1 .. 4; default: 3")
+    parser.add_argument("--lk_max_iter", default=None, type=int, help="with --f2f_tracker lk: iterations per level 1 .. 30; default: 30")
+    parser.add_argument("--lk_fb_max", default=None, type=float,
+                        help="with --f2f_tracker lk: forward-backward check, the largest round-trip error in pixels; default: no check")
+
+
+def f2f_tracker_arguments(args):
+    """The parsed flags of add_f2f_tracker_arguments -> run_VO's f2f_tracker= / lk= (lk None: the tracker's defaults)."""
+    lk = {name: getattr(args, "lk_" + name) for name in ("half", "levels", "max_iter", "fb_max") if getattr(args, "lk_" + name) is not None}
+    return dict(f2f_tracker=args.f2f_tracker, lk=lk or None)
+
+
 def copy_only_attributes(objfrom, objto, exclude_names=()):
     """common_tools.py:154-159: every non-dunder member of objfrom is set on objto."""
     for n in dir(objfrom):

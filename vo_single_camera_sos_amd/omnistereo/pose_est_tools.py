@@ -230,6 +230,21 @@ class StereoPanoramicFrame(object):
         good = omnistereo_model.filter_panoramic_points_due_to_range(xyz0, min_3D_range=self.min_range,
                                                                      max_3D_range=self.max_range)
         self.num_valid_keypoints = int(np.count_nonzero(good))
+        # a tracker that tracks (set_f2f_tracker) follows this frame's points into the next frame's gray panoramas: they stay
+        # on the device, [2, rows, cols] u8 with the rows the front end computed (gray_rows: int32 [2, 2] or None = all)
+        self.gray_panoramas = self.gray_rows = None
+        if getattr(omnistereo_model, "lk_options", None) is not None:
+            fe = omnistereo_model._front_end(fm.feature_detection_method, fm.num_of_features, self.median_win_size)
+            self.gray_panoramas = fe.gray.clone()
+            # the rows the sequence engines' front end computes for this detector (GFT with the fused median: the reach of
+            # its masks and descriptors, else every row): the tracker clamps to them there, so it does here, although this
+            # front end has computed them all
+            if fe.method == "GFT" and fe.median_win_size in (3, 5, 11):
+                m, key = fe.model, (fe.edge, fe.cos_a, fe.sin_a)
+                cache = m.__dict__.setdefault("_gray_rows", {})
+                if key not in cache:
+                    cache[key] = fe.ctx.gray_rows_needed(m.mask_bits, m.nmask, fe.edge, m.pattern, fe.cos_a, fe.sin_a)
+                self.gray_rows = cache[key]
         self.bearing_vectors_top_stereo_triangulated = b1[good]
         self.bearing_vectors_bottom_stereo_triangulated = b2[good]
         self.pano_correspondences = PanoramicCorrespondences(
@@ -275,6 +290,8 @@ class TrackerSE3(object):
         self.ratio_for_motion = None
         # sub-pixel refinement of the detected keypoints (window half-size): off; see set_subpixel_refinement
         self.subpix_half = None
+        # Lucas-Kanade tracking in place of the frame-to-frame matcher (an LKOptions): off; see set_f2f_tracker
+        self.lk_options = None
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -365,6 +382,7 @@ class TrackerStereoSE3(TrackerSE3):
             percentage_good_matches=self.percentage_good_matches, num_of_features=self.num_features_detection_for_motion,
             use_radius_match=self.use_descriptor_radius_match_for_motion, cross_check=self.cross_check_for_motion,
             gated=self.gated_for_motion, gated_max_distance=self.gated_max_distance, ratio=self.ratio_for_motion)
+        om.lk_options = self.lk_options    # (the frames keep their gray panoramas on the device when the tracker tracks)
         self.omni_mask_extra_padding = 10
         shape = None if om.current_omni_img is None else om.current_omni_img.shape[:2]
         if shape is None:
@@ -384,6 +402,8 @@ class TrackerStereoSE3(TrackerSE3):
         self.inlier_tracked_correspondences_ratio = 0.
         if isinstance(current_frame, _DeviceFrame):
             return self._track_device_frame(reference_frame, current_frame)
+        if self.lk_options is not None:
+            return self._track_frame_lk(reference_frame, current_frame)
         ref, cur = reference_frame.pano_correspondences, current_frame.pano_correspondences
         (t_top, _, _), (q_top, _, _), _ = match_features_frame_to_frame(
             cam_model=self.omnistereo_model, train_kpts=ref.kpts_top, train_desc=ref.desc_top, query_kpts=cur.kpts_top,
@@ -420,6 +440,61 @@ class TrackerStereoSE3(TrackerSE3):
                                                             np.ones((len(inliers), 1))))
         return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
 
+    LK_FRAME_CAP = 4096     # the points of a frame the tracker follows: the sequence engines' frame_cap (_sos_engine_settings)
+
+    def _track_frame_lk(self, reference_frame, current_frame):
+        """track_frame with set_f2f_tracker(..., "lk"): the reference frame's stereo points m_top / m_bot are tracked into the
+        current frame's gray panoramas (Context.gray_pyramid / track_lk, two problems: top view, bottom view) and stacked by
+        Context.f2f_assemble_tracked -- the stages, the layout and the row range of the sequence engines' tracking step."""
+        import torch
+        from ..device import make_rig
+        om, o, ref = self.omnistereo_model, self.lk_options, reference_frame.pano_correspondences
+        ctx = om._context()
+        if reference_frame.gray_panoramas is None or current_frame.gray_panoramas is None:
+            raise RuntimeError("f2f_tracker=\"lk\": the frames were built before set_f2f_tracker and keep no gray panoramas")
+        dev = ctx.device
+        n = min(len(ref.m_top), self.LK_FRAME_CAP)
+        cap = max(n, 1)
+        # view-major images [top of the reference, top of the current frame, bottom ..., bottom ...]
+        gray = torch.stack([reference_frame.gray_panoramas[0], current_frame.gray_panoramas[0],
+                            reference_frame.gray_panoramas[1], current_frame.gray_panoramas[1]])
+        pts = np.zeros((2, cap, 2), np.float32)
+        pts[0, :n], pts[1, :n] = ref.m_top[:n, :2], ref.m_bot[:n, :2]
+        X = np.zeros((1, cap, 3))
+        X[0, :n] = ref.points_3D_coords_homo[:n, ..., :3].reshape(n, 3)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)    # noqa: E731
+        prev = to(pts)
+        pyr = ctx.gray_pyramid(gray, o.levels, row_range=reference_frame.gray_rows)
+        res = ctx.track_lk(pyr, i32([0, 2]), i32([1, 3]), prev, i32([n, n]), half=o.half, max_iter=o.max_iter, eps=o.eps,
+                           min_eig=o.min_eig, fb_max=o.fb_max)
+        top, bot = om.top_model, om.bot_model
+        geo = [(m.panorama.cols, m.panorama.rows, m.panorama.pixel_size, m.panorama.cyl_height_max) for m in (top, bot)]
+        rig = make_rig(geo[0], geo[1], top.F[:3, 0], bot.F[:3, 0], 0.0, 0.0, f2f_max_hdiff=self.max_horizontal_diff_f2f_matches)
+        frames = dict(m_top=prev[0:1], m_bot=prev[1:2], X=to(X), M=i32([n]))
+        nxt, st = res[0], res[1]
+        corr = ctx.f2f_assemble_tracked(rig, frames, i32([0]), nxt[0:1], nxt[1:2], st[0:1], st[1:2], 2 * cap)
+        ctx.synchronize()
+        num_initial_matches = int(corr["n"].cpu().numpy()[0])
+        if num_initial_matches < self.min_matches_to_track():
+            return False, "Cannot track on only %d point correspondences" % (num_initial_matches)
+        b_all = corr["f"][0, :num_initial_matches].cpu().numpy()
+        p_all = corr["p"][0, :num_initial_matches].cpu().numpy()
+        cam_all = corr["cam"][0, :num_initial_matches].cpu().numpy().astype(np.float64).reshape(-1, 1)
+        T_ransac, inliers = pyopengv.absolute_pose_noncentral_ransac(
+            b_all, cam_all, p_all, self.cam_offsets, self.cam_rotations, self.backprojection_score_threshold_3D_to_2D,
+            self.max_ransac_iterations_3D_to_2D)
+        self.indices_inliers_combined = inliers
+        self.num_tracked_correspondences = len(inliers)
+        self.inlier_tracked_correspondences_ratio = float(self.num_tracked_correspondences) / float(num_initial_matches)
+        T_nl = pyopengv.absolute_pose_noncentral_optimize_nonlinear(
+            b_all[inliers], cam_all[inliers], p_all[inliers], self.cam_offsets, self.cam_rotations, T_ransac[:3, 3],
+            T_ransac[:3, :3])
+        self._keep_pose(current_frame, T_nl)
+        if self.show_3D_points:
+            self.xyz_homo_points_wrt_C_inliers = np.hstack((p_all[inliers] * current_frame.conversion_factor_length_to_m,
+                                                            np.ones((len(inliers), 1))))
+        return True, "tracking used %d inlier point correspondences" % (self.num_tracked_correspondences)
 
 
 class _DeviceFrame(object):
@@ -581,6 +656,25 @@ def set_subpixel_refinement(tracker, subpix, half=5):
     tracker.subpix_half = value
 
 
+def set_f2f_tracker(tracker, f2f_tracker, lk=None):
+    """Where the frame-to-frame correspondences come from.  f2f_tracker: None = leave the tracker's own setting (and lk must be
+    None), "match" = the descriptor matcher (the reference's way), "lk" = pyramidal Lucas-Kanade tracking of the reference
+    frame's stereo points into the current frame's gray panoramas (Context.track_lk; cv2.calcOpticalFlowPyrLK,
+    camera_models.py:3070); lk: its settings, None / an LKOptions / a dict of its fields.  The camera model carries the setting
+    to the frames (they keep their gray panoramas on the device), so the per-frame mirror path and the engine chosen from the
+    tracker's settings both follow.  An RGB-D tracker refuses "lk"; so does a tracker whose frame-to-frame matcher has an
+    option set (cross_check, gated_matching, ratio_test): the tracker replaces that matcher."""
+    from .._lib import f2f_tracker_options
+    if f2f_tracker is None:
+        if lk is not None:
+            raise ValueError("lk settings without f2f_tracker=\"lk\"")
+        return
+    cm = tracker.camera_model
+    opts = MatchOptions.from_matchers(None, getattr(cm, "feature_matcher_for_motion", None))
+    value = f2f_tracker_options(f2f_tracker, lk, opts, rgbd=_is_rgbd_model(cm))
+    tracker.lk_options = cm.lk_options = value
+
+
 def _has_batched_counterpart(tracker, fm):
     """Whether the sequence engines run what `tracker` is set to; fm: the matcher the family's frames detect with (None:
     none yet)."""
@@ -623,11 +717,13 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           opts, getattr(fm, "subpix_half", None))
+           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None))
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
                   subpix=getattr(fm, "subpix_half", None), **opts._asdict())
+    if getattr(tracker, "lk_options", None) is not None:
+        kwargs.update(f2f_tracker="lk", lk=tracker.lk_options)
     return (model, rig), kwargs, key
 
 
@@ -1180,7 +1276,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
            cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-           subpix_refine=None, subpix_half=None):
+           subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -1212,7 +1308,12 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     subpix_refine: the detected keypoints move to their sub-pixel positions before the static-stereo matching (the
     descriptors stay those of the detector's positions); None = the tracker's own setting (off), True / False.
     subpix_half: the window half-size 2 .. 5, None = 5 (see set_subpixel_refinement).  Sequence mode and the mirror path
-    follow alike; an RGB-D camera model refuses True."""
+    follow alike; an RGB-D camera model refuses True.
+
+    f2f_tracker: None = the tracker's own setting ("match"), "match" = the frame-to-frame correspondences come from the
+    descriptor matcher, "lk" = the reference frame's stereo points are tracked into the current frame's gray panoramas by
+    pyramidal Lucas-Kanade (see set_f2f_tracker); lk: its settings, None / an LKOptions / a dict of its fields.  Sequence mode
+    and the mirror path follow alike; an RGB-D camera model refuses "lk", and so does a frame-to-frame matcher option."""
     from .common_cv import get_images
     if visualizer_3D_VO is not None:
         raise NotImplementedError("3-D visualisation is not built: pass visualizer_3D_VO=None")
@@ -1241,6 +1342,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         set_gated_matching(tracker, gated_matching, gated_max_distance)   # (... and their search under the gates)
         set_ratio_test(tracker, ratio_test, ratio)                        # (... and their ratio rule)
         set_subpixel_refinement(tracker, subpix_refine, subpix_half)      # (... and the frames' sub-pixel keypoints)
+        set_f2f_tracker(tracker, f2f_tracker, lk)                         # (... and tracking in place of the f2f matcher)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1354,7 +1456,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
                 results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
                 gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                subpix_refine=None, subpix_half=None):
+                subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1377,7 +1479,8 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   _keyframe_thresholds=(0.05, 0.50, np.deg2rad(5.0), np.deg2rad(60.0)), frame_window=frame_window,
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
-                  subpix_refine=subpix_refine, subpix_half=subpix_half)
+                  subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
+                   lk=lk)
 
 
 def _est_poses_filename(timestamped):
@@ -1419,14 +1522,15 @@ def _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_in
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
                    gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
-                   subpix_refine=subpix_refine, subpix_half=subpix_half)
+                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
+                   lk=lk)
     est_poses_filename = _est_poses_filename(timestamped=not use_multithreads_for_VO)
     cam_working_thread.start()
     if not getattr(cam_working_thread, "lockstep", False):
@@ -1448,14 +1552,15 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
               last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
               gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-              subpix_refine=None, subpix_half=None):
+              subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
-                   subpix_refine=subpix_refine, subpix_half=subpix_half)
+                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
+                   lk=lk)
     gt_poses_filename, vo_frame_indices = _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index,
                                                                           last_image_index, step_for_scene_images)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
@@ -1480,7 +1585,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
                 _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None,
-                ratio=None, subpix_refine=None, subpix_half=None):
+                ratio=None, subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1533,7 +1638,8 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
     S = _lane_limit(len(sequences), lanes, W)
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
-                   subpix_refine=subpix_refine, subpix_half=subpix_half)
+                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
+                   lk=lk)
     shared = dict(engine=None, key=None)
     guard, exited = threading.Lock(), set()
 
@@ -1609,7 +1715,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
                    frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
                    gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1617,7 +1723,8 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
         raise NotImplementedError("3-D visualisation is not built: visualize_VO must be False")
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
-                   subpix_refine=subpix_refine, subpix_half=subpix_half)
+                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
+                   lk=lk)
     sequences = []
     for sc in scenes:
         gt_poses_filename, indices = _scene_ground_truth_and_indices(sc["scene_path"], int(sc["num_scene_images"]), first_image_index,

@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import LKOptions, MatchOptions, subpix_flags, subpix_half
+from ._lib import LKOptions, MatchOptions, f2f_tracker_options, subpix_flags, subpix_half
 from .device import Context, make_rig
 
 
@@ -236,13 +236,15 @@ class OverlappedFramePairs(object):
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
-        RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray."""
+        RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray.
+        f2f_tracker / lk: as FramePairPipeline ("lk": every part's pipeline tracks with these settings)."""
         from .frontend import DeviceImageModel, ImageFrontEnd
         from .parallel import shard_range
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
+        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
@@ -266,7 +268,8 @@ class OverlappedFramePairs(object):
                                      median_win_size=median_win_size, subpix=subpix)
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
-                                           ransac_solver=ransac_solver, **opts._asdict())
+                                           ransac_solver=ransac_solver, f2f_tracker=f2f_tracker, lk=self.lk,
+                                           **opts._asdict())
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -397,10 +400,11 @@ class OverlappedFramePairs(object):
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
               adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
               gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
-              subpix=None):
+              subpix=None, lk=None):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
-    any ransac_solver but "GP3P" is P3P."""
+    any ransac_solver but "GP3P" is P3P.  lk: None, or the LKOptions of an engine that tracks (SOSVO_FLAG_LK_F2F; the
+    settings themselves belong to the context, see use_lk_options)."""
     from . import _lib, orb_pattern
     from .frontend import default_kp_cap
     detector = _lib.detector_code(detection_method)
@@ -419,7 +423,16 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_flags |= MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                                    ratio_f2f, ratio).flags()
     c.ransac_flags |= subpix_flags(subpix)
+    if lk is not None:
+        c.ransac_flags |= _lib.FLAG_LK_F2F
     return c
+
+
+def use_lk_options(ctx, lk):
+    """Before a call of an engine that tracks with the settings `lk` (None: it matches, nothing to do): contexts are shared
+    between engines, so the context gets them whenever they differ from what it was last given."""
+    if lk is not None and getattr(ctx, "lk_options", None) != lk:
+        ctx.set_lk_options(lk)
 
 
 class FramePairBatch(object):
@@ -430,19 +443,22 @@ class FramePairBatch(object):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap).
-        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement (SOSVO_FLAG_SUBPIX)."""
+        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement (SOSVO_FLAG_SUBPIX).
+        f2f_tracker / lk: as FramePairPipeline -- "lk": SOSVO_FLAG_LK_F2F, the reference frames' points are tracked into the
+        current frames' gray panoramas; a frame-to-frame matcher option with it raises ValueError."""
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
+        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
         self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                  median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                  max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                 detection_method=detection_method, subpix=subpix, **opts._asdict())
+                                 detection_method=detection_method, subpix=subpix, lk=self.lk, **opts._asdict())
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -460,6 +476,7 @@ class FramePairBatch(object):
     def step(self):
         """-> results [B,16] f64 (asynchronous)."""
         m = self.model
+        use_lk_options(self.ctx, self.lk)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out, n_streams=self.n_streams)
 
@@ -468,6 +485,7 @@ class FramePairBatch(object):
         the library's internal streams.  Pass alternating `results` buffers while something still reads the previous
         step's records; call join() before reading records on the context's stream."""
         m = self.model
+        use_lk_options(self.ctx, self.lk)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out if results is None else results, n_streams=self.n_streams,
                                          join=self.n_streams <= 1)
@@ -569,12 +587,14 @@ class _SequenceFamily(object):
 class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
-    def __init__(self, ctx, model, rig, frames, slots, gather, opts, **settings):
-        """opts: a MatchOptions; settings: batch_cfg's tracker settings (num_of_features ... detection_method) but the seed."""
+    def __init__(self, ctx, model, rig, frames, slots, gather, opts, f2f_tracker="match", lk=None, **settings):
+        """opts: a MatchOptions; f2f_tracker / lk: as FramePairPipeline's; settings: batch_cfg's tracker settings
+        (num_of_features ... detection_method) but the seed."""
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
-        self.cfg = batch_cfg(model, frames, seed=0, **settings, **opts._asdict())
+        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
+        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, **settings, **opts._asdict())
         self.method = str(settings["detection_method"]).upper()
         if str(settings["ransac_solver"]).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -585,6 +605,12 @@ class _OmniFamily(_SequenceFamily):
     def consts(self):
         m = self.model
         return m.unwrap_table, m.mask_bits, m.pattern
+
+    def _call(self, name, heads, *args):
+        """Engines that share a context may track with different settings: every device call of a tracking family runs under
+        its own (the front end builds, the copies move and the tracker reads the pyramid levels they name)."""
+        use_lk_options(self.ctx, self.lk)
+        return super()._call(name, heads, *args)
 
     @staticmethod
     def _planes(images):
@@ -868,17 +894,19 @@ class SequenceEngine(_SequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
         cross_check_stereo / cross_check_f2f: mutual matches only in the static-stereo / the frame-to-frame matcher.
         gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline.
-        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement, as FramePairBatch."""
+        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement, as FramePairBatch.
+        f2f_tracker / lk: "lk" = Lucas-Kanade tracking in place of the frame-to-frame matcher, as FramePairBatch; the store
+        then keeps every frame's gray panoramas and their pyramid."""
         self._init_windows(window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts,
+        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts, f2f_tracker, lk,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1114,8 +1142,9 @@ class RGBDPairBatch(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
         from . import orb_pattern
+        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
@@ -1162,7 +1191,8 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
+        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         self._init_windows(window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, opts, mask,
@@ -1497,11 +1527,11 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
         self._init_lanes(lanes, window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts,
+        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts, f2f_tracker, lk,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1515,7 +1545,8 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
+        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         self._init_lanes(lanes, window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, opts, mask,
