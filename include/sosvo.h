@@ -193,7 +193,8 @@ int32_t sosvo_gray_rows_needed(sosvo_ctx* ctx, const uint32_t* mask_bits, int32_
  *   of cap alone; the strongest in the order of the sort: descending response, higher address first among equal
  *   responses; when max_corners or cap is reached inside them the result is the full one); bit 1 = mask too large for the on-chip grid (3584 / 15872 cells of
  *   minDistance^2 pixels) and more than 1024 corners wanted, or more than 1024 corners were the THIRD of their grid
- *   cell (possible from minDistance ~30 px on; up to 1024 of them are kept exactly in an overflow list). */
+ *   cell (possible from minDistance ~30 px on; up to 1024 of them are kept exactly in an overflow list).
+ * rows, cols <= 65535 (and rows * cols < 2^28): the candidates travel as y << 16 | x. */
 int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask_bits, int32_t nimg,
                          int32_t images_per_maskset, int32_t rows, int32_t cols, int32_t nmask,
                          double quality, double min_distance, int32_t max_corners, int32_t cap,

@@ -10,7 +10,7 @@
 //            map: the kernel keeps three rows in registers, tests the 3x3 local maximum there and emits the positive
 //            local maxima as compact records (value, pixel) into a region of its own per wave;
 //   select   one workgroup per problem: the records of the waves that cover the mask's bounding box, thresholded ->
-//            sort keys (ordered(value) << 32 | pixel index) in LDS, rank sort (descending value,
+//            sort keys (ordered(value) << 32 | y << 16 | x) in LDS, rank sort (descending value,
 //            higher address first), then the greedy minimum-distance pass on an LDS cell grid by the first wave,
 //            64 candidates per step with an exact replay of the sequential acceptance rule;
 //   blur     7x7 sigma=2 Gaussian in 8.8 fixed point (separable, LDS tile);
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kThreads) void min_eigen_kernel(const uint8_t* __re
       const unsigned long long bal = __ballot(is_cand);
       if (bal) {  // uniform
         const int pos = wpos + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-        if (is_cand && pos < wcap) region[pos] = make_uint2(__float_as_uint(ev), (uint32_t)(f * cols + xc));
+        if (is_cand && pos < wcap) region[pos] = make_uint2(__float_as_uint(ev), ((uint32_t)f << 16) | (uint32_t)xc);
         wpos += __popcll(bal);
       }
     }
@@ -311,12 +311,57 @@ __device__ __forceinline__ uint32_t dist2_packed(uint32_t a, uint32_t b) {
   return (uint32_t)__builtin_amdgcn_sdot2(d, d, 0, false);
 }
 
+// The integer form of the greedy pass's cell grid, shared by its spread and its one-wave form: a one-cell border around the
+// cells of the mask's bounding box (no bounds tests on the nine neighbours), two slots of packed coordinates per cell, empty
+// slots = kGridEmpty, a third point of a cell in the overflow list.  Holds when min_distance >= 1, cell <= 2048 and rows,
+// cols <= 32768: squared distances below 2^31, thresholds below 2^24, so the integer comparisons are the float ones exactly.
+constexpr uint32_t kGridEmpty = 0xFFFFFFFFu;
+struct gft_igrid {
+  uint32_t thr_i;  // integer d2 < md2  <=>  d2 < ceil(md2)
+  uint32_t magic;  // v / cell = mulhi(v, magic) for v < 2^16 (cell > 1)
+  int cell, cx0, cy0, gwp;
+  __device__ __forceinline__ gft_igrid(float md2, int cell_, int cx0_, int cy0_, int gwp_)
+      : thr_i((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ceilf(md2))),  // (uniform, but out of the VALU: to SGPRs)
+        magic((uint32_t)__builtin_amdgcn_readfirstlane((int)(cell_ > 1 ? 0xFFFFFFFFu / (uint32_t)cell_ + 1u : 0u))), cell(cell_),
+        cx0(cx0_), cy0(cy0_), gwp(gwp_) {}
+  // first slot of the cell of a candidate (every candidate of a mask lies inside the mask's bounding box); an idle lane
+  // gets cell (1, 1), which exists
+  __device__ __forceinline__ int cell_index(uint32_t xy, bool active) const {
+    const uint32_t x = xy & 0xFFFFu, y = xy >> 16;
+    const int xc = active ? (int)(cell > 1 ? __umulhi(x, magic) : x) - cx0 + 1 : 1;
+    const int yc = active ? (int)(cell > 1 ? __umulhi(y, magic) : y) - cy0 + 1 : 1;
+    return (yc * gwp + xc) * 2;
+  }
+  // does a point of the neighbour cell (dxc, dyc in -1 .. 1 around cidx) lie closer than min_distance to xy?
+  __device__ __forceinline__ uint32_t cell_hit(const uint32_t* grid, int cidx, int dxc, int dyc, uint32_t xy) const {
+    const uint2 q2 = *reinterpret_cast<const uint2*>(&grid[cidx + dyc * gwp * 2 + dxc * 2]);
+    return ((uint32_t)(q2.x != kGridEmpty) & (uint32_t)(dist2_packed(xy, q2.x) < thr_i)) |
+           ((uint32_t)(q2.y != kGridEmpty) & (uint32_t)(dist2_packed(xy, q2.y) < thr_i));
+  }
+  __device__ __forceinline__ bool near(uint32_t a, uint32_t b) const { return dist2_packed(a, b) < thr_i; }
+  // an accepted point enters its cell.  A cell of round(minDistance) pixels holds two points -- or, from a distance of ~30
+  // pixels on, three in a triangle: the third goes to the overflow list every candidate is tested against (an overflow of
+  // that list is reported once, after the loop, from s_ovf)
+  __device__ __forceinline__ void insert(uint32_t* grid, int cidx, uint32_t xy, int* s_ovf, uint32_t* acc_list, int limit_list) const {
+    if (atomicCAS(&grid[cidx], kGridEmpty, xy) != kGridEmpty && atomicCAS(&grid[cidx + 1], kGridEmpty, xy) != kGridEmpty) {
+      const int o = atomicAdd(s_ovf, 1);
+      if (o < limit_list) acc_list[o] = xy;
+    }
+  }
+};
+
+// The candidate records carry their pixel as y << 16 | x (rows, cols <= 65535), and so do the sort keys (ordered response
+// << 32 | y << 16 | x).  For x < cols <= 65535 the order of (y << 16 | x) is the lexicographic order of (y, x), which is the
+// order of the linear address y * cols + x: among equal responses "higher address first" picks the same candidate, the
+// keys stay unique, and the CAND largest keys of the overflow path are the same set -- every output is what the linear keys
+// gave.  The mask word of a record is one multiply-add away (y * cols + x); nothing divides by cols any more.
+//
 // The candidate regions of one problem (what phase 1 of gft_select_kernel walks), for the overflow path below.
 struct gft_regions {
   const uint2* cand;
   const uint32_t* wcnt;
   const uint32_t* mb;
-  int img, m, strips, nchunks, wcap, s0, c0, ns, R;
+  int img, m, cols, strips, nchunks, wcap, s0, c0, ns, R;
   float thr;
 };
 
@@ -338,7 +383,7 @@ __device__ __forceinline__ void gft_walk_keys(const gft_regions& g, int* s_regio
       const uint2* region = g.cand + (size_t)((g.img * g.nchunks + c) * g.strips + sidx) * g.wcap;
       for (int i = lane; i < have; i += 64) {
         const uint2 r = region[i];
-        if (__uint_as_float(r.x) > g.thr && ((g.mb[r.y] >> g.m) & 1u))
+        if (__uint_as_float(r.x) > g.thr && ((g.mb[(r.y >> 16) * (uint32_t)g.cols + (r.y & 0xFFFFu)] >> g.m) & 1u))
           f(((unsigned long long)sosvo_float_ordered(__uint_as_float(r.x)) << 32) | r.y);
       }
     }
@@ -347,7 +392,7 @@ __device__ __forceinline__ void gft_walk_keys(const gft_regions& g, int* s_regio
 }
 
 // More candidates than the selection sorts (total > CAND, uniform): the kept set is the CAND LARGEST keys.  The keys
-// (ordered response << 32 | pixel) are unique, so that set -- and with it kp, n and their order -- depends on the image, the
+// (ordered response << 32 | y << 16 | x) are unique, so that set -- and with it kp, n and their order -- depends on the image, the
 // mask and the parameters only, and the greedy pass on it gives a prefix of the unlimited result.  A radix select finds the
 // CAND-th largest key: one more walk over the regions per 11-bit digit with a histogram in the key LDS (which holds
 // nothing worth keeping at this point), from the top digit down, until every key left under the digits found so far is
@@ -488,7 +533,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
           bool keep = false;
           if (i < have) {
             r = region[i];
-            keep = __uint_as_float(r.x) > thr && ((mb[r.y] >> m) & 1u);
+            keep = __uint_as_float(r.x) > thr && ((mb[(r.y >> 16) * (uint32_t)cols + (r.y & 0xFFFFu)] >> m) & 1u);
           }
           const unsigned long long km = __ballot(keep);
           if (km) {  // uniform
@@ -514,7 +559,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
     if (!fits) return;
   }
   if (__builtin_expect(total > CAND, 0)) {  // uniform, and rare: the slots above went to whichever waves came first -- gather the CAND largest keys
-    const gft_regions g = {cand, wcnt, mask_bits + (size_t)(img / images_per_maskset) * rows * cols, img, m, strips, nchunks, wcap,
+    const gft_regions g = {cand, wcnt, mask_bits + (size_t)(img / images_per_maskset) * rows * cols, img, m, cols, strips, nchunks, wcap,
                            bx0 / kEigStripW, by0 / chunk_rows, bx1 / kEigStripW - bx0 / kEigStripW + 1,
                            (by1 / chunk_rows - by0 / chunk_rows + 1) * (bx1 / kEigStripW - bx0 / kEigStripW + 1),
                            (float)((double)sosvo_ordered_float(st[0]) * quality)};
@@ -540,12 +585,8 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
       __syncthreads();
     }
   }
-  // candidates leave as packed (y << 16 | x), in order
-  for (int i = tid; i < n; i += NT) {
-    const uint32_t pix = (uint32_t)keys[i];
-    const uint32_t y = pix / (uint32_t)cols;
-    sorted[i] = (y << 16) | (pix - y * (uint32_t)cols);
-  }
+  // candidates leave as packed (y << 16 | x), in order: the low word of the key as it stands
+  for (int i = tid; i < n; i += NT) sorted[i] = (uint32_t)keys[i];
   int stt = (total > CAND || s_overflow) ? 1 : 0;
   const int cx0 = bx0 / cell, cy0 = by0 / cell;
   const int gw = bw > 0 ? bx1 / cell - cx0 + 1 : 0, gh = bh > 0 ? by1 / cell - cy0 + 1 : 0;
@@ -555,16 +596,16 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   const bool spaced = min_distance >= 1.0f;
   int limit = cap;
   if (max_corners > 0 && max_corners < limit) limit = max_corners;
-  // The usual case runs on integers (squared distances below 2^31, thresholds below 2^24: the comparisons are the float
-  // ones exactly) with a one-cell border around the grid, and on ALL waves of the workgroup -- see below.
-  constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+  // The usual case runs on integers (gft_igrid: the comparisons are the float ones exactly) with a one-cell border around
+  // the grid -- on ALL waves of the workgroup (`fast`, see below) or on the first one.
   const int gwp = gw + 2;
+  const bool igrid = spaced && n > 0 && cell <= 2048 && rows <= 32768 && cols <= 32768 && gwp * (gh + 2) <= kSelGridCells;  // uniform
   // (workgroups of eight waves and more -- launches of few problems, where the pass is latency: the C2 batch of 4096 problems
   // keeps the one-wave form, which issues fewer instructions in total: + 0.35 % on the issue-bound step, measured)
-  const bool fast = NT > 256 && spaced && n > 0 && cell <= 2048 && rows <= 32768 && cols <= 32768 && gwp * (gh + 2) <= kSelGridCells;  // uniform
+  const bool fast = NT > 256 && igrid;
   __syncthreads();  // keys are dead from here on; sorted[] is visible to the whole workgroup
-  if (fast) {
-    for (int i = tid; i < gwp * (gh + 2) * 2; i += NT) grid[i] = kEmpty;
+  if (igrid) {
+    for (int i = tid; i < gwp * (gh + 2) * 2; i += NT) grid[i] = kGridEmpty;
   } else {
     for (int i = tid; i < (use_grid ? gw * gh * 2 : 0); i += NT) grid[i] = 0u;
   }
@@ -580,8 +621,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   // accepted point: a dependent chain of ~10 instructions of a wave that runs alone, 90 ns per point.
   if (fast) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const uint32_t thr_i = (uint32_t)ceilf(md2);  // integer d2 < md2  <=>  d2 < ceil(md2)
-    const uint32_t magic = cell > 1 ? 0xFFFFFFFFu / (uint32_t)cell + 1u : 0u;  // v / cell = mulhi(v, magic) for v < 2^16
+    const gft_igrid ig(md2, cell, cx0, cy0, gwp);
     int accepted = 0;                                 // uniform over the workgroup
     uint32_t xy_next = lane < n ? sorted[lane] : 0u;  // one coalesced read per 64 candidates, requested a round ahead
     for (int k0 = 0; k0 < n && accepted < limit; k0 += 64) {
@@ -590,22 +630,16 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
       const uint32_t xy = xy_next;
       xy_next = k0 + 64 + lane < n ? sorted[k0 + 64 + lane] : 0u;
       const int y = (int)(xy >> 16), x = (int)(xy & 0xFFFFu);
-      // cell in the bordered grid (every candidate of this mask lies inside the mask's bounding box)
-      const int xc = active ? (int)(cell > 1 ? __umulhi((uint32_t)x, magic) : (uint32_t)x) - cx0 + 1 : 1;
-      const int yc = active ? (int)(cell > 1 ? __umulhi((uint32_t)y, magic) : (uint32_t)y) - cy0 + 1 : 1;
-      const int cidx = (yc * gwp + xc) * 2;
+      const int cidx = ig.cell_index(xy, active);  // in the bordered grid
       // (i) + (ii): 9 cell tests and kend matrix rows are 9 + kend work items dealt round-robin over the waves (a lone wave
       // issues an instruction every 5+ cycles and waits for every dependent one: the round is latency, so it is spread)
       constexpr int NWV = NT / 64;
       for (int c9 = wave; c9 < 9; c9 += NWV) {  // uniform per wave
-        const uint2 q2 = *reinterpret_cast<const uint2*>(&grid[cidx + (c9 / 3 - 1) * gwp * 2 + (c9 % 3 - 1) * 2]);
-        const uint32_t hit = ((uint32_t)(q2.x != kEmpty) & (uint32_t)(dist2_packed(xy, q2.x) < thr_i)) |
-                             ((uint32_t)(q2.y != kEmpty) & (uint32_t)(dist2_packed(xy, q2.y) < thr_i));
-        const unsigned long long hb = __ballot(active && hit != 0u);  // conflict with a point accepted in an earlier round
+        const unsigned long long hb = __ballot(active && ig.cell_hit(grid, cidx, c9 % 3 - 1, c9 / 3 - 1, xy) != 0u);  // conflict with a point accepted in an earlier round
         if (hb && lane == 0) atomicOr(&s_prior, hb);
       }
       for (int a = wave, novf = min(s_ovf, limit_list); a < novf; a += NWV) {  // (normally empty) uniform per wave
-        const unsigned long long hb = __ballot(active && dist2_packed(xy, acc_list[a]) < thr_i);
+        const unsigned long long hb = __ballot(active && ig.near(xy, acc_list[a]));
         if (hb && lane == 0) atomicOr(&s_prior, hb);
       }
       {
@@ -618,7 +652,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int j = min(jb + u * NWV, 63);  // (rows beyond kend: computed, never stored)
-            const unsigned long long row = __ballot(active && dist2_packed(xy, (uint32_t)__builtin_amdgcn_readlane((int)xy, j)) < thr_i);
+            const unsigned long long row = __ballot(active && ig.near(xy, (uint32_t)__builtin_amdgcn_readlane((int)xy, j)));
             const bool here = lane == t + u;
             glo = here ? (uint32_t)row : glo;
             ghi = here ? (uint32_t)(row >> 32) : ghi;
@@ -652,12 +686,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
           const int pos = accepted + __popcll(acc & ((1ULL << lane) - 1ULL));
           kp[((size_t)p * cap + pos) * 2] = (float)x;
           kp[((size_t)p * cap + pos) * 2 + 1] = (float)y;
-          // a cell of round(minDistance) pixels holds two points -- or, from a distance of ~30 pixels on, three in a
-          // triangle: the third goes to the overflow list every candidate is tested against
-          if (atomicCAS(&grid[cidx], kEmpty, xy) != kEmpty && atomicCAS(&grid[cidx + 1], kEmpty, xy) != kEmpty) {
-            const int o = atomicAdd(&s_ovf, 1);
-            if (o < limit_list) acc_list[o] = xy;
-          }
+          ig.insert(grid, cidx, xy, &s_ovf, acc_list, limit_list);
         }
         if (lane == 0) {
           s_accepted = accepted + __popcll(acc);
@@ -668,6 +697,48 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
       accepted = s_accepted;
     }
     if (s_ovf > limit_list) stt |= 2;
+  } else if (NT <= 256 && igrid) {
+    // One-wave form on the integer grid (workgroups of four waves: launches of more than 1024 problems).  The control flow is
+    // that of the float form below -- which candidate is accepted when is the sequential rule, replayed point by point --
+    // with the spread form's arithmetic: nine unconditional cell reads, one v_readlane and one packed distance per accepted
+    // point, no division, no bounds test, no conversion.
+    if (tid < 64) {
+      const int lane = tid;
+      const gft_igrid ig(md2, cell, cx0, cy0, gwp);
+      int accepted = 0;
+      uint32_t xy_next = lane < n ? sorted[lane] : 0u;  // one coalesced read per 64 candidates, requested a round ahead
+      for (int k0 = 0; k0 < n && accepted < limit; k0 += 64) {
+        const int kend = min(64, n - k0);
+        const bool active = lane < kend;
+        const uint32_t xy = xy_next;
+        xy_next = k0 + 64 + lane < n ? sorted[k0 + 64 + lane] : 0u;
+        const int cidx = ig.cell_index(xy, active);
+        uint32_t prior = 0u;  // conflict with a point accepted in an earlier round
+#pragma unroll 1
+        for (int dyc = -1; dyc <= 1; ++dyc)  // a row of three cells at a time: six slots in flight, not eighteen (registers)
+#pragma unroll
+          for (int dxc = -1; dxc <= 1; ++dxc) prior |= ig.cell_hit(grid, cidx, dxc, dyc, xy);
+        for (int a = 0, novf = min(s_ovf, limit_list); a < novf; ++a) prior |= (uint32_t)ig.near(xy, acc_list[a]);  // (normally none)
+        unsigned long long alive = __ballot(active && prior == 0u);
+        unsigned long long acc = 0ULL;
+        int room = limit - accepted;
+        while (alive && room > 0) {
+          const int j = __ffsll((long long)alive) - 1;
+          alive &= alive - 1ULL;
+          acc |= 1ULL << j;
+          room--;
+          alive &= ~__ballot(ig.near(xy, (uint32_t)__builtin_amdgcn_readlane((int)xy, j)));
+        }
+        if ((acc >> lane) & 1ULL) {
+          const int pos = accepted + __popcll(acc & ((1ULL << lane) - 1ULL));
+          kp[((size_t)p * cap + pos) * 2] = (float)(xy & 0xFFFFu);
+          kp[((size_t)p * cap + pos) * 2 + 1] = (float)(xy >> 16);
+          ig.insert(grid, cidx, xy, &s_ovf, acc_list, limit_list);
+        }
+        accepted += __popcll(acc);
+      }
+      if (lane == 0) s_accepted = accepted;
+    }
   } else
   if (tid < 64) {  // one-wave form (float distances; the accepted points in a list when the grid does not fit)
     const int lane = tid;
@@ -843,46 +914,83 @@ __global__ __launch_bounds__(kThreads) void gauss7_kernel(const uint8_t* __restr
 constexpr int kPatchMaxR = 23, kPatchRows = 48, kPatchStride = 64;
 constexpr int kDescRegionBytesGft = 24 * 1024;
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+
+// The rotated BRIEF pattern depends on (pattern, cos_a, sin_a) only: one workgroup per CALL writes it to the call's
+// workspace, every problem's workgroup reads it.  pt[t] is test t's two points in pixels, rounded to nearest, each as
+// dy << 16 | (dx & 0xFFFF) (|dx|, |dy| <= 181: int8 coordinates times sqrt 2); R = max(|dx|, |dy|) over all of them; poff
+// the points' byte offsets in a per-keypoint LDS patch (origin R before the keypoint, rows 4 * pstride bytes apart, pstride a
+// function of R), zero when R is beyond the patches.  (Per call and in stream order, never kept across calls: the caller
+// owns `pattern` and may rewrite it in place.)
+__host__ __device__ __forceinline__ int orb_patch_stride_dw(int R) { return ((2 * R + 1 + 3) >> 2) | 1; }  // row pitch in dwords, odd
+struct orb_pattern_table {
+  int2 pt[256];
+  int R, pad;
+  uint16_t poff[512];
+};
+__global__ __launch_bounds__(256) void orb_pattern_table_kernel(const int8_t* __restrict__ pattern, float cos_a, float sin_a,
+                                                                orb_pattern_table* __restrict__ tab) {
+  __shared__ int s_R;
+  const int t = threadIdx.x;
+  if (t == 0) s_R = 0;
+  __syncthreads();
+  int d[4];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const float px = (float)pattern[4 * t + 2 * e], py = (float)pattern[4 * t + 2 * e + 1];
+    const float xr = (px * cos_a) - (py * sin_a), yr = (px * sin_a) + (py * cos_a);
+    d[2 * e] = __float2int_rn(xr);
+    d[2 * e + 1] = __float2int_rn(yr);
+  }
+  tab->pt[t] = make_int2((int)(((uint32_t)d[1] << 16) | ((uint32_t)d[0] & 0xFFFFu)), (int)(((uint32_t)d[3] << 16) | ((uint32_t)d[2] & 0xFFFFu)));
+  atomicMax(&s_R, max(max(abs(d[0]), abs(d[1])), max(abs(d[2]), abs(d[3]))));
+  __syncthreads();
+  const int R = s_R;
+  if (t == 0) tab->R = R;
+  const int pitch = R <= kPatchMaxR ? 4 * orb_patch_stride_dw(R) : 0;
+  tab->poff[2 * t] = (uint16_t)(R <= kPatchMaxR ? (d[1] + R) * pitch + (d[0] + R) : 0);
+  tab->poff[2 * t + 1] = (uint16_t)(R <= kPatchMaxR ? (d[3] + R) * pitch + (d[2] + R) : 0);
+}
+
 // (NT threads: a problem's keypoints are shared by NT / 64 waves, one keypoint per wave and step -- 256 for the C2 batch of
 // 4096 problems, 512 when a launch has few problems, 1024 for the whole-image problems of up to 4096 keypoints)
 template <int NT>
 __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restrict__ blurred, int rows, int cols,
                                                                 int nmask, int cap, float* __restrict__ kp,
-                                                                int32_t* __restrict__ n_io, float cos_a, float sin_a,
-                                                                const int8_t* __restrict__ pattern, int edge,
+                                                                int32_t* __restrict__ n_io, const orb_pattern_table* __restrict__ ptab, int edge,
                                                                 uint8_t* __restrict__ desc, int nimg_total,
                                                                 const int32_t* __restrict__ row_range, int imgs_per_range) {
   SOSVO_LATENCY_BOUND_PRIO();
   extern __shared__ float lds_kp[];  // [cap][2] compacted keypoints
-  __shared__ int off[512];
-  __shared__ uint16_t poff[512];
   // one LDS area, two uses (NT = 256, the batch of (image, mask) problems): the REGION of the blurred image under all of the
   // problem's keypoints (below), or the waves' per-keypoint patches; the larger workgroups keep the patches only
   constexpr int kPatchWords = (NT / 64) * (kPatchRows * kPatchStride / 4);
   constexpr int kRegionWords = NT == 256 ? kDescRegionBytesGft / 4 : 0;
   __shared__ uint32_t patch_area[kPatchWords > kRegionWords ? kPatchWords : kRegionWords];
   __shared__ int wave_off[NT / 64 + 1];
-  __shared__ int s_running, s_R;
+  __shared__ int s_running;
   __shared__ int s_bb[4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int p = xcd_problem(nimg_total, nmask);
   if (p < 0) return;  // uniform (padding workgroup)
   const int img = p / nmask;
   const int n = min(n_io[p], cap);
-  if (tid == 0) {
-    s_running = 0;
-    s_R = 0;
-  }
+  if (tid == 0) s_running = 0;
   __syncthreads();
-  for (int i = tid; i < 512; i += NT) {
-    const float px = (float)pattern[2 * i], py = (float)pattern[2 * i + 1];
-    const float xr = (px * cos_a) - (py * sin_a), yr = (px * sin_a) + (py * cos_a);
-    const int dx = __float2int_rn(xr), dy = __float2int_rn(yr);
-    off[i] = dy * cols + dx;
-    atomicMax(&s_R, max(abs(dx), abs(dy)));
-  }
-  __syncthreads();
-  const int R = s_R;
+  const int R = ptab->R;  // uniform
+  // this lane's four tests (lane, 64 + lane, 128 + lane, 192 + lane) as offsets from a keypoint in an array whose rows lie
+  // `pitch` apart: multiply-adds on the table's (dx, dy)
+  // (the table pointer goes through an empty asm in the path that calls this: the eight loads then stay in that path, next to
+  // their use, and are not hoisted to the top of the kernel to be carried across the compaction and the staging)
+  auto lane_offsets = [&](int pitch, int* a, int* b) __attribute__((always_inline)) {
+    const int2* tp = ptab->pt;
+    asm volatile("" : "+s"(tp));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int2 d = tp[64 * r + lane];
+      a[r] = (d.x >> 16) * pitch + (int)(short)d.x;
+      b[r] = (d.y >> 16) * pitch + (int)(short)d.y;
+    }
+  };
   // Patch path: the (2R+1)^2 neighbourhood of a keypoint goes through LDS, fetched as unaligned dwords -- a few
   // row segments per lane instead of 512 scattered byte loads.  Patch rows are `pstride` dwords apart with
   // pstride ODD, so the rows spread over all 32 banks (a 64-byte row pitch would leave half of them unused and
@@ -901,13 +1009,7 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
     y_last = (rr_hi >= rows ? rows : rr_hi - 3) - 1 - R;
   }
   const int pdw = (PR + 3) >> 2;      // dwords per patch row
-  const int pstride = pdw | 1;        // row pitch in dwords
-  if (patch_ok)
-    for (int i = tid; i < 512; i += NT) {
-      const int dy = (off[i] + R * cols + R) / cols - R;  // recover (dx, dy): |dx| <= R < cols
-      const int dx = off[i] - dy * cols;
-      poff[i] = (uint16_t)((dy + R) * (4 * pstride) + (dx + R));
-    }
+  const int pstride = orb_patch_stride_dw(R);  // row pitch in dwords: pdw | 1
   for (int i0 = 0; i0 < n; i0 += NT) {
     const int i = i0 + tid;
     float x = 0.f, y = 0.f;
@@ -975,15 +1077,7 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
         }
         // this lane's eight test points as offsets inside the region (tests lane, 64 + lane, 128 + lane, 192 + lane)
         int ra[4], rb[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const int o = off[2 * (64 * r + lane) + e];
-            const int dy = (o + R * cols + R) / cols - R, dx = o - dy * cols;  // recover (dx, dy): |dx| <= R < cols
-            (e ? rb[r] : ra[r]) = dy * pitch_b + dx;
-          }
-        }
+        lane_offsets(pitch_b, ra, rb);
         __syncthreads();
         const uint8_t* region8 = reinterpret_cast<const uint8_t*>(patch_area);
         const int wid_s = __builtin_amdgcn_readfirstlane(wid);
@@ -1033,8 +1127,8 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
     int pa[4], pb[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      pa[r] = poff[2 * (64 * r + lane)];
-      pb[r] = poff[2 * (64 * r + lane) + 1];
+      pa[r] = ptab->poff[2 * (64 * r + lane)];
+      pb[r] = ptab->poff[2 * (64 * r + lane) + 1];
     }
     int j = wid;
     if (j < m) issue(j);
@@ -1054,13 +1148,14 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
     }
     return;
   }
+  int ga[4], gb[4];
+  lane_offsets(cols, ga, gb);
   for (int j = wid; j < m; j += NT / 64) {
     const uint8_t* c = im + (size_t)__float2int_rn(lds_kp[2 * j + 1]) * cols + __float2int_rn(lds_kp[2 * j]);
     unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((size_t)p * cap + j) * 32);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int t = 64 * r + lane;
-      const unsigned long long bal = __ballot(c[off[2 * t]] < c[off[2 * t + 1]]);
+      const unsigned long long bal = __ballot(c[ga[r]] < c[gb[r]]);
       if (lane == 0) d[r] = bal;
     }
   }
@@ -1112,6 +1207,7 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   SOSVO_REQUIRE(ctx, gray && mask_bits && kp && n, "null pointer");
   SOSVO_REQUIRE(ctx, nimg >= 0 && nimg <= 65535 && images_per_maskset > 0, "nimg out of range");
   SOSVO_REQUIRE(ctx, rows >= 3 && cols >= 3 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
+  SOSVO_REQUIRE(ctx, rows <= 65535 && cols <= 65535, "image sizes out of range (the candidates are packed as y << 16 | x)");
   SOSVO_REQUIRE(ctx, nmask >= 1 && nmask <= kMaxMasks, "nmask out of range (1..32)");
   // quality >= 1 is legal as in cv2.goodFeaturesToTrack: the threshold quality * max is then >= every response (the
   // candidate records hold the POSITIVE local maxima only), so no corner passes `v > thr` and every count comes back 0
@@ -1204,9 +1300,13 @@ int32_t sosvo_describe_orb_rows(sosvo_ctx* ctx, const uint8_t* gray, int32_t nim
   SOSVO_REQUIRE(ctx, ((uintptr_t)desc & 7) == 0, "desc must be 8-byte aligned");
   if (nimg == 0) return SOSVO_OK;
   const size_t bytes = (size_t)nimg * rows * cols;
-  int32_t rc = sosvo_ws_reserve(ctx, bytes);
+  const size_t o_tab = (bytes + 255) & ~(size_t)255;  // the rotated pattern of THIS call, next to the blurred images
+  int32_t rc = sosvo_ws_reserve(ctx, o_tab + sizeof(orb_pattern_table));
   if (rc != SOSVO_OK) return rc;
   uint8_t* blurred = (uint8_t*)ctx->ws;
+  orb_pattern_table* ptab = (orb_pattern_table*)((char*)ctx->ws + o_tab);
+  SOSVO_LAUNCH(ctx, orb_pattern_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pattern, cos_a, sin_a, ptab);
+  SOSVO_LAUNCH_CHECK(ctx);
   rc = launch_gauss7_rows(ctx, gray, (long long)rows * cols, nimg, rows, cols, blurred, (long long)rows * cols, row_range,
                           nimg > 1 ? nimg / 2 : 1);
   if (rc != SOSVO_OK) return rc;
@@ -1215,7 +1315,7 @@ int32_t sosvo_describe_orb_rows(sosvo_ctx* ctx, const uint8_t* gray, int32_t nim
   SOSVO_PROFILE(ctx, "orb_describe_kernel");
   auto launch = [&](auto kernel, int nt) {
     hipLaunchKernelGGL(kernel, dim3(xcd_grid(nimg, nmask)), dim3(nt), lds_kp_bytes, ctx->stream, blurred, rows, cols, nmask, cap, kp,
-                       n, cos_a, sin_a, pattern, edge, desc, nimg, row_range, irange);
+                       n, ptab, edge, desc, nimg, row_range, irange);
   };
   if (cap > 1024)
     launch(orb_describe_kernel<1024>, 1024);
