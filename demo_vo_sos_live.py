@@ -19,7 +19,7 @@ if ROOT not in sys.path:
 
 
 def build_parser():
-    from vo_single_camera_sos_amd.omnistereo.common_tools import add_f2f_tracker_arguments, str2bool
+    from vo_single_camera_sos_amd.omnistereo.common_tools import add_f2f_tracker_arguments, add_stereo_refine_arguments, str2bool
     parser = ArgumentParser(description="Live demo of frame-to-frame visual odometry for the Single-camera SOS rig.")
     parser.register("type", "bool", str2bool)
     parser.add_argument("results_path", nargs=1, help="The path where the results will be saved into.")
@@ -54,11 +54,12 @@ def build_parser():
     parser.add_argument("--subpix_half", default=None, type=int,
                         help="with --subpix_refine: the window half-size 2 .. 5; default: 5")
     add_f2f_tracker_arguments(parser)
+    add_stereo_refine_arguments(parser)
     return parser
 
 
 def main_sos_vo_live(argv=None, frame_source=None):
-    from vo_single_camera_sos_amd.omnistereo.common_tools import f2f_tracker_arguments, make_sure_path_exists
+    from vo_single_camera_sos_amd.omnistereo.common_tools import f2f_tracker_arguments, make_sure_path_exists, stereo_refine_arguments
     parser = build_parser()
     args = parser.parse_args(argv)
 
@@ -82,7 +83,8 @@ def main_sos_vo_live(argv=None, frame_source=None):
                          gated_max_distance=args.gated_max_distance,
                          ratio_test=None if args.ratio_test is None else (True if args.ratio_test == "both" else args.ratio_test),
                          ratio=args.ratio,
-                         subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half, **f2f_tracker_arguments(args))
+                         subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half, **f2f_tracker_arguments(args),
+                         **stereo_refine_arguments(args))
     print("GOODBYE!")
     return out
 

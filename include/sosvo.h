@@ -806,6 +806,63 @@ typedef struct sosvo_lk_options {
 } sosvo_lk_options;
 #define SOSVO_LK_OPTIONS_DEFAULT {10, 3, 30, 0, 0.01, 1e-4, 0.0}
 int32_t sosvo_set_lk_options(sosvo_ctx* ctx, const sosvo_lk_options* options);
+
+/* ---- sub-pixel static stereo: Lucas-Kanade disparity refinement (the cv2.calcOpticalFlowPyrLK(prevImg = top, nextImg = bottom)
+ * call of match_features_panoramic_top_bottom, omnistereo/camera_models.py:3070, between the two views of ONE frame) ----------
+ * sosvo_refine_stereo_lk runs after the static-stereo matching step (cross-check filter included: the keys are final) and
+ * before sosvo_stereo_assemble.  It moves the BOTTOM keypoint of every matched pair to where the top keypoint's window is
+ * found in the bottom image; the matcher's partner is the initial flow, so there is no pyramid.
+ *   gray [nimg, rows, cols] u8, view-major: image f is the top view of frame f, image nimg / 2 + f its bottom view (nimg
+ *   even, F = nimg / 2 frames); row_range as for sosvo_refine_subpix; kp_top, kp_bot [F * nmask, cap, 2] f32 and n_top, n_bot
+ *   [F * nmask] i32; keys [F * nmask, cap] u32 in QUERY order (query = bottom, train = top, k = 1, SOSVO_KEY_NONE for a query
+ *   without a match); status [F * nmask, cap] u8, optional.
+ * Per problem p = frame * nmask + mask and bottom keypoint q < min(n_bot[p], cap), with t = keys[p, q] & SOSVO_KEY_IDX_MASK:
+ *   1. keys[p, q] == SOSVO_KEY_NONE or t >= min(n_top[p], cap): kp_bot[p, q] is untouched, status 0.
+ *   2. otherwise the point kp_top[p, t] of image frame is tracked into image nimg / 2 + frame by sosvo_track_lk's rule, word
+ *      for word, with levels = 1, SOSVO_LK_INITIAL_FLOW and the guess g = kp_bot[p, q], no forward-backward check; half,
+ *      max_iter, eps, min_eig from the settings.  Rounding, row ranges, the lost conditions are the tracker's (a non-finite
+ *      coordinate: status 0).
+ *   3. the result (x', y') is accepted iff the tracker's status is 1 and |x' - g.x| <= max_shift and |y' - g.y| <= max_shift
+ *      (differences of the float32 values in double; a NaN fails).  Accepted: kp_bot[p, q] = (x', y'), status 1.  Otherwise
+ *      kp_bot[p, q] keeps its bits, status 0 -- the revert of sosvo_refine_subpix rule 5, whose bound is the window half-size:
+ *      max_shift = 0 means half.
+ *   Rows at and beyond n_bot[p], kp_top, the descriptors and the counts are untouched.  Bottom queries are distinct: the order
+ *   of work cannot matter.
+ * The pre-gate: a pair that cannot pass sosvo_stereo_assemble's pixel gates after a move of at most max_shift per axis is not
+ * tracked (untouched, status 0).  With du = u_top - u_bot, dv = v_top - v_bot, s = max_shift (all double) a pair is skipped iff
+ *   stereo_max_hdiff > 0 and |du| > (stereo_max_hdiff + s) * (1 + 2^-40), or
+ *   stereo_min_disp >= 0 and dv + s < stereo_min_disp - 2^-40 * (|dv| + s + stereo_min_disp);
+ * each side is disabled exactly when the assemble stage's gate is.  The 2^-40 margins cover the rounding of the differences
+ * (2^-53 relative): a pair that passes the gates after an accepted move is never skipped, and a skipped pair fails the gates
+ * unrefined as well, so what sosvo_stereo_assemble writes does not depend on the pre-gate.
+ *   options: NULL = the context's settings (sosvo_set_stereo_lk_options).  half 2 .. 10, max_iter 1 .. 30, eps and min_eig
+ *   finite and >= 0, max_shift finite and >= 0 (0: half); nimg even, <= 65535; nmask >= 1; cap 1 .. 4096; F * nmask <= 65535;
+ *   otherwise SOSVO_ERR_ARG.  Temporaries live in the context's scratch.
+ *
+ * In the batch and sequence entry points:
+ *   SOSVO_FLAG_LK_STEREO     sosvo_batch_cfg.ransac_flags: the front end runs the stage between sosvo_sort_matches and the
+ *                            stereo assemble, with the context's settings (SOSVO_STEREO_LK_OPTIONS_DEFAULT at creation:
+ *                            half 4, max_iter 30, eps 0.01, min_eig 1e-4, max_shift = half).
+ * Everything from the stereo gates on sees the refined bottom positions: bearings, triangulation, m_bot in the frame records,
+ * the bottom view's frame-to-frame gates and SOSVO_FLAG_LK_F2F starts.  Descriptors stay those of the detector's positions.
+ * It combines freely with every other option; with SOSVO_FLAG_SUBPIX that stage runs first and this one refines its result;
+ * with the ORB detector it acts on kp_xy.  Bits 8 - 9 are free in the omni word only: sosvo_rgbd_batch_cfg.flags keeps its
+ * detector there and has no stereo step.  The bit never reaches the RANSAC flags; the struct layouts and, with the bit
+ * clear, workspace sizes, launches and results are unchanged.  With it set the workspace grows by the stage's status flags
+ * ([window * nmask, kp_cap] u8).  sosvo_set_stereo_lk_options behaves like sosvo_set_lk_options: refused whole on a bad value
+ * or a NULL pointer (SOSVO_ERR_ARG, the previous settings stay); sosvo_frame_pair_batch_streams* hands the settings to its
+ * internal contexts at every call. */
+#define SOSVO_FLAG_LK_STEREO 0x100
+typedef struct sosvo_stereo_lk_options {
+  int32_t half, max_iter;
+  double eps, min_eig, max_shift;
+} sosvo_stereo_lk_options;
+#define SOSVO_STEREO_LK_OPTIONS_DEFAULT {4, 30, 0.01, 1e-4, 0.0}
+int32_t sosvo_set_stereo_lk_options(sosvo_ctx* ctx, const sosvo_stereo_lk_options* options);
+int32_t sosvo_refine_stereo_lk(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,
+                               const int32_t* row_range, int32_t nmask, int32_t cap, const float* kp_top, const int32_t* n_top,
+                               float* kp_bot, const int32_t* n_bot, const uint32_t* keys, double stereo_min_disp,
+                               double stereo_max_hdiff, const sosvo_stereo_lk_options* options, uint8_t* status);
 #define SOSVO_SUBPIX_HALF_SHIFT 10
 #define SOSVO_SUBPIX_HALF_MASK (3 << SOSVO_SUBPIX_HALF_SHIFT)
 #define SOSVO_SUBPIX_HALF(h) (((h) - 2) << SOSVO_SUBPIX_HALF_SHIFT)
@@ -859,7 +916,8 @@ typedef struct sosvo_batch_cfg {
                               SOSVO_FLAG_GATED_STEREO / _F2F, SOSVO_GATED_MAX_DIST(d): search under the pixel gates (see above);
                               SOSVO_FLAG_RATIO_STEREO / _F2F, SOSVO_RATIO_64THS(r): the ratio rule (see above);
                               SOSVO_FLAG_SUBPIX, SOSVO_SUBPIX_HALF(h): sub-pixel keypoint refinement (see above);
-                              SOSVO_FLAG_LK_F2F: Lucas-Kanade tracking in place of the frame-to-frame matcher (see above) */
+                              SOSVO_FLAG_LK_F2F: Lucas-Kanade tracking in place of the frame-to-frame matcher (see above);
+                              SOSVO_FLAG_LK_STEREO: sub-pixel static stereo, sosvo_refine_stereo_lk in the front end (see above) */
   int32_t detector;       /* enum sosvo_detector; 0 = GFT (this field was `reserved`, always 0, before) */
 } sosvo_batch_cfg;
 

@@ -41,6 +41,7 @@ SIGNATURES = {
     "sosvo_set_stream": (c_i32, [c_p, c_p]),
     "sosvo_set_hint": (c_i32, [c_p, c_i32, c_i32]),
     "sosvo_set_lk_options": (c_i32, [c_p, c_p]),
+    "sosvo_set_stereo_lk_options": (c_i32, [c_p, c_p]),
     "sosvo_synchronize": (c_i32, [c_p]),
     "sosvo_last_error": (ctypes.c_char_p, [c_p]),
     "sosvo_timer_start": (c_i32, [c_p]),
@@ -69,6 +70,8 @@ SIGNATURES = {
     "sosvo_gray_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_track_lk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32,
                                c_f64, c_f64, c_i32, c_p, c_p, c_p, c_p, c_f64]),
+    "sosvo_refine_stereo_lk": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64,
+                                       c_p, c_p]),
     "sosvo_orb_pyramid_pixels": (ctypes.c_int64, [c_i32, c_i32]),
     "sosvo_orb_mask_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_detect_orb": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
@@ -156,6 +159,7 @@ SUBPIX_HALF_MASK = 3 << SUBPIX_HALF_SHIFT
 SUBPIX_MAX_ITER = 10               # what the one-call and sequence entry points run the stage with
 SUBPIX_EPS = 0.01
 FLAG_LK_F2F = 0x80                 # Lucas-Kanade tracking in place of the frame-to-frame matcher (sosvo_batch_cfg.ransac_flags)
+FLAG_LK_STEREO = 0x100             # sub-pixel static stereo: sosvo_refine_stereo_lk in the front end (sosvo_batch_cfg.ransac_flags)
 LK_INITIAL_FLOW = 1                # SOSVO_LK_INITIAL_FLOW: next_pts holds the starting guess on entry
 LK_MAX_HALF, LK_MAX_LEVELS, LK_MAX_ITER, LK_MAX_CAP = 10, 4, 30, 4096
 DETECTOR_GFT = 0
@@ -337,6 +341,71 @@ class LkOptionsStruct(ctypes.Structure):
     def of(cls, lk):
         """An LKOptions -> the struct of sosvo_set_lk_options (fb_max None -> 0: no forward-backward check)."""
         return cls(lk.half, lk.levels, lk.max_iter, 0, lk.eps, lk.min_eig, 0.0 if lk.fb_max is None else lk.fb_max)
+
+
+class StereoLKOptions(namedtuple("StereoLKOptions", "half max_iter eps min_eig max_shift")):
+    """The settings of the static-stereo Lucas-Kanade refinement (sosvo_refine_stereo_lk) as one checked value: window
+    half-size 2 .. 10, max_iter 1 .. 30, eps >= 0, min_eig >= 0, max_shift None (= half) or a finite number >= 0 (pixels; 0
+    means half as well): a tracked position further than that from the matcher's partner on either axis is reverted.  A
+    value out of range raises ValueError; nothing is rounded."""
+    __slots__ = ()
+
+    def __new__(cls, half=4, max_iter=30, eps=0.01, min_eig=1e-4, max_shift=None):
+        for name, v, lo, hi in (("half", half, 2, LK_MAX_HALF), ("max_iter", max_iter, 1, LK_MAX_ITER)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
+                raise ValueError("stereo_lk %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+        for name, v in (("eps", eps), ("min_eig", min_eig)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
+                raise ValueError("stereo_lk %s must be a finite number >= 0, got %r" % (name, v))
+        if max_shift is not None and (isinstance(max_shift, bool) or not isinstance(max_shift, (int, float))
+                                      or not 0.0 <= max_shift < float("inf")):
+            raise ValueError("stereo_lk max_shift must be None or a finite number >= 0 (pixels), got %r" % (max_shift,))
+        return super().__new__(cls, int(half), int(max_iter), float(eps), float(min_eig),
+                               None if max_shift is None else float(max_shift))
+
+    @property
+    def bound(self):
+        """The acceptance bound in pixels: max_shift, or half where it is None or 0."""
+        return float(self.max_shift) if self.max_shift else float(self.half)
+
+    @classmethod
+    def of(cls, stereo_lk):
+        """A `stereo_lk` argument (None: the defaults; a StereoLKOptions; a dict of its fields) -> StereoLKOptions."""
+        if stereo_lk is None:
+            return cls()
+        if isinstance(stereo_lk, cls):
+            return stereo_lk
+        if isinstance(stereo_lk, dict):
+            unknown = set(stereo_lk) - set(cls._fields)
+            if unknown:
+                raise ValueError("stereo_lk: unknown settings %s" % sorted(unknown))
+            return cls(**stereo_lk)
+        raise ValueError("stereo_lk must be None, a StereoLKOptions or a dict of its fields, got %r" % (stereo_lk,))
+
+
+class StereoLkOptionsStruct(ctypes.Structure):
+    """Mirror of `struct sosvo_stereo_lk_options` (include/sosvo.h)."""
+    _fields_ = [("half", c_i32), ("max_iter", c_i32), ("eps", c_f64), ("min_eig", c_f64), ("max_shift", c_f64)]
+
+    @classmethod
+    def of(cls, o):
+        """A StereoLKOptions -> the struct of sosvo_set_stereo_lk_options (max_shift None -> 0: half)."""
+        return cls(o.half, o.max_iter, o.eps, o.min_eig, 0.0 if o.max_shift is None else o.max_shift)
+
+
+def stereo_refine_options(stereo_refine, stereo_lk, rgbd=False):
+    """The `stereo_refine` / `stereo_lk` arguments of the engines' constructors -> the StereoLKOptions of an engine that refines
+    its static stereo by tracking ("lk"), None for one that does not (None).  Settings without the switch are refused, and so
+    is the switch on an RGB-D engine: it has no static stereo."""
+    if stereo_refine not in (None, "lk"):
+        raise ValueError("stereo_refine: None or \"lk\", got %r" % (stereo_refine,))
+    if stereo_refine is None:
+        if stereo_lk is not None:
+            raise ValueError("stereo_lk settings without stereo_refine=\"lk\"")
+        return None
+    if rgbd:
+        raise ValueError("stereo_refine=\"lk\": an RGB-D camera has no static stereo")
+    return StereoLKOptions.of(stereo_lk)
 
 
 def f2f_tracker_options(f2f_tracker, lk, opts=None, rgbd=False):

@@ -37,6 +37,7 @@ struct sosvo_ctx {
   int32_t hint_shared_device;  // sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other streams' kernels share the chip
   int32_t hint_match_unsplit;  // sosvo_set_hint(SOSVO_HINT_MATCH_UNSPLIT): the matrix-core matchers do not split the train range
   sosvo_lk_options lk;  // sosvo_set_lk_options: the tracker's settings under SOSVO_FLAG_LK_F2F (cv2's defaults at creation)
+  sosvo_stereo_lk_options stereo_lk;  // sosvo_set_stereo_lk_options: the settings of the stage under SOSVO_FLAG_LK_STEREO
   int32_t sub_last;  // parts of the most recent sosvo_frame_pair_batch_streams[_enqueue] call
   // un-joined work of an ..._enqueue call is pending on the part streams: only then does the next call chain its first
   // median behind the previous call's last one, and only then must its slice layout (workspace pointer, part count, each
@@ -265,6 +266,7 @@ struct sosvo_lk_images {
   int32_t slots, rows, cols;
 };
 bool sosvo_lk_options_ok(const sosvo_lk_options& o);
+bool sosvo_stereo_lk_options_ok(const sosvo_stereo_lk_options& o);
 int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
                              int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame);
 int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,

@@ -7,6 +7,8 @@
 // the defaults of LKOptions (_lib.py): a 21 x 21 window, three levels, TermCriteria(COUNT + EPS, 30, 0.01), minEigThreshold
 // 1e-4, no forward-backward check
 static const sosvo_lk_options kLkDefaults = SOSVO_LK_OPTIONS_DEFAULT;
+// the defaults of StereoLKOptions (_lib.py): a 9 x 9 window, max_shift = half
+static const sosvo_stereo_lk_options kStereoLkDefaults = SOSVO_STEREO_LK_OPTIONS_DEFAULT;
 
 extern "C" {
 
@@ -39,6 +41,7 @@ int32_t sosvo_create(sosvo_ctx** out, int32_t device, void* stream) {
     return SOSVO_ERR_HIP;
   }
   ctx->lk = kLkDefaults;
+  ctx->stereo_lk = kStereoLkDefaults;
   *out = ctx;
   return SOSVO_OK;
 }
@@ -53,6 +56,18 @@ int32_t sosvo_set_lk_options(sosvo_ctx* ctx, const sosvo_lk_options* options) {
                       "out of range: half 2..10, levels 1..4, max_iter 1..30, eps and min_eig finite and >= 0, fb_max finite");
   ctx->lk = o;
   ctx->lk.reserved = 0;
+  return SOSVO_OK;
+}
+
+int32_t sosvo_set_stereo_lk_options(sosvo_ctx* ctx, const sosvo_stereo_lk_options* options) {
+  if (!ctx) return SOSVO_ERR_ARG;
+  if (!options)
+    return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, "null pointer (SOSVO_STEREO_LK_OPTIONS_DEFAULT gives the defaults)");
+  const sosvo_stereo_lk_options o = *options;
+  if (!sosvo_stereo_lk_options_ok(o))  // (the previous settings stay)
+    return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__,
+                      "out of range: half 2..10, max_iter 1..30, eps and min_eig finite and >= 0, max_shift finite and >= 0");
+  ctx->stereo_lk = o;
   return SOSVO_OK;
 }
 

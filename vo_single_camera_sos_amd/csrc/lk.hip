@@ -1,5 +1,6 @@
 // sosvo_gray_pyramid, sosvo_track_lk -- cv2.calcOpticalFlowPyrLK restated in exact integers: the points
-// of one gray image are tracked into another, coarse to fine over a pyramid of up to four levels.
+// of one gray image are tracked into another, coarse to fine over a pyramid of up to four levels.  sosvo_refine_stereo_lk
+// (section 29) is the same tracker at one level between the two views of a frame, behind a gather and before an acceptance.
 //
 // Per point and level: the template T is (2 half + 3)^2 integer bilinear samples on the 1/32-px grid (at most 255 * 1024),
 // its Scharr gradients are integers below 2^22, the normal equations A, B, C and the right-hand sides b1, b2 of every
@@ -438,7 +439,99 @@ int32_t lk_launch(sosvo_ctx* ctx, LkArgs a, const int32_t* row_range, const int3
   return SOSVO_OK;
 }
 
+// ---- static stereo by tracking (sosvo_refine_stereo_lk) ---------------------------------------------------
+// The tracker above does the work; the new device code is the GATHER in front of it and the ACCEPTANCE behind it.
+//
+// Gather, one workgroup per problem p = frame * nmask + mask: the matched bottom keypoints that pass the pre-gate and have
+// finite coordinates are COMPACTED into the tracker's tables -- start[p, j] = the top partner, guess[p, j] = the bottom
+// keypoint, idx[p, j] = its row q -- so that no group of the tracker idles on a row that is not tracked; count[p] = how many,
+// from[p] / to[p] = the frame's top / bottom image.  status[p, q] = 0 for every q < n_bot[p].  (The order inside a problem is
+// that of q; it does not matter: the bottom rows are distinct.)
+struct StereoLkGate {
+  double max_du, min_dv, max_shift;  // max_du = +inf: the du side is off
+  int dv_on;
+};
+constexpr double kStereoLkSlack = 1.0 / 1099511627776.0;  // 2^-40: far above the 2^-53 rounding of a difference, far below a pixel
+
+__global__ __launch_bounds__(256) void stereo_lk_gather_kernel(int nmask, int nframes, int cap, const float* __restrict__ kp_top,
+                                                               const int32_t* __restrict__ n_top, const float* __restrict__ kp_bot,
+                                                               const int32_t* __restrict__ n_bot, const uint32_t* __restrict__ keys,
+                                                               StereoLkGate g, float* __restrict__ start, float* __restrict__ guess,
+                                                               int32_t* __restrict__ idx, int32_t* __restrict__ count,
+                                                               int32_t* __restrict__ from, int32_t* __restrict__ to,
+                                                               uint8_t* __restrict__ status) {
+  __shared__ int wave_off[5];
+  __shared__ int s_running;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nb = min(max(n_bot[p], 0), cap), nt = min(max(n_top[p], 0), cap);
+  if (tid == 0) s_running = 0;
+  __syncthreads();
+  const size_t base = (size_t)p * cap;
+  for (int q0 = 0; q0 < nb; q0 += 256) {  // (uniform)
+    const int q = q0 + tid;
+    bool track = false;
+    float ut = 0.f, vt = 0.f, ub = 0.f, vb = 0.f;
+    if (q < nb) {
+      if (status) status[base + q] = 0;
+      const uint32_t key = keys[base + q];
+      const int t = (int)(key & SOSVO_KEY_IDX_MASK);
+      if (key != SOSVO_KEY_NONE && t < nt) {
+        ut = kp_top[2 * (base + t)];
+        vt = kp_top[2 * (base + t) + 1];
+        ub = kp_bot[2 * (base + q)];
+        vb = kp_bot[2 * (base + q) + 1];
+        const double du = (double)ut - (double)ub, dv = (double)vt - (double)vb;
+        // the pre-gate (a NaN difference compares false: the pair goes on and fails the test below)
+        const bool far_u = fabs(du) > (g.max_du + g.max_shift) * (1.0 + kStereoLkSlack);
+        const bool far_v = g.dv_on && dv + g.max_shift < g.min_dv - kStereoLkSlack * (fabs(dv) + g.max_shift + g.min_dv);
+        track = !far_u && !far_v && isfinite(ut) && isfinite(vt) && isfinite(ub) && isfinite(vb);
+      }
+    }
+    const int pos = sosvo_block_compact_pos<4>(track, wave_off, &s_running, tid);
+    if (track) {  // (pos < nb <= cap)
+      start[2 * (base + pos)] = ut;
+      start[2 * (base + pos) + 1] = vt;
+      guess[2 * (base + pos)] = ub;
+      guess[2 * (base + pos) + 1] = vb;
+      idx[base + pos] = q;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    count[p] = s_running;
+    from[p] = p / nmask;
+    to[p] = nframes + p / nmask;
+  }
+}
+
+// Acceptance: entry j < count[p] of problem p is the bottom row q = idx[p, j]; kp_bot[p, q] still holds the guess.  The
+// tracked position replaces it iff the tracker's status is 1 and it lies within max_shift of the guess on both axes (float32
+// values compared in double; a NaN fails).
+__global__ __launch_bounds__(256) void stereo_lk_accept_kernel(int nprob, int cap, double max_shift, const int32_t* __restrict__ count,
+                                                               const int32_t* __restrict__ idx, const float* __restrict__ next,
+                                                               const uint8_t* __restrict__ tracked, float* __restrict__ kp_bot,
+                                                               uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)nprob * cap) return;
+  const int p = (int)(i / cap), j = (int)(i - (size_t)p * cap);
+  if (j >= min(count[p], cap) || tracked[i] == 0) return;
+  const int q = idx[i];
+  if (q < 0 || q >= cap) return;  // (never: the gather wrote it)
+  const size_t o = (size_t)p * cap + q;
+  const float x = next[2 * i], y = next[2 * i + 1];
+  const double dx = (double)x - (double)kp_bot[2 * o], dy = (double)y - (double)kp_bot[2 * o + 1];
+  if (!(fabs(dx) <= max_shift && fabs(dy) <= max_shift)) return;
+  kp_bot[2 * o] = x;
+  kp_bot[2 * o + 1] = y;
+  if (status) status[o] = 1;
+}
+
 }  // namespace
+
+bool sosvo_stereo_lk_options_ok(const sosvo_stereo_lk_options& o) {
+  return o.half >= 2 && o.half <= kLkMaxHalf && o.max_iter >= 1 && o.max_iter <= 30 && o.eps >= 0.0 && isfinite(o.eps) &&
+         o.min_eig >= 0.0 && isfinite(o.min_eig) && o.max_shift >= 0.0 && isfinite(o.max_shift);
+}
 
 bool sosvo_lk_options_ok(const sosvo_lk_options& o) {
   return o.half >= 2 && o.half <= kLkMaxHalf && o.levels >= 1 && o.levels <= kLkMaxLevels && o.max_iter >= 1 && o.max_iter <= 30 &&
@@ -552,6 +645,66 @@ int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, 
   a.eps2 = eps * eps;
   a.min_eig = min_eig;
   return lk_launch(ctx, a, row_range, prev_img, next_img, nprob, prev_pts, nullptr, n, next_pts, status, err, back, fb_max);
+}
+
+int32_t sosvo_refine_stereo_lk(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,
+                               const int32_t* row_range, int32_t nmask, int32_t cap, const float* kp_top, const int32_t* n_top,
+                               float* kp_bot, const int32_t* n_bot, const uint32_t* keys, double stereo_min_disp,
+                               double stereo_max_hdiff, const sosvo_stereo_lk_options* options, uint8_t* status) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray && kp_top && n_top && kp_bot && n_bot && keys, "null pointer");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, 1) && nimg % 2 == 0, "sizes out of range (nimg even: view-major top / bottom images)");
+  SOSVO_REQUIRE(ctx, nmask >= 1 && cap > 0 && cap <= 4096 && (int64_t)(nimg / 2) * nmask <= 65535, "nmask / cap / problem count out of range");
+  const sosvo_stereo_lk_options o = options ? *options : ctx->stereo_lk;
+  SOSVO_REQUIRE(ctx, sosvo_stereo_lk_options_ok(o),
+                "settings out of range: half 2..10, max_iter 1..30, eps and min_eig finite and >= 0, max_shift finite and >= 0");
+  SOSVO_REQUIRE(ctx, !isnan(stereo_min_disp) && !isnan(stereo_max_hdiff), "the gates must not be NaN");
+  const int F = nimg / 2, P = F * nmask;
+  if (P == 0) return SOSVO_OK;
+  // the tracker's tables, in the context's scratch
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t at = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  const size_t n_pts = (size_t)P * cap;
+  const size_t o_start = carve(sizeof(float) * 2 * n_pts), o_next = carve(sizeof(float) * 2 * n_pts);
+  const size_t o_err = carve(sizeof(float) * n_pts), o_idx = carve(sizeof(int32_t) * n_pts), o_trk = carve(n_pts);
+  const size_t o_count = carve(sizeof(int32_t) * P), o_from = carve(sizeof(int32_t) * P), o_to = carve(sizeof(int32_t) * P);
+  int32_t rc = sosvo_ws_reserve(ctx, off);
+  if (rc != SOSVO_OK) return rc;
+  char* w = reinterpret_cast<char*>(ctx->ws);
+  float *start = reinterpret_cast<float*>(w + o_start), *next = reinterpret_cast<float*>(w + o_next);
+  float* err = reinterpret_cast<float*>(w + o_err);
+  int32_t *idx = reinterpret_cast<int32_t*>(w + o_idx), *count = reinterpret_cast<int32_t*>(w + o_count);
+  int32_t *from = reinterpret_cast<int32_t*>(w + o_from), *to = reinterpret_cast<int32_t*>(w + o_to);
+  uint8_t* tracked = reinterpret_cast<uint8_t*>(w + o_trk);
+  const double max_shift = o.max_shift > 0.0 ? o.max_shift : (double)o.half;
+  StereoLkGate g;  // sv_pixel_gate's switches: the du side is on for max_hdiff > 0, the dv side for min_disp >= 0
+  g.max_du = stereo_max_hdiff > 0 ? stereo_max_hdiff : HUGE_VAL;
+  g.dv_on = stereo_min_disp >= 0 ? 1 : 0;
+  g.min_dv = g.dv_on ? stereo_min_disp : 0.0;
+  g.max_shift = max_shift;
+  SOSVO_LAUNCH(ctx, stereo_lk_gather_kernel, dim3(P), dim3(256), 0, ctx->stream, nmask, F, cap, kp_top, n_top, kp_bot, n_bot, keys, g,
+               start, next, idx, count, from, to, status);
+  SOSVO_LAUNCH_CHECK(ctx);
+  LkArgs a;
+  lk_levels(gray, nullptr, nimg, rows, cols, 1, &a.lv);
+  a.nimg = nimg;
+  a.levels = 1;
+  a.cap = cap;
+  a.half = o.half;
+  a.max_iter = o.max_iter;
+  a.initial_flow = 1;
+  a.eps2 = o.eps * o.eps;
+  a.min_eig = o.min_eig;
+  rc = lk_launch(ctx, a, row_range, from, to, P, start, nullptr, count, next, tracked, err, nullptr, 0.0);
+  if (rc != SOSVO_OK) return rc;
+  SOSVO_LAUNCH(ctx, stereo_lk_accept_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, ctx->stream, P, cap, max_shift, count,
+               idx, next, tracked, kp_bot, status);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
 }
 
 }  // extern "C"

@@ -97,6 +97,9 @@ bool lk_flags_ok(int32_t flags) {
 }
 constexpr const char* kBadLkFlags =
     "SOSVO_FLAG_LK_F2F replaces the frame-to-frame matcher: SOSVO_FLAG_CROSS_CHECK_F2F / _GATED_F2F / _RATIO_F2F cannot be set with it";
+// ---- sub-pixel static stereo (SOSVO_FLAG_LK_STEREO): sosvo_refine_stereo_lk between the sort and the stereo assemble, with the
+// context's settings.  Its status flags are carved only when the switch is set, after everything else.
+bool lk_stereo(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_LK_STEREO) != 0; }
 // what every omni entry point asks of cfg->ransac_flags (nullptr: fine)
 const char* omni_flags_msg(int32_t flags) { return !ratio_flags_ok(flags) ? kBadRatioFlags : lk_flags_ok(flags) ? nullptr : kBadLkFlags; }
 // the gray rows the front end computes are those of sosvo_gray_rows_needed (GFT with the fused median), else all rows
@@ -153,6 +156,7 @@ struct FrontEndTmp {
   float* kp;
   int32_t *n, *status, *s_order, *n_cand, *gray_rows;
   uint32_t* s_keys;
+  uint8_t* lk_status;  // (nullptr without SOSVO_FLAG_LK_STEREO)
   OrbBufs orb;
   MutualTabs mutual;
   Ratio ratio;
@@ -309,6 +313,7 @@ Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* bas
   ws.img_in_place = pair_batch;
   ws.img_rows = gray_rows_known(c) ? ws.fe.gray_rows : nullptr;
   ws.tt.lk = carve_lk_tmp(cv, lk_f2f(c), c.n_pairs, c.frame_cap);
+  ws.fe.lk_status = lk_stereo(c) ? cv.take<uint8_t>(window * c.nmask * (size_t)c.kp_cap) : nullptr;
   ws.bytes = cv.off;
   return ws;
 }
@@ -759,6 +764,12 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   } else
     STAGE(match_1nn(ctx, gate, t.ratio, desc_bot, desc_top, kp_bot, kp_top, n_bot, n_top, nullptr, nullptr, h, h, cap, t.s_keys));
   STAGE(sosvo_sort_matches(ctx, t.s_keys, n_bot, nullptr, h, cap, t.s_order));
+  // sub-pixel static stereo (SOSVO_FLAG_LK_STEREO): the bottom keypoint of every matched pair moves to where the top one's
+  // window is found in the bottom panorama; the gates, bearings, triangulation and m_bot below see the refined positions
+  if (lk_stereo(*cfg))
+    STAGE(sosvo_refine_stereo_lk(ctx, t.gray, NI, cfg->rows, cfg->cols, rows_known ? t.gray_rows : nullptr, NM, cap, kp_top, n_top,
+                                 t.kp + (size_t)h * cap * 2, n_bot, t.s_keys, rig->stereo_min_disp, rig->stereo_max_hdiff, nullptr,
+                                 t.lk_status));
   if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
     STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
                                       slot_of_frame, NM, cap, Fc, o.m_top, o.m_bot, o.d_top, o.d_bot, o.X, o.b_top, o.b_bot, o.M,
@@ -970,6 +981,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     c.seed = cfg->seed + (uint64_t)lo;  // pair i samples with seed + i, whatever the split
     sosvo_ctx* sc = ctx->sub[s];
     sc->lk = ctx->lk;  // (settings, not hints: they change results, so every part tracks with the caller's)
+    sc->stereo_lk = ctx->stereo_lk;
     SOSVO_HIP(ctx, hipStreamWaitEvent(sc->stream, ctx->sub_begin, 0));
     const int32_t rc = run_frame_pairs(sc, rig, &c, omni + (size_t)2 * lo * cfg->H * cfg->W * 3, unwrap_table, mask_bits, pattern,
                                        ws, bytes[s], results + (size_t)16 * lo, token, ctx->sub_median[s]);

@@ -86,6 +86,7 @@ class Context(object):
             raise SosvoError("sosvo_create failed: %s" % _lib.STATUS_NAMES.get(rc, rc))
         self._h = h
         self.lk_options = _lib.LKOptions()   # what the context tracks with under SOSVO_FLAG_LK_F2F (set_lk_options)
+        self.stereo_lk_options = _lib.StereoLKOptions()   # ... and refines with under SOSVO_FLAG_LK_STEREO
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -127,6 +128,14 @@ class Context(object):
         lk = _lib.LKOptions.of(lk)
         self._call(self._lib.sosvo_set_lk_options, ctypes.byref(_lib.LkOptionsStruct.of(lk)))
         self.lk_options = lk
+
+    def set_stereo_lk_options(self, stereo_lk=None):
+        """sosvo_set_stereo_lk_options: the settings of the static-stereo refinement of the batch and sequence entry points
+        under SOSVO_FLAG_LK_STEREO (a StereoLKOptions, a dict of its fields, or None = the defaults).  They change results; a
+        refused value leaves the previous settings.  self.stereo_lk_options is what the context holds."""
+        o = _lib.StereoLKOptions.of(stereo_lk)
+        self._call(self._lib.sosvo_set_stereo_lk_options, ctypes.byref(_lib.StereoLkOptionsStruct.of(o)))
+        self.stereo_lk_options = o
 
     def set_stream(self, stream):
         """Enqueue on `stream` (a torch.cuda.Stream) from now on, e.g. the capture stream of a HIP graph."""
@@ -391,6 +400,39 @@ class Context(object):
                    int(max_iter), float(eps), float(min_eig), flags, _ptr(next_pts), _ptr(status), _ptr(err), _ptr(back),
                    0.0 if fb_max is None else float(fb_max))
         return (next_pts, status, err) if fb_max is None else (next_pts, status, err, back)
+
+    def refine_stereo_lk(self, gray, kp_top, n_top, kp_bot, n_bot, keys, nmask, stereo_min_disp=-1.0, stereo_max_hdiff=0.0,
+                         stereo_lk=None, row_range=None, status=None):
+        """sosvo_refine_stereo_lk: the bottom keypoint of every matched top / bottom pair is tracked from the top view's image
+        into the bottom view's (one level, the matcher's partner as the initial flow) and moved IN PLACE where the result is
+        accepted.  gray [2F,rows,cols] u8 view-major; kp_top, kp_bot [F*nmask, cap, 2] f32; n_top, n_bot [F*nmask] i32; keys
+        [F*nmask, cap(, 1)] u32 in query order (query = bottom); stereo_min_disp / stereo_max_hdiff: the rig's gates for the
+        pre-gate (the defaults disable it); stereo_lk: a StereoLKOptions / dict / None = the defaults; row_range as for
+        refine_subpix -> (kp_bot, status [F*nmask, cap] u8)."""
+        o = _lib.StereoLKOptions.of(stereo_lk)
+        _check(gray, torch.uint8, "gray", ndim=3)
+        NI, rows, cols = gray.shape
+        if NI % 2:
+            raise SosvoError("gray: expected the top and bottom views' images, view-major (an even count)")
+        P = (NI // 2) * int(nmask)
+        _check(kp_bot, torch.float32, "kp_bot", (P, None, 2))
+        cap = kp_bot.shape[1]
+        _check(kp_top, torch.float32, "kp_top", (P, cap, 2))
+        _check(n_top, torch.int32, "n_top", (P,))
+        _check(n_bot, torch.int32, "n_bot", (P,))
+        _check(keys, torch.uint32, "keys")
+        if tuple(keys.shape) not in ((P, cap), (P, cap, 1)):
+            raise SosvoError("keys: expected shape %r (k = 1), got %r" % ((P, cap), tuple(keys.shape)))
+        if row_range is not None:
+            _check(row_range, torch.int32, "row_range", (2, 2))
+        if status is None:
+            status = torch.zeros((P, cap), dtype=torch.uint8, device=gray.device)
+        _check(status, torch.uint8, "status", (P, cap))
+        opt = _lib.StereoLkOptionsStruct.of(o)
+        self._call(self._lib.sosvo_refine_stereo_lk, _ptr(gray), NI, rows, cols, _ptr(row_range), int(nmask), cap, _ptr(kp_top),
+                   _ptr(n_top), _ptr(kp_bot), _ptr(n_bot), _ptr(keys), float(stereo_min_disp), float(stereo_max_hdiff),
+                   ctypes.cast(ctypes.pointer(opt), c_p), _ptr(status))
+        return kp_bot, status
 
     def f2f_assemble_tracked(self, rig, frames, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, out=None):
         """sosvo_f2f_assemble_tracked: frames = dict from stereo_assemble (m_top, m_bot, X, M); ref_frame [NP] i32; trk_*

@@ -48,6 +48,23 @@ def f2f_tracker_arguments(args):
     return dict(f2f_tracker=args.f2f_tracker, lk=lk or None)
 
 
+def add_stereo_refine_arguments(parser):
+    """The demos' flags for the sub-pixel static stereo (run_VO's stereo_refine / stereo_lk)."""
+    parser.add_argument("--stereo_refine", default=None, choices=("lk",),
+                        help="lk: after the top / bottom matching the bottom keypoint of every matched pair is tracked from the top "
+                             "panorama into the bottom one (one-level Lucas-Kanade from the matcher's partner), on the GPU; default: off")
+    parser.add_argument("--stereo_lk_half", default=None, type=int, help="with --stereo_refine lk: the window half-size 2 .. 10; default: 4")
+    parser.add_argument("--stereo_lk_max_shift", default=None, type=float,
+                        help="with --stereo_refine lk: a tracked position further than this from the matcher's partner on either axis "
+                             "is reverted, in pixels; default: the window half-size")
+
+
+def stereo_refine_arguments(args):
+    """The parsed flags of add_stereo_refine_arguments -> run_VO's stereo_refine= / stereo_lk= (None: the defaults)."""
+    o = {name: getattr(args, "stereo_lk_" + name) for name in ("half", "max_shift") if getattr(args, "stereo_lk_" + name) is not None}
+    return dict(stereo_refine=args.stereo_refine, stereo_lk=o or None)
+
+
 def copy_only_attributes(objfrom, objto, exclude_names=()):
     """common_tools.py:154-159: every non-dunder member of objfrom is set on objto."""
     for n in dir(objfrom):

@@ -280,6 +280,7 @@ class GUMStereo(object):
         fe = self._front_end(method, num_of_features, median_win_size)
         fe.load_frames(np.ascontiguousarray(self.current_omni_img)[None])
         fe.run()
+        self._detect_front_end = fe      # (its gray panoramas are the current image's: what _refine_stereo_lk reads)
         fe.ctx.synchronize()
         nm = fe.model.nmask
         kp, n, desc = fe.kp.cpu().numpy(), fe.n.cpu().numpy(), fe.desc.cpu().numpy()
@@ -292,6 +293,47 @@ class GUMStereo(object):
                 desc_lists[view].append(np.ascontiguousarray(desc[p, :cnt]))
         self._detect_cache = (token, (kp_lists, desc_lists))
         return self._detect_cache[1]
+
+    def _engine_gray_rows(self, fe):
+        """The rows the sequence engines' front end computes for this detector (GFT with the fused median: the reach of its
+        masks and descriptors -> int32 [2, 2] on the device; else None = every row): the trackers clamp to them there, so
+        they do here, although this front end has computed them all."""
+        if not (fe.method == "GFT" and fe.median_win_size in (3, 5, 11)):
+            return None
+        m, key = fe.model, (fe.edge, fe.cos_a, fe.sin_a)
+        cache = m.__dict__.setdefault("_gray_rows", {})
+        if key not in cache:
+            cache[key] = fe.ctx.gray_rows_needed(m.mask_bits, m.nmask, fe.edge, m.pattern, fe.cos_a, fe.sin_a)
+        return cache[key]
+
+    def _refine_stereo_lk(self, options, buckets, matched, min_disp, max_hdiff):
+        """Sub-pixel static stereo on the per-frame path (set_stereo_refinement): Context.refine_stereo_lk on the matched
+        buckets of the current image -- bucket i is problem i of one frame, its keys in query order from the matches (a bottom
+        keypoint without a match: SOSVO_KEY_NONE) -> the buckets with the bottom keypoints at their refined positions."""
+        import torch
+        from .._lib import KEY_NONE
+        from .camera_models import KeyPoint, keypoints_to_array
+        fe = getattr(self, "_detect_front_end", None)
+        if fe is None or not buckets:
+            return buckets
+        ctx, P = fe.ctx, len(buckets)
+        cap = max(max(len(b[0]), len(b[2])) for b in buckets)
+        kp = np.zeros((2, P, cap, 2), np.float32)
+        n = np.zeros((2, P), np.int32)
+        keys = np.full((P, cap), KEY_NONE, np.uint32)
+        for i, ((top_k, _, bot_k, _), (q, t, _)) in enumerate(zip(buckets, matched)):
+            n[0, i], n[1, i] = len(top_k), len(bot_k)
+            kp[0, i, :len(top_k)] = keypoints_to_array(top_k)
+            kp[1, i, :len(bot_k)] = keypoints_to_array(bot_k)
+            keys[i, np.asarray(q, np.int64)] = np.asarray(t, np.uint32)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)  # noqa: E731
+        kp_bot = dev(kp[1])
+        ctx.refine_stereo_lk(fe.gray, dev(kp[0]), dev(n[0]), kp_bot, dev(n[1]), dev(keys), P, float(min_disp), float(max_hdiff),
+                             stereo_lk=options, row_range=self._engine_gray_rows(fe))
+        ctx.synchronize()
+        refined = kp_bot.cpu().numpy()
+        return [(top_k, top_d, [KeyPoint(x, y, size=1.0) for x, y in refined[i, :len(bot_k)]], bot_d)
+                for i, (top_k, top_d, bot_k, bot_d) in enumerate(buckets)]
 
     def match_features_panoramic_top_bottom(self, keypts_list_top, desc_list_top, keypts_list_bot, desc_list_bot,
                                             min_rectified_disparity=1, max_horizontal_diff=1, show_matches=False,
@@ -309,6 +351,8 @@ class GUMStereo(object):
                                           max_horizontal_diff, fm.gated_max_distance)
         else:
             matched = fm.match_arrays_many([(bot_d, top_d) for _, top_d, _, bot_d in buckets])   # all buckets in one launch
+        if getattr(fm, "stereo_lk_options", None) is not None:    # sub-pixel static stereo: the gates below see the refined positions
+            buckets = self._refine_stereo_lk(fm.stereo_lk_options, buckets, matched, min_rectified_disparity, max_horizontal_diff)
         for (top_k, top_d, bot_k, bot_d), (q, t, _) in zip(buckets, matched):
             good = int(fm.percentage_good_matches * len(q))
             if good > 0:

@@ -292,6 +292,8 @@ class TrackerSE3(object):
         self.subpix_half = None
         # Lucas-Kanade tracking in place of the frame-to-frame matcher (an LKOptions): off; see set_f2f_tracker
         self.lk_options = None
+        # sub-pixel static stereo (a StereoLKOptions): off; see set_stereo_refinement
+        self.stereo_lk_options = None
         self.num_features_detection_for_motion = 1000
         self.max_horizontal_search_ratio = 0.50
         self.pose_est_algorithm = "EPNP"
@@ -675,6 +677,27 @@ def set_f2f_tracker(tracker, f2f_tracker, lk=None):
     tracker.lk_options = cm.lk_options = value
 
 
+def set_stereo_refinement(tracker, stereo_refine, stereo_lk=None):
+    """Sub-pixel static stereo.  stereo_refine: None = leave the tracker's own setting (and stereo_lk must be None), False = off,
+    "lk" = after the top / bottom matching the bottom keypoint of every matched pair is tracked from the top panorama into the
+    bottom one by one-level Lucas-Kanade with the matcher's partner as the initial flow (Context.refine_stereo_lk; the
+    cv2.calcOpticalFlowPyrLK(prevImg = top, nextImg = bottom) call of camera_models.py:3070); stereo_lk: its settings, None / a
+    StereoLKOptions / a dict of its fields.  The static-stereo matcher bootstrap_tracker built carries the setting to the frames,
+    so the per-frame mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker has no static
+    stereo: "lk" is a ValueError."""
+    from .._lib import stereo_refine_options
+    if stereo_refine is None:
+        if stereo_lk is not None:
+            raise ValueError("stereo_lk settings without stereo_refine=\"lk\"")
+        return
+    cm = tracker.camera_model
+    value = stereo_refine_options(None if stereo_refine is False else stereo_refine, stereo_lk, rgbd=_is_rgbd_model(cm))
+    fm = getattr(cm, "feature_matcher_for_static_stereo", None)
+    if fm is not None:
+        fm.stereo_lk_options = value
+    tracker.stereo_lk_options = value
+
+
 def _has_batched_counterpart(tracker, fm):
     """Whether the sequence engines run what `tracker` is set to; fm: the matcher the family's frames detect with (None:
     none yet)."""
@@ -717,13 +740,15 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None))
+           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None), getattr(fm, "stereo_lk_options", None))
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
                   subpix=getattr(fm, "subpix_half", None), **opts._asdict())
     if getattr(tracker, "lk_options", None) is not None:
         kwargs.update(f2f_tracker="lk", lk=tracker.lk_options)
+    if getattr(fm, "stereo_lk_options", None) is not None:
+        kwargs.update(stereo_refine="lk", stereo_lk=fm.stereo_lk_options)
     return (model, rig), kwargs, key
 
 
@@ -1276,7 +1301,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
            cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-           subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+           subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -1313,7 +1338,10 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
     f2f_tracker: None = the tracker's own setting ("match"), "match" = the frame-to-frame correspondences come from the
     descriptor matcher, "lk" = the reference frame's stereo points are tracked into the current frame's gray panoramas by
     pyramidal Lucas-Kanade (see set_f2f_tracker); lk: its settings, None / an LKOptions / a dict of its fields.  Sequence mode
-    and the mirror path follow alike; an RGB-D camera model refuses "lk", and so does a frame-to-frame matcher option."""
+    and the mirror path follow alike; an RGB-D camera model refuses "lk", and so does a frame-to-frame matcher option.
+    stereo_refine: None = the tracker's own setting (off), "lk" = sub-pixel static stereo: the bottom keypoint of every matched
+    top / bottom pair is tracked from the top panorama into the bottom one (see set_stereo_refinement); stereo_lk: its
+    settings, None / a StereoLKOptions / a dict of its fields.  An RGB-D camera model refuses "lk"."""
     from .common_cv import get_images
     if visualizer_3D_VO is not None:
         raise NotImplementedError("3-D visualisation is not built: pass visualizer_3D_VO=None")
@@ -1343,6 +1371,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         set_ratio_test(tracker, ratio_test, ratio)                        # (... and their ratio rule)
         set_subpixel_refinement(tracker, subpix_refine, subpix_half)      # (... and the frames' sub-pixel keypoints)
         set_f2f_tracker(tracker, f2f_tracker, lk)                         # (... and tracking in place of the f2f matcher)
+        set_stereo_refinement(tracker, stereo_refine, stereo_lk)          # (... and the sub-pixel static stereo)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1456,7 +1485,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
                 results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
                 gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+                subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1480,7 +1509,7 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
 
 
 def _est_poses_filename(timestamped):
@@ -1522,7 +1551,7 @@ def _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_in
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
                    gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1530,7 +1559,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
     est_poses_filename = _est_poses_filename(timestamped=not use_multithreads_for_VO)
     cam_working_thread.start()
     if not getattr(cam_working_thread, "lockstep", False):
@@ -1552,7 +1581,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
               last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
               gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-              subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+              subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1560,7 +1589,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
     gt_poses_filename, vo_frame_indices = _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index,
                                                                           last_image_index, step_for_scene_images)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
@@ -1585,7 +1614,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
                 _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None,
-                ratio=None, subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+                ratio=None, subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1639,7 +1668,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
     shared = dict(engine=None, key=None)
     guard, exited = threading.Lock(), set()
 
@@ -1715,7 +1744,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
                    frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
                    gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1724,7 +1753,7 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
     sequences = []
     for sc in scenes:
         gt_poses_filename, indices = _scene_ground_truth_and_indices(sc["scene_path"], int(sc["num_scene_images"]), first_image_index,

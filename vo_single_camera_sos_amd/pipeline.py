@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import LKOptions, MatchOptions, f2f_tracker_options, subpix_flags, subpix_half
+from ._lib import LKOptions, MatchOptions, f2f_tracker_options, stereo_refine_options, subpix_flags, subpix_half
 from .device import Context, make_rig
 
 
@@ -35,7 +35,7 @@ class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
                  adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
@@ -52,8 +52,15 @@ class FramePairPipeline(object):
         f2f_tracker: "match" = the frame-to-frame correspondences come from the descriptor matcher (the reference's way);
         "lk" = the reference frames' stereo points are tracked into the current frames' gray panoramas by pyramidal
         Lucas-Kanade (Context.track_lk; cv2.calcOpticalFlowPyrLK, camera_models.py:3070) -- needs a front end.  lk: its
-        settings, None / an LKOptions / a dict of its fields (half, levels, max_iter, eps, min_eig, fb_max)."""
+        settings, None / an LKOptions / a dict of its fields (half, levels, max_iter, eps, min_eig, fb_max).
+        stereo_refine: None, or "lk" = sub-pixel static stereo: between sort_matches and stereo_assemble the bottom keypoint of
+        every matched pair is tracked from the top panorama into the bottom one (Context.refine_stereo_lk; the same call of
+        the reference, between the two views of one frame) -- needs a front end.  stereo_lk: its settings, None / a
+        StereoLKOptions / a dict of its fields (half, max_iter, eps, min_eig, max_shift)."""
         assert isinstance(ctx, Context)
+        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
+        if self.stereo_lk is not None and front_end is None:
+            raise ValueError("stereo_refine=\"lk\" needs a front end: the refinement reads the gray panoramas")
         if f2f_tracker not in ("match", "lk"):
             raise ValueError("f2f_tracker: \"match\" or \"lk\", got %r" % (f2f_tracker,))
         if f2f_tracker == "lk" and front_end is None:
@@ -134,6 +141,8 @@ class FramePairPipeline(object):
         self.lm_cost, self.lm_iters = z((self.B,), torch.float64), z((self.B,), torch.int32)
         self.cam_off = torch.from_numpy(np.stack([rig.F_top, rig.F_bot])).to(dev)
         self.cam_rot = torch.from_numpy(np.stack([np.eye(3), np.eye(3)])).to(dev)
+        if self.stereo_lk is not None:    # the refinement's flags, one per bottom keypoint
+            self.s_lk_status = z((P, self.bucket_cap), torch.uint8)
         if self.lk is not None:    # the tracker's buffers: 2B problems (top views, then bottom views), frame_cap points each
             self._lk_pyr = None
             self._lk_prev = z((2 * self.B, Fc, 2), torch.float32)
@@ -156,6 +165,11 @@ class FramePairPipeline(object):
         c.match_1nn_two_launch(self.desc_bot, self.desc_top, self.n_bot, self.n_top, q_pos=self.kp_bot, t_pos=self.kp_top,
                                **self._stereo_search)
         c.sort_matches(self.s_keys, self.n_bot, order=self.s_order)
+        if self.stereo_lk is not None:
+            fe = self.front_end
+            c.refine_stereo_lk(fe.gray, self.kp_top, self.n_top, self.kp_bot, self.n_bot, self.s_keys, self.NM,
+                               self.rig_cfg.stereo_min_disp, self.rig_cfg.stereo_max_hdiff, stereo_lk=self.stereo_lk,
+                               row_range=None if fe.keep_panoramas else fe.gray_rows, status=self.s_lk_status)
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
                           self.s_keys, self.s_order, self.F, self.NM, self.frame_cap, out=self.frames)
 
@@ -236,15 +250,17 @@ class OverlappedFramePairs(object):
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray.
-        f2f_tracker / lk: as FramePairPipeline ("lk": every part's pipeline tracks with these settings)."""
+        f2f_tracker / lk: as FramePairPipeline ("lk": every part's pipeline tracks with these settings).
+        stereo_refine / stereo_lk: as FramePairPipeline, in every part."""
         from .frontend import DeviceImageModel, ImageFrontEnd
         from .parallel import shard_range
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
+        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
@@ -269,7 +285,7 @@ class OverlappedFramePairs(object):
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
                                            ransac_solver=ransac_solver, f2f_tracker=f2f_tracker, lk=self.lk,
-                                           **opts._asdict())
+                                           stereo_refine=stereo_refine, stereo_lk=self.stereo_lk, **opts._asdict())
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -400,11 +416,12 @@ class OverlappedFramePairs(object):
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
               adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
               gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
-              subpix=None, lk=None):
+              subpix=None, lk=None, stereo_lk=None):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
     any ransac_solver but "GP3P" is P3P.  lk: None, or the LKOptions of an engine that tracks (SOSVO_FLAG_LK_F2F; the
-    settings themselves belong to the context, see use_lk_options)."""
+    settings themselves belong to the context, see use_lk_options).  stereo_lk: None, or the StereoLKOptions of an engine
+    that refines its static stereo (SOSVO_FLAG_LK_STEREO; the settings belong to the context likewise)."""
     from . import _lib, orb_pattern
     from .frontend import default_kp_cap
     detector = _lib.detector_code(detection_method)
@@ -425,14 +442,19 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.ransac_flags |= subpix_flags(subpix)
     if lk is not None:
         c.ransac_flags |= _lib.FLAG_LK_F2F
+    if stereo_lk is not None:
+        c.ransac_flags |= _lib.FLAG_LK_STEREO
     return c
 
 
-def use_lk_options(ctx, lk):
-    """Before a call of an engine that tracks with the settings `lk` (None: it matches, nothing to do): contexts are shared
-    between engines, so the context gets them whenever they differ from what it was last given."""
+def use_lk_options(ctx, lk, stereo_lk=None):
+    """Before a call of an engine that tracks with the settings `lk` (None: it matches, nothing to do) or refines its static
+    stereo with the settings `stereo_lk` (None: it does not): contexts are shared between engines, so the context gets them
+    whenever they differ from what it was last given."""
     if lk is not None and getattr(ctx, "lk_options", None) != lk:
         ctx.set_lk_options(lk)
+    if stereo_lk is not None and getattr(ctx, "stereo_lk_options", None) != stereo_lk:
+        ctx.set_stereo_lk_options(stereo_lk)
 
 
 class FramePairBatch(object):
@@ -443,22 +465,25 @@ class FramePairBatch(object):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap).
         subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement (SOSVO_FLAG_SUBPIX).
         f2f_tracker / lk: as FramePairPipeline -- "lk": SOSVO_FLAG_LK_F2F, the reference frames' points are tracked into the
-        current frames' gray panoramas; a frame-to-frame matcher option with it raises ValueError."""
+        current frames' gray panoramas; a frame-to-frame matcher option with it raises ValueError.
+        stereo_refine / stereo_lk: as FramePairPipeline -- "lk": SOSVO_FLAG_LK_STEREO."""
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
+        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
         self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                  median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                  max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                 detection_method=detection_method, subpix=subpix, lk=self.lk, **opts._asdict())
+                                 detection_method=detection_method, subpix=subpix, lk=self.lk, stereo_lk=self.stereo_lk,
+                                 **opts._asdict())
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -476,7 +501,7 @@ class FramePairBatch(object):
     def step(self):
         """-> results [B,16] f64 (asynchronous)."""
         m = self.model
-        use_lk_options(self.ctx, self.lk)
+        use_lk_options(self.ctx, self.lk, self.stereo_lk)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out, n_streams=self.n_streams)
 
@@ -485,7 +510,7 @@ class FramePairBatch(object):
         the library's internal streams.  Pass alternating `results` buffers while something still reads the previous
         step's records; call join() before reading records on the context's stream."""
         m = self.model
-        use_lk_options(self.ctx, self.lk)
+        use_lk_options(self.ctx, self.lk, self.stereo_lk)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out if results is None else results, n_streams=self.n_streams,
                                          join=self.n_streams <= 1)
@@ -587,14 +612,16 @@ class _SequenceFamily(object):
 class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
-    def __init__(self, ctx, model, rig, frames, slots, gather, opts, f2f_tracker="match", lk=None, **settings):
-        """opts: a MatchOptions; f2f_tracker / lk: as FramePairPipeline's; settings: batch_cfg's tracker settings
+    def __init__(self, ctx, model, rig, frames, slots, gather, opts, f2f_tracker="match", lk=None, stereo_refine=None,
+                 stereo_lk=None, **settings):
+        """opts: a MatchOptions; f2f_tracker / lk, stereo_refine / stereo_lk: as FramePairPipeline's; settings: batch_cfg's tracker settings
         (num_of_features ... detection_method) but the seed."""
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
-        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, **settings, **opts._asdict())
+        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
+        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, stereo_lk=self.stereo_lk, **settings, **opts._asdict())
         self.method = str(settings["detection_method"]).upper()
         if str(settings["ransac_solver"]).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -609,7 +636,7 @@ class _OmniFamily(_SequenceFamily):
     def _call(self, name, heads, *args):
         """Engines that share a context may track with different settings: every device call of a tracking family runs under
         its own (the front end builds, the copies move and the tracker reads the pyramid levels they name)."""
-        use_lk_options(self.ctx, self.lk)
+        use_lk_options(self.ctx, self.lk, self.stereo_lk)
         return super()._call(name, heads, *args)
 
     @staticmethod
@@ -894,7 +921,7 @@ class SequenceEngine(_SequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
@@ -902,11 +929,12 @@ class SequenceEngine(_SequenceBase):
         gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline.
         subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement, as FramePairBatch.
         f2f_tracker / lk: "lk" = Lucas-Kanade tracking in place of the frame-to-frame matcher, as FramePairBatch; the store
-        then keeps every frame's gray panoramas and their pyramid."""
+        then keeps every frame's gray panoramas and their pyramid.
+        stereo_refine / stereo_lk: "lk" = sub-pixel static stereo (SOSVO_FLAG_LK_STEREO), as FramePairBatch."""
         self._init_windows(window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts, f2f_tracker, lk,
+        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts, f2f_tracker, lk, stereo_refine, stereo_lk,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1142,9 +1170,10 @@ class RGBDPairBatch(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         from . import orb_pattern
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
+        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
@@ -1191,8 +1220,9 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
+        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
         self._init_windows(window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, opts, mask,
@@ -1527,11 +1557,12 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         self._init_lanes(lanes, window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts, f2f_tracker, lk,
+        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts, f2f_tracker, lk, stereo_refine,
+                                stereo_lk,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1545,8 +1576,9 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
+        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
         self._init_lanes(lanes, window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, opts, mask,
