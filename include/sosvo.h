@@ -82,6 +82,11 @@ int32_t sosvo_set_stream(sosvo_ctx* ctx, void* stream);
  * (tests/test_gpu_ratio_test.py compares the two forms).  For A/B measurements (scripts/bench_ratio_test.py); not passed on
  * to the internal contexts of sosvo_frame_pair_batch_streams. */
 #define SOSVO_HINT_MATCH_UNSPLIT 3
+/* SOSVO_HINT_ROLLING_NARROW (value != 0): the rolling image kernels run in their one-column-per-lane form at every image
+ * width: the 7x7 blur of sosvo_gauss7, sosvo_describe_orb* and the ORB detector's levels (otherwise four columns per lane
+ * from 8 columns on) and the corner response of sosvo_detect_gft (otherwise two).  Same bytes, same keypoints
+ * (tests/test_gpu_blur_wide.py and tests/test_gpu_response_wide.py compare the forms).  For A/B measurements; passed on to the internal contexts of sosvo_frame_pair_batch_streams. */
+#define SOSVO_HINT_ROLLING_NARROW 4
 int32_t sosvo_set_hint(sosvo_ctx* ctx, int32_t hint, int32_t value);
 int32_t sosvo_synchronize(sosvo_ctx* ctx);
 const char* sosvo_last_error(const sosvo_ctx* ctx);
@@ -199,6 +204,32 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
                          int32_t images_per_maskset, int32_t rows, int32_t cols, int32_t nmask,
                          double quality, double min_distance, int32_t max_corners, int32_t cap,
                          float* kp, int32_t* n, int32_t* status);
+
+/* The first half of sosvo_detect_gft on its own, for tests of the corner-response kernel: the masks' bounding boxes and the
+ * response kernel, whose outputs are copied out of the context's workspace (stream-ordered device-to-device copies).
+ *   geometry (HOST, int32 [6], always written): strip width, strips per row, row chunks, rows per chunk, record slots per
+ *     region (wcap), number of regions = nimg * strips * chunks.  Region r = (image * chunks + chunk) * strips + strip holds
+ *     the positive 3x3 local maxima of the response inside some mask among the columns strip * width .. + width - 1 and
+ *     the rows chunk * rows_per_chunk .. + rows_per_chunk - 1, except the image's outermost rows and columns, row-major
+ *     and by ascending x within a row.
+ *   With cand_out, wcnt_out and mstat_out all NULL only geometry is written (the sizes to allocate).  Otherwise (DEVICE):
+ *   cand_out u32 [regions, wcap, 2]: (response bits, y << 16 | x), the first min(wcnt, wcap) of a region are valid;
+ *   wcnt_out u32 [regions]: candidates found in the region (may exceed wcap);
+ *   mstat_out u32 [nimg * nmask, 5]: [0] the mask's largest response in the order-preserving integer form (0 = no pixel;
+ *     f >= 0 -> bits | 0x80000000, f < 0 -> ~bits), [1..4] the bounding box fields of sosvo_detect_gft's selection.
+ * The geometry depends on the sizes, the context's hints and the library version, never on the image content. */
+int32_t sosvo_detect_gft_candidates(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask_bits, int32_t nimg,
+                                    int32_t images_per_maskset, int32_t rows, int32_t cols, int32_t nmask, int32_t* geometry,
+                                    uint32_t* cand_out, uint32_t* wcnt_out, uint32_t* mstat_out);
+
+/* ---- K6a on its own: the 7x7 sigma-2 Gaussian of the descriptor stage ---------------------------
+ * out = the blur of gray in 8.8 fixed point (weights 18 34 49 54 49 34 18 / 256 per axis, reflect-101 border, horizontal
+ * sums kept exactly, (v + 32768) >> 16 after the vertical pass): image i is read at gray + i * img_stride and written at
+ * out + i * out_stride, rows * cols bytes each (strides >= rows * cols; nothing between or beyond the images is read or
+ * written).  row_range: int32 [2][2] in DEVICE memory as for sosvo_describe_orb_rows (view-major, nimg even; rows outside a
+ * view's range are not written), NULL = all rows.  gray and out must not overlap. */
+int32_t sosvo_gauss7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int64_t img_stride,
+                     uint8_t* out, int64_t out_stride, const int32_t* row_range);
 
 /* ---- K6: ORB descriptors on provided keypoints (a4) --------------------------------------------
  * Replaces ORB_create(nfeatures).compute(image, keypoints) (omnistereo/camera_models.py:1765, :1785;

@@ -60,6 +60,9 @@ SIGNATURES = {
     "sosvo_gray_rows_needed": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_f32, c_f32, c_p]),
     "sosvo_detect_gft": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, c_p,
                                  c_p, c_p]),
+    "sosvo_detect_gft_candidates": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_p, c_p,
+                                            c_p]),
+    "sosvo_gauss7": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, ctypes.c_int64, c_p, ctypes.c_int64, c_p]),
     "sosvo_describe_orb": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_f32, c_f32, c_p, c_i32,
                                    c_p]),
     "sosvo_describe_orb_rows": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_f32, c_f32, c_p, c_i32,
@@ -139,6 +142,7 @@ SIGNATURES = {
 HINT_SHARED_DEVICE = 1
 HINT_SCORE_FP64_ONLY = 2
 HINT_MATCH_UNSPLIT = 3
+HINT_ROLLING_NARROW = 4
 FLAG_CAM_ROT_IDENTITY = 1
 FLAG_EPNP = 2
 FLAG_GP3P = 4

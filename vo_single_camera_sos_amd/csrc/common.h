@@ -36,6 +36,7 @@ struct sosvo_ctx {
   int32_t hint_score_fp64_only;  // sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): no single-precision tier in ransac_score_kernel
   int32_t hint_shared_device;  // sosvo_set_hint(SOSVO_HINT_SHARED_DEVICE): other streams' kernels share the chip
   int32_t hint_match_unsplit;  // sosvo_set_hint(SOSVO_HINT_MATCH_UNSPLIT): the matrix-core matchers do not split the train range
+  int32_t hint_rolling_narrow;  // sosvo_set_hint(SOSVO_HINT_ROLLING_NARROW): the rolling image kernels in their one-column form
   sosvo_lk_options lk;  // sosvo_set_lk_options: the tracker's settings under SOSVO_FLAG_LK_F2F (cv2's defaults at creation)
   sosvo_stereo_lk_options stereo_lk;  // sosvo_set_stereo_lk_options: the settings of the stage under SOSVO_FLAG_LK_STEREO
   int32_t sub_last;  // parts of the most recent sosvo_frame_pair_batch_streams[_enqueue] call

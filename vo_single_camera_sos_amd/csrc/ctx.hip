@@ -81,6 +81,10 @@ int32_t sosvo_set_hint(sosvo_ctx* ctx, int32_t hint, int32_t value) {
       if (ctx->sub[i]) ctx->sub[i]->hint_score_fp64_only = value != 0;
   } else if (hint == SOSVO_HINT_MATCH_UNSPLIT) {
     ctx->hint_match_unsplit = value != 0;
+  } else if (hint == SOSVO_HINT_ROLLING_NARROW) {
+    ctx->hint_rolling_narrow = value != 0;
+    for (int i = 0; i < ctx->n_sub; ++i)  // the internal contexts of sosvo_frame_pair_batch_streams follow
+      if (ctx->sub[i]) ctx->sub[i]->hint_rolling_narrow = value != 0;
   } else {
     return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, "unknown hint");
   }

@@ -18,6 +18,7 @@
 //            lane l evaluates tests l, 64+l, 128+l, 192+l; four 64-bit ballots ARE the 32 descriptor bytes.
 // Everything is integer work or float32 with a pinned evaluation order -> bit-exact against the oracle.
 #include "common.h"
+#include "rolling_layout.h"
 
 #include <type_traits>
 
@@ -28,6 +29,8 @@ constexpr int kCandCap = 4096;       // candidates kept per (image, mask): 32 KB
 constexpr int kCandCapSmall = 2048;   // first pass of the two-pass selection: 16 KB of LDS keys, 1536 grid cells
 constexpr int kCandCapLarge = 16384; // large-mask variant (whole-image detection, cap > 1024): 128 KB of the 160 KB LDS
 constexpr int kMaxMasks = 32;
+typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
+typedef uint16_t __attribute__((aligned(1))) u16_unaligned;
 
 // ---- K4a: min-eigenvalue map, rolling over rows ---------------------------------------------------------
 // One wave owns a 64-column strip (3 halo columns each side, 58 output columns) of one image and walks down a
@@ -234,6 +237,242 @@ __global__ __launch_bounds__(kThreads) void min_eigen_kernel(const uint8_t* __re
       eig_flush(mstat_img, cur_bits, cur_max);
     }
   }
+}
+
+// ---- K4a, two columns per lane ---------------------------------------------------------------------------------
+// The same walk with lane l holding the columns xb + 2 l (`lo`) and xb + 2 l + 1 (`hi`) of a 128-column span: one gray
+// load (a dword that holds the two bytes) and one 8-byte load of the two mask words per row.  A wave owns TWO logical
+// strips of kEigWideStripW = 61 outputs (2 x 61 + 6 halo columns = 128): strip 2 sp in the lanes 0 .. 31 (lane 1 hi ..
+// lane 31 hi), strip 2 sp + 1 in the lanes 32 .. 63 (lane 32 lo .. lane 62 lo); with an odd strip count the last wave of a
+// row of strips owns one.  Regions and their numbering (img * nchunks + chunk) * strips + strip are those of the
+// one-column form at this strip width: the wave keeps two running positions and writes two wcnt entries.
+//   Neighbours: the left neighbour of a lane's lo pixel is the hi pixel of the lane before it, the right neighbour of its hi
+// pixel the lo pixel of the lane after it, the other two are its own -- ten lane moves per row for two pixels.  Every float
+// expression is min_eigen_kernel's, association included.
+//   Record order inside a region: row-major (rows are walked in order), then ascending x = ascending lane, lo before hi.  A
+// candidate's position is the region's running count + the candidates of BOTH ballots (lo and hi) in the lanes below it
+// within its half of the wave (v_mbcnt_lo on the low words for the lanes 0 .. 31, v_mbcnt_hi on the high words for the lanes
+// 32 .. 63), and a hi candidate follows its own lane's lo candidate.
+//   Image border (EDGE instantiation): a lane's two "virtual" columns outside the image load the gray value of their
+// reflect-101 mirror image (a mirrored pair is adjacent in memory too, in descending order: the same one load, the bytes
+// picked the other way round).  Computed from those, a virtual column's Sobel pair is (-dx, dy) of the mirrored column, exactly (integers, and the float
+// conversion and products are sign-symmetric): dx*dx and dy*dy ARE the products at the mirrored position and dx*dy is its
+// negative, negated back by a sign flip -- the rule "a product outside the image is the product at the mirrored position"
+// with the neighbours still taken from the neighbouring lanes.  In y nothing changes.
+//   Loads: the gray row t + 3 and the mask words of the e row t + 1 are requested in step t, a ring revolution before the
+// step that reads them, so no step waits on a load it issued itself.
+constexpr int kEigWideStripW = 61;
+constexpr int kEigWideMinCols = 8;  // below it the one-column form runs (the wide form's border rule needs cols >= 3; 8 as for the blur)
+
+__global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t* __restrict__ gray,
+                                                                  const uint32_t* __restrict__ mask_bits, int nimg,
+                                                                  int images_per_maskset, int rows, int cols, int nmask,
+                                                                  int strips, int nchunks, int chunk_rows, int wcap,
+                                                                  uint2* __restrict__ cand, uint32_t* __restrict__ wcnt,
+                                                                  uint32_t* __restrict__ mstat) {
+  SOSVO_STREAMING_PRIO();
+  const int lane = threadIdx.x & 63;
+  const int spairs = (strips + 1) >> 1;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kThreads + threadIdx.x) >> 6));
+  if (wave >= nimg * spairs * nchunks) return;  // wave-uniform
+  const int img = wave / (spairs * nchunks);
+  const int rem = wave - img * spairs * nchunks;
+  const int chunk = rem / spairs, sp = rem - chunk * spairs;
+  const int reg_a = (img * nchunks + chunk) * strips + 2 * sp;  // region of the lanes 0 .. 31; reg_a + 1: the lanes 32 .. 63
+  const bool has_b = 2 * sp + 1 < strips;                       // (uniform) the second strip exists
+  const int xb = sp * (2 * kEigWideStripW) - kEigHalo;          // column of lane 0's lo pixel
+  const int x_lo = xb + 2 * lane, x_hi = x_lo + 1;
+  // outputs are the columns xb + 3 .. xb + 124 inside the image (x >= 0 follows)
+  const bool own_lo = lane >= 2 && lane <= 62 && x_lo < cols, own_hi = lane >= 1 && lane <= 61 && x_hi < cols;
+  const bool cd_lo = own_lo && x_lo >= 1 && x_lo <= cols - 2, cd_hi = own_hi && x_hi >= 1 && x_hi <= cols - 2;
+  const uint32_t mask_all = nmask < 32 ? (1u << nmask) - 1u : 0xFFFFFFFFu;
+  const uint32_t am_lo = own_lo ? mask_all : 0u, am_hi = own_hi ? mask_all : 0u;  // a mask word counts in an output column only
+  // gray source of the two virtual columns
+  auto mirror = [&](int x) { return clampi(x < 0 ? -x : (x >= cols ? 2 * (cols - 1) - x : x), 0, cols - 1); };
+  const int m_lo = mirror(x_lo), m_hi = mirror(x_hi);
+  // (a dword load at a column clamped into the row, the two bytes picked out of it where they are used: a 16-bit load is
+  // zero-extended by an instruction of its own, which the compiler places at the load and with it the wait)
+  const int ld_col = clampi(min(m_lo, m_hi), 0, cols - 4);
+  const uint32_t src_col = (uint32_t)ld_col;
+  const uint32_t sh_lo = 8u * (uint32_t)clampi(m_lo - ld_col, 0, 3), sh_hi = 8u * (uint32_t)clampi(m_hi - ld_col, 0, 3);
+  const uint32_t neg_lo = (x_lo < 0 || x_lo >= cols) ? 0x80000000u : 0u, neg_hi = (x_hi < 0 || x_hi >= cols) ? 0x80000000u : 0u;
+  uint32_t* mstat_img = mstat + (size_t)img * nmask * 5;
+  int r_lo = rows, r_hi = 0;  // rows that hold a pixel of some mask of the image's mask set, as in min_eigen_kernel
+  {
+    const uint32_t* sbb = mstat + (size_t)(img / images_per_maskset) * images_per_maskset * nmask * 5;
+    for (int m = 0; m < nmask; ++m) {
+      const uint32_t y1 = sbb[m * 5 + 4];
+      if (y1) {
+        r_lo = min(r_lo, (int)(0xFFFFFFFFu - sbb[m * 5 + 2]));
+        r_hi = max(r_hi, (int)y1);
+      }
+    }
+  }
+  const int ys = max(chunk * chunk_rows, r_lo), ye = min(min(rows, chunk * chunk_rows + chunk_rows), r_hi);
+  if (ys >= ye) {
+    if (lane == 0) {
+      wcnt[reg_a] = 0u;
+      if (has_b) wcnt[reg_a + 1] = 0u;
+    }
+    return;
+  }
+  const int e_lo = max(ys - 1, 0), e_hi = min(ye, rows - 1);
+  const int f_lo = max(ys, 1), f_hi = min(ye, rows - 1) - 1;
+  const uint8_t* g = gray + (size_t)img * rows * cols;
+  uint2* region = cand + (size_t)(reg_a + (lane >> 5)) * wcap;  // the lane's region
+  int wpos_a = 0, wpos_b = 0;                                  // records emitted so far (wave-uniform)
+  const uint32_t* mb = mask_bits + (size_t)(img / images_per_maskset) * rows * cols;
+  const float scale = (float)(1.0 / 3060.0);
+
+  int hd_l[3] = {0, 0, 0}, hs_l[3] = {0, 0, 0}, hd_h[3] = {0, 0, 0}, hs_h[3] = {0, 0, 0};
+  float pxx_l[3] = {0.f, 0.f, 0.f}, pxy_l[3] = {0.f, 0.f, 0.f}, pyy_l[3] = {0.f, 0.f, 0.f};
+  float pxx_h[3] = {0.f, 0.f, 0.f}, pxy_h[3] = {0.f, 0.f, 0.f}, pyy_h[3] = {0.f, 0.f, 0.f};
+  float hm_l[3] = {0.f, 0.f, 0.f}, ec_l[3] = {0.f, 0.f, 0.f}, hm_h[3] = {0.f, 0.f, 0.f}, ec_h[3] = {0.f, 0.f, 0.f};
+  uint32_t bits_l = 0u, max_l = 0u, bits_h = 0u, max_h = 0u;  // running per-mask maximum of the lo / hi column
+  uint32_t mprev_l = 0u, mprev_h = 0u;                        // mask words of the row the flag stage looks at
+  const int t_first = e_lo - 2, t_last = e_hi + 2;
+  const bool edge_strip = xb < 0 || xb + 128 > cols;  // wave-uniform: some lane's column is outside the image
+  uint32_t c_pre[3] = {0u, 0u, 0u}, mw_l[3] = {0u, 0u, 0u}, mw_h[3] = {0u, 0u, 0u};
+  auto request = [&](auto slot_tag, auto edge_tag, const int t) __attribute__((always_inline)) {  // row t -> slot t mod 3
+    constexpr int P = decltype(slot_tag)::value;
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    c_pre[P] = *reinterpret_cast<const u32_unaligned*>(g + ((uint32_t)(refl101(min(t, t_last), rows) * cols) + src_col));
+    const int y = t - 2;  // the e row that step t finishes
+    mw_l[P] = 0u;
+    mw_h[P] = 0u;
+    if (y >= ys && y < ye) {  // uniform; 0 <= y < rows follows
+      if (EDGE) {  // (an own column lies inside the image)
+        if (own_lo) mw_l[P] = mb[(uint32_t)(y * cols) + (uint32_t)x_lo];
+        if (own_hi) mw_h[P] = mb[(uint32_t)(y * cols) + (uint32_t)x_hi];
+      } else {  // all 128 columns lie inside the image: x_lo >= 0
+        uint32_t w[2];
+        __builtin_memcpy(w, mb + ((uint32_t)(y * cols) + (uint32_t)x_lo), 8);
+        mw_l[P] = w[0];
+        mw_h[P] = w[1];
+      }
+    }
+  };
+  auto eig = [&](float xx0, float xx1, float xx2, float xy0, float xy1, float xy2, float yy0, float yy1, float yy2) {
+    const float a = ((xx0 + xx1) + xx2) * 0.5f, b = (xy0 + xy1) + xy2;
+    const float c = ((yy0 + yy1) + yy2) * 0.5f;
+    return (a + c) - sqrt_rn_normal(((a - c) * (a - c)) + (b * b));
+  };
+  auto step = [&](auto phase_tag, auto edge_tag, const int t) __attribute__((always_inline)) {
+    constexpr int P = decltype(phase_tag)::value;
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    constexpr int i0 = (P + 1) % 3, i1 = (P + 2) % 3, i2 = P;  // slots of rows t-2, t-1, t
+    if (t > t_last) return;  // uniform
+    const uint32_t c = c_pre[P];
+    const uint32_t mb_l = mw_l[P] & am_lo, mb_h = mw_h[P] & am_hi;  // mask words of the e row t - 2
+    request(phase_tag, edge_tag, t + 3);
+    {
+      const int cl = (int)((c >> sh_lo) & 0xFFu), ch = (int)((c >> sh_hi) & 0xFFu);
+      const int l = lane_from_left(ch), r = lane_from_right(cl);
+      hd_l[i2] = ch - l;
+      hs_l[i2] = (l + 2 * cl) + ch;
+      hd_h[i2] = r - cl;
+      hs_h[i2] = (cl + 2 * ch) + r;
+    }
+    const int v = t - 1;
+    if (v < e_lo - 1) return;  // uniform
+    {
+      const float dx_l = (float)((hd_l[i0] + 2 * hd_l[i1]) + hd_l[i2]) * scale, dy_l = (float)(hs_l[i2] - hs_l[i0]) * scale;
+      const float dx_h = (float)((hd_h[i0] + 2 * hd_h[i1]) + hd_h[i2]) * scale, dy_h = (float)(hs_h[i2] - hs_h[i0]) * scale;
+      const float xx_l = dx_l * dx_l, yy_l = dy_l * dy_l, xx_h = dx_h * dx_h, yy_h = dy_h * dy_h;
+      float xy_l = dx_l * dy_l, xy_h = dx_h * dy_h;
+      if (v < 0 || v >= rows) {  // mirrored row: dy came out negated
+        xy_l = -xy_l;
+        xy_h = -xy_h;
+      }
+      if (EDGE) {  // mirrored column: dx came out negated
+        xy_l = __uint_as_float(__float_as_uint(xy_l) ^ neg_lo);
+        xy_h = __uint_as_float(__float_as_uint(xy_h) ^ neg_hi);
+      }
+      pxx_l[i2] = (lane_from_left(xx_h) + xx_l) + xx_h;
+      pxx_h[i2] = (xx_l + xx_h) + lane_from_right(xx_l);
+      pxy_l[i2] = (lane_from_left(xy_h) + xy_l) + xy_h;
+      pxy_h[i2] = (xy_l + xy_h) + lane_from_right(xy_l);
+      pyy_l[i2] = (lane_from_left(yy_h) + yy_l) + yy_h;
+      pyy_h[i2] = (yy_l + yy_h) + lane_from_right(yy_l);
+    }
+    const int y = v - 1;
+    if (y < e_lo) return;  // uniform
+    {
+      const float e_l = eig(pxx_l[i0], pxx_l[i1], pxx_l[i2], pxy_l[i0], pxy_l[i1], pxy_l[i2], pyy_l[i0], pyy_l[i1], pyy_l[i2]);
+      const float e_h = eig(pxx_h[i0], pxx_h[i1], pxx_h[i2], pxy_h[i0], pxy_h[i1], pxy_h[i2], pyy_h[i0], pyy_h[i1], pyy_h[i2]);
+      // per-mask maximum: a mask word is 0 outside the output columns and the rows ys .. ye - 1, and a run under the word 0
+      // is never flushed
+      if (mb_l != bits_l) {
+        eig_flush(mstat_img, bits_l, max_l);
+        bits_l = mb_l;
+        max_l = 0u;
+      }
+      max_l = max(max_l, sosvo_float_ordered(e_l));
+      if (mb_h != bits_h) {
+        eig_flush(mstat_img, bits_h, max_h);
+        bits_h = mb_h;
+        max_h = 0u;
+      }
+      max_h = max(max_h, sosvo_float_ordered(e_h));
+      hm_l[i2] = fmaxf(fmaxf(lane_from_left(e_h), e_l), e_h);
+      hm_h[i2] = fmaxf(fmaxf(e_l, e_h), lane_from_right(e_l));
+      ec_l[i2] = e_l;
+      ec_h[i2] = e_h;
+    }
+    const int f = y - 1;
+    const uint32_t mf_l = mprev_l, mf_h = mprev_h;  // row f was the e row of the previous step
+    mprev_l = mb_l;
+    mprev_h = mb_h;
+    if (f < f_lo || f > f_hi) return;  // uniform
+    {
+      const float ev_l = ec_l[i1], ev_h = ec_h[i1];
+      const bool is_l = cd_lo && ev_l == fmaxf(fmaxf(hm_l[i0], hm_l[i1]), hm_l[i2]) && ev_l > 0.0f && mf_l != 0u;
+      const bool is_h = cd_hi && ev_h == fmaxf(fmaxf(hm_h[i0], hm_h[i1]), hm_h[i2]) && ev_h > 0.0f && mf_h != 0u;
+      const unsigned long long bal_l = __ballot(is_l), bal_h = __ballot(is_h);
+      if (bal_l | bal_h) {  // uniform
+        const uint32_t al = (uint32_t)bal_l, ah = (uint32_t)bal_h, bl = (uint32_t)(bal_l >> 32), bh = (uint32_t)(bal_h >> 32);
+        const int below_a = (int)__builtin_amdgcn_mbcnt_lo(al, __builtin_amdgcn_mbcnt_lo(ah, 0u));  // lanes 0 .. 31
+        const int below_b = (int)__builtin_amdgcn_mbcnt_hi(bl, __builtin_amdgcn_mbcnt_hi(bh, 0u));  // lanes 32 .. 63 (0 below them)
+        const int pos_l = lane < 32 ? wpos_a + below_a : wpos_b + below_b, pos_h = pos_l + (is_l ? 1 : 0);
+        if (is_l && pos_l < wcap) region[pos_l] = make_uint2(__float_as_uint(ev_l), ((uint32_t)f << 16) | (uint32_t)x_lo);
+        if (is_h && pos_h < wcap) region[pos_h] = make_uint2(__float_as_uint(ev_h), ((uint32_t)f << 16) | (uint32_t)x_hi);
+        wpos_a += __popc(al) + __popc(ah);
+        wpos_b += __popc(bl) + __popc(bh);
+      }
+    }
+  };
+  auto run = [&](auto edge_tag) __attribute__((always_inline)) {
+    request(std::integral_constant<int, 0>{}, edge_tag, t_first);
+    request(std::integral_constant<int, 1>{}, edge_tag, t_first + 1);
+    request(std::integral_constant<int, 2>{}, edge_tag, t_first + 2);
+    for (int t = t_first; t <= t_last; t += 3) {
+      step(std::integral_constant<int, 0>{}, edge_tag, t);
+      step(std::integral_constant<int, 1>{}, edge_tag, t + 1);
+      step(std::integral_constant<int, 2>{}, edge_tag, t + 2);
+    }
+  };
+  if (edge_strip) run(std::true_type{}); else run(std::false_type{});
+  if (lane == 0) {  // may exceed wcap: the selection kernel reports the overflow
+    wcnt[reg_a] = (uint32_t)wpos_a;
+    if (has_b) wcnt[reg_a + 1] = (uint32_t)wpos_b;
+  }
+  // per-mask maxima: one set of atomics per wave and column parity when all its lanes saw a single mask word
+  auto finish = [&](uint32_t cur_bits, uint32_t cur_max) __attribute__((always_inline)) {
+    const unsigned long long act = __ballot(cur_bits != 0u);
+    if (act) {
+      const int first = __ffsll((long long)act) - 1;
+      const uint32_t b0 = __shfl(cur_bits, first);
+      if (__ballot(cur_bits != 0u && cur_bits != b0) == 0ULL) {
+        uint32_t om = cur_bits != 0u ? cur_max : 0u;
+        for (int s = 32; s > 0; s >>= 1) om = max(om, (uint32_t)__shfl_down((int)om, s));
+        if (lane == 0) eig_flush(mstat_img, b0, om);
+      } else {
+        eig_flush(mstat_img, cur_bits, cur_max);
+      }
+    }
+  };
+  finish(bits_l, max_l);
+  finish(bits_h, max_h);
 }
 
 // Bounding box of every mask of every mask set (depends on the masks only): mstat fields 1..4 of the FIRST
@@ -459,7 +698,7 @@ __device__ __forceinline__ void gft_keep_largest(const gft_regions g, unsigned l
 
 template <int CAND, int NT>
 __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict__ cand,
-                                                              const uint32_t* __restrict__ wcnt, int strips, int nchunks,
+                                                              const uint32_t* __restrict__ wcnt, int strip_w, int strips, int nchunks,
                                                               int chunk_rows, int wcap, const uint32_t* __restrict__ mask_bits,
                                                               const uint32_t* __restrict__ mstat, int images_per_maskset,
                                                               int nmask, int rows, int cols, double quality,
@@ -507,7 +746,7 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   if (any && bw > 0 && bh > 0) {
     const float thr = (float)((double)sosvo_ordered_float(st[0]) * quality);
     const uint32_t* mb = mask_bits + (size_t)(img / images_per_maskset) * rows * cols;
-    const int s0 = bx0 / kEigStripW, s1 = bx1 / kEigStripW;
+    const int s0 = bx0 / strip_w, s1 = bx1 / strip_w;  // (the strip width of the response kernel that wrote the regions)
     const int c0 = by0 / chunk_rows, c1 = by1 / chunk_rows;
     // The regions (strip, row chunk) that meet the bounding box, NT at a time: every thread fetches ONE region's count (the
     // dependent global loads of a region-by-region walk were most of this phase), then the waves take the regions round-robin,
@@ -560,8 +799,8 @@ __global__ __launch_bounds__(NT) void gft_select_kernel(const uint2* __restrict_
   }
   if (__builtin_expect(total > CAND, 0)) {  // uniform, and rare: the slots above went to whichever waves came first -- gather the CAND largest keys
     const gft_regions g = {cand, wcnt, mask_bits + (size_t)(img / images_per_maskset) * rows * cols, img, m, cols, strips, nchunks, wcap,
-                           bx0 / kEigStripW, by0 / chunk_rows, bx1 / kEigStripW - bx0 / kEigStripW + 1,
-                           (by1 / chunk_rows - by0 / chunk_rows + 1) * (bx1 / kEigStripW - bx0 / kEigStripW + 1),
+                           bx0 / strip_w, by0 / chunk_rows, bx1 / strip_w - bx0 / strip_w + 1,
+                           (by1 / chunk_rows - by0 / chunk_rows + 1) * (bx1 / strip_w - bx0 / strip_w + 1),
                            (float)((double)sosvo_ordered_float(st[0]) * quality)};
     gft_keep_largest<CAND, NT>(g, keys, s_region, &s_count, s_sel, tid);
     __syncthreads();
@@ -910,10 +1149,108 @@ __global__ __launch_bounds__(kThreads) void gauss7_kernel(const uint8_t* __restr
   if (edge_strip) run(std::true_type{}); else run(std::false_type{});
 }
 
+// ---- K6a, four columns per lane -------------------------------------------------------------------------------
+// The same rolling walk with a lane holding four adjacent gray bytes of a row as one dword C (layout, load offsets and the
+// border rule: rolling_layout.h): a wave covers 256 columns and owns 250 outputs.  L and R are the neighbouring lanes' dwords
+// (two lane moves per row for four pixels instead of six for one); the horizontal sum of pixel j of the lane is two
+// v_dot4_u32_u8, over the bytes j-3 .. j with the weights (18, 34, 49, 54) and over j+1 .. j+4 with (49, 34, 18, 0), the byte
+// windows cut out of (L, C) and (C, R) by v_alignbyte_b32 -- the windows of j = 3 are C and R themselves.  Integer arithmetic
+// below 2^24: the value is gauss7_kernel's whatever the order.  The vertical pass is per pixel as there; the rounding
+// constant rides in the first multiply-add, and the four output bytes leave as one dword where all four columns are outputs
+// inside the image, in smaller stores otherwise.
+// At the image border (EDGE instantiation) one v_perm_b32 per row turns the lane's load -- taken at an offset clamped into
+// the row -- into its four virtual columns, mirrored ones included; L and R then come from the neighbours as in the interior.
+// Lanes 0 / 63 receive L = 0 / R = 0: byte 3 of lane 0 does not read L, and byte 0 of lane 63 reads R under the weight 0.
+__global__ __launch_bounds__(kThreads) void gauss7_wide_kernel(const uint8_t* __restrict__ gray, long long img_stride, int nimg,
+                                                               int rows, int cols, int strips, int nchunks, int chunk_rows,
+                                                               uint8_t* __restrict__ out, long long out_stride,
+                                                               const int32_t* __restrict__ row_range, int imgs_per_range) {
+  SOSVO_STREAMING_PRIO();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * kThreads + threadIdx.x) >> 6));
+  if (wave >= nimg * strips * nchunks) return;  // wave-uniform
+  const int img = wave / (strips * nchunks);
+  const int rem = wave - img * strips * nchunks;
+  const int chunk = rem / strips, strip = rem - chunk * strips;
+  const sosvo_blur_wide_lane lay = sosvo_blur_wide_layout(cols, strip, lane);
+  const int x0 = strip * SOSVO_BLUR_WIDE_STRIP_W - 3 + 4 * lane;  // the lane's first column: a store happens only where it is inside the image
+  int ys = chunk * chunk_rows, ye = min(rows, ys + chunk_rows);
+  if (row_range) {  // wave-uniform, as in gauss7_kernel
+    const int v = img / imgs_per_range;
+    ys = max(ys, row_range[2 * v]);
+    ye = min(ye, row_range[2 * v + 1]);
+    if (ys >= ye) return;
+  }
+  const uint8_t* g = gray + (size_t)img * img_stride;
+  uint8_t* o = out + (size_t)img * out_stride;
+  // The lane's outputs are a run of nb adjacent bytes from byte jb on (lay.own): all four leave as a dword, otherwise two of
+  // them as a 16-bit store and / or the last one as a byte (lanes 0 and 63 own one column each; so may the lane that holds the
+  // image's last column).  Stores touch owned columns only: x0 + jb >= 0 wherever a store is enabled.
+  const int jb = lay.own ? __builtin_ctz(lay.own) : 0, nb = __builtin_popcount(lay.own);
+  const bool st_dword = nb == 4, st_short = nb == 2 || nb == 3, st_byte = nb == 1 || nb == 3;
+  const uint32_t st_x = (uint32_t)(x0 + jb), st_shift = 8u * (uint32_t)jb;
+  const uint32_t st_xb = (uint32_t)(x0 + jb + nb - 1), st_shiftb = 8u * (uint32_t)(st_byte ? jb + nb - 1 : 0);
+  const uint32_t ld_x = (uint32_t)lay.off;
+  uint32_t h[7][4];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) h[k][0] = h[k][1] = h[k][2] = h[k][3] = 0u;
+  const bool edge_strip = sosvo_blur_wide_edge_strip(cols, strip) != 0;  // wave-uniform
+  const int t_first = ys - 3, t_last = ye + 2;
+  const uint32_t w_lo = 0x36312212u, w_hi = 0x00122231u;  // byte weights (18, 34, 49, 54) and (49, 34, 18, 0)
+  uint32_t c_pre[7];
+  auto request = [&](int t0, int k0, int k1) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+      if (k >= k0 && k < k1)
+        c_pre[k] = *reinterpret_cast<const u32_unaligned*>(g + ((uint32_t)(refl101(min(t0 + k, t_last), rows) * cols) + ld_x));
+  };
+  request(t_first, 0, 7);
+  auto step = [&](auto phase_tag, auto edge_tag, const int t) __attribute__((always_inline)) {
+    constexpr int P = decltype(phase_tag)::value;
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    if (t > t_last) return;  // uniform
+    uint32_t c = c_pre[P];   // gray row t
+    if (EDGE) c = __builtin_amdgcn_perm(c, c, lay.sel);
+    const uint32_t l = (uint32_t)lane_from_left((int)c), r = (uint32_t)lane_from_right((int)c);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      h[P][j] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(c, l, j + 1), w_lo,
+                                       __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(r, c, j + 1), w_hi, 0u, false), false);
+    h[P][3] = __builtin_amdgcn_udot4(c, w_lo, __builtin_amdgcn_udot4(r, w_hi, 0u, false), false);
+    const int y = t - 3;
+    if (y < ys) return;  // uniform
+    // rows y-3 .. y+3 = t-6 .. t live in slots P+1 .. P+7 (mod 7); s = vertical sum + 32768, the output byte is its bits 16 .. 23
+    uint32_t s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      s[j] = vmad24(18u, h[(P + 1) % 7][j] + h[P][j], vmad24(34u, h[(P + 2) % 7][j] + h[(P + 6) % 7][j],
+                    vmad24(49u, h[(P + 3) % 7][j] + h[(P + 5) % 7][j], vmad24(54u, h[(P + 4) % 7][j], 32768u))));
+    const uint32_t p01 = __builtin_amdgcn_perm(s[1], s[0], 0x0C0C0602u), p23 = __builtin_amdgcn_perm(s[3], s[2], 0x0C0C0602u);
+    const uint32_t pk = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
+    const uint32_t oy = (uint32_t)(y * cols);
+    if (st_dword) *reinterpret_cast<u32_unaligned*>(o + (oy + st_x)) = pk;
+    if (st_short) *reinterpret_cast<u16_unaligned*>(o + (oy + st_x)) = (uint16_t)(pk >> st_shift);
+    if (st_byte) o[oy + st_xb] = (uint8_t)(pk >> st_shiftb);
+  };
+  auto run = [&](auto edge_tag) __attribute__((always_inline)) {
+    for (int t = t_first; t <= t_last; t += 7) {
+      step(std::integral_constant<int, 0>{}, edge_tag, t);
+      step(std::integral_constant<int, 1>{}, edge_tag, t + 1);
+      step(std::integral_constant<int, 2>{}, edge_tag, t + 2);
+      step(std::integral_constant<int, 3>{}, edge_tag, t + 3);
+      request(t + 7, 0, 4);
+      step(std::integral_constant<int, 4>{}, edge_tag, t + 4);
+      step(std::integral_constant<int, 5>{}, edge_tag, t + 5);
+      step(std::integral_constant<int, 6>{}, edge_tag, t + 6);
+      request(t + 7, 4, 7);
+    }
+  };
+  if (edge_strip) run(std::true_type{}); else run(std::false_type{});
+}
+
 // ---- K6b: border rule + descriptors ---------------------------------------------------------------------
 constexpr int kPatchMaxR = 23, kPatchRows = 48, kPatchStride = 64;
 constexpr int kDescRegionBytesGft = 24 * 1024;
-typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
 
 // The rotated BRIEF pattern depends on (pattern, cos_a, sin_a) only: one workgroup per CALL writes it to the call's
 // workspace, every problem's workgroup reads it.  pt[t] is test t's two points in pixels, rounded to nearest, each as
@@ -1171,13 +1508,39 @@ static void rolling_chunks(int nimg, int rows, int strips, int* nchunks, int* ch
   *nchunks = cdiv(rows, *chunk_rows);
 }
 
+// Row chunks of the four-columns-per-lane form.  A wave of it carries the work of four of the one-column form's, so the
+// 16 384-wave target above would cut the bench's batch (1024 images per part, 6 strips of 1440 columns) into three chunks
+// and pay 6 halo rows in each: + 12 % of rows for nothing.  The target here is the number of waves the chip needs, not a
+// multiple of it: 6 per SIMD in one pass, 6 144.  A batch whose (image, strip) pairs reach that runs unchunked; a smaller
+// one (a window of a sequence, a single frame) is cut into cdiv(6144, pairs) chunks of at least 24 rows, as before.
+static void rolling_chunks_wide(int nimg, int rows, int strips, int* nchunks, int* chunk_rows) {
+  int nc = cdiv(6144, nimg * strips);
+  if (nc > rows / 24) nc = rows / 24;
+  if (nc < 1) nc = 1;
+  *chunk_rows = cdiv(rows, nc);
+  *nchunks = cdiv(rows, *chunk_rows);
+}
+
 }  // namespace
 
-// 7x7 sigma-2 blur (8.8 fixed point) of nimg images that lie img_stride bytes apart (shared with the ORB pyramid levels)
+// 7x7 sigma-2 blur (8.8 fixed point) of nimg images that lie img_stride bytes apart (shared with the ORB pyramid levels).
+// Four columns per lane (gauss7_wide_kernel) from SOSVO_BLUR_WIDE_MIN_COLS columns on, unless SOSVO_HINT_ROLLING_NARROW
+// asks for the one-column form; the bytes are the same, and so is the profile label.
 static int32_t launch_gauss7_rows(sosvo_ctx* ctx, const uint8_t* in, long long in_stride, int nimg, int rows, int cols,
                                   uint8_t* out, long long out_stride, const int32_t* row_range, int imgs_per_range) {
-  const int strips = cdiv(cols, kEigStripW);
   int nchunks, chunk_rows;
+  if (cols >= SOSVO_BLUR_WIDE_MIN_COLS && !ctx->hint_rolling_narrow) {
+    const int strips = sosvo_blur_wide_strips(cols);
+    rolling_chunks_wide(nimg, rows, strips, &nchunks, &chunk_rows);
+    {
+      SOSVO_PROFILE(ctx, "gauss7_kernel");
+      hipLaunchKernelGGL(gauss7_wide_kernel, dim3(cdiv(nimg * strips * nchunks, kThreads / 64)), dim3(kThreads), 0, ctx->stream, in,
+                         in_stride, nimg, rows, cols, strips, nchunks, chunk_rows, out, out_stride, row_range, imgs_per_range);
+    }
+    SOSVO_LAUNCH_CHECK(ctx);
+    return SOSVO_OK;
+  }
+  const int strips = cdiv(cols, kEigStripW);
   rolling_chunks(nimg, rows, strips, &nchunks, &chunk_rows);
   SOSVO_LAUNCH(ctx, gauss7_kernel, dim3(cdiv(nimg * strips * nchunks, kThreads / 64)), dim3(kThreads), 0, ctx->stream, in,
                in_stride, nimg, rows, cols, strips, nchunks, chunk_rows, out, out_stride, row_range, imgs_per_range);
@@ -1197,7 +1560,98 @@ int32_t sosvo_launch_gauss7(sosvo_ctx* ctx, const uint8_t* in, long long img_str
   return sosvo_launch_gauss7_to(ctx, in, img_stride, nimg, rows, cols, out, img_stride);
 }
 
+// Geometry of one corner-response launch and where its outputs lie in the workspace.  Two columns per lane
+// (min_eigen_wide_kernel, strips of 61 columns, a wave per PAIR of strips) from kEigWideMinCols columns on, unless
+// SOSVO_HINT_ROLLING_NARROW asks for the one-column form (strips of 58, a wave per strip); regions are numbered
+// (img * nchunks + chunk) * strips + strip in both, and gft_select_kernel gets the strip width that was used.
+struct gft_plan {
+  bool wide;
+  int strip_w, strips, nchunks, chunk_rows, wcap, waves;
+  size_t n_regions, o_cand, o_wcnt, o_stat, end;
+};
+static gft_plan gft_plan_make(const sosvo_ctx* ctx, int nimg, int rows, int cols, int nmask) {
+  gft_plan g;
+  g.wide = cols >= kEigWideMinCols && !ctx->hint_rolling_narrow;
+  g.strip_w = g.wide ? kEigWideStripW : kEigStripW;
+  g.strips = cdiv(cols, g.strip_w);
+  if (g.wide)
+    rolling_chunks_wide(nimg, rows, cdiv(g.strips, 2), &g.nchunks, &g.chunk_rows);
+  else
+    rolling_chunks(nimg, rows, g.strips, &g.nchunks, &g.chunk_rows);
+  g.waves = nimg * g.nchunks * (g.wide ? cdiv(g.strips, 2) : g.strips);
+  // candidate records (8 bytes: response, pixel): a region per (strip, row chunk) with room for EVERY pixel of it -- 3x3
+  // maxima of distinct values fill at most a quarter of it, but an exactly periodic texture gives a plateau of equal
+  // positive responses on which every pixel is a candidate, and goodFeaturesToTrack handles that; only what is written
+  // costs traffic
+  g.wcap = (g.chunk_rows * g.strip_w + 63) & ~63;
+  g.n_regions = (size_t)nimg * g.strips * g.nchunks;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  g.o_cand = carve(sizeof(uint2) * g.n_regions * g.wcap);
+  g.o_wcnt = carve(sizeof(uint32_t) * g.n_regions);
+  g.o_stat = carve(sizeof(uint32_t) * (size_t)nimg * nmask * 5);
+  g.end = off;
+  return g;
+}
+// mstat cleared, mask bounding boxes, the response kernel: candidate records, their counts and the per-mask maxima
+static int32_t gft_launch_response(sosvo_ctx* ctx, const gft_plan& g, const uint8_t* gray, const uint32_t* mask_bits, int nimg,
+                                   int images_per_maskset, int rows, int cols, int nmask) {
+  char* ws = (char*)ctx->ws;
+  uint2* cand = (uint2*)(ws + g.o_cand);
+  uint32_t* wcnt = (uint32_t*)(ws + g.o_wcnt);
+  uint32_t* mstat = (uint32_t*)(ws + g.o_stat);
+  SOSVO_HIP(ctx, hipMemsetAsync(mstat, 0, sizeof(uint32_t) * (size_t)nimg * nmask * 5, ctx->stream));
+  const int nsets = cdiv(nimg, images_per_maskset);
+  SOSVO_LAUNCH(ctx, mask_bbox_kernel, dim3(rows, nsets), dim3(kThreads), 0, ctx->stream, mask_bits, images_per_maskset, rows,
+               cols, nmask, mstat);
+  SOSVO_LAUNCH_CHECK(ctx);
+  if (g.wide) {
+    SOSVO_PROFILE(ctx, "min_eigen_kernel");
+    hipLaunchKernelGGL(min_eigen_wide_kernel, dim3(cdiv(g.waves, kThreads / 64)), dim3(kThreads), 0, ctx->stream, gray, mask_bits,
+                       nimg, images_per_maskset, rows, cols, nmask, g.strips, g.nchunks, g.chunk_rows, g.wcap, cand, wcnt, mstat);
+  } else {
+    SOSVO_LAUNCH(ctx, min_eigen_kernel, dim3(cdiv(g.waves, kThreads / 64)), dim3(kThreads), 0, ctx->stream, gray, mask_bits, nimg,
+                 images_per_maskset, rows, cols, nmask, g.strips, g.nchunks, g.chunk_rows, g.wcap, cand, wcnt, mstat);
+  }
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
 extern "C" {
+
+int32_t sosvo_detect_gft_candidates(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask_bits, int32_t nimg,
+                                    int32_t images_per_maskset, int32_t rows, int32_t cols, int32_t nmask, int32_t* geometry,
+                                    uint32_t* cand_out, uint32_t* wcnt_out, uint32_t* mstat_out) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, geometry, "null pointer");
+  SOSVO_REQUIRE(ctx, nimg >= 1 && nimg <= 65535 && images_per_maskset > 0, "nimg out of range");
+  SOSVO_REQUIRE(ctx, rows >= 3 && cols >= 3 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
+  SOSVO_REQUIRE(ctx, rows <= 65535 && cols <= 65535, "image sizes out of range (the candidates are packed as y << 16 | x)");
+  SOSVO_REQUIRE(ctx, nmask >= 1 && nmask <= kMaxMasks, "nmask out of range (1..32)");
+  const gft_plan g = gft_plan_make(ctx, nimg, rows, cols, nmask);
+  SOSVO_REQUIRE(ctx, g.n_regions * (size_t)g.wcap < ((size_t)1 << 31), "too many candidate slots for this entry point");
+  geometry[0] = g.strip_w;
+  geometry[1] = g.strips;
+  geometry[2] = g.nchunks;
+  geometry[3] = g.chunk_rows;
+  geometry[4] = g.wcap;
+  geometry[5] = (int32_t)g.n_regions;
+  if (!cand_out && !wcnt_out && !mstat_out) return SOSVO_OK;  // the sizes only
+  SOSVO_REQUIRE(ctx, gray && mask_bits && cand_out && wcnt_out && mstat_out, "null pointer");
+  int32_t rc = sosvo_ws_reserve(ctx, g.end);
+  if (rc != SOSVO_OK) return rc;
+  rc = gft_launch_response(ctx, g, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
+  if (rc != SOSVO_OK) return rc;
+  const char* ws = (const char*)ctx->ws;
+  SOSVO_HIP(ctx, hipMemcpyAsync(cand_out, ws + g.o_cand, sizeof(uint2) * g.n_regions * g.wcap, hipMemcpyDeviceToDevice, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(wcnt_out, ws + g.o_wcnt, sizeof(uint32_t) * g.n_regions, hipMemcpyDeviceToDevice, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(mstat_out, ws + g.o_stat, sizeof(uint32_t) * (size_t)nimg * nmask * 5, hipMemcpyDeviceToDevice, ctx->stream));
+  return SOSVO_OK;
+}
 
 int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* mask_bits, int32_t nimg,
                          int32_t images_per_maskset, int32_t rows, int32_t cols, int32_t nmask, double quality,
@@ -1214,24 +1668,14 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   SOSVO_REQUIRE(ctx, cap > 0 && cap <= 4096 && quality > 0 && min_distance >= 0, "bad detector parameters (quality > 0)");
   if (nimg == 0) return SOSVO_OK;
   const size_t P = (size_t)nimg * nmask;
-  size_t off = 0;
+  const gft_plan g = gft_plan_make(ctx, nimg, rows, cols, nmask);
+  size_t off = g.end;
   auto carve = [&](size_t bytes) {
     size_t o = off;
     off += (bytes + 255) & ~(size_t)255;
     return o;
   };
-  const int strips = cdiv(cols, kEigStripW);
-  int nchunks, chunk_rows;
-  rolling_chunks(nimg, rows, strips, &nchunks, &chunk_rows);
-  // candidate records (8 bytes: response, pixel): a region per wave of min_eigen_kernel with room for EVERY pixel of its
-  // (strip, row chunk) -- 3x3 maxima of distinct values fill at most a quarter of it, but an exactly periodic texture
-  // gives a plateau of equal positive responses on which every pixel is a candidate, and goodFeaturesToTrack handles
-  // that; only what is written costs traffic
-  const int wcap = (chunk_rows * kEigStripW + 63) & ~63;
-  const size_t n_waves = (size_t)nimg * strips * nchunks;
-  const size_t o_cand = carve(sizeof(uint2) * n_waves * wcap);
-  const size_t o_wcnt = carve(sizeof(uint32_t) * n_waves);
-  const size_t o_stat = carve(sizeof(uint32_t) * P * 5);
+  const int strip_w = g.strip_w, strips = g.strips, nchunks = g.nchunks, chunk_rows = g.chunk_rows, wcap = g.wcap;
   const bool large = cap > 1024;  // whole-image masks (RGB-D frames): 16384 candidates, 15872 grid cells
   const int sorted_stride = large ? kCandCapLarge : kCandCap;
   const size_t o_sorted = carve(sizeof(uint32_t) * P * sorted_stride);
@@ -1239,36 +1683,28 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   int32_t rc = sosvo_ws_reserve(ctx, off);
   if (rc != SOSVO_OK) return rc;
   char* ws = (char*)ctx->ws;
-  uint2* cand = (uint2*)(ws + o_cand);
-  uint32_t* wcnt = (uint32_t*)(ws + o_wcnt);
-  uint32_t* mstat = (uint32_t*)(ws + o_stat);
+  uint2* cand = (uint2*)(ws + g.o_cand);
+  uint32_t* wcnt = (uint32_t*)(ws + g.o_wcnt);
+  uint32_t* mstat = (uint32_t*)(ws + g.o_stat);
   uint32_t* sorted_g = (uint32_t*)(ws + o_sorted);
-  SOSVO_HIP(ctx, hipMemsetAsync(mstat, 0, sizeof(uint32_t) * P * 5, ctx->stream));
-
-  const int nsets = cdiv(nimg, images_per_maskset);
-  SOSVO_LAUNCH(ctx, mask_bbox_kernel, dim3(rows, nsets), dim3(kThreads), 0, ctx->stream, mask_bits, images_per_maskset, rows,
-               cols, nmask, mstat);
-  SOSVO_LAUNCH_CHECK(ctx);
-  const int waves = nimg * strips * nchunks;
-  SOSVO_LAUNCH(ctx, min_eigen_kernel, dim3(cdiv(waves, kThreads / 64)), dim3(kThreads), 0, ctx->stream, gray, mask_bits, nimg,
-               images_per_maskset, rows, cols, nmask, strips, nchunks, chunk_rows, wcap, cand, wcnt, mstat);
-  SOSVO_LAUNCH_CHECK(ctx);
+  rc = gft_launch_response(ctx, g, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
+  if (rc != SOSVO_OK) return rc;
   const int cell = min_distance >= 1 ? (int)lrint(min_distance) : 1;
   int32_t* redo = (int32_t*)(ws + o_redo);
   if (large) {
     SOSVO_PROFILE(ctx, "gft_select_kernel");
     hipLaunchKernelGGL((gft_select_kernel<kCandCapLarge, 1024>), dim3(xcd_grid(nimg, nmask)), dim3(1024), 0, ctx->stream, cand, wcnt,
-                       strips, nchunks, chunk_rows, wcap, mask_bits, mstat, images_per_maskset, nmask, rows, cols, quality, (float)min_distance, cell,
+                       strip_w, strips, nchunks, chunk_rows, wcap, mask_bits, mstat, images_per_maskset, nmask, rows, cols, quality, (float)min_distance, cell,
                        max_corners, cap, sorted_g, sorted_stride, kp, n, status, nullptr, 0, nimg);
   } else {
     // Few problems (a window of a sequence, a handful of large frames): eight waves per workgroup share the rounds of the
     // greedy pass and the sort; many problems (the C2 batch: 4096 per launch): four, so that twice as many are resident.
     SOSVO_PROFILE(ctx, "gft_select_kernel");
     auto launch = [&](auto small, auto full, int nt) {
-      hipLaunchKernelGGL(small, dim3(xcd_grid(nimg, nmask)), dim3(nt), 0, ctx->stream, cand, wcnt, strips, nchunks, chunk_rows, wcap,
+      hipLaunchKernelGGL(small, dim3(xcd_grid(nimg, nmask)), dim3(nt), 0, ctx->stream, cand, wcnt, strip_w, strips, nchunks, chunk_rows, wcap,
                          mask_bits, mstat, images_per_maskset, nmask, rows, cols, quality, (float)min_distance, cell, max_corners, cap,
                          sorted_g, sorted_stride, kp, n, status, redo, 0, nimg);
-      hipLaunchKernelGGL(full, dim3(xcd_grid(nimg, nmask)), dim3(nt), 0, ctx->stream, cand, wcnt, strips, nchunks, chunk_rows, wcap,
+      hipLaunchKernelGGL(full, dim3(xcd_grid(nimg, nmask)), dim3(nt), 0, ctx->stream, cand, wcnt, strip_w, strips, nchunks, chunk_rows, wcap,
                          mask_bits, mstat, images_per_maskset, nmask, rows, cols, quality, (float)min_distance, cell, max_corners, cap,
                          sorted_g, sorted_stride, kp, n, status, redo, 1, nimg);
     };
@@ -1279,6 +1715,18 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   }
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
+}
+
+int32_t sosvo_gauss7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int64_t img_stride,
+                     uint8_t* out, int64_t out_stride, const int32_t* row_range) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray && out, "null pointer");
+  SOSVO_REQUIRE(ctx, nimg >= 0 && nimg <= 65535, "nimg out of range");
+  SOSVO_REQUIRE(ctx, rows >= 1 && cols >= 1 && rows * (int64_t)cols < (1 << 28), "image sizes out of range");
+  SOSVO_REQUIRE(ctx, img_stride >= rows * (int64_t)cols && out_stride >= rows * (int64_t)cols, "a stride is shorter than an image");
+  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
+  if (nimg == 0) return SOSVO_OK;
+  return launch_gauss7_rows(ctx, gray, img_stride, nimg, rows, cols, out, out_stride, row_range, nimg > 1 ? nimg / 2 : 1);
 }
 
 int32_t sosvo_describe_orb(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,

@@ -116,6 +116,11 @@ class Context(object):
         instead of splitting it (same keys, bit for bit; for A/B measurements)."""
         self._call(self._lib.sosvo_set_hint, _lib.HINT_MATCH_UNSPLIT, 1 if on else 0)
 
+    def set_hint_rolling_narrow(self, on=True):
+        """sosvo_set_hint(SOSVO_HINT_ROLLING_NARROW): the rolling image kernels in their one-column-per-lane form at every
+        width (same bytes; for A/B measurements and the cross-check of the two forms)."""
+        self._call(self._lib.sosvo_set_hint, _lib.HINT_ROLLING_NARROW, 1 if on else 0)
+
     def set_hint_score_fp64_only(self, on=True):
         """sosvo_set_hint(SOSVO_HINT_SCORE_FP64_ONLY): RANSAC scoring without its single-precision first tier (same counts;
         for A/B measurements and the cross-check of the two forms)."""
@@ -332,6 +337,48 @@ class Context(object):
         self._call(self._lib.sosvo_describe_orb_rows, _ptr(gray), NI, rows, cols, int(nmask), cap, _ptr(kp), _ptr(n),
                    float(cos_a), float(sin_a), _ptr(pattern), int(edge), _ptr(row_range), _ptr(desc))
         return desc
+
+    def detect_gft_candidates(self, gray, mask_bits, images_per_maskset, nmask):
+        """sosvo_detect_gft_candidates: the corner-response half of detect_gft.  gray [NI,rows,cols] u8, mask_bits
+        [NI/images_per_maskset, rows, cols] u32 -> dict(strip_w, strips, nchunks, chunk_rows, wcap, regions, cand
+        [regions, wcap, 2] u32 (response bits, y << 16 | x), wcnt [regions] u32, mstat [NI*nmask, 5] u32)."""
+        _check(gray, torch.uint8, "gray", ndim=3)
+        NI, rows, cols = gray.shape
+        _check(mask_bits, torch.uint32, "mask_bits", (None, rows, cols))
+        if mask_bits.shape[0] * images_per_maskset < NI:
+            raise SosvoError("mask_bits has too few sets for %d images" % NI)
+        geo = (ctypes.c_int32 * 6)()
+        args = (_ptr(gray), _ptr(mask_bits), NI, int(images_per_maskset), rows, cols, int(nmask), geo)
+        self._call(self._lib.sosvo_detect_gft_candidates, *(args + (NULL, NULL, NULL)))
+        strip_w, strips, nchunks, chunk_rows, wcap, regions = [int(v) for v in geo]
+        cand = torch.zeros((regions, wcap, 2), dtype=torch.uint32, device=gray.device)
+        wcnt = torch.zeros((regions,), dtype=torch.uint32, device=gray.device)
+        mstat = torch.zeros((NI * int(nmask), 5), dtype=torch.uint32, device=gray.device)
+        self._call(self._lib.sosvo_detect_gft_candidates, *(args + (_ptr(cand), _ptr(wcnt), _ptr(mstat))))
+        return dict(strip_w=strip_w, strips=strips, nchunks=nchunks, chunk_rows=chunk_rows, wcap=wcap, regions=regions,
+                    cand=cand, wcnt=wcnt, mstat=mstat)
+
+    def gauss7(self, gray, nimg, rows, cols, out=None, img_stride=None, out_stride=None, row_range=None):
+        """sosvo_gauss7: the descriptor stage's 7x7 sigma-2 blur on its own.  gray and out are FLAT u8 tensors that hold image
+        i at element i * img_stride / i * out_stride (default rows * cols: a dense [nimg, rows, cols] batch, which may also
+        be passed as such); only the images' own bytes are read and written.  row_range (int32 [2,2] on the device, nimg
+        even): only those rows of each view are written.  Returns out."""
+        nimg, rows, cols = int(nimg), int(rows), int(cols)
+        px = rows * cols
+        img_stride = px if img_stride is None else int(img_stride)
+        out_stride = px if out_stride is None else int(out_stride)
+        _check(gray, torch.uint8, "gray")
+        if out is None:
+            out = torch.zeros(max(nimg - 1, 0) * out_stride + px, dtype=torch.uint8, device=gray.device)
+        _check(out, torch.uint8, "out")
+        if nimg < 0 or rows < 1 or cols < 1 or img_stride < px or out_stride < px:
+            raise SosvoError("gauss7: nimg >= 0, rows, cols >= 1 and strides >= rows * cols")
+        if nimg > 0 and (gray.numel() < (nimg - 1) * img_stride + px or out.numel() < (nimg - 1) * out_stride + px):
+            raise SosvoError("gauss7: a buffer is shorter than (nimg - 1) * stride + rows * cols")
+        if row_range is not None:
+            _check(row_range, torch.int32, "row_range", (2, 2))
+        self._call(self._lib.sosvo_gauss7, _ptr(gray), nimg, rows, cols, img_stride, _ptr(out), out_stride, _ptr(row_range))
+        return out
 
     def refine_subpix(self, gray, kp, n, nmask, half=5, max_iter=_lib.SUBPIX_MAX_ITER, eps=_lib.SUBPIX_EPS, row_range=None):
         """cv2.cornerSubPix in exact integers (sosvo_refine_subpix): refines kp [NI*nmask, cap, 2] f32 in place on gray
