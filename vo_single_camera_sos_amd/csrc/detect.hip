@@ -1328,6 +1328,17 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
       b[r] = (d.y >> 16) * pitch + (int)(short)d.y;
     }
   };
+  // A descriptor's four ballots to its 32 bytes: lane 0 holds the eight halves (eight moves of scalars) and stores them as
+  // two 16-byte pieces at a 32-bit offset from the problem's first row, a scalar.  (`desc` is 8-byte aligned, hence the type.)
+  struct __attribute__((packed, aligned(8))) desc_half { uint32_t w[4]; };
+  uint8_t* const desc_p = desc + (size_t)p * cap * 32;
+  auto store_desc = [&](int j, const unsigned long long* bal) __attribute__((always_inline)) {
+    if (lane == 0) {
+      desc_half* d = reinterpret_cast<desc_half*>(desc_p + ((uint32_t)j << 5));
+      d[0] = desc_half{{(uint32_t)bal[0], (uint32_t)(bal[0] >> 32), (uint32_t)bal[1], (uint32_t)(bal[1] >> 32)}};
+      d[1] = desc_half{{(uint32_t)bal[2], (uint32_t)(bal[2] >> 32), (uint32_t)bal[3], (uint32_t)(bal[3] >> 32)}};
+    }
+  };
   // Patch path: the (2R+1)^2 neighbourhood of a keypoint goes through LDS, fetched as unaligned dwords -- a few
   // row segments per lane instead of 512 scattered byte loads.  Patch rows are `pstride` dwords apart with
   // pstride ODD, so the rows spread over all 32 banks (a 64-byte row pitch would leave half of them unused and
@@ -1412,24 +1423,35 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
               if (dst[u] >= 0) patch_area[dst[u]] = v[u];
           }
         }
-        // this lane's eight test points as offsets inside the region (tests lane, 64 + lane, 128 + lane, 192 + lane)
+        // Every keypoint's origin inside the region, once: the float pair of keypoint i is read by this thread only (kp has
+        // its copy already), so the origin takes the place of its x.  __float2int_rn of the same floats: the same integers
+        // as the bounding box saw.
+        int* lds_org = reinterpret_cast<int*>(lds_kp);
+        for (int i = tid; i < m; i += NT) {
+          const int cx = __float2int_rn(lds_kp[2 * i]), cy = __float2int_rn(lds_kp[2 * i + 1]);
+          lds_org[2 * i] = (cy - ry0) * pitch_b + (cx - rx0);
+        }
+        // this lane's eight test points as LDS addresses of the region's origin (tests lane, 64 + lane, 128 + lane,
+        // 192 + lane): the region's base is folded in here, so that a test address in the loop is ONE addition
+        typedef __attribute__((address_space(3))) const uint8_t lds_u8;
         int ra[4], rb[4];
         lane_offsets(pitch_b, ra, rb);
+        const int region_base = (int)(uintptr_t)(lds_u8*)reinterpret_cast<const uint8_t*>(patch_area);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          ra[r] += region_base;
+          rb[r] += region_base;
+          asm volatile("" : "+v"(ra[r]), "+v"(rb[r]));
+        }
         __syncthreads();
-        const uint8_t* region8 = reinterpret_cast<const uint8_t*>(patch_area);
         const int wid_s = __builtin_amdgcn_readfirstlane(wid);
         for (int j = wid_s; j < m; j += NT / 64) {
-          const int cx = __builtin_amdgcn_readfirstlane(__float2int_rn(lds_kp[2 * j]));
-          const int cy = __builtin_amdgcn_readfirstlane(__float2int_rn(lds_kp[2 * j + 1]));
-          const int org = (cy - ry0) * pitch_b + (cx - rx0);
-          unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((size_t)p * cap + j) * 32);
-          unsigned long long mine = 0ULL;
+          const int org = lds_org[2 * j];  // (the same value in every lane)
+          unsigned long long bal[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const unsigned long long bal = __ballot(region8[org + ra[r]] < region8[org + rb[r]]);
-            if (lane == r) mine = bal;
-          }
-          if (lane < 4) d[lane] = mine;  // one 32-byte store
+          for (int r = 0; r < 4; ++r)
+            bal[r] = __ballot(*(lds_u8*)(uintptr_t)(uint32_t)(org + ra[r]) < *(lds_u8*)(uintptr_t)(uint32_t)(org + rb[r]));
+          store_desc(j, bal);
         }
         return;
       }
@@ -1474,14 +1496,10 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
       for (int it = 0; it < kPatchRows / 4; ++it)
         if (it < nit) patch32[lidx[it]] = reg[it];
       if (j + NT / 64 < m) issue(j + NT / 64);  // next keypoint's rows fly while this one is tested
-      unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((size_t)p * cap + j) * 32);
-      unsigned long long mine = 0ULL;
+      unsigned long long bal[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const unsigned long long bal = __ballot(patch[pa[r]] < patch[pb[r]]);
-        if (lane == r) mine = bal;
-      }
-      if (lane < 4) d[lane] = mine;  // one 32-byte store
+      for (int r = 0; r < 4; ++r) bal[r] = __ballot(patch[pa[r]] < patch[pb[r]]);
+      store_desc(j, bal);
     }
     return;
   }
@@ -1489,12 +1507,10 @@ __global__ __launch_bounds__(NT) void orb_describe_kernel(const uint8_t* __restr
   lane_offsets(cols, ga, gb);
   for (int j = wid; j < m; j += NT / 64) {
     const uint8_t* c = im + (size_t)__float2int_rn(lds_kp[2 * j + 1]) * cols + __float2int_rn(lds_kp[2 * j]);
-    unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((size_t)p * cap + j) * 32);
+    unsigned long long bal[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const unsigned long long bal = __ballot(c[ga[r]] < c[gb[r]]);
-      if (lane == 0) d[r] = bal;
-    }
+    for (int r = 0; r < 4; ++r) bal[r] = __ballot(c[ga[r]] < c[gb[r]]);
+    store_desc(j, bal);
   }
 }
 

@@ -441,34 +441,131 @@ __global__ __launch_bounds__(64) void match_l2_kernel(const float* __restrict__ 
   }
 }
 
-// Rank sort: the sort key of query i is (distance << 20 | i); its rank is the number of
-// smaller sort keys.  Keys are unique, so ranks are a permutation and ties on distance
-// keep query order (stable), as Python's sorted() does at camera_models.py:444.
+// Sort by (distance field, query index): ties on distance keep query order (stable), as Python's sorted() does at
+// camera_models.py:444.  One workgroup per problem, two forms with the same result:
+// * n <= kSortRankMaxN: rank sort.  The sort key of query i is (distance << 20 | i); its rank is the number of smaller sort
+//   keys.  Keys are unique, so ranks are a permutation.  O(n^2 / 64) wave-instructions, but next to no fixed cost.
+// * larger n: a stable counting sort over the 12-bit field, O(n).  The histogram is indexed by the field itself; `used` =
+//   the largest field below 0xFFF plus one (0: every key is SOSVO_KEY_NONE), and only the bins 0 .. used are scanned, where
+//   bin `used` stands for NONE in the placement: its exclusive prefix is the number of keys that are not NONE.  The
+//   placement walks the queries 64 at a time in index order (one wave: LDS operations of a wave execute in order, so the
+//   running per-bin positions are exact without a barrier).  Inside a chunk a lane's peers are the lanes with the same bin
+//   (one ballot per bit of the bin index); a lane's position is the bin's running position plus the peers below it, and
+//   the lowest peer advances the running position by the number of peers.
+constexpr int kSortRankMaxN = 64;
+constexpr int kSortBins = 1 << (32 - SOSVO_KEY_SHIFT);  // 4096 values of the field
+
+// Inclusive prefix sum over the 64 lanes through the DPP operand path: four shifts inside the rows of 16 lanes, then the
+// last lane of row 0 / 2 into row 1 / 3 (row_bcast:15) and lane 31 into the upper half (row_bcast:31).
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);  // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);  // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);  // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);  // row_shr:8
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v) {  // (0 is the identity: the shifts fill with zeros)
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false));
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false));
+  return v;
+}
+
 __global__ __launch_bounds__(kThreads) void sort_matches_kernel(const uint32_t* __restrict__ keys,
                                                                 const int32_t* __restrict__ nq,
                                                                 const int32_t* __restrict__ q_slot, int q_stride,
                                                                 int32_t* __restrict__ order) {
   SOSVO_LATENCY_BOUND_PRIO();
-  extern __shared__ uint32_t sk[];
-  const int tid = threadIdx.x;
-  const int p = blockIdx.x;  // problem fastest, tile second (see match_hamming_kernel)
+  extern __shared__ uint32_t sk[];  // rank form: n4 sort keys; counting form: ceil64(n) fields, 16 bits each
+  __shared__ uint32_t bins[kSortBins];
+  __shared__ uint32_t wave_used[kThreads / 64], wave_tot[kThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int p = blockIdx.x;
   const int n = min(nq[q_slot ? q_slot[p] : p], q_stride);
-  const int i0 = blockIdx.y * kThreads;
-  if (i0 >= n) return;
-  const int n4 = (n + 3) & ~3;
+  if (n <= 0) return;
   const uint32_t* src = keys + (size_t)p * q_stride;
-  for (int i = tid; i < n4; i += kThreads)
-    sk[i] = i < n ? ((src[i] & ~SOSVO_KEY_IDX_MASK) | (uint32_t)i) : 0xFFFFFFFFu;
-  __syncthreads();
-  const int i = i0 + tid;
-  const uint32_t mine = i < n ? sk[i] : 0u;
-  int rank = 0;
-  const uint4* sk4 = reinterpret_cast<const uint4*>(sk);
-  for (int j = 0; j < n4 / 4; ++j) {
-    const uint4 v = sk4[j];
-    rank += (v.x < mine) + (v.y < mine) + (v.z < mine) + (v.w < mine);
+  int32_t* dst = order + (size_t)p * q_stride;
+  if (n <= kSortRankMaxN) {  // uniform
+    const int n4 = (n + 3) & ~3;
+    if (tid < n4) sk[tid] = tid < n ? ((src[tid] & ~SOSVO_KEY_IDX_MASK) | (uint32_t)tid) : 0xFFFFFFFFu;
+    __syncthreads();
+    if (tid - lane >= n) return;  // (a whole wave)
+    const uint32_t mine = tid < n ? sk[tid] : 0u;
+    int rank = 0;
+    const uint4* sk4 = reinterpret_cast<const uint4*>(sk);
+    for (int j = 0; j < n4 / 4; ++j) {
+      const uint4 v = sk4[j];
+      rank += (v.x < mine) + (v.y < mine) + (v.z < mine) + (v.w < mine);
+    }
+    if (tid < n) *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(dst) + ((uint32_t)rank << 2)) = tid;
+    return;
   }
-  if (i < n) order[(size_t)p * q_stride + rank] = i;
+  uint16_t* sf = reinterpret_cast<uint16_t*>(sk);
+#pragma unroll
+  for (int k = 0; k < kSortBins / 4 / kThreads; ++k) reinterpret_cast<uint4*>(bins)[k * kThreads + tid] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();  // (a bin is cleared by one wave and counted in by any)
+  {  // fields to LDS (the chunk of the last query filled up with NONE), histogram, largest field below 0xFFF
+    const int n64 = (n + 63) & ~63;
+    uint32_t used = 0u;
+    for (int i = tid; i < n64; i += kThreads) {
+      // (a 32-bit lane offset on the problem's scalar base, here and at the stores)
+      const uint32_t key = i < n ? *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(src) + ((uint32_t)i << 2)) : SOSVO_KEY_NONE;
+      const uint32_t f = key >> SOSVO_KEY_SHIFT;
+      sf[i] = (uint16_t)f;
+      atomicAdd(&bins[f], 1u);
+      used = max(used, (key + (1u << SOSVO_KEY_SHIFT)) >> SOSVO_KEY_SHIFT);  // field + 1, and 0 for the field 0xFFF (wraps)
+    }
+    used = wave_inclusive_max(used);
+    if (lane == 63) wave_used[wid] = used;
+  }
+  __syncthreads();
+  // bins 0 .. used - 1 hold the keys that are not NONE
+  const int used = __builtin_amdgcn_readfirstlane((int)max(max(wave_used[0], wave_used[1]), max(wave_used[2], wave_used[3])));
+  const int per = (used + kThreads) / kThreads;   // bins per thread for the scan of used + 1 bins: 1 .. 16
+  const bool scans = wid * 64 * per <= used;      // uniform per wave: the wave owns a bin of 0 .. used
+  uint32_t excl = 0u;
+  if (scans) {
+    uint32_t sum = 0u;
+    for (int k = 0; k < per; ++k) sum += bins[tid * per + k];  // (<= 4095; bins past `used` feed no prefix that is read)
+    const uint32_t incl = wave_inclusive_sum(sum);
+    excl = incl - sum;
+    if (lane == 63) wave_tot[wid] = incl;
+  }
+  __syncthreads();
+  if (scans) {
+    for (int w = 0; w < wid; ++w) excl += wave_tot[w];
+    for (int k = 0; k < per; ++k) {
+      const uint32_t c = bins[tid * per + k];
+      bins[tid * per + k] = excl;
+      excl += c;
+    }
+  }
+  __syncthreads();
+  if (wid != 0) return;
+  const int nbits = __builtin_amdgcn_readfirstlane(32 - __clz(used));  // bits of the largest bin index in use (`used` itself: NONE)
+  const int nchunk = (n + 63) >> 6;
+  uint32_t f = sf[lane];
+  for (int c = 0; c < nchunk; ++c) {
+    const int b = (int)min(f, (uint32_t)used);
+    if (c + 1 < nchunk) f = sf[64 * (c + 1) + lane];  // (in flight while this chunk's masks are taken)
+    uint32_t peers_lo = 0xFFFFFFFFu, peers_hi = 0xFFFFFFFFu;
+    for (int k = 0; k < nbits; ++k) {
+      const int bit = __builtin_amdgcn_sbfe(b, k, 1);  // all ones where the bin has bit k
+      const unsigned long long bal = __ballot(bit != 0);
+      peers_lo &= ~((uint32_t)bal ^ (uint32_t)bit);
+      peers_hi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)bit);
+    }
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi(peers_hi, __builtin_amdgcn_mbcnt_lo(peers_lo, 0u));
+    const uint32_t base = bins[b];
+    if (below == 0u) atomicAdd(&bins[b], (uint32_t)(__popc(peers_lo) + __popc(peers_hi)));
+    const int i = 64 * c + lane;
+    if (i < n) *reinterpret_cast<int32_t*>(reinterpret_cast<char*>(dst) + ((base + below) << 2)) = i;
+  }
 }
 
 // ---- mutual-consistency filter (cv2.BFMatcher(NORM_HAMMING, crossCheck=True), the commented-out matcher of
@@ -781,8 +878,10 @@ int32_t sosvo_sort_matches(sosvo_ctx* ctx, const uint32_t* keys, const int32_t* 
   SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
   SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= 16384, "q_stride out of range (max 16384)");
   if (nprob == 0) return SOSVO_OK;
-  const size_t lds = (size_t)((q_stride + 3) & ~3) * sizeof(uint32_t);
-  dim3 grid(nprob, cdiv(q_stride, kThreads)), block(kThreads);
+  // the rank form's sort keys (n <= kSortRankMaxN) or the counting form's 16-bit fields, whichever needs more
+  const size_t lds_rank = (size_t)((std::min(q_stride, kSortRankMaxN) + 3) & ~3) * sizeof(uint32_t);
+  const size_t lds = std::max(lds_rank, (size_t)((q_stride + 63) & ~63) * sizeof(uint16_t));
+  dim3 grid(nprob), block(kThreads);
   SOSVO_LAUNCH(ctx,sort_matches_kernel, grid, block, lds, ctx->stream, keys, nq, q_slot, q_stride, order);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
