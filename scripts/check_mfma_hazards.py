@@ -163,10 +163,22 @@ def check_text(asm_text, only=None):
     return report, bad
 
 
+def file_flags(src):
+    """The flags csrc/Makefile gives this one file (its `FLAGS_<stem> := ...` line), so that a recompile here is the
+    library's own: FLAGS_ransac and FLAGS_detect switch the SLP vectoriser off."""
+    try:
+        text = open(os.path.join(ROOT, "vo_single_camera_sos_amd", "csrc", "Makefile")).read()
+    except OSError:
+        return []
+    stem = os.path.splitext(os.path.basename(src))[0]
+    m = re.search(r"^FLAGS_%s\s*:=\s*(.*)$" % re.escape(stem), text, re.M)
+    return m.group(1).split() if m else []
+
+
 def compile_hip(src, extra=()):
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "k.s")
-        subprocess.check_call(["/opt/rocm/bin/hipcc"] + MAKE_FLAGS + list(extra) +
+        subprocess.check_call(["/opt/rocm/bin/hipcc"] + MAKE_FLAGS + file_flags(src) + list(extra) +
                               ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.dirname(os.path.abspath(src)),
                                "--cuda-device-only", "-S", "-o", asm, src], stderr=subprocess.DEVNULL)
         return open(asm).read()

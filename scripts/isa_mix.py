@@ -25,6 +25,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from check_mfma_hazards import file_flags  # noqa: E402
+
 CYC_E32, CYC_OTHER = 2.7, 4.4   # class means; per-opcode values below where measured
 FAST = {"v_and_b32": 2.79, "v_xor_b32": 2.84, "v_or_b32": 2.63, "v_not_b32": 2.58, "v_add_u32": 2.79, "v_sub_u32": 2.76,
         "v_subrev_u32": 2.76, "v_lshrrev_b32": 2.51, "v_ashrrev_i32": 2.60, "v_mov_b32": 2.57, "v_bitop3_b32": 2.67,
@@ -56,8 +59,9 @@ def demangled_label(sym):
 def kernels_of(src):
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "k.s")
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                               "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", asm, src],
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math"] +
+                              file_flags(src) +   # what csrc/Makefile gives this one file (FLAGS_<stem>)
+                              ["-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", asm, src],
                               stderr=subprocess.DEVNULL)
         lines = open(asm).read().split("\n")
     res = {}

@@ -261,6 +261,26 @@ __global__ __launch_bounds__(kThreads) void min_eigen_kernel(const uint8_t* __re
 // with the neighbours still taken from the neighbouring lanes.  In y nothing changes.
 //   Loads: the gray row t + 3 and the mask words of the e row t + 1 are requested in step t, a ring revolution before the
 // step that reads them, so no step waits on a load it issued itself.
+
+// One v_max_f32, as written: the compiler's fmaxf puts a canonicalising v_max_f32 v, v, v in front of a loop-carried operand it
+// cannot prove quiet.  For operands that are never NaN (the only use) the two are the same function.
+__device__ __forceinline__ float vmax_f32(float a, float b) {
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// A wave-uniform pointer into global memory, pinned to a scalar register pair by an empty asm: an address is then (scalar
+// base + the lane's 32-bit offset), one v_lshl_add_u64, where the compiler otherwise keeps a 64-bit pointer per lane and adds
+// the uniform part to that -- the same instruction count, two VGPRs more, and with them min_eigen_wide_kernel's 80.
+typedef const uint8_t __attribute__((address_space(1)))* global_bytes;
+typedef unsigned long long __attribute__((aligned(4))) u64_align4;  // two neighbouring 32-bit words
+__device__ __forceinline__ global_bytes uniform_global(const void* p) {
+  uint64_t u = reinterpret_cast<uint64_t>(p);
+  asm("" : "+s"(u));
+  return reinterpret_cast<global_bytes>(u);
+}
+
 constexpr int kEigWideStripW = 61;
 constexpr int kEigWideMinCols = 8;  // below it the one-column form runs (the wide form's border rule needs cols >= 3; 8 as for the blur)
 
@@ -286,7 +306,6 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
   const bool own_lo = lane >= 2 && lane <= 62 && x_lo < cols, own_hi = lane >= 1 && lane <= 61 && x_hi < cols;
   const bool cd_lo = own_lo && x_lo >= 1 && x_lo <= cols - 2, cd_hi = own_hi && x_hi >= 1 && x_hi <= cols - 2;
   const uint32_t mask_all = nmask < 32 ? (1u << nmask) - 1u : 0xFFFFFFFFu;
-  const uint32_t am_lo = own_lo ? mask_all : 0u, am_hi = own_hi ? mask_all : 0u;  // a mask word counts in an output column only
   // gray source of the two virtual columns
   auto mirror = [&](int x) { return clampi(x < 0 ? -x : (x >= cols ? 2 * (cols - 1) - x : x), 0, cols - 1); };
   const int m_lo = mirror(x_lo), m_hi = mirror(x_hi);
@@ -324,32 +343,53 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
   const uint32_t* mb = mask_bits + (size_t)(img / images_per_maskset) * rows * cols;
   const float scale = (float)(1.0 / 3060.0);
 
-  int hd_l[3] = {0, 0, 0}, hs_l[3] = {0, 0, 0}, hd_h[3] = {0, 0, 0}, hs_h[3] = {0, 0, 0};
-  float pxx_l[3] = {0.f, 0.f, 0.f}, pxy_l[3] = {0.f, 0.f, 0.f}, pyy_l[3] = {0.f, 0.f, 0.f};
-  float pxx_h[3] = {0.f, 0.f, 0.f}, pxy_h[3] = {0.f, 0.f, 0.f}, pyy_h[3] = {0.f, 0.f, 0.f};
-  float hm_l[3] = {0.f, 0.f, 0.f}, ec_l[3] = {0.f, 0.f, 0.f}, hm_h[3] = {0.f, 0.f, 0.f}, ec_h[3] = {0.f, 0.f, 0.f};
-  uint32_t bits_l = 0u, max_l = 0u, bits_h = 0u, max_h = 0u;  // running per-mask maximum of the lo / hi column
-  uint32_t mprev_l = 0u, mprev_h = 0u;                        // mask words of the row the flag stage looks at
+  // The rings start unset: a stage first runs once the three rows it reads are written (the P stage from the third step on,
+  // after three gray rows; the e stage two steps later, after three P rows; the flag stage from f_lo = e_lo + 1 on, after the
+  // e rows e_lo .. e_lo + 2), so no slot is read before a step wrote it and no register is cleared for nothing.
+  int hd_l[3], hs_l[3], hd_h[3], hs_h[3];
+  float pxx_l[3], pxy_l[3], pyy_l[3], pxx_h[3], pxy_h[3], pyy_h[3];
+  float hm_l[3], ec_l[3], hm_h[3], ec_h[3];
+  // Running per-mask maximum of the lo / hi column: the mask word of the current run and the largest response under it AS A
+  // FLOAT (one v_max_f32 per pixel and row); the ordered key that mstat holds is made where a run is flushed.  Exact: a
+  // response here is finite -- the products are bounded by (4 * 255 / 3060)^2 and sqrt_rn_normal gets a sum of two squares,
+  // so no operand is ever NaN or infinite -- and never -0.0 (a + c is a sum of halved sums of squares, >= +0, and x - y
+  // with x, y >= +0 rounds to +0 when it is zero), so two responses that compare equal have the same bits and
+  // sosvo_float_ordered, strictly increasing on such values, commutes with the maximum.  A run starts at -inf (key
+  // 0x007FFFFF, below every response's) and takes a response in the same step; a run under the word 0 is never flushed.
+  // The word of the running run IS the mask word of the previous e row (a run ends where the word changes), which is also
+  // the row the flag stage looks at: the words live in a ring indexed by phase like the others, mk_*[slot of row y], and
+  // nothing is handed over from step to step.  Words are kept for every lane (cleared outside the rows ys .. ye - 1 only);
+  // a lane outside the output columns is cleared where a run is flushed, and cd_* keeps it out of the flag stage.
+  uint32_t mk_l[3] = {0u, 0u, 0u}, mk_h[3] = {0u, 0u, 0u};
+  float max_l = -__builtin_inff(), max_h = -__builtin_inff();
   const int t_first = e_lo - 2, t_last = e_hi + 2;
   const bool edge_strip = xb < 0 || xb + 128 > cols;  // wave-uniform: some lane's column is outside the image
-  uint32_t c_pre[3] = {0u, 0u, 0u}, mw_l[3] = {0u, 0u, 0u}, mw_h[3] = {0u, 0u, 0u};
+  // mask-word columns: the lane's own ones where they lie inside the image (as byte offsets into a row of mask words)
+  const uint32_t mo_lo = 4u * (uint32_t)clampi(x_lo, 0, cols - 1), mo_hi = 4u * (uint32_t)clampi(x_hi, 0, cols - 1);
+  // The sign rules as factors: a mirrored row negates dy and a mirrored column dx, and the dx * dy product is negated back.
+  // IEEE multiplication is symmetric in sign, so scaling dy (dx) by -scale gives exactly -dy (-dx): the squares keep their
+  // bits and dx * dy comes out as the negated product, signed zeros included -- the same values as negating the product.
+  const unsigned long long cdb_lo = __builtin_amdgcn_ballot_w64(cd_lo), cdb_hi = __builtin_amdgcn_ballot_w64(cd_hi);
+  const float sx_lo = __uint_as_float(__float_as_uint(scale) ^ neg_lo), sx_hi = __uint_as_float(__float_as_uint(scale) ^ neg_hi);
+  // Prefetch slots, indexed by phase like the rings: step t reads slot t mod 3 and then refills it for step t + 3, so the
+  // value a step reads is in the register the step three before it loaded into -- no hand-over copies.
+  // (All three are requested before the first step.)
+  uint32_t c_pre[3], mw_l[3], mw_h[3];
   auto request = [&](auto slot_tag, auto edge_tag, const int t) __attribute__((always_inline)) {  // row t -> slot t mod 3
     constexpr int P = decltype(slot_tag)::value;
     constexpr bool EDGE = decltype(edge_tag)::value;
     c_pre[P] = *reinterpret_cast<const u32_unaligned*>(g + ((uint32_t)(refl101(min(t, t_last), rows) * cols) + src_col));
-    const int y = t - 2;  // the e row that step t finishes
-    mw_l[P] = 0u;
-    mw_h[P] = 0u;
-    if (y >= ys && y < ye) {  // uniform; 0 <= y < rows follows
-      if (EDGE) {  // (an own column lies inside the image)
-        if (own_lo) mw_l[P] = mb[(uint32_t)(y * cols) + (uint32_t)x_lo];
-        if (own_hi) mw_h[P] = mb[(uint32_t)(y * cols) + (uint32_t)x_hi];
-      } else {  // all 128 columns lie inside the image: x_lo >= 0
-        uint32_t w[2];
-        __builtin_memcpy(w, mb + ((uint32_t)(y * cols) + (uint32_t)x_lo), 8);
-        mw_l[P] = w[0];
-        mw_h[P] = w[1];
-      }
+    // the mask words of the e row that step t finishes, y = t - 2: always loaded, from a row clamped into the image; the
+    // step clears the words of a row outside ys .. ye - 1 (the few rows a chunk steps over before ys and after ye - 1), so no slot is zeroed here
+    // (the row's base is uniform, held in a scalar pair; the lane's byte offset is constant: one 64-bit add per load)
+    const global_bytes mrow = uniform_global(mb + (uint32_t)(clampi(t - 2, 0, rows - 1) * cols));
+    if (EDGE) {
+      mw_l[P] = *reinterpret_cast<const uint32_t __attribute__((address_space(1)))*>(mrow + mo_lo);
+      mw_h[P] = *reinterpret_cast<const uint32_t __attribute__((address_space(1)))*>(mrow + mo_hi);
+    } else {  // all 128 columns lie inside the image: x_lo >= 0, x_hi <= cols - 1
+      const unsigned long long w = *reinterpret_cast<const u64_align4 __attribute__((address_space(1)))*>(mrow + mo_lo);
+      mw_l[P] = (uint32_t)w;
+      mw_h[P] = (uint32_t)(w >> 32);
     }
   };
   auto eig = [&](float xx0, float xx1, float xx2, float xy0, float xy1, float xy2, float yy0, float yy1, float yy2) {
@@ -357,16 +397,21 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
     const float c = ((yy0 + yy1) + yy2) * 0.5f;
     return (a + c) - sqrt_rn_normal(((a - c) * (a - c)) + (b * b));
   };
+  // One row step; false once t is past the last row (the caller leaves the loop: nothing of the rings or the prefetch slots
+  // is live after it, so the ragged tail costs the steady loop no merge).
   auto step = [&](auto phase_tag, auto edge_tag, const int t) __attribute__((always_inline)) {
     constexpr int P = decltype(phase_tag)::value;
     constexpr bool EDGE = decltype(edge_tag)::value;
     constexpr int i0 = (P + 1) % 3, i1 = (P + 2) % 3, i2 = P;  // slots of rows t-2, t-1, t
-    if (t > t_last) return;  // uniform
+    if (t > t_last) return false;  // uniform
+    const int y = t - 2;           // the e row this step finishes
     const uint32_t c = c_pre[P];
-    const uint32_t mb_l = mw_l[P] & am_lo, mb_h = mw_h[P] & am_hi;  // mask words of the e row t - 2
-    request(phase_tag, edge_tag, t + 3);
+    const int cl = (int)((c >> sh_lo) & 0xFFu), ch = (int)((c >> sh_hi) & 0xFFu);
+    const uint32_t row_all = (y >= ys && y < ye) ? mask_all : 0u;  // uniform
+    mk_l[i2] = mw_l[P] & row_all;                                  // mask words of the e row
+    mk_h[i2] = mw_h[P] & row_all;
+    request(phase_tag, edge_tag, t + 3);  // (after the slot's last read)
     {
-      const int cl = (int)((c >> sh_lo) & 0xFFu), ch = (int)((c >> sh_hi) & 0xFFu);
       const int l = lane_from_left(ch), r = lane_from_right(cl);
       hd_l[i2] = ch - l;
       hs_l[i2] = (l + 2 * cl) + ch;
@@ -374,20 +419,14 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
       hs_h[i2] = (cl + 2 * ch) + r;
     }
     const int v = t - 1;
-    if (v < e_lo - 1) return;  // uniform
+    if (v < e_lo - 1) return true;  // uniform
     {
-      const float dx_l = (float)((hd_l[i0] + 2 * hd_l[i1]) + hd_l[i2]) * scale, dy_l = (float)(hs_l[i2] - hs_l[i0]) * scale;
-      const float dx_h = (float)((hd_h[i0] + 2 * hd_h[i1]) + hd_h[i2]) * scale, dy_h = (float)(hs_h[i2] - hs_h[i0]) * scale;
+      // mirrored row (v < 0 or v > rows - 1; uniform, so the sign is made by scalar integer instructions): dy comes out negated
+      const float sy = __uint_as_float(__float_as_uint(scale) ^ ((uint32_t)(v | (rows - 1 - v)) & 0x80000000u));
+      const float dx_l = (float)((hd_l[i0] + 2 * hd_l[i1]) + hd_l[i2]) * (EDGE ? sx_lo : scale), dy_l = (float)(hs_l[i2] - hs_l[i0]) * sy;
+      const float dx_h = (float)((hd_h[i0] + 2 * hd_h[i1]) + hd_h[i2]) * (EDGE ? sx_hi : scale), dy_h = (float)(hs_h[i2] - hs_h[i0]) * sy;
       const float xx_l = dx_l * dx_l, yy_l = dy_l * dy_l, xx_h = dx_h * dx_h, yy_h = dy_h * dy_h;
-      float xy_l = dx_l * dy_l, xy_h = dx_h * dy_h;
-      if (v < 0 || v >= rows) {  // mirrored row: dy came out negated
-        xy_l = -xy_l;
-        xy_h = -xy_h;
-      }
-      if (EDGE) {  // mirrored column: dx came out negated
-        xy_l = __uint_as_float(__float_as_uint(xy_l) ^ neg_lo);
-        xy_h = __uint_as_float(__float_as_uint(xy_h) ^ neg_hi);
-      }
+      const float xy_l = dx_l * dy_l, xy_h = dx_h * dy_h;
       pxx_l[i2] = (lane_from_left(xx_h) + xx_l) + xx_h;
       pxx_h[i2] = (xx_l + xx_h) + lane_from_right(xx_l);
       pxy_l[i2] = (lane_from_left(xy_h) + xy_l) + xy_h;
@@ -395,41 +434,39 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
       pyy_l[i2] = (lane_from_left(yy_h) + yy_l) + yy_h;
       pyy_h[i2] = (yy_l + yy_h) + lane_from_right(yy_l);
     }
-    const int y = v - 1;
-    if (y < e_lo) return;  // uniform
+    if (y < e_lo) return true;  // uniform
     {
       const float e_l = eig(pxx_l[i0], pxx_l[i1], pxx_l[i2], pxy_l[i0], pxy_l[i1], pxy_l[i2], pyy_l[i0], pyy_l[i1], pyy_l[i2]);
       const float e_h = eig(pxx_h[i0], pxx_h[i1], pxx_h[i2], pxy_h[i0], pxy_h[i1], pxy_h[i2], pyy_h[i0], pyy_h[i1], pyy_h[i2]);
-      // per-mask maximum: a mask word is 0 outside the output columns and the rows ys .. ye - 1, and a run under the word 0
-      // is never flushed
-      if (mb_l != bits_l) {
-        eig_flush(mstat_img, bits_l, max_l);
-        bits_l = mb_l;
-        max_l = 0u;
+      // per-mask maximum: a mask word is 0 outside the rows ys .. ye - 1, and a run under the word 0 is never flushed
+      if (mk_l[i2] != mk_l[i1]) {
+        eig_flush(mstat_img, own_lo ? mk_l[i1] : 0u, sosvo_float_ordered(max_l));
+        max_l = -__builtin_inff();
       }
-      max_l = max(max_l, sosvo_float_ordered(e_l));
-      if (mb_h != bits_h) {
-        eig_flush(mstat_img, bits_h, max_h);
-        bits_h = mb_h;
-        max_h = 0u;
+      max_l = vmax_f32(max_l, e_l);
+      if (mk_h[i2] != mk_h[i1]) {
+        eig_flush(mstat_img, own_hi ? mk_h[i1] : 0u, sosvo_float_ordered(max_h));
+        max_h = -__builtin_inff();
       }
-      max_h = max(max_h, sosvo_float_ordered(e_h));
+      max_h = vmax_f32(max_h, e_h);
       hm_l[i2] = fmaxf(fmaxf(lane_from_left(e_h), e_l), e_h);
       hm_h[i2] = fmaxf(fmaxf(e_l, e_h), lane_from_right(e_l));
       ec_l[i2] = e_l;
       ec_h[i2] = e_h;
     }
     const int f = y - 1;
-    const uint32_t mf_l = mprev_l, mf_h = mprev_h;  // row f was the e row of the previous step
-    mprev_l = mb_l;
-    mprev_h = mb_h;
-    if (f < f_lo || f > f_hi) return;  // uniform
+    if (f < f_lo || f > f_hi) return true;  // uniform
     {
       const float ev_l = ec_l[i1], ev_h = ec_h[i1];
-      const bool is_l = cd_lo && ev_l == fmaxf(fmaxf(hm_l[i0], hm_l[i1]), hm_l[i2]) && ev_l > 0.0f && mf_l != 0u;
-      const bool is_h = cd_hi && ev_h == fmaxf(fmaxf(hm_h[i0], hm_h[i1]), hm_h[i2]) && ev_h > 0.0f && mf_h != 0u;
-      const unsigned long long bal_l = __ballot(is_l), bal_h = __ballot(is_h);
+      // row f was the e row of the previous step (slot i1).  Each predicate goes to a ballot of its own (a compare that
+      // writes the lane mask) and the masks are combined as scalars: no predicate is materialised as 0 / 1 on the way.
+      const float m3_l = fmaxf(fmaxf(hm_l[i0], hm_l[i1]), hm_l[i2]), m3_h = fmaxf(fmaxf(hm_h[i0], hm_h[i1]), hm_h[i2]);
+      const unsigned long long bal_l = cdb_lo & __builtin_amdgcn_ballot_w64(ev_l == m3_l) & __builtin_amdgcn_ballot_w64(ev_l > 0.0f) &
+                                       __builtin_amdgcn_ballot_w64(mk_l[i1] != 0u);
+      const unsigned long long bal_h = cdb_hi & __builtin_amdgcn_ballot_w64(ev_h == m3_h) & __builtin_amdgcn_ballot_w64(ev_h > 0.0f) &
+                                       __builtin_amdgcn_ballot_w64(mk_h[i1] != 0u);
       if (bal_l | bal_h) {  // uniform
+        const bool is_l = (bal_l >> lane) & 1ull, is_h = (bal_h >> lane) & 1ull;
         const uint32_t al = (uint32_t)bal_l, ah = (uint32_t)bal_h, bl = (uint32_t)(bal_l >> 32), bh = (uint32_t)(bal_h >> 32);
         const int below_a = (int)__builtin_amdgcn_mbcnt_lo(al, __builtin_amdgcn_mbcnt_lo(ah, 0u));  // lanes 0 .. 31
         const int below_b = (int)__builtin_amdgcn_mbcnt_hi(bl, __builtin_amdgcn_mbcnt_hi(bh, 0u));  // lanes 32 .. 63 (0 below them)
@@ -440,16 +477,24 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
         wpos_b += __popc(bl) + __popc(bh);
       }
     }
+    return true;
   };
+  uint32_t bits_l = 0u, bits_h = 0u;  // words of the runs still open after the last row
   auto run = [&](auto edge_tag) __attribute__((always_inline)) {
     request(std::integral_constant<int, 0>{}, edge_tag, t_first);
     request(std::integral_constant<int, 1>{}, edge_tag, t_first + 1);
     request(std::integral_constant<int, 2>{}, edge_tag, t_first + 2);
-    for (int t = t_first; t <= t_last; t += 3) {
-      step(std::integral_constant<int, 0>{}, edge_tag, t);
-      step(std::integral_constant<int, 1>{}, edge_tag, t + 1);
-      step(std::integral_constant<int, 2>{}, edge_tag, t + 2);
+    int last = 2;  // slot of the last row stepped: where the running runs' words are
+    for (int t = t_first;; t += 3) {
+      if (!step(std::integral_constant<int, 0>{}, edge_tag, t)) break;
+      last = 0;
+      if (!step(std::integral_constant<int, 1>{}, edge_tag, t + 1)) break;
+      last = 1;
+      if (!step(std::integral_constant<int, 2>{}, edge_tag, t + 2)) break;
+      last = 2;
     }
+    bits_l = last == 0 ? mk_l[0] : (last == 1 ? mk_l[1] : mk_l[2]);
+    bits_h = last == 0 ? mk_h[0] : (last == 1 ? mk_h[1] : mk_h[2]);
   };
   if (edge_strip) run(std::true_type{}); else run(std::false_type{});
   if (lane == 0) {  // may exceed wcap: the selection kernel reports the overflow
@@ -471,8 +516,8 @@ __global__ __launch_bounds__(kThreads) void min_eigen_wide_kernel(const uint8_t*
       }
     }
   };
-  finish(bits_l, max_l);
-  finish(bits_h, max_h);
+  finish(own_lo ? bits_l : 0u, sosvo_float_ordered(max_l));
+  finish(own_hi ? bits_h : 0u, sosvo_float_ordered(max_h));
 }
 
 // Bounding box of every mask of every mask set (depends on the masks only): mstat fields 1..4 of the FIRST
