@@ -15,8 +15,8 @@
 //                  (workgroup, hypothesis).  A squared-cosine test with a 1e-9 guard band decides
 //                  all but near-threshold points without FP64 sqrt/div; the guard band falls back
 //                  to the exact reference formula, so counts are bit-identical to it.  With a fixed iteration count and no
-//                  counts asked for: a probe pass over the first 256 points, ransac_prune_kernel (drops every hypothesis
-//                  that provably cannot reach the best count), then the rest of the points for the survivors only.
+//                  counts asked for: the point sets in stages, least reliable matches first, ransac_prune_kernel after each
+//                  (drops every hypothesis that provably cannot reach the best count), the next stage for the survivors only.
 //   4. select      sequential semantics of sac::Ransac (strictly-better update, adaptive stop)
 //                  replayed over the counts; exact inlier mask + ascending index list of the winner.
 //   5. refine      one workgroup per problem, Levenberg-Marquardt on (t, Cayley) with fixed-order
@@ -47,27 +47,34 @@ __device__ __forceinline__ uint64_t problem_seed(const uint64_t* seeds, int b) {
 __global__ __launch_bounds__(kThreads) void ransac_prepare_kernel(const int32_t* __restrict__ cam,
                                                                   const int32_t* __restrict__ n_arr, int stride,
                                                                   int ncam, int32_t* __restrict__ perm,
-                                                                  int32_t* __restrict__ cinfo) {
+                                                                  int32_t* __restrict__ cinfo,
+                                                                  int32_t* __restrict__ split_out) {
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ int cnt[kThreads][kMaxCam];
   __shared__ int cstart[kMaxCam + 1];
+  __shared__ int s_split;  // length of the leading run of rows with the first row's camera (score_set_at's `split`)
   const int tid = threadIdx.x, b = blockIdx.x;
   const int n = min(n_arr[b], stride);
+  if (tid == 0) s_split = n;
   const int chunk = (n + kThreads - 1) / kThreads;
   const int begin = min(n, tid * chunk), end = min(n, begin + chunk);
   const int32_t* camb = cam ? cam + (size_t)b * stride : nullptr;
   int local[kMaxCam];
 #pragma unroll
   for (int c = 0; c < kMaxCam; ++c) local[c] = 0;
+  const int c0 = camb && n > 0 ? max(0, min(ncam - 1, camb[0])) : 0;
+  int other = n;  // the thread's first row of another camera than row 0's
   for (int i = begin; i < end; ++i) {
     int c = camb ? camb[i] : 0;
     c = max(0, min(ncam - 1, c));
 #pragma unroll
     for (int k = 0; k < kMaxCam; ++k) local[k] += (k == c);
+    if (c != c0) other = min(other, i);
   }
 #pragma unroll
   for (int c = 0; c < kMaxCam; ++c) cnt[tid][c] = local[c];
   __syncthreads();
+  if (other < n) atomicMin(&s_split, other);
   if (tid < kMaxCam) {
     int running = 0;
     for (int t = 0; t < kThreads; ++t) {
@@ -83,6 +90,7 @@ __global__ __launch_bounds__(kThreads) void ransac_prepare_kernel(const int32_t*
     cstart[0] = 0;
     for (int c = 0; c < kMaxCam; ++c) cstart[c + 1] += cstart[c];
     for (int c = 0; c <= kMaxCam; ++c) cinfo[(size_t)b * (2 * kMaxCam + 1) + c] = cstart[c];
+    split_out[b] = s_split;
   }
   __syncthreads();
   int pos[kMaxCam];
@@ -370,6 +378,20 @@ __device__ __forceinline__ void score_tier1_hyp(const double* __restrict__ h, fl
   hs[14] = 0.0f, hs[15] = 0.0f;
 }
 
+// The staged flow walks the E = ceil(n / 64) point sets of a problem worst first: position k of
+// the order -> set.  The rows arrive as [top view ; bottom view], each view's matches sorted by descriptor distance, so
+// the misses that tell hypotheses apart sit at the END of either list.  With `split` = the length of the leading run of
+// rows with the first row's camera and tb = split / 64: the bottom list is the sets E-1, E-2, ..., tb+1, the top list
+// tb, tb-1, ..., 0, and the order takes one from each in turn, bottom first, then the remainder of the longer one
+// (split == 0 or >= n: plain back to front).  Position 0 is always set E-1, the one partial set.  A heuristic only: any
+// permutation gives the same counts.  Scalar operands in, scalar out.
+__device__ __forceinline__ int score_set_at(int E, int n, int split, int k) {
+  if (split <= 0 || split >= n) return E - 1 - k;
+  const int tb = split >> 6, nbot = E - 1 - tb, ntop = tb + 1, m = min(nbot, ntop);
+  if (k < 2 * m) return (k & 1) ? tb - (k >> 1) : E - 1 - (k >> 1);
+  return nbot > ntop ? E - 1 - (k - m) : tb - (k - m);
+}
+
 // T1 = false: double-precision tiers only (thr >= 0.5, or camera rotations that are not the identity) and the lane's
 // constants in double precision in registers.  T1 = true: tier 1 in front; the lane keeps the float copies and its
 // row, and re-reads bearing, point and camera offset in the rare fallback (128 VGPRs, four waves per SIMD).
@@ -379,7 +401,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
     const double* __restrict__ cam_off, const double* __restrict__ cam_rot, const int32_t* __restrict__ n_arr,
     int stride, int H, int hchunk, int hspan, double thr, int fast_ok, const double* __restrict__ hyp,
     int32_t* __restrict__ counts, int set_lo, int set_hi, int hsplit, const int32_t* __restrict__ alive_idx,
-    const int32_t* __restrict__ n_alive) {
+    const int32_t* __restrict__ n_alive, const int32_t* __restrict__ split_arr) {
   static_assert(!T1 || (IDENT && PPT <= 4), "tier 1 is written for the identity-rotation form");
   SOSVO_LATENCY_BOUND_PRIO();
   constexpr bool KEEP = !T1;
@@ -404,9 +426,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   // Point sets of 64 are split EVENLY over the point blocks this problem needs (nb = sets / 16 rounded up, each block
   // takes ceil(sets / nb) consecutive sets): a ragged problem (say 22 sets) runs as 11 + 11 instead of 16 + 6, so
   // every block amortises its per-hypothesis work (LDS reads, the count atomic) over about the same number of sets.
-  // The launch covers the point sets [set_lo, set_hi) of every problem (all of them: 0, INT_MAX).  The pruned flow
-  // (ransac_abs_pose_impl) scores a probe range first and the rest for the hypotheses that ransac_prune_kernel left alive.
-  const int sbeg = set_lo, send = min((n + 63) >> 6, set_hi);
+  // The launch covers the positions [set_lo, set_hi) of every problem's set order (all of them: 0, INT_MAX): the sets
+  // themselves without split_arr, score_set_at's order with it.  The pruned flow (ransac_abs_pose_impl) scores the
+  // positions stage by stage, each stage for the hypotheses that ransac_prune_kernel left alive after the one before.
+  const int nset_all = (n + 63) >> 6, split = split_arr ? split_arr[b] : 0;
+  auto set_at = [&](int k) { return split_arr ? score_set_at(nset_all, n, split, k) : k; };  // scalar
+  const int sbeg = set_lo, send = min(nset_all, set_hi);
   const int nsets = send - sbeg;
   const int bcap = hsplit ? PPT : (kThreads / 64) * PPT;  // sets a point block can take
   const int nb = (nsets + bcap - 1) / bcap;
@@ -415,7 +440,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   // (hsplit: blocks of floor or ceil(nsets / nb) sets -- 17 sets run as 4 + 3 + 3 + 4 + 3, not 4 + 4 + 4 + 4 + 1)
   const int set0 = hsplit ? sbeg + ((int)blockIdx.y * nsets) / nb : sbeg + (int)blockIdx.y * spb;
   const int set1 = hsplit ? sbeg + (((int)blockIdx.y + 1) * nsets) / nb : min(set0 + spb, send);
-  const int p0 = set0 * 64;
+  const int p0 = set_at(set0) * 64;  // (set0, set1: positions; a live block's first set has a valid first row)
 
   double fx[KEEP ? PPT : 1], fy[KEEP ? PPT : 1], fz[KEEP ? PPT : 1];
   double px[KEEP ? PPT : 1], py[KEEP ? PPT : 1], pz[KEEP ? PPT : 1];
@@ -441,10 +466,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   int nlive_v = 0;
 #pragma unroll
   for (int r = 0; r < PPT; ++r) {
-    const int set = set0 + (hsplit ? r : r * (kThreads / 64) + wslot);
-    const int i0 = set * 64;
+    const int pos = set0 + (hsplit ? r : r * (kThreads / 64) + wslot);
+    const int i0 = (pos < set1 ? set_at(pos) : nset_all) * 64;  // (beyond the block: no valid row)
     const int i = i0 + lane;
-    nlive_v += set < set1 ? 1 : 0;
+    nlive_v += pos < set1 ? 1 : 0;
     const bool valid = i < n;
     vmask[r] = __ballot(valid);
     rowi[r] = valid ? i : p0;
@@ -649,20 +674,25 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(T1 ? 4
   }  // chunks of the workgroup
 }
 
-// ---- 3b. prune ---------------------------------------------------------
-// Between the probe pass (counts over the first pn = min(n, 64 probe_sets) points) and the rest pass; one workgroup per
-// problem.  h* = the first solved hypothesis with the largest probe count; L = its count over all n points by the
-// reference's formula (what the score kernel's tiers add up to).  The best full count is >= L, and the full count of
-// hypothesis h is <= probe[h] + (n - pn): h is left alive iff that bound reaches L (a tie may be the first maximum), and
-// only those are scored on the remaining points.  A pruned hypothesis keeps its probe count, which is below L: the
-// select kernel sees the same first maximum as with every count complete.  The hypothesis records are not touched: the
-// survivors leave as an ascending index list (alive_idx[b * H + 0 .. n_alive[b])), which the rest pass walks in spans
-// as full as those of a launch over all hypotheses, whatever fraction survived; workgroups beyond the list exit at once.
+// ---- 3b. prune (DESIGN.md sections 17 and 33) ----------------------------------------------------
+// After every stage of the pruned flow; one workgroup per problem.  The positions [0, k_done) of the problem's set order
+// are scored for the hypotheses of the list in_idx / n_in (first stage: in_idx == NULL, every hypothesis).  h* = the first
+// listed hypothesis with the largest partial count; L = max(L of the stage before, the count of h* over all n points by the
+// reference's formula: what the score kernel's tiers add up to); when h* is the stage before's, its count is in that L
+// already.  The best full count is >= L, and the full count of hypothesis h is <= partial[h] + rest, rest = the points
+// behind the positions from k_done on = 64 (E - k_done): position 0 is the one partial set.  h is left alive iff that
+// bound reaches L (a tie may be the first maximum), and only those are scored further.  A pruned hypothesis keeps its
+// partial count, which is below L: the select kernel sees the same first maximum as with every count complete.  The
+// hypothesis records are not touched: the survivors leave as an ascending index list (alive_idx[b * H + 0 .. n_alive[b]),
+// another buffer than in_idx), which the next score launch walks in spans as full as those of a launch over all
+// hypotheses, whatever fraction survived; workgroups beyond the list exit at once.  state[2 b], state[2 b + 1]: L and h*,
+// from stage to stage.
 __global__ __launch_bounds__(kThreads) void ransac_prune_kernel(
     const double* __restrict__ f, const double* __restrict__ p, const int32_t* __restrict__ cam,
-    const double* __restrict__ cam_off, const int32_t* __restrict__ n_arr, int stride, int H, int probe_sets, double thr,
-    const double* __restrict__ hyp, const int32_t* __restrict__ counts, int32_t* __restrict__ alive_idx,
-    int32_t* __restrict__ n_alive) {
+    const double* __restrict__ cam_off, const int32_t* __restrict__ n_arr, int stride, int H, int k_done, double thr,
+    const double* __restrict__ hyp, const int32_t* __restrict__ counts, const int32_t* __restrict__ in_idx,
+    const int32_t* __restrict__ n_in, int32_t* __restrict__ alive_idx, int32_t* __restrict__ n_alive,
+    int32_t* __restrict__ state) {
   SOSVO_LATENCY_BOUND_PRIO();
   __shared__ long long red[kThreads / 64];
   __shared__ int redc[kThreads / 64];
@@ -670,9 +700,12 @@ __global__ __launch_bounds__(kThreads) void ransac_prune_kernel(
   const int tid = threadIdx.x, b = blockIdx.x, lane = tid & 63, wid = tid >> 6;
   const int n = min(n_arr[b], stride);
   const int32_t* cb = counts + (size_t)b * H;
+  const int32_t* ib = in_idx ? in_idx + (size_t)b * H : nullptr;
   int32_t* ab = alive_idx + (size_t)b * H;
+  const int Hin = in_idx ? n_in[b] : H;
   long long best_key = -1;
-  for (int it = tid; it < H; it += kThreads) {
+  for (int j = tid; j < Hin; j += kThreads) {
+    const int it = ib ? ib[j] : j;
     const int c = cb[it];
     const long long key = ((long long)c << 32) | (long long)(0x7FFFFFFF - it);  // max count, then min it
     if (c >= 0 && key > best_key) best_key = key;
@@ -690,24 +723,29 @@ __global__ __launch_bounds__(kThreads) void ransac_prune_kernel(
     return;
   }
   const int hstar = 0x7FFFFFFF - (int)(best_key & 0xFFFFFFFFLL);
-  const double* hp = hyp + ((size_t)b * H + hstar) * kHypDoubles;
-  const size_t base = (size_t)b * stride;
-  int cnt = 0;
-  for (int i = tid; i < n; i += kThreads) {
-    const size_t row = base + i;
-    const double* o = cam ? cam_off + 3 * cam[row] : kZero3;
-    cnt += inlier_exact<true>(hp, f[3 * row], f[3 * row + 1], f[3 * row + 2], p[3 * row], p[3 * row + 1], p[3 * row + 2], o[0],
-                              o[1], o[2], kEye9, thr) ? 1 : 0;
+  const int L_prev = in_idx ? state[2 * b] : 0, h_prev = in_idx ? state[2 * b + 1] : -1;
+  int L = L_prev;
+  if (hstar != h_prev) {  // (uniform over the workgroup)
+    const double* hp = hyp + ((size_t)b * H + hstar) * kHypDoubles;
+    const size_t base = (size_t)b * stride;
+    int cnt = 0;
+    for (int i = tid; i < n; i += kThreads) {
+      const size_t row = base + i;
+      const double* o = cam ? cam_off + 3 * cam[row] : kZero3;
+      cnt += inlier_exact<true>(hp, f[3 * row], f[3 * row + 1], f[3 * row + 2], p[3 * row], p[3 * row + 1], p[3 * row + 2],
+                                o[0], o[1], o[2], kEye9, thr) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if (lane == 0) redc[wid] = cnt;
+    __syncthreads();
+    L = max(L_prev, ((redc[0] + redc[1]) + redc[2]) + redc[3]);
   }
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-  if (lane == 0) redc[wid] = cnt;
-  __syncthreads();
-  const int L = ((redc[0] + redc[1]) + redc[2]) + redc[3];
-  const int rest = n - min(n, probe_sets * 64);
+  const int rest = 64 * max(0, ((n + 63) >> 6) - k_done);
   int running = 0;  // stable compaction, 256 hypotheses a round
-  for (int it0 = 0; it0 < H; it0 += kThreads) {
-    const int it = it0 + tid;
-    const int c = it < H ? cb[it] : -1;
+  for (int j0 = 0; j0 < Hin; j0 += kThreads) {
+    const int j = j0 + tid;
+    const int it = j < Hin ? (ib ? ib[j] : j) : 0;
+    const int c = j < Hin ? cb[it] : -1;
     const bool keep = c >= 0 && c + rest >= L;
     const unsigned long long bal = __ballot(keep);
     __syncthreads();
@@ -718,7 +756,11 @@ __global__ __launch_bounds__(kThreads) void ransac_prune_kernel(
     if (keep) ab[off + __popcll(bal & ((1ULL << lane) - 1ULL))] = it;
     running += ((wave_off[1] + wave_off[2]) + wave_off[3]) + wave_off[4];
   }
-  if (tid == 0) n_alive[b] = running;
+  if (tid == 0) {  // (every thread read the state before the loop's barriers)
+    n_alive[b] = running;
+    state[2 * b] = L;
+    state[2 * b + 1] = hstar;
+  }
 }
 
 // ---- 4. select ------------------------------------------------------------------------------
@@ -1061,7 +1103,12 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   const size_t o_counts = carve(sizeof(int32_t) * (size_t)nprob * H);
   const bool epnp_vec = (flags & SOSVO_FLAG_EPNP) != 0;
   const size_t o_vv = carve(epnp_vec ? sizeof(double) * (size_t)nprob * H * kEpnpVecDoubles : 0);
-  const size_t o_alive = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));  // ransac_prune_kernel's survivor lists and their lengths
+  // ransac_prune_kernel's survivor lists and their lengths, one buffer for the even stages and one for the odd ones; its
+  // (L, h*) per problem from stage to stage; ransac_prepare_kernel's `split` per problem
+  const size_t o_alive = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));
+  const size_t o_alive2 = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));
+  const size_t o_stage = carve(sizeof(int32_t) * (size_t)nprob * 2);
+  const size_t o_split = carve(sizeof(int32_t) * (size_t)nprob);
   int32_t rc = sosvo_ws_reserve(ctx, off);
   if (rc != SOSVO_OK) return rc;
   char* ws = (char*)ctx->ws;
@@ -1069,9 +1116,10 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   int32_t* cinfo = (int32_t*)(ws + o_cinfo);
   double* hyp = (double*)(ws + o_hyp);
   int32_t* counts = hyp_counts ? hyp_counts : (int32_t*)(ws + o_counts);
+  int32_t* split = (int32_t*)(ws + o_split);
 
   SOSVO_LAUNCH(ctx,ransac_prepare_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, cam, n, stride,
-                     cam ? ncam : 1, perm, cinfo);
+                     cam ? ncam : 1, perm, cinfo, split);
   SOSVO_LAUNCH_CHECK(ctx);
   const int epnp = (flags & SOSVO_FLAG_EPNP) != 0;
   SOSVO_REQUIRE_FN(ctx, !epnp || cam == nullptr, "SOSVO_FLAG_EPNP is for central problems (cam == NULL)");
@@ -1114,34 +1162,61 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   hchunks = cdiv(H, hspan);
   const int hchunk = cdiv(hspan, cdiv(hspan, kScoreHypChunkMax));
   dim3 grid(hchunks, gx, nprob);
-  // Pruned flow: only where nothing the caller receives depends on the count of a losing
+  // Pruned flow (DESIGN.md sections 17 and 33): only where nothing the caller receives depends on the count of a losing
   // hypothesis -- fixed iteration count, no counts asked for -- and only in the tier-1 form with Kneip P3P hypotheses
   // (or GP3P: the records and the scoring are the same); a capacity of at least kPruneMinSets sets of 64, or the probe
-  // leaves too little to skip; and at least kPruneMinProblems problems, or the two extra launches cost more than the
+  // leaves too little to skip; and at least kPruneMinProblems problems, or the extra launches cost more than the
   // skipped work saves (measured at 2000 hypotheses x ~1285 points: 16 problems 42 -> 63 us, 64: 142 -> 136 us, 128: 233 ->
   // 228 us, 256: 425 -> 377 us).  Everything else scores every hypothesis on every point in one launch, as before.
-  constexpr int kProbeSets = 4, kPruneMinSets = 8, kPruneMinProblems = 64;
+  // The plan: the positions (of score_set_at's worst-first order) after which ransac_prune_kernel runs.  A capacity below
+  // kStageMinSets sets prunes once, after the probe; from there on every boundary of kStagePlan below the capacity is a
+  // stage.  The launches depend on the call's arguments only (a captured graph replays them); positions beyond a
+  // problem's own sets exit at once.  4, 14: the fastest of eleven plans on the headline (more
+  // stages skip more work and lose it again in launches); score + prune launches of a step on the bench's own
+  // correspondences against the probe / rest flow, isolated: 256 problems 377 -> 346 us, 128: 219 -> 205 us, 64: 131 -> 136 us.
+  constexpr int kProbeSets = 4, kPruneMinSets = 8, kStageMinSets = 16, kPruneMinProblems = 64;
+#ifndef SOSVO_STAGE_PLAN
+#define SOSVO_STAGE_PLAN 4, 14
+#endif
+  static const int kStagePlan[] = {SOSVO_STAGE_PLAN};  // ascending, the first one below kStageMinSets
   const bool prune = t1 && adaptive == 0 && hyp_counts == nullptr && !epnp && !twopt && stride >= 64 * kPruneMinSets &&
                      nprob >= kPruneMinProblems;
-#define SOSVO_SCORE_ARGS grid, dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hchunk, hspan, thr, fast_ok, hyp, counts, 0, INT_MAX, 0, (const int32_t*)nullptr, (const int32_t*)nullptr
+#define SOSVO_SCORE_ARGS grid, dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hchunk, hspan, thr, fast_ok, hyp, counts, 0, INT_MAX, 0, (const int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr
   if (prune) {
-    int32_t* alive_idx = (int32_t*)(ws + o_alive);
-    int32_t* n_alive = alive_idx + (size_t)nprob * H;
-    // Both passes in the hypothesis-split form (point blocks of at most 4 sets, see the kernel): a workgroup sets up a
-    // quarter of the points of a full block, so it takes more hypotheses -- 4 spans in the probe (one block per problem),
-    // 2 in the rest pass and never less than one full LDS chunk there (measured at 256 x 1285 x 2000: probe 97 -> 92 us,
-    // rest 292 -> 272 us against 1 span each; at 64 problems, rest pass with 64 / 125 hypotheses a workgroup: 133 / 91 us)
-    auto pass = [&](int set_lo, int set_hi, int hs, const int32_t* list, const int32_t* nlist) {
+    const int capsets = cdiv(stride, 64);
+    const bool staged = stride >= 64 * kStageMinSets;
+    int nstage = 1;
+    if (staged)
+      for (nstage = 0; nstage < (int)(sizeof(kStagePlan) / sizeof(kStagePlan[0])) && kStagePlan[nstage] < capsets;) ++nstage;
+    int32_t* alive_idx[2] = {(int32_t*)(ws + o_alive), (int32_t*)(ws + o_alive2)};
+    int32_t* stage_state = (int32_t*)(ws + o_stage);
+    // Every pass in the hypothesis-split form (point blocks of at most 4 sets, see the kernel): a workgroup sets up a
+    // quarter of the points of a full block, so it takes more hypotheses -- 4 spans where a problem is one block (the
+    // probe, a stage of 4 sets), 2 otherwise, and never less than one full LDS chunk over a survivor list (measured at
+    // 256 x 1285 x 2000: probe 97 -> 92 us, rest 292 -> 272 us against 1 span each; at 64 problems, rest pass with 64 /
+    // 125 hypotheses a workgroup: 133 / 91 us)
+    auto pass = [&](int k_lo, int k_hi, const int32_t* list) {
+      const int sets = min(k_hi, capsets) - k_lo;
+      int hs = min(H, (sets <= 4 ? 4 : 2) * hspan);
+      if (list) hs = min(H, max(kScoreHypChunkMax, hs));
       const int hck = cdiv(hs, cdiv(hs, kScoreHypChunkMax));
-      const int sets = min(set_hi, cdiv(stride, 64)) - set_lo;
       SOSVO_LAUNCH(ctx,(ransac_score_kernel<true, 4, true>), dim3(cdiv(H, hs), cdiv(sets, 4), nprob), dim3(kThreads), 0,
-                   ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hck, hs, thr, fast_ok, hyp, counts, set_lo, set_hi, 1,
-                   list, nlist);
+                   ctx->stream, f, p, cam, cam_off, cam_rot, n, stride, H, hck, hs, thr, fast_ok, hyp, counts, k_lo, k_hi, 1,
+                   list, list ? list + (size_t)nprob * H : nullptr, split);
     };
-    pass(0, kProbeSets, min(H, 4 * hspan), nullptr, nullptr);
-    SOSVO_LAUNCH(ctx,ransac_prune_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, n, stride, H,
-                 kProbeSets, thr, hyp, counts, alive_idx, n_alive);
-    pass(kProbeSets, INT_MAX, min(H, max(kScoreHypChunkMax, 2 * hspan)), alive_idx, n_alive);
+    int k_lo = 0;
+    const int32_t* list = nullptr;
+    for (int s = 0; s < nstage; ++s) {
+      const int k_hi = staged ? kStagePlan[s] : kProbeSets;
+      pass(k_lo, k_hi, list);
+      int32_t* out = alive_idx[s & 1];
+      SOSVO_LAUNCH(ctx,ransac_prune_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, f, p, cam, cam_off, n, stride, H,
+                   k_hi, thr, hyp, counts, list, list ? list + (size_t)nprob * H : nullptr, out, out + (size_t)nprob * H,
+                   stage_state);
+      list = out;
+      k_lo = k_hi;
+    }
+    pass(k_lo, INT_MAX, list);
   } else if (t1)
     SOSVO_LAUNCH(ctx,(ransac_score_kernel<true, 4, true>), SOSVO_SCORE_ARGS);
   else if (ident)
