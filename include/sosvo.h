@@ -321,15 +321,40 @@ int32_t sosvo_refine_subpix(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, i
  *   5. l > 0: g_{l-1} = 2 g_l.  l = 0: the guess is rounded once more (outside: LOST), err = sum |J - T| / (1024 N) there,
  *      next = (float)g, status 1.  A LOST point: status 0, err 0, next = (float) of the guess it was lost with.
  *   half 2 .. 10, max_iter 1 .. 30, eps >= 0, min_eig >= 0 (OpenCV's default 1e-4), cap <= 4096, levels 1 .. 4; otherwise
- *   SOSVO_ERR_ARG.  No wrap-around of the panorama's columns.
+ *   SOSVO_ERR_ARG.  No wrap-around of the panorama's columns without SOSVO_LK_CYCLIC_COLUMNS (below).
  *   back (optional, [nprob, cap, 2] f32) with fb_max > 0: the forward-backward check.  Every point with status 1 is tracked
  *   back from next_pts (no initial guess) in image next_img[p] to image prev_img[p]; back receives that position (next_pts for
  *   the points whose status was 0) and the status is cleared where the way back is lost or |back - prev|^2 > fb_max^2
- *   (differences of the float32 values in double).                                                                      */
+ *   (differences of the float32 values in double).
+ *
+ * CYCLIC COLUMNS (a panorama is a full circle: column W = cols is column 0 again).
+ * sosvo_gray_pyramid_cyclic is sosvo_gray_pyramid with the column index (2 x + j) mod cols_l in place of the clamp; rows and
+ * row ranges exactly as above, clamp included.  It needs cols % 2^(levels - 1) == 0, so that level l has exactly cols >> l
+ * columns and is one period; otherwise SOSVO_ERR_ARG.  Same sizes, same buffer (sosvo_gray_pyramid_bytes).
+ * sosvo_track_lk with SOSVO_LK_CYCLIC_COLUMNS in flags (it combines with SOSVO_LK_INITIAL_FLOW; pyr = the cyclic pyramid) is
+ * the rule above with these changes and no others:
+ *   a. wherever a position is rounded to the 1/32-px grid (the template centre, every guess, the final rounding) the x
+ *      component tq_x = floor(32 x + 0.5) is reduced to tq_x mod (32 cols_l), in [0, 32 cols_l).  "Outside the level" is a
+ *      matter of the rows only; a non-finite value, or |32 x + 0.5| >= 2^40, is outside as it is above.
+ *   b. every sample's two column taps are (bx + j) mod cols_l and (bx + j + 1) mod cols_l: base cols_l - 1 with a fraction
+ *      blends into column 0.
+ *   c. the step is taken from the wrapped rounded guess: g = gq / 32 + (dx, dy); g_{l-1} = 2 g_l as above.
+ *   d. the x written is w = g.x - W floor(g.x / W) in double, cast to float32; a float that equals W is written as 0.  The
+ *      same for the guess a LOST point is written with.  y, status and err are unchanged.
+ *   e. in the forward-backward check the x part of |back - prev|^2 is the cyclic distance min(d, W - d), d = |back.x - prev.x|,
+ *      with prev.x as given: the check assumes starts within one period of [0, W) (d <= W); a start further out is tracked
+ *      as a position on the circle but its check fails.
+ *   Same window sizes, same sums, same bounds.  It needs cols % 2^(levels - 1) == 0 and at least 2 half + 3 columns on the
+ *   top level (cols >> (levels - 1): the template fits one period, no column is sampled twice in a row of it); otherwise
+ *   SOSVO_ERR_ARG.  Points whose windows stay away from columns 0 and W - 1 on every level get the bits of the plain call.
+ *   Flag value 2 is not a flag and stays refused.                                                                       */
 #define SOSVO_LK_INITIAL_FLOW 1
+#define SOSVO_LK_CYCLIC_COLUMNS 4
 int32_t sosvo_gray_pyramid_bytes(sosvo_ctx* ctx, int32_t nimg, int32_t rows, int32_t cols, int32_t levels, int64_t* bytes);
 int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
                            const int32_t* row_range, uint8_t* pyr);
+int32_t sosvo_gray_pyramid_cyclic(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
+                                  const int32_t* row_range, uint8_t* pyr);
 int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
                        int32_t levels, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int32_t nprob,
                        int32_t cap, const float* prev_pts, const int32_t* n, int32_t half, int32_t max_iter, double eps,
@@ -432,6 +457,20 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
                                   const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
                                   const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
                                   double min_dv, double max_du, int32_t max_distance, uint32_t* keys);
+
+/* sosvo_match_hamming_gated in its frame-to-frame form (no v side) with the CYCLIC u side: the
+ * positions are columns of a panorama of `period` columns, a full circle.  With d = fabs(u_t - u_q) in double,
+ *   gate(i, j) = max_du > 0 ? (d <= max_du || d >= period - max_du) : true
+ * where period - max_du is formed once, in double, on the host.  Where that difference is exact (max_du a multiple of 2^-38)
+ * this is sosvo_f2f_assemble_cyclic's d <= max_du || period - d <= max_du; where it rounds, the two can differ for a pair whose
+ * d equals the rounded difference, and the assemble behind the matcher decides (it gates again).
+ * period: a positive integer up to 16384, otherwise SOSVO_ERR_ARG.  Everything else (blocks, slots, reversed problems, the
+ * cap, the train-range split) as in sosvo_match_hamming_gated; with max_du <= 0 the keys are those of that call with both
+ * sides disabled. */
+int32_t sosvo_match_hamming_gated_cyclic(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                                         const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
+                                         const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride,
+                                         int32_t t_stride, double max_du, double period, int32_t max_distance, uint32_t* keys);
 
 /* Lowe's distinctiveness ("ratio") rule fused into the 1-NN search (omnistereo/camera_models.py:421-423: knnMatch(k = 2) and
  * m[0].distance < m[1].distance * 0.75).  Arguments as in sosvo_match_hamming_gated, and two forms:
@@ -697,6 +736,24 @@ int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, co
                                    int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam, int32_t* corr_q,
                                    int32_t* corr_t, int32_t* n, int32_t* n_topview);
 
+/* The two assembles with the CYCLIC |du| gate: a panorama is a full circle, column W is column 0
+ * again, W = pano_top[0] / pano_bot[0] of the rig for the view.  With d = |u_a - u_b| computed in double from the float32
+ * values, a pair passes iff d <= f2f_max_hdiff or W - d <= f2f_max_hdiff; the gate's switch is the plain one's (off for
+ * f2f_max_hdiff <= 0).  Both comparisons are exact: differences of float32 coordinates below 16384, and W - d, are
+ * representable in double.  Arguments, outputs and order exactly as in sosvo_f2f_assemble / sosvo_f2f_assemble_tracked; the
+ * two periods must be positive integers (up to 16384), otherwise SOSVO_ERR_ARG.                                          */
+int32_t sosvo_f2f_assemble_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                  const double* X, const double* b_top, const double* b_bot, const int32_t* M,
+                                  int32_t frame_cap, const int32_t* ref_frame, const int32_t* cur_frame,
+                                  const uint32_t* keys_top, const int32_t* order_top, const uint32_t* keys_bot,
+                                  const int32_t* order_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
+                                  int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview);
+int32_t sosvo_f2f_assemble_tracked_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                          const double* X, const int32_t* M, int32_t frame_cap, const int32_t* ref_frame,
+                                          const float* trk_top, const float* trk_bot, const uint8_t* st_top,
+                                          const uint8_t* st_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
+                                          int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview);
+
 /* ---- RGB-D (perspective camera) variant: a12 + a15 glue ----------------------------------------
  * Constants of one RGB-D camera (HOST struct): RGBDCamModel (omnistereo/camera_models.py:756-779) and the
  * RGBDFrame ranges (pose_est_tools.py:428-430, in the depth map's units).                           */
@@ -831,6 +888,21 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
  * A pair's record depends only on its two slots' frames, its seed and the context's settings. */
 #define SOSVO_FLAG_LK_F2F 0x80
 #define SOSVO_LK_MAX_LEVELS 4
+/* ---- cyclic panorama columns in the batch and sequence entry points --------------------------------
+ *   SOSVO_FLAG_CYCLIC_F2F    a panorama is a full circle, column `cols` is column 0 again: the frame-to-frame |du| gate is the
+ *                            cyclic one (sosvo_f2f_assemble_cyclic in place of sosvo_f2f_assemble); with SOSVO_FLAG_GATED_F2F
+ *                            the gate is cyclic inside the matcher as well (sosvo_match_hamming_gated_cyclic, the view's period);
+ *                            with SOSVO_FLAG_LK_F2F the tracked assemble is sosvo_f2f_assemble_tracked_cyclic, the store's
+ *                            pyramids are those of sosvo_gray_pyramid_cyclic and the tracker runs with SOSVO_LK_CYCLIC_COLUMNS.
+ * Honoured in sosvo_batch_cfg.ransac_flags (sosvo_frame_pair_batch*, sosvo_sequence_*); the bit is free in that word only: in
+ * sosvo_rgbd_batch_cfg.flags bits 8 - 9 are the detector, and a pinhole image is not cyclic.  The period is pano_top[0] /
+ * pano_bot[0] of the rig, positive integers.  With SOSVO_FLAG_LK_F2F it needs cols % 8 == 0 (every level the store may hold
+ * is one period: 2^(SOSVO_LK_MAX_LEVELS - 1); the workspace functions take no context), and at call time 2 half + 3 columns
+ * on the top level of the context's settings; together with SOSVO_FLAG_GATED_F2F | SOSVO_FLAG_RATIO_F2F it is refused (the
+ * ratio form has no cyclic gate).  Otherwise SOSVO_ERR_ARG and a workspace size of 0.  The bit never reaches the RANSAC flags;
+ * workspace sizes with the bit set equal those with it clear (no new buffers), and with the bit clear launches and results
+ * are unchanged. */
+#define SOSVO_FLAG_CYCLIC_F2F 0x200
 typedef struct sosvo_lk_options {
   int32_t half, levels, max_iter, reserved;
   double eps, min_eig, fb_max;

@@ -71,6 +71,7 @@ SIGNATURES = {
     "sosvo_refine_subpix": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_f64, c_p]),
     "sosvo_gray_pyramid_bytes": (c_i32, [c_p, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_int64)]),
     "sosvo_gray_pyramid": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sosvo_gray_pyramid_cyclic": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_track_lk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32,
                                c_f64, c_f64, c_i32, c_p, c_p, c_p, c_p, c_f64]),
     "sosvo_refine_stereo_lk": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_f64, c_f64,
@@ -86,6 +87,8 @@ SIGNATURES = {
     "sosvo_match_hamming": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_match_hamming_gated": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64,
                                           c_i32, c_p]),
+    "sosvo_match_hamming_gated_cyclic": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64,
+                                                 c_f64, c_i32, c_p]),
     "sosvo_match_hamming_ratio": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_f64, c_f64,
                                           c_i32, c_i32, c_p, c_p]),
     "sosvo_match_radius": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
@@ -100,6 +103,8 @@ SIGNATURES = {
     "sosvo_stereo_assemble": (c_i32, [c_p] + [c_p] * 9 + [c_i32] * 4 + [c_p] * 9),
     "sosvo_f2f_assemble": (c_i32, [c_p] + [c_p] * 7 + [c_i32] + [c_p] * 6 + [c_i32, c_i32] + [c_p] * 7),
     "sosvo_f2f_assemble_tracked": (c_i32, [c_p] + [c_p] * 5 + [c_i32] + [c_p] * 5 + [c_i32, c_i32] + [c_p] * 7),
+    "sosvo_f2f_assemble_cyclic": (c_i32, [c_p] + [c_p] * 7 + [c_i32] + [c_p] * 6 + [c_i32, c_i32] + [c_p] * 7),
+    "sosvo_f2f_assemble_tracked_cyclic": (c_i32, [c_p] + [c_p] * 5 + [c_i32] + [c_p] * 5 + [c_i32, c_i32] + [c_p] * 7),
     "sosvo_ransac_abs_pose": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
                                       c_i32, c_i32, c_u64, c_p, c_p, c_p, c_p, c_p, c_p]),
     "sosvo_ransac_abs_pose_seeds": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_i32, c_f64,
@@ -164,7 +169,9 @@ SUBPIX_MAX_ITER = 10               # what the one-call and sequence entry points
 SUBPIX_EPS = 0.01
 FLAG_LK_F2F = 0x80                 # Lucas-Kanade tracking in place of the frame-to-frame matcher (sosvo_batch_cfg.ransac_flags)
 FLAG_LK_STEREO = 0x100             # sub-pixel static stereo: sosvo_refine_stereo_lk in the front end (sosvo_batch_cfg.ransac_flags)
+FLAG_CYCLIC_F2F = 0x200            # cyclic panorama columns frame to frame (sosvo_batch_cfg.ransac_flags only: DESIGN.md section 34)
 LK_INITIAL_FLOW = 1                # SOSVO_LK_INITIAL_FLOW: next_pts holds the starting guess on entry
+LK_CYCLIC_COLUMNS = 4              # SOSVO_LK_CYCLIC_COLUMNS: the columns are one period (a panorama is a full circle)
 LK_MAX_HALF, LK_MAX_LEVELS, LK_MAX_ITER, LK_MAX_CAP = 10, 4, 30, 4096
 DETECTOR_GFT = 0
 DETECTOR_ORB = 1

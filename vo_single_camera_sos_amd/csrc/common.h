@@ -269,7 +269,8 @@ struct sosvo_lk_images {
 bool sosvo_lk_options_ok(const sosvo_lk_options& o);
 bool sosvo_stereo_lk_options_ok(const sosvo_stereo_lk_options& o);
 int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
-                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame);
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic = false);
 int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,
                               const int32_t* from_img, const int32_t* to_img, int32_t nprob, int32_t cap, const float* pts,
-                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back);
+                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back,
+                              bool cyclic = false);

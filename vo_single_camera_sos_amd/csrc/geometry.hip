@@ -227,8 +227,19 @@ __global__ __launch_bounds__(kThreads) void stereo_assemble_slots_kernel(
                         keys, order, nmask, cap, out_cap, m_top, m_bot, d_top, d_bot, X, b_top, b_bot, M, n_cand);
 }
 
-__global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
-    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+// The CYCLIC frame-to-frame |du| gate: a panorama's column W is column 0 again, so a pair passes iff
+// d <= max_du or W - d <= max_du, d = |a - b| in double from the float32 values.  Both comparisons are exact (differences of
+// float32 coordinates below 16384 and W - d are doubles), and the switch is sv_pixel_gate's: on for max_du > 0.
+__device__ __forceinline__ bool f2f_du_gate_cyclic(double ua, double ub, double max_du, double W) {
+  if (!(max_du > 0)) return true;
+  const double d = fabs(ua - ub);
+  return d <= max_du || W - d <= max_du;
+}
+
+// (CYC: the gate above with the view's period rig.pano_top[0] / rig.pano_bot[0]; nothing else differs)
+template <bool CYC>
+__device__ __forceinline__ void f2f_assemble_body(
+    const sosvo_rig& rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
     const double* __restrict__ b_top, const double* __restrict__ b_bot, const int32_t* __restrict__ M, int frame_cap,
     const int32_t* __restrict__ ref_frame, const int32_t* __restrict__ cur_frame,
     const uint32_t* __restrict__ keys_top, const int32_t* __restrict__ order_top,
@@ -266,7 +277,10 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
         if (valid && rig.f2f_max_hdiff >= 0) {              // :245-247, gate inside common_cv.py:177
           const double u_train = (double)mm[2 * ((size_t)fr_ref * frame_cap + t)];
           const double u_query = (double)mm[2 * ((size_t)fr_cur * frame_cap + q)];
-          valid = sv_pixel_gate(u_train, 0.0, u_query, 0.0, -1.0, rig.f2f_max_hdiff);
+          if constexpr (CYC)
+            valid = f2f_du_gate_cyclic(u_train, u_query, rig.f2f_max_hdiff, view == 0 ? rig.pano_top[0] : rig.pano_bot[0]);
+          else
+            valid = sv_pixel_gate(u_train, 0.0, u_query, 0.0, -1.0, rig.f2f_max_hdiff);
         }
       }
       const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
@@ -289,11 +303,34 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
   __syncthreads();
   if (tid == 0) n[pr] = min(s_running, corr_cap);
 }
+__global__ __launch_bounds__(kThreads) void f2f_assemble_kernel(
+    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+    const double* __restrict__ b_top, const double* __restrict__ b_bot, const int32_t* __restrict__ M, int frame_cap,
+    const int32_t* __restrict__ ref_frame, const int32_t* __restrict__ cur_frame,
+    const uint32_t* __restrict__ keys_top, const int32_t* __restrict__ order_top,
+    const uint32_t* __restrict__ keys_bot, const int32_t* __restrict__ order_bot, int corr_cap,
+    double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
+    int32_t* __restrict__ corr_t, int32_t* __restrict__ n, int32_t* __restrict__ n_topview) {
+  f2f_assemble_body<false>(rig, m_top, m_bot, X, b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot, corr_cap, f,
+                           p, cam, corr_q, corr_t, n, n_topview);
+}
+__global__ __launch_bounds__(kThreads) void f2f_assemble_cyclic_kernel(
+    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+    const double* __restrict__ b_top, const double* __restrict__ b_bot, const int32_t* __restrict__ M, int frame_cap,
+    const int32_t* __restrict__ ref_frame, const int32_t* __restrict__ cur_frame,
+    const uint32_t* __restrict__ keys_top, const int32_t* __restrict__ order_top,
+    const uint32_t* __restrict__ keys_bot, const int32_t* __restrict__ order_bot, int corr_cap,
+    double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
+    int32_t* __restrict__ corr_t, int32_t* __restrict__ n, int32_t* __restrict__ n_topview) {
+  f2f_assemble_body<true>(rig, m_top, m_bot, X, b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot, corr_cap, f,
+                           p, cam, corr_q, corr_t, n, n_topview);
+}
 
 // f2f_assemble_kernel for tracked points: the correspondences of pair pr are the reference frame's points whose track
 // succeeded, in point order; the bearing of the tracked pixel is computed here, as stereo_assemble_frame computes its own.
-__global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_kernel(
-    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+template <bool CYC>
+__device__ __forceinline__ void f2f_assemble_tracked_body(
+    const sosvo_rig& rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
     const int32_t* __restrict__ M, int frame_cap, const int32_t* __restrict__ ref_frame, const float* __restrict__ trk_top,
     const float* __restrict__ trk_bot, const uint8_t* __restrict__ st_top, const uint8_t* __restrict__ st_bot, int corr_cap,
     double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
@@ -319,7 +356,12 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_kernel(
       if (t < nt && st[kb + t] != 0) {
         const double u = (double)trk[2 * (kb + t)], v = (double)trk[2 * (kb + t) + 1];
         valid = true;
-        if (rig.f2f_max_hdiff >= 0) valid = sv_pixel_gate((double)mm[2 * (rb + t)], 0.0, u, 0.0, -1.0, rig.f2f_max_hdiff);
+        if (rig.f2f_max_hdiff >= 0) {
+          if constexpr (CYC)
+            valid = f2f_du_gate_cyclic((double)mm[2 * (rb + t)], u, rig.f2f_max_hdiff, pano[0]);
+          else
+            valid = sv_pixel_gate((double)mm[2 * (rb + t)], 0.0, u, 0.0, -1.0, rig.f2f_max_hdiff);
+        }
         double az, el;
         sv_pano_angles(u, v, pano, &az, &el);
         sv_bearing(az, el, b);
@@ -342,6 +384,24 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_kernel(
   }
   __syncthreads();
   if (tid == 0) n[pr] = min(s_running, corr_cap);
+}
+__global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_kernel(
+    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+    const int32_t* __restrict__ M, int frame_cap, const int32_t* __restrict__ ref_frame, const float* __restrict__ trk_top,
+    const float* __restrict__ trk_bot, const uint8_t* __restrict__ st_top, const uint8_t* __restrict__ st_bot, int corr_cap,
+    double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
+    int32_t* __restrict__ corr_t, int32_t* __restrict__ n, int32_t* __restrict__ n_topview) {
+  f2f_assemble_tracked_body<false>(rig, m_top, m_bot, X, M, frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t,
+                                   n, n_topview);
+}
+__global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_cyclic_kernel(
+    sosvo_rig rig, const float* __restrict__ m_top, const float* __restrict__ m_bot, const double* __restrict__ X,
+    const int32_t* __restrict__ M, int frame_cap, const int32_t* __restrict__ ref_frame, const float* __restrict__ trk_top,
+    const float* __restrict__ trk_bot, const uint8_t* __restrict__ st_top, const uint8_t* __restrict__ st_bot, int corr_cap,
+    double* __restrict__ f, double* __restrict__ p, int32_t* __restrict__ cam, int32_t* __restrict__ corr_q,
+    int32_t* __restrict__ corr_t, int32_t* __restrict__ n, int32_t* __restrict__ n_topview) {
+  f2f_assemble_tracked_body<true>(rig, m_top, m_bot, X, M, frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t,
+                                   n, n_topview);
 }
 
 }  // namespace
@@ -459,6 +519,33 @@ int32_t sosvo_stereo_assemble_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, c
   return SOSVO_OK;
 }
 
+// the cyclic gate's periods: the views' column counts, positive integers
+static bool f2f_periods_ok(const sosvo_rig* rig) {
+  const double a = rig->pano_top[0], b = rig->pano_bot[0];
+  return a >= 1.0 && b >= 1.0 && a <= 16384.0 && b <= 16384.0 && a == floor(a) && b == floor(b);
+}
+
+int32_t sosvo_f2f_assemble_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                  const double* X, const double* b_top, const double* b_bot, const int32_t* M,
+                                  int32_t frame_cap, const int32_t* ref_frame, const int32_t* cur_frame,
+                                  const uint32_t* keys_top, const int32_t* order_top, const uint32_t* keys_bot,
+                                  const int32_t* order_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
+                                  int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && b_top && b_bot && M && ref_frame && cur_frame,
+                "null input pointer");
+  SOSVO_REQUIRE(ctx, keys_top && order_top && keys_bot && order_bot && f && p && cam && corr_q && corr_t && n,
+                "null pointer");
+  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
+  SOSVO_REQUIRE(ctx, f2f_periods_ok(rig_host), "the period (pano_top[0], pano_bot[0]) must be a positive integer up to 16384");
+  if (npairs == 0) return SOSVO_OK;
+  SOSVO_LAUNCH(ctx, f2f_assemble_cyclic_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, b_top,
+               b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot, corr_cap, f, p, cam, corr_q,
+               corr_t, n, n_topview);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
 int32_t sosvo_f2f_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
                            const double* X, const double* b_top, const double* b_bot, const int32_t* M,
                            int32_t frame_cap, const int32_t* ref_frame, const int32_t* cur_frame,
@@ -491,6 +578,24 @@ int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, co
   SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
   if (npairs == 0) return SOSVO_OK;
   SOSVO_LAUNCH(ctx, f2f_assemble_tracked_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, M,
+               frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_f2f_assemble_tracked_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
+                                          const double* X, const int32_t* M, int32_t frame_cap, const int32_t* ref_frame,
+                                          const float* trk_top, const float* trk_bot, const uint8_t* st_top,
+                                          const uint8_t* st_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
+                                          int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && M && ref_frame && trk_top && trk_bot && st_top && st_bot,
+                "null input pointer");
+  SOSVO_REQUIRE(ctx, f && p && cam && corr_q && corr_t && n, "null output pointer");
+  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
+  SOSVO_REQUIRE(ctx, f2f_periods_ok(rig_host), "the period (pano_top[0], pano_bot[0]) must be a positive integer up to 16384");
+  if (npairs == 0) return SOSVO_OK;
+  SOSVO_LAUNCH(ctx, f2f_assemble_tracked_cyclic_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, M,
                frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;

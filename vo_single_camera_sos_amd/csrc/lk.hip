@@ -72,6 +72,10 @@ __device__ __forceinline__ void lk_level_rows(const int32_t* __restrict__ row_ra
 
 // ---- one pyramid level: (sum k_i k_j in[clamp(2 y + i)][clamp(2 x + j)] + 128) >> 8, k = (1, 4, 6, 4, 1) --------------------
 // (the tile blockIdx.x, blockIdx.y of image `image`, which belongs to view `view` of the row range)
+// CYC (sosvo_gray_pyramid_cyclic): the column index is (2 x + j) mod cols_in, cols_in even.  An output
+// column reads the columns -2 .. cols_in of the level below: one conditional add per side wraps them; the clamp behind it only
+// keeps the loads of a tile's lanes beyond the level (never used) inside the row.
+template <bool CYC = false>
 __device__ __forceinline__ void lk_pyr_down_tile(const uint8_t* __restrict__ in, int rows_in, int cols_in, uint8_t* __restrict__ out,
                                                  int rows_out, int cols_out, const int32_t* __restrict__ row_range, int image, int view,
                                                  int rows0, int level_in) {
@@ -88,7 +92,13 @@ __device__ __forceinline__ void lk_pyr_down_tile(const uint8_t* __restrict__ in,
   const int tid = threadIdx.y * kPyrTileX + threadIdx.x;
   for (int s = tid; s < TH * TW; s += kPyrTileX * kPyrTileY) {
     const int i = s / TW, j = s - i * TW;
-    const int y = clampi(2 * y0 - 2 + i, ri0, ri1 - 1), x = clampi(2 * x0 - 2 + j, 0, cols_in - 1);
+    const int y = clampi(2 * y0 - 2 + i, ri0, ri1 - 1);
+    int x = 2 * x0 - 2 + j;
+    if constexpr (CYC) {
+      x += x < 0 ? cols_in : 0;
+      x -= x >= cols_in ? cols_in : 0;
+    }
+    x = clampi(x, 0, cols_in - 1);
     s_in[i][j] = src[(size_t)y * cols_in + x];
   }
   __syncthreads();
@@ -112,6 +122,14 @@ __global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_kernel(const
                                                                           int rows0, int level_in) {
   const int image = blockIdx.z;
   lk_pyr_down_tile(in, rows_in, cols_in, out, rows_out, cols_out, row_range, image, image / imgs_per_range, rows0, level_in);
+}
+
+__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_cyclic_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
+                                                                                 uint8_t* __restrict__ out, int rows_out, int cols_out,
+                                                                                 const int32_t* __restrict__ row_range,
+                                                                                 int imgs_per_range, int rows0, int level_in) {
+  const int image = blockIdx.z;
+  lk_pyr_down_tile<true>(in, rows_in, cols_in, out, rows_out, cols_out, row_range, image, image / imgs_per_range, rows0, level_in);
 }
 
 // ---- the images of a frame store (SOSVO_FLAG_LK_F2F) ----------------------------------------------------
@@ -138,6 +156,15 @@ __global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_slots_kernel
   const int v = blockIdx.z / nf, i = blockIdx.z - v * nf;
   lk_pyr_down_tile(in, rows_in, cols_in, out, rows_out, cols_out, row_range, v * slots + tab.slot[i], v, rows0, level_in);
 }
+__global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_slots_cyclic_kernel(const uint8_t* __restrict__ in, int rows_in,
+                                                                                       int cols_in, uint8_t* __restrict__ out,
+                                                                                       int rows_out, int cols_out,
+                                                                                       const int32_t* __restrict__ row_range, int nf,
+                                                                                       sosvo_slot_table tab, int slots, int rows0,
+                                                                                       int level_in) {
+  const int v = blockIdx.z / nf, i = blockIdx.z - v * nf;
+  lk_pyr_down_tile<true>(in, rows_in, cols_in, out, rows_out, cols_out, row_range, v * slots + tab.slot[i], v, rows0, level_in);
+}
 
 // ---- the tracker -------------------------------------------------------------------------------------------------------------
 template <int GS>
@@ -149,8 +176,20 @@ __device__ __forceinline__ long long group_sum(long long v) {
 
 // the integer bilinear sample of a level at pixel (x, y) + (fx, fy) / 32, coordinates clamped to the columns and to the rows
 // [r0, r1) of the level
+// CYC: the two column taps are x mod cols and (x + 1) mod cols.  x lies within half + 2 columns of a base in [0, cols) and the
+// top level holds at least 2 half + 3 columns (the entry point checks it), so one conditional add per side is the modulo.
+template <bool CYC = false>
 __device__ __forceinline__ int lk_sample(const uint8_t* __restrict__ img, int cols, int r0, int r1, int x, int y, int fx, int fy) {
-  const int xa = clampi(x, 0, cols - 1), xb = clampi(x + 1, 0, cols - 1);
+  int xa, xb;
+  if constexpr (CYC) {
+    xa = x + (x < 0 ? cols : 0);
+    xa -= xa >= cols ? cols : 0;
+    xb = xa + 1;
+    xb -= xb >= cols ? cols : 0;
+  } else {
+    xa = clampi(x, 0, cols - 1);
+    xb = clampi(x + 1, 0, cols - 1);
+  }
   const int ya = clampi(y, r0, r1 - 1), yb = clampi(y + 1, r0, r1 - 1);
   const int p00 = img[(size_t)ya * cols + xa], p01 = img[(size_t)ya * cols + xb];
   const int p10 = img[(size_t)yb * cols + xa], p11 = img[(size_t)yb * cols + xb];
@@ -164,11 +203,31 @@ struct LkGrid {
   int bx, by, fx, fy;
   bool inside;
 };
+// CYC: tqx is reduced to [0, 32 cols) -- tq - P floor(tq / P), P = 32 cols: exact, tq is an integer below 2^40 and P one of at
+// most 2^19, so the quotient's rounding (below 2^-17) never reaches the next integer from a fraction of at least 1 / P -- and
+// "inside" is a matter of the rows; a non-finite value or |32 x + 0.5| >= 2^40 is outside, as it is without CYC.
+template <bool CYC = false>
 __device__ __forceinline__ LkGrid lk_grid(double cx, double cy, int cols, int r0, int r1) {
   LkGrid g;
   g.tqx = floor(32.0 * cx + 0.5);
   g.tqy = floor(32.0 * cy + 0.5);
-  g.inside = g.tqx >= 0.0 && g.tqx <= 32.0 * (double)(cols - 1) && g.tqy >= 32.0 * (double)r0 && g.tqy <= 32.0 * (double)(r1 - 1);
+  if constexpr (CYC) {
+    const double period = 32.0 * (double)cols;
+    const bool okx = fabs(32.0 * cx + 0.5) < 1099511627776.0;  // (false for NaN)
+    // (a guess one step away from a reduced position lies within a period of [0, P): one conditional add per side is the
+    // reduction; the division serves the rest -- a start or a guess from anywhere, a step of a period or more.  Same value.)
+    double t = g.tqx;
+    if (t >= -period && t < 2.0 * period) {
+      t += t < 0.0 ? period : 0.0;
+      t -= t >= period ? period : 0.0;
+    } else {
+      t = t - period * floor(t / period);
+    }
+    g.tqx = okx ? t : 0.0;
+    g.inside = okx && g.tqy >= 32.0 * (double)r0 && g.tqy <= 32.0 * (double)(r1 - 1);
+  } else {
+    g.inside = g.tqx >= 0.0 && g.tqx <= 32.0 * (double)(cols - 1) && g.tqy >= 32.0 * (double)r0 && g.tqy <= 32.0 * (double)(r1 - 1);
+  }
   const int qx = g.inside ? (int)g.tqx : 0, qy = g.inside ? (int)g.tqy : 0;
   g.bx = qx >> 5;
   g.fx = qx & 31;
@@ -196,7 +255,12 @@ constexpr int kLkLdsWords16 = 4 * lk_group_words(5), kLkLdsWords64 = lk_group_wo
 // for the others), and the status is cleared where the point is lost or |back - ref|^2 > fb_max^2 (ref = the forward start).
 // store_pt (nullptr: the points of problem p are the rows p * cap ...): the forward start points -- `start` of the forward pass,
 // `ref` of the backward pass -- are read where they lie, problem p's from point store_pt[p] on (a frame store's m_top / m_bot).
-template <int GS>
+//
+// CYC (SOSVO_LK_CYCLIC_COLUMNS): the columns are one period.  Rounded x positions and column taps wrap
+// (lk_grid, lk_sample), a position is never "outside" by its x, the x written is g.x - W floor(g.x / W) (W = level 0's columns;
+// a float that rounds up to W is written as 0), and the backward pass measures x the short way round.  Everything else is
+// the text below, shared.
+template <int GS, bool CYC = false>
 __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* __restrict__ row_range, const int32_t* __restrict__ from_img,
                                                       const int32_t* __restrict__ to_img, const float* __restrict__ start,
                                                       const int32_t* __restrict__ n, float* __restrict__ out,
@@ -249,14 +313,14 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
       const uint8_t* ia = a.lv.base[l] + (size_t)img_a * rows * cols;
       const uint8_t* ib = a.lv.base[l] + (size_t)img_b * rows * cols;
       const double scale = 1.0 / (double)(1 << l);
-      const LkGrid t = lk_grid(px * scale, py * scale, cols, ra0, ra1);
+      const LkGrid t = lk_grid<CYC>(px * scale, py * scale, cols, ra0, ra1);
       bool run = live && !lost && t.inside;  // this group iterates at this level
       if (live && !lost && !t.inside && l == 0) lost = true;
       // ---- the template and its gradients
       if (run) {
         for (int s = r; s < side3 * side3; s += GS) {
           const int i = s / side3, j = s - i * side3;
-          s_T[s] = lk_sample(ia, cols, ra0, ra1, t.bx + j - half - 1, t.by + i - half - 1, t.fx, t.fy);
+          s_T[s] = lk_sample<CYC>(ia, cols, ra0, ra1, t.bx + j - half - 1, t.by + i - half - 1, t.fx, t.fy);
         }
       }
       __syncthreads();
@@ -291,7 +355,7 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
       bool iterating = run;
       for (int it = 0; it < a.max_iter; ++it) {  // (uniform bound; left when no group of the wave iterates)
         if (!__any(iterating)) break;
-        const LkGrid g = lk_grid(cx, cy, cols, rb0, rb1);
+        const LkGrid g = lk_grid<CYC>(cx, cy, cols, rb0, rb1);
         if (iterating && !g.inside) {  // left the image: lost at level 0, the end of this level above it
           iterating = false;
           if (l == 0) lost = true;
@@ -300,7 +364,7 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
         if (iterating) {
           for (int e = r; e < N; e += GS) {
             const int i = e / side1, j = e - i * side1;
-            const long long d = lk_sample(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
+            const long long d = lk_sample<CYC>(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
             s1 += d * s_gx[e];
             s2 += d * s_gy[e];
           }
@@ -337,14 +401,14 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
         cy *= 2.0;
       } else {
         // ---- the residual at the final rounded position
-        const LkGrid g = lk_grid(cx, cy, cols, rb0, rb1);
+        const LkGrid g = lk_grid<CYC>(cx, cy, cols, rb0, rb1);
         const bool ok = live && !lost && g.inside;
         if (live && !lost && !g.inside) lost = true;
         long long s = 0;
         if (ok) {
           for (int e = r; e < N; e += GS) {
             const int i = e / side1, j = e - i * side1;
-            const int d = lk_sample(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
+            const int d = lk_sample<CYC>(ib, cols, rb0, rb1, g.bx + j - half, g.by + i - half, g.fx, g.fy) - s_Tc[e];
             s += d < 0 ? -d : d;
           }
         }
@@ -363,7 +427,13 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
           err[o] = 0.0f;
         }
       } else {
-        const float ox = (float)cx, oy = (float)cy;
+        float ox = (float)cx;
+        const float oy = (float)cy;
+        if constexpr (CYC) {
+          const double W = (double)a.lv.cols[0];
+          ox = (float)(cx - W * floor(cx / W));
+          if (ox == (float)W) ox = 0.0f;
+        }
         out[2 * o] = ox;
         out[2 * o + 1] = oy;
         if (!backward) {
@@ -371,7 +441,9 @@ __global__ __launch_bounds__(64) void lk_track_kernel(LkArgs a, const int32_t* _
           err[o] = lost ? 0.0f : (float)((double)err_sum / (1024.0 * (double)N));
         } else {
           const size_t ro = store_pt ? (size_t)store_pt[p] + k : o;
-          const double ddx = (double)ox - (double)ref[2 * ro], ddy = (double)oy - (double)ref[2 * ro + 1];
+          double ddx = (double)ox - (double)ref[2 * ro];
+          const double ddy = (double)oy - (double)ref[2 * ro + 1];
+          if constexpr (CYC) ddx = fmin(fabs(ddx), (double)a.lv.cols[0] - fabs(ddx));
           if (lost || !(ddx * ddx + ddy * ddy <= a.fb_max2)) status[o] = 0;
         }
       }
@@ -383,6 +455,9 @@ bool lk_sizes_ok(int64_t nimg, int64_t rows, int64_t cols, int64_t levels) {
   return nimg >= 0 && nimg <= 65535 && rows >= 1 && cols >= 1 && rows <= 16384 && cols <= 16384 && levels >= 1 &&
          levels <= kLkMaxLevels && nimg * rows * cols < ((int64_t)1 << 40);
 }
+
+// cyclic columns: every level in use is one period, level l has exactly cols >> l columns
+bool lk_cyclic_cols_ok(int64_t cols, int64_t levels) { return cols % ((int64_t)1 << (levels - 1)) == 0; }
 
 // the levels of a frame store's images as the kernels' table
 LkLevels lk_store_levels(const sosvo_lk_images& im) {
@@ -399,11 +474,15 @@ LkLevels lk_store_levels(const sosvo_lk_images& im) {
 }
 
 // the levels 1 .. levels - 1 of all nimg images of the table, each from the one below
-int32_t lk_build_levels(sosvo_ctx* ctx, const LkLevels& t, int nimg, int levels, const int32_t* row_range) {
+int32_t lk_build_levels(sosvo_ctx* ctx, const LkLevels& t, int nimg, int levels, const int32_t* row_range, bool cyclic = false) {
   for (int l = 0; l + 1 < levels; ++l) {
     const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), nimg);
-    SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                 const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
+    if (cyclic)
+      SOSVO_LAUNCH(ctx, lk_pyr_down_cyclic_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                   const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
+    else
+      SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                   const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
     SOSVO_LAUNCH_CHECK(ctx);
   }
   return SOSVO_OK;
@@ -412,28 +491,33 @@ int32_t lk_build_levels(sosvo_ctx* ctx, const LkLevels& t, int nimg, int levels,
 // the forward launch and, with `back`, the backward one (a: everything but initial_flow's reset and fb_max2, set here)
 int32_t lk_launch(sosvo_ctx* ctx, LkArgs a, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int nprob,
                   const float* prev_pts, const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err,
-                  float* back, double fb_max) {
+                  float* back, double fb_max, bool cyclic = false) {
   a.fb_max2 = -1.0;
   const bool small = a.half <= 5;
   const int kpw = small ? 4 : 1;
   // waves per problem: enough for the chip at a few problems, several rounds per wave at thousands
   const dim3 grid(nprob, min(cdiv(a.cap, kpw), nprob >= 4096 ? 16 : 64));
-  if (small)
-    SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
-                 status, err, (const float*)nullptr, store_pt);
-  else
-    SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, prev_img, next_img, prev_pts, n, next_pts,
-                 status, err, (const float*)nullptr, store_pt);
+  // (the profile labels a launch with its instantiation, as SOSVO_LAUNCH does)
+  auto launch = [&](auto kernel, const char* name, const int32_t* from, const int32_t* to, const float* start, float* out, float* e,
+                    const float* ref) {
+    SOSVO_PROFILE(ctx, name);
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, ctx->stream, a, row_range, from, to, start, n, out, status, e, ref, store_pt);
+  };
+  auto pass = [&](const int32_t* from, const int32_t* to, const float* start, float* out, float* e, const float* ref) {
+    if (cyclic) {
+      if (small) launch(lk_track_kernel<16, true>, "(lk_track_kernel<16, true>)", from, to, start, out, e, ref);
+      else launch(lk_track_kernel<64, true>, "(lk_track_kernel<64, true>)", from, to, start, out, e, ref);
+    } else {
+      if (small) launch(lk_track_kernel<16>, "lk_track_kernel<16>", from, to, start, out, e, ref);
+      else launch(lk_track_kernel<64>, "lk_track_kernel<64>", from, to, start, out, e, ref);
+    }
+  };
+  pass(prev_img, next_img, prev_pts, next_pts, err, nullptr);
   SOSVO_LAUNCH_CHECK(ctx);
   if (back) {  // the forward results tracked back: images swapped, no initial guess
     a.initial_flow = 0;
     a.fb_max2 = fb_max * fb_max;
-    if (small)
-      SOSVO_LAUNCH(ctx, lk_track_kernel<16>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
-                   (float*)nullptr, prev_pts, store_pt);
-    else
-      SOSVO_LAUNCH(ctx, lk_track_kernel<64>, grid, dim3(64), 0, ctx->stream, a, row_range, next_img, prev_img, next_pts, n, back, status,
-                   (float*)nullptr, prev_pts, store_pt);
+    pass(next_img, prev_img, next_pts, back, nullptr, prev_pts);
     SOSVO_LAUNCH_CHECK(ctx);
   }
   return SOSVO_OK;
@@ -543,11 +627,12 @@ bool sosvo_lk_options_ok(const sosvo_lk_options& o) {
 // the store IS the front end's buffer (a pair batch, frame i in slot i) and nothing is copied.  Then the levels in use, each
 // from the one below inside the store.  The table travels in kernel arguments, kSosvoSlotArgFrames frames per launch.
 int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
-                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame) {
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic) {
   SOSVO_REQUIRE(ctx, im.level[0] && im.level[1] && im.level[2] && im.level[3], "null pointer");
   SOSVO_REQUIRE(ctx, lk_sizes_ok(2 * (int64_t)im.slots, im.rows, im.cols, levels), "sizes out of range (2 * slots <= 65535, levels 1..4)");
   const LkLevels t = lk_store_levels(im);
-  if (!gray) return lk_build_levels(ctx, t, 2 * im.slots, levels, row_range);
+  SOSVO_REQUIRE(ctx, !cyclic || lk_cyclic_cols_ok(im.cols, levels), "cyclic columns need cols to be a multiple of 2^(levels - 1)");
+  if (!gray) return lk_build_levels(ctx, t, 2 * im.slots, levels, row_range, cyclic);
   for (int f0 = 0; f0 < nframes; f0 += kSosvoSlotArgFrames) {
     const int nf = nframes - f0 < kSosvoSlotArgFrames ? nframes - f0 : kSosvoSlotArgFrames;
     sosvo_slot_table tab;
@@ -559,8 +644,12 @@ int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t 
     SOSVO_LAUNCH_CHECK(ctx);
     for (int l = 0; l + 1 < levels; ++l) {
       const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), 2 * nf);
-      SOSVO_LAUNCH(ctx, lk_pyr_down_slots_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                   im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
+      if (cyclic)
+        SOSVO_LAUNCH(ctx, lk_pyr_down_slots_cyclic_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l],
+                     t.cols[l], im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
+      else
+        SOSVO_LAUNCH(ctx, lk_pyr_down_slots_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
+                     im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
       SOSVO_LAUNCH_CHECK(ctx);
     }
   }
@@ -572,13 +661,16 @@ int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t 
 // sosvo_track_lk's, [nprob, cap, ...]; back: its buffer, used when o.fb_max > 0.
 int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,
                               const int32_t* from_img, const int32_t* to_img, int32_t nprob, int32_t cap, const float* pts,
-                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back) {
+                              const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back,
+                              bool cyclic) {
   SOSVO_REQUIRE(ctx, im.level[0] && im.level[1] && im.level[2] && im.level[3] && from_img && to_img && pts && store_pt && n &&
                          next_pts && status && err && back,
                 "null pointer");
   SOSVO_REQUIRE(ctx, sosvo_lk_options_ok(o), "LK settings out of range (sosvo_set_lk_options)");
   SOSVO_REQUIRE(ctx, lk_sizes_ok(2 * (int64_t)im.slots, im.rows, im.cols, o.levels), "sizes out of range (2 * slots <= 65535)");
   SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535 && cap > 0, "nprob / cap out of range");
+  SOSVO_REQUIRE(ctx, !cyclic || (lk_cyclic_cols_ok(im.cols, o.levels) && (im.cols >> (o.levels - 1)) >= 2 * o.half + 3),
+                "cyclic columns need cols % 2^(levels - 1) == 0 and 2 half + 3 columns on the top level");
   if (nprob == 0) return SOSVO_OK;
   LkArgs a;
   a.lv = lk_store_levels(im);
@@ -592,7 +684,7 @@ int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const s
   a.eps2 = o.eps * o.eps;
   a.min_eig = o.min_eig;
   return lk_launch(ctx, a, row_range, from_img, to_img, nprob, pts, store_pt, n, next_pts, status, err, o.fb_max > 0.0 ? back : nullptr,
-                   o.fb_max);
+                   o.fb_max, cyclic);
 }
 
 extern "C" {
@@ -617,6 +709,20 @@ int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, in
   return lk_build_levels(ctx, t, nimg, levels, row_range);
 }
 
+int32_t sosvo_gray_pyramid_cyclic(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
+                                  const int32_t* row_range, uint8_t* pyr) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray, "null pointer");
+  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
+  SOSVO_REQUIRE(ctx, lk_cyclic_cols_ok(cols, levels), "cyclic columns need cols to be a multiple of 2^(levels - 1)");
+  SOSVO_REQUIRE(ctx, pyr || levels == 1, "null pointer");
+  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
+  if (nimg == 0) return SOSVO_OK;
+  LkLevels t;
+  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
+  return lk_build_levels(ctx, t, nimg, levels, row_range, true);
+}
+
 int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
                        int32_t levels, const int32_t* row_range, const int32_t* prev_img, const int32_t* next_img, int32_t nprob,
                        int32_t cap, const float* prev_pts, const int32_t* n, int32_t half, int32_t max_iter, double eps,
@@ -631,7 +737,11 @@ int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, 
   SOSVO_REQUIRE(ctx, half >= 2 && half <= kLkMaxHalf, "half out of range (2..10)");
   SOSVO_REQUIRE(ctx, max_iter >= 1 && max_iter <= 30, "max_iter out of range (1..30)");
   SOSVO_REQUIRE(ctx, eps >= 0.0 && min_eig >= 0.0, "eps / min_eig must not be negative or NaN");
-  SOSVO_REQUIRE(ctx, (flags & ~SOSVO_LK_INITIAL_FLOW) == 0, "unknown flag");
+  SOSVO_REQUIRE(ctx, (flags & ~(SOSVO_LK_INITIAL_FLOW | SOSVO_LK_CYCLIC_COLUMNS)) == 0, "unknown flag");
+  const bool cyclic = (flags & SOSVO_LK_CYCLIC_COLUMNS) != 0;
+  SOSVO_REQUIRE(ctx, !cyclic || lk_cyclic_cols_ok(cols, levels), "cyclic columns need cols to be a multiple of 2^(levels - 1)");
+  SOSVO_REQUIRE(ctx, !cyclic || (cols >> (levels - 1)) >= 2 * half + 3,
+                "cyclic columns need 2 half + 3 columns on the top level (the template fits one period)");
   SOSVO_REQUIRE(ctx, back == nullptr || fb_max > 0.0, "fb_max must be positive with a back buffer");
   if (nprob == 0 || nimg == 0) return SOSVO_OK;
   LkArgs a;
@@ -644,7 +754,7 @@ int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, 
   a.initial_flow = (flags & SOSVO_LK_INITIAL_FLOW) ? 1 : 0;
   a.eps2 = eps * eps;
   a.min_eig = min_eig;
-  return lk_launch(ctx, a, row_range, prev_img, next_img, nprob, prev_pts, nullptr, n, next_pts, status, err, back, fb_max);
+  return lk_launch(ctx, a, row_range, prev_img, next_img, nprob, prev_pts, nullptr, n, next_pts, status, err, back, fb_max, cyclic);
 }
 
 int32_t sosvo_refine_stereo_lk(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,

@@ -119,14 +119,18 @@ __device__ __forceinline__ uint32_t ratio_filter(uint32_t k1, uint32_t k2, uint3
 
 // (q_pos ... max_distance are read by the GATED form only; n_forward by the GATED and the RATIO forms; ratio and rivals by
 // the RATIO form, whose K is 1: one key per query in each of keys and rivals)
-template <int QT, int K, bool GATED, bool DV, bool RATIO = false>
+// CYC (match_hamming_gated_cyclic_mfma_kernel<QT>, sosvo_match_hamming_gated_cyclic): the u side of the
+// gate is cyclic with period W -- d = fabs(u_t - u_q) passes iff d <= max_du or d >= wrap_du, wrap_du = W - max_du made once
+// on the host: one more double comparison and an OR beside the existing one, still nothing that depends on the accumulators.
+template <int QT, int K, bool GATED, bool DV, bool RATIO = false, bool CYC = false>
 __device__ __forceinline__ void match_hamming_mfma_body(
     const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
     const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
     const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
     double min_dv, double max_du, uint32_t max_distance, uint32_t ratio, uint32_t* __restrict__ keys,
-    uint32_t* __restrict__ rivals) {
+    uint32_t* __restrict__ rivals, double wrap_du = 0.0) {
   static_assert(!GATED || K == 1, "the gated search stores one key per query");
+  static_assert(!CYC || (GATED && !RATIO), "the cyclic gate is a form of the gated search");
   static_assert(!RATIO || K == 1, "the ratio form stores one key per query in keys and one in rivals");
   constexpr bool TWO = K == 2 || RATIO;  // track the runner-up
   SOSVO_LATENCY_BOUND_PRIO();
@@ -271,7 +275,13 @@ __device__ __forceinline__ void match_hamming_mfma_body(
           for (int r = 0; r < 4; ++r) {
             e[r] = acc[t][4 * g + r];
             if constexpr (GATED) {
-              bool pass = fabs(ur[r] - qu[t]) <= max_du;
+              bool pass;
+              if constexpr (CYC) {
+                const double d = fabs(ur[r] - qu[t]);
+                pass = d <= max_du || d >= wrap_du;
+              } else {
+                pass = fabs(ur[r] - qu[t]) <= max_du;
+              }
               if (DV) pass = pass && (vr[r] - qv[t] >= min_dv);
               e[r] = pass ? e[r] : kMmaInvalid;
             }
@@ -353,6 +363,17 @@ __global__ __launch_bounds__(kThreads) void match_hamming_gated_mfma_kernel(
     double min_dv, double max_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
   match_hamming_mfma_body<QT, 1, true, DV>(q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, n_forward, q_stride, t_stride,
                                            nsplit, min_dv, max_du, max_distance, 0u, keys, nullptr);
+}
+
+// (the frame-to-frame form only: no v side)
+template <int QT>
+__global__ __launch_bounds__(kThreads) void match_hamming_gated_cyclic_mfma_kernel(
+    const uint4* __restrict__ q_desc, const uint4* __restrict__ t_desc, const float2* __restrict__ q_pos,
+    const float2* __restrict__ t_pos, const int32_t* __restrict__ nq, const int32_t* __restrict__ nt,
+    const int32_t* __restrict__ q_slot, const int32_t* __restrict__ t_slot, int n_forward, int q_stride, int t_stride, int nsplit,
+    double max_du, double wrap_du, uint32_t max_distance, uint32_t* __restrict__ keys) {
+  match_hamming_mfma_body<QT, 1, true, false, false, true>(q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, n_forward, q_stride,
+                                                           t_stride, nsplit, -1.0, max_du, max_distance, 0u, keys, nullptr, wrap_du);
 }
 
 template <int QT, bool GATED, bool DV>
@@ -790,6 +811,44 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
     if (dv) launch(match_hamming_gated_mfma_kernel<1, true>, "(match_hamming_gated_mfma_kernel<1, true>)");
     else launch(match_hamming_gated_mfma_kernel<1, false>, "(match_hamming_gated_mfma_kernel<1, false>)");
   }
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_match_hamming_gated_cyclic(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
+                                         const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
+                                         const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride,
+                                         int32_t t_stride, double max_du, double period, int32_t max_distance, uint32_t* keys) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, q_desc && t_desc && q_pos && t_pos && nq && nt && keys, "null pointer");
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
+  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");
+  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");
+  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range");
+  SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)");
+  SOSVO_REQUIRE(ctx, max_du == max_du, "max_du must not be NaN");
+  SOSVO_REQUIRE(ctx, period >= 1.0 && period <= 16384.0 && period == floor(period), "the period must be a positive integer up to 16384");
+  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0,
+                "descriptor arrays must be 16-byte aligned");
+  SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned");
+  if (nprob == 0) return SOSVO_OK;
+  const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
+  const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
+  const float2* qp = reinterpret_cast<const float2*>(q_pos);
+  const float2* tp = reinterpret_cast<const float2*>(t_pos);
+  MmaPlan plan;
+  if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan)) return rc;
+  // the switch is sv_pixel_gate's: the gate is on for max_du > 0; off, both sides pass everything
+  const double du = max_du > 0 ? max_du : HUGE_VAL;
+  const double wrap = max_du > 0 ? period - max_du : HUGE_VAL;
+  const uint32_t cap = (uint32_t)max_distance;
+  auto launch = [&](auto kernel, const char* name) {
+    SOSVO_PROFILE(ctx, name);
+    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                       q_stride, t_stride, plan.nsplit, du, wrap, cap, keys);
+  };
+  if (plan.qt == 2) launch(match_hamming_gated_cyclic_mfma_kernel<2>, "(match_hamming_gated_cyclic_mfma_kernel<2>)");
+  else launch(match_hamming_gated_cyclic_mfma_kernel<1>, "(match_hamming_gated_cyclic_mfma_kernel<1>)");
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }

@@ -100,8 +100,23 @@ constexpr const char* kBadLkFlags =
 // ---- sub-pixel static stereo (SOSVO_FLAG_LK_STEREO): sosvo_refine_stereo_lk between the sort and the stereo assemble, with the
 // context's settings.  Its status flags are carved only when the switch is set, after everything else.
 bool lk_stereo(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_LK_STEREO) != 0; }
-// what every omni entry point asks of cfg->ransac_flags (nullptr: fine)
-const char* omni_flags_msg(int32_t flags) { return !ratio_flags_ok(flags) ? kBadRatioFlags : lk_flags_ok(flags) ? nullptr : kBadLkFlags; }
+// ---- cyclic panorama columns (SOSVO_FLAG_CYCLIC_F2F): the frame-to-frame |du| gate is cyclic in the
+// assemble and, under SOSVO_FLAG_GATED_F2F, inside the matcher; under SOSVO_FLAG_LK_F2F the store's pyramids and the tracker
+// are cyclic too, which needs every level the store may hold to be one period (cols % 2^(SOSVO_LK_MAX_LEVELS - 1) == 0: the
+// workspace functions take no context).  The ratio form of the gated matcher has no cyclic instantiation.
+bool cyclic_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_CYCLIC_F2F) != 0; }
+constexpr const char* kBadCyclicCols = "SOSVO_FLAG_CYCLIC_F2F with SOSVO_FLAG_LK_F2F needs cols % 8 == 0 (every level of the store is one period)";
+constexpr const char* kBadCyclicRatio =
+    "SOSVO_FLAG_CYCLIC_F2F: the ratio form of the gated frame-to-frame matcher (SOSVO_FLAG_GATED_F2F | SOSVO_FLAG_RATIO_F2F) has no cyclic gate";
+// what every omni entry point asks of cfg->ransac_flags and the shape (nullptr: fine)
+const char* omni_flags_msg(const sosvo_batch_cfg& c) {
+  const int32_t flags = c.ransac_flags;
+  if (!ratio_flags_ok(flags)) return kBadRatioFlags;
+  if (!lk_flags_ok(flags)) return kBadLkFlags;
+  if (cyclic_f2f(c) && lk_f2f(c) && c.cols % (1 << (SOSVO_LK_MAX_LEVELS - 1)) != 0) return kBadCyclicCols;
+  if (cyclic_f2f(c) && (flags & SOSVO_FLAG_GATED_F2F) && (flags & SOSVO_FLAG_RATIO_F2F)) return kBadCyclicRatio;
+  return nullptr;
+}
 // the gray rows the front end computes are those of sosvo_gray_rows_needed (GFT with the fused median), else all rows
 bool gray_rows_known(const sosvo_batch_cfg& c) {
   return c.detector == SOSVO_DETECTOR_GFT && (c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11);
@@ -123,6 +138,7 @@ struct Gate {
   bool on;
   double min_dv, max_du;
   int32_t max_distance;
+  double period = 0.0;  // > 0: the u side is cyclic with this period (sosvo_match_hamming_gated_cyclic; no v side, no ratio form)
 };
 int32_t gate_cap(int32_t flags) { return SOSVO_GATED_MAX_DIST_OF(flags) ? SOSVO_GATED_MAX_DIST_OF(flags) : 256; }
 Gate gate_stereo(const sosvo_batch_cfg& c, const sosvo_rig& rig) {  // stereo_assemble_frame's sv_pixel_gate
@@ -645,7 +661,7 @@ extern "C" {
 
 size_t sosvo_frame_pair_batch_workspace(const sosvo_batch_cfg* cfg) {
   if (!cfg || cfg->n_pairs <= 0 || cfg->rows <= 0 || cfg->cols <= 0 || cfg->nmask <= 0 || cfg->kp_cap <= 0 ||
-      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap) || omni_flags_msg(cfg->ransac_flags) ||
+      cfg->frame_cap <= 0 || !detector_ok(cfg->detector, cfg->kp_cap) || omni_flags_msg(*cfg) ||
       (lk_f2f(*cfg) && cfg->n_pairs > 8192))  // (the store's images: 2 * slots <= 65535)
     return 0;
   // (laxer than the call itself, which refuses nmask > 32, kp_cap > 4096 and frame_cap > 16384: such a shape gets a size
@@ -679,6 +695,9 @@ static int32_t match_1nn(sosvo_ctx* ctx, const Gate& g, const Ratio& r, const ui
                                      nprob, n_forward, stride, stride, g.min_dv, g.max_du, g.on ? g.max_distance : 256, r.r64,
                                      keys, r.rivals);
   if (!g.on) return sosvo_match_hamming(ctx, q_desc, t_desc, nq, nt, q_slot, t_slot, nprob, stride, stride, 1, keys);
+  if (g.period > 0.0)
+    return sosvo_match_hamming_gated_cyclic(ctx, q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, nprob, n_forward, stride,
+                                            stride, g.max_du, g.period, g.max_distance, keys);
   return sosvo_match_hamming_gated(ctx, q_desc, t_desc, q_pos, t_pos, nq, nt, q_slot, t_slot, nprob, n_forward, stride, stride,
                                    g.min_dv, g.max_du, g.max_distance, keys);
 }
@@ -729,7 +748,7 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   // whose store `o` belongs to, o shifted by first_slot)
   if (images && images->img.level[0])
     STAGE(sosvo_lk_images_fill(ctx, images->img, ctx->lk.levels, images->img_rows, images->img_in_place ? nullptr : t.gray, F,
-                               first_slot, slot_of_frame));
+                               first_slot, slot_of_frame, cyclic_f2f(*cfg)));
   // the stages ImageFrontEnd.run_features calls for the detector (frontend.py), with the same arguments
   if (det == SOSVO_DETECTOR_ORB) {
     // the mask pyramid is a model constant, rebuilt here on every call (as gray_rows above) to keep the entry point free of
@@ -786,20 +805,27 @@ static int32_t correspondences_matched(sosvo_ctx* ctx, const sosvo_rig* rig, con
                                        const TrackTmp& b) {
   const int Fc = cfg->frame_cap, Cc = 2 * Fc;
   int32_t rc;
-  const bool mutual = cross_f2f(*cfg);
+  const bool mutual = cross_f2f(*cfg), cyclic = cyclic_f2f(*cfg);
   const Gate gate = gate_f2f(*cfg, *rig);
+  Gate gate_bot = gate;
+  if (cyclic && gate.on) {  // the view's period; the entry point refuses a period that is no positive integer
+    SOSVO_REQUIRE(ctx, rig->pano_top[0] >= 1.0 && rig->pano_bot[0] >= 1.0, "SOSVO_FLAG_CYCLIC_F2F: the period (pano_top[0], pano_bot[0]) must be positive");
+    gate_bot.period = rig->pano_bot[0];
+  }
+  Gate gate_top = gate_bot;
+  gate_top.period = cyclic && gate.on ? rig->pano_top[0] : 0.0;
   if (mutual) {  // (one pair of tables serves both views)
     STAGE(mutual_tabs(ctx, b.cur_frame, b.ref_frame, B, b.mutual));
-    STAGE(match_mutual(ctx, gate, b.ratio, s.d_top, s.m_top, s.M, B, Fc, b.mutual, b.k_top));
+    STAGE(match_mutual(ctx, gate_top, b.ratio, s.d_top, s.m_top, s.M, B, Fc, b.mutual, b.k_top));
   } else
-    STAGE(match_1nn(ctx, gate, b.ratio, s.d_top, s.d_top, s.m_top, s.m_top, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_top));
+    STAGE(match_1nn(ctx, gate_top, b.ratio, s.d_top, s.d_top, s.m_top, s.m_top, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_top));
   STAGE(sosvo_sort_matches(ctx, b.k_top, s.M, b.cur_frame, B, Fc, b.o_top));
   if (mutual)
-    STAGE(match_mutual(ctx, gate, b.ratio, s.d_bot, s.m_bot, s.M, B, Fc, b.mutual, b.k_bot));
+    STAGE(match_mutual(ctx, gate_bot, b.ratio, s.d_bot, s.m_bot, s.M, B, Fc, b.mutual, b.k_bot));
   else
-    STAGE(match_1nn(ctx, gate, b.ratio, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
+    STAGE(match_1nn(ctx, gate_bot, b.ratio, s.d_bot, s.d_bot, s.m_bot, s.m_bot, s.M, s.M, b.cur_frame, b.ref_frame, B, B, Fc, b.k_bot));
   STAGE(sosvo_sort_matches(ctx, b.k_bot, s.M, b.cur_frame, B, Fc, b.o_bot));
-  return sosvo_f2f_assemble(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top, b.o_top,
+  return (cyclic ? sosvo_f2f_assemble_cyclic : sosvo_f2f_assemble)(ctx, rig, s.m_top, s.m_bot, s.X, s.b_top, s.b_bot, s.M, Fc, b.ref_frame, b.cur_frame, b.k_top, b.o_top,
                             b.k_bot, b.o_bot, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top);
 }
 
@@ -815,8 +841,10 @@ static int32_t correspondences_tracked(sosvo_ctx* ctx, const sosvo_rig* rig, con
   SOSVO_LAUNCH(ctx, lk_setup_kernel, dim3(cdiv(2 * B, 256)), dim3(256), 0, ctx->stream, B, im.slots, Fc, b.ref_frame, b.cur_frame, s.M,
                (int64_t)((s.m_bot - s.m_top) / 2), k.from, k.to, k.n, k.pt);
   SOSVO_LAUNCH_CHECK(ctx);
-  STAGE(sosvo_lk_images_track(ctx, im, ctx->lk, img_rows, k.from, k.to, 2 * B, Fc, s.m_top, k.pt, k.n, k.next, k.status, k.err, k.back));
-  return sosvo_f2f_assemble_tracked(ctx, rig, s.m_top, s.m_bot, s.X, s.M, Fc, b.ref_frame, k.next, k.next + (size_t)B * Fc * 2, k.status,
+  const bool cyclic = cyclic_f2f(*cfg);
+  STAGE(sosvo_lk_images_track(ctx, im, ctx->lk, img_rows, k.from, k.to, 2 * B, Fc, s.m_top, k.pt, k.n, k.next, k.status, k.err, k.back,
+                              cyclic));
+  return (cyclic ? sosvo_f2f_assemble_tracked_cyclic : sosvo_f2f_assemble_tracked)(ctx, rig, s.m_top, s.m_bot, s.X, s.M, Fc, b.ref_frame, k.next, k.next + (size_t)B * Fc * 2, k.status,
                                     k.status + (size_t)B * Fc, B, Cc, b.f, b.p, b.cam, b.cq, b.ct, b.cn, b.cn_top);
 }
 
@@ -866,7 +894,7 @@ static int32_t run_frame_pairs(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo
   SOSVO_REQUIRE(ctx, cfg->nmask >= 1 && cfg->nmask <= 32 && cfg->kp_cap > 0 && cfg->kp_cap <= 4096, "nmask / kp_cap out of range");
   SOSVO_REQUIRE(ctx, cfg->frame_cap > 0 && cfg->frame_cap <= 16384, "frame_cap out of range (max 16384)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
-  if (omni_flags_msg(cfg->ransac_flags)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(cfg->ransac_flags));
+  if (omni_flags_msg(*cfg)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(*cfg));
   SOSVO_REQUIRE(ctx, !lk_f2f(*cfg) || sosvo_lk_options_ok(ctx->lk), "LK settings out of range (sosvo_set_lk_options)");
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const int B = cfg->n_pairs, F = 2 * B;
@@ -919,7 +947,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
   SOSVO_REQUIRE(ctx, n_streams >= 1 && n_streams <= kSosvoMaxSubStreams, "n_streams out of range (1..4)");
   SOSVO_REQUIRE(ctx, cfg->n_pairs >= n_streams && cfg->n_pairs <= 8192, "n_pairs out of range (n_streams..8192)");
   SOSVO_REQUIRE(ctx, detector_ok(cfg->detector, cfg->kp_cap), "unknown detector, or ORB with kp_cap > 2048");
-  if (omni_flags_msg(cfg->ransac_flags)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(cfg->ransac_flags));
+  if (omni_flags_msg(*cfg)) return sosvo_fail(ctx, SOSVO_ERR_ARG, __func__, omni_flags_msg(*cfg));
   SOSVO_REQUIRE(ctx, ((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
   const size_t need = sosvo_frame_pair_batch_streams_workspace(cfg, n_streams);
   SOSVO_REQUIRE(ctx, need > 0 && workspace_bytes >= need, "workspace too small (see sosvo_frame_pair_batch_streams_workspace)");
@@ -1166,10 +1194,10 @@ struct OmniSeq {
   using Frames = OmniFrames;
   static constexpr const char* kTooSmall = "workspace too small (see sosvo_sequence_workspace)";
   static bool shape_ok(const Cfg* c, int32_t window, int32_t slots) {
-    return c && c->nmask >= 1 && c->nmask <= 32 && !omni_flags_msg(c->ransac_flags) && seq_shape_ok(c, c->detector, window, slots) &&
+    return c && c->nmask >= 1 && c->nmask <= 32 && !omni_flags_msg(*c) && seq_shape_ok(c, c->detector, window, slots) &&
            (!lk_f2f(*c) || slots <= 32767);  // (the store's images: 2 * slots <= 65535)
   }
-  static const char* flags_msg(const Cfg* c) { return omni_flags_msg(c->ransac_flags); }
+  static const char* flags_msg(const Cfg* c) { return omni_flags_msg(*c); }
   static constexpr const char* kBadFrames = SOSVO_TABLE_FRAME_MSG;
   static bool frames_ok(const Cfg* c) { return sosvo_table_frame_ok(c->H, c->W); }  // the front end reads them through the table
   static Ws carve(const Cfg& c, size_t window, size_t slots, void* base) { return ::carve(c, window, slots, base); }

@@ -50,10 +50,11 @@ def make_rig(pano_top, pano_bot, F_top, F_bot, min_range, max_range, stereo_min_
 
 class GrayPyramid(object):
     """What Context.gray_pyramid returns and Context.track_lk reads: `gray` [NI,rows,cols] u8 (level 0, the caller's tensor),
-    `upper` (the levels 1 .. levels - 1 back to back, flat u8), `levels`, and the `row_range` the levels were built under."""
+    `upper` (the levels 1 .. levels - 1 back to back, flat u8), `levels`, the `row_range` the levels were built under, and
+    `cyclic`: built by gray_pyramid_cyclic, the columns are one period."""
 
-    def __init__(self, gray, upper, levels, row_range):
-        self.gray, self.upper, self.levels, self.row_range = gray, upper, levels, row_range
+    def __init__(self, gray, upper, levels, row_range, cyclic=False):
+        self.gray, self.upper, self.levels, self.row_range, self.cyclic = gray, upper, levels, row_range, bool(cyclic)
 
     def level(self, l):
         """Level l as a [NI, rows_l, cols_l] view."""
@@ -400,6 +401,15 @@ class Context(object):
         """sosvo_gray_pyramid: the levels 1 .. levels - 1 of gray [NI,rows,cols] u8 (level 0 is `gray` itself, not copied) ->
         a GrayPyramid, what track_lk reads.  row_range (int32 [2,2] on the device, view-major) as for refine_subpix: only the
         rows a level inherits from it are computed.  out: a GrayPyramid of the same sizes to refill (no allocation)."""
+        return self._gray_pyramid(False, gray, levels, row_range, out)
+
+    def gray_pyramid_cyclic(self, gray, levels, row_range=None, out=None):
+        """sosvo_gray_pyramid_cyclic: gray_pyramid for the panoramas of a full circle -- column `cols` is column 0 again, the
+        column index wraps where gray_pyramid's clamps; cols must be a multiple of 2^(levels - 1).  -> a GrayPyramid with
+        cyclic = True, which track_lk then tracks around the circle."""
+        return self._gray_pyramid(True, gray, levels, row_range, out)
+
+    def _gray_pyramid(self, cyclic, gray, levels, row_range, out):
         _check(gray, torch.uint8, "gray", ndim=3)
         NI, rows, cols = gray.shape
         nbytes = _lib.gray_pyramid_bytes(NI, rows, cols, levels)     # (SosvoError for sizes / levels out of range)
@@ -407,18 +417,19 @@ class Context(object):
             _check(row_range, torch.int32, "row_range", (2, 2))
         upper = out.upper if out is not None else torch.zeros((nbytes,), dtype=torch.uint8, device=gray.device)
         _check(upper, torch.uint8, "out.upper", (nbytes,))
-        self._call(self._lib.sosvo_gray_pyramid, _ptr(gray), NI, rows, cols, int(levels), _ptr(row_range),
-                   _ptr(upper) if nbytes else NULL)
-        return GrayPyramid(gray, upper, int(levels), row_range)
+        self._call(self._lib.sosvo_gray_pyramid_cyclic if cyclic else self._lib.sosvo_gray_pyramid, _ptr(gray), NI, rows, cols,
+                   int(levels), _ptr(row_range), _ptr(upper) if nbytes else NULL)
+        return GrayPyramid(gray, upper, int(levels), row_range, cyclic)
 
     def track_lk(self, pyr, prev_img, next_img, prev_pts, n, half=10, max_iter=30, eps=0.01, min_eig=1e-4, next_pts=None,
-                 fb_max=None, out=None):
+                 fb_max=None, out=None, cyclic=None):
         """sosvo_track_lk: problem p tracks prev_pts[p, :n[p]] ([NP,cap,2] f32) from image prev_img[p] to image next_img[p]
         ([NP] i32 on the device) of the GrayPyramid `pyr` -> (next_pts [NP,cap,2] f32, status [NP,cap] u8, err [NP,cap] f32).
         next_pts: given = the starting guesses (SOSVO_LK_INITIAL_FLOW), overwritten with the results.  fb_max: None, or the
         forward-backward check's bound in pixels; then the 4-tuple (next_pts, status, err, back).  out: buffers to reuse, in
         the order of the result (out[0] is not read when next_pts is given); rows at and beyond n[p] of every output are
-        untouched."""
+        untouched.  cyclic: SOSVO_LK_CYCLIC_COLUMNS -- x is a position on the circle, results in [0, cols); None: as `pyr`
+        was built (gray_pyramid_cyclic: True)."""
         if not isinstance(pyr, GrayPyramid):
             raise SosvoError("pyr: expected the result of gray_pyramid")
         NI, rows, cols = pyr.gray.shape
@@ -427,9 +438,9 @@ class Context(object):
         _check(prev_img, torch.int32, "prev_img", (NP,))
         _check(next_img, torch.int32, "next_img", (NP,))
         _check(n, torch.int32, "n", (NP,))
-        flags = 0
+        flags = _lib.LK_CYCLIC_COLUMNS if (pyr.cyclic if cyclic is None else cyclic) else 0
         if next_pts is not None:
-            flags = _lib.LK_INITIAL_FLOW
+            flags |= _lib.LK_INITIAL_FLOW
         else:
             next_pts = out[0] if out is not None else torch.zeros_like(prev_pts)
         _check(next_pts, torch.float32, "next_pts", (NP, cap, 2))
@@ -481,9 +492,10 @@ class Context(object):
                    ctypes.cast(ctypes.pointer(opt), c_p), _ptr(status))
         return kp_bot, status
 
-    def f2f_assemble_tracked(self, rig, frames, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, out=None):
+    def f2f_assemble_tracked(self, rig, frames, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, out=None, cyclic=False):
         """sosvo_f2f_assemble_tracked: frames = dict from stereo_assemble (m_top, m_bot, X, M); ref_frame [NP] i32; trk_*
-        [NP, frame_cap, 2] f32 and st_* [NP, frame_cap] u8 from track_lk -> the dict of f2f_assemble (q = -1)."""
+        [NP, frame_cap, 2] f32 and st_* [NP, frame_cap] u8 from track_lk -> the dict of f2f_assemble (q = -1).  cyclic:
+        sosvo_f2f_assemble_tracked_cyclic, the |du| gate around the circle (period = the rig's pano_top[0] / pano_bot[0])."""
         F, frame_cap = frames["m_top"].shape[0], frames["m_top"].shape[1]
         NP = ref_frame.shape[0]
         _check(ref_frame, torch.int32, "ref_frame", (NP,))
@@ -510,7 +522,7 @@ class Context(object):
             _check(out[k], torch.int32, k, (NP, corr_cap))
         _check(out["n"], torch.int32, "n", (NP,))
         _check(out["n_top"], torch.int32, "n_top", (NP,))
-        self._call(self._lib.sosvo_f2f_assemble_tracked, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
+        self._call(self._lib.sosvo_f2f_assemble_tracked_cyclic if cyclic else self._lib.sosvo_f2f_assemble_tracked, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
                    _ptr(frames["m_bot"]), _ptr(frames["X"]), _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(trk_top),
                    _ptr(trk_bot), _ptr(st_top), _ptr(st_bot), NP, corr_cap, _ptr(out["f"]), _ptr(out["p"]), _ptr(out["cam"]),
                    _ptr(out["q"]), _ptr(out["t"]), _ptr(out["n"]), _ptr(out["n_top"]))
@@ -639,6 +651,17 @@ class Context(object):
                    float(max_du), 256 if max_distance is None else int(max_distance), _ptr(keys))
         return keys
 
+    def match_hamming_gated_cyclic(self, q_desc, t_desc, q_pos, t_pos, nq, nt, max_du, period, max_distance=None, keys=None,
+                                   q_slot=None, t_slot=None, n_forward=None):
+        """match_hamming_gated in its frame-to-frame form (no v side) with the u side around the circle of `period` columns
+        (sosvo_match_hamming_gated_cyclic): gate = d <= max_du or d >= period - max_du, d = |u_t - u_q| in double (if
+        max_du > 0).  -> keys [P, Sq, 1] u32."""
+        P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, keys, 1, (q_pos, t_pos))
+        self._call(self._lib.sosvo_match_hamming_gated_cyclic, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq),
+                   _ptr(nt), _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(max_du),
+                   float(period), 256 if max_distance is None else int(max_distance), _ptr(keys))
+        return keys
+
     def match_hamming_ratio(self, q_desc, t_desc, nq, nt, ratio_64ths, q_pos=None, t_pos=None, min_dv=-1.0, max_du=0.0,
                             max_distance=None, keys=None, rivals=None, q_slot=None, t_slot=None, n_forward=None):
         """The 1-NN search with Lowe's ratio rule fused in (sosvo_match_hamming_ratio): a forward problem's query keeps its
@@ -663,12 +686,19 @@ class Context(object):
         return keys, rivals
 
     def match_1nn(self, q_desc, t_desc, nq, nt, *, ratio_64ths=0, rivals=None, gate=None, q_pos=None, t_pos=None, keys=None,
-                  q_slot=None, t_slot=None, n_forward=None):
+                  q_slot=None, t_slot=None, n_forward=None, period=None):
         """The Python twin of match_1nn in pipeline.hip: one best-match search, ONE library call.  ratio_64ths > 0: the ratio
         form (match_hamming_ratio), plain or, with a gate, gated; else with a gate: match_hamming_gated; else
         match_hamming(k=1), which has no reversed problems and so no n_forward.  gate: None or (min_dv, max_du, max_distance)
-        on q_pos / t_pos.  -> keys [P, Sq, 1] u32."""
+        on q_pos / t_pos.  period: None, or the period of a gate whose u side is cyclic (match_hamming_gated_cyclic: the
+        frame-to-frame form, no v side, no ratio form; without a gate it is ignored, as the gate's values are).
+        -> keys [P, Sq, 1] u32."""
         where = dict(keys=keys, q_slot=q_slot, t_slot=t_slot)
+        if gate is not None and period is not None:
+            if ratio_64ths or gate[0] >= 0:
+                raise SosvoError("the cyclic gate has no ratio form and no v side")
+            return self.match_hamming_gated_cyclic(q_desc, t_desc, q_pos, t_pos, nq, nt, gate[1], period, max_distance=gate[2],
+                                                   n_forward=n_forward, **where)
         if ratio_64ths:
             g = dict(q_pos=q_pos, t_pos=t_pos, min_dv=gate[0], max_du=gate[1], max_distance=gate[2]) if gate is not None else {}
             return self.match_hamming_ratio(q_desc, t_desc, nq, nt, ratio_64ths, rivals=rivals, n_forward=n_forward, **g, **where)[0]
@@ -676,26 +706,27 @@ class Context(object):
             return self.match_hamming_gated(q_desc, t_desc, q_pos, t_pos, nq, nt, *gate, n_forward=n_forward, **where)
         return self.match_hamming(q_desc, t_desc, nq, nt, k=1, **where)
 
-    def match_1nn_slots(self, desc, pos, n, q_slot, t_slot, keys, n_forward, *, ratio_64ths=0, rivals=None, gate=None):
+    def match_1nn_slots(self, desc, pos, n, q_slot, t_slot, keys, n_forward, *, ratio_64ths=0, rivals=None, gate=None, period=None):
         """The matching step, slot form: ONE search over the problems (q_slot[p], t_slot[p]) of one set of blocks (desc, pos, n).
         Problems p >= n_forward are the role-swapped twins of the forward ones (reversed gate, no ratio rule); when there are
         any, the forward keys are filtered to the mutual matches in place.  -> the forward keys, keys[:n_forward]."""
         self.match_1nn(desc, desc, n, n, ratio_64ths=ratio_64ths, rivals=rivals, gate=gate, q_pos=pos, t_pos=pos, keys=keys,
-                       q_slot=q_slot, t_slot=t_slot, n_forward=n_forward)
+                       q_slot=q_slot, t_slot=t_slot, n_forward=n_forward, **({} if period is None else dict(period=period)))
         fwd = keys[:n_forward]
         if keys.shape[0] > n_forward:
             self.cross_check_matches(fwd, keys[n_forward:], n, n, q_slot=q_slot[:n_forward], t_slot=t_slot[:n_forward], keys_out=fwd)
         return fwd
 
     def match_1nn_two_launch(self, q_desc, t_desc, nq, nt, *, cross_check=False, keys_rev=None, ratio_64ths=0, rivals=None,
-                             gate=None, q_pos=None, t_pos=None, keys=None):
+                             gate=None, q_pos=None, t_pos=None, keys=None, period=None):
         """The matching step, two-launch form: the forward search; with cross_check a second search with roles and positions
         swapped (every problem reversed: n_forward=0, never the ratio rule) into keys_rev, then the mutual filter on keys in
         place.  -> keys."""
+        cyc = {} if period is None else dict(period=period)    # (the u side is symmetric: the swapped search takes it as well)
         keys = self.match_1nn(q_desc, t_desc, nq, nt, ratio_64ths=ratio_64ths, rivals=rivals, gate=gate, q_pos=q_pos, t_pos=t_pos,
-                              keys=keys)
+                              keys=keys, **cyc)
         if cross_check:
-            rev = self.match_1nn(t_desc, q_desc, nt, nq, gate=gate, q_pos=t_pos, t_pos=q_pos, keys=keys_rev, n_forward=0)
+            rev = self.match_1nn(t_desc, q_desc, nt, nq, gate=gate, q_pos=t_pos, t_pos=q_pos, keys=keys_rev, n_forward=0, **cyc)
             self.cross_check_matches(keys, rev, nq, nt, keys_out=keys)
         return keys
 
@@ -1225,9 +1256,10 @@ class Context(object):
         return results
 
     def f2f_assemble(self, rig, frames, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot, corr_cap,
-                     out=None):
+                     out=None, cyclic=False):
         """frames = dict from stereo_assemble; ref_frame / cur_frame [NP] i32; keys_* [NP, frame_cap, 1] u32,
-        order_* [NP, frame_cap] i32 -> dict(f, p [NP,corr_cap,3] f64, cam, q, t [NP,corr_cap] i32, n, n_top [NP])."""
+        order_* [NP, frame_cap] i32 -> dict(f, p [NP,corr_cap,3] f64, cam, q, t [NP,corr_cap] i32, n, n_top [NP]).  cyclic:
+        sosvo_f2f_assemble_cyclic, the |du| gate around the circle (period = the rig's pano_top[0] / pano_bot[0])."""
         F, frame_cap = frames["m_top"].shape[0], frames["m_top"].shape[1]
         NP = ref_frame.shape[0]
         _check(ref_frame, torch.int32, "ref_frame", (NP,))
@@ -1256,7 +1288,7 @@ class Context(object):
             _check(out[k], torch.int32, k, (NP, corr_cap))
         _check(out["n"], torch.int32, "n", (NP,))
         _check(out["n_top"], torch.int32, "n_top", (NP,))
-        self._call(self._lib.sosvo_f2f_assemble, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
+        self._call(self._lib.sosvo_f2f_assemble_cyclic if cyclic else self._lib.sosvo_f2f_assemble, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
                    _ptr(frames["m_bot"]), _ptr(frames["X"]), _ptr(frames["b_top"]), _ptr(frames["b_bot"]),
                    _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(cur_frame), _ptr(keys_top), _ptr(order_top),
                    _ptr(keys_bot), _ptr(order_bot), NP, corr_cap, _ptr(out["f"]), _ptr(out["p"]), _ptr(out["cam"]),

@@ -236,7 +236,7 @@ class FeatureMatcher(object):
                 raise ValueError("%s: expected [n, 32] uint8 descriptors, got %s" % (name, a.shape))
         return out
 
-    def _match_many(self, qs, ts, r64, q_pts=None, t_pts=None, gate=None):
+    def _match_many(self, qs, ts, r64, q_pts=None, t_pts=None, gate=None, period=None):
         """The batched best-match search of match_arrays_many / match_gated_many: the P problems padded to [P, cap, 32] (and
         their positions to [P, cap, 2] under a gate), counts, upload; the matching step (Context.match_1nn_two_launch: one
         launch, two with cross_check) and the sort; one copy back, the queries in rank order without those that have no match
@@ -253,7 +253,8 @@ class FeatureMatcher(object):
             return torch.from_numpy(h).to(ctx.device)
         dq, dt = upload(qs, nq, 32, np.uint8), upload(ts, nt, 32, np.uint8)
         nq_d, nt_d = torch.from_numpy(nq).to(ctx.device), torch.from_numpy(nt).to(ctx.device)
-        pos = dict(q_pos=upload(q_pts, nq, 2, np.float32), t_pos=upload(t_pts, nt, 2, np.float32), gate=gate) if gate else {}
+        pos = dict(q_pos=upload(q_pts, nq, 2, np.float32), t_pos=upload(t_pts, nt, 2, np.float32), gate=gate,
+                   **({} if period is None else dict(period=float(period)))) if gate else {}
         keys = ctx.match_1nn_two_launch(dq, dt, nq_d, nt_d, cross_check=self.cross_check, ratio_64ths=r64, **pos)
         order = ctx.sort_matches(keys, nq_d)
         kh, oh = keys[:, :, 0].cpu().numpy().astype(np.int64), order.cpu().numpy().astype(np.int64)
@@ -279,16 +280,19 @@ class FeatureMatcher(object):
         empty = (np.empty(0, np.int64),) * 2 + (np.empty(0, np.float32),)
         return [empty if len(q) == 0 or len(t) == 0 else m for q, t, m in zip(qs, ts, self._match_many(qs, ts, r64))]
 
-    def match_gated_many(self, items, min_dv, max_du, max_distance=None):
+    def match_gated_many(self, items, min_dv, max_du, max_distance=None, period=None):
         """[(query_descriptors, train_descriptors, query_pts, train_pts), ...] -> [(query_idx, train_idx, distance), ...] as
         match_arrays_many, each query searching among the trains that pass the pixel gate (Context.match_hamming_gated):
         |u_train - u_query| <= max_du (if max_du > 0) and v_train - v_query >= min_dv (if min_dv >= 0) on the float32
         positions *_pts [n, >= 2] (u, v), in double.  max_distance: None = no cap, else 0 .. 256.  A query without an
         admissible train within the cap has no match.  With cross_check the role-swapped search runs under the same gate.
-        One launch (two with cross_check) and one copy back for all items."""
+        One launch (two with cross_check) and one copy back for all items.  period: None, or the column count of a full-circle
+        panorama: the u side is cyclic (Context.match_hamming_gated_cyclic; min_dv must be off, and there is no ratio form)."""
         self._check_cross_check()
         self._check_gated(max_distance)
         r64 = self._check_ratio()
+        if period is not None and (r64 or min_dv >= 0):
+            raise ValueError("the cyclic gate has no ratio form and no v side")
         if any(self._is_float(q) or self._is_float(t) for q, t, _, _ in items):
             raise ValueError("gated matching is built for binary (Hamming) descriptors only, not float descriptors")
         if len(items) == 0:
@@ -301,7 +305,7 @@ class FeatureMatcher(object):
             if any(x.shape[1] < 2 for x in a):
                 raise ValueError("%s: expected [n, 2] pixel positions" % name)
             pts.append([x[:, :2] for x in a])
-        return self._match_many(qs, ts, r64, pts[0], pts[1], (min_dv, max_du, max_distance))
+        return self._match_many(qs, ts, r64, pts[0], pts[1], (min_dv, max_du, max_distance), period)
 
     def match_gated(self, query_desc, train_desc, query_pts, train_pts, min_dv, max_du, max_distance=None):
         """match() under the pixel gates -> MatchList, ascending by distance, ties in query order (see match_gated_many)."""

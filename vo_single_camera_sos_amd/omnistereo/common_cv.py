@@ -63,13 +63,15 @@ def filter_pixel_correspondences(matched_points_top, matched_points_bot, min_rec
 
 
 def calc_optical_flow_pyr_lk(prev_gray, next_gray, prev_pts, next_pts=None, win_half=10, max_level=2, max_iter=30, eps=0.01,
-                             min_eig_threshold=1e-4, ctx=None):
+                             min_eig_threshold=1e-4, ctx=None, cyclic=False):
     """cv2.calcOpticalFlowPyrLK(prevImg, nextImg, prevPts, nextPts, winSize=(2 win_half + 1,) * 2, maxLevel=max_level,
     criteria=(COUNT + EPS, max_iter, eps), minEigThreshold=min_eig_threshold), the call the reference carries commented out
     at camera_models.py:3070, with cv2's shapes and the arithmetic on the GPU (Context.gray_pyramid + Context.track_lk: the
     integer restatement of include/sosvo.h, replicated borders).  prev_gray, next_gray: [rows, cols] u8 of one size;
     prev_pts: [N, 1, 2] or [N, 2] float32; next_pts: the starting guesses (OPTFLOW_USE_INITIAL_FLOW) or None
-    -> (next_pts [N, 1, 2] float32, status [N, 1] uint8, err [N, 1] float32).  More than 4096 points go in chunks."""
+    -> (next_pts [N, 1, 2] float32, status [N, 1] uint8, err [N, 1] float32).  More than 4096 points go in chunks.
+    cyclic: the images are full-circle panoramas, column `cols` is column 0 again (SOSVO_LK_CYCLIC_COLUMNS: no cv2
+    counterpart); cols must be a multiple of 2^max_level and the top level at least 2 win_half + 3 columns wide."""
     import torch
     from .. import _lib
     from ..runtime import default_context
@@ -83,12 +85,15 @@ def calc_optical_flow_pyr_lk(prev_gray, next_gray, prev_pts, next_pts=None, win_
         raise ValueError("next_pts: one starting guess per point")
     opts = _lib.LKOptions(half=win_half, levels=max_level + 1 if isinstance(max_level, int) else max_level,
                           max_iter=max_iter, eps=eps, min_eig=min_eig_threshold)
+    if cyclic and (prev_gray.shape[1] % (1 << (opts.levels - 1)) or (prev_gray.shape[1] >> (opts.levels - 1)) < 2 * opts.half + 3):
+        raise ValueError("cyclic: a width of %d columns is no multiple of %d, or its top level is narrower than the %d-column "
+                         "template" % (prev_gray.shape[1], 1 << (opts.levels - 1), 2 * opts.half + 3))
     N = len(pts)
     out = (np.zeros((N, 1, 2), np.float32), np.zeros((N, 1), np.uint8), np.zeros((N, 1), np.float32))
     if N == 0:
         return out
     dev = c.device
-    pyr = c.gray_pyramid(torch.from_numpy(np.stack([prev_gray, next_gray])).to(dev), opts.levels)
+    pyr = (c.gray_pyramid_cyclic if cyclic else c.gray_pyramid)(torch.from_numpy(np.stack([prev_gray, next_gray])).to(dev), opts.levels)
     img0, img1 = torch.zeros((1,), dtype=torch.int32, device=dev), torch.ones((1,), dtype=torch.int32, device=dev)
     for lo in range(0, N, _lib.LK_MAX_CAP):
         hi = min(N, lo + _lib.LK_MAX_CAP)

@@ -119,14 +119,16 @@ def match_features_frame_to_frame(cam_model, train_kpts, train_desc, query_kpts,
                                   keypts_as_points_query=None, pano_img_train=None, pano_img_query=None,
                                   show_matches=False, win_name="Matches (Frame-to-Frame)"):
     """pose_est_tools.py:211-269: query = current frame, train = keyframe; first percentage_good_matches of the
-    sorted matches; gate |du| <= max_horizontal_diff (no wrap-around, as the reference).
+    sorted matches; gate |du| <= max_horizontal_diff -- no wrap-around, as the reference, unless the camera model carries
+    set_cyclic_columns: then d <= max or cols - d <= max, in the search too when it is gated.
     -> (train idx, train kpts, train desc), (query idx, query kpts, query desc), colours"""
     fm = cam_model.feature_matcher_for_motion
     if getattr(fm, "gated", False):   # the search under the |du| gate applied below (off when that gate is off)
         pts = [keypoints_to_array(k) if p is None else np.asarray(p)
                for k, p in ((query_kpts, keypts_as_points_query), (train_kpts, keypts_as_points_train))]
+        cyc = dict(period=cam_model.top_model.panorama.cols) if getattr(cam_model, "cyclic_columns", False) else {}
         q, t, _ = fm.match_gated_many([(query_desc, train_desc, pts[0], pts[1])], -1.0, max_horizontal_diff,
-                                      fm.gated_max_distance)[0]
+                                      fm.gated_max_distance, **cyc)[0]
     else:
         q, t, _ = fm.match_arrays(query_desc, train_desc)
     matched_train_indices, matched_query_indices = [], []
@@ -148,6 +150,9 @@ def match_features_frame_to_frame(cam_model, train_kpts, train_desc, query_kpts,
             ok = filter_pixel_correspondences(matched_points_top=keypts_as_points_train,
                                               matched_points_bot=keypts_as_points_query, min_rectified_disparity=-1,
                                               max_horizontal_diff=max_horizontal_diff)
+            if getattr(cam_model, "cyclic_columns", False) and max_horizontal_diff > 0:   # ... or the short way round
+                d = np.abs(np.asarray(keypts_as_points_train)[..., 0] - np.asarray(keypts_as_points_query)[..., 0])
+                ok = np.logical_or(ok, float(cam_model.top_model.panorama.cols) - d <= max_horizontal_diff)
             matched_train_indices, matched_query_indices = t_all[ok], q_all[ok]
             matched_kpts_train, matched_kpts_query = k_train_all[ok], k_query_all[ok]
         else:
@@ -467,7 +472,8 @@ class TrackerStereoSE3(TrackerSE3):
         to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)    # noqa: E731
         prev = to(pts)
-        pyr = ctx.gray_pyramid(gray, o.levels, row_range=reference_frame.gray_rows)
+        cyclic = bool(getattr(om, "cyclic_columns", False))
+        pyr = (ctx.gray_pyramid_cyclic if cyclic else ctx.gray_pyramid)(gray, o.levels, row_range=reference_frame.gray_rows)
         res = ctx.track_lk(pyr, i32([0, 2]), i32([1, 3]), prev, i32([n, n]), half=o.half, max_iter=o.max_iter, eps=o.eps,
                            min_eig=o.min_eig, fb_max=o.fb_max)
         top, bot = om.top_model, om.bot_model
@@ -475,7 +481,8 @@ class TrackerStereoSE3(TrackerSE3):
         rig = make_rig(geo[0], geo[1], top.F[:3, 0], bot.F[:3, 0], 0.0, 0.0, f2f_max_hdiff=self.max_horizontal_diff_f2f_matches)
         frames = dict(m_top=prev[0:1], m_bot=prev[1:2], X=to(X), M=i32([n]))
         nxt, st = res[0], res[1]
-        corr = ctx.f2f_assemble_tracked(rig, frames, i32([0]), nxt[0:1], nxt[1:2], st[0:1], st[1:2], 2 * cap)
+        corr = ctx.f2f_assemble_tracked(rig, frames, i32([0]), nxt[0:1], nxt[1:2], st[0:1], st[1:2], 2 * cap,
+                                        **(dict(cyclic=True) if cyclic else {}))
         ctx.synchronize()
         num_initial_matches = int(corr["n"].cpu().numpy()[0])
         if num_initial_matches < self.min_matches_to_track():
@@ -677,6 +684,29 @@ def set_f2f_tracker(tracker, f2f_tracker, lk=None):
     tracker.lk_options = cm.lk_options = value
 
 
+def set_cyclic_columns(tracker, on):
+    """Cyclic panorama columns frame to frame.  on: None = leave the tracker's own setting, False = off,
+    True = column `cols` is column 0 again: the frame-to-frame |du| gate is cyclic (on the host, in the gated search and in
+    the assembles) and, with set_f2f_tracker(..., "lk"), so are the pyramids and the tracker.  Call it after set_f2f_tracker
+    and the matcher's setters: it checks the panorama width against them.  The camera model carries the setting, so the
+    per-frame mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker refuses True."""
+    if on is None:
+        return
+    cm = tracker.camera_model
+    value = False
+    if on:
+        if _is_rgbd_model(cm):
+            raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
+        from ..pipeline import _cyclic_columns
+        from .._lib import LK_MAX_LEVELS
+        from types import SimpleNamespace
+        fm = getattr(cm, "feature_matcher_for_motion", None)
+        widths = SimpleNamespace(pano_top=(cm.top_model.panorama.cols,), pano_bot=(cm.bot_model.panorama.cols,))
+        value = _cyclic_columns(True, widths, getattr(tracker, "lk_options", None), bool(getattr(fm, "gated", False)),
+                                getattr(fm, "ratio", None) is not None, LK_MAX_LEVELS)
+    tracker.cyclic_columns = cm.cyclic_columns = value
+
+
 def set_stereo_refinement(tracker, stereo_refine, stereo_lk=None):
     """Sub-pixel static stereo.  stereo_refine: None = leave the tracker's own setting (and stereo_lk must be None), False = off,
     "lk" = after the top / bottom matching the bottom keypoint of every matched pair is tracked from the top panorama into the
@@ -740,7 +770,8 @@ def _sos_engine_settings(tracker, camera_model, first_image):
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None), getattr(fm, "stereo_lk_options", None))
+           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None), getattr(fm, "stereo_lk_options", None),
+           bool(getattr(om, "cyclic_columns", False)))
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
@@ -749,6 +780,8 @@ def _sos_engine_settings(tracker, camera_model, first_image):
         kwargs.update(f2f_tracker="lk", lk=tracker.lk_options)
     if getattr(fm, "stereo_lk_options", None) is not None:
         kwargs.update(stereo_refine="lk", stereo_lk=fm.stereo_lk_options)
+    if getattr(om, "cyclic_columns", False):
+        kwargs.update(cyclic_columns=True)
     return (model, rig), kwargs, key
 
 
@@ -1301,7 +1334,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
            img_filename_template=None, depth_filename_template=None, img_indices=(), results_path="~/temp", thread_name="",
            _live_frames=None, _keyframe_thresholds=None, frame_window=None, detection_method=None, _engine_for=None,
            cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-           subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+           subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """pose_est_tools.py:1264-1678 without the 3-D visualisation (visualizer_3D_VO must be None): the frame loop,
     the keyframe policy (translation 0.01-0.20 m or rotation 1-10 degrees wrt the keyframe, enough tracked
     correspondences and keypoints), pose chaining through the keyframes, and the result files
@@ -1372,6 +1405,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
         set_subpixel_refinement(tracker, subpix_refine, subpix_half)      # (... and the frames' sub-pixel keypoints)
         set_f2f_tracker(tracker, f2f_tracker, lk)                         # (... and tracking in place of the f2f matcher)
         set_stereo_refinement(tracker, stereo_refine, stereo_lk)          # (... and the sub-pixel static stereo)
+        set_cyclic_columns(tracker, cyclic_columns)                       # (... and the seam; after the matcher's and the tracker's)
     if frame_window is None:
         frame_window = 32 if _live_frames is None else 1
     engine_state = dict(engine=None, tried=False, window_s=0.0, windows=0)
@@ -1485,7 +1519,7 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_filename="estimated_frame_poses_TUM.txt",
                 results_path="~/temp", thread_name="", frame_window=None, detection_method=None, cross_check=None,
                 gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+                subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """pose_est_tools.py:960-1262: the VO loop on the frames of a running camera thread.  `cam_working_thread` is the
     reference's CamAsWorkingThread contract (webcam_live.py:256-291; `omnistereo.webcam_live.FrameSourceThread` here):
     `.current_frame` = the most recent omni image (None when the source ends), `.quit_flag`.  Each pass of the loop
@@ -1509,7 +1543,7 @@ def run_VO_live(visualizer_3D_VO, camera_model, cam_working_thread, est_poses_fi
                   detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                   gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                   subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk, cyclic_columns=cyclic_columns)
 
 
 def _est_poses_filename(timestamped):
@@ -1551,7 +1585,7 @@ def _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_in
 def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visualize_VO=False, use_multithreads_for_VO=True,
                    thread_name="LIVE", frame_window=None, detection_method=None, cross_check=None,
                    gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """pose_est_tools.py:1743-1797: start the camera thread, run run_VO_live (on a worker thread or inline), then stop
     and join the camera thread."""
     if visualize_VO:
@@ -1559,7 +1593,7 @@ def driver_VO_live(camera_model, scene_path_vo_results, cam_working_thread, visu
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk, cyclic_columns=cyclic_columns)
     est_poses_filename = _est_poses_filename(timestamped=not use_multithreads_for_VO)
     cam_working_thread.start()
     if not getattr(cam_working_thread, "lockstep", False):
@@ -1581,7 +1615,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
               num_scene_images, visualize_VO=False, use_multithreads_for_VO=True, step_for_scene_images=1, first_image_index=0,
               last_image_index=-1, thread_name="", frame_window=None, detection_method=None, cross_check=None,
               gated_matching=None, gated_max_distance=None, ratio_test=None, ratio=None,
-              subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+              subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """pose_est_tools.py:1680-1741: frame index list, ground truth file discovery (gt_TUM.txt unless the scene is a
     static one), run_VO on a worker thread (as the reference does next to its GUI loop) or inline."""
     if visualize_VO:
@@ -1589,7 +1623,7 @@ def driver_VO(camera_model, scene_path, scene_path_vo_results, scene_img_filenam
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk, cyclic_columns=cyclic_columns)
     gt_poses_filename, vo_frame_indices = _scene_ground_truth_and_indices(scene_path, num_scene_images, first_image_index,
                                                                           last_image_index, step_for_scene_images)
     kwargs = dict(visualizer_3D_VO=None, camera_model=camera_model, gt_poses_filename=gt_poses_filename,
@@ -1614,7 +1648,7 @@ def _lane_limit(n_sequences, lanes, window):
 
 def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None, lanes=None, shard=None,
                 _keyframe_thresholds=None, cross_check=None, gated_matching=None, gated_max_distance=None, ratio_test=None,
-                ratio=None, subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+                ratio=None, subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """run_VO on SEVERAL sequences of one camera model at once: the sequences advance together as the lanes of one
     pipeline.MultiSequenceEngine / RGBDMultiSequenceEngine (one frame store, one stream; per round ONE front-end launch
     over the windows of all live lanes, one tracking launch per speculative guess, and the serial tracking calls the lanes
@@ -1668,7 +1702,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk, cyclic_columns=cyclic_columns)
     shared = dict(engine=None, key=None)
     guard, exited = threading.Lock(), set()
 
@@ -1744,7 +1778,7 @@ def run_VO_many(camera_model, sequences, frame_window=32, detection_method=None,
 def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_images=1, first_image_index=0, last_image_index=-1,
                    frame_window=None, detection_method=None, lanes=None, shard=None, cross_check=None, gated_matching=None,
                    gated_max_distance=None, ratio_test=None, ratio=None,
-                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None):
+                   subpix_refine=None, subpix_half=None, f2f_tracker=None, lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=None):
     """driver_VO for several scenes of one camera model through run_VO_many.  scenes: a list of dicts(scene_path,
     scene_path_vo_results, scene_img_filename_template, depth_filename_template, num_scene_images, thread_name); the frame
     index list and the ground-truth file of each scene are found as driver_VO finds them.  -> run_VO_many's list."""
@@ -1753,7 +1787,7 @@ def driver_VO_many(camera_model, scenes, visualize_VO=False, step_for_scene_imag
     options = dict(detection_method=detection_method, cross_check=cross_check, gated_matching=gated_matching,
                    gated_max_distance=gated_max_distance, ratio_test=ratio_test, ratio=ratio,
                    subpix_refine=subpix_refine, subpix_half=subpix_half, f2f_tracker=f2f_tracker,
-                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk)
+                   lk=lk, stereo_refine=stereo_refine, stereo_lk=stereo_lk, cyclic_columns=cyclic_columns)
     sequences = []
     for sc in scenes:
         gt_poses_filename, indices = _scene_ground_truth_and_indices(sc["scene_path"], int(sc["num_scene_images"]), first_image_index,

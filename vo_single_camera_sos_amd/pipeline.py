@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import LKOptions, MatchOptions, f2f_tracker_options, stereo_refine_options, subpix_flags, subpix_half
+from ._lib import LK_MAX_LEVELS, LKOptions, MatchOptions, f2f_tracker_options, stereo_refine_options, subpix_flags, subpix_half
 from .device import Context, make_rig
 
 
@@ -31,11 +31,40 @@ class RigConfig(object):
                         self.stereo_min_disp, self.stereo_max_hdiff, self.f2f_max_hdiff, self.pct_good_matches)
 
 
+def _no_cyclic_columns(cyclic_columns):
+    if cyclic_columns:
+        raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
+
+
+def _cyclic_columns(cyclic_columns, rig, lk, gated_f2f, ratio_f2f, store_levels=None):
+    """The `cyclic_columns` argument checked against the rig and the frame-to-frame settings -> bool.  lk: the tracker's
+    LKOptions or None.  store_levels: the levels a frame store keeps whatever the settings (the batched engines:
+    SOSVO_LK_MAX_LEVELS), None for the pair pipeline, which builds the levels it tracks on."""
+    if not cyclic_columns:
+        return False
+    widths = (rig.pano_top[0], rig.pano_bot[0])
+    for w in widths:
+        if not (w == int(w) and 1 <= w <= 16384):
+            raise ValueError("cyclic_columns: the panorama width must be a positive integer up to 16384, got %r" % (w,))
+    if lk is not None:
+        for w in widths:
+            levels = max(lk.levels, store_levels or 1)
+            if int(w) % (1 << (levels - 1)) or (int(w) >> (lk.levels - 1)) < 2 * lk.half + 3:
+                raise ValueError("cyclic_columns with f2f_tracker=\"lk\": a panorama width of %d columns is no multiple of %d, or "
+                                 "its top level is narrower than the %d-column template" % (w, 1 << (levels - 1), 2 * lk.half + 3))
+    if gated_f2f and ratio_f2f:
+        raise ValueError("cyclic_columns: the ratio form of the gated frame-to-frame matcher has no cyclic gate")
+    if gated_f2f and widths[0] != widths[1]:
+        raise ValueError("cyclic_columns with gated_f2f: one search serves both views, their widths must be equal (%r, %r)" % widths)
+    return True
+
+
 class FramePairPipeline(object):
     def __init__(self, ctx, rig, n_pairs, nmask=12, bucket_cap=192, frame_cap=2048, thr=None, max_iter=2000,
                  adaptive=False, seed=0, lm_iter=30, front_end=None, ransac_solver="P3P", cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None,
+                 cyclic_columns=False):
         """front_end: an ImageFrontEnd over 2 * n_pairs frames; its keypoint/descriptor buffers are used in
         place (no copy).  Without it, keypoints are loaded with load_keypoints().
         ransac_solver: "GP3P" = generalised P3P on samples across both mirrors (what the reference's non-central RANSAC
@@ -56,8 +85,13 @@ class FramePairPipeline(object):
         stereo_refine: None, or "lk" = sub-pixel static stereo: between sort_matches and stereo_assemble the bottom keypoint of
         every matched pair is tracked from the top panorama into the bottom one (Context.refine_stereo_lk; the same call of
         the reference, between the two views of one frame) -- needs a front end.  stereo_lk: its settings, None / a
-        StereoLKOptions / a dict of its fields (half, max_iter, eps, min_eig, max_shift)."""
+        StereoLKOptions / a dict of its fields (half, max_iter, eps, min_eig, max_shift).
+        cyclic_columns: the panoramas are full circles, column `cols` is column 0 again: the
+        frame-to-frame |du| gate is cyclic in the assemble and, with gated_f2f, inside the matcher; with f2f_tracker="lk" the
+        pyramids and the tracker are cyclic too (cols a multiple of 2^(levels - 1), the top level at least 2 half + 3 columns
+        wide).  The period is the rig's pano_top[0] / pano_bot[0]."""
         assert isinstance(ctx, Context)
+        self.cyclic = _cyclic_columns(cyclic_columns, rig, LKOptions.of(lk) if f2f_tracker == "lk" else None, gated_f2f, ratio_f2f)
         self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
         if self.stereo_lk is not None and front_end is None:
             raise ValueError("stereo_refine=\"lk\" needs a front end: the refinement reads the gray panoramas")
@@ -129,6 +163,9 @@ class FramePairPipeline(object):
         self._q2, self._t2, self._k2 = q[: 2 * self.B], t[: 2 * self.B], self._k[: 2 * self.B]     # the forward problems
         self._f2f_search = dict(ratio_64ths=o.ratio_64ths_f2f, rivals=torch.zeros_like(self._k) if o.ratio_f2f else None,
                                 gate=(-1.0, rig.f2f_max_hdiff, gated_max_distance) if o.gated_f2f else None)
+        if self.cyclic and o.gated_f2f:    # (one search serves both views: _cyclic_columns checked that their widths agree)
+            self._f2f_search["period"] = float(rig.pano_top[0])
+        self._cyc = dict(cyclic=True) if self.cyclic else {}     # (off: the assembles are called as they always were)
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
         self.o_top, self.o_bot = self._o2[: self.B], self._o2[self.B:]
         self.corr = dict(f=z((self.B, Cc, 3), torch.float64), p=z((self.B, Cc, 3), torch.float64),
@@ -179,14 +216,14 @@ class FramePairPipeline(object):
         c, fe, o = self.ctx, self.front_end, self.lk
         self._M2[1].copy_(self._M2[0])
         rr = None if fe.keep_panoramas else fe.gray_rows
-        self._lk_pyr = c.gray_pyramid(fe.gray, o.levels, row_range=rr, out=self._lk_pyr)
+        self._lk_pyr = (c.gray_pyramid_cyclic if self.cyclic else c.gray_pyramid)(fe.gray, o.levels, row_range=rr, out=self._lk_pyr)
         torch.index_select(self._m2.view(2 * self.F, self.frame_cap, 2), 0, self._lk_ref, out=self._lk_prev)
         torch.index_select(self._M2.view(2 * self.F), 0, self._lk_ref, out=self._lk_n)
         res = c.track_lk(self._lk_pyr, self._t2, self._q2, self._lk_prev, self._lk_n, half=o.half, max_iter=o.max_iter,
                          eps=o.eps, min_eig=o.min_eig, fb_max=o.fb_max, out=self._lk_out)
         nxt, st = res[0], res[1]
         c.f2f_assemble_tracked(self.rig, self.frames, self.ref_frame, nxt[: self.B], nxt[self.B:], st[: self.B], st[self.B:],
-                               self.corr_cap, out=self.corr)
+                               self.corr_cap, out=self.corr, **self._cyc)
 
     def track(self):
         c, fr = self.ctx, self.frames
@@ -199,7 +236,7 @@ class FramePairPipeline(object):
         c.match_1nn_slots(d2, m2, M2, self._q, self._t, self._k, 2 * self.B, **self._f2f_search)   # both views, 2B problems
         c.sort_matches(self._k2, M2, order=self._o2, q_slot=self._q2)
         c.f2f_assemble(self.rig, fr, self.ref_frame, self.cur_frame, self.k_top, self.o_top, self.k_bot, self.o_bot,
-                       self.corr_cap, out=self.corr)
+                       self.corr_cap, out=self.corr, **self._cyc)
         self._solve()
 
     def _solve(self):
@@ -250,7 +287,7 @@ class OverlappedFramePairs(object):
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray.
         f2f_tracker / lk: as FramePairPipeline ("lk": every part's pipeline tracks with these settings).
@@ -261,6 +298,7 @@ class OverlappedFramePairs(object):
                             ratio_f2f, ratio)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
         self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
+        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, gated_f2f, ratio_f2f)      # (before the device is touched)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
@@ -285,7 +323,8 @@ class OverlappedFramePairs(object):
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
                                            ransac_solver=ransac_solver, f2f_tracker=f2f_tracker, lk=self.lk,
-                                           stereo_refine=stereo_refine, stereo_lk=self.stereo_lk, **opts._asdict())
+                                           stereo_refine=stereo_refine, stereo_lk=self.stereo_lk,
+                                           **(dict(cyclic_columns=True) if self.cyclic else {}), **opts._asdict())
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -416,7 +455,7 @@ class OverlappedFramePairs(object):
 def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
               adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
               gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
-              subpix=None, lk=None, stereo_lk=None):
+              subpix=None, lk=None, stereo_lk=None, cyclic_columns=False):
     """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
     any ransac_solver but "GP3P" is P3P.  lk: None, or the LKOptions of an engine that tracks (SOSVO_FLAG_LK_F2F; the
@@ -444,6 +483,8 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
         c.ransac_flags |= _lib.FLAG_LK_F2F
     if stereo_lk is not None:
         c.ransac_flags |= _lib.FLAG_LK_STEREO
+    if cyclic_columns:    # (checked by the caller: _cyclic_columns)
+        c.ransac_flags |= _lib.FLAG_CYCLIC_F2F
     return c
 
 
@@ -465,7 +506,7 @@ class FramePairBatch(object):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap).
@@ -479,11 +520,12 @@ class FramePairBatch(object):
                             ratio_f2f, ratio)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
         self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
+        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, gated_f2f, ratio_f2f, LK_MAX_LEVELS)
         self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                  median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                  max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
                                  detection_method=detection_method, subpix=subpix, lk=self.lk, stereo_lk=self.stereo_lk,
-                                 **opts._asdict())
+                                 **(dict(cyclic_columns=True) if self.cyclic else {}), **opts._asdict())
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -613,7 +655,7 @@ class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
     def __init__(self, ctx, model, rig, frames, slots, gather, opts, f2f_tracker="match", lk=None, stereo_refine=None,
-                 stereo_lk=None, **settings):
+                 stereo_lk=None, cyclic_columns=False, **settings):
         """opts: a MatchOptions; f2f_tracker / lk, stereo_refine / stereo_lk: as FramePairPipeline's; settings: batch_cfg's tracker settings
         (num_of_features ... detection_method) but the seed."""
         assert isinstance(ctx, Context)
@@ -621,7 +663,9 @@ class _OmniFamily(_SequenceFamily):
         self.heads = self.track_heads = (self.rig,)
         self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
         self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
-        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, stereo_lk=self.stereo_lk, **settings, **opts._asdict())
+        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, opts.gated_f2f, opts.ratio_f2f, LK_MAX_LEVELS)
+        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, stereo_lk=self.stereo_lk,
+                             **(dict(cyclic_columns=True) if self.cyclic else {}), **settings, **opts._asdict())
         self.method = str(settings["detection_method"]).upper()
         if str(settings["ransac_solver"]).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -921,7 +965,7 @@ class SequenceEngine(_SequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
         detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
@@ -935,6 +979,7 @@ class SequenceEngine(_SequenceBase):
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
         self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts, f2f_tracker, lk, stereo_refine, stereo_lk,
+                                cyclic_columns,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1170,10 +1215,11 @@ class RGBDPairBatch(object):
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
                  seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         from . import orb_pattern
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
+        _no_cyclic_columns(cyclic_columns)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
@@ -1220,9 +1266,10 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
+        _no_cyclic_columns(cyclic_columns)
         self._init_windows(window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, opts, mask,
@@ -1557,12 +1604,12 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
                  gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         self._init_lanes(lanes, window)
         opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio)
         self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts, f2f_tracker, lk, stereo_refine,
-                                stereo_lk,
+                                stereo_lk, cyclic_columns,
                                 num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
                                 max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
@@ -1576,9 +1623,10 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None):
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
         stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
+        _no_cyclic_columns(cyclic_columns)
         self._init_lanes(lanes, window)
         opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
         self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, opts, mask,
