@@ -155,7 +155,8 @@ def test_every_driver_and_engine_takes_the_arguments():
 
 def test_every_constructor_hands_the_value_inward(monkeypatch):
     """ImageFrontEnd keeps it (on a stand-in context: host tensors); FramePairPipeline hands it to its front end; the one-call
-    and sequence engines hand it to batch_cfg (recorded, and the construction stopped there)."""
+    and sequence engines hand it, in their StepOptions, to the function behind batch_cfg (recorded, and the construction
+    stopped there)."""
     from vo_single_camera_sos_amd import frontend, pipeline
     from vo_single_camera_sos_amd.device import Context
     model = SimpleNamespace(H=8, W=8, rows=4, cols=4, nmask=1, unwrap_table=object())
@@ -192,10 +193,10 @@ def test_every_constructor_hands_the_value_inward(monkeypatch):
 
     seen = []
 
-    def recorder(*args, **kwargs):
-        seen.append(kwargs.get("subpix", "missing"))
+    def recorder(so, *args, **kwargs):      # (the engines hand their StepOptions to the function behind batch_cfg)
+        seen.append(so.subpix if "subpix" not in kwargs else "twice")
         raise _Stop()
-    monkeypatch.setattr(pipeline, "batch_cfg", recorder)
+    monkeypatch.setattr(pipeline, "_batch_cfg", recorder)
     rig = SimpleNamespace(as_struct=lambda: None)
     for build in (lambda s: pipeline.FramePairBatch(ctx, model, rig, 2, subpix=s),
                   lambda s: pipeline.SequenceEngine(ctx, model, rig, window=2, subpix=s),

@@ -307,40 +307,47 @@ def subpix_weights(half):
     return list(w)[:2 * int(half) + 1]
 
 
-class LKOptions(namedtuple("LKOptions", "half levels max_iter eps min_eig fb_max")):
+class _Settings(object):
+    """What LKOptions and StereoLKOptions share: the range checks of their fields and of().  `arg`, `kind`: their argument and
+    themselves as the messages name them."""
+    __slots__ = ()
+
+    @classmethod
+    def _check(cls, integers, numbers):
+        for name, v, lo, hi in integers:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
+                raise ValueError("%s %s must be an integer in %d .. %d, got %r" % (cls.arg, name, lo, hi, v))
+        for name, v in numbers:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
+                raise ValueError("%s %s must be a finite number >= 0, got %r" % (cls.arg, name, v))
+
+    @classmethod
+    def of(cls, value):
+        """An `lk` / `stereo_lk` argument (None: the defaults; a value of the class; a dict of its fields) -> the value."""
+        if value is None or isinstance(value, cls):
+            return cls() if value is None else value
+        if not isinstance(value, dict):
+            raise ValueError("%s must be None, %s or a dict of its fields, got %r" % (cls.arg, cls.kind, value))
+        if set(value) - set(cls._fields):
+            raise ValueError("%s: unknown settings %s" % (cls.arg, sorted(set(value) - set(cls._fields))))
+        return cls(**value)
+
+
+class LKOptions(_Settings, namedtuple("LKOptions", "half levels max_iter eps min_eig fb_max")):
     """The settings of the pyramidal Lucas-Kanade tracker (sosvo_track_lk) as one checked value: window half-size 2 .. 10,
     pyramid levels 1 .. 4, max_iter 1 .. 30, eps >= 0, min_eig >= 0 (OpenCV's minEigThreshold), fb_max None (no
     forward-backward check) or > 0 pixels.  Defaults: cv2.calcOpticalFlowPyrLK's (21 x 21 window, maxLevel 2 -> 3 levels,
     TermCriteria(30, 0.01), 1e-4).  A value out of range raises ValueError; nothing is rounded."""
-    __slots__ = ()
+    __slots__, arg, kind = (), "lk", "an LKOptions"
 
     def __new__(cls, half=10, levels=3, max_iter=30, eps=0.01, min_eig=1e-4, fb_max=None):
-        for name, v, lo, hi in (("half", half, 2, LK_MAX_HALF), ("levels", levels, 1, LK_MAX_LEVELS),
-                                ("max_iter", max_iter, 1, LK_MAX_ITER)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
-                raise ValueError("lk %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
-        for name, v in (("eps", eps), ("min_eig", min_eig)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
-                raise ValueError("lk %s must be a finite number >= 0, got %r" % (name, v))
+        cls._check((("half", half, 2, LK_MAX_HALF), ("levels", levels, 1, LK_MAX_LEVELS), ("max_iter", max_iter, 1, LK_MAX_ITER)),
+                   (("eps", eps), ("min_eig", min_eig)))
         if fb_max is not None and (isinstance(fb_max, bool) or not isinstance(fb_max, (int, float))
                                    or not 0.0 < fb_max < float("inf")):
             raise ValueError("lk fb_max must be None or a finite number > 0 (pixels), got %r" % (fb_max,))
         return super().__new__(cls, int(half), int(levels), int(max_iter), float(eps), float(min_eig),
                                None if fb_max is None else float(fb_max))
-
-    @classmethod
-    def of(cls, lk):
-        """An `lk` argument (None: the defaults; an LKOptions; a dict of its fields) -> LKOptions."""
-        if lk is None:
-            return cls()
-        if isinstance(lk, cls):
-            return lk
-        if isinstance(lk, dict):
-            unknown = set(lk) - set(cls._fields)
-            if unknown:
-                raise ValueError("lk: unknown settings %s" % sorted(unknown))
-            return cls(**lk)
-        raise ValueError("lk must be None, an LKOptions or a dict of its fields, got %r" % (lk,))
 
 
 class LkOptionsStruct(ctypes.Structure):
@@ -354,20 +361,15 @@ class LkOptionsStruct(ctypes.Structure):
         return cls(lk.half, lk.levels, lk.max_iter, 0, lk.eps, lk.min_eig, 0.0 if lk.fb_max is None else lk.fb_max)
 
 
-class StereoLKOptions(namedtuple("StereoLKOptions", "half max_iter eps min_eig max_shift")):
+class StereoLKOptions(_Settings, namedtuple("StereoLKOptions", "half max_iter eps min_eig max_shift")):
     """The settings of the static-stereo Lucas-Kanade refinement (sosvo_refine_stereo_lk) as one checked value: window
     half-size 2 .. 10, max_iter 1 .. 30, eps >= 0, min_eig >= 0, max_shift None (= half) or a finite number >= 0 (pixels; 0
     means half as well): a tracked position further than that from the matcher's partner on either axis is reverted.  A
     value out of range raises ValueError; nothing is rounded."""
-    __slots__ = ()
+    __slots__, arg, kind = (), "stereo_lk", "a StereoLKOptions"
 
     def __new__(cls, half=4, max_iter=30, eps=0.01, min_eig=1e-4, max_shift=None):
-        for name, v, lo, hi in (("half", half, 2, LK_MAX_HALF), ("max_iter", max_iter, 1, LK_MAX_ITER)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
-                raise ValueError("stereo_lk %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
-        for name, v in (("eps", eps), ("min_eig", min_eig)):
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v < float("inf"):
-                raise ValueError("stereo_lk %s must be a finite number >= 0, got %r" % (name, v))
+        cls._check((("half", half, 2, LK_MAX_HALF), ("max_iter", max_iter, 1, LK_MAX_ITER)), (("eps", eps), ("min_eig", min_eig)))
         if max_shift is not None and (isinstance(max_shift, bool) or not isinstance(max_shift, (int, float))
                                       or not 0.0 <= max_shift < float("inf")):
             raise ValueError("stereo_lk max_shift must be None or a finite number >= 0 (pixels), got %r" % (max_shift,))
@@ -378,20 +380,6 @@ class StereoLKOptions(namedtuple("StereoLKOptions", "half max_iter eps min_eig m
     def bound(self):
         """The acceptance bound in pixels: max_shift, or half where it is None or 0."""
         return float(self.max_shift) if self.max_shift else float(self.half)
-
-    @classmethod
-    def of(cls, stereo_lk):
-        """A `stereo_lk` argument (None: the defaults; a StereoLKOptions; a dict of its fields) -> StereoLKOptions."""
-        if stereo_lk is None:
-            return cls()
-        if isinstance(stereo_lk, cls):
-            return stereo_lk
-        if isinstance(stereo_lk, dict):
-            unknown = set(stereo_lk) - set(cls._fields)
-            if unknown:
-                raise ValueError("stereo_lk: unknown settings %s" % sorted(unknown))
-            return cls(**stereo_lk)
-        raise ValueError("stereo_lk must be None, a StereoLKOptions or a dict of its fields, got %r" % (stereo_lk,))
 
 
 class StereoLkOptionsStruct(ctypes.Structure):
@@ -420,9 +408,8 @@ def stereo_refine_options(stereo_refine, stereo_lk, rgbd=False):
 
 
 def f2f_tracker_options(f2f_tracker, lk, opts=None, rgbd=False):
-    """The `f2f_tracker` / `lk` arguments of the engines' constructors -> the LKOptions of an engine that tracks ("lk"), None
-    for one that matches ("match").  As FramePairPipeline: settings without the tracker are refused; so are the options
-    (`opts`, a MatchOptions) of the frame-to-frame matcher the tracker replaces, and the tracker on an RGB-D engine."""
+    """The `f2f_tracker` / `lk` arguments -> the LKOptions of an engine that tracks ("lk"), None for one that matches ("match").
+    Refused: settings without the tracker, the options (`opts`, a MatchOptions) of the matcher it replaces, an RGB-D engine."""
     if f2f_tracker not in ("match", "lk"):
         raise ValueError("f2f_tracker: \"match\" or \"lk\", got %r" % (f2f_tracker,))
     if f2f_tracker != "lk":
@@ -448,7 +435,7 @@ def gray_pyramid_bytes(nimg, rows, cols, levels):
 
 class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2f gated_stereo gated_f2f gated_max_distance "
                                               "ratio_stereo ratio_f2f ratio")):
-    """The matchers' options as ONE value: what every public constructor builds from its own arguments and passes inward,
+    """The matchers' options as ONE value, the `match` of a StepOptions: what every public constructor builds and passes inward,
     down to the flags of a batch configuration (flags()) or the arguments of Context.match_1nn.  Checked on construction by
     the three flag functions above (their ValueErrors).  Immutable and hashable: it is its own engine-cache key.  A new
     matcher option is a field here, an argument of Context.match_1nn and of match_1nn in pipeline.hip."""
@@ -499,6 +486,105 @@ class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2
             return None
         return cls(cross[0], cross[1], gated[0], gated[1], caps.pop() if caps else None, ratios[0] is not None,
                    ratios[1] is not None, ratios[0] if ratios[0] is not None else ratios[1])
+
+
+class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic")):
+    """Everything a step can be told, as ONE value: `match` a MatchOptions; `subpix` the window half-size 2 .. 5 of the sub-pixel
+    keypoint refinement or None; `lk` the LKOptions of a step that tracks frame to frame, None for one that matches;
+    `stereo_lk` the StereoLKOptions of one that refines its static stereo, or None; `cyclic`: the panorama columns are one
+    period.  Every public constructor builds one from its own arguments first (of() / rgbd() run the checks) and uses it from
+    there, down to flags().  Hashable: its own engine-cache key.  A new option is a field here, a public keyword and its C flag."""
+    __slots__ = ()
+    # of()'s checks in the order the pair pipeline and the batched layers have always run them: of two broken rules the first
+    # one speaks.  "lk" parses the tracker's settings alone; "tracker" is f2f_tracker_options, and gives `lk` too
+    PAIR_ORDER = ("lk", "cyclic", "stereo_lk", "tracker", "subpix", "match")
+    BATCH_ORDER = ("match", "tracker", "stereo_lk", "cyclic", "subpix")
+
+    def __new__(cls, match=None, subpix=None, lk=None, stereo_lk=None, cyclic=False):
+        return super().__new__(cls, MatchOptions() if match is None else match, subpix_half(subpix), lk, stereo_lk, bool(cyclic))
+
+    def flags(self):
+        """The options' bits of sosvo_batch_cfg.ransac_flags (an RGB-D value has the matcher's alone: sosvo_rgbd_batch_cfg.flags)."""
+        return (self.match.flags() | subpix_flags(self.subpix) | (FLAG_LK_F2F if self.lk is not None else 0)
+                | (FLAG_LK_STEREO if self.stereo_lk is not None else 0) | (FLAG_CYCLIC_F2F if self.cyclic else 0))
+
+    @classmethod
+    def of(cls, cross_check_stereo=False, cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None,
+           ratio_stereo=False, ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None,
+           stereo_lk=None, cyclic_columns=False, rig=None, store_levels=None, order=BATCH_ORDER, tracker_sees_match=True,
+           gray=True):
+        """From the public keyword names (FramePairPipeline's docstring describes them), checked.  rig: a RigConfig or the
+        panoramas' (top, bottom) widths, the period of cyclic_columns (not looked at without).  store_levels: the pyramid levels
+        a frame store keeps whatever the settings (the batched engines: SOSVO_LK_MAX_LEVELS), None for a caller that builds the
+        levels it tracks on.  order: the checks to run, in turn.  tracker_sees_match: f2f_tracker="lk" refuses the options of
+        the matcher it replaces ("match" comes before "tracker" then).  gray: False = no gray panoramas to read (a pair
+        pipeline without a front end): what reads them is refused."""
+        def needs_gray(on, what, who):
+            if on is not None and not gray:
+                raise ValueError("%s needs a front end: the %s reads the gray panoramas" % (what, who))
+            return on
+
+        def cyclic():
+            if not cyclic_columns:
+                return False
+            o, widths = v["lk"], (rig.pano_top[0], rig.pano_bot[0]) if hasattr(rig, "pano_top") else tuple(rig)
+            for w in widths:
+                if not (w == int(w) and 1 <= w <= 16384):
+                    raise ValueError("cyclic_columns: the panorama width must be a positive integer up to 16384, got %r" % (w,))
+            for w in widths if o is not None else ():
+                levels = max(o.levels, store_levels or 1)
+                if int(w) % (1 << (levels - 1)) or (int(w) >> (o.levels - 1)) < 2 * o.half + 3:
+                    raise ValueError("cyclic_columns with f2f_tracker=\"lk\": a panorama width of %d columns is no multiple of %d, or "
+                                     "its top level is narrower than the %d-column template" % (w, 1 << (levels - 1), 2 * o.half + 3))
+            if gated_f2f and ratio_f2f:
+                raise ValueError("cyclic_columns: the ratio form of the gated frame-to-frame matcher has no cyclic gate")
+            if gated_f2f and widths[0] != widths[1]:
+                raise ValueError("cyclic_columns with gated_f2f: one search serves both views, their widths must be equal (%r, %r)"
+                                 % widths)
+            return True
+        match = (cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
+        v, checks = {}, dict(
+            match=lambda: MatchOptions(*match),
+            lk=lambda: LKOptions.of(lk) if f2f_tracker == "lk" else None,
+            tracker=lambda: needs_gray(f2f_tracker_options(f2f_tracker, lk, v["match"] if tracker_sees_match else None),
+                                       "f2f_tracker=\"lk\"", "tracker"),
+            stereo_lk=lambda: needs_gray(stereo_refine_options(stereo_refine, stereo_lk), "stereo_refine=\"lk\"", "refinement"),
+            subpix=lambda: subpix_half(needs_gray(subpix, "subpix", "refinement")), cyclic=cyclic)
+        for name in order:
+            v["lk" if name == "tracker" else name] = checks[name]()
+        return cls(**v)
+
+    @classmethod
+    def rgbd(cls, cross_check=False, gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match",
+             lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+        """From the RGB-D classes' names: a camera without static stereo has the frame-to-frame matcher only (`match` is
+        MatchOptions.rgbd), no tracker, and a pinhole image that is not cyclic -- asking for one of these is a ValueError."""
+        f2f_tracker_options(f2f_tracker, lk, rgbd=True)
+        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)
+        if cyclic_columns:
+            raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
+        return cls(MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio))
+
+    def kwargs(self):
+        """The inverse of of(): the public keywords of a constructor that is handed this value.  Options that came after the
+        matcher's are left out when they are off, so that such a constructor is called as it was before they existed."""
+        kw = dict(self.match._asdict(), subpix=self.subpix)
+        if self.lk is not None:
+            kw.update(f2f_tracker="lk", lk=self.lk)
+        if self.stereo_lk is not None:
+            kw.update(stereo_refine="lk", stereo_lk=self.stereo_lk)
+        if self.cyclic:
+            kw.update(cyclic_columns=True)
+        return kw
+
+    @classmethod
+    def from_tracker(cls, tracker, camera_model):
+        """What a batched engine runs for a tracker and its camera model, read where the set_* functions of pose_est_tools wrote
+        it (the matchers, tracker.lk_options, camera_model.cyclic_columns); None where MatchOptions.from_matchers is."""
+        fm = getattr(camera_model, "feature_matcher_for_static_stereo", None)
+        match = MatchOptions.from_matchers(fm, getattr(camera_model, "feature_matcher_for_motion", None))
+        return None if match is None else cls(match, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None),
+                                              getattr(fm, "stereo_lk_options", None), getattr(camera_model, "cyclic_columns", False))
 
 
 def rgbd_flags_detector(flags):

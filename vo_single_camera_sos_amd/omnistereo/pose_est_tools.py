@@ -28,7 +28,7 @@ from math import log10, sqrt
 import numpy as np
 
 from .. import pyopengv
-from .._lib import MatchOptions
+from .._lib import LK_MAX_LEVELS, MatchOptions, StepOptions, f2f_tracker_options, gated_flags, ratio_flags, stereo_refine_options
 from . import transformations as tr
 from .camera_models import FeatureMatcher, KeyPoint, KeyPointAndDescriptor, PanoramicCorrespondences, keypoints_to_array
 from .common_cv import filter_pixel_correspondences
@@ -574,9 +574,11 @@ def parse_cross_check(cross_check):
 def _set_matcher_option(tracker, name, value, validate, setting, check, mirror):
     """What set_cross_check / set_gated_matching / set_ratio_test share.  value as parse_cross_check takes its argument (None:
     nothing happens); validate(stereo, f2f) checks the option's own values; an RGB-D tracker has the frame-to-frame matcher
-    only ("stereo" is a ValueError); setting(on) -> the FeatureMatcher attributes of a matcher switched `on`, check(fm, on)
-    raises what that matcher refuses (k_best > 1, radius match, float descriptors); mirror(stereo, f2f) -> the tracker's
-    attributes.  Every matcher is checked before anything is kept: a refused setting leaves matchers and tracker as they were."""
+    only (True / False / "f2f" set it, "stereo" is a ValueError); setting(on) -> the FeatureMatcher attributes of a matcher
+    switched `on`, check(fm, on) raises what that matcher refuses (k_best > 1, radius match, float descriptors);
+    mirror(stereo, f2f) -> the tracker's attributes.  Every matcher is checked before anything is kept: a refused setting
+    leaves matchers and tracker as they were.  The matchers bootstrap_tracker built carry the setting, so the per-frame
+    mirror path and the engine chosen from the tracker's settings both follow."""
     if value is None:
         return
     try:
@@ -607,9 +609,8 @@ def _set_matcher_option(tracker, name, value, validate, setting, check, mirror):
 
 def set_cross_check(tracker, cross_check):
     """Switch the mutual-consistency filter (cv2.BFMatcher's crossCheck, camera_models.py:401) of the tracker's matchers:
-    cross_check as parse_cross_check takes it (None: leave the tracker's own setting).  The matchers bootstrap_tracker
-    built carry the switch, so the per-frame mirror path and the engine chosen from the tracker's settings both follow.
-    An RGB-D tracker has the frame-to-frame matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
+    cross_check as parse_cross_check takes it (None: leave the tracker's own setting).  Who carries the switch, and what an
+    RGB-D tracker refuses: _set_matcher_option."""
     _set_matcher_option(tracker, "cross_check", cross_check, lambda stereo, f2f: None, lambda on: dict(cross_check=on),
                         lambda fm, on: fm._check_cross_check(),
                         lambda stereo, f2f: dict(cross_check_static_stereo=stereo, cross_check_for_motion=f2f))
@@ -618,10 +619,8 @@ def set_cross_check(tracker, cross_check):
 def set_gated_matching(tracker, gated_matching, gated_max_distance=None):
     """Switch the search under the pixel gates (FeatureMatcher.match_gated) of the tracker's matchers: gated_matching as
     parse_cross_check takes its argument (None: leave the tracker's own setting, and gated_max_distance is ignored);
-    gated_max_distance: None = no cap, or 1 .. 256.  The matchers bootstrap_tracker built carry the switch, so the per-frame
-    mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame
-    matcher only: True / False / "f2f" set it, "stereo" is a ValueError."""
-    from .._lib import gated_flags
+    gated_max_distance: None = no cap, or 1 .. 256.  Who carries the switch, and what an RGB-D tracker refuses:
+    _set_matcher_option."""
     cap = gated_max_distance      # (gated_flags: ValueError for a cap outside 1 .. 256; then an integer)
     _set_matcher_option(tracker, "gated_matching", gated_matching, lambda stereo, f2f: gated_flags(stereo, f2f, cap),
                         lambda on: dict(gated=on, gated_max_distance=None if cap is None else int(cap)),
@@ -634,10 +633,7 @@ def set_ratio_test(tracker, ratio_test, ratio=None):
     """Switch Lowe's ratio rule (FeatureMatcher's ratio: evaluated on the device, fused into the search) of the tracker's
     matchers: ratio_test as parse_cross_check takes its argument (None: leave the tracker's own setting, and ratio is
     ignored); ratio: a float in (0, 1) with ratio * 64 an integer (0.75: the reference's, camera_models.py:423), required
-    when a matcher is switched on.  The matchers bootstrap_tracker built carry the setting, so the per-frame mirror path and
-    the engine chosen from the tracker's settings both follow.  An RGB-D tracker has the frame-to-frame matcher only: True /
-    False / "f2f" set it, "stereo" is a ValueError."""
-    from .._lib import ratio_flags
+    when a matcher is switched on.  Who carries the setting, and what an RGB-D tracker refuses: _set_matcher_option."""
     of = lambda on: float(ratio) if on else None      # noqa: E731 (ratio_flags: ValueError for a ratio that is no 64th, or none)
     _set_matcher_option(tracker, "ratio_test", ratio_test, lambda stereo, f2f: ratio_flags(stereo, f2f, ratio),
                         lambda on: dict(ratio=of(on)), lambda fm, on: fm._check_ratio(),
@@ -650,7 +646,7 @@ def set_subpixel_refinement(tracker, subpix, half=5):
     own setting (and half is ignored), True / False; half: the window half-size 2 .. 5 (None: 5).  The static-stereo matcher
     bootstrap_tracker built carries the setting to the frames, so the per-frame mirror path and the engine chosen from the
     tracker's settings both follow.  An RGB-D tracker reads depth at the keypoints' integer pixels: True is a ValueError."""
-    from .._lib import subpix_half
+    from .._lib import subpix_half      # (a name run_VO's arguments use too)
     if subpix is None:
         return
     if not isinstance(subpix, (bool, np.bool_)):
@@ -673,7 +669,6 @@ def set_f2f_tracker(tracker, f2f_tracker, lk=None):
     to the frames (they keep their gray panoramas on the device), so the per-frame mirror path and the engine chosen from the
     tracker's settings both follow.  An RGB-D tracker refuses "lk"; so does a tracker whose frame-to-frame matcher has an
     option set (cross_check, gated_matching, ratio_test): the tracker replaces that matcher."""
-    from .._lib import f2f_tracker_options
     if f2f_tracker is None:
         if lk is not None:
             raise ValueError("lk settings without f2f_tracker=\"lk\"")
@@ -697,13 +692,11 @@ def set_cyclic_columns(tracker, on):
     if on:
         if _is_rgbd_model(cm):
             raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
-        from ..pipeline import _cyclic_columns
-        from .._lib import LK_MAX_LEVELS
-        from types import SimpleNamespace
-        fm = getattr(cm, "feature_matcher_for_motion", None)
-        widths = SimpleNamespace(pano_top=(cm.top_model.panorama.cols,), pano_bot=(cm.bot_model.panorama.cols,))
-        value = _cyclic_columns(True, widths, getattr(tracker, "lk_options", None), bool(getattr(fm, "gated", False)),
-                                getattr(fm, "ratio", None) is not None, LK_MAX_LEVELS)
+        fm, lk = getattr(cm, "feature_matcher_for_motion", None), getattr(tracker, "lk_options", None)
+        value = StepOptions.of(gated_f2f=bool(getattr(fm, "gated", False)), ratio_f2f=getattr(fm, "ratio", None) is not None,
+                               f2f_tracker="match" if lk is None else "lk", lk=lk, cyclic_columns=True,
+                               rig=(cm.top_model.panorama.cols, cm.bot_model.panorama.cols), store_levels=LK_MAX_LEVELS,
+                               order=("lk", "cyclic")).cyclic      # (the engines' check of the width, and only that)
     tracker.cyclic_columns = cm.cyclic_columns = value
 
 
@@ -715,7 +708,6 @@ def set_stereo_refinement(tracker, stereo_refine, stereo_lk=None):
     StereoLKOptions / a dict of its fields.  The static-stereo matcher bootstrap_tracker built carries the setting to the frames,
     so the per-frame mirror path and the engine chosen from the tracker's settings both follow.  An RGB-D tracker has no static
     stereo: "lk" is a ValueError."""
-    from .._lib import stereo_refine_options
     if stereo_refine is None:
         if stereo_lk is not None:
             raise ValueError("stereo_lk settings without stereo_refine=\"lk\"")
@@ -762,26 +754,16 @@ def _sos_engine_settings(tracker, camera_model, first_image):
                     f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     nfeat = tracker.num_features_detection_for_static_stereo
     cap = mirror_kp_cap(method, nfeat)      # as GUMStereo._front_end (the mirror path's capacity)
-    # the two matchers' options (what the mirror path matches with): part of the engine's configuration and of its key.  The
-    # engine has one cap and one ratio for both matchers (as set_gated_matching / set_ratio_test set them)
-    opts = MatchOptions.from_matchers(fm, getattr(om, "feature_matcher_for_motion", None))
-    if opts is None:
+    # the step options (what the mirror path runs) are part of the engine's key; one cap and one ratio serve both its matchers
+    so = StepOptions.from_tracker(tracker, om)
+    if so is None:
         return None
     key = (method, int(nfeat), cap, float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
-           float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model),
-           opts, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None), getattr(fm, "stereo_lk_options", None),
-           bool(getattr(om, "cyclic_columns", False)))
+           float(tracker.percentage_good_matches), tuple(geo[0]), tuple(geo[1]), tuple(top.F[:3, 0]), tuple(bot.F[:3, 0]), id(model), so)
     kwargs = dict(num_of_features=nfeat, kp_cap=cap, frame_cap=4096, median_win_size=11,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
-                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method,
-                  subpix=getattr(fm, "subpix_half", None), **opts._asdict())
-    if getattr(tracker, "lk_options", None) is not None:
-        kwargs.update(f2f_tracker="lk", lk=tracker.lk_options)
-    if getattr(fm, "stereo_lk_options", None) is not None:
-        kwargs.update(stereo_refine="lk", stereo_lk=fm.stereo_lk_options)
-    if getattr(om, "cyclic_columns", False):
-        kwargs.update(cyclic_columns=True)
+                  adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, ransac_solver="GP3P", detection_method=method, **so.kwargs())
     return (model, rig), kwargs, key
 
 
@@ -889,15 +871,15 @@ def _rgbd_engine_settings(tracker, camera_model, first_rgb):
     cam = RGBDCamConfig(cm.fx, cm.fy, cm.center_x, cm.center_y, cm.focal_length_m, cm.depth_is_Z, 0.8, 7.0,
                         f2f_max_hdiff=tracker.max_horizontal_diff_f2f_matches, pct_good_matches=tracker.percentage_good_matches)
     shape = tuple(int(v) for v in np.asarray(first_rgb).shape[:2])
-    opts = MatchOptions.from_matchers(None, fm)
+    so = StepOptions.from_tracker(tracker, cm)
     key = (method, shape, int(tracker.num_features_detection_for_motion), float(tracker.backprojection_score_threshold_3D_to_2D),
            int(tracker.max_ransac_iterations_3D_to_2D), float(tracker.max_horizontal_diff_f2f_matches),
            float(tracker.percentage_good_matches), str(tracker.pose_est_algorithm), float(cm.fx), float(cm.fy), float(cm.center_x),
-           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), opts)
+           float(cm.center_y), float(cm.focal_length_m), bool(cm.depth_is_Z), so)
     kwargs = dict(image_shape=shape, num_of_features=tracker.num_features_detection_for_motion, median_win_size=0,
                   thr=tracker.backprojection_score_threshold_3D_to_2D, max_iter=tracker.max_ransac_iterations_3D_to_2D,
                   adaptive=True, lm_iter=pyopengv.LM_MAX_ITERATIONS, pose_est_algorithm=tracker.pose_est_algorithm,
-                  detection_method=method, **opts.rgbd_kwargs())
+                  detection_method=method, **so.match.rgbd_kwargs())
     return (cam,), kwargs, key
 
 
@@ -1351,30 +1333,12 @@ def run_VO(visualizer_3D_VO, camera_model, gt_poses_filename=None, est_poses_fil
 
     detection_method: "GFT", "ORB", "FAST" or "AGAST" for the tracker and its frames; None = the tracker's own (GFT).
 
-    cross_check: mutual matches only, cv2.BFMatcher's crossCheck (camera_models.py:401).  None = the tracker's own setting
-    (off); True / False = both matchers; "stereo" / "f2f" = the static-stereo / the frame-to-frame matcher alone (see
-    set_cross_check).  Sequence mode and the mirror path follow alike.
-
-    gated_matching: the matchers search among the candidates that pass their pixel gates (the static-stereo gates / the
-    frame-to-frame |du| gate) instead of everywhere; same values as cross_check.  gated_max_distance: None = no cap, or
-    1 .. 256: a match whose Hamming distance exceeds it is no match (see set_gated_matching).  Off by default.
-
-    ratio_test: Lowe's ratio rule in the matchers, evaluated on the device: a match is kept iff its distance is below
-    ratio times the runner-up's (under gated_matching: the runner-up among the admissible candidates); same values as
-    cross_check.  ratio: a float in (0, 1) with ratio * 64 an integer, e.g. 0.75 (see set_ratio_test).  Off by default.
-
-    subpix_refine: the detected keypoints move to their sub-pixel positions before the static-stereo matching (the
-    descriptors stay those of the detector's positions); None = the tracker's own setting (off), True / False.
-    subpix_half: the window half-size 2 .. 5, None = 5 (see set_subpixel_refinement).  Sequence mode and the mirror path
-    follow alike; an RGB-D camera model refuses True.
-
-    f2f_tracker: None = the tracker's own setting ("match"), "match" = the frame-to-frame correspondences come from the
-    descriptor matcher, "lk" = the reference frame's stereo points are tracked into the current frame's gray panoramas by
-    pyramidal Lucas-Kanade (see set_f2f_tracker); lk: its settings, None / an LKOptions / a dict of its fields.  Sequence mode
-    and the mirror path follow alike; an RGB-D camera model refuses "lk", and so does a frame-to-frame matcher option.
-    stereo_refine: None = the tracker's own setting (off), "lk" = sub-pixel static stereo: the bottom keypoint of every matched
-    top / bottom pair is tracked from the top panorama into the bottom one (see set_stereo_refinement); stereo_lk: its
-    settings, None / a StereoLKOptions / a dict of its fields.  An RGB-D camera model refuses "lk"."""
+    cross_check, gated_matching / gated_max_distance, ratio_test / ratio, subpix_refine / subpix_half, f2f_tracker / lk,
+    stereo_refine / stereo_lk, cyclic_columns: the step options.  Each is None = the tracker's own setting (off; "match"), or
+    what its setter takes and describes: set_cross_check (True / False = both matchers, "stereo" / "f2f" = the static-stereo /
+    the frame-to-frame matcher alone), set_gated_matching and set_ratio_test (the same values), set_subpixel_refinement,
+    set_f2f_tracker, set_stereo_refinement, set_cyclic_columns.  Sequence mode and the mirror path follow alike.  An RGB-D
+    camera model has the frame-to-frame matcher only: it refuses "stereo", sub-pixel keypoints, "lk" and cyclic columns."""
     from .common_cv import get_images
     if visualizer_3D_VO is not None:
         raise NotImplementedError("3-D visualisation is not built: pass visualizer_3D_VO=None")

@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import LK_MAX_LEVELS, LKOptions, MatchOptions, f2f_tracker_options, stereo_refine_options, subpix_flags, subpix_half
+from ._lib import LK_MAX_LEVELS, StepOptions, detector_code, rgbd_detector_flags
 from .device import Context, make_rig
 
 
@@ -29,34 +29,6 @@ class RigConfig(object):
     def as_struct(self):
         return make_rig(self.pano_top, self.pano_bot, self.F_top, self.F_bot, self.min_range, self.max_range,
                         self.stereo_min_disp, self.stereo_max_hdiff, self.f2f_max_hdiff, self.pct_good_matches)
-
-
-def _no_cyclic_columns(cyclic_columns):
-    if cyclic_columns:
-        raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
-
-
-def _cyclic_columns(cyclic_columns, rig, lk, gated_f2f, ratio_f2f, store_levels=None):
-    """The `cyclic_columns` argument checked against the rig and the frame-to-frame settings -> bool.  lk: the tracker's
-    LKOptions or None.  store_levels: the levels a frame store keeps whatever the settings (the batched engines:
-    SOSVO_LK_MAX_LEVELS), None for the pair pipeline, which builds the levels it tracks on."""
-    if not cyclic_columns:
-        return False
-    widths = (rig.pano_top[0], rig.pano_bot[0])
-    for w in widths:
-        if not (w == int(w) and 1 <= w <= 16384):
-            raise ValueError("cyclic_columns: the panorama width must be a positive integer up to 16384, got %r" % (w,))
-    if lk is not None:
-        for w in widths:
-            levels = max(lk.levels, store_levels or 1)
-            if int(w) % (1 << (levels - 1)) or (int(w) >> (lk.levels - 1)) < 2 * lk.half + 3:
-                raise ValueError("cyclic_columns with f2f_tracker=\"lk\": a panorama width of %d columns is no multiple of %d, or "
-                                 "its top level is narrower than the %d-column template" % (w, 1 << (levels - 1), 2 * lk.half + 3))
-    if gated_f2f and ratio_f2f:
-        raise ValueError("cyclic_columns: the ratio form of the gated frame-to-frame matcher has no cyclic gate")
-    if gated_f2f and widths[0] != widths[1]:
-        raise ValueError("cyclic_columns with gated_f2f: one search serves both views, their widths must be equal (%r, %r)" % widths)
-    return True
 
 
 class FramePairPipeline(object):
@@ -91,24 +63,15 @@ class FramePairPipeline(object):
         pyramids and the tracker are cyclic too (cols a multiple of 2^(levels - 1), the top level at least 2 half + 3 columns
         wide).  The period is the rig's pano_top[0] / pano_bot[0]."""
         assert isinstance(ctx, Context)
-        self.cyclic = _cyclic_columns(cyclic_columns, rig, LKOptions.of(lk) if f2f_tracker == "lk" else None, gated_f2f, ratio_f2f)
-        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
-        if self.stereo_lk is not None and front_end is None:
-            raise ValueError("stereo_refine=\"lk\" needs a front end: the refinement reads the gray panoramas")
-        if f2f_tracker not in ("match", "lk"):
-            raise ValueError("f2f_tracker: \"match\" or \"lk\", got %r" % (f2f_tracker,))
-        if f2f_tracker == "lk" and front_end is None:
-            raise ValueError("f2f_tracker=\"lk\" needs a front end: the tracker reads the gray panoramas")
-        if f2f_tracker != "lk" and lk is not None:
-            raise ValueError("lk settings without f2f_tracker=\"lk\"")
-        self.f2f_tracker, self.lk = f2f_tracker, LKOptions.of(lk) if f2f_tracker == "lk" else None
+        # (ValueError for a value out of range, settings without their switch, a width that cannot be cyclic, what reads the gray
+        # panoramas without a front end.  This tracker has never refused the options of the matcher it replaces)
+        so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
+                            order=StepOptions.PAIR_ORDER, tracker_sees_match=False, gray=front_end is not None)
+        self.opts = o = so.match
+        self.lk, self.stereo_lk, self.cyclic, self.f2f_tracker = so.lk, so.stereo_lk, so.cyclic, f2f_tracker
         if subpix is not None:
-            if front_end is None:
-                raise ValueError("subpix needs a front end: the refinement reads the gray panoramas")
-            front_end.subpix = subpix_half(subpix)
-        # (ValueError for a cap out of range, a ratio that is no 64th)
-        self.opts = o = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance,
-                                     ratio_stereo, ratio_f2f, ratio)
+            front_end.subpix = so.subpix
         self.ctx, self.rig_cfg, self.rig = ctx, rig, rig.as_struct()
         self.front_end = front_end
         if front_end is not None:
@@ -163,7 +126,7 @@ class FramePairPipeline(object):
         self._q2, self._t2, self._k2 = q[: 2 * self.B], t[: 2 * self.B], self._k[: 2 * self.B]     # the forward problems
         self._f2f_search = dict(ratio_64ths=o.ratio_64ths_f2f, rivals=torch.zeros_like(self._k) if o.ratio_f2f else None,
                                 gate=(-1.0, rig.f2f_max_hdiff, gated_max_distance) if o.gated_f2f else None)
-        if self.cyclic and o.gated_f2f:    # (one search serves both views: _cyclic_columns checked that their widths agree)
+        if self.cyclic and o.gated_f2f:    # (one search serves both views: StepOptions.of checked that their widths agree)
             self._f2f_search["period"] = float(rig.pano_top[0])
         self._cyc = dict(cyclic=True) if self.cyclic else {}     # (off: the assembles are called as they always were)
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
@@ -287,18 +250,17 @@ class OverlappedFramePairs(object):
                  frame_cap=2048, max_iter=2000, adaptive=False, seed=0, detection_method="GFT", lm_iter=30, thr=None,
                  serialize_medians=True, ransac_solver="P3P", median_win_size=11, cross_check_stereo=False,
                  cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None,
+                 cyclic_columns=False):
         """median_win_size: StereoPanoramicFrame.median_win_size (11, pose_est_tools.py:296); 0 = no median blur (the
         RGB-D frames' setting, :427) -- then the colour panoramas are materialised and only converted to gray.
-        f2f_tracker / lk: as FramePairPipeline ("lk": every part's pipeline tracks with these settings).
-        stereo_refine / stereo_lk: as FramePairPipeline, in every part."""
+        cross_check_stereo ... cyclic_columns: as FramePairPipeline, in every part; a frame-to-frame matcher option with
+        f2f_tracker="lk" raises ValueError."""
         from .frontend import DeviceImageModel, ImageFrontEnd
         from .parallel import shard_range
-        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                            ratio_f2f, ratio)
-        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
-        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
-        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, gated_f2f, ratio_f2f)      # (before the device is touched)
+        so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig)
+        self.lk, self.stereo_lk, self.cyclic = so.lk, so.stereo_lk, so.cyclic      # (checked before the device is touched)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
@@ -322,9 +284,7 @@ class OverlappedFramePairs(object):
                                      median_win_size=median_win_size, subpix=subpix)
                 p.pipe = FramePairPipeline(p.ctx, rig, hi - lo, frame_cap=frame_cap, max_iter=max_iter, adaptive=adaptive,
                                            seed=seed + lo, front_end=p.fe, lm_iter=lm_iter, thr=thr,
-                                           ransac_solver=ransac_solver, f2f_tracker=f2f_tracker, lk=self.lk,
-                                           stereo_refine=stereo_refine, stereo_lk=self.stereo_lk,
-                                           **(dict(cyclic_columns=True) if self.cyclic else {}), **opts._asdict())
+                                           ransac_solver=ransac_solver, **so.kwargs())
             p.median_done = torch.cuda.Event()
             p.done = torch.cuda.Event()
             self.parts.append(p)
@@ -452,15 +412,12 @@ class OverlappedFramePairs(object):
         self.main.close()
 
 
-def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
-              adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
-              gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
-              subpix=None, lk=None, stereo_lk=None, cyclic_columns=False):
-    """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call).
+def _batch_cfg(so, model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
+               adaptive, seed, lm_iter, ransac_solver, detection_method):
+    """The `sosvo_batch_cfg` of FramePairBatch and SequenceEngine (n_pairs: pairs per call / slot pairs per tracking call) for
+    the StepOptions `so` (its flags(); the settings of so.lk / so.stereo_lk belong to the context, see use_lk_options).
     kp_cap None = the detector's default capacity (frontend.default_kp_cap); thr None = the trackers' 5-degree threshold;
-    any ransac_solver but "GP3P" is P3P.  lk: None, or the LKOptions of an engine that tracks (SOSVO_FLAG_LK_F2F; the
-    settings themselves belong to the context, see use_lk_options).  stereo_lk: None, or the StereoLKOptions of an engine
-    that refines its static stereo (SOSVO_FLAG_LK_STEREO; the settings belong to the context likewise)."""
+    any ransac_solver but "GP3P" is P3P."""
     from . import _lib, orb_pattern
     from .frontend import default_kp_cap
     detector = _lib.detector_code(detection_method)
@@ -475,27 +432,31 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     c.quality, c.min_distance = float(quality), float(min_distance)
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
-    c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0), detector
-    c.ransac_flags |= MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                                   ratio_f2f, ratio).flags()
-    c.ransac_flags |= subpix_flags(subpix)
-    if lk is not None:
-        c.ransac_flags |= _lib.FLAG_LK_F2F
-    if stereo_lk is not None:
-        c.ransac_flags |= _lib.FLAG_LK_STEREO
-    if cyclic_columns:    # (checked by the caller: _cyclic_columns)
-        c.ransac_flags |= _lib.FLAG_CYCLIC_F2F
+    c.ransac_flags, c.detector = (_lib.FLAG_GP3P if str(ransac_solver).upper() == "GP3P" else 0) | so.flags(), detector
     return c
 
 
-def use_lk_options(ctx, lk, stereo_lk=None):
-    """Before a call of an engine that tracks with the settings `lk` (None: it matches, nothing to do) or refines its static
-    stereo with the settings `stereo_lk` (None: it does not): contexts are shared between engines, so the context gets them
+def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter,
+              adaptive, seed, lm_iter, ransac_solver, detection_method, cross_check_stereo=False, cross_check_f2f=False,
+              gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
+              subpix=None, lk=None, stereo_lk=None, cyclic_columns=False):
+    """_batch_cfg with the options by name.  lk / stereo_lk: None, or the LKOptions / StereoLKOptions of an engine that tracks /
+    refines its static stereo; what options go together is the caller's to check (StepOptions.of)."""
+    detector_code(detection_method)      # (refused before a bad option, as ever)
+    so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f,
+                        ratio, subpix, order=("match", "subpix"))._replace(lk=lk, stereo_lk=stereo_lk, cyclic=bool(cyclic_columns))
+    return _batch_cfg(so, model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr,
+                      max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method)
+
+
+def use_lk_options(ctx, so):
+    """Before a call of an engine with the StepOptions `so` that tracks (so.lk; None: it matches, nothing to do) or refines its
+    static stereo (so.stereo_lk; None: it does not): contexts are shared between engines, so the context gets the settings
     whenever they differ from what it was last given."""
-    if lk is not None and getattr(ctx, "lk_options", None) != lk:
-        ctx.set_lk_options(lk)
-    if stereo_lk is not None and getattr(ctx, "stereo_lk_options", None) != stereo_lk:
-        ctx.set_stereo_lk_options(stereo_lk)
+    if so.lk is not None and getattr(ctx, "lk_options", None) != so.lk:
+        ctx.set_lk_options(so.lk)
+    if so.stereo_lk is not None and getattr(ctx, "stereo_lk_options", None) != so.stereo_lk:
+        ctx.set_stereo_lk_options(so.stereo_lk)
 
 
 class FramePairBatch(object):
@@ -505,27 +466,23 @@ class FramePairBatch(object):
     def __init__(self, ctx, model, rig, n_pairs, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False, seed=0, lm_iter=30,
                  n_streams=1, ransac_solver="P3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
+                 subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         """n_streams > 1: sosvo_frame_pair_batch_streams (the batch split over internal HIP streams of the library).
         detection_method: "GFT", "ORB", "FAST" or "AGAST" -- the stages ImageFrontEnd runs for it; kp_cap None = its
         default capacity (frontend.default_kp_cap).
-        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement (SOSVO_FLAG_SUBPIX).
-        f2f_tracker / lk: as FramePairPipeline -- "lk": SOSVO_FLAG_LK_F2F, the reference frames' points are tracked into the
-        current frames' gray panoramas; a frame-to-frame matcher option with it raises ValueError.
-        stereo_refine / stereo_lk: as FramePairPipeline -- "lk": SOSVO_FLAG_LK_STEREO."""
+        cross_check_stereo ... cyclic_columns: as FramePairPipeline (the SOSVO_FLAG_* bits of cfg.ransac_flags), but subpix
+        None = off, and a frame-to-frame matcher option with f2f_tracker="lk" raises ValueError."""
+        so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
+                            store_levels=LK_MAX_LEVELS)
+        self.options, self.lk, self.stereo_lk, self.cyclic = so, so.lk, so.stereo_lk, so.cyclic
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
-        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                            ratio_f2f, ratio)
-        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
-        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
-        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, gated_f2f, ratio_f2f, LK_MAX_LEVELS)
-        self.cfg = c = batch_cfg(model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
-                                 median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
-                                 max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                 detection_method=detection_method, subpix=subpix, lk=self.lk, stereo_lk=self.stereo_lk,
-                                 **(dict(cyclic_columns=True) if self.cyclic else {}), **opts._asdict())
+        self.cfg = c = _batch_cfg(so, model, self.B, num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
+                                  median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
+                                  max_iter=max_iter, adaptive=adaptive, seed=seed, lm_iter=lm_iter, ransac_solver=ransac_solver,
+                                  detection_method=detection_method)
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
@@ -543,7 +500,7 @@ class FramePairBatch(object):
     def step(self):
         """-> results [B,16] f64 (asynchronous)."""
         m = self.model
-        use_lk_options(self.ctx, self.lk, self.stereo_lk)
+        use_lk_options(self.ctx, self.options)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out, n_streams=self.n_streams)
 
@@ -552,7 +509,7 @@ class FramePairBatch(object):
         the library's internal streams.  Pass alternating `results` buffers while something still reads the previous
         step's records; call join() before reading records on the context's stream."""
         m = self.model
-        use_lk_options(self.ctx, self.lk, self.stereo_lk)
+        use_lk_options(self.ctx, self.options)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out if results is None else results, n_streams=self.n_streams,
                                          join=self.n_streams <= 1)
@@ -654,18 +611,13 @@ class _SequenceFamily(object):
 class _OmniFamily(_SequenceFamily):
     prefix, shared = "sequence_", ("ctx", "cfg", "method", "workspace", "model", "rig_cfg", "rig")
 
-    def __init__(self, ctx, model, rig, frames, slots, gather, opts, f2f_tracker="match", lk=None, stereo_refine=None,
-                 stereo_lk=None, cyclic_columns=False, **settings):
-        """opts: a MatchOptions; f2f_tracker / lk, stereo_refine / stereo_lk: as FramePairPipeline's; settings: batch_cfg's tracker settings
-        (num_of_features ... detection_method) but the seed."""
+    def __init__(self, ctx, model, rig, frames, slots, gather, so, **settings):
+        """so: the engine's StepOptions; settings: _batch_cfg's tracker settings (num_of_features ... detection_method) but the seed."""
         assert isinstance(ctx, Context)
         self.model, self.rig_cfg, self.rig = model, rig, rig.as_struct()
         self.heads = self.track_heads = (self.rig,)
-        self.lk = f2f_tracker_options(f2f_tracker, lk, opts)
-        self.stereo_lk = stereo_refine_options(stereo_refine, stereo_lk)
-        self.cyclic = _cyclic_columns(cyclic_columns, rig, self.lk, opts.gated_f2f, opts.ratio_f2f, LK_MAX_LEVELS)
-        self.cfg = batch_cfg(model, frames, seed=0, lk=self.lk, stereo_lk=self.stereo_lk,
-                             **(dict(cyclic_columns=True) if self.cyclic else {}), **settings, **opts._asdict())
+        self.options, self.lk, self.stereo_lk, self.cyclic = so, so.lk, so.stereo_lk, so.cyclic
+        self.cfg = _batch_cfg(so, model, frames, seed=0, **settings)
         self.method = str(settings["detection_method"]).upper()
         if str(settings["ransac_solver"]).upper() not in ("P3P", "GP3P"):
             raise ValueError("ransac_solver: P3P or GP3P")
@@ -680,7 +632,7 @@ class _OmniFamily(_SequenceFamily):
     def _call(self, name, heads, *args):
         """Engines that share a context may track with different settings: every device call of a tracking family runs under
         its own (the front end builds, the copies move and the tracker reads the pyramid levels they name)."""
-        use_lk_options(self.ctx, self.lk, self.stereo_lk)
+        use_lk_options(self.ctx, self.options)
         return super()._call(name, heads, *args)
 
     @staticmethod
@@ -692,13 +644,13 @@ class _RGBDFamily(_SequenceFamily):
     prefix, track_heads = "rgbd_sequence_", ()
     shared = ("ctx", "cfg", "method", "workspace", "cam_cfg", "cam", "mask_bits", "pattern")
 
-    def __init__(self, ctx, cam, frames, slots, gather, opts, mask, **settings):
-        """opts: a MatchOptions; settings: rgbd_batch_cfg's tracker settings (image_shape ... detection_method) but the seed."""
+    def __init__(self, ctx, cam, frames, slots, gather, so, mask, **settings):
+        """so: the engine's StepOptions; settings: _rgbd_batch_cfg's tracker settings (image_shape ... detection_method) but the seed."""
         from . import orb_pattern
         assert isinstance(ctx, Context)
         self.cam_cfg, self.cam = cam, cam.as_struct()
         self.heads = (self.cam,)
-        self.cfg = c = rgbd_batch_cfg(cam, frames, seed=0, **settings, **opts.rgbd_kwargs())
+        self.cfg = c = _rgbd_batch_cfg(so, cam, frames, seed=0, **settings)
         self.method = str(settings["detection_method"]).upper()
         rows, cols = c.rows, c.cols
         mb = np.ones((1, rows, cols), np.uint32) if mask is None else (np.asarray(mask) != 0).astype(np.uint32).reshape(1, rows, cols)
@@ -964,26 +916,20 @@ class SequenceEngine(_SequenceBase):
     def __init__(self, ctx, model, rig, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
+                 subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         """Defaults: the trackers' settings (pose_est_tools.py:672-707: 5-degree threshold, the iteration budget of
         compute_num_of_iterations_RANSAC = 210 with the adaptive stop, generalised P3P; LM 30 iterations).
-        detection_method: "GFT", "ORB", "FAST" or "AGAST", as FramePairBatch.
-        cross_check_stereo / cross_check_f2f: mutual matches only in the static-stereo / the frame-to-frame matcher.
-        gated_stereo / gated_f2f / gated_max_distance: the search under the pixel gates, as FramePairPipeline.
-        subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel keypoint refinement, as FramePairBatch.
-        f2f_tracker / lk: "lk" = Lucas-Kanade tracking in place of the frame-to-frame matcher, as FramePairBatch; the store
-        then keeps every frame's gray panoramas and their pyramid.
-        stereo_refine / stereo_lk: "lk" = sub-pixel static stereo (SOSVO_FLAG_LK_STEREO), as FramePairBatch."""
+        detection_method and cross_check_stereo ... cyclic_columns: as FramePairBatch; with f2f_tracker="lk" the store keeps
+        every frame's gray panoramas and their pyramid."""
+        so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
+                            store_levels=LK_MAX_LEVELS)
         self._init_windows(window)
-        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                            ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, opts, f2f_tracker, lk, stereo_refine, stereo_lk,
-                                cyclic_columns,
-                                num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
-                                median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
-                                max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                detection_method=detection_method, subpix=subpix))
+        self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, so, num_of_features=num_of_features, kp_cap=kp_cap,
+                                frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                                edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                                ransac_solver=ransac_solver, detection_method=detection_method))
 
 
 def rgbd_solver_flags(pose_est_algorithm):
@@ -1105,12 +1051,11 @@ class RGBDPairPipeline(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None):
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False,
+                 gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None):
         """detection_method: "GFT", "ORB", "FAST" or "AGAST" (RGBDFrontEnd).
-        cross_check: mutual matches only (cv2.BFMatcher's crossCheck, camera_models.py:401) in feature_matcher_for_motion.
-        gated_f2f: the matcher searches among the keypoints within the tracker's |du| gate (Context.match_hamming_gated);
-        gated_max_distance: None = no cap, or 1 .. 256.
+        cross_check, gated_f2f ... ratio: FramePairPipeline's cross_check_f2f, gated_f2f ... ratio, in the one matcher of an
+        RGB-D camera (feature_matcher_for_motion; the gate is the tracker's |du| gate).
         pose_est_algorithm: TrackerSE3.pose_est_algorithm (pose_est_tools.py:697): "EPNP" = 6-point samples solved by
         EPnP; "KNEIP" = P3P on 3 points + a 4th for disambiguation; "GAO" / "GP3P" = the depth formulation through the
         generalised solver; "TWOPT" = translation from 2 points.  Anything else raises ValueError."""
@@ -1131,7 +1076,7 @@ class RGBDPairPipeline(object):
         self.cur_frame = torch.arange(1, F, 2, dtype=torch.int32, device=dev)
         self.order = z((B, Fc), torch.int32)
         # (ValueError for a cap out of range, a ratio that is no 64th)
-        self.opts = o = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
+        self.opts = o = StepOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio).match
         q, t = self.cur_frame, self.ref_frame
         if o.cross_check_f2f:   # the B role-swapped problems ride in the same launch, after the forward ones
             q, t = torch.cat([q, t]), torch.cat([t, q])
@@ -1184,12 +1129,11 @@ class RGBDPairPipeline(object):
         return out
 
 
-def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
-                   thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check=False, gated_f2f=False,
-                   gated_max_distance=None, ratio_f2f=False, ratio=None):
+def _rgbd_batch_cfg(so, cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                    thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method):
     """The `sosvo_rgbd_batch_cfg` of RGBDPairBatch and RGBDSequenceEngine (n_pairs: pairs per call / slot pairs per tracking
-    call; cam: an RGBDCamConfig).  kp_cap None or 0 = rgbd_kp_cap; frame_cap None or 0 = kp_cap; thr None = the trackers'
-    5-degree threshold."""
+    call; cam: an RGBDCamConfig) for the StepOptions `so` (StepOptions.rgbd).  kp_cap None or 0 = rgbd_kp_cap; frame_cap None
+    or 0 = kp_cap; thr None = the trackers' 5-degree threshold."""
     from . import _lib, orb_pattern
     detector_flags = _lib.rgbd_detector_flags(detection_method)
     kp_cap = int(kp_cap) if kp_cap else rgbd_kp_cap(str(detection_method).upper(), num_of_features)
@@ -1199,13 +1143,22 @@ def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap
     c.kp_cap, c.frame_cap = kp_cap, int(frame_cap) if frame_cap else kp_cap
     c.median_ksize, c.max_corners, c.edge = int(median_win_size), int(num_of_features), int(edge)
     c.ransac_max_iter, c.ransac_adaptive, c.lm_max_iter = int(max_iter), 1 if adaptive else 0, int(lm_iter)
-    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags
-    c.flags |= MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio).flags()
+    c.flags = rgbd_solver_flags(pose_est_algorithm) | detector_flags | so.flags()
     c.quality, c.min_distance = float(quality), float(min_distance)
     c.ransac_threshold = float(1.0 - np.cos(np.deg2rad(5.0))) if thr is None else float(thr)
     c.pct_good_matches, c.f2f_max_hdiff = float(cam.pct_good_matches), float(cam.f2f_max_hdiff)
     c.seed, c.cos_a, c.sin_a = int(seed), float(cos_a), float(sin_a)
     return c
+
+
+def rgbd_batch_cfg(cam, n_pairs, image_shape, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge,
+                   thr, max_iter, adaptive, seed, lm_iter, pose_est_algorithm, detection_method, cross_check=False, gated_f2f=False,
+                   gated_max_distance=None, ratio_f2f=False, ratio=None):
+    """_rgbd_batch_cfg with the options by name."""
+    rgbd_detector_flags(detection_method), rgbd_solver_flags(pose_est_algorithm)      # (refused before a bad option, as ever)
+    return _rgbd_batch_cfg(StepOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio), cam, n_pairs, image_shape,
+                           num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr, max_iter, adaptive,
+                           seed, lm_iter, pose_est_algorithm, detection_method)
 
 
 class RGBDPairBatch(object):
@@ -1214,20 +1167,18 @@ class RGBDPairBatch(object):
 
     def __init__(self, ctx, cam, n_pairs, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=2000, adaptive=False,
-                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+                 seed=0, lm_iter=30, mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False,
+                 gated_f2f=False, gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None,
+                 stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         from . import orb_pattern
-        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
-        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
-        _no_cyclic_columns(cyclic_columns)
+        so = StepOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio, f2f_tracker, lk, stereo_refine, stereo_lk,
+                              cyclic_columns)      # (a tracker, a stereo refinement, cyclic columns: ValueError)
         self.ctx, self.cam_cfg, self.cam = ctx, cam, cam.as_struct()
         self.B = int(n_pairs)
-        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
-        c = rgbd_batch_cfg(cam, self.B, seed=seed, image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
-                           frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
-                           edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
-                           pose_est_algorithm=pose_est_algorithm, detection_method=detection_method,
-                           **opts.rgbd_kwargs())
+        c = _rgbd_batch_cfg(so, cam, self.B, seed=seed, image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
+                            frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                            edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                            pose_est_algorithm=pose_est_algorithm, detection_method=detection_method)
         self.method = str(detection_method).upper()
         rows, cols = c.rows, c.cols
         self.cfg, self.thr = c, c.ransac_threshold
@@ -1266,13 +1217,12 @@ class RGBDSequenceEngine(_SequenceBase):
     def __init__(self, ctx, cam, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
-        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
-        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
-        _no_cyclic_columns(cyclic_columns)
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None,
+                 stereo_lk=None, cyclic_columns=False):
+        so = StepOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio, f2f_tracker, lk, stereo_refine, stereo_lk,
+                              cyclic_columns)      # (a tracker, a stereo refinement, cyclic columns: ValueError)
         self._init_windows(window)
-        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
-        self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, opts, mask,
+        self._adopt(_RGBDFamily(ctx, cam, self.W, self.slots, False, so, mask,
                                 image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
                                 frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
                                 edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
@@ -1603,17 +1553,16 @@ class MultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, model, rig, lanes=2, window=32, num_of_features=1000, kp_cap=None, frame_cap=2048, median_win_size=11,
                  quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  ransac_solver="GP3P", detection_method="GFT", cross_check_stereo=False, cross_check_f2f=False,
-                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False,
-                 ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+                 gated_stereo=False, gated_f2f=False, gated_max_distance=None, ratio_stereo=False, ratio_f2f=False, ratio=None,
+                 subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
+        so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
+                            store_levels=LK_MAX_LEVELS)
         self._init_lanes(lanes, window)
-        opts = MatchOptions(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                            ratio_f2f, ratio)
-        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, opts, f2f_tracker, lk, stereo_refine,
-                                stereo_lk, cyclic_columns,
-                                num_of_features=num_of_features, kp_cap=kp_cap, frame_cap=frame_cap,
-                                median_win_size=median_win_size, quality=quality, min_distance=min_distance, edge=edge, thr=thr,
-                                max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter, ransac_solver=ransac_solver,
-                                detection_method=detection_method, subpix=subpix))
+        self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, so, num_of_features=num_of_features, kp_cap=kp_cap,
+                                frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
+                                edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
+                                ransac_solver=ransac_solver, detection_method=detection_method))
 
 
 class RGBDMultiSequenceEngine(_MultiSequenceBase):
@@ -1623,13 +1572,12 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
     def __init__(self, ctx, cam, lanes=2, window=32, image_shape=(480, 640), num_of_features=1000, kp_cap=None, frame_cap=None,
                  median_win_size=0, quality=0.01, min_distance=5.0, edge=31, thr=None, max_iter=210, adaptive=True, lm_iter=30,
                  mask=None, pose_est_algorithm="EPNP", detection_method="GFT", cross_check=False, gated_f2f=False,
-                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
-        f2f_tracker_options(f2f_tracker, lk, rgbd=True)   # ("lk": ValueError)
-        stereo_refine_options(stereo_refine, stereo_lk, rgbd=True)   # ("lk": ValueError)
-        _no_cyclic_columns(cyclic_columns)
+                 gated_max_distance=None, ratio_f2f=False, ratio=None, f2f_tracker="match", lk=None, stereo_refine=None,
+                 stereo_lk=None, cyclic_columns=False):
+        so = StepOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio, f2f_tracker, lk, stereo_refine, stereo_lk,
+                              cyclic_columns)      # (a tracker, a stereo refinement, cyclic columns: ValueError)
         self._init_lanes(lanes, window)
-        opts = MatchOptions.rgbd(cross_check, gated_f2f, gated_max_distance, ratio_f2f, ratio)
-        self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, opts, mask,
+        self._adopt(_RGBDFamily(ctx, cam, self.window, self.slots, True, so, mask,
                                 image_shape=image_shape, num_of_features=num_of_features, kp_cap=kp_cap,
                                 frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
                                 edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
