@@ -58,6 +58,9 @@ def build_parser():
     parser.add_argument("--cyclic_columns", action="store_true",
                         help="the panoramas are full circles: the frame-to-frame |du| gate (and, with --f2f_tracker lk, the pyramids "
                              "and the tracker) go across the seam between the last and the first column; default: off")
+    parser.add_argument("--seam_free", action="store_true",
+                        help="--cyclic_columns plus the seam-free front end: keypoints and stereo points up to the seam (the image "
+                             "stages run on panoramas padded by 40 cyclic columns on either side); default: off")
     return parser
 
 
@@ -87,7 +90,7 @@ def main_sos_vo_live(argv=None, frame_source=None):
                          ratio_test=None if args.ratio_test is None else (True if args.ratio_test == "both" else args.ratio_test),
                          ratio=args.ratio,
                          subpix_refine=True if args.subpix_refine else None, subpix_half=args.subpix_half, **f2f_tracker_arguments(args),
-                         **stereo_refine_arguments(args), cyclic_columns=True if args.cyclic_columns else None)
+                         **stereo_refine_arguments(args), cyclic_columns="seam_free" if args.seam_free else (True if args.cyclic_columns else None))
     print("GOODBYE!")
     return out
 

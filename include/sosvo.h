@@ -903,6 +903,53 @@ enum sosvo_detector { SOSVO_DETECTOR_GFT = 0, SOSVO_DETECTOR_ORB = 1, SOSVO_DETE
  * workspace sizes with the bit set equal those with it clear (no new buffers), and with the bit clear launches and results
  * are unchanged. */
 #define SOSVO_FLAG_CYCLIC_F2F 0x200
+/* ---- the seam-free front end: keypoints and stereo points up to the panorama seam ------------------
+ * For a panorama P of `cols` columns (one period) and mask bits M, the seam-free front end is BY DEFINITION the plain front end
+ * run on the padded inputs
+ *   pad(P)[:, c']  = P[:, (c' - SOSVO_SEAM_HALO) mod cols]   for c' in [0, cols + 2 * SOSVO_SEAM_HALO)
+ *   pad0(M)        = M in the columns [SOSVO_SEAM_HALO, SOSVO_SEAM_HALO + cols) and 0 in the halo
+ * followed by the UNPAD of every keypoint's x, in float32: x = x' - 40, then + cols if x < 0, then - cols if x >= cols, and a
+ * result equal to cols is written as 0.  Every original pixel is detected exactly once, and every pixel a stage reads for a
+ * keypoint of the original columns is its true cyclic neighbour (the stages read at most about 35 columns around a keypoint;
+ * the padded image's own border artefacts are its outer 5 to 8 columns).  The tuned image kernels are not edited: they run at
+ * cols + 80 columns.  y, descriptors, counts and order are untouched; on the detector's grid (multiples of 1/32) the unpad is exact.
+ * Limit: the greedy minimum distance and the per-mask maximum are not cyclic inside ONE mask that itself straddles the seam.
+ *
+ * The stages (each refuses NULL arguments and sizes out of range with SOSVO_ERR_ARG):
+ *   sosvo_unwrap_prepare_seam_free  table [2, rows, cols + 80, 2] u32: byte for byte what sosvo_unwrap_prepare writes for maps
+ *                                   padded by the rule above (an entry is a function of its map values alone); cols >= 40
+ *   sosvo_mask_bits_seam_free       mask_bits [nsets, rows, cols] u32 -> out [nsets, rows, cols + 80]: pad0
+ *   sosvo_keypoints_unpad           kp [nprob, cap, 2] f32, n [nprob] i32 (device): the unpad rule in place on the first
+ *                                   min(n[p], cap) rows of every problem; the rows beyond are untouched.  period 1 .. 16384
+ *   sosvo_gray_unpad                gray [nimg, rows, cols + 80] u8 -> out [nimg, rows, cols]: the interior columns; row_range as
+ *                                   for sosvo_gauss7 (int32 [2][2] in DEVICE memory, view-major, nimg even; rows outside a view's
+ *                                   range are not written), NULL = all rows
+ *
+ * In the batch and sequence entry points:
+ *   SOSVO_FLAG_SEAM_FREE     sosvo_batch_cfg.ransac_flags (sosvo_frame_pair_batch*, sosvo_sequence_*).  cfg->cols stays the
+ *                            period; the front end runs its image stages at cols + 80 internally and the caller passes the
+ *                            table and mask bits made by the two helpers above.  Detection, description, sub-pixel refinement,
+ *                            static-stereo matching, sort and sosvo_refine_stereo_lk keep padded coordinates (all of them are
+ *                            shift-invariant or read the padded gray); top and bottom keypoints are unpadded as the last thing
+ *                            before the stereo assemble.  A refined pair that ends up straddling the seam fails the plain stereo
+ *                            gate and is dropped (the static-stereo gate is not cyclic).  With SOSVO_FLAG_LK_F2F level 0 of the
+ *                            store is the interior crop, so a pair batch no longer uses the front end's buffer in place and its
+ *                            workspace grows by one level 0.  The tracking step and everything behind it is unchanged.
+ * The flag word is full except for its sign bit, so this IS the int32 sign bit; the next option needs a second word.  The
+ * struct does not grow.  Refused with SOSVO_ERR_ARG and a workspace size of 0: the flag without SOSVO_FLAG_CYCLIC_F2F;
+ * detector ORB (each pyramid level keeps a 31-pixel border of its own, which a 40-column halo covers on level 0 only);
+ * edge > 31; cols < 40 or cols + 80 > 16384; everything SOSVO_FLAG_CYCLIC_F2F refuses; and, at call time (the workspace
+ * functions take no context), SOSVO_FLAG_LK_STEREO settings with 2 + half + ceil(max_shift) > 35 (max_shift 0 = half).
+ * sosvo_rgbd_batch_cfg.flags has no such bit.  With the flag clear launches, buffers and workspace sizes are unchanged. */
+#define SOSVO_SEAM_HALO 40
+#define SOSVO_FLAG_SEAM_FREE ((int32_t)(-2147483647 - 1))
+int32_t sosvo_unwrap_prepare_seam_free(sosvo_ctx* ctx, const uint8_t* masks, const float* map_x, const float* map_y,
+                                       int32_t H, int32_t W, int32_t rows, int32_t cols, uint32_t* table);
+int32_t sosvo_mask_bits_seam_free(sosvo_ctx* ctx, const uint32_t* mask_bits, int32_t nsets, int32_t rows, int32_t cols,
+                                  uint32_t* out);
+int32_t sosvo_keypoints_unpad(sosvo_ctx* ctx, float* kp, const int32_t* n, int32_t nprob, int32_t cap, int32_t period);
+int32_t sosvo_gray_unpad(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,
+                         const int32_t* row_range, uint8_t* out);
 typedef struct sosvo_lk_options {
   int32_t half, levels, max_iter, reserved;
   double eps, min_eig, fb_max;

@@ -53,6 +53,10 @@ SIGNATURES = {
     "sosvo_profile_get": (c_i32, [c_p, c_i32, ctypes.c_char_p, c_i32, ctypes.POINTER(c_f32)]),
     "sosvo_unwrap": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_unwrap_prepare": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_unwrap_prepare_seam_free": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_mask_bits_seam_free": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_keypoints_unpad": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32]),
+    "sosvo_gray_unpad": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_unwrap_table": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_median_gray": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_unwrap_median_gray": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
@@ -170,6 +174,10 @@ SUBPIX_EPS = 0.01
 FLAG_LK_F2F = 0x80                 # Lucas-Kanade tracking in place of the frame-to-frame matcher (sosvo_batch_cfg.ransac_flags)
 FLAG_LK_STEREO = 0x100             # sub-pixel static stereo: sosvo_refine_stereo_lk in the front end (sosvo_batch_cfg.ransac_flags)
 FLAG_CYCLIC_F2F = 0x200            # cyclic panorama columns frame to frame (sosvo_batch_cfg.ransac_flags only: DESIGN.md section 34)
+FLAG_SEAM_FREE = -0x80000000       # the seam-free front end: the int32 sign bit, the word's last free one
+SEAM_HALO = 40                     # SOSVO_SEAM_HALO: the cyclic columns a seam-free front end pads on either side
+SEAM_REACH = 35                    # columns a stage may read around a keypoint of the original columns
+SEAM_FREE = "seam_free"            # the third value of cyclic_columns: True plus the seam-free front end
 LK_INITIAL_FLOW = 1                # SOSVO_LK_INITIAL_FLOW: next_pts holds the starting guess on entry
 LK_CYCLIC_COLUMNS = 4              # SOSVO_LK_CYCLIC_COLUMNS: the columns are one period (a panorama is a full circle)
 LK_MAX_HALF, LK_MAX_LEVELS, LK_MAX_ITER, LK_MAX_CAP = 10, 4, 30, 4096
@@ -424,6 +432,33 @@ def f2f_tracker_options(f2f_tracker, lk, opts=None, rgbd=False):
     return LKOptions.of(lk)
 
 
+def cyclic_value(cyclic_columns):
+    """A `cyclic_columns` argument -> False, True or SEAM_FREE ("seam_free": True plus the seam-free front end).  Anything but
+    the string is taken by its truth, as it always was."""
+    if isinstance(cyclic_columns, str):
+        if cyclic_columns != SEAM_FREE:
+            raise ValueError("cyclic_columns: False, True or \"seam_free\", got %r" % (cyclic_columns,))
+        return SEAM_FREE
+    return bool(cyclic_columns)
+
+
+def seam_free_check(cols, detection_method="GFT", edge=31, stereo_lk=None):
+    """What SOSVO_FLAG_SEAM_FREE asks of the shape and the detector (the C layer's refusals, before the device is asked
+    anything): a width of 40 .. 16304 columns, no ORB detector, edge <= 31, stereo-LK windows inside the halo's clean columns."""
+    for w in cols if isinstance(cols, (tuple, list)) else (cols,):
+        if not (w == int(w) and SEAM_HALO <= w and w + 2 * SEAM_HALO <= 16384):
+            raise ValueError("cyclic_columns=\"seam_free\": the panorama width must be an integer in %d .. %d, got %r"
+                             % (SEAM_HALO, 16384 - 2 * SEAM_HALO, w))
+    if str(detection_method).upper() == "ORB":
+        raise ValueError("cyclic_columns=\"seam_free\": the ORB detector's pyramid levels keep borders of their own, which the "
+                         "%d-column halo covers on level 0 only" % SEAM_HALO)
+    if edge > 31:
+        raise ValueError("cyclic_columns=\"seam_free\" needs edge <= 31, got %r" % (edge,))
+    if stereo_lk is not None and 2 + stereo_lk.half + -(-stereo_lk.bound // 1) > SEAM_REACH:
+        raise ValueError("cyclic_columns=\"seam_free\" with stereo_refine=\"lk\": 2 + half + ceil(max_shift) must be <= %d, got "
+                         "half %d, max_shift %r" % (SEAM_REACH, stereo_lk.half, stereo_lk.bound))
+
+
 def gray_pyramid_bytes(nimg, rows, cols, levels):
     """sosvo_gray_pyramid_bytes: bytes of the levels 1 .. levels - 1 of nimg images (host call, no GPU)."""
     out = ctypes.c_int64(0)
@@ -491,8 +526,8 @@ class MatchOptions(namedtuple("MatchOptions", "cross_check_stereo cross_check_f2
 class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic")):
     """Everything a step can be told, as ONE value: `match` a MatchOptions; `subpix` the window half-size 2 .. 5 of the sub-pixel
     keypoint refinement or None; `lk` the LKOptions of a step that tracks frame to frame, None for one that matches;
-    `stereo_lk` the StereoLKOptions of one that refines its static stereo, or None; `cyclic`: the panorama columns are one
-    period.  Every public constructor builds one from its own arguments first (of() / rgbd() run the checks) and uses it from
+    `stereo_lk` the StereoLKOptions of one that refines its static stereo, or None; `cyclic`: False, True (the panorama columns are one
+    period) or "seam_free" (True plus the seam-free front end).  Every public constructor builds one from its own arguments first (of() / rgbd() run the checks) and uses it from
     there, down to flags().  Hashable: its own engine-cache key.  A new option is a field here, a public keyword and its C flag."""
     __slots__ = ()
     # of()'s checks in the order the pair pipeline and the batched layers have always run them: of two broken rules the first
@@ -501,24 +536,30 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
     BATCH_ORDER = ("match", "tracker", "stereo_lk", "cyclic", "subpix")
 
     def __new__(cls, match=None, subpix=None, lk=None, stereo_lk=None, cyclic=False):
-        return super().__new__(cls, MatchOptions() if match is None else match, subpix_half(subpix), lk, stereo_lk, bool(cyclic))
+        return super().__new__(cls, MatchOptions() if match is None else match, subpix_half(subpix), lk, stereo_lk, cyclic_value(cyclic))
 
     def flags(self):
         """The options' bits of sosvo_batch_cfg.ransac_flags (an RGB-D value has the matcher's alone: sosvo_rgbd_batch_cfg.flags)."""
         return (self.match.flags() | subpix_flags(self.subpix) | (FLAG_LK_F2F if self.lk is not None else 0)
-                | (FLAG_LK_STEREO if self.stereo_lk is not None else 0) | (FLAG_CYCLIC_F2F if self.cyclic else 0))
+                | (FLAG_LK_STEREO if self.stereo_lk is not None else 0) | (FLAG_CYCLIC_F2F if self.cyclic else 0)
+                | (FLAG_SEAM_FREE if self.cyclic == SEAM_FREE else 0))
+
+    @property
+    def seam_free(self):
+        """The front end is the seam-free one (cyclic == "seam_free")."""
+        return self.cyclic == SEAM_FREE
 
     @classmethod
     def of(cls, cross_check_stereo=False, cross_check_f2f=False, gated_stereo=False, gated_f2f=False, gated_max_distance=None,
            ratio_stereo=False, ratio_f2f=False, ratio=None, subpix=None, f2f_tracker="match", lk=None, stereo_refine=None,
            stereo_lk=None, cyclic_columns=False, rig=None, store_levels=None, order=BATCH_ORDER, tracker_sees_match=True,
-           gray=True):
+           gray=True, detection_method="GFT", edge=31):
         """From the public keyword names (FramePairPipeline's docstring describes them), checked.  rig: a RigConfig or the
         panoramas' (top, bottom) widths, the period of cyclic_columns (not looked at without).  store_levels: the pyramid levels
         a frame store keeps whatever the settings (the batched engines: SOSVO_LK_MAX_LEVELS), None for a caller that builds the
         levels it tracks on.  order: the checks to run, in turn.  tracker_sees_match: f2f_tracker="lk" refuses the options of
         the matcher it replaces ("match" comes before "tracker" then).  gray: False = no gray panoramas to read (a pair
-        pipeline without a front end): what reads them is refused."""
+        pipeline without a front end): what reads them is refused.  detection_method, edge: what cyclic_columns="seam_free" looks at besides the widths."""
         def needs_gray(on, what, who):
             if on is not None and not gray:
                 raise ValueError("%s needs a front end: the %s reads the gray panoramas" % (what, who))
@@ -541,7 +582,13 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
             if gated_f2f and widths[0] != widths[1]:
                 raise ValueError("cyclic_columns with gated_f2f: one search serves both views, their widths must be equal (%r, %r)"
                                  % widths)
-            return True
+            if cyclic_value(cyclic_columns) == SEAM_FREE:
+                if not gray:
+                    raise ValueError("cyclic_columns=\"seam_free\" needs a front end: it is the front end that changes")
+                if widths[0] != widths[1]:
+                    raise ValueError("cyclic_columns=\"seam_free\": both panoramas must have one width (%r, %r)" % widths)
+                seam_free_check(widths, detection_method, edge)
+            return cyclic_value(cyclic_columns)
         match = (cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f, ratio)
         v, checks = {}, dict(
             match=lambda: MatchOptions(*match),
@@ -552,6 +599,8 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
             subpix=lambda: subpix_half(needs_gray(subpix, "subpix", "refinement")), cyclic=cyclic)
         for name in order:
             v["lk" if name == "tracker" else name] = checks[name]()
+        if v.get("cyclic") == SEAM_FREE:    # (the refinement's settings may be parsed after the widths: PAIR_ORDER)
+            seam_free_check((), stereo_lk=v.get("stereo_lk"))
         return cls(**v)
 
     @classmethod
@@ -574,7 +623,7 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
         if self.stereo_lk is not None:
             kw.update(stereo_refine="lk", stereo_lk=self.stereo_lk)
         if self.cyclic:
-            kw.update(cyclic_columns=True)
+            kw.update(cyclic_columns=self.cyclic)
         return kw
 
     @classmethod

@@ -170,6 +170,24 @@ __device__ __forceinline__ void sosvo_copy_bytes(uint8_t* __restrict__ d, const 
   for (size_t i = done + i0; i < nbytes; i += stride) d[i] = s[i];
 }
 
+// nrows rows of `width` bytes from s (rows s_pitch bytes apart) to d (d_pitch apart) by the threads i0, i0 + stride, ... of a
+// launch: 4 bytes per lane where the pointers, the pitches and the width allow it, byte by byte otherwise.
+__device__ __forceinline__ void sosvo_copy_rows(uint8_t* __restrict__ d, size_t d_pitch, const uint8_t* __restrict__ s, size_t s_pitch,
+                                                int width, int nrows, int i0, int stride) {
+  if ((((uintptr_t)d | (uintptr_t)s | d_pitch | s_pitch | (size_t)width) & 3) == 0) {
+    const int wq = width / 4;
+    for (size_t i = i0; i < (size_t)nrows * wq; i += stride) {
+      const size_t r = i / wq, c = i - r * wq;
+      reinterpret_cast<uint32_t*>(d + r * d_pitch)[c] = reinterpret_cast<const uint32_t*>(s + r * s_pitch)[c];
+    }
+    return;
+  }
+  for (size_t i = i0; i < (size_t)nrows * width; i += stride) {
+    const size_t r = i / width, c = i - r * width;
+    d[r * d_pitch + c] = s[r * s_pitch + c];
+  }
+}
+
 // Value of the neighbouring lane through the DPP operand path (wave_shr:1 / wave_shl:1): a VALU move the compiler
 // folds into the consuming add/max where it can, instead of a ds_bpermute through the LDS crossbar -- the rolling
 // kernels issue 6-10 lane exchanges per row and the LDS pipe, shared by the four SIMDs of a CU, was their limit.
@@ -269,7 +287,7 @@ struct sosvo_lk_images {
 bool sosvo_lk_options_ok(const sosvo_lk_options& o);
 bool sosvo_stereo_lk_options_ok(const sosvo_stereo_lk_options& o);
 int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
-                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic = false);
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic = false, int32_t pad = 0);
 int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const sosvo_lk_options& o, const int32_t* row_range,
                               const int32_t* from_img, const int32_t* to_img, int32_t nprob, int32_t cap, const float* pts,
                               const int64_t* store_pt, const int32_t* n, float* next_pts, uint8_t* status, float* err, float* back,

@@ -81,13 +81,9 @@ __global__ __launch_bounds__(kThreads) void unwrap_kernel(const uint8_t* __restr
 constexpr uint32_t kTabEdge = 0x80000000u;
 constexpr uint32_t kTabOffMask = 0x3FFFFFu;
 
-__global__ __launch_bounds__(kThreads) void unwrap_table_kernel(const uint8_t* __restrict__ masks,
-                                                                const float* __restrict__ map_x,
-                                                                const float* __restrict__ map_y, int H, int W, int npix,
-                                                                uint2* __restrict__ table) {
-  const int pix = blockIdx.x * kThreads + threadIdx.x, view = blockIdx.y;
-  if (pix >= npix) return;
-  const float mx = map_x[(size_t)view * npix + pix], my = map_y[(size_t)view * npix + pix];
+// The entry of a panorama pixel of view `view` whose map values are (mx, my): a pure function of them, the frame size and the
+// view's annulus mask.
+__device__ __forceinline__ uint2 unwrap_table_entry(const uint8_t* __restrict__ masks, float mx, float my, int H, int W, int view) {
   uint2 e = make_uint2(0u, 0u);
   if (mx == mx && my == my && mx > -4.0f && mx < (float)W + 4.0f && my > -4.0f && my < (float)H + 4.0f) {
     const int sx = __float2int_rn(mx * 32.0f), sy = __float2int_rn(my * 32.0f);
@@ -112,7 +108,34 @@ __global__ __launch_bounds__(kThreads) void unwrap_table_kernel(const uint8_t* _
       }
     }
   }
-  table[(size_t)view * npix + pix] = e;
+  return e;
+}
+
+__global__ __launch_bounds__(kThreads) void unwrap_table_kernel(const uint8_t* __restrict__ masks,
+                                                                const float* __restrict__ map_x,
+                                                                const float* __restrict__ map_y, int H, int W, int npix,
+                                                                uint2* __restrict__ table) {
+  const int pix = blockIdx.x * kThreads + threadIdx.x, view = blockIdx.y;
+  if (pix >= npix) return;
+  const float mx = map_x[(size_t)view * npix + pix], my = map_y[(size_t)view * npix + pix];
+  table[(size_t)view * npix + pix] = unwrap_table_entry(masks, mx, my, H, W, view);
+}
+
+// The table of the maps padded by SOSVO_SEAM_HALO cyclic columns on either side: padded column c' of a
+// row is the entry of the map values at column (c' - HALO) mod cols.  cols >= HALO, so one conditional add per side wraps.
+__global__ __launch_bounds__(kThreads) void unwrap_table_seam_free_kernel(const uint8_t* __restrict__ masks,
+                                                                          const float* __restrict__ map_x,
+                                                                          const float* __restrict__ map_y, int H, int W, int rows,
+                                                                          int cols, uint2* __restrict__ table) {
+  const int colsp = cols + 2 * SOSVO_SEAM_HALO, npixp = rows * colsp;
+  const int pix = blockIdx.x * kThreads + threadIdx.x, view = blockIdx.y;
+  if (pix >= npixp) return;
+  const int r = pix / colsp;
+  int c = pix - r * colsp - SOSVO_SEAM_HALO;
+  c += c < 0 ? cols : 0;
+  c -= c >= cols ? cols : 0;
+  const size_t src = ((size_t)view * rows + r) * cols + c;
+  table[(size_t)view * npixp + pix] = unwrap_table_entry(masks, map_x[src], map_y[src], H, W, view);
 }
 
 typedef uint32_t __attribute__((aligned(1))) u32_unaligned;
@@ -660,6 +683,20 @@ int32_t sosvo_unwrap_prepare(sosvo_ctx* ctx, const uint8_t* masks, const float* 
   SOSVO_REQUIRE(ctx, ((uintptr_t)table & 7) == 0, "table must be 8-byte aligned");
   SOSVO_LAUNCH(ctx, unwrap_table_kernel, dim3(cdiv(rows * cols, kThreads), 2), dim3(kThreads), 0, ctx->stream, masks, map_x,
                map_y, H, W, rows * cols, reinterpret_cast<uint2*>(table));
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+int32_t sosvo_unwrap_prepare_seam_free(sosvo_ctx* ctx, const uint8_t* masks, const float* map_x, const float* map_y, int32_t H,
+                                       int32_t W, int32_t rows, int32_t cols, uint32_t* table) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, map_x && map_y && table, "null pointer");
+  SOSVO_REQUIRE(ctx, sosvo_table_frame_ok(H, W), SOSVO_TABLE_FRAME_MSG);
+  SOSVO_REQUIRE(ctx, rows > 0 && cols >= SOSVO_SEAM_HALO && rows * ((int64_t)cols + 2 * SOSVO_SEAM_HALO) < (1 << 28),
+                "image sizes out of range (cols >= SOSVO_SEAM_HALO)");
+  SOSVO_REQUIRE(ctx, ((uintptr_t)table & 7) == 0, "table must be 8-byte aligned");
+  SOSVO_LAUNCH(ctx, unwrap_table_seam_free_kernel, dim3(cdiv(rows * (cols + 2 * SOSVO_SEAM_HALO), kThreads), 2), dim3(kThreads), 0,
+               ctx->stream, masks, map_x, map_y, H, W, rows, cols, reinterpret_cast<uint2*>(table));
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }

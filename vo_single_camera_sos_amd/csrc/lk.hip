@@ -148,6 +148,19 @@ __global__ __launch_bounds__(256) void lk_store_level0_kernel(const uint8_t* __r
   sosvo_copy_bytes(level0 + ((size_t)v * slots + tab.slot[i]) * npx + first, gray + ((size_t)v * nf_all + f0 + i) * npx + first, bytes,
                    blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
+// ... from a front end that ran on padded panoramas (SOSVO_FLAG_SEAM_FREE): gray rows are cols + 2 pad bytes
+// long and the store takes their interior, the columns [pad, pad + cols).
+__global__ __launch_bounds__(256) void lk_store_level0_padded_kernel(const uint8_t* __restrict__ gray, int nf_all, int f0,
+                                                                     sosvo_slot_table tab, int slots, int rows, int cols, int pad,
+                                                                     const int32_t* __restrict__ row_range, uint8_t* __restrict__ level0) {
+  const int i = blockIdx.y, v = blockIdx.z;
+  int r0, r1;
+  lk_level_rows(row_range, v, rows, 0, &r0, &r1);
+  const size_t pitch = (size_t)cols + 2 * pad;
+  sosvo_copy_rows(level0 + (((size_t)v * slots + tab.slot[i]) * rows + r0) * cols, (size_t)cols,
+                  gray + (((size_t)v * nf_all + f0 + i) * rows + r0) * pitch + pad, pitch, cols, r1 - r0,
+                  blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
 // Level l + 1 from level l, both in the store: blockIdx.z = v * nf + i is view v of slot tab.slot[i].
 __global__ __launch_bounds__(kPyrTileX* kPyrTileY) void lk_pyr_down_slots_kernel(const uint8_t* __restrict__ in, int rows_in, int cols_in,
                                                                                 uint8_t* __restrict__ out, int rows_out, int cols_out,
@@ -626,8 +639,9 @@ bool sosvo_lk_options_ok(const sosvo_lk_options& o) {
 // rows, frame i goes to slot slot_of_frame[i] (HOST table, checked by the caller) or first_slot + i; gray == nullptr: level 0 of
 // the store IS the front end's buffer (a pair batch, frame i in slot i) and nothing is copied.  Then the levels in use, each
 // from the one below inside the store.  The table travels in kernel arguments, kSosvoSlotArgFrames frames per launch.
+// pad > 0: gray is [2, nframes, rows, cols + 2 pad], the rows of a padded front end, and level 0 takes their interior.
 int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t levels, const int32_t* row_range, const uint8_t* gray,
-                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic) {
+                             int32_t nframes, int32_t first_slot, const int32_t* slot_of_frame, bool cyclic, int32_t pad) {
   SOSVO_REQUIRE(ctx, im.level[0] && im.level[1] && im.level[2] && im.level[3], "null pointer");
   SOSVO_REQUIRE(ctx, lk_sizes_ok(2 * (int64_t)im.slots, im.rows, im.cols, levels), "sizes out of range (2 * slots <= 65535, levels 1..4)");
   const LkLevels t = lk_store_levels(im);
@@ -639,8 +653,12 @@ int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t 
     for (int i = 0; i < kSosvoSlotArgFrames; ++i) tab.slot[i] = i >= nf ? 0 : slot_of_frame ? slot_of_frame[f0 + i] : first_slot + f0 + i;
     for (int i = 0; i < nf; ++i) SOSVO_REQUIRE(ctx, tab.slot[i] >= 0 && tab.slot[i] < im.slots, "slot out of range");
     const int blocks = min(cdiv(im.rows * im.cols, 4096), 64);
-    SOSVO_LAUNCH(ctx, lk_store_level0_kernel, dim3(blocks, nf, 2), dim3(256), 0, ctx->stream, gray, nframes, f0, tab, im.slots, im.rows,
-                 im.cols, row_range, im.level[0]);
+    if (pad > 0)
+      SOSVO_LAUNCH(ctx, lk_store_level0_padded_kernel, dim3(blocks, nf, 2), dim3(256), 0, ctx->stream, gray, nframes, f0, tab, im.slots,
+                   im.rows, im.cols, pad, row_range, im.level[0]);
+    else
+      SOSVO_LAUNCH(ctx, lk_store_level0_kernel, dim3(blocks, nf, 2), dim3(256), 0, ctx->stream, gray, nframes, f0, tab, im.slots, im.rows,
+                   im.cols, row_range, im.level[0]);
     SOSVO_LAUNCH_CHECK(ctx);
     for (int l = 0; l + 1 < levels; ++l) {
       const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), 2 * nf);

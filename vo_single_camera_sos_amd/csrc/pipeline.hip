@@ -108,9 +108,31 @@ bool cyclic_f2f(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_
 constexpr const char* kBadCyclicCols = "SOSVO_FLAG_CYCLIC_F2F with SOSVO_FLAG_LK_F2F needs cols % 8 == 0 (every level of the store is one period)";
 constexpr const char* kBadCyclicRatio =
     "SOSVO_FLAG_CYCLIC_F2F: the ratio form of the gated frame-to-frame matcher (SOSVO_FLAG_GATED_F2F | SOSVO_FLAG_RATIO_F2F) has no cyclic gate";
+// ---- the seam-free front end (SOSVO_FLAG_SEAM_FREE): the image stages run on panoramas padded by
+// SOSVO_SEAM_HALO cyclic columns on either side (the caller's table and mask bits are the padded ones), the keypoints are
+// unpadded before the stereo assemble.  c.cols stays the period; run_cols is what the image stages see.
+bool seam_free(const sosvo_batch_cfg& c) { return (c.ransac_flags & SOSVO_FLAG_SEAM_FREE) != 0; }
+int run_cols(const sosvo_batch_cfg& c) { return seam_free(c) ? c.cols + 2 * SOSVO_SEAM_HALO : c.cols; }
+constexpr int kSeamReach = 35;  // columns a stage may read around a keypoint of the original columns
+const char* seam_free_msg(const sosvo_batch_cfg& c) {
+  if (!seam_free(c)) return nullptr;
+  if (!cyclic_f2f(c)) return "SOSVO_FLAG_SEAM_FREE needs SOSVO_FLAG_CYCLIC_F2F";
+  if (c.detector == SOSVO_DETECTOR_ORB) return "SOSVO_FLAG_SEAM_FREE: the ORB detector's pyramid levels keep borders the halo does not cover";
+  if (c.edge > 31) return "SOSVO_FLAG_SEAM_FREE needs edge <= 31";
+  if (c.cols < SOSVO_SEAM_HALO || c.cols + 2 * SOSVO_SEAM_HALO > 16384) return "SOSVO_FLAG_SEAM_FREE needs 40 <= cols and cols + 80 <= 16384";
+  return nullptr;
+}
+// (at call time: the settings live in the context) the stereo-LK windows stay inside the halo's clean columns
+bool seam_free_stereo_lk_ok(const sosvo_batch_cfg& c, const sosvo_stereo_lk_options& o) {
+  if (!seam_free(c) || !lk_stereo(c)) return true;
+  const double shift = o.max_shift > 0.0 ? o.max_shift : (double)o.half;
+  return 2.0 + o.half + ceil(shift) <= (double)kSeamReach;
+}
+constexpr const char* kBadSeamStereoLk = "SOSVO_FLAG_SEAM_FREE with SOSVO_FLAG_LK_STEREO needs 2 + half + ceil(max_shift) <= 35";
 // what every omni entry point asks of cfg->ransac_flags and the shape (nullptr: fine)
 const char* omni_flags_msg(const sosvo_batch_cfg& c) {
   const int32_t flags = c.ransac_flags;
+  if (seam_free_msg(c)) return seam_free_msg(c);
   if (!ratio_flags_ok(flags)) return kBadRatioFlags;
   if (!lk_flags_ok(flags)) return kBadLkFlags;
   if (cyclic_f2f(c) && lk_f2f(c) && c.cols % (1 << (SOSVO_LK_MAX_LEVELS - 1)) != 0) return kBadCyclicCols;
@@ -179,7 +201,7 @@ struct FrontEndTmp {
 };
 FrontEndTmp carve_front_end(Carver& cv, const sosvo_batch_cfg& c, size_t F) {
   FrontEndTmp t{};
-  const size_t NI = 2 * F, P = NI * c.nmask, cap = c.kp_cap, npx = (size_t)c.rows * c.cols;
+  const size_t NI = 2 * F, P = NI * c.nmask, cap = c.kp_cap, npx = (size_t)c.rows * run_cols(c);
   const bool fused = c.median_ksize <= 1 || c.median_ksize == 3 || c.median_ksize == 5 || c.median_ksize == 11;  // K1 inside the median / gray kernel
   t.pano = fused ? nullptr : cv.take<uint8_t>(NI * npx * 3);
   t.gray = cv.take<uint8_t>(NI * npx);
@@ -320,13 +342,14 @@ Workspace carve(const sosvo_batch_cfg& c, size_t window, size_t slots, void* bas
   ws.fe = carve_front_end(cv, c, window);
   ws.store = carve_store(cv, slots, c.frame_cap);
   ws.tt = carve_track(cv, c.n_pairs, c.frame_cap, cross_f2f(c));
-  ws.fe.orb = carve_orb(cv, c.detector, 2 * window * c.nmask, c.kp_cap, 2, c.rows, c.cols);
+  ws.fe.orb = carve_orb(cv, c.detector, 2 * window * c.nmask, c.kp_cap, 2, c.rows, c.cols);  // (never with SOSVO_FLAG_SEAM_FREE)
   ws.fe.mutual = carve_mutual(cv, cross_stereo(c), window * c.nmask);
   ws.tt.mutual = carve_mutual(cv, cross_f2f(c), c.n_pairs);
   ws.fe.ratio = carve_ratio(cv, ratio_stereo(c), (cross_stereo(c) ? 2 : 1) * window * c.nmask * c.kp_cap);
   ws.tt.ratio = carve_ratio(cv, ratio_f2f(c), (cross_f2f(c) ? 2 : 1) * (size_t)c.n_pairs * c.frame_cap);
-  ws.img = carve_lk_images(cv, lk_f2f(c), slots, c.rows, c.cols, ws.fe.gray, pair_batch);
-  ws.img_in_place = pair_batch;
+  // (SOSVO_FLAG_SEAM_FREE: the front end's rows are padded, level 0 is their interior crop and has a buffer of its own)
+  ws.img_in_place = pair_batch && !seam_free(c);
+  ws.img = carve_lk_images(cv, lk_f2f(c), slots, c.rows, c.cols, ws.fe.gray, ws.img_in_place);
   ws.img_rows = gray_rows_known(c) ? ws.fe.gray_rows : nullptr;
   ws.tt.lk = carve_lk_tmp(cv, lk_f2f(c), c.n_pairs, c.frame_cap);
   ws.fe.lk_status = lk_stereo(c) ? cv.take<uint8_t>(window * c.nmask * (size_t)c.kp_cap) : nullptr;
@@ -722,7 +745,9 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
                              const int32_t* slot_of_frame = nullptr, const Workspace* images = nullptr, int first_slot = 0) {
   const int NI = 2 * F, NM = cfg->nmask, cap = cfg->kp_cap, Fc = cfg->frame_cap;
   const int h = F * NM;  // problems of one view: (frame, mask); the top view's come first (view-major images)
+  const int cols = run_cols(*cfg);  // the columns of the image stages: the period, or the padded panorama (SOSVO_FLAG_SEAM_FREE)
   int32_t rc;
+  SOSVO_REQUIRE(ctx, seam_free_stereo_lk_ok(*cfg, ctx->stereo_lk), kBadSeamStereoLk);
   if (median_wait) SOSVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, median_wait, 0));
   const int det = cfg->detector;
   const bool fused_median = cfg->median_ksize == 3 || cfg->median_ksize == 5 || cfg->median_ksize == 11;
@@ -732,45 +757,45 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   if (rows_known) {
     // rows beyond the reach of GFT on the masks and of ORB.compute on its keypoints are not computed (the range is a
     // model constant; a 2-workgroup kernel per call keeps this entry point free of caller-side state)
-    STAGE(sosvo_gray_rows_needed(ctx, mask_bits, 2, cfg->rows, cfg->cols, NM, cfg->edge, pattern, cfg->cos_a, cfg->sin_a,
+    STAGE(sosvo_gray_rows_needed(ctx, mask_bits, 2, cfg->rows, cols, NM, cfg->edge, pattern, cfg->cos_a, cfg->sin_a,
                                  t.gray_rows));
-    STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cfg->cols, cfg->median_ksize,
+    STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cols, cfg->median_ksize,
                                         t.gray_rows, t.gray));
   } else if (cfg->median_ksize <= 1 || fused_median) {  // every row (ksize <= 1: unwrap straight to gray)
-    STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cfg->cols, cfg->median_ksize,
+    STAGE(sosvo_unwrap_median_gray_rows(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cols, cfg->median_ksize,
                                         nullptr, t.gray));
   } else {
-    STAGE(sosvo_unwrap_table(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cfg->cols, t.pano));
-    STAGE(sosvo_median_gray(ctx, t.pano, NI, cfg->rows, cfg->cols, cfg->median_ksize, t.gray));
+    STAGE(sosvo_unwrap_table(ctx, omni, unwrap_table, F, cfg->H, cfg->W, cfg->rows, cols, t.pano));
+    STAGE(sosvo_median_gray(ctx, t.pano, NI, cfg->rows, cols, cfg->median_ksize, t.gray));
   }
   if (median_done) SOSVO_HIP(ctx, hipEventRecord(median_done, ctx->stream));
   // SOSVO_FLAG_LK_F2F: the frames' gray rows and the pyramid levels in use go where their records go (`images`: the workspace
   // whose store `o` belongs to, o shifted by first_slot)
   if (images && images->img.level[0])
     STAGE(sosvo_lk_images_fill(ctx, images->img, ctx->lk.levels, images->img_rows, images->img_in_place ? nullptr : t.gray, F,
-                               first_slot, slot_of_frame, cyclic_f2f(*cfg)));
+                               first_slot, slot_of_frame, cyclic_f2f(*cfg), seam_free(*cfg) ? SOSVO_SEAM_HALO : 0));
   // the stages ImageFrontEnd.run_features calls for the detector (frontend.py), with the same arguments
   if (det == SOSVO_DETECTOR_ORB) {
     // the mask pyramid is a model constant, rebuilt here on every call (as gray_rows above) to keep the entry point free of
     // caller-side state; kp_xy (level-0 x, y of the compacted keypoints) feeds the matching, each keypoint keeps its angle
-    STAGE(sosvo_orb_mask_pyramid(ctx, mask_bits, 2, cfg->rows, cfg->cols, NM, t.orb.mask_pyr));
-    STAGE(sosvo_detect_describe_orb(ctx, t.gray, t.orb.mask_pyr, NI, F, cfg->rows, cfg->cols, NM, cfg->max_corners, cap,
+    STAGE(sosvo_orb_mask_pyramid(ctx, mask_bits, 2, cfg->rows, cols, NM, t.orb.mask_pyr));
+    STAGE(sosvo_detect_describe_orb(ctx, t.gray, t.orb.mask_pyr, NI, F, cfg->rows, cols, NM, cfg->max_corners, cap,
                                     t.orb.kp4, t.orb.resp, t.n, pattern, t.desc, t.kp));
   } else if (det == SOSVO_DETECTOR_FAST || det == SOSVO_DETECTOR_AGAST) {
     STAGE((det == SOSVO_DETECTOR_FAST ? sosvo_detect_fast : sosvo_detect_agast)(ctx, t.gray, mask_bits, NI, F, cfg->rows,
-                                                                                cfg->cols, NM, 10, cap, t.kp, t.n, t.status));
-    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
+                                                                                cols, NM, 10, cap, t.kp, t.n, t.status));
+    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
                                   cfg->edge, nullptr, t.desc));
   } else {
-    STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, NI, F, cfg->rows, cfg->cols, NM, cfg->quality, cfg->min_distance,
+    STAGE(sosvo_detect_gft(ctx, t.gray, mask_bits, NI, F, cfg->rows, cols, NM, cfg->quality, cfg->min_distance,
                            cfg->max_corners, cap, t.kp, t.n, t.status));
-    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
+    STAGE(sosvo_describe_orb_rows(ctx, t.gray, NI, cfg->rows, cols, NM, cap, t.kp, t.n, cfg->cos_a, cfg->sin_a, pattern,
                                   cfg->edge, rows_known ? t.gray_rows : nullptr, t.desc));
   }
   // sub-pixel refinement (SOSVO_FLAG_SUBPIX) where ImageFrontEnd.run_features has it: the descriptors above are those of the
   // detector's positions, everything below sees the refined ones (ORB: kp_xy; kp4 keeps the detector's)
   if (cfg->ransac_flags & SOSVO_FLAG_SUBPIX)
-    STAGE(sosvo_refine_subpix(ctx, t.gray, NI, cfg->rows, cfg->cols, NM, cap, t.kp, t.n, SOSVO_SUBPIX_HALF_OF(cfg->ransac_flags), 10,
+    STAGE(sosvo_refine_subpix(ctx, t.gray, NI, cfg->rows, cols, NM, cap, t.kp, t.n, SOSVO_SUBPIX_HALF_OF(cfg->ransac_flags), 10,
                               0.01, rows_known ? t.gray_rows : nullptr));
   // static stereo per frame: query = bottom view, train = top view, bucket by bucket
   const float *kp_top = t.kp, *kp_bot = t.kp + (size_t)h * cap * 2;
@@ -786,9 +811,12 @@ static int32_t run_front_end(sosvo_ctx* ctx, const sosvo_rig* rig, const sosvo_b
   // sub-pixel static stereo (SOSVO_FLAG_LK_STEREO): the bottom keypoint of every matched pair moves to where the top one's
   // window is found in the bottom panorama; the gates, bearings, triangulation and m_bot below see the refined positions
   if (lk_stereo(*cfg))
-    STAGE(sosvo_refine_stereo_lk(ctx, t.gray, NI, cfg->rows, cfg->cols, rows_known ? t.gray_rows : nullptr, NM, cap, kp_top, n_top,
+    STAGE(sosvo_refine_stereo_lk(ctx, t.gray, NI, cfg->rows, cols, rows_known ? t.gray_rows : nullptr, NM, cap, kp_top, n_top,
                                  t.kp + (size_t)h * cap * 2, n_bot, t.s_keys, rig->stereo_min_disp, rig->stereo_max_hdiff, nullptr,
                                  t.lk_status));
+  // SOSVO_FLAG_SEAM_FREE: everything above ran in the padded panoramas' coordinates; the assemble, the store and the tracking
+  // step see the period's columns (both views' keypoints: they are the two halves of t.kp)
+  if (seam_free(*cfg)) STAGE(sosvo_keypoints_unpad(ctx, t.kp, t.n, 2 * h, cap, cfg->cols));
   if (slot_of_frame)  // (HOST table: frame i's record goes to record slot_of_frame[i] of o)
     STAGE(sosvo_stereo_assemble_slots(ctx, rig, kp_top, kp_bot, desc_top, desc_bot, n_top, n_bot, t.s_keys, t.s_order, F,
                                       slot_of_frame, NM, cap, Fc, o.m_top, o.m_bot, o.d_top, o.d_bot, o.X, o.b_top, o.b_bot, o.M,

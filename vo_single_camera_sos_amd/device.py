@@ -15,6 +15,12 @@ def _ptr(t):
     return c_p(t.data_ptr()) if t is not None else NULL
 
 
+def _run_cols(cfg):
+    """The columns of the table and the mask bits a batch configuration's front end takes: cfg.cols, or with
+    SOSVO_FLAG_SEAM_FREE the padded panorama's (sosvo_unwrap_prepare_seam_free, sosvo_mask_bits_seam_free)."""
+    return cfg.cols + (2 * _lib.SEAM_HALO if cfg.ransac_flags & _lib.FLAG_SEAM_FREE else 0)
+
+
 def _check(t, dtype, name, shape=None, ndim=None):
     if not isinstance(t, torch.Tensor):
         raise SosvoError("%s: expected a torch tensor, got %r" % (name, type(t)))
@@ -211,6 +217,55 @@ class Context(object):
         table = torch.empty((2, rows, cols, 2), dtype=torch.uint32, device=map_x.device)
         self._call(self._lib.sosvo_unwrap_prepare, _ptr(masks), _ptr(map_x), _ptr(map_y), H, W, rows, cols, _ptr(table))
         return table
+
+    # ---- the seam-free front end's stages -------------------------------------------------------
+    def unwrap_prepare_seam_free(self, masks, map_x, map_y, omni_shape):
+        """sosvo_unwrap_prepare_seam_free: the table [2, rows, cols + 80, 2] u32 of the maps padded by SEAM_HALO cyclic columns on
+        either side -- byte for byte unwrap_prepare on such maps.  cols >= 40."""
+        H, W = omni_shape
+        if masks is not None:
+            _check(masks, torch.uint8, "masks", (2, H, W))
+        _check(map_x, torch.float32, "map_x", (2, None, None))
+        rows, cols = map_x.shape[1], map_x.shape[2]
+        _check(map_y, torch.float32, "map_y", (2, rows, cols))
+        table = torch.empty((2, rows, cols + 2 * _lib.SEAM_HALO, 2), dtype=torch.uint32, device=map_x.device)
+        self._call(self._lib.sosvo_unwrap_prepare_seam_free, _ptr(masks), _ptr(map_x), _ptr(map_y), H, W, rows, cols, _ptr(table))
+        return table
+
+    def mask_bits_seam_free(self, mask_bits, out=None):
+        """sosvo_mask_bits_seam_free: mask_bits [nsets, rows, cols] u32 -> [nsets, rows, cols + 80], the masks in the columns
+        [40, 40 + cols) and an empty halo: every original pixel is detected exactly once."""
+        _check(mask_bits, torch.uint32, "mask_bits", (None, None, None))
+        nsets, rows, cols = mask_bits.shape
+        if out is None:
+            out = torch.empty((nsets, rows, cols + 2 * _lib.SEAM_HALO), dtype=torch.uint32, device=mask_bits.device)
+        _check(out, torch.uint32, "out", (nsets, rows, cols + 2 * _lib.SEAM_HALO))
+        self._call(self._lib.sosvo_mask_bits_seam_free, _ptr(mask_bits), nsets, rows, cols, _ptr(out))
+        return out
+
+    def keypoints_unpad(self, kp, n, period):
+        """sosvo_keypoints_unpad: the first n[p] keypoints of kp [nprob, cap, 2] f32 from a padded panorama's columns back to
+        the period's, in place (float32: x - 40, + period if negative, - period if >= period, `period` itself is 0).  Rows at
+        and beyond n[p], y and everything else are untouched."""
+        _check(kp, torch.float32, "kp", (None, None, 2))
+        nprob, cap = kp.shape[0], kp.shape[1]
+        _check(n, torch.int32, "n", (nprob,))
+        self._call(self._lib.sosvo_keypoints_unpad, _ptr(kp), _ptr(n), nprob, cap, int(period))
+        return kp
+
+    def gray_unpad(self, gray, cols, row_range=None, out=None):
+        """sosvo_gray_unpad: gray [nimg, rows, cols + 80] u8 -> out [nimg, rows, cols], the interior columns.  row_range (int32
+        [2,2] on the device, nimg even): only those rows of each view are written."""
+        cols = int(cols)
+        _check(gray, torch.uint8, "gray", (None, None, cols + 2 * _lib.SEAM_HALO))
+        nimg, rows = gray.shape[0], gray.shape[1]
+        if out is None:
+            out = torch.zeros((nimg, rows, cols), dtype=torch.uint8, device=gray.device)
+        _check(out, torch.uint8, "out", (nimg, rows, cols))
+        if row_range is not None:
+            _check(row_range, torch.int32, "row_range", (2, 2))
+        self._call(self._lib.sosvo_gray_unpad, _ptr(gray), nimg, rows, cols, _ptr(row_range), _ptr(out))
+        return out
 
     def unwrap_table(self, omni, table, pano=None):
         """omni [F,H,W,3] u8, table from unwrap_prepare -> pano [2,F,rows,cols,3] u8 (view-major)."""
@@ -1072,14 +1127,16 @@ class Context(object):
 
     def frame_pair_batch(self, rig, cfg, omni, unwrap_table, mask_bits, pattern, workspace, results=None, n_streams=1,
                          join=True):
-        """omni [2B,H,W,3] u8, unwrap_table [2,rows,cols,2] u32, mask_bits [2,rows,cols] u32, pattern [512,2] i8,
+        """omni [2B,H,W,3] u8, unwrap_table [2,rows,cols,2] u32, mask_bits [2,rows,cols] u32 (with SOSVO_FLAG_SEAM_FREE:
+        cols + 80 columns, from unwrap_prepare_seam_free / mask_bits_seam_free), pattern [512,2] i8,
         workspace u8 [>= frame_pair_batch_workspace(cfg)] -> results [B,16] f64 (see include/sosvo.h).
         join=False (n_streams > 1 only): sosvo_frame_pair_batch_streams_enqueue -- call frame_pair_batch_join() before
         reading the records on this context's stream."""
         B = int(cfg.n_pairs)
+        cols = _run_cols(cfg)
         _check(omni, torch.uint8, "omni", (2 * B, cfg.H, cfg.W, 3))
-        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cfg.cols, 2))
-        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cfg.cols))
+        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cols, 2))
+        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cols))
         _check(pattern, torch.int8, "pattern", (512, 2))
         _check(workspace, torch.uint8, "workspace", ndim=1)
         if results is None:
@@ -1157,9 +1214,10 @@ class Context(object):
 
     @staticmethod
     def _check_omni_inputs(cfg, omni, unwrap_table, mask_bits, pattern, workspace):
+        cols = _run_cols(cfg)
         _check(omni, torch.uint8, "omni", (None, cfg.H, cfg.W, 3))
-        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cfg.cols, 2))
-        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cfg.cols))
+        _check(unwrap_table, torch.uint32, "unwrap_table", (2, cfg.rows, cols, 2))
+        _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cols))
         _check(pattern, torch.int8, "pattern", (512, 2))
         _check(workspace, torch.uint8, "workspace", ndim=1)
 

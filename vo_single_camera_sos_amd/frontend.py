@@ -46,6 +46,34 @@ class DeviceImageModel(object):
         self.mask_bits = torch.from_numpy(self.mask_bits_host).to(dev)
         self.pattern_host = orb_pattern.orb_pattern()
         self.pattern = torch.from_numpy(self.pattern_host).to(dev)
+        self.seam_free, self.cols_run = False, self.cols     # (the plain form: the image stages run at the panorama's width)
+
+    def seam_free_form(self, ctx):
+        """The model as a seam-free front end sees it, made once: see SeamFreeImageModel."""
+        if self.__dict__.get("_seam_free_form") is None:
+            self._seam_free_form = SeamFreeImageModel(ctx, self)
+        return self._seam_free_form
+
+
+class SeamFreeImageModel(object):
+    """A DeviceImageModel for the seam-free front end: the image stages run on panoramas padded by SEAM_HALO cyclic columns on
+    either side, `cols_run` = cols + 80 wide.  `unwrap_table_run` [2, rows, cols_run, 2] and `mask_bits_run` [2, rows, cols_run]
+    (the masks with an empty halo) are made on the device; every plain member (cols: the period, mask_bits, unwrap_table, ...)
+    is the plain model's, unchanged for its other users."""
+    seam_free = True
+
+    def __init__(self, ctx, model):
+        _lib.seam_free_check(model.cols)
+        self.plain, self.cols_run = model, model.cols + 2 * _lib.SEAM_HALO
+        self.unwrap_table_run = ctx.unwrap_prepare_seam_free(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        self.mask_bits_run = ctx.mask_bits_seam_free(model.mask_bits)
+        ctx.synchronize()      # (front ends on other streams that share the model find them ready)
+
+    def seam_free_form(self, ctx):
+        return self
+
+    def __getattr__(self, name):    # (only what this form does not have itself)
+        return getattr(self.__dict__["plain"], name)
 
 
 def default_kp_cap(method, num_of_features):
@@ -70,7 +98,9 @@ class ImageFrontEnd(object):
     def __init__(self, ctx, model, nframes, detection_method="GFT", num_of_features=1000, kp_cap=None,
                  median_win_size=11, quality=0.01, min_distance=5.0, edge=31, keep_panoramas=True,
                  skip_unreachable_rows=True, subpix=None):
-        """num_of_features: per azimuthal mask (FeatureMatcher.num_of_features, pose_est_tools.py:862).
+        """model: a DeviceImageModel, or its seam_free_form(ctx) for the seam-free front end (gray and
+        panoramas are cols + 80 wide, keypoints are in the padded columns until unpad(); ORB and edge > 31 are refused).
+        num_of_features: per azimuthal mask (FeatureMatcher.num_of_features, pose_est_tools.py:862).
         keep_panoramas=False: K1 is fused into the median kernel and the colour panoramas are not materialised
         (nothing downstream of K3 reads them); identical gray images.
         subpix: None = off, or the window half-size 2 .. 5 of the sub-pixel refinement (Context.refine_subpix) that
@@ -85,12 +115,16 @@ class ImageFrontEnd(object):
         self.skip_unreachable_rows = bool(skip_unreachable_rows)
         self.subpix = _lib.subpix_half(subpix)
         self.kp_cap = int(kp_cap) if kp_cap else default_kp_cap(self.method, self.num_of_features)
+        self.seam_free = bool(getattr(model, "seam_free", False))
+        if self.seam_free:
+            _lib.seam_free_check(model.cols, self.method, self.edge)
         dev, m = ctx.device, model
+        cols = m.cols_run if self.seam_free else m.cols
         NI, P = 2 * self.F, 2 * self.F * m.nmask
         self.omni = torch.zeros((self.F, m.H, m.W, 3), dtype=torch.uint8, device=dev)
         self.keep_panoramas = bool(keep_panoramas) or self.median_win_size not in (0, 1, 3, 5, 11)
-        self.pano = torch.zeros((2, self.F, m.rows, m.cols, 3), dtype=torch.uint8, device=dev) if self.keep_panoramas else None
-        self.gray = torch.zeros((NI, m.rows, m.cols), dtype=torch.uint8, device=dev)
+        self.pano = torch.zeros((2, self.F, m.rows, cols, 3), dtype=torch.uint8, device=dev) if self.keep_panoramas else None
+        self.gray = torch.zeros((NI, m.rows, cols), dtype=torch.uint8, device=dev)
         self.kp = torch.zeros((P, self.kp_cap, 2), dtype=torch.float32, device=dev)
         self.n = torch.zeros((P,), dtype=torch.int32, device=dev)
         self.status = torch.zeros((P,), dtype=torch.int32, device=dev)
@@ -104,7 +138,7 @@ class ImageFrontEnd(object):
             key = (self.edge, self.cos_a, self.sin_a)
             cache = m.__dict__.setdefault("_gray_rows", {})
             if key not in cache:
-                cache[key] = ctx.gray_rows_needed(m.mask_bits, m.nmask, self.edge, m.pattern, self.cos_a, self.sin_a)
+                cache[key] = ctx.gray_rows_needed(self._mask_bits, m.nmask, self.edge, m.pattern, self.cos_a, self.sin_a)
                 ctx.synchronize()
             self.gray_rows = cache[key]
         if self.method == "ORB":
@@ -113,25 +147,47 @@ class ImageFrontEnd(object):
             if getattr(model, "mask_pyr", None) is None:
                 model.mask_pyr = ctx.orb_mask_pyramid(model.mask_bits, model.nmask)
 
+    @property
+    def _mask_bits(self):
+        """The mask bits the detectors run on: the model's, or (seam-free) those with the empty halo."""
+        return self.model.mask_bits_run if self.seam_free else self.model.mask_bits
+
     def load_frames(self, omni):
         """omni: numpy or torch uint8 [F, H, W, 3] (BGR) -> resident in HBM."""
         t = torch.from_numpy(np.ascontiguousarray(omni)) if isinstance(omni, np.ndarray) else omni
         self.omni.copy_(t.to(self.ctx.device))
 
-    def run(self):
+    def run(self, unpad=True):
+        """unpad=False: a seam-free front end leaves its keypoints in the padded columns (the pair pipeline's static stereo
+        reads the padded gray around them and calls unpad() itself)."""
         self.run_images()
         self.run_features()
+        if self.seam_free and unpad:
+            self.unpad()
+
+    def unpad(self):
+        """Seam-free: the keypoints of both views from the padded columns back to the period's (Context.keypoints_unpad)."""
+        self.ctx.keypoints_unpad(self.kp, self.n, self.model.cols)
+
+    def gray_interior(self, out=None):
+        """Seam-free: the gray panoramas at the period's width [2 F, rows, cols] (Context.gray_unpad), for what reads them as a
+        circle (the cyclic pyramid of the Lucas-Kanade tracker)."""
+        return self.ctx.gray_unpad(self.gray, self.model.cols, row_range=None if self.keep_panoramas else self.gray_rows, out=out)
 
     def run_images(self):
         """K1 + K2 + K3: omni frames -> median-blurred gray panoramas (the VALU-bound half of the front end)."""
         c, m = self.ctx, self.model
-        if getattr(m, "unwrap_table", None) is None:  # once per model
-            m.unwrap_table = c.unwrap_prepare(m.omni_masks, m.map_x, m.map_y, (m.H, m.W))
-        if self.keep_panoramas:
-            c.unwrap_table(self.omni, m.unwrap_table, pano=self.pano)                                 # K1 (a1 + a2)
-            c.median_gray(self.pano.view(2 * self.F, m.rows, m.cols, 3), self.median_win_size, gray=self.gray)  # K2 + K3
+        if self.seam_free:
+            table, cols = m.unwrap_table_run, m.cols_run
         else:
-            c.unwrap_median_gray(self.omni, m.unwrap_table, self.median_win_size, gray=self.gray,
+            if getattr(m, "unwrap_table", None) is None:  # once per model
+                m.unwrap_table = c.unwrap_prepare(m.omni_masks, m.map_x, m.map_y, (m.H, m.W))
+            table, cols = m.unwrap_table, m.cols
+        if self.keep_panoramas:
+            c.unwrap_table(self.omni, table, pano=self.pano)                                          # K1 (a1 + a2)
+            c.median_gray(self.pano.view(2 * self.F, m.rows, cols, 3), self.median_win_size, gray=self.gray)  # K2 + K3
+        else:
+            c.unwrap_median_gray(self.omni, table, self.median_win_size, gray=self.gray,
                                  row_range=self.gray_rows)                                           # K1 + K2 + K3
 
     def run_features(self):
@@ -150,12 +206,12 @@ class ImageFrontEnd(object):
             return
         if self.method in ("FAST", "AGAST"):
             (c.detect_fast if self.method == "FAST" else c.detect_agast)(
-                self.gray, m.mask_bits, self.F, m.nmask, self.kp_cap, threshold=10, kp=self.kp, n=self.n,
+                self.gray, self._mask_bits, self.F, m.nmask, self.kp_cap, threshold=10, kp=self.kp, n=self.n,
                 status=self.status)                                                               # FAST / AGAST + NMS
             c.describe_orb(self.gray, self.kp, self.n, m.nmask, m.pattern, self.cos_a, self.sin_a, edge=self.edge,
                            desc=self.desc)                                                        # K6
             return
-        c.detect_gft(self.gray, m.mask_bits, self.F, m.nmask, self.kp_cap, quality=self.quality,
+        c.detect_gft(self.gray, self._mask_bits, self.F, m.nmask, self.kp_cap, quality=self.quality,
                      min_distance=self.min_distance, max_corners=self.num_of_features, kp=self.kp, n=self.n,
                      status=self.status)                                                          # K4
         c.describe_orb(self.gray, self.kp, self.n, m.nmask, m.pattern, self.cos_a, self.sin_a, edge=self.edge,

@@ -244,12 +244,19 @@ class GUMStereo(object):
 
     def _front_end(self, method, num_of_features, median_win_size):
         key = (str(method).upper(), int(num_of_features), int(median_win_size), self._subpix_half())
+        if self._seam_free():    # (set_cyclic_columns(tracker, "seam_free"): a front end of its own, on the padded panoramas)
+            key += ("seam_free",)
         if key not in self._front_ends:
             from ..frontend import ImageFrontEnd, mirror_kp_cap
             cap = mirror_kp_cap(key[0], num_of_features)
-            self._front_ends[key] = ImageFrontEnd(self._context(), self._device_model(), 1, detection_method=key[0],
+            model = self._device_model().seam_free_form(self._context()) if self._seam_free() else self._device_model()
+            self._front_ends[key] = ImageFrontEnd(self._context(), model, 1, detection_method=key[0],
                                                   num_of_features=key[1], kp_cap=cap, median_win_size=key[2], subpix=key[3])
         return self._front_ends[key]
+
+    def _seam_free(self):
+        """The frames detect with the seam-free front end: set_cyclic_columns(tracker, "seam_free")."""
+        return getattr(self, "cyclic_columns", False) == "seam_free"
 
     def set_current_omni_image(self, img, pano_width_in_pixels=1200, generate_panoramas=False, idx=-1, view=False,
                                apply_mask=True, mask_RGB=None):
@@ -273,13 +280,14 @@ class GUMStereo(object):
             self.top_model.panorama.omni_img = self.bot_model.panorama.omni_img = img
 
     def _detect_both(self, method, num_of_features, median_win_size):
-        token = (self._omni_serial, str(method).upper(), int(num_of_features), int(median_win_size), self._subpix_half())
+        token = (self._omni_serial, str(method).upper(), int(num_of_features), int(median_win_size), self._subpix_half(),
+                 self._seam_free())
         if self._detect_cache[0] == token:
             return self._detect_cache[1]
         from .camera_models import KeyPoint
         fe = self._front_end(method, num_of_features, median_win_size)
         fe.load_frames(np.ascontiguousarray(self.current_omni_img)[None])
-        fe.run()
+        fe.run()                         # (a seam-free front end ends with its unpad: the lists are in the period's columns)
         self._detect_front_end = fe      # (its gray panoramas are the current image's: what _refine_stereo_lk reads)
         fe.ctx.synchronize()
         nm = fe.model.nmask
@@ -327,9 +335,13 @@ class GUMStereo(object):
             kp[1, i, :len(bot_k)] = keypoints_to_array(bot_k)
             keys[i, np.asarray(q, np.int64)] = np.asarray(t, np.uint32)
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)  # noqa: E731
-        kp_bot = dev(kp[1])
-        ctx.refine_stereo_lk(fe.gray, dev(kp[0]), dev(n[0]), kp_bot, dev(n[1]), dev(keys), P, float(min_disp), float(max_hdiff),
+        if fe.seam_free:    # fe.gray is the padded panorama: its columns are the keypoints' + 40 (float32, exact on the grid)
+            kp[..., 0] += np.float32(fe.model.cols_run - fe.model.cols) / np.float32(2)
+        kp_bot, n_bot = dev(kp[1]), dev(n[1])
+        ctx.refine_stereo_lk(fe.gray, dev(kp[0]), dev(n[0]), kp_bot, n_bot, dev(keys), P, float(min_disp), float(max_hdiff),
                              stereo_lk=options, row_range=self._engine_gray_rows(fe))
+        if fe.seam_free:
+            ctx.keypoints_unpad(kp_bot, n_bot, fe.model.cols)
         ctx.synchronize()
         refined = kp_bot.cpu().numpy()
         return [(top_k, top_d, [KeyPoint(x, y, size=1.0) for x, y in refined[i, :len(bot_k)]], bot_d)

@@ -240,7 +240,8 @@ class StereoPanoramicFrame(object):
         self.gray_panoramas = self.gray_rows = None
         if getattr(omnistereo_model, "lk_options", None) is not None:
             fe = omnistereo_model._front_end(fm.feature_detection_method, fm.num_of_features, self.median_win_size)
-            self.gray_panoramas = fe.gray.clone()
+            # (a seam-free front end's panoramas are padded: the tracker's circle is their interior, a tensor of its own)
+            self.gray_panoramas = fe.gray_interior() if fe.seam_free else fe.gray.clone()
             # the rows the sequence engines' front end computes for this detector (GFT with the fused median: the reach of
             # its masks and descriptors, else every row): the tracker clamps to them there, so it does here, although this
             # front end has computed them all
@@ -681,6 +682,8 @@ def set_f2f_tracker(tracker, f2f_tracker, lk=None):
 
 def set_cyclic_columns(tracker, on):
     """Cyclic panorama columns frame to frame.  on: None = leave the tracker's own setting, False = off,
+    "seam_free" = True plus the seam-free front end (GUMStereo._front_end detects on the padded panoramas
+    and unpads after the features, _refine_stereo_lk adds the halo before its upload and unpads after; ORB is refused),
     True = column `cols` is column 0 again: the frame-to-frame |du| gate is cyclic (on the host, in the gated search and in
     the assembles) and, with set_f2f_tracker(..., "lk"), so are the pyramids and the tracker.  Call it after set_f2f_tracker
     and the matcher's setters: it checks the panorama width against them.  The camera model carries the setting, so the
@@ -694,9 +697,9 @@ def set_cyclic_columns(tracker, on):
             raise ValueError("cyclic_columns: an RGB-D camera's pinhole image is not cyclic")
         fm, lk = getattr(cm, "feature_matcher_for_motion", None), getattr(tracker, "lk_options", None)
         value = StepOptions.of(gated_f2f=bool(getattr(fm, "gated", False)), ratio_f2f=getattr(fm, "ratio", None) is not None,
-                               f2f_tracker="match" if lk is None else "lk", lk=lk, cyclic_columns=True,
+                               f2f_tracker="match" if lk is None else "lk", lk=lk, cyclic_columns=on,
                                rig=(cm.top_model.panorama.cols, cm.bot_model.panorama.cols), store_levels=LK_MAX_LEVELS,
-                               order=("lk", "cyclic")).cyclic      # (the engines' check of the width, and only that)
+                               order=("lk", "cyclic"), detection_method=tracker.detection_method).cyclic      # (the engines' check of the width, and only that)
     tracker.cyclic_columns = cm.cyclic_columns = value
 
 

@@ -9,7 +9,7 @@ import threading
 import numpy as np
 import torch
 
-from ._lib import LK_MAX_LEVELS, StepOptions, detector_code, rgbd_detector_flags
+from ._lib import LK_MAX_LEVELS, SEAM_FREE, StepOptions, cyclic_value, detector_code, rgbd_detector_flags
 from .device import Context, make_rig
 
 
@@ -61,13 +61,20 @@ class FramePairPipeline(object):
         cyclic_columns: the panoramas are full circles, column `cols` is column 0 again: the
         frame-to-frame |du| gate is cyclic in the assemble and, with gated_f2f, inside the matcher; with f2f_tracker="lk" the
         pyramids and the tracker are cyclic too (cols a multiple of 2^(levels - 1), the top level at least 2 half + 3 columns
-        wide).  The period is the rig's pano_top[0] / pano_bot[0]."""
+        wide).  The period is the rig's pano_top[0] / pano_bot[0].  "seam_free": all of that plus the seam-free front end
+         -- front_end is an ImageFrontEnd over the model's seam_free_form(ctx); its keypoints stay in the
+        padded columns through the static-stereo matching and refinement and are unpadded before the stereo assemble (a refined
+        pair that ends up straddling the seam fails the plain stereo gate and is dropped); the tracker's cyclic pyramid is built
+        on the interior columns (Context.gray_unpad)."""
         assert isinstance(ctx, Context)
         # (ValueError for a value out of range, settings without their switch, a width that cannot be cyclic, what reads the gray
         # panoramas without a front end.  This tracker has never refused the options of the matcher it replaces)
         so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
-                            order=StepOptions.PAIR_ORDER, tracker_sees_match=False, gray=front_end is not None)
+                            order=StepOptions.PAIR_ORDER, tracker_sees_match=False, gray=front_end is not None,
+                            detection_method=getattr(front_end, "method", "GFT"), edge=getattr(front_end, "edge", 31))
+        if so.seam_free != bool(getattr(front_end, "seam_free", False)):
+            raise ValueError("cyclic_columns=\"seam_free\" and a front end over the model's seam_free_form(ctx) go together")
         self.opts = o = so.match
         self.lk, self.stereo_lk, self.cyclic, self.f2f_tracker = so.lk, so.stereo_lk, so.cyclic, f2f_tracker
         if subpix is not None:
@@ -170,6 +177,8 @@ class FramePairPipeline(object):
             c.refine_stereo_lk(fe.gray, self.kp_top, self.n_top, self.kp_bot, self.n_bot, self.s_keys, self.NM,
                                self.rig_cfg.stereo_min_disp, self.rig_cfg.stereo_max_hdiff, stereo_lk=self.stereo_lk,
                                row_range=None if fe.keep_panoramas else fe.gray_rows, status=self.s_lk_status)
+        if self.cyclic == SEAM_FREE:    # (everything above ran in the padded columns)
+            self.front_end.unpad()
         c.stereo_assemble(self.rig, self.kp_top, self.kp_bot, self.desc_top, self.desc_bot, self.n_top, self.n_bot,
                           self.s_keys, self.s_order, self.F, self.NM, self.frame_cap, out=self.frames)
 
@@ -179,7 +188,10 @@ class FramePairPipeline(object):
         c, fe, o = self.ctx, self.front_end, self.lk
         self._M2[1].copy_(self._M2[0])
         rr = None if fe.keep_panoramas else fe.gray_rows
-        self._lk_pyr = (c.gray_pyramid_cyclic if self.cyclic else c.gray_pyramid)(fe.gray, o.levels, row_range=rr, out=self._lk_pyr)
+        gray = fe.gray
+        if self.cyclic == SEAM_FREE:    # the circle is the interior of the padded panoramas
+            gray = self._lk_gray = fe.gray_interior(out=getattr(self, "_lk_gray", None))
+        self._lk_pyr = (c.gray_pyramid_cyclic if self.cyclic else c.gray_pyramid)(gray, o.levels, row_range=rr, out=self._lk_pyr)
         torch.index_select(self._m2.view(2 * self.F, self.frame_cap, 2), 0, self._lk_ref, out=self._lk_prev)
         torch.index_select(self._M2.view(2 * self.F), 0, self._lk_ref, out=self._lk_n)
         res = c.track_lk(self._lk_pyr, self._t2, self._q2, self._lk_prev, self._lk_n, half=o.half, max_iter=o.max_iter,
@@ -215,7 +227,9 @@ class FramePairPipeline(object):
     def step(self):
         """The whole hot path for all B pairs (asynchronous): image front end (when attached), stereo
         correspondences, frame-to-frame tracking."""
-        if self.front_end is not None:
+        if self.front_end is not None and self.cyclic == SEAM_FREE:
+            self.front_end.run(unpad=False)     # (stereo() unpads, after its refinement)
+        elif self.front_end is not None:
             self.front_end.run()
         self.stereo()
         self.track()
@@ -259,13 +273,16 @@ class OverlappedFramePairs(object):
         from .frontend import DeviceImageModel, ImageFrontEnd
         from .parallel import shard_range
         so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
-                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig)
+                            ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
+                            detection_method=detection_method)
         self.lk, self.stereo_lk, self.cyclic = so.lk, so.stereo_lk, so.cyclic      # (checked before the device is touched)
         self.main = Context(device)                       # model constants + result collection: torch's current stream
         self.device = self.main.device
         self.model = DeviceImageModel(self.main, gums, omni_shape)
         m = self.model
         m.unwrap_table = self.main.unwrap_prepare(m.omni_masks, m.map_x, m.map_y, (m.H, m.W))
+        if so.seam_free:    # the parts' front ends run on the padded panoramas
+            m = m.seam_free_form(self.main)
         self.B, self.S = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
         self.out = torch.zeros((self.B, 16), dtype=torch.float64, device=self.device)
         self.main.synchronize()
@@ -444,9 +461,18 @@ def batch_cfg(model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_siz
     refines its static stereo; what options go together is the caller's to check (StepOptions.of)."""
     detector_code(detection_method)      # (refused before a bad option, as ever)
     so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo, ratio_f2f,
-                        ratio, subpix, order=("match", "subpix"))._replace(lk=lk, stereo_lk=stereo_lk, cyclic=bool(cyclic_columns))
+                        ratio, subpix, order=("match", "subpix"))._replace(lk=lk, stereo_lk=stereo_lk, cyclic=cyclic_value(cyclic_columns))
     return _batch_cfg(so, model, n_pairs, num_of_features, kp_cap, frame_cap, median_win_size, quality, min_distance, edge, thr,
                       max_iter, adaptive, seed, lm_iter, ransac_solver, detection_method)
+
+
+def _model_consts(ctx, model, so):
+    """The model tensors a batched engine with the options `so` hands its front end when they are not the plain ones (None):
+    the seam-free front end (SOSVO_FLAG_SEAM_FREE) takes the padded table and mask bits of the model's seam-free form."""
+    if not so.seam_free:
+        return None
+    sf = model.seam_free_form(ctx)
+    return sf.unwrap_table_run, sf.mask_bits_run, model.pattern
 
 
 def use_lk_options(ctx, so):
@@ -475,7 +501,7 @@ class FramePairBatch(object):
         None = off, and a frame-to-frame matcher option with f2f_tracker="lk" raises ValueError."""
         so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
-                            store_levels=LK_MAX_LEVELS)
+                            store_levels=LK_MAX_LEVELS, detection_method=detection_method, edge=edge)
         self.options, self.lk, self.stereo_lk, self.cyclic = so, so.lk, so.stereo_lk, so.cyclic
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         self.B, self.n_streams = int(n_pairs), max(1, min(int(n_streams), int(n_pairs)))
@@ -486,6 +512,7 @@ class FramePairBatch(object):
         self.method = str(detection_method).upper()
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        self._consts = _model_consts(ctx, model, so)
         nbytes = ctx.frame_pair_batch_workspace(c) if self.n_streams == 1 else ctx.frame_pair_batch_streams_workspace(c, self.n_streams)
         if nbytes <= 0:
             raise ValueError("bad batch configuration")
@@ -501,6 +528,9 @@ class FramePairBatch(object):
         """-> results [B,16] f64 (asynchronous)."""
         m = self.model
         use_lk_options(self.ctx, self.options)
+        if self._consts is not None:
+            return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, *self._consts, self.workspace, results=self.out,
+                                             n_streams=self.n_streams)
         return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
                                          results=self.out, n_streams=self.n_streams)
 
@@ -510,7 +540,8 @@ class FramePairBatch(object):
         step's records; call join() before reading records on the context's stream."""
         m = self.model
         use_lk_options(self.ctx, self.options)
-        return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, m.unwrap_table, m.mask_bits, m.pattern, self.workspace,
+        table, bits, pattern = self._consts or (m.unwrap_table, m.mask_bits, m.pattern)
+        return self.ctx.frame_pair_batch(self.rig, self.cfg, self.omni, table, bits, pattern, self.workspace,
                                          results=self.out if results is None else results, n_streams=self.n_streams,
                                          join=self.n_streams <= 1)
 
@@ -623,11 +654,12 @@ class _OmniFamily(_SequenceFamily):
             raise ValueError("ransac_solver: P3P or GP3P")
         if getattr(model, "unwrap_table", None) is None:  # once per model
             model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        self._consts = _model_consts(ctx, model, so)
         self._allocate(ctx, frames, slots, gather, [((model.H, model.W, 3), torch.uint8)])
 
     def consts(self):
         m = self.model
-        return m.unwrap_table, m.mask_bits, m.pattern
+        return self._consts or (m.unwrap_table, m.mask_bits, m.pattern)
 
     def _call(self, name, heads, *args):
         """Engines that share a context may track with different settings: every device call of a tracking family runs under
@@ -924,7 +956,7 @@ class SequenceEngine(_SequenceBase):
         every frame's gray panoramas and their pyramid."""
         so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
-                            store_levels=LK_MAX_LEVELS)
+                            store_levels=LK_MAX_LEVELS, detection_method=detection_method, edge=edge)
         self._init_windows(window)
         self._adopt(_OmniFamily(ctx, model, rig, self.W, self.slots, False, so, num_of_features=num_of_features, kp_cap=kp_cap,
                                 frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
@@ -1557,7 +1589,7 @@ class MultiSequenceEngine(_MultiSequenceBase):
                  subpix=None, f2f_tracker="match", lk=None, stereo_refine=None, stereo_lk=None, cyclic_columns=False):
         so = StepOptions.of(cross_check_stereo, cross_check_f2f, gated_stereo, gated_f2f, gated_max_distance, ratio_stereo,
                             ratio_f2f, ratio, subpix, f2f_tracker, lk, stereo_refine, stereo_lk, cyclic_columns, rig,
-                            store_levels=LK_MAX_LEVELS)
+                            store_levels=LK_MAX_LEVELS, detection_method=detection_method, edge=edge)
         self._init_lanes(lanes, window)
         self._adopt(_OmniFamily(ctx, model, rig, self.window, self.slots, True, so, num_of_features=num_of_features, kp_cap=kp_cap,
                                 frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
