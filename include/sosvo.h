@@ -1258,6 +1258,63 @@ int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cf
                                        const int32_t* src_slot_host, const int32_t* dst_slot_host, int32_t n_copies,
                                        void* workspace, size_t workspace_bytes);
 
+/* ---- dense omnistereo: SGM disparity map and point cloud -----------------------------------------
+ * Restates OmniStereoModel.get_depth_map_from_panoramas (camera_models.py:3395) with the SGBM settings of
+ * common_cv.StereoMatchTuner (common_cv.py:482-497: num_of_disparities 64, uniqueness 15, disp12MaxDiff; :644 the match of
+ * the rotated panoramas), resolve_pano_correspondences_from_disparity_map (:2492) and triangulate_from_depth_map (:2567).
+ * The reference runs cv2.StereoSGBM inside a tuner window; the algorithm here is THIS header's definition, modelled on
+ * SGBM, and the device reproduces tests/refdense.py (the same text in numpy) bit for bit.  It is no claim of parity with cv2.
+ *
+ * The rig is coaxial and its panoramas are rectified cylinders: epipolar lines are columns, and the top pixel (r, c) with
+ * disparity d corresponds to the bottom pixel (r - d, c) (the reference's m_bot = (u, v_top - disp); the sign of
+ * sosvo_rig.stereo_min_disp).  D = 64 disparities d = d0 + k, k = 0 .. 63, d0 = min_disparity.
+ *
+ * sosvo_census_9x7: gray [nimg, rows, cols] u8 -> census_out [nimg, rows, cols] u64.
+ *   a. A 9-row by 7-column window, 62 bits: taps in the order dy = -4 .. 4 outer, dx = -3 .. 3 inner, centre skipped, each
+ *      appending census = census << 1 | (g[r + dy, c + dx] < g[r, c]); the first tap ends in bit 61.  Rows clamp (replicated
+ *      border).  Columns clamp, or with SOSVO_DENSE_CYCLIC_COLUMNS in flags wrap modulo cols (the seam is no border: the
+ *      meaning of SOSVO_LK_CYCLIC_COLUMNS).  The flag changes nothing but these taps.
+ *
+ * sosvo_dense_stereo: top, bot [n, rows, cols] u8 gray panoramas (sosvo_unwrap_median_gray's output: top = its first n
+ *   images, bot = the next n; any two buffers will do), mask [rows, cols] u8 shared by the n frames or NULL (all valid).
+ *   b. C(r, c, k) = popcount(census_top(r, c) ^ census_bot(r - d, c)); 64 where r - d < 0.
+ *   c. Four paths (down, up, left to right, right to left).  Each starts at the image border with L = C; after that, with
+ *      m = min_j L_prev(j):  L(p, k) = C(p, k) + min(L_prev(k), L_prev(k - 1) + P1, L_prev(k + 1) + P1, m + P2) - m,
+ *      a missing neighbour (k - 1 < 0, k + 1 > 63) taking no part.  S = the sum of the four L (<= 4 * (64 + P2) <= 33020).
+ *      P1 = P2 = 0 (what the reference's tuner passes) switches the smoothness off and is accepted.
+ *   d. k* = the smallest k with the minimal S, mS = S(k*).
+ *   e. The pixel is dropped if some k with |k - k*| > 1 has S(k) * (100 - uniqueness) < mS * 100 (int32), or
+ *      r - (d0 + k*) < 0, or the mask is 0 at (r, c).
+ *   f. Left-right check, lr_max >= 0 (negative: none, the reference's disp12MaxDiff = -1): per column, over the pixels that
+ *      survived e in ascending r, the bottom row rb = r - (d0 + k*) keeps the k* of the surviving pixel with the smallest
+ *      mS (ties: the smaller r); a pixel is dropped if |kept(rb) - k*| > lr_max.
+ *   g. Sub-pixel, 1/16 row: for 1 <= k* <= 62, a = S(k* - 1), b = S(k* + 1), den = max(a + b - 2 mS, 1),
+ *      off = floor(((a - b) * 16 + den) / (2 den)) in [-8, 8]; off = 0 at k* = 0 and 63.
+ *   d16_out [n, rows, cols] i16 = (d0 + k*) * 16 + off, -1 for a dropped pixel.  S_out [n, rows, cols, 64] u16 or NULL: the
+ *   aggregated volume of step c (so that a failing parity test says which stage differs).  No speckle filter, no pre-filter.
+ *   Temporaries (census words, the cost volume, S without S_out, the left-right keys: about 210 bytes per pixel) live in the
+ *   context's scratch.
+ *
+ * sosvo_dense_triangulate: d16 [n, rows, cols] i16 -> X_out [n, rows, cols, 3] f64 in the rig's frame [C].  rig_host: the
+ *   sosvo_rig of sosvo_stereo_assemble (pano_top, pano_bot, F_top, F_bot, min_range, max_range are read).  For d16 >= 0,
+ *   d16 >= min_d16 and (max_d16 <= 0 or d16 <= max_d16): top pixel (c, r), bottom pixel (c, r - d16 / 16.0) in double; angles,
+ *   midpoint and range filter exactly as sosvo_pano_to_bearing -> sosvo_triangulate_midpoint -> sosvo_range_filter give them
+ *   (the same device functions, the same bits).  Everything else is NaN in all three components; a bottom row outside
+ *   [0, rows) is NaN because the angle is.
+ *
+ * SOSVO_ERR_ARG before any launch: rows or cols outside 1 .. 16384; n (nimg) < 1 (or > 32767; nimg > 65535); P1 < 0,
+ * P1 > P2, P2 > 8191; uniqueness outside [0, 100); min_disparity outside [0, 1024]; unknown flag bits; a NULL required
+ * pointer; a rig whose two panoramas differ in geometry.  Asynchronous on the context's stream.                       */
+#define SOSVO_DENSE_CYCLIC_COLUMNS 1
+#define SOSVO_DENSE_DISPARITIES 64
+int32_t sosvo_census_9x7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t flags,
+                         uint64_t* census_out);
+int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                           const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
+                           int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out);
+int32_t sosvo_dense_triangulate(sosvo_ctx* ctx, const sosvo_rig* rig_host, const int16_t* d16, int32_t n, int32_t rows,
+                                int32_t cols, int32_t min_d16, int32_t max_d16, double* X_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,9 @@ SIGNATURES = {
     "sosvo_rgbd_sequence_copy_slots": (c_i32, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_p, ctypes.c_size_t]),
     "sosvo_rgbd_pair_batch_workspace": (ctypes.c_size_t, [c_p]),
     "sosvo_rgbd_pair_batch": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
+    "sosvo_census_9x7": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_dense_stereo": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sosvo_dense_triangulate": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
 }
 
 HINT_SHARED_DEVICE = 1
@@ -634,6 +637,50 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
         match = MatchOptions.from_matchers(fm, getattr(camera_model, "feature_matcher_for_motion", None))
         return None if match is None else cls(match, getattr(fm, "subpix_half", None), getattr(tracker, "lk_options", None),
                                               getattr(fm, "stereo_lk_options", None), getattr(camera_model, "cyclic_columns", False))
+
+
+DENSE_CYCLIC_COLUMNS = 1           # SOSVO_DENSE_CYCLIC_COLUMNS: the census taps wrap modulo cols
+DENSE_DISPARITIES = 64             # SOSVO_DENSE_DISPARITIES: one lane of a wave per disparity
+DENSE_MAX_P2, DENSE_MAX_MIN_DISPARITY = 8191, 1024
+
+
+class DenseOptions(namedtuple("DenseOptions", "min_disparity P1 P2 uniqueness lr_max cyclic")):
+    """The settings of the dense stereo stage (sosvo_dense_stereo) as one checked value: min_disparity
+    0 .. 1024 rows (the first of the 64 disparities searched), the smoothness penalties 0 <= P1 <= P2 <= 8191 (the reference's
+    tuner passes P1 = P2 = 0: no smoothness), uniqueness 0 .. 99 per cent, lr_max the largest |k* difference| the left-right
+    check lets pass (negative: no check, the reference's disp12MaxDiff = -1), cyclic: the census taps wrap around the
+    panorama's seam.  A value out of range raises ValueError; nothing is rounded.  It is not a field of StepOptions: dense
+    stereo is no step of the VO pair."""
+    __slots__ = ()
+
+    def __new__(cls, min_disparity=1, P1=8, P2=48, uniqueness=15, lr_max=1, cyclic=False):
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or int(v) != v or not lo <= v <= hi:
+                raise ValueError("dense %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+            return int(v)
+        d0 = integer("min_disparity", min_disparity, 0, DENSE_MAX_MIN_DISPARITY)
+        p2 = integer("P2", P2, 0, DENSE_MAX_P2)
+        p1 = integer("P1", P1, 0, DENSE_MAX_P2)
+        if p1 > p2:
+            raise ValueError("dense P1 must not exceed P2, got P1 %r, P2 %r" % (P1, P2))
+        return super().__new__(cls, d0, p1, p2, integer("uniqueness", uniqueness, 0, 99),
+                               integer("lr_max", lr_max, -(1 << 31), (1 << 31) - 1), bool(cyclic))
+
+    @classmethod
+    def of(cls, value):
+        """An `options` argument (None: the defaults; a DenseOptions; a dict of its fields) -> the value."""
+        if value is None or isinstance(value, cls):
+            return cls() if value is None else value
+        if not isinstance(value, dict):
+            raise ValueError("options must be None, a DenseOptions or a dict of its fields, got %r" % (value,))
+        if set(value) - set(cls._fields):
+            raise ValueError("options: unknown settings %s" % sorted(set(value) - set(cls._fields)))
+        return cls(**value)
+
+    @property
+    def flags(self):
+        """The flags word of sosvo_dense_stereo / sosvo_census_9x7."""
+        return DENSE_CYCLIC_COLUMNS if self.cyclic else 0
 
 
 def rgbd_flags_detector(flags):

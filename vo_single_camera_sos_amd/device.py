@@ -1003,6 +1003,45 @@ class Context(object):
         self._call(self._lib.sosvo_range_filter, _ptr(X), X.shape[0], float(min_range), float(max_range), _ptr(ok))
         return ok
 
+    # ---- dense omnistereo ------------------------------------------
+    def census(self, gray, cyclic=False):
+        """sosvo_census_9x7: gray [NI,rows,cols] u8 -> the 62-bit census words [NI,rows,cols] (int64 holds the u64's bits)."""
+        _check(gray, torch.uint8, "gray", ndim=3)
+        out = torch.empty(gray.shape, dtype=torch.int64, device=gray.device)
+        self._call(self._lib.sosvo_census_9x7, _ptr(gray), gray.shape[0], gray.shape[1], gray.shape[2],
+                   _lib.DENSE_CYCLIC_COLUMNS if cyclic else 0, _ptr(out))
+        return out
+
+    def dense_stereo(self, top, bot, mask=None, *, options=None, want_volume=False):
+        """sosvo_dense_stereo: top, bot [n,rows,cols] u8 gray panoramas (the halves of unwrap_median_gray's output), mask
+        [rows,cols] u8 or None, options a DenseOptions (None: the defaults) -> d16 [n,rows,cols] i16 (disparity in 1/16 row,
+        -1 = invalid); with want_volume (d16, S [n,rows,cols,64] u16, the aggregated volume)."""
+        o = _lib.DenseOptions.of(options)
+        _check(top, torch.uint8, "top", ndim=3)
+        n, rows, cols = top.shape
+        _check(bot, torch.uint8, "bot", (n, rows, cols))
+        if mask is not None:
+            _check(mask, torch.uint8, "mask", (rows, cols))
+        d16 = torch.empty((n, rows, cols), dtype=torch.int16, device=top.device)
+        S = torch.empty((n, rows, cols, _lib.DENSE_DISPARITIES), dtype=torch.uint16, device=top.device) if want_volume else None
+        self._call(self._lib.sosvo_dense_stereo, _ptr(top), _ptr(bot), n, rows, cols, _ptr(mask), o.min_disparity, o.P1, o.P2,
+                   o.uniqueness, o.lr_max, o.flags, _ptr(d16), _ptr(S))
+        return (d16, S) if want_volume else d16
+
+    def dense_triangulate(self, rig, d16, min_disparity=1.0, max_disparity=0.0):
+        """sosvo_dense_triangulate: d16 [n,rows,cols] i16 -> X [n,rows,cols,3] f64 in the rig's frame, NaN where the pixel has
+        no disparity, min_disparity <= d16 / 16 <= max_disparity fails (the reference's two filters; max_disparity <= 0: no
+        upper one), the bottom pixel leaves the panorama or the point fails the rig's range filter."""
+        _check(d16, torch.int16, "d16", ndim=3)
+        n, rows, cols = d16.shape
+        lo = int(-(-float(min_disparity) * 16 // 1))                      # d16 >= ceil(16 min)
+        hi = int(float(max_disparity) * 16 // 1) if max_disparity > 0 else 0   # d16 <= floor(16 max)
+        if max_disparity > 0 and hi <= 0:      # (an upper gate below 1/16 row passes nothing; 0 would mean no gate)
+            lo, hi = 1 << 20, 1
+        X = torch.empty((n, rows, cols, 3), dtype=torch.float64, device=d16.device)
+        self._call(self._lib.sosvo_dense_triangulate, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(d16), n, rows, cols, lo, hi, _ptr(X))
+        return X
+
     def rgbd_backproject(self, depth, u, v, fx, fy, cx, cy, focal_length_m, depth_is_Z):
         _check(depth, torch.float32, "depth", ndim=2)
         n = u.shape[0]

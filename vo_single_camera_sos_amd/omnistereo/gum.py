@@ -388,6 +388,96 @@ class GUMStereo(object):
         m_bot = np.hstack((p_bot[ok], np.ones((int(ok.sum()), 1))))
         return (m_top, k_top[ok], d_top[ok]), (m_bot, k_bot[ok], d_bot[ok]), colors
 
+    # ---- dense stereo: disparity map and point cloud ---------------------------------
+    def _dense_engine(self, median_win_size, options):
+        """One-frame pipeline.DenseOmniStereo per (median, options), on the rig's own geometry and without a range filter
+        (the reference's dense path has none)."""
+        from .._lib import DenseOptions
+        from ..pipeline import DenseOmniStereo, RigConfig
+        key = (int(median_win_size), DenseOptions.of(options))
+        cache = self.__dict__.setdefault("_dense_engines", {})
+        if key not in cache:
+            geo = [(p.cols, p.rows, p.pixel_size, p.cyl_height_max) for p in (self.top_model.panorama, self.bot_model.panorama)]
+            rig = RigConfig(geo[0], geo[1], self.top_model.F[:3, 0], self.bot_model.F[:3, 0], 0.0, 0.0)
+            cache[key] = DenseOmniStereo(self._context(), self._device_model(), rig, 1, median_win_size=key[0], options=key[1],
+                                         min_disparity=0.0)
+        return cache[key]
+
+    def get_depth_map_from_panoramas(self, method="sgbm", use_cropped_panoramas=False, rows_roi=(), cols_roi=(), show=False,
+                                     load_stereo_tuner_from_pickle=False, stereo_tuner_filename=None, tune_live=False,
+                                     use_heat_map=True, stereo_matcher_tuner=None, median_win_size=0, options=None):
+        """camera_models.py:3395 without the tuner window: semi-global matching between the top and the bottom panorama of the
+        current omni image on the device (sosvo_dense_stereo; `options`: a DenseOptions, None = its defaults, in place of the
+        tuner's sliders).  Sets self.disparity_map (float64 [rows, cols] in rows, 0 = invalid as in the reference) and
+        self.disparity_img (u8, (d - min) * 255 / (64 - min) as common_cv.py:700) and returns them; self.disparity_d16 keeps the
+        device's int16 map.  The GUI-only arguments (show, tune_live, use_heat_map, the tuner and its pickle) are ignored;
+        cropping and regions of interest are not built."""
+        if str(method).lower() != "sgbm":
+            raise NotImplementedError("dense stereo method %r: only \"sgbm\" is built" % (method,))
+        if use_cropped_panoramas or len(rows_roi) or len(cols_roi):
+            raise NotImplementedError("cropped panoramas and regions of interest are not built: the whole panorama is matched")
+        if self.current_omni_img is None:
+            raise ValueError("set_current_omni_image first")
+        eng = self._dense_engine(median_win_size, options)
+        eng.load_frames(np.ascontiguousarray(self.current_omni_img)[None])
+        d16, X = eng.step()
+        eng.ctx.synchronize()
+        self.disparity_d16, self._dense_X = d16.cpu().numpy()[0], X.cpu().numpy()[0]
+        valid, d0 = self.disparity_d16 >= 0, eng.options.min_disparity
+        self.disparity_map = np.where(valid, self.disparity_d16 / 16.0, 0.0)
+        img = np.clip((self.disparity_map - d0) * 255.0 / (64 - d0), 0, 255)
+        self.disparity_img = np.where(valid, img, 0).astype(np.uint8)
+        return self.disparity_map, self.disparity_img
+
+    def resolve_pano_correspondences_from_disparity_map(self, ref_points_uv_coords, min_disparity=0, max_disparity=0, verbose=False,
+                                                        roi_cols=None):
+        """camera_models.py:2492: the reference's filters on self.disparity_map at the given top pixels (u, v) -- non-zero,
+        min_disparity <= d <= max_disparity (0: the map's maximum), bottom row v - d no lower than the row of the bottom mirror's
+        lowest elevation -> (top [1, m, 2] int, bottom [1, m, 2] float (u, v - d), disparities [m])."""
+        dm = self.disparity_map
+        if roi_cols is not None:
+            dm = np.zeros_like(self.disparity_map)
+            dm[:, roi_cols[0]:roi_cols[1]] = self.disparity_map[:, roi_cols[0]:roi_cols[1]]
+        if max_disparity == 0:
+            max_disparity = dm.max()
+        uv = np.asarray(ref_points_uv_coords)
+        d = dm[uv[..., 1], uv[..., 0]]
+        pano = self.bot_model.panorama      # (panorama.py:676: the row an elevation maps to)
+        lowest_row = int((pano.cyl_height_max - np.tan(self.bot_model.lowest_elevation_angle)) / pano.pixel_size)
+        keep = (d != 0) & (min_disparity <= d) & (d <= max_disparity) & (uv[..., 1] - d <= lowest_row)
+        top, disp = uv[keep], d[keep]
+        bot = np.transpose((top[..., 0], top[..., 1] - disp))
+        return top[np.newaxis, ...], bot[np.newaxis, ...], disp
+
+    def triangulate_from_depth_map(self, min_disparity=1, max_disparity=0, use_PCL=False, export_to_pcd=False, cloud_path="data",
+                                   use_LUTs=False, roi_cols=None, use_midpoint_triangulation=True, cloud_index=None,
+                                   use_opengv_triangulation=False, profile_triang_opengv=False):
+        """camera_models.py:2567 + generate_point_clouds (:2687) without PCL: every pixel of self.disparity_map that passes
+        resolve_pano_correspondences_from_disparity_map, in the reference's order (u outer, v inner), triangulated on the device
+        (sosvo_dense_triangulate: the midpoint method) -> ((points [1, m, 4] homogeneous wrt [C], colours [m, 3] float32 RGB of the
+        top panorama), (None, None)).  With export_to_pcd the points are written to <cloud_path>/XYZ[-<cloud_index>].pcd (ASCII)."""
+        if use_PCL or use_LUTs or use_opengv_triangulation or profile_triang_opengv or not use_midpoint_triangulation:
+            raise NotImplementedError("only the midpoint triangulation without PCL, LUTs and OpenGV is built")
+        rows, cols = self.disparity_map.shape
+        ref = np.transpose(np.indices((cols, rows)), (1, 2, 0))
+        top, _, _ = self.resolve_pano_correspondences_from_disparity_map(ref, min_disparity, max_disparity, roi_cols=roi_cols)
+        u, v = top[0, :, 0], top[0, :, 1]
+        X = self._dense_X[v, u]
+        ok = ~np.isnan(X[:, 0])        # (a bottom row above the panorama has no angle)
+        u, v, X = u[ok], v[ok], X[ok]
+        xyz = np.ones((1, X.shape[0], 4))
+        xyz[0, :, :3] = X
+        pano_img = self.top_model.panorama.panoramic_img
+        if pano_img is None:
+            self.set_current_omni_image(self.current_omni_img, generate_panoramas=True)
+            pano_img = self.top_model.panorama.panoramic_img
+        rgb = (pano_img[v, u, ::-1] if pano_img.ndim == 3 else np.repeat(pano_img[v, u, None], 3, axis=-1)).astype(np.float32)
+        if export_to_pcd:
+            import os
+            os.makedirs(cloud_path, exist_ok=True)
+            write_pcd_ascii(os.path.join(cloud_path, "XYZ%s.pcd" % ("" if cloud_index is None else "-%d" % cloud_index)), xyz[0, :, :3])
+        return (xyz, rgb), (None, None)
+
     def get_triangulated_point_from_direction_angles(self, dir_angs_top, dir_angs_bot, use_midpoint_triangulation=True):
         """camera_models.py:3323-3364 -> [1, m, 4] homogeneous points wrt [C] (midpoint of the common
         perpendicular of the two rays; the only method the VO path uses)."""
@@ -438,6 +528,18 @@ class GUMStereo(object):
         t.mask, b.mask = top.astype(np.uint8) * 255, bot.astype(np.uint8) * 255
         self.construct_new_mask = False
         return t.mask, b.mask
+
+
+def write_pcd_ascii(filename, xyz):
+    """An ASCII .pcd file (PCD v0.7, fields x y z as float32) of the points xyz [m, 3]: what pcl.save(..., binary=False)
+    writes for a pcl.PointCloud (camera_models.py:2739)."""
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    with open(filename, "w") as f:
+        f.write("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z\nSIZE 4 4 4\nTYPE F F F\nCOUNT 1 1 1\n")
+        f.write("WIDTH %d\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %d\nDATA ascii\n" % (xyz.shape[0], xyz.shape[0]))
+        for p in xyz:
+            f.write("%.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
+    return filename
 
 
 def synthetic_gums(scale=1.0, units="mm"):

@@ -1614,3 +1614,56 @@ class RGBDMultiSequenceEngine(_MultiSequenceBase):
                                 frame_cap=frame_cap, median_win_size=median_win_size, quality=quality, min_distance=min_distance,
                                 edge=edge, thr=thr, max_iter=max_iter, adaptive=adaptive, lm_iter=lm_iter,
                                 pose_est_algorithm=pose_est_algorithm, detection_method=detection_method))
+
+
+def dense_mask(ctx, model):
+    """The top view's unwrapped annulus mask [rows, cols] u8 of a DeviceImageModel (1 = valid): a pixel is valid where unwrapping
+    an all-255 frame gives 255.  Made once per model."""
+    if getattr(model, "_dense_mask", None) is None:
+        if getattr(model, "unwrap_table", None) is None:  # once per model
+            model.unwrap_table = ctx.unwrap_prepare(model.omni_masks, model.map_x, model.map_y, (model.H, model.W))
+        white = torch.full((1, model.H, model.W, 3), 255, dtype=torch.uint8, device=ctx.device)
+        gray = ctx.unwrap_median_gray(white, model.unwrap_table, 0)
+        model._dense_mask = (gray[0] == 255).to(torch.uint8).contiguous()
+        ctx.synchronize()      # (engines on other streams that share the model find it ready)
+    return model._dense_mask
+
+
+class DenseOmniStereo(object):
+    """Dense omnistereo for n_frames frames at once: OmniStereoModel.get_depth_map_from_panoramas
+    (camera_models.py:3395) + triangulate_from_depth_map (:2567) as a batched device stage.  step() runs unwrap_median_gray
+    through the model's table, Context.dense_stereo between the top and the bottom gray panoramas under the top view's
+    annulus mask, and Context.dense_triangulate: three asynchronous C-ABI calls on one stream.
+    options: a DenseOptions (None: the defaults).  min_disparity / max_disparity (rows): the reference's two filters of
+    resolve_pano_correspondences_from_disparity_map, applied by the triangulation (max_disparity <= 0: no upper one)."""
+
+    def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0):
+        from ._lib import DenseOptions
+        self.options = DenseOptions.of(options)
+        self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
+        if tuple(rig.pano_top) != tuple(rig.pano_bot):
+            raise ValueError("dense stereo needs two panoramas of one geometry, got %r and %r" % (rig.pano_top, rig.pano_bot))
+        self.F, self.median_win_size = int(n_frames), int(median_win_size)
+        self.min_disparity, self.max_disparity = float(min_disparity), float(max_disparity)
+        self.mask = dense_mask(ctx, model)
+        dev = ctx.device
+        self.omni = torch.zeros((self.F, model.H, model.W, 3), dtype=torch.uint8, device=dev)
+        self.gray = torch.zeros((2 * self.F, model.rows, model.cols), dtype=torch.uint8, device=dev)
+        self.d16 = self.X = None
+
+    def load_frames(self, omni):
+        t = torch.from_numpy(np.ascontiguousarray(omni)) if isinstance(omni, np.ndarray) else omni
+        self.omni.copy_(t.to(self.ctx.device))
+
+    def step(self):
+        """-> (d16 [F,rows,cols] i16, X [F,rows,cols,3] f64) on the device (asynchronous)."""
+        c, m = self.ctx, self.model
+        c.unwrap_median_gray(self.omni, m.unwrap_table, self.median_win_size, gray=self.gray)
+        self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options)
+        self.X = c.dense_triangulate(self.rig, self.d16, self.min_disparity, self.max_disparity)
+        return self.d16, self.X
+
+    def depth(self):
+        """|X - F_top| as f32 [F,rows,cols] of the last step (NaN where invalid), by torch on the device."""
+        F_top = torch.from_numpy(np.asarray(self.rig_cfg.F_top, np.float64).reshape(3)).to(self.ctx.device)
+        return torch.linalg.vector_norm(self.X - F_top, dim=-1).to(torch.float32)
