@@ -1291,7 +1291,8 @@ int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cf
  *   g. Sub-pixel, 1/16 row: for 1 <= k* <= 62, a = S(k* - 1), b = S(k* + 1), den = max(a + b - 2 mS, 1),
  *      off = floor(((a - b) * 16 + den) / (2 den)) in [-8, 8]; off = 0 at k* = 0 and 63.
  *   d16_out [n, rows, cols] i16 = (d0 + k*) * 16 + off, -1 for a dropped pixel.  S_out [n, rows, cols, 64] u16 or NULL: the
- *   aggregated volume of step c (so that a failing parity test says which stage differs).  No speckle filter, no pre-filter.
+ *   aggregated volume of step c (so that a failing parity test says which stage differs).  No pre-filter; the speckle
+ *   filter is a call of its own, sosvo_dense_speckle below.
  *   Temporaries (census words, the cost volume, S without S_out, the left-right keys: about 210 bytes per pixel) live in the
  *   context's scratch.
  *
@@ -1314,6 +1315,32 @@ int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bo
                            int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out);
 int32_t sosvo_dense_triangulate(sosvo_ctx* ctx, const sosvo_rig* rig_host, const int16_t* d16, int32_t n, int32_t rows,
                                 int32_t cols, int32_t min_d16, int32_t max_d16, double* X_out);
+
+/* ---- dense omnistereo: speckle filter -------------------------------------------------------------
+ * The reference's tuner sliders "Speckle Window Size" / "Speckle Range" (common_cv.StereoMatchTuner, common_cv.py:496-497,
+ * passed to cv2.StereoSGBM as speckleWindowSize / speckleRange): what cv2.filterSpeckles' flood fill computes, stated here
+ * and in tests/refspeckle.py (the same text in numpy), which the device reproduces bit for bit.
+ *
+ * sosvo_dense_speckle: d16 [n, rows, cols] i16 (sosvo_dense_stereo's map; any map will do) -> d16_out [n, rows, cols] i16.
+ * Per frame; no frame sees another.
+ *   a. A pixel is valid iff d16 >= 0 (ANY negative value is invalid, not only -1).
+ *   b. Two 4-neighbours are joined iff both are valid and |d16_a - d16_b| <= max_diff, the difference taken in int32.  The
+ *      pairs are (r, c)-(r + 1, c) and (r, c)-(r, c + 1); with SOSVO_DENSE_CYCLIC_COLUMNS in flags also (r, cols - 1)-(r, 0)
+ *      when cols > 1 (the panorama's seam is no border).
+ *   c. Components are the connected components of that graph.  The relation is not transitive, the graph is: a ramp
+ *      0, 16, 32, 48 with max_diff 16 is one component.
+ *   d. A valid pixel whose component has size <= max_size becomes -1.  Everything else, the original values of invalid
+ *      pixels included, is copied unchanged.  max_size = 0 therefore drops nothing; it is accepted and still runs.
+ *   labels_out [n, rows, cols] u32 or NULL: the smallest row-major index r * cols + c of the pixel's component, 0xFFFFFFFF
+ *   for an invalid pixel (so that a failing parity test says whether the labelling or the threshold differs).
+ *   d16_out == d16 is allowed: the call then filters in place.  Temporaries (a u32 label and a u32 size per pixel, 8 bytes
+ *   per pixel) live in the context's scratch.  The result is a pure function of the input: the label is a minimum, so it
+ *   depends on no order of execution.
+ *
+ * SOSVO_ERR_ARG before any launch: rows or cols outside 1 .. 16384; n < 1 or > 32767; max_size < 0; max_diff outside
+ * 0 .. 32767; unknown flag bits; d16 or d16_out NULL.  Asynchronous on the context's stream.                           */
+int32_t sosvo_dense_speckle(sosvo_ctx* ctx, const int16_t* d16, int32_t n, int32_t rows, int32_t cols, int32_t max_size,
+                            int32_t max_diff, int32_t flags, int16_t* d16_out, uint32_t* labels_out);
 
 #ifdef __cplusplus
 }

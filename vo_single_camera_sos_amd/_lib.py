@@ -149,6 +149,7 @@ SIGNATURES = {
     "sosvo_census_9x7": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_dense_stereo": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     "sosvo_dense_triangulate": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
+    "sosvo_dense_speckle": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
 }
 
 HINT_SHARED_DEVICE = 1
@@ -680,6 +681,55 @@ class DenseOptions(namedtuple("DenseOptions", "min_disparity P1 P2 uniqueness lr
     @property
     def flags(self):
         """The flags word of sosvo_dense_stereo / sosvo_census_9x7."""
+        return DENSE_CYCLIC_COLUMNS if self.cyclic else 0
+
+
+SPECKLE_MAX_DIFF = 32767           # sosvo_dense_speckle: max_diff is compared with a difference of two int16 values
+SPECKLE_TUNER_SCALE = 16           # cv2.StereoSGBM compares 16 * speckleRange with its 1/16-pixel disparities
+
+
+class SpeckleOptions(namedtuple("SpeckleOptions", "max_size max_diff cyclic")):
+    """The settings of the speckle filter (sosvo_dense_speckle) as one checked value: max_size 0 ..
+    2^31 - 1 pixels (a component of at most that many pixels is removed; 0 removes nothing), max_diff 0 .. 32767 in 1/16 row
+    (two neighbours are joined when their d16 differ by at most that), cyclic: the last column is joined to the first.
+    Integers only; a value out of range raises ValueError; nothing is rounded.  A value of its own: no field of DenseOptions
+    and none of StepOptions."""
+    __slots__ = ()
+
+    def __new__(cls, max_size=100, max_diff=16, cyclic=False):
+        def integer(name, v, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or int(v) != v or not 0 <= v <= hi:
+                raise ValueError("speckle %s must be an integer in 0 .. %d, got %r" % (name, hi, v))
+            return int(v)
+        if not isinstance(cyclic, (bool, int)) or cyclic not in (0, 1):
+            raise ValueError("speckle cyclic must be a bool, got %r" % (cyclic,))
+        return super().__new__(cls, integer("max_size", max_size, (1 << 31) - 1), integer("max_diff", max_diff, SPECKLE_MAX_DIFF),
+                               bool(cyclic))
+
+    @classmethod
+    def of(cls, value):
+        """A `speckle` argument (None: the filter is off, None comes back; a SpeckleOptions; a dict of its fields) -> the value."""
+        if value is None or isinstance(value, cls):
+            return value
+        if not isinstance(value, dict):
+            raise ValueError("speckle must be None, a SpeckleOptions or a dict of its fields, got %r" % (value,))
+        if set(value) - set(cls._fields):
+            raise ValueError("speckle: unknown settings %s" % sorted(set(value) - set(cls._fields)))
+        return cls(**value)
+
+    @classmethod
+    def from_tuner(cls, speckle_window_size, speckle_range, cyclic=False):
+        """The reference's two sliders (common_cv.StereoMatchTuner: "Speckle Window Size", "Speckle Range", handed to
+        cv2.StereoSGBM as speckleWindowSize / speckleRange) -> the value: window 0 switches the filter off (None), and
+        max_diff = 16 * speckle_range, the factor OpenCV applies to its 1/16-pixel disparities."""
+        window = cls(max_size=speckle_window_size).max_size
+        if isinstance(speckle_range, bool) or not isinstance(speckle_range, (int, float)) or int(speckle_range) != speckle_range:
+            raise ValueError("speckle_range must be an integer, got %r" % (speckle_range,))
+        return None if window == 0 else cls(window, SPECKLE_TUNER_SCALE * int(speckle_range), cyclic)
+
+    @property
+    def flags(self):
+        """The flags word of sosvo_dense_speckle."""
         return DENSE_CYCLIC_COLUMNS if self.cyclic else 0
 
 

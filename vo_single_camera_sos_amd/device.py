@@ -1042,6 +1042,23 @@ class Context(object):
         self._call(self._lib.sosvo_dense_triangulate, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(d16), n, rows, cols, lo, hi, _ptr(X))
         return X
 
+    def dense_speckle(self, d16, *, options, want_labels=False, out=None):
+        """sosvo_dense_speckle: d16 [n,rows,cols] i16, options a SpeckleOptions (or a dict of its
+        fields) -> the map with every component of at most max_size pixels set to -1, in `out` (None: a new tensor; d16
+        itself: in place); with want_labels (map, labels [n,rows,cols] u32: the smallest row-major index of the pixel's
+        component, 0xFFFFFFFF for an invalid pixel)."""
+        o = _lib.SpeckleOptions.of(options)
+        if o is None:
+            raise ValueError("dense_speckle needs a SpeckleOptions: None means that the filter is off, and then there is no call")
+        _check(d16, torch.int16, "d16", ndim=3)
+        n, rows, cols = d16.shape
+        if out is None:
+            out = torch.empty_like(d16)
+        _check(out, torch.int16, "out", (n, rows, cols))
+        labels = torch.empty((n, rows, cols), dtype=torch.uint32, device=d16.device) if want_labels else None
+        self._call(self._lib.sosvo_dense_speckle, _ptr(d16), n, rows, cols, o.max_size, o.max_diff, o.flags, _ptr(out), _ptr(labels))
+        return (out, labels) if want_labels else out
+
     def rgbd_backproject(self, depth, u, v, fx, fy, cx, cy, focal_length_m, depth_is_Z):
         _check(depth, torch.float32, "depth", ndim=2)
         n = u.shape[0]

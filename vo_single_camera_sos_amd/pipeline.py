@@ -1635,11 +1635,15 @@ class DenseOmniStereo(object):
     through the model's table, Context.dense_stereo between the top and the bottom gray panoramas under the top view's
     annulus mask, and Context.dense_triangulate: three asynchronous C-ABI calls on one stream.
     options: a DenseOptions (None: the defaults).  min_disparity / max_disparity (rows): the reference's two filters of
-    resolve_pano_correspondences_from_disparity_map, applied by the triangulation (max_disparity <= 0: no upper one)."""
+    resolve_pano_correspondences_from_disparity_map, applied by the triangulation (max_disparity <= 0: no upper one).
+    speckle: what SpeckleOptions.of takes.  None: no filter, and nothing differs from an engine without
+    the argument.  With a value step() filters d16 in place (Context.dense_speckle) between the stereo and the triangulation,
+    so that the returned map, X and depth() are the filtered ones."""
 
-    def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0):
-        from ._lib import DenseOptions
-        self.options = DenseOptions.of(options)
+    def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0,
+                 speckle=None):
+        from ._lib import DenseOptions, SpeckleOptions
+        self.options, self.speckle = DenseOptions.of(options), SpeckleOptions.of(speckle)
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         if tuple(rig.pano_top) != tuple(rig.pano_bot):
             raise ValueError("dense stereo needs two panoramas of one geometry, got %r and %r" % (rig.pano_top, rig.pano_bot))
@@ -1660,6 +1664,8 @@ class DenseOmniStereo(object):
         c, m = self.ctx, self.model
         c.unwrap_median_gray(self.omni, m.unwrap_table, self.median_win_size, gray=self.gray)
         self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options)
+        if self.speckle is not None:
+            c.dense_speckle(self.d16, options=self.speckle, out=self.d16)
         self.X = c.dense_triangulate(self.rig, self.d16, self.min_disparity, self.max_disparity)
         return self.d16, self.X
 
