@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "scratch_carver.h"
 #include "sosvo.h"
 
 struct sosvo_prof_entry {
@@ -71,12 +72,14 @@ struct SosvoProfScope {
 };
 #define SOSVO_PROFILE(ctx, name) SosvoProfScope sosvo_prof_scope_(ctx, name)
 
-// Kernel launch on the context's stream, labelled with the kernel's name for the profile.
-#define SOSVO_LAUNCH(ctx, kernel, ...)            \
-  do {                                            \
-    SOSVO_PROFILE(ctx, #kernel);                  \
-    hipLaunchKernelGGL(kernel, __VA_ARGS__);      \
+// Kernel launch on the context's stream, labelled `name` in the profile (a kernel picked at run time) ...
+#define SOSVO_LAUNCH_AS(ctx, name, kernel, ...) \
+  do {                                          \
+    SOSVO_PROFILE(ctx, name);                   \
+    hipLaunchKernelGGL(kernel, __VA_ARGS__);    \
   } while (0)
+// ... and labelled with the kernel's name as it is written.
+#define SOSVO_LAUNCH(ctx, kernel, ...) SOSVO_LAUNCH_AS(ctx, #kernel, kernel, __VA_ARGS__)
 
 #define SOSVO_WAVE 64
 
@@ -88,6 +91,12 @@ static inline int32_t sosvo_fail(sosvo_ctx* ctx, int32_t code, const char* what,
 #define SOSVO_REQUIRE(ctx, cond, msg)                                   \
   do {                                                                  \
     if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, __func__, msg); \
+  } while (0)
+
+// ... in a file-local body that several entry points share: `fn` is the public function's name
+#define SOSVO_REQUIRE_FN(ctx, cond, msg)                           \
+  do {                                                             \
+    if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, fn, msg); \
   } while (0)
 
 // Frames that are read through the unwrap table (sosvo_unwrap_prepare and every consumer of its table): the per-frame
@@ -130,6 +139,20 @@ static inline int32_t sosvo_ws_reserve(sosvo_ctx* ctx, size_t bytes) {
   }
   SOSVO_HIP(ctx, hipMalloc(&ctx->ws, bytes));
   ctx->ws_bytes = bytes;
+  return SOSVO_OK;
+}
+
+// A stage's buffers in the context's scratch.  `layout` takes them from a Carver (scratch_carver.h) into the site's
+// pointers: it runs over a null base to measure, the total is reserved, and it runs again over ctx->ws as it is AFTER the
+// reserve (which may have moved it), so no pointer is ever computed from a stale base.
+template <typename Layout>
+static inline int32_t sosvo_ws_carve(sosvo_ctx* ctx, Layout layout) {
+  Carver measure{nullptr};
+  layout(measure);
+  const int32_t rc = sosvo_ws_reserve(ctx, measure.off);
+  if (rc != SOSVO_OK) return rc;
+  Carver place{static_cast<char*>(ctx->ws)};
+  layout(place);
   return SOSVO_OK;
 }
 
@@ -248,6 +271,12 @@ __device__ __forceinline__ int sosvo_block_count_matches(const uint32_t* __restr
   return kept;
 }
 #endif
+
+// dense.hip / dense_speckle.hip: what every dense entry point asks of its frame stack and of its flags
+#define SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols) \
+  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)")
+#define SOSVO_REQUIRE_DENSE_N(ctx, n) SOSVO_REQUIRE(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)")
+#define SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags) SOSVO_REQUIRE(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits")
 
 // detect.hip: the rolling 7x7 blur on images that lie img_stride bytes apart (also used by orb.hip for the pyramid levels)
 int32_t sosvo_launch_gauss7(sosvo_ctx* ctx, const uint8_t* in, long long img_stride, int nimg, int rows, int cols,

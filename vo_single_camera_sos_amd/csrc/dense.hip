@@ -13,6 +13,7 @@
 // by the other three passes as one 64-byte line per step; S [n, rows, cols, 64] u16 is written by the downward pass and
 // added to by the other three, one launch after the other on the context's stream.
 #include "common.h"
+#include "dense_scratch.h"
 #include "geom_core.h"
 
 namespace {
@@ -223,8 +224,6 @@ __global__ __launch_bounds__(256) void dense_triangulate_kernel(DenseRig rig, co
   X[3 * p + 2] = x[2];
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int32_t launch_census(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, int cols, bool cyclic, uint64_t* out) {
   const dim3 grid(cdiv(cols, 256), rows, nimg);
   if (cyclic)
@@ -243,9 +242,9 @@ int32_t sosvo_census_9x7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int3
                          uint64_t* census_out) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, gray && census_out, "null pointer");
-  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)");
+  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
   SOSVO_REQUIRE(ctx, nimg >= 1 && nimg <= 65535, "nimg out of range (1..65535)");
-  SOSVO_REQUIRE(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits");
+  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
   return launch_census(ctx, gray, nimg, rows, cols, (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, census_out);
 }
 
@@ -254,26 +253,21 @@ int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bo
                            int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, top && bot && d16_out, "null pointer");
-  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)");
-  SOSVO_REQUIRE(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)");
+  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
+  SOSVO_REQUIRE_DENSE_N(ctx, n);
   SOSVO_REQUIRE(ctx, P1 >= 0 && P1 <= P2 && P2 <= 8191, "penalties out of range (0 <= P1 <= P2 <= 8191)");
   SOSVO_REQUIRE(ctx, uniqueness >= 0 && uniqueness < 100, "uniqueness out of range (0..99)");
   SOSVO_REQUIRE(ctx, min_disparity >= 0 && min_disparity <= 1024, "min_disparity out of range (0..1024)");
-  SOSVO_REQUIRE(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits");
+  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
   const bool cyclic = (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, want_lr = lr_max >= 0;
   const size_t frame_pixels = (size_t)rows * cols, total = (size_t)n * frame_pixels;
-  // scratch: census words of both views, C, S (unless the caller takes it), k*, the left-right keys
-  const size_t census_bytes = align256(total * 8), c_bytes = align256(total * kD), s_bytes = S_out ? 0 : align256(total * kD * 2),
-               k_bytes = align256(total), best_bytes = want_lr ? align256(total * 4) : 0;
-  const int32_t rc = sosvo_ws_reserve(ctx, 2 * census_bytes + c_bytes + s_bytes + k_bytes + best_bytes);
+  sosvo_dense_scratch b;  // (dense_scratch.h)
+  const int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { b = sosvo_dense_carve(cv, total, kD, S_out != nullptr, want_lr); });
   if (rc != SOSVO_OK) return rc;
-  uint8_t* ws = (uint8_t*)ctx->ws;
-  uint64_t* census_top = (uint64_t*)ws;
-  uint64_t* census_bot = (uint64_t*)(ws + census_bytes);
-  uint8_t* C = ws + 2 * census_bytes;
-  uint16_t* S = S_out ? S_out : (uint16_t*)(C + c_bytes);
-  uint8_t* kstar = C + c_bytes + s_bytes;
-  uint32_t* best = want_lr ? (uint32_t*)(kstar + k_bytes) : nullptr;
+  uint64_t *census_top = b.census_top, *census_bot = b.census_bot;
+  uint8_t *C = b.C, *kstar = b.kstar;
+  uint16_t* S = S_out ? S_out : b.S;
+  uint32_t* best = want_lr ? b.best : nullptr;
 
   int32_t st = launch_census(ctx, top, n, rows, cols, cyclic, census_top);
   if (st != SOSVO_OK) return st;
@@ -317,8 +311,8 @@ int32_t sosvo_dense_triangulate(sosvo_ctx* ctx, const sosvo_rig* rig_host, const
                                 int32_t cols, int32_t min_d16, int32_t max_d16, double* X_out) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, rig_host && d16 && X_out, "null pointer");
-  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)");
-  SOSVO_REQUIRE(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)");
+  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
+  SOSVO_REQUIRE_DENSE_N(ctx, n);
   DenseRig rig;
   for (int k = 0; k < 4; ++k) {
     SOSVO_REQUIRE(ctx, rig_host->pano_top[k] == rig_host->pano_bot[k], "the rig's two panoramas differ in geometry");

@@ -181,24 +181,24 @@ __global__ __launch_bounds__(256) void speckle_apply_kernel(const int16_t* d16, 
   d16_out[f0 + p] = (l != kNone && size[f0 + l] <= max_size) ? (int16_t)-1 : v;
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int32_t sosvo_dense_speckle(sosvo_ctx* ctx, const int16_t* d16, int32_t n, int32_t rows, int32_t cols, int32_t max_size,
                                        int32_t max_diff, int32_t flags, int16_t* d16_out, uint32_t* labels_out) {
   SOSVO_ENTER(ctx);
   SOSVO_REQUIRE(ctx, d16 && d16_out, "null pointer");
-  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)");
-  SOSVO_REQUIRE(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)");
+  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
+  SOSVO_REQUIRE_DENSE_N(ctx, n);
   SOSVO_REQUIRE(ctx, max_size >= 0, "max_size is negative");
   SOSVO_REQUIRE(ctx, max_diff >= 0 && max_diff <= 32767, "max_diff out of range (0..32767)");
-  SOSVO_REQUIRE(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits");
-  const size_t frame_pixels = (size_t)rows * cols, total = (size_t)n * frame_pixels, bytes = align256(total * 4);
-  const int32_t rc = sosvo_ws_reserve(ctx, 2 * bytes);
+  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
+  const size_t frame_pixels = (size_t)rows * cols, total = (size_t)n * frame_pixels;
+  uint32_t *parent, *size;
+  const int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    parent = cv.take<uint32_t>(total);
+    size = cv.take<uint32_t>(total);
+  });
   if (rc != SOSVO_OK) return rc;
-  uint32_t* parent = (uint32_t*)ctx->ws;
-  uint32_t* size = (uint32_t*)((uint8_t*)ctx->ws + bytes);
   const dim3 per_pixel((unsigned)((frame_pixels + 255) / 256), n);
   SOSVO_LAUNCH(ctx, speckle_init_kernel, dim3(rows, n), dim3(256), 0, ctx->stream, d16, rows, cols, max_diff, parent, size);
   SOSVO_LAUNCH_CHECK(ctx);

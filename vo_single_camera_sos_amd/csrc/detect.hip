@@ -1621,14 +1621,14 @@ int32_t sosvo_launch_gauss7(sosvo_ctx* ctx, const uint8_t* in, long long img_str
   return sosvo_launch_gauss7_to(ctx, in, img_stride, nimg, rows, cols, out, img_stride);
 }
 
-// Geometry of one corner-response launch and where its outputs lie in the workspace.  Two columns per lane
+// Geometry of one corner-response launch.  Two columns per lane
 // (min_eigen_wide_kernel, strips of 61 columns, a wave per PAIR of strips) from kEigWideMinCols columns on, unless
 // SOSVO_HINT_ROLLING_NARROW asks for the one-column form (strips of 58, a wave per strip); regions are numbered
 // (img * nchunks + chunk) * strips + strip in both, and gft_select_kernel gets the strip width that was used.
 struct gft_plan {
   bool wide;
   int strip_w, strips, nchunks, chunk_rows, wcap, waves;
-  size_t n_regions, o_cand, o_wcnt, o_stat, end;
+  size_t n_regions;
 };
 static gft_plan gft_plan_make(const sosvo_ctx* ctx, int nimg, int rows, int cols, int nmask) {
   gft_plan g;
@@ -1646,25 +1646,28 @@ static gft_plan gft_plan_make(const sosvo_ctx* ctx, int nimg, int rows, int cols
   // costs traffic
   g.wcap = (g.chunk_rows * g.strip_w + 63) & ~63;
   g.n_regions = (size_t)nimg * g.strips * g.nchunks;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  g.o_cand = carve(sizeof(uint2) * g.n_regions * g.wcap);
-  g.o_wcnt = carve(sizeof(uint32_t) * g.n_regions);
-  g.o_stat = carve(sizeof(uint32_t) * (size_t)nimg * nmask * 5);
-  g.end = off;
   return g;
 }
+// The scratch of a plan: the response kernel's outputs, then (sosvo_detect_gft, sorted_stride > 0) what the selection adds
+struct gft_bufs {
+  uint2* cand;
+  uint32_t *wcnt, *mstat, *sorted;
+  int32_t* redo;
+};
+static gft_bufs gft_carve(Carver& cv, const gft_plan& g, size_t P, int sorted_stride) {
+  gft_bufs b;
+  b.cand = cv.take<uint2>(g.n_regions * g.wcap);
+  b.wcnt = cv.take<uint32_t>(g.n_regions);
+  b.mstat = cv.take<uint32_t>(P * 5);
+  b.sorted = cv.take<uint32_t>(P * sorted_stride);
+  b.redo = cv.take<int32_t>(sorted_stride ? P : 0);
+  return b;
+}
 // mstat cleared, mask bounding boxes, the response kernel: candidate records, their counts and the per-mask maxima
-static int32_t gft_launch_response(sosvo_ctx* ctx, const gft_plan& g, const uint8_t* gray, const uint32_t* mask_bits, int nimg,
-                                   int images_per_maskset, int rows, int cols, int nmask) {
-  char* ws = (char*)ctx->ws;
-  uint2* cand = (uint2*)(ws + g.o_cand);
-  uint32_t* wcnt = (uint32_t*)(ws + g.o_wcnt);
-  uint32_t* mstat = (uint32_t*)(ws + g.o_stat);
+static int32_t gft_launch_response(sosvo_ctx* ctx, const gft_plan& g, const gft_bufs& b, const uint8_t* gray, const uint32_t* mask_bits,
+                                   int nimg, int images_per_maskset, int rows, int cols, int nmask) {
+  uint2* cand = b.cand;
+  uint32_t *wcnt = b.wcnt, *mstat = b.mstat;
   SOSVO_HIP(ctx, hipMemsetAsync(mstat, 0, sizeof(uint32_t) * (size_t)nimg * nmask * 5, ctx->stream));
   const int nsets = cdiv(nimg, images_per_maskset);
   SOSVO_LAUNCH(ctx, mask_bbox_kernel, dim3(rows, nsets), dim3(kThreads), 0, ctx->stream, mask_bits, images_per_maskset, rows,
@@ -1703,14 +1706,14 @@ int32_t sosvo_detect_gft_candidates(sosvo_ctx* ctx, const uint8_t* gray, const u
   geometry[5] = (int32_t)g.n_regions;
   if (!cand_out && !wcnt_out && !mstat_out) return SOSVO_OK;  // the sizes only
   SOSVO_REQUIRE(ctx, gray && mask_bits && cand_out && wcnt_out && mstat_out, "null pointer");
-  int32_t rc = sosvo_ws_reserve(ctx, g.end);
+  gft_bufs b;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { b = gft_carve(cv, g, (size_t)nimg * nmask, 0); });
   if (rc != SOSVO_OK) return rc;
-  rc = gft_launch_response(ctx, g, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
+  rc = gft_launch_response(ctx, g, b, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
   if (rc != SOSVO_OK) return rc;
-  const char* ws = (const char*)ctx->ws;
-  SOSVO_HIP(ctx, hipMemcpyAsync(cand_out, ws + g.o_cand, sizeof(uint2) * g.n_regions * g.wcap, hipMemcpyDeviceToDevice, ctx->stream));
-  SOSVO_HIP(ctx, hipMemcpyAsync(wcnt_out, ws + g.o_wcnt, sizeof(uint32_t) * g.n_regions, hipMemcpyDeviceToDevice, ctx->stream));
-  SOSVO_HIP(ctx, hipMemcpyAsync(mstat_out, ws + g.o_stat, sizeof(uint32_t) * (size_t)nimg * nmask * 5, hipMemcpyDeviceToDevice, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(cand_out, b.cand, sizeof(uint2) * g.n_regions * g.wcap, hipMemcpyDeviceToDevice, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(wcnt_out, b.wcnt, sizeof(uint32_t) * g.n_regions, hipMemcpyDeviceToDevice, ctx->stream));
+  SOSVO_HIP(ctx, hipMemcpyAsync(mstat_out, b.mstat, sizeof(uint32_t) * (size_t)nimg * nmask * 5, hipMemcpyDeviceToDevice, ctx->stream));
   return SOSVO_OK;
 }
 
@@ -1730,28 +1733,18 @@ int32_t sosvo_detect_gft(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   if (nimg == 0) return SOSVO_OK;
   const size_t P = (size_t)nimg * nmask;
   const gft_plan g = gft_plan_make(ctx, nimg, rows, cols, nmask);
-  size_t off = g.end;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
   const int strip_w = g.strip_w, strips = g.strips, nchunks = g.nchunks, chunk_rows = g.chunk_rows, wcap = g.wcap;
   const bool large = cap > 1024;  // whole-image masks (RGB-D frames): 16384 candidates, 15872 grid cells
   const int sorted_stride = large ? kCandCapLarge : kCandCap;
-  const size_t o_sorted = carve(sizeof(uint32_t) * P * sorted_stride);
-  const size_t o_redo = carve(sizeof(int32_t) * P);
-  int32_t rc = sosvo_ws_reserve(ctx, off);
+  gft_bufs b;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { b = gft_carve(cv, g, P, sorted_stride); });
   if (rc != SOSVO_OK) return rc;
-  char* ws = (char*)ctx->ws;
-  uint2* cand = (uint2*)(ws + g.o_cand);
-  uint32_t* wcnt = (uint32_t*)(ws + g.o_wcnt);
-  uint32_t* mstat = (uint32_t*)(ws + g.o_stat);
-  uint32_t* sorted_g = (uint32_t*)(ws + o_sorted);
-  rc = gft_launch_response(ctx, g, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
+  uint2* cand = b.cand;
+  uint32_t *wcnt = b.wcnt, *mstat = b.mstat, *sorted_g = b.sorted;
+  rc = gft_launch_response(ctx, g, b, gray, mask_bits, nimg, images_per_maskset, rows, cols, nmask);
   if (rc != SOSVO_OK) return rc;
   const int cell = min_distance >= 1 ? (int)lrint(min_distance) : 1;
-  int32_t* redo = (int32_t*)(ws + o_redo);
+  int32_t* redo = b.redo;
   if (large) {
     SOSVO_PROFILE(ctx, "gft_select_kernel");
     hipLaunchKernelGGL((gft_select_kernel<kCandCapLarge, 1024>), dim3(xcd_grid(nimg, nmask)), dim3(1024), 0, ctx->stream, cand, wcnt,
@@ -1808,12 +1801,13 @@ int32_t sosvo_describe_orb_rows(sosvo_ctx* ctx, const uint8_t* gray, int32_t nim
   SOSVO_REQUIRE(ctx, edge >= 19, "edge must cover the rotated 31x31 patch (>= 19)");
   SOSVO_REQUIRE(ctx, ((uintptr_t)desc & 7) == 0, "desc must be 8-byte aligned");
   if (nimg == 0) return SOSVO_OK;
-  const size_t bytes = (size_t)nimg * rows * cols;
-  const size_t o_tab = (bytes + 255) & ~(size_t)255;  // the rotated pattern of THIS call, next to the blurred images
-  int32_t rc = sosvo_ws_reserve(ctx, o_tab + sizeof(orb_pattern_table));
+  uint8_t* blurred;
+  orb_pattern_table* ptab;  // the rotated pattern of THIS call, next to the blurred images
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    blurred = cv.take<uint8_t>((size_t)nimg * rows * cols);
+    ptab = cv.take<orb_pattern_table>(1);
+  });
   if (rc != SOSVO_OK) return rc;
-  uint8_t* blurred = (uint8_t*)ctx->ws;
-  orb_pattern_table* ptab = (orb_pattern_table*)((char*)ctx->ws + o_tab);
   SOSVO_LAUNCH(ctx, orb_pattern_table_kernel, dim3(1), dim3(256), 0, ctx->stream, pattern, cos_a, sin_a, ptab);
   SOSVO_LAUNCH_CHECK(ctx);
   rc = launch_gauss7_rows(ctx, gray, (long long)rows * cols, nimg, rows, cols, blurred, (long long)rows * cols, row_range,

@@ -102,23 +102,6 @@ __global__ void rgbd_backproject_kernel(const float* __restrict__ depth, int row
   bearing[3 * i + 2] = Z / nrm;
 }
 
-// Stable position of a lane's element among the workgroup's valid elements of this round.
-// Returns the position (valid lanes only meaningful) and advances *s_running by the round total.
-__device__ __forceinline__ int block_compact_pos(bool valid, int* wave_off /*[5]*/, int* s_running, int tid) {
-  const int lane = tid & 63, wid = tid >> 6;
-  const unsigned long long bal = __ballot(valid);
-  __syncthreads();
-  if (lane == 0) wave_off[wid + 1] = __popcll(bal);
-  __syncthreads();
-  if (tid == 0) {
-    wave_off[0] = *s_running;
-    for (int w = 0; w < kThreads / 64; ++w) wave_off[w + 1] += wave_off[w];
-    *s_running = wave_off[kThreads / 64];
-  }
-  __syncthreads();
-  return wave_off[wid] + __popcll(bal & ((1ULL << lane) - 1ULL));
-}
-
 // The record of input frame `fr` (one workgroup) written at record `slot` of the outputs.
 __device__ __forceinline__ void stereo_assemble_frame(
     const int fr, const int slot, const sosvo_rig& rig, const float* __restrict__ kp_top, const float* __restrict__ kp_bot,
@@ -175,7 +158,7 @@ __device__ __forceinline__ void stereo_assemble_frame(
         sv_triangulate(az1, el1, az2, el2, rig.F_top, rig.F_bot, xyz);
         valid = valid && sv_range_ok(xyz, rig.min_range, rig.max_range);
       }
-      const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
+      const int pos = sosvo_block_compact_pos<kThreads / 64>(valid, wave_off, &s_running, tid);
       if (valid && pos < out_cap) {
         const size_t o = (size_t)slot * out_cap + pos;
         m_top[2 * o] = ut;
@@ -283,7 +266,7 @@ __device__ __forceinline__ void f2f_assemble_body(
             valid = sv_pixel_gate(u_train, 0.0, u_query, 0.0, -1.0, rig.f2f_max_hdiff);
         }
       }
-      const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
+      const int pos = sosvo_block_compact_pos<kThreads / 64>(valid, wave_off, &s_running, tid);
       if (valid && pos < corr_cap) {
         const size_t o = (size_t)pr * corr_cap + pos;
         const size_t qrow = (size_t)fr_cur * frame_cap + q, trow = (size_t)fr_ref * frame_cap + t;
@@ -366,7 +349,7 @@ __device__ __forceinline__ void f2f_assemble_tracked_body(
         sv_pano_angles(u, v, pano, &az, &el);
         sv_bearing(az, el, b);
       }
-      const int pos = block_compact_pos(valid, wave_off, &s_running, tid);
+      const int pos = sosvo_block_compact_pos<kThreads / 64>(valid, wave_off, &s_running, tid);
       if (valid && pos < corr_cap) {
         const size_t o = (size_t)pr * corr_cap + pos;
 #pragma unroll
@@ -405,6 +388,64 @@ __global__ __launch_bounds__(kThreads) void f2f_assemble_tracked_cyclic_kernel(
 }
 
 }  // namespace
+
+// ---- host bodies shared by twin entry points: `fn` is the public function's name, for its messages
+
+// what sosvo_stereo_assemble and sosvo_stereo_assemble_slots (table: its slot_of_frame) ask of their arguments
+#define SOSVO_STEREO_ASSEMBLE_ARGS_OK(ctx, table)                                                                                  \
+  SOSVO_REQUIRE(ctx, rig_host && kp_top && kp_bot && desc_top && desc_bot && n_top && n_bot && keys && order && (table),         \
+                "null input pointer");                                                                                           \
+  SOSVO_REQUIRE(ctx, m_top && m_bot && d_top && d_bot && X && b_top && b_bot && M, "null output pointer");                       \
+  SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= (1 << 20) && nmask > 0 && cap > 0 && out_cap > 0, "sizes out of range");         \
+  SOSVO_REQUIRE(ctx, cap <= (1 << SOSVO_KEY_SHIFT), "cap out of range")
+
+// the cyclic gate's periods: the views' column counts, positive integers
+static bool f2f_periods_ok(const sosvo_rig* rig) {
+  const double a = rig->pano_top[0], b = rig->pano_bot[0];
+  return a >= 1.0 && b >= 1.0 && a <= 16384.0 && b <= 16384.0 && a == floor(a) && b == floor(b);
+}
+#define SOSVO_F2F_PERIOD_MSG "the period (pano_top[0], pano_bot[0]) must be a positive integer up to 16384"
+
+// sosvo_f2f_assemble and sosvo_f2f_assemble_cyclic
+static int32_t f2f_assemble(sosvo_ctx* ctx, const char* fn, bool cyclic, const sosvo_rig* rig_host, const float* m_top,
+                            const float* m_bot, const double* X, const double* b_top, const double* b_bot, const int32_t* M,
+                            int32_t frame_cap, const int32_t* ref_frame, const int32_t* cur_frame, const uint32_t* keys_top,
+                            const int32_t* order_top, const uint32_t* keys_bot, const int32_t* order_bot, int32_t npairs,
+                            int32_t corr_cap, double* f, double* p, int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n,
+                            int32_t* n_topview) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE_FN(ctx, rig_host && m_top && m_bot && X && b_top && b_bot && M && ref_frame && cur_frame, "null input pointer");
+  SOSVO_REQUIRE_FN(ctx, keys_top && order_top && keys_bot && order_bot && f && p && cam && corr_q && corr_t && n, "null pointer");
+  SOSVO_REQUIRE_FN(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
+  SOSVO_REQUIRE_FN(ctx, !cyclic || f2f_periods_ok(rig_host), SOSVO_F2F_PERIOD_MSG);
+  if (npairs == 0) return SOSVO_OK;
+  SOSVO_LAUNCH_AS(ctx, cyclic ? "f2f_assemble_cyclic_kernel" : "f2f_assemble_kernel", cyclic ? f2f_assemble_cyclic_kernel : f2f_assemble_kernel,
+                  dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, b_top, b_bot, M, frame_cap, ref_frame, cur_frame,
+                  keys_top, order_top, keys_bot, order_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
+
+// sosvo_f2f_assemble_tracked and sosvo_f2f_assemble_tracked_cyclic
+static int32_t f2f_assemble_tracked(sosvo_ctx* ctx, const char* fn, bool cyclic, const sosvo_rig* rig_host, const float* m_top,
+                                    const float* m_bot, const double* X, const int32_t* M, int32_t frame_cap,
+                                    const int32_t* ref_frame, const float* trk_top, const float* trk_bot, const uint8_t* st_top,
+                                    const uint8_t* st_bot, int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam,
+                                    int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE_FN(ctx, rig_host && m_top && m_bot && X && M && ref_frame && trk_top && trk_bot && st_top && st_bot,
+                   "null input pointer");
+  SOSVO_REQUIRE_FN(ctx, f && p && cam && corr_q && corr_t && n, "null output pointer");
+  SOSVO_REQUIRE_FN(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
+  SOSVO_REQUIRE_FN(ctx, !cyclic || f2f_periods_ok(rig_host), SOSVO_F2F_PERIOD_MSG);
+  if (npairs == 0) return SOSVO_OK;
+  SOSVO_LAUNCH_AS(ctx, cyclic ? "f2f_assemble_tracked_cyclic_kernel" : "f2f_assemble_tracked_kernel",
+                  cyclic ? f2f_assemble_tracked_cyclic_kernel : f2f_assemble_tracked_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream,
+                  *rig_host, m_top, m_bot, X, M, frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t,
+                  n, n_topview);
+  SOSVO_LAUNCH_CHECK(ctx);
+  return SOSVO_OK;
+}
 
 extern "C" {
 
@@ -479,11 +520,7 @@ int32_t sosvo_stereo_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const f
                               int32_t nmask, int32_t cap, int32_t out_cap, float* m_top, float* m_bot, uint8_t* d_top,
                               uint8_t* d_bot, double* X, double* b_top, double* b_bot, int32_t* M, int32_t* n_cand) {
   SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig_host && kp_top && kp_bot && desc_top && desc_bot && n_top && n_bot && keys && order,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, m_top && m_bot && d_top && d_bot && X && b_top && b_bot && M, "null output pointer");
-  SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= (1 << 20) && nmask > 0 && cap > 0 && out_cap > 0, "sizes out of range");
-  SOSVO_REQUIRE(ctx, cap <= (1 << SOSVO_KEY_SHIFT), "cap out of range");
+  SOSVO_STEREO_ASSEMBLE_ARGS_OK(ctx, true);
   if (nframes == 0) return SOSVO_OK;
   SOSVO_LAUNCH(ctx,stereo_assemble_kernel, dim3(nframes), dim3(kThreads), 0, ctx->stream, *rig_host, kp_top, kp_bot,
                      reinterpret_cast<const uint4*>(desc_top), reinterpret_cast<const uint4*>(desc_bot), n_top, n_bot,
@@ -501,11 +538,7 @@ int32_t sosvo_stereo_assemble_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, c
                                     const int32_t* slot_of_frame, int32_t nmask, int32_t cap, int32_t out_cap, float* m_top,
                                     float* m_bot, uint8_t* d_top, uint8_t* d_bot, double* X, double* b_top, double* b_bot,
                                     int32_t* M, int32_t* n_cand) {
-  SOSVO_REQUIRE(ctx, rig_host && kp_top && kp_bot && desc_top && desc_bot && n_top && n_bot && keys && order && slot_of_frame,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, m_top && m_bot && d_top && d_bot && X && b_top && b_bot && M, "null output pointer");
-  SOSVO_REQUIRE(ctx, nframes >= 0 && nframes <= (1 << 20) && nmask > 0 && cap > 0 && out_cap > 0, "sizes out of range");
-  SOSVO_REQUIRE(ctx, cap <= (1 << SOSVO_KEY_SHIFT), "cap out of range");
+  SOSVO_STEREO_ASSEMBLE_ARGS_OK(ctx, slot_of_frame);
   for (int f0 = 0; f0 < nframes; f0 += kSosvoSlotArgFrames) {
     const int nf = nframes - f0 < kSosvoSlotArgFrames ? nframes - f0 : kSosvoSlotArgFrames;
     sosvo_slot_table tab;
@@ -519,31 +552,14 @@ int32_t sosvo_stereo_assemble_slots(sosvo_ctx* ctx, const sosvo_rig* rig_host, c
   return SOSVO_OK;
 }
 
-// the cyclic gate's periods: the views' column counts, positive integers
-static bool f2f_periods_ok(const sosvo_rig* rig) {
-  const double a = rig->pano_top[0], b = rig->pano_bot[0];
-  return a >= 1.0 && b >= 1.0 && a <= 16384.0 && b <= 16384.0 && a == floor(a) && b == floor(b);
-}
-
 int32_t sosvo_f2f_assemble_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
                                   const double* X, const double* b_top, const double* b_bot, const int32_t* M,
                                   int32_t frame_cap, const int32_t* ref_frame, const int32_t* cur_frame,
                                   const uint32_t* keys_top, const int32_t* order_top, const uint32_t* keys_bot,
                                   const int32_t* order_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
                                   int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && b_top && b_bot && M && ref_frame && cur_frame,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, keys_top && order_top && keys_bot && order_bot && f && p && cam && corr_q && corr_t && n,
-                "null pointer");
-  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
-  SOSVO_REQUIRE(ctx, f2f_periods_ok(rig_host), "the period (pano_top[0], pano_bot[0]) must be a positive integer up to 16384");
-  if (npairs == 0) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx, f2f_assemble_cyclic_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, b_top,
-               b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot, corr_cap, f, p, cam, corr_q,
-               corr_t, n, n_topview);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return f2f_assemble(ctx, __func__, true, rig_host, m_top, m_bot, X, b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top,
+                      order_top, keys_bot, order_bot, npairs, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
 }
 
 int32_t sosvo_f2f_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
@@ -552,18 +568,8 @@ int32_t sosvo_f2f_assemble(sosvo_ctx* ctx, const sosvo_rig* rig_host, const floa
                            const uint32_t* keys_top, const int32_t* order_top, const uint32_t* keys_bot,
                            const int32_t* order_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
                            int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && b_top && b_bot && M && ref_frame && cur_frame,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, keys_top && order_top && keys_bot && order_bot && f && p && cam && corr_q && corr_t && n,
-                "null pointer");
-  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
-  if (npairs == 0) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx,f2f_assemble_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X,
-                     b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top, order_top, keys_bot, order_bot,
-                     corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return f2f_assemble(ctx, __func__, false, rig_host, m_top, m_bot, X, b_top, b_bot, M, frame_cap, ref_frame, cur_frame, keys_top,
+                      order_top, keys_bot, order_bot, npairs, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
 }
 
 int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
@@ -571,16 +577,8 @@ int32_t sosvo_f2f_assemble_tracked(sosvo_ctx* ctx, const sosvo_rig* rig_host, co
                                    const float* trk_top, const float* trk_bot, const uint8_t* st_top, const uint8_t* st_bot,
                                    int32_t npairs, int32_t corr_cap, double* f, double* p, int32_t* cam, int32_t* corr_q,
                                    int32_t* corr_t, int32_t* n, int32_t* n_topview) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && M && ref_frame && trk_top && trk_bot && st_top && st_bot,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, f && p && cam && corr_q && corr_t && n, "null output pointer");
-  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
-  if (npairs == 0) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx, f2f_assemble_tracked_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, M,
-               frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return f2f_assemble_tracked(ctx, __func__, false, rig_host, m_top, m_bot, X, M, frame_cap, ref_frame, trk_top, trk_bot, st_top,
+                              st_bot, npairs, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
 }
 
 int32_t sosvo_f2f_assemble_tracked_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_host, const float* m_top, const float* m_bot,
@@ -588,17 +586,8 @@ int32_t sosvo_f2f_assemble_tracked_cyclic(sosvo_ctx* ctx, const sosvo_rig* rig_h
                                           const float* trk_top, const float* trk_bot, const uint8_t* st_top,
                                           const uint8_t* st_bot, int32_t npairs, int32_t corr_cap, double* f, double* p,
                                           int32_t* cam, int32_t* corr_q, int32_t* corr_t, int32_t* n, int32_t* n_topview) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, rig_host && m_top && m_bot && X && M && ref_frame && trk_top && trk_bot && st_top && st_bot,
-                "null input pointer");
-  SOSVO_REQUIRE(ctx, f && p && cam && corr_q && corr_t && n, "null output pointer");
-  SOSVO_REQUIRE(ctx, npairs >= 0 && npairs <= (1 << 20) && frame_cap > 0 && corr_cap > 0, "sizes out of range");
-  SOSVO_REQUIRE(ctx, f2f_periods_ok(rig_host), "the period (pano_top[0], pano_bot[0]) must be a positive integer up to 16384");
-  if (npairs == 0) return SOSVO_OK;
-  SOSVO_LAUNCH(ctx, f2f_assemble_tracked_cyclic_kernel, dim3(npairs), dim3(kThreads), 0, ctx->stream, *rig_host, m_top, m_bot, X, M,
-               frame_cap, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
-  SOSVO_LAUNCH_CHECK(ctx);
-  return SOSVO_OK;
+  return f2f_assemble_tracked(ctx, __func__, true, rig_host, m_top, m_bot, X, M, frame_cap, ref_frame, trk_top, trk_bot, st_top,
+                              st_bot, npairs, corr_cap, f, p, cam, corr_q, corr_t, n, n_topview);
 }
 
 }  // extern "C"

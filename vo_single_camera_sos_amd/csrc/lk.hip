@@ -490,15 +490,32 @@ LkLevels lk_store_levels(const sosvo_lk_images& im) {
 int32_t lk_build_levels(sosvo_ctx* ctx, const LkLevels& t, int nimg, int levels, const int32_t* row_range, bool cyclic = false) {
   for (int l = 0; l + 1 < levels; ++l) {
     const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), nimg);
-    if (cyclic)
-      SOSVO_LAUNCH(ctx, lk_pyr_down_cyclic_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                   const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
-    else
-      SOSVO_LAUNCH(ctx, lk_pyr_down_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                   const_cast<uint8_t*>(t.base[l + 1]), t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
+    SOSVO_LAUNCH_AS(ctx, cyclic ? "lk_pyr_down_cyclic_kernel" : "lk_pyr_down_kernel", cyclic ? lk_pyr_down_cyclic_kernel : lk_pyr_down_kernel,
+                    grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l], const_cast<uint8_t*>(t.base[l + 1]),
+                    t.rows[l + 1], t.cols[l + 1], row_range, nimg > 1 ? nimg / 2 : 1, t.rows[0], l);
     SOSVO_LAUNCH_CHECK(ctx);
   }
   return SOSVO_OK;
+}
+
+// the tracker's arguments over a levels table, in LkArgs's member order (fb_max2, the last: lk_launch sets it per pass)
+LkArgs lk_args(const LkLevels& lv, int nimg, int levels, int cap, int half, int max_iter, double eps, double min_eig, int initial_flow) {
+  return LkArgs{lv, nimg, levels, cap, half, max_iter, initial_flow, eps * eps, min_eig, -1.0};
+}
+
+// sosvo_gray_pyramid and sosvo_gray_pyramid_cyclic
+int32_t gray_pyramid(sosvo_ctx* ctx, const char* fn, bool cyclic, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols,
+                     int32_t levels, const int32_t* row_range, uint8_t* pyr) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE_FN(ctx, gray, "null pointer");
+  SOSVO_REQUIRE_FN(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
+  SOSVO_REQUIRE_FN(ctx, !cyclic || lk_cyclic_cols_ok(cols, levels), "cyclic columns need cols to be a multiple of 2^(levels - 1)");
+  SOSVO_REQUIRE_FN(ctx, pyr || levels == 1, "null pointer");
+  SOSVO_REQUIRE_FN(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
+  if (nimg == 0) return SOSVO_OK;
+  LkLevels t;
+  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
+  return lk_build_levels(ctx, t, nimg, levels, row_range, cyclic);
 }
 
 // the forward launch and, with `back`, the backward one (a: everything but initial_flow's reset and fb_max2, set here)
@@ -513,8 +530,7 @@ int32_t lk_launch(sosvo_ctx* ctx, LkArgs a, const int32_t* row_range, const int3
   // (the profile labels a launch with its instantiation, as SOSVO_LAUNCH does)
   auto launch = [&](auto kernel, const char* name, const int32_t* from, const int32_t* to, const float* start, float* out, float* e,
                     const float* ref) {
-    SOSVO_PROFILE(ctx, name);
-    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, ctx->stream, a, row_range, from, to, start, n, out, status, e, ref, store_pt);
+    SOSVO_LAUNCH_AS(ctx, name, kernel, grid, dim3(64), 0, ctx->stream, a, row_range, from, to, start, n, out, status, e, ref, store_pt);
   };
   auto pass = [&](const int32_t* from, const int32_t* to, const float* start, float* out, float* e, const float* ref) {
     if (cyclic) {
@@ -662,12 +678,9 @@ int32_t sosvo_lk_images_fill(sosvo_ctx* ctx, const sosvo_lk_images& im, int32_t 
     SOSVO_LAUNCH_CHECK(ctx);
     for (int l = 0; l + 1 < levels; ++l) {
       const dim3 grid(cdiv(t.cols[l + 1], kPyrTileX), cdiv(t.rows[l + 1], kPyrTileY), 2 * nf);
-      if (cyclic)
-        SOSVO_LAUNCH(ctx, lk_pyr_down_slots_cyclic_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l],
-                     t.cols[l], im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
-      else
-        SOSVO_LAUNCH(ctx, lk_pyr_down_slots_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream, t.base[l], t.rows[l], t.cols[l],
-                     im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
+      SOSVO_LAUNCH_AS(ctx, cyclic ? "lk_pyr_down_slots_cyclic_kernel" : "lk_pyr_down_slots_kernel",
+                      cyclic ? lk_pyr_down_slots_cyclic_kernel : lk_pyr_down_slots_kernel, grid, dim3(kPyrTileX, kPyrTileY), 0, ctx->stream,
+                      t.base[l], t.rows[l], t.cols[l], im.level[l + 1], t.rows[l + 1], t.cols[l + 1], row_range, nf, tab, im.slots, im.rows, l);
       SOSVO_LAUNCH_CHECK(ctx);
     }
   }
@@ -690,17 +703,9 @@ int32_t sosvo_lk_images_track(sosvo_ctx* ctx, const sosvo_lk_images& im, const s
   SOSVO_REQUIRE(ctx, !cyclic || (lk_cyclic_cols_ok(im.cols, o.levels) && (im.cols >> (o.levels - 1)) >= 2 * o.half + 3),
                 "cyclic columns need cols % 2^(levels - 1) == 0 and 2 half + 3 columns on the top level");
   if (nprob == 0) return SOSVO_OK;
-  LkArgs a;
-  a.lv = lk_store_levels(im);
-  for (int l = o.levels; l < kLkMaxLevels; ++l) a.lv.base[l] = nullptr;  // (not built, never read)
-  a.nimg = 2 * im.slots;
-  a.levels = o.levels;
-  a.cap = cap;
-  a.half = o.half;
-  a.max_iter = o.max_iter;
-  a.initial_flow = 0;
-  a.eps2 = o.eps * o.eps;
-  a.min_eig = o.min_eig;
+  LkLevels t = lk_store_levels(im);
+  for (int l = o.levels; l < kLkMaxLevels; ++l) t.base[l] = nullptr;  // (not built, never read)
+  const LkArgs a = lk_args(t, 2 * im.slots, o.levels, cap, o.half, o.max_iter, o.eps, o.min_eig, 0);
   return lk_launch(ctx, a, row_range, from_img, to_img, nprob, pts, store_pt, n, next_pts, status, err, o.fb_max > 0.0 ? back : nullptr,
                    o.fb_max, cyclic);
 }
@@ -716,29 +721,12 @@ int32_t sosvo_gray_pyramid_bytes(sosvo_ctx* ctx, int32_t nimg, int32_t rows, int
 
 int32_t sosvo_gray_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
                            const int32_t* row_range, uint8_t* pyr) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, gray, "null pointer");
-  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
-  SOSVO_REQUIRE(ctx, pyr || levels == 1, "null pointer");
-  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
-  if (nimg == 0) return SOSVO_OK;
-  LkLevels t;
-  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
-  return lk_build_levels(ctx, t, nimg, levels, row_range);
+  return gray_pyramid(ctx, __func__, false, gray, nimg, rows, cols, levels, row_range, pyr);
 }
 
 int32_t sosvo_gray_pyramid_cyclic(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t levels,
                                   const int32_t* row_range, uint8_t* pyr) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, gray, "null pointer");
-  SOSVO_REQUIRE(ctx, lk_sizes_ok(nimg, rows, cols, levels), "sizes out of range (levels 1..4, rows and cols 1..16384)");
-  SOSVO_REQUIRE(ctx, lk_cyclic_cols_ok(cols, levels), "cyclic columns need cols to be a multiple of 2^(levels - 1)");
-  SOSVO_REQUIRE(ctx, pyr || levels == 1, "null pointer");
-  SOSVO_REQUIRE(ctx, row_range == nullptr || nimg % 2 == 0, "row_range needs the two views' images (nimg even, view-major)");
-  if (nimg == 0) return SOSVO_OK;
-  LkLevels t;
-  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
-  return lk_build_levels(ctx, t, nimg, levels, row_range, true);
+  return gray_pyramid(ctx, __func__, true, gray, nimg, rows, cols, levels, row_range, pyr);
 }
 
 int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, int32_t nimg, int32_t rows, int32_t cols,
@@ -762,16 +750,9 @@ int32_t sosvo_track_lk(sosvo_ctx* ctx, const uint8_t* gray, const uint8_t* pyr, 
                 "cyclic columns need 2 half + 3 columns on the top level (the template fits one period)");
   SOSVO_REQUIRE(ctx, back == nullptr || fb_max > 0.0, "fb_max must be positive with a back buffer");
   if (nprob == 0 || nimg == 0) return SOSVO_OK;
-  LkArgs a;
-  lk_levels(gray, pyr, nimg, rows, cols, levels, &a.lv);
-  a.nimg = nimg;
-  a.levels = levels;
-  a.cap = cap;
-  a.half = half;
-  a.max_iter = max_iter;
-  a.initial_flow = (flags & SOSVO_LK_INITIAL_FLOW) ? 1 : 0;
-  a.eps2 = eps * eps;
-  a.min_eig = min_eig;
+  LkLevels t;
+  lk_levels(gray, pyr, nimg, rows, cols, levels, &t);
+  const LkArgs a = lk_args(t, nimg, levels, cap, half, max_iter, eps, min_eig, (flags & SOSVO_LK_INITIAL_FLOW) ? 1 : 0);
   return lk_launch(ctx, a, row_range, prev_img, next_img, nprob, prev_pts, nullptr, n, next_pts, status, err, back, fb_max, cyclic);
 }
 
@@ -790,24 +771,21 @@ int32_t sosvo_refine_stereo_lk(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg
   const int F = nimg / 2, P = F * nmask;
   if (P == 0) return SOSVO_OK;
   // the tracker's tables, in the context's scratch
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return at;
-  };
   const size_t n_pts = (size_t)P * cap;
-  const size_t o_start = carve(sizeof(float) * 2 * n_pts), o_next = carve(sizeof(float) * 2 * n_pts);
-  const size_t o_err = carve(sizeof(float) * n_pts), o_idx = carve(sizeof(int32_t) * n_pts), o_trk = carve(n_pts);
-  const size_t o_count = carve(sizeof(int32_t) * P), o_from = carve(sizeof(int32_t) * P), o_to = carve(sizeof(int32_t) * P);
-  int32_t rc = sosvo_ws_reserve(ctx, off);
+  float *start, *next, *err;
+  int32_t *idx, *count, *from, *to;
+  uint8_t* tracked;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    start = cv.take<float>(2 * n_pts);
+    next = cv.take<float>(2 * n_pts);
+    err = cv.take<float>(n_pts);
+    idx = cv.take<int32_t>(n_pts);
+    tracked = cv.take<uint8_t>(n_pts);
+    count = cv.take<int32_t>(P);
+    from = cv.take<int32_t>(P);
+    to = cv.take<int32_t>(P);
+  });
   if (rc != SOSVO_OK) return rc;
-  char* w = reinterpret_cast<char*>(ctx->ws);
-  float *start = reinterpret_cast<float*>(w + o_start), *next = reinterpret_cast<float*>(w + o_next);
-  float* err = reinterpret_cast<float*>(w + o_err);
-  int32_t *idx = reinterpret_cast<int32_t*>(w + o_idx), *count = reinterpret_cast<int32_t*>(w + o_count);
-  int32_t *from = reinterpret_cast<int32_t*>(w + o_from), *to = reinterpret_cast<int32_t*>(w + o_to);
-  uint8_t* tracked = reinterpret_cast<uint8_t*>(w + o_trk);
   const double max_shift = o.max_shift > 0.0 ? o.max_shift : (double)o.half;
   StereoLkGate g;  // sv_pixel_gate's switches: the du side is on for max_hdiff > 0, the dv side for min_disp >= 0
   g.max_du = stereo_max_hdiff > 0 ? stereo_max_hdiff : HUGE_VAL;
@@ -817,16 +795,9 @@ int32_t sosvo_refine_stereo_lk(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg
   SOSVO_LAUNCH(ctx, stereo_lk_gather_kernel, dim3(P), dim3(256), 0, ctx->stream, nmask, F, cap, kp_top, n_top, kp_bot, n_bot, keys, g,
                start, next, idx, count, from, to, status);
   SOSVO_LAUNCH_CHECK(ctx);
-  LkArgs a;
-  lk_levels(gray, nullptr, nimg, rows, cols, 1, &a.lv);
-  a.nimg = nimg;
-  a.levels = 1;
-  a.cap = cap;
-  a.half = o.half;
-  a.max_iter = o.max_iter;
-  a.initial_flow = 1;
-  a.eps2 = o.eps * o.eps;
-  a.min_eig = o.min_eig;
+  LkLevels t;
+  lk_levels(gray, nullptr, nimg, rows, cols, 1, &t);
+  const LkArgs a = lk_args(t, nimg, 1, cap, o.half, o.max_iter, o.eps, o.min_eig, 1);
   rc = lk_launch(ctx, a, row_range, from, to, P, start, nullptr, count, next, tracked, err, nullptr, 0.0);
   if (rc != SOSVO_OK) return rc;
   SOSVO_LAUNCH(ctx, stereo_lk_accept_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, ctx->stream, P, cap, max_shift, count,

@@ -758,9 +758,8 @@ int32_t sosvo_match_hamming(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t
   if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, k, keys, &plan)) return rc;
   // (the profile labels a launch with its instantiation, as SOSVO_LAUNCH does)
   auto launch = [&](auto kernel, const char* name) {
-    SOSVO_PROFILE(ctx, name);
-    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride, t_stride,
-                       plan.nsplit, keys);
+    SOSVO_LAUNCH_AS(ctx, name, kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, nq, nt, q_slot, t_slot, q_stride, t_stride,
+                    plan.nsplit, keys);
   };
   if (k == 1) {
     if (plan.qt == 2) launch(match_hamming_mfma_kernel<2, 1>, "(match_hamming_mfma_kernel<2, 1>)");
@@ -773,26 +772,37 @@ int32_t sosvo_match_hamming(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t
   return SOSVO_OK;
 }
 
+// The argument checks and casts that sosvo_match_hamming_gated, ..._gated_cyclic and ..._ratio have in common, over the
+// parameter names they share.  Each entry point runs them in the order in which its checks have always fired: the first
+// failing one decides the message.
+#define MATCH_SIZES_OK(ctx)                                                                                    \
+  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");                                      \
+  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");               \
+  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");             \
+  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range")
+#define MATCH_MAX_DISTANCE_OK(ctx) SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)")
+#define MATCH_GATED_HEAD_OK(ctx)                                                                         \
+  SOSVO_REQUIRE(ctx, q_desc && t_desc && q_pos && t_pos && nq && nt && keys, "null pointer");            \
+  MATCH_SIZES_OK(ctx);                                                                                   \
+  MATCH_MAX_DISTANCE_OK(ctx)
+#define MATCH_DESC_ALIGNED(ctx) \
+  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0, "descriptor arrays must be 16-byte aligned")
+#define MATCH_POS_ALIGNED(ctx) SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned")
+#define MATCH_CASTS                                                                                             \
+  const uint4 *q4 = reinterpret_cast<const uint4*>(q_desc), *t4 = reinterpret_cast<const uint4*>(t_desc);      \
+  const float2 *qp = reinterpret_cast<const float2*>(q_pos), *tp = reinterpret_cast<const float2*>(t_pos)
+
 int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const uint8_t* t_desc, const float* q_pos,
                                   const float* t_pos, const int32_t* nq, const int32_t* nt, const int32_t* q_slot,
                                   const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride, int32_t t_stride,
                                   double min_dv, double max_du, int32_t max_distance, uint32_t* keys) {
   SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, q_desc && t_desc && q_pos && t_pos && nq && nt && keys, "null pointer");
-  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
-  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");
-  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");
-  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range");
-  SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)");
+  MATCH_GATED_HEAD_OK(ctx);
   SOSVO_REQUIRE(ctx, min_dv == min_dv && max_du == max_du, "min_dv / max_du must not be NaN");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0,
-                "descriptor arrays must be 16-byte aligned");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned");
+  MATCH_DESC_ALIGNED(ctx);
+  MATCH_POS_ALIGNED(ctx);
   if (nprob == 0) return SOSVO_OK;
-  const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
-  const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
-  const float2* qp = reinterpret_cast<const float2*>(q_pos);
-  const float2* tp = reinterpret_cast<const float2*>(t_pos);
+  MATCH_CASTS;
   MmaPlan plan;
   if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan)) return rc;
   // sv_pixel_gate's switches: the du side is on for max_du > 0, the dv side for min_dv >= 0
@@ -800,9 +810,8 @@ int32_t sosvo_match_hamming_gated(sosvo_ctx* ctx, const uint8_t* q_desc, const u
   const bool dv = min_dv >= 0;
   const uint32_t cap = (uint32_t)max_distance;
   auto launch = [&](auto kernel, const char* name) {
-    SOSVO_PROFILE(ctx, name);
-    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
-                       q_stride, t_stride, plan.nsplit, min_dv, du, cap, keys);
+    SOSVO_LAUNCH_AS(ctx, name, kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                    q_stride, t_stride, plan.nsplit, min_dv, du, cap, keys);
   };
   if (plan.qt == 2) {
     if (dv) launch(match_hamming_gated_mfma_kernel<2, true>, "(match_hamming_gated_mfma_kernel<2, true>)");
@@ -820,22 +829,13 @@ int32_t sosvo_match_hamming_gated_cyclic(sosvo_ctx* ctx, const uint8_t* q_desc, 
                                          const int32_t* t_slot, int32_t nprob, int32_t n_forward, int32_t q_stride,
                                          int32_t t_stride, double max_du, double period, int32_t max_distance, uint32_t* keys) {
   SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, q_desc && t_desc && q_pos && t_pos && nq && nt && keys, "null pointer");
-  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
-  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");
-  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");
-  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range");
-  SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)");
+  MATCH_GATED_HEAD_OK(ctx);
   SOSVO_REQUIRE(ctx, max_du == max_du, "max_du must not be NaN");
   SOSVO_REQUIRE(ctx, period >= 1.0 && period <= 16384.0 && period == floor(period), "the period must be a positive integer up to 16384");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0,
-                "descriptor arrays must be 16-byte aligned");
-  SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned");
+  MATCH_DESC_ALIGNED(ctx);
+  MATCH_POS_ALIGNED(ctx);
   if (nprob == 0) return SOSVO_OK;
-  const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
-  const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
-  const float2* qp = reinterpret_cast<const float2*>(q_pos);
-  const float2* tp = reinterpret_cast<const float2*>(t_pos);
+  MATCH_CASTS;
   MmaPlan plan;
   if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan)) return rc;
   // the switch is sv_pixel_gate's: the gate is on for max_du > 0; off, both sides pass everything
@@ -843,9 +843,8 @@ int32_t sosvo_match_hamming_gated_cyclic(sosvo_ctx* ctx, const uint8_t* q_desc, 
   const double wrap = max_du > 0 ? period - max_du : HUGE_VAL;
   const uint32_t cap = (uint32_t)max_distance;
   auto launch = [&](auto kernel, const char* name) {
-    SOSVO_PROFILE(ctx, name);
-    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
-                       q_stride, t_stride, plan.nsplit, du, wrap, cap, keys);
+    SOSVO_LAUNCH_AS(ctx, name, kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                    q_stride, t_stride, plan.nsplit, du, wrap, cap, keys);
   };
   if (plan.qt == 2) launch(match_hamming_gated_cyclic_mfma_kernel<2>, "(match_hamming_gated_cyclic_mfma_kernel<2>)");
   else launch(match_hamming_gated_cyclic_mfma_kernel<1>, "(match_hamming_gated_cyclic_mfma_kernel<1>)");
@@ -864,34 +863,26 @@ int32_t sosvo_match_hamming_ratio(sosvo_ctx* ctx, const uint8_t* q_desc, const u
   SOSVO_REQUIRE(ctx, (q_pos != nullptr) == (t_pos != nullptr), "q_pos and t_pos go together (both NULL: the plain form)");
   const bool gated = q_pos != nullptr;
   SOSVO_REQUIRE(ctx, ratio_64ths >= 1 && ratio_64ths <= 63, "ratio_64ths out of range (1..63)");
-  SOSVO_REQUIRE(ctx, nprob >= 0 && nprob <= 65535, "nprob out of range");
-  SOSVO_REQUIRE(ctx, n_forward >= 0 && n_forward <= nprob, "n_forward out of range (0..nprob)");
-  SOSVO_REQUIRE(ctx, q_stride > 0 && q_stride <= (1 << SOSVO_KEY_SHIFT), "q_stride out of range");
-  SOSVO_REQUIRE(ctx, t_stride > 0 && t_stride <= (1 << SOSVO_KEY_SHIFT), "t_stride out of range");
+  MATCH_SIZES_OK(ctx);
   if (gated) {
-    SOSVO_REQUIRE(ctx, max_distance >= 0 && max_distance <= 256, "max_distance out of range (0..256)");
+    MATCH_MAX_DISTANCE_OK(ctx);
     SOSVO_REQUIRE(ctx, min_dv == min_dv && max_du == max_du, "min_dv / max_du must not be NaN");
-    SOSVO_REQUIRE(ctx, ((uintptr_t)q_pos & 7) == 0 && ((uintptr_t)t_pos & 7) == 0, "position arrays must be 8-byte aligned");
+    MATCH_POS_ALIGNED(ctx);
   } else {
     SOSVO_REQUIRE(ctx, max_distance == 256, "max_distance must be 256 in the plain form (no positions)");
   }
-  SOSVO_REQUIRE(ctx, ((uintptr_t)q_desc & 15) == 0 && ((uintptr_t)t_desc & 15) == 0,
-                "descriptor arrays must be 16-byte aligned");
+  MATCH_DESC_ALIGNED(ctx);
   SOSVO_REQUIRE(ctx, ((uintptr_t)keys & 3) == 0 && ((uintptr_t)rivals & 3) == 0, "keys and rivals must be 4-byte aligned");
   if (nprob == 0) return SOSVO_OK;
-  const uint4* q4 = reinterpret_cast<const uint4*>(q_desc);
-  const uint4* t4 = reinterpret_cast<const uint4*>(t_desc);
-  const float2* qp = reinterpret_cast<const float2*>(q_pos);
-  const float2* tp = reinterpret_cast<const float2*>(t_pos);
+  MATCH_CASTS;
   MmaPlan plan;
   if (const int32_t rc = mma_plan(ctx, nprob, q_stride, t_stride, 1, keys, &plan, rivals)) return rc;
   const double du = max_du > 0 ? max_du : HUGE_VAL;  // (sv_pixel_gate's switches, as in sosvo_match_hamming_gated)
   const bool dv = gated && min_dv >= 0;
   const uint32_t cap = (uint32_t)max_distance, ratio = (uint32_t)ratio_64ths;
   auto launch = [&](auto kernel, const char* name) {
-    SOSVO_PROFILE(ctx, name);
-    hipLaunchKernelGGL(kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
-                       q_stride, t_stride, plan.nsplit, min_dv, du, cap, ratio, keys, rivals);
+    SOSVO_LAUNCH_AS(ctx, name, kernel, plan.grid, dim3(kThreads), 0, ctx->stream, q4, t4, qp, tp, nq, nt, q_slot, t_slot, n_forward,
+                    q_stride, t_stride, plan.nsplit, min_dv, du, cap, ratio, keys, rivals);
   };
   if (plan.qt == 2) {
     if (!gated) launch(match_hamming_ratio_mfma_kernel<2, false, false>, "(match_hamming_ratio_mfma_kernel<2, false, false>)");

@@ -1815,10 +1815,8 @@ int32_t build_pyramid(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, i
   return SOSVO_OK;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// Scratch layout shared by the three ORB entry points: pyramid levels, FAST scores (same layout), blurred levels (same
-// layout), local-maximum flags, mask bounding boxes, resize taps.
+// Scratch of the three ORB entry points, carved by orb_scratch below in this order (score and blur are laid out like pyr;
+// what only the detector or only the descriptors need takes no room without them).
 struct OrbScratch {
   uint8_t *pyr, *score, *blur;
   unsigned long long* flags;
@@ -1826,28 +1824,22 @@ struct OrbScratch {
   int32_t* lvl_rows;  // [kLevels][2]: blurred rows a detected keypoint's descriptor can read (written with the taps)
   uint2* rowtab;      // [kLevels][rowtab_stride]: orb_level_pass_kernel's row tables
   int rowtab_stride;
-  size_t bbox_bytes, bytes;
+  size_t bbox_bytes;
 };
-OrbScratch orb_scratch(const Pyr& P, int nimg, int nsets, bool detect, bool describe, char* base) {
+OrbScratch orb_scratch(Carver& cv, const Pyr& P, int nimg, int nsets, bool detect, bool describe) {
   OrbScratch o;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += al256(bytes);
-    return p;
-  };
   const size_t lv = (size_t)nimg * P.total;
-  o.pyr = (uint8_t*)take(lv);
-  o.score = (uint8_t*)take(detect ? lv : 0);
-  o.blur = (uint8_t*)take(describe ? lv : 0);
-  o.flags = (unsigned long long*)take(detect ? sizeof(unsigned long long) * (size_t)nimg * P.ftotal : 0);
-  o.bbox_bytes = detect ? (size_t)nsets * kLevels * 32 * 4 * sizeof(uint32_t) : 0;
-  o.bbox = (uint32_t*)take(o.bbox_bytes);
-  o.taps = (uint32_t*)take(sizeof(uint32_t) * (size_t)(P.ttotal > 0 ? P.ttotal : 1));
-  o.lvl_rows = (int32_t*)take(sizeof(int32_t) * 2 * kLevels);
+  o.pyr = cv.take<uint8_t>(lv);
+  o.score = cv.take<uint8_t>(detect ? lv : 0);
+  o.blur = cv.take<uint8_t>(describe ? lv : 0);
+  o.flags = cv.take<unsigned long long>(detect ? (size_t)nimg * P.ftotal : 0);
+  const size_t bbox_words = detect ? (size_t)nsets * kLevels * 32 * 4 : 0;
+  o.bbox_bytes = bbox_words * sizeof(uint32_t);
+  o.bbox = cv.take<uint32_t>(bbox_words);
+  o.taps = cv.take<uint32_t>((size_t)(P.ttotal > 0 ? P.ttotal : 1));
+  o.lvl_rows = cv.take<int32_t>(2 * kLevels);
   o.rowtab_stride = P.h[0] + 6;
-  o.rowtab = (uint2*)take(detect ? sizeof(uint2) * (size_t)kLevels * o.rowtab_stride : 0);
-  o.bytes = off;
+  o.rowtab = cv.take<uint2>(detect ? (size_t)kLevels * o.rowtab_stride : 0);
   return o;
 }
 
@@ -2001,9 +1993,9 @@ int32_t sosvo_detect_orb(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* ma
   if (nimg == 0) return SOSVO_OK;
   const Pyr P = make_pyr(rows, cols, nfeatures);
   const int nsets = cdiv(nimg, images_per_maskset);
-  int32_t rc = sosvo_ws_reserve(ctx, orb_scratch(P, nimg, nsets, true, false, nullptr).bytes);
+  OrbScratch W;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { W = orb_scratch(cv, P, nimg, nsets, true, false); });
   if (rc != SOSVO_OK) return rc;
-  const OrbScratch W = orb_scratch(P, nimg, nsets, true, false, (char*)ctx->ws);
   const bool fused = orb_level_passes_ok(P);
   rc = fused ? run_orb_level_passes(ctx, gray, nimg, rows, cols, P, W, false, nullptr)
              : build_pyramid(ctx, gray, nimg, rows, cols, P, P.ndet, W.pyr, W.taps);
@@ -2022,9 +2014,9 @@ int32_t sosvo_describe_orb_levels(sosvo_ctx* ctx, const uint8_t* gray, int32_t n
   SOSVO_REQUIRE(ctx, ((uintptr_t)desc & 7) == 0, "desc must be 8-byte aligned");
   if (nimg == 0) return SOSVO_OK;
   const Pyr P = make_pyr(rows, cols, 0);
-  int32_t rc = sosvo_ws_reserve(ctx, orb_scratch(P, nimg, 1, false, true, nullptr).bytes);
+  OrbScratch W;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { W = orb_scratch(cv, P, nimg, 1, false, true); });
   if (rc != SOSVO_OK) return rc;
-  const OrbScratch W = orb_scratch(P, nimg, 1, false, true, (char*)ctx->ws);
   rc = build_pyramid(ctx, gray, nimg, rows, cols, P, P.nlev, W.pyr, W.taps);  // keypoints of any level: the whole pyramid
   if (rc != SOSVO_OK) return rc;
   return run_orb_describe(ctx, gray, nimg, rows, cols, nmask, cap, P, P.nlev, W, kp4, n, pattern, desc, kp_xy, false);
@@ -2042,9 +2034,9 @@ int32_t sosvo_detect_describe_orb(sosvo_ctx* ctx, const uint8_t* gray, const uin
   if (nimg == 0) return SOSVO_OK;
   const Pyr P = make_pyr(rows, cols, nfeatures);
   const int nsets = cdiv(nimg, images_per_maskset);
-  int32_t rc = sosvo_ws_reserve(ctx, orb_scratch(P, nimg, nsets, true, true, nullptr).bytes);
+  OrbScratch W;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { W = orb_scratch(cv, P, nimg, nsets, true, true); });
   if (rc != SOSVO_OK) return rc;
-  const OrbScratch W = orb_scratch(P, nimg, nsets, true, true, (char*)ctx->ws);
   // ONE pyramid for both halves, built only as far as a keypoint can come from (the levels with a quota and more than the
   // 31-px border): the detector's keypoints all lie on those levels
   const bool fused = orb_level_passes_ok(P);
@@ -2067,12 +2059,13 @@ int32_t sosvo_detect_fast(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* m
   SOSVO_REQUIRE(ctx, cap > 0 && cap <= 16384 && threshold >= 0 && threshold <= 254, "bad detector parameters");
   if (nimg == 0) return SOSVO_OK;
   const int words = cdiv(cols, 64);
-  const size_t score_bytes = ((size_t)nimg * rows * cols + 255) & ~(size_t)255;
-  const size_t flag_bytes = sizeof(unsigned long long) * (size_t)nimg * rows * words;
-  int32_t rc = sosvo_ws_reserve(ctx, score_bytes + flag_bytes);
+  uint8_t* score;
+  unsigned long long* flags;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    score = cv.take<uint8_t>((size_t)nimg * rows * cols);
+    flags = cv.take<unsigned long long>((size_t)nimg * rows * words);
+  });
   if (rc != SOSVO_OK) return rc;
-  uint8_t* score = (uint8_t*)ctx->ws;
-  unsigned long long* flags = (unsigned long long*)((char*)ctx->ws + score_bytes);
   {
     const int32_t rc2 = launch_fast_score(ctx, gray, (long long)rows * cols, nimg, rows, cols, threshold, 0, rows, score,
                                           (long long)rows * cols, nullptr, 0);
@@ -2098,10 +2091,9 @@ int32_t sosvo_detect_agast(sosvo_ctx* ctx, const uint8_t* gray, const uint32_t* 
   SOSVO_REQUIRE(ctx, nmask >= 1 && nmask <= 32, "nmask out of range (1..32)");
   SOSVO_REQUIRE(ctx, cap > 0 && cap <= 16384 && threshold >= 0 && threshold <= 254, "bad detector parameters");
   if (nimg == 0) return SOSVO_OK;
-  const size_t score_bytes = ((size_t)nimg * rows * cols + 255) & ~(size_t)255;
-  int32_t rc = sosvo_ws_reserve(ctx, score_bytes);
+  uint8_t* score;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) { score = cv.take<uint8_t>((size_t)nimg * rows * cols); });
   if (rc != SOSVO_OK) return rc;
-  uint8_t* score = (uint8_t*)ctx->ws;
   rc = launch_fast_score(ctx, gray, (long long)rows * cols, nimg, rows, cols, threshold, 0, rows, score, (long long)rows * cols,
                          nullptr, 0);
   if (rc != SOSVO_OK) return rc;

@@ -10,17 +10,6 @@
 
 namespace {
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += (count * sizeof(T) + 255) & ~(size_t)255;
-    return p;
-  }
-};
-
 // the ORB detector's extra buffers (sosvo_detect_describe_orb): oriented keypoints, responses, the mask pyramid.  Carved
 // after everything else, and only for ORB, so that the other detectors' workspaces keep their sizes and layout.
 struct OrbBufs {
@@ -964,7 +953,7 @@ size_t sosvo_frame_pair_batch_streams_workspace(const sosvo_batch_cfg* cfg, int3
     c.n_pairs = hi - lo;
     const size_t bytes = sosvo_frame_pair_batch_workspace(&c);
     if (bytes == 0) return 0;
-    total += (bytes + 255) & ~(size_t)255;
+    total += sosvo_round256(bytes);
   }
   return total;
 }
@@ -1005,7 +994,7 @@ static int32_t sosvo_frame_pair_batch_streams_impl(sosvo_ctx* ctx, const sosvo_r
     part_range(cfg->n_pairs, s, n_streams, &lo, &hi);
     sosvo_batch_cfg c = *cfg;
     c.n_pairs = hi - lo;
-    bytes[s] = (sosvo_frame_pair_batch_workspace(&c) + 255) & ~(size_t)255;
+    bytes[s] = sosvo_round256(sosvo_frame_pair_batch_workspace(&c));
   }
   if (ctx->sub_pending) {
     // un-joined parts of an earlier ..._enqueue call may still run.  A stream capture cannot depend on them (their events

@@ -1077,10 +1077,6 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
     SOSVO_PROFILE(ctx, #kernel);                        \
     hipLaunchKernelGGL((kernel<SeedT>), __VA_ARGS__);   \
   } while (0)
-#define SOSVO_REQUIRE_FN(ctx, cond, msg)                               \
-  do {                                                                 \
-    if (!(cond)) return sosvo_fail((ctx), SOSVO_ERR_ARG, fn, msg);     \
-  } while (0)
   SOSVO_REQUIRE_FN(ctx, f && p && n && T_out && inlier_mask && inlier_idx && n_inliers && info, "null pointer");
   SOSVO_REQUIRE_FN(ctx, cam == nullptr || (cam_off && cam_rot), "cam given without cam_off / cam_rot");
   SOSVO_REQUIRE_FN(ctx, ncam >= 1 && ncam <= kMaxCam, "ncam out of range (1..8)");
@@ -1090,33 +1086,25 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   SOSVO_REQUIRE_FN(ctx, thr > 0.0, "threshold must be positive");
   if (nprob == 0) return SOSVO_OK;
   const int H = max_iter;
-  // workspace carve-up
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_perm = carve(sizeof(int32_t) * (size_t)nprob * stride);
-  const size_t o_cinfo = carve(sizeof(int32_t) * (size_t)nprob * (2 * kMaxCam + 1));
-  const size_t o_hyp = carve(sizeof(double) * (size_t)nprob * H * kHypDoubles);
-  const size_t o_counts = carve(sizeof(int32_t) * (size_t)nprob * H);
-  const bool epnp_vec = (flags & SOSVO_FLAG_EPNP) != 0;
-  const size_t o_vv = carve(epnp_vec ? sizeof(double) * (size_t)nprob * H * kEpnpVecDoubles : 0);
+  // the scratch.  counts_ws is carved whether or not the caller's hyp_counts replaces it, vvbuf only under SOSVO_FLAG_EPNP.
   // ransac_prune_kernel's survivor lists and their lengths, one buffer for the even stages and one for the odd ones; its
   // (L, h*) per problem from stage to stage; ransac_prepare_kernel's `split` per problem
-  const size_t o_alive = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));
-  const size_t o_alive2 = carve(sizeof(int32_t) * (size_t)nprob * (H + 1));
-  const size_t o_stage = carve(sizeof(int32_t) * (size_t)nprob * 2);
-  const size_t o_split = carve(sizeof(int32_t) * (size_t)nprob);
-  int32_t rc = sosvo_ws_reserve(ctx, off);
+  const bool epnp_vec = (flags & SOSVO_FLAG_EPNP) != 0;
+  int32_t *perm, *cinfo, *counts_ws, *alive_idx[2], *stage_state, *split;
+  double *hyp, *vvbuf;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    perm = cv.take<int32_t>((size_t)nprob * stride);
+    cinfo = cv.take<int32_t>((size_t)nprob * (2 * kMaxCam + 1));
+    hyp = cv.take<double>((size_t)nprob * H * kHypDoubles);
+    counts_ws = cv.take<int32_t>((size_t)nprob * H);
+    vvbuf = cv.take<double>(epnp_vec ? (size_t)nprob * H * kEpnpVecDoubles : 0);
+    alive_idx[0] = cv.take<int32_t>((size_t)nprob * (H + 1));
+    alive_idx[1] = cv.take<int32_t>((size_t)nprob * (H + 1));
+    stage_state = cv.take<int32_t>((size_t)nprob * 2);
+    split = cv.take<int32_t>((size_t)nprob);
+  });
   if (rc != SOSVO_OK) return rc;
-  char* ws = (char*)ctx->ws;
-  int32_t* perm = (int32_t*)(ws + o_perm);
-  int32_t* cinfo = (int32_t*)(ws + o_cinfo);
-  double* hyp = (double*)(ws + o_hyp);
-  int32_t* counts = hyp_counts ? hyp_counts : (int32_t*)(ws + o_counts);
-  int32_t* split = (int32_t*)(ws + o_split);
+  int32_t* counts = hyp_counts ? hyp_counts : counts_ws;
 
   SOSVO_LAUNCH(ctx,ransac_prepare_kernel, dim3(nprob), dim3(kThreads), 0, ctx->stream, cam, n, stride,
                      cam ? ncam : 1, perm, cinfo, split);
@@ -1128,7 +1116,6 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   if (epnp) adaptive = (adaptive ? 1 : 0) | 2;  // bit 1: the adaptive stop uses 6-point samples
   if (twopt) adaptive = (adaptive ? 1 : 0) | 4;  // bit 2: ... 2-point samples
   if (epnp) {
-    double* vvbuf = (double*)(ws + o_vv);
     SOSVO_LAUNCH_HYP(ctx, ransac_epnp_eigen_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
                  seed, vvbuf, counts);
     SOSVO_LAUNCH_HYP(ctx, ransac_epnp_pose_kernel, dim3(hyp_grid(nprob, cdiv(H, 64))), dim3(64), 0, ctx->stream, f, p, n, nprob, stride, H,
@@ -1188,8 +1175,6 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
     int nstage = 1;
     if (staged)
       for (nstage = 0; nstage < (int)(sizeof(kStagePlan) / sizeof(kStagePlan[0])) && kStagePlan[nstage] < capsets;) ++nstage;
-    int32_t* alive_idx[2] = {(int32_t*)(ws + o_alive), (int32_t*)(ws + o_alive2)};
-    int32_t* stage_state = (int32_t*)(ws + o_stage);
     // Every pass in the hypothesis-split form (point blocks of at most 4 sets, see the kernel): a workgroup sets up a
     // quarter of the points of a full block, so it takes more hypotheses -- 4 spans where a problem is one block (the
     // probe, a stage of 4 sets), 2 otherwise, and never less than one full LDS chunk over a survivor list (measured at
@@ -1236,7 +1221,6 @@ static int32_t ransac_abs_pose_impl(sosvo_ctx* ctx, const char* fn, const double
   SOSVO_LAUNCH_CHECK(ctx);
   return SOSVO_OK;
 }
-#undef SOSVO_REQUIRE_FN
 #undef SOSVO_LAUNCH_HYP
 
 extern "C" {

@@ -190,12 +190,14 @@ extern "C" int32_t sosvo_ransac_rel_pose(sosvo_ctx* ctx, const double* f1, const
   SOSVO_REQUIRE(ctx, thr > 0.0, "threshold must be positive");
   if (nprob == 0) return SOSVO_OK;
   const int H = max_iter;
-  const size_t hyp_bytes = (sizeof(double) * (size_t)nprob * H * kRelHypDoubles + 255) & ~(size_t)255;
-  const size_t cnt_bytes = sizeof(int32_t) * (size_t)nprob * H;
-  int32_t rc = sosvo_ws_reserve(ctx, hyp_bytes + cnt_bytes);
+  double* hyp;
+  int32_t* counts;
+  int32_t rc = sosvo_ws_carve(ctx, [&](Carver& cv) {
+    hyp = cv.take<double>((size_t)nprob * H * kRelHypDoubles);
+    counts = cv.take<int32_t>((size_t)nprob * H);
+  });
   if (rc != SOSVO_OK) return rc;
-  double* hyp = (double*)ctx->ws;
-  int32_t* counts = hyp_counts ? hyp_counts : (int32_t*)((char*)ctx->ws + hyp_bytes);
+  if (hyp_counts) counts = hyp_counts;
   SOSVO_LAUNCH(ctx, relpose_hyp_kernel, dim3(cdiv(H, 64), nprob), dim3(64), 0, ctx->stream, f1, f2, n, stride, H, algorithm, seed,
                hyp, counts);
   SOSVO_LAUNCH_CHECK(ctx);
