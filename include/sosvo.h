@@ -1296,6 +1296,24 @@ int32_t sosvo_rgbd_sequence_copy_slots(sosvo_ctx* ctx, const sosvo_rgbd_batch_cf
  *   Temporaries (census words, the cost volume, S without S_out, the left-right keys: about 210 bytes per pixel) live in the
  *   context's scratch.
  *
+ * sosvo_dense_stereo_paths: sosvo_dense_stereo with the number of aggregation paths as an argument.
+ *   paths = 4: exactly sosvo_dense_stereo, the same launches and the same bytes.  paths = 8: the reference tuner's "Full DP"
+ *   switch (common_cv.StereoMatchTuner.full_dyn_prog, cv2.STEREO_SGBM_MODE_HH); a caller maps it as
+ *   paths = full_dyn_prog ? 8 : 4.  Steps a, b, d, e, f and g are unchanged; step c gains four diagonal paths, with
+ *   (dr, dc) in {(+1, +1), (+1, -1), (-1, +1), (-1, -1)}:
+ *   c8. The predecessor of pixel (r, c) on path (dr, dc) is (r - dr, c - dc).  The path starts at (r, c), L = C, where
+ *      r - dr lies outside [0, rows); without SOSVO_DENSE_CYCLIC_COLUMNS also where c - dc lies outside [0, cols).  With
+ *      the flag the predecessor's column is (c - dc) mod cols: the seam is no border, as for the census taps, and for
+ *      cols = 1 the predecessor is the pixel above or below in the same column.  Elsewhere the recurrence of step c runs on
+ *      the predecessor's L.  S = the sum of the eight L (<= 8 * (64 + P2)) and stays u16, so that eight paths require
+ *      P2 <= SOSVO_DENSE_MAX_P2_EIGHT_PATHS = 8127 (S <= 65528); four paths keep 8191.
+ *      The same thing as lines (tests/refdense8.py, the kernel): line j in [0, cols) at step i in [0, rows) visits row i
+ *      (dr = +1) or rows - 1 - i (dr = -1) and column (j + dc * i) mod cols; in the clamped form it starts again with L = C
+ *      at every step i > 0 whose column is 0 (dc = +1) or cols - 1 (dc = -1).  Every pixel is visited by exactly one line
+ *      of a pass, exactly once, whether rows > cols or not.
+ *   Refusals (SOSVO_ERR_ARG before any launch): those of sosvo_dense_stereo, paths not 4 or 8, paths = 8 with P2 > 8127.
+ *   The scratch is that of sosvo_dense_stereo.
+ *
  * sosvo_dense_triangulate: d16 [n, rows, cols] i16 -> X_out [n, rows, cols, 3] f64 in the rig's frame [C].  rig_host: the
  *   sosvo_rig of sosvo_stereo_assemble (pano_top, pano_bot, F_top, F_bot, min_range, max_range are read).  For d16 >= 0,
  *   d16 >= min_d16 and (max_d16 <= 0 or d16 <= max_d16): top pixel (c, r), bottom pixel (c, r - d16 / 16.0) in double; angles,
@@ -1313,6 +1331,10 @@ int32_t sosvo_census_9x7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int3
 int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
                            const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
                            int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out);
+#define SOSVO_DENSE_MAX_P2_EIGHT_PATHS 8127
+int32_t sosvo_dense_stereo_paths(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                                 const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
+                                 int32_t lr_max, int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out);
 int32_t sosvo_dense_triangulate(sosvo_ctx* ctx, const sosvo_rig* rig_host, const int16_t* d16, int32_t n, int32_t rows,
                                 int32_t cols, int32_t min_d16, int32_t max_d16, double* X_out);
 

@@ -148,6 +148,8 @@ SIGNATURES = {
     "sosvo_rgbd_pair_batch": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]),
     "sosvo_census_9x7": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_dense_stereo": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
+    "sosvo_dense_stereo_paths": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p,
+                                         c_p]),
     "sosvo_dense_triangulate": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p]),
     "sosvo_dense_speckle": (c_i32, [c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
 }
@@ -643,6 +645,18 @@ class StepOptions(namedtuple("StepOptions", "match subpix lk stereo_lk cyclic"))
 DENSE_CYCLIC_COLUMNS = 1           # SOSVO_DENSE_CYCLIC_COLUMNS: the census taps wrap modulo cols
 DENSE_DISPARITIES = 64             # SOSVO_DENSE_DISPARITIES: one lane of a wave per disparity
 DENSE_MAX_P2, DENSE_MAX_MIN_DISPARITY = 8191, 1024
+DENSE_MAX_P2_EIGHT_PATHS = 8127    # SOSVO_DENSE_MAX_P2_EIGHT_PATHS: S = the sum of eight L <= 8 * (64 + P2) stays u16
+
+
+def dense_paths(paths, options=None):
+    """A `paths` argument of the dense stage -> 4 or 8, checked against the options it goes with: 4 =
+    down, up, left to right, right to left; 8 = those and the four diagonals, the reference tuner's "Full DP" trackbar
+    (paths = 8 if tuner.full_dyn_prog else 4).  Anything else, and 8 with P2 > 8127, raises ValueError."""
+    if isinstance(paths, bool) or not isinstance(paths, int) or paths not in (4, 8):
+        raise ValueError("dense paths must be 4 or 8, got %r" % (paths,))
+    if paths == 8 and DenseOptions.of(options).P2 > DENSE_MAX_P2_EIGHT_PATHS:
+        raise ValueError("dense paths = 8 needs P2 <= %d, got %r" % (DENSE_MAX_P2_EIGHT_PATHS, DenseOptions.of(options).P2))
+    return paths
 
 
 class DenseOptions(namedtuple("DenseOptions", "min_disparity P1 P2 uniqueness lr_max cyclic")):

@@ -272,11 +272,15 @@ __device__ __forceinline__ int sosvo_block_count_matches(const uint32_t* __restr
 }
 #endif
 
-// dense.hip / dense_speckle.hip: what every dense entry point asks of its frame stack and of its flags
-#define SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols) \
-  SOSVO_REQUIRE(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)")
-#define SOSVO_REQUIRE_DENSE_N(ctx, n) SOSVO_REQUIRE(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)")
-#define SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags) SOSVO_REQUIRE(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits")
+// dense.hip / dense_speckle.hip: what every dense entry point asks of its frame stack and of its flags (REQ: SOSVO_REQUIRE, or
+// SOSVO_REQUIRE_FN in a body that two entry points share)
+#define SOSVO_REQUIRE_DENSE_SIZE_AS(REQ, ctx, rows, cols) \
+  REQ(ctx, rows >= 1 && rows <= 16384 && cols >= 1 && cols <= 16384, "rows / cols out of range (1..16384)")
+#define SOSVO_REQUIRE_DENSE_N_AS(REQ, ctx, n) REQ(ctx, n >= 1 && n <= 32767, "n out of range (1..32767)")
+#define SOSVO_REQUIRE_DENSE_FLAGS_AS(REQ, ctx, flags) REQ(ctx, (flags & ~SOSVO_DENSE_CYCLIC_COLUMNS) == 0, "unknown flag bits")
+#define SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols) SOSVO_REQUIRE_DENSE_SIZE_AS(SOSVO_REQUIRE, ctx, rows, cols)
+#define SOSVO_REQUIRE_DENSE_N(ctx, n) SOSVO_REQUIRE_DENSE_N_AS(SOSVO_REQUIRE, ctx, n)
+#define SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags) SOSVO_REQUIRE_DENSE_FLAGS_AS(SOSVO_REQUIRE, ctx, flags)
 
 // detect.hip: the rolling 7x7 blur on images that lie img_stride bytes apart (also used by orb.hip for the pyramid levels)
 int32_t sosvo_launch_gauss7(sosvo_ctx* ctx, const uint8_t* in, long long img_stride, int nimg, int rows, int cols,

@@ -3,15 +3,16 @@
 //   OmniStereoModel.get_depth_map_from_panoramas (camera_models.py:3395) with common_cv.StereoMatchTuner's SGBM settings
 //   (common_cv.py:482-497, :644), resolve_pano_correspondences_from_disparity_map (:2492), triangulate_from_depth_map (:2567)
 // The algorithm is the one include/sosvo.h states for sosvo_dense_stereo (tests/refdense.py is the same text in numpy):
-// 9 x 7 census, Hamming cost over D = 64 disparities, four aggregation paths, winner + uniqueness + left-right + 1/16-row
-// parabola.  Small integers throughout, so the device equals the numpy statement bit for bit.
+// 9 x 7 census, Hamming cost over D = 64 disparities, four aggregation paths (eight with sosvo_dense_stereo_paths, DESIGN.md
+// section 39, tests/refdense8.py), winner + uniqueness + left-right + 1/16-row parabola.  Small integers throughout, so the
+// device equals the numpy statement bit for bit.
 //
 // Lane = disparity: a wave64 holds the 64 values L(p, .) of one pixel of one scan line.  The path minimum is four DPP
 // exchanges inside the rows of 16 lanes and four readlanes; the k - 1 / k + 1 terms are the whole-wave shifts of common.h
 // with the entering lane poisoned.  No LDS.  The cost volume C [n, rows, cols, 64] u8 is written once, by the downward
 // pass (there the bottom column's census words slide one lane per row: one shift and one new word per step), and read
 // by the other three passes as one 64-byte line per step; S [n, rows, cols, 64] u16 is written by the downward pass and
-// added to by the other three, one launch after the other on the context's stream.
+// added to by the other three (and by the four diagonal passes), one launch after the other on the context's stream.
 #include "common.h"
 #include "dense_scratch.h"
 #include "geom_core.h"
@@ -133,6 +134,44 @@ __global__ __launch_bounds__(256) void dense_path_kernel(const uint8_t* __restri
   }
 }
 
+// One diagonal path per wave: line j of frame f starts in column j of the first row (dr = +1) or of
+// the last row (dr = -1) and at every step moves one row by dr and one column by dc, the column wrapping modulo cols, so that
+// the cols lines of a launch visit every pixel exactly once.  Cyclic: the wrap is the predecessor across the seam.  Clamped:
+// the line starts again with L = C in the column it wraps into.  The wave's number is made uniform, so the pixel, its column
+// and the wrap are scalar; C, S and the one-step-ahead loads are those of dense_path_kernel.  One direction per launch: two
+// of them in one launch would have two waves read-modify-write the same S.
+template <bool kCyclic>
+__global__ __launch_bounds__(256) void dense_diag_kernel(const uint8_t* __restrict__ C, uint16_t* __restrict__ S, int rows, int cols, int dr,
+                                                         int dc, int P1, int P2) {
+  const int lane = threadIdx.x & 63, j = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (j >= cols) return;  // (the whole wave)
+  const long long row_step = dr > 0 ? (long long)cols : -(long long)cols;
+  const int start_col = dc > 0 ? 0 : cols - 1;  // clamped: where a line starts again
+  long long p = (long long)blockIdx.y * rows * cols + (dr > 0 ? 0LL : (long long)(rows - 1) * cols) + j;
+  int c = j, cn = C[(size_t)p * kD + lane], sn = S[(size_t)p * kD + lane], Lp = 0;
+  for (int i = 0; i < rows; ++i) {
+    const int cost = cn, s = sn;
+    int c2 = c + dc;
+    long long q = p + row_step + dc;
+    if (c2 == cols) {
+      c2 = 0;
+      q -= cols;
+    } else if (c2 < 0) {
+      c2 = cols - 1;
+      q += cols;
+    }
+    if (i + 1 < rows) {
+      cn = C[(size_t)q * kD + lane];
+      sn = S[(size_t)q * kD + lane];
+    }
+    const int L = i == 0 || (!kCyclic && c == start_col) ? cost : sgm_step(cost, Lp, P1, P2, lane);
+    S[(size_t)p * kD + lane] = (uint16_t)(s + L);
+    Lp = L;
+    p = q;
+    c = c2;
+  }
+}
+
 // Winner, uniqueness, reach, mask and the parabola of 64 consecutive pixels per wave; d16 before the left-right check,
 // kstar (0xFF = dropped), and with `best` the left-right key (mS << 14 | r) of the bottom row the pixel points at.
 // First lane = disparity, one pixel after the other: the reductions (winner key, rivals, the two neighbours of the winner),
@@ -234,31 +273,20 @@ int32_t launch_census(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, i
   return SOSVO_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t sosvo_census_9x7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t flags,
-                         uint64_t* census_out) {
+// sosvo_dense_stereo (paths = 4) and sosvo_dense_stereo_paths: one body, `fn` the public name in the messages
+int32_t dense_stereo_body(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                          const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max,
+                          int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out) {
   SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, gray && census_out, "null pointer");
-  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
-  SOSVO_REQUIRE(ctx, nimg >= 1 && nimg <= 65535, "nimg out of range (1..65535)");
-  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
-  return launch_census(ctx, gray, nimg, rows, cols, (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, census_out);
-}
-
-int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
-                           const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
-                           int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out) {
-  SOSVO_ENTER(ctx);
-  SOSVO_REQUIRE(ctx, top && bot && d16_out, "null pointer");
-  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
-  SOSVO_REQUIRE_DENSE_N(ctx, n);
-  SOSVO_REQUIRE(ctx, P1 >= 0 && P1 <= P2 && P2 <= 8191, "penalties out of range (0 <= P1 <= P2 <= 8191)");
-  SOSVO_REQUIRE(ctx, uniqueness >= 0 && uniqueness < 100, "uniqueness out of range (0..99)");
-  SOSVO_REQUIRE(ctx, min_disparity >= 0 && min_disparity <= 1024, "min_disparity out of range (0..1024)");
-  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
+  SOSVO_REQUIRE_FN(ctx, top && bot && d16_out, "null pointer");
+  SOSVO_REQUIRE_DENSE_SIZE_AS(SOSVO_REQUIRE_FN, ctx, rows, cols);
+  SOSVO_REQUIRE_DENSE_N_AS(SOSVO_REQUIRE_FN, ctx, n);
+  SOSVO_REQUIRE_FN(ctx, P1 >= 0 && P1 <= P2 && P2 <= 8191, "penalties out of range (0 <= P1 <= P2 <= 8191)");
+  SOSVO_REQUIRE_FN(ctx, uniqueness >= 0 && uniqueness < 100, "uniqueness out of range (0..99)");
+  SOSVO_REQUIRE_FN(ctx, min_disparity >= 0 && min_disparity <= 1024, "min_disparity out of range (0..1024)");
+  SOSVO_REQUIRE_DENSE_FLAGS_AS(SOSVO_REQUIRE_FN, ctx, flags);
+  SOSVO_REQUIRE_FN(ctx, paths == 4 || paths == 8, "paths must be 4 or 8");
+  SOSVO_REQUIRE_FN(ctx, paths == 4 || P2 <= SOSVO_DENSE_MAX_P2_EIGHT_PATHS, "eight paths need P2 <= 8127 (S stays 16 bits)");
   const bool cyclic = (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, want_lr = lr_max >= 0;
   const size_t frame_pixels = (size_t)rows * cols, total = (size_t)n * frame_pixels;
   sosvo_dense_scratch b;  // (dense_scratch.h)
@@ -294,6 +322,15 @@ int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bo
                        (long long)cols - 1, (long long)cols, -1LL, P1, P2);
   }
   SOSVO_LAUNCH_CHECK(ctx);
+  if (paths == 8) {  // the diagonals: line j from column j of the first (dr = +1) or the last row, one direction per launch
+    static const struct { const char* name; int dr, dc; } kDiag[4] = {{"dense_diag_kernel_dr", 1, 1}, {"dense_diag_kernel_dl", 1, -1},
+                                                                      {"dense_diag_kernel_ur", -1, 1}, {"dense_diag_kernel_ul", -1, -1}};
+    for (const auto& d : kDiag) {
+      SOSVO_LAUNCH_AS(ctx, d.name, cyclic ? dense_diag_kernel<true> : dense_diag_kernel<false>, dim3(cdiv(cols, 4), n), dim3(256), 0,
+                      ctx->stream, C, S, rows, cols, d.dr, d.dc, P1, P2);
+      SOSVO_LAUNCH_CHECK(ctx);
+    }
+  }
   if (want_lr) SOSVO_HIP(ctx, hipMemsetAsync(best, 0xFF, total * 4, ctx->stream));
   const size_t select_blocks = (total + 4 * kD - 1) / (4 * kD);
   SOSVO_LAUNCH(ctx, dense_select_kernel, dim3((unsigned)select_blocks), dim3(256), 0, ctx->stream, S, mask, rows, cols, total,
@@ -305,6 +342,33 @@ int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bo
     SOSVO_LAUNCH_CHECK(ctx);
   }
   return SOSVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t sosvo_census_9x7(sosvo_ctx* ctx, const uint8_t* gray, int32_t nimg, int32_t rows, int32_t cols, int32_t flags,
+                         uint64_t* census_out) {
+  SOSVO_ENTER(ctx);
+  SOSVO_REQUIRE(ctx, gray && census_out, "null pointer");
+  SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols);
+  SOSVO_REQUIRE(ctx, nimg >= 1 && nimg <= 65535, "nimg out of range (1..65535)");
+  SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags);
+  return launch_census(ctx, gray, nimg, rows, cols, (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, census_out);
+}
+
+int32_t sosvo_dense_stereo(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                           const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
+                           int32_t lr_max, int32_t flags, int16_t* d16_out, uint16_t* S_out) {
+  return dense_stereo_body(__func__, ctx, top, bot, n, rows, cols, mask, min_disparity, P1, P2, uniqueness, lr_max, flags, 4, d16_out, S_out);
+}
+
+int32_t sosvo_dense_stereo_paths(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                                 const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness,
+                                 int32_t lr_max, int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out) {
+  return dense_stereo_body(__func__, ctx, top, bot, n, rows, cols, mask, min_disparity, P1, P2, uniqueness, lr_max, flags, paths, d16_out,
+                           S_out);
 }
 
 int32_t sosvo_dense_triangulate(sosvo_ctx* ctx, const sosvo_rig* rig_host, const int16_t* d16, int32_t n, int32_t rows,

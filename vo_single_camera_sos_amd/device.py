@@ -1012,11 +1012,14 @@ class Context(object):
                    _lib.DENSE_CYCLIC_COLUMNS if cyclic else 0, _ptr(out))
         return out
 
-    def dense_stereo(self, top, bot, mask=None, *, options=None, want_volume=False):
+    def dense_stereo(self, top, bot, mask=None, *, options=None, want_volume=False, paths=4):
         """sosvo_dense_stereo: top, bot [n,rows,cols] u8 gray panoramas (the halves of unwrap_median_gray's output), mask
         [rows,cols] u8 or None, options a DenseOptions (None: the defaults) -> d16 [n,rows,cols] i16 (disparity in 1/16 row,
-        -1 = invalid); with want_volume (d16, S [n,rows,cols,64] u16, the aggregated volume)."""
+        -1 = invalid); with want_volume (d16, S [n,rows,cols,64] u16, the aggregated volume).  paths: 4, or 8 for the four
+        diagonal paths as well (sosvo_dense_stereo_paths; needs P2 <= 8127); anything else raises
+        ValueError before the call."""
         o = _lib.DenseOptions.of(options)
+        paths = _lib.dense_paths(paths, o)
         _check(top, torch.uint8, "top", ndim=3)
         n, rows, cols = top.shape
         _check(bot, torch.uint8, "bot", (n, rows, cols))
@@ -1024,8 +1027,12 @@ class Context(object):
             _check(mask, torch.uint8, "mask", (rows, cols))
         d16 = torch.empty((n, rows, cols), dtype=torch.int16, device=top.device)
         S = torch.empty((n, rows, cols, _lib.DENSE_DISPARITIES), dtype=torch.uint16, device=top.device) if want_volume else None
-        self._call(self._lib.sosvo_dense_stereo, _ptr(top), _ptr(bot), n, rows, cols, _ptr(mask), o.min_disparity, o.P1, o.P2,
-                   o.uniqueness, o.lr_max, o.flags, _ptr(d16), _ptr(S))
+        if paths == 4:
+            self._call(self._lib.sosvo_dense_stereo, _ptr(top), _ptr(bot), n, rows, cols, _ptr(mask), o.min_disparity, o.P1, o.P2,
+                       o.uniqueness, o.lr_max, o.flags, _ptr(d16), _ptr(S))
+        else:
+            self._call(self._lib.sosvo_dense_stereo_paths, _ptr(top), _ptr(bot), n, rows, cols, _ptr(mask), o.min_disparity, o.P1,
+                       o.P2, o.uniqueness, o.lr_max, o.flags, paths, _ptr(d16), _ptr(S))
         return (d16, S) if want_volume else d16
 
     def dense_triangulate(self, rig, d16, min_disparity=1.0, max_disparity=0.0):

@@ -389,31 +389,33 @@ class GUMStereo(object):
         return (m_top, k_top[ok], d_top[ok]), (m_bot, k_bot[ok], d_bot[ok]), colors
 
     # ---- dense stereo: disparity map and point cloud ---------------------------------
-    def _dense_engine(self, median_win_size, options, speckle=None):
-        """One-frame pipeline.DenseOmniStereo per (median, options, speckle), on the rig's own geometry and without a range
-        filter (the reference's dense path has none)."""
-        from .._lib import DenseOptions, SpeckleOptions
+    def _dense_engine(self, median_win_size, options, speckle=None, paths=4):
+        """One-frame pipeline.DenseOmniStereo per (median, options, speckle, paths), on the rig's own geometry and without a
+        range filter (the reference's dense path has none)."""
+        from .._lib import DenseOptions, SpeckleOptions, dense_paths
         from ..pipeline import DenseOmniStereo, RigConfig
-        key = (int(median_win_size), DenseOptions.of(options), SpeckleOptions.of(speckle))
+        key = (int(median_win_size), DenseOptions.of(options), SpeckleOptions.of(speckle), dense_paths(paths, options))
         cache = self.__dict__.setdefault("_dense_engines", {})
         if key not in cache:
             geo = [(p.cols, p.rows, p.pixel_size, p.cyl_height_max) for p in (self.top_model.panorama, self.bot_model.panorama)]
             rig = RigConfig(geo[0], geo[1], self.top_model.F[:3, 0], self.bot_model.F[:3, 0], 0.0, 0.0)
             cache[key] = DenseOmniStereo(self._context(), self._device_model(), rig, 1, median_win_size=key[0], options=key[1],
-                                         min_disparity=0.0, speckle=key[2])
+                                         min_disparity=0.0, speckle=key[2], paths=key[3])
         return cache[key]
 
     def get_depth_map_from_panoramas(self, method="sgbm", use_cropped_panoramas=False, rows_roi=(), cols_roi=(), show=False,
                                      load_stereo_tuner_from_pickle=False, stereo_tuner_filename=None, tune_live=False,
                                      use_heat_map=True, stereo_matcher_tuner=None, median_win_size=0, options=None,
-                                     speckle=None):
+                                     speckle=None, paths=4):
         """camera_models.py:3395 without the tuner window: semi-global matching between the top and the bottom panorama of the
         current omni image on the device (sosvo_dense_stereo; `options`: a DenseOptions, None = its defaults, in place of the
         tuner's sliders).  Sets self.disparity_map (float64 [rows, cols] in rows, 0 = invalid as in the reference) and
         self.disparity_img (u8, (d - min) * 255 / (64 - min) as common_cv.py:700) and returns them; self.disparity_d16 keeps the
         device's int16 map.  `speckle`: None (no filter), a SpeckleOptions or a dict of its fields: the three maps are then the
         filtered ones (sosvo_dense_speckle); the tuner's "Speckle Window Size" / "Speckle Range" enter
-        through SpeckleOptions.from_tuner(window, range).  The GUI-only arguments (show, tune_live, use_heat_map, the tuner and its pickle) are ignored;
+        through SpeckleOptions.from_tuner(window, range).  `paths`: 4, or 8 for the diagonal aggregation paths as well
+        (sosvo_dense_stereo_paths): the tuner's "Full DP" trackbar, paths = 8 if tuner.full_dyn_prog else 4.
+        The GUI-only arguments (show, tune_live, use_heat_map, the tuner and its pickle) are ignored;
         cropping and regions of interest are not built."""
         if str(method).lower() != "sgbm":
             raise NotImplementedError("dense stereo method %r: only \"sgbm\" is built" % (method,))
@@ -421,7 +423,7 @@ class GUMStereo(object):
             raise NotImplementedError("cropped panoramas and regions of interest are not built: the whole panorama is matched")
         if self.current_omni_img is None:
             raise ValueError("set_current_omni_image first")
-        eng = self._dense_engine(median_win_size, options, speckle)
+        eng = self._dense_engine(median_win_size, options, speckle, paths)
         eng.load_frames(np.ascontiguousarray(self.current_omni_img)[None])
         d16, X = eng.step()
         eng.ctx.synchronize()

@@ -1638,12 +1638,15 @@ class DenseOmniStereo(object):
     resolve_pano_correspondences_from_disparity_map, applied by the triangulation (max_disparity <= 0: no upper one).
     speckle: what SpeckleOptions.of takes.  None: no filter, and nothing differs from an engine without
     the argument.  With a value step() filters d16 in place (Context.dense_speckle) between the stereo and the triangulation,
-    so that the returned map, X and depth() are the filtered ones."""
+    so that the returned map, X and depth() are the filtered ones.
+    paths: 4, or 8 for the diagonal aggregation paths as well, the reference tuner's "Full DP"
+    trackbar: paths = 8 if tuner.full_dyn_prog else 4.  With 4 nothing differs from an engine without the argument."""
 
     def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0,
-                 speckle=None):
-        from ._lib import DenseOptions, SpeckleOptions
+                 speckle=None, paths=4):
+        from ._lib import DenseOptions, SpeckleOptions, dense_paths
         self.options, self.speckle = DenseOptions.of(options), SpeckleOptions.of(speckle)
+        self.paths = dense_paths(paths, self.options)
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         if tuple(rig.pano_top) != tuple(rig.pano_bot):
             raise ValueError("dense stereo needs two panoramas of one geometry, got %r and %r" % (rig.pano_top, rig.pano_bot))
@@ -1663,7 +1666,7 @@ class DenseOmniStereo(object):
         """-> (d16 [F,rows,cols] i16, X [F,rows,cols,3] f64) on the device (asynchronous)."""
         c, m = self.ctx, self.model
         c.unwrap_median_gray(self.omni, m.unwrap_table, self.median_win_size, gray=self.gray)
-        self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options)
+        self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options, paths=self.paths)
         if self.speckle is not None:
             c.dense_speckle(self.d16, options=self.speckle, out=self.d16)
         self.X = c.dense_triangulate(self.rig, self.d16, self.min_disparity, self.max_disparity)
