@@ -1,11 +1,17 @@
-"""The scenes, the setting and the small helpers the matcher-option tests share (test infrastructure, like refflow.py and
-refmatch.py): the calibrated rig, the rendered omni and RGB-D pairs with the reference flow under a setting, the synthetic
-sequences behind run_VO, descriptor / position stores for the stage tests.
+"""The scenes, the settings and the drivers every option's tests share (test infrastructure, like refflow.py and
+refmatch.py): the calibrated rig, the rendered omni and RGB-D pairs with the reference flow under a setting, the translating
+and the turning scene of the *_layers modules, the synthetic sequences behind run_VO, descriptor / position stores for the
+stage tests -- and the plumbing of the chain every option is tested through: the one-call batch's records (batch_records,
+pair_record), a sequence engine's speculative records (hop_records), a VO loop on one engine (drive) and on the lanes of a
+multi-sequence engine (drive_lanes, assert_same_drive), run_VO over several frame windows (run_vo_windows) and run_VO_many
+against solo runs (run_vo_many_against_solo).  The drivers return data; what it has to equal is asserted by the test that
+makes the claim.
 
 The scene builders memoise per (ctx, parameters) -- ctx is the session's context -- so the modules that ask for the same scene
 share one rendering, one oracle detection and one cache of references, keyed by the matchers' VALUES (refmatch.Matching).
 Nobody writes into a scene."""
 import os
+import threading
 
 import numpy as np
 
@@ -17,6 +23,12 @@ FX = FY = 554.256258
 CX, CY = 319.5, 239.5
 N_SEQ = 6
 THR = float(1.0 - np.cos(np.deg2rad(5.0)))                    # the reference's 5-degree threshold
+# the *_layers modules' settings (test_gpu_stereo_lk_layers passes its own 330 / 2048 / 500)
+NFEAT, FRAME_CAP, ITERS = 300, 1024, 210
+KW = dict(num_of_features=NFEAT, frame_cap=FRAME_CAP, max_iter=ITERS)
+SEQ_KW = dict(KW, adaptive=True, ransac_solver="GP3P")
+LK_CHECKED = dict(half=4, levels=3, max_iter=10, fb_max=0.5)      # 16 lanes per keypoint, forward-backward check
+LK_WAVE = dict(half=10, levels=2, max_iter=10)                    # the whole-wave mapping, no check
 _memo = {}
 
 
@@ -133,6 +145,157 @@ def drive(eng, frames, window):
                 rec = eng.track(eng.key_slot, info["slot"], info["seed"])
             out.append((info["count"], info["seed"], info["spec"], info["spec2"], rec))
     return out
+
+
+def drive_lanes(multi, sequences, window):
+    """sequences[k] through lane k of the multi-sequence engine, one host thread each, as run_VO_many drives them.  Every lane
+    is live before the first one parks, so the rounds are in lockstep.  -> per lane what drive() returns.  A lane's exception
+    is raised (the first lane's that has one) once every lane has been ended and joined."""
+    S = len(sequences)
+    got, errors = [None] * S, [None] * S
+
+    def work(k):
+        try:
+            got[k] = drive(multi.lane(k), sequences[k], window)
+        except BaseException as e:  # noqa: B902
+            errors[k] = e
+        finally:
+            multi.end(k)
+    for k in range(S):
+        multi.begin(k)
+    threads = [threading.Thread(target=work, args=(k,)) for k in range(S)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    for e in errors:
+        if e is not None:
+            raise e
+    return got
+
+
+def assert_same_drive(got, want):
+    """Two results of drive() are the same: as many frames, count and seed equal, the two speculative records and the serial
+    record both None or equal bit for bit."""
+    assert len(got) == len(want), (len(got), len(want))
+    for t, (g, w) in enumerate(zip(got, want)):
+        assert g[:2] == w[:2], (t, g[:2], w[:2])
+        for x, y in zip(g[2:], w[2:]):
+            assert (x is None) == (y is None) and (x is None or np.array_equal(x, y)), t
+
+
+def hop_records(eng, frames, window):
+    """The frames through a sequence engine window by window (the last one may be ragged; RGB-D: a list of (bgr, depth)
+    tuples).  -> [len(frames) - 1, 16]: every frame's speculative record against its predecessor, in frame order."""
+    got = []
+    for w0 in range(0, len(frames), window):
+        got += [info["spec"] for info in eng.push_window(list(frames[w0:w0 + window])) if info["spec"] is not None]
+    return np.stack(got)
+
+
+def batch_records(ctx, s, frames, seed=5, n_streams=1, fill=None, **kw):
+    """The records of the frames' pairs from one FramePairBatch on the scene's model and rig (kw: its settings, the solver's
+    among them); fill: a byte the workspace holds before the call."""
+    from vo_single_camera_sos_amd.pipeline import FramePairBatch, RigConfig
+    b = FramePairBatch(ctx, s["model"], RigConfig(**s["rig_kw"]), len(frames) // 2, seed=seed, n_streams=n_streams, **kw)
+    if fill is not None:
+        b.workspace.fill_(fill)
+    b.load_frames(frames)
+    out = b.step().cpu().numpy().copy()
+    ctx.synchronize()
+    return out
+
+
+def pair_record(ctx, s, a, b, seed, **kw):
+    """The pair batch's record of frames (a, b) of the scene's sequence, memoised per (scene, a, b, seed, settings): what
+    the sequence tests compare against."""
+    key = ("pair", ctx, s["name"], a, b, seed, repr(sorted(kw.items())))
+    if key not in _memo:
+        _memo[key] = batch_records(ctx, s, s["seq"][[a, b]], seed=seed, **kw)[0]
+    return _memo[key]
+
+
+def run_vo_windows(cam, seq, n, root, windows, **kw):
+    """run_VO on the first n frames of the SOS sequence once per frame window (0: the per-frame mirror path), each into a
+    directory of its own under root; every run tracks every frame.  -> (the result files' texts, run_VO's outputs), per window."""
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
+    texts, outs = {}, {}
+    for w in windows:
+        results = os.path.join(str(root), "window_%s" % w)
+        outs[w] = run_VO(None, cam, frame_window=w, **kw, **sos_kwargs(seq, n, results))
+        texts[w] = read_results(results)
+        assert outs[w]["tracked"] == n - 1, (w, outs[w].get("message"))
+    return texts, outs
+
+
+def run_vo_many_against_solo(gums, sequences, n, root, frame_window=5, lanes=2, **kw):
+    """The sequences through the lanes of one engine (run_VO_many) against each through run_VO alone: every sequence's
+    result files are its solo run's, byte for byte.  -> (the solo runs' texts, run_VO_many's outputs), per sequence."""
+    from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO, run_VO_many
+    want = []
+    for k, seq in enumerate(sequences):
+        res = os.path.join(str(root), "solo_%d" % k)
+        out = run_VO(None, load_gums_json(gums), frame_window=frame_window, **kw, **sos_kwargs(seq, n, res))
+        assert out["tracked"] == n - 1, (k, out.get("message"))
+        want.append(read_results(res))
+    many = [sos_kwargs(seq, n, os.path.join(str(root), "many_%d" % k)) for k, seq in enumerate(sequences)]
+    outs = run_VO_many(load_gums_json(gums), many, frame_window=frame_window, lanes=lanes, **kw)
+    for k, (q, files) in enumerate(zip(many, want)):
+        assert read_results(q["results_path"]) == files, k
+    return want, outs
+
+
+# ---- the scenes of the *_layers modules ------------------------------------------------------------------------------------------
+def _yaw(deg):
+    a = np.deg2rad(deg)
+    return np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+
+
+def translating_scene(ctx):
+    """3 rendered pairs (seed 99: the first two are the pairs test_pair_pipeline_tracks_with_lk uses) with their poses, and a
+    6-frame sequence with steps |t| <= 40 mm, <= 2 degrees.  Fewer pairs or frames of the same seeds are prefixes of these."""
+    key = ("translating", ctx)
+    if key not in _memo:
+        from vo_single_camera_sos_amd import synthetic
+        from vo_single_camera_sos_amd.frontend import DeviceImageModel
+        gs, rig_kw = rig()
+        omni, poses = synthetic.make_frame_pairs(gs, 3, seed=99)
+        room, rng = synthetic.Room(seed=61), np.random.default_rng(62)
+        seq = np.stack([synthetic.render_omni(gs, room, R, t, 2.0, rng) for R, t in synthetic.trajectory(6, 61, max_t=40.0, max_deg=2.0)])
+        _memo[key] = dict(name="translating", gs=gs, rig_kw=rig_kw, omni=omni, poses=poses, seq=seq,
+                          model=DeviceImageModel(ctx, gs, (480, 640)))
+    return _memo[key]
+
+
+def yaw_pairs(gs, yaw_deg, seeds=(5, 6)):
+    """-> (omni [4, H, W, 3], poses): pair i = one room seen from the identity pose and from the pose turned by -/+ yaw_deg."""
+    from vo_single_camera_sos_amd import synthetic
+    omni, poses = [], []
+    for k, seed in enumerate(seeds):
+        rng = np.random.default_rng(seed)
+        room = synthetic.Room(seed=seed)
+        R = _yaw(yaw_deg if k else -yaw_deg)
+        omni += [synthetic.render_omni(gs, room, np.eye(3), np.zeros(3), 2.0, rng), synthetic.render_omni(gs, room, R, np.zeros(3), 2.0, rng)]
+        poses.append((R, np.zeros(3)))
+    return np.stack(omni), poses
+
+
+def turning_scene(ctx):
+    """Per yaw angle (21 degrees: a matched pair can cross the seam; 11: a tracked point can) two rendered pairs whose second
+    frame is the first turned about the vertical axis, as yaw_omni[yaw] and yaw_poses[yaw]; and a 6-frame sequence that turns
+    by 7 degrees a frame about the vertical axis while it drifts 30 mm a frame."""
+    key = ("turning", ctx)
+    if key not in _memo:
+        from vo_single_camera_sos_amd import synthetic
+        from vo_single_camera_sos_amd.frontend import DeviceImageModel
+        gs, rig_kw = rig()
+        pairs = {yaw: yaw_pairs(gs, yaw) for yaw in (21.0, 11.0)}
+        room, rng = synthetic.Room(seed=71), np.random.default_rng(72)
+        seq = np.stack([synthetic.render_omni(gs, room, _yaw(7.0 * k), np.array([30.0 * k, -10.0 * k, 0.0]), 2.0, rng) for k in range(6)])
+        _memo[key] = dict(name="turning", gs=gs, rig_kw=rig_kw, yaw_omni={yaw: p[0] for yaw, p in pairs.items()},
+                          yaw_poses={yaw: p[1] for yaw, p in pairs.items()}, seq=seq, model=DeviceImageModel(ctx, gs, (480, 640)))
+    return _memo[key]
 
 
 # ---- the rendered omni pairs ---------------------------------------------------------------------------------------------------

@@ -16,14 +16,16 @@ Then SOSVO_FLAG_CYCLIC_F2F in the one-call batches, sequence mode and run_VO (th
 for bit, with the matcher and with the tracker: the one-call batch equals the pair pipeline, also over two internal streams;
 records do not depend on the workspace's contents; the sequence engine equals the pair batch for windows 1, 2 and 5; the
 lanes of a multi-sequence engine equal solo engines; run_VO writes the same pose file whatever the frame window."""
+import os
+
 import numpy as np
 import pytest
 
 import matching_scenes as scenes
 import synth
-from vo_single_camera_sos_amd import synthetic
-from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
-from vo_single_camera_sos_amd.pipeline import FramePairPipeline, RigConfig
+from matching_scenes import FRAME_CAP, ITERS, KW, LK_CHECKED, LK_WAVE, NFEAT, SEQ_KW
+from vo_single_camera_sos_amd.frontend import ImageFrontEnd
+from vo_single_camera_sos_amd.pipeline import FramePairPipeline, MultiSequenceEngine, RigConfig, SequenceEngine
 
 pytestmark = pytest.mark.gpu
 
@@ -31,31 +33,16 @@ YAW_MATCH, YAW_LK = 21.0, 11.0
 LK = dict(half=10, levels=4, max_iter=30, fb_max=0.5)
 
 
-def _yaw_pairs(gs, yaw_deg, seeds=(5, 6)):
-    """-> (omni [4, H, W, 3], poses): pair i = one room seen from the identity pose and from the pose turned by -/+ yaw_deg."""
-    omni, poses = [], []
-    for k, seed in enumerate(seeds):
-        rng = np.random.default_rng(seed)
-        room = synthetic.Room(seed=seed)
-        a = np.deg2rad(yaw_deg if k else -yaw_deg)
-        R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
-        omni += [synthetic.render_omni(gs, room, np.eye(3), np.zeros(3), 2.0, rng), synthetic.render_omni(gs, room, R, np.zeros(3), 2.0, rng)]
-        poses.append((R, np.zeros(3)))
-    return np.stack(omni), poses
-
-
 @pytest.fixture(scope="module")
 def rigs(ctx):
-    """The rig, and per yaw angle a front end that has run on its two pairs (rendered once)."""
-    gs, rig_kw = scenes.rig()
-    model = DeviceImageModel(ctx, gs, (480, 640))
-    out = dict(rig_kw=rig_kw, cols=int(rig_kw["pano_top"][0]))
+    """The rig, and per yaw angle a front end that has run on the turning scene's two pairs."""
+    s = scenes.turning_scene(ctx)
+    out = dict(rig_kw=s["rig_kw"], cols=int(s["rig_kw"]["pano_top"][0]))
     for yaw in (YAW_MATCH, YAW_LK):
-        omni, poses = _yaw_pairs(gs, yaw)
-        fe = ImageFrontEnd(ctx, model, 4, detection_method="GFT", num_of_features=330, keep_panoramas=False)
-        fe.load_frames(omni)
+        fe = ImageFrontEnd(ctx, s["model"], 4, detection_method="GFT", num_of_features=330, keep_panoramas=False)
+        fe.load_frames(s["yaw_omni"][yaw])
         fe.run()
-        out[yaw] = (fe, poses)
+        out[yaw] = (fe, s["yaw_poses"][yaw])
     return out
 
 
@@ -166,53 +153,32 @@ def test_the_constructor_refuses_what_cannot_be_cyclic(ctx, rigs):
 
 # ---- the batched layers: SOSVO_FLAG_CYCLIC_F2F in the one-call batches, sequence mode and run_VO --------------------------------
 # Every record comparison is bit for bit, each once with the matcher (plain and gated) and once with the tracker, as
-# tests/test_gpu_lk_layers.py does for the tracker alone; its helpers and settings are used as they are.
-import os  # noqa: E402
-
-from test_gpu_lk_layers import FRAME_CAP, ITERS, KW, LK_CHECKED, LK_WAVE, NFEAT, SEQ_KW, _batch_records  # noqa: E402
-from vo_single_camera_sos_amd.pipeline import FramePairBatch, MultiSequenceEngine, SequenceEngine  # noqa: E402
-
+# tests/test_gpu_lk_layers.py does for the tracker alone, with its settings (matching_scenes): the turning scene's yaw pairs (21
+# degrees for the matcher, 11 for the tracker) and its 6-frame sequence.
 CYC = dict(cyclic_columns=True)
 SETTINGS = {"match": {}, "gated": dict(gated_f2f=True), "lk4_fb": dict(f2f_tracker="lk", lk=LK_CHECKED),
             "lk10": dict(f2f_tracker="lk", lk=LK_WAVE), "lk10_4_fb": dict(f2f_tracker="lk", lk=LK)}
-_memo = {}
 
 
-def _layers_scene(ctx, rigs):
-    """The yaw pairs of the fixture (21 degrees for the matcher, 11 for the tracker), and a 6-frame sequence that turns by 7
-    degrees a frame about the vertical axis while it drifts 30 mm a frame."""
-    if "scene" not in _memo:
-        gs, _ = scenes.rig()
-        room, rng = synthetic.Room(seed=71), np.random.default_rng(72)
-        seq = []
-        for k in range(6):
-            a = np.deg2rad(7.0 * k)
-            R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
-            seq.append(synthetic.render_omni(gs, room, R, np.array([30.0 * k, -10.0 * k, 0.0]), 2.0, rng))
-        _memo["scene"] = dict(rig_kw=rigs["rig_kw"], model=rigs[YAW_MATCH][0].model, seq=np.stack(seq))
-        _memo["pairs"] = {yaw: _yaw_pairs(gs, yaw)[0] for yaw in (YAW_MATCH, YAW_LK)}
-    return _memo["scene"]
-
-
-def _omni_of(name):
-    return _memo["pairs"][YAW_LK if name.startswith("lk") else YAW_MATCH]
+def _omni_of(s, name):
+    return s["yaw_omni"][YAW_LK if name.startswith("lk") else YAW_MATCH]
 
 
 @pytest.mark.parametrize("name", list(SETTINGS))
-def test_one_call_batch_equals_the_pair_pipeline_also_over_two_streams(ctx, rigs, name):
-    s = _layers_scene(ctx, rigs)
-    kw, omni = SETTINGS[name], _omni_of(name)
+def test_one_call_batch_equals_the_pair_pipeline_also_over_two_streams(ctx, name):
+    s = scenes.turning_scene(ctx)
+    kw, omni = SETTINGS[name], _omni_of(s, name)
     fe = ImageFrontEnd(ctx, s["model"], 4, detection_method="GFT", num_of_features=NFEAT, keep_panoramas=False)
     pipe = FramePairPipeline(ctx, RigConfig(**s["rig_kw"]), 2, frame_cap=FRAME_CAP, max_iter=ITERS, seed=5, front_end=fe, **kw, **CYC)
     fe.load_frames(omni)
     pipe.step()
     want = pipe.results().cpu().numpy()
-    got = _batch_records(ctx, s, omni, kp_cap=fe.kp_cap, **kw, **CYC)
+    got = scenes.batch_records(ctx, s, omni, kp_cap=fe.kp_cap, **KW, **kw, **CYC)
     assert (want[:, 14] == 0).all() and (want[:, 13] > 50).all(), want[:, 12:16]
     assert np.array_equal(got, want), np.argwhere(got != want)[:6]
-    two = _batch_records(ctx, s, omni, kp_cap=fe.kp_cap, n_streams=2, **kw, **CYC)
+    two = scenes.batch_records(ctx, s, omni, kp_cap=fe.kp_cap, n_streams=2, **KW, **kw, **CYC)
     assert np.array_equal(two, want), np.argwhere(two != want)[:6]
-    plain = _batch_records(ctx, s, omni, kp_cap=fe.kp_cap, **kw)
+    plain = scenes.batch_records(ctx, s, omni, kp_cap=fe.kp_cap, **KW, **kw)
     # the bit does something on these pairs -- where a window can reach the seam at all: a window of half 4 over 3 levels
     # spans 24 columns and no keypoint lies within 31 of the border, and two levels of half 10 do not follow 37 columns
     if name in ("match", "gated", "lk10_4_fb"):
@@ -222,69 +188,39 @@ def test_one_call_batch_equals_the_pair_pipeline_also_over_two_streams(ctx, rigs
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb"])
-def test_records_do_not_depend_on_the_workspaces_contents(ctx, rigs, name):
-    s = _layers_scene(ctx, rigs)
-    kw, omni = SETTINGS[name], _omni_of(name)
-    a = _batch_records(ctx, s, omni, fill=0x00, **kw, **CYC)
-    b = _batch_records(ctx, s, omni, fill=0xFF, **kw, **CYC)
+def test_records_do_not_depend_on_the_workspaces_contents(ctx, name):
+    s = scenes.turning_scene(ctx)
+    kw, omni = SETTINGS[name], _omni_of(s, name)
+    a = scenes.batch_records(ctx, s, omni, fill=0x00, **KW, **kw, **CYC)
+    b = scenes.batch_records(ctx, s, omni, fill=0xFF, **KW, **kw, **CYC)
     assert np.array_equal(a, b), np.argwhere(a != b)[:6]
 
 
-def _pair_of(ctx, s, a, b, seed, name):
-    key = ("pair", a, b, seed, name)
-    if key not in _memo:
-        _memo[key] = _batch_records(ctx, s, s["seq"][[a, b]], seed=seed, adaptive=True, ransac_solver="GP3P", **SETTINGS[name], **CYC)[0]
-    return _memo[key]
-
-
 @pytest.mark.parametrize("name", ["match", "gated", "lk4_fb", "lk10"])
-def test_sequence_engine_equals_the_pair_batch_for_every_window(ctx, rigs, name):
-    s = _layers_scene(ctx, rigs)
+def test_sequence_engine_equals_the_pair_batch_for_every_window(ctx, name):
+    s = scenes.turning_scene(ctx)
     n = 5
-    want = np.stack([_pair_of(ctx, s, t - 1, t, t - 1, name) for t in range(1, n)])
+    want = np.stack([scenes.pair_record(ctx, s, t - 1, t, t - 1, **SEQ_KW, **SETTINGS[name], **CYC) for t in range(1, n)])
     assert (want[:, 14] == 0).all() and (want[:, 12] > 30).all(), want[:, 12:16]
     for window in (1, 2, 5):
         eng = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=window, **SETTINGS[name], **CYC, **SEQ_KW)
-        got = [i["spec"] for w0 in range(0, n, window) for i in eng.push_window(list(s["seq"][w0:min(w0 + window, n)]))
-               if i["spec"] is not None]
-        got = np.stack(got)
+        got = scenes.hop_records(eng, s["seq"][:n], window)
         assert np.array_equal(got, want), (window, np.argwhere(got != want)[:6])
     off = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=5, **SETTINGS[name], **SEQ_KW)
-    plain = np.stack([i["spec"] for i in off.push_window(list(s["seq"][:n])) if i["spec"] is not None])
+    plain = scenes.hop_records(off, s["seq"][:n], 5)
     assert not np.array_equal(plain, want)
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb"])
-def test_multi_sequence_lanes_equal_solo_engines(ctx, rigs, name):
-    import threading
-    s = _layers_scene(ctx, rigs)
+def test_multi_sequence_lanes_equal_solo_engines(ctx, name):
+    s = scenes.turning_scene(ctx)
     seqs = [s["seq"][0:4], s["seq"][2:6]]
     new = lambda cls, **kw: cls(ctx, s["model"], RigConfig(**s["rig_kw"]), window=2, **SETTINGS[name], **CYC, **kw, **SEQ_KW)  # noqa: E731
-    multi = new(MultiSequenceEngine, lanes=2)
-    got, errors = [None, None], []
-
-    def work(k):
-        try:
-            got[k] = scenes.drive(multi.lane(k), seqs[k], 2)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(k)
-    for k in range(2):
-        multi.begin(k)
-    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(new(MultiSequenceEngine, lanes=2), seqs, 2)
     for k in range(2):
         want = scenes.drive(new(SequenceEngine), seqs[k], 2)
         assert len(got[k]) == len(want) == 4
-        for a, b in zip(got[k], want):
-            assert a[:2] == b[:2]
-            for x, y in zip(a[2:], b[2:]):
-                assert (x is None) == (y is None) and (x is None or np.array_equal(x, y)), k
+        scenes.assert_same_drive(got[k], want)
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb"])
@@ -294,19 +230,13 @@ def test_run_vo_pose_file_does_not_depend_on_the_frame_window(ctx, tmp_path, nam
     asks of it; the demo's command line writes the same files."""
     import demo_vo_sos
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     n = 12
     seq = scenes.write_sos_sequences(tmp_path, seeds=(77,), frames=n)[0]
     gums = os.path.join(seq, "gums-calibrated.json")
     cam = load_gums_json(gums)
     lk = dict(half=4, max_iter=10, fb_max=0.5)
     opt = dict(f2f_tracker="lk", lk=lk) if name.startswith("lk") else dict(f2f_tracker="match")
-    texts, outs = {}, {}
-    for w in (32, 5, 1, 0):
-        results = str(tmp_path / ("results_%s" % w))
-        outs[w] = run_VO(None, cam, **scenes.sos_kwargs(seq, n, results), frame_window=w, cyclic_columns=True, **opt)
-        texts[w] = scenes.read_results(results)
-        assert outs[w]["tracked"] == n - 1, (w, outs[w]["message"])
+    texts, outs = scenes.run_vo_windows(cam, seq, n, tmp_path, (32, 5, 1, 0), cyclic_columns=True, **opt)
     assert texts[32] == texts[5] == texts[1] and len(texts[32][0].splitlines()) == n
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[32]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())

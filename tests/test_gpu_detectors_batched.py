@@ -18,6 +18,7 @@ import torch
 
 import refflow
 import synth
+from matching_scenes import hop_records
 from vo_single_camera_sos_amd import _lib, orb_pattern, synthetic
 from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
 from vo_single_camera_sos_amd.omnistereo.gum import synthetic_gums
@@ -150,10 +151,8 @@ def test_sequence_engine_equals_the_pair_batch(ctx, method):
     for window in (1, 4, 6):
         eng = SequenceEngine(ctx, model, RigConfig(**rig_kw), window=window, **kw)
         assert eng.cfg.detector == _lib.DETECTORS[method]
-        got = []
-        for w0 in range(0, n, window):
-            got += [i["spec"] for i in eng.push_window(list(frames[w0:w0 + window])) if i["spec"] is not None]
-        assert np.array_equal(_bits(np.stack(got)), _bits(want)), (method, window)
+        got = hop_records(eng, frames, window)
+        assert np.array_equal(_bits(got), _bits(want)), (method, window)
 
 
 def test_run_vo_with_orb_does_not_depend_on_the_frame_window(ctx, tmp_path):
@@ -279,11 +278,8 @@ def test_rgbd_sequence_engine_and_run_vo(ctx, tmp_path, method):
     assert (want[:, 14] == 0).all() and (want[:, 12] >= 20).all(), (method, want[:, 12:16])
     for window in (1, 3, 5):
         eng = RGBDSequenceEngine(ctx, cam, window=window, **kw)
-        got = []
-        for w0 in range(0, 5, window):
-            got += [i["spec"] for i in eng.push_window([(bgr[i], depth[i]) for i in range(w0, min(5, w0 + window))])
-                    if i["spec"] is not None]
-        assert np.array_equal(_bits(np.stack(got)), _bits(want)), (method, window)
+        got = hop_records(eng, list(zip(bgr[:5], depth[:5])), window)
+        assert np.array_equal(_bits(got), _bits(want)), (method, window)
     outs, texts = {}, {}
     for w in (8, 1, 0):
         outs[w] = demo_vo_rgbd.main_rgbd_vo([seq, "--is_synthetic", "true", "--frame_window", str(w), "--detection_method",

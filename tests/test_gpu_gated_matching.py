@@ -364,10 +364,8 @@ def test_sequence_engine_equals_the_gated_refflow_for_windows_1_and_5(ctx, pairs
     n = 2 * s.B
     for window in (1, 5):
         eng = SequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), window=window, **kw)
-        got = []
-        for w0 in range(0, n, window):
-            got += [info["spec"] for info in eng.push_window(list(s.omni[w0:w0 + window])) if info["spec"] is not None]
-        assert np.array_equal(np.stack(got).view(np.uint64), want.view(np.uint64)), window
+        got = scenes.hop_records(eng, s.omni[:n], window)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), window
     assert MultiSequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), lanes=2, window=2, **kw).cfg.ransac_flags == eng.cfg.ransac_flags
 
 
@@ -407,11 +405,8 @@ def test_rgbd_pair_paths_and_sequence_equal_the_gated_refflow(ctx, rgbd, setting
     assert np.array_equal(got.cpu().numpy().view(np.uint64), rec.view(np.uint64))
     for window in (1, 5):
         eng = RGBDSequenceEngine(ctx, s.cam, window=window, **s.kw, **setting.rgbd_kw())
-        got = []
-        for w0 in range(0, 2 * s.B, window):
-            infos = eng.push_window([(s.bgr[i], s.depth[i]) for i in range(w0, min(2 * s.B, w0 + window))])
-            got += [info["spec"] for info in infos if info["spec"] is not None]
-        assert np.array_equal(np.stack(got).view(np.uint64), want_seq.view(np.uint64)), window
+        got = scenes.hop_records(eng, list(zip(s.bgr, s.depth)), window)
+        assert np.array_equal(got.view(np.uint64), want_seq.view(np.uint64)), window
 
 
 def test_rgbd_refuses_gated_stereo(ctx):
@@ -439,12 +434,7 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     seq, kw = sos_sequences[0], BY_NAME[name].run_vo_kw()
     model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
-    outs, files = {}, {}
-    for w in (5, 1, 0):
-        res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **kw, **sos_kwargs(seq, N_SEQ, res))
-        files[w] = read_results(res)
-        assert outs[w]["tracked"] == N_SEQ - 1
+    files, outs = scenes.run_vo_windows(model, seq, N_SEQ, tmp_path, (5, 1, 0), **kw)
     assert files[5] == files[1] and "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[5]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())
@@ -459,21 +449,9 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
 
 @pytest.mark.parametrize("name", NAMES)
 def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):
-    from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO, run_VO_many
     gums = os.path.join(sos_sequences[0], "gums-calibrated.json")
-    kw = BY_NAME[name].run_vo_kw()
-    want = []
-    for k, seq in enumerate(sos_sequences):
-        res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **sos_kwargs(seq, N_SEQ, res))
-        assert out["tracked"] == N_SEQ - 1
-        want.append(read_results(res))
-    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
-    outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, **kw)
-    for q, files, o in zip(many, want, outs):
-        assert read_results(q["results_path"]) == files
-        assert o["sequence_mode"]["lanes"] == 2
+    want, outs = scenes.run_vo_many_against_solo(gums, sos_sequences, N_SEQ, tmp_path, **BY_NAME[name].run_vo_kw())
+    assert all(o["sequence_mode"]["lanes"] == 2 for o in outs)
     assert want[0] != want[1]
 
 

@@ -17,50 +17,20 @@ import pytest
 
 import matching_scenes as scenes
 import synth
-from vo_single_camera_sos_amd import _lib, synthetic
+from matching_scenes import FRAME_CAP, ITERS, KW, LK_CHECKED, LK_WAVE, NFEAT, SEQ_KW
+from vo_single_camera_sos_amd import _lib
 from vo_single_camera_sos_amd.device import SosvoError
-from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
+from vo_single_camera_sos_amd.frontend import ImageFrontEnd
 from vo_single_camera_sos_amd.pipeline import FramePairBatch, FramePairPipeline, MultiSequenceEngine, RigConfig, SequenceEngine
 
 pytestmark = pytest.mark.gpu
 
-NFEAT, FRAME_CAP, ITERS = 300, 1024, 210
-LK_CHECKED = dict(half=4, levels=3, max_iter=10, fb_max=0.5)      # 16 lanes per keypoint, forward-backward check
-LK_WAVE = dict(half=10, levels=2, max_iter=10)                    # the whole-wave mapping, no check
-KW = dict(num_of_features=NFEAT, frame_cap=FRAME_CAP, max_iter=ITERS)
-_memo = {}
+_scene = scenes.translating_scene      # 3 pairs and a 6-frame sequence, used whole
 
 
-def _scene(ctx):
-    """3 rendered pairs (seed 99: its first two are the pairs test_pair_pipeline_tracks_with_lk uses) and a 6-frame sequence."""
-    if "scene" not in _memo:
-        gs, rig_kw = scenes.rig()
-        omni, poses = synthetic.make_frame_pairs(gs, 3, seed=99)
-        room, rng = synthetic.Room(seed=61), np.random.default_rng(62)
-        seq = np.stack([synthetic.render_omni(gs, room, R, t, 2.0, rng) for R, t in synthetic.trajectory(6, 61, max_t=40.0, max_deg=2.0)])
-        _memo["scene"] = dict(gs=gs, rig_kw=rig_kw, omni=omni, poses=poses, seq=seq, model=DeviceImageModel(ctx, gs, (480, 640)))
-    return _memo["scene"]
-
-
-def _batch_records(ctx, s, frames, seed=5, fill=None, n_streams=1, **kw):
-    b = FramePairBatch(ctx, s["model"], RigConfig(**s["rig_kw"]), len(frames) // 2, seed=seed, n_streams=n_streams, **dict(KW, **kw))
-    if fill is not None:
-        b.workspace.fill_(fill)
-    b.load_frames(frames)
-    out = b.step().cpu().numpy().copy()
-    ctx.synchronize()
-    return out
-
-
-def _pair_of(ctx, s, a, b, seed, lk):
-    """The pair batch's record of frames (a, b) of the sequence, memoised: what every sequence test compares against."""
-    key = ("pair", a, b, seed, tuple(sorted(lk.items())))
-    if key not in _memo:
-        _memo[key] = _batch_records(ctx, s, s["seq"][[a, b]], seed=seed, f2f_tracker="lk", lk=lk, adaptive=True, ransac_solver="GP3P")[0]
-    return _memo[key]
-
-
-SEQ_KW = dict(KW, adaptive=True, ransac_solver="GP3P")
+def _pair_record(ctx, s, a, b, seed, lk):
+    """The pair batch's record of frames (a, b) of the sequence under the tracker's settings."""
+    return scenes.pair_record(ctx, s, a, b, seed, f2f_tracker="lk", lk=lk, **SEQ_KW)
 
 
 # ---- 1. the one-call batch ---------------------------------------------------------------------------------------------------
@@ -74,20 +44,20 @@ def test_one_call_batch_equals_the_pair_pipeline(ctx, lk, subpix):
     fe.load_frames(omni)
     pipe.step()
     want = pipe.results().cpu().numpy()
-    got = _batch_records(ctx, s, omni, kp_cap=fe.kp_cap, subpix=subpix, f2f_tracker="lk", lk=lk)
+    got = scenes.batch_records(ctx, s, omni, **KW, kp_cap=fe.kp_cap, subpix=subpix, f2f_tracker="lk", lk=lk)
     assert (want[:, 14] == 0).all() and (want[:, 13] > 50).all(), want[:, 12:16]
     assert np.array_equal(got, want), np.argwhere(got != want)[:6]
-    matched = _batch_records(ctx, s, omni, kp_cap=fe.kp_cap, subpix=subpix)
+    matched = scenes.batch_records(ctx, s, omni, **KW, kp_cap=fe.kp_cap, subpix=subpix)
     assert not np.array_equal(got, matched)                      # the switch does something
 
 
 def test_streams_batch_gives_the_single_calls_records(ctx):
     """3 pairs over 2 internal streams with settings that are not the context's defaults: they reach the internal contexts."""
     s = _scene(ctx)
-    one = _batch_records(ctx, s, s["omni"], f2f_tracker="lk", lk=LK_CHECKED)
-    two = _batch_records(ctx, s, s["omni"], f2f_tracker="lk", lk=LK_CHECKED, n_streams=2)
+    one = scenes.batch_records(ctx, s, s["omni"], **KW, f2f_tracker="lk", lk=LK_CHECKED)
+    two = scenes.batch_records(ctx, s, s["omni"], **KW, f2f_tracker="lk", lk=LK_CHECKED, n_streams=2)
     assert np.array_equal(one, two), np.argwhere(one != two)[:6]
-    assert not np.array_equal(one, _batch_records(ctx, s, s["omni"], f2f_tracker="lk", lk=dict(LK_CHECKED, half=5)))
+    assert not np.array_equal(one, scenes.batch_records(ctx, s, s["omni"], **KW, f2f_tracker="lk", lk=dict(LK_CHECKED, half=5)))
 
 
 # ---- 2. the workspace's contents ---------------------------------------------------------------------------------------------
@@ -95,14 +65,14 @@ def test_records_do_not_depend_on_the_workspaces_contents(ctx):
     """Rows outside the gray range and levels that are not built keep what the workspace held: nothing may read them."""
     s = _scene(ctx)
     for lk in (LK_CHECKED, LK_WAVE):
-        a = _batch_records(ctx, s, s["omni"][:4], fill=0x00, f2f_tracker="lk", lk=lk)
-        b = _batch_records(ctx, s, s["omni"][:4], fill=0xFF, f2f_tracker="lk", lk=lk)
+        a = scenes.batch_records(ctx, s, s["omni"][:4], **KW, fill=0x00, f2f_tracker="lk", lk=lk)
+        b = scenes.batch_records(ctx, s, s["omni"][:4], **KW, fill=0xFF, f2f_tracker="lk", lk=lk)
         assert np.array_equal(a, b), np.argwhere(a != b)[:6]
     for fill in (0x00, 0xFF):                                    # ... and the sequence store: slots not written, the other half
         eng = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=2, f2f_tracker="lk", lk=LK_CHECKED, **SEQ_KW)
         eng.workspace.fill_(fill)
-        got = [i["spec"] for w0 in (0, 2) for i in eng.push_window(list(s["seq"][w0:w0 + 2])) if i["spec"] is not None]
-        assert np.array_equal(np.stack(got), np.stack([_pair_of(ctx, s, t - 1, t, t - 1, LK_CHECKED) for t in (1, 2, 3)])), fill
+        got = scenes.hop_records(eng, s["seq"][:4], 2)
+        assert np.array_equal(got, np.stack([_pair_record(ctx, s, t - 1, t, t - 1, LK_CHECKED) for t in (1, 2, 3)])), fill
 
 
 # ---- 3. the sequence engine ----------------------------------------------------------------------------------------------------
@@ -110,13 +80,11 @@ def test_records_do_not_depend_on_the_workspaces_contents(ctx):
 def test_sequence_engine_equals_the_pair_batch_for_every_window(ctx, lk):
     s = _scene(ctx)
     n = 5
-    want = np.stack([_pair_of(ctx, s, t - 1, t, t - 1, lk) for t in range(1, n)])
+    want = np.stack([_pair_record(ctx, s, t - 1, t, t - 1, lk) for t in range(1, n)])
     assert (want[:, 14] == 0).all() and (want[:, 12] > 50).all(), want[:, 12:16]
     for window in (1, 2, 5):
         eng = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=window, f2f_tracker="lk", lk=lk, **SEQ_KW)
-        got = [i["spec"] for w0 in range(0, n, window) for i in eng.push_window(list(s["seq"][w0:min(w0 + window, n)]))
-               if i["spec"] is not None]
-        got = np.stack(got)
+        got = scenes.hop_records(eng, s["seq"][:n], window)
         assert np.array_equal(got, want), (window, np.argwhere(got != want)[:6])
 
 
@@ -130,48 +98,27 @@ def test_a_promoted_keyframe_takes_its_images_along(ctx):
     slot5 = eng.push_window(list(s["seq"][4:6]))[1]["slot"]       # refills half 0: frame 1's record and images move first
     assert slot5 == infos[1]["slot"]
     got = eng.track(eng.key_slot, slot3, seed=2)
-    assert np.array_equal(got, _pair_of(ctx, s, 1, 3, 2, LK_CHECKED)), (got, _pair_of(ctx, s, 1, 3, 2, LK_CHECKED))
-    assert not np.array_equal(got, _pair_of(ctx, s, 2, 3, 2, LK_CHECKED))
-    assert not np.array_equal(got[:12], _pair_of(ctx, s, 5, 3, 2, LK_CHECKED)[:12])   # (what the slot frame 1 left now holds)
+    assert np.array_equal(got, _pair_record(ctx, s, 1, 3, 2, LK_CHECKED)), (got, _pair_record(ctx, s, 1, 3, 2, LK_CHECKED))
+    assert not np.array_equal(got, _pair_record(ctx, s, 2, 3, 2, LK_CHECKED))
+    assert not np.array_equal(got[:12], _pair_record(ctx, s, 5, 3, 2, LK_CHECKED)[:12])   # (what the slot frame 1 left now holds)
     # the list form moves images too: key slot -> the slot frame 4 sits in would be refused (read and written); copy frame 3's
     # slot over the key slot and track frame 5 against it
     eng.fam.copy_slots([slot3], [eng.key_slot])
-    assert np.array_equal(eng.track(eng.key_slot, slot5, seed=4), _pair_of(ctx, s, 3, 5, 4, LK_CHECKED))
+    assert np.array_equal(eng.track(eng.key_slot, slot5, seed=4), _pair_record(ctx, s, 3, 5, 4, LK_CHECKED))
 
 
 # ---- 5. several sequences --------------------------------------------------------------------------------------------------------
 def test_multi_sequence_lanes_equal_solo_engines(ctx):
     """Two 4-frame sequences through the lanes of one engine (one host thread each, as run_VO_many drives them) against each
     through a SequenceEngine alone: counts, seeds, both speculative records and the serial records."""
-    import threading
     s = _scene(ctx)
     seqs = [s["seq"][0:4], s["seq"][2:6]]
     new = lambda cls, **kw: cls(ctx, s["model"], RigConfig(**s["rig_kw"]), window=2, f2f_tracker="lk", lk=LK_CHECKED, **kw, **SEQ_KW)  # noqa: E731
-    multi = new(MultiSequenceEngine, lanes=2)
-    got, errors = [None, None], []
-
-    def work(k):
-        try:
-            got[k] = scenes.drive(multi.lane(k), seqs[k], 2)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(k)
-    for k in range(2):
-        multi.begin(k)
-    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(new(MultiSequenceEngine, lanes=2), seqs, 2)
     for k in range(2):
         want = scenes.drive(new(SequenceEngine), seqs[k], 2)
         assert len(got[k]) == len(want) == 4
-        for a, b in zip(got[k], want):
-            assert a[:2] == b[:2]
-            for x, y in zip(a[2:], b[2:]):
-                assert (x is None) == (y is None) and (x is None or np.array_equal(x, y)), k
+        scenes.assert_same_drive(got[k], want)
         assert want[3][4] is not None and want[3][4][14] == 0
 
 
@@ -188,15 +135,12 @@ def test_run_vo_pose_file_does_not_depend_on_the_frame_window(ctx, tmp_path):
     gums = os.path.join(seq, "gums-calibrated.json")
     cam = load_gums_json(gums)
     lk = dict(half=4, max_iter=10, fb_max=0.5)
-    texts, outs = {}, {}
-    for w in (32, 5, 1, 0, "match"):
-        results = str(tmp_path / ("results_%s" % w))
-        kw = dict(frame_window=32, f2f_tracker="match") if w == "match" else dict(frame_window=w, f2f_tracker="lk", lk=lk)
-        outs[w] = run_VO(None, cam, **scenes.sos_kwargs(seq, n, results), **kw)
-        texts[w] = scenes.read_results(results)
-        assert outs[w]["tracked"] == n - 1, (w, outs[w]["message"])
+    texts, outs = scenes.run_vo_windows(cam, seq, n, tmp_path, (32, 5, 1, 0), f2f_tracker="lk", lk=lk)
     assert texts[32] == texts[5] == texts[1] and len(texts[32][0].splitlines()) == n
-    assert texts[32][0] != texts["match"][0]
+    results = str(tmp_path / "results_match")
+    match = run_VO(None, cam, frame_window=32, f2f_tracker="match", **scenes.sos_kwargs(seq, n, results))
+    assert match["tracked"] == n - 1, match["message"]
+    assert texts[32][0] != scenes.read_results(results)[0]
     assert "sequence_mode" not in outs[0] and len(outs[0]["poses"]) == n
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[32]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())
@@ -255,7 +199,7 @@ def test_one_call_batch_tracks_with_lk(ctx):
     s = _scene(ctx)
     for name, kw in (("match", {}), ("lk half 4 + fb", dict(f2f_tracker="lk", lk=dict(half=4, max_iter=10, fb_max=0.5))),
                      ("lk half 10 + fb", dict(f2f_tracker="lk", lk=dict(half=10, max_iter=10, fb_max=0.5)))):
-        rec = _batch_records(ctx, s, s["omni"][:4], **dict(kw, num_of_features=330, frame_cap=2048, max_iter=500))
+        rec = scenes.batch_records(ctx, s, s["omni"][:4], **dict(kw, num_of_features=330, frame_cap=2048, max_iter=500))
         rot = [np.degrees(synth.pose_error(rec[i, :12].reshape(3, 4), R, t)[0]) for i, (R, t) in enumerate(s["poses"][:2])]
         print("%-16s inliers / correspondences %d / %d = %.3f, rotation error %s deg" % (
             name, rec[:, 12].sum(), rec[:, 13].sum(), rec[:, 12].sum() / max(rec[:, 13].sum(), 1), ["%.3f" % r for r in rot]))

@@ -8,7 +8,6 @@ of (reference record, current record, seed) only, so the launch that computes a 
 Seeds of the synthetic sequences (synthetic.write_sos_sequence / write_rgbd_sequence, steps |t| <= 40 mm, <= 2 degrees):
 SOS 77, 5 and 61, RGB-D 41 and 43 -- the seeds tests/test_gpu_sequence.py tracks over their whole length."""
 import os
-import threading
 
 import numpy as np
 import pytest
@@ -98,36 +97,14 @@ def test_per_problem_seeds_equal_the_oracle_problem_by_problem(ctx, solver, adap
 
 
 # ---- 2. the engines against the single-sequence engines ---------------------------------------------------------------
-def _same(a, b):
-    return (a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b))
-
-
 def _lanes_against_solo(multi, solo_of, sequences, window):
     """sequences through the lanes of `multi` (one thread each) against each through solo_of() alone."""
     S = len(sequences)
-    got, errors = [None] * S, []
-
-    def work(s):
-        try:
-            got[s] = _drive(multi.lane(s), sequences[s], window)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(s)
-    for s in range(S):
-        multi.begin(s)                  # (all live before the first one parks: the rounds are then in lockstep)
-    threads = [threading.Thread(target=work, args=(s,)) for s in range(S)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(multi, sequences, window)
     for s in range(S):
         want = _drive(solo_of(), sequences[s], window)
         assert len(got[s]) == len(want) == len(sequences[s])
-        for t, (g, w) in enumerate(zip(got[s], want)):
-            assert g[0] == w[0] and g[1] == w[1], (s, t, g[:2], w[:2])
-            assert _same(g[2], w[2]) and _same(g[3], w[3]) and _same(g[4], w[4]), (window, s, t)
+        scenes.assert_same_drive(got[s], want)
         assert max(g[0] for g in got[s]) > 50
     rounds = max(-(-len(q) // window) for q in sequences)
     c = multi.counters

@@ -162,10 +162,8 @@ def test_sequence_engines_equal_the_patched_refflow_for_windows_1_and_5(ctx, pai
     n = 2 * s.B
     for window in (1, 5):
         eng = SequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), window=window, **kw)
-        got = []
-        for w0 in range(0, n, window):
-            got += [info["spec"] for info in eng.push_window(list(s.omni[w0:w0 + window])) if info["spec"] is not None]
-        assert np.array_equal(np.stack(got).view(np.uint64), want.view(np.uint64)), window
+        got = scenes.hop_records(eng, s.omni[:n], window)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), window
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -175,7 +173,6 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
     each, as run_VO_many drives them.  Frame 0 of a lane becomes its keyframe; every later frame's speculative record (against
     its predecessor, seed t - 1) and its serial record against the keyframe slot (the lanes' serial calls of one moment share a
     launch) equal the patched refflow bit for bit."""
-    import threading
     from vo_single_camera_sos_amd.pipeline import MultiSequenceEngine
     s, setting = pairs, BY_NAME[name]
     frames, _, hops = reference(s, setting)
@@ -185,23 +182,7 @@ def test_multi_sequence_engine_equals_the_patched_refflow(ctx, pairs, name):
     multi = MultiSequenceEngine(ctx, s.model, RigConfig(**s.rig_kw), lanes=2, window=2, **kw)
     assert multi.slots == 2 * (2 * 2 + 1) and multi.cfg.n_pairs == 2 * 2
     sequences = [s.omni[:4], s.omni[:3]]
-    got, errors = [None, None], []
-
-    def work(lane):
-        try:
-            got[lane] = scenes.drive(multi.lane(lane), sequences[lane], 2)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(lane)
-    for lane in range(2):
-        multi.begin(lane)
-    threads = [threading.Thread(target=work, args=(lane,)) for lane in range(2)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(multi, sequences, 2)
     for lane in range(2):
         assert len(got[lane]) == len(sequences[lane])
         for t, (count, seed, spec, _, rec) in enumerate(got[lane]):
@@ -252,11 +233,8 @@ def test_rgbd_pair_paths_and_sequence_equal_the_patched_refflow(ctx, rgbd, setti
     assert np.array_equal(got.cpu().numpy().view(np.uint64), rec.view(np.uint64))
     for window in (1, 5):
         eng = RGBDSequenceEngine(ctx, s.cam, window=window, **s.kw, **setting.rgbd_kw())
-        got = []
-        for w0 in range(0, 2 * s.B, window):
-            infos = eng.push_window([(s.bgr[i], s.depth[i]) for i in range(w0, min(2 * s.B, w0 + window))])
-            got += [info["spec"] for info in infos if info["spec"] is not None]
-        assert np.array_equal(np.stack(got).view(np.uint64), want_seq.view(np.uint64)), window
+        got = scenes.hop_records(eng, list(zip(s.bgr, s.depth)), window)
+        assert np.array_equal(got.view(np.uint64), want_seq.view(np.uint64)), window
 
 
 def test_rgbd_refuses_the_stereo_bit_and_a_switch_without_a_ratio(ctx):
@@ -293,12 +271,7 @@ def test_run_vo_windows_and_mirror_path(ctx, sos_sequences, tmp_path, name):
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     seq, kw = sos_sequences[0], BY_NAME[name].run_vo_kw()
     model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
-    outs, files = {}, {}
-    for w in (5, 1, 0):
-        res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **kw, **sos_kwargs(seq, N_SEQ, res))
-        files[w] = read_results(res)
-        assert outs[w]["tracked"] == N_SEQ - 1
+    files, outs = scenes.run_vo_windows(model, seq, N_SEQ, tmp_path, (5, 1, 0), **kw)
     assert "sequence_mode" in outs[5] and "sequence_mode" not in outs[0]
     assert files[5] == files[1] and outs[0]["keyframe_ids"] == outs[5]["keyframe_ids"]
     print("max |pose difference| mirror path against window 5: %.3e" % max(
@@ -317,14 +290,9 @@ def test_run_vo_mirror_path_pose_file_is_byte_identical_to_the_engines_without_a
     stereo assembly uses (sosvo_pano_to_bearing), so its pose file is the engines' byte for byte.  (With numpy's arithmetic
     there, one elevation in 70 differed in its last bit and the poses in their 15th digit: at most 3.98e-15.)"""
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     seq = sos_sequences[0]
     model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
-    files, outs = {}, {}
-    for w in (5, 0):
-        res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, **sos_kwargs(seq, N_SEQ, res))
-        files[w] = read_results(res)
+    files, outs = scenes.run_vo_windows(model, seq, N_SEQ, tmp_path, (5, 0))
     print("max |pose difference| mirror path against window 5: %.3e" % max(
         float(np.abs(Ta - Tb).max()) for (_, Ta), (_, Tb) in zip(outs[0]["poses"], outs[5]["poses"])))
     assert outs[0]["tracked"] == N_SEQ - 1 and files[0] == files[5]
@@ -335,20 +303,10 @@ def test_run_vo_many_equals_the_solo_runs(ctx, sos_sequences, tmp_path, name):
     """Two sequences through the two lanes of one MultiSequenceEngine (run_VO_many) write the pose and keyframe files of their
     solo run_VO runs, byte for byte."""
     from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO, run_VO_many
+    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     gums = os.path.join(sos_sequences[0], "gums-calibrated.json")
-    kw = BY_NAME[name].run_vo_kw()
-    want = []
-    for k, seq in enumerate(sos_sequences):
-        res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=5, **kw, **sos_kwargs(seq, N_SEQ, res))
-        assert out["tracked"] == N_SEQ - 1
-        want.append(read_results(res))
-    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
-    outs = run_VO_many(load_gums_json(gums), many, frame_window=5, lanes=2, **kw)
-    for q, files, o in zip(many, want, outs):
-        assert read_results(q["results_path"]) == files
-        assert o["sequence_mode"]["lanes"] == 2
+    want, outs = scenes.run_vo_many_against_solo(gums, sos_sequences, N_SEQ, tmp_path, **BY_NAME[name].run_vo_kw())
+    assert all(o["sequence_mode"]["lanes"] == 2 for o in outs)
     assert want[0] != want[1]
     res = str(tmp_path / "off")                              # (the rule did something to these sequences)
     run_VO(None, load_gums_json(gums), frame_window=5, **sos_kwargs(sos_sequences[0], N_SEQ, res))

@@ -6,7 +6,7 @@ store's padded level-0 fill under its row range against the pair batch's); multi
 writes the same pose file whatever the window, the mirror path agrees to 1e-6 and the demo's command line writes the same file.
 And what the option is for: a seam-free frame's stereo points are those of the CPU flow on the padded model
 (oracle.flow.detect_view, refseam.unpad, refflow.stereo_frame), some of them inside the 31-column bands where the plain front
-end has none.  The helpers and settings of tests/test_gpu_lk_layers.py are used as they are."""
+end has none.  The settings are those of tests/test_gpu_lk_layers.py (matching_scenes)."""
 import os
 
 import numpy as np
@@ -15,9 +15,9 @@ import pytest
 import matching_scenes as scenes
 import refflow
 import refseam
-from test_gpu_lk_layers import FRAME_CAP, ITERS, LK_CHECKED, NFEAT, SEQ_KW, _batch_records
-from vo_single_camera_sos_amd import orb_pattern, synthetic
-from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
+from matching_scenes import FRAME_CAP, ITERS, KW, LK_CHECKED, NFEAT, SEQ_KW
+from vo_single_camera_sos_amd import orb_pattern
+from vo_single_camera_sos_amd.frontend import ImageFrontEnd
 from vo_single_camera_sos_amd.pipeline import FramePairPipeline, MultiSequenceEngine, RigConfig, SequenceEngine
 
 pytestmark = pytest.mark.gpu
@@ -25,27 +25,13 @@ pytestmark = pytest.mark.gpu
 SF = dict(cyclic_columns="seam_free")
 SETTINGS = {"match": {}, "gated": dict(gated_f2f=True), "lk4_fb": dict(f2f_tracker="lk", lk=LK_CHECKED),
             "stereo_lk": dict(stereo_refine="lk"), "lk4_fb_stereo_lk_subpix": dict(f2f_tracker="lk", lk=LK_CHECKED, stereo_refine="lk", subpix=3)}
-_memo = {}
 
 
 @pytest.fixture(scope="module")
 def scene(ctx):
-    """The rig, two rendered pairs whose second frame is the first turned by -/+ 11 degrees about the vertical axis, and a
-    6-frame sequence that turns by 7 degrees a frame while it drifts 30 mm a frame (the scenes of tests/test_gpu_cyclic_layers.py)."""
-    gs, rig_kw = scenes.rig()
-    omni = []
-    for k, seed in enumerate((5, 6)):
-        rng, room = np.random.default_rng(seed), synthetic.Room(seed=seed)
-        a = np.deg2rad(11.0 if k else -11.0)
-        R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
-        omni += [synthetic.render_omni(gs, room, np.eye(3), np.zeros(3), 2.0, rng), synthetic.render_omni(gs, room, R, np.zeros(3), 2.0, rng)]
-    room, rng = synthetic.Room(seed=71), np.random.default_rng(72)
-    seq = []
-    for k in range(6):
-        a = np.deg2rad(7.0 * k)
-        R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
-        seq.append(synthetic.render_omni(gs, room, R, np.array([30.0 * k, -10.0 * k, 0.0]), 2.0, rng))
-    return dict(gs=gs, rig_kw=rig_kw, model=DeviceImageModel(ctx, gs, (480, 640)), omni=np.stack(omni), seq=np.stack(seq))
+    """The turning scene (tests/test_gpu_cyclic_layers.py uses it too) with its -/+ 11-degree pairs as `omni`."""
+    s = scenes.turning_scene(ctx)
+    return dict(s, omni=s["yaw_omni"][11.0])
 
 
 def _pipeline(ctx, s, omni, seam_free=True, **kw):
@@ -64,77 +50,47 @@ def test_one_call_batch_equals_the_pair_pipeline_also_over_two_streams(ctx, scen
     kw, omni = SETTINGS[name], scene["omni"]
     fe, pipe = _pipeline(ctx, scene, omni, **kw)
     want = pipe.results().cpu().numpy()
-    got = _batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, **kw, **SF)
+    got = scenes.batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, **KW, **kw, **SF)
     assert (want[:, 14] == 0).all() and (want[:, 13] > 50).all(), want[:, 12:16]
     assert np.array_equal(got, want), np.argwhere(got != want)[:6]
-    two = _batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, n_streams=2, **kw, **SF)
+    two = scenes.batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, n_streams=2, **KW, **kw, **SF)
     assert np.array_equal(two, want), np.argwhere(two != want)[:6]
-    plain = _batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, cyclic_columns=True, **kw)
+    plain = scenes.batch_records(ctx, scene, omni, kp_cap=fe.kp_cap, cyclic_columns=True, **KW, **kw)
     assert not np.array_equal(got, plain)                          # the switch does something: there are points in the bands
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb", "stereo_lk"])
 def test_records_do_not_depend_on_the_workspaces_contents(ctx, scene, name):
     kw = SETTINGS[name]
-    a = _batch_records(ctx, scene, scene["omni"], fill=0x00, **kw, **SF)
-    b = _batch_records(ctx, scene, scene["omni"], fill=0xFF, **kw, **SF)
+    a = scenes.batch_records(ctx, scene, scene["omni"], fill=0x00, **KW, **kw, **SF)
+    b = scenes.batch_records(ctx, scene, scene["omni"], fill=0xFF, **KW, **kw, **SF)
     assert np.array_equal(a, b), np.argwhere(a != b)[:6]
-
-
-def _pair_of(ctx, s, a, b, seed, name):
-    key = ("pair", a, b, seed, name)
-    if key not in _memo:
-        _memo[key] = _batch_records(ctx, s, s["seq"][[a, b]], seed=seed, adaptive=True, ransac_solver="GP3P", **SETTINGS[name], **SF)[0]
-    return _memo[key]
 
 
 @pytest.mark.parametrize("name", ["match", "gated", "lk4_fb", "stereo_lk"])
 def test_sequence_engine_equals_the_pair_batch_for_every_window(ctx, scene, name):
     s, n = scene, 5
-    want = np.stack([_pair_of(ctx, s, t - 1, t, t - 1, name) for t in range(1, n)])
+    want = np.stack([scenes.pair_record(ctx, s, t - 1, t, t - 1, **SEQ_KW, **SETTINGS[name], **SF) for t in range(1, n)])
     assert (want[:, 14] == 0).all() and (want[:, 12] > 30).all(), want[:, 12:16]
     for window in (1, 2, 5):
         eng = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=window, **SETTINGS[name], **SF, **SEQ_KW)
-        got = [i["spec"] for w0 in range(0, n, window) for i in eng.push_window(list(s["seq"][w0:min(w0 + window, n)]))
-               if i["spec"] is not None]
-        got = np.stack(got)
+        got = scenes.hop_records(eng, s["seq"][:n], window)
         assert np.array_equal(got, want), (window, np.argwhere(got != want)[:6])
     off = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=5, cyclic_columns=True, **SETTINGS[name], **SEQ_KW)
-    plain = np.stack([i["spec"] for i in off.push_window(list(s["seq"][:n])) if i["spec"] is not None])
+    plain = scenes.hop_records(off, s["seq"][:n], 5)
     assert not np.array_equal(plain, want)
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb"])
 def test_multi_sequence_lanes_equal_solo_engines(ctx, scene, name):
-    import threading
     s = scene
     seqs = [s["seq"][0:4], s["seq"][2:6]]
     new = lambda cls, **kw: cls(ctx, s["model"], RigConfig(**s["rig_kw"]), window=2, **SETTINGS[name], **SF, **kw, **SEQ_KW)  # noqa: E731
-    multi = new(MultiSequenceEngine, lanes=2)
-    got, errors = [None, None], []
-
-    def work(k):
-        try:
-            got[k] = scenes.drive(multi.lane(k), seqs[k], 2)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(k)
-    for k in range(2):
-        multi.begin(k)
-    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(new(MultiSequenceEngine, lanes=2), seqs, 2)
     for k in range(2):
         want = scenes.drive(new(SequenceEngine), seqs[k], 2)
         assert len(got[k]) == len(want) == 4
-        for a, b in zip(got[k], want):
-            assert a[:2] == b[:2]
-            for x, y in zip(a[2:], b[2:]):
-                assert (x is None) == (y is None) and (x is None or np.array_equal(x, y)), k
+        scenes.assert_same_drive(got[k], want)
 
 
 @pytest.mark.parametrize("name", ["match", "lk4_fb_stereo_lk"])
@@ -151,12 +107,7 @@ def test_run_vo_pose_file_does_not_depend_on_the_frame_window(ctx, tmp_path, nam
     cam = load_gums_json(gums)
     lk = dict(half=4, max_iter=10, fb_max=0.5)
     opt = dict(f2f_tracker="lk", lk=lk, stereo_refine="lk") if name.startswith("lk") else dict(f2f_tracker="match")
-    texts, outs = {}, {}
-    for w in (32, 5, 1, 0):
-        results = str(tmp_path / ("results_%s" % w))
-        outs[w] = run_VO(None, cam, **scenes.sos_kwargs(seq, n, results), frame_window=w, cyclic_columns="seam_free", **opt)
-        texts[w] = scenes.read_results(results)
-        assert outs[w]["tracked"] == n - 1, (w, outs[w]["message"])
+    texts, outs = scenes.run_vo_windows(cam, seq, n, tmp_path, (32, 5, 1, 0), cyclic_columns="seam_free", **opt)
     assert texts[32] == texts[5] == texts[1] and len(texts[32][0].splitlines()) == n
     for (i, Ta), (j, Tb) in zip(outs[0]["poses"], outs[32]["poses"]):
         assert i == j and np.allclose(Ta, Tb, rtol=1e-6, atol=1e-9), (i, np.abs(Ta - Tb).max())

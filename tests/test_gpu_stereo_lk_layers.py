@@ -12,7 +12,6 @@ The chain rests on the stage against tests/refstereolk.py (tests/test_gpu_stereo
      run_VO_many; the demo's flags;
   5. the pose error on the two pairs beside the option off (figures printed, tracking must succeed)."""
 import os
-import threading
 
 import numpy as np
 import pytest
@@ -22,8 +21,7 @@ import matching_scenes as scenes
 import refflow
 import refstereolk as ref
 import synth
-from vo_single_camera_sos_amd import synthetic
-from vo_single_camera_sos_amd.frontend import DeviceImageModel, ImageFrontEnd
+from vo_single_camera_sos_amd.frontend import ImageFrontEnd
 from vo_single_camera_sos_amd.pipeline import (FramePairBatch, FramePairPipeline, MultiSequenceEngine, OverlappedFramePairs, RigConfig,
                                                SequenceEngine)
 
@@ -33,7 +31,6 @@ NFEAT, FRAME_CAP, ITERS = 330, 2048, 500
 KW = dict(num_of_features=NFEAT, frame_cap=FRAME_CAP, max_iter=ITERS)
 SEQ_KW = dict(num_of_features=NFEAT, frame_cap=FRAME_CAP, max_iter=210, adaptive=True, ransac_solver="GP3P")
 SLK = dict(half=3, max_shift=2.0)                    # settings that are not the context's defaults
-_memo = {}
 
 
 def _u32(a):
@@ -41,13 +38,9 @@ def _u32(a):
 
 
 def _scene(ctx):
-    if "scene" not in _memo:
-        gs, rig_kw = scenes.rig()
-        omni, poses = synthetic.make_frame_pairs(gs, 2, seed=99)
-        room, rng = synthetic.Room(seed=61), np.random.default_rng(62)
-        seq = np.stack([synthetic.render_omni(gs, room, R, t, 2.0, rng) for R, t in synthetic.trajectory(5, 61, max_t=40.0, max_deg=2.0)])
-        _memo["scene"] = dict(gs=gs, rig_kw=rig_kw, omni=omni, poses=poses, seq=seq, model=DeviceImageModel(ctx, gs, (480, 640)))
-    return _memo["scene"]
+    """The translating scene's first 2 pairs and first 5 frames."""
+    s = scenes.translating_scene(ctx)
+    return dict(s, omni=s["omni"][:4], poses=s["poses"][:2], seq=s["seq"][:5])
 
 
 def _pipe(ctx, s, **kw):
@@ -58,14 +51,9 @@ def _pipe(ctx, s, **kw):
     return fe, pipe
 
 
-def _batch_records(ctx, s, frames, seed=5, n_streams=1, fill=None, **kw):
-    b = FramePairBatch(ctx, s["model"], RigConfig(**s["rig_kw"]), len(frames) // 2, seed=seed, n_streams=n_streams, **dict(KW, **kw))
-    if fill is not None:
-        b.workspace.fill_(fill)
-    b.load_frames(frames)
-    out = b.step().cpu().numpy().copy()
-    ctx.synchronize()
-    return out
+def _records(ctx, s, frames, **kw):
+    """The one-call batch's records under this module's settings."""
+    return scenes.batch_records(ctx, s, frames, **dict(KW, **kw))
 
 
 # ---- 1. the pair pipeline ----------------------------------------------------------------------------------------------------
@@ -118,7 +106,7 @@ def test_pair_pipeline_refines_between_sort_and_assemble(ctx):
     ctx.synchronize()
     assert np.array_equal(off.results().cpu().numpy(), none.results().cpu().numpy())
     assert np.array_equal(fe0.kp.cpu().numpy(), before) and not hasattr(off, "s_lk_status")
-    assert np.array_equal(_batch_records(ctx, s, s["omni"], kp_cap=fe.kp_cap), off.results().cpu().numpy())
+    assert np.array_equal(_records(ctx, s, s["omni"], kp_cap=fe.kp_cap), off.results().cpu().numpy())
 
 
 # ---- 2. the one-call batch -----------------------------------------------------------------------------------------------------
@@ -133,12 +121,12 @@ def test_one_call_batch_equals_the_pair_pipeline(ctx, more):
     pipe.step()
     want = pipe.results().cpu().numpy()
     assert (want[:, 14] == 0).all() and (want[:, 13] > 50).all(), want[:, 12:16]
-    got = _batch_records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk", fill=0xA5, **more)
+    got = _records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk", fill=0xA5, **more)
     assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), np.argwhere(got != want)[:6]
-    off = _batch_records(ctx, s, s["omni"], kp_cap=fe.kp_cap, **{k: v for k, v in more.items() if k != "stereo_lk"})
+    off = _records(ctx, s, s["omni"], kp_cap=fe.kp_cap, **{k: v for k, v in more.items() if k != "stereo_lk"})
     assert not np.array_equal(got, off)                              # the switch does something
     if not more or "stereo_lk" in more:                              # the streams form and the stream-split pipeline
-        two = _batch_records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk", n_streams=2, **more)
+        two = _records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk", n_streams=2, **more)
         assert np.array_equal(two.view(np.uint64), want.view(np.uint64)), np.argwhere(two != want)[:6]
     if "stereo_lk" in more:
         over = OverlappedFramePairs(ctx.device.index, s["gs"], (480, 640), RigConfig(**s["rig_kw"]), 2, n_streams=2, num_of_features=NFEAT,
@@ -149,7 +137,7 @@ def test_one_call_batch_equals_the_pair_pipeline(ctx, more):
         torch.cuda.synchronize()
         over.close()
         assert np.array_equal(res.cpu().numpy().view(np.uint64), want.view(np.uint64))
-        assert not np.array_equal(got, _batch_records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk"))   # the settings arrive
+        assert not np.array_equal(got, _records(ctx, s, s["omni"], kp_cap=fe.kp_cap, stereo_refine="lk"))   # the settings arrive
 
 
 @pytest.mark.parametrize("method", ["ORB", "FAST"])
@@ -183,11 +171,8 @@ def test_other_detectors(ctx, method):
 
 
 # ---- 3. the sequence engines ---------------------------------------------------------------------------------------------------
-def _pair_of(ctx, s, a, b, seed, **kw):
-    key = ("pair", a, b, seed, repr(sorted(kw.items())))
-    if key not in _memo:
-        _memo[key] = _batch_records(ctx, s, s["seq"][[a, b]], seed=seed, **dict(SEQ_KW, **kw))[0]
-    return _memo[key]
+def _pair_record(ctx, s, a, b, seed, **kw):
+    return scenes.pair_record(ctx, s, a, b, seed, **dict(SEQ_KW, **kw))
 
 
 @pytest.mark.parametrize("more", [dict(stereo_refine="lk"), dict(stereo_refine="lk", stereo_lk=SLK, f2f_tracker="lk", lk=dict(half=4, max_iter=10))],
@@ -195,14 +180,13 @@ def _pair_of(ctx, s, a, b, seed, **kw):
 def test_sequence_engine_equals_the_pair_batch_for_every_window(ctx, more):
     s = _scene(ctx)
     n = 5
-    want = np.stack([_pair_of(ctx, s, t - 1, t, t - 1, **more) for t in range(1, n)])
+    want = np.stack([_pair_record(ctx, s, t - 1, t, t - 1, **more) for t in range(1, n)])
     assert (want[:, 14] == 0).all() and (want[:, 12] > 50).all(), want[:, 12:16]
-    assert not np.array_equal(want[0], _pair_of(ctx, s, 0, 1, 0))
+    assert not np.array_equal(want[0], _pair_record(ctx, s, 0, 1, 0))
     for window in (1, 2, 5):
         eng = SequenceEngine(ctx, s["model"], RigConfig(**s["rig_kw"]), window=window, **more, **SEQ_KW)
         eng.workspace.fill_(0x5A)
-        got = np.stack([i["spec"] for w0 in range(0, n, window) for i in eng.push_window(list(s["seq"][w0:min(w0 + window, n)]))
-                        if i["spec"] is not None])
+        got = scenes.hop_records(eng, s["seq"][:n], window)
         assert np.array_equal(got, want), (window, np.argwhere(got != want)[:6])
 
 
@@ -210,31 +194,11 @@ def test_multi_sequence_lanes_equal_solo_engines(ctx):
     s = _scene(ctx)
     seqs = [s["seq"][0:4], s["seq"][1:5]]
     new = lambda cls, **kw: cls(ctx, s["model"], RigConfig(**s["rig_kw"]), window=2, stereo_refine="lk", stereo_lk=SLK, **kw, **SEQ_KW)  # noqa: E731
-    multi = new(MultiSequenceEngine, lanes=2)
-    got, errors = [None, None], []
-
-    def work(k):
-        try:
-            got[k] = scenes.drive(multi.lane(k), seqs[k], 2)
-        except BaseException as e:  # noqa: B902
-            errors.append(e)
-        finally:
-            multi.end(k)
-    for k in range(2):
-        multi.begin(k)
-    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errors, errors
+    got = scenes.drive_lanes(new(MultiSequenceEngine, lanes=2), seqs, 2)
     for k in range(2):
         want = scenes.drive(new(SequenceEngine), seqs[k], 2)
         assert len(got[k]) == len(want) == 4
-        for a, b in zip(got[k], want):
-            assert a[:2] == b[:2]
-            for x, y in zip(a[2:], b[2:]):
-                assert (x is None) == (y is None) and (x is None or np.array_equal(x, y)), k
+        scenes.assert_same_drive(got[k], want)
         assert want[3][4] is not None and want[3][4][14] == 0
 
 
@@ -250,15 +214,12 @@ def test_run_vo_pose_file_does_not_depend_on_the_frame_window(ctx, tmp_path):
     seq, seq_b = scenes.write_sos_sequences(tmp_path, seeds=(77, 61), frames=n)
     gums = os.path.join(seq, "gums-calibrated.json")
     cam = load_gums_json(gums)
-    texts, outs = {}, {}
-    for w in (32, 5, 1, 0, "off"):
-        results = str(tmp_path / ("results_%s" % w))
-        kw = dict(frame_window=32) if w == "off" else dict(frame_window=w, stereo_refine="lk", stereo_lk=SLK)
-        outs[w] = run_VO(None, cam, **scenes.sos_kwargs(seq, n, results), **kw)
-        texts[w] = scenes.read_results(results)
-        assert outs[w]["tracked"] == n - 1, (w, outs[w]["message"])
+    texts, outs = scenes.run_vo_windows(cam, seq, n, tmp_path, (32, 5, 1, 0), stereo_refine="lk", stereo_lk=SLK)
     assert texts[32] == texts[5] == texts[1] and len(texts[32][0].splitlines()) == n
-    assert texts[32][0] != texts["off"][0]
+    results = str(tmp_path / "results_off")
+    off = run_VO(None, cam, frame_window=32, **scenes.sos_kwargs(seq, n, results))
+    assert off["tracked"] == n - 1, off["message"]
+    assert texts[32][0] != scenes.read_results(results)[0]
     assert "sequence_mode" not in outs[0] and len(outs[0]["poses"]) == n
     assert texts[0] == texts[32]                                     # the per-frame mirror path writes the same bytes
     # two lanes of one engine (run_VO_many): every sequence gets the files of its solo run
@@ -282,7 +243,7 @@ def test_pose_error_with_and_without_the_option(ctx):
     s = _scene(ctx)
     for name, kw in (("off", {}), ("half 2", dict(stereo_refine="lk", stereo_lk=dict(half=2))), ("half 4", dict(stereo_refine="lk")),
                      ("half 10", dict(stereo_refine="lk", stereo_lk=dict(half=10)))):
-        rec = _batch_records(ctx, s, s["omni"], **kw)
+        rec = _records(ctx, s, s["omni"], **kw)
         err = [synth.pose_error(rec[i, :12].reshape(3, 4), R, t) for i, (R, t) in enumerate(s["poses"])]
         print("%-8s inliers / correspondences %d / %d = %.3f, rotation error %s deg, translation error %s mm" % (
             name, rec[:, 12].sum(), rec[:, 13].sum(), rec[:, 12].sum() / max(rec[:, 13].sum(), 1),

@@ -349,12 +349,7 @@ def test_run_vo_windows_mirror_path_and_the_switch(ctx, sos_sequences, tmp_path)
     from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO
     seq = sos_sequences[0]
     model = load_gums_json(os.path.join(seq, "gums-calibrated.json"))
-    outs, files = {}, {}
-    for w in (4, 1, 0):
-        res = str(tmp_path / ("w%d" % w))
-        outs[w] = run_VO(None, model, frame_window=w, subpix_refine=True, **sos_kwargs(seq, N_SEQ, res))
-        files[w] = read_results(res)
-        assert outs[w]["tracked"] == N_SEQ - 1
+    files, outs = scenes.run_vo_windows(model, seq, N_SEQ, tmp_path, (4, 1, 0), subpix_refine=True)
     assert "sequence_mode" in outs[4] and "sequence_mode" not in outs[0]
     assert files[4] == files[1] and files[0] == files[4]
     res = str(tmp_path / "off")
@@ -369,18 +364,7 @@ def test_run_vo_windows_mirror_path_and_the_switch(ctx, sos_sequences, tmp_path)
 
 
 def test_two_lanes_equal_two_solo_runs(ctx, sos_sequences, tmp_path):
-    from vo_single_camera_sos_amd.omnistereo.gum import load_gums_json
-    from vo_single_camera_sos_amd.omnistereo.pose_est_tools import run_VO, run_VO_many
     gums = os.path.join(sos_sequences[0], "gums-calibrated.json")
-    want = []
-    for k, seq in enumerate(sos_sequences):
-        res = str(tmp_path / ("solo_%d" % k))
-        out = run_VO(None, load_gums_json(gums), frame_window=4, subpix_refine=True, **sos_kwargs(seq, N_SEQ, res))
-        assert out["tracked"] == N_SEQ - 1
-        want.append(read_results(res))
-    many = [sos_kwargs(seq, N_SEQ, str(tmp_path / ("many_%d" % k))) for k, seq in enumerate(sos_sequences)]
-    outs = run_VO_many(load_gums_json(gums), many, frame_window=4, lanes=2, subpix_refine=True)
-    for q, files, o in zip(many, want, outs):
-        assert read_results(q["results_path"]) == files
-        assert o["sequence_mode"]["lanes"] == 2
+    want, outs = scenes.run_vo_many_against_solo(gums, sos_sequences, N_SEQ, tmp_path, frame_window=4, subpix_refine=True)
+    assert all(o["sequence_mode"]["lanes"] == 2 for o in outs)
     assert want[0] != want[1]
