@@ -80,3 +80,26 @@ def test_opencv_pattern_headers_and_c_entry_carry_the_data_file():
     assert _lib.load().sosvo_orb_bit_pattern_31(None) != 0
     import oracle
     assert np.array_equal(oracle.orb_pattern(), orb_pattern.opencv_pattern())
+
+
+def test_signatures_agree_with_the_header_by_kind():
+    """Every prototype of include/sosvo.h against _lib.SIGNATURES, parameter by parameter: an int32_t / double / float /
+    uint64_t / int64_t / size_t parameter or return type is the ctypes type of that name, and every pointer is c_void_p,
+    c_char_p or a ctypes POINTER."""
+    from sosvo_header import prototypes
+    scalar = {"int32_t": ctypes.c_int32, "double": ctypes.c_double, "float": ctypes.c_float, "uint64_t": ctypes.c_uint64,
+              "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
+
+    def agrees(c_type, ct):
+        if "*" in c_type:
+            return ct in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ct, ctypes._Pointer)
+        return scalar[c_type.replace("const ", "")] is ct
+
+    protos = prototypes()
+    assert sorted(protos) == sorted(_lib.SIGNATURES) and len(protos) >= 100
+    for entry, (ret, params) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[entry]
+        assert agrees(ret, restype), "%s returns %s, bound as %s" % (entry, ret, restype)
+        assert len(params) == len(argtypes), entry
+        for (c_type, name), ct in zip(params, argtypes):
+            assert agrees(c_type, ct), "%s: %s %s is bound as %s" % (entry, c_type, name, ct)

@@ -210,3 +210,20 @@ def test_per_frame_api_tracks_like_the_batched_pipeline(ctx):
     cur.bearing_vectors_bottom_stereo_triangulated = cur.bearing_vectors_top_stereo_triangulated
     ok, msg = tracker.track_frame(ref, cur)
     assert not ok and msg == "Cannot track on only 0 point correspondences"
+
+
+def test_a_host_tensor_is_refused_before_any_library_call(ctx, monkeypatch):
+    """The residency branch of device._check, the one rule tests/test_context_calls.py cannot reach on the CPU."""
+    import torch
+    from vo_single_camera_sos_amd._lib import SosvoError
+    calls = []
+    real = ctx._call
+    monkeypatch.setattr(ctx, "_call", lambda fn, *args: (calls.append(fn.__name__), real(fn, *args))[1])
+    keys, nq = torch.zeros((1, 4, 1), dtype=torch.uint32), torch.zeros((1,), dtype=torch.int32, device=ctx.device)
+    with pytest.raises(SosvoError, match=r"^keys: must live on the GPU$"):
+        ctx.sort_matches(keys, nq)
+    assert calls == []
+    order = ctx.sort_matches(keys.to(ctx.device), nq)
+    ctx.synchronize()
+    assert calls == ["sosvo_sort_matches", "sosvo_synchronize"]
+    assert order.is_cuda and tuple(order.shape) == (1, 4) and order.dtype == torch.int32

@@ -4,11 +4,11 @@ the library: what is asserted is WHICH entry points are called, in which order, 
 here by rule (ratio -> sosvo_match_hamming_ratio, else gate -> sosvo_match_hamming_gated, else sosvo_match_hamming), the
 arguments decoded by the names of the prototypes in include/sosvo.h.  No device call is made.  Then _lib.MatchOptions."""
 import itertools
-import re
 from types import SimpleNamespace
 
 import pytest
 import torch
+from sosvo_header import parameter_names as _parameter_names
 
 from vo_single_camera_sos_amd import _lib, device
 from vo_single_camera_sos_amd._lib import MatchOptions
@@ -19,15 +19,6 @@ PLAIN, GATED, RATIO, CROSS = ("sosvo_match_hamming", "sosvo_match_hamming_gated"
 GATE = (1.0, 2.5, 80)                      # (min_dv, max_du, max_distance)
 COMBOS = list(itertools.product((0, 48), (None, GATE), (False, True)))      # ratio in 64ths, gate, cross-check
 IDS = ["%s-%s-%s" % ("ratio" if r else "noratio", "gate" if g else "nogate", "cc" if cc else "nocc") for r, g, cc in COMBOS]
-
-
-def _parameter_names(entry):
-    """The parameter names of a prototype of include/sosvo.h, without the context."""
-    text = re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
-    params = re.search(r"\b%s\s*\(([^)]*)\)" % entry, text).group(1).split(",")
-    names = [re.search(r"(\w+)\s*$", p).group(1) for p in params]
-    assert names[0] == "ctx" and len(names) == len(_lib.SIGNATURES[entry][1])
-    return names[1:]
 
 
 @pytest.fixture

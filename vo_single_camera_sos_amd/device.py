@@ -38,6 +38,110 @@ def _check(t, dtype, name, shape=None, ndim=None):
     return t
 
 
+def _check_opt(t, dtype, name, shape=None, ndim=None):
+    """An optional input: checked when given."""
+    return t if t is None else _check(t, dtype, name, shape, ndim)
+
+
+def _new(shape, dtype, dev, fill=None):
+    """A fresh buffer: fill None = uninitialised, 0 = zeros, anything else = that value everywhere."""
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if fill == 0:
+        return torch.zeros(shape, dtype=dtype, device=dev)
+    return torch.full(shape, fill, dtype=dtype, device=dev)
+
+
+def _buf(t, dtype, name, shape, dev, fill=None):
+    """An optional output: allocated when None, checked either way."""
+    return _check(_new(shape, dtype, dev, fill) if t is None else t, dtype, name, shape)
+
+
+def _struct_ptr(s):
+    """A host struct (ctypes.Structure) as the void* the entry points take."""
+    return ctypes.cast(ctypes.pointer(s), c_p)
+
+
+class Record(object):
+    """One buffer record of the C ABI, described once: (key, dtype, shape, fill) per field, in the order the entry points
+    take the pointers.  A shape names the dimensions that the call decides ("F", "cap") and spells out the rest; they are
+    bound by keyword at use (None: that dimension is not checked).  fill is what a buffer that device.py allocates holds
+    before the call (_new).  Allocation, the checks -- also of the part of a record a reader takes, sub() -- and the
+    pointer list all come from this one text."""
+
+    def __init__(self, *fields):
+        self.fields = fields
+        self.keys = tuple(f[0] for f in fields)
+        self._memo = (None, None)
+
+    def sub(self, *keys):
+        """The record of these fields only, in this record's order."""
+        assert set(keys) <= set(self.keys)
+        return Record(*[f for f in self.fields if f[0] in keys])
+
+    def _bound(self, dims):
+        """The fields with their shapes bound to `dims`.  The latest binding is kept: a hot loop asks for the same one call
+        after call (one attribute, replaced whole: records are shared by the contexts of every host thread)."""
+        memo = self._memo
+        if memo[0] != dims:
+            memo = self._memo = (dims, [(key, dtype, tuple([dims[d] if type(d) is str else d for d in shape]), fill)
+                                        for key, dtype, shape, fill in self.fields])
+        return memo[1]
+
+    def alloc(self, dev, zeroed=False, **dims):
+        """-> {key: fresh buffer}; zeroed: zeros everywhere instead of the fields' own fills."""
+        return {key: _new(shape, dtype, dev, 0 if zeroed else fill) for key, dtype, shape, fill in self._bound(dims)}
+
+    def check(self, rec, **dims):
+        for key, dtype, shape, _ in self._bound(dims):
+            _check(rec[key], dtype, key, shape)
+
+    def fill(self, dev, given, **dims):
+        """given: {key: tensor or None}, every None replaced by a fresh buffer, every field checked -> given."""
+        for key, dtype, shape, fill in self._bound(dims):
+            given[key] = _buf(given.get(key), dtype, key, shape, dev, fill)
+        return given
+
+    def of(self, dev, given, **dims):
+        """The caller's record `given`, checked, or a fresh one where it is None."""
+        if given is None:
+            return self.fill(dev, {}, **dims)
+        self.check(given, **dims)
+        return given
+
+    def ptrs(self, rec):
+        """The pointers in ABI order (a field the record lacks: NULL)."""
+        return [_ptr(rec.get(key)) for key in self.keys]
+
+
+f32, f64, i32, u8, u32 = torch.float32, torch.float64, torch.int32, torch.uint8, torch.uint32
+
+# what stereo_assemble writes per frame, and the parts f2f_assemble / f2f_assemble_tracked read
+FRAME = Record(("m_top", f32, ("F", "cap", 2), 0), ("m_bot", f32, ("F", "cap", 2), 0), ("d_top", u8, ("F", "cap", 32), 0),
+               ("d_bot", u8, ("F", "cap", 32), 0), ("X", f64, ("F", "cap", 3), 0), ("b_top", f64, ("F", "cap", 3), 0),
+               ("b_bot", f64, ("F", "cap", 3), 0), ("M", i32, ("F",), 0), ("n_cand", i32, ("F",), 0))
+FRAME_MATCHED = FRAME.sub("m_top", "m_bot", "X", "b_top", "b_bot", "M")
+FRAME_TRACKED = FRAME.sub("m_top", "m_bot", "X", "M")
+# what rgbd_assemble writes per frame
+RGBD_FRAME = Record(("m", f32, ("F", "cap", 2), 0), ("d", u8, ("F", "cap", 32), 0), ("X", f64, ("F", "cap", 3), 0),
+                    ("b", f64, ("F", "cap", 3), 0), ("M", i32, ("F",), 0))
+RGBD_FRAME_READ = RGBD_FRAME.sub("m", "X", "b", "M")        # the part f2f_assemble_central reads (it checks none of it)
+# the correspondences of f2f_assemble / f2f_assemble_tracked, and the central form of f2f_assemble_central
+CORR = Record(("f", f64, ("NP", "cap", 3), 0), ("p", f64, ("NP", "cap", 3), 0), ("cam", i32, ("NP", "cap"), 0),
+              ("q", i32, ("NP", "cap"), 0), ("t", i32, ("NP", "cap"), 0), ("n", i32, ("NP",), 0), ("n_top", i32, ("NP",), 0))
+CORR_CENTRAL = CORR.sub("f", "p", "q", "t", "n")
+# the result of ransac_abs_pose / ransac_rel_pose, with and without the per-hypothesis counts
+RANSAC_COUNTED = Record(("T", f64, ("P", 3, 4), None), ("mask", u8, ("P", "S"), 0), ("idx", i32, ("P", "S"), -1),
+                        ("n_inliers", i32, ("P",), None), ("info", i32, ("P", 4), None), ("counts", i32, ("P", "K"), None))
+RANSAC = RANSAC_COUNTED.sub("T", "mask", "idx", "n_inliers", "info")
+# the outputs of the per-mask detectors (detect_fast / detect_agast / detect_gft) and of the three ORB methods
+DETECTED = Record(("kp", f32, ("P", "cap", 2), 0), ("n", i32, ("P",), 0), ("status", i32, ("P",), 0))
+ORB = Record(("kp4", f32, ("P", "cap", 4), 0), ("resp", f32, ("P", "cap"), 0), ("n", i32, ("P",), 0),
+             ("desc", u8, ("P", "cap", 32), 0), ("kp_xy", f32, ("P", "cap", 2), 0))
+ORB_DETECTED, ORB_KP4, ORB_RESP_N = ORB.sub("kp4", "resp", "n"), ORB.sub("kp4"), ORB.sub("resp", "n")
+ORB_KP4_N, ORB_DESC, ORB_DESCRIBED = ORB.sub("kp4", "n"), ORB.sub("desc"), ORB.sub("desc", "kp_xy")
+
+
 def make_rig(pano_top, pano_bot, F_top, F_bot, min_range, max_range, stereo_min_disp=1.0, stereo_max_hdiff=2.5,
              f2f_max_hdiff=-1.0, pct_good_matches=1.0):
     """Host-side sosvo_rig.  pano_* = (cols, rows, pixel_size, cyl_height_max)."""
@@ -193,14 +297,11 @@ class Context(object):
         pano [2,F,rows,cols,3] u8 (view-major)."""
         _check(omni, torch.uint8, "omni", (None, None, None, 3))
         F, H, W = omni.shape[0], omni.shape[1], omni.shape[2]
-        if masks is not None:
-            _check(masks, torch.uint8, "masks", (2, H, W))
+        _check_opt(masks, torch.uint8, "masks", (2, H, W))
         _check(map_x, torch.float32, "map_x", (2, None, None))
         rows, cols = map_x.shape[1], map_x.shape[2]
         _check(map_y, torch.float32, "map_y", (2, rows, cols))
-        if pano is None:
-            pano = torch.empty((2, F, rows, cols, 3), dtype=torch.uint8, device=omni.device)
-        _check(pano, torch.uint8, "pano", (2, F, rows, cols, 3))
+        pano = _buf(pano, torch.uint8, "pano", (2, F, rows, cols, 3), omni.device)
         self._call(self._lib.sosvo_unwrap, _ptr(omni), _ptr(masks), _ptr(map_x), _ptr(map_y), F, H, W, rows, cols,
                    _ptr(pano))
         return pano
@@ -208,38 +309,30 @@ class Context(object):
     def unwrap_prepare(self, masks, map_x, map_y, omni_shape):
         """Model constants -> packed unwrap table [2, rows, cols, 2] u32 (once per model).  omni_shape (H, W): at most
         16384 each and 3 * W * (H - 1) >= 8, the frame-size rule of the table form (include/sosvo.h)."""
+        return self._unwrap_prepare(self._lib.sosvo_unwrap_prepare, 0, masks, map_x, map_y, omni_shape)
+
+    def _unwrap_prepare(self, entry, halo, masks, map_x, map_y, omni_shape):
         H, W = omni_shape
-        if masks is not None:
-            _check(masks, torch.uint8, "masks", (2, H, W))
+        _check_opt(masks, torch.uint8, "masks", (2, H, W))
         _check(map_x, torch.float32, "map_x", (2, None, None))
         rows, cols = map_x.shape[1], map_x.shape[2]
         _check(map_y, torch.float32, "map_y", (2, rows, cols))
-        table = torch.empty((2, rows, cols, 2), dtype=torch.uint32, device=map_x.device)
-        self._call(self._lib.sosvo_unwrap_prepare, _ptr(masks), _ptr(map_x), _ptr(map_y), H, W, rows, cols, _ptr(table))
+        table = torch.empty((2, rows, cols + 2 * halo, 2), dtype=torch.uint32, device=map_x.device)
+        self._call(entry, _ptr(masks), _ptr(map_x), _ptr(map_y), H, W, rows, cols, _ptr(table))
         return table
 
     # ---- the seam-free front end's stages (DESIGN.md section 36) -------------------------------------------------------
     def unwrap_prepare_seam_free(self, masks, map_x, map_y, omni_shape):
         """sosvo_unwrap_prepare_seam_free: the table [2, rows, cols + 80, 2] u32 of the maps padded by SEAM_HALO cyclic columns on
         either side -- byte for byte unwrap_prepare on such maps.  cols >= 40."""
-        H, W = omni_shape
-        if masks is not None:
-            _check(masks, torch.uint8, "masks", (2, H, W))
-        _check(map_x, torch.float32, "map_x", (2, None, None))
-        rows, cols = map_x.shape[1], map_x.shape[2]
-        _check(map_y, torch.float32, "map_y", (2, rows, cols))
-        table = torch.empty((2, rows, cols + 2 * _lib.SEAM_HALO, 2), dtype=torch.uint32, device=map_x.device)
-        self._call(self._lib.sosvo_unwrap_prepare_seam_free, _ptr(masks), _ptr(map_x), _ptr(map_y), H, W, rows, cols, _ptr(table))
-        return table
+        return self._unwrap_prepare(self._lib.sosvo_unwrap_prepare_seam_free, _lib.SEAM_HALO, masks, map_x, map_y, omni_shape)
 
     def mask_bits_seam_free(self, mask_bits, out=None):
         """sosvo_mask_bits_seam_free: mask_bits [nsets, rows, cols] u32 -> [nsets, rows, cols + 80], the masks in the columns
         [40, 40 + cols) and an empty halo: every original pixel is detected exactly once."""
         _check(mask_bits, torch.uint32, "mask_bits", (None, None, None))
         nsets, rows, cols = mask_bits.shape
-        if out is None:
-            out = torch.empty((nsets, rows, cols + 2 * _lib.SEAM_HALO), dtype=torch.uint32, device=mask_bits.device)
-        _check(out, torch.uint32, "out", (nsets, rows, cols + 2 * _lib.SEAM_HALO))
+        out = _buf(out, torch.uint32, "out", (nsets, rows, cols + 2 * _lib.SEAM_HALO), mask_bits.device)
         self._call(self._lib.sosvo_mask_bits_seam_free, _ptr(mask_bits), nsets, rows, cols, _ptr(out))
         return out
 
@@ -259,11 +352,8 @@ class Context(object):
         cols = int(cols)
         _check(gray, torch.uint8, "gray", (None, None, cols + 2 * _lib.SEAM_HALO))
         nimg, rows = gray.shape[0], gray.shape[1]
-        if out is None:
-            out = torch.zeros((nimg, rows, cols), dtype=torch.uint8, device=gray.device)
-        _check(out, torch.uint8, "out", (nimg, rows, cols))
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
+        out = _buf(out, torch.uint8, "out", (nimg, rows, cols), gray.device, 0)
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
         self._call(self._lib.sosvo_gray_unpad, _ptr(gray), nimg, rows, cols, _ptr(row_range), _ptr(out))
         return out
 
@@ -273,9 +363,7 @@ class Context(object):
         F, H, W = omni.shape[0], omni.shape[1], omni.shape[2]
         _check(table, torch.uint32, "table", (2, None, None, 2))
         rows, cols = table.shape[1], table.shape[2]
-        if pano is None:
-            pano = torch.empty((2, F, rows, cols, 3), dtype=torch.uint8, device=omni.device)
-        _check(pano, torch.uint8, "pano", (2, F, rows, cols, 3))
+        pano = _buf(pano, torch.uint8, "pano", (2, F, rows, cols, 3), omni.device)
         self._call(self._lib.sosvo_unwrap_table, _ptr(omni), _ptr(table), F, H, W, rows, cols, _ptr(pano))
         return pano
 
@@ -286,9 +374,7 @@ class Context(object):
             raise SosvoError("img: expected [..., rows, cols, 3]")
         rows, cols = img.shape[-3], img.shape[-2]
         nimg = int(img.numel() // (rows * cols * 3))
-        if gray is None:
-            gray = torch.empty(tuple(img.shape[:-1]), dtype=torch.uint8, device=img.device)
-        _check(gray, torch.uint8, "gray", tuple(img.shape[:-1]))
+        gray = _buf(gray, torch.uint8, "gray", tuple(img.shape[:-1]), img.device)
         self._call(self._lib.sosvo_median_gray, _ptr(img), nimg, rows, cols, int(ksize), _ptr(gray))
         return gray
 
@@ -311,9 +397,7 @@ class Context(object):
         F, H, W = omni.shape[0], omni.shape[1], omni.shape[2]
         _check(table, torch.uint32, "table", (2, None, None, 2))
         rows, cols = table.shape[1], table.shape[2]
-        if gray is None:
-            gray = torch.empty((2 * F, rows, cols), dtype=torch.uint8, device=omni.device)
-        _check(gray, torch.uint8, "gray", (2 * F, rows, cols))
+        gray = _buf(gray, torch.uint8, "gray", (2 * F, rows, cols), omni.device)
         if row_range is None:
             self._call(self._lib.sosvo_unwrap_median_gray, _ptr(omni), _ptr(table), F, H, W, rows, cols, int(ksize), _ptr(gray))
         else:
@@ -326,25 +410,23 @@ class Context(object):
         """AGAST (OAST 9/16) + its block-maximum NMS per azimuthal mask, raster order; arguments as detect_fast."""
         return self.detect_fast(gray, mask_bits, images_per_maskset, nmask, cap, threshold, kp, n, status, _agast=True)
 
-    def detect_fast(self, gray, mask_bits, images_per_maskset, nmask, cap, threshold=10, kp=None, n=None, status=None,
-                    _agast=False):
-        """FAST-9/16 + NMS per azimuthal mask, raster order: gray [NI,rows,cols] u8, mask_bits [nsets,rows,cols] u32
-        -> kp [NI*nmask, cap, 2] f32, n [NI*nmask] i32, status [NI*nmask] i32."""
+    @staticmethod
+    def _masked_images(gray, mask_bits, images_per_maskset):
+        """What the per-mask detectors check of their inputs: gray [NI,rows,cols] u8 and mask_bits with enough sets for the
+        images -> (NI, rows, cols)."""
         _check(gray, torch.uint8, "gray", ndim=3)
         NI, rows, cols = gray.shape
         _check(mask_bits, torch.uint32, "mask_bits", (None, rows, cols))
         if mask_bits.shape[0] * images_per_maskset < NI:
             raise SosvoError("mask_bits has too few sets for %d images" % NI)
-        P, dev = NI * nmask, gray.device
-        if kp is None:
-            kp = torch.zeros((P, cap, 2), dtype=torch.float32, device=dev)
-        if n is None:
-            n = torch.zeros((P,), dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.zeros((P,), dtype=torch.int32, device=dev)
-        _check(kp, torch.float32, "kp", (P, cap, 2))
-        _check(n, torch.int32, "n", (P,))
-        _check(status, torch.int32, "status", (P,))
+        return NI, rows, cols
+
+    def detect_fast(self, gray, mask_bits, images_per_maskset, nmask, cap, threshold=10, kp=None, n=None, status=None,
+                    _agast=False):
+        """FAST-9/16 + NMS per azimuthal mask, raster order: gray [NI,rows,cols] u8, mask_bits [nsets,rows,cols] u32
+        -> kp [NI*nmask, cap, 2] f32, n [NI*nmask] i32, status [NI*nmask] i32."""
+        NI, rows, cols = self._masked_images(gray, mask_bits, images_per_maskset)
+        kp, n, status = DETECTED.fill(gray.device, dict(kp=kp, n=n, status=status), P=NI * nmask, cap=cap).values()
         self._call(self._lib.sosvo_detect_agast if _agast else self._lib.sosvo_detect_fast, _ptr(gray), _ptr(mask_bits), NI,
                    int(images_per_maskset), rows, cols, int(nmask), int(threshold), int(cap), _ptr(kp), _ptr(n), _ptr(status))
         return kp, n, status
@@ -354,22 +436,8 @@ class Context(object):
                    max_corners=1000, kp=None, n=None, status=None):
         """gray [NI,rows,cols] u8, mask_bits [nsets,rows,cols] u32 (as int32 bit patterns are not accepted: use
         torch.uint32) -> kp [NI*nmask, cap, 2] f32, n [NI*nmask] i32, status [NI*nmask] i32."""
-        _check(gray, torch.uint8, "gray", ndim=3)
-        NI, rows, cols = gray.shape
-        _check(mask_bits, torch.uint32, "mask_bits", (None, rows, cols))
-        if mask_bits.shape[0] * images_per_maskset < NI:
-            raise SosvoError("mask_bits has too few sets for %d images" % NI)
-        P = NI * nmask
-        dev = gray.device
-        if kp is None:
-            kp = torch.zeros((P, cap, 2), dtype=torch.float32, device=dev)
-        if n is None:
-            n = torch.zeros((P,), dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.zeros((P,), dtype=torch.int32, device=dev)
-        _check(kp, torch.float32, "kp", (P, cap, 2))
-        _check(n, torch.int32, "n", (P,))
-        _check(status, torch.int32, "status", (P,))
+        NI, rows, cols = self._masked_images(gray, mask_bits, images_per_maskset)
+        kp, n, status = DETECTED.fill(gray.device, dict(kp=kp, n=n, status=status), P=NI * nmask, cap=cap).values()
         self._call(self._lib.sosvo_detect_gft, _ptr(gray), _ptr(mask_bits), NI, int(images_per_maskset), rows, cols,
                    int(nmask), float(quality), float(min_distance), int(max_corners), int(cap), _ptr(kp), _ptr(n),
                    _ptr(status))
@@ -385,11 +453,8 @@ class Context(object):
         cap = kp.shape[1]
         _check(n, torch.int32, "n", (P,))
         _check(pattern, torch.int8, "pattern", (512, 2))
-        if desc is None:
-            desc = torch.zeros((P, cap, 32), dtype=torch.uint8, device=gray.device)
-        _check(desc, torch.uint8, "desc", (P, cap, 32))
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
+        desc = ORB_DESC.fill(gray.device, dict(desc=desc), P=P, cap=cap)["desc"]
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
         self._call(self._lib.sosvo_describe_orb_rows, _ptr(gray), NI, rows, cols, int(nmask), cap, _ptr(kp), _ptr(n),
                    float(cos_a), float(sin_a), _ptr(pattern), int(edge), _ptr(row_range), _ptr(desc))
         return desc
@@ -398,11 +463,7 @@ class Context(object):
         """sosvo_detect_gft_candidates: the corner-response half of detect_gft.  gray [NI,rows,cols] u8, mask_bits
         [NI/images_per_maskset, rows, cols] u32 -> dict(strip_w, strips, nchunks, chunk_rows, wcap, regions, cand
         [regions, wcap, 2] u32 (response bits, y << 16 | x), wcnt [regions] u32, mstat [NI*nmask, 5] u32)."""
-        _check(gray, torch.uint8, "gray", ndim=3)
-        NI, rows, cols = gray.shape
-        _check(mask_bits, torch.uint32, "mask_bits", (None, rows, cols))
-        if mask_bits.shape[0] * images_per_maskset < NI:
-            raise SosvoError("mask_bits has too few sets for %d images" % NI)
+        NI, rows, cols = self._masked_images(gray, mask_bits, images_per_maskset)
         geo = (ctypes.c_int32 * 6)()
         args = (_ptr(gray), _ptr(mask_bits), NI, int(images_per_maskset), rows, cols, int(nmask), geo)
         self._call(self._lib.sosvo_detect_gft_candidates, *(args + (NULL, NULL, NULL)))
@@ -431,8 +492,7 @@ class Context(object):
             raise SosvoError("gauss7: nimg >= 0, rows, cols >= 1 and strides >= rows * cols")
         if nimg > 0 and (gray.numel() < (nimg - 1) * img_stride + px or out.numel() < (nimg - 1) * out_stride + px):
             raise SosvoError("gauss7: a buffer is shorter than (nimg - 1) * stride + rows * cols")
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
         self._call(self._lib.sosvo_gauss7, _ptr(gray), nimg, rows, cols, img_stride, _ptr(out), out_stride, _ptr(row_range))
         return out
 
@@ -445,8 +505,7 @@ class Context(object):
         P = NI * nmask
         _check(kp, torch.float32, "kp", (P, None, 2))
         _check(n, torch.int32, "n", (P,))
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
         self._call(self._lib.sosvo_refine_subpix, _ptr(gray), NI, rows, cols, int(nmask), kp.shape[1], _ptr(kp), _ptr(n),
                    int(half), int(max_iter), float(eps), _ptr(row_range))
         return kp
@@ -468,8 +527,7 @@ class Context(object):
         _check(gray, torch.uint8, "gray", ndim=3)
         NI, rows, cols = gray.shape
         nbytes = _lib.gray_pyramid_bytes(NI, rows, cols, levels)     # (SosvoError for sizes / levels out of range)
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
         upper = out.upper if out is not None else torch.zeros((nbytes,), dtype=torch.uint8, device=gray.device)
         _check(upper, torch.uint8, "out.upper", (nbytes,))
         self._call(self._lib.sosvo_gray_pyramid_cyclic if cyclic else self._lib.sosvo_gray_pyramid, _ptr(gray), NI, rows, cols,
@@ -500,10 +558,8 @@ class Context(object):
             next_pts = out[0] if out is not None else torch.zeros_like(prev_pts)
         _check(next_pts, torch.float32, "next_pts", (NP, cap, 2))
         dev = prev_pts.device
-        status = out[1] if out is not None else torch.zeros((NP, cap), dtype=torch.uint8, device=dev)
-        err = out[2] if out is not None else torch.zeros((NP, cap), dtype=torch.float32, device=dev)
-        _check(status, torch.uint8, "status", (NP, cap))
-        _check(err, torch.float32, "err", (NP, cap))
+        status = _buf(out[1] if out is not None else None, torch.uint8, "status", (NP, cap), dev, 0)
+        err = _buf(out[2] if out is not None else None, torch.float32, "err", (NP, cap), dev, 0)
         back = None
         if fb_max is not None:
             back = out[3] if out is not None and len(out) > 3 else torch.zeros_like(prev_pts)
@@ -536,15 +592,12 @@ class Context(object):
         _check(keys, torch.uint32, "keys")
         if tuple(keys.shape) not in ((P, cap), (P, cap, 1)):
             raise SosvoError("keys: expected shape %r (k = 1), got %r" % ((P, cap), tuple(keys.shape)))
-        if row_range is not None:
-            _check(row_range, torch.int32, "row_range", (2, 2))
-        if status is None:
-            status = torch.zeros((P, cap), dtype=torch.uint8, device=gray.device)
-        _check(status, torch.uint8, "status", (P, cap))
+        _check_opt(row_range, torch.int32, "row_range", (2, 2))
+        status = _buf(status, torch.uint8, "status", (P, cap), gray.device, 0)
         opt = _lib.StereoLkOptionsStruct.of(o)
         self._call(self._lib.sosvo_refine_stereo_lk, _ptr(gray), NI, rows, cols, _ptr(row_range), int(nmask), cap, _ptr(kp_top),
                    _ptr(n_top), _ptr(kp_bot), _ptr(n_bot), _ptr(keys), float(stereo_min_disp), float(stereo_max_hdiff),
-                   ctypes.cast(ctypes.pointer(opt), c_p), _ptr(status))
+                   _struct_ptr(opt), _ptr(status))
         return kp_bot, status
 
     def f2f_assemble_tracked(self, rig, frames, ref_frame, trk_top, trk_bot, st_top, st_bot, corr_cap, out=None, cyclic=False):
@@ -554,33 +607,15 @@ class Context(object):
         F, frame_cap = frames["m_top"].shape[0], frames["m_top"].shape[1]
         NP = ref_frame.shape[0]
         _check(ref_frame, torch.int32, "ref_frame", (NP,))
-        _check(frames["m_top"], torch.float32, "m_top", (F, frame_cap, 2))
-        _check(frames["m_bot"], torch.float32, "m_bot", (F, frame_cap, 2))
-        _check(frames["X"], torch.float64, "X", (F, frame_cap, 3))
-        _check(frames["M"], torch.int32, "M", (F,))
+        FRAME_TRACKED.check(frames, F=F, cap=frame_cap)
         for name, t in (("trk_top", trk_top), ("trk_bot", trk_bot)):
             _check(t, torch.float32, name, (NP, frame_cap, 2))
         for name, t in (("st_top", st_top), ("st_bot", st_bot)):
             _check(t, torch.uint8, name, (NP, frame_cap))
-        dev = ref_frame.device
-        if out is None:
-            out = dict(f=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       p=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       cam=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       q=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       t=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       n=torch.zeros((NP,), dtype=torch.int32, device=dev),
-                       n_top=torch.zeros((NP,), dtype=torch.int32, device=dev))
-        _check(out["f"], torch.float64, "f", (NP, corr_cap, 3))
-        _check(out["p"], torch.float64, "p", (NP, corr_cap, 3))
-        for k in ("cam", "q", "t"):
-            _check(out[k], torch.int32, k, (NP, corr_cap))
-        _check(out["n"], torch.int32, "n", (NP,))
-        _check(out["n_top"], torch.int32, "n_top", (NP,))
-        self._call(self._lib.sosvo_f2f_assemble_tracked_cyclic if cyclic else self._lib.sosvo_f2f_assemble_tracked, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
-                   _ptr(frames["m_bot"]), _ptr(frames["X"]), _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(trk_top),
-                   _ptr(trk_bot), _ptr(st_top), _ptr(st_bot), NP, corr_cap, _ptr(out["f"]), _ptr(out["p"]), _ptr(out["cam"]),
-                   _ptr(out["q"]), _ptr(out["t"]), _ptr(out["n"]), _ptr(out["n_top"]))
+        out = CORR.of(ref_frame.device, out, NP=NP, cap=corr_cap)
+        self._call(self._lib.sosvo_f2f_assemble_tracked_cyclic if cyclic else self._lib.sosvo_f2f_assemble_tracked,
+                   _struct_ptr(rig), *FRAME_TRACKED.ptrs(frames), frame_cap, _ptr(ref_frame), _ptr(trk_top), _ptr(trk_bot),
+                   _ptr(st_top), _ptr(st_bot), NP, corr_cap, *CORR.ptrs(out))
         return out
 
     # ---- K5 / K6' ----------------------------------------------------------------------
@@ -603,17 +638,7 @@ class Context(object):
         _check(mask_pyr, torch.uint32, "mask_pyr", (None, self.orb_pyramid_pixels(rows, cols)))
         if mask_pyr.shape[0] * images_per_maskset < NI:
             raise SosvoError("mask_pyr has too few sets for %d images" % NI)
-        P = NI * nmask
-        dev = gray.device
-        if kp4 is None:
-            kp4 = torch.zeros((P, cap, 4), dtype=torch.float32, device=dev)
-        if resp is None:
-            resp = torch.zeros((P, cap), dtype=torch.float32, device=dev)
-        if n is None:
-            n = torch.zeros((P,), dtype=torch.int32, device=dev)
-        _check(kp4, torch.float32, "kp4", (P, cap, 4))
-        _check(resp, torch.float32, "resp", (P, cap))
-        _check(n, torch.int32, "n", (P,))
+        kp4, resp, n = ORB_DETECTED.fill(gray.device, dict(kp4=kp4, resp=resp, n=n), P=NI * nmask, cap=cap).values()
         self._call(self._lib.sosvo_detect_orb, _ptr(gray), _ptr(mask_pyr), NI, int(images_per_maskset), rows, cols,
                    int(nmask), int(nfeatures), int(cap), _ptr(kp4), _ptr(resp), _ptr(n))
         return kp4, resp, n
@@ -623,16 +648,10 @@ class Context(object):
         _check(gray, torch.uint8, "gray", ndim=3)
         NI, rows, cols = gray.shape
         P = NI * nmask
-        _check(kp4, torch.float32, "kp4", (P, None, 4))
+        ORB_KP4_N.check(dict(kp4=kp4, n=n), P=P, cap=None)
         cap = kp4.shape[1]
-        _check(n, torch.int32, "n", (P,))
         _check(pattern, torch.int8, "pattern", (512, 2))
-        if desc is None:
-            desc = torch.zeros((P, cap, 32), dtype=torch.uint8, device=gray.device)
-        if kp_xy is None:
-            kp_xy = torch.zeros((P, cap, 2), dtype=torch.float32, device=gray.device)
-        _check(desc, torch.uint8, "desc", (P, cap, 32))
-        _check(kp_xy, torch.float32, "kp_xy", (P, cap, 2))
+        desc, kp_xy = ORB_DESCRIBED.fill(gray.device, dict(desc=desc, kp_xy=kp_xy), P=P, cap=cap).values()
         self._call(self._lib.sosvo_describe_orb_levels, _ptr(gray), NI, rows, cols, int(nmask), cap, _ptr(kp4), _ptr(n),
                    _ptr(pattern), _ptr(desc), _ptr(kp_xy))
         return desc, kp_xy
@@ -645,14 +664,12 @@ class Context(object):
         NI, rows, cols = gray.shape
         P = NI * nmask
         _check(mask_pyr, torch.uint32, "mask_pyr", (None, self.orb_pyramid_pixels(rows, cols)))
-        _check(kp4, torch.float32, "kp4", (P, None, 4))
+        rec = dict(kp4=kp4, resp=resp, n=n, desc=desc, kp_xy=kp_xy)
+        ORB_KP4.check(rec, P=P, cap=None)
         cap = kp4.shape[1]
-        _check(resp, torch.float32, "resp", (P, cap))
-        _check(n, torch.int32, "n", (P,))
+        ORB_RESP_N.check(rec, P=P, cap=cap)
         _check(pattern, torch.int8, "pattern", (512, 2))
-        _check(desc, torch.uint8, "desc", (P, cap, 32))
-        if kp_xy is not None:
-            _check(kp_xy, torch.float32, "kp_xy", (P, cap, 2))
+        (ORB_DESC if kp_xy is None else ORB_DESCRIBED).check(rec, P=P, cap=cap)
         self._call(self._lib.sosvo_detect_describe_orb, _ptr(gray), _ptr(mask_pyr), NI, int(images_per_maskset), rows, cols,
                    int(nmask), int(nfeatures), cap, _ptr(kp4), _ptr(resp), _ptr(n), _ptr(pattern), _ptr(desc),
                    _ptr(kp_xy) if kp_xy is not None else None)
@@ -681,10 +698,7 @@ class Context(object):
             if Bq != Bt:
                 raise SosvoError("q_desc and t_desc must have the same number of blocks without slots")
             P = Bq
-        if keys is None:
-            keys = torch.empty((P, Sq, k), dtype=torch.uint32, device=q_desc.device)
-        _check(keys, torch.uint32, "keys", (P, Sq, k))
-        return P, Sq, St, keys
+        return P, Sq, St, _buf(keys, torch.uint32, "keys", (P, Sq, k), q_desc.device)
 
     def match_hamming(self, q_desc, t_desc, nq, nt, k=1, keys=None, q_slot=None, t_slot=None):
         """q_desc [Bq, Sq, 32] u8, t_desc [Bt, St, 32] u8, nq [Bq] / nt [Bt] i32 -> keys [P, Sq, k] u32.
@@ -731,9 +745,7 @@ class Context(object):
             raise SosvoError("max_distance belongs to the gated form (q_pos / t_pos)")
         P, Sq, St, keys = self._hamming_args(q_desc, t_desc, nq, nt, q_slot, t_slot, keys, 1,
                                              None if q_pos is None else (q_pos, t_pos))
-        if rivals is None:
-            rivals = torch.empty((P, Sq, 1), dtype=torch.uint32, device=q_desc.device)
-        _check(rivals, torch.uint32, "rivals", (P, Sq, 1))
+        rivals = _buf(rivals, torch.uint32, "rivals", (P, Sq, 1), q_desc.device)
         self._call(self._lib.sosvo_match_hamming_ratio, _ptr(q_desc), _ptr(t_desc), _ptr(q_pos), _ptr(t_pos), _ptr(nq), _ptr(nt),
                    _ptr(q_slot), _ptr(t_slot), P, P if n_forward is None else int(n_forward), Sq, St, float(min_dv),
                    float(max_du), 256 if max_distance is None else int(max_distance), int(ratio_64ths), _ptr(keys),
@@ -825,12 +837,8 @@ class Context(object):
             _check(t_slot, torch.int32, "t_slot", (P,))
         elif nq.shape[0] != P or nt.shape[0] != P:
             raise SosvoError("nq and nt must have one entry per problem without slots")
-        if keys_out is None:
-            keys_out = torch.full((P, Sq, 1), _lib.KEY_NONE, dtype=torch.uint32, device=keys_fwd.device)
-        _check(keys_out, torch.uint32, "keys_out", (P, Sq, 1))
-        if n_kept is None:
-            n_kept = torch.empty((P,), dtype=torch.int32, device=keys_fwd.device)
-        _check(n_kept, torch.int32, "n_kept", (P,))
+        keys_out = _buf(keys_out, torch.uint32, "keys_out", (P, Sq, 1), keys_fwd.device, _lib.KEY_NONE)
+        n_kept = _buf(n_kept, torch.int32, "n_kept", (P,), keys_fwd.device)
         self._call(self._lib.sosvo_cross_check_matches, _ptr(keys_fwd), _ptr(keys_rev), _ptr(nq), _ptr(nt), _ptr(q_slot),
                    _ptr(t_slot), P, Sq, St, _ptr(keys_out), _ptr(n_kept))
         return keys_out, n_kept
@@ -844,9 +852,7 @@ class Context(object):
             _check(q_slot, torch.int32, "q_slot", (P,))
         elif nq.shape[0] != P:
             raise SosvoError("nq must have one entry per problem without q_slot")
-        if order is None:
-            order = torch.full((P, Sq), -1, dtype=torch.int32, device=keys.device)
-        _check(order, torch.int32, "order", (P, Sq))
+        order = _buf(order, torch.int32, "order", (P, Sq), keys.device, -1)
         self._call(self._lib.sosvo_sort_matches, _ptr(keys), _ptr(nq), _ptr(q_slot), P, Sq, _ptr(order))
         return order
 
@@ -877,21 +883,8 @@ class Context(object):
         cam_p, off_p, rot_p, ncam = self._rig_cams(cam, cam_off, cam_rot, P, S)
         dev = f.device
         if out is None:
-            out = dict(T=torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
-                       mask=torch.zeros((P, S), dtype=torch.uint8, device=dev),
-                       idx=torch.full((P, S), -1, dtype=torch.int32, device=dev),
-                       n_inliers=torch.empty((P,), dtype=torch.int32, device=dev),
-                       info=torch.empty((P, 4), dtype=torch.int32, device=dev))
-            if want_counts:
-                out["counts"] = torch.empty((P, int(max_iter)), dtype=torch.int32, device=dev)
-        _check(out["T"], torch.float64, "T", (P, 3, 4))
-        _check(out["mask"], torch.uint8, "mask", (P, S))
-        _check(out["idx"], torch.int32, "idx", (P, S))
-        _check(out["n_inliers"], torch.int32, "n_inliers", (P,))
-        _check(out["info"], torch.int32, "info", (P, 4))
-        counts = out.get("counts")
-        if counts is not None:
-            _check(counts, torch.int32, "counts", (P, int(max_iter)))
+            out = (RANSAC_COUNTED if want_counts else RANSAC).alloc(dev, P=P, S=S, K=int(max_iter))
+        (RANSAC if out.get("counts") is None else RANSAC_COUNTED).check(out, P=P, S=S, K=int(max_iter))
         flags = (_lib.FLAG_CAM_ROT_IDENTITY if cam_rot_identity else 0) | (_lib.FLAG_EPNP if epnp else 0) | \
             (_lib.FLAG_GP3P if gp3p else 0) | (_lib.FLAG_TWOPT if twopt else 0)
         if seeds is not None:
@@ -902,14 +895,11 @@ class Context(object):
                     or not seeds.is_contiguous() or seeds.device != dev:
                 raise SosvoError("seeds: [P] 64-bit integers, contiguous, on the problems' device")
             self._call(self._lib.sosvo_ransac_abs_pose_seeds, _ptr(f), _ptr(p), cam_p, off_p, rot_p, ncam, flags,
-                       _ptr(n), P, S, float(thr), int(max_iter), 1 if adaptive else 0, _ptr(seeds),
-                       _ptr(out["T"]), _ptr(out["mask"]), _ptr(out["idx"]), _ptr(out["n_inliers"]), _ptr(out["info"]),
-                       _ptr(counts))
+                       _ptr(n), P, S, float(thr), int(max_iter), 1 if adaptive else 0, _ptr(seeds), *RANSAC_COUNTED.ptrs(out))
             return out
         self._call(self._lib.sosvo_ransac_abs_pose, _ptr(f), _ptr(p), cam_p, off_p, rot_p, ncam, flags,
                    _ptr(n), P, S, float(thr), int(max_iter), 1 if adaptive else 0, int(seed) & (2 ** 64 - 1),
-                   _ptr(out["T"]), _ptr(out["mask"]), _ptr(out["idx"]), _ptr(out["n_inliers"]), _ptr(out["info"]),
-                   _ptr(counts))
+                   *RANSAC_COUNTED.ptrs(out))
         return out
 
     def ransac_abs_pose_seeds(self, f, p, n, thr, max_iter, seeds, **kwargs):
@@ -926,17 +916,9 @@ class Context(object):
         P, S = f1.shape[0], f1.shape[1]
         _check(f2, torch.float64, "f2", (P, S, 3))
         _check(n, torch.int32, "n", (P,))
-        dev = f1.device
-        out = dict(T=torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
-                   mask=torch.zeros((P, S), dtype=torch.uint8, device=dev),
-                   idx=torch.full((P, S), -1, dtype=torch.int32, device=dev),
-                   n_inliers=torch.empty((P,), dtype=torch.int32, device=dev),
-                   info=torch.empty((P, 4), dtype=torch.int32, device=dev))
-        if want_counts:
-            out["counts"] = torch.empty((P, int(max_iter)), dtype=torch.int32, device=dev)
+        out = (RANSAC_COUNTED if want_counts else RANSAC).alloc(f1.device, P=P, S=S, K=int(max_iter))
         self._call(self._lib.sosvo_ransac_rel_pose, _ptr(f1), _ptr(f2), _ptr(n), P, S, int(algorithm), float(thr), int(max_iter),
-                   1 if adaptive else 0, int(seed) & (2 ** 64 - 1), _ptr(out["T"]), _ptr(out["mask"]), _ptr(out["idx"]),
-                   _ptr(out["n_inliers"]), _ptr(out["info"]), _ptr(out.get("counts")))
+                   1 if adaptive else 0, int(seed) & (2 ** 64 - 1), *RANSAC_COUNTED.ptrs(out))
         return out
 
     def refine_abs_pose(self, f, p, n, T, idx=None, m=None, cam=None, cam_off=None, cam_rot=None,
@@ -953,12 +935,8 @@ class Context(object):
         if idx is not None:
             _check(idx, torch.int32, "idx", (P, S))
             _check(m, torch.int32, "m", (P,))
-        if cost is None:
-            cost = torch.empty((P,), dtype=torch.float64, device=f.device)
-        if iters is None:
-            iters = torch.empty((P,), dtype=torch.int32, device=f.device)
-        _check(cost, torch.float64, "cost", (P,))
-        _check(iters, torch.int32, "iters", (P,))
+        cost = _buf(cost, torch.float64, "cost", (P,), f.device)
+        iters = _buf(iters, torch.int32, "iters", (P,), f.device)
         self._call(self._lib.sosvo_refine_abs_pose, _ptr(f), _ptr(p), cam_p, off_p, rot_p, ncam, _ptr(n), P, S,
                    _ptr(idx), _ptr(m), int(max_lm_iter), _ptr(T), _ptr(cost), _ptr(iters))
         return T, cost, iters
@@ -1023,8 +1001,7 @@ class Context(object):
         _check(top, torch.uint8, "top", ndim=3)
         n, rows, cols = top.shape
         _check(bot, torch.uint8, "bot", (n, rows, cols))
-        if mask is not None:
-            _check(mask, torch.uint8, "mask", (rows, cols))
+        _check_opt(mask, torch.uint8, "mask", (rows, cols))
         d16 = torch.empty((n, rows, cols), dtype=torch.int16, device=top.device)
         S = torch.empty((n, rows, cols, _lib.DENSE_DISPARITIES), dtype=torch.uint16, device=top.device) if want_volume else None
         if paths == 4:
@@ -1046,7 +1023,7 @@ class Context(object):
         if max_disparity > 0 and hi <= 0:      # (an upper gate below 1/16 row passes nothing; 0 would mean no gate)
             lo, hi = 1 << 20, 1
         X = torch.empty((n, rows, cols, 3), dtype=torch.float64, device=d16.device)
-        self._call(self._lib.sosvo_dense_triangulate, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(d16), n, rows, cols, lo, hi, _ptr(X))
+        self._call(self._lib.sosvo_dense_triangulate, _struct_ptr(rig), _ptr(d16), n, rows, cols, lo, hi, _ptr(X))
         return X
 
     def dense_speckle(self, d16, *, options, want_labels=False, out=None):
@@ -1094,30 +1071,11 @@ class Context(object):
         _check(n_bot, torch.int32, "n_bot", (P,))
         _check(keys, torch.uint32, "keys", (P, cap, 1))
         _check(order, torch.int32, "order", (P, cap))
-        dev = kp_top.device
         F = nframes
-        if out is None:
-            out = dict(m_top=torch.zeros((F, out_cap, 2), dtype=torch.float32, device=dev),
-                       m_bot=torch.zeros((F, out_cap, 2), dtype=torch.float32, device=dev),
-                       d_top=torch.zeros((F, out_cap, 32), dtype=torch.uint8, device=dev),
-                       d_bot=torch.zeros((F, out_cap, 32), dtype=torch.uint8, device=dev),
-                       X=torch.zeros((F, out_cap, 3), dtype=torch.float64, device=dev),
-                       b_top=torch.zeros((F, out_cap, 3), dtype=torch.float64, device=dev),
-                       b_bot=torch.zeros((F, out_cap, 3), dtype=torch.float64, device=dev),
-                       M=torch.zeros((F,), dtype=torch.int32, device=dev),
-                       n_cand=torch.zeros((F,), dtype=torch.int32, device=dev))
-        _check(out["m_top"], torch.float32, "m_top", (F, out_cap, 2))
-        _check(out["m_bot"], torch.float32, "m_bot", (F, out_cap, 2))
-        _check(out["d_top"], torch.uint8, "d_top", (F, out_cap, 32))
-        _check(out["d_bot"], torch.uint8, "d_bot", (F, out_cap, 32))
-        for k in ("X", "b_top", "b_bot"):
-            _check(out[k], torch.float64, k, (F, out_cap, 3))
-        _check(out["M"], torch.int32, "M", (F,))
-        _check(out["n_cand"], torch.int32, "n_cand", (F,))
-        self._call(self._lib.sosvo_stereo_assemble, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(kp_top), _ptr(kp_bot),
+        out = FRAME.of(kp_top.device, out, F=F, cap=out_cap)
+        self._call(self._lib.sosvo_stereo_assemble, _struct_ptr(rig), _ptr(kp_top), _ptr(kp_bot),
                    _ptr(desc_top), _ptr(desc_bot), _ptr(n_top), _ptr(n_bot), _ptr(keys), _ptr(order), F, nmask, cap,
-                   out_cap, _ptr(out["m_top"]), _ptr(out["m_bot"]), _ptr(out["d_top"]), _ptr(out["d_bot"]),
-                   _ptr(out["X"]), _ptr(out["b_top"]), _ptr(out["b_bot"]), _ptr(out["M"]), _ptr(out["n_cand"]))
+                   out_cap, *FRAME.ptrs(out))
         return out
 
     # ---- RGB-D variant ---------------------------------------------------------------------
@@ -1131,21 +1089,9 @@ class Context(object):
         _check(n, torch.int32, "n", (F,))
         _check(depth, torch.float32, "depth", (F, None, None))
         rows, cols = depth.shape[1], depth.shape[2]
-        dev = kp.device
-        if out is None:
-            out = dict(m=torch.zeros((F, out_cap, 2), dtype=torch.float32, device=dev),
-                       d=torch.zeros((F, out_cap, 32), dtype=torch.uint8, device=dev),
-                       X=torch.zeros((F, out_cap, 3), dtype=torch.float64, device=dev),
-                       b=torch.zeros((F, out_cap, 3), dtype=torch.float64, device=dev),
-                       M=torch.zeros((F,), dtype=torch.int32, device=dev))
-        _check(out["m"], torch.float32, "m", (F, out_cap, 2))
-        _check(out["d"], torch.uint8, "d", (F, out_cap, 32))
-        _check(out["X"], torch.float64, "X", (F, out_cap, 3))
-        _check(out["b"], torch.float64, "b", (F, out_cap, 3))
-        _check(out["M"], torch.int32, "M", (F,))
-        self._call(self._lib.sosvo_rgbd_assemble, ctypes.cast(ctypes.pointer(cam), c_p), _ptr(kp), _ptr(desc), _ptr(n),
-                   _ptr(depth), F, rows, cols, cap, int(out_cap), _ptr(out["m"]), _ptr(out["d"]), _ptr(out["X"]),
-                   _ptr(out["b"]), _ptr(out["M"]))
+        out = RGBD_FRAME.of(kp.device, out, F=F, cap=out_cap)
+        self._call(self._lib.sosvo_rgbd_assemble, _struct_ptr(cam), _ptr(kp), _ptr(desc), _ptr(n),
+                   _ptr(depth), F, rows, cols, cap, int(out_cap), *RGBD_FRAME.ptrs(out))
         return out
 
     def f2f_assemble_central(self, frames, ref_frame, cur_frame, keys, order, corr_cap, pct_good_matches=1.0,
@@ -1159,30 +1105,18 @@ class Context(object):
         _check(cur_frame, torch.int32, "cur_frame", (NP,))
         _check(keys, torch.uint32, "keys", (NP, frame_cap, 1))
         _check(order, torch.int32, "order", (NP, frame_cap))
-        dev = ref_frame.device
-        if out is None:
-            out = dict(f=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       p=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       q=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       t=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       n=torch.zeros((NP,), dtype=torch.int32, device=dev))
-        _check(out["f"], torch.float64, "f", (NP, corr_cap, 3))
-        _check(out["p"], torch.float64, "p", (NP, corr_cap, 3))
-        _check(out["q"], torch.int32, "q", (NP, corr_cap))
-        _check(out["t"], torch.int32, "t", (NP, corr_cap))
-        _check(out["n"], torch.int32, "n", (NP,))
-        self._call(self._lib.sosvo_f2f_assemble_central, float(pct_good_matches), float(max_hdiff), _ptr(frames["m"]),
-                   _ptr(frames["X"]), _ptr(frames["b"]), _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(cur_frame),
-                   _ptr(keys), _ptr(order), NP, int(corr_cap), _ptr(out["f"]), _ptr(out["p"]), _ptr(out["q"]),
-                   _ptr(out["t"]), _ptr(out["n"]))
+        out = CORR_CENTRAL.of(ref_frame.device, out, NP=NP, cap=corr_cap)
+        self._call(self._lib.sosvo_f2f_assemble_central, float(pct_good_matches), float(max_hdiff),
+                   *RGBD_FRAME_READ.ptrs(frames), frame_cap, _ptr(ref_frame), _ptr(cur_frame), _ptr(keys), _ptr(order), NP,
+                   int(corr_cap), *CORR_CENTRAL.ptrs(out))
         return out
 
     # ---- whole hot path ------------------------------------------------------------------
     def frame_pair_batch_workspace(self, cfg):
-        return int(self._lib.sosvo_frame_pair_batch_workspace(ctypes.cast(ctypes.pointer(cfg), c_p)))
+        return int(self._lib.sosvo_frame_pair_batch_workspace(_struct_ptr(cfg)))
 
     def frame_pair_batch_streams_workspace(self, cfg, n_streams):
-        return int(self._lib.sosvo_frame_pair_batch_streams_workspace(ctypes.cast(ctypes.pointer(cfg), c_p), int(n_streams)))
+        return int(self._lib.sosvo_frame_pair_batch_streams_workspace(_struct_ptr(cfg), int(n_streams)))
 
     def frame_pair_batch_join(self):
         """sosvo_frame_pair_batch_streams_join: the context's stream waits for every part of the latest enqueue."""
@@ -1202,17 +1136,15 @@ class Context(object):
         _check(mask_bits, torch.uint32, "mask_bits", (2, cfg.rows, cols))
         _check(pattern, torch.int8, "pattern", (512, 2))
         _check(workspace, torch.uint8, "workspace", ndim=1)
-        if results is None:
-            results = torch.empty((B, 16), dtype=torch.float64, device=omni.device)
-        _check(results, torch.float64, "results", (B, 16))
+        results = _buf(results, torch.float64, "results", (B, 16), omni.device)
         if int(n_streams) > 1:   # the batch split over internal HIP streams of the library
             fn = self._lib.sosvo_frame_pair_batch_streams if join else self._lib.sosvo_frame_pair_batch_streams_enqueue
-            self._call(fn, ctypes.cast(ctypes.pointer(rig), c_p),
-                       ctypes.cast(ctypes.pointer(cfg), c_p), int(n_streams), _ptr(omni), _ptr(unwrap_table), _ptr(mask_bits),
+            self._call(fn, _struct_ptr(rig),
+                       _struct_ptr(cfg), int(n_streams), _ptr(omni), _ptr(unwrap_table), _ptr(mask_bits),
                        _ptr(pattern), _ptr(workspace), int(workspace.numel()), _ptr(results))
             return results
-        self._call(self._lib.sosvo_frame_pair_batch, ctypes.cast(ctypes.pointer(rig), c_p),
-                   ctypes.cast(ctypes.pointer(cfg), c_p), _ptr(omni), _ptr(unwrap_table), _ptr(mask_bits), _ptr(pattern),
+        self._call(self._lib.sosvo_frame_pair_batch, _struct_ptr(rig),
+                   _struct_ptr(cfg), _ptr(omni), _ptr(unwrap_table), _ptr(mask_bits), _ptr(pattern),
                    _ptr(workspace), int(workspace.numel()), _ptr(results))
         return results
 
@@ -1226,10 +1158,10 @@ class Context(object):
         return ctypes.cast((ctype * max(len(values), 1))(*[int(x) & wrap for x in values]), c_p)
 
     def _seq_call(self, name, heads, window, slots, *args):
-        self._call(getattr(self._lib, name), *[ctypes.cast(ctypes.pointer(h), c_p) for h in heads], int(window), int(slots), *args)
+        self._call(getattr(self._lib, name), *[_struct_ptr(h) for h in heads], int(window), int(slots), *args)
 
     def _seq_workspace(self, prefix, cfg, window, slots):
-        return int(getattr(self._lib, prefix + "workspace")(ctypes.cast(ctypes.pointer(cfg), c_p), int(window), int(slots)))
+        return int(getattr(self._lib, prefix + "workspace")(_struct_ptr(cfg), int(window), int(slots)))
 
     def _seq_front_end(self, prefix, heads, window, slots, images, first_slot, slot_of_frame, consts, workspace):
         """images: the tensors with one row per frame, consts: the model's; slot_of_frame None: ..._front_end at first_slot."""
@@ -1357,7 +1289,7 @@ class Context(object):
         self._seq_copy("sosvo_rgbd_sequence_", cfg, window, slots, src_slots, dst_slots, workspace, True)
 
     def rgbd_pair_batch_workspace(self, cfg):
-        return int(self._lib.sosvo_rgbd_pair_batch_workspace(ctypes.cast(ctypes.pointer(cfg), c_p)))
+        return int(self._lib.sosvo_rgbd_pair_batch_workspace(_struct_ptr(cfg)))
 
     def rgbd_pair_batch(self, cam, cfg, bgr, depth, mask_bits, pattern, workspace, results=None):
         """bgr [2B,rows,cols,3] u8, depth [2B,rows,cols] f32, mask_bits [1,rows,cols] u32, pattern [512,2] i8,
@@ -1368,11 +1300,9 @@ class Context(object):
         _check(mask_bits, torch.uint32, "mask_bits", (1, cfg.rows, cfg.cols))
         _check(pattern, torch.int8, "pattern", (512, 2))
         _check(workspace, torch.uint8, "workspace", ndim=1)
-        if results is None:
-            results = torch.empty((B, 16), dtype=torch.float64, device=bgr.device)
-        _check(results, torch.float64, "results", (B, 16))
-        self._call(self._lib.sosvo_rgbd_pair_batch, ctypes.cast(ctypes.pointer(cam), c_p),
-                   ctypes.cast(ctypes.pointer(cfg), c_p), _ptr(bgr), _ptr(depth), _ptr(mask_bits), _ptr(pattern),
+        results = _buf(results, torch.float64, "results", (B, 16), bgr.device)
+        self._call(self._lib.sosvo_rgbd_pair_batch, _struct_ptr(cam),
+                   _struct_ptr(cfg), _ptr(bgr), _ptr(depth), _ptr(mask_bits), _ptr(pattern),
                    _ptr(workspace), int(workspace.numel()), _ptr(results))
         return results
 
@@ -1385,33 +1315,13 @@ class Context(object):
         NP = ref_frame.shape[0]
         _check(ref_frame, torch.int32, "ref_frame", (NP,))
         _check(cur_frame, torch.int32, "cur_frame", (NP,))
-        _check(frames["m_top"], torch.float32, "m_top", (F, frame_cap, 2))
-        _check(frames["m_bot"], torch.float32, "m_bot", (F, frame_cap, 2))
-        for k in ("X", "b_top", "b_bot"):
-            _check(frames[k], torch.float64, k, (F, frame_cap, 3))
-        _check(frames["M"], torch.int32, "M", (F,))
+        FRAME_MATCHED.check(frames, F=F, cap=frame_cap)
         for name, t in (("keys_top", keys_top), ("keys_bot", keys_bot)):
             _check(t, torch.uint32, name, (NP, frame_cap, 1))
         for name, t in (("order_top", order_top), ("order_bot", order_bot)):
             _check(t, torch.int32, name, (NP, frame_cap))
-        dev = ref_frame.device
-        if out is None:
-            out = dict(f=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       p=torch.zeros((NP, corr_cap, 3), dtype=torch.float64, device=dev),
-                       cam=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       q=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       t=torch.zeros((NP, corr_cap), dtype=torch.int32, device=dev),
-                       n=torch.zeros((NP,), dtype=torch.int32, device=dev),
-                       n_top=torch.zeros((NP,), dtype=torch.int32, device=dev))
-        _check(out["f"], torch.float64, "f", (NP, corr_cap, 3))
-        _check(out["p"], torch.float64, "p", (NP, corr_cap, 3))
-        for k in ("cam", "q", "t"):
-            _check(out[k], torch.int32, k, (NP, corr_cap))
-        _check(out["n"], torch.int32, "n", (NP,))
-        _check(out["n_top"], torch.int32, "n_top", (NP,))
-        self._call(self._lib.sosvo_f2f_assemble_cyclic if cyclic else self._lib.sosvo_f2f_assemble, ctypes.cast(ctypes.pointer(rig), c_p), _ptr(frames["m_top"]),
-                   _ptr(frames["m_bot"]), _ptr(frames["X"]), _ptr(frames["b_top"]), _ptr(frames["b_bot"]),
-                   _ptr(frames["M"]), frame_cap, _ptr(ref_frame), _ptr(cur_frame), _ptr(keys_top), _ptr(order_top),
-                   _ptr(keys_bot), _ptr(order_bot), NP, corr_cap, _ptr(out["f"]), _ptr(out["p"]), _ptr(out["cam"]),
-                   _ptr(out["q"]), _ptr(out["t"]), _ptr(out["n"]), _ptr(out["n_top"]))
+        out = CORR.of(ref_frame.device, out, NP=NP, cap=corr_cap)
+        self._call(self._lib.sosvo_f2f_assemble_cyclic if cyclic else self._lib.sosvo_f2f_assemble, _struct_ptr(rig),
+                   *FRAME_MATCHED.ptrs(frames), frame_cap, _ptr(ref_frame), _ptr(cur_frame), _ptr(keys_top), _ptr(order_top),
+                   _ptr(keys_bot), _ptr(order_bot), NP, corr_cap, *CORR.ptrs(out))
         return out

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib, orb_pattern
-from .device import Context
+from .device import DETECTED, ORB, ORB_DESC, Context
 
 
 class DeviceImageModel(object):
@@ -125,10 +125,8 @@ class ImageFrontEnd(object):
         self.keep_panoramas = bool(keep_panoramas) or self.median_win_size not in (0, 1, 3, 5, 11)
         self.pano = torch.zeros((2, self.F, m.rows, cols, 3), dtype=torch.uint8, device=dev) if self.keep_panoramas else None
         self.gray = torch.zeros((NI, m.rows, cols), dtype=torch.uint8, device=dev)
-        self.kp = torch.zeros((P, self.kp_cap, 2), dtype=torch.float32, device=dev)
-        self.n = torch.zeros((P,), dtype=torch.int32, device=dev)
-        self.status = torch.zeros((P,), dtype=torch.int32, device=dev)
-        self.desc = torch.zeros((P, self.kp_cap, 32), dtype=torch.uint8, device=dev)
+        self.kp, self.n, self.status = DETECTED.alloc(dev, zeroed=True, P=P, cap=self.kp_cap).values()
+        self.desc = ORB_DESC.alloc(dev, zeroed=True, P=P, cap=self.kp_cap)["desc"]
         self.cos_a, self.sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
         # Rows no consumer can reach (beyond the masks' elevation padding + the GFT halo and the descriptor border) are
         # not computed by the fused K1-K3 kernel.  Model constant, keyed by what it depends on; computed here (and
@@ -142,8 +140,7 @@ class ImageFrontEnd(object):
                 ctx.synchronize()
             self.gray_rows = cache[key]
         if self.method == "ORB":
-            self.kp4 = torch.zeros((P, self.kp_cap, 4), dtype=torch.float32, device=dev)
-            self.resp = torch.zeros((P, self.kp_cap), dtype=torch.float32, device=dev)
+            self.kp4, self.resp = ORB.sub("kp4", "resp").alloc(dev, zeroed=True, P=P, cap=self.kp_cap).values()
             if getattr(model, "mask_pyr", None) is None:
                 model.mask_pyr = ctx.orb_mask_pyramid(model.mask_bits, model.nmask)
 

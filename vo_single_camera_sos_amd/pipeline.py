@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import LK_MAX_LEVELS, SEAM_FREE, StepOptions, cyclic_value, detector_code, rgbd_detector_flags
-from .device import Context, make_rig
+from .device import CORR, CORR_CENTRAL, DETECTED, FRAME, ORB, ORB_DESC, RANSAC, RGBD_FRAME, Context, make_rig
 
 
 class RigConfig(object):
@@ -117,11 +117,8 @@ class FramePairPipeline(object):
         self._d2 = z((2, self.F, Fc, 32), torch.uint8)
         self._M2 = z((2, self.F), torch.int32)
         self._m2 = z((2, self.F, Fc, 2), torch.float32)      # (the positions likewise: the gated search reads them)
-        self.frames = dict(m_top=self._m2[0], m_bot=self._m2[1],
-                           d_top=self._d2[0], d_bot=self._d2[1],
-                           X=z((self.F, Fc, 3), torch.float64), b_top=z((self.F, Fc, 3), torch.float64),
-                           b_bot=z((self.F, Fc, 3), torch.float64), M=self._M2[0],
-                           n_cand=z((self.F,), torch.int32))
+        self.frames = dict(m_top=self._m2[0], m_bot=self._m2[1], d_top=self._d2[0], d_bot=self._d2[1], M=self._M2[0],
+                           **FRAME.sub("X", "b_top", "b_bot", "n_cand").alloc(dev, zeroed=True, F=self.F, cap=Fc))
         self.ref_frame = torch.arange(0, self.F, 2, dtype=torch.int32, device=dev)
         self.cur_frame = torch.arange(1, self.F, 2, dtype=torch.int32, device=dev)
         q = torch.cat([self.cur_frame, self.cur_frame + self.F])   # problem i: top view, B + i: bottom view
@@ -138,12 +135,8 @@ class FramePairPipeline(object):
         self._cyc = dict(cyclic=True) if self.cyclic else {}     # (off: the assembles are called as they always were)
         self.k_top, self.k_bot = self._k2[: self.B], self._k2[self.B:]
         self.o_top, self.o_bot = self._o2[: self.B], self._o2[self.B:]
-        self.corr = dict(f=z((self.B, Cc, 3), torch.float64), p=z((self.B, Cc, 3), torch.float64),
-                         cam=z((self.B, Cc), torch.int32), q=z((self.B, Cc), torch.int32),
-                         t=z((self.B, Cc), torch.int32), n=z((self.B,), torch.int32), n_top=z((self.B,), torch.int32))
-        self.ransac = dict(T=z((self.B, 3, 4), torch.float64), mask=z((self.B, Cc), torch.uint8),
-                           idx=z((self.B, Cc), torch.int32), n_inliers=z((self.B,), torch.int32),
-                           info=z((self.B, 4), torch.int32))
+        self.corr = CORR.alloc(dev, zeroed=True, NP=self.B, cap=Cc)
+        self.ransac = RANSAC.alloc(dev, zeroed=True, P=self.B, S=Cc)
         self.T = z((self.B, 3, 4), torch.float64)
         self.lm_cost, self.lm_iters = z((self.B,), torch.float64), z((self.B,), torch.int32)
         self.cam_off = torch.from_numpy(np.stack([rig.F_top, rig.F_bot])).to(dev)
@@ -1039,14 +1032,12 @@ class RGBDFrontEnd(object):
         self.mask_bits = torch.from_numpy(mb).to(dev)       # one mask (bit 0): RGBDFrame.mask or the whole image
         self.pattern = torch.from_numpy(orb_pattern.orb_pattern()).to(dev)
         self.cos_a, self.sin_a = orb_pattern.angle_cos_sin(orb_pattern.GFT_KEYPOINT_ANGLE)
-        self.kp, self.n = z((F, self.kp_cap, 2), torch.float32), z((F,), torch.int32)
-        self.status, self.desc = z((F,), torch.int32), z((F, self.kp_cap, 32), torch.uint8)
+        self.kp, self.n, self.status = DETECTED.alloc(dev, zeroed=True, P=F, cap=self.kp_cap).values()
+        self.desc = ORB_DESC.alloc(dev, zeroed=True, P=F, cap=self.kp_cap)["desc"]
         if self.method == "ORB":
-            self.kp4, self.resp = z((F, self.kp_cap, 4), torch.float32), z((F, self.kp_cap), torch.float32)
+            self.kp4, self.resp = ORB.sub("kp4", "resp").alloc(dev, zeroed=True, P=F, cap=self.kp_cap).values()
             self.mask_pyr = ctx.orb_mask_pyramid(self.mask_bits, 1)   # once per mask
-        Fc = self.frame_cap
-        self.frames = dict(m=z((F, Fc, 2), torch.float32), d=z((F, Fc, 32), torch.uint8), X=z((F, Fc, 3), torch.float64),
-                           b=z((F, Fc, 3), torch.float64), M=z((F,), torch.int32))
+        self.frames = RGBD_FRAME.alloc(dev, zeroed=True, F=F, cap=self.frame_cap)
 
     def load_frames(self, bgr, depth):
         """bgr [F,rows,cols,3] u8, depth [F,rows,cols] f32 (the camera's depth units, 0 = no reading)."""
@@ -1117,10 +1108,8 @@ class RGBDPairPipeline(object):
         # what track() hands the matching step: the |du| gate of f2f_assemble_central
         self._f2f_search = dict(ratio_64ths=o.ratio_64ths_f2f, rivals=torch.zeros_like(self._k) if o.ratio_f2f else None,
                                 gate=(-1.0, cam.f2f_max_hdiff, gated_max_distance) if o.gated_f2f else None)
-        self.corr = dict(f=z((B, Fc, 3), torch.float64), p=z((B, Fc, 3), torch.float64), q=z((B, Fc), torch.int32),
-                         t=z((B, Fc), torch.int32), n=z((B,), torch.int32))
-        self.ransac = dict(T=z((B, 3, 4), torch.float64), mask=z((B, Fc), torch.uint8), idx=z((B, Fc), torch.int32),
-                           n_inliers=z((B,), torch.int32), info=z((B, 4), torch.int32))
+        self.corr = CORR_CENTRAL.alloc(dev, zeroed=True, NP=B, cap=Fc)
+        self.ransac = RANSAC.alloc(dev, zeroed=True, P=B, S=Fc)
         self.T = z((B, 3, 4), torch.float64)
         self.lm_cost, self.lm_iters = z((B,), torch.float64), z((B,), torch.int32)
 
