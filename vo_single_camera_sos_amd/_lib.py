@@ -747,6 +747,71 @@ class SpeckleOptions(namedtuple("SpeckleOptions", "max_size max_diff cyclic")):
         return DENSE_CYCLIC_COLUMNS if self.cyclic else 0
 
 
+WLS_MAX_LAMBDA, WLS_MAX_ITERS, WLS_MAX_RADIUS, WLS_MAX_ROLL_PPM = 1.0e6, 8, 7, 1000000
+
+
+class WlsOptions(namedtuple("WlsOptions", "lam sigma iters radius roll_ppm min_weight cyclic")):
+    """The settings of the WLS disparity filter (sosvo_dense_confidence, sosvo_dense_wls in include/sosvo_dense_filter.h,
+    DESIGN.md section 41) as one checked value: lam 0 .. 10^6 (the smoothing weight, the reference's "WLS lambda"), sigma > 0
+    (two neighbours whose gray values differ by k have the affinity exp(-k / sigma); the reference's "WLS sigma" / 100), iters
+    1 .. 8 passes of the row and the column solve, radius 0 .. 7 and roll_ppm 0 .. 10^6 of the confidence's variance window,
+    min_weight > 0 (a pixel whose smoothed confidence stays below 255 * min_weight has no disparity), cyclic: the last column
+    neighbours the first.  A value out of range raises ValueError; nothing is rounded.  A value of its own: no field of
+    DenseOptions and none of StepOptions."""
+    __slots__ = ()
+
+    def __new__(cls, lam=8000.0, sigma=1.0, iters=3, radius=3, roll_ppm=1000, min_weight=2.0 ** -20, cyclic=False):
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or int(v) != v or not lo <= v <= hi:
+                raise ValueError("wls %s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+            return int(v)
+
+        def number(name, v, ok, what):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), -float("inf")) or not ok(v):
+                raise ValueError("wls %s must be %s, got %r" % (name, what, v))
+            return float(v)
+        if not isinstance(cyclic, (bool, int)) or cyclic not in (0, 1):
+            raise ValueError("wls cyclic must be a bool, got %r" % (cyclic,))
+        return super().__new__(cls, number("lam", lam, lambda v: 0 <= v <= WLS_MAX_LAMBDA, "a number in 0 .. 10^6"),
+                               number("sigma", sigma, lambda v: v > 0, "a finite number above 0"),
+                               integer("iters", iters, 1, WLS_MAX_ITERS), integer("radius", radius, 0, WLS_MAX_RADIUS),
+                               integer("roll_ppm", roll_ppm, 0, WLS_MAX_ROLL_PPM),
+                               number("min_weight", min_weight, lambda v: v > 0, "a finite number above 0"), bool(cyclic))
+
+    @classmethod
+    def of(cls, value):
+        """A `wls` argument (None: the filter is off, None comes back; a WlsOptions; a dict of its fields) -> the value."""
+        if value is None or isinstance(value, cls):
+            return value
+        if not isinstance(value, dict):
+            raise ValueError("wls must be None, a WlsOptions or a dict of its fields, got %r" % (value,))
+        if set(value) - set(cls._fields):
+            raise ValueError("wls: unknown settings %s" % sorted(set(value) - set(cls._fields)))
+        return cls(**value)
+
+    @classmethod
+    def from_tuner(cls, use_WLS_filter, wls_lambda, wls_sigma, cyclic=False):
+        """The reference's three controls (common_cv.StereoMatchTuner: "Use WLS filter", "WLS lambda", "WLS sigma") -> the
+        value: the switch off gives None, and sigma = wls_sigma / 100 as common_cv.py:679 hands it to setSigmaColor."""
+        if use_WLS_filter not in (0, 1):
+            raise ValueError("use_WLS_filter must be a bool, got %r" % (use_WLS_filter,))
+        if isinstance(wls_sigma, bool) or not isinstance(wls_sigma, (int, float)):
+            raise ValueError("wls_sigma must be a number, got %r" % (wls_sigma,))
+        value = cls(lam=wls_lambda, sigma=wls_sigma / 100.0, cyclic=cyclic)
+        return value if use_WLS_filter else None
+
+    def weight_table(self):
+        """The 256 doubles sosvo_dense_wls takes: exp(-k / sigma) for the gray difference k, made here once so that the
+        device and the numpy reference read the same table (the device evaluates no exponential)."""
+        import math
+        return [math.exp(-k / self.sigma) for k in range(256)]
+
+    @property
+    def flags(self):
+        """The flags word of sosvo_dense_confidence / sosvo_dense_wls."""
+        return DENSE_CYCLIC_COLUMNS if self.cyclic else 0
+
+
 def rgbd_flags_detector(flags):
     """SOSVO_RGBD_DETECTOR_OF(flags)."""
     return (int(flags) & RGBD_DETECTOR_MASK) >> RGBD_DETECTOR_SHIFT

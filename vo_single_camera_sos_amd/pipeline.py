@@ -1629,12 +1629,16 @@ class DenseOmniStereo(object):
     the argument.  With a value step() filters d16 in place (Context.dense_speckle) between the stereo and the triangulation,
     so that the returned map, X and depth() are the filtered ones.
     paths: 4, or 8 for the diagonal aggregation paths as well, the reference tuner's "Full DP"
-    trackbar: paths = 8 if tuner.full_dyn_prog else 4.  With 4 nothing differs from an engine without the argument."""
+    trackbar: paths = 8 if tuner.full_dyn_prog else 4.  With 4 nothing differs from an engine without the argument.
+    wls: what WlsOptions.of takes, the tuner's "Use WLS filter" / "WLS lambda" / "WLS sigma" through
+    WlsOptions.from_tuner.  None: no filter, and nothing differs from an engine without the argument.  With a value step() runs
+    dense_filter.dense_confidence and dense_filter.dense_wls on d16, guided by the top gray panoramas under the engine's mask,
+    in place, after the stereo and the speckle filter and before the triangulation."""
 
     def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0,
-                 speckle=None, paths=4):
-        from ._lib import DenseOptions, SpeckleOptions, dense_paths
-        self.options, self.speckle = DenseOptions.of(options), SpeckleOptions.of(speckle)
+                 speckle=None, paths=4, wls=None):
+        from ._lib import DenseOptions, SpeckleOptions, WlsOptions, dense_paths
+        self.options, self.speckle, self.wls = DenseOptions.of(options), SpeckleOptions.of(speckle), WlsOptions.of(wls)
         self.paths = dense_paths(paths, self.options)
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         if tuple(rig.pano_top) != tuple(rig.pano_bot):
@@ -1658,6 +1662,10 @@ class DenseOmniStereo(object):
         self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options, paths=self.paths)
         if self.speckle is not None:
             c.dense_speckle(self.d16, options=self.speckle, out=self.d16)
+        if self.wls is not None:
+            from . import dense_filter
+            self.conf = dense_filter.dense_confidence(c, self.d16, options=self.wls)   # (kept: the step is asynchronous)
+            dense_filter.dense_wls(c, self.d16, self.gray[:self.F], options=self.wls, conf=self.conf, mask=self.mask, out=self.d16)
         self.X = c.dense_triangulate(self.rig, self.d16, self.min_disparity, self.max_disparity)
         return self.d16, self.X
 
