@@ -659,6 +659,23 @@ def dense_paths(paths, options=None):
     return paths
 
 
+DENSE_WIDE_MIN_DISPARITIES, DENSE_WIDE_MAX_DISPARITIES = 16, 256   # SOSVO_DENSE_WIDE_MIN / MAX_DISPARITIES
+
+
+def dense_disparities(disparities, paths=4, options=None):
+    """A `disparities` argument of the dense stage -> the number D of disparities searched from
+    options.min_disparity on, checked together with the `paths` and the options it goes with (dense_paths): a multiple of 16
+    in 16 .. 256, the reference tuner's num_of_disparities (disparities = tuner.num_of_disparities).  64 is the stage as it
+    was (sosvo_dense_stereo / sosvo_dense_stereo_paths); every other value runs sosvo_dense_stereo_wide.  Anything else raises
+    ValueError."""
+    dense_paths(paths, options)
+    if (isinstance(disparities, bool) or not isinstance(disparities, int) or disparities % 16 != 0
+            or not DENSE_WIDE_MIN_DISPARITIES <= disparities <= DENSE_WIDE_MAX_DISPARITIES):
+        raise ValueError("dense disparities must be a multiple of 16 in %d .. %d, got %r"
+                         % (DENSE_WIDE_MIN_DISPARITIES, DENSE_WIDE_MAX_DISPARITIES, disparities))
+    return disparities
+
+
 class DenseOptions(namedtuple("DenseOptions", "min_disparity P1 P2 uniqueness lr_max cyclic")):
     """The settings of the dense stereo stage (sosvo_dense_stereo) as one checked value: min_disparity
     0 .. 1024 rows (the first of the 64 disparities searched), the smoothness penalties 0 <= P1 <= P2 <= 8191 (the reference's

@@ -221,6 +221,17 @@ __device__ __forceinline__ int lane_from_right(int v) { return __builtin_amdgcn_
 __device__ __forceinline__ float lane_from_left(float v) { return __int_as_float(lane_from_left(__float_as_int(v))); }
 __device__ __forceinline__ float lane_from_right(float v) { return __int_as_float(lane_from_right(__float_as_int(v))); }
 
+// min over the 64 lanes of a non-negative value, in every lane: inside each row of 16 lanes by DPP (two quad
+// permutations, row_half_mirror, row_mirror), across the four rows by readlane
+__device__ __forceinline__ int wave_min(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1, 0, 3, 2]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));   // quad_perm [2, 3, 0, 1]
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));  // row_mirror
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
 // k * x + acc with 24-bit k, x as ONE v_mad_u32_u24, every operand in a VGPR (the compiler multiplies 32-bit values with
 // v_mul_lo_u32 and adds separately; __umul24 does not survive its constant folding either).  Integer arithmetic: the
 // order of the additions does not matter.
@@ -281,6 +292,16 @@ __device__ __forceinline__ int sosvo_block_count_matches(const uint32_t* __restr
 #define SOSVO_REQUIRE_DENSE_SIZE(ctx, rows, cols) SOSVO_REQUIRE_DENSE_SIZE_AS(SOSVO_REQUIRE, ctx, rows, cols)
 #define SOSVO_REQUIRE_DENSE_N(ctx, n) SOSVO_REQUIRE_DENSE_N_AS(SOSVO_REQUIRE, ctx, n)
 #define SOSVO_REQUIRE_DENSE_FLAGS(ctx, flags) SOSVO_REQUIRE_DENSE_FLAGS_AS(SOSVO_REQUIRE, ctx, flags)
+
+// dense.hip, for dense_wide.hip: what every dense stereo entry point refuses (SOSVO_ERR_ARG under the name `fn`), the census
+// launch, and the launches of sosvo_dense_stereo / sosvo_dense_stereo_paths on arguments already checked
+int32_t sosvo_dense_stereo_check(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows,
+                                 int32_t cols, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t flags,
+                                 int32_t paths, const int16_t* d16_out);
+int32_t sosvo_dense_launch_census(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, int cols, bool cyclic, uint64_t* out);
+int32_t sosvo_dense_stereo_run64(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                                 const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max,
+                                 int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out);
 
 // detect.hip: the rolling 7x7 blur on images that lie img_stride bytes apart (also used by orb.hip for the pyramid levels)
 int32_t sosvo_launch_gauss7(sosvo_ctx* ctx, const uint8_t* in, long long img_stride, int nimg, int rows, int cols,

@@ -23,17 +23,6 @@ constexpr int kD = 64;              // disparities = lanes
 constexpr int kBig = 1 << 20;       // above any L (<= 64 + 8191) plus P1
 constexpr uint32_t kRowBits = 14;   // rows <= 16384: a row index fits 14 bits of the left-right key
 
-// min over the 64 lanes of a non-negative value, in every lane: inside each row of 16 lanes by DPP (two quad
-// permutations, row_half_mirror, row_mirror), across the four rows by readlane
-__device__ __forceinline__ int wave_min(int v) {
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1, 0, 3, 2]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));   // quad_perm [2, 3, 0, 1]
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));  // row_half_mirror
-  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));  // row_mirror
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
 // L(p, k) = C(p, k) + min(L_prev(k), L_prev(k - 1) + P1, L_prev(k + 1) + P1, m + P2) - m, m = min_j L_prev(j)
 __device__ __forceinline__ int sgm_step(int cost, int Lp, int P1, int P2, int lane) {
   const int m = wave_min(Lp);
@@ -273,11 +262,10 @@ int32_t launch_census(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, i
   return SOSVO_OK;
 }
 
-// sosvo_dense_stereo (paths = 4) and sosvo_dense_stereo_paths: one body, `fn` the public name in the messages
-int32_t dense_stereo_body(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
-                          const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max,
-                          int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out) {
-  SOSVO_ENTER(ctx);
+// What sosvo_dense_stereo, sosvo_dense_stereo_paths and sosvo_dense_stereo_wide (dense_wide.hip) refuse alike, in this order
+int32_t dense_stereo_check(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                           int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t flags, int32_t paths,
+                           const int16_t* d16_out) {
   SOSVO_REQUIRE_FN(ctx, top && bot && d16_out, "null pointer");
   SOSVO_REQUIRE_DENSE_SIZE_AS(SOSVO_REQUIRE_FN, ctx, rows, cols);
   SOSVO_REQUIRE_DENSE_N_AS(SOSVO_REQUIRE_FN, ctx, n);
@@ -287,6 +275,27 @@ int32_t dense_stereo_body(const char* fn, sosvo_ctx* ctx, const uint8_t* top, co
   SOSVO_REQUIRE_DENSE_FLAGS_AS(SOSVO_REQUIRE_FN, ctx, flags);
   SOSVO_REQUIRE_FN(ctx, paths == 4 || paths == 8, "paths must be 4 or 8");
   SOSVO_REQUIRE_FN(ctx, paths == 4 || P2 <= SOSVO_DENSE_MAX_P2_EIGHT_PATHS, "eight paths need P2 <= 8127 (S stays 16 bits)");
+  return SOSVO_OK;
+}
+
+int32_t dense_stereo_run(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols, const uint8_t* mask,
+                         int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max, int32_t flags, int32_t paths,
+                         int16_t* d16_out, uint16_t* S_out);
+
+// sosvo_dense_stereo (paths = 4) and sosvo_dense_stereo_paths: one body, `fn` the public name in the messages
+int32_t dense_stereo_body(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                          const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max,
+                          int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out) {
+  SOSVO_ENTER(ctx);
+  const int32_t ok = dense_stereo_check(fn, ctx, top, bot, n, rows, cols, min_disparity, P1, P2, uniqueness, flags, paths, d16_out);
+  if (ok != SOSVO_OK) return ok;
+  return dense_stereo_run(ctx, top, bot, n, rows, cols, mask, min_disparity, P1, P2, uniqueness, lr_max, flags, paths, d16_out, S_out);
+}
+
+// The launches of sosvo_dense_stereo (paths = 4) and sosvo_dense_stereo_paths on checked arguments
+int32_t dense_stereo_run(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols, const uint8_t* mask,
+                         int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max, int32_t flags, int32_t paths,
+                         int16_t* d16_out, uint16_t* S_out) {
   const bool cyclic = (flags & SOSVO_DENSE_CYCLIC_COLUMNS) != 0, want_lr = lr_max >= 0;
   const size_t frame_pixels = (size_t)rows * cols, total = (size_t)n * frame_pixels;
   sosvo_dense_scratch b;  // (dense_scratch.h)
@@ -345,6 +354,23 @@ int32_t dense_stereo_body(const char* fn, sosvo_ctx* ctx, const uint8_t* top, co
 }
 
 }  // namespace
+
+// For dense_wide.hip (declared in common.h): the shared refusals, the census launch, and the 64-disparity launches on checked arguments
+int32_t sosvo_dense_stereo_check(const char* fn, sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows,
+                                 int32_t cols, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t flags,
+                                 int32_t paths, const int16_t* d16_out) {
+  return dense_stereo_check(fn, ctx, top, bot, n, rows, cols, min_disparity, P1, P2, uniqueness, flags, paths, d16_out);
+}
+
+int32_t sosvo_dense_launch_census(sosvo_ctx* ctx, const uint8_t* gray, int nimg, int rows, int cols, bool cyclic, uint64_t* out) {
+  return launch_census(ctx, gray, nimg, rows, cols, cyclic, out);
+}
+
+int32_t sosvo_dense_stereo_run64(sosvo_ctx* ctx, const uint8_t* top, const uint8_t* bot, int32_t n, int32_t rows, int32_t cols,
+                                 const uint8_t* mask, int32_t min_disparity, int32_t P1, int32_t P2, int32_t uniqueness, int32_t lr_max,
+                                 int32_t flags, int32_t paths, int16_t* d16_out, uint16_t* S_out) {
+  return dense_stereo_run(ctx, top, bot, n, rows, cols, mask, min_disparity, P1, P2, uniqueness, lr_max, flags, paths, d16_out, S_out);
+}
 
 extern "C" {
 

@@ -389,25 +389,25 @@ class GUMStereo(object):
         return (m_top, k_top[ok], d_top[ok]), (m_bot, k_bot[ok], d_bot[ok]), colors
 
     # ---- dense stereo: disparity map and point cloud ---------------------------------
-    def _dense_engine(self, median_win_size, options, speckle=None, paths=4, wls=None):
-        """One-frame pipeline.DenseOmniStereo per (median, options, speckle, paths, wls), on the rig's own geometry and without a
-        range filter (the reference's dense path has none)."""
-        from .._lib import DenseOptions, SpeckleOptions, WlsOptions, dense_paths
+    def _dense_engine(self, median_win_size, options, speckle=None, paths=4, wls=None, disparities=64):
+        """One-frame pipeline.DenseOmniStereo per (median, options, speckle, paths, wls, disparities), on the rig's own geometry
+        and without a range filter (the reference's dense path has none)."""
+        from .._lib import DenseOptions, SpeckleOptions, WlsOptions, dense_disparities, dense_paths
         from ..pipeline import DenseOmniStereo, RigConfig
         key = (int(median_win_size), DenseOptions.of(options), SpeckleOptions.of(speckle), dense_paths(paths, options),
-               WlsOptions.of(wls))
+               WlsOptions.of(wls), dense_disparities(disparities, paths, options))
         cache = self.__dict__.setdefault("_dense_engines", {})
         if key not in cache:
             geo = [(p.cols, p.rows, p.pixel_size, p.cyl_height_max) for p in (self.top_model.panorama, self.bot_model.panorama)]
             rig = RigConfig(geo[0], geo[1], self.top_model.F[:3, 0], self.bot_model.F[:3, 0], 0.0, 0.0)
             cache[key] = DenseOmniStereo(self._context(), self._device_model(), rig, 1, median_win_size=key[0], options=key[1],
-                                         min_disparity=0.0, speckle=key[2], paths=key[3], wls=key[4])
+                                         min_disparity=0.0, speckle=key[2], paths=key[3], wls=key[4], disparities=key[5])
         return cache[key]
 
     def get_depth_map_from_panoramas(self, method="sgbm", use_cropped_panoramas=False, rows_roi=(), cols_roi=(), show=False,
                                      load_stereo_tuner_from_pickle=False, stereo_tuner_filename=None, tune_live=False,
                                      use_heat_map=True, stereo_matcher_tuner=None, median_win_size=0, options=None,
-                                     speckle=None, paths=4, wls=None):
+                                     speckle=None, paths=4, wls=None, disparities=64):
         """camera_models.py:3395 without the tuner window: semi-global matching between the top and the bottom panorama of the
         current omni image on the device (sosvo_dense_stereo; `options`: a DenseOptions, None = its defaults, in place of the
         tuner's sliders).  Sets self.disparity_map (float64 [rows, cols] in rows, 0 = invalid as in the reference) and
@@ -420,6 +420,9 @@ class GUMStereo(object):
         top panorama's guidance (sosvo_dense_wls) after the speckle filter; the tuner's "Use WLS filter" /
         "WLS lambda" / "WLS sigma" enter through WlsOptions.from_tuner(use, lambda, sigma), and self.disparity_img is then scaled
         from -1 instead of the minimum disparity, as common_cv.py:696-700 does.
+        `disparities`: the number of disparities searched, a multiple of 16 in 16 .. 256 (sosvo_dense_stereo_wide, DESIGN.md
+        section 42): the tuner's num_of_disparities, disparities = tuner.num_of_disparities; self.disparity_img then scales by
+        it where it has 64.
         The GUI-only arguments (show, tune_live, use_heat_map, the tuner and its pickle) are ignored;
         cropping and regions of interest are not built."""
         if str(method).lower() != "sgbm":
@@ -428,14 +431,14 @@ class GUMStereo(object):
             raise NotImplementedError("cropped panoramas and regions of interest are not built: the whole panorama is matched")
         if self.current_omni_img is None:
             raise ValueError("set_current_omni_image first")
-        eng = self._dense_engine(median_win_size, options, speckle, paths, wls)
+        eng = self._dense_engine(median_win_size, options, speckle, paths, wls, disparities)
         eng.load_frames(np.ascontiguousarray(self.current_omni_img)[None])
         d16, X = eng.step()
         eng.ctx.synchronize()
         self.disparity_d16, self._dense_X = d16.cpu().numpy()[0], X.cpu().numpy()[0]
         valid, d0 = self.disparity_d16 >= 0, eng.options.min_disparity if eng.wls is None else -1   # (min_disp_for_vis)
         self.disparity_map = np.where(valid, self.disparity_d16 / 16.0, 0.0)
-        img = np.clip((self.disparity_map - d0) * 255.0 / (64 - d0), 0, 255)
+        img = np.clip((self.disparity_map - d0) * 255.0 / (eng.disparities - d0), 0, 255)
         self.disparity_img = np.where(valid, img, 0).astype(np.uint8)
         return self.disparity_map, self.disparity_img
 

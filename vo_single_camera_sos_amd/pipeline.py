@@ -1633,13 +1633,19 @@ class DenseOmniStereo(object):
     wls: what WlsOptions.of takes, the tuner's "Use WLS filter" / "WLS lambda" / "WLS sigma" through
     WlsOptions.from_tuner.  None: no filter, and nothing differs from an engine without the argument.  With a value step() runs
     dense_filter.dense_confidence and dense_filter.dense_wls on d16, guided by the top gray panoramas under the engine's mask,
-    in place, after the stereo and the speckle filter and before the triangulation."""
+    in place, after the stereo and the speckle filter and before the triangulation.
+    disparities: the number of disparities searched from options.min_disparity on, a multiple of 16 in 16 .. 256 (DESIGN.md
+    section 42), the reference tuner's num_of_disparities: disparities = tuner.num_of_disparities.  With 64 nothing differs from
+    an engine without the argument; every other value runs dense_wide.dense_stereo in place of Context.dense_stereo, and the
+    speckle filter, the WLS filter and the triangulation follow unchanged."""
 
     def __init__(self, ctx, model, rig, n_frames, median_win_size=0, options=None, min_disparity=1.0, max_disparity=0.0,
-                 speckle=None, paths=4, wls=None):
-        from ._lib import DenseOptions, SpeckleOptions, WlsOptions, dense_paths
+                 speckle=None, paths=4, wls=None, disparities=64):
+        from ._lib import DENSE_DISPARITIES, DenseOptions, SpeckleOptions, WlsOptions, dense_disparities, dense_paths
         self.options, self.speckle, self.wls = DenseOptions.of(options), SpeckleOptions.of(speckle), WlsOptions.of(wls)
         self.paths = dense_paths(paths, self.options)
+        self.disparities = dense_disparities(disparities, self.paths, self.options)
+        self._wide = self.disparities != DENSE_DISPARITIES
         self.ctx, self.model, self.rig_cfg, self.rig = ctx, model, rig, rig.as_struct()
         if tuple(rig.pano_top) != tuple(rig.pano_bot):
             raise ValueError("dense stereo needs two panoramas of one geometry, got %r and %r" % (rig.pano_top, rig.pano_bot))
@@ -1659,7 +1665,12 @@ class DenseOmniStereo(object):
         """-> (d16 [F,rows,cols] i16, X [F,rows,cols,3] f64) on the device (asynchronous)."""
         c, m = self.ctx, self.model
         c.unwrap_median_gray(self.omni, m.unwrap_table, self.median_win_size, gray=self.gray)
-        self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options, paths=self.paths)
+        if self._wide:
+            from . import dense_wide
+            self.d16 = dense_wide.dense_stereo(c, self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options,
+                                               disparities=self.disparities, paths=self.paths)
+        else:
+            self.d16 = c.dense_stereo(self.gray[:self.F], self.gray[self.F:], self.mask, options=self.options, paths=self.paths)
         if self.speckle is not None:
             c.dense_speckle(self.d16, options=self.speckle, out=self.d16)
         if self.wls is not None:
